@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- factorize+solve time of the nested-dissection elimination on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
 
 A *step* is one numeric factorization (``factor(A, nd, nd_loc; swlevel=0)``) plus one ``ldiv!`` with a
 single right-hand side, with the sparsity pattern analysed and every input (values of A, b) already
@@ -9,7 +9,14 @@ resident in HBM when the timed region starts.  Metric (BASELINE.json): factorize
 (lower is better) on a synthetic 3D problem; N > 1 is STRONG scaling of the same problem (subtrees of the
 elimination tree per rank, Schur complements sent point-to-point at the joins, RCCL over xGMI).
 
-One JSON line on rank 0.  ``roofline`` describes the dominant kernel (the FP64 MFMA GEMM): achieved =
+A plain run sets up, warms up, times the K steps and prints one JSON line (``value`` = seconds per step,
+``ms_per_step``); the inputs are seeded, so the same arguments give the same inputs in every run.
+``--dump-outputs DIR`` writes the solution of the last timed step as ``DIR/x.npy`` (float64; complex
+workloads: ``x_real.npy`` and ``x_imag.npy``), in the solver's post-ordered numbering, at most 64 MB in all: a
+larger solution is written as a fixed seeded sample of its entries with their positions in ``x_index.npy``.
+
+``--full`` adds the checks and side measurements below to the JSON line (most of them run the solver again).
+``residual`` = ||A x - b|| / ||b|| of the last solve.  ``roofline`` describes the dominant kernel (the FP64 MFMA GEMM): achieved =
 its executed flops / its HIP-event time over one extra profiled step; ``traffic`` = measured HBM bytes per launch from a
 committed PMC pass of THIS round whose launch count equals the run's (else null, with the reason).  ``cpu_baseline``
 times the NumPy oracle (a port of the reference's algorithm, redundant LUs included) and SuperLU on a bounded sample,
@@ -275,6 +282,26 @@ def metric_workload(hs, hsdist, dev, name, swlevel, tol, steps):
     return out
 
 
+DUMP_BYTES_MAX = 64 * 10**6
+
+
+def dump_outputs(out_dir, x):
+    """The solution of the last timed step as float64 .npy files (complex: real and imaginary parts), DUMP_BYTES_MAX at most in all;
+    a longer solution as its entries at a fixed seeded sample of positions, the positions beside them in x_index.npy."""
+    import numpy as np
+
+    parts = {"x_real": x.real, "x_imag": x.imag} if np.iscomplexobj(x) else {"x": x}
+    n = x.shape[0]
+    if len(parts) * n * 8 > DUMP_BYTES_MAX:
+        k = (DUMP_BYTES_MAX - 4096) // ((len(parts) + 1) * 8)  # (4 KiB for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        parts = {name: v[idx] for name, v in parts.items()}
+        parts["x_index"] = idx
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in parts.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -301,6 +328,9 @@ def main():
     ap.add_argument("--dist-min-gbps", type=float, default=25.0, help="--dist-top -1: minimum measured point-to-point rate (ring shift of 128 MiB through the library's communicator, slowest rank); below ~25 GB/s the block-column "
                     "messages of a 32,768 front (4.3 GB of L parts on the critical path of 2 ranks) cost more than the second rank's share of the trailing updates gains (DESIGN.md section 6)")
     ap.add_argument("--leafsize", type=int, default=32, help="SolverOptions.leafsize (HSS leaves; the device uses at least 128)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the solution of the last timed step to DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true", help="also the side measurements (residual, ldiv! alone and per level, roofline step, one-shot factor, "
+                    "metric workload, CPU baseline, per-rank times); the --no-* and --metric-* options select among them")
     args = ap.parse_args()
 
     import numpy as np
@@ -404,10 +434,12 @@ def main():
         dt = float(tt.item())
     per_step = dt / max(args.steps, 1)
     st = S.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, b_dev.cpu().numpy())
     # N > 1, host-driven joins: one more, INSTRUMENTED factorization (the host waits for the device after every stage; not part of `value`):
     # what each rank spent computing, and sending / receiving -- which includes waiting for the peer -- so a first run on real links is diagnosable
     rank_times = None
-    if world > 1 and not fopts.get("dist_top"):
+    if args.full and world > 1 and not fopts.get("dist_top"):
         tr = []
         S.numeric(trace=tr)
         mine = {"rank": rank, "compute_s": sum(t for w, t in tr if w.startswith("level")), "transfer_and_wait_s": sum(t for w, t in tr if w.startswith(("send", "recv"))),
@@ -416,7 +448,7 @@ def main():
         torch.distributed.all_gather_object(rank_times, mine)
     # ldiv! alone (part of every timed step; timed separately here for the HBM roofline of the solve kernels)
     t_ldiv = 0.0
-    if world == 1:
+    if args.full and world == 1:
         sync()
         t0 = time.perf_counter()
         for _ in range(3):
@@ -427,7 +459,7 @@ def main():
     # ... and once more level by level (hs_solve_*_levels with events between the levels): GB/s of the sweeps of every tree level against the
     # bytes they must read, (ni^2 + 2 ni nb) * sizeof(T) per front
     solve_levels = None
-    if world == 1 and not fopts.get("dist_top"):
+    if args.full and world == 1 and not fopts.get("dist_top"):
         try:
             nl = S.plan.nlevels
             st0 = S.stats()
@@ -455,13 +487,15 @@ def main():
         except Exception as e:  # diagnostics only: never fail the bench line for it
             solve_levels = "unavailable: %r" % (e,)
 
-    # correctness of what was timed: residual of the last solve (never skipped)
-    x = b_dev.cpu().numpy()
-    res = float(np.linalg.norm(Ap @ x - bp) / np.linalg.norm(bp))
+    # correctness of what was timed: residual of the last solve (every --full run)
+    res = None
+    if args.full:
+        x = b_dev.cpu().numpy()
+        res = float(np.linalg.norm(Ap @ x - bp) / np.linalg.norm(bp))
 
     # ---- roofline of the dominant kernel: one more step with per-launch HIP events --------------------------
     roofline = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         S.backend.L.hs_free(S.backend._h)
         S.backend._h = None
         del S
@@ -519,7 +553,7 @@ def main():
         S.backend._h = None
         del S
         torch.cuda.empty_cache()
-        if not args.no_oneshot:
+        if args.full and not args.no_oneshot:
             # what the Julia shim binds: factor(A, nd, nd_loc) from HOST arrays = analysis + arena allocation + upload + numeric, then ldiv!
             # from a host vector (PCIe-inclusive; never `value`)
             t0 = time.perf_counter()
@@ -531,7 +565,7 @@ def main():
             oneshot = {"factor_oneshot_s": t_f1, "ldiv_host_s": t_l1, "residual": float(np.linalg.norm(Ap @ x1 - bp) / np.linalg.norm(bp))}
             F1.free()
             del F1
-        if args.metric_workload and args.swlevel == 0 and args.workload != args.metric_workload:
+        if args.full and args.metric_workload and args.swlevel == 0 and args.workload != args.metric_workload:
             try:
                 extra_metric = metric_workload(hs, hsdist, dev, args.metric_workload, args.metric_swlevel, args.metric_tol, args.metric_steps)
             except Exception as e:  # never lose the headline line to the extra
@@ -560,12 +594,13 @@ def main():
                                                                         ("packed HSS generators (hs_schur_pack / hs_schur_unpack)" if (flow_main or {}).get("mf") else "dense Schur complements")) if world > 1 else ""))},
             "flow": flow_main,
             "factor_s": st["t_total"],
-            "residual": res,
             "maxrank": maxrank_main,
             "bytes_factors_GiB": st["bytes_factors"] / 2**30,
             "host_symbolic_s": t_host,
             "analyze_s": t_analyze,
         }
+        if res is not None:
+            out["residual"] = res
         if dist_note:
             out["dist_top_note"] = dist_note
         if world > 1 and args.dist_top != 0 and args.swlevel == 0:
@@ -588,7 +623,7 @@ def main():
             out["oneshot"] = oneshot
         if extra_metric:
             out["metric_workload"] = extra_metric
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, dev)
         print(json.dumps(out))
     if world > 1:
