@@ -1582,6 +1582,116 @@ static void ldiv_dev(hs_handle* h, T* dC, int64_t ldc, const T* dB, int64_t ldb,
 }
 
 // ------------------------------------------------------------------------------------------------
+// ldiv!(transpose(F), B), ldiv!(adjoint(F), B): the same factors read along their columns (kernels_solve_t.hip); CONJ = adjoint.
+// The triangular sweeps of a level are one dataflow launch; HS_SOLVE_FLOW=0 selects the launch-per-step sweeps, as for ldiv!
+// ------------------------------------------------------------------------------------------------
+template <class T, bool CONJ>
+static void solve_fwd_t(hs_handle* h, T* db, hipStream_t s) {  // leaves -> root:  z = U11^-T rhs[int];  rhs[bnd] -= Uib^T z
+  flow_arm(h, s);
+  const bool flow = solve_flow_on() && h->d_e1;
+  const SolveNode<T>* sn = (const SolveNode<T>*)h->d_solve;
+  T* w1 = (T*)h->d_w1;
+  T* w2 = (T*)h->d_w2;
+  for (int lv = (int)h->levels.size() - 1; lv >= 0; --lv) {
+    const LevelH& L = h->levels[lv];
+    if (L.mine.empty() || L.maxni == 0) continue;
+    const SolveNode<T>* dn = sn + L.desc_off;
+    const int nb_ = (int)L.mine.size();
+    launch_t_gather<T>(dn, nb_, L.maxni, db, w1, s);
+    if (flow) {  // the whole level in one launch
+      launch_t_fwd_flow<T, CONJ>(dn, nb_, L.maxni, L.maxnb, w1, w2, db, (T*)h->d_e1, (T*)h->d_e2, flow_counter(h, s), h->h_flow_err, s);
+    } else {
+      const int nblk = (L.maxni + hs_solve_t_cols() - 1) / hs_solve_t_cols();
+      for (int blk = 0; blk < nblk; ++blk) launch_t_fwd_step<T, CONJ>(dn, nb_, blk, L.maxm, w1, w2, db, s);
+    }
+    solve_lr_fwd_t<T, CONJ>(h, lv, db, s);
+  }
+}
+template <class T, bool CONJ>
+static void solve_bwd_t(hs_handle* h, T* db, hipStream_t s) {  // root -> leaves:  v = z - Lbi^T rhs[bnd];  rhs[int[rperm]] = L11^-T v
+  flow_arm(h, s);
+  const bool flow = solve_flow_on() && h->d_e1;
+  const SolveNode<T>* sn = (const SolveNode<T>*)h->d_solve;
+  T* w1 = (T*)h->d_w1;
+  T* w2 = (T*)h->d_w2;
+  for (int lv = 0; lv < (int)h->levels.size(); ++lv) {
+    const LevelH& L = h->levels[lv];
+    if (L.mine.empty() || L.maxni == 0) continue;
+    const SolveNode<T>* dn = sn + L.desc_off;
+    const int nb_ = (int)L.mine.size();
+    launch_t_int_update<T, CONJ>(dn, nb_, L.maxni, db, w2, w1, s);
+    solve_lr_bwd_t<T, CONJ>(h, lv, db, s);
+    if (flow) {
+      launch_t_bwd_flow<T, CONJ>(dn, nb_, L.maxni, w1, w2, (T*)h->d_e1, (T*)h->d_e2, flow_counter(h, s), h->h_flow_err, s);
+    } else {
+      const int nblk = (L.maxni + hs_solve_t_cols() - 1) / hs_solve_t_cols();
+      for (int blk = nblk - 1; blk >= 0; --blk) launch_t_bwd_step<T, CONJ>(dn, nb_, blk, w1, w2, s);
+    }
+    launch_t_scatter<T>(dn, nb_, L.maxni, db, w2, s);
+  }
+}
+template <class T>
+static void solve_t(hs_handle* h, int trans, T* db, hipStream_t s) {
+  if (trans == 2 && sizeof(T) == 16) {
+    solve_fwd_t<T, true>(h, db, s);
+    solve_bwd_t<T, true>(h, db, s);
+  } else {
+    solve_fwd_t<T, false>(h, db, s);
+    solve_bwd_t<T, false>(h, db, s);
+  }
+}
+// refuse, never drop: what the transposed sweeps do not cover is named before any device work
+static void check_solve_t(hs_handle* h, int trans, const char* fn) {
+  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
+  if (trans == 0) return;
+  if (h->nranks > 1)
+    HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: transposed solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", fn, h->nranks);
+  for (size_t i = 0; i < h->nodes.size(); ++i) {
+    const NodeH& x = h->nodes[i];
+    if (!x.mine) continue;
+    if (x.hssd || (x.mf && !x.mfd))
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): transposed ULV solves are not implemented",
+              fn, (int)i);
+  }
+}
+template <class T>
+static void ldiv_host_t(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  check_handle(h);
+  check_solve_t(h, trans, "hs_ldiv_t_*");
+  if (trans == 0) return ldiv_host<T>(h, C, ldc, B, ldb, n, nrhs);
+  check_solve_args(h, sizeof(T) == 16, ldc, ldb, n, nrhs);
+  hipStream_t s = h->stream;
+  double tsum = 0.0;
+  for (int64_t r = 0; r < nrhs; ++r) {
+    T* db = (T*)h->d_b;
+    HS_HIP(hipMemcpyAsync(db, B + r * ldb, n * sizeof(T), hipMemcpyHostToDevice, s));
+    HS_HIP(hipEventRecord(h->ev0, s));
+    solve_t<T>(h, trans, db, s);
+    HS_HIP(hipEventRecord(h->ev1, s));
+    HS_HIP(hipMemcpyAsync(C + r * ldc, db, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
+    flow_check(h);
+    float ms = 0.f;
+    HS_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    tsum += ms * 1e-3;
+  }
+  h->stats.t_solve = tsum;
+}
+template <class T>
+static void ldiv_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  check_handle(h);
+  check_solve_t(h, trans, "hs_ldiv_dev_t_*");
+  if (trans == 0) return ldiv_dev<T>(h, dC, ldc, dB, ldb, n, nrhs, stream);
+  check_solve_args(h, sizeof(T) == 16, ldc, ldb, n, nrhs);
+  hipStream_t s = (hipStream_t)stream;
+  for (int64_t r = 0; r < nrhs; ++r) {
+    T* c = dC + r * ldc;
+    if (c != dB + r * ldb) HS_HIP(hipMemcpyAsync(c, dB + r * ldb, n * sizeof(T), hipMemcpyDeviceToDevice, s));
+    solve_t<T>(h, trans, c, s);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
 extern "C" int hs_analyze(int is_complex, int64_t n, const int64_t* colptr, const int64_t* rowval, const hs_tree* tree, const hs_options* opts,
@@ -1688,6 +1798,19 @@ extern "C" int hs_ldiv_dev_d(hs_handle* F, double* dC, int64_t ldc, const double
 }
 extern "C" int hs_ldiv_dev_z(hs_handle* F, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   HS_GUARD(ldiv_dev<cplx>(F, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
+}
+
+extern "C" int hs_ldiv_t_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  HS_GUARD(ldiv_host_t<double>(F, trans, C, ldc, B, ldb, n, nrhs));
+}
+extern "C" int hs_ldiv_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  HS_GUARD(ldiv_host_t<cplx>(F, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
+}
+extern "C" int hs_ldiv_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  HS_GUARD(ldiv_dev_t<double>(F, trans, dC, ldc, dB, ldb, n, nrhs, stream));
+}
+extern "C" int hs_ldiv_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  HS_GUARD(ldiv_dev_t<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
 }
 
 extern "C" int hs_solve_fwd_levels(hs_handle* h, void* d_b, int64_t lv_from, int64_t lv_to, void* stream) {

@@ -266,6 +266,33 @@ template <class T>
 void launch_lr_zmul(const T* Z, int ldz, int r, int cols, const T* x, const int* xidx, T* part, T* t, hipStream_t s);
 template <class T>
 void launch_lr_trap(const T* Lp, int ldp, int rows, int r, const int* rp, const T* t, T* dst, const int* didx, hipStream_t s);
+// ldiv!(transpose(F), B) / ldiv!(adjoint(F), B) (kernels_solve_t.hip; CONJ: adjoint).  The same descriptors and work vectors as the sweeps above:
+//   forward:  w = rhs[int] (launch_t_gather);  per 256-column block: z_blk = inv256U^T w_blk, then w[j] / rhs[bnd_j] -= (U11 | Uib)[blk, j]^T z_blk
+//   backward: v = z - Lbi^T rhs[bnd] (launch_t_int_update);  per block, last first: x_blk = inv256L^T v_blk, v[j] -= L11[blk, j]^T x_blk;
+//             rhs[int[rperm[i]]] = x[i] (launch_t_scatter)
+template <class T>
+void launch_t_gather(const SolveNode<T>* dn, int nbatch, int maxni, const T* b, T* w, hipStream_t s);
+template <class T>
+void launch_t_scatter(const SolveNode<T>* dn, int nbatch, int maxni, T* b, const T* x, hipStream_t s);
+template <class T, bool CONJ>
+void launch_t_fwd_step(const SolveNode<T>* dn, int nbatch, int blk, int maxm, T* w, T* z, T* b, hipStream_t s);
+template <class T, bool CONJ>
+void launch_t_bwd_step(const SolveNode<T>* dn, int nbatch, int blk, T* v, T* x, hipStream_t s);
+// the same sweeps of a whole level in ONE dataflow launch (E1, E2 armed with the sentinel; the counter and *err as for launch_fwd_flow)
+template <class T, bool CONJ>
+void launch_t_fwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, int maxnb, const T* w, T* z, T* b, T* E1, T* E2, int* counter, int* err, hipStream_t s);
+template <class T, bool CONJ>
+void launch_t_bwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, const T* v, T* x, T* E1, T* E2, int* counter, int* err, hipStream_t s);
+template <class T, bool CONJ>
+void launch_t_int_update(const SolveNode<T>* dn, int nbatch, int maxni, const T* b, const T* z, T* v, hipStream_t s);
+int hs_solve_t_cols();
+// low-rank transforms transposed: t = C^T x (C dense, x gathered through xidx; `part` >= hs_lr_ct_part_elems(rows, r)),
+// and dst[didx ? didx[j] : j] -= (Z^T t)[j]
+template <class T, bool CONJ>
+void launch_t_lr_ct(const T* Cd, int ldc, int rows, int r, const T* x, const int* xidx, T* part, T* t, hipStream_t s);
+int hs_lr_ct_part_elems(int rows, int r);
+template <class T, bool CONJ>
+void launch_t_lr_zt(const T* Z, int ldz, int r, int cols, const T* t, T* dst, const int* didx, hipStream_t s);
 void launch_pack_idx(const int* idx, int cnt, const void* b, void* buf, int esz, hipStream_t s);    // buf[i] = b[idx[i]]
 void launch_unpack_idx(const int* idx, int cnt, void* b, const void* buf, int esz, hipStream_t s);  // b[idx[i]] = buf[i]
 void launch_copy_idx(const int* idx, int cnt, const void* b, void* out, int esz, hipStream_t s);      // out[idx[i]] = b[idx[i]]

@@ -354,6 +354,52 @@ static void solve_lr_bwd(hs_handle* h, int lv, T* db, hipStream_t s) {
   }
 }
 
+// the partial sums of launch_t_lr_ct: hs_lr_ct_part_elems(rows, r) entries in d_lr_part (grown like ensure_lr_workspace, never shrunk)
+template <class T>
+static void ensure_lr_ct_workspace(hs_handle* h, int r, int rows) {
+  ensure_lr_workspace<T>(h, r, 0);  // d_lr_t: r entries
+  const size_t need = (size_t)hs_lr_ct_part_elems(rows, r) + 1;
+  if (need > h->lr_part_elems) {
+    if (h->d_lr_part) (void)hipFree(h->d_lr_part);
+    h->d_lr_part = nullptr;
+    dmalloc(&h->d_lr_part, need * sizeof(T), "low-rank workspace");
+    h->lr_part_elems = need;
+  }
+}
+// ldiv!(transpose / adjoint(F), B) (kernels_solve_t.hip).  R ~= C_R*Z_R (stored G = L^-1*P*C_R, ni x r), L ~= C_L*Z_L (Z_L*U^-1 stored):
+// forward, after z = U11^-T rhs[int] of level lv (in w2):  rhs[bnd] -= Z_R^T * (C_R^T * z)
+template <class T, bool CONJ>
+static void solve_lr_fwd_t(hs_handle* h, int lv, T* db, hipStream_t s) {
+  const LevelH& L = h->levels[lv];
+  T* w2 = (T*)h->d_w2;
+  for (int id : L.mine) {
+    const NodeH& x = h->nodes[id];
+    if (!(x.compressed || x.mfd) || !x.lrR || x.hssd || (x.mf && !x.mfd)) continue;
+    const LowRank<T>& lr = *(const LowRank<T>*)x.lrR;
+    if (lr.r == 0) continue;
+    if (!lr.Cd) HS_FAIL(HS_ERR_UNSUPPORTED, id, "transposed ldiv!: node %d holds a low-rank transform without its dense C", id);
+    ensure_lr_ct_workspace<T>(h, lr.r, lr.rows);
+    launch_t_lr_ct<T, CONJ>(lr.Cd, lr.ldc, lr.rows, lr.r, w2 + x.woff, nullptr, (T*)h->d_lr_part, (T*)h->d_lr_t, s);
+    launch_t_lr_zt<T, CONJ>(lr.Z, lr.ldz, lr.r, lr.cols, (const T*)h->d_lr_t, db, h->d_int + x.off_fidx + x.ni, s);
+  }
+}
+// backward, after v = z for the compressed fronts of level lv (in w1):  v -= Z_L^T * (C_L^T * rhs[bnd])
+template <class T, bool CONJ>
+static void solve_lr_bwd_t(hs_handle* h, int lv, T* db, hipStream_t s) {
+  const LevelH& L = h->levels[lv];
+  T* w1 = (T*)h->d_w1;
+  for (int id : L.mine) {
+    const NodeH& x = h->nodes[id];
+    if (!(x.compressed || x.mfd) || !x.lrL || x.hssd || (x.mf && !x.mfd)) continue;
+    const LowRank<T>& lr = *(const LowRank<T>*)x.lrL;
+    if (lr.r == 0) continue;
+    if (!lr.Cd) HS_FAIL(HS_ERR_UNSUPPORTED, id, "transposed ldiv!: node %d holds a low-rank transform without its dense C", id);
+    ensure_lr_ct_workspace<T>(h, lr.r, lr.rows);
+    launch_t_lr_ct<T, CONJ>(lr.Cd, lr.ldc, lr.rows, lr.r, db, h->d_int + x.off_fidx + x.ni, (T*)h->d_lr_part, (T*)h->d_lr_t, s);
+    launch_t_lr_zt<T, CONJ>(lr.Z, lr.ldz, lr.r, lr.cols, (const T*)h->d_lr_t, w1 + x.woff, nullptr, s);
+  }
+}
+
 // dense reconstruction of a compressed Gauss transform on the host (parity tests): out = C * Z (rows x cols)
 template <class T>
 static void lowrank_to_dense(const LowRank<T>& lr, T* out) {

@@ -11,6 +11,7 @@
 // redundantly, the block comes from L2) followed by the 256-column panel update of the workgroup's own 256 rows:
 // up to 64 MB per launch and 8x fewer launches.
 #include "hs_common.h"
+#include "hs_flow.h"  // HS_FLOW_SPIN, HS_SENT, flow_ldbits, flow_publish (shared with kernels_solve_t.hip)
 
 #define HS_SW 256  // columns per launch
 
@@ -357,8 +358,6 @@ __global__ __launch_bounds__(1024) void wide_first_kernel(const SolveNode<T>* __
 //    workgroup that runs out raises *err and leaves without publishing, its dependents run out in turn, the grid drains, and the host
 //    reports it at the next call instead of the GPU hanging.
 // ------------------------------------------------------------------------------------------------
-#define HS_FLOW_SPIN (1 << 22)
-static constexpr unsigned long long HS_SENT = ~0ull;
 // Thread layout of a tile (512 threads = 8 waves): the LANES run along the rows and a WAVE owns 32 consecutive columns, so the column of a
 // load is wave-uniform -- its address is a scalar base plus one per-lane byte offset, and 32 (16) loads in flight cost their data registers
 // only.  Float64: 64 rows, one 8-byte load per lane and column.  ComplexF64: 32 rows, the two half-waves take the two columns of a pair.
@@ -375,16 +374,6 @@ struct FlowCfg {
   static constexpr int NP = (NT / 64) * SC;             // partial sums per row
   static constexpr int Q = HS_SW / FB;                  // sub-blocks per 256-block
 };
-__device__ __forceinline__ unsigned long long flow_ldbits(const double* p) {
-  return __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void flow_publish(double* p, double v) {
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void flow_publish(cplx* p, cplx v) {
-  flow_publish(reinterpret_cast<double*>(p), v.re);
-  flow_publish(reinterpret_cast<double*>(p) + 1, v.im);
-}
 // thread t < 256 fetches element t of a published vector (cnt <= 256 entries) into dst[t], zero beyond cnt; false when the wait ran out
 __device__ __forceinline__ bool flow_poll(const double* src, int cnt, double* dst, int t) {
   if (t >= HS_SW) return true;

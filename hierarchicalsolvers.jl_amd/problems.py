@@ -35,7 +35,10 @@ def grid_matrix(shape, kind="poisson", ppw=10.0, dtype=None):
 
     ``poisson``: 2d on the diagonal, -1 to each neighbour (h^2-scaled Laplacian).
     ``helmholtz``: Laplacian - (kh)^2 I - i (kh) * (#exposed faces) on boundary nodes,
-    ``kh = 2 pi / ppw`` (``ppw`` points per wavelength)."""
+    ``kh = 2 pi / ppw`` (``ppw`` points per wavelength).
+    ``convdiff``: the Laplacian plus central-difference convection with the fixed cell Peclet numbers ``CONVDIFF_PECLET`` per axis
+    (well below 2): nonsymmetric, same 5/7-point pattern.  ``convdiff_helmholtz``: the same plus the Helmholtz shift above, complex and
+    neither symmetric nor Hermitian."""
     shape = tuple(int(s) for s in shape)
     d = len(shape)
     eyes = [sp.identity(s, format="csr") for s in shape]
@@ -47,9 +50,11 @@ def grid_matrix(shape, kind="poisson", ppw=10.0, dtype=None):
             f = _lap1d(shape[a]) if a == ax else eyes[a]
             term = f if term is None else sp.kron(term, f, format="csr")
         A = term if A is None else A + term
-    if kind == "poisson":
+    if kind in ("convdiff", "convdiff_helmholtz"):
+        A = A + _convection(shape)
+    if kind in ("poisson", "convdiff"):
         A = A.astype(dtype or np.float64)
-    elif kind == "helmholtz":
+    elif kind in ("helmholtz", "convdiff_helmholtz"):
         kh = 2.0 * np.pi / ppw
         faces = np.zeros(shape[::-1], dtype=np.float64)  # C-order array indexed [z][y][x]
         for ax in range(d):
@@ -66,6 +71,25 @@ def grid_matrix(shape, kind="poisson", ppw=10.0, dtype=None):
     A = sp.csc_matrix(A)
     A.sort_indices()
     return A
+
+
+CONVDIFF_PECLET = (0.6, 0.3, 0.15)  # h * velocity per axis for the velocity (1, 0.5, 0.25), h = 0.6
+
+
+def _convection(shape):
+    """h^2-scaled central-difference ``h * (v . grad)``: ``+-pe/2`` on the two neighbours along each axis."""
+    shape = tuple(int(s) for s in shape)
+    d = len(shape)
+    C = None
+    for ax in range(d):
+        n = shape[ax]
+        c1 = sp.diags([-0.5 * np.ones(n - 1), 0.5 * np.ones(n - 1)], [-1, 1], format="csr") * CONVDIFF_PECLET[ax]
+        term = None
+        for a in reversed(range(d)):
+            f = c1 if a == ax else sp.identity(shape[a], format="csr")
+            term = f if term is None else sp.kron(term, f, format="csr")
+        C = term if C is None else C + term
+    return C
 
 
 def _box_ids(lo, hi, shape):

@@ -7,6 +7,7 @@ reference (Julia)                      here
 ``factor(A, nd, nd_loc, opts; kw...)`` :func:`factor`          (factorization.jl:5-11)
 ``FactorNode{T}``                      :class:`FactorNode`     (factornode.jl:7-39)
 ``ldiv!(F, B)``, ``ldiv!(C, F, B)``    :func:`ldiv`            (factornode.jl:62-74)
+``transpose(F)``, ``adjoint(F)``       :func:`transpose`, :func:`adjoint` (``ldiv`` takes them: ``A^T x = b``, ``A^H x = b``)
 ``maxrank(F)``                         :func:`maxrank`         (factornode.jl:49-57)
 ``F \\ b``                              ``F.solve(b)``
 =====================================  ====================================================
@@ -23,7 +24,7 @@ import scipy.sparse as sp
 from . import _lib
 from .nesteddissection import flatten_tree
 
-__all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank"]
+__all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint"]
 
 
 class SolverOptions:
@@ -157,9 +158,11 @@ class FactorNode:
         _lib.check(_lib.lib().hs_get_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
 
-    def solve(self, b):
-        """``F \\ b``."""
-        return ldiv(self, b)
+    def solve(self, b, trans="N"):
+        """``F \\ b``; ``trans="T"``: ``transpose(F) \\ b``, ``"C"``: ``adjoint(F) \\ b``."""
+        if trans not in ("N", "T", "C"):
+            raise ValueError(f"trans must be 'N', 'T' or 'C', not {trans!r}")
+        return ldiv({"N": self, "T": transpose(self), "C": adjoint(self)}[trans], b)
 
     # -- inspection (tests) -------------------------------------------------------------------
     @property
@@ -278,10 +281,63 @@ def trim():
     return int(_lib.lib().hs_trim())
 
 
+class TransposedFactor:
+    """``Transpose(F)`` / ``Adjoint(F)`` of a :class:`FactorNode` (Julia's lazy wrappers): holds the factorization, reads the same
+    factors.  Made by :func:`transpose` / :func:`adjoint`, consumed by :func:`ldiv` (``hs_ldiv_t_*``, include/hs_solver.h)."""
+
+    def __init__(self, parent, conj):
+        self.parent = parent
+        self.conj = bool(conj)
+
+    @property
+    def trans(self):
+        return 2 if self.conj else 1  # the `trans` argument of hs_ldiv_t_*
+
+    @property
+    def n(self):
+        return self.parent.n
+
+    @property
+    def dtype(self):
+        return self.parent.dtype
+
+    @property
+    def shape(self):
+        return self.parent.shape
+
+    def __repr__(self):
+        return f"{'Adjoint' if self.conj else 'Transpose'}{{{repr(self.parent)}}}"
+
+    def solve(self, b):
+        """``transpose(F) \\ b`` / ``adjoint(F) \\ b``."""
+        return ldiv(self, b)
+
+
+def _wrap(F, conj):
+    if isinstance(F, TransposedFactor):
+        if F.conj == conj or F.dtype.kind != "c":  # transpose(transpose(F)) = adjoint(adjoint(F)) = F; Float64: adjoint = transpose
+            return F.parent
+        raise TypeError("conj(F) of a ComplexF64 factorization (transpose of an adjoint) is not supported")
+    if not isinstance(F, FactorNode):
+        raise TypeError(f"expected a FactorNode, got {type(F).__name__}")
+    return TransposedFactor(F, conj)
+
+
+def transpose(F):
+    """``transpose(F)``: ``ldiv(transpose(F), B)`` solves ``A^T X = B`` with the factors of ``A``."""
+    return _wrap(F, False)
+
+
+def adjoint(F):
+    """``adjoint(F)`` (``F'``): ``ldiv(adjoint(F), B)`` solves ``A^H X = B`` with the factors of ``A``."""
+    return _wrap(F, True)
+
+
 def ldiv(*args):
     """``ldiv!(F, B)`` / ``ldiv!(C, F, B)`` (factornode.jl:62-74): ``C = F^-1 B`` for a vector or an
     ``n x nrhs`` matrix.  The 2-argument form returns a new array like the reference (which
-    allocates ``similar(B)``, factornode.jl:62); the 3-argument form writes into ``C`` (``C`` may be ``B``)."""
+    allocates ``similar(B)``, factornode.jl:62); the 3-argument form writes into ``C`` (``C`` may be ``B``).
+    ``F`` may be ``transpose(F)`` or ``adjoint(F)``: then ``C = F^-T B`` / ``C = F^-H B``."""
     if len(args) == 2:
         F, B = args
         Cout = None
@@ -289,6 +345,9 @@ def ldiv(*args):
         Cout, F, B = args
     else:
         raise TypeError("ldiv(F, B) or ldiv(C, F, B)")
+    trans = 0
+    if isinstance(F, TransposedFactor):
+        F, trans = F.parent, F.trans
     B = np.asarray(B)
     if B.shape[0] != F.n:
         raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
@@ -300,8 +359,12 @@ def ldiv(*args):
     Bm = np.asfortranarray(B.reshape(F.n, -1))
     Cm = np.empty_like(Bm, order="F")
     L = _lib.lib()
-    fn = L.hs_ldiv_z if F.dtype.kind == "c" else L.hs_ldiv_d
-    _lib.check(fn(F._h, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
+    if trans:
+        fn = L.hs_ldiv_t_z if F.dtype.kind == "c" else L.hs_ldiv_t_d
+        _lib.check(fn(F._h, trans, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
+    else:
+        fn = L.hs_ldiv_z if F.dtype.kind == "c" else L.hs_ldiv_d
+        _lib.check(fn(F._h, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
     res = Cm[:, 0] if vec else Cm
     if Cout is not None:
         Cout[...] = res

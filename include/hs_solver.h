@@ -6,6 +6,7 @@
  *   factor(A::SparseMatrixCSC{T}, nd, nd_loc, opts; kw...) -> FactorNode{T}
  *                                      (reference src/factorization.jl:5-11)
  *   ldiv!(C, F, B), ldiv!(F, B)        (reference src/factornode.jl:62-74)
+ *   ldiv!(C, transpose(F), B), ldiv!(C, adjoint(F), B)   (hs_ldiv_t_*, hs_ldiv_dev_t_*)
  *   maxrank(F)                         (reference src/factornode.jl:49-57)
  *
  * The reference has no FFI of its own (it is pure Julia); these entry points
@@ -135,6 +136,16 @@ int hs_ldiv_z(hs_handle* F, double* C, int64_t ldc, const double* B, int64_t ldb
  * for an on-device Krylov caller (gmres(...; Pr=F), test/rungmres.jl:47-48). */
 int hs_ldiv_dev_d(hs_handle* F, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 int hs_ldiv_dev_z(hs_handle* F, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+
+/* ldiv!(C, transpose(F), B) (trans = 1) and ldiv!(C, adjoint(F), B) (trans = 2; = 1 for Float64); trans = 0: hs_ldiv_*.
+ * Same factors, no refactorization; single-rank factorizations whose fronts all keep a dense LU of D (else HS_ERR_UNSUPPORTED).
+ * Limits, refused with HS_ERR_UNSUPPORTED before any device work: fronts that keep D as an HSS matrix (hs_options.hss_d, mf = 2, 3:
+ * no transposed ULV solve) and factorizations over more than one rank (whatever dist_top is).  Other trans: HS_ERR_ARGUMENT.
+ * The _dev_ forms take device pointers on `stream` like hs_ldiv_dev_*; C may alias B in both.  The host forms set stats.t_solve. */
+int hs_ldiv_t_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_ldiv_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_ldiv_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+int hs_ldiv_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 
 /* ---- phased form of factor (hs_factor_* = hs_analyze + hs_numeric_* over all levels) -------------------------
  * hs_analyze builds the plan and uploads the sparsity pattern, so a later numeric factorization starts with
