@@ -72,6 +72,7 @@ HS_BLK_LU, HS_BLK_LBI, HS_BLK_UIB, HS_BLK_S = 0, 1, 2, 3
 EXPORTS = [
     "hs_options_default", "hs_factor_d", "hs_factor_z", "hs_ldiv_d", "hs_ldiv_z", "hs_ldiv_dev_d", "hs_ldiv_dev_z",
     "hs_ldiv_t_d", "hs_ldiv_t_z", "hs_ldiv_dev_t_d", "hs_ldiv_dev_t_z",
+    "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_maxrank", "hs_is_complex", "hs_size", "hs_free", "hs_last_error", "hs_last_error_info", "hs_get_stats",
     "hs_node_info", "hs_node_ranks", "hs_node_export", "hs_node_export_piv", "hs_device_info",
     "hs_analyze", "hs_plan", "hs_numeric_begin", "hs_numeric_levels", "hs_numeric_end", "hs_solve_fwd_levels", "hs_solve_bwd_levels",
@@ -135,6 +136,18 @@ def lib():
         f.restype = C.c_int
     for f in (L.hs_ldiv_dev_t_d, L.hs_ldiv_dev_t_z):
         f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
+        f.restype = C.c_int
+    L.hs_opnorm.argtypes = [vp, C.c_int, p_f64]
+    L.hs_opnorm.restype = C.c_int
+    L.hs_normestinv.argtypes = [vp, C.c_int, i64, i64, p_f64, p_i64, vp]
+    L.hs_normestinv.restype = C.c_int
+    L.hs_condest.argtypes = [vp, C.c_int, i64, p_f64, p_f64, p_f64, vp]
+    L.hs_condest.restype = C.c_int
+    for f in (L.hs_ldiv_refine_d, L.hs_ldiv_refine_z):
+        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64, i64, p_f64, p_f64, p_i64]
+        f.restype = C.c_int
+    for f in (L.hs_ldiv_refine_dev_d, L.hs_ldiv_refine_dev_z):
+        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, i64, p_f64, p_f64, p_i64, vp]
         f.restype = C.c_int
     L.hs_analyze.argtypes = [C.c_int, i64, p_i64, p_i64, C.POINTER(hs_tree), C.POINTER(hs_options), i64, i64, C.POINTER(vp)]
     L.hs_analyze.restype = C.c_int

@@ -29,6 +29,7 @@
 #include "../../include/hs_solver.h"
 #include "../../include/hs_hss.h"
 #include "hs_common.h"
+#include "hs_condest.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -277,6 +278,8 @@ struct hs_handle {
   std::vector<std::pair<int, hipEvent_t>> level_events;
   double flops = 0.0;
   hs_stats stats;
+  void* cx = nullptr;  // hs_condest.hip: the CSR map of A, built by the first call that needs rows of A
+  void (*cx_free)(void*) = nullptr;
 };
 
 static inline int rup(int x, int a) { return (x + a - 1) / a * a; }
@@ -352,6 +355,7 @@ static void free_mfd_buffers(hs_handle* h);
 static void free_handle(hs_handle* h) {
   if (!h) return;
   if (h->stream) (void)hipStreamSynchronize(h->stream);  // recycled blocks must be idle when they go back to the caches
+  if (h->cx && h->cx_free) h->cx_free(h->cx);
   for (auto& x : h->nodes)
     if (x.S_hss) {
       hs_hss_free((hs_hss*)x.S_hss);
@@ -1690,6 +1694,34 @@ static void ldiv_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB,
     solve_t<T>(h, trans, c, s);
   }
 }
+
+// the handle as hs_condest.hip sees it (hs_condest.h)
+void hs_handle_view(hs_handle* h, HsHandleView* v) {
+  *v = HsHandleView();
+  v->n = h->n;
+  v->nnz = h->nnz;
+  v->is_complex = h->is_complex ? 1 : 0;
+  v->factored = h->factored ? 1 : 0;
+  v->device = h->d_nodes ? 1 : 0;
+  v->nranks = h->nranks;
+  for (size_t i = 0; i < h->nodes.size() && v->t_refused_node < 0; ++i) {
+    const NodeH& x = h->nodes[i];
+    if (x.mine && (x.hssd || (x.mf && !x.mfd))) v->t_refused_node = (int)i;  // what check_solve_t refuses
+  }
+  v->seed = h->opts.seed;
+  v->colptr = h->d_colptr;
+  v->rowval = h->d_rowval;
+  v->nz = h->d_nz;
+  if (h->mf_on) {
+    v->rowptr = h->d_rowptr;
+    v->colind = h->d_colind;
+    v->tperm = h->d_tperm;
+  }
+  v->stream = h->stream;
+  v->cx = &h->cx;
+  v->cx_free = &h->cx_free;
+}
+int hs_handle_flow_check(hs_handle* h) { HS_GUARD(flow_check(h)); }
 
 // ------------------------------------------------------------------------------------------------
 // C ABI

@@ -9,6 +9,9 @@ reference (Julia)                      here
 ``ldiv!(F, B)``, ``ldiv!(C, F, B)``    :func:`ldiv`            (factornode.jl:62-74)
 ``transpose(F)``, ``adjoint(F)``       :func:`transpose`, :func:`adjoint` (``ldiv`` takes them: ``A^T x = b``, ``A^H x = b``)
 ``maxrank(F)``                         :func:`maxrank`         (factornode.jl:49-57)
+``opnorm(A, p)``, ``opnormestinv(A)``  :func:`opnorm`, :func:`opnormestinv` (on the factorization's A and F; ``hs_condest.hip``)
+``cond(A, p)`` (estimated)             :func:`condest`
+``xGERFS`` (refine, berr, ferr)        :func:`ldiv_refine`
 ``F \\ b``                              ``F.solve(b)``
 =====================================  ====================================================
 
@@ -24,7 +27,8 @@ import scipy.sparse as sp
 from . import _lib
 from .nesteddissection import flatten_tree
 
-__all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint"]
+__all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
+           "ldiv_refine"]
 
 
 class SolverOptions:
@@ -375,3 +379,84 @@ def ldiv(*args):
 def maxrank(F):
     """``maxrank(F)`` (factornode.jl:49-57)."""
     return int(_lib.lib().hs_maxrank(F._h))
+
+
+def _unwrap(F):
+    """``(FactorNode, trans)`` of ``F``, ``transpose(F)`` or ``adjoint(F)``."""
+    if isinstance(F, TransposedFactor):
+        return F.parent, F.trans
+    if not isinstance(F, FactorNode):
+        raise TypeError(f"expected a FactorNode, got {type(F).__name__}")
+    return F, 0
+
+
+def _pcode(p):
+    if p == 1:
+        return 1
+    if p in (np.inf, "inf", "Inf"):
+        return 0
+    raise ValueError(f"ArgumentError: p must be 1 or Inf, not {p!r}")
+
+
+def opnorm(F, p=1):
+    """``opnorm(A, p)``, p = 1 or ``np.inf``, of the matrix ``F`` factors (the values of its last numeric factorization), computed on the
+    device (``hs_opnorm``).  For ``transpose(F)`` / ``adjoint(F)``: the norm of ``A^T`` / ``A^H``."""
+    F, trans = _unwrap(F)
+    pc = _pcode(p)
+    if trans:
+        pc = 1 - pc  # ||A^T||_1 = ||A||_Inf
+    out = C.c_double()
+    _lib.check(_lib.lib().hs_opnorm(F._h, pc, C.byref(out)))
+    return out.value
+
+
+def opnormestinv(F, t=2, itmax=5, nsolves=False):
+    """Julia's ``opnormestinv``: a lower bound of ``||op(F)^-1||_1`` (usually within a factor of 3) by the Higham-Tisseur block 1-norm
+    estimator with ``t`` columns (``t`` is clipped to ``n`` like Julia's ``min(2, n)``).  ``F`` may be ``transpose(F)`` or ``adjoint(F)``.
+    ``nsolves=True`` returns ``(est, columns solved)``."""
+    F, trans = _unwrap(F)
+    t = min(int(t), F.n)
+    est, ns = C.c_double(), _lib.i64()
+    _lib.check(_lib.lib().hs_normestinv(F._h, trans, t, int(itmax), C.byref(est), C.byref(ns), None))
+    return (est.value, ns.value) if nsolves else est.value
+
+
+def condest(F, p=1, t=2):
+    """``cond(A, p) ~ opnorm(A, p) * opnormestinv``, p = 1 or ``np.inf`` (``hs_condest``).  For a compressed factorization this estimates
+    cond(A) only as well as F approximates A.  ``condest(transpose(F), p)`` is the estimate for ``A^T``."""
+    F, trans = _unwrap(F)
+    pc = _pcode(p)
+    if trans:
+        pc = 1 - pc  # cond_1(A^T) = cond_Inf(A)
+    t = min(int(t), F.n)
+    out = C.c_double()
+    _lib.check(_lib.lib().hs_condest(F._h, pc, t, C.byref(out), None, None, None))
+    return out.value
+
+
+def ldiv_refine(F, B, itmax=5, ferr=True):
+    """LAPACK xGERFS on ``op(A) X = B`` (``op`` by ``F``, ``transpose(F)`` or ``adjoint(F)``): ``X = op(F) \\ B``, then iterative refinement
+    with the residual of A itself, at most ``itmax`` corrections (``hs_ldiv_refine_*``).  Returns ``(X, berr, ferr, steps)``: the componentwise
+    backward error, the forward error bound (None with ``ferr=False``) and the corrections made, per column (scalars for a vector B)."""
+    F, trans = _unwrap(F)
+    B = np.asarray(B)
+    if B.shape[0] != F.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
+    if B.dtype != F.dtype:
+        if F.dtype.kind == "f" and B.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching ldiv_refine(::FactorNode{Float64}, ::Array{ComplexF64})")
+        B = B.astype(F.dtype)
+    vec = B.ndim == 1
+    Bm = np.asfortranarray(B.reshape(F.n, -1))
+    k = Bm.shape[1]
+    X = np.empty_like(Bm, order="F")
+    be = np.zeros(k)
+    fe = np.zeros(k) if ferr else None
+    st = np.zeros(k, dtype=np.int64)
+    L = _lib.lib()
+    fn = L.hs_ldiv_refine_z if F.dtype.kind == "c" else L.hs_ldiv_refine_d
+    _lib.check(fn(F._h, trans, X.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, k, int(itmax), _pf64(be),
+                  _pf64(fe) if ferr else None, _p64(st)))
+    if vec:
+        return X[:, 0], float(be[0]), (float(fe[0]) if ferr else None), int(st[0])
+    return X, be, fe, st

@@ -7,6 +7,7 @@
  *                                      (reference src/factorization.jl:5-11)
  *   ldiv!(C, F, B), ldiv!(F, B)        (reference src/factornode.jl:62-74)
  *   ldiv!(C, transpose(F), B), ldiv!(C, adjoint(F), B)   (hs_ldiv_t_*, hs_ldiv_dev_t_*)
+ *   opnorm(A, p), opnormestinv(A), cond(A, p), refined solves (xGERFS)   (hs_opnorm, hs_normestinv, hs_condest, hs_ldiv_refine_*)
  *   maxrank(F)                         (reference src/factornode.jl:49-57)
  *
  * The reference has no FFI of its own (it is pure Julia); these entry points
@@ -146,6 +147,34 @@ int hs_ldiv_t_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B
 int hs_ldiv_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
 int hs_ldiv_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 int hs_ldiv_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+
+/* ---- accuracy tools: norm and condition estimates, refined solves with error bounds (hs_condest.hip) --------------------------
+ * opnorm(A, 1), opnorm(A, Inf) of the handle's A (the values of the last hs_numeric_begin); p = 1 or 0 (= Inf).  The first call that needs
+ * rows of A (p = 0, hs_condest p = 0, hs_ldiv_refine_* with trans = 0) builds a CSR map of A's pattern on the device and keeps it in the handle. */
+int hs_opnorm(hs_handle* F, int p, double* norm);
+/* Julia's opnormestinv: the Higham-Tisseur block 1-norm estimate (SIAM J. Matrix Anal. Appl. 21(4), 2000, Alg. 2.4) of op(F)^-1,
+ * op = F (trans 0), transpose(F) (1), adjoint(F) (2), with t columns (1:min(8, n); Julia's default min(2, n)) and at most itmax iterations
+ * (>= 1; Julia's 5).  A lower bound of ||op(F)^-1||_1, usually within a factor of 3; *nsolves (may be NULL) = columns solved.  Deterministic:
+ * the +-1 columns come from a hash of hs_options.seed, every reduction runs in a fixed order, two calls return the same bits. */
+int hs_normestinv(hs_handle* F, int trans, int64_t t, int64_t itmax, double* est, int64_t* nsolves, void* stream);
+/* cond(A, p) ~ ||A||_p * ||F^-1||_p, p = 1 or 0 (= Inf; ||F^-1||_Inf = ||F^-T||_1), itmax = 5.  For a compressed factorization (swlevel > 0)
+ * this estimates cond(A) only as well as F approximates A.  normA, normFinv may be NULL. */
+int hs_condest(hs_handle* F, int p, int64_t t, double* cond, double* normA, double* normFinv, void* stream);
+/* LAPACK xGERFS on op(A) X = B, op by trans as in hs_ldiv_t_*: X = op(F) \ B, then per column r = b - op(A) x, the componentwise backward
+ * error berr = max_i |r_i| / (|b| + |op(A)| |x|)_i (cabs1 for ComplexF64), and x += op(F) \ r while berr > eps, berr at least halves and
+ * fewer than itmax (>= 0; 5 as in LAPACK) corrections were made.  ferr (may be NULL) = the estimate of || |op(A)^-1| (|r| + nz eps w) ||_Inf
+ * / ||x||_Inf (the hs_normestinv engine, t = min(2, n), on diag(v) op(F)^-H).  berr, ferr and steps are host arrays of nrhs entries.
+ * Refused with HS_ERR_UNSUPPORTED before any device work: factorizations over more than one rank; and where transposed solves are refused
+ * (fronts that keep D as an HSS matrix), trans != 0 or ferr != NULL (hs_normestinv and hs_condest too).  Bad t, p, itmax, trans or
+ * dimensions: HS_ERR_ARGUMENT / HS_ERR_DIMENSION.  The _dev_ forms take device X, B on `stream`; X may not alias B. */
+int hs_ldiv_refine_d(hs_handle* F, int trans, double* X, int64_t ldx, const double* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                     double* berr, double* ferr, int64_t* steps);
+int hs_ldiv_refine_z(hs_handle* F, int trans, double* X, int64_t ldx, const double* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                     double* berr, double* ferr, int64_t* steps);
+int hs_ldiv_refine_dev_d(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                         double* berr, double* ferr, int64_t* steps, void* stream);
+int hs_ldiv_refine_dev_z(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                         double* berr, double* ferr, int64_t* steps, void* stream);
 
 /* ---- phased form of factor (hs_factor_* = hs_analyze + hs_numeric_* over all levels) -------------------------
  * hs_analyze builds the plan and uploads the sparsity pattern, so a later numeric factorization starts with
