@@ -1,6 +1,7 @@
 // hs_testhooks.hip -- kernel-level entry points used only by tests/ (declared in include/hs_kernels.h).
 // They drive exactly the kernels hs_factor_* uses, on caller-supplied dense data, so every kernel
 // can be checked against the oracle in isolation.
+#include <algorithm>
 #include <cstring>
 #include <chrono>
 #include <vector>
@@ -70,56 +71,112 @@ extern "C" int hsk_gemm_z(int64_t M, int64_t N, int64_t K, const double* A, int6
   return gemm_hook<cplx>(M, N, K, (const cplx*)A, lda, (const cplx*)B, ldb, (cplx*)C, ldc, minus, repeat, ms_out);
 }
 
-// Factor `count` identical-shape dense fronts F[k] ((ni+nb)^2, column-major, front order [int;bnd]) in one batch.
+// Factor a batch of `count` dense fronts F[k] ((ni[k]+nb[k])^2, column-major, front order [int;bnd], packed one after another) the way
+// hs_numeric factors a level: one Sched over the batch (batch maxima, per-front sizes on the host, the look-ahead streams).
+//   mode 0: tournament pivoting, no solve descriptors   1: optimistic, no descriptors (32-row TRSM base case, full-height panels)
+//        2: optimistic WITH descriptors -- the production default: diagonal-block-first 256-column groups, inv256, ainv 3..8 / 16..19
+//        3: tournament with descriptors -- what a redone level runs
+// Outputs (any may be null) are packed per front in the same order: LF m x ni, UR ni x nb, SB nb x nb, rperm ni, info, growth;
+// invL / invU ceil(ni/32) blocks of 32 x 32, inv256L / inv256U ceil(ni/256) blocks of 256 x 256 (column-major; modes 2, 3 only).
 template <class T>
-static int front_hook(int64_t count, int64_t ni, int64_t nb, const T* F, T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info,
-                      double* ms_out) {
+static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, T* outLF, T* outUR, T* outSB,
+                            int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U,
+                            double* ms_out) {
+  if (count <= 0 || count > 65535 || !ni_ || !nb_ || !F || mode < 0 || mode > 3) {
+    hs_set_error(HS_ERR_ARGUMENT, count, "hsk_front_batch: count in [1, 65535], ni, nb and F non-null and mode in 0..3 required");
+    return HS_ERR_ARGUMENT;
+  }
+  for (int64_t k = 0; k < count; ++k)
+    if (ni_[k] < 0 || nb_[k] < 0 || ni_[k] + nb_[k] > (1 << 16)) {
+      hs_set_error(HS_ERR_ARGUMENT, k, "hsk_front_batch: front %lld has ni = %lld, nb = %lld (need 0 <= ni, nb and ni + nb <= 65536)", (long long)k,
+                   (long long)ni_[k], (long long)nb_[k]);
+      return HS_ERR_ARGUMENT;
+    }
+  if ((outInvL || outInvU || outInv256L || outInv256U) && mode < 2) {
+    hs_set_error(HS_ERR_ARGUMENT, mode, "hsk_front_batch: the stored inverses are returned by modes 2 and 3 only");
+    return HS_ERR_ARGUMENT;
+  }
   int cnt = 0;
   if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
     hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
     return HS_ERR_DEVICE;
   }
-  const int m = (int)(ni + nb);
-  const int ldl = (m + 1) / 2 * 2, ldu = ((int)ni + 1) / 2 * 2 > 0 ? ((int)ni + 1) / 2 * 2 : 2, lds = ((int)nb + 1) / 2 * 2 > 0 ? ((int)nb + 1) / 2 * 2 : 2;
-  const int nblk = ((int)ni + HS_PB - 1) / HS_PB;
-  const size_t eLF = (size_t)ldl * ni + 32, eUR = (size_t)ldu * nb + 32, eSB = (size_t)lds * nb + 32, eInv = (size_t)2 * nblk * 1024 + 32;
-  const int ncand = (((int)ni + HS_CHUNK - 1) / HS_CHUNK + 1) * HS_PB;
-  const size_t eInt = (size_t)2 * ni + 2 * ncand + HS_PB + 1;
+  auto rup32 = [](size_t e) { return (e + 31) / 32 * 32; };
+  // per-front layout of one device buffer of T and one of int, laid out as hs_analyze lays out the factor arenas
+  struct Off {
+    int ni, nb, m, ldl, ldu, lds, nblk, nb256, ncand;
+    size_t lf, ur, sb, inv, inv256, ip, cand;
+  };
+  std::vector<Off> o(count);
+  std::vector<int> h_ni(count), h_nb(count);
+  size_t nT = 0, nI = 0;
+  int maxni = 0, maxnb = 0, maxm = 0;
+  for (int64_t k = 0; k < count; ++k) {
+    Off& x = o[k];
+    x.ni = (int)ni_[k]; x.nb = (int)nb_[k]; x.m = x.ni + x.nb;
+    x.ldl = std::max((x.m + 1) / 2 * 2, 2); x.ldu = std::max((x.ni + 1) / 2 * 2, 2); x.lds = std::max((x.nb + 1) / 2 * 2, 2);
+    x.nblk = (x.ni + HS_PB - 1) / HS_PB;
+    x.nb256 = (x.ni + 255) / 256;
+    x.ncand = ((x.ni + HS_CHUNK - 1) / HS_CHUNK + 1) * HS_PB;
+    x.lf = nT; nT += rup32((size_t)x.ldl * x.ni) + 32;
+    x.ur = nT; nT += rup32((size_t)x.ldu * x.nb) + 32;
+    x.sb = nT; nT += rup32((size_t)x.lds * x.nb) + 32;
+    x.inv = nT; nT += (size_t)2 * x.nblk * HS_PB * HS_PB + 32;
+    x.inv256 = nT; nT += (size_t)2 * x.nb256 * 65536 + 32;
+    x.ip = nI; nI += (size_t)2 * x.ni + 2;  // ipiv, rperm, info, growth
+    x.cand = nI; nI += (size_t)2 * x.ncand + HS_PB + 32;
+    h_ni[k] = x.ni; h_nb[k] = x.nb;
+    maxni = std::max(maxni, x.ni); maxnb = std::max(maxnb, x.nb); maxm = std::max(maxm, x.m);
+  }
   T* dbuf = nullptr;
   int* dint = nullptr;
   NodeDesc<T>* dn = nullptr;
-  const size_t per = eLF + eUR + eSB + eInv;
-  CK(hipMalloc((void**)&dbuf, sizeof(T) * per * count));
-  CK(hipMalloc((void**)&dint, sizeof(int) * eInt * count));
+  SolveNode<T>* dsn = nullptr;
+  CK(hipMalloc((void**)&dbuf, sizeof(T) * nT));
+  CK(hipMalloc((void**)&dint, sizeof(int) * nI));
   CK(hipMalloc((void**)&dn, sizeof(NodeDesc<T>) * count));
-  CK(hipMemset(dbuf, 0, sizeof(T) * per * count));
-  CK(hipMemset(dint, 0, sizeof(int) * eInt * count));
+  CK(hipMalloc((void**)&dsn, sizeof(SolveNode<T>) * count));
+  CK(hipMemset(dbuf, 0, sizeof(T) * nT));
+  CK(hipMemset(dint, 0, sizeof(int) * nI));
   std::vector<NodeDesc<T>> hn(count);
+  std::vector<SolveNode<T>> hs(count);
+  const T* Fk = F;
   for (int64_t k = 0; k < count; ++k) {
+    const Off& x = o[k];
     NodeDesc<T>& d = hn[k];
     memset(&d, 0, sizeof d);
-    d.LF = dbuf + per * k;
-    d.UR = d.LF + eLF;
-    d.SB = d.UR + eUR;
-    d.invL = d.SB + eSB;
-    d.invU = d.invL + (size_t)nblk * 1024;
-    d.ipiv = dint + eInt * k;
-    d.rperm = d.ipiv + ni;
-    d.cand0 = d.rperm + ni;
-    d.cand1 = d.cand0 + ncand;
-    d.pivlist = d.cand1 + ncand;
-    d.info = d.pivlist + HS_PB;
-    d.growth = d.info;  // HS_HOOK_OPTIMISTIC=1: the growth flag of optimistic pivoting comes back through `info` as -1
-    d.ni = (int)ni; d.nb = (int)nb; d.m = m;
-    d.ldl = ldl; d.ldu = ldu; d.lds = lds;
-    d.ni1 = (int)ni; d.nb1 = (int)nb; d.isleaf = 1; d.node = (int)k;
+    d.LF = dbuf + x.lf; d.UR = dbuf + x.ur; d.SB = dbuf + x.sb;
+    d.invL = dbuf + x.inv;
+    d.invU = d.invL + (size_t)x.nblk * HS_PB * HS_PB;
+    d.inv256L = dbuf + x.inv256;
+    d.inv256U = d.inv256L + (size_t)x.nb256 * 65536;
+    d.ipiv = dint + x.ip;
+    d.rperm = d.ipiv + x.ni;
+    d.info = d.rperm + x.ni;
+    d.growth = d.info + 1;
+    d.cand0 = dint + x.cand;
+    d.cand1 = d.cand0 + x.ncand;
+    d.pivlist = d.cand1 + x.ncand;
+    d.ni = x.ni; d.nb = x.nb; d.m = x.m;
+    d.ldl = x.ldl; d.ldu = x.ldu; d.lds = x.lds;
+    d.ni1 = x.ni; d.nb1 = x.nb; d.isleaf = 1; d.node = (int)k;
+    d.pivrows = x.ni;
     d.finalize();
-    const T* Fk = F + (size_t)m * m * k;
-    if (ni > 0) CK(hipMemcpy2D(d.LF, sizeof(T) * ldl, Fk, sizeof(T) * m, sizeof(T) * m, ni, hipMemcpyHostToDevice));
-    if (ni > 0 && nb > 0) CK(hipMemcpy2D(d.UR, sizeof(T) * ldu, Fk + (size_t)m * ni, sizeof(T) * m, sizeof(T) * ni, nb, hipMemcpyHostToDevice));
-    if (nb > 0) CK(hipMemcpy2D(d.SB, sizeof(T) * lds, Fk + (size_t)m * ni + ni, sizeof(T) * m, sizeof(T) * nb, nb, hipMemcpyHostToDevice));
+    SolveNode<T>& q = hs[k];
+    memset(&q, 0, sizeof q);
+    q.LF = d.LF; q.UR = d.UR; q.invL = d.invL; q.invU = d.invU;
+    q.inv256L = d.inv256L; q.inv256U = d.inv256U;
+    q.rperm = d.rperm;
+    q.ni = x.ni; q.nb = x.nb; q.m = x.m; q.ldl = x.ldl; q.ldu = x.ldu;
+    q.mrows = x.m;
+    const int m = x.m;
+    if (x.ni > 0) CK(hipMemcpy2D(d.LF, sizeof(T) * x.ldl, Fk, sizeof(T) * m, sizeof(T) * m, x.ni, hipMemcpyHostToDevice));
+    if (x.ni > 0 && x.nb > 0) CK(hipMemcpy2D(d.UR, sizeof(T) * x.ldu, Fk + (size_t)m * x.ni, sizeof(T) * m, sizeof(T) * x.ni, x.nb, hipMemcpyHostToDevice));
+    if (x.nb > 0) CK(hipMemcpy2D(d.SB, sizeof(T) * x.lds, Fk + (size_t)m * x.ni + x.ni, sizeof(T) * m, sizeof(T) * x.nb, x.nb, hipMemcpyHostToDevice));
+    Fk += (size_t)m * m;
   }
   CK(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice));
   Profiler prof;
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
@@ -129,11 +186,11 @@ static int front_hook(int64_t count, int64_t ni, int64_t nb, const T* F, T* outL
   CK(hipStreamCreate(&s_main));
   hs_create_lookahead_streams(&s_la, &s_sidem, &s_side);
   CK(hipEventRecord(e0, s_main));
-  launch_init_fronts<T>(dn, (int)count, (int)ni, s_main);
-  Sched<T> sch{dn, (int)count, (int)ni, (int)nb, m, s_main, &prof, nullptr, nullptr, s_side, 0, s_la, s_sidem};
+  launch_init_fronts<T>(dn, (int)count, maxni, s_main);
+  Sched<T> sch{dn, (int)count, maxni, maxnb, maxm, s_main, &prof, h_ni.data(), h_nb.data(), s_side, 0, s_la, s_sidem};
+  if (mode >= 2) sch.sn = dsn;
+  sch.optimistic = (mode == 1 || mode == 2);
   const auto h0 = std::chrono::steady_clock::now();
-  const bool hook_opt = getenv("HS_HOOK_OPTIMISTIC") != nullptr;
-  sch.optimistic = hook_opt;
   sch.factor_fronts();
   CK(hipEventRecord(e1, s_main));
   if (getenv("HS_HOOK_VERBOSE"))
@@ -143,18 +200,27 @@ static int front_hook(int64_t count, int64_t ni, int64_t nb, const T* F, T* outL
   CK(hipEventElapsedTime(&ms, e0, e1));
   if (ms_out) *ms_out = ms;
   CK(hipDeviceSynchronize());
-  std::vector<int> ip(ni);
+  std::vector<int> ip;
+  size_t pLF = 0, pUR = 0, pSB = 0, pR = 0, pInv = 0, pInv256 = 0;
   for (int64_t k = 0; k < count; ++k) {
-    NodeDesc<T>& d = hn[k];
-    if (ni > 0 && outLF) CK(hipMemcpy2D(outLF + (size_t)m * ni * k, sizeof(T) * m, d.LF, sizeof(T) * ldl, sizeof(T) * m, ni, hipMemcpyDeviceToHost));
-    if (ni > 0 && nb > 0 && outUR) CK(hipMemcpy2D(outUR + (size_t)ni * nb * k, sizeof(T) * ni, d.UR, sizeof(T) * ldu, sizeof(T) * ni, nb, hipMemcpyDeviceToHost));
-    if (nb > 0 && outSB) CK(hipMemcpy2D(outSB + (size_t)nb * nb * k, sizeof(T) * nb, d.SB, sizeof(T) * lds, sizeof(T) * nb, nb, hipMemcpyDeviceToHost));
-    if (ni > 0) CK(hipMemcpy(ip.data(), d.rperm, sizeof(int) * ni, hipMemcpyDeviceToHost));
+    const Off& x = o[k];
+    const NodeDesc<T>& d = hn[k];
+    const int ni = x.ni, nb = x.nb, m = x.m;
+    if (ni > 0 && outLF) CK(hipMemcpy2D(outLF + pLF, sizeof(T) * m, d.LF, sizeof(T) * x.ldl, sizeof(T) * m, ni, hipMemcpyDeviceToHost));
+    if (ni > 0 && nb > 0 && outUR) CK(hipMemcpy2D(outUR + pUR, sizeof(T) * ni, d.UR, sizeof(T) * x.ldu, sizeof(T) * ni, nb, hipMemcpyDeviceToHost));
+    if (nb > 0 && outSB) CK(hipMemcpy2D(outSB + pSB, sizeof(T) * nb, d.SB, sizeof(T) * x.lds, sizeof(T) * nb, nb, hipMemcpyDeviceToHost));
+    ip.resize((size_t)ni + 2);
+    CK(hipMemcpy(ip.data(), d.rperm, sizeof(int) * ((size_t)ni + 2), hipMemcpyDeviceToHost));  // rperm, info, growth
     if (out_rperm)
-      for (int64_t i = 0; i < ni; ++i) out_rperm[ni * k + i] = ip[i];
-    int inf = 0;
-    CK(hipMemcpy(&inf, d.info, sizeof(int), hipMemcpyDeviceToHost));
-    if (info) info[k] = (hook_opt && inf != 0) ? -1 : inf;
+      for (int i = 0; i < ni; ++i) out_rperm[pR + i] = ip[i];
+    if (info) info[k] = ip[ni];
+    if (growth) growth[k] = ip[ni + 1];
+    const size_t n32 = (size_t)x.nblk * HS_PB * HS_PB, n256 = (size_t)x.nb256 * 65536;
+    if (outInvL && n32) CK(hipMemcpy(outInvL + pInv, d.invL, sizeof(T) * n32, hipMemcpyDeviceToHost));
+    if (outInvU && n32) CK(hipMemcpy(outInvU + pInv, d.invU, sizeof(T) * n32, hipMemcpyDeviceToHost));
+    if (outInv256L && n256) CK(hipMemcpy(outInv256L + pInv256, d.inv256L, sizeof(T) * n256, hipMemcpyDeviceToHost));
+    if (outInv256U && n256) CK(hipMemcpy(outInv256U + pInv256, d.inv256U, sizeof(T) * n256, hipMemcpyDeviceToHost));
+    pLF += (size_t)m * ni; pUR += (size_t)ni * nb; pSB += (size_t)nb * nb; pR += ni; pInv += n32; pInv256 += n256;
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
@@ -165,6 +231,38 @@ static int front_hook(int64_t count, int64_t ni, int64_t nb, const T* F, T* outL
   (void)hipFree(dbuf);
   (void)hipFree(dint);
   (void)hipFree(dn);
+  (void)hipFree(dsn);
+  return HS_OK;
+}
+
+extern "C" int hsk_front_batch_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
+                                 double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
+                                 double* outInv256L, double* outInv256U, double* ms_out) {
+  return front_batch_hook<double>(count, ni, nb, mode, F, outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U, ms_out);
+}
+extern "C" int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
+                                 double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
+                                 double* outInv256L, double* outInv256U, double* ms_out) {
+  return front_batch_hook<cplx>(count, ni, nb, mode, (const cplx*)F, (cplx*)outLF, (cplx*)outUR, (cplx*)outSB, out_rperm, info, growth,
+                                (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, ms_out);
+}
+
+// `count` fronts of one shape, tournament pivoting without solve descriptors (mode 0); HS_HOOK_OPTIMISTIC=1: mode 1, and a raised growth
+// flag comes back through `info` as -1
+template <class T>
+static int front_hook(int64_t count, int64_t ni, int64_t nb, const T* F, T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info,
+                      double* ms_out) {
+  if (count <= 0) {
+    hs_set_error(HS_ERR_ARGUMENT, count, "hsk_front_factor: count must be positive");
+    return HS_ERR_ARGUMENT;
+  }
+  const bool hook_opt = getenv("HS_HOOK_OPTIMISTIC") != nullptr;
+  std::vector<int64_t> vni(count, ni), vnb(count, nb), inf(count), gr(count);
+  const int st = front_batch_hook<T>(count, vni.data(), vnb.data(), hook_opt ? 1 : 0, F, outLF, outUR, outSB, out_rperm, inf.data(), gr.data(),
+                                     nullptr, nullptr, nullptr, nullptr, ms_out);
+  if (st != HS_OK) return st;
+  if (info)
+    for (int64_t k = 0; k < count; ++k) info[k] = hook_opt ? ((inf[k] != 0 || gr[k] != 0) ? -1 : 0) : inf[k];
   return HS_OK;
 }
 

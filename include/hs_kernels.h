@@ -31,6 +31,21 @@ int hsk_front_factor_d(int64_t count, int64_t ni, int64_t nb, const double* F, d
 int hsk_front_factor_z(int64_t count, int64_t ni, int64_t nb, const double* F, double* outLF, double* outUR,
                        double* outSB, int64_t* out_rperm, int64_t* info, double* ms_out);
 
+/* The same elimination for a batch of `count` fronts of their own sizes ni[k], nb[k] (F packed column-major, one front after another),
+ * scheduled as hs_numeric schedules a level.  mode 0: tournament pivoting, no solve descriptors (hsk_front_factor_*); 1: optimistic
+ * pivoting, no descriptors; 2: optimistic pivoting with descriptors (the default path: diagonal-block-first 256-column groups and the
+ * inverses of the 256 x 256 diagonal blocks); 3: tournament pivoting with descriptors (a redone level).  Every output may be null; each is
+ * packed per front in batch order: outLF m x ni, outUR ni x nb, outSB nb x nb, out_rperm ni, info[k], growth[k] (1: optimistic
+ * pivoting met a multiplier above HS_GROWTH_MAX = 4, a NaN multiplier or a diagonal block singular on its own rows), outInvL / outInvU
+ * ceil(ni/32) column-major 32 x 32 inverses of the diagonal blocks of L (unit lower) and U, outInv256L / outInv256U ceil(ni/256)
+ * 256 x 256 ones (modes 2 and 3 only). */
+int hsk_front_batch_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
+                      double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
+                      double* outInv256L, double* outInv256U, double* ms_out);
+int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
+                      double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
+                      double* outInv256L, double* outInv256U, double* ms_out);
+
 /* Low-rank compression X (rows x cols) ~= C (rows x r) * Z (r x cols) to tolerance max(atol, rtol*|u_11|): the
  * device primitive behind the compressed Gauss transforms (`_lgauss_transform` / `_rgauss_transform`,
  * src/factorization.jl:171-182, which call LowRankApprox.pqrfact).  cap = capacity (in columns of C / rows of Z)
