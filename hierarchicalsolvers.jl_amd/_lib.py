@@ -66,13 +66,14 @@ HS_TRANSFER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, i64, p_i64, C.POINTER(C.c_void
 HS_OK = 0
 HS_ERR_ARGUMENT, HS_ERR_DIMENSION, HS_ERR_TREE, HS_ERR_SINGULAR = -1, -2, -3, -4
 HS_ERR_HSS_LEAF, HS_ERR_DEVICE, HS_ERR_NOMEM, HS_ERR_UNSUPPORTED = -5, -6, -7, -8
-HS_BLK_LU, HS_BLK_LBI, HS_BLK_UIB, HS_BLK_S = 0, 1, 2, 3
+HS_BLK_LU, HS_BLK_LBI, HS_BLK_UIB, HS_BLK_S, HS_BLK_DLU = 0, 1, 2, 3, 4
 
 # every symbol include/*.h declares (tests check the library exports all of them)
 EXPORTS = [
     "hs_options_default", "hs_factor_d", "hs_factor_z", "hs_ldiv_d", "hs_ldiv_z", "hs_ldiv_dev_d", "hs_ldiv_dev_z",
     "hs_ldiv_t_d", "hs_ldiv_t_z", "hs_ldiv_dev_t_d", "hs_ldiv_dev_t_z",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
+    "hs_logabsdet", "hs_selinv", "hs_selinv_info",
     "hs_maxrank", "hs_is_complex", "hs_size", "hs_free", "hs_last_error", "hs_last_error_info", "hs_get_stats",
     "hs_node_info", "hs_node_ranks", "hs_node_export", "hs_node_export_piv", "hs_device_info",
     "hs_analyze", "hs_plan", "hs_numeric_begin", "hs_numeric_levels", "hs_numeric_end", "hs_solve_fwd_levels", "hs_solve_bwd_levels",
@@ -149,6 +150,12 @@ def lib():
     for f in (L.hs_ldiv_refine_dev_d, L.hs_ldiv_refine_dev_z):
         f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, i64, p_f64, p_f64, p_i64, vp]
         f.restype = C.c_int
+    L.hs_logabsdet.argtypes = [vp, p_f64, p_f64]
+    L.hs_logabsdet.restype = C.c_int
+    L.hs_selinv.argtypes = [vp, C.c_int, vp, vp, C.c_int, i64, vp]
+    L.hs_selinv.restype = C.c_int
+    L.hs_selinv_info.argtypes = [vp, p_f64]
+    L.hs_selinv_info.restype = C.c_int
     L.hs_analyze.argtypes = [C.c_int, i64, p_i64, p_i64, C.POINTER(hs_tree), C.POINTER(hs_options), i64, i64, C.POINTER(vp)]
     L.hs_analyze.restype = C.c_int
     L.hs_plan.argtypes = [C.c_int, i64, C.POINTER(hs_tree), C.POINTER(hs_options), i64, i64, C.POINTER(vp)]

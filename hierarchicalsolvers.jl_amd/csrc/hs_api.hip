@@ -30,6 +30,7 @@
 #include "../../include/hs_hss.h"
 #include "hs_common.h"
 #include "hs_condest.h"
+#include "hs_selinv.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -280,6 +281,8 @@ struct hs_handle {
   hs_stats stats;
   void* cx = nullptr;  // hs_condest.hip: the CSR map of A, built by the first call that needs rows of A
   void (*cx_free)(void*) = nullptr;
+  void* sx = nullptr;  // hs_selinv.hip: the entry lists of A's pattern per front, the figures of the last hs_selinv call
+  void (*sx_free)(void*) = nullptr;
 };
 
 static inline int rup(int x, int a) { return (x + a - 1) / a * a; }
@@ -356,6 +359,7 @@ static void free_handle(hs_handle* h) {
   if (!h) return;
   if (h->stream) (void)hipStreamSynchronize(h->stream);  // recycled blocks must be idle when they go back to the caches
   if (h->cx && h->cx_free) h->cx_free(h->cx);
+  if (h->sx && h->sx_free) h->sx_free(h->sx);
   for (auto& x : h->nodes)
     if (x.S_hss) {
       hs_hss_free((hs_hss*)x.S_hss);
@@ -1723,6 +1727,74 @@ void hs_handle_view(hs_handle* h, HsHandleView* v) {
 }
 int hs_handle_flow_check(hs_handle* h) { HS_GUARD(flow_check(h)); }
 
+// the handle as hs_selinv.hip sees it (hs_selinv.h): the owned fronts in post-order with the blocks their pivoted LU lives in
+void hs_selinv_view(hs_handle* h, HsSelView* v) {
+  *v = HsSelView();
+  v->n = h->n;
+  v->nnz = h->nnz;
+  v->is_complex = h->is_complex ? 1 : 0;
+  v->factored = h->factored ? 1 : 0;
+  v->device = h->d_nodes ? 1 : 0;
+  v->nranks = h->nranks;
+  v->stream = h->stream;
+  v->sx = &h->sx;
+  v->sx_free = &h->sx_free;
+  if (!v->device) return;
+  v->fidx_host = h->fidx_host.data();
+  v->colptr = h->d_colptr;
+  v->rowval = h->d_rowval;
+  const size_t esz = h->is_complex ? sizeof(cplx) : sizeof(double);
+  bool sb_idle = !h->sb_kept && h->d_sb && h->nranks == 1;
+  v->fronts.resize((size_t)h->nnodes);
+  for (int i = 0; i < h->nnodes; ++i) {
+    const NodeH& x = h->nodes[(size_t)i];
+    HsSelFront& f = v->fronts[(size_t)i];
+    f.parent = x.parent;
+    f.level = x.level;
+    f.ni = x.ni;
+    f.nb = x.nb;
+    if (x.ext_sb) sb_idle = false;
+    if (x.hssd || (x.mf && !x.mfd)) f.flags |= HS_SEL_NOLU;
+    if (x.compressed || x.mf) f.flags |= HS_SEL_LOWRANK;
+    if (x.kind != 0) f.flags |= HS_SEL_SLICE;
+    const char* fac = (const char*)h->d_fac;
+    if (x.mf) {
+      f.LU = x.mfd_LF;
+      f.ldlu = x.mfd_ldl;
+    } else if (x.cfront) {
+      f.LU = fac + x.off_LFc * esz;
+      f.ldlu = x.ldc;
+    } else {
+      f.LU = fac + x.off_LF * esz;
+      f.ldlu = x.ldl;
+      f.UR = fac + x.off_UR * esz;
+      f.ldu = x.ldu;
+    }
+    f.inv256L = (const char*)h->d_inv + x.off_inv256 * esz;
+    f.inv256U = (const char*)f.inv256L + (size_t)((x.ni + 255) / 256) * 256 * 256 * esz;
+    f.rperm = h->d_int + x.off_rperm;
+    f.fidx = h->d_int + x.off_fidx;
+    f.off_fidx_host = x.off_fidx;
+  }
+  if (sb_idle) {
+    v->sb = h->d_sb;
+    v->sb_bytes = h->sb_bytes;
+  }
+}
+void* hs_scratch_take(size_t bytes, const char* what) {
+  bytes = std::max<size_t>(bytes, 256);
+  void* p = arena_take(bytes);
+  if (!p) {
+    try {
+      dmalloc(&p, bytes, what);
+    } catch (const HsError& e) {  // (the callers outside this file carry error codes as plain ints)
+      throw (int)e.code;
+    }
+  }
+  return p;
+}
+void hs_scratch_give(void* p, size_t bytes) { arena_give(p, std::max<size_t>(bytes, 256)); }
+
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
@@ -2070,6 +2142,11 @@ extern "C" int hs_node_info(const hs_handle* F, int64_t node, int64_t* ni, int64
 template <class T>
 static void export_block(const hs_handle* F, const NodeH& x, int which, T* out) {
   if (!x.mine) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: node is owned by rank %d", x.owner);
+  if (which == HS_BLK_DLU && x.mf && x.mfd && !x.hssd && x.mfd_LF) {  // a matrix-free front whose D was expanded and eliminated densely: the LU hs_logabsdet reads
+    if (x.ni > 0)
+      HS_HIP(hipMemcpy2D(out, (size_t)x.ni * sizeof(T), x.mfd_LF, (size_t)x.mfd_ldl * sizeof(T), (size_t)x.ni * sizeof(T), x.ni, hipMemcpyDeviceToHost));
+    return;
+  }
   if (x.hssd || x.mf) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "the interior block of this node is an HSS matrix (hs_options.hss_d / mf): it has no dense D, L, R blocks");
   if (x.compressed && (which == HS_BLK_LBI || which == HS_BLK_UIB)) {  // dense reconstruction C*Z of the low-rank transform
     const void* lr = which == HS_BLK_LBI ? x.lrL : x.lrR;
@@ -2081,6 +2158,7 @@ static void export_block(const hs_handle* F, const NodeH& x, int which, T* out) 
   int rows, cols, ld;
   switch (which) {
     case HS_BLK_LU:
+    case HS_BLK_DLU:
       if (x.cfront) { base = (const T*)F->d_fac + x.off_LFc; rows = x.ni; cols = x.ni; ld = x.ldc; break; }
       base = (const T*)F->d_fac + x.off_LF; rows = x.ni; cols = x.ni; ld = x.ldl; break;
     case HS_BLK_LBI: base = (const T*)F->d_fac + x.off_LF + x.ni; rows = x.nb; cols = x.ni; ld = x.ldl; break;

@@ -1,0 +1,87 @@
+// hs_selinv.h -- what hs_selinv.hip (log-determinant, selected inversion) reads from a factorization handle, and the launch API of
+// kernels_selinv.hip.  hs_api.hip owns the handle; hs_selinv_view and the two scratch calls are the whole interface between the files.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <vector>
+
+#include "hs_common.h"
+
+struct hs_handle;
+
+enum {
+  HS_SEL_NOLU = 1,     // D = Aii is kept as an HSS matrix (hss_d, mf = 2, 3): there is no pivoted LU to read
+  HS_SEL_LOWRANK = 2,  // Lbi / Uib live in low-rank objects (compressed front)
+  HS_SEL_SLICE = 4,    // the front is one slice of a split front (hs_options.split)
+};
+
+struct HsSelFront {          // one owned front, every pointer a device pointer
+  int parent = -1;           // index into HsSelView::fronts, -1: root (or pseudo-root)
+  int level = 0, ni = 0, nb = 0;
+  int flags = 0;
+  const void* LU = nullptr;  // pivoted L\U of Aii (ni x ni, ld ldlu); with a dense front Lbi = Abi U^-1 follows below it (rows ni..m)
+  const void* UR = nullptr;  // Uib = L^-1 P Aib (ni x nb, ld ldu); null unless the front is dense
+  int ldlu = 0, ldu = 0;
+  const void* inv256L = nullptr;  // inverses of the 256 x 256 diagonal blocks (ld 256); the factorization leaves them behind for ldiv!
+  const void* inv256U = nullptr;
+  const int* rperm = nullptr;
+  const int* fidx = nullptr;  // m global ids, front order [int; bnd]
+  size_t off_fidx_host = 0;   // the same ids in HsSelView::fidx_host
+};
+
+struct HsSelView {
+  int64_t n = 0, nnz = 0;
+  int is_complex = 0, factored = 0, device = 0, nranks = 1;
+  std::vector<HsSelFront> fronts;  // tree nodes in post-order (children before parents), the pseudo-root last
+  const int* fidx_host = nullptr;
+  const int64_t* colptr = nullptr;  // A's pattern on the device, 0-based
+  const int32_t* rowval = nullptr;
+  void* sb = nullptr;               // the Schur scratch when it is idle (not kept, no buffer of another rank inside), else null
+  size_t sb_bytes = 0;
+  hipStream_t stream = nullptr;
+  void** sx = nullptr;              // cache slot of hs_selinv.hip (entry lists of A's pattern, the last call's figures), freed by hs_free through *sx_free
+  void (**sx_free)(void*) = nullptr;
+};
+
+void hs_selinv_view(hs_handle* h, HsSelView* v);
+// device scratch through the library's arena cache (a parked block of about that size, else hipMalloc with the library's retry); throws on failure
+void* hs_scratch_take(size_t bytes, const char* what);
+void hs_scratch_give(void* p, size_t bytes);
+
+// ---- kernels_selinv.hip ---------------------------------------------------------------------------------------------------------------
+struct LogdetFront {  // input of the log-determinant reduction
+  const void* LU;
+  const int* rperm;
+  int ni, ld;
+};
+struct LogdetOut {  // per front: sum log|u_kk|, sum arg(u_kk) (Float64: pi per negative entry is NOT used -- `neg` counts them), flags
+  double logabs, angle;
+  int neg, odd, zero, pad;  // negative diagonal entries (Float64), parity of the row permutation, exactly zero pivots
+};
+template <class T>
+void launch_logdet(const LogdetFront* df, int nfronts, LogdetOut* out, hipStream_t s);
+
+template <class T>
+struct SelDesc {  // one front of a selected-inversion batch
+  T* Z;           // its m x m block of A^-1, front order [int; bnd]
+  const T* Zp;    // the parent's finished block (null: no boundary to gather)
+  const int* cmap;
+  const int* rperm;
+  const int* fidx;
+  T* Vi;          // ni x ni work block (starts as the identity), ld ldv
+  T* Tm;          // m x ni work block (starts as zero), ld ldz
+  T* X2;          // m x ni: Z[:, int] before the column permutation, ld ldz
+  const int* epr;  // entries of A this front owns: row / column position in the front, index into A's nzval
+  const int* epc;
+  const int64_t* ee;
+  int ecnt;
+  int ni, nb, m, ldz, ldzp, ldv;
+};
+template <class T>
+void launch_zinit(const SelDesc<T>* d, int nbatch, int maxni, hipStream_t s);                 // Vi = I
+template <class T>
+void launch_zgather(const SelDesc<T>* d, int nbatch, int maxnb, hipStream_t s);               // Z[bnd, bnd] = Zp[cmap, cmap]
+template <class T>
+void launch_zpermute_cols(const SelDesc<T>* d, int nbatch, int maxm, int maxni, hipStream_t s);  // Z[:, rperm[i]] = X2[:, i]
+template <class T>
+void launch_zextract(const SelDesc<T>* d, int nbatch, int maxni, int maxe, int trans, T* diag, T* zval, hipStream_t s);

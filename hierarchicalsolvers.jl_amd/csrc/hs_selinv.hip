@@ -1,0 +1,605 @@
+// hs_selinv.hip -- log|det| and selected inversion from the stored factors (include/hs_solver.h: hs_logabsdet, hs_selinv, hs_selinv_info).
+//
+// det.  Every front keeps P Aii = L U, and the Gauss transforms between fronts are unit block-triangular, so
+//   det(F) = prod over fronts of sign(P) * prod diag(U).
+// One grouped launch (logdet_kernel, one workgroup per front) reduces log|u_kk|, the phase and the parity of P per front in a fixed order;
+// the host adds the per-front results in post-order.  Nothing but the diagonals and the permutations is read.
+//
+// Selected inversion (exact factorizations: every front dense).  With Z = A^-1 and Zbb = Z[bnd, bnd] of a front known,
+//   Z[int, bnd] = -R Zbb,   Z[bnd, int] = -Zbb Lm,   Z[int, int] = Aii^-1 + R Zbb Lm,      R = U^-1 Uib,  Lm = Lbi L^-1 P.
+// A child's boundary is a subset of its parent's front, so its Zbb is a gather from the parent's finished block: the tree is walked from
+// the root to the leaves, the fronts of a level batched like the factorization batches them.  Per batch, with m = ni + nb:
+//   Vb  = -Uib Zbb                      (GEMM)            Z[int, bnd] = U^-1 Vb         (blocked back substitution, below)
+//   Vi  = I                                               Tm[int, :]  = U^-1 Vi = U^-1  (the same launches; only the upper triangle is computed)
+//   Tm -= Z[:, bnd] Lbi                 (GEMM, m x ni)    now Tm = [U^-1; 0] - [Zib; Zbb] Lbi
+//   X2  = Tm L^-1                       (blocked substitution from the right)
+//   Z[:, rperm[i]] = X2[:, i]           (zpermute_cols: the trailing P)  -> Z[:, int] = [Zii; Zbi]
+// The triangular solves run over the stored inverses of the 256 x 256 diagonal blocks (inv256L / inv256U, which every factorization leaves
+// behind for ldiv!): per block one product with the inverse and one update product, all of them GemmProb lists for launch_gemm_probs.
+// About 4/3 ni^3 + 4 ni^2 nb + 4 ni nb^2 flops per front.  The stored factors are only read.
+//
+// Memory.  A batch holds the m x m blocks of its fronts and 2 m ni work elements per front (the Schur scratch of the handle serves as work
+// space when it is idle).  A parent batch's blocks live until the last batch of its children has gathered from them; a level that does not
+// fit the byte budget is cut into several batches of fronts, each followed by its own subtree before the next one starts.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <new>
+#include <vector>
+
+#include "../../include/hs_solver.h"
+#include "hs_common.h"
+#include "hs_selinv.h"
+
+namespace {
+
+#define SI_FAIL(code, info, ...)               \
+  do {                                         \
+    hs_set_error((code), (info), __VA_ARGS__); \
+    throw (int)(code);                         \
+  } while (0)
+#define SI_HIP(call)                                                                                                                \
+  do {                                                                                                                              \
+    hipError_t e__ = (call);                                                                                                        \
+    if (e__ != hipSuccess) SI_FAIL(HS_ERR_DEVICE, 0, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
+  } while (0)
+#define SI_GUARD(...)                                        \
+  try {                                                      \
+    __VA_ARGS__;                                             \
+    return HS_OK;                                            \
+  } catch (int code) {                                       \
+    return code;                                             \
+  } catch (const std::bad_alloc&) {                          \
+    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed"); \
+    return HS_ERR_NOMEM;                                     \
+  }
+
+inline int rup2(int x) { return (std::max(x, 1) + 1) / 2 * 2; }
+inline size_t rup32(size_t x) { return (x + 31) / 32 * 32; }
+
+struct DevBuf {  // a device block from the library's arena cache, given back on scope exit
+  void* p = nullptr;
+  size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  void take(size_t b, const char* what) {
+    give();
+    p = hs_scratch_take(b, what);
+    bytes = b;
+  }
+  void give() {
+    if (p) hs_scratch_give(p, bytes);
+    p = nullptr;
+    bytes = 0;
+  }
+  ~DevBuf() { give(); }
+};
+
+// What the first hs_selinv call of a handle builds and keeps: which front owns which stored entry of A, and where every front's boundary
+// sits in its parent's front.  Both depend on the pattern and the tree only.
+struct SelCache {
+  bool built = false;
+  long long hole = -1;      // first stored entry of A (CSC position) that lies in no front's [int; bnd] x [int; bnd] block, -1: none
+  int hole_front = -1;      // first front with a boundary DOF its parent's front does not hold, -1: none
+  std::vector<int64_t> eptr;   // per front: range of its entries in the three arrays below
+  std::vector<size_t> cmoff;   // per front: offset of its cmap
+  int* d_epr = nullptr;
+  int* d_epc = nullptr;
+  int64_t* d_ee = nullptr;
+  int* d_cmap = nullptr;
+  double info[4] = {0, 0, 0, 0};  // last call: seconds, flops, peak scratch bytes, batches
+  ~SelCache() {
+    if (d_epr) (void)hipFree(d_epr);
+    if (d_epc) (void)hipFree(d_epc);
+    if (d_ee) (void)hipFree(d_ee);
+    if (d_cmap) (void)hipFree(d_cmap);
+  }
+};
+void free_cache(void* p) { delete (SelCache*)p; }
+
+SelCache* cache_of(const HsSelView& v) {
+  if (!*v.sx) {
+    *v.sx = new SelCache();
+    *v.sx_free = free_cache;
+  }
+  return (SelCache*)*v.sx;
+}
+
+void build_cache(const HsSelView& v, SelCache* c) {
+  const int nf = (int)v.fronts.size();
+  const int64_t n = v.n, nnz = v.nnz;
+  std::vector<int64_t> cp((size_t)n + 1);
+  std::vector<int32_t> rv((size_t)std::max<int64_t>(nnz, 1));
+  SI_HIP(hipMemcpy(cp.data(), v.colptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (nnz) SI_HIP(hipMemcpy(rv.data(), v.rowval, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+  // the front that eliminates each DOF
+  std::vector<int> elim((size_t)n, -1);
+  for (int f = 0; f < nf; ++f) {
+    const HsSelFront& x = v.fronts[f];
+    const int* ids = v.fidx_host + x.off_fidx_host;
+    for (int i = 0; i < x.ni; ++i) elim[(size_t)ids[i]] = f;
+  }
+  // owner of a stored entry (r, c): the front that eliminates whichever of r, c goes first.  The two fronts lie on one path to the root
+  // when the tree fits the pattern, and the deeper one is eliminated first.
+  std::vector<int> owner((size_t)std::max<int64_t>(nnz, 1), -1);
+  c->eptr.assign((size_t)nf + 1, 0);
+  for (int64_t col = 0; col < n && c->hole < 0; ++col)
+    for (int64_t e = cp[col]; e < cp[col + 1]; ++e) {
+      const int fr = elim[(size_t)rv[e]], fc = elim[(size_t)col];
+      if (fr < 0 || fc < 0 || (fr != fc && v.fronts[fr].level == v.fronts[fc].level)) {
+        c->hole = e;
+        break;
+      }
+      const int o = v.fronts[fr].level >= v.fronts[fc].level ? fr : fc;
+      owner[(size_t)e] = o;
+      c->eptr[(size_t)o + 1]++;
+    }
+  std::vector<int> epr((size_t)std::max<int64_t>(nnz, 1)), epc((size_t)std::max<int64_t>(nnz, 1));
+  std::vector<int64_t> ee((size_t)std::max<int64_t>(nnz, 1));
+  std::vector<int> pos((size_t)n, -1);
+  if (c->hole < 0) {
+    for (int f = 0; f < nf; ++f) c->eptr[(size_t)f + 1] += c->eptr[(size_t)f];
+    std::vector<int64_t> fill(c->eptr.begin(), c->eptr.end() - 1);
+    std::vector<int64_t> ecol((size_t)std::max<int64_t>(nnz, 1));
+    for (int64_t col = 0; col < n; ++col)
+      for (int64_t e = cp[col]; e < cp[col + 1]; ++e) {
+        const int64_t k = fill[(size_t)owner[(size_t)e]]++;
+        ee[(size_t)k] = e;
+        ecol[(size_t)k] = col;
+      }
+    for (int f = 0; f < nf && c->hole < 0; ++f) {
+      const HsSelFront& x = v.fronts[f];
+      const int* ids = v.fidx_host + x.off_fidx_host;
+      const int m = x.ni + x.nb;
+      for (int i = 0; i < m; ++i) pos[(size_t)ids[i]] = i;
+      for (int64_t k = c->eptr[f]; k < c->eptr[(size_t)f + 1]; ++k) {
+        const int pr = pos[(size_t)rv[(size_t)ee[(size_t)k]]], pc = pos[(size_t)ecol[(size_t)k]];
+        if (pr < 0 || pc < 0) {
+          c->hole = ee[(size_t)k];
+          break;
+        }
+        epr[(size_t)k] = pr;
+        epc[(size_t)k] = pc;
+      }
+      for (int i = 0; i < m; ++i) pos[(size_t)ids[i]] = -1;
+    }
+  }
+  // position of every front's boundary in its parent's front, by global id
+  c->cmoff.assign((size_t)nf + 1, 0);
+  for (int f = 0; f < nf; ++f) c->cmoff[(size_t)f + 1] = c->cmoff[(size_t)f] + (size_t)v.fronts[f].nb;
+  std::vector<int> cm(std::max<size_t>(c->cmoff[(size_t)nf], 1), 0);
+  std::vector<std::vector<int>> kids((size_t)nf);
+  for (int f = 0; f < nf; ++f)
+    if (v.fronts[f].parent >= 0) kids[(size_t)v.fronts[f].parent].push_back(f);
+  for (int p = 0; p < nf; ++p) {
+    if (kids[(size_t)p].empty()) continue;
+    const HsSelFront& x = v.fronts[p];
+    const int* ids = v.fidx_host + x.off_fidx_host;
+    const int m = x.ni + x.nb;
+    for (int i = 0; i < m; ++i) pos[(size_t)ids[i]] = i;
+    for (int f : kids[(size_t)p]) {
+      const HsSelFront& y = v.fronts[f];
+      const int* cid = v.fidx_host + y.off_fidx_host + y.ni;
+      for (int a = 0; a < y.nb; ++a) {
+        const int q = pos[(size_t)cid[a]];
+        if (q < 0 && c->hole_front < 0) c->hole_front = f;
+        cm[c->cmoff[(size_t)f] + (size_t)a] = std::max(q, 0);
+      }
+    }
+    for (int i = 0; i < m; ++i) pos[(size_t)ids[i]] = -1;
+  }
+  for (int f = 0; f < nf; ++f)  // only a root may keep a boundary nobody hands it
+    if (v.fronts[f].parent < 0 && v.fronts[f].nb > 0 && c->hole_front < 0) c->hole_front = f;
+  if (c->hole < 0 && c->hole_front < 0) {
+    const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
+    SI_HIP(hipMalloc((void**)&c->d_epr, ne * sizeof(int)));
+    SI_HIP(hipMalloc((void**)&c->d_epc, ne * sizeof(int)));
+    SI_HIP(hipMalloc((void**)&c->d_ee, ne * sizeof(int64_t)));
+    SI_HIP(hipMalloc((void**)&c->d_cmap, cm.size() * sizeof(int)));
+    SI_HIP(hipMemcpy(c->d_epr, epr.data(), ne * sizeof(int), hipMemcpyHostToDevice));
+    SI_HIP(hipMemcpy(c->d_epc, epc.data(), ne * sizeof(int), hipMemcpyHostToDevice));
+    SI_HIP(hipMemcpy(c->d_ee, ee.data(), ne * sizeof(int64_t), hipMemcpyHostToDevice));
+    SI_HIP(hipMemcpy(c->d_cmap, cm.data(), cm.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  c->built = true;
+}
+
+// ---- checks shared by the entry points: everything here happens before any device work ---------------------------------------------
+void check_common(hs_handle* F, HsSelView& v, const char* fn) {
+  if (!F) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
+  hs_selinv_view(F, &v);
+  if (v.nranks > 1)
+    SI_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: the factorization is spread over %d ranks; this call needs all fronts in one process", fn, v.nranks);
+  if (!v.device || !v.factored) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs a completed numeric factorization (the handle is a plan, or hs_numeric_end has not run)", fn);
+  for (size_t i = 0; i < v.fronts.size(); ++i)
+    if (v.fronts[i].flags & HS_SEL_NOLU)
+      SI_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d keeps its interior block D as an HSS matrix (ULV factors; hs_options.hss_d, mf = 2, 3): it has no pivoted LU whose diagonal could be read", fn, (int)i);
+}
+
+// ---- log-determinant ------------------------------------------------------------------------------------------------------------------
+template <class T>
+void logabsdet_impl(const HsSelView& v, double* logabs, double* sign2) {
+  std::vector<LogdetFront> lf;
+  for (const HsSelFront& x : v.fronts)
+    if (x.ni > 0) lf.push_back(LogdetFront{x.LU, x.rperm, x.ni, x.ldlu});
+  const int nf = (int)lf.size();
+  double la = 0.0, ang = 0.0;
+  long long flips = 0;
+  bool zero = false;
+  if (nf > 0) {
+    DevBuf din, dout;
+    din.take(sizeof(LogdetFront) * (size_t)nf, "log-determinant descriptors");
+    dout.take(sizeof(LogdetOut) * (size_t)nf, "log-determinant partial results");
+    std::vector<LogdetOut> out((size_t)nf);
+    SI_HIP(hipStreamSynchronize(v.stream));  // the factors are written on the handle's stream
+    SI_HIP(hipMemcpy(din.p, lf.data(), sizeof(LogdetFront) * (size_t)nf, hipMemcpyHostToDevice));
+    launch_logdet<T>((const LogdetFront*)din.p, nf, (LogdetOut*)dout.p, v.stream);
+    SI_HIP(hipGetLastError());
+    SI_HIP(hipStreamSynchronize(v.stream));
+    SI_HIP(hipMemcpy(out.data(), dout.p, sizeof(LogdetOut) * (size_t)nf, hipMemcpyDeviceToHost));
+    const double twopi = 6.283185307179586476925286766559;
+    for (int i = 0; i < nf; ++i) {  // post-order, always the same
+      la += out[(size_t)i].logabs;
+      ang = std::remainder(ang + std::remainder(out[(size_t)i].angle, twopi), twopi);
+      flips += out[(size_t)i].neg + out[(size_t)i].odd;
+      zero = zero || out[(size_t)i].zero != 0;
+    }
+  }
+  if (zero) {
+    *logabs = -std::numeric_limits<double>::infinity();
+    sign2[0] = sign2[1] = 0.0;
+    return;
+  }
+  *logabs = la;
+  if (sizeof(T) == sizeof(double)) {
+    sign2[0] = (flips & 1) ? -1.0 : 1.0;
+    sign2[1] = 0.0;
+  } else {
+    if (flips & 1) ang += 3.14159265358979323846264338327950288;
+    sign2[0] = std::cos(ang);
+    sign2[1] = std::sin(ang);
+  }
+}
+
+// ---- selected inversion ---------------------------------------------------------------------------------------------------------------
+struct Launch {
+  size_t off;
+  int cnt, maxM, maxN, minus;
+};
+
+template <class T>
+struct SelRun {
+  const HsSelView& v;
+  SelCache* c;
+  hipStream_t s;
+  int trans;
+  T* d_diag;
+  T* d_zval;
+  size_t budget;
+  std::vector<std::vector<int>> kids;
+  size_t alive = 0, peak = 0;
+  double flops = 0.0;
+  int batches = 0;
+  DevBuf work, descs;  // work blocks and descriptors of the current batch (reused, grown on demand)
+
+  struct Batch {
+    std::vector<int> fronts;
+    std::vector<size_t> zoff;  // element offset of every front's block
+    DevBuf Z;
+    int pending = 0;  // batches of children that still have to gather from Z
+  };
+
+  static size_t zelems(const HsSelFront& x) {
+    const int m = x.ni + x.nb;
+    return rup32((size_t)rup2(m) * (size_t)m + 32);
+  }
+  static size_t r1elems(const HsSelFront& x) {
+    const int m = x.ni + x.nb;
+    return rup32(std::max((size_t)rup2(m) * (size_t)x.ni, (size_t)rup2(x.ni) * (size_t)m) + 32);
+  }
+  static size_t r2elems(const HsSelFront& x) { return rup32((size_t)rup2(x.ni + x.nb) * (size_t)x.ni + 32); }
+  static size_t cost(const HsSelFront& x) { return (zelems(x) + r1elems(x) + r2elems(x)) * sizeof(T); }
+
+  void note_alive(long long delta) {
+    alive = (size_t)((long long)alive + delta);
+    peak = std::max(peak, alive);
+  }
+
+  void add(std::vector<GemmProb<T>>& P, const T* A, int lda, const T* B, int ldb, T* C, int ldc, int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return;
+    GemmProb<T> p;
+    p.A = A; p.B = B; p.C = C;
+    p.M = M; p.N = N; p.K = K;
+    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    P.push_back(p);
+    flops += (sizeof(T) == 16 ? 8.0 : 2.0) * (double)M * (double)N * (double)K;
+  }
+
+  // the fronts of one level (all of them children of `parent`'s fronts, or the roots): cut into batches by the budget, every batch followed
+  // by the batches of its own children
+  void run_level(const std::vector<int>& fronts, Batch* parent, const std::vector<size_t>* pzoff_of_front) {
+    std::vector<std::vector<int>> cuts;
+    {
+      const size_t room = budget > alive ? budget - alive : 0;
+      size_t used = 0;
+      for (int f : fronts) {
+        const size_t cst = cost(v.fronts[f]);
+        if (cuts.empty() || (used + cst > room && !cuts.back().empty()) || cuts.back().size() >= 16384) {  // (two GEMM problems per front, grid.y <= 65535)
+          cuts.emplace_back();
+          used = 0;
+        }
+        cuts.back().push_back(f);
+        used += cst;
+      }
+    }
+    if (parent) parent->pending = (int)cuts.size();
+    for (auto& cut : cuts) {
+      Batch b;
+      b.fronts = cut;
+      run_batch(b, parent, pzoff_of_front);
+      if (parent && --parent->pending == 0) {  // (run_batch ended with a synchronisation: the gathers are done)
+        note_alive(-(long long)parent->Z.bytes);
+        parent->Z.give();
+      }
+      std::vector<int> ch;
+      for (int f : b.fronts)
+        for (int k : kids[(size_t)f]) ch.push_back(k);
+      if (ch.empty()) {
+        note_alive(-(long long)b.Z.bytes);
+        b.Z.give();
+      } else {
+        std::vector<size_t> zof(v.fronts.size(), 0);
+        for (size_t i = 0; i < b.fronts.size(); ++i) zof[(size_t)b.fronts[i]] = b.zoff[i];
+        run_level(ch, &b, &zof);
+      }
+    }
+  }
+
+  void run_batch(Batch& b, Batch* parent, const std::vector<size_t>* pzoff) {
+    const int nbt = (int)b.fronts.size();
+    ++batches;
+    size_t ztot = 0, wtot = 0;
+    b.zoff.resize((size_t)nbt);
+    std::vector<size_t> woff((size_t)nbt);
+    for (int i = 0; i < nbt; ++i) {
+      const HsSelFront& x = v.fronts[b.fronts[(size_t)i]];
+      b.zoff[(size_t)i] = ztot;
+      ztot += zelems(x);
+      woff[(size_t)i] = wtot;
+      wtot += r1elems(x) + r2elems(x);
+    }
+    b.Z.take(ztot * sizeof(T), "blocks of the selected inverse");
+    note_alive((long long)b.Z.bytes);
+    T* W;
+    if (v.sb && wtot * sizeof(T) <= v.sb_bytes) {
+      W = (T*)v.sb;  // the Schur scratch of the factorization, idle now
+    } else {
+      if (work.bytes < wtot * sizeof(T)) {
+        note_alive(-(long long)work.bytes);
+        work.take(wtot * sizeof(T), "work blocks of the selected inversion");
+        note_alive((long long)work.bytes);
+      }
+      W = (T*)work.p;
+    }
+    peak = std::max(peak, alive + (W == (T*)v.sb ? wtot * sizeof(T) : 0));
+
+    std::vector<SelDesc<T>> D((size_t)nbt);
+    std::vector<GemmProb<T>> P;
+    std::vector<Launch> L;
+    int maxni = 0, maxnb = 0, maxm = 0, maxe = 0, maxblk = 0;
+    for (int i = 0; i < nbt; ++i) {
+      const int f = b.fronts[(size_t)i];
+      const HsSelFront& x = v.fronts[f];
+      SelDesc<T>& d = D[(size_t)i];
+      memset(&d, 0, sizeof d);
+      d.ni = x.ni; d.nb = x.nb; d.m = x.ni + x.nb;
+      d.ldz = rup2(d.m);
+      d.ldv = rup2(d.ni);
+      d.Z = (T*)b.Z.p + b.zoff[(size_t)i];
+      if (parent && x.parent >= 0 && x.nb > 0) {
+        const HsSelFront& px = v.fronts[x.parent];
+        d.Zp = (const T*)parent->Z.p + (*pzoff)[(size_t)x.parent];
+        d.ldzp = rup2(px.ni + px.nb);
+        d.cmap = c->d_cmap + c->cmoff[(size_t)f];
+      }
+      d.rperm = x.rperm;
+      d.fidx = x.fidx;
+      d.Vi = W + woff[(size_t)i];
+      d.X2 = d.Vi;                            // (Vi and Vb are dead when X2 is written)
+      d.Tm = W + woff[(size_t)i] + r1elems(x);
+      d.epr = c->d_epr + c->eptr[(size_t)f];
+      d.epc = c->d_epc + c->eptr[(size_t)f];
+      d.ee = c->d_ee + c->eptr[(size_t)f];
+      d.ecnt = (int)(c->eptr[(size_t)f + 1] - c->eptr[(size_t)f]);
+      maxni = std::max(maxni, d.ni); maxnb = std::max(maxnb, d.nb); maxm = std::max(maxm, d.m); maxe = std::max(maxe, d.ecnt);
+      maxblk = std::max(maxblk, (d.ni + 255) / 256);
+    }
+    auto close = [&](size_t from, int minus) {
+      if (P.size() == from) return;
+      Launch l{from, (int)(P.size() - from), 0, 0, minus};
+      for (size_t k = from; k < P.size(); ++k) {
+        l.maxM = std::max(l.maxM, P[k].M);
+        l.maxN = std::max(l.maxN, P[k].N);
+      }
+      L.push_back(l);
+    };
+    auto each = [&](auto&& body) {
+      for (int i = 0; i < nbt; ++i) {
+        const HsSelFront& x = v.fronts[b.fronts[(size_t)i]];
+        body(D[(size_t)i], x, (const T*)x.LU, (const T*)x.UR, D[(size_t)i].Vi + (size_t)D[(size_t)i].ldv * D[(size_t)i].ni);
+      }
+    };
+    size_t from = P.size();
+    // Vb = -Uib Zbb
+    each([&](SelDesc<T>& d, const HsSelFront& x, const T*, const T* UR, T* Vb) {
+      add(P, UR, x.ldu, d.Z + d.ni + (size_t)d.ni * d.ldz, d.ldz, Vb, d.ldv, d.ni, d.nb, d.nb);
+    });
+    close(from, 1);
+    // [Tm[int, :] | Z[int, bnd]] = U^-1 [Vi | Vb], the last 256-block of every front first
+    for (int st = 0; st < maxblk; ++st) {
+      from = P.size();
+      each([&](SelDesc<T>& d, const HsSelFront& x, const T*, const T*, T* Vb) {
+        const int kb = (d.ni + 255) / 256 - 1 - st;
+        if (kb < 0) return;
+        const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
+        const T* iU = (const T*)x.inv256U + (size_t)kb * 65536;
+        add(P, iU, 256, Vb + k0, d.ldv, d.Z + k0 + (size_t)d.ni * d.ldz, d.ldz, wk, d.nb, wk);
+        add(P, iU, 256, d.Vi + k0 + (size_t)k0 * d.ldv, d.ldv, d.Tm + k0 + (size_t)k0 * d.ldz, d.ldz, wk, d.ni - k0, wk);
+      });
+      close(from, 0);
+      from = P.size();
+      each([&](SelDesc<T>& d, const HsSelFront& x, const T* LU, const T*, T* Vb) {
+        const int kb = (d.ni + 255) / 256 - 1 - st;
+        if (kb <= 0) return;
+        const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
+        const T* U01 = LU + (size_t)k0 * x.ldlu;  // rows 0:k0 of the block column
+        add(P, U01, x.ldlu, d.Z + k0 + (size_t)d.ni * d.ldz, d.ldz, Vb, d.ldv, k0, d.nb, wk);
+        add(P, U01, x.ldlu, d.Tm + k0 + (size_t)k0 * d.ldz, d.ldz, d.Vi + (size_t)k0 * d.ldv, d.ldv, k0, d.ni - k0, wk);
+      });
+      close(from, 1);
+    }
+    // Tm -= Z[:, bnd] Lbi
+    from = P.size();
+    each([&](SelDesc<T>& d, const HsSelFront& x, const T* LU, const T*, T*) {
+      add(P, d.Z + (size_t)d.ni * d.ldz, d.ldz, LU + d.ni, x.ldlu, d.Tm, d.ldz, d.m, d.ni, d.nb);
+    });
+    close(from, 1);
+    // X2 = Tm L^-1
+    for (int st = 0; st < maxblk; ++st) {
+      from = P.size();
+      each([&](SelDesc<T>& d, const HsSelFront& x, const T*, const T*, T*) {
+        const int kb = (d.ni + 255) / 256 - 1 - st;
+        if (kb < 0) return;
+        const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
+        add(P, d.Tm + (size_t)k0 * d.ldz, d.ldz, (const T*)x.inv256L + (size_t)kb * 65536, 256, d.X2 + (size_t)k0 * d.ldz, d.ldz, d.m, wk, wk);
+      });
+      close(from, 0);
+      from = P.size();
+      each([&](SelDesc<T>& d, const HsSelFront& x, const T* LU, const T*, T*) {
+        const int kb = (d.ni + 255) / 256 - 1 - st;
+        if (kb <= 0) return;
+        const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
+        add(P, d.X2 + (size_t)k0 * d.ldz, d.ldz, LU + k0, x.ldlu, d.Tm, d.ldz, d.m, k0, wk);
+      });
+      close(from, 1);
+    }
+
+    const size_t dbytes = sizeof(SelDesc<T>) * (size_t)nbt, pbytes = sizeof(GemmProb<T>) * std::max<size_t>(P.size(), 1);
+    if (descs.bytes < dbytes + pbytes + 256) descs.take(2 * (dbytes + pbytes) + 256, "descriptors of the selected inversion");
+    SelDesc<T>* dD = (SelDesc<T>*)descs.p;
+    GemmProb<T>* dP = (GemmProb<T>*)((char*)descs.p + (dbytes + 255) / 256 * 256);
+    SI_HIP(hipMemcpy(dD, D.data(), dbytes, hipMemcpyHostToDevice));  // (the stream is idle: every batch ends with a synchronisation)
+    if (!P.empty()) SI_HIP(hipMemcpy(dP, P.data(), sizeof(GemmProb<T>) * P.size(), hipMemcpyHostToDevice));
+    SI_HIP(hipMemsetAsync(W, 0, wtot * sizeof(T), s));
+    launch_zinit<T>(dD, nbt, maxni, s);
+    if (parent) launch_zgather<T>(dD, nbt, maxnb, s);
+    for (const Launch& l : L) launch_gemm_probs<T>(dP + l.off, l.cnt, l.maxM, l.maxN, l.minus, s);
+    launch_zpermute_cols<T>(dD, nbt, maxm, maxni, s);
+    launch_zextract<T>(dD, nbt, maxni, maxe, trans, d_diag, d_zval, s);
+    SI_HIP(hipGetLastError());
+    SI_HIP(hipStreamSynchronize(s));
+  }
+};
+
+template <class T>
+void selinv_impl(const HsSelView& v, SelCache* c, int trans, void* diag, void* zval, int where, int64_t budget_bytes, hipStream_t s) {
+  const int nf = (int)v.fronts.size();
+  SI_HIP(hipStreamSynchronize(v.stream));  // the factors are written on the handle's stream
+  DevBuf odiag, ozval;
+  T *d_diag = nullptr, *d_zval = nullptr;
+  if (diag) {
+    if (where) d_diag = (T*)diag;
+    else {
+      odiag.take(sizeof(T) * (size_t)std::max<int64_t>(v.n, 1), "diagonal of the inverse");
+      d_diag = (T*)odiag.p;
+    }
+  }
+  if (zval) {
+    if (where) d_zval = (T*)zval;
+    else {
+      ozval.take(sizeof(T) * (size_t)std::max<int64_t>(v.nnz, 1), "pattern values of the inverse");
+      d_zval = (T*)ozval.p;
+    }
+  }
+  size_t budget = (size_t)std::max<int64_t>(budget_bytes, 0);
+  if (budget == 0) {  // what the device can give right now, with a margin for the allocator
+    size_t fr = 0, tot = 0;
+    SI_HIP(hipMemGetInfo(&fr, &tot));
+    budget = (size_t)((double)fr * 0.85) + (v.sb ? v.sb_bytes : 0);
+  }
+  SelRun<T> R{v, c, s, trans, d_diag, d_zval, budget};
+  R.kids.assign((size_t)nf, {});
+  std::vector<int> roots;
+  for (int f = 0; f < nf; ++f) {
+    if (v.fronts[f].parent >= 0) R.kids[(size_t)v.fronts[f].parent].push_back(f);
+    else roots.push_back(f);
+  }
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  SI_HIP(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    SI_FAIL(HS_ERR_DEVICE, 0, "hipEventCreate failed");
+  }
+  float ms = 0.f;
+  try {
+    SI_HIP(hipEventRecord(e0, s));
+    R.run_level(roots, nullptr, nullptr);
+    SI_HIP(hipEventRecord(e1, s));
+    SI_HIP(hipEventSynchronize(e1));
+    SI_HIP(hipEventElapsedTime(&ms, e0, e1));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);  // nothing may still be reading the blocks the unwinding gives back
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    throw;
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (diag && !where) SI_HIP(hipMemcpy(diag, d_diag, sizeof(T) * (size_t)v.n, hipMemcpyDeviceToHost));
+  if (zval && !where && v.nnz) SI_HIP(hipMemcpy(zval, d_zval, sizeof(T) * (size_t)v.nnz, hipMemcpyDeviceToHost));
+  c->info[0] = ms * 1e-3;
+  c->info[1] = R.flops;
+  c->info[2] = (double)R.peak;
+  c->info[3] = (double)R.batches;
+}
+
+}  // namespace
+
+extern "C" int hs_logabsdet(hs_handle* F, double* logabs, double* sign2) {
+  SI_GUARD(HsSelView v; check_common(F, v, "hs_logabsdet");
+           if (!logabs || !sign2) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_logabsdet: logabs and sign2 must not be NULL");
+           if (v.is_complex) logabsdet_impl<cplx>(v, logabs, sign2); else logabsdet_impl<double>(v, logabs, sign2));
+}
+
+extern "C" int hs_selinv(hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream) {
+  SI_GUARD(HsSelView v; check_common(F, v, "hs_selinv");
+           if (trans != 0 && trans != 1) SI_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_selinv: trans = %d must be 0 (entries of A^-1) or 1 (of its transpose)", trans);
+           if (where != 0 && where != 1) SI_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: hs_selinv: where = %d must be 0 (host pointers) or 1 (device pointers)", where);
+           if (!diag && !zval) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_selinv: diag and zval are both NULL, nothing to compute");
+           if (budget_bytes < 0) SI_FAIL(HS_ERR_ARGUMENT, budget_bytes, "ArgumentError: hs_selinv: budget_bytes < 0");
+           for (size_t i = 0; i < v.fronts.size(); ++i) {
+             const int fl = v.fronts[i].flags;
+             if (fl & HS_SEL_LOWRANK)
+               SI_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_selinv: front %d keeps low-rank Gauss transforms L / R (compressed factorization); selected inversion needs the exact path (swlevel = 0)", (int)i);
+             if (fl & HS_SEL_SLICE)
+               SI_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_selinv: front %d is eliminated in slices (hs_options.split)", (int)i);
+           }
+           SelCache* c = cache_of(v);
+           if (!c->built) build_cache(v, c);  // (host work and uploads of index lists only)
+           if (c->hole >= 0)
+             SI_FAIL(HS_ERR_UNSUPPORTED, c->hole, "hs_selinv: stored entry %lld of A (CSC order) lies outside every front's [int; bnd] block: the tree does not cover A's pattern, the pattern values of the inverse would have a hole", c->hole);
+           if (c->hole_front >= 0)
+             SI_FAIL(HS_ERR_UNSUPPORTED, c->hole_front, "hs_selinv: the boundary of front %d is not contained in its parent's front (a root that keeps a boundary without a pseudo-root, or an inconsistent tree)", c->hole_front);
+           hipStream_t s = stream ? (hipStream_t)stream : v.stream;
+           if (v.is_complex) selinv_impl<cplx>(v, c, trans, diag, zval, where, budget_bytes, s);
+           else selinv_impl<double>(v, c, trans, diag, zval, where, budget_bytes, s));
+}
+
+extern "C" int hs_selinv_info(const hs_handle* F, double* out4) {
+  SI_GUARD(if (!F || !out4) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_selinv_info: null argument");
+           HsSelView v; hs_selinv_view(const_cast<hs_handle*>(F), &v);
+           const SelCache* c = (const SelCache*)*v.sx;
+           for (int k = 0; k < 4; ++k) out4[k] = c ? c->info[k] : 0.0);
+}

@@ -12,6 +12,8 @@ reference (Julia)                      here
 ``opnorm(A, p)``, ``opnormestinv(A)``  :func:`opnorm`, :func:`opnormestinv` (on the factorization's A and F; ``hs_condest.hip``)
 ``cond(A, p)`` (estimated)             :func:`condest`
 ``xGERFS`` (refine, berr, ferr)        :func:`ldiv_refine`
+``logabsdet(F)``, ``logdet``, ``det``  :func:`logabsdet`, :func:`logdet`, :func:`det` (``hs_selinv.hip``)
+selected inverse (no Julia name)       :func:`selinv`, :func:`selinv_diag`: ``diag(A^-1)`` and ``A^-1`` on the pattern of ``A``
 ``F \\ b``                              ``F.solve(b)``
 =====================================  ====================================================
 
@@ -28,7 +30,7 @@ from . import _lib
 from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
-           "ldiv_refine"]
+           "ldiv_refine", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info"]
 
 
 class SolverOptions:
@@ -137,6 +139,7 @@ class FactorNode:
         self.dtype = np.dtype(dtype)
         self.n = int(n)
         self._flat = flat
+        self._pattern = None  # (indptr, indices) of the factored matrix, CSC with sorted indices: the order of hs_selinv's pattern values
 
     def __del__(self):
         self.free()
@@ -204,6 +207,17 @@ class FactorNode:
             _lib.check(L.hs_node_export_piv(self._h, node, _p64(rp)))
         out["rperm"] = rp
         return out
+
+    def node_lu(self, node):
+        """``(LU, rperm)`` of one front's interior block wherever it keeps a dense pivoted LU -- also a matrix-free front with a densely
+        eliminated ``D`` (``mf=True``), which exports no other block (``HS_BLK_DLU``)."""
+        ni, _, _ = self.node_info(node)
+        LU = np.zeros((ni, ni), dtype=self.dtype, order="F")
+        rp = np.zeros(ni, dtype=np.int64)
+        if ni:
+            _lib.check(_lib.lib().hs_node_export(self._h, node, _lib.HS_BLK_DLU, LU.ctypes.data_as(_lib.p_f64)))
+            _lib.check(_lib.lib().hs_node_export_piv(self._h, node, _p64(rp)))
+        return LU, rp
 
     def schur_hss(self, node, **kw):
         """``F.S`` of one node as an :class:`hss.HssMatrix` (``compress(S[perm,perm], cl, cl)``, factorization.jl:56-57,109-110;
@@ -273,7 +287,9 @@ def factor(A, nd, nd_loc, opts=None, **kw):
     fn = L.hs_factor_z if is_c else L.hs_factor_d
     st = fn(n, _p64(colptr), _p64(rowval), nzval.ctypes.data_as(_lib.p_f64), C.byref(t), C.byref(co), C.byref(h))
     _lib.check(st)
-    return FactorNode(h, dtype, n, flat)
+    F = FactorNode(h, dtype, n, flat)
+    F._pattern = (A.indptr.copy(), A.indices.copy())
+    return F
 
 
 factorize = factor  # BASELINE.json's north star uses this name
@@ -460,3 +476,74 @@ def ldiv_refine(F, B, itmax=5, ferr=True):
     if vec:
         return X[:, 0], float(be[0]), (float(fe[0]) if ferr else None), int(st[0])
     return X, be, fe, st
+
+
+def logabsdet(F):
+    """``LinearAlgebra.logabsdet(F) -> (log|det F|, sign)`` from the diagonals and row permutations of the stored LU factors
+    (``hs_logabsdet``); ``sign`` is ``+-1.0`` for Float64 and a unit complex number for ComplexF64 (``0`` with ``-inf`` for an exactly
+    singular pivot).  ``transpose(F)`` has the same determinant, ``adjoint(F)`` the conjugate.  For a compressed factorization this is the
+    determinant of ``F``, which approximates that of ``A`` only as well as ``F`` approximates ``A``."""
+    F, trans = _unwrap(F)
+    la = C.c_double()
+    sg = np.zeros(2)
+    _lib.check(_lib.lib().hs_logabsdet(F._h, C.byref(la), _pf64(sg)))
+    if F.dtype.kind == "c":
+        sign = complex(sg[0], -sg[1] if trans == 2 else sg[1])
+    else:
+        sign = float(sg[0])
+    return la.value, sign
+
+
+def logdet(F):
+    """``LinearAlgebra.logdet(F)``: ``log(det(F))``; for Float64 a negative determinant raises ``ValueError`` (Julia's ``DomainError``),
+    for ComplexF64 the complex logarithm with the imaginary part in ``(-pi, pi]``."""
+    la, sign = logabsdet(F)
+    if isinstance(sign, complex):
+        return complex(la, np.angle(sign)) if sign != 0 else complex(la, 0.0)
+    if sign < 0:
+        raise ValueError("DomainError: the determinant is negative; logdet of a real factorization needs det > 0 (use logabsdet)")
+    return la
+
+
+def det(F):
+    """``LinearAlgebra.det(F) = sign * exp(log|det F|)`` (over- and underflows like Julia's)."""
+    la, sign = logabsdet(F)
+    return sign * np.exp(la)
+
+
+def selinv(F, diag=True, pattern=True, budget=0):
+    """Selected inverse of an exact factorization (``hs_selinv``): ``(diag(A^-1), Z)`` with ``Z`` a ``scipy.sparse.csc_matrix`` that has
+    ``A``'s ``indptr / indices`` and ``Z[i, j] = (A^-1)[i, j]`` on them -- computed from the stored factors front by front, root to
+    leaves, without the dense inverse.  ``diag=False`` / ``pattern=False`` return ``None`` in that place.  ``budget``: bytes of device
+    scratch alive at a time (0: what the device has free).  ``transpose(F)`` / ``adjoint(F)`` give the selected inverse of ``A^T`` /
+    ``A^H`` on the pattern of ``A`` (``Z[i, j] = (A^-1)[j, i]``, conjugated for the adjoint).  Compressed factorizations are refused
+    (``UnsupportedError``)."""
+    F, trans = _unwrap(F)
+    if not diag and not pattern:
+        raise ValueError("ArgumentError: selinv with diag=False and pattern=False computes nothing")
+    d = np.zeros(F.n, dtype=F.dtype) if diag else None
+    z = None
+    if pattern:
+        if F._pattern is None:
+            raise ValueError("ArgumentError: this FactorNode does not know the pattern of its matrix")
+        z = np.zeros(len(F._pattern[1]), dtype=F.dtype)
+    _lib.check(_lib.lib().hs_selinv(F._h, 1 if trans else 0, d.ctypes.data if diag else None, z.ctypes.data if pattern else None, 0, int(budget), None))
+    if trans == 2 and F.dtype.kind == "c":
+        d = d.conj() if diag else None
+        z = z.conj() if pattern else None
+    Z = sp.csc_matrix((z, F._pattern[1].copy(), F._pattern[0].copy()), shape=(F.n, F.n)) if pattern else None
+    return d, Z
+
+
+def selinv_diag(F, budget=0):
+    """``diag(A^-1)`` (marginal variances of a GMRF with precision ``A``, the diagonal of a Green's function) by :func:`selinv`."""
+    return selinv(F, diag=True, pattern=False, budget=budget)[0]
+
+
+def selinv_info(F):
+    """Figures of the last :func:`selinv` call on ``F`` (``hs_selinv_info``): device seconds, real flops executed, peak scratch bytes,
+    batches of fronts."""
+    F, _ = _unwrap(F)
+    out = np.zeros(4)
+    _lib.check(_lib.lib().hs_selinv_info(F._h, _pf64(out)))
+    return dict(seconds=float(out[0]), flops=float(out[1]), peak_bytes=float(out[2]), batches=int(out[3]))

@@ -8,6 +8,7 @@
  *   ldiv!(C, F, B), ldiv!(F, B)        (reference src/factornode.jl:62-74)
  *   ldiv!(C, transpose(F), B), ldiv!(C, adjoint(F), B)   (hs_ldiv_t_*, hs_ldiv_dev_t_*)
  *   opnorm(A, p), opnormestinv(A), cond(A, p), refined solves (xGERFS)   (hs_opnorm, hs_normestinv, hs_condest, hs_ldiv_refine_*)
+ *   logabsdet(F), logdet(F), det(F), selected inverse (diag(A^-1), A^-1 on A's pattern)   (hs_logabsdet, hs_selinv)
  *   maxrank(F)                         (reference src/factornode.jl:49-57)
  *
  * The reference has no FFI of its own (it is pure Julia); these entry points
@@ -176,6 +177,31 @@ int hs_ldiv_refine_dev_d(hs_handle* F, int trans, double* dX, int64_t ldx, const
 int hs_ldiv_refine_dev_z(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                          double* berr, double* ferr, int64_t* steps, void* stream);
 
+/* ---- log-determinant and selected inversion from the stored factors (hs_selinv.hip) ----------------------------------------------
+ * LinearAlgebra.logabsdet(F): *logabs = log|det F|, sign2 = {re, im} of det F / |det F| ({+-1, 0} for Float64); an exactly zero pivot gives
+ * logabs = -Inf, sign = 0.  det F = prod over fronts of sign(P) prod diag(U) of the pivoted LU of every front's interior block; one grouped
+ * launch reads the n diagonal entries and the n permutation entries, every reduction runs in a fixed order (two calls return the same bits).
+ * Compressed factorizations (swlevel > 0) whose fronts keep a dense or compact LU of D are supported and return logabsdet(F), which
+ * approximates A's only as well as F approximates A.  Refused with HS_ERR_UNSUPPORTED before any device work: fronts that keep D as an HSS
+ * matrix (hs_options.hss_d, mf = 2, 3), factorizations over more than one rank. */
+int hs_logabsdet(hs_handle* F, double* logabs, double* sign2);
+/* Selected inverse of an exact factorization (swlevel = 0): diag (n elements of T, or NULL) = diag(A^-1); zval (nnz(A) elements of T in A's
+ * CSC order, or NULL) = (A^-1)_ij for every stored entry (i, j) of A (trans = 0) or (A^-1)_ji (trans = 1: the selected inverse of A^T on
+ * A's pattern).  where: 0 host pointers, 1 device pointers.  The tree is walked from the root to the leaves; per front
+ * Z[int, bnd] = -R Zbb, Z[bnd, int] = -Zbb Lm, Z[int, int] = Aii^-1 + R Zbb Lm with Zbb gathered from the parent's block, as grouped GEMMs
+ * over the stored factors and the stored inverses of their 256 x 256 diagonal blocks; about three factorizations' worth of flops.  The
+ * factors are only read.  budget_bytes bounds the scratch alive at a time (0: derived from hipMemGetInfo at call time): a level that does
+ * not fit is processed in several batches of fronts.  The first call builds, on the host, the list of A's entries every front owns and
+ * keeps it in the handle.  Work runs on `stream` (NULL: the handle's); the call returns when the results are complete.
+ * Refused with HS_ERR_UNSUPPORTED before any device work: what hs_logabsdet refuses; any front with low-rank Gauss transforms L / R (see
+ * hs_flow_info) or eliminated in slices (hs_options.split); a pattern with a stored entry outside every front's [int; bnd] x [int; bnd]
+ * block (a tree that does not cover A's pattern -- no value is returned with a hole).  A root that keeps a boundary is an ordinary front
+ * under the handle's pseudo-root and is supported.  A handle that is only planned or not yet factored, trans not in 0:1, where not in 0:1,
+ * diag == zval == NULL: HS_ERR_ARGUMENT. */
+int hs_selinv(hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream);
+/* the last hs_selinv call of the handle: out4 = {seconds on the device, flops executed (real), peak scratch bytes, batches of fronts} */
+int hs_selinv_info(const hs_handle* F, double* out4);
+
 /* ---- phased form of factor (hs_factor_* = hs_analyze + hs_numeric_* over all levels) -------------------------
  * hs_analyze builds the plan and uploads the sparsity pattern, so a later numeric factorization starts with
  * every input resident in HBM; the pattern (colptr, rowval, tree) is reused for new values of A.
@@ -307,10 +333,12 @@ int hs_node_info(const hs_handle* F, int64_t node, int64_t* ni, int64_t* nb, int
  *   HS_BLK_LBI : nb x ni   Abi * U^{-1}
  *   HS_BLK_UIB : ni x nb   L^{-1} * P * Aib
  *   HS_BLK_S   : nb x nb   Schur complement in the node's own bnd order (needs opts.keep_schur)
+ *   HS_BLK_DLU : ni x ni   the same packed L\U wherever D has one: also for a matrix-free front (hs_options.mf = 1) whose D was expanded
+ *                         and eliminated densely and which exports no other block (what hs_logabsdet reads; with hs_node_export_piv)
  * out must hold rows*cols elements of T (2 doubles per element for complex).
  *   hs_node_export_piv: ni int64 values, 0-based row permutation p with (P*x)[i] = x[p[i]].
  * From these: D = P'LU, L = Lbi*L^{-1}*P, R = U^{-1}*Uib  (FactorNode fields, factornode.jl:7-12). */
-enum { HS_BLK_LU = 0, HS_BLK_LBI = 1, HS_BLK_UIB = 2, HS_BLK_S = 3 };
+enum { HS_BLK_LU = 0, HS_BLK_LBI = 1, HS_BLK_UIB = 2, HS_BLK_S = 3, HS_BLK_DLU = 4 };
 int hs_node_export(const hs_handle* F, int64_t node, int which, double* out);
 int hs_node_export_piv(const hs_handle* F, int64_t node, int64_t* out);
 
