@@ -31,6 +31,7 @@
 #include "hs_common.h"
 #include "hs_condest.h"
 #include "hs_selinv.h"
+#include "hs_solve_multi.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -283,6 +284,8 @@ struct hs_handle {
   void (*cx_free)(void*) = nullptr;
   void* sx = nullptr;  // hs_selinv.hip: the entry lists of A's pattern per front, the figures of the last hs_selinv call
   void (*sx_free)(void*) = nullptr;
+  void* mx = nullptr;  // hs_solve_multi.hip: the work blocks of the block solves, the figures of the last hs_ldiv_block_* call
+  void (*mx_free)(void*) = nullptr;
 };
 
 static inline int rup(int x, int a) { return (x + a - 1) / a * a; }
@@ -360,6 +363,7 @@ static void free_handle(hs_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);  // recycled blocks must be idle when they go back to the caches
   if (h->cx && h->cx_free) h->cx_free(h->cx);
   if (h->sx && h->sx_free) h->sx_free(h->sx);
+  if (h->mx && h->mx_free) h->mx_free(h->mx);
   for (auto& x : h->nodes)
     if (x.S_hss) {
       hs_hss_free((hs_hss*)x.S_hss);
@@ -1699,6 +1703,92 @@ static void ldiv_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB,
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// ldiv!(C, F, B) for a block of right-hand sides, the factors read once per chunk of columns (hs_solve_multi.hip)
+// ------------------------------------------------------------------------------------------------
+// the handle as hs_solve_multi.hip sees it (hs_solve_multi.h): per level the solve descriptors the single-vector sweeps read, and the
+// low-rank objects of the fronts solve_lr_fwd / solve_lr_bwd serve
+void hs_multi_view(hs_handle* h, HsMultiView* v) {
+  *v = HsMultiView();
+  v->n = h->n;
+  v->mx = &h->mx;
+  v->mx_free = &h->mx_free;
+  const size_t ssz = h->is_complex ? sizeof(SolveNode<cplx>) : sizeof(SolveNode<double>);
+  v->levels.resize(h->levels.size());
+  for (size_t lv = 0; lv < h->levels.size(); ++lv) {
+    const LevelH& L = h->levels[lv];
+    HsMultiLevel& M = v->levels[lv];
+    if (L.mine.empty() || L.maxni == 0 || !h->d_solve) continue;
+    M.sn = (const char*)h->d_solve + L.desc_off * ssz;
+    M.nfronts = (int)L.mine.size();
+    M.maxni = L.maxni;
+    M.maxnb = 0;
+    long long lo = -1, hi = 0;
+    for (int id : L.mine) {
+      const NodeH& x = h->nodes[id];
+      const bool lowrank = x.compressed || x.mf;
+      M.fronts.push_back({x.ni, x.nb, lowrank ? 0 : 1});
+      M.maxnb = std::max(M.maxnb, x.nb);
+      if (x.ni > 0) {
+        lo = lo < 0 ? x.woff : std::min(lo, x.woff);
+        hi = std::max(hi, x.woff + x.ni);
+      }
+      v->wtotal = std::max(v->wtotal, x.woff + x.ni);
+      v->sum_fac += (double)x.ni * x.ni + 2.0 * x.ni * x.nb;
+      if ((x.compressed || x.mfd) && (x.lrL || x.lrR)) M.lr.push_back({x.lrL, x.lrR, x.woff, x.batch_pos});
+    }
+    M.wbase = std::max(lo, 0LL);
+    M.wrows = std::max(hi - M.wbase, 0LL);
+  }
+}
+// everything hs_ldiv_block_* refuses, before any device work and before C is written
+static void check_solve_block(hs_handle* h, int trans, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
+  check_handle(h);
+  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_ldiv_block_*: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", trans);
+  if (trans != 0) HS_FAIL(HS_ERR_UNSUPPORTED, trans, "hs_ldiv_block_*: transposed and adjoint block solves are not implemented (trans must be 0; hs_ldiv_t_* solves column by column)");
+  check_solve_args(h, cplx, ldc, ldb, n, nrhs);
+  if (h->nranks > 1) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "hs_ldiv_block_*: block solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", h->nranks);
+  for (size_t i = 0; i < h->nodes.size(); ++i) {
+    const NodeH& x = h->nodes[i];
+    if (x.mine && (x.hssd || (x.mf && !x.mfd)))
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_ldiv_block_*: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): block solves are not implemented", (int)i);
+  }
+}
+template <class T>
+static void ldiv_block_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  check_solve_block(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs);
+  if (nrhs == 0) return;
+  if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_*: null block");
+  hipStream_t s = h->stream;
+  HsMultiView v;
+  hs_multi_view(h, &v);
+  const size_t bytes = (size_t)n * nrhs * sizeof(T);
+  T* d = (T*)hs_scratch_take(bytes, "block solve right-hand sides");
+  try {  // the whole block goes up and comes down once
+    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
+    hs_solve_multi_run<T>(v, d, n, nrhs, s);
+    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    hs_scratch_give(d, bytes);
+    throw;
+  }
+  hs_scratch_give(d, bytes);
+  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
+}
+template <class T>
+static void ldiv_block_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  check_solve_block(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs);
+  if (nrhs == 0) return;
+  if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_dev_*: null block");
+  hipStream_t s = (hipStream_t)stream;
+  HsMultiView v;
+  hs_multi_view(h, &v);
+  if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
+  hs_solve_multi_run<T>(v, dC, ldc, nrhs, s);
+}
+
 // the handle as hs_condest.hip sees it (hs_condest.h)
 void hs_handle_view(hs_handle* h, HsHandleView* v) {
   *v = HsHandleView();
@@ -1915,6 +2005,23 @@ extern "C" int hs_ldiv_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc,
 }
 extern "C" int hs_ldiv_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   HS_GUARD(ldiv_dev_t<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
+}
+
+extern "C" int hs_ldiv_block_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  HS_GUARD(ldiv_block_host<double>(F, trans, C, ldc, B, ldb, n, nrhs));
+}
+extern "C" int hs_ldiv_block_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  HS_GUARD(ldiv_block_host<cplx>(F, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
+}
+extern "C" int hs_ldiv_block_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  HS_GUARD(ldiv_block_dev<double>(F, trans, dC, ldc, dB, ldb, n, nrhs, stream));
+}
+extern "C" int hs_ldiv_block_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  HS_GUARD(ldiv_block_dev<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
+}
+extern "C" int hs_ldiv_block_info(const hs_handle* F, double* out6) {
+  HS_GUARD(if (!F || !out6) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_info: null argument");
+           hs_solve_multi_info(F->mx, out6));
 }
 
 extern "C" int hs_solve_fwd_levels(hs_handle* h, void* d_b, int64_t lv_from, int64_t lv_to, void* stream) {

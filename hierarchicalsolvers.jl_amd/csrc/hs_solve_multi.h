@@ -1,0 +1,92 @@
+// hs_solve_multi.h -- the blocked multi-right-hand-side ldiv! (hs_ldiv_block_*): what hs_solve_multi.hip reads from a factorization handle
+// and the launch API of kernels_solve_multi.hip.  hs_api.hip owns the handle and checks the arguments; hs_multi_view and the two scratch calls
+// of hs_selinv.h are the whole interface between the files.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <vector>
+
+#include "hs_common.h"
+
+struct hs_handle;
+
+struct HsMultiLR {            // a front whose Gauss transforms are low-rank (compressed front, or mf = 1 with dense D)
+  const void* lrL = nullptr;  // LowRank<T>* of Lbi (nb x ni), null: none
+  const void* lrR = nullptr;  // LowRank<T>* of Uib (ni x nb)
+  long long woff = 0;         // its ni-segment in the work blocks
+  int pos = 0;                // its index in the level's SolveNode array
+};
+struct HsMultiFront {  // host copy of what the flop count and the boundary work block need
+  int ni = 0, nb = 0, dense_bnd = 0;
+};
+struct HsMultiLevel {
+  const void* sn = nullptr;  // SolveNode<T>[] of the level's fronts (device)
+  int nfronts = 0, maxni = 0, maxnb = 0;
+  long long wbase = 0, wrows = 0;  // the level's range of ni-segments: [wbase, wbase + wrows)
+  std::vector<HsMultiFront> fronts;
+  std::vector<HsMultiLR> lr;
+};
+struct HsMultiView {
+  int64_t n = 0;
+  long long wtotal = 0;              // sum of ni over every front
+  double sum_fac = 0.0;              // sum over fronts of ni^2 + 2 ni nb
+  std::vector<HsMultiLevel> levels;  // index = level (0 = root / pseudo-root)
+  void** mx = nullptr;               // cache slot of hs_solve_multi.hip (work blocks, the last call's figures), freed by hs_free through *mx_free
+  void (**mx_free)(void*) = nullptr;
+};
+void hs_multi_view(hs_handle* h, HsMultiView* v);
+
+// C[:, 0:nrhs] = F^-1 C[:, 0:nrhs] in place on the device (ld ldc), chunk by chunk, on stream s; events around the launches
+template <class T>
+void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s);
+double hs_solve_multi_seconds(void* mx);  // waits for the last block solve and returns its device seconds
+void hs_solve_multi_info(void* mx, double* out6);
+int hs_ldiv_block_cols();  // KC: columns per chunk (HS_LDIV_BLOCK_COLS = 16 / 32 / 48 / 64, default 32)
+
+// ---- kernels_solve_multi.hip ----------------------------------------------------------------------------------------------------------
+// One tall-skinny product  D = A X  or  D = Cin - A X  with A (M x K, column-major, a stored factor panel) read once and fed to
+// v_mfma_f64_16x16x4_f64 from registers.  X (K x kc, kc <= 64), Cin and D are rows of row-major work blocks (one pitch for all columns).
+template <class T>
+struct MultiProb {
+  const T* A;
+  int lda, M, K;
+  int trap;  // 1: A is the unit lower trapezoid of what is stored (LowRank::Lp)
+  const T* X;
+  long long xrs;    // X(k, c) = X[k * xrs + c]
+  const T* Cin;     // null: D = A X; else D = Cin - A X, addressed like C
+  T* C;
+  long long crs;    // D(i, c) -> C[(cmap ? cmap[i] : i) * crs + c]
+  const int* cmap;
+};
+enum {
+  HSM_DIAG_L = 0,  // Y_j = inv256L_j W_j                         (W: work block 1, Y: work block 2)
+  HSM_BELOW_L,     // W[rows below block j] -= L[below, j] Y_j    (interior rows)
+  HSM_BND_L,       // Xb -= Lbi Y                                 (Xb: the gathered boundary rows B[bnd, :])
+  HSM_UR,          // W = Y - Uib Xb
+  HSM_DIAG_U,      // X_j = inv256U_j W_j                         (X overwrites Y)
+  HSM_ABOVE_U,     // W[rows above block j] -= U[above, j] X_j
+};
+struct MultiAux {   // per front, in the order of the level's SolveNode array (the driver builds and uploads it once per handle)
+  long long boff;   // its nb-segment in the boundary work block
+  int nb, pad;      // boundary size (the SolveNode of a matrix-free front carries 0)
+};
+struct MultiArgs {  // what the grouped kernels need besides the level's SolveNode array
+  void* W1;         // work block of the level: (wrows x kcw), row-major, segment of a front at woff - wbase
+  void* W2;         // y / x of every front: (wtotal x kcw), row-major, segment at woff
+  void* XB;         // boundary rows of the level's fronts: (sum of nb x kcw), row-major, segment at boff
+  const MultiAux* aux;
+  long long wbase;
+  int kcw;          // row pitch of the work blocks
+  void* B;          // the caller's block (column-major)
+  long long ldb;
+  int kc;           // columns of this chunk
+};
+__host__ __device__ constexpr int hs_multi_rows_per_wg_c(bool is_complex) { return is_complex ? 32 : 64; }  // 4 waves split K over these rows
+int hs_multi_rows_per_wg(bool is_complex);
+template <class T>
+void launch_multi_level(const SolveNode<T>* sn, int nfronts, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s);
+template <class T>
+void launch_multi_prob(const MultiProb<T>& p, int kc, hipStream_t s);
+// what = 0: W1 = (P B)[int, :]   1: Xb = B[bnd, :]   2: B[int, :] = W2   3: B[bnd, :] = Xb
+template <class T>
+void launch_multi_move(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s);

@@ -1,0 +1,259 @@
+// hs_solve_multi.hip -- ldiv!(C, F, B) for an n x nrhs block with the factors read once per chunk of columns (hs_ldiv_block_*).
+//
+// The single-vector sweeps (kernels_solve_wide.hip) run at the HBM roofline, so k looped solves read the factors k times.  Here a chunk of
+// KC columns (HS_LDIV_BLOCK_COLS = 16 / 32 / 48 / 64, default 32; the last chunk may be ragged) travels through the tree together; every
+// step is one tall-skinny product on the matrix pipe (kernels_solve_multi.hip), grouped over the fronts of the level.  Per chunk:
+//
+//   forward, leaves -> root, per level:   W = (P B)[int, :],  Xb = B[bnd, :];   per 256-column block j:  Y_j = inv256L_j W_j,
+//                                         W[below j] -= L[below, j] Y_j;   Xb -= Lbi Y  (low-rank fronts: -= C_L (Z_L Y));   B[bnd, :] = Xb
+//   backward, root -> leaves, per level:  Xb = B[bnd, :];  W = Y - Uib Xb   (low-rank: - G (Z_R Xb));
+//                                         per block j, last first:  X_j = inv256U_j W_j,  W[above j] -= U[above, j] X_j;   B[int, :] = X
+//
+// The triangular sweeps are RIGHT-looking (everything below / above a block is updated as soon as the block is solved): a step's product
+// has (ni - 256 j) / 256 independent row tiles, so the top fronts fill the machine, and every output row has one fixed summation order.  The
+// left-looking order would read Y once more but write W only once per block -- half the work-block traffic -- at the price of a product with
+// 256 rows and K up to ni: one workgroup per front and step on the root (or a split K with a second reduction pass).  The boundary rows are
+// NOT updated step by step (the sweeps of one vector do that): they take one product with K = ni after the triangle.  The caller's matrix is
+// column-major and reached through the fronts' index lists; the products never see it: its rows are copied into row-major work blocks
+// before (multi_move_kernel) and back after, once per front and sweep, so that the 16 columns a lane group of an MFMA tile reads or
+// writes are adjacent (fronts of one level are disjoint, boundaries included -- hs_analyze checks it -- so the copies cannot collide).
+//
+// Work blocks, all row-major with a pitch of KC: W (largest level's sum of ni), Y (sum of ni over all fronts: y of every level is needed
+// again on the way down), Xb (largest level's sum of nb), T (largest rank) for the low-rank products.  Taken from the library's scratch cache on first use, kept in the handle, freed by hs_free.  The single-vector workspaces and the
+// exchange vectors of the dataflow sweeps are not touched.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "hs_solve_multi.h"
+#include "hs_lowrank.h"
+#include "hs_selinv.h"  // hs_scratch_take / hs_scratch_give
+
+int hs_ldiv_block_cols() {
+  static const int kc = [] {
+    const char* e = getenv("HS_LDIV_BLOCK_COLS");
+    const int v = e ? atoi(e) : 32;
+    return (v == 16 || v == 32 || v == 48 || v == 64) ? v : 32;
+  }();
+  return kc;
+}
+
+namespace {
+struct MultiCache {
+  void *W1 = nullptr, *W2 = nullptr, *T1 = nullptr, *XB = nullptr;
+  size_t b1 = 0, b2 = 0, bt = 0, bx = 0;
+  MultiAux* d_aux = nullptr;      // per front, level after level (root first)
+  std::vector<size_t> aux_off;    // first entry of every level
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  bool pending = false;  // the events of the last call have not been read yet
+  double info[6] = {0, 0, 0, 0, 0, 0};
+  ~MultiCache() {
+    if (e1 && pending) (void)hipEventSynchronize(e1);
+    if (W1) hs_scratch_give(W1, b1);
+    if (W2) hs_scratch_give(W2, b2);
+    if (T1) hs_scratch_give(T1, bt);
+    if (XB) hs_scratch_give(XB, bx);
+    if (d_aux) (void)hipFree(d_aux);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+void free_cache(void* p) { delete (MultiCache*)p; }
+MultiCache* cache_of(const HsMultiView& v) {
+  if (!*v.mx) {
+    *v.mx = new MultiCache();
+    *v.mx_free = free_cache;
+  }
+  return (MultiCache*)*v.mx;
+}
+void ensure(void** p, size_t* have, size_t need, const char* what) {
+  if (need <= *have) return;
+  if (*p) hs_scratch_give(*p, *have);
+  *p = nullptr;
+  *have = 0;
+  *p = hs_scratch_take(need, what);
+  *have = need;
+}
+
+long long boff_of(const HsMultiLevel& L, int pos) {
+  long long b = 0;
+  for (int i = 0; i < pos; ++i) b += L.fronts[i].nb;
+  return b;
+}
+
+struct FlopCount {
+  double exec = 0.0, useful = 0.0;
+  int tr, cmul;
+  void add(double M, double K, int kc, double useful_mk = -1.0) {
+    if (M <= 0 || kc <= 0) return;
+    const double nt16 = (double)((kc + 15) / 16 * 16);
+    exec += 2.0 * cmul * (std::ceil(M / tr) * tr) * (std::ceil(K / 16.0) * 16.0) * nt16;
+    useful += 2.0 * cmul * (useful_mk >= 0 ? useful_mk : M * K) * kc;
+  }
+};
+
+// t = Z x (r x kc, in T1), then dst -= C t with C dense or the unit trapezoid of the packed sketch; x, dst: rows of the work blocks
+template <class T>
+void lr_apply(const LowRank<T>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
+  MultiProb<T> p;
+  memset(&p, 0, sizeof p);
+  p.A = lr.Z; p.lda = lr.ldz; p.M = lr.r; p.K = lr.cols;
+  p.X = x; p.xrs = kcw;
+  p.C = tbuf; p.crs = kcw;
+  launch_multi_prob<T>(p, kc, s);
+  fc.add(lr.r, lr.cols, kc);
+  memset(&p, 0, sizeof p);
+  if (lr.Cd) {
+    p.A = lr.Cd; p.lda = lr.ldc;
+  } else {
+    p.A = lr.Lp; p.lda = lr.ldp; p.trap = 1; p.cmap = lr.rperm;
+  }
+  p.M = lr.rows; p.K = lr.r;
+  p.X = tbuf; p.xrs = kcw;
+  p.Cin = dst; p.C = dst; p.crs = kcw;
+  launch_multi_prob<T>(p, kc, s);
+  fc.add(lr.rows, lr.r, kc);
+}
+}  // namespace
+
+template <class T>
+void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+  MultiCache* mc = cache_of(v);
+  const int KC = hs_ldiv_block_cols();
+  const int kcw = KC;
+  long long wmax = 1, rmax = 1, bmax = 1;
+  if (mc->aux_off.empty()) {  // the boundary segments of every level's fronts: fixed by the tree, uploaded once
+    std::vector<MultiAux> aux;
+    for (const HsMultiLevel& L : v.levels) {
+      mc->aux_off.push_back(aux.size());
+      long long boff = 0;
+      for (const HsMultiFront& f : L.fronts) {
+        aux.push_back({boff, f.nb, 0});
+        boff += f.nb;
+      }
+    }
+    aux.push_back({0, 0, 0});
+    HS_HIP(hipMalloc((void**)&mc->d_aux, aux.size() * sizeof(MultiAux)));
+    HS_HIP(hipMemcpy(mc->d_aux, aux.data(), aux.size() * sizeof(MultiAux), hipMemcpyHostToDevice));
+  }
+  for (const HsMultiLevel& L : v.levels) {
+    wmax = std::max(wmax, L.wrows);
+    long long bsum = 0;
+    for (const HsMultiFront& f : L.fronts) bsum += f.nb;
+    bmax = std::max(bmax, bsum);
+    for (const HsMultiLR& q : L.lr) {
+      if (q.lrL) rmax = std::max<long long>(rmax, ((const LowRank<T>*)q.lrL)->r);
+      if (q.lrR) rmax = std::max<long long>(rmax, ((const LowRank<T>*)q.lrR)->r);
+    }
+  }
+  if (mc->pending && mc->e1) (void)hipEventSynchronize(mc->e1);  // a call on another stream may still use the work blocks
+  mc->pending = false;
+  ensure(&mc->W1, &mc->b1, (size_t)wmax * kcw * sizeof(T), "block solve work block");
+  ensure(&mc->W2, &mc->b2, (size_t)std::max<long long>(v.wtotal, 1) * kcw * sizeof(T), "block solve work block");
+  ensure(&mc->T1, &mc->bt, (size_t)rmax * kcw * sizeof(T), "block solve low-rank intermediate");
+  ensure(&mc->XB, &mc->bx, (size_t)bmax * kcw * sizeof(T), "block solve boundary block");
+  if (!mc->e0) {
+    HS_HIP(hipEventCreate(&mc->e0));
+    HS_HIP(hipEventCreate(&mc->e1));
+  }
+  FlopCount fc;
+  fc.tr = hs_multi_rows_per_wg(sizeof(T) == 16);
+  fc.cmul = sizeof(T) == 16 ? 4 : 1;
+  const int nl = (int)v.levels.size();
+  int chunks = 0;
+  HS_HIP(hipEventRecord(mc->e0, s));
+  for (int64_t c0 = 0; c0 < nrhs; c0 += KC, ++chunks) {
+    const int kc = (int)std::min<int64_t>(KC, nrhs - c0);
+    MultiArgs a;
+    a.W1 = mc->W1; a.W2 = mc->W2; a.XB = mc->XB; a.kcw = kcw;
+    a.B = dC + c0 * ldc; a.ldb = ldc; a.kc = kc;
+    for (int lv = nl - 1; lv >= 0; --lv) {  // leaves -> root
+      const HsMultiLevel& L = v.levels[lv];
+      if (L.nfronts == 0 || L.maxni == 0) continue;
+      const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+      a.wbase = L.wbase;
+      a.aux = mc->d_aux + mc->aux_off[lv];
+      launch_multi_move<T>(sn, L.nfronts, 0, L.maxni, a, s);
+      launch_multi_move<T>(sn, L.nfronts, 1, L.maxnb, a, s);
+      const int nblk = (L.maxni + 255) / 256;
+      for (int j = 0; j < nblk; ++j) {
+        launch_multi_level<T>(sn, L.nfronts, HSM_DIAG_L, j, std::min(256, L.maxni - j * 256), a, s);
+        launch_multi_level<T>(sn, L.nfronts, HSM_BELOW_L, j, L.maxni - (j + 1) * 256, a, s);
+      }
+      launch_multi_level<T>(sn, L.nfronts, HSM_BND_L, 0, L.maxnb, a, s);
+      for (const HsMultiFront& f : L.fronts) {
+        for (int j = 0; j * 256 < f.ni; ++j) {
+          const double wl = std::min(256, f.ni - j * 256);
+          fc.add(wl, wl, kc, wl * (wl + 1) / 2);
+          fc.add(f.ni - (j + 1) * 256, 256, kc);
+        }
+        if (f.dense_bnd) fc.add(f.nb, f.ni, kc);
+      }
+      for (const HsMultiLR& q : L.lr) {
+        if (!q.lrL) continue;
+        const LowRank<T>& lr = *(const LowRank<T>*)q.lrL;
+        if (lr.r == 0) continue;
+        lr_apply<T>(lr, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+      }
+      launch_multi_move<T>(sn, L.nfronts, 3, L.maxnb, a, s);
+    }
+    for (int lv = 0; lv < nl; ++lv) {  // root -> leaves
+      const HsMultiLevel& L = v.levels[lv];
+      if (L.nfronts == 0 || L.maxni == 0) continue;
+      const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+      a.wbase = L.wbase;
+      a.aux = mc->d_aux + mc->aux_off[lv];
+      launch_multi_move<T>(sn, L.nfronts, 1, L.maxnb, a, s);
+      launch_multi_level<T>(sn, L.nfronts, HSM_UR, 0, L.maxni, a, s);
+      for (const HsMultiLR& q : L.lr) {
+        if (!q.lrR) continue;
+        const LowRank<T>& lr = *(const LowRank<T>*)q.lrR;
+        if (lr.r == 0) continue;
+        lr_apply<T>(lr, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+      }
+      const int nblk = (L.maxni + 255) / 256;
+      for (int j = nblk - 1; j >= 0; --j) {
+        launch_multi_level<T>(sn, L.nfronts, HSM_DIAG_U, j, std::min(256, L.maxni - j * 256), a, s);
+        launch_multi_level<T>(sn, L.nfronts, HSM_ABOVE_U, j, j * 256, a, s);
+      }
+      launch_multi_move<T>(sn, L.nfronts, 2, L.maxni, a, s);
+      for (const HsMultiFront& f : L.fronts) {
+        if (f.dense_bnd) fc.add(f.ni, f.nb, kc);
+        for (int j = 0; j * 256 < f.ni; ++j) {
+          const double wl = std::min(256, f.ni - j * 256);
+          fc.add(wl, wl, kc, wl * (wl + 1) / 2);
+          fc.add(j * 256, wl, kc);
+        }
+      }
+    }
+  }
+  HS_HIP(hipEventRecord(mc->e1, s));
+  HS_HIP(hipGetLastError());
+  mc->pending = true;
+  mc->info[0] = 0.0;
+  mc->info[1] = (double)chunks * v.sum_fac * sizeof(T);
+  mc->info[2] = fc.exec;
+  mc->info[3] = fc.useful;
+  mc->info[4] = (double)chunks;
+  mc->info[5] = (double)(mc->b1 + mc->b2 + mc->bt + mc->bx);
+}
+template void hs_solve_multi_run<double>(const HsMultiView&, double*, int64_t, int64_t, hipStream_t);
+template void hs_solve_multi_run<cplx>(const HsMultiView&, cplx*, int64_t, int64_t, hipStream_t);
+
+double hs_solve_multi_seconds(void* mx) {
+  MultiCache* mc = (MultiCache*)mx;
+  if (!mc) return 0.0;
+  if (mc->pending) {
+    float ms = 0.f;
+    if (hipEventSynchronize(mc->e1) == hipSuccess && hipEventElapsedTime(&ms, mc->e0, mc->e1) == hipSuccess) mc->info[0] = ms * 1e-3;
+    mc->pending = false;
+  }
+  return mc->info[0];
+}
+void hs_solve_multi_info(void* mx, double* out6) {
+  MultiCache* mc = (MultiCache*)mx;
+  if (mc) (void)hs_solve_multi_seconds(mx);
+  for (int k = 0; k < 6; ++k) out6[k] = mc ? mc->info[k] : 0.0;
+}

@@ -9,6 +9,7 @@
 #include "../../include/hs_kernels.h"
 #include "hs_sched.h"
 #include "hs_lowrank.h"
+#include "hs_solve_multi.h"
 
 #define CK(call)                                                                                   \
   do {                                                                                             \
@@ -331,4 +332,55 @@ extern "C" int hsk_lowrank_d(int64_t rows, int64_t cols, const double* X, double
 extern "C" int hsk_lowrank_z(int64_t rows, int64_t cols, const double* X, double atol, double rtol, int64_t kinit, int64_t seed, int64_t* r_out,
                              double* Cout, double* Zout, int64_t cap) {
   return lowrank_hook<cplx>(rows, cols, (const cplx*)X, atol, rtol, kinit, seed, r_out, (cplx*)Cout, (cplx*)Zout, cap);
+}
+
+// the panel product of the block solves (kernels_solve_multi.hip) on host data; X and C reach the kernel row-major with a pitch of 64, as
+// the work blocks of the driver do
+template <class T>
+static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap) {
+  if (M < 1 || K < 0 || kc < 1 || kc > 64 || lda < M || ldx < std::max<int64_t>(K, 1) || ldc < M || !A || !X || !C) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_multi_prob: M >= 1, K >= 0, kc in 1..64, leading dimensions and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
+    return HS_ERR_DEVICE;
+  }
+  const int64_t P = 64;
+  std::vector<T> hx((size_t)std::max<int64_t>(K, 1) * P), hc((size_t)M * P);
+  for (int64_t c = 0; c < kc; ++c) {
+    for (int64_t k = 0; k < K; ++k) hx[k * P + c] = X[k + c * ldx];
+    for (int64_t i = 0; i < M; ++i) hc[i * P + c] = C[i + c * ldc];
+  }
+  T *dA = nullptr, *dX = nullptr, *dC = nullptr;
+  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)lda * std::max<int64_t>(K, 1)));
+  CK(hipMalloc((void**)&dX, sizeof(T) * hx.size()));
+  CK(hipMalloc((void**)&dC, sizeof(T) * hc.size()));
+  if (K > 0) CK(hipMemcpy(dA, A, sizeof(T) * (size_t)lda * K, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dX, hx.data(), sizeof(T) * hx.size(), hipMemcpyHostToDevice));
+  CK(hipMemcpy(dC, hc.data(), sizeof(T) * hc.size(), hipMemcpyHostToDevice));
+  MultiProb<T> p;
+  memset(&p, 0, sizeof p);
+  p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0;
+  p.X = dX; p.xrs = P;
+  p.Cin = minus ? dC : nullptr;
+  p.C = dC; p.crs = P;
+  launch_multi_prob<T>(p, (int)kc, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy(hc.data(), dC, sizeof(T) * hc.size(), hipMemcpyDeviceToHost));
+  for (int64_t c = 0; c < kc; ++c)
+    for (int64_t i = 0; i < M; ++i) C[i + c * ldc] = hc[i * P + c];
+  (void)hipFree(dA);
+  (void)hipFree(dX);
+  (void)hipFree(dC);
+  return HS_OK;
+}
+extern "C" int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                int64_t ldc, int minus, int trap) {
+  return multi_prob_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap);
+}
+extern "C" int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                int64_t ldc, int minus, int trap) {
+  return multi_prob_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap);
 }

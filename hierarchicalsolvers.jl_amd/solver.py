@@ -392,6 +392,51 @@ def ldiv(*args):
     return res
 
 
+def ldiv_block(*args):
+    """``ldiv!(F, B)`` / ``ldiv!(C, F, B)`` through the block solve (``hs_ldiv_block_*``): the same arguments and results as :func:`ldiv`
+    (to rounding), but the ``nrhs`` columns travel through the elimination tree together, ``HS_LDIV_BLOCK_COLS`` (default 32) at a time, so
+    the factors are read once per chunk instead of once per column.  ``F`` must be a plain :class:`FactorNode` whose fronts keep a dense LU
+    of their interior block (``transpose(F)`` / ``adjoint(F)`` and HSS interior blocks raise :class:`UnsupportedError`)."""
+    if len(args) == 2:
+        F, B = args
+        Cout = None
+    elif len(args) == 3:
+        Cout, F, B = args
+    else:
+        raise TypeError("ldiv_block(F, B) or ldiv_block(C, F, B)")
+    trans = 0
+    if isinstance(F, TransposedFactor):
+        F, trans = F.parent, F.trans
+    B = np.asarray(B)
+    if B.shape[0] != F.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
+    if B.dtype != F.dtype:
+        if F.dtype.kind == "f" and B.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::FactorNode{Float64}, ::Array{ComplexF64})")
+        B = B.astype(F.dtype)
+    vec = B.ndim == 1
+    Bm = np.asfortranarray(B.reshape(F.n, -1))
+    Cm = np.empty_like(Bm, order="F")
+    L = _lib.lib()
+    fn = L.hs_ldiv_block_z if F.dtype.kind == "c" else L.hs_ldiv_block_d
+    _lib.check(fn(F._h, trans, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
+    res = Cm[:, 0] if vec else Cm
+    if Cout is not None:
+        Cout[...] = res
+        return Cout
+    return res
+
+
+def ldiv_block_info(F):
+    """Figures of the last :func:`ldiv_block` call on ``F`` (``hs_ldiv_block_info``): device seconds, factor bytes read by the model
+    (chunks x sum over fronts of ``(ni^2 + 2 ni nb) sizeof(T)``), flops executed on the matrix pipe (padding included), useful flops,
+    column chunks, workspace bytes."""
+    out = np.zeros(6)
+    _lib.check(_lib.lib().hs_ldiv_block_info(F._h, _pf64(out)))
+    return {"seconds": float(out[0]), "factor_bytes": float(out[1]), "flops_executed": float(out[2]), "flops_useful": float(out[3]),
+            "chunks": int(out[4]), "workspace_bytes": int(out[5])}
+
+
 def maxrank(F):
     """``maxrank(F)`` (factornode.jl:49-57)."""
     return int(_lib.lib().hs_maxrank(F._h))

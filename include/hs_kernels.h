@@ -55,6 +55,14 @@ int hsk_lowrank_d(int64_t rows, int64_t cols, const double* X, double atol, doub
 int hsk_lowrank_z(int64_t rows, int64_t cols, const double* X, double atol, double rtol, int64_t kinit, int64_t seed,
                   int64_t* r_out, double* Cout, double* Zout, int64_t cap);
 
+/* The tall-skinny panel product of the block solves (kernels_solve_multi.hip) on host data: C = A X (minus == 0) or C = C - A X, A M x K
+ * (column-major, lda), X K x kc and C M x kc column-major with kc in 1..64 (they reach the kernel row-major with a pitch of 64, as the work
+ * blocks of hs_ldiv_block_* do).  trap != 0: A stands for its unit lower trapezoid. */
+int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                     int minus, int trap);
+int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                     int minus, int trap);
+
 /* Host-only: the order in which the HSS form of a front's interior block lists its DOFs (hs_options.hss_d): recursive bisection of
  * the graph of A (1-based CSC pattern colptr / rowval of the n x n matrix) restricted to the ni DOFs `ids` (1-based), split where the
  * HSS cluster tree splits its index range.  perm_out[new position] = position in `ids` (0-based). */

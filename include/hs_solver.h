@@ -149,6 +149,25 @@ int hs_ldiv_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B
 int hs_ldiv_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 int hs_ldiv_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 
+/* ldiv!(C, F, B) for an n x nrhs block, the factors read once per chunk of columns (hs_solve_multi.hip). Same arguments as hs_ldiv_t_*;
+ * trans must be 0. C may alias B.  The block travels through the elimination tree in chunks of HS_LDIV_BLOCK_COLS columns (16 / 32 / 48 / 64,
+ * default 32; read once per process); every step is a tall-skinny product on the FP64 matrix pipe.  No atomics and a fixed summation order:
+ * two calls return the same bits, and a column of C does not depend on the values, the number or the position of the other columns.
+ * The results agree with hs_ldiv_* to rounding, not bit for bit.  Served: what hs_ldiv_t_* serves (single-rank handles whose fronts all
+ * keep a dense LU of D, low-rank L / R included).  Refused with HS_ERR_UNSUPPORTED before any device work and before C is written: fronts
+ * that keep D as an HSS matrix (hs_options.hss_d, mf = 2, 3), more than one rank, trans = 1, 2 (other trans: HS_ERR_ARGUMENT).  nrhs = 0
+ * touches nothing.  The host forms move the whole block once and set stats.t_solve; the _dev_ forms are asynchronous on `stream`.  The work
+ * blocks ((sum of ni + the largest level's sum of ni and of nb) x chunk columns) are taken on first use, kept in the handle and freed by hs_free; the
+ * workspaces of hs_ldiv_* / hs_ldiv_t_* are not touched, so the calls may alternate freely. */
+int hs_ldiv_block_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_ldiv_block_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_ldiv_block_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+int hs_ldiv_block_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+/* last block solve of the handle (waits for it): out6 = {seconds on the device, factor bytes read by the model (column chunks x sum over
+ * fronts of (ni^2 + 2 ni nb) sizeof(T), the factor term of hs_stats.bytes_solve), flops executed on the matrix pipe (padding included),
+ * useful flops, column chunks, workspace bytes} */
+int hs_ldiv_block_info(const hs_handle* F, double* out6);
+
 /* ---- accuracy tools: norm and condition estimates, refined solves with error bounds (hs_condest.hip) --------------------------
  * opnorm(A, 1), opnorm(A, Inf) of the handle's A (the values of the last hs_numeric_begin); p = 1 or 0 (= Inf).  The first call that needs
  * rows of A (p = 0, hs_condest p = 0, hs_ldiv_refine_* with trans = 0) builds a CSR map of A's pattern on the device and keeps it in the handle. */
