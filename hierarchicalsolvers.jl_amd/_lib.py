@@ -88,6 +88,7 @@ EXPORTS = [
     "hs_hss_offdiag", "hs_hss_bytes", "hs_hss_prune_leaves", "hs_hss_compatible", "hs_hss_depth", "hs_hss_compress_blockop_d", "hs_hss_compress_blockop_z", "hs_hss_blockop_apply",
     "hsk_gemm_d", "hsk_gemm_z", "hsk_lowrank_d", "hsk_lowrank_z", "hsk_front_factor_d", "hsk_front_factor_z", "hsk_front_batch_d", "hsk_front_batch_z", "hsk_mfma_f64_peak", "hsk_mfma_f64_peak_random", "hsk_flow_pingpong_us", "hsk_bisect_perm",
     "hs_probs_stats_mode", "hs_probs_stats", "hs_trim", "hs_stream_order",
+    "hsk_leaf_envelope", "hsk_envelope_enable", "hsk_op_flops_mode", "hsk_op_flops",
 ]
 
 _lib = None
@@ -352,6 +353,14 @@ def lib():
     L.hs_probs_stats_mode.restype = C.c_int
     L.hs_probs_stats.argtypes = [p_f64]
     L.hs_probs_stats.restype = C.c_int
+    L.hsk_leaf_envelope.argtypes = [i64, p_i64, p_i64, C.POINTER(C.c_int32), i64, i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.hsk_leaf_envelope.restype = C.c_int
+    L.hsk_envelope_enable.argtypes = [C.c_int]
+    L.hsk_envelope_enable.restype = C.c_int
+    L.hsk_op_flops_mode.argtypes = [C.c_int]
+    L.hsk_op_flops_mode.restype = C.c_int
+    L.hsk_op_flops.argtypes = [p_f64]
+    L.hsk_op_flops.restype = C.c_int
     L.hsk_flow_pingpong_us.argtypes = [C.c_int, C.c_int]
     L.hsk_flow_pingpong_us.restype = C.c_double
     L.hsk_mfma_f64_peak.argtypes = [C.c_int, C.c_int]

@@ -130,6 +130,7 @@ struct NodeH {
   size_t off_fidx = 0, off_ipiv = 0, off_rperm = 0, off_cmap = 0, off_cand = 0;  // int offsets
   int ncand = 0;
   int batch_pos = -1;      // index inside its level's batch of owned fronts
+  long long off_env = -1;  // leaf eliminated by Sched: int offset of its block envelope in hs_handle::env_host / d_env (hs_envelope.h); -1: dense
   void* ext_sb = nullptr;  // caller-provided device buffer for the Schur complement (exchange between ranks)
   long long woff = 0;
   bool compressed = false;  // level <= swlevel && |bnd| >= swsize (factorization.jl:15): low-rank Gauss transforms
@@ -183,6 +184,7 @@ struct LevelH {
   size_t desc_off = 0;              // first NodeDesc / SolveNode of this level (owned fronts only)
   size_t sc_off = 0, sc_cnt = 0;    // ScatterDesc range
   std::vector<int> h_ni, h_nb;
+  std::vector<const int*> h_env;    // block envelopes of the dense batch on the host (null: dense front); empty when no front of the level has one
   int ndense = 0;                          // the first ndense entries of `mine` are dense fronts (one batch), the rest compressed
   int nplain = 0;                          // of those, the first nplain keep a dense LU of D, the others an HSS form (hs_hssfront.h)
   int nmf = 0;                             // the last nmf entries of `mine` are matrix-free fronts (hs_mffront.h): never assembled
@@ -195,6 +197,7 @@ struct Exchange {
   int hss = 0;  // 1: the node's Schur complement crosses as a packed HSS matrix (hs_schur_pack / hs_schur_unpack), not as a dense block
 };
 
+#include "hs_envelope.h"
 #include "hs_sched.h"
 #include "hs_split.h"
 #include "hs_comm.h"
@@ -242,6 +245,8 @@ struct hs_handle {
   void* d_nodes = nullptr;  // NodeDesc<T>[] of the owned fronts, level by level
   void* d_sc = nullptr;     // ScatterDesc<T>[]
   void* d_solve = nullptr;  // SolveNode<T>[] (same order as d_nodes)
+  int* d_env = nullptr;     // block envelopes of the leaf fronts (NodeDesc::env), built once per pattern
+  std::vector<int> env_host;
   void* d_w1 = nullptr;
   void* d_w2 = nullptr;
   int* d_flow = nullptr;    // dataflow sweeps (kernels_solve_wide.hip): 64 workgroup-id counters, one per launch, used as a ring
@@ -378,7 +383,7 @@ static void free_handle(hs_handle* h) {
   arena_give(h->d_cfs, h->cfs_bytes);
   void* ptrs[] = {h->d_int, h->d_tmpi, h->d_colptr, h->d_rowval, h->d_nz,
                   h->d_nodes, h->d_sc,  h->d_solve, h->d_w1,  h->d_w2,   h->d_part,   h->d_b,   h->d_owned,
-                  h->d_rowptr, h->d_colind, h->d_tperm, h->d_nzr, h->d_lpos};
+                  h->d_rowptr, h->d_colind, h->d_tperm, h->d_nzr, h->d_lpos, h->d_env};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1062,6 +1067,38 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
       if (!owned.empty()) HS_HIP(hipMemcpy(h->d_owned, owned.data(), owned.size() * sizeof(int), hipMemcpyHostToDevice));
     }
 
+    // ---- block envelopes of the leaf fronts the level schedule eliminates densely (hs_envelope.h) -----------------
+    // A leaf is assembled from A alone, so its pattern is known here.  Everything else (branch fronts: two dense Schur complements; slices
+    // of split fronts; fronts of the compressed / HSS / matrix-free flows) keeps a null pointer, which means "dense".
+    if (colptr && rowval) {
+      std::vector<int> where((size_t)n, -1);
+      for (LevelH& L : h->levels) {
+        L.h_env.clear();
+        for (int k = 0; k < L.ndense; ++k) {
+          NodeH& x = N[L.mine[k]];
+          if (!x.leaf || x.kind != 0 || x.dist || x.compressed || x.hssd || x.mf || x.ni <= 0) continue;
+          const int nblk = hs_env_nblocks(x.ni, x.nb);
+          x.off_env = (long long)h->env_host.size();
+          h->env_host.resize(h->env_host.size() + 2 * (size_t)nblk);
+          int* fl = h->env_host.data() + x.off_env;
+          hs_leaf_envelope(colptr, rowval, h->fidx_host.data() + x.off_fidx, x.ni, x.nb, where.data(), fl, fl + nblk);
+        }
+      }
+      if (!h->env_host.empty()) {
+        dmalloc((void**)&h->d_env, h->env_host.size() * sizeof(int), "leaf envelopes");
+        HS_HIP(hipMemcpy(h->d_env, h->env_host.data(), h->env_host.size() * sizeof(int), hipMemcpyHostToDevice));
+        for (LevelH& L : h->levels) {  // (env_host no longer moves)
+          bool any = false;
+          for (int k = 0; k < L.ndense; ++k) any = any || N[L.mine[k]].off_env >= 0;
+          if (!any) continue;
+          for (int k = 0; k < L.ndense; ++k) {
+            const NodeH& x = N[L.mine[k]];
+            L.h_env.push_back(x.off_env >= 0 ? h->env_host.data() + x.off_env : nullptr);
+          }
+        }
+      }
+    }
+
     // ---- device descriptors (built once; pointers are fixed from here on) ------------------------------------
     {
       std::vector<NodeDesc<T>> hn;
@@ -1097,6 +1134,7 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
           d.spos = x.off_spos >= 0 ? dint + x.off_spos : nullptr;
           d.isleaf = x.leaf ? 1 : 0;
           d.node = id;
+          d.env = x.off_env >= 0 ? h->d_env + x.off_env : nullptr;
           d.finalize();
           hn.push_back(d);
           SolveNode<T> q;
@@ -1288,6 +1326,12 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
       Sched<T> sch{dn, L.ndense, L.dmaxni, L.dmaxnb, L.dmaxm, s, &h->prof, L.h_ni.data(), L.h_nb.data(), h->stream2, 0, h->stream_la, h->stream2m};
       sch.sn = (const SolveNode<T>*)h->d_solve + L.desc_off;  // lu_rec leaves the 256x256 inverse diagonal blocks behind
       sch.optimistic = try_opt && attempt == 0;
+      // the block envelope of the leaves holds while rows are swapped inside 32-row diagonal blocks only: the redo of a level and
+      // HS_OPTIMISTIC=0 (tournament pivoting) eliminate every front as a dense matrix
+      if (sch.optimistic && !dx && !L.h_env.empty() && hs_envelope_enabled()) {
+        sch.env = true;
+        sch.h_env = L.h_env.data();
+      }
       if (dx)
         factor_front_dist<T>(sch, DF);
       else

@@ -120,6 +120,8 @@ struct NodeDesc {
   int pivrows;   // pivot candidates are rows [c0, pivrows): ni for a front (`\\` on Aii pivots inside Aii only), all rows for a sketch
   int isleaf;
   int node;      // post-order id
+  const int* env;  // leaf front: block envelope of its sparsity pattern (hs_envelope.h), firstL then firstU, one entry per 32-row / 32-column
+                   // block of the front (interior blocks first, boundary blocks counted from the start of the boundary part); null = dense
   // the same three matrices indexed by HS_MAT_*: kernels that pick a matrix at run time index these
   // tables (plain address arithmetic) instead of branching over LF/UR/SB -- hipcc (ROCm 7.2) was seen
   // to miscompile the three-way scalar select of field addresses ("compiler notes").
@@ -152,7 +154,34 @@ struct GemmOp {
   int cap;         // > 0: launch at most this many workgroups per front (they walk the tiles): leaves CU slots free for a
                    // concurrent stream (the look-ahead panel chain); 0: one workgroup per tile
   int prio;        // 1: raise the waves' issue priority (s_setprio): panel work of the look-ahead side stream
+  int env;         // 1: fronts that carry a block envelope (NodeDesc::env) skip the K range and the tiles known to be exact zeros (optimistic pivoting only)
+  int count;       // 1: the launch goes to gemm_op_env_kernel, which adds the flops of the K-steps it runs to a device counter (hsk_op_flops; set by
+                   // launch_gemm_op while the hook is on)
 };
+
+// Block envelope of a leaf front (hs_envelope.h): the smallest entry of `first` over the 32-blocks that meet the front positions [lo, hi).
+// Interior positions (< ni) are block p / 32, boundary positions block nI + (p - ni) / 32 with nI = ceil(ni / 32): consecutive in the table.
+#define HS_ENV_NONE HS_BIG  // a block without any structural entry in the interior rows / columns
+__host__ __device__ inline int hs_env_block(int p, int ni) { return p < ni ? p >> 5 : ((ni + 31) >> 5) + ((p - ni) >> 5); }
+__host__ __device__ inline int hs_env_min(const int* first, int ni, int lo, int hi) {
+  int v = HS_ENV_NONE;
+  for (int b = hs_env_block(lo, ni), b1 = hs_env_block(hi - 1, ni); b <= b1; ++b) v = first[b] < v ? first[b] : v;
+  return v;
+}
+// What a tile needs to clip its K range: C(0, 0) sits at front position (row0, col0), the K index 0 of the resolved problem at front column kbase.
+// fL / fU null: that side carries no information for this product (or the front is dense).
+struct EnvClip {
+  const int* fL;
+  const int* fU;
+  int row0, col0, kbase, ni;
+};
+// first K index (front column, multiple of 32 as kbase is) the tile rows [m_lo, m_hi) x columns [n_lo, n_hi) of C has to start at
+__host__ __device__ inline int hs_env_kstart(const EnvClip& e, int m_lo, int m_hi, int n_lo, int n_hi) {
+  int k = e.kbase;
+  if (e.fL) { const int v = hs_env_min(e.fL, e.ni, e.row0 + m_lo, e.row0 + m_hi); k = v > k ? v : k; }
+  if (e.fU) { const int v = hs_env_min(e.fU, e.ni, e.col0 + n_lo, e.col0 + n_hi); k = v > k ? v : k; }
+  return k;
+}
 
 // plain problem (test hooks, root Schur, compressed path)
 template <class T>
@@ -177,6 +206,7 @@ __device__ inline void mat_of(const NodeDesc<T>* pn, int which, T*& p, int& ld, 
 // ---- launch API (implemented in the kernels_*.hip files) -------------------------------------
 template <class T>
 void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s);
+bool hs_envelope_enabled();  // HS_LEAF_ENVELOPE (default on) / hsk_envelope_enable: leaf fronts are eliminated inside their block envelope
 template <class T>
 void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN, int accumulate_minus, hipStream_t s);
 

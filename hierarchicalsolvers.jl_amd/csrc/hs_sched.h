@@ -85,6 +85,9 @@ struct Sched {
   int rlim = HS_BIG;                 // rows the panel kernels and the in-group updates of lu_rec may touch (diagonal-block-first groups)
   bool optimistic = false;           // no tournament: every panel pivots among its own 32 rows, panel_l21 checks the multipliers
                                      // (NodeDesc::growth); the caller redoes the batch with the tournament if the flag went up
+  bool env = false;                  // leaf fronts of the batch are eliminated inside their block envelope (NodeDesc::env, hs_envelope.h).  Only with
+                                     // `optimistic`: the tournament swaps rows across 32-blocks, which breaks the row envelope
+  const int* const* h_env = nullptr; // the same tables on the host, one pointer per front (null: dense), for the flop / byte accounting
 
   // HS_DEBUG_SYNC=1: synchronise after every launch and report the first failing one (diagnostics only)
   void dbg(const char* what, int a = 0, int b = 0, int c = 0, int d = 0) {
@@ -106,8 +109,9 @@ struct Sched {
   int rows_of(int mat) const { return mat == HS_MAT_LF ? maxm : (mat == HS_MAT_UR ? maxni : maxnb); }
   int cols_of(int mat) const { return mat == HS_MAT_LF ? maxni : maxnb; }
 
+  std::vector<int> kcol, kcol_rd;  // scratch of the enveloped accounting below
   void gemm(int cmat, int bmat, int r0, int r1, int c0, int c1, int k0, int k1, int cap = 0) {
-    GemmOp op{cmat, bmat, r0, r1, c0, c1, k0, k1, 0, cap, hiprio};
+    GemmOp op{cmat, bmat, r0, r1, c0, c1, k0, k1, 0, cap, hiprio, env ? 1 : 0};
     int M = std::min(r1, rows_of(cmat)) - r0, N = std::min(c1, cols_of(cmat)) - c0, K = std::min(k1, maxni) - k0;
     if (M <= 0 || N <= 0 || K <= 0) return;
     double fl = 0.0;
@@ -117,6 +121,37 @@ struct Sched {
         int rows = cmat == HS_MAT_LF ? m : (cmat == HS_MAT_UR ? ni : nb), cols = cmat == HS_MAT_LF ? ni : nb;
         double Mi = std::min(r1, rows) - r0, Ni = std::min(c1, cols) - c0, Ki = std::min(k1, ni) - k0;
         if (Mi > 0 && Ni > 0 && Ki > 0) {
+          if (env && h_env && h_env[i]) {
+            // the clipped ranges, by the rule of the kernel (gemm_dispatch_env, kernels_gemm.hip): per tile of 128 x (128 | 64) the K loop
+            // starts at max(k0, min firstL of its rows, min firstU of its columns).  Bytes: C of the tiles that run, A / B once per tile
+            // row / column over the longest K range one of its tiles reads.
+            const int BMh = 128, BNh = sizeof(T) == 16 ? 64 : 128;
+            const int M_ = (int)Mi, N_ = (int)Ni, K_ = (int)Ki;
+            const int* fL = h_env[i];
+            const int* fU = fL + hs_env_block(m - 1, ni) + 1;
+            const int row0 = r0 + (cmat == HS_MAT_SB ? ni : 0), col0 = c0 + (cmat == HS_MAT_LF ? 0 : ni);
+            const int tn_ = (N_ + BNh - 1) / BNh;
+            kcol.resize(tn_);
+            kcol_rd.assign(tn_, 0);
+            for (int tn = 0; tn < tn_; ++tn) kcol[tn] = hs_env_min(fU, ni, col0 + tn * BNh, col0 + std::min(N_, (tn + 1) * BNh));
+            for (int m0 = 0; m0 < M_; m0 += BMh) {
+              const int mt = std::min(BMh, M_ - m0);
+              const int kr = std::max(k0, hs_env_min(fL, ni, row0 + m0, row0 + m0 + mt));
+              int krow_rd = 0;
+              for (int tn = 0; tn < tn_; ++tn) {
+                const int kt = K_ - (std::max(kr, kcol[tn]) - k0);
+                if (kt <= 0) continue;
+                const int nt = std::min(BNh, N_ - tn * BNh);
+                fl += 2.0 * mt * (double)nt * kt;
+                pf->gemm_bytes += 2.0 * mt * nt * sizeof(T);
+                krow_rd = std::max(krow_rd, kt);
+                kcol_rd[tn] = std::max(kcol_rd[tn], kt);
+              }
+              pf->gemm_bytes += (double)mt * krow_rd * sizeof(T);
+            }
+            for (int tn = 0; tn < tn_; ++tn) pf->gemm_bytes += (double)std::min(BNh, N_ - tn * BNh) * kcol_rd[tn] * sizeof(T);
+            continue;
+          }
           fl += 2.0 * Mi * Ni * Ki;
           pf->gemm_bytes += (Mi * Ki + Ki * Ni + 2.0 * Mi * Ni) * sizeof(T);
         }
@@ -176,7 +211,7 @@ struct Sched {
   void trsm256(int mat, int r0, int c0, int c1, int nc, bool upper) {
     const int first = upper ? 5 : 3, second = upper ? 6 : 4;
     for (int code : {first, second}) {
-      GemmOp op{mat, mat, r0, r0 + 256, c0, c1, 0, 0, code};
+      GemmOp op{mat, mat, r0, r0 + 256, c0, c1, 0, 0, code, 0, 0, env ? 1 : 0};
       hipEvent_t e0 = pf->begin(s);
       launch_gemm_op<T>(dn, nbatch, 128, nc, op, s);
       pf->end(e0, HS_CAT_TRSM, s);
@@ -203,7 +238,7 @@ struct Sched {
     }
     if (r1 - r0 == HS_PB) {
       // base case: multiply by the stored inverse of the 32x32 unit-lower diagonal block (MFMA GEMM, in place)
-      GemmOp op{mat, mat, r0, r0 + HS_PB, c0, c1, 0, 0, 1};
+      GemmOp op{mat, mat, r0, r0 + HS_PB, c0, c1, 0, 0, 1, 0, 0, env ? 1 : 0};
       hipEvent_t e0 = pf->begin(s);
       launch_gemm_op<T>(dn, nbatch, HS_PB, nc, op, s);
       pf->end(e0, HS_CAT_TRSM, s);
@@ -272,7 +307,7 @@ struct Sched {
       if (r0 < maxm) {
         if (sizeof(T) == 8) {
           for (int code : {7, 8}) {
-            GemmOp op{HS_MAT_LF, HS_MAT_LF, r0, HS_BIG, c0, c1, c0, c1, code, 0, hiprio};
+            GemmOp op{HS_MAT_LF, HS_MAT_LF, r0, HS_BIG, c0, c1, c0, c1, code, 0, hiprio, env ? 1 : 0};
             hipEvent_t e0 = pf->begin(s);
             launch_gemm_op<T>(dn, nbatch, maxm - r0, 128, op, s);
             pf->end(e0, HS_CAT_TRSM, s);
@@ -281,7 +316,7 @@ struct Sched {
         } else {
           const int wl = std::min(256, maxni - c0);
           for (int q = (wl - 1) / 64; q >= 0; --q) {
-            GemmOp op{HS_MAT_LF, HS_MAT_LF, r0, HS_BIG, c0, c1, c0, c1, 16 + q, 0, hiprio};
+            GemmOp op{HS_MAT_LF, HS_MAT_LF, r0, HS_BIG, c0, c1, c0, c1, 16 + q, 0, hiprio, env ? 1 : 0};
             hipEvent_t e0 = pf->begin(s);
             launch_gemm_op<T>(dn, nbatch, maxm - r0, 64, op, s);
             pf->end(e0, HS_CAT_TRSM, s);

@@ -384,3 +384,20 @@ extern "C" int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* 
                                 int64_t ldc, int minus, int trap) {
   return multi_prob_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap);
 }
+
+// The leaf-envelope builder of the analysis (hs_envelope.h), host only: tests compare it with a NumPy computation from A[idx][:, idx]
+#include "hs_envelope.h"
+extern "C" int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL,
+                                 int32_t* firstU) {
+  if (n <= 0 || !colptr || !rowval || !fidx || ni < 0 || nb < 0 || ni + nb <= 0 || !firstL || !firstU) return -1;
+  for (int64_t p = 0; p < ni + nb; ++p)
+    if (fidx[p] < 0 || fidx[p] >= n) return -1;
+  if (colptr[0] != 1) return -1;
+  for (int64_t j = 0; j < n; ++j)
+    if (colptr[j + 1] < colptr[j]) return -1;
+  for (int64_t e = 0; e < colptr[n] - 1; ++e)
+    if (rowval[e] < 1 || rowval[e] > n) return -1;
+  std::vector<int> where((size_t)n, -1);
+  hs_leaf_envelope(colptr, rowval, fidx, (int)ni, (int)nb, where.data(), firstL, firstU);
+  return 0;
+}

@@ -19,6 +19,7 @@
 //
 // Complex: planar split when staging (re / im images in LDS), 4 real MFMAs per k-step
 // (re += ar*br - ai*bi, im += ar*bi + ai*br); 128x64 tile, wave tile 64x32.
+#include <atomic>
 #include <mutex>
 #include <vector>
 #include <algorithm>
@@ -72,14 +73,40 @@ __device__ inline void tile_coords(int t, int tiles_m, int tiles_n, int& tm, int
   tn = in_g / gm;
 }
 
-template <class T>
-__device__ inline bool resolve_op(const NodeDesc<T>* pn, const GemmOp& op, GemmProb<T>& p) {
+// The block envelope of a leaf front (GemmOp::env, NodeDesc::env; hs_envelope.h) comes back in `e`: which of firstL / firstU says something
+// about this product, and where C and the K index sit in the front.  gemm_dispatch_env clips every tile with it (the enveloped launches run
+// in kernels of their own, gemm_op_env_kernel / trsm_inv_env_kernel; the dense kernels instantiate resolve_op<T, false>, which holds none of
+// this).  What each form may skip:
+//   plain update C -= L[rows, k] * U[k, cols]: L[r, k] = 0 for k < firstL[r] and U[k, c] = 0 for k < firstU[c], so the K loop of a tile starts
+//     at the larger of the two minima over its rows / columns; a tile with nothing left subtracts an exact +0 from C and is not run at all.
+//   ainv 1, 3, 4 (X <- inv(L block) * X, in place; X is a piece of U or U12): column c of X is zero above firstU[c], so the same clip by the
+//     columns alone.  A tile with nothing left reads only zeros of X -- its own rows among them, as its K range covers the rows it writes --
+//     and would store zeros over zeros; the tiles that do run read what they read before (nobody has written anything else), so the
+//     read-all-of-K-before-the-stores ordering argument below is untouched.
+//   ainv 7, 8, 16 + q (L_below <- A_below * inv(U_group), in place): row r of A_below is zero left of firstL[r], so the clip by the rows alone;
+//     an empty tile has zero rows over the whole group, the product with the triangular inverse is zero, zeros stay (and raise no growth flag).
+//   ainv 2, 5, 6 (X <- inv(U block) * X, backward substitution) fill upwards: no clip.
+template <class T, bool ENV>
+__device__ inline bool resolve_op(const NodeDesc<T>* pn, const GemmOp& op, GemmProb<T>& p, EnvClip* ep) {
+  EnvClip e_unused;  // (ENV == false: every use below is compiled out)
+  EnvClip& e = ENV ? *ep : e_unused;
   T *cp, *bp;
   int ldc, ldb, crows, ccols, brows, bcols;
   mat_of(pn, op.cmat, cp, ldc, crows, ccols);
   mat_of(pn, op.bmat, bp, ldb, brows, bcols);
   const int ni = pn->ni, ldl = pn->ldl;
   T* const LF = pn->LF;
+  const int* env = nullptr;
+  const int* envU = nullptr;
+  if constexpr (ENV) {
+    env = op.env ? pn->env : nullptr;
+    envU = env ? env + hs_env_block(pn->m - 1, ni) + 1 : nullptr;  // firstU follows the firstL entries of all blocks
+    e.fL = e.fU = nullptr;
+    e.ni = ni;
+    e.row0 = op.r0 + (op.cmat == HS_MAT_SB ? ni : 0);
+    e.col0 = op.c0 + (op.cmat == HS_MAT_LF ? 0 : ni);
+    e.kbase = op.k0;
+  }
   if (op.ainv >= 16) {
     // The same product for tiles that are 64 columns wide (ComplexF64): column block q = ainv - 16 of the group, from the right (3, 2, 1, 0):
     //   L[r0.., k0+64q : k0+64q+64) <- A[r0.., k0 : k0+64(q+1)) * V[0 : 64(q+1), 64q : 64q+64)      (V = inv(U_group) is upper triangular)
@@ -97,6 +124,7 @@ __device__ inline bool resolve_op(const NodeDesc<T>* pn, const GemmOp& op, GemmP
     p.lda = ldl; p.ldb = 256; p.ldc = ldl;
     p.flag = pn->growth;
     p.flag_rows = pn->pivrows - op.r0;
+    if constexpr (ENV) e.fL = env;
     return true;
   }
   if (op.ainv >= 7) {
@@ -118,6 +146,7 @@ __device__ inline bool resolve_op(const NodeDesc<T>* pn, const GemmOp& op, GemmP
     p.lda = ldl; p.ldb = 256; p.ldc = ldl;
     p.flag = pn->growth;
     p.flag_rows = pn->pivrows - op.r0;
+    if constexpr (ENV) e.fL = env;
     return true;
   }
   if (op.ainv >= 3) {
@@ -143,6 +172,8 @@ __device__ inline bool resolve_op(const NodeDesc<T>* pn, const GemmOp& op, GemmP
     p.C = cp + (size_t)(op.r0 + ro) + (size_t)op.c0 * ldc;
     p.M = M; p.N = N; p.K = K;
     p.lda = 256; p.ldb = ldc; p.ldc = ldc;
+    if constexpr (ENV)
+      if (!up) { e.fU = envU; e.kbase = op.r0; }  // (ko == 0 for the lower forms)
     return true;
   }
   if (op.ainv) {  // X[r0:r0+w, c0:c1) <- inv(L11[r0/32]) * X, in place (one tile row, all of K is read before the stores)
@@ -154,6 +185,8 @@ __device__ inline bool resolve_op(const NodeDesc<T>* pn, const GemmOp& op, GemmP
     p.C = cp + (size_t)op.r0 + (size_t)op.c0 * ldc;
     p.M = w; p.N = N; p.K = w;
     p.lda = HS_PB; p.ldb = ldc; p.ldc = ldc;
+    if constexpr (ENV)
+      if (op.ainv == 1) { e.fU = envU; e.kbase = op.r0; }
     return true;
   }
   int r1 = min(op.r1, crows), c1 = min(op.c1, ccols), k1 = min(op.k1, ni);
@@ -165,6 +198,10 @@ __device__ inline bool resolve_op(const NodeDesc<T>* pn, const GemmOp& op, GemmP
   p.C = cp + (size_t)op.r0 + (size_t)op.c0 * ldc;
   p.M = M; p.N = N; p.K = K;
   p.lda = ldl; p.ldb = ldb; p.ldc = ldc;
+  if constexpr (ENV) {
+    e.fL = env;
+    e.fU = envU;
+  }
   return true;
 }
 
@@ -636,6 +673,10 @@ struct TileCfg<cplx> {
 
 
 
+// Device-side flop count of the plain updates (hsk_op_flops): the K-steps the tiles really ran, added up by gemm_op_env_kernel while
+// GemmOp::count is set -- launch_gemm_op then sends EVERY plain update there, dense ones included; gemm_op_kernel itself never counts
+__device__ double g_op_flops;
+
 template <class T>
 __device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* smem) {
   int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + TileCfg<T>::bn - 1) / TileCfg<T>::bn;
@@ -655,12 +696,55 @@ __device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* s
   }
 }
 
+// The same walk for a launch whose fronts may carry a block envelope (gemm_op_env_kernel, trsm_inv_env_kernel below)
+template <class T>
+__device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* smem, const EnvClip* e, int count) {
+  int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + TileCfg<T>::bn - 1) / TileCfg<T>::bn;
+  int ntiles = tiles_m * tiles_n;
+  // a launch may be capped to fewer workgroups than tiles (GemmOp::cap): each workgroup then walks the tiles
+  // bid, bid + gridDim.x, ... -- with gridDim.x a multiple of 8 they all stay in the same XCD chunk of the remap
+  const int shift = (int)((gridDim.x * blockIdx.y) & 7u);
+  bool ran = false;
+  for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+    int t = xcd_remap_shift(bid, ntiles, (gridDim.x & 7u) ? shift : 0);  // (a walking workgroup keeps its XCD only when gridDim.x is a multiple of 8: then shift == 0)
+    int tm, tn;
+    tile_coords(t, tiles_m, tiles_n, tm, tn);
+    int dk = 0;
+    {
+      // Leaf front with a block envelope: everything here is uniform over the workgroup and done once per tile; the tile code is handed a
+      // problem whose A, B and K are already shifted.  dk is a multiple of 32: the 16-byte operand loads keep their alignment and the
+      // remaining BK-steps hold the same k as before, in the same order -- every stored value keeps its bits.
+      const int m_lo = tm * BM, n_lo = tn * TileCfg<T>::bn;
+      const int m_hi = min(m_lo + BM, p.M), n_hi = min(n_lo + TileCfg<T>::bn, p.N);
+      if (e->fL || e->fU) {
+        dk = hs_env_kstart(*e, m_lo, m_hi, n_lo, n_hi) - e->kbase;
+        if (dk >= p.K) continue;  // only exact zeros left: nothing to subtract / zeros stay zeros (no LDS touched, so no barrier either)
+      }
+      if (count && threadIdx.x == 0)  // (test hook: one atomic per tile, i.e. per workgroup unless the launch walks)
+        atomicAdd(&g_op_flops, (sizeof(T) == 16 ? 8.0 : 2.0) * (double)(m_hi - m_lo) * (double)(n_hi - n_lo) * (double)(p.K - dk));
+    }
+    const size_t da = (size_t)dk * p.lda;  // the problem is shifted in place and put back after the tile (a shifted copy next to the original
+    p.A += da;                             // keeps both alive in scalar registers through the tile code)
+    p.B += dk;
+    p.K -= dk;
+    if (ran) __syncthreads();  // this tile re-uses the LDS stages of the last one that ran
+    ran = true;
+    if constexpr (sizeof(T) == 8)
+      gemm_tile_d<128>(p, tm, tn, minus, smem);
+    else
+      gemm_tile_z(p, tm, tn, minus, smem);
+    p.A -= da;
+    p.B -= dk;
+    p.K += dk;
+  }
+}
+
 template <class T>
 __global__ __launch_bounds__(256, 2) void gemm_op_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   GemmProb<T> p;
   if (op.prio) __builtin_amdgcn_s_setprio(2);  // look-ahead panel work sharing CUs with the big trailing update
-  if (!resolve_op(nodes + blockIdx.y, op, p)) return;
+  if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
   gemm_dispatch<T>(p, true, smem);
 }
 // The TRSM base case (X <- inv(diagonal block) * X, in place) runs the same tile code under its own name, so that
@@ -670,8 +754,31 @@ __global__ __launch_bounds__(256, 2) void trsm_inv_kernel(const NodeDesc<T>* __r
   extern __shared__ __attribute__((aligned(16))) double smem[];
   GemmProb<T> p;
   __builtin_amdgcn_s_setprio(2);
-  if (!resolve_op(nodes + blockIdx.y, op, p)) return;
+  if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
   gemm_dispatch<T>(p, false, smem);
+}
+// The two kernels again for launches with GemmOp::env (batches of leaf fronts under optimistic pivoting) or GemmOp::count: kernels of their
+// own, so that the dense launches above -- every level but the leaves, 87 % of the factorization -- keep the code they had: with the
+// clip inside gemm_op_kernel<double> its register allocation moved and the dense levels of Poisson 128^3 ran 10-14 % slower.
+template <class T>
+__global__ __launch_bounds__(256, 2) void gemm_op_env_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  GemmProb<T> p;
+  EnvClip e;
+  if (op.prio) __builtin_amdgcn_s_setprio(2);
+  if (op.ainv) return;  // (launch_gemm_op sends those to trsm_inv_env_kernel: lets the compiler drop the in-place forms and their growth check here)
+  if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
+  gemm_dispatch_env<T>(p, true, smem, &e, op.count);
+}
+template <class T>
+__global__ __launch_bounds__(256, 2) void trsm_inv_env_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  GemmProb<T> p;
+  EnvClip e;
+  __builtin_amdgcn_s_setprio(2);
+  if (!op.ainv) return;  // (plain updates run as gemm_op_env_kernel)
+  if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
+  gemm_dispatch_env<T>(p, false, smem, &e, 0);
 }
 
 // Accounting of the grouped products (hs_probs_stats, include/hs_kernels.h): the descriptors live on the device, so the kernel itself adds
@@ -714,13 +821,46 @@ template <class T>
 __global__ void resolve_dump_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op, GemmProb<T>* out, int* ok) {
   GemmProb<T> p;
   memset(&p, 0, sizeof p);
-  ok[blockIdx.x] = resolve_op(nodes + blockIdx.x, op, p) ? 1 : 0;
+  ok[blockIdx.x] = resolve_op<T, false>(nodes + blockIdx.x, op, p, nullptr) ? 1 : 0;
   out[blockIdx.x] = p;
 }
 
+// Switches of the leaf envelope and of the device-side flop count (test hooks, include/hs_kernels.h)
+namespace {
+std::atomic<int> g_env_on{-1};      // -1: not read yet (HS_LEAF_ENVELOPE, default on)
+std::atomic<int> g_op_count_on{0};
+}  // namespace
+bool hs_envelope_enabled() {
+  int v = g_env_on.load();
+  if (v < 0) {
+    const char* e = getenv("HS_LEAF_ENVELOPE");
+    v = (e && e[0] == '0') ? 0 : 1;
+    g_env_on.store(v);
+  }
+  return v != 0;
+}
+extern "C" int hsk_envelope_enable(int on) {  // returns the previous setting
+  const int prev = hs_envelope_enabled() ? 1 : 0;
+  g_env_on.store(on ? 1 : 0);
+  return prev;
+}
+extern "C" int hsk_op_flops_mode(int on) {  // resets the counter
+  (void)hipDeviceSynchronize();
+  g_op_count_on.store(on ? 1 : 0);
+  const double z = 0.0;
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_op_flops), &z, sizeof z) == hipSuccess ? 0 : -6;
+}
+extern "C" int hsk_op_flops(double* out) {
+  if (!out) return -1;
+  if (hipDeviceSynchronize() != hipSuccess) return -6;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_op_flops), sizeof *out) == hipSuccess ? 0 : -6;
+}
+
 template <class T>
-void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s) {
+void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s) {
   if (nbatch <= 0 || maxM <= 0 || maxN <= 0) return;
+  GemmOp op = op_in;
+  op.count = (!op.ainv && g_op_count_on.load(std::memory_order_relaxed)) ? 1 : 0;
   {
     static int dbg = -1;
     if (dbg < 0) {
@@ -751,14 +891,28 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
   }
   int tiles = ((maxM + BM - 1) / BM) * ((maxN + TileCfg<T>::bn - 1) / TileCfg<T>::bn);
   if (op.cap > 0 && tiles > op.cap) tiles = std::max(8, op.cap / 8 * 8);
+  // Enveloped launch (a batch of leaf fronts): most tiles of the bounding box are empty.  A workgroup per tile would start, read its
+  // descriptor and leave; instead a quarter as many workgroups (HS_ENV_WALK, 1: off) walk the tiles, so that an empty tile costs a table
+  // look-up inside a running workgroup.  The batch itself keeps the chip full (hundreds of fronts).
+  if (op.env && !(op.cap > 0)) {
+    static const int walk = getenv("HS_ENV_WALK") ? atoi(getenv("HS_ENV_WALK")) : 4;
+    if (walk > 1 && tiles >= 32 && (long long)tiles * nbatch >= 4096) tiles = std::max(8, tiles / walk / 8 * 8);
+  }
   constexpr int lds_bytes = TileCfg<T>::smem_doubles * 8;
   static bool attr_set = false;
   if (!attr_set) {  // > 64 KiB of LDS per workgroup needs the opt-in
     (void)hipFuncSetAttribute((const void*)gemm_op_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     (void)hipFuncSetAttribute((const void*)trsm_inv_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    (void)hipFuncSetAttribute((const void*)gemm_op_env_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    (void)hipFuncSetAttribute((const void*)trsm_inv_env_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     attr_set = true;
   }
-  if (op.ainv)
+  if (op.env || op.count) {
+    if (op.ainv)
+      hipLaunchKernelGGL(trsm_inv_env_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
+    else
+      hipLaunchKernelGGL(gemm_op_env_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
+  } else if (op.ainv)
     hipLaunchKernelGGL(trsm_inv_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
   else
     hipLaunchKernelGGL(gemm_op_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);

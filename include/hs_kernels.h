@@ -76,6 +76,25 @@ int hsk_bisect_perm(int64_t n, const int64_t* colptr, const int64_t* rowval, int
 int hs_probs_stats_mode(int mode);
 int hs_probs_stats(double* out3);
 
+/* Block envelope of leaf fronts (optimistic pivoting eliminates a leaf inside the envelope of its sparsity pattern, taken per 32-row /
+ * 32-column block).
+ *   hsk_leaf_envelope   : host only, no device.  The builder the analysis runs for every leaf: CSC pattern of A (1-based colptr / rowval, n
+ *                         columns), fidx = ni + nb global ids (0-based) in front order [int; bnd]; firstL / firstU receive
+ *                         ceil(ni / 32) + ceil(nb / 32) entries each (interior blocks first, boundary blocks counted from the start of the
+ *                         boundary part): first interior column / row, rounded down to a multiple of 32, with a structural entry in the
+ *                         block's rows / columns; 2^30 = none.  Returns 0, or -1 for a bad argument.
+ *   hsk_envelope_enable : 1 / 0 turns the envelope on / off for the factorizations that follow (default: on unless HS_LEAF_ENVELOPE=0);
+ *                         returns the previous setting.  Off, every front is eliminated as a dense matrix.
+ *   hsk_op_flops_mode   : 1: the plain updates add the flops of the K-steps they really run to a device counter (one atomic per tile);
+ *                         resets the counter.  Counting changes which kernel runs: while it is on, every plain update -- of dense fronts
+ *                         too -- is launched as `gemm_op_env_kernel` (the same tile code; `gemm_op_kernel` holds no counter).
+ *                         hsk_op_flops(out) reads the counter (synchronises the device): equals hs_stats.gemm_flops.
+ *   (hsk_leaf_envelope checks fidx, colptr and rowval against n.) */
+int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL, int32_t* firstU);
+int hsk_envelope_enable(int on);
+int hsk_op_flops_mode(int on);
+int hsk_op_flops(double* out);
+
 /* Microseconds per ROUND TRIP (two exchanges) between workgroup 0 and workgroup `peer` of one launch through agent-scope atomic stores and polled
  * loads -- the exchange primitive of the dataflow sweeps of ldiv! (kernels_solve_wide.hip).  peer = 1: another XCD, peer = 8: the same XCD. */
 double hsk_flow_pingpong_us(int peer, int iters);
