@@ -14,5 +14,5 @@ from .solver import SolverOptions, chkopts, factor, factorize, FactorNode, Trans
 from ._lib import DimensionMismatch, SingularException, DeviceError, UnsupportedError  # noqa: F401,E402
 from . import _lib  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
-from .gmres import gmres  # noqa: F401,E402
+from .gmres import gmres, gmres_block, gmres_block_info  # noqa: F401,E402
 from . import hss  # noqa: F401,E402

@@ -1,0 +1,730 @@
+// hs_gmres_block.hip -- right-preconditioned restarted GMRES on a block of right-hand sides in lockstep (hs_gmres_block_*, include/hs_solver.h).
+//
+// nrhs independent Arnoldi processes advance together: every column keeps its own Krylov space, Hessenberg matrix, rotations and stopping
+// test, exactly the iteration of hs_gmres.hip (classical Gram-Schmidt with one re-orthogonalisation pass, Givens rotations,
+// x = x0 + Pr^-1 V y), but a step applies the preconditioner to all active columns with ONE hs_ldiv_block_dev_* call (the factors are read
+// once per 32 columns, not once per column), multiplies by A with ONE CSR SpMM, runs the orthogonalisations as batched kernels (column =
+// blockIdx.y) and reads 2 nact doubles to the host with one synchronisation.  This is not block-Krylov: a column returns what hs_gmres_*
+// returns for it alone (to the rounding by which hs_ldiv_block_* and hs_ldiv_* differ).
+//
+// Layout: every n x nact object is a column-major block with leading dimension ldv (n rounded up to an even value); the basis is
+// V[(j G + c) ldv + i] (G: group width), so V_j is directly the dB argument of hs_ldiv_block_dev_*.  A column that converges, breaks down or
+// exhausts maxiter is frozen for the rest of the restart cycle by a device-resident mask (its state is no longer written); at cycle boundaries
+// the columns that go on are gathered into the leading columns ("slots") of the residual block, so the block solve runs ceil(nact / 32) chunks.
+// X and B are never repacked: the kernels that touch them take a slot -> column map.
+//
+// Determinism: no atomics, every reduction in a fixed order that depends on the row index alone, so a column's results do not depend on its
+// slot, on the other columns, on G or on compaction.
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/hs_kernels.h"
+#include "hs_gmres_common.h"
+#include "hs_solve_multi.h"
+
+namespace {
+
+// Y[:, c] = A X[:, xmap[c]]   or, with B,   Y[:, c] = B[:, bmap[c]] - A X[:, xmap[c]]   (CSR, 0-based; null map: identity), c < nc.
+// A workgroup owns 256 rows and walks the columns CB at a time, lanes along rows: X[:, c] and Y[:, c] are read and written contiguously, and
+// rowptr / colind / val of the row tile are read once per chunk of CB columns, not once per column (the chunks after the first follow it in
+// the same workgroup and should find them in L2; that is not measured).  Per (row, column) the sum runs over e in
+// stored order with Scal<T>::fma, as spmv_csr_kernel (hs_gmres.hip) does.
+template <class T, int CB>
+__global__ __launch_bounds__(256) void spmm_csr_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ colind, const T* __restrict__ val,
+                                                       const T* __restrict__ X, int64_t ldx, const int64_t* __restrict__ xmap, T* __restrict__ Y, int64_t ldy,
+                                                       const T* __restrict__ B, int64_t ldb, const int64_t* __restrict__ bmap, int64_t n, int nc) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
+  for (int c0 = 0; c0 < nc; c0 += CB) {
+    T acc[CB];
+    const T* xp[CB];
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+      const int cc = min(c0 + c, nc - 1);  // a ragged chunk recomputes its last column and does not store it
+      xp[c] = X + (size_t)(xmap ? xmap[cc] : cc) * ldx;
+      acc[c] = Scal<T>::zero();
+    }
+    for (int64_t e = e0; e < e1; ++e) {
+      const T a = val[e];
+      const int32_t j = colind[e];
+#pragma unroll
+      for (int c = 0; c < CB; ++c) acc[c] = Scal<T>::fma(a, xp[c][j], acc[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+      const int cc = c0 + c;
+      if (cc < nc) Y[(size_t)cc * ldy + i] = B ? B[(size_t)(bmap ? bmap[cc] : cc) * ldb + i] - acc[c] : acc[c];
+    }
+  }
+}
+template <class T>
+void launch_spmm(const int64_t* rowptr, const int32_t* colind, const T* val, const T* X, int64_t ldx, const int64_t* xmap, T* Y, int64_t ldy, const T* B, int64_t ldb,
+                 const int64_t* bmap, int64_t n, int nc, hipStream_t s) {
+  constexpr int CB = sizeof(T) == 16 ? 4 : 8;
+  hipLaunchKernelGGL((spmm_csr_kernel<T, CB>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rowptr, colind, val, X, ldx, xmap, Y, ldy, B, ldb, bmap, n, nc);
+}
+
+// The batched forms of the kernels of hs_gmres.hip: the column (slot) is blockIdx.y, a frozen column (mask[c] == 0) is skipped.
+// part[(c nblk + blockIdx.x) k1 + j] = sum over the block's 1024 rows of conj(V_j[i, c]) W[i, c],  j = 0..k;  w stays in registers
+template <class T>
+__global__ __launch_bounds__(256) void bdot_kernel(const T* __restrict__ V, int64_t ldv, int64_t jstride, int k1, const T* __restrict__ W, T* __restrict__ part, int64_t n,
+                                                   const int* __restrict__ mask) {
+  __shared__ T sh[256];
+  const int c = blockIdx.y;
+  if (!mask[c]) return;
+  const T* Vc = V + (size_t)c * ldv;
+  const T* w = W + (size_t)c * ldv;
+  T* pc = part + ((size_t)c * gridDim.x + blockIdx.x) * k1;
+  const int64_t i0 = (int64_t)blockIdx.x * 1024;
+  T wv[4];
+  for (int t = 0; t < 4; ++t) {
+    const int64_t i = i0 + t * 256 + threadIdx.x;
+    wv[t] = i < n ? w[i] : Scal<T>::zero();
+  }
+  for (int j = 0; j < k1; ++j) {
+    T acc = Scal<T>::zero();
+    for (int t = 0; t < 4; ++t) {
+      const int64_t i = i0 + t * 256 + threadIdx.x;
+      if (i < n) acc = Scal<T>::fma(conj_(Vc[(size_t)j * jstride + i]), wv[t], acc);
+    }
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+      if ((int)threadIdx.x < st) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + st];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) pc[j] = sh[0];
+    __syncthreads();
+  }
+}
+// h[c hs + j] = sum over blocks of part[(c nblk + b) k1 + j], hacc += the same   (one workgroup per column; fixed order)
+template <class T>
+__global__ __launch_bounds__(256) void breduce_kernel(const T* __restrict__ part, int nblk, int k1, T* __restrict__ h, T* __restrict__ hacc, int hs, const int* __restrict__ mask) {
+  __shared__ T sh[256];
+  const int c = blockIdx.x;
+  if (!mask[c]) return;
+  const T* pc = part + (size_t)c * nblk * k1;
+  for (int j = 0; j < k1; ++j) {
+    T acc = Scal<T>::zero();
+    for (int b = threadIdx.x; b < nblk; b += 256) acc = acc + pc[(size_t)b * k1 + j];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+      if ((int)threadIdx.x < st) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + st];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      h[(size_t)c * hs + j] = sh[0];
+      if (hacc) hacc[(size_t)c * hs + j] = hacc[(size_t)c * hs + j] + sh[0];
+    }
+    __syncthreads();
+  }
+}
+// W[i, c] -= sum_j h[c hs + j] V_j[i, c]
+template <class T>
+__global__ __launch_bounds__(256) void baxpy_kernel(const T* __restrict__ V, int64_t ldv, int64_t jstride, int k1, const T* __restrict__ h, int hs, T* __restrict__ W, int64_t n,
+                                                    const int* __restrict__ mask) {
+  __shared__ T sh[GM_MAXK + 1];
+  const int c = blockIdx.y;
+  if (!mask[c]) return;
+  if ((int)threadIdx.x < k1) sh[threadIdx.x] = h[(size_t)c * hs + threadIdx.x];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const T* Vc = V + (size_t)c * ldv;
+  T acc = W[(size_t)c * ldv + i];
+  for (int j = 0; j < k1; ++j) acc = Scal<T>::fnma(sh[j], Vc[(size_t)j * jstride + i], acc);
+  W[(size_t)c * ldv + i] = acc;
+}
+// cycle end: out[:, c] = x[:, c] + sum_{j < kused[c]} y[c ys + j] V_j[:, c], every column with its own kused.  x null: out = V y (slot
+// order, ld ldo); else x = out = the caller's X through the slot -> column map (the unpreconditioned update)
+template <class T>
+__global__ __launch_bounds__(256) void bcombine_kernel(const T* __restrict__ V, int64_t ldv, int64_t jstride, const T* __restrict__ y, int ys, const int* __restrict__ kused,
+                                                       T* __restrict__ X, int64_t ldx, const int64_t* __restrict__ xmap, T* __restrict__ out, int64_t ldo, int64_t n) {
+  __shared__ T sh[GM_MAXK + 1];
+  const int c = blockIdx.y;
+  const int k = kused[c];
+  if ((int)threadIdx.x < k) sh[threadIdx.x] = y[(size_t)c * ys + threadIdx.x];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  T* dst = X ? X + (size_t)xmap[c] * ldx : out + (size_t)c * ldo;
+  const T* Vc = V + (size_t)c * ldv;
+  T acc = X ? dst[i] : Scal<T>::zero();
+  for (int j = 0; j < k; ++j) acc = Scal<T>::fma(sh[j], Vc[(size_t)j * jstride + i], acc);
+  dst[i] = acc;
+}
+// X[:, xmap[c]] += Z[:, c]   (the preconditioned update; what combine_kernel of hs_gmres.hip computes with y = 1)
+template <class T>
+__global__ __launch_bounds__(256) void badd_kernel(const T* __restrict__ Z, int64_t ldz, T* __restrict__ X, int64_t ldx, const int64_t* __restrict__ xmap, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  T* x = X + (size_t)xmap[blockIdx.y] * ldx;
+  x[i] = Scal<T>::fma(Scal<T>::one(), Z[(size_t)blockIdx.y * ldz + i], x[i]);
+}
+template <class T>
+__global__ __launch_bounds__(256) void bnorm2_part_kernel(const T* __restrict__ W, int64_t ldw, double* __restrict__ part, int64_t n, const int* __restrict__ mask) {
+  __shared__ double sh[256];
+  const int c = blockIdx.y;
+  if (mask && !mask[c]) return;
+  const T* w = W + (size_t)c * ldw;
+  double acc = 0.0;
+  for (int t = 0; t < 4; ++t) {
+    const int64_t i = (int64_t)blockIdx.x * 1024 + t * 256 + threadIdx.x;
+    if (i < n) acc += abs2_(w[i]);
+  }
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[(size_t)c * gridDim.x + blockIdx.x] = sh[0];
+}
+// out[c ostride] = sqrt(sum of the column's partial sums)
+__global__ __launch_bounds__(256) void bnorm2_final_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out, int ostride, const int* __restrict__ mask) {
+  __shared__ double sh[256];
+  const int c = blockIdx.x;
+  if (mask && !mask[c]) return;
+  double acc = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += 256) acc += part[(size_t)c * nblk + b];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[(size_t)c * ostride] = sqrt(sh[0]);
+}
+// V[i, c] = W[i, c] / nrm[c nstride]  (a zero norm copies: breakdown is handled through the residual estimate)
+template <class T>
+__global__ __launch_bounds__(256) void bscale_into_kernel(const T* __restrict__ W, int64_t ldw, const double* __restrict__ nrm, int nstride, T* __restrict__ V, int64_t ldv,
+                                                          int64_t n, const int* __restrict__ mask) {
+  const int c = blockIdx.y;
+  if (mask && !mask[c]) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double a = nrm[(size_t)c * nstride];
+  const T w = W[(size_t)c * ldw + i];
+  V[(size_t)c * ldv + i] = a > 0.0 ? scale_(w, 1.0 / a) : w;
+}
+// cycle boundary: Rn[:, c] = R[:, src[c]]
+template <class T>
+__global__ __launch_bounds__(256) void bgather_kernel(const T* __restrict__ R, T* __restrict__ Rn, int64_t ld, const int* __restrict__ src, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  Rn[(size_t)blockIdx.y * ld + i] = R[(size_t)src[blockIdx.y] * ld + i];
+}
+
+// Device-resident small state of the slots in one restart cycle, slot c at c times the stride: H ((m+1) x m, ld m+1), cs, sn, g, the new
+// column h (and h2 of the second pass), y; {||w||, |g[k+1]|} adjacent in hnres; what decides freezing (tol, itleft) and its result (mask, kused)
+template <class T>
+struct GbSmall {
+  T *H, *cs, *sn, *g, *h, *h2, *y;
+  double* hnres;  // 2 per slot
+  double* beta;   // ||r|| at the start of the cycle
+  double* tol;
+  int* itleft;    // iterations the column may still take
+  int* mask;      // 1: the column advances in this cycle
+  int* kused;
+  int64_t* col;   // slot -> column of the caller's B / X
+  int ld, sH, s1, s2;  // strides: H, (m+1)-arrays, (m+2)-arrays
+};
+// one thread per slot: the rotations of givens_kernel (hs_gmres.hip) on the slot's own state, then the freezing decision the host repeats from
+// the same two doubles
+template <class T>
+__global__ __launch_bounds__(64) void bgivens_kernel(GbSmall<T> S, int k, int nact) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= nact || !S.mask[c]) return;
+  T* Hc = S.H + (size_t)c * S.sH + (size_t)k * S.ld;
+  const T* h = S.h + (size_t)c * S.s2;
+  T* cs = S.cs + (size_t)c * S.s1;
+  T* sn = S.sn + (size_t)c * S.s1;
+  T* g = S.g + (size_t)c * S.s2;
+  const double hn = S.hnres[2 * c];
+  for (int i = 0; i <= k; ++i) Hc[i] = h[i];
+  T hk1 = Scal<T>::zero();
+  *((double*)&hk1) = hn;  // real part = ||w||
+  Hc[k + 1] = hk1;
+  for (int i = 0; i < k; ++i) {
+    const T t = cs[i] * Hc[i] + sn[i] * Hc[i + 1];
+    Hc[i + 1] = Scal<T>::zero() - conj_(sn[i]) * Hc[i] + cs[i] * Hc[i + 1];
+    Hc[i] = t;
+  }
+  const T a = Hc[k], b = Hc[k + 1];
+  const double aa = absT(a), den = sqrt(aa * aa + absT(b) * absT(b));
+  T cc = Scal<T>::one(), s = Scal<T>::zero();
+  if (den != 0.0) {
+    cc = Scal<T>::zero();
+    *((double*)&cc) = aa / den;
+    const T ph = aa > 0.0 ? scale_(a, 1.0 / aa) : Scal<T>::one();
+    s = scale_(ph * conj_(b), 1.0 / den);
+  }
+  cs[k] = cc;
+  sn[k] = s;
+  Hc[k] = cc * a + s * b;
+  Hc[k + 1] = Scal<T>::zero();
+  g[k + 1] = Scal<T>::zero() - conj_(s) * g[k];
+  g[k] = cc * g[k];
+  const double res = absT(g[k + 1]);
+  S.hnres[2 * c + 1] = res;
+  S.kused[c] = k + 1;
+  const int left = S.itleft[c] - 1;
+  S.itleft[c] = left;
+  if (res <= S.tol[c] || hn == 0.0 || left <= 0) S.mask[c] = 0;
+}
+// y = triu(H[:k, :k]) \ g[:k] with the slot's own k = kused[c]
+template <class T>
+__global__ __launch_bounds__(64) void bhess_solve_kernel(GbSmall<T> S, int nact) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= nact) return;
+  const int k = S.kused[c];
+  const T* H = S.H + (size_t)c * S.sH;
+  const T* g = S.g + (size_t)c * S.s2;
+  T* y = S.y + (size_t)c * S.s1;
+  for (int i = k - 1; i >= 0; --i) {
+    T acc = g[i];
+    for (int j = i + 1; j < k; ++j) acc = Scal<T>::fnma(H[(size_t)i + (size_t)j * S.ld], y[j], acc);
+    y[i] = acc / H[(size_t)i + (size_t)i * S.ld];
+  }
+}
+template <class T>
+__global__ __launch_bounds__(64) void breset_kernel(GbSmall<T> S, int m, int nact) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= nact) return;
+  T* g = S.g + (size_t)c * S.s2;
+  for (int i = 0; i <= m; ++i) g[i] = Scal<T>::zero();
+  T b = Scal<T>::zero();
+  *((double*)&b) = S.beta[c];
+  g[0] = b;
+  S.kused[c] = 0;
+  S.mask[c] = 1;
+}
+
+template <class T>
+int prec_block(hs_handle* F, T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s);
+template <>
+int prec_block<double>(hs_handle* F, double* out, const double* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) {
+  return hs_ldiv_block_dev_d(F, 0, out, ld, in, ld, n, nc, (void*)s);
+}
+template <>
+int prec_block<cplx>(hs_handle* F, cplx* out, const cplx* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) {
+  return hs_ldiv_block_dev_z(F, 0, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
+}
+
+// figures of the calling thread's last hs_gmres_block_* call (hs_gmres_block_info)
+enum { GI_SECONDS = 0, GI_PREC_CALLS, GI_COL_APPS, GI_SPMM, GI_CYCLES, GI_GROUPS, GI_WORK_BYTES, GI_MAX_ACTIVE };
+thread_local double g_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+struct Column {  // host side of one right-hand side
+  int64_t col = 0;
+  double beta = 0.0, tol = 0.0;
+  int64_t it = 0;
+  bool conv = false, frozen = false;
+  std::vector<double> hist;
+};
+
+template <class T>
+struct Workspace {
+  int64_t ldv = 0, G = 0;
+  int m = 0, nblk = 0;
+  T *V = nullptr, *W = nullptr, *Z = nullptr, *R = nullptr, *R2 = nullptr, *part = nullptr;
+  double *dpart = nullptr;
+  int* src = nullptr;
+  GbSmall<T> S;
+};
+template <class T>
+size_t bytes_per_column(int64_t n, int m) {
+  const size_t ldv = (size_t)(n + 1) / 2 * 2, nblk = (size_t)(n + 1023) / 1024;
+  return ((size_t)(m + 5) * ldv + nblk * (m + 2) + (size_t)(m + 1) * m + 3 * (size_t)(m + 1) + 3 * (size_t)(m + 2)) * sizeof(T) + (nblk + 4) * sizeof(double) +
+         4 * sizeof(int) + sizeof(int64_t);
+}
+
+// one group of gc <= G columns (g0 .. g0 + gc of the caller's B and X, device pointers) from start to finish
+template <class T>
+void gmres_group(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t* colind, const T* val, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t g0, int gc,
+                 int use_x0, double reltol, double abstol, int64_t maxiter, Workspace<T>& ws, Column* cols, hipStream_t s) {
+  const int m = ws.m, nblk = ws.nblk;
+  const int64_t ldv = ws.ldv, jstride = ws.G * ldv;
+  GbSmall<T>& S = ws.S;
+  const unsigned gn = (unsigned)((n + 255) / 256);
+  std::vector<double> hd((size_t)2 * gc);
+  std::vector<int64_t> hcol((size_t)gc);
+  std::vector<double> hbeta((size_t)gc), htol((size_t)gc);
+  std::vector<int> hleft((size_t)gc), hsrc((size_t)gc);
+  auto read = [&](const double* d, int cnt) {
+    GM_HIP(hipMemcpyAsync(hd.data(), d, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s));
+    GM_HIP(hipStreamSynchronize(s));
+  };
+  auto norms = [&](const T* Wb, double* out, int ostride, int nc, const int* mask) {
+    hipLaunchKernelGGL(bnorm2_part_kernel<T>, dim3(nblk, nc), dim3(256), 0, s, Wb, ldv, ws.dpart, n, mask);
+    hipLaunchKernelGGL(bnorm2_final_kernel, dim3(nc), dim3(256), 0, s, (const double*)ws.dpart, nblk, out, ostride, mask);
+  };
+  auto residual = [&](int nc) {  // R[:, c] = B[:, col[c]] - A X[:, col[c]]
+    launch_spmm<T>(rowptr, colind, val, (const T*)X, ldx, (const int64_t*)S.col, ws.R, ldv, B, ldb, (const int64_t*)S.col, n, nc, s);
+    g_info[GI_SPMM] += 1;
+  };
+  // r0 = b - A x0, slots in the order of the columns
+  for (int c = 0; c < gc; ++c) hcol[(size_t)c] = g0 + c;
+  GM_HIP(hipMemcpyAsync(S.col, hcol.data(), sizeof(int64_t) * (size_t)gc, hipMemcpyHostToDevice, s));
+  GM_HIP(hipStreamSynchronize(s));
+  if (use_x0) {
+    residual(gc);
+  } else {
+    GM_HIP(hipMemset2DAsync(X + (size_t)g0 * ldx, sizeof(T) * (size_t)ldx, 0, sizeof(T) * (size_t)n, (size_t)gc, s));
+    GM_HIP(hipMemcpy2DAsync(ws.R, sizeof(T) * (size_t)ldv, B + (size_t)g0 * ldb, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)gc, hipMemcpyDeviceToDevice, s));
+  }
+  norms(ws.R, S.beta, 1, gc, nullptr);
+  read(S.beta, gc);
+  std::vector<Column*> cur((size_t)gc);
+  for (int c = 0; c < gc; ++c) {
+    Column& q = cols[c];
+    q.col = g0 + c;
+    q.beta = hd[(size_t)c];
+    q.tol = std::max(reltol * q.beta, abstol);
+    q.hist.push_back(q.beta);
+    q.conv = q.beta <= q.tol;
+    cur[(size_t)c] = &q;
+  }
+  for (;;) {
+    // the columns that go on move into the leading slots
+    std::vector<Column*> next;
+    bool moved = false;
+    for (size_t c = 0; c < cur.size(); ++c)
+      if (!cur[c]->conv && cur[c]->it < maxiter) {
+        moved = moved || c != next.size();
+        hsrc[next.size()] = (int)c;
+        next.push_back(cur[c]);
+      }
+    if (next.empty()) break;
+    const int nact = (int)next.size();
+    if (moved) {
+      GM_HIP(hipMemcpyAsync(ws.src, hsrc.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(bgather_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.R, ws.R2, ldv, (const int*)ws.src, n);
+      std::swap(ws.R, ws.R2);
+    }
+    cur.swap(next);
+    for (int c = 0; c < nact; ++c) {
+      Column& q = *cur[(size_t)c];
+      hcol[(size_t)c] = q.col;
+      hbeta[(size_t)c] = q.beta;
+      htol[(size_t)c] = q.tol;
+      hleft[(size_t)c] = (int)std::min<int64_t>(maxiter - q.it, 1 << 30);
+      q.frozen = false;
+    }
+    GM_HIP(hipMemcpyAsync(S.col, hcol.data(), sizeof(int64_t) * (size_t)nact, hipMemcpyHostToDevice, s));
+    GM_HIP(hipMemcpyAsync(S.beta, hbeta.data(), sizeof(double) * (size_t)nact, hipMemcpyHostToDevice, s));
+    GM_HIP(hipMemcpyAsync(S.tol, htol.data(), sizeof(double) * (size_t)nact, hipMemcpyHostToDevice, s));
+    GM_HIP(hipMemcpyAsync(S.itleft, hleft.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
+    GM_HIP(hipStreamSynchronize(s));  // the host arrays are reused
+    g_info[GI_CYCLES] += 1;
+    g_info[GI_MAX_ACTIVE] = std::max(g_info[GI_MAX_ACTIVE], (double)nact);
+    const unsigned gs = (unsigned)((nact + 63) / 64);
+    hipLaunchKernelGGL(bscale_into_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.R, ldv, (const double*)S.beta, 1, ws.V, ldv, n, (const int*)nullptr);
+    hipLaunchKernelGGL(breset_kernel<T>, dim3(gs), dim3(64), 0, s, S, m, nact);
+    int running = nact;
+    for (int k = 0; k < m && running > 0; ++k) {
+      const T* Vk = ws.V + (size_t)k * jstride;
+      const T* zz = Vk;
+      if (F) {
+        const int st = prec_block<T>(F, ws.Z, Vk, ldv, n, nact, s);
+        if (st != 0) throw st;
+        g_info[GI_PREC_CALLS] += 1;
+        g_info[GI_COL_APPS] += nact;
+        zz = ws.Z;
+      }
+      launch_spmm<T>(rowptr, colind, val, zz, ldv, (const int64_t*)nullptr, ws.W, ldv, (const T*)nullptr, 0, (const int64_t*)nullptr, n, nact, s);
+      g_info[GI_SPMM] += 1;
+      // classical Gram-Schmidt with one re-orthogonalisation pass, per column: h = V^H w; w -= V h; h2 = V^H w; w -= V h2; H[:, k] = h + h2
+      const int k1 = k + 1;
+      const int* mask = S.mask;
+      hipLaunchKernelGGL(bdot_kernel<T>, dim3(nblk, nact), dim3(256), 0, s, (const T*)ws.V, ldv, jstride, k1, (const T*)ws.W, ws.part, n, mask);
+      hipLaunchKernelGGL(breduce_kernel<T>, dim3(nact), dim3(256), 0, s, (const T*)ws.part, nblk, k1, S.h, (T*)nullptr, S.s2, mask);
+      hipLaunchKernelGGL(baxpy_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.V, ldv, jstride, k1, (const T*)S.h, S.s2, ws.W, n, mask);
+      hipLaunchKernelGGL(bdot_kernel<T>, dim3(nblk, nact), dim3(256), 0, s, (const T*)ws.V, ldv, jstride, k1, (const T*)ws.W, ws.part, n, mask);
+      hipLaunchKernelGGL(breduce_kernel<T>, dim3(nact), dim3(256), 0, s, (const T*)ws.part, nblk, k1, S.h2, S.h, S.s2, mask);
+      hipLaunchKernelGGL(baxpy_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.V, ldv, jstride, k1, (const T*)S.h2, S.s2, ws.W, n, mask);
+      norms(ws.W, S.hnres, 2, nact, mask);
+      hipLaunchKernelGGL(bscale_into_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.W, ldv, (const double*)S.hnres, 2, ws.V + (size_t)(k + 1) * jstride, ldv, n, mask);
+      hipLaunchKernelGGL(bgivens_kernel<T>, dim3(gs), dim3(64), 0, s, S, k, nact);
+      read(S.hnres, 2 * nact);  // the one synchronisation of the step
+      for (int c = 0; c < nact; ++c) {
+        Column& q = *cur[(size_t)c];
+        if (q.frozen) continue;
+        const double hn = hd[(size_t)2 * c], res = hd[(size_t)2 * c + 1];
+        ++q.it;
+        q.hist.push_back(res);
+        if (res <= q.tol || hn == 0.0 || q.it >= maxiter) {  // what bgivens_kernel decided for the mask
+          q.conv = res <= q.tol;
+          q.frozen = true;
+          --running;
+        }
+      }
+    }
+    // x += Pr^-1 (V y), H y = g, every column with its own k_used; then the true residuals
+    hipLaunchKernelGGL(bhess_solve_kernel<T>, dim3(gs), dim3(64), 0, s, S, nact);
+    if (F) {
+      hipLaunchKernelGGL(bcombine_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.V, ldv, jstride, (const T*)S.y, S.s1, (const int*)S.kused, (T*)nullptr, (int64_t)0,
+                         (const int64_t*)nullptr, ws.W, ldv, n);
+      const int st = prec_block<T>(F, ws.Z, ws.W, ldv, n, nact, s);
+      if (st != 0) throw st;
+      g_info[GI_PREC_CALLS] += 1;
+      g_info[GI_COL_APPS] += nact;
+      hipLaunchKernelGGL(badd_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.Z, ldv, X, ldx, (const int64_t*)S.col, n);
+    } else {
+      hipLaunchKernelGGL(bcombine_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.V, ldv, jstride, (const T*)S.y, S.s1, (const int*)S.kused, X, ldx,
+                         (const int64_t*)S.col, (T*)nullptr, (int64_t)0, n);
+    }
+    residual(nact);
+    norms(ws.R, S.beta, 1, nact, nullptr);
+    read(S.beta, nact);
+    for (int c = 0; c < nact; ++c) {
+      Column& q = *cur[(size_t)c];
+      q.beta = hd[(size_t)c];
+      q.conv = q.conv || q.beta <= q.tol;
+    }
+  }
+  GM_HIP(hipStreamSynchronize(s));
+}
+
+// G: the widest group (a multiple of the block solve's chunk width) whose workspace fits half of the free memory, HS_GMRES_BLOCK_GROUP overrides
+int64_t group_width(size_t per_col, int64_t nrhs) {
+  const int64_t KC = hs_ldiv_block_cols();
+  const int64_t all = std::min<int64_t>((nrhs + KC - 1) / KC * KC, 32768);  // the column is blockIdx.y
+  if (const char* e = getenv("HS_GMRES_BLOCK_GROUP")) {
+    const long long v = atoll(e);
+    if (v > 0) return std::min<int64_t>(all, (v + KC - 1) / KC * KC);
+  }
+  size_t fr = 0, tot = 0;
+  GM_HIP(hipMemGetInfo(&fr, &tot));
+  const int64_t fit = (int64_t)(fr / 2 / per_col);
+  if (fit >= all) return all;
+  if (fit < std::min<int64_t>(KC, nrhs)) {
+    hs_set_error(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_gmres_block_* needs %zu bytes for one group of %lld columns, half of the free device memory is %zu bytes",
+                 per_col * (size_t)std::min<int64_t>(KC, nrhs), (long long)std::min<int64_t>(KC, nrhs), fr / 2);
+    throw (int)HS_ERR_NOMEM;
+  }
+  return std::max<int64_t>(fit / KC * KC, std::min<int64_t>(KC, nrhs));
+}
+
+template <class T>
+int refused_by_block_solve(hs_handle* F, int64_t n);
+template <>
+int refused_by_block_solve<double>(hs_handle* F, int64_t n) { return hs_ldiv_block_dev_d(F, 0, nullptr, n, nullptr, n, n, 0, nullptr); }
+template <>
+int refused_by_block_solve<cplx>(hs_handle* F, int64_t n) { return hs_ldiv_block_dev_z(F, 0, nullptr, n, nullptr, n, n, 0, nullptr); }
+
+template <class T>
+int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where,
+                      int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  if (n <= 0 || nrhs < 0 || !colptr || !rowval || !nz) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs A (CSC) and nrhs >= 0");
+    return HS_ERR_ARGUMENT;
+  }
+  if (nrhs == 0) {
+    for (double& v : g_info) v = 0.0;
+    return HS_OK;
+  }
+  if (!B || !X || !iters || !converged || (const void*)B == (const void*)X) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs B, X (not aliasing B) and the two result arrays");
+    return HS_ERR_ARGUMENT;
+  }
+  if (where != 0 && where != 1) {
+    hs_set_error(HS_ERR_ARGUMENT, where, "ArgumentError: hs_gmres_block: where = %d (0: host pointers, 1: device pointers)", where);
+    return HS_ERR_ARGUMENT;
+  }
+  if (ldb < n || ldx < n) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block: ldb = %lld, ldx = %lld below n = %lld", (long long)ldb, (long long)ldx, (long long)n);
+    return HS_ERR_ARGUMENT;
+  }
+  if (F && (hs_size(F) != n || (hs_is_complex(F) != 0) != (sizeof(T) == 16))) {
+    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld", (long long)hs_size(F), (long long)hs_size(F),
+                 hs_is_complex(F) ? "ComplexF64" : "Float64", (long long)n, (long long)n);
+    return HS_ERR_DIMENSION;
+  }
+  // defaults of IterativeSolvers 0.9, as hs_gmres_*
+  if (restart <= 0) restart = std::min<int64_t>(20, n);
+  if (restart > GM_MAXK) {
+    hs_set_error(HS_ERR_ARGUMENT, restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)restart, GM_MAXK);
+    return HS_ERR_ARGUMENT;
+  }
+  if (maxiter < 0) maxiter = n;
+  if (!(reltol >= 0.0)) reltol = 1.4901161193847656e-08;
+  if (F) {  // what hs_ldiv_block_* refuses is refused here, before any device work: nothing is silently looped
+    const int st = refused_by_block_solve<T>(F, n);
+    if (st == HS_ERR_UNSUPPORTED) {
+      const std::string why = hs_last_error();
+      hs_set_error(HS_ERR_UNSUPPORTED, hs_last_error_info(), "hs_gmres_block_*: the block solve does not serve this preconditioner (%s); hs_gmres_* serves it, one right-hand side at a time",
+                   why.c_str());
+      return st;
+    }
+    if (st != 0) return st;
+  }
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
+    return HS_ERR_DEVICE;
+  }
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = HS_OK;
+  DevBuf buf;  // outlives the try block: after a throw the stream is drained below before the workspace is freed
+  try {
+    for (double& v : g_info) v = 0.0;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t* d_rp;
+    int32_t* d_ci;
+    T* d_v;
+    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+    const T* dB = B;
+    T* dX = X;
+    int64_t dldb = ldb, dldx = ldx;
+    if (where == 0) {  // the whole block goes up and comes down once
+      T* tb = buf.get<T>((size_t)n * nrhs);
+      T* tx = buf.get<T>((size_t)n * nrhs);
+      GM_HIP(hipMemcpy2D(tb, sizeof(T) * (size_t)n, B, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
+      if (use_x0) GM_HIP(hipMemcpy2D(tx, sizeof(T) * (size_t)n, X, sizeof(T) * (size_t)ldx, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
+      dB = tb;
+      dX = tx;
+      dldb = dldx = n;
+    }
+    const int m = (int)restart;
+    Workspace<T> ws;
+    const size_t per_col = bytes_per_column<T>(n, m);
+    ws.G = std::min<int64_t>(group_width(per_col, nrhs), nrhs);
+    ws.m = m;
+    ws.ldv = (n + 1) / 2 * 2;
+    ws.nblk = (int)((n + 1023) / 1024);
+    const size_t G = (size_t)ws.G, blk = G * (size_t)ws.ldv;
+    T* big = buf.get<T>((size_t)(m + 5) * blk);
+    ws.V = big;
+    ws.W = big + (size_t)(m + 1) * blk;
+    ws.Z = ws.W + blk;
+    ws.R = ws.Z + blk;
+    ws.R2 = ws.R + blk;
+    ws.part = buf.get<T>(G * ws.nblk * (m + 2));
+    ws.dpart = buf.get<double>(G * ws.nblk);
+    ws.src = buf.get<int>(G);
+    GbSmall<T>& S = ws.S;
+    S.ld = m + 1;
+    S.sH = (m + 1) * m;
+    S.s1 = m + 1;
+    S.s2 = m + 2;
+    S.H = buf.get<T>(G * S.sH);
+    S.cs = buf.get<T>(G * S.s1);
+    S.sn = buf.get<T>(G * S.s1);
+    S.y = buf.get<T>(G * S.s1);
+    S.g = buf.get<T>(G * S.s2);
+    S.h = buf.get<T>(G * S.s2);
+    S.h2 = buf.get<T>(G * S.s2);
+    S.hnres = buf.get<double>(2 * G);
+    S.beta = buf.get<double>(G);
+    S.tol = buf.get<double>(G);
+    S.itleft = buf.get<int>(G);
+    S.mask = buf.get<int>(G);
+    S.kused = buf.get<int>(G);
+    S.col = buf.get<int64_t>(G);
+    g_info[GI_WORK_BYTES] = (double)(per_col * G);
+    GM_HIP(hipEventCreate(&e0));
+    GM_HIP(hipEventCreate(&e1));
+    GM_HIP(hipEventRecord(e0, s));
+    // a frozen column's basis vectors still travel through the block solve: they must be finite from the first step on
+    GM_HIP(hipMemsetAsync(big, 0, sizeof(T) * (size_t)(m + 5) * blk, s));
+    std::vector<Column> cols((size_t)nrhs);
+    for (int64_t g0 = 0; g0 < nrhs; g0 += ws.G) {
+      const int gc = (int)std::min<int64_t>(ws.G, nrhs - g0);
+      gmres_group<T>(F, n, d_rp, d_ci, d_v, dB, dldb, dX, dldx, g0, gc, use_x0, reltol, abstol, maxiter, ws, cols.data() + g0, s);
+      g_info[GI_GROUPS] += 1;
+    }
+    GM_HIP(hipEventRecord(e1, s));
+    GM_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    GM_HIP(hipEventElapsedTime(&ms, e0, e1));
+    g_info[GI_SECONDS] = ms * 1e-3;
+    if (where == 0) GM_HIP(hipMemcpy2D(X, sizeof(T) * (size_t)ldx, dX, sizeof(T) * (size_t)n, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyDeviceToHost));
+    for (int64_t c = 0; c < nrhs; ++c) {
+      const Column& q = cols[(size_t)c];
+      iters[c] = q.it;
+      converged[c] = q.conv ? 1 : 0;
+      if (resnorm)
+        for (int64_t i = 0; i <= q.it; ++i) resnorm[(size_t)c * ((size_t)maxiter + 1) + (size_t)i] = q.hist[(size_t)i];
+    }
+  } catch (int code) {
+    rc = code;
+  } catch (const std::bad_alloc&) {
+    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
+    rc = HS_ERR_NOMEM;
+  }
+  if (rc != HS_OK) (void)hipStreamSynchronize((hipStream_t)stream);  // nothing in flight may outlive the workspace
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
+}
+
+// hsk_spmm_*: the SpMM kernel alone on host data
+template <class T>
+int spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy, int64_t nrhs) {
+  if (n <= 0 || nrhs < 1 || !colptr || !rowval || !nz || !X || !Y || ldx < n || ldy < n || (B && ldb < n)) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_spmm: n >= 1, nrhs >= 1, leading dimensions >= n and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  try {
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+      hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
+      return HS_ERR_DEVICE;
+    }
+    DevBuf buf;
+    int64_t* d_rp;
+    int32_t* d_ci;
+    T* d_v;
+    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+    T* dX = buf.get<T>((size_t)ldx * nrhs);
+    T* dY = buf.get<T>((size_t)ldy * nrhs);
+    T* dB = B ? buf.get<T>((size_t)ldb * nrhs) : nullptr;
+    GM_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
+    GM_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
+    if (B) GM_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
+    launch_spmm<T>(d_rp, d_ci, d_v, dX, ldx, (const int64_t*)nullptr, dY, ldy, dB, ldb, (const int64_t*)nullptr, n, (int)nrhs, (hipStream_t)0);
+    GM_HIP(hipDeviceSynchronize());
+    GM_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
+    return HS_OK;
+  } catch (int code) {
+    return code;
+  } catch (const std::bad_alloc&) {
+    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
+    return HS_ERR_NOMEM;
+  }
+}
+
+}  // namespace
+
+extern "C" int hs_gmres_block_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
+                                int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
+                                int64_t* iters, int* converged, void* stream) {
+  return gmres_block_entry<double>(Pr, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+extern "C" int hs_gmres_block_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
+                                int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
+                                int64_t* iters, int* converged, void* stream) {
+  return gmres_block_entry<cplx>(Pr, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm,
+                                 iters, converged, stream);
+}
+extern "C" int hs_gmres_block_info(double* out8) {
+  if (!out8) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block_info: null argument");
+    return HS_ERR_ARGUMENT;
+  }
+  for (int i = 0; i < 8; ++i) out8[i] = g_info[i];
+  return HS_OK;
+}
+extern "C" int hsk_spmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,
+                          int64_t ldy, int64_t nrhs) {
+  return spmm_hook<double>(n, colptr, rowval, nzval, X, ldx, B, ldb, Y, ldy, nrhs);
+}
+extern "C" int hsk_spmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,
+                          int64_t ldy, int64_t nrhs) {
+  return spmm_hook<cplx>(n, colptr, rowval, (const cplx*)nzval, (const cplx*)X, ldx, (const cplx*)B, ldb, (cplx*)Y, ldy, nrhs);
+}

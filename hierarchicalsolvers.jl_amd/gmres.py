@@ -19,7 +19,7 @@ import scipy.sparse as sp
 
 from . import _lib
 
-__all__ = ["gmres", "gmres_native", "gmres_device"]
+__all__ = ["gmres", "gmres_native", "gmres_device", "gmres_block", "gmres_block_info"]
 
 
 def _csc_fields(A, dtype):
@@ -77,3 +77,54 @@ def gmres_device(A, b_dev, solver, reltol=1e-9, abstol=0.0, restart=30, maxiter=
                   C.c_void_p(b_dev.data_ptr()), C.c_void_p(x.data_ptr()), 1, 0, float(reltol), float(abstol), int(restart), int(maxiter),
                   hist.ctypes.data_as(_lib.p_f64), C.byref(iters), C.byref(conv), stream))
     return x, [float(v) for v in hist[: iters.value + 1]]
+
+
+def gmres_block(A, B, Pr=None, reltol=None, abstol=0.0, restart=None, maxiter=None, log=False, X0=None):
+    """:func:`gmres` on every column of the ``n x nrhs`` block ``B`` in lockstep (``hs_gmres_block_{d,z}``): the columns share the restart
+    cycle and the Arnoldi index, so a step applies ``Pr`` to all active columns with one block solve (``hs_ldiv_block_dev_*``) and multiplies
+    by ``A`` with one SpMM.  Every column keeps its own Krylov space and stopping test and returns what :func:`gmres` returns for it alone
+    (to the rounding by which :func:`ldiv_block` and :func:`ldiv` differ).  ``Pr`` must be a handle the block solve serves
+    (:class:`UnsupportedError` otherwise: :func:`gmres` serves those).  Returns ``X`` or ``(X, [history dict per column])``; a 1-D ``B`` is
+    one column and returns a vector (and one history dict).  With ``log=True`` the history buffer is ``(maxiter + 1) x nrhs`` doubles: give a
+    ``maxiter`` when ``n`` and ``nrhs`` are both large (the default is ``n``)."""
+    n = A.shape[0]
+    B = np.asarray(B)
+    vec = B.ndim == 1
+    if B.shape[0] != n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, A is {n} x {n}")
+    cplx = np.iscomplexobj(A.data) or np.iscomplexobj(B) or (Pr is not None and Pr.dtype.kind == "c") or (X0 is not None and np.iscomplexobj(X0))
+    dt = np.complex128 if cplx else np.float64
+    colptr, rowval, nz = _csc_fields(A, dt)
+    Bm = np.asfortranarray(B.reshape(n, -1), dtype=dt)
+    k = Bm.shape[1]
+    if X0 is None:
+        X = np.zeros((n, k), dtype=dt, order="F")
+    else:
+        X = np.array(np.asarray(X0).reshape(n, -1), dtype=dt, order="F")
+        if X.shape != Bm.shape:
+            raise _lib.DimensionMismatch(f"DimensionMismatch: X0 is {X.shape[0]} x {X.shape[1]}, B is {n} x {k}")
+    maxit = n if maxiter is None else int(maxiter)
+    # (maxiter + 1) x nrhs doubles, of which the library writes iters[c] + 1 per column: with the default maxiter = n that is 8 n nrhs bytes of
+    # address space, so it is allocated only when the history is asked for
+    hist = np.zeros((maxit + 1, max(k, 1)), order="F") if log else None
+    iters = np.zeros(max(k, 1), dtype=np.int64)
+    conv = np.zeros(max(k, 1), dtype=np.int32)
+    L = _lib.lib()
+    fn = L.hs_gmres_block_z if cplx else L.hs_gmres_block_d
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _lib.check(fn(Pr._h if Pr is not None else None, n, colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz), vp(Bm), n, vp(X), n, k, 0,
+                  int(X0 is not None), -1.0 if reltol is None else float(reltol), float(abstol), -1 if restart is None else int(restart), maxit,
+                  hist.ctypes.data_as(_lib.p_f64) if log else None, iters.ctypes.data_as(_lib.p_i64), conv.ctypes.data_as(C.POINTER(C.c_int)), None))
+    res = X[:, 0] if vec else X
+    if log:
+        chs = [dict(resnorm=[float(v) for v in hist[: iters[c] + 1, c]], isconverged=bool(conv[c]), iters=int(iters[c])) for c in range(k)]
+        return res, (chs[0] if vec else chs)
+    return res
+
+
+def gmres_block_info():
+    """Figures of this thread's last :func:`gmres_block` call (``hs_gmres_block_info``)."""
+    out = np.zeros(8)
+    _lib.check(_lib.lib().hs_gmres_block_info(out.ctypes.data_as(_lib.p_f64)))
+    return {"seconds": float(out[0]), "prec_calls": int(out[1]), "column_applications": int(out[2]), "spmm_launches": int(out[3]), "cycles": int(out[4]),
+            "groups": int(out[5]), "workspace_bytes": int(out[6]), "max_active": int(out[7])}

@@ -63,6 +63,13 @@ int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t 
 int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
                      int minus, int trap);
 
+/* The CSR SpMM of hs_gmres_block_* (hs_gmres_block.hip) on host data: Y = A X (B == NULL) or Y = B - A X, A n x n CSC with 1-based colptr /
+ * rowval, X, B, Y column-major n x nrhs blocks (ldx, ldb, ldy >= n; rows of Y beyond n are left as they are). */
+int hsk_spmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,
+               int64_t ldy, int64_t nrhs);
+int hsk_spmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,
+               int64_t ldy, int64_t nrhs);
+
 /* Host-only: the order in which the HSS form of a front's interior block lists its DOFs (hs_options.hss_d): recursive bisection of
  * the graph of A (1-based CSC pattern colptr / rowval of the n x n matrix) restricted to the ni DOFs `ids` (1-based), split where the
  * HSS cluster tree splits its index range.  perm_out[new position] = position in `ids` (0-based). */

@@ -308,6 +308,33 @@ int hs_gmres_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* r
 int hs_gmres_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
                double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream);
 
+/* The same iteration on an n x nrhs block of right-hand sides in lockstep (hs_gmres_block.hip): nrhs independent GMRES processes share the
+ * restart cycle and the Arnoldi index, so a step costs ONE block preconditioner application (hs_ldiv_block_dev_* on the active columns: the
+ * factors are read once per chunk of columns), ONE sparse product with a block, batched orthogonalisations and one host synchronisation.
+ * This is not block-Krylov: every column keeps its own Krylov space, Hessenberg matrix and stopping test, and column c returns what hs_gmres_*
+ * returns for B[:, c] alone -- same defaults, restart limit, tolerance tol_c = max(reltol * ||r0_c||, abstol), breakdown handling -- to the
+ * rounding by which hs_ldiv_block_* and hs_ldiv_* differ.  A zero column returns iters = 0, converged, X[:, c] = 0.
+ * B, X: column-major blocks (ldb, ldx >= n) on the host (where = 0) or the device (where = 1); X may not alias B.  use_x0 != 0: X holds the
+ * initial guesses.  resnorm (may be NULL): (maxiter + 1) x nrhs column-major, column c receives iters[c] + 1 residual norms; iters, converged:
+ * nrhs entries.  nrhs = 0 touches nothing.  Pr = NULL runs unpreconditioned.
+ * A column that converges, breaks down or reaches maxiter is frozen for the rest of the cycle; at cycle boundaries the columns that go on are
+ * compacted, so the block solve runs ceil(nact / chunk) chunks.  Columns are processed in groups of G (a multiple of the block solve's chunk
+ * width, chosen per call so that the workspace of (restart + 5) G n elements takes at most half of the free device memory; HS_ERR_NOMEM when
+ * not even one chunk fits; HS_GMRES_BLOCK_GROUP in the environment overrides G, read per call).  No atomics, fixed summation orders: two calls
+ * return the same bits, and X[:, c], resnorm[:, c], iters[c] do not depend on the values, number or order of the other columns, nor on G.
+ * Refused before any device work, X untouched: HS_ERR_UNSUPPORTED for a Pr that hs_ldiv_block_* refuses (HSS interior blocks, more than one
+ * rank: hs_gmres_* serves those, one right-hand side at a time); HS_ERR_ARGUMENT for null pointers, X aliasing B, restart above the limit, ldb
+ * or ldx < n, where outside 0:1; HS_ERR_DIMENSION for a handle of another size or element type. */
+int hs_gmres_block_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X, int64_t ldx,
+                     int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged,
+                     void* stream);
+int hs_gmres_block_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X, int64_t ldx,
+                     int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged,
+                     void* stream);
+/* the calling thread's last hs_gmres_block_* call: out8 = {seconds on the device, block preconditioner calls, column-applications summed over
+ * those calls, SpMM launches, restart cycles (summed over the groups), column groups, workspace bytes, the largest active-column count} */
+int hs_gmres_block_info(double* out8);
+
 int64_t hs_maxrank(const hs_handle* F); /* factornode.jl:49-57: largest of rank(L), rank(R) and the HSS ranks the factorization
                                            holds (hssrank of the interior blocks kept as HSS, hs_options.hss_d); 0 for the dense path */
 /* ranks of one front's Gauss transforms (0 = dense); returns 1 if the front is compressed, 0 if not, <0 on error */
