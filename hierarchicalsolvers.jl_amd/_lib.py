@@ -73,6 +73,7 @@ EXPORTS = [
     "hs_options_default", "hs_factor_d", "hs_factor_z", "hs_ldiv_d", "hs_ldiv_z", "hs_ldiv_dev_d", "hs_ldiv_dev_z",
     "hs_ldiv_t_d", "hs_ldiv_t_z", "hs_ldiv_dev_t_d", "hs_ldiv_dev_t_z",
     "hs_ldiv_block_d", "hs_ldiv_block_z", "hs_ldiv_block_dev_d", "hs_ldiv_block_dev_z", "hs_ldiv_block_info", "hsk_multi_prob_d", "hsk_multi_prob_z",
+    "hs_ldiv_block_t_d", "hs_ldiv_block_t_z", "hs_ldiv_block_dev_t_d", "hs_ldiv_block_dev_t_z", "hsk_multi_prob_t_d", "hsk_multi_prob_t_z",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_logabsdet", "hs_selinv", "hs_selinv_info",
     "hs_maxrank", "hs_is_complex", "hs_size", "hs_free", "hs_last_error", "hs_last_error_info", "hs_get_stats",
@@ -146,10 +147,19 @@ def lib():
     for f in (L.hs_ldiv_block_dev_d, L.hs_ldiv_block_dev_z):
         f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
         f.restype = C.c_int
+    for f in (L.hs_ldiv_block_t_d, L.hs_ldiv_block_t_z):
+        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
+        f.restype = C.c_int
+    for f in (L.hs_ldiv_block_dev_t_d, L.hs_ldiv_block_dev_t_z):
+        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
+        f.restype = C.c_int
     L.hs_ldiv_block_info.argtypes = [vp, p_f64]
     L.hs_ldiv_block_info.restype = C.c_int
     for f in (L.hsk_multi_prob_d, L.hsk_multi_prob_z):
         f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int]
+        f.restype = C.c_int
+    for f in (L.hsk_multi_prob_t_d, L.hsk_multi_prob_t_z):
+        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, C.c_int]
         f.restype = C.c_int
     L.hs_opnorm.argtypes = [vp, C.c_int, p_f64]
     L.hs_opnorm.restype = C.c_int

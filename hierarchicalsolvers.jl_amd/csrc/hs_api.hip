@@ -1833,6 +1833,58 @@ static void ldiv_block_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T*
   hs_solve_multi_run<T>(v, dC, ldc, nrhs, s);
 }
 
+// hs_ldiv_block_t_*: the block solve with transpose(F) (trans = 1) or adjoint(F) (trans = 2); trans = 0 is hs_ldiv_block_* itself.  The same
+// handles are served and the same ones refused, before any device work and before C is written
+static void check_solve_block_t(hs_handle* h, int trans, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
+  check_handle(h);
+  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_ldiv_block_t_*: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", trans);
+  check_solve_args(h, cplx, ldc, ldb, n, nrhs);
+  if (h->nranks > 1)
+    HS_FAIL(HS_ERR_UNSUPPORTED, 0, "hs_ldiv_block_t_*: block solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", h->nranks);
+  for (size_t i = 0; i < h->nodes.size(); ++i) {
+    const NodeH& x = h->nodes[i];
+    if (x.mine && (x.hssd || (x.mf && !x.mfd)))
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i,
+              "hs_ldiv_block_t_*: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): transposed ULV solves are not implemented", (int)i);
+  }
+}
+template <class T>
+static void ldiv_block_host_t(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  check_solve_block_t(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs);
+  if (trans == 0) return ldiv_block_host<T>(h, 0, C, ldc, B, ldb, n, nrhs);
+  if (nrhs == 0) return;
+  if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_t_*: null block");
+  hipStream_t s = h->stream;
+  HsMultiView v;
+  hs_multi_view(h, &v);
+  const size_t bytes = (size_t)n * nrhs * sizeof(T);
+  T* d = (T*)hs_scratch_take(bytes, "block solve right-hand sides");
+  try {  // the whole block goes up and comes down once
+    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
+    hs_solve_multi_run_t<T>(v, trans, d, n, nrhs, s);
+    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    hs_scratch_give(d, bytes);
+    throw;
+  }
+  hs_scratch_give(d, bytes);
+  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
+}
+template <class T>
+static void ldiv_block_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  check_solve_block_t(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs);
+  if (trans == 0) return ldiv_block_dev<T>(h, 0, dC, ldc, dB, ldb, n, nrhs, stream);
+  if (nrhs == 0) return;
+  if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_dev_t_*: null block");
+  hipStream_t s = (hipStream_t)stream;
+  HsMultiView v;
+  hs_multi_view(h, &v);
+  if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
+  hs_solve_multi_run_t<T>(v, trans, dC, ldc, nrhs, s);
+}
+
 // the handle as hs_condest.hip sees it (hs_condest.h)
 void hs_handle_view(hs_handle* h, HsHandleView* v) {
   *v = HsHandleView();
@@ -2062,6 +2114,18 @@ extern "C" int hs_ldiv_block_dev_d(hs_handle* F, int trans, double* dC, int64_t 
 }
 extern "C" int hs_ldiv_block_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   HS_GUARD(ldiv_block_dev<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
+}
+extern "C" int hs_ldiv_block_t_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  HS_GUARD(ldiv_block_host_t<double>(F, trans, C, ldc, B, ldb, n, nrhs));
+}
+extern "C" int hs_ldiv_block_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  HS_GUARD(ldiv_block_host_t<cplx>(F, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
+}
+extern "C" int hs_ldiv_block_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  HS_GUARD(ldiv_block_dev_t<double>(F, trans, dC, ldc, dB, ldb, n, nrhs, stream));
+}
+extern "C" int hs_ldiv_block_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  HS_GUARD(ldiv_block_dev_t<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
 }
 extern "C" int hs_ldiv_block_info(const hs_handle* F, double* out6) {
   HS_GUARD(if (!F || !out6) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_info: null argument");

@@ -39,6 +39,9 @@ void hs_multi_view(hs_handle* h, HsMultiView* v);
 // C[:, 0:nrhs] = F^-1 C[:, 0:nrhs] in place on the device (ld ldc), chunk by chunk, on stream s; events around the launches
 template <class T>
 void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s);
+// the same for transpose(F) (trans = 1) and adjoint(F) (trans = 2): C[:, 0:nrhs] = F^-T C / F^-H C (kernels_solve_multi_t.hip)
+template <class T>
+void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s);
 double hs_solve_multi_seconds(void* mx);  // waits for the last block solve and returns its device seconds
 void hs_solve_multi_info(void* mx, double* out6);
 int hs_ldiv_block_cols();  // KC: columns per chunk (HS_LDIV_BLOCK_COLS = 16 / 32 / 48 / 64, default 32)
@@ -90,3 +93,38 @@ void launch_multi_prob(const MultiProb<T>& p, int kc, hipStream_t s);
 // what = 0: W1 = (P B)[int, :]   1: Xb = B[bnd, :]   2: B[int, :] = W2   3: B[bnd, :] = Xb
 template <class T>
 void launch_multi_move(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s);
+
+// ---- kernels_solve_multi_t.hip --------------------------------------------------------------------------------------------------------
+// The product of the transposed / adjoint block solve:  D = op(A)^T X  or  D = Cin - op(A)^T X  with A stored K x M column-major (the
+// reduction index is the contiguous one), op = identity or conj; X, Cin and D as above.
+template <class T>
+struct MultiProbT {
+  const T* A;
+  int lda, M, K;    // M outputs = columns of A, K = rows of A
+  int trap;         // 1: A is the unit lower trapezoid of what is stored (LowRank::Lp, K x M)
+  int conj;         // 1: op = conj (ComplexF64)
+  const T* X;
+  long long xrs;    // X(k, c) = X[(xmap ? xmap[k] : k) * xrs + c]
+  const int* xmap;
+  const T* Cin;     // null: D = op(A)^T X; else D = Cin - op(A)^T X, addressed like C
+  T* C;
+  long long crs;    // D(i, c) -> C[(cmap ? cmap[i] : i) * crs + c]
+  const int* cmap;
+};
+enum {
+  HSMT_DIAG_U = 0,  // Z_j = op(inv256U_j)^T W_j                          (W: work block 1, Z: work block 2)
+  HSMT_BELOW_U,     // W[below j] -= op(U11[j, below])^T Z_j              (right-looking)
+  HSMT_LEFT_U,      // W_j -= op(U11[above j, j])^T Z[above j]            (left-looking)
+  HSMT_BND_U,       // Xb -= op(Uib)^T Z
+  HSMT_LB,          // W = Z - op(Lbi)^T Xb
+  HSMT_DIAG_L,      // X_j = op(inv256L_j)^T W_j                          (X overwrites Z)
+  HSMT_ABOVE_L,     // W[above j] -= op(L11[j, above])^T X_j              (right-looking)
+  HSMT_LEFT_L,      // W_j -= op(L11[below j, j])^T X[below j]            (left-looking)
+};
+template <class T>
+void launch_multi_level_t(const SolveNode<T>* sn, int nfronts, int mode, int blk, int conj, int maxM, const MultiArgs& a, hipStream_t s);
+template <class T>
+void launch_multi_prob_t(const MultiProbT<T>& p, int kc, hipStream_t s);
+// what = 0: W1 = B[int, :]   1: Xb = B[bnd, :]   2: B[int[rperm[i]], :] = W2[i, :]   3: B[bnd, :] = Xb
+template <class T>
+void launch_multi_move_t(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s);

@@ -1,4 +1,5 @@
-// hs_solve_multi.hip -- ldiv!(C, F, B) for an n x nrhs block with the factors read once per chunk of columns (hs_ldiv_block_*).
+// hs_solve_multi.hip -- ldiv!(C, F, B) for an n x nrhs block with the factors read once per chunk of columns (hs_ldiv_block_*), and the
+// same for transpose(F) / adjoint(F) (hs_ldiv_block_t_*: hs_solve_multi_run_t at the end of this file).
 //
 // The single-vector sweeps (kernels_solve_wide.hip) run at the HBM roofline, so k looped solves read the factors k times.  Here a chunk of
 // KC columns (HS_LDIV_BLOCK_COLS = 16 / 32 / 48 / 64, default 32; the last chunk may be ragged) travels through the tree together; every
@@ -116,13 +117,11 @@ void lr_apply(const LowRank<T>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc
   launch_multi_prob<T>(p, kc, s);
   fc.add(lr.rows, lr.r, kc);
 }
-}  // namespace
 
+// the work blocks and the boundary segments of the handle, sized for a chunk of kcw columns (shared by both directions of the block solve)
 template <class T>
-void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+MultiCache* multi_prepare(const HsMultiView& v, int kcw) {
   MultiCache* mc = cache_of(v);
-  const int KC = hs_ldiv_block_cols();
-  const int kcw = KC;
   long long wmax = 1, rmax = 1, bmax = 1;
   if (mc->aux_off.empty()) {  // the boundary segments of every level's fronts: fixed by the tree, uploaded once
     std::vector<MultiAux> aux;
@@ -158,6 +157,60 @@ void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, 
     HS_HIP(hipEventCreate(&mc->e0));
     HS_HIP(hipEventCreate(&mc->e1));
   }
+  return mc;
+}
+// closes the timed region of a block solve and files its figures (hs_ldiv_block_info)
+void multi_finish(MultiCache* mc, const HsMultiView& v, const FlopCount& fc, int chunks, size_t esz, hipStream_t s) {
+  HS_HIP(hipEventRecord(mc->e1, s));
+  HS_HIP(hipGetLastError());
+  mc->pending = true;
+  mc->info[0] = 0.0;
+  mc->info[1] = (double)chunks * v.sum_fac * esz;
+  mc->info[2] = fc.exec;
+  mc->info[3] = fc.useful;
+  mc->info[4] = (double)chunks;
+  mc->info[5] = (double)(mc->b1 + mc->b2 + mc->bt + mc->bx);
+}
+
+// dst -= op(Z)^T (op(C)^T x): the transposed low-rank transform.  C dense, or the unit trapezoid of the packed sketch: C = P' trap(Lp), so
+// C^T x = trap(Lp)^T (P x) -- the INPUT rows are gathered through rperm, where lr_apply scatters its output
+template <class T>
+void lr_apply_t(const LowRank<T>& lr, int conj, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
+  MultiProbT<T> p;
+  memset(&p, 0, sizeof p);
+  if (lr.Cd) {
+    p.A = lr.Cd; p.lda = lr.ldc;
+  } else {
+    p.A = lr.Lp; p.lda = lr.ldp; p.trap = 1; p.xmap = lr.rperm;
+  }
+  p.M = lr.r; p.K = lr.rows; p.conj = conj;
+  p.X = x; p.xrs = kcw;
+  p.C = tbuf; p.crs = kcw;
+  launch_multi_prob_t<T>(p, kc, s);
+  fc.add(lr.r, lr.rows, kc);
+  memset(&p, 0, sizeof p);
+  p.A = lr.Z; p.lda = lr.ldz; p.M = lr.cols; p.K = lr.r; p.conj = conj;
+  p.X = tbuf; p.xrs = kcw;
+  p.Cin = dst; p.C = dst; p.crs = kcw;
+  launch_multi_prob_t<T>(p, kc, s);
+  fc.add(lr.cols, lr.r, kc);
+}
+
+// HS_LDIV_BLOCK_T_LOOK = left selects the left-looking triangular sweeps of the transposed solve (a measurement switch; default: right)
+bool multi_t_left_looking() {
+  static const bool left = [] {
+    const char* e = getenv("HS_LDIV_BLOCK_T_LOOK");
+    return e && (e[0] == 'l' || e[0] == 'L');
+  }();
+  return left;
+}
+}  // namespace
+
+template <class T>
+void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+  const int KC = hs_ldiv_block_cols();
+  const int kcw = KC;
+  MultiCache* mc = multi_prepare<T>(v, kcw);
   FlopCount fc;
   fc.tr = hs_multi_rows_per_wg(sizeof(T) == 16);
   fc.cmul = sizeof(T) == 16 ? 4 : 1;
@@ -229,18 +282,116 @@ void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, 
       }
     }
   }
-  HS_HIP(hipEventRecord(mc->e1, s));
-  HS_HIP(hipGetLastError());
-  mc->pending = true;
-  mc->info[0] = 0.0;
-  mc->info[1] = (double)chunks * v.sum_fac * sizeof(T);
-  mc->info[2] = fc.exec;
-  mc->info[3] = fc.useful;
-  mc->info[4] = (double)chunks;
-  mc->info[5] = (double)(mc->b1 + mc->b2 + mc->bt + mc->bx);
+  multi_finish(mc, v, fc, chunks, sizeof(T), s);
 }
 template void hs_solve_multi_run<double>(const HsMultiView&, double*, int64_t, int64_t, hipStream_t);
 template void hs_solve_multi_run<cplx>(const HsMultiView&, cplx*, int64_t, int64_t, hipStream_t);
+
+// transpose(F) \ B and adjoint(F) \ B: the same chunks, work blocks and stored blocks, every product with the factor panel transposed
+// (kernels_solve_multi_t.hip).  op(x) = x (trans = 1) or conj(x) (trans = 2: the factor entries are conjugated as they are loaded).  Per chunk:
+//
+//   forward, leaves -> root, per level:   W = B[int, :] (no permutation),  Xb = B[bnd, :];   per 256-block j:  Z_j = op(inv256U_j)^T W_j,
+//                                         W[below j] -= op(U11[j, below])^T Z_j;   Xb -= op(Uib)^T Z  (low-rank: -= op(Z_R)^T (op(G)^T Z));
+//                                         B[bnd, :] = Xb
+//   backward, root -> leaves, per level:  Xb = B[bnd, :];  W = Z - op(Lbi)^T Xb   (low-rank: - op(Z_L)^T (op(C_L)^T Xb));
+//                                         per block j, last first:  X_j = op(inv256L_j)^T W_j,  W[above j] -= op(L11[j, above])^T X_j;
+//                                         B[int[rperm[i]], :] = X[i, :]
+//
+// Right-looking like the forward solve: the update of a step reads the ROW panel U11[j, below] / L11[j, above] -- 256 contiguous doubles
+// per output row -- and has (ni - 256 (j + 1)) / 64 workgroups.  The left-looking order (HS_LDIV_BLOCK_T_LOOK=left) reads the column panel
+// above / below the block with K up to ni and 256 outputs: W is written once per block, by four workgroups per front (DESIGN.md section 4a⁗″).
+template <class T>
+void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+  const int KC = hs_ldiv_block_cols();
+  const int kcw = KC;
+  const int cj = (trans == 2 && sizeof(T) == 16) ? 1 : 0;
+  const bool left = multi_t_left_looking();
+  MultiCache* mc = multi_prepare<T>(v, kcw);
+  FlopCount fc;
+  fc.tr = hs_multi_rows_per_wg(sizeof(T) == 16);
+  fc.cmul = sizeof(T) == 16 ? 4 : 1;
+  const int nl = (int)v.levels.size();
+  int chunks = 0;
+  HS_HIP(hipEventRecord(mc->e0, s));
+  for (int64_t c0 = 0; c0 < nrhs; c0 += KC, ++chunks) {
+    const int kc = (int)std::min<int64_t>(KC, nrhs - c0);
+    MultiArgs a;
+    a.W1 = mc->W1; a.W2 = mc->W2; a.XB = mc->XB; a.kcw = kcw;
+    a.B = dC + c0 * ldc; a.ldb = ldc; a.kc = kc;
+    for (int lv = nl - 1; lv >= 0; --lv) {  // leaves -> root
+      const HsMultiLevel& L = v.levels[lv];
+      if (L.nfronts == 0 || L.maxni == 0) continue;
+      const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+      a.wbase = L.wbase;
+      a.aux = mc->d_aux + mc->aux_off[lv];
+      launch_multi_move_t<T>(sn, L.nfronts, 0, L.maxni, a, s);
+      launch_multi_move_t<T>(sn, L.nfronts, 1, L.maxnb, a, s);
+      const int nblk = (L.maxni + 255) / 256;
+      for (int j = 0; j < nblk; ++j) {
+        const int wl = std::min(256, L.maxni - j * 256);
+        if (left && j > 0) launch_multi_level_t<T>(sn, L.nfronts, HSMT_LEFT_U, j, cj, wl, a, s);
+        launch_multi_level_t<T>(sn, L.nfronts, HSMT_DIAG_U, j, cj, wl, a, s);
+        if (!left) launch_multi_level_t<T>(sn, L.nfronts, HSMT_BELOW_U, j, cj, L.maxni - (j + 1) * 256, a, s);
+      }
+      launch_multi_level_t<T>(sn, L.nfronts, HSMT_BND_U, 0, cj, L.maxnb, a, s);
+      for (const HsMultiFront& f : L.fronts) {
+        for (int j = 0; j * 256 < f.ni; ++j) {
+          const double wl = std::min(256, f.ni - j * 256);
+          fc.add(wl, wl, kc, wl * (wl + 1) / 2);
+          if (left)
+            fc.add(wl, j * 256, kc);
+          else
+            fc.add(f.ni - (j + 1) * 256, 256, kc);
+        }
+        if (f.dense_bnd) fc.add(f.nb, f.ni, kc);
+      }
+      for (const HsMultiLR& q : L.lr) {
+        if (!q.lrR) continue;
+        const LowRank<T>& lr = *(const LowRank<T>*)q.lrR;
+        if (lr.r == 0) continue;
+        lr_apply_t<T>(lr, cj, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+      }
+      launch_multi_move_t<T>(sn, L.nfronts, 3, L.maxnb, a, s);
+    }
+    for (int lv = 0; lv < nl; ++lv) {  // root -> leaves
+      const HsMultiLevel& L = v.levels[lv];
+      if (L.nfronts == 0 || L.maxni == 0) continue;
+      const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+      a.wbase = L.wbase;
+      a.aux = mc->d_aux + mc->aux_off[lv];
+      launch_multi_move_t<T>(sn, L.nfronts, 1, L.maxnb, a, s);
+      launch_multi_level_t<T>(sn, L.nfronts, HSMT_LB, 0, cj, L.maxni, a, s);
+      for (const HsMultiLR& q : L.lr) {
+        if (!q.lrL) continue;
+        const LowRank<T>& lr = *(const LowRank<T>*)q.lrL;
+        if (lr.r == 0) continue;
+        lr_apply_t<T>(lr, cj, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+      }
+      const int nblk = (L.maxni + 255) / 256;
+      for (int j = nblk - 1; j >= 0; --j) {
+        const int wl = std::min(256, L.maxni - j * 256);
+        if (left) launch_multi_level_t<T>(sn, L.nfronts, HSMT_LEFT_L, j, cj, 256, a, s);
+        launch_multi_level_t<T>(sn, L.nfronts, HSMT_DIAG_L, j, cj, wl, a, s);
+        if (!left) launch_multi_level_t<T>(sn, L.nfronts, HSMT_ABOVE_L, j, cj, j * 256, a, s);
+      }
+      launch_multi_move_t<T>(sn, L.nfronts, 2, L.maxni, a, s);
+      for (const HsMultiFront& f : L.fronts) {
+        if (f.dense_bnd) fc.add(f.ni, f.nb, kc);
+        for (int j = 0; j * 256 < f.ni; ++j) {
+          const double wl = std::min(256, f.ni - j * 256);
+          fc.add(wl, wl, kc, wl * (wl + 1) / 2);
+          if (left)
+            fc.add(wl, std::max(f.ni - (j + 1) * 256, 0), kc);
+          else
+            fc.add(j * 256, wl, kc);
+        }
+      }
+    }
+  }
+  multi_finish(mc, v, fc, chunks, sizeof(T), s);
+}
+template void hs_solve_multi_run_t<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t);
+template void hs_solve_multi_run_t<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t);
 
 double hs_solve_multi_seconds(void* mx) {
   MultiCache* mc = (MultiCache*)mx;

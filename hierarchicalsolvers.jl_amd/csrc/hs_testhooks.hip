@@ -385,6 +385,56 @@ extern "C" int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* 
   return multi_prob_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap);
 }
 
+// the panel product of the transposed block solves (kernels_solve_multi_t.hip) on host data: A is K x M, C = C - op(A)^T X or op(A)^T X
+template <class T>
+static int multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj) {
+  if (M < 1 || K < 0 || kc < 1 || kc > 64 || lda < std::max<int64_t>(K, 1) || ldx < std::max<int64_t>(K, 1) || ldc < M || !A || !X || !C) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_multi_prob_t: M >= 1, K >= 0, kc in 1..64, leading dimensions and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
+    return HS_ERR_DEVICE;
+  }
+  const int64_t P = 64;
+  std::vector<T> hx((size_t)std::max<int64_t>(K, 1) * P), hc((size_t)M * P);
+  for (int64_t c = 0; c < kc; ++c) {
+    for (int64_t k = 0; k < K; ++k) hx[k * P + c] = X[k + c * ldx];
+    for (int64_t i = 0; i < M; ++i) hc[i * P + c] = C[i + c * ldc];
+  }
+  T *dA = nullptr, *dX = nullptr, *dC = nullptr;
+  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)lda * M));
+  CK(hipMalloc((void**)&dX, sizeof(T) * hx.size()));
+  CK(hipMalloc((void**)&dC, sizeof(T) * hc.size()));
+  if (K > 0) CK(hipMemcpy(dA, A, sizeof(T) * ((size_t)lda * (M - 1) + K), hipMemcpyHostToDevice));
+  CK(hipMemcpy(dX, hx.data(), sizeof(T) * hx.size(), hipMemcpyHostToDevice));
+  CK(hipMemcpy(dC, hc.data(), sizeof(T) * hc.size(), hipMemcpyHostToDevice));
+  MultiProbT<T> p;
+  memset(&p, 0, sizeof p);
+  p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
+  p.X = dX; p.xrs = P;
+  p.Cin = minus ? dC : nullptr;
+  p.C = dC; p.crs = P;
+  launch_multi_prob_t<T>(p, (int)kc, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy(hc.data(), dC, sizeof(T) * hc.size(), hipMemcpyDeviceToHost));
+  for (int64_t c = 0; c < kc; ++c)
+    for (int64_t i = 0; i < M; ++i) C[i + c * ldc] = hc[i * P + c];
+  (void)hipFree(dA);
+  (void)hipFree(dX);
+  (void)hipFree(dC);
+  return HS_OK;
+}
+extern "C" int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                  int64_t ldc, int minus, int trap, int conj) {
+  return multi_prob_t_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj);
+}
+extern "C" int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                  int64_t ldc, int minus, int trap, int conj) {
+  return multi_prob_t_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj);
+}
+
 // The leaf-envelope builder of the analysis (hs_envelope.h), host only: tests compare it with a NumPy computation from A[idx][:, idx]
 #include "hs_envelope.h"
 extern "C" int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL,

@@ -396,7 +396,8 @@ def ldiv_block(*args):
     """``ldiv!(F, B)`` / ``ldiv!(C, F, B)`` through the block solve (``hs_ldiv_block_*``): the same arguments and results as :func:`ldiv`
     (to rounding), but the ``nrhs`` columns travel through the elimination tree together, ``HS_LDIV_BLOCK_COLS`` (default 32) at a time, so
     the factors are read once per chunk instead of once per column.  ``F`` must be a plain :class:`FactorNode` whose fronts keep a dense LU
-    of their interior block (``transpose(F)`` / ``adjoint(F)`` and HSS interior blocks raise :class:`UnsupportedError`)."""
+    of their interior block (``transpose(F)`` / ``adjoint(F)`` -- served by :func:`ldiv_block_t` -- and HSS interior blocks raise
+    :class:`UnsupportedError`)."""
     if len(args) == 2:
         F, B = args
         Cout = None
@@ -427,8 +428,42 @@ def ldiv_block(*args):
     return res
 
 
+def ldiv_block_t(*args):
+    """``ldiv!(F, B)`` / ``ldiv!(C, F, B)`` with ``F`` a :class:`FactorNode`, ``transpose(F)`` or ``adjoint(F)``, through the block solve
+    (``hs_ldiv_block_t_*``): the arguments and results of :func:`ldiv_block`, the columns travelling through the tree together in both
+    directions.  A plain ``F`` returns the bits of :func:`ldiv_block`.  The same handles are served as there."""
+    if len(args) == 2:
+        F, B = args
+        Cout = None
+    elif len(args) == 3:
+        Cout, F, B = args
+    else:
+        raise TypeError("ldiv_block_t(F, B) or ldiv_block_t(C, F, B)")
+    trans = 0
+    if isinstance(F, TransposedFactor):
+        F, trans = F.parent, F.trans
+    B = np.asarray(B)
+    if B.shape[0] != F.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
+    if B.dtype != F.dtype:
+        if F.dtype.kind == "f" and B.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::FactorNode{Float64}, ::Array{ComplexF64})")
+        B = B.astype(F.dtype)
+    vec = B.ndim == 1
+    Bm = np.asfortranarray(B.reshape(F.n, -1))
+    Cm = np.empty_like(Bm, order="F")
+    L = _lib.lib()
+    fn = L.hs_ldiv_block_t_z if F.dtype.kind == "c" else L.hs_ldiv_block_t_d
+    _lib.check(fn(F._h, trans, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
+    res = Cm[:, 0] if vec else Cm
+    if Cout is not None:
+        Cout[...] = res
+        return Cout
+    return res
+
+
 def ldiv_block_info(F):
-    """Figures of the last :func:`ldiv_block` call on ``F`` (``hs_ldiv_block_info``): device seconds, factor bytes read by the model
+    """Figures of the last :func:`ldiv_block` / :func:`ldiv_block_t` call on ``F`` (``hs_ldiv_block_info``): device seconds, factor bytes read by the model
     (chunks x sum over fronts of ``(ni^2 + 2 ni nb) sizeof(T)``), flops executed on the matrix pipe (padding included), useful flops,
     column chunks, workspace bytes."""
     out = np.zeros(6)

@@ -63,6 +63,14 @@ int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t 
 int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
                      int minus, int trap);
 
+/* The panel product of the transposed block solves (kernels_solve_multi_t.hip) on host data: C = op(A)^T X (minus == 0) or C = C - op(A)^T X,
+ * A K x M (column-major, lda >= K), X K x kc and C M x kc column-major with kc in 1..64 (row-major with a pitch of 64 on the device).
+ * trap != 0: A stands for its unit lower trapezoid (K x M); conj != 0: op = conj (ComplexF64; ignored for Float64). */
+int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                       int minus, int trap, int conj);
+int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                       int minus, int trap, int conj);
+
 /* The CSR SpMM of hs_gmres_block_* (hs_gmres_block.hip) on host data: Y = A X (B == NULL) or Y = B - A X, A n x n CSC with 1-based colptr /
  * rowval, X, B, Y column-major n x nrhs blocks (ldx, ldb, ldy >= n; rows of Y beyond n are left as they are). */
 int hsk_spmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,

@@ -155,7 +155,8 @@ int hs_ldiv_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const doub
  * two calls return the same bits, and a column of C does not depend on the values, the number or the position of the other columns.
  * The results agree with hs_ldiv_* to rounding, not bit for bit.  Served: what hs_ldiv_t_* serves (single-rank handles whose fronts all
  * keep a dense LU of D, low-rank L / R included).  Refused with HS_ERR_UNSUPPORTED before any device work and before C is written: fronts
- * that keep D as an HSS matrix (hs_options.hss_d, mf = 2, 3), more than one rank, trans = 1, 2 (other trans: HS_ERR_ARGUMENT).  nrhs = 0
+ * that keep D as an HSS matrix (hs_options.hss_d, mf = 2, 3), more than one rank, trans = 1, 2 (served by hs_ldiv_block_t_*; other trans:
+ * HS_ERR_ARGUMENT).  nrhs = 0
  * touches nothing.  The host forms move the whole block once and set stats.t_solve; the _dev_ forms are asynchronous on `stream`.  The work
  * blocks ((sum of ni + the largest level's sum of ni and of nb) x chunk columns) are taken on first use, kept in the handle and freed by hs_free; the
  * workspaces of hs_ldiv_* / hs_ldiv_t_* are not touched, so the calls may alternate freely. */
@@ -163,7 +164,20 @@ int hs_ldiv_block_d(hs_handle* F, int trans, double* C, int64_t ldc, const doubl
 int hs_ldiv_block_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
 int hs_ldiv_block_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 int hs_ldiv_block_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
-/* last block solve of the handle (waits for it): out6 = {seconds on the device, factor bytes read by the model (column chunks x sum over
+/* ldiv!(C, transpose(F), B) (trans = 1) and ldiv!(C, adjoint(F), B) (trans = 2; = 1 for Float64) for an n x nrhs block, the factors read
+ * once per chunk of columns: hs_ldiv_block_* for op(F).  trans = 0 goes through hs_ldiv_block_* and returns its bits.  Everything else as
+ * there: C may alias B, nrhs = 0 touches nothing, chunks of HS_LDIV_BLOCK_COLS columns, the same work blocks (the workspace does not grow),
+ * the same determinism (no atomics, one summation order, a column independent of its neighbours and of its position), the same handles
+ * served and the same ones refused with HS_ERR_UNSUPPORTED before any device work and before C is written (HSS interior blocks, more than
+ * one rank); trans outside 0..2, null blocks, a mismatched element type: HS_ERR_ARGUMENT; bad sizes: HS_ERR_DIMENSION.  The stored blocks
+ * serve both directions (the 256 x 256 inverse diagonal blocks are applied transposed): no factor memory is added.  The results agree
+ * with hs_ldiv_t_* to rounding, not bit for bit.  The host forms move the whole block once and set stats.t_solve; the _dev_ forms are
+ * asynchronous on `stream`. */
+int hs_ldiv_block_t_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_ldiv_block_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_ldiv_block_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+int hs_ldiv_block_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+/* last block solve of the handle, whichever direction it had (waits for it): out6 = {seconds on the device, factor bytes read by the model (column chunks x sum over
  * fronts of (ni^2 + 2 ni nb) sizeof(T), the factor term of hs_stats.bytes_solve), flops executed on the matrix pipe (padding included),
  * useful flops, column chunks, workspace bytes} */
 int hs_ldiv_block_info(const hs_handle* F, double* out6);
