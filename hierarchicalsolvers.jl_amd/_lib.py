@@ -75,6 +75,7 @@ EXPORTS = [
     "hs_ldiv_block_d", "hs_ldiv_block_z", "hs_ldiv_block_dev_d", "hs_ldiv_block_dev_z", "hs_ldiv_block_info", "hsk_multi_prob_d", "hsk_multi_prob_z",
     "hs_ldiv_block_t_d", "hs_ldiv_block_t_z", "hs_ldiv_block_dev_t_d", "hs_ldiv_block_dev_t_z", "hsk_multi_prob_t_d", "hsk_multi_prob_t_z",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
+    "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
     "hs_logabsdet", "hs_selinv", "hs_selinv_info",
     "hs_maxrank", "hs_is_complex", "hs_size", "hs_free", "hs_last_error", "hs_last_error_info", "hs_get_stats",
     "hs_node_info", "hs_node_ranks", "hs_node_export", "hs_node_export_piv", "hs_device_info",
@@ -173,6 +174,14 @@ def lib():
     for f in (L.hs_ldiv_refine_dev_d, L.hs_ldiv_refine_dev_z):
         f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, i64, p_f64, p_f64, p_i64, vp]
         f.restype = C.c_int
+    for f in (L.hs_ldiv_refine_block_d, L.hs_ldiv_refine_block_z):
+        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64, i64, p_f64, p_f64, p_i64]
+        f.restype = C.c_int
+    for f in (L.hs_ldiv_refine_block_dev_d, L.hs_ldiv_refine_block_dev_z):
+        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, i64, p_f64, p_f64, p_i64, vp]
+        f.restype = C.c_int
+    L.hs_ldiv_refine_block_info.argtypes = [p_f64]
+    L.hs_ldiv_refine_block_info.restype = C.c_int
     L.hs_logabsdet.argtypes = [vp, p_f64, p_f64]
     L.hs_logabsdet.restype = C.c_int
     L.hs_selinv.argtypes = [vp, C.c_int, vp, vp, C.c_int, i64, vp]

@@ -1,5 +1,5 @@
-// hs_condest.h -- what the accuracy tools of hs_condest.hip (norm and condition estimates, refined solves) read from a factorization handle.
-// hs_api.hip owns the handle; these two calls are the whole interface between the two files.
+// hs_condest.h -- what the accuracy tools of hs_condest.hip (norm and condition estimates, refined solves) read from a factorization handle,
+// and what hs_refine_block.hip shares with them.  hs_api.hip owns the handle; the two calls below are the whole interface to it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,3 +28,128 @@ struct HsHandleView {
 void hs_handle_view(hs_handle* h, HsHandleView* v);
 // HS_OK, or HS_ERR_DEVICE with hs_last_error set when a dataflow sweep since the last check timed out (call after every synchronisation)
 int hs_handle_flow_check(hs_handle* h);
+
+// ---- shared by hs_condest.hip and hs_refine_block.hip (define HS_CONDEST_KERNELS before the include; needs hs_solver.h and hs_common.h) ----
+#ifdef HS_CONDEST_KERNELS
+#include <algorithm>
+#include <vector>
+// No contraction of a*b + c into an fma from here to the end of the including file: residuals and weights are the plain products and sums,
+// entry by entry, in both files (see hs_condest.hip).
+#pragma clang fp contract(off)
+
+#define CE_ROWS 2048    // rows per workgroup of the reduction kernels (256 threads x 8)
+
+#define CE_FAIL(code, info, ...)                \
+  do {                                          \
+    hs_set_error((code), (info), __VA_ARGS__);  \
+    throw (int)(code);                          \
+  } while (0)
+#define CE_HIP(call)                                                                                              \
+  do {                                                                                                            \
+    hipError_t e__ = (call);                                                                                      \
+    if (e__ != hipSuccess) CE_FAIL(HS_ERR_DEVICE, 0, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
+  } while (0)
+#define CE_CHECK(st)            \
+  do {                          \
+    int s__ = (st);             \
+    if (s__ != HS_OK) throw s__; \
+  } while (0)
+#define CE_GUARD(...)                                         \
+  try {                                                       \
+    __VA_ARGS__;                                              \
+    return HS_OK;                                             \
+  } catch (int code) {                                        \
+    return code;                                              \
+  } catch (const std::bad_alloc&) {                           \
+    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");  \
+    return HS_ERR_NOMEM;                                      \
+  }
+
+namespace hs_ce {
+
+// ---- scalar helpers ------------------------------------------------------------------------------------------------------------
+__device__ inline double abs_(double a) { return fabs(a); }
+__device__ inline double abs_(cplx a) { return hypot(a.re, a.im); }
+__device__ inline double abs1_(double a) { return fabs(a); }
+__device__ inline double abs1_(cplx a) { return fabs(a.re) + fabs(a.im); }  // cabs1, as zgerfs
+template <bool CJ>
+__device__ inline double cj_(double a) { return a; }
+template <bool CJ>
+__device__ inline cplx cj_(cplx a) { return CJ ? cplx{a.re, -a.im} : a; }
+__device__ inline double sign_(double a) { return a >= 0.0 ? 1.0 : -1.0; }  // sign(0) = 1
+__device__ inline cplx sign_(cplx a) {
+  const double m = hypot(a.re, a.im);
+  return m == 0.0 ? cplx{1.0, 0.0} : cplx{a.re / m, a.im / m};
+}
+template <class T>
+__device__ inline T from_real(double a);
+template <>
+__device__ inline double from_real<double>(double a) { return a; }
+template <>
+__device__ inline cplx from_real<cplx>(double a) { return {a, 0.0}; }
+__device__ inline double mul_(double a, double b) { return a * b; }
+__device__ inline cplx mul_(cplx a, cplx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+__device__ inline double add_(double a, double b) { return a + b; }
+__device__ inline cplx add_(cplx a, cplx b) { return {a.re + b.re, a.im + b.im}; }
+__device__ inline double sub_(double a, double b) { return a - b; }
+__device__ inline cplx sub_(cplx a, cplx b) { return {a.re - b.re, a.im - b.im}; }
+__device__ inline double scale_(double a, double s) { return a * s; }
+__device__ inline cplx scale_(cplx a, double s) { return {a.re * s, a.im * s}; }
+
+__host__ __device__ inline uint64_t sm64(uint64_t x) {  // splitmix64 finaliser
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+// the +-1 column `col` of draw `salt` (0: the start block; k * 64 + attempt: a re-drawn sign column of iteration k): entry i = low bit of
+// splitmix64(key ^ i)
+inline uint64_t col_key(int64_t seed, int col, int salt) { return sm64(sm64((uint64_t)seed) ^ ((uint64_t)salt << 8) ^ (uint64_t)col); }
+__device__ inline double pm1(uint64_t key, int64_t i) { return (sm64(key ^ (uint64_t)i) & 1) ? -1.0 : 1.0; }
+
+// the xGERFS ratio |r_i| / w_i with its safe1 / safe2 guard
+struct ResidArgs {
+  double safe1, safe2;
+};
+__device__ inline double berr_ratio(double ra, double wa, ResidArgs g) { return wa > g.safe2 ? ra / wa : (ra + g.safe1) / (wa + g.safe1); }
+
+inline unsigned nb256(int64_t cnt) { return (unsigned)std::max<int64_t>(1, (cnt + 255) / 256); }
+inline unsigned nbrows(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + CE_ROWS - 1) / CE_ROWS); }
+
+struct DevBuf {
+  std::vector<void*> p;
+  ~DevBuf() {
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+  }
+  template <class U>
+  U* get(size_t count) {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(count * sizeof(U), 256)) != hipSuccess) CE_FAIL(HS_ERR_NOMEM, 0, "hipMalloc of %zu bytes failed (condest workspace)", count * sizeof(U));
+    p.push_back(q);
+    return (U*)q;
+  }
+};
+
+// kept in the handle (hs_handle::cx): the CSR map of A (borrowed from the matrix-free fronts when hs_options.mf built one), a buffer for its
+// values, and the longest row / column of A
+struct CsrMap {
+  int64_t* rowptr = nullptr;
+  int32_t* colind = nullptr;
+  int64_t* tperm = nullptr;
+  bool owned = false;
+  void* valr = nullptr;
+  int64_t maxrow = -1, maxcol = -1;
+};
+
+constexpr double CE_EPS = 1.1102230246251565e-16;     // dlamch('Epsilon') = 2^-53
+constexpr double CE_SAFMIN = 2.2250738585072014e-308;  // dlamch('Safe minimum')
+
+// hs_condest.hip: the longest column of A, and the CSR map of A (built on first use, kept in the handle) with its values gathered from the
+// CSC values of the last hs_numeric_begin
+int64_t max_col(const HsHandleView& v, hipStream_t s);
+template <class T>
+CsrMap* csr_of(const HsHandleView& v, hipStream_t s);
+
+}  // namespace hs_ce
+#endif  // HS_CONDEST_KERNELS

@@ -19,6 +19,7 @@
 
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
+#define HS_CONDEST_KERNELS
 #include "hs_condest.h"
 
 // No contraction of a*b + c into an fma in this file: the residual r = b - op(A) x and the weights w are then the plain products and sums, row by
@@ -28,76 +29,11 @@
 
 #define CE_MAXT 8       // estimator columns
 #define CE_MAXIT 16     // estimator iterations (the index history holds t * itmax entries)
-#define CE_ROWS 2048    // rows per workgroup of the reduction kernels (256 threads x 8)
 #define CE_WAVE_ROW 64  // rows of op(A) longer than this are gathered by a whole wave (graphs from hs_symbolic_from_graph)
 
+using namespace hs_ce;
+
 namespace {
-
-#define CE_FAIL(code, info, ...)                \
-  do {                                          \
-    hs_set_error((code), (info), __VA_ARGS__);  \
-    throw (int)(code);                          \
-  } while (0)
-#define CE_HIP(call)                                                                                              \
-  do {                                                                                                            \
-    hipError_t e__ = (call);                                                                                      \
-    if (e__ != hipSuccess) CE_FAIL(HS_ERR_DEVICE, 0, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-  } while (0)
-#define CE_CHECK(st)            \
-  do {                          \
-    int s__ = (st);             \
-    if (s__ != HS_OK) throw s__; \
-  } while (0)
-#define CE_GUARD(...)                                         \
-  try {                                                       \
-    __VA_ARGS__;                                              \
-    return HS_OK;                                             \
-  } catch (int code) {                                        \
-    return code;                                              \
-  } catch (const std::bad_alloc&) {                           \
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");  \
-    return HS_ERR_NOMEM;                                      \
-  }
-
-// ---- scalar helpers ------------------------------------------------------------------------------------------------------------
-__device__ inline double abs_(double a) { return fabs(a); }
-__device__ inline double abs_(cplx a) { return hypot(a.re, a.im); }
-__device__ inline double abs1_(double a) { return fabs(a); }
-__device__ inline double abs1_(cplx a) { return fabs(a.re) + fabs(a.im); }  // cabs1, as zgerfs
-template <bool CJ>
-__device__ inline double cj_(double a) { return a; }
-template <bool CJ>
-__device__ inline cplx cj_(cplx a) { return CJ ? cplx{a.re, -a.im} : a; }
-__device__ inline double sign_(double a) { return a >= 0.0 ? 1.0 : -1.0; }  // sign(0) = 1
-__device__ inline cplx sign_(cplx a) {
-  const double m = hypot(a.re, a.im);
-  return m == 0.0 ? cplx{1.0, 0.0} : cplx{a.re / m, a.im / m};
-}
-template <class T>
-__device__ inline T from_real(double a);
-template <>
-__device__ inline double from_real<double>(double a) { return a; }
-template <>
-__device__ inline cplx from_real<cplx>(double a) { return {a, 0.0}; }
-__device__ inline double mul_(double a, double b) { return a * b; }
-__device__ inline cplx mul_(cplx a, cplx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ inline double add_(double a, double b) { return a + b; }
-__device__ inline cplx add_(cplx a, cplx b) { return {a.re + b.re, a.im + b.im}; }
-__device__ inline double sub_(double a, double b) { return a - b; }
-__device__ inline cplx sub_(cplx a, cplx b) { return {a.re - b.re, a.im - b.im}; }
-__device__ inline double scale_(double a, double s) { return a * s; }
-__device__ inline cplx scale_(cplx a, double s) { return {a.re * s, a.im * s}; }
-
-__host__ __device__ inline uint64_t sm64(uint64_t x) {  // splitmix64 finaliser
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-// the +-1 column `col` of draw `salt` (0: the start block; k * 64 + attempt: a re-drawn sign column of iteration k): entry i = low bit of
-// splitmix64(key ^ i)
-static uint64_t col_key(int64_t seed, int col, int salt) { return sm64(sm64((uint64_t)seed) ^ ((uint64_t)salt << 8) ^ (uint64_t)col); }
-__device__ inline double pm1(uint64_t key, int64_t i) { return (sm64(key ^ (uint64_t)i) & 1) ? -1.0 : 1.0; }
 
 struct Keys {
   uint64_t k[CE_MAXT];
@@ -362,10 +298,6 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(T* __restrict__ X, cons
 // ---- residual, norms, CSR map ----------------------------------------------------------------------------------------------------
 // Row i of op(A) is row i of the CSR map (op = N) or column i of the CSC arrays (op = T, H: CJ conjugates).  One pass reads A, x, b and
 // writes r = b - op(A) x and w = |b| + |op(A)| |x| (cabs1), and the workgroup's max of the xGERFS ratio |r_i| / w_i (safe1 / safe2 guard).
-struct ResidArgs {
-  double safe1, safe2;
-};
-__device__ inline double berr_ratio(double ra, double wa, ResidArgs g) { return wa > g.safe2 ? ra / wa : (ra + g.safe1) / (wa + g.safe1); }
 template <class T, bool CJ>
 __global__ __launch_bounds__(256) void resid_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const T* __restrict__ val,
                                                     const T* __restrict__ x, const T* __restrict__ b, T* __restrict__ r, double* __restrict__ w,
@@ -564,35 +496,7 @@ __global__ __launch_bounds__(256) void seglen_max_kernel(const int64_t* __restri
   if (i < n) atomicMax(out, (unsigned long long)(ptr[i + 1] - ptr[i]));
 }
 
-inline unsigned nb256(int64_t cnt) { return (unsigned)std::max<int64_t>(1, (cnt + 255) / 256); }
-inline unsigned nbrows(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + CE_ROWS - 1) / CE_ROWS); }
-
 // ---- device buffers, handle cache --------------------------------------------------------------------------------------------------
-struct DevBuf {
-  std::vector<void*> p;
-  ~DevBuf() {
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-  }
-  template <class U>
-  U* get(size_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(count * sizeof(U), 256)) != hipSuccess) CE_FAIL(HS_ERR_NOMEM, 0, "hipMalloc of %zu bytes failed (condest workspace)", count * sizeof(U));
-    p.push_back(q);
-    return (U*)q;
-  }
-};
-
-// kept in the handle (hs_handle::cx): the CSR map of A (borrowed from the matrix-free fronts when hs_options.mf built one), a buffer for its
-// values, and the longest row / column of A
-struct CsrMap {
-  int64_t* rowptr = nullptr;
-  int32_t* colind = nullptr;
-  int64_t* tperm = nullptr;
-  bool owned = false;
-  void* valr = nullptr;
-  int64_t maxrow = -1, maxcol = -1;
-};
 void csrmap_free(void* p) {
   CsrMap* m = (CsrMap*)p;
   if (m->owned)
@@ -618,6 +522,8 @@ int64_t seg_max(const int64_t* ptr, int64_t n, hipStream_t s) {
   CE_HIP(hipStreamSynchronize(s));
   return (int64_t)m;
 }
+}  // namespace
+namespace hs_ce {
 int64_t max_col(const HsHandleView& v, hipStream_t s) {
   CsrMap* m = cache_of(v);
   if (m->maxcol < 0) m->maxcol = seg_max(v.colptr, v.n, s);
@@ -669,6 +575,10 @@ CsrMap* csr_of(const HsHandleView& v, hipStream_t s) {
   launch_perm_gather<T>((const T*)v.nz, m->tperm, (T*)m->valr, nnz, s);
   return m;
 }
+template CsrMap* csr_of<double>(const HsHandleView&, hipStream_t);
+template CsrMap* csr_of<cplx>(const HsHandleView&, hipStream_t);
+}  // namespace hs_ce
+namespace {
 
 // ---- solves --------------------------------------------------------------------------------------------------------------------------
 // op(F)^-1 by code: 0 = F^-1, 1 = F^-T, 2 = F^-H, 3 = conj(F)^-1 (= conj(F^-1 conj(.))); adj() gives the code of the adjoint
@@ -879,9 +789,6 @@ double normestinv_impl(hs_handle* F, const HsHandleView& v, int trans, int t, in
   if (nsolves) *nsolves = c.nsolves;
   return est;
 }
-
-constexpr double CE_EPS = 1.1102230246251565e-16;     // dlamch('Epsilon') = 2^-53
-constexpr double CE_SAFMIN = 2.2250738585072014e-308;  // dlamch('Safe minimum')
 
 template <class T>
 void refine_dev(hs_handle* F, const HsHandleView& v, int trans, T* dX, int64_t ldx, const T* dB, int64_t ldb, int64_t nrhs, int64_t itmax, double* berr,

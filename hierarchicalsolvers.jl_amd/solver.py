@@ -11,7 +11,7 @@ reference (Julia)                      here
 ``maxrank(F)``                         :func:`maxrank`         (factornode.jl:49-57)
 ``opnorm(A, p)``, ``opnormestinv(A)``  :func:`opnorm`, :func:`opnormestinv` (on the factorization's A and F; ``hs_condest.hip``)
 ``cond(A, p)`` (estimated)             :func:`condest`
-``xGERFS`` (refine, berr, ferr)        :func:`ldiv_refine`
+``xGERFS`` (refine, berr, ferr)        :func:`ldiv_refine`, :func:`ldiv_refine_block`
 ``logabsdet(F)``, ``logdet``, ``det``  :func:`logabsdet`, :func:`logdet`, :func:`det` (``hs_selinv.hip``)
 selected inverse (no Julia name)       :func:`selinv`, :func:`selinv_diag`: ``diag(A^-1)`` and ``A^-1`` on the pattern of ``A``
 ``F \\ b``                              ``F.solve(b)``
@@ -30,7 +30,7 @@ from . import _lib
 from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
-           "ldiv_refine", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info"]
+           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info"]
 
 
 class SolverOptions:
@@ -556,6 +556,44 @@ def ldiv_refine(F, B, itmax=5, ferr=True):
     if vec:
         return X[:, 0], float(be[0]), (float(fe[0]) if ferr else None), int(st[0])
     return X, be, fe, st
+
+
+def ldiv_refine_block(F, B, itmax=5, ferr=True):
+    """:func:`ldiv_refine` for a block of right-hand sides in lockstep (``hs_ldiv_refine_block_*``): the same arguments and return shapes,
+    every column the same xGERFS iteration and error bounds, but all active columns take a correction together through one block solve
+    (:func:`ldiv_block_t`), so the factors are read once per chunk of columns and not once per column.  Results agree with
+    :func:`ldiv_refine` to the rounding by which block and single solves differ.  Handles the block solve refuses (HSS interior blocks,
+    more than one rank) raise :class:`UnsupportedError`."""
+    F, trans = _unwrap(F)
+    B = np.asarray(B)
+    if B.shape[0] != F.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
+    if B.dtype != F.dtype:
+        if F.dtype.kind == "f" and B.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching ldiv_refine_block(::FactorNode{Float64}, ::Array{ComplexF64})")
+        B = B.astype(F.dtype)
+    vec = B.ndim == 1
+    Bm = np.asfortranarray(B.reshape(F.n, -1))
+    k = Bm.shape[1]
+    X = np.empty_like(Bm, order="F")
+    be = np.zeros(k)
+    fe = np.zeros(k) if ferr else None
+    st = np.zeros(k, dtype=np.int64)
+    L = _lib.lib()
+    fn = L.hs_ldiv_refine_block_z if F.dtype.kind == "c" else L.hs_ldiv_refine_block_d
+    _lib.check(fn(F._h, trans, X.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, k, int(itmax), _pf64(be),
+                  _pf64(fe) if ferr else None, _p64(st)))
+    if vec:
+        return X[:, 0], float(be[0]), (float(fe[0]) if ferr else None), int(st[0])
+    return X, be, fe, st
+
+
+def ldiv_refine_block_info():
+    """Figures of this thread's last :func:`ldiv_refine_block` call (``hs_ldiv_refine_block_info``)."""
+    out = np.zeros(8)
+    _lib.check(_lib.lib().hs_ldiv_refine_block_info(_pf64(out)))
+    return {"seconds": float(out[0]), "block_solves": int(out[1]), "column_applications": int(out[2]), "residual_launches": int(out[3]),
+            "max_active": int(out[4]), "groups": int(out[5]), "workspace_bytes": int(out[6]), "estimator_column_applications": int(out[7])}
 
 
 def logabsdet(F):

@@ -7,7 +7,7 @@
  *                                      (reference src/factorization.jl:5-11)
  *   ldiv!(C, F, B), ldiv!(F, B)        (reference src/factornode.jl:62-74)
  *   ldiv!(C, transpose(F), B), ldiv!(C, adjoint(F), B)   (hs_ldiv_t_*, hs_ldiv_dev_t_*)
- *   opnorm(A, p), opnormestinv(A), cond(A, p), refined solves (xGERFS)   (hs_opnorm, hs_normestinv, hs_condest, hs_ldiv_refine_*)
+ *   opnorm(A, p), opnormestinv(A), cond(A, p), refined solves (xGERFS)   (hs_opnorm, hs_normestinv, hs_condest, hs_ldiv_refine_*, hs_ldiv_refine_block_*)
  *   logabsdet(F), logdet(F), det(F), selected inverse (diag(A^-1), A^-1 on A's pattern)   (hs_logabsdet, hs_selinv)
  *   maxrank(F)                         (reference src/factornode.jl:49-57)
  *
@@ -209,6 +209,34 @@ int hs_ldiv_refine_dev_d(hs_handle* F, int trans, double* dX, int64_t ldx, const
                          double* berr, double* ferr, int64_t* steps, void* stream);
 int hs_ldiv_refine_dev_z(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                          double* berr, double* ferr, int64_t* steps, void* stream);
+
+/* hs_ldiv_refine_* for a block of right-hand sides in lockstep (hs_refine_block.hip): column c gets the xGERFS iteration hs_ldiv_refine_*
+ * runs for B[:, c] alone (the same start, residual, weights, guarded ratio, continuation rule and ferr definition), but every application of
+ * op(F)^-1 is one hs_ldiv_block_dev_t_* call on all columns that are still active: the factors are read once per chunk of columns.  A
+ * correction is one block solve, one fused residual pass over op(A) and one host synchronisation; a column whose test ends is frozen and the
+ * columns that go on are compacted into the leading slots, so a correction runs ceil(nact / chunk) chunks.  With ferr every column runs its
+ * own Higham-Tisseur estimator (t = min(2, n), 5 iterations, the +-1 keys of hs_normestinv); all active estimators share one block
+ * application of op(F)^-H and one of op(F)^-1 per iteration.  Results agree with hs_ldiv_refine_* to the rounding by which block and single
+ * solves differ, not bit for bit; steps may differ by one where a column sits on the stopping threshold; with rows of op(A) longer than 64
+ * entries the residual's summation order differs too.  No floating-point atomics, fixed reduction orders: two calls return the same bits,
+ * and X[:, c], berr[c], ferr[c], steps[c] do not depend on the values, number or order of the other columns nor on the group width.
+ * Columns are processed in groups of G (a multiple of HS_LDIV_BLOCK_COLS) whose workspace (R, D, W, V of n x G; with ferr five blocks of
+ * n x 2G; partials) fits half of the free device memory, else HS_ERR_NOMEM; HS_REFINE_BLOCK_GROUP overrides G (read per call).
+ * Refused before any device work, X untouched: what hs_ldiv_block_t_* refuses (HSS interior blocks, more than one rank) with
+ * HS_ERR_UNSUPPORTED whatever trans and ferr are (no fallback: hs_ldiv_refine_* serves those handles); null pointers, X aliasing B, trans
+ * outside 0..2, itmax < 0, a plan-only or unfactored handle, a mismatched element type: HS_ERR_ARGUMENT; bad n / ldx / ldb / nrhs < 0:
+ * HS_ERR_DIMENSION.  nrhs = 0 touches nothing.  berr, ferr (may be NULL) and steps are host arrays; the _dev_ forms take device X, B. */
+int hs_ldiv_refine_block_d(hs_handle* F, int trans, double* X, int64_t ldx, const double* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                           double* berr, double* ferr, int64_t* steps);
+int hs_ldiv_refine_block_z(hs_handle* F, int trans, double* X, int64_t ldx, const double* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                           double* berr, double* ferr, int64_t* steps);
+int hs_ldiv_refine_block_dev_d(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                               double* berr, double* ferr, int64_t* steps, void* stream);
+int hs_ldiv_refine_block_dev_z(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                               double* berr, double* ferr, int64_t* steps, void* stream);
+/* the calling thread's last hs_ldiv_refine_block_* call: out8 = {seconds on the device, block-solve calls, column-applications summed over
+ * them, residual launches, the largest active-column count, column groups, workspace bytes, estimator column-applications} */
+int hs_ldiv_refine_block_info(double* out8);
 
 /* ---- log-determinant and selected inversion from the stored factors (hs_selinv.hip) ----------------------------------------------
  * LinearAlgebra.logabsdet(F): *logabs = log|det F|, sign2 = {re, im} of det F / |det F| ({+-1, 0} for Float64); an exactly zero pivot gives
