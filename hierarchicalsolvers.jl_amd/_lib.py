@@ -82,6 +82,7 @@ EXPORTS = [
     "hs_analyze", "hs_plan", "hs_numeric_begin", "hs_numeric_levels", "hs_numeric_end", "hs_solve_fwd_levels", "hs_solve_bwd_levels",
     "hs_nlevels", "hs_cut_level", "hs_node_owner", "hs_num_exchanges", "hs_exchange_info", "hs_set_schur_buffer",
     "hs_pack_bnd", "hs_unpack_bnd", "hs_extract_owned", "hs_gmres_d", "hs_gmres_z", "hs_gmres_block_d", "hs_gmres_block_z", "hs_gmres_block_info", "hsk_spmm_d", "hsk_spmm_z",
+    "hs_gmres_t_d", "hs_gmres_t_z", "hs_gmres_block_t_d", "hs_gmres_block_t_z", "hsk_spmm_op_d", "hsk_spmm_op_z",
     "hs_exchange_kind", "hs_schur_pack_size", "hs_schur_pack", "hs_schur_unpack", "hs_flow_info", "hs_hss_pack_size", "hs_hss_pack", "hs_hss_unpack", "hs_hss_qr_order",
     "hs_comm_unique_id", "hs_comm_create_rccl", "hs_comm_create_host", "hs_comm_free", "hs_comm_kind", "hs_comm_selftest", "hs_comm_bandwidth", "hs_set_comm",
     "hs_symbolic_from_elimtree", "hs_symbolic_from_graph", "hs_symbolic_size", "hs_symbolic_perm", "hs_symbolic_tree", "hs_symbolic_free",
@@ -255,6 +256,15 @@ def lib():
         f.restype = C.c_int
     for f in (L.hs_gmres_block_d, L.hs_gmres_block_z):
         f.argtypes = [vp, i64, p_i64, p_i64, vp, vp, i64, vp, i64, i64, C.c_int, C.c_int, C.c_double, C.c_double, i64, i64, p_f64, p_i64, C.POINTER(C.c_int), vp]
+        f.restype = C.c_int
+    for f in (L.hs_gmres_t_d, L.hs_gmres_t_z):
+        f.argtypes = [vp, C.c_int, i64, p_i64, p_i64, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, i64, i64, p_f64, p_i64, C.POINTER(C.c_int), vp]
+        f.restype = C.c_int
+    for f in (L.hs_gmres_block_t_d, L.hs_gmres_block_t_z):
+        f.argtypes = [vp, C.c_int, i64, p_i64, p_i64, vp, vp, i64, vp, i64, i64, C.c_int, C.c_int, C.c_double, C.c_double, i64, i64, p_f64, p_i64, C.POINTER(C.c_int), vp]
+        f.restype = C.c_int
+    for f in (L.hsk_spmm_op_d, L.hsk_spmm_op_z):
+        f.argtypes = [C.c_int, i64, p_i64, p_i64, vp, vp, i64, vp, i64, vp, i64, i64]
         f.restype = C.c_int
     L.hs_gmres_block_info.argtypes = [p_f64]
     L.hs_gmres_block_info.restype = C.c_int

@@ -11,6 +11,11 @@
 // the Hessenberg / Givens recurrences and the final triangular solve run in one single-thread kernel each on device-resident H, c, s,
 // g -- the host reads ONE double (the residual estimate) per iteration to decide whether to go on: a preconditioner application costs
 // three orders of magnitude more than that read, and an iteration that is not needed costs a whole `ldiv!`.
+//
+// hs_gmres_t_* runs the same iteration on op(A) x = b, op(A) = A, transpose(A) or adjoint(A), right-preconditioned by op(Pr): gmres_device is a
+// template on the operator (the CSR SpMV above, or the SpMV over "entry ranges as rows" of hs_gmres_common.h, which reads the CSC columns of A
+// as the rows of op(A)) and on the preconditioner call (hs_ldiv_dev_* / hs_ldiv_dev_t_*).  A is passed as host CSC arrays or is the handle's
+// own (hs_gmres_op.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -20,16 +25,8 @@
 
 namespace {
 
-// y = A x (CSR, 0-based)   mode 1: y = b - A x
-template <class T>
-__global__ __launch_bounds__(256) void spmv_csr_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ colind, const T* __restrict__ val,
-                                                       const T* __restrict__ x, T* __restrict__ y, const T* __restrict__ b, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  T acc = Scal<T>::zero();
-  for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) acc = Scal<T>::fma(val[e], x[colind[e]], acc);
-  y[i] = b ? b[i] - acc : acc;
-}
+// y = A x (CSR, 0-based), or y = b - A x with b, is spmv_op_kernel<T, false> (hs_gmres_common.h): a CSR is the plain case of its "entry
+// ranges as rows".
 
 // part[blockIdx.x * (k+1) + j] = sum over the block's rows of conj(V[j][i]) * w[i],  j = 0..k
 template <class T>
@@ -216,8 +213,52 @@ int prec_apply<cplx>(hs_handle* F, cplx* out, const cplx* in, int64_t n, hipStre
 }
 
 template <class T>
-void gmres_device(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t* colind, const T* val, const T* b, T* x, int use_x0, double reltol, double abstol,
-                  int restart, int64_t maxiter, double* hist, int64_t* iters_out, int* conv_out, hipStream_t s) {
+int prec_apply_t(hs_handle* F, int trans, T* out, const T* in, int64_t n, hipStream_t s);
+template <>
+int prec_apply_t<double>(hs_handle* F, int trans, double* out, const double* in, int64_t n, hipStream_t s) {
+  return hs_ldiv_dev_t_d(F, trans, out, n, in, n, n, 1, (void*)s);
+}
+template <>
+int prec_apply_t<cplx>(hs_handle* F, int trans, cplx* out, const cplx* in, int64_t n, hipStream_t s) {
+  return hs_ldiv_dev_t_z(F, trans, (double*)out, n, (const double*)in, n, n, 1, (void*)s);
+}
+
+template <class T>
+int prec_apply_probe(hs_handle* F, int trans, int64_t n) {
+  return sizeof(T) == 16 ? hs_ldiv_dev_t_z(F, trans, nullptr, n, nullptr, n, n, 0, nullptr) : hs_ldiv_dev_t_d(F, trans, nullptr, n, nullptr, n, n, 0, nullptr);
+}
+
+// What gmres_device is instantiated on.  The operator: y = A x, or y = b - A x with b.  The preconditioner: out = Pr^-1 in; F == nullptr: none.
+template <class T>
+struct CsrSpmv {  // hs_gmres_*: the CSR upload of A
+  const int64_t* rowptr;
+  const int32_t* colind;
+  const T* val;
+  void operator()(const T* x, T* y, const T* b, int64_t n, hipStream_t s) const {
+    hipLaunchKernelGGL((spmv_op_kernel<T, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rowptr, colind, val, x, y, b, n);
+  }
+};
+template <class T>
+struct RowsSpmv {  // hs_gmres_t_*: op(A) over entry ranges
+  RowsOf<T> A;
+  void operator()(const T* x, T* y, const T* b, int64_t n, hipStream_t s) const { launch_spmv_op<T>(A, x, y, b, n, s); }
+};
+template <class T>
+struct PrecFwd {  // hs_ldiv_dev_*
+  hs_handle* F;
+  int operator()(T* out, const T* in, int64_t n, hipStream_t s) const { return prec_apply<T>(F, out, in, n, s); }
+};
+template <class T>
+struct PrecOp {  // hs_ldiv_dev_t_*: op(F)
+  hs_handle* F;
+  int trans;
+  int operator()(T* out, const T* in, int64_t n, hipStream_t s) const { return prec_apply_t<T>(F, trans, out, in, n, s); }
+};
+
+template <class T, class Op, class Prec>
+void gmres_device(const Op& A, const Prec& Pr, int64_t n, const T* b, T* x, int use_x0, double reltol, double abstol, int restart, int64_t maxiter, double* hist,
+                  int64_t* iters_out, int* conv_out, hipStream_t s) {
+  hs_handle* const F = Pr.F;
   DevBuf buf;
   const int m = restart;
   const int64_t ldv = (n + 1) / 2 * 2;
@@ -254,7 +295,7 @@ void gmres_device(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t*
   if (!use_x0) GM_HIP(hipMemsetAsync(x, 0, sizeof(T) * (size_t)n, s));
   // r = b - A x
   if (use_x0)
-    hipLaunchKernelGGL(spmv_csr_kernel<T>, dim3(gn), dim3(256), 0, s, rowptr, colind, val, (const T*)x, r, b, n);
+    A((const T*)x, r, b, n, s);
   else
     GM_HIP(hipMemcpyAsync(r, b, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, s));
   norm(r, dscal);
@@ -272,11 +313,11 @@ void gmres_device(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t*
       const T* vk = V + (size_t)k * ldv;
       const T* zz = vk;
       if (F) {
-        const int st = prec_apply<T>(F, z, vk, n, s);
+        const int st = Pr(z, vk, n, s);
         if (st != 0) throw st;
         zz = z;
       }
-      hipLaunchKernelGGL(spmv_csr_kernel<T>, dim3(gn), dim3(256), 0, s, rowptr, colind, val, zz, w, (const T*)nullptr, n);
+      A(zz, w, (const T*)nullptr, n, s);
       // classical Gram-Schmidt with one re-orthogonalisation pass: h = V^H w; w -= V h; h2 = V^H w; w -= V h2; H[:, k] = h + h2
       const int k1 = k + 1;
       hipLaunchKernelGGL(multi_dot_kernel<T>, dim3(nblk), dim3(256), 0, s, (const T*)V, ldv, k1, (const T*)w, part, n);
@@ -303,7 +344,7 @@ void gmres_device(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t*
       hipLaunchKernelGGL(hess_solve_kernel<T>, dim3(1), dim3(1), 0, s, S, k_used);
       if (F) {
         hipLaunchKernelGGL(combine_kernel<T>, dim3(gn), dim3(256), 0, s, (const T*)V, ldv, k_used, (const T*)S.y, (const T*)nullptr, w, n);
-        const int st = prec_apply<T>(F, z, w, n, s);
+        const int st = Pr(z, w, n, s);
         if (st != 0) throw st;
         T one = Scal<T>::one();
         GM_HIP(hipMemcpyAsync(S.y, &one, sizeof(T), hipMemcpyHostToDevice, s));
@@ -313,7 +354,7 @@ void gmres_device(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t*
         hipLaunchKernelGGL(combine_kernel<T>, dim3(gn), dim3(256), 0, s, (const T*)V, ldv, k_used, (const T*)S.y, (const T*)x, x, n);
       }
     }
-    hipLaunchKernelGGL(spmv_csr_kernel<T>, dim3(gn), dim3(256), 0, s, rowptr, colind, val, (const T*)x, r, b, n);
+    A((const T*)x, r, b, n, s);
     norm(r, dscal);
     beta = read(dscal);
     converged = converged || beta <= tol;
@@ -325,26 +366,28 @@ void gmres_device(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t*
 }
 
 
+// the checks and defaults hs_gmres_* and hs_gmres_t_* share (A apart)
 template <class T>
-int gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol, double abstol,
-                int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  if (n <= 0 || !colptr || !rowval || !nz || !b || !x || !iters || !converged) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres needs A (CSC), b, x and the two result slots");
-    return HS_ERR_ARGUMENT;
-  }
+int gmres_check(hs_handle* F, int64_t n, int64_t* restart, int64_t* maxiter, double* reltol) {
   if (F && (hs_size(F) != n || (hs_is_complex(F) != 0) != (sizeof(T) == 16))) {
     hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld", (long long)hs_size(F), (long long)hs_size(F),
                  hs_is_complex(F) ? "ComplexF64" : "Float64", (long long)n, (long long)n);
     return HS_ERR_DIMENSION;
   }
   // defaults of IterativeSolvers 0.9: restart = min(20, n), maxiter = n, reltol = sqrt(eps)
-  if (restart <= 0) restart = std::min<int64_t>(20, n);
-  if (restart > GM_MAXK) {
-    hs_set_error(HS_ERR_ARGUMENT, restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)restart, GM_MAXK);
+  if (*restart <= 0) *restart = std::min<int64_t>(20, n);
+  if (*restart > GM_MAXK) {
+    hs_set_error(HS_ERR_ARGUMENT, *restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)*restart, GM_MAXK);
     return HS_ERR_ARGUMENT;
   }
-  if (maxiter < 0) maxiter = n;
-  if (!(reltol >= 0.0)) reltol = 1.4901161193847656e-08;
+  if (*maxiter < 0) *maxiter = n;
+  if (!(*reltol >= 0.0)) *reltol = 1.4901161193847656e-08;
+  return HS_OK;
+}
+// from the device check to the results; make_op(buf, s) puts A on the device (or finds it there) and returns the operator
+template <class T, class MakeOp, class Prec>
+int gmres_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* b, T* x, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
+              double* resnorm, int64_t* iters, int* converged, void* stream) {
   try {
     int cnt = 0;
     if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
@@ -353,10 +396,7 @@ int gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* r
     }
     DevBuf buf;
     hipStream_t s = (hipStream_t)stream;
-    int64_t* d_rp;
-    int32_t* d_ci;
-    T* d_v;
-    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+    const auto A = make_op(buf, s);
     std::vector<double> hist((size_t)maxiter + 2, 0.0);
     const T* db = b;
     T* dx = x;
@@ -368,7 +408,7 @@ int gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* r
       db = tb;
       dx = tx;
     }
-    gmres_device<T>(F, n, d_rp, d_ci, d_v, db, dx, use_x0, reltol, abstol, (int)restart, maxiter, hist.data(), iters, converged, s);
+    gmres_device<T>(A, Pr, n, db, dx, use_x0, reltol, abstol, (int)restart, maxiter, hist.data(), iters, converged, s);
     if (where == 0) GM_HIP(hipMemcpy(x, dx, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost));
     if (resnorm)
       for (int64_t i = 0; i <= *iters; ++i) resnorm[i] = hist[(size_t)i];
@@ -381,6 +421,46 @@ int gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* r
   }
 }
 
+template <class T>
+int gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol, double abstol,
+                int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  if (n <= 0 || !colptr || !rowval || !nz || !b || !x || !iters || !converged) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres needs A (CSC), b, x and the two result slots");
+    return HS_ERR_ARGUMENT;
+  }
+  if (const int st = gmres_check<T>(F, n, &restart, &maxiter, &reltol)) return st;
+  auto make_op = [&](DevBuf& buf, hipStream_t) {
+    int64_t* d_rp;
+    int32_t* d_ci;
+    T* d_v;
+    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+    return CsrSpmv<T>{d_rp, d_ci, d_v};
+  };
+  return gmres_run<T>(make_op, PrecFwd<T>{F}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+
+// hs_gmres_t_*: op(A) x = b right-preconditioned by op(Pr); A explicit or the handle's own
+template <class T>
+int gmres_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol,
+                  double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  bool own = false;
+  if (const int st = gm_check_op_args("hs_gmres_t_*", F, trans, colptr, rowval, nz, &own)) return st;
+  if (trans == 0 && !own) return gmres_entry<T>(F, n, colptr, rowval, nz, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  if (n <= 0 || !b || !x || !iters || !converged) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_t needs n >= 1, b, x and the two result slots");
+    return HS_ERR_ARGUMENT;
+  }
+  if (const int st = gmres_check<T>(F, n, &restart, &maxiter, &reltol)) return st;
+  if (own)
+    if (const int st = hs_gmres_own_check(F, "hs_gmres_t_*", 1)) return st;
+  if (F)  // what hs_ldiv_t_* refuses (or an unfactored handle) is refused here, before any device work: zero columns are solved
+    if (const int st = prec_apply_probe<T>(F, trans, n)) return st;
+  if (own)
+    if (const int st = hs_gmres_own_check(F, "hs_gmres_t_*", 0)) return st;
+  auto make_op = [&](DevBuf& buf, hipStream_t s) { return RowsSpmv<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
+  return gmres_run<T>(make_op, PrecOp<T>{F, trans}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+
 }  // namespace
 
 extern "C" int hs_gmres_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
@@ -391,4 +471,13 @@ extern "C" int hs_gmres_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const
                           double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
   return gmres_entry<cplx>(Pr, n, colptr, rowval, (const cplx*)nzval, (const cplx*)b, (cplx*)x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
                            stream);
+}
+extern "C" int hs_gmres_t_d(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where,
+                            int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_t_entry<double>(Pr, trans, n, colptr, rowval, nzval, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+extern "C" int hs_gmres_t_z(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where,
+                            int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_t_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)b, (cplx*)x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters,
+                             converged, stream);
 }

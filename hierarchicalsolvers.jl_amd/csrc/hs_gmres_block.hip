@@ -15,6 +15,10 @@
 //
 // Determinism: no atomics, every reduction in a fixed order that depends on the row index alone, so a column's results do not depend on its
 // slot, on the other columns, on G or on compaction.
+//
+// hs_gmres_block_t_* runs the same schedule on op(A) X = B right-preconditioned by op(Pr): gmres_group is a template on the operator (the CSR
+// SpMM below, or the SpMM over "entry ranges as rows" of hs_gmres_common.h) and on the preconditioner call (hs_ldiv_block_dev_* /
+// hs_ldiv_block_dev_t_*); A is passed as host CSC arrays or is the handle's own (hs_gmres_op.h).
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -30,41 +34,13 @@ namespace {
 // A workgroup owns 256 rows and walks the columns CB at a time, lanes along rows: X[:, c] and Y[:, c] are read and written contiguously, and
 // rowptr / colind / val of the row tile are read once per chunk of CB columns, not once per column (the chunks after the first follow it in
 // the same workgroup and should find them in L2; that is not measured).  Per (row, column) the sum runs over e in
-// stored order with Scal<T>::fma, as spmv_csr_kernel (hs_gmres.hip) does.
-template <class T, int CB>
-__global__ __launch_bounds__(256) void spmm_csr_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ colind, const T* __restrict__ val,
-                                                       const T* __restrict__ X, int64_t ldx, const int64_t* __restrict__ xmap, T* __restrict__ Y, int64_t ldy,
-                                                       const T* __restrict__ B, int64_t ldb, const int64_t* __restrict__ bmap, int64_t n, int nc) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
-  for (int c0 = 0; c0 < nc; c0 += CB) {
-    T acc[CB];
-    const T* xp[CB];
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-      const int cc = min(c0 + c, nc - 1);  // a ragged chunk recomputes its last column and does not store it
-      xp[c] = X + (size_t)(xmap ? xmap[cc] : cc) * ldx;
-      acc[c] = Scal<T>::zero();
-    }
-    for (int64_t e = e0; e < e1; ++e) {
-      const T a = val[e];
-      const int32_t j = colind[e];
-#pragma unroll
-      for (int c = 0; c < CB; ++c) acc[c] = Scal<T>::fma(a, xp[c][j], acc[c]);
-    }
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-      const int cc = c0 + c;
-      if (cc < nc) Y[(size_t)cc * ldy + i] = B ? B[(size_t)(bmap ? bmap[cc] : cc) * ldb + i] - acc[c] : acc[c];
-    }
-  }
-}
+// stored order with Scal<T>::fma, as the single-vector product of hs_gmres.hip (spmv_op_kernel) does.
+// The kernel is spmm_op_kernel<T, CB, false> (hs_gmres_common.h): a CSR is the plain case of its "entry ranges as rows".
 template <class T>
 void launch_spmm(const int64_t* rowptr, const int32_t* colind, const T* val, const T* X, int64_t ldx, const int64_t* xmap, T* Y, int64_t ldy, const T* B, int64_t ldb,
                  const int64_t* bmap, int64_t n, int nc, hipStream_t s) {
   constexpr int CB = sizeof(T) == 16 ? 4 : 8;
-  hipLaunchKernelGGL((spmm_csr_kernel<T, CB>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rowptr, colind, val, X, ldx, xmap, Y, ldy, B, ldb, bmap, n, nc);
+  hipLaunchKernelGGL((spmm_op_kernel<T, CB, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rowptr, colind, val, X, ldx, xmap, Y, ldy, B, ldb, bmap, n, nc);
 }
 
 // The batched forms of the kernels of hs_gmres.hip: the column (slot) is blockIdx.y, a frozen column (mask[c] == 0) is skipped.
@@ -315,6 +291,47 @@ int prec_block<cplx>(hs_handle* F, cplx* out, const cplx* in, int64_t ld, int64_
   return hs_ldiv_block_dev_z(F, 0, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
 }
 
+template <class T>
+int prec_block_t(hs_handle* F, int trans, T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s);
+template <>
+int prec_block_t<double>(hs_handle* F, int trans, double* out, const double* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) {
+  return hs_ldiv_block_dev_t_d(F, trans, out, ld, in, ld, n, nc, (void*)s);
+}
+template <>
+int prec_block_t<cplx>(hs_handle* F, int trans, cplx* out, const cplx* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) {
+  return hs_ldiv_block_dev_t_z(F, trans, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
+}
+
+// What gmres_group is instantiated on.  The operator: Y[:, c] = A X[:, xmap[c]], or B[:, bmap[c]] - A X[:, xmap[c]] with B.  The
+// preconditioner: out = Pr^-1 in on an n x nc block; F == nullptr: none.
+template <class T>
+struct CsrSpmm {  // hs_gmres_block_*: the CSR upload of A
+  const int64_t* rowptr;
+  const int32_t* colind;
+  const T* val;
+  void operator()(const T* X, int64_t ldx, const int64_t* xmap, T* Y, int64_t ldy, const T* B, int64_t ldb, const int64_t* bmap, int64_t n, int nc, hipStream_t s) const {
+    launch_spmm<T>(rowptr, colind, val, X, ldx, xmap, Y, ldy, B, ldb, bmap, n, nc, s);
+  }
+};
+template <class T>
+struct RowsSpmm {  // hs_gmres_block_t_*: op(A) over entry ranges
+  RowsOf<T> A;
+  void operator()(const T* X, int64_t ldx, const int64_t* xmap, T* Y, int64_t ldy, const T* B, int64_t ldb, const int64_t* bmap, int64_t n, int nc, hipStream_t s) const {
+    launch_spmm_op<T>(A, X, ldx, xmap, Y, ldy, B, ldb, bmap, n, nc, s);
+  }
+};
+template <class T>
+struct PrecBlockFwd {  // hs_ldiv_block_dev_*
+  hs_handle* F;
+  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return prec_block<T>(F, out, in, ld, n, nc, s); }
+};
+template <class T>
+struct PrecBlockOp {  // hs_ldiv_block_dev_t_*: op(F)
+  hs_handle* F;
+  int trans;
+  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return prec_block_t<T>(F, trans, out, in, ld, n, nc, s); }
+};
+
 // figures of the calling thread's last hs_gmres_block_* call (hs_gmres_block_info)
 enum { GI_SECONDS = 0, GI_PREC_CALLS, GI_COL_APPS, GI_SPMM, GI_CYCLES, GI_GROUPS, GI_WORK_BYTES, GI_MAX_ACTIVE };
 thread_local double g_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -344,9 +361,10 @@ size_t bytes_per_column(int64_t n, int m) {
 }
 
 // one group of gc <= G columns (g0 .. g0 + gc of the caller's B and X, device pointers) from start to finish
-template <class T>
-void gmres_group(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t* colind, const T* val, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t g0, int gc,
-                 int use_x0, double reltol, double abstol, int64_t maxiter, Workspace<T>& ws, Column* cols, hipStream_t s) {
+template <class T, class Op, class Prec>
+void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t g0, int gc, int use_x0, double reltol, double abstol,
+                 int64_t maxiter, Workspace<T>& ws, Column* cols, hipStream_t s) {
+  hs_handle* const F = Pr.F;
   const int m = ws.m, nblk = ws.nblk;
   const int64_t ldv = ws.ldv, jstride = ws.G * ldv;
   GbSmall<T>& S = ws.S;
@@ -364,7 +382,7 @@ void gmres_group(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t* 
     hipLaunchKernelGGL(bnorm2_final_kernel, dim3(nc), dim3(256), 0, s, (const double*)ws.dpart, nblk, out, ostride, mask);
   };
   auto residual = [&](int nc) {  // R[:, c] = B[:, col[c]] - A X[:, col[c]]
-    launch_spmm<T>(rowptr, colind, val, (const T*)X, ldx, (const int64_t*)S.col, ws.R, ldv, B, ldb, (const int64_t*)S.col, n, nc, s);
+    A((const T*)X, ldx, (const int64_t*)S.col, ws.R, ldv, B, ldb, (const int64_t*)S.col, n, nc, s);
     g_info[GI_SPMM] += 1;
   };
   // r0 = b - A x0, slots in the order of the columns
@@ -430,13 +448,13 @@ void gmres_group(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t* 
       const T* Vk = ws.V + (size_t)k * jstride;
       const T* zz = Vk;
       if (F) {
-        const int st = prec_block<T>(F, ws.Z, Vk, ldv, n, nact, s);
+        const int st = Pr(ws.Z, Vk, ldv, n, nact, s);
         if (st != 0) throw st;
         g_info[GI_PREC_CALLS] += 1;
         g_info[GI_COL_APPS] += nact;
         zz = ws.Z;
       }
-      launch_spmm<T>(rowptr, colind, val, zz, ldv, (const int64_t*)nullptr, ws.W, ldv, (const T*)nullptr, 0, (const int64_t*)nullptr, n, nact, s);
+      A(zz, ldv, (const int64_t*)nullptr, ws.W, ldv, (const T*)nullptr, (int64_t)0, (const int64_t*)nullptr, n, nact, s);
       g_info[GI_SPMM] += 1;
       // classical Gram-Schmidt with one re-orthogonalisation pass, per column: h = V^H w; w -= V h; h2 = V^H w; w -= V h2; H[:, k] = h + h2
       const int k1 = k + 1;
@@ -469,7 +487,7 @@ void gmres_group(hs_handle* F, int64_t n, const int64_t* rowptr, const int32_t* 
     if (F) {
       hipLaunchKernelGGL(bcombine_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.V, ldv, jstride, (const T*)S.y, S.s1, (const int*)S.kused, (T*)nullptr, (int64_t)0,
                          (const int64_t*)nullptr, ws.W, ldv, n);
-      const int st = prec_block<T>(F, ws.Z, ws.W, ldv, n, nact, s);
+      const int st = Pr(ws.Z, ws.W, ldv, n, nact, s);
       if (st != 0) throw st;
       g_info[GI_PREC_CALLS] += 1;
       g_info[GI_COL_APPS] += nact;
@@ -511,23 +529,15 @@ int64_t group_width(size_t per_col, int64_t nrhs) {
 }
 
 template <class T>
-int refused_by_block_solve(hs_handle* F, int64_t n);
-template <>
-int refused_by_block_solve<double>(hs_handle* F, int64_t n) { return hs_ldiv_block_dev_d(F, 0, nullptr, n, nullptr, n, n, 0, nullptr); }
-template <>
-int refused_by_block_solve<cplx>(hs_handle* F, int64_t n) { return hs_ldiv_block_dev_z(F, 0, nullptr, n, nullptr, n, n, 0, nullptr); }
+int refused_by_block_solve(hs_handle* F, int trans, int64_t n) {  // zero columns: the checks of the block solve and nothing else
+  if (trans == 0) return sizeof(T) == 16 ? hs_ldiv_block_dev_z(F, 0, nullptr, n, nullptr, n, n, 0, nullptr) : hs_ldiv_block_dev_d(F, 0, nullptr, n, nullptr, n, n, 0, nullptr);
+  return sizeof(T) == 16 ? hs_ldiv_block_dev_t_z(F, trans, nullptr, n, nullptr, n, n, 0, nullptr) : hs_ldiv_block_dev_t_d(F, trans, nullptr, n, nullptr, n, n, 0, nullptr);
+}
 
+// the checks and defaults hs_gmres_block_* and hs_gmres_block_t_* share (A and nrhs = 0 apart)
 template <class T>
-int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where,
-                      int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  if (n <= 0 || nrhs < 0 || !colptr || !rowval || !nz) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs A (CSC) and nrhs >= 0");
-    return HS_ERR_ARGUMENT;
-  }
-  if (nrhs == 0) {
-    for (double& v : g_info) v = 0.0;
-    return HS_OK;
-  }
+int gmres_block_check(hs_handle* F, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int where, int64_t* restart, int64_t* maxiter, double* reltol, int64_t* iters,
+                      int* converged) {
   if (!B || !X || !iters || !converged || (const void*)B == (const void*)X) {
     hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs B, X (not aliasing B) and the two result arrays");
     return HS_ERR_ARGUMENT;
@@ -546,23 +556,20 @@ int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int6
     return HS_ERR_DIMENSION;
   }
   // defaults of IterativeSolvers 0.9, as hs_gmres_*
-  if (restart <= 0) restart = std::min<int64_t>(20, n);
-  if (restart > GM_MAXK) {
-    hs_set_error(HS_ERR_ARGUMENT, restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)restart, GM_MAXK);
+  if (*restart <= 0) *restart = std::min<int64_t>(20, n);
+  if (*restart > GM_MAXK) {
+    hs_set_error(HS_ERR_ARGUMENT, *restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)*restart, GM_MAXK);
     return HS_ERR_ARGUMENT;
   }
-  if (maxiter < 0) maxiter = n;
-  if (!(reltol >= 0.0)) reltol = 1.4901161193847656e-08;
-  if (F) {  // what hs_ldiv_block_* refuses is refused here, before any device work: nothing is silently looped
-    const int st = refused_by_block_solve<T>(F, n);
-    if (st == HS_ERR_UNSUPPORTED) {
-      const std::string why = hs_last_error();
-      hs_set_error(HS_ERR_UNSUPPORTED, hs_last_error_info(), "hs_gmres_block_*: the block solve does not serve this preconditioner (%s); hs_gmres_* serves it, one right-hand side at a time",
-                   why.c_str());
-      return st;
-    }
-    if (st != 0) return st;
-  }
+  if (*maxiter < 0) *maxiter = n;
+  if (!(*reltol >= 0.0)) *reltol = 1.4901161193847656e-08;
+  return HS_OK;
+}
+
+// from the device check to the results; make_op(buf, s) puts A on the device (or finds it there) and returns the operator
+template <class T, class MakeOp, class Prec>
+int gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol,
+                    int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
   int cnt = 0;
   if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
     hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
@@ -574,10 +581,7 @@ int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int6
   try {
     for (double& v : g_info) v = 0.0;
     hipStream_t s = (hipStream_t)stream;
-    int64_t* d_rp;
-    int32_t* d_ci;
-    T* d_v;
-    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+    const auto A = make_op(buf, s);
     const T* dB = B;
     T* dX = X;
     int64_t dldb = ldb, dldx = ldx;
@@ -635,7 +639,7 @@ int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int6
     std::vector<Column> cols((size_t)nrhs);
     for (int64_t g0 = 0; g0 < nrhs; g0 += ws.G) {
       const int gc = (int)std::min<int64_t>(ws.G, nrhs - g0);
-      gmres_group<T>(F, n, d_rp, d_ci, d_v, dB, dldb, dX, dldx, g0, gc, use_x0, reltol, abstol, maxiter, ws, cols.data() + g0, s);
+      gmres_group<T>(A, Pr, n, dB, dldb, dX, dldx, g0, gc, use_x0, reltol, abstol, maxiter, ws, cols.data() + g0, s);
       g_info[GI_GROUPS] += 1;
     }
     GM_HIP(hipEventRecord(e1, s));
@@ -663,6 +667,76 @@ int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int6
   return rc;
 }
 
+template <class T>
+int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where,
+                      int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  if (n <= 0 || nrhs < 0 || !colptr || !rowval || !nz) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs A (CSC) and nrhs >= 0");
+    return HS_ERR_ARGUMENT;
+  }
+  if (nrhs == 0) {
+    for (double& v : g_info) v = 0.0;
+    return HS_OK;
+  }
+  if (const int st = gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
+  if (F) {  // what hs_ldiv_block_* refuses is refused here, before any device work: nothing is silently looped
+    const int st = refused_by_block_solve<T>(F, 0, n);
+    if (st == HS_ERR_UNSUPPORTED) {
+      const std::string why = hs_last_error();
+      hs_set_error(HS_ERR_UNSUPPORTED, hs_last_error_info(), "hs_gmres_block_*: the block solve does not serve this preconditioner (%s); hs_gmres_* serves it, one right-hand side at a time",
+                   why.c_str());
+      return st;
+    }
+    if (st != 0) return st;
+  }
+  auto make_op = [&](DevBuf& buf, hipStream_t) {
+    int64_t* d_rp;
+    int32_t* d_ci;
+    T* d_v;
+    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+    return CsrSpmm<T>{d_rp, d_ci, d_v};
+  };
+  return gmres_block_run<T>(make_op, PrecBlockFwd<T>{F}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+
+// hs_gmres_block_t_*: op(A) X = B right-preconditioned by op(Pr); A explicit or the handle's own
+template <class T>
+int gmres_block_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs,
+                        int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  bool own = false;
+  if (const int st = gm_check_op_args("hs_gmres_block_t_*", F, trans, colptr, rowval, nz, &own)) return st;
+  if (trans == 0 && !own)
+    return gmres_block_entry<T>(F, n, colptr, rowval, nz, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  if (n <= 0 || nrhs < 0) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block_t needs n >= 1 and nrhs >= 0");
+    return HS_ERR_ARGUMENT;
+  }
+  if (own && hs_size(F) != n) {
+    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the handle's own A is %lld x %lld, n = %lld", (long long)hs_size(F), (long long)hs_size(F), (long long)n);
+    return HS_ERR_DIMENSION;
+  }
+  if (nrhs == 0) {
+    for (double& v : g_info) v = 0.0;
+    return HS_OK;
+  }
+  if (const int st = gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
+  if (own)
+    if (const int st = hs_gmres_own_check(F, "hs_gmres_block_t_*", 1)) return st;
+  if (F) {  // what hs_ldiv_block_t_* refuses is refused here whatever trans is, before any device work
+    const int st = refused_by_block_solve<T>(F, trans, n);
+    if (st == HS_ERR_UNSUPPORTED) {
+      const std::string why = hs_last_error();
+      hs_set_error(HS_ERR_UNSUPPORTED, hs_last_error_info(), "hs_gmres_block_t_*: the block solve does not serve this preconditioner (%s)", why.c_str());
+      return st;
+    }
+    if (st != 0) return st;
+  }
+  if (own)
+    if (const int st = hs_gmres_own_check(F, "hs_gmres_block_t_*", 0)) return st;
+  auto make_op = [&](DevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
+  return gmres_block_run<T>(make_op, PrecBlockOp<T>{F, trans}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+
 // hsk_spmm_*: the SpMM kernel alone on host data
 template <class T>
 int spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy, int64_t nrhs) {
@@ -688,6 +762,51 @@ int spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* 
     GM_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
     if (B) GM_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
     launch_spmm<T>(d_rp, d_ci, d_v, dX, ldx, (const int64_t*)nullptr, dY, ldy, dB, ldb, (const int64_t*)nullptr, n, (int)nrhs, (hipStream_t)0);
+    GM_HIP(hipDeviceSynchronize());
+    GM_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
+    return HS_OK;
+  } catch (int code) {
+    return code;
+  } catch (const std::bad_alloc&) {
+    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
+    return HS_ERR_NOMEM;
+  }
+}
+
+// hsk_spmm_op_*: the op(A) SpMM kernel alone on host data.  trans = 0 reads the CSR upload of A, trans = 1, 2 the 0-based CSC upload itself.
+template <class T>
+int spmm_op_hook(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy,
+                 int64_t nrhs) {
+  if (trans < 0 || trans > 2 || n <= 0 || nrhs < 1 || !colptr || !rowval || !nz || !X || !Y || ldx < n || ldy < n || (B && ldb < n)) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_spmm_op: trans in 0:2, n >= 1, nrhs >= 1, leading dimensions >= n and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  try {
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+      hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
+      return HS_ERR_DEVICE;
+    }
+    DevBuf buf;
+    int64_t* d_p;
+    int32_t* d_i;
+    T* d_v;
+    if (trans == 0)
+      upload_csr<T>(buf, n, colptr, rowval, nz, &d_p, &d_i, &d_v);
+    else
+      upload_csc<T>(buf, n, colptr, rowval, nz, &d_p, &d_i, &d_v);
+    RowsOf<T> A;
+    A.ptr = d_p;
+    A.idx = d_i;
+    A.val = d_v;
+    A.conj = trans == 2;
+    T* dX = buf.get<T>((size_t)ldx * nrhs);
+    T* dY = buf.get<T>((size_t)ldy * nrhs);
+    T* dB = B ? buf.get<T>((size_t)ldb * nrhs) : nullptr;
+    GM_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
+    GM_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
+    if (B) GM_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
+    launch_spmm_op<T>(A, dX, ldx, (const int64_t*)nullptr, dY, ldy, dB, ldb, (const int64_t*)nullptr, n, (int)nrhs, (hipStream_t)0);
     GM_HIP(hipDeviceSynchronize());
     GM_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
     return HS_OK;
@@ -727,4 +846,24 @@ extern "C" int hsk_spmm_d(int64_t n, const int64_t* colptr, const int64_t* rowva
 extern "C" int hsk_spmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,
                           int64_t ldy, int64_t nrhs) {
   return spmm_hook<cplx>(n, colptr, rowval, (const cplx*)nzval, (const cplx*)X, ldx, (const cplx*)B, ldb, (cplx*)Y, ldy, nrhs);
+}
+extern "C" int hs_gmres_block_t_d(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
+                                  double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
+                                  int64_t* iters, int* converged, void* stream) {
+  return gmres_block_t_entry<double>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                                     stream);
+}
+extern "C" int hs_gmres_block_t_z(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
+                                  double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
+                                  int64_t* iters, int* converged, void* stream) {
+  return gmres_block_t_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter,
+                                   resnorm, iters, converged, stream);
+}
+extern "C" int hsk_spmm_op_d(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B,
+                             int64_t ldb, double* Y, int64_t ldy, int64_t nrhs) {
+  return spmm_op_hook<double>(trans, n, colptr, rowval, nzval, X, ldx, B, ldb, Y, ldy, nrhs);
+}
+extern "C" int hsk_spmm_op_z(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B,
+                             int64_t ldb, double* Y, int64_t ldy, int64_t nrhs) {
+  return spmm_op_hook<cplx>(trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)X, ldx, (const cplx*)B, ldb, (cplx*)Y, ldy, nrhs);
 }

@@ -7,6 +7,8 @@ The call the reference's scenario makes (``test/rungmres.jl:47-48``)::
 ``IterativeSolvers.gmres`` (0.9.0, not part of the reference tree) uses the preconditioner only through ``ldiv!``.  ``gmres`` here is
 ``hs_gmres_{d,z}`` of the C ABI (include/hs_solver.h, csrc/hs_gmres.hip): hand-written CSR SpMV, Gram-Schmidt and Givens kernels, the
 preconditioner applied through ``hs_ldiv_dev_*`` on device pointers -- what a Julia host calls instead of ``IterativeSolvers.gmres``.
+``trans="T"`` / ``"C"`` (or ``Pr=transpose(F)`` / ``adjoint(F)``) solve ``transpose(A) x = b`` / ``A' x = b`` with the same factorization
+(``hs_gmres_t_*``, ``hs_gmres_block_t_*``); ``A=None`` takes the matrix the handle already holds on the device.
 (An independent torch restatement of the same iteration lives under tests/gmres_mirror.py: test infrastructure, not product.)
 Parity unpinned: IterativeSolvers is absent.
 """
@@ -29,27 +31,66 @@ def _csc_fields(A, dtype):
             np.ascontiguousarray(A.data, dtype=dtype))
 
 
-def gmres(A, b, Pr=None, reltol=None, abstol=0.0, restart=None, maxiter=None, log=False, x0=None, device=None):
+_TRANS = {"N": 0, "T": 1, "C": 2}
+
+
+def _op_of(Pr, trans):
+    """``(FactorNode or None, trans code)`` of the ``Pr`` / ``trans`` pair: ``Pr=transpose(F)`` / ``adjoint(F)`` is shorthand for the matching
+    ``trans``; a pair that names two different operators raises ``ValueError``."""
+    from .solver import TransposedFactor
+
+    if trans is not None and trans not in _TRANS:
+        raise ValueError(f"trans must be 'N', 'T' or 'C', not {trans!r}")
+    code = None if trans is None else _TRANS[trans]
+    if isinstance(Pr, TransposedFactor):
+        w = Pr.trans
+        if code is not None and code != w and not (Pr.dtype.kind != "c" and code in (1, 2)):  # Float64: adjoint = transpose
+            raise ValueError(f"trans={trans!r} conflicts with Pr={Pr!r}")
+        return Pr.parent, w
+    return Pr, code or 0
+
+
+def _own_size(A, Pr):
+    if A is not None:
+        return A.shape[0]
+    if Pr is None:
+        raise ValueError("ArgumentError: A=None selects the matrix of the factorization Pr, which is None")
+    return Pr.n
+
+
+def gmres(A, b, Pr=None, reltol=None, abstol=0.0, restart=None, maxiter=None, log=False, x0=None, device=None, trans=None):
     """Restarted GMRES(restart) on ``A x = b`` with right preconditioner ``Pr`` (a :class:`FactorNode`), behind the C ABI (``hs_gmres_{d,z}``).
+
+    ``trans="T"`` / ``"C"`` (the letters of :meth:`FactorNode.solve`) solve ``transpose(A) x = b`` / ``adjoint(A) x = b`` preconditioned by
+    ``transpose(Pr)`` / ``adjoint(Pr)`` (``hs_gmres_t_{d,z}``); ``A`` is always the matrix itself.  ``Pr=transpose(F)`` / ``adjoint(F)`` is
+    shorthand for the matching ``trans``.  ``A=None`` takes the matrix ``Pr`` was factored from, as the handle holds it on the device: nothing
+    is converted or uploaded.  With ``trans`` ``"N"`` (the default) and an explicit ``A`` the call is ``hs_gmres_{d,z}`` as before.
 
     Defaults follow IterativeSolvers 0.9: ``restart = min(20, n)``, ``maxiter = n``, ``reltol = sqrt(eps)``; convergence when
     ``||b - A x|| <= max(reltol * ||r0||, abstol)``.  Returns ``x`` (NumPy, host) or ``(x, history)`` with
     ``history = dict(resnorm=[...], isconverged, iters)``.  (``device`` is accepted for compatibility; the library uses the current device.)"""
-    n = A.shape[0]
-    cplx = np.iscomplexobj(A.data) or np.iscomplexobj(b) or (Pr is not None and Pr.dtype.kind == "c")
+    Pr, tcode = _op_of(Pr, trans)
+    n = _own_size(A, Pr)
+    cplx = (A is not None and np.iscomplexobj(A.data)) or np.iscomplexobj(b) or (Pr is not None and Pr.dtype.kind == "c")
     dt = np.complex128 if cplx else np.float64
-    colptr, rowval, nz = _csc_fields(A, dt)
+    colptr, rowval, nz = _csc_fields(A, dt) if A is not None else (None, None, None)
     bb = np.ascontiguousarray(b, dtype=dt)
     x = np.zeros(n, dtype=dt) if x0 is None else np.ascontiguousarray(x0, dtype=dt).copy()
     maxit = n if maxiter is None else int(maxiter)
     hist = np.zeros(maxit + 2)
     iters, conv = _lib.i64(0), C.c_int(0)
     L = _lib.lib()
-    fn = L.hs_gmres_z if cplx else L.hs_gmres_d
     vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _lib.check(fn(Pr._h if Pr is not None else None, n, colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz), vp(bb), vp(x), 0,
-                  int(x0 is not None), -1.0 if reltol is None else float(reltol), float(abstol), -1 if restart is None else int(restart), maxit,
-                  hist.ctypes.data_as(_lib.p_f64), C.byref(iters), C.byref(conv), None))
+    tail = (vp(bb), vp(x), 0, int(x0 is not None), -1.0 if reltol is None else float(reltol), float(abstol), -1 if restart is None else int(restart), maxit,
+            hist.ctypes.data_as(_lib.p_f64), C.byref(iters), C.byref(conv), None)
+    h = Pr._h if Pr is not None else None
+    if tcode == 0 and A is not None:
+        fn = L.hs_gmres_z if cplx else L.hs_gmres_d
+        _lib.check(fn(h, n, colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz), *tail))
+    else:
+        fn = L.hs_gmres_t_z if cplx else L.hs_gmres_t_d
+        a3 = (None, None, None) if A is None else (colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz))
+        _lib.check(fn(h, tcode, n, *a3, *tail))
     if log:
         return x, dict(resnorm=[float(v) for v in hist[: iters.value + 1]], isconverged=bool(conv.value), iters=int(iters.value))
     return x
@@ -79,22 +120,24 @@ def gmres_device(A, b_dev, solver, reltol=1e-9, abstol=0.0, restart=30, maxiter=
     return x, [float(v) for v in hist[: iters.value + 1]]
 
 
-def gmres_block(A, B, Pr=None, reltol=None, abstol=0.0, restart=None, maxiter=None, log=False, X0=None):
+def gmres_block(A, B, Pr=None, reltol=None, abstol=0.0, restart=None, maxiter=None, log=False, X0=None, trans=None):
     """:func:`gmres` on every column of the ``n x nrhs`` block ``B`` in lockstep (``hs_gmres_block_{d,z}``): the columns share the restart
     cycle and the Arnoldi index, so a step applies ``Pr`` to all active columns with one block solve (``hs_ldiv_block_dev_*``) and multiplies
     by ``A`` with one SpMM.  Every column keeps its own Krylov space and stopping test and returns what :func:`gmres` returns for it alone
     (to the rounding by which :func:`ldiv_block` and :func:`ldiv` differ).  ``Pr`` must be a handle the block solve serves
     (:class:`UnsupportedError` otherwise: :func:`gmres` serves those).  Returns ``X`` or ``(X, [history dict per column])``; a 1-D ``B`` is
     one column and returns a vector (and one history dict).  With ``log=True`` the history buffer is ``(maxiter + 1) x nrhs`` doubles: give a
-    ``maxiter`` when ``n`` and ``nrhs`` are both large (the default is ``n``)."""
-    n = A.shape[0]
+    ``maxiter`` when ``n`` and ``nrhs`` are both large (the default is ``n``).  ``trans``, ``Pr=transpose(F)`` / ``adjoint(F)`` and ``A=None``
+    as in :func:`gmres` (``hs_gmres_block_t_{d,z}``, the block solve ``hs_ldiv_block_dev_t_*``)."""
+    Pr, tcode = _op_of(Pr, trans)
+    n = _own_size(A, Pr)
     B = np.asarray(B)
     vec = B.ndim == 1
     if B.shape[0] != n:
         raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, A is {n} x {n}")
-    cplx = np.iscomplexobj(A.data) or np.iscomplexobj(B) or (Pr is not None and Pr.dtype.kind == "c") or (X0 is not None and np.iscomplexobj(X0))
+    cplx = (A is not None and np.iscomplexobj(A.data)) or np.iscomplexobj(B) or (Pr is not None and Pr.dtype.kind == "c") or (X0 is not None and np.iscomplexobj(X0))
     dt = np.complex128 if cplx else np.float64
-    colptr, rowval, nz = _csc_fields(A, dt)
+    colptr, rowval, nz = _csc_fields(A, dt) if A is not None else (None, None, None)
     Bm = np.asfortranarray(B.reshape(n, -1), dtype=dt)
     k = Bm.shape[1]
     if X0 is None:
@@ -110,11 +153,17 @@ def gmres_block(A, B, Pr=None, reltol=None, abstol=0.0, restart=None, maxiter=No
     iters = np.zeros(max(k, 1), dtype=np.int64)
     conv = np.zeros(max(k, 1), dtype=np.int32)
     L = _lib.lib()
-    fn = L.hs_gmres_block_z if cplx else L.hs_gmres_block_d
     vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _lib.check(fn(Pr._h if Pr is not None else None, n, colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz), vp(Bm), n, vp(X), n, k, 0,
-                  int(X0 is not None), -1.0 if reltol is None else float(reltol), float(abstol), -1 if restart is None else int(restart), maxit,
-                  hist.ctypes.data_as(_lib.p_f64) if log else None, iters.ctypes.data_as(_lib.p_i64), conv.ctypes.data_as(C.POINTER(C.c_int)), None))
+    tail = (vp(Bm), n, vp(X), n, k, 0, int(X0 is not None), -1.0 if reltol is None else float(reltol), float(abstol), -1 if restart is None else int(restart), maxit,
+            hist.ctypes.data_as(_lib.p_f64) if log else None, iters.ctypes.data_as(_lib.p_i64), conv.ctypes.data_as(C.POINTER(C.c_int)), None)
+    h = Pr._h if Pr is not None else None
+    if tcode == 0 and A is not None:
+        fn = L.hs_gmres_block_z if cplx else L.hs_gmres_block_d
+        _lib.check(fn(h, n, colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz), *tail))
+    else:
+        fn = L.hs_gmres_block_t_z if cplx else L.hs_gmres_block_t_d
+        a3 = (None, None, None) if A is None else (colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz))
+        _lib.check(fn(h, tcode, n, *a3, *tail))
     res = X[:, 0] if vec else X
     if log:
         chs = [dict(resnorm=[float(v) for v in hist[: iters[c] + 1, c]], isconverged=bool(conv[c]), iters=int(iters[c])) for c in range(k)]

@@ -78,6 +78,14 @@ int hsk_spmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, const do
 int hsk_spmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,
                int64_t ldy, int64_t nrhs);
 
+/* The SpMM of hs_gmres_block_t_* over "entry ranges as rows" (hs_gmres_common.h) on host data: Y = op(A) X (B == NULL) or Y = B - op(A) X,
+ * op by trans (0: A, through its CSR; 1: transpose(A), 2: adjoint(A), both through the CSC arrays of A read as rows, the adjoint conjugating
+ * every value as it is loaded).  Arguments as hsk_spmm_*. */
+int hsk_spmm_op_d(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb,
+                  double* Y, int64_t ldy, int64_t nrhs);
+int hsk_spmm_op_z(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb,
+                  double* Y, int64_t ldy, int64_t nrhs);
+
 /* Host-only: the order in which the HSS form of a front's interior block lists its DOFs (hs_options.hss_d): recursive bisection of
  * the graph of A (1-based CSC pattern colptr / rowval of the n x n matrix) restricted to the ni DOFs `ids` (1-based), split where the
  * HSS cluster tree splits its index range.  perm_out[new position] = position in `ids` (0-based). */

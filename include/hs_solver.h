@@ -7,6 +7,7 @@
  *                                      (reference src/factorization.jl:5-11)
  *   ldiv!(C, F, B), ldiv!(F, B)        (reference src/factornode.jl:62-74)
  *   ldiv!(C, transpose(F), B), ldiv!(C, adjoint(F), B)   (hs_ldiv_t_*, hs_ldiv_dev_t_*)
+ *   gmres(transpose(A), b; Pr=transpose(F)), gmres(A', b; Pr=F')   (hs_gmres_t_*, hs_gmres_block_t_*)
  *   opnorm(A, p), opnormestinv(A), cond(A, p), refined solves (xGERFS)   (hs_opnorm, hs_normestinv, hs_condest, hs_ldiv_refine_*, hs_ldiv_refine_block_*)
  *   logabsdet(F), logdet(F), det(F), selected inverse (diag(A^-1), A^-1 on A's pattern)   (hs_logabsdet, hs_selinv)
  *   maxrank(F)                         (reference src/factornode.jl:49-57)
@@ -373,7 +374,41 @@ int hs_gmres_block_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int6
 int hs_gmres_block_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X, int64_t ldx,
                      int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged,
                      void* stream);
-/* the calling thread's last hs_gmres_block_* call: out8 = {seconds on the device, block preconditioner calls, column-applications summed over
+/* hs_gmres_* / hs_gmres_block_* on op(A) x = b, right-preconditioned by op(Pr): x = x0 + op(Pr)^-1 V y, with op the identity (trans = 0), the
+ * transpose (1) or the adjoint (2; = 1 for Float64) -- the solve of adjoint-state and sensitivity computations, with the SAME factorization
+ * (compressed or exact) as preconditioner.  The preconditioner goes through hs_ldiv_dev_t_* (single vector) / hs_ldiv_block_dev_t_* (block).
+ * Everything else is what hs_gmres_* / hs_gmres_block_* document: defaults, tol_c, breakdown, zero columns, the resnorm layout, use_x0, where,
+ * groups, HS_GMRES_BLOCK_GROUP, compaction, freezing; hs_gmres_block_info reports the block calls.
+ * colptr, rowval, nzval hold A itself, never op(A).  All three NULL: the handle's own A with the values of the last hs_numeric_begin; this
+ * needs Pr != NULL with a completed numeric factorization (else HS_ERR_ARGUMENT) and n == hs_size(Pr) (else HS_ERR_DIMENSION); no host pass
+ * over A and no upload happens: trans = 0 reads the CSR map of A that the handle keeps (built on the device at the first use by any call that
+ * needs rows of A, see hs_opnorm; its values are gathered from the CSC values per call), trans = 1, 2 read the handle's CSC arrays in place.
+ * Some but not all of the three NULL: HS_ERR_ARGUMENT.  trans = 0 with an explicit A goes through hs_gmres_* / hs_gmres_block_* and returns
+ * their bits.  For trans = 1, 2 the rows of op(A) are the CSC columns of A: the kernels walk colptr / rowval directly, the adjoint conjugates a
+ * value as it is loaded, no transposed or conjugated copy is stored, and with an explicit A the host only rebases the indices (0-based,
+ * 32-bit rows).
+ * Refused before any device work, x / X untouched: trans outside 0..2: HS_ERR_ARGUMENT; a single-vector call with trans != 0 on a handle
+ * hs_ldiv_t_* refuses (fronts that keep D as an HSS matrix; more than one rank): HS_ERR_UNSUPPORTED with its message; a block call on a handle
+ * hs_ldiv_block_t_* refuses, whatever trans: HS_ERR_UNSUPPORTED with its message; the handle's own A on a handle over more than one rank:
+ * HS_ERR_UNSUPPORTED.  Pr = NULL with an explicit A is not refused: the iteration runs unpreconditioned on op(A).
+ * Determinism as hs_gmres_block_*: no floating-point atomics, fixed summation orders (per row of op(A) the stored entries in order), two calls
+ * return the same bits, a column does not depend on its neighbours, their number or order, or on G.  An own-A call and an explicit-A call
+ * with the same matrix and trans return the same bits, where "the same matrix" means the arrays the handle was given (hs_analyze,
+ * hs_numeric_begin): the same entries in the same stored order, no (row, column) stored twice.  trans = 0: a row of the CSR map is in column
+ * order, the order of the host conversion, whether the map was built on the device or, for hs_options.mf, on the host with the pattern of the
+ * matrix-free fronts; among duplicates of one (row, column) the two orders may differ.  trans = 1, 2: a row of op(A) is a CSC column in its
+ * stored order, so an explicit A whose columns are ordered differently from the handle's copy sums in another order. */
+int hs_gmres_t_d(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
+                 double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream);
+int hs_gmres_t_z(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
+                 double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream);
+int hs_gmres_block_t_d(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
+                       int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
+                       int* converged, void* stream);
+int hs_gmres_block_t_z(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
+                       int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
+                       int* converged, void* stream);
+/* the calling thread's last hs_gmres_block_* / hs_gmres_block_t_* call: out8 = {seconds on the device, block preconditioner calls, column-applications summed over
  * those calls, SpMM launches, restart cycles (summed over the groups), column groups, workspace bytes, the largest active-column count} */
 int hs_gmres_block_info(double* out8);
 

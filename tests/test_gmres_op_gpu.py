@@ -1,0 +1,479 @@
+"""GMRES on transposed and adjoint systems, and on the handle's own A (hs_gmres_t_*, hs_gmres_block_t_*, csrc/hs_gmres.hip,
+hs_gmres_block.hip, hs_gmres_op.hip) on the MI355X: the single-vector calls against the NumPy GMRES of tests/gmres_block_mirror.py on op(A)
+with hs.ldiv(op(F), .) as preconditioner, every column of the block calls against the single-vector call, the lockstep schedule, bitwise
+determinism, own-A against explicit-A, the other paths of the ABI, the refusals on real handles, and the op(A) SpMM kernel alone on exact
+integer data.  Both problems are nonsymmetric: a dropped `trans` cannot pass."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+from gmres_block_mirror import gmres_single, rhs_mix
+from helpers import prepare, relerr
+
+pytestmark = pytest.mark.gpu
+
+PROBLEMS = [("convdiff", (30, 27), 40), ("convdiff_helmholtz", (30, 27), 40), ("convdiff", (20, 20, 20), 300), ("convdiff_helmholtz", (20, 20, 20), 300)]
+COMPRESSED = dict(swlevel=2, swsize=8, atol=1e-2, rtol=1e-2)
+LABELS = ["exact", "compressed", "none"]
+NRHS = 40  # one full chunk of the block solve plus a ragged one
+ZERO = 3   # the zero column of rhs_mix
+LETTER = {0: "N", 1: "T", 2: "C"}
+
+_CACHE = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _free_cached_factors():
+    yield
+    for P, Fs in _CACHE.values():
+        for F in Fs.values():
+            if F is not None:
+                F.free()
+    _CACHE.clear()
+
+
+def _problem(hs, i):
+    if i not in _CACHE:
+        kind, shape, nmax = PROBLEMS[i]
+        P = prepare(hs, shape, kind=kind, nmax=nmax, rhs="randn")
+        _CACHE[i] = (P, dict(exact=hs.factor(P["A"], P["nd"], P["nd_loc"], swlevel=0), compressed=hs.factor(P["A"], P["nd"], P["nd_loc"], **COMPRESSED), none=None))
+    return _CACHE[i]
+
+
+def _transes(A):
+    return (1, 2) if np.iscomplexobj(A.data) else (1,)
+
+
+def _op(A, trans):
+    return A if trans == 0 else (A.T if trans == 1 else A.conj().T)
+
+
+def _opF(hs, F, trans):
+    return F if trans == 0 else (hs.transpose(F) if trans == 1 else hs.adjoint(F))
+
+
+def _kw(F):
+    return dict(reltol=1e-9, restart=30, maxiter=30 if F is not None else 45)
+
+
+HIST_ATOL = 1e-12  # of ||r0||: the rule of tests/test_gmres_block_gpu.py
+# The one amendment, block against single-vector call with a preconditioner on convdiff_helmholtz (30, 27) (PROBLEMS[1]): 1e-11 ||r0||.  There
+# the two calls apply different solves (hs_ldiv_block_dev_t_* on the block, the single-vector sweeps of hs_ldiv_dev_t_* on the column), each
+# backward stable, and a history entry at the stopping level is the norm of what one solve leaves: kappa_1(A) = 4.4e6 puts that at up to
+# kappa 2^-53 = 4.9e-10 ||r0||, and the residual of one exact solve was measured on the MI355X at 2.7e-11 (single) and 3.4e-11 (block).  The
+# entries after the one step differ by 4.0e-12 ||r0|| between hs_gmres_block_t_* and hs_gmres_t_*, and by 7.2e-12 ||r0|| between
+# hs_gmres_block_* and hs_gmres_*: the entry points without _t, as they were before the _t calls existed, miss 1e-12 on this problem as well, so
+# 1e-12 cannot be asked of the _t calls here.  The bound is the next power of ten above what those unchanged entry points need; it is a
+# constant, a hundredth of a column's tolerance (1e-9 ||r0||), and holds for no other scenario of this file.
+HIST_ATOL_BLOCK_VS_SINGLE = {1: 1e-11}
+
+
+def _needed_atol(c1, c2):
+    """What rtol 1e-6 leaves uncovered between two histories, in units of ||r0|| (printed beside the assertions)."""
+    h1, h2 = np.array(c1["resnorm"]), np.array(c2["resnorm"])
+    m = min(len(h1), len(h2))
+    if m == 0 or h1[0] == 0:
+        return 0.0
+    return float(max(0.0, np.max(np.abs(h1[:m] - h2[:m]) - 1e-6 * np.abs(h2[:m]))) / h1[0])
+
+
+def _compare(ref, got, reltol, what, atol=HIST_ATOL):
+    """The rule of test_gmres_block_gpu.py: the same iteration count, histories to rtol 1e-6 (entries below atol ||r0|| are not compared digit
+    by digit), solutions to 1e-6; the one allowance is +-1 iteration where the reference's deciding residual lies within a relative 1e-6 of
+    its tolerance.  Returns 1 if the allowance was used."""
+    (x1, c1), (x2, c2) = ref, got
+    h1, h2 = np.array(c1["resnorm"]), np.array(c2["resnorm"])
+    near = 0
+    if c2["iters"] != c1["iters"]:
+        tol = max(reltol * h1[0], 0.0)
+        k = min(c1["iters"], c2["iters"])
+        assert abs(c2["iters"] - c1["iters"]) == 1 and 0 < k < len(h1) and abs(h1[k] - tol) <= 1e-6 * tol, (what, c1["iters"], c2["iters"])
+        near = 1
+        m = min(len(h1), len(h2))
+        h1, h2 = h1[:m], h2[:m]
+    else:
+        assert c2["isconverged"] == c1["isconverged"], what
+        assert relerr(x2, x1) < 1e-6, (what, relerr(x2, x1))
+    assert np.allclose(h1, h2, rtol=1e-6, atol=atol * h1[0]), (what, atol, h1, h2)
+    return near
+
+
+def _same(r1, r2):
+    (X1, c1), (X2, c2) = r1, r2
+    if isinstance(c1, dict):
+        c1, c2 = [c1], [c2]
+    return np.array_equal(X1, X2) and len(c1) == len(c2) and all(a["iters"] == b["iters"] and a["isconverged"] == b["isconverged"] and a["resnorm"] == b["resnorm"] for a, b in zip(c1, c2))
+
+
+@pytest.mark.parametrize("label", LABELS)
+@pytest.mark.parametrize("pi", range(len(PROBLEMS)))
+def test_single_vector_matches_the_reference_on_op_a(hs, pi, label):
+    P, Fs = _problem(hs, pi)
+    F = Fs[label]
+    A, b = P["A"], P["b"]
+    kw = _kw(F)
+    xN = hs.gmres(A, b, Pr=F, **kw)
+    sols = {}
+    near = 0
+    for trans in _transes(A):
+        Aop = _op(A, trans)
+        x, ch = hs.gmres(A, b, Pr=F, trans=LETTER[trans], log=True, **kw)
+        prec = None if F is None else (lambda v, G=_opF(hs, F, trans): hs.ldiv(G, v))
+        ref = gmres_single(Aop.tocsr(), b, prec=prec, **kw)
+        print(PROBLEMS[pi], label, LETTER[trans], "iterations: reference", ref[1]["iters"], "device", ch["iters"], "converged", ch["isconverged"])
+        near += _compare(ref, (x, ch), kw["reltol"], (PROBLEMS[pi], label, trans))
+        if ch["isconverged"]:
+            assert np.linalg.norm(Aop @ x - b) <= 1e-8 * np.linalg.norm(b)
+        if label == "exact":
+            assert ch["isconverged"] and ch["iters"] <= 2, ch
+            assert relerr(x, spla.splu(Aop.tocsc()).solve(b)) < 1e-8
+        # Pr = transpose(F) / adjoint(F) is the same call
+        if F is not None:
+            assert _same((x, ch), hs.gmres(A, b, Pr=_opF(hs, F, trans), log=True, **kw))
+        assert relerr(x, xN) > 1e-3, (label, trans, relerr(x, xN))
+        sols[trans] = x
+    assert near <= 1
+    if 2 in sols:
+        assert relerr(sols[2], sols[1]) > 1e-3
+
+
+@pytest.mark.parametrize("label", LABELS)
+@pytest.mark.parametrize("pi", range(len(PROBLEMS)))
+def test_every_column_matches_the_single_vector_call_and_the_schedule_is_lockstep(hs, pi, label):
+    P, Fs = _problem(hs, pi)
+    F = Fs[label]
+    A = P["A"]
+    n = A.shape[0]
+    B = rhs_mix(n, NRHS, np.iscomplexobj(A.data), seed=2)
+    kw = _kw(F)
+    atol = HIST_ATOL_BLOCK_VS_SINGLE.get(pi, HIST_ATOL) if F is not None else HIST_ATOL
+    for trans in _transes(A):
+        t = LETTER[trans]
+        X, chs = hs.gmres_block(A, B, Pr=F, trans=t, log=True, **kw)
+        info = hs.gmres_block_info()
+        chunks_last = hs.ldiv_block_info(F)["chunks"] if F is not None else None
+        assert X.shape == B.shape and len(chs) == NRHS
+        near = 0
+        its = []
+        need = 0.0
+        Aop = _op(A, trans)
+        for c in range(NRHS):
+            ref = hs.gmres(A, B[:, c], Pr=F, trans=t, log=True, **kw)
+            need = max(need, _needed_atol(ref[1], chs[c]))
+            near += _compare(ref, (X[:, c], chs[c]), kw["reltol"], (PROBLEMS[pi], label, trans, c), atol)
+            its.append(chs[c]["iters"])
+            if chs[c]["isconverged"]:
+                assert np.linalg.norm(Aop @ X[:, c] - B[:, c]) <= 1e-8 * np.linalg.norm(B[:, c]), (label, trans, c)
+        print(f"{PROBLEMS[pi]} {label} {t}: iterations {its}  columns within 1e-6 of their tolerance: {near}  history atol needed {need:.2e} allowed {atol:.0e}  info {info}")
+        assert near <= 1
+        assert its[ZERO] == 0 and chs[ZERO]["isconverged"] and not np.any(X[:, ZERO])
+        assert info["groups"] == 1 and info["max_active"] == NRHS - 1 and info["seconds"] > 0 and info["workspace_bytes"] > 0
+        assert info["cycles"] >= 1 and info["spmm_launches"] >= max(its) + info["cycles"]
+        if F is not None:
+            assert max(its) + 1 <= info["prec_calls"] <= max(its) + info["cycles"]
+            assert info["prec_calls"] < sum(its)
+            assert info["column_applications"] <= info["prec_calls"] * (NRHS - 1)
+            if label == "exact":
+                assert info["cycles"] == 1
+            if info["cycles"] == 1:
+                assert chunks_last == -(-(NRHS - 1) // 32)
+        else:
+            assert info["prec_calls"] == 0 and info["column_applications"] == 0
+
+
+def _raw(hs, F, trans, A, B, block, where=0, use_x0=0, X=None, ld=None, stream=None, restart=5, maxiter=30, reltol=1e-9):
+    """The _t entry points themselves (hs.gmres routes trans = 0 with an explicit A to the entry points without _t); B, X host arrays
+    (column-major n x k) or, with where = 1, device pointers.  Returns (status, X, iters, conv, hist)."""
+    from hierarchicalsolvers_jl_amd.gmres import _csc_fields
+
+    L = hs._lib.lib()
+    n = F.n if A is None else A.shape[0]
+    cplx = (F.dtype.kind == "c") if A is None else np.iscomplexobj(A.data)
+    dt = np.complex128 if cplx else np.float64
+    pi = hs._lib.p_i64
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    if A is None:
+        a3 = (None, None, None)
+    else:
+        colptr, rowval, nz = _csc_fields(A, dt)
+        a3 = (colptr.ctypes.data_as(pi), rowval.ctypes.data_as(pi), vp(nz))
+    k = 1 if not block else (B.shape[1] if where == 0 else X.shape[0])
+    if where == 0:
+        B = np.asfortranarray(np.asarray(B, dtype=dt).reshape(n, -1))
+        X = np.zeros_like(B, order="F") if X is None else X
+        pB, pX = vp(B), vp(X)
+        ld = n
+    else:
+        pB, pX = C.c_void_p(B.data_ptr()), C.c_void_p(X.data_ptr())
+    hist = np.zeros((maxiter + 1, max(k, 1)), order="F")
+    iters = np.zeros(max(k, 1), dtype=np.int64)
+    conv = np.zeros(max(k, 1), dtype=np.int32)
+    tail = (where, use_x0, reltol, 0.0, restart, maxiter, hist.ctypes.data_as(hs._lib.p_f64), iters.ctypes.data_as(pi), conv.ctypes.data_as(C.POINTER(C.c_int)),
+            None if stream is None else C.c_void_p(stream))
+    h = F._h if F is not None else None
+    if block:
+        fn = L.hs_gmres_block_t_z if cplx else L.hs_gmres_block_t_d
+        st = fn(h, trans, n, *a3, pB, ld, pX, ld, k, *tail)
+    else:
+        fn = L.hs_gmres_t_z if cplx else L.hs_gmres_t_d
+        st = fn(h, trans, n, *a3, pB, pX, *tail)
+    return st, X, iters, conv, hist
+
+
+def _as_result(X, iters, conv, hist, vec=False):
+    chs = [dict(resnorm=[float(v) for v in hist[: iters[c] + 1, c]], isconverged=bool(conv[c]), iters=int(iters[c])) for c in range(len(iters))]
+    return (X[:, 0], chs[0]) if vec else (X, chs)
+
+
+@pytest.mark.parametrize("pi", [2, 3])
+def test_determinism_and_column_independence_bitwise(hs, pi, monkeypatch):
+    P, Fs = _problem(hs, pi)
+    F = Fs["compressed"]
+    A = P["A"]
+    n = A.shape[0]
+    cplx = np.iscomplexobj(A.data)
+    t = "C" if cplx else "T"
+    kw = dict(Pr=F, trans=t, reltol=1e-9, restart=5, maxiter=30, log=True)
+    B = rhs_mix(n, NRHS, cplx, seed=2)
+    ref = hs.gmres_block(A, B, **kw)
+    assert _same(ref, hs.gmres_block(A, B, **kw))
+    perm = np.random.default_rng(3).permutation(NRHS)
+    Xp, cp = hs.gmres_block(A, B[:, perm], **kw)
+    assert _same((Xp, cp), (ref[0][:, perm], [ref[1][j] for j in perm]))
+    for j in (0, 5, 17, 32, 39):
+        x, ch = hs.gmres_block(A, B[:, j], **kw)
+        assert np.array_equal(x, ref[0][:, j]) and ch["resnorm"] == ref[1][j]["resnorm"] and ch["iters"] == ref[1][j]["iters"]
+    # groups of 32 columns against one group of 70
+    B70 = rhs_mix(n, 70, cplx, seed=4)
+    one = hs.gmres_block(A, B70, **kw)
+    assert hs.gmres_block_info()["groups"] == 1
+    monkeypatch.setenv("HS_GMRES_BLOCK_GROUP", "32")
+    grouped = hs.gmres_block(A, B70, **kw)
+    assert hs.gmres_block_info()["groups"] == 3 and hs.gmres_block_info()["max_active"] <= 32
+    monkeypatch.delenv("HS_GMRES_BLOCK_GROUP")
+    assert _same(one, grouped)
+    # the single-vector call twice
+    b = B[:, 2]
+    kws = dict(Pr=F, trans=t, reltol=1e-9, restart=5, maxiter=30, log=True)
+    assert _same(hs.gmres(A, b, **kws), hs.gmres(A, b, **kws))
+
+
+@pytest.mark.parametrize("label", ["compressed", "none"])
+@pytest.mark.parametrize("pi", [0, 1, 2, 3])
+def test_trans_0_returns_the_bits_of_the_entry_points_without_t_and_own_a_those_of_explicit_a(hs, pi, label):
+    P, Fs = _problem(hs, pi)
+    F = Fs[label]
+    A = P["A"]
+    n = A.shape[0]
+    cplx = np.iscomplexobj(A.data)
+    B = rhs_mix(n, 9, cplx, seed=5)
+    kw = dict(Pr=F, reltol=1e-9, restart=5, maxiter=12, log=True)
+    # trans = 0 with an explicit A through the _t entry points: hs.gmres / hs.gmres_block
+    st, X, iters, conv, hist = _raw(hs, F, 0, A, B, True, maxiter=12)
+    assert st == 0 and _same(_as_result(X, iters, conv, hist), hs.gmres_block(A, B, **kw))
+    st, X, iters, conv, hist = _raw(hs, F, 0, A, B[:, 2], False, maxiter=12)
+    assert st == 0 and _same(_as_result(X, iters, conv, hist, vec=True), hs.gmres(A, B[:, 2], **kw))
+    if F is None:
+        return
+    # the handle's own A against the explicit one, every trans, single and block
+    for trans in (0,) + _transes(A):
+        t = LETTER[trans]
+        assert _same(hs.gmres_block(None, B, trans=t, **kw), hs.gmres_block(A, B, trans=t, **kw)), (pi, trans)
+        assert _same(hs.gmres(None, B[:, 2], trans=t, **kw), hs.gmres(A, B[:, 2], trans=t, **kw)), (pi, trans)
+        # and a second own-A call, after the CSR map exists
+        assert _same(hs.gmres(None, B[:, 4], trans=t, **kw), hs.gmres(A, B[:, 4], trans=t, **kw)), (pi, trans)
+
+
+def test_own_a_on_a_matrix_free_handle_returns_the_bits_of_explicit_a(hs):
+    """A handle with hs_options.mf lends the CSR map the pattern of its matrix-free fronts (built on the host, not by the device sort): its
+    rows are in column order too, so trans = 0 on the handle's own A returns the bits of the explicit-A call, as trans = 1, 2 do."""
+    P = prepare(hs, (24, 24, 24), kind="convdiff_helmholtz", nmax=300, rhs="randn")
+    F = hs.factor(P["A"], P["nd"], P["nd_loc"], swlevel=2, swsize=8, atol=1e-6, rtol=1e-6, mf=True, leafsize=128)
+    flow = (hs._lib.i64 * 8)()
+    hs._lib.check(hs._lib.lib().hs_flow_info(F._h, flow))
+    assert flow[1] > 0  # matrix-free fronts: the handle holds their CSR pattern
+    A = P["A"]
+    B = rhs_mix(A.shape[0], 9, True, seed=5)
+    kw = dict(Pr=F, reltol=1e-9, restart=5, maxiter=12, log=True)
+    for t in ("N", "T", "C"):
+        assert _same(hs.gmres_block(None, B, trans=t, **kw), hs.gmres_block(A, B, trans=t, **kw)), t
+        assert _same(hs.gmres(None, B[:, 2], trans=t, **kw), hs.gmres(A, B[:, 2], trans=t, **kw)), t
+    F.free()
+
+
+@pytest.mark.parametrize("pi", [0, 1])
+def test_other_paths_of_the_abi(hs, pi):
+    import torch
+
+    P, Fs = _problem(hs, pi)
+    Fc = Fs["compressed"]
+    A = P["A"]
+    n = A.shape[0]
+    cplx = np.iscomplexobj(A.data)
+    dt = np.complex128 if cplx else np.float64
+    trans = 2 if cplx else 1
+    t = LETTER[trans]
+    Aop = _op(A, trans)
+    k = 7
+    B = rhs_mix(n, k, cplx, seed=6)
+    kw = dict(Pr=Fc, trans=t, reltol=1e-9, restart=30, maxiter=30, log=True)
+    # initial guesses: the residual of the guess is the reference of reltol
+    X0 = np.asfortranarray(np.random.default_rng(7).standard_normal((n, k)).astype(dt))
+    Xg, cg = hs.gmres_block(A, B, X0=X0, **kw)
+    for c in (0, ZERO, 5):
+        x1, c1 = hs.gmres(A, B[:, c], x0=X0[:, c], **kw)
+        ref = gmres_single(Aop.tocsr(), B[:, c], prec=lambda v: hs.ldiv(_opF(hs, Fc, trans), v), x0=X0[:, c], reltol=1e-9, restart=30, maxiter=30)
+        assert c1["iters"] == ref[1]["iters"] and cg[c]["iters"] == c1["iters"] and cg[c]["isconverged"] == c1["isconverged"]
+        assert np.allclose(c1["resnorm"], ref[1]["resnorm"], rtol=1e-6, atol=1e-12 * c1["resnorm"][0])
+        if c == ZERO:  # b = 0: what is left of the guess has no digits in common; the residual is what counts
+            assert c1["isconverged"] and np.linalg.norm(Aop @ Xg[:, c]) <= 1e-8 * np.linalg.norm(Aop @ X0[:, c])
+        else:
+            assert relerr(Xg[:, c], x1) < 1e-6 and relerr(x1, ref[0]) < 1e-6
+        assert np.allclose(cg[c]["resnorm"], c1["resnorm"], rtol=1e-6, atol=1e-12 * c1["resnorm"][0])
+    # device pointers on a torch stream, leading dimensions above n: bitwise the host form, the padding untouched; explicit A and own A
+    ref, cref = hs.gmres_block(A, B, **kw)
+    dev = torch.device("cuda:0")
+    s = torch.cuda.Stream(device=dev)
+    ld = n + 3
+    Bp = np.zeros((k, ld), dtype=dt)
+    Bp[:, :n] = B.T
+    dB = torch.from_numpy(Bp).to(dev)  # row r of dB = column r of B (column-major, ld n + 3)
+    for Aarg in (A, None):
+        dX = torch.full((k, ld), 7.0, dtype=dB.dtype, device=dev)
+        with torch.cuda.stream(s):
+            st, _, iters, conv, hist = _raw(hs, Fc, trans, Aarg, dB, True, where=1, X=dX, ld=ld, stream=s.cuda_stream, restart=30)
+        hs._lib.check(st)
+        s.synchronize()
+        Xd = dX.cpu().numpy()
+        assert np.array_equal(Xd[:, :n].T, ref) and np.all(Xd[:, n:] == 7.0)
+        assert _same(_as_result(ref, iters, conv, hist), (ref, cref))
+        # the single-vector call on device pointers
+        dx = torch.full((n,), 7.0, dtype=dB.dtype, device=dev)
+        with torch.cuda.stream(s):
+            st, _, iters, conv, hist = _raw(hs, Fc, trans, Aarg, dB[5], False, where=1, X=dx, stream=s.cuda_stream, restart=30)
+        hs._lib.check(st)
+        s.synchronize()
+        x5, c5 = hs.gmres(A, B[:, 5], **kw)
+        assert np.array_equal(dx.cpu().numpy(), x5) and int(iters[0]) == c5["iters"] and [float(v) for v in hist[: iters[0] + 1, 0]] == c5["resnorm"]
+    # nrhs = 0, a vector, an all-zero block
+    assert hs.gmres_block(A, np.zeros((n, 0), dtype=dt), **kw)[0].shape == (n, 0)
+    assert hs.gmres_block(None, np.zeros((n, 0), dtype=dt), **kw)[0].shape == (n, 0)
+    x, ch = hs.gmres_block(A, B[:, 1], **kw)
+    assert x.shape == (n,) and isinstance(ch, dict) and np.array_equal(x, ref[:, 1])
+    Xz, cz = hs.gmres_block(None, np.zeros((n, 3), dtype=dt), **kw)
+    assert not np.any(Xz) and all(c["iters"] == 0 and c["isconverged"] and c["resnorm"] == [0.0] for c in cz)
+    assert hs.gmres_block_info()["prec_calls"] == 0 and hs.gmres_block_info()["cycles"] == 0
+    # interleaving with the other solves of the handle leaves their results unchanged
+    b2 = rhs_mix(n, 2, cplx, seed=8)[:, ::-1].copy() + 1.0
+    before = hs.ldiv(Fc, b2), hs.ldiv_block(Fc, B), hs.gmres(A, b2[:, 0], Pr=Fc, reltol=1e-9, restart=30, maxiter=30, log=True), hs.opnorm(Fc, np.inf)
+    again = hs.gmres_block(None, B, **kw)
+    hs.gmres(None, b2[:, 0], Pr=Fc, trans="N", reltol=1e-9, restart=30, maxiter=30)
+    after = hs.ldiv(Fc, b2), hs.ldiv_block(Fc, B), hs.gmres(A, b2[:, 0], Pr=Fc, reltol=1e-9, restart=30, maxiter=30, log=True), hs.opnorm(Fc, np.inf)
+    assert np.array_equal(again[0], ref) and np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])
+    assert _same(before[2], after[2]) and before[3] == after[3]
+
+
+def test_refusals_on_real_handles(hs):
+    E = hs._lib
+    L = E.lib()
+    for shape, opts in (((32, 32, 32), dict(swlevel=2, swsize=8, atol=1e-6, rtol=1e-6, hss_min=1024)), ((24, 24, 24), dict(swlevel=2, swsize=8, atol=1e-6, rtol=1e-6, mf=2, leafsize=128))):
+        P = prepare(hs, shape, kind="convdiff", nmax=512, rhs="randn")
+        F = hs.factor(P["A"], P["nd"], P["nd_loc"], **opts)
+        A = P["A"]
+        n = A.shape[0]
+        B = np.asfortranarray(rhs_mix(n, 3, False, seed=9))
+        for Aarg in (A, None):
+            # the single-vector call: what hs_ldiv_t_* refuses
+            X = np.full((n, 1), 42.0, order="F")
+            st = _raw(hs, F, 1, Aarg, B[:, 0], False, X=X)[0]
+            msg = L.hs_last_error().decode()
+            assert st == E.HS_ERR_UNSUPPORTED and np.all(X == 42.0) and "ULV" in msg and "hs_ldiv_dev_t_*" in msg, (opts, st, msg)
+            # the block call: what hs_ldiv_block_t_* refuses, whatever trans
+            for trans in (0, 1, 2):
+                X = np.full((n, 3), 42.0, order="F")
+                st = _raw(hs, F, trans, Aarg, B, True, X=X)[0]
+                msg = L.hs_last_error().decode()
+                assert st == E.HS_ERR_UNSUPPORTED and np.all(X == 42.0) and "HSS" in msg, (opts, trans, st, msg)
+                if trans != 0 or Aarg is None:
+                    assert "hs_gmres_block_t_*" in msg and "hs_ldiv_block" in msg, msg
+        with pytest.raises(hs.UnsupportedError, match="ULV"):
+            hs.gmres(A, B[:, 0], Pr=hs.transpose(F), reltol=1e-9, restart=30, maxiter=30)
+        # trans = 0 on the single-vector path serves such a handle, with its own A too
+        x, ch = hs.gmres(None, B[:, 0], Pr=F, reltol=1e-9, restart=30, maxiter=30, log=True)
+        x1, ch1 = hs.gmres(A, B[:, 0], Pr=F, reltol=1e-9, restart=30, maxiter=30, log=True)
+        assert ch["isconverged"] and ch["iters"] == ch1["iters"] and relerr(x, x1) < 1e-6
+        F.free()
+    # a handle of another element type or size; a restart above the limit; trans outside 0..2
+    Pc = prepare(hs, (15, 15), kind="convdiff_helmholtz", nmax=20, rhs="randn")
+    Pr = prepare(hs, (15, 15), kind="convdiff", nmax=20, rhs="randn")
+    Fr = hs.factor(Pr["A"], Pr["nd"], Pr["nd_loc"], swlevel=0)
+    Fz = hs.factor(Pc["A"], Pc["nd"], Pc["nd_loc"], swlevel=0)
+    Bz = rhs_mix(Pc["A"].shape[0], 3, True, seed=9)
+    for fn in (hs.gmres_block, lambda A, B, **kw: hs.gmres(A, B[:, 0], **kw)):
+        with pytest.raises(hs.DimensionMismatch):
+            fn(Pc["A"], Bz, Pr=Fr, trans="T", reltol=1e-9, restart=30, maxiter=10)
+        with pytest.raises(ValueError):
+            fn(Pc["A"], Bz, Pr=Fz, trans="C", restart=1000, maxiter=10)
+        with pytest.raises(ValueError):
+            fn(None, Bz, Pr=Fz, trans="C", restart=1000, maxiter=10)
+    with pytest.raises(hs.DimensionMismatch):
+        hs.gmres_block(None, Bz[:-1], Pr=Fz, trans="T", maxiter=10)
+    assert _raw(hs, Fz, 3, Pc["A"], Bz, True)[0] == E.HS_ERR_ARGUMENT and _raw(hs, Fz, -1, None, Bz[:, 0], False)[0] == E.HS_ERR_ARGUMENT
+    # Pr = NULL with an explicit A is not refused: unpreconditioned on op(A)
+    x, ch = hs.gmres(Pr["A"], Pr["b"], trans="T", reltol=1e-10, restart=60, maxiter=225, log=True)
+    assert ch["isconverged"] and relerr(x, spla.splu(Pr["A"].T.tocsc()).solve(Pr["b"])) < 1e-7
+    assert relerr(x, spla.splu(Pr["A"].tocsc()).solve(Pr["b"])) > 1e-3
+    Fr.free()
+    Fz.free()
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_spmm_op_kernel_exact_on_integers(hs, cplx):
+    """The kernel alone (hsk_spmm_op_*) on small integers, where every product and sum is exact in Float64: equality with SciPy for op(A) X and
+    B - op(A) X, every trans, ragged n (against the 256-row tile), 1, 8, 9 and 40 columns (against the 8- / 4-column register chunk), an
+    empty row and a row longer than 64 entries (of A and of its transpose), leading dimensions above n."""
+    L = hs._lib.lib()
+    fn = L.hsk_spmm_op_z if cplx else L.hsk_spmm_op_d
+    dt = np.complex128 if cplx else np.float64
+    rng = np.random.default_rng(11)
+    pi = hs._lib.p_i64
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+
+    def ints(shape):
+        v = rng.integers(-7, 8, size=shape).astype(np.float64)
+        return (v + 1j * rng.integers(-7, 8, size=shape)).astype(dt) if cplx else v
+
+    for n in (1, 255, 257, 1000):
+        pat = sp.lil_matrix(sp.random(n, n, density=min(1.0, 9.0 / n), random_state=5, format="csc") + sp.eye(n, format="csc"))
+        if n > 100:
+            pat[7, :] = 0      # an empty row of A ...
+            pat[:, 11] = 0     # ... and an empty column (an empty row of its transpose)
+            pat[20, 30:110] = 1  # a row of A with 80 entries
+            pat[40:120, 50] = 1  # a column of A with 80 entries
+            pat[7, :] = 0
+            pat[:, 11] = 0
+        pat = sp.csc_matrix(pat)
+        pat.eliminate_zeros()
+        pat.sort_indices()
+        A = sp.csc_matrix((ints(pat.nnz), pat.indices, pat.indptr), shape=(n, n))
+        if n > 100:
+            assert A.getnnz(axis=1)[7] == 0 and A.getnnz(axis=0)[11] == 0 and A.getnnz(axis=1)[20] > 64 and A.getnnz(axis=0)[50] > 64
+        colptr, rowval, nz = A.indptr.astype(np.int64) + 1, A.indices.astype(np.int64) + 1, np.ascontiguousarray(A.data, dtype=dt)
+        for nrhs in (1, 8, 9, 40):
+            X = np.asfortranarray(ints((n + 2, nrhs)))
+            X[:n] += (np.arange(n)[:, None] - 2 * np.arange(nrhs)[None, :]) % 5  # columns differ: a swapped column map cannot pass
+            Bm = np.asfortranarray(ints((n + 1, nrhs)))
+            for trans in (0, 1, 2):
+                Aop = _op(A, trans)
+                for minus in (0, 1):
+                    Y0 = np.asfortranarray(ints((n + 3, nrhs)))
+                    Y = Y0.copy(order="F")
+                    hs._lib.check(fn(trans, n, colptr.ctypes.data_as(pi), rowval.ctypes.data_as(pi), vp(nz), vp(X), n + 2, vp(Bm) if minus else None, n + 1, vp(Y), n + 3, nrhs))
+                    want = (Bm[:n] - Aop @ X[:n]) if minus else Aop @ X[:n]
+                    assert np.array_equal(Y[:n], want), (n, nrhs, trans, minus)
+                    assert np.array_equal(Y[n:], Y0[n:])
+    if cplx:  # the adjoint differs from the transpose on this data
+        assert not np.array_equal(A.conj().T @ X[:n], A.T @ X[:n])
