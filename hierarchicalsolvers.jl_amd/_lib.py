@@ -74,6 +74,7 @@ EXPORTS = [
     "hs_ldiv_t_d", "hs_ldiv_t_z", "hs_ldiv_dev_t_d", "hs_ldiv_dev_t_z",
     "hs_ldiv_block_d", "hs_ldiv_block_z", "hs_ldiv_block_dev_d", "hs_ldiv_block_dev_z", "hs_ldiv_block_info", "hsk_multi_prob_d", "hsk_multi_prob_z",
     "hs_ldiv_block_t_d", "hs_ldiv_block_t_z", "hs_ldiv_block_dev_t_d", "hs_ldiv_block_dev_t_z", "hsk_multi_prob_t_d", "hsk_multi_prob_t_z",
+    "hs_ldiv_sparse_d", "hs_ldiv_sparse_z", "hs_ldiv_sparse_dev_d", "hs_ldiv_sparse_dev_z", "hs_ldiv_sparse_plan", "hs_ldiv_sparse_info",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
     "hs_logabsdet", "hs_selinv", "hs_selinv_info",
@@ -157,6 +158,16 @@ def lib():
         f.restype = C.c_int
     L.hs_ldiv_block_info.argtypes = [vp, p_f64]
     L.hs_ldiv_block_info.restype = C.c_int
+    for f in (L.hs_ldiv_sparse_d, L.hs_ldiv_sparse_z):
+        f.argtypes = [vp, C.c_int, i64, i64, p_i64, p_i64, p_f64, p_i64, i64, p_f64, i64]
+        f.restype = C.c_int
+    for f in (L.hs_ldiv_sparse_dev_d, L.hs_ldiv_sparse_dev_z):
+        f.argtypes = [vp, C.c_int, i64, i64, p_i64, p_i64, vp, p_i64, i64, vp, i64, vp]
+        f.restype = C.c_int
+    L.hs_ldiv_sparse_plan.argtypes = [vp, C.c_int, i64, i64, p_i64, p_i64, p_i64, i64, p_i64, p_i64, C.POINTER(C.c_uint8)]
+    L.hs_ldiv_sparse_plan.restype = C.c_int
+    L.hs_ldiv_sparse_info.argtypes = [vp, p_f64]
+    L.hs_ldiv_sparse_info.restype = C.c_int
     for f in (L.hsk_multi_prob_d, L.hsk_multi_prob_z):
         f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int]
         f.restype = C.c_int

@@ -291,6 +291,8 @@ struct hs_handle {
   void (*sx_free)(void*) = nullptr;
   void* mx = nullptr;  // hs_solve_multi.hip: the work blocks of the block solves, the figures of the last hs_ldiv_block_* call
   void (*mx_free)(void*) = nullptr;
+  std::vector<int> sp_owner;  // hs_ldiv_sparse_*: per row the internal node whose int holds it (built by the first call that needs it)
+  double sp_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the figures of the last hs_ldiv_sparse_* call
 };
 
 static inline int rup(int x, int a) { return (x + a - 1) / a * a; }
@@ -1771,7 +1773,8 @@ void hs_multi_view(hs_handle* h, HsMultiView* v) {
     for (int id : L.mine) {
       const NodeH& x = h->nodes[id];
       const bool lowrank = x.compressed || x.mf;
-      M.fronts.push_back({x.ni, x.nb, lowrank ? 0 : 1});
+      M.fronts.push_back({x.ni, x.nb, lowrank ? 0 : 1, x.woff});
+      M.node.push_back(id);
       M.maxnb = std::max(M.maxnb, x.nb);
       if (x.ni > 0) {
         lo = lo < 0 ? x.woff : std::min(lo, x.woff);
@@ -2289,6 +2292,155 @@ static inline int hs_internal_id(const hs_handle* F, int64_t node) {
   return node < F->nuser ? F->last_of_user[node] : (int)(F->nreal + (node - F->nuser));
 }
 static inline int64_t hs_num_user_nodes(const hs_handle* F) { return F->last_of_user.empty() ? F->nnodes : F->nuser + (F->nnodes - F->nreal); }
+
+// ------------------------------------------------------------------------------------------------
+// hs_ldiv_sparse_*: sparse right-hand sides and selected rows of the solution on pruned tree paths (hs_solve_sparse.hip)
+// ------------------------------------------------------------------------------------------------
+// the internal front graph as hs_solve_sparse.hip sees it (hs_solve_multi.h); host data only, so a plan-only handle serves too
+void hs_sparse_tree(const hs_handle* hc, HsSparseTree* t) {
+  hs_handle* h = const_cast<hs_handle*>(hc);
+  const int nn = (int)h->nodes.size();
+  if (h->sp_owner.empty()) {
+    h->sp_owner.assign((size_t)h->n, -1);
+    for (int i = 0; i < nn; ++i) {
+      const NodeH& x = h->nodes[i];
+      for (int e = 0; e < x.ni; ++e) h->sp_owner[h->fidx_host[x.off_fidx + e]] = i;
+    }
+  }
+  *t = HsSparseTree();
+  t->n = h->n;
+  t->nuser = (int)hs_num_user_nodes(h);
+  t->owner = h->sp_owner.data();
+  for (int i = 0; i < nn; ++i) {
+    const NodeH& x = h->nodes[i];
+    t->parent.push_back(x.parent);
+    t->user.push_back(i < h->nreal ? x.user : (int)hs_num_user_nodes(h) - (nn - i));
+    t->ni.push_back(x.ni);
+    t->nb.push_back(x.nb);
+  }
+}
+// what hs_ldiv_block_t_* refuses, before any device work and before X is written
+static void check_sparse_handle(const hs_handle* h, int trans, const char* fn) {
+  check_handle(h);
+  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
+  if (h->nranks > 1)
+    HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: block solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", fn, h->nranks);
+  for (size_t i = 0; i < h->nodes.size(); ++i) {
+    const NodeH& x = h->nodes[i];
+    if (x.mine && (x.hssd || (x.mf && !x.mfd)))
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): block solves are not implemented", fn,
+              (int)i);
+  }
+}
+// the CSC block and the row list; false: there is nothing to do (nrhs == 0, or an empty row list)
+static bool check_sparse_args(const hs_handle* h, const char* fn, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const int64_t* rows, int64_t nrows) {
+  if (n != h->n) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: B has %lld rows, F is %lld x %lld", fn, (long long)n, (long long)h->n, (long long)h->n);
+  if (nrhs < 0 || (rows && nrows < 0)) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: nrhs = %lld, nrows = %lld", fn, (long long)nrhs, (long long)nrows);
+  if (nrhs == 0) return false;
+  if (!bcolptr) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: bcolptr == NULL", fn);
+  if (bcolptr[0] != 1) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: bcolptr must be 1-based (SparseMatrixCSC)", fn);
+  for (int64_t j = 0; j < nrhs; ++j)
+    if (bcolptr[j + 1] < bcolptr[j] || bcolptr[j + 1] - bcolptr[j] > n) HS_FAIL(HS_ERR_ARGUMENT, j, "ArgumentError: %s: bcolptr is inconsistent at column %lld", fn, (long long)j + 1);
+  if (bcolptr[nrhs] > 1 && !browval) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: browval == NULL", fn);
+  for (int64_t j = 0; j < nrhs; ++j)
+    for (int64_t e = bcolptr[j] - 1; e < bcolptr[j + 1] - 1; ++e) {
+      const int64_t r = browval[e];
+      if (r < 1 || r > n) HS_FAIL(HS_ERR_DIMENSION, e, "BoundsError: %s: browval[%lld] = %lld outside 1:%lld", fn, (long long)e + 1, (long long)r, (long long)n);
+      if (e > bcolptr[j] - 1 && r <= browval[e - 1])
+        HS_FAIL(HS_ERR_ARGUMENT, e, "ArgumentError: %s: the rows of column %lld of B are not strictly increasing", fn, (long long)j + 1);
+    }
+  if (rows)
+    for (int64_t r = 0; r < nrows; ++r)
+      if (rows[r] < 1 || rows[r] > n) HS_FAIL(HS_ERR_DIMENSION, r, "BoundsError: %s: rows[%lld] = %lld outside 1:%lld", fn, (long long)r + 1, (long long)rows[r], (long long)n);
+  return !(rows && nrows == 0);
+}
+template <class T>
+static void ldiv_sparse(hs_handle* h, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const T* bnzval, const int64_t* rows, int64_t nrows,
+                        T* X, int64_t ldx, bool on_device, void* stream) {
+  const char* fn = on_device ? "hs_ldiv_sparse_dev_*" : "hs_ldiv_sparse_*";
+  check_sparse_handle(h, trans, fn);
+  check_solve_args(h, sizeof(T) == 16, n, n, n, nrhs < 0 ? 0 : nrhs);
+  if (!check_sparse_args(h, fn, n, nrhs, bcolptr, browval, rows, nrows)) return;
+  const int64_t nout = rows ? nrows : n, nnzb = bcolptr[nrhs] - 1;
+  if (ldx < nout) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldx = %lld, X has %lld rows", fn, (long long)ldx, (long long)nout);
+  if (!X || (nnzb > 0 && !bnzval)) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
+  if (!h->d_solve) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: handle holds a host-side plan only (hs_plan); use hs_analyze");
+  HsMultiView v;
+  hs_multi_view(h, &v);
+  HsSparseTree t;
+  hs_sparse_tree(h, &t);
+  double out8[8];
+  if (on_device) {
+    hs_solve_sparse_run<T>(v, t, trans, nrhs, bcolptr, browval, bnzval, rows, nrows, X, ldx, (hipStream_t)stream, out8);
+  } else {
+    hipStream_t s = h->stream;
+    const size_t vbytes = (size_t)std::max<int64_t>(nnzb, 1) * sizeof(T), xbytes = (size_t)nout * nrhs * sizeof(T);
+    T* dv = (T*)hs_scratch_take(vbytes, "sparse solve values");
+    T* dx = nullptr;
+    try {  // nnz values go up, nrows x nrhs come down
+      dx = (T*)hs_scratch_take(xbytes, "sparse solve result");
+      if (nnzb > 0) HS_HIP(hipMemcpy(dv, bnzval, (size_t)nnzb * sizeof(T), hipMemcpyHostToDevice));
+      hs_solve_sparse_run<T>(v, t, trans, nrhs, bcolptr, browval, dv, rows, nrows, dx, nout, s, out8);
+      HS_HIP(hipMemcpy2D(X, ldx * sizeof(T), dx, nout * sizeof(T), nout * sizeof(T), nrhs, hipMemcpyDeviceToHost));
+    } catch (...) {
+      (void)hipStreamSynchronize(s);
+      if (dx) hs_scratch_give(dx, xbytes);
+      hs_scratch_give(dv, vbytes);
+      throw;
+    }
+    hs_scratch_give(dx, xbytes);
+    hs_scratch_give(dv, vbytes);
+    out8[6] = (double)nnzb + (double)nout * nrhs;
+    out8[7] += (double)(vbytes + xbytes);
+  }
+  double b6[6];
+  hs_solve_multi_info(h->mx, b6);
+  out8[0] = b6[0];
+  out8[7] += b6[5];
+  memcpy(h->sp_info, out8, sizeof out8);
+  if (!on_device) h->stats.t_solve = b6[0];
+}
+static void ldiv_sparse_plan(const hs_handle* h, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const int64_t* rows, int64_t nrows,
+                             int64_t* order, int64_t* nchunks, uint8_t* active) {
+  check_sparse_handle(h, trans, "hs_ldiv_sparse_plan");
+  if (nchunks) *nchunks = 0;
+  if (!check_sparse_args(h, "hs_ldiv_sparse_plan", n, nrhs, bcolptr, browval, rows, nrows) && nrhs == 0) return;
+  HsSparseTree t;
+  hs_sparse_tree(h, &t);
+  HsSparsePlan p;
+  hs_sparse_plan(t, nrhs, bcolptr, browval, 1, rows, rows ? nrows : 0, &p);
+  if (order) std::copy(p.order.begin(), p.order.end(), order);
+  if (nchunks) *nchunks = p.nchunks;
+  if (active) {
+    const int nn = (int)t.parent.size();
+    memset(active, 0, (size_t)p.nchunks * t.nuser);
+    for (int c = 0; c < p.nchunks; ++c)
+      for (int i = 0; i < nn; ++i) active[(size_t)c * t.nuser + t.user[i]] |= p.act[(size_t)c * nn + i];
+  }
+}
+extern "C" int hs_ldiv_sparse_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const double* bnzval, const int64_t* rows,
+                                int64_t nrows, double* X, int64_t ldx) {
+  HS_GUARD(ldiv_sparse<double>(F, trans, n, nrhs, bcolptr, browval, bnzval, rows, nrows, X, ldx, false, nullptr));
+}
+extern "C" int hs_ldiv_sparse_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const double* bnzval, const int64_t* rows,
+                                int64_t nrows, double* X, int64_t ldx) {
+  HS_GUARD(ldiv_sparse<cplx>(F, trans, n, nrhs, bcolptr, browval, (const cplx*)bnzval, rows, nrows, (cplx*)X, ldx, false, nullptr));
+}
+extern "C" int hs_ldiv_sparse_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const double* d_bnzval,
+                                    const int64_t* rows, int64_t nrows, double* dX, int64_t ldx, void* stream) {
+  HS_GUARD(ldiv_sparse<double>(F, trans, n, nrhs, bcolptr, browval, d_bnzval, rows, nrows, dX, ldx, true, stream));
+}
+extern "C" int hs_ldiv_sparse_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const double* d_bnzval,
+                                    const int64_t* rows, int64_t nrows, double* dX, int64_t ldx, void* stream) {
+  HS_GUARD(ldiv_sparse<cplx>(F, trans, n, nrhs, bcolptr, browval, (const cplx*)d_bnzval, rows, nrows, (cplx*)dX, ldx, true, stream));
+}
+extern "C" int hs_ldiv_sparse_plan(const hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const int64_t* rows, int64_t nrows,
+                                   int64_t* order, int64_t* nchunks, uint8_t* active) {
+  HS_GUARD(ldiv_sparse_plan(F, trans, n, nrhs, bcolptr, browval, rows, nrows, order, nchunks, active));
+}
+extern "C" int hs_ldiv_sparse_info(const hs_handle* F, double* out8) {
+  HS_GUARD(if (!F || !out8) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_sparse_info: null argument"); memcpy(out8, F->sp_info, sizeof F->sp_info));
+}
 
 extern "C" int hs_node_ranks(const hs_handle* F, int64_t node, int64_t* rank_L, int64_t* rank_R) {
   if (!F || node < 0 || node >= hs_num_user_nodes(F)) {

@@ -18,6 +18,7 @@ struct HsMultiLR {            // a front whose Gauss transforms are low-rank (co
 };
 struct HsMultiFront {  // host copy of what the flop count and the boundary work block need
   int ni = 0, nb = 0, dense_bnd = 0;
+  long long woff = 0;  // its ni-segment in the work blocks
 };
 struct HsMultiLevel {
   const void* sn = nullptr;  // SolveNode<T>[] of the level's fronts (device)
@@ -25,6 +26,7 @@ struct HsMultiLevel {
   long long wbase = 0, wrows = 0;  // the level's range of ni-segments: [wbase, wbase + wrows)
   std::vector<HsMultiFront> fronts;
   std::vector<HsMultiLR> lr;
+  std::vector<int> node;  // the handle's internal node id of every front, in the order of sn / fronts
 };
 struct HsMultiView {
   int64_t n = 0;
@@ -36,15 +38,85 @@ struct HsMultiView {
 };
 void hs_multi_view(hs_handle* h, HsMultiView* v);
 
-// C[:, 0:nrhs] = F^-1 C[:, 0:nrhs] in place on the device (ld ldc), chunk by chunk, on stream s; events around the launches
+// Optional active set of the two drivers below (hs_solve_sparse.hip builds it): which fronts each sweep of each chunk visits.  A level's
+// grouped launches then run over a compacted SolveNode / MultiAux array of its active fronts (their woff / boff segments stay where they
+// are), maxni / maxnb are taken over the subset, and a level without an active front launches nothing.
+struct MultiAux;
+struct HsMultiSubset {          // the fronts of one level that one sweep of one chunk visits
+  const void* sn = nullptr;     // compacted SolveNode<T>[] (device)
+  const MultiAux* aux = nullptr;  // compacted alike (device)
+  int maxni = 0, maxnb = 0;
+  std::vector<int> pos;         // their indices in the level's arrays, increasing
+};
+struct HsZeroSeg {  // rows [woff, woff + ni) of work block 2
+  long long woff;
+  int ni, pad;
+};
+struct HsMultiActive {
+  int nlevels = 0;
+  std::vector<HsMultiSubset> sub;    // [(chunk * nlevels + level) * 2 + sweep], sweep 0: forward, 1: backward
+  // fronts the backward sweep of a chunk visits and its forward sweep did not: their y is zero, and work block 2 is cleared there before the
+  // backward sweep reads it (it holds the x of an earlier chunk or call)
+  const HsZeroSeg* zseg = nullptr;   // device
+  std::vector<size_t> zoff;          // chunk c owns zseg[zoff[c] .. zoff[c + 1])
+  std::vector<int> zmaxni;           // per chunk: the longest of them
+  // every chunk lives in the same n x KC block dC: begin(c, kc, s) fills it before the sweeps of chunk c, end(c, kc, s) reads it after them
+  void* ctx = nullptr;
+  void (*begin)(void* ctx, int chunk, int kc, hipStream_t s) = nullptr;
+  void (*end)(void* ctx, int chunk, int kc, hipStream_t s) = nullptr;
+  const HsMultiSubset& at(int chunk, int level, int sweep) const { return sub[((size_t)chunk * nlevels + level) * 2 + sweep]; }
+};
+
+// C[:, 0:nrhs] = F^-1 C[:, 0:nrhs] in place on the device (ld ldc), chunk by chunk, on stream s; events around the launches.  act == nullptr:
+// every front in both sweeps
 template <class T>
-void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s);
+void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act = nullptr);
 // the same for transpose(F) (trans = 1) and adjoint(F) (trans = 2): C[:, 0:nrhs] = F^-T C / F^-H C (kernels_solve_multi_t.hip)
 template <class T>
-void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s);
+void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act = nullptr);
 double hs_solve_multi_seconds(void* mx);  // waits for the last block solve and returns its device seconds
 void hs_solve_multi_info(void* mx, double* out6);
 int hs_ldiv_block_cols();  // KC: columns per chunk (HS_LDIV_BLOCK_COLS = 16 / 32 / 48 / 64, default 32)
+
+// ---- hs_solve_sparse.hip: sparse right-hand sides, selected rows of the solution (hs_ldiv_sparse_*) --------------------------------------
+struct HsSparseTree {         // the handle's internal front graph (host); hs_api.hip fills it, also for a plan-only handle
+  int64_t n = 0;
+  int nuser = 0;              // nodes the C ABI numbers (the user's tree, then the pseudo-root if there is one)
+  std::vector<int> parent;    // per internal node (slices of a split front are a chain), -1: none
+  std::vector<int> user;      // per internal node: the C ABI's node id
+  std::vector<int> ni, nb;    // per internal node
+  const int* owner = nullptr; // per row (0-based): the internal node whose int holds it, -1: none
+};
+void hs_sparse_tree(const hs_handle* h, HsSparseTree* t);
+struct HsSparsePlan {
+  int KC = 0, nchunks = 0;
+  std::vector<int64_t> order;       // processing order of the columns (0-based ids)
+  std::vector<unsigned char> act;   // [chunk * nnodes + internal node]: bit 0 forward, bit 1 backward
+  double visits[2] = {0, 0};        // front visits, forward / backward
+  double model = 0.0;               // sum over chunks and sweeps of ni^2 / 2 + ni nb over the visited fronts (elements)
+};
+// 0-based or 1-based indices (base); rows == nullptr: every row is wanted
+void hs_sparse_plan(const HsSparseTree& t, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, int64_t base, const int64_t* rows, int64_t nrows,
+                    HsSparsePlan* p);
+// X[r, j] = (op(F)^-1 B)[rows[r], j]: bval / dX on the device (X column-major, ld ldx), the index arrays on the host (1-based).  Waits for s.
+// out8: the figures of hs_ldiv_sparse_info but the seconds and the values moved
+template <class T>
+void hs_solve_sparse_run(const HsMultiView& v, const HsSparseTree& t, int trans, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const T* d_bval,
+                         const int64_t* rows, int64_t nrows, T* dX, int64_t ldx, hipStream_t s, double* out8);
+
+// ---- kernels_solve_sparse.hip ------------------------------------------------------------------------------------------------------------
+// W[row[e], col[e]] = val[src[e]] for the cnt entries of a chunk (W: n x kc column-major, ld ldw, zero before)
+template <class T>
+void launch_sparse_scatter(T* W, long long ldw, const T* val, const int* row, const int* col, const long long* src, long long cnt, hipStream_t s);
+// X[r, xcol[c]] = W[rows[r], c] for r < nrows, c < kc (X: ld ldx; rows == nullptr: row r itself)
+template <class T>
+void launch_sparse_gather(T* X, long long ldx, const long long* xcol, const T* W, long long ldw, const int* rows, long long nrows, int kc, hipStream_t s);
+// dst[e] = src[idx[e]] for whole SolveNode<T> entries (src: base of the handle's array, idx: element offsets from it)
+template <class T>
+void launch_sparse_compact(SolveNode<T>* dst, const SolveNode<T>* src, const long long* idx, long long cnt, hipStream_t s);
+// rows [woff, woff + ni) x kc of the row-major work block W2 (pitch kcw) = 0 for every segment, one launch
+template <class T>
+void launch_sparse_zero(T* W2, int kcw, int kc, const HsZeroSeg* seg, int nseg, int maxni, hipStream_t s);
 
 // ---- kernels_solve_multi.hip ----------------------------------------------------------------------------------------------------------
 // One tall-skinny product  D = A X  or  D = Cin - A X  with A (M x K, column-major, a stored factor panel) read once and fed to

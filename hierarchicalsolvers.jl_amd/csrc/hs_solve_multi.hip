@@ -196,6 +196,28 @@ void lr_apply_t(const LowRank<T>& lr, int conj, const T* x, T* dst, T* tbuf, int
   fc.add(lr.cols, lr.r, kc);
 }
 
+// what a level's grouped launches run over: the level's own arrays, or the compacted ones of an active set (hs_solve_multi.h)
+struct LevelSel {
+  const void* sn;
+  const MultiAux* aux;
+  int nf, maxni, maxnb;
+  const std::vector<int>* pos;  // null: every front of the level
+  bool has(int p) const { return !pos || std::binary_search(pos->begin(), pos->end(), p); }
+};
+LevelSel level_sel(const HsMultiLevel& L, const MultiAux* aux, const HsMultiActive* act, int chunk, int lv, int sweep) {
+  if (!act) return {L.sn, aux, L.nfronts, L.maxni, L.maxnb, nullptr};
+  const HsMultiSubset& q = act->at(chunk, lv, sweep);
+  return {q.sn, q.aux, (int)q.pos.size(), q.maxni, q.maxnb, &q.pos};
+}
+template <class F>
+void each_front(const HsMultiLevel& L, const LevelSel& q, F f) {
+  if (!q.pos) {
+    for (const HsMultiFront& x : L.fronts) f(x);
+  } else {
+    for (int p : *q.pos) f(L.fronts[p]);
+  }
+}
+
 // HS_LDIV_BLOCK_T_LOOK = left selects the left-looking triangular sweeps of the transposed solve (a measurement switch; default: right)
 bool multi_t_left_looking() {
   static const bool left = [] {
@@ -207,7 +229,7 @@ bool multi_t_left_looking() {
 }  // namespace
 
 template <class T>
-void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act) {
   const int KC = hs_ldiv_block_cols();
   const int kcw = KC;
   MultiCache* mc = multi_prepare<T>(v, kcw);
@@ -221,71 +243,81 @@ void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, 
     const int kc = (int)std::min<int64_t>(KC, nrhs - c0);
     MultiArgs a;
     a.W1 = mc->W1; a.W2 = mc->W2; a.XB = mc->XB; a.kcw = kcw;
-    a.B = dC + c0 * ldc; a.ldb = ldc; a.kc = kc;
+    a.B = act ? dC : dC + c0 * ldc; a.ldb = ldc; a.kc = kc;  // an active set keeps every chunk in the same block
+    if (act && act->begin) act->begin(act->ctx, chunks, kc, s);
     for (int lv = nl - 1; lv >= 0; --lv) {  // leaves -> root
       const HsMultiLevel& L = v.levels[lv];
       if (L.nfronts == 0 || L.maxni == 0) continue;
-      const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+      const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 0);
+      if (q_.nf == 0 || q_.maxni == 0) continue;
+      const SolveNode<T>* sn = (const SolveNode<T>*)q_.sn;
+      const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
-      a.aux = mc->d_aux + mc->aux_off[lv];
-      launch_multi_move<T>(sn, L.nfronts, 0, L.maxni, a, s);
-      launch_multi_move<T>(sn, L.nfronts, 1, L.maxnb, a, s);
-      const int nblk = (L.maxni + 255) / 256;
+      a.aux = q_.aux;
+      launch_multi_move<T>(sn, nf, 0, maxni, a, s);
+      launch_multi_move<T>(sn, nf, 1, maxnb, a, s);
+      const int nblk = (maxni + 255) / 256;
       for (int j = 0; j < nblk; ++j) {
-        launch_multi_level<T>(sn, L.nfronts, HSM_DIAG_L, j, std::min(256, L.maxni - j * 256), a, s);
-        launch_multi_level<T>(sn, L.nfronts, HSM_BELOW_L, j, L.maxni - (j + 1) * 256, a, s);
+        launch_multi_level<T>(sn, nf, HSM_DIAG_L, j, std::min(256, maxni - j * 256), a, s);
+        launch_multi_level<T>(sn, nf, HSM_BELOW_L, j, maxni - (j + 1) * 256, a, s);
       }
-      launch_multi_level<T>(sn, L.nfronts, HSM_BND_L, 0, L.maxnb, a, s);
-      for (const HsMultiFront& f : L.fronts) {
+      launch_multi_level<T>(sn, nf, HSM_BND_L, 0, maxnb, a, s);
+      each_front(L, q_, [&](const HsMultiFront& f) {
         for (int j = 0; j * 256 < f.ni; ++j) {
           const double wl = std::min(256, f.ni - j * 256);
           fc.add(wl, wl, kc, wl * (wl + 1) / 2);
           fc.add(f.ni - (j + 1) * 256, 256, kc);
         }
         if (f.dense_bnd) fc.add(f.nb, f.ni, kc);
-      }
+      });
       for (const HsMultiLR& q : L.lr) {
-        if (!q.lrL) continue;
+        if (!q.lrL || !q_.has(q.pos)) continue;
         const LowRank<T>& lr = *(const LowRank<T>*)q.lrL;
         if (lr.r == 0) continue;
         lr_apply<T>(lr, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
-      launch_multi_move<T>(sn, L.nfronts, 3, L.maxnb, a, s);
+      launch_multi_move<T>(sn, nf, 3, maxnb, a, s);
     }
+    if (act && act->zoff[chunks + 1] > act->zoff[chunks])  // backward-only fronts: y = 0
+      launch_sparse_zero<T>((T*)mc->W2, kcw, kc, act->zseg + act->zoff[chunks], (int)(act->zoff[chunks + 1] - act->zoff[chunks]), act->zmaxni[chunks], s);
     for (int lv = 0; lv < nl; ++lv) {  // root -> leaves
       const HsMultiLevel& L = v.levels[lv];
       if (L.nfronts == 0 || L.maxni == 0) continue;
-      const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+      const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 1);
+      if (q_.nf == 0 || q_.maxni == 0) continue;
+      const SolveNode<T>* sn = (const SolveNode<T>*)q_.sn;
+      const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
-      a.aux = mc->d_aux + mc->aux_off[lv];
-      launch_multi_move<T>(sn, L.nfronts, 1, L.maxnb, a, s);
-      launch_multi_level<T>(sn, L.nfronts, HSM_UR, 0, L.maxni, a, s);
+      a.aux = q_.aux;
+      launch_multi_move<T>(sn, nf, 1, maxnb, a, s);
+      launch_multi_level<T>(sn, nf, HSM_UR, 0, maxni, a, s);
       for (const HsMultiLR& q : L.lr) {
-        if (!q.lrR) continue;
+        if (!q.lrR || !q_.has(q.pos)) continue;
         const LowRank<T>& lr = *(const LowRank<T>*)q.lrR;
         if (lr.r == 0) continue;
         lr_apply<T>(lr, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
-      const int nblk = (L.maxni + 255) / 256;
+      const int nblk = (maxni + 255) / 256;
       for (int j = nblk - 1; j >= 0; --j) {
-        launch_multi_level<T>(sn, L.nfronts, HSM_DIAG_U, j, std::min(256, L.maxni - j * 256), a, s);
-        launch_multi_level<T>(sn, L.nfronts, HSM_ABOVE_U, j, j * 256, a, s);
+        launch_multi_level<T>(sn, nf, HSM_DIAG_U, j, std::min(256, maxni - j * 256), a, s);
+        launch_multi_level<T>(sn, nf, HSM_ABOVE_U, j, j * 256, a, s);
       }
-      launch_multi_move<T>(sn, L.nfronts, 2, L.maxni, a, s);
-      for (const HsMultiFront& f : L.fronts) {
+      launch_multi_move<T>(sn, nf, 2, maxni, a, s);
+      each_front(L, q_, [&](const HsMultiFront& f) {
         if (f.dense_bnd) fc.add(f.ni, f.nb, kc);
         for (int j = 0; j * 256 < f.ni; ++j) {
           const double wl = std::min(256, f.ni - j * 256);
           fc.add(wl, wl, kc, wl * (wl + 1) / 2);
           fc.add(j * 256, wl, kc);
         }
-      }
+      });
     }
+    if (act && act->end) act->end(act->ctx, chunks, kc, s);
   }
   multi_finish(mc, v, fc, chunks, sizeof(T), s);
 }
-template void hs_solve_multi_run<double>(const HsMultiView&, double*, int64_t, int64_t, hipStream_t);
-template void hs_solve_multi_run<cplx>(const HsMultiView&, cplx*, int64_t, int64_t, hipStream_t);
+template void hs_solve_multi_run<double>(const HsMultiView&, double*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
+template void hs_solve_multi_run<cplx>(const HsMultiView&, cplx*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
 
 // transpose(F) \ B and adjoint(F) \ B: the same chunks, work blocks and stored blocks, every product with the factor panel transposed
 // (kernels_solve_multi_t.hip).  op(x) = x (trans = 1) or conj(x) (trans = 2: the factor entries are conjugated as they are loaded).  Per chunk:
@@ -301,7 +333,7 @@ template void hs_solve_multi_run<cplx>(const HsMultiView&, cplx*, int64_t, int64
 // per output row -- and has (ni - 256 (j + 1)) / 64 workgroups.  The left-looking order (HS_LDIV_BLOCK_T_LOOK=left) reads the column panel
 // above / below the block with K up to ni and 256 outputs: W is written once per block, by four workgroups per front (DESIGN.md section 4a⁗″).
 template <class T>
-void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act) {
   const int KC = hs_ldiv_block_cols();
   const int kcw = KC;
   const int cj = (trans == 2 && sizeof(T) == 16) ? 1 : 0;
@@ -317,24 +349,28 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
     const int kc = (int)std::min<int64_t>(KC, nrhs - c0);
     MultiArgs a;
     a.W1 = mc->W1; a.W2 = mc->W2; a.XB = mc->XB; a.kcw = kcw;
-    a.B = dC + c0 * ldc; a.ldb = ldc; a.kc = kc;
+    a.B = act ? dC : dC + c0 * ldc; a.ldb = ldc; a.kc = kc;  // an active set keeps every chunk in the same block
+    if (act && act->begin) act->begin(act->ctx, chunks, kc, s);
     for (int lv = nl - 1; lv >= 0; --lv) {  // leaves -> root
       const HsMultiLevel& L = v.levels[lv];
       if (L.nfronts == 0 || L.maxni == 0) continue;
-      const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+      const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 0);
+      if (q_.nf == 0 || q_.maxni == 0) continue;
+      const SolveNode<T>* sn = (const SolveNode<T>*)q_.sn;
+      const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
-      a.aux = mc->d_aux + mc->aux_off[lv];
-      launch_multi_move_t<T>(sn, L.nfronts, 0, L.maxni, a, s);
-      launch_multi_move_t<T>(sn, L.nfronts, 1, L.maxnb, a, s);
-      const int nblk = (L.maxni + 255) / 256;
+      a.aux = q_.aux;
+      launch_multi_move_t<T>(sn, nf, 0, maxni, a, s);
+      launch_multi_move_t<T>(sn, nf, 1, maxnb, a, s);
+      const int nblk = (maxni + 255) / 256;
       for (int j = 0; j < nblk; ++j) {
-        const int wl = std::min(256, L.maxni - j * 256);
-        if (left && j > 0) launch_multi_level_t<T>(sn, L.nfronts, HSMT_LEFT_U, j, cj, wl, a, s);
-        launch_multi_level_t<T>(sn, L.nfronts, HSMT_DIAG_U, j, cj, wl, a, s);
-        if (!left) launch_multi_level_t<T>(sn, L.nfronts, HSMT_BELOW_U, j, cj, L.maxni - (j + 1) * 256, a, s);
+        const int wl = std::min(256, maxni - j * 256);
+        if (left && j > 0) launch_multi_level_t<T>(sn, nf, HSMT_LEFT_U, j, cj, wl, a, s);
+        launch_multi_level_t<T>(sn, nf, HSMT_DIAG_U, j, cj, wl, a, s);
+        if (!left) launch_multi_level_t<T>(sn, nf, HSMT_BELOW_U, j, cj, maxni - (j + 1) * 256, a, s);
       }
-      launch_multi_level_t<T>(sn, L.nfronts, HSMT_BND_U, 0, cj, L.maxnb, a, s);
-      for (const HsMultiFront& f : L.fronts) {
+      launch_multi_level_t<T>(sn, nf, HSMT_BND_U, 0, cj, maxnb, a, s);
+      each_front(L, q_, [&](const HsMultiFront& f) {
         for (int j = 0; j * 256 < f.ni; ++j) {
           const double wl = std::min(256, f.ni - j * 256);
           fc.add(wl, wl, kc, wl * (wl + 1) / 2);
@@ -344,38 +380,43 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
             fc.add(f.ni - (j + 1) * 256, 256, kc);
         }
         if (f.dense_bnd) fc.add(f.nb, f.ni, kc);
-      }
+      });
       for (const HsMultiLR& q : L.lr) {
-        if (!q.lrR) continue;
+        if (!q.lrR || !q_.has(q.pos)) continue;
         const LowRank<T>& lr = *(const LowRank<T>*)q.lrR;
         if (lr.r == 0) continue;
         lr_apply_t<T>(lr, cj, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
-      launch_multi_move_t<T>(sn, L.nfronts, 3, L.maxnb, a, s);
+      launch_multi_move_t<T>(sn, nf, 3, maxnb, a, s);
     }
+    if (act && act->zoff[chunks + 1] > act->zoff[chunks])  // backward-only fronts: y = 0
+      launch_sparse_zero<T>((T*)mc->W2, kcw, kc, act->zseg + act->zoff[chunks], (int)(act->zoff[chunks + 1] - act->zoff[chunks]), act->zmaxni[chunks], s);
     for (int lv = 0; lv < nl; ++lv) {  // root -> leaves
       const HsMultiLevel& L = v.levels[lv];
       if (L.nfronts == 0 || L.maxni == 0) continue;
-      const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+      const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 1);
+      if (q_.nf == 0 || q_.maxni == 0) continue;
+      const SolveNode<T>* sn = (const SolveNode<T>*)q_.sn;
+      const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
-      a.aux = mc->d_aux + mc->aux_off[lv];
-      launch_multi_move_t<T>(sn, L.nfronts, 1, L.maxnb, a, s);
-      launch_multi_level_t<T>(sn, L.nfronts, HSMT_LB, 0, cj, L.maxni, a, s);
+      a.aux = q_.aux;
+      launch_multi_move_t<T>(sn, nf, 1, maxnb, a, s);
+      launch_multi_level_t<T>(sn, nf, HSMT_LB, 0, cj, maxni, a, s);
       for (const HsMultiLR& q : L.lr) {
-        if (!q.lrL) continue;
+        if (!q.lrL || !q_.has(q.pos)) continue;
         const LowRank<T>& lr = *(const LowRank<T>*)q.lrL;
         if (lr.r == 0) continue;
         lr_apply_t<T>(lr, cj, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
-      const int nblk = (L.maxni + 255) / 256;
+      const int nblk = (maxni + 255) / 256;
       for (int j = nblk - 1; j >= 0; --j) {
-        const int wl = std::min(256, L.maxni - j * 256);
-        if (left) launch_multi_level_t<T>(sn, L.nfronts, HSMT_LEFT_L, j, cj, 256, a, s);
-        launch_multi_level_t<T>(sn, L.nfronts, HSMT_DIAG_L, j, cj, wl, a, s);
-        if (!left) launch_multi_level_t<T>(sn, L.nfronts, HSMT_ABOVE_L, j, cj, j * 256, a, s);
+        const int wl = std::min(256, maxni - j * 256);
+        if (left) launch_multi_level_t<T>(sn, nf, HSMT_LEFT_L, j, cj, 256, a, s);
+        launch_multi_level_t<T>(sn, nf, HSMT_DIAG_L, j, cj, wl, a, s);
+        if (!left) launch_multi_level_t<T>(sn, nf, HSMT_ABOVE_L, j, cj, j * 256, a, s);
       }
-      launch_multi_move_t<T>(sn, L.nfronts, 2, L.maxni, a, s);
-      for (const HsMultiFront& f : L.fronts) {
+      launch_multi_move_t<T>(sn, nf, 2, maxni, a, s);
+      each_front(L, q_, [&](const HsMultiFront& f) {
         if (f.dense_bnd) fc.add(f.ni, f.nb, kc);
         for (int j = 0; j * 256 < f.ni; ++j) {
           const double wl = std::min(256, f.ni - j * 256);
@@ -385,13 +426,14 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
           else
             fc.add(j * 256, wl, kc);
         }
-      }
+      });
     }
+    if (act && act->end) act->end(act->ctx, chunks, kc, s);
   }
   multi_finish(mc, v, fc, chunks, sizeof(T), s);
 }
-template void hs_solve_multi_run_t<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t);
-template void hs_solve_multi_run_t<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t);
+template void hs_solve_multi_run_t<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
+template void hs_solve_multi_run_t<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
 
 double hs_solve_multi_seconds(void* mx) {
   MultiCache* mc = (MultiCache*)mx;

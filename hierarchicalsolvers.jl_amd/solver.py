@@ -22,6 +22,7 @@ All arithmetic happens in ``libhs_solver.so`` on the GPU; this module only marsh
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import scipy.sparse as sp
@@ -470,6 +471,143 @@ def ldiv_block_info(F):
     _lib.check(_lib.lib().hs_ldiv_block_info(F._h, _pf64(out)))
     return {"seconds": float(out[0]), "factor_bytes": float(out[1]), "flops_executed": float(out[2]), "flops_useful": float(out[3]),
             "chunks": int(out[4]), "workspace_bytes": int(out[5])}
+
+
+def _sparse_rhs(F, B):
+    """``(F, trans, raw handle, B as canonical CSC, 1-based colptr, 1-based rowval)`` for the ``hs_ldiv_sparse_*`` calls."""
+    trans = 0
+    if isinstance(F, TransposedFactor):
+        F, trans = F.parent, F.trans
+    h = F._h if isinstance(F, FactorNode) else F  # a raw handle: dist.plan_only
+    n = F.n if isinstance(F, FactorNode) else int(_lib.lib().hs_size(h))
+    if not sp.issparse(B):
+        raise TypeError(f"expected a scipy.sparse matrix, got {type(B).__name__}")
+    if B.shape[0] != n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {n} x {n}")
+    B = sp.csc_matrix(B, copy=True)
+    B.sum_duplicates()
+    B.sort_indices()
+    colptr = np.ascontiguousarray(B.indptr, dtype=np.int64) + 1
+    rowval = np.ascontiguousarray(B.indices, dtype=np.int64) + 1
+    return F, trans, h, n, B, colptr, rowval
+
+
+def _wanted_rows(rows, n):
+    if rows is None:
+        return None
+    rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= n):
+        raise _lib.DimensionMismatch(f"BoundsError: rows outside 0:{n - 1}")
+    return rows + 1
+
+
+def ldiv_sparse(F, B, rows=None):
+    """``(F \\ B)[rows, :]`` for a sparse ``B`` (``hs_ldiv_sparse_*``): ``B`` is any ``scipy.sparse`` matrix with ``n`` rows (converted to canonical
+    CSC: duplicates summed, indices sorted), ``F`` a :class:`FactorNode`, ``transpose(F)`` or ``adjoint(F)``, ``rows`` a 0-based integer
+    array (any order, repeats allowed) or ``None`` for all rows.  Returns a dense ``len(rows) x nrhs`` array (``n x nrhs`` for ``None``).
+    The forward sweep of a chunk of columns visits only the fronts that own a stored row of ``B`` and their ancestors, the backward sweep
+    only the fronts that own a wanted row and their ancestors; the result equals ``ldiv_block_t(F, B.toarray())[rows]`` bit for bit.
+    Indices refer to the factored (already permuted) matrix.  Dtype rules and refusals are those of :func:`ldiv_block`."""
+    F, trans, h, n, B, colptr, rowval = _sparse_rhs(F, B)
+    if not isinstance(F, FactorNode):
+        raise TypeError(f"expected a FactorNode, got {type(F).__name__}")
+    if B.dtype != F.dtype:
+        if F.dtype.kind == "f" and B.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::FactorNode{Float64}, ::SparseMatrixCSC{ComplexF64})")
+        B = B.astype(F.dtype)
+    vals = np.ascontiguousarray(B.data, dtype=F.dtype)
+    rows1 = _wanted_rows(rows, n)
+    nout = n if rows1 is None else len(rows1)
+    X = np.zeros((nout, B.shape[1]), dtype=F.dtype, order="F")
+    L = _lib.lib()
+    fn = L.hs_ldiv_sparse_z if F.dtype.kind == "c" else L.hs_ldiv_sparse_d
+    _lib.check(fn(h, trans, n, B.shape[1], _p64(colptr), _p64(rowval), vals.ctypes.data_as(_lib.p_f64), None if rows1 is None else _p64(rows1), nout,
+                  X.ctypes.data_as(_lib.p_f64), max(nout, 1)))
+    return X
+
+
+def _num_nodes(h):
+    """Node ids of the C ABI on this handle: the user's tree, and the pseudo-root when the root keeps a boundary."""
+    st = _lib.hs_stats()
+    _lib.check(_lib.lib().hs_get_stats(h, C.byref(st)))
+    nn = int(st.nnodes)
+    return nn + 1 if _lib.lib().hs_node_info(h, nn, None, None, None) == _lib.HS_OK else nn
+
+
+def ldiv_sparse_plan(F, B, rows=None):
+    """What ``ldiv_sparse(F, B, rows)`` would visit (``hs_ldiv_sparse_plan``; host work only, ``F`` may also be the handle of
+    ``dist.plan_only``): ``order`` (the processing order, 0-based column ids), ``nchunks``, and ``active[chunk, node]`` with bit 0 = the
+    forward sweep of the chunk visits the node, bit 1 = the backward sweep does (node ids of the tree in post-order)."""
+    F, trans, h, n, B, colptr, rowval = _sparse_rhs(F, B)
+    rows1 = _wanted_rows(rows, n)
+    nr = 0 if rows1 is None else len(rows1)
+    pr = None if rows1 is None else _p64(rows1)
+    L = _lib.lib()
+    order = np.zeros(B.shape[1], dtype=np.int64)
+    nch = _lib.i64(0)
+    _lib.check(L.hs_ldiv_sparse_plan(h, trans, n, B.shape[1], _p64(colptr), _p64(rowval), pr, nr, _p64(order), C.byref(nch), None))
+    nn = _num_nodes(h)
+    active = np.zeros((nch.value, nn), dtype=np.uint8)
+    if active.size:
+        _lib.check(L.hs_ldiv_sparse_plan(h, trans, n, B.shape[1], _p64(colptr), _p64(rowval), pr, nr, None, None, active.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return {"order": order, "nchunks": int(nch.value), "active": active}
+
+
+def ldiv_sparse_info(F):
+    """Figures of the last :func:`ldiv_sparse` call on ``F`` (``hs_ldiv_sparse_info``): device seconds, factor bytes read by the model (per chunk
+    and sweep ``(ni^2 / 2 + ni nb) sizeof(T)`` over the visited fronts), front visits of the forward and of the backward sweeps, fronts x
+    chunks (what a dense block solve visits per sweep), chunks, values moved between host and device, workspace bytes."""
+    F, _ = _unwrap(F)
+    out = np.zeros(8)
+    _lib.check(_lib.lib().hs_ldiv_sparse_info(F._h, _pf64(out)))
+    return {"seconds": float(out[0]), "factor_bytes": float(out[1]), "visits_forward": int(out[2]), "visits_backward": int(out[3]),
+            "visits_dense": int(out[4]), "chunks": int(out[5]), "values_moved": int(out[6]), "workspace_bytes": int(out[7])}
+
+
+def _block_cols():
+    """Columns per chunk of the block solves: the library's reading of ``HS_LDIV_BLOCK_COLS``."""
+    try:
+        v = int(os.environ.get("HS_LDIV_BLOCK_COLS", "32"))
+    except ValueError:
+        v = 32
+    return v if v in (16, 32, 48, 64) else 32
+
+
+def inv_entries(F, I, J):
+    """``(A^-1)[I[k], J[k]]`` for arbitrary 0-based index pairs -- entries of the inverse outside the pattern of ``A`` too, which
+    :func:`selinv` does not give -- by :func:`ldiv_sparse` on unit columns: the distinct ``J`` become unit right-hand sides, the library
+    orders them so that the columns of a chunk are neighbours in the tree, and each group of ``HS_LDIV_BLOCK_COLS`` columns asks for the
+    union of its ``I`` only.  ``transpose(F)`` / ``adjoint(F)`` give the entries of ``(A^T)^-1`` / ``(A^H)^-1``.  On a compressed
+    factorization the result is the entry of the approximate inverse the factors define.  The cost follows the number of distinct
+    columns: with few distinct rows and many columns ask the transposed form, ``inv_entries(transpose(F), J, I)`` (conjugate it for a
+    ComplexF64 ``adjoint``), which solves for the few rows instead.  Indices refer to the factored (already permuted) matrix."""
+    Fn, _ = _unwrap(F)
+    n = Fn.n
+    I = np.asarray(I, dtype=np.int64).reshape(-1)
+    J = np.asarray(J, dtype=np.int64).reshape(-1)
+    if I.shape != J.shape:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: {len(I)} row and {len(J)} column indices")
+    for a in (I, J):
+        if a.size and (a.min() < 0 or a.max() >= n):
+            raise _lib.DimensionMismatch(f"BoundsError: index outside 0:{n - 1}")
+    out = np.zeros(len(I), dtype=Fn.dtype)
+    if not len(I):
+        return out
+    cols, cid = np.unique(J, return_inverse=True)
+    E = sp.csc_matrix((np.ones(len(cols), dtype=Fn.dtype), cols, np.arange(len(cols) + 1)), shape=(n, len(cols)))
+    order = ldiv_sparse_plan(F, E, rows=I[:1])["order"]
+    by_col = np.argsort(cid, kind="stable")  # the pairs of column c: by_col[start[c]:start[c + 1]]
+    start = np.searchsorted(cid[by_col], np.arange(len(cols) + 1))
+    kc = _block_cols()
+    for g0 in range(0, len(cols), kc):
+        grp = order[g0:g0 + kc]
+        pairs = np.concatenate([by_col[start[c]:start[c + 1]] for c in grp])
+        rows, rid = np.unique(I[pairs], return_inverse=True)
+        X = ldiv_sparse(F, E[:, grp], rows)
+        pos = np.empty(len(cols), dtype=np.int64)
+        pos[grp] = np.arange(len(grp))
+        out[pairs] = X[rid, pos[cid[pairs]]]
+    return out
 
 
 def maxrank(F):

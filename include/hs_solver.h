@@ -183,6 +183,44 @@ int hs_ldiv_block_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, cons
  * useful flops, column chunks, workspace bytes} */
 int hs_ldiv_block_info(const hs_handle* F, double* out6);
 
+/* ---- sparse right-hand sides, selected rows of the solution (hs_solve_sparse.hip) ---------------------------------------------------
+ * X[r, j] = (op(F)^-1 B)[rows[r], j] for a sparse B and a list of wanted rows.  B is n x nrhs in CSC form, 1-based like A, rows strictly
+ * increasing within a column (stored zeros count as entries); rows: 1-based, any order, repeats allowed; rows == NULL: all n rows (nrows is
+ * ignored, X is n x nrhs).  X is column-major with leading dimension ldx.  trans = 0 / 1 / 2: F, transpose(F), adjoint(F) -- trans acts
+ * on F, never on B.
+ * The columns travel through the tree in chunks of HS_LDIV_BLOCK_COLS like hs_ldiv_block_t_*, but a chunk's forward sweep visits only the
+ * fronts that own a stored row of its columns and their ancestors, and its backward sweep only the fronts that own a wanted row and their
+ * ancestors (closed on the handle's internal front graph: slices of hs_options.split, the pseudo-root).  Columns are processed in a stable
+ * sort by the node id of the front that owns their first stored row, empty columns last; results return to the caller's positions.  The
+ * per-front arithmetic is that of the block solve and what is skipped is exactly zero there: X equals the wanted rows of hs_ldiv_block_t_*
+ * on the expanded block bit for bit, with its determinism.  A chunk of empty columns launches nothing and returns zeros.
+ * The host forms move nnz values up and nrows x nrhs values down; the _dev_ forms take bnzval and X on the device and the index arrays on
+ * the host (the closure is host work), run on `stream` and return when X is complete.
+ * Refused before any device work, X untouched: what hs_ldiv_block_t_* refuses (HSS interior blocks, more than one rank) with
+ * HS_ERR_UNSUPPORTED; a null handle, trans outside 0..2, a plan-only or unfactored handle, a mismatched element type, null pointers with
+ * nonzero sizes, bcolptr not 1-based or decreasing, rows of a column of B not strictly increasing: HS_ERR_ARGUMENT; n != size(F), a row
+ * index outside 1..n, ldx too small, negative sizes: HS_ERR_DIMENSION.  nrhs == 0, or nrows == 0 with rows != NULL: HS_OK, nothing written. */
+int hs_ldiv_sparse_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const double* bnzval,
+                     const int64_t* rows, int64_t nrows, double* X, int64_t ldx);
+int hs_ldiv_sparse_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const double* bnzval,
+                     const int64_t* rows, int64_t nrows, double* X, int64_t ldx); /* bnzval, X: interleaved (re, im) */
+int hs_ldiv_sparse_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const double* d_bnzval,
+                         const int64_t* rows, int64_t nrows, double* dX, int64_t ldx, void* stream);
+int hs_ldiv_sparse_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const double* d_bnzval,
+                         const int64_t* rows, int64_t nrows, double* dX, int64_t ldx, void* stream);
+/* what such a call would visit; host only, also on an hs_plan handle.  order[nrhs]: the processing order (0-based column ids); *nchunks;
+ * active[chunk * nnodes + node]: bit 0 = the forward sweep of the chunk visits the node, bit 1 = the backward sweep does, node ids as in
+ * hs_node_info (the user's tree; a split front is visited when any of its slices is).  Any of the three may be NULL (ask for *nchunks first
+ * to size active).  Refusals as above. */
+int hs_ldiv_sparse_plan(const hs_handle* F, int trans, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval,
+                        const int64_t* rows, int64_t nrows, int64_t* order, int64_t* nchunks, uint8_t* active);
+/* the last hs_ldiv_sparse_* call of the handle: out8 = {seconds on the device, factor bytes read by the model (sizeof(T) x sum over chunks of
+ * the sum of ni^2 / 2 + ni nb over the forward-visited fronts plus the same over the backward-visited ones; with every front visited this is
+ * hs_ldiv_block_info's figure), front visits forward, front visits backward, fronts x chunks (what a dense block solve visits per sweep),
+ * chunks, values moved between host and device (nnz + nrows x nrhs; 0 for the _dev_ forms), workspace bytes}.  The call runs through the
+ * block-solve driver, so hs_ldiv_block_info then reports that driver's figures of it. */
+int hs_ldiv_sparse_info(const hs_handle* F, double* out8);
+
 /* ---- accuracy tools: norm and condition estimates, refined solves with error bounds (hs_condest.hip) --------------------------
  * opnorm(A, 1), opnorm(A, Inf) of the handle's A (the values of the last hs_numeric_begin); p = 1 or 0 (= Inf).  The first call that needs
  * rows of A (p = 0, hs_condest p = 0, hs_ldiv_refine_* with trans = 0) builds a CSR map of A's pattern on the device and keeps it in the handle. */
