@@ -51,6 +51,11 @@ class hs_sparse_dev(C.Structure):
                 ("rowptr", C.c_void_p), ("colind", C.c_void_p), ("nzval_r", C.c_void_p)]
 
 
+class hs_block_arg(C.Structure):
+    """An n x nrhs block of ``hs_sens_*`` / ``hs_misfit_*``: dense (``dense``, ``ld``) or, with ``dense`` NULL, 1-based CSC."""
+    _fields_ = [("dense", C.c_void_p), ("ld", i64), ("colptr", p_i64), ("rowval", p_i64), ("nzval", C.c_void_p)]
+
+
 class hs_hss_blockop(C.Structure):
     _fields_ = [("n1", i64), ("n2", i64), ("H1", C.c_void_p), ("H2", C.c_void_p), ("gid", p_i64), ("A", C.POINTER(hs_sparse_dev)), ("lpos", C.c_void_p)]
 
@@ -78,6 +83,7 @@ EXPORTS = [
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
     "hs_logabsdet", "hs_selinv", "hs_selinv_info",
+    "hs_sens_d", "hs_sens_z", "hs_sens_dev_d", "hs_sens_dev_z", "hs_misfit_d", "hs_misfit_z", "hs_misfit_dev_d", "hs_misfit_dev_z", "hs_sens_info", "hsk_sddmm_d", "hsk_sddmm_z",
     "hs_maxrank", "hs_is_complex", "hs_size", "hs_free", "hs_last_error", "hs_last_error_info", "hs_get_stats",
     "hs_node_info", "hs_node_ranks", "hs_node_export", "hs_node_export_piv", "hs_device_info",
     "hs_analyze", "hs_plan", "hs_numeric_begin", "hs_numeric_levels", "hs_numeric_end", "hs_solve_fwd_levels", "hs_solve_bwd_levels",
@@ -194,6 +200,24 @@ def lib():
         f.restype = C.c_int
     L.hs_ldiv_refine_block_info.argtypes = [p_f64]
     L.hs_ldiv_refine_block_info.restype = C.c_int
+    pb = C.POINTER(hs_block_arg)
+    for f in (L.hs_sens_d, L.hs_sens_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, pb, i64, C.c_int, vp, vp, i64, vp, i64]
+        f.restype = C.c_int
+    for f in (L.hs_sens_dev_d, L.hs_sens_dev_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, pb, i64, C.c_int, vp, vp, i64, vp, i64, vp]
+        f.restype = C.c_int
+    for f in (L.hs_misfit_d, L.hs_misfit_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, p_i64, i64, vp, i64, i64, C.c_int, vp, vp, i64, vp]
+        f.restype = C.c_int
+    for f in (L.hs_misfit_dev_d, L.hs_misfit_dev_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, p_i64, i64, vp, i64, i64, C.c_int, vp, vp, i64, vp, vp]
+        f.restype = C.c_int
+    L.hs_sens_info.argtypes = [vp, p_f64]
+    L.hs_sens_info.restype = C.c_int
+    for f in (L.hsk_sddmm_d, L.hsk_sddmm_z):
+        f.argtypes = [i64, p_i64, p_i64, i64, vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, p_f64]
+        f.restype = C.c_int
     L.hs_logabsdet.argtypes = [vp, p_f64, p_f64]
     L.hs_logabsdet.restype = C.c_int
     L.hs_selinv.argtypes = [vp, C.c_int, vp, vp, C.c_int, i64, vp]

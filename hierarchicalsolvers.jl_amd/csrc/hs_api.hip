@@ -293,6 +293,7 @@ struct hs_handle {
   void (*mx_free)(void*) = nullptr;
   std::vector<int> sp_owner;  // hs_ldiv_sparse_*: per row the internal node whose int holds it (built by the first call that needs it)
   double sp_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the figures of the last hs_ldiv_sparse_* call
+  double sens_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the figures of the last hs_sens_* / hs_misfit_* call (hs_sens.hip)
 };
 
 static inline int rup(int x, int a) { return (x + a - 1) / a * a; }
@@ -1915,6 +1916,7 @@ void hs_handle_view(hs_handle* h, HsHandleView* v) {
   v->cx_free = &h->cx_free;
 }
 int hs_handle_flow_check(hs_handle* h) { HS_GUARD(flow_check(h)); }
+double* hs_handle_sens_info(hs_handle* h) { return h->sens_info; }  // hs_sens.h
 
 // the handle as hs_selinv.hip sees it (hs_selinv.h): the owned fronts in post-order with the blocks their pivoted LU lives in
 void hs_selinv_view(hs_handle* h, HsSelView* v) {

@@ -436,6 +436,116 @@ extern "C" int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double
 }
 
 // The leaf-envelope builder of the analysis (hs_envelope.h), host only: tests compare it with a NumPy computation from A[idx][:, idx]
+// hsk_sddmm_*: the reduction kernel of hs_sens_* (kernels_sens.hip) alone on host data
+#include "hs_sens.h"
+namespace {
+struct SddmmBufs {
+  std::vector<void*> p;
+  ~SddmmBufs() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  void* get(size_t bytes) {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
+    p.push_back(q);
+    return q;
+  }
+};
+}  // namespace
+template <class T>
+static int sddmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const T* L, int64_t ldl, const T* R, int64_t ldr, int swap, int conjl, int conjr,
+                      int diag, int form, T* G, double* seconds) {
+  if (n < 1 || n > 0x7fffffff || kc < 1 || kc > 4096 || !colptr || !L || !R || !G || ldl < n || ldr < n || form < 0 || form > 1 || colptr[0] != 1) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_sddmm: n >= 1, kc in 1..4096, 1-based colptr, leading dimensions >= n, form in 0:1 and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  const int64_t nnz = colptr[n] - 1;
+  std::vector<int64_t> cp((size_t)n + 1);
+  std::vector<int32_t> rv((size_t)std::max<int64_t>(nnz, 0));
+  bool ok = nnz >= 0 && (nnz == 0 || rowval);
+  for (int64_t j = 0; ok && j <= n; ++j) {
+    cp[(size_t)j] = colptr[j] - 1;
+    ok = j == 0 || cp[(size_t)j] >= cp[(size_t)j - 1];
+  }
+  for (int64_t e = 0; ok && e < nnz; ++e) {
+    ok = rowval[e] >= 1 && rowval[e] <= n;
+    rv[(size_t)e] = (int32_t)(rowval[e] - 1);
+  }
+  if (!ok) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_sddmm: colptr decreases or rowval is outside 1:n");
+    return HS_ERR_ARGUMENT;
+  }
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
+    return HS_ERR_DEVICE;
+  }
+  const int64_t glen = diag ? n : nnz, stride = hs_sens_row_stride((int)kc, sizeof(T) == 16);
+  const bool staged = form == 1 && !diag;
+  SddmmBufs b;
+  int64_t* dcp = (int64_t*)b.get(sizeof(int64_t) * (size_t)(n + 1));
+  int32_t* drv = (int32_t*)b.get(sizeof(int32_t) * (size_t)nnz);
+  int32_t* dec = (int32_t*)b.get(sizeof(int32_t) * (size_t)nnz);
+  T* dL = (T*)b.get(sizeof(T) * (size_t)ldl * kc);
+  T* dR = (T*)b.get(sizeof(T) * (size_t)ldr * kc);
+  T* dG = (T*)b.get(sizeof(T) * (size_t)glen);
+  T* dG2 = seconds ? (T*)b.get(sizeof(T) * (size_t)glen) : dG;
+  T* dLt = staged ? (T*)b.get(sizeof(T) * (size_t)n * stride) : dL;
+  T* dRt = staged ? (T*)b.get(sizeof(T) * (size_t)n * stride) : dR;
+  if (!dcp || !drv || !dec || !dL || !dR || !dG || !dG2 || !dLt || !dRt) {
+    hs_set_error(HS_ERR_NOMEM, 0, "hsk_sddmm: hipMalloc failed");
+    return HS_ERR_NOMEM;
+  }
+  CK(hipMemcpy(dcp, cp.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+  if (nnz > 0) CK(hipMemcpy(drv, rv.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dL, L, sizeof(T) * (size_t)ldl * kc, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dR, R, sizeof(T) * (size_t)ldr * kc, hipMemcpyHostToDevice));
+  if (glen > 0) CK(hipMemcpy(dG, G, sizeof(T) * (size_t)glen, hipMemcpyHostToDevice));
+  const HsSddmmFlags f{swap ? 1 : 0, conjl ? 1 : 0, conjr ? 1 : 0};
+  launch_sens_entry_cols(dcp, n, nnz, dec, 0);
+  auto run = [&](T* g) {
+    if (diag) {
+      launch_sddmm_diag<T>(dcp, drv, n, dL, ldl, dR, ldr, (int)kc, f, g, 0);
+    } else if (staged) {
+      launch_sens_rowstage<T>(dL, ldl, n, (int)kc, dLt, stride, 0);
+      launch_sens_rowstage<T>(dR, ldr, n, (int)kc, dRt, stride, 0);
+      launch_sddmm_rows<T>(drv, dec, nnz, dLt, dRt, stride, (int)kc, f, g, 0);
+    } else {
+      launch_sddmm<T>(drv, dec, nnz, dL, ldl, dR, ldr, (int)kc, f, g, 0);
+    }
+  };
+  if (seconds) {  // one warm-up and three timed runs on a copy of G; the median
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};
+    if (glen > 0) CK(hipMemcpy(dG2, dG, sizeof(T) * (size_t)glen, hipMemcpyDeviceToDevice));
+    for (int k = 0; k < 4; ++k) {
+      CK(hipEventRecord(e0, 0));
+      run(dG2);
+      CK(hipEventRecord(e1, 0));
+      CK(hipEventSynchronize(e1));
+      CK(hipEventElapsedTime(&ms[k], e0, e1));
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    std::sort(ms + 1, ms + 4);
+    *seconds = ms[2] * 1e-3;
+  }
+  run(dG);
+  CK(hipDeviceSynchronize());
+  if (glen > 0) CK(hipMemcpy(G, dG, sizeof(T) * (size_t)glen, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+extern "C" int hsk_sddmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const double* L, int64_t ldl, const double* R, int64_t ldr, int swap,
+                           int conjl, int conjr, int diag, int form, double* G, double* seconds) {
+  return sddmm_hook<double>(n, colptr, rowval, kc, L, ldl, R, ldr, swap, conjl, conjr, diag, form, G, seconds);
+}
+extern "C" int hsk_sddmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const double* L, int64_t ldl, const double* R, int64_t ldr, int swap,
+                           int conjl, int conjr, int diag, int form, double* G, double* seconds) {
+  return sddmm_hook<cplx>(n, colptr, rowval, kc, (const cplx*)L, ldl, (const cplx*)R, ldr, swap, conjl, conjr, diag, form, (cplx*)G, seconds);
+}
+
 #include "hs_envelope.h"
 extern "C" int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL,
                                  int32_t* firstU) {

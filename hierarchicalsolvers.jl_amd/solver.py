@@ -31,7 +31,8 @@ from . import _lib
 from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
-           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info"]
+           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info",
+           "sensitivity", "sensitivity_matrix", "misfit", "sens_info"]
 
 
 class SolverOptions:
@@ -562,6 +563,160 @@ def ldiv_sparse_info(F):
     _lib.check(_lib.lib().hs_ldiv_sparse_info(F._h, _pf64(out)))
     return {"seconds": float(out[0]), "factor_bytes": float(out[1]), "visits_forward": int(out[2]), "visits_backward": int(out[3]),
             "visits_dense": int(out[4]), "chunks": int(out[5]), "values_moved": int(out[6]), "workspace_bytes": int(out[7])}
+
+
+def _sens_handle(F):
+    """``(FactorNode or None, trans, raw handle, n, dtype)``: ``F`` may also be the raw handle of ``dist.plan_only`` (refusal tests)."""
+    trans = 0
+    if isinstance(F, TransposedFactor):
+        F, trans = F.parent, F.trans
+    if isinstance(F, FactorNode):
+        return F, trans, F._h, F.n, F.dtype
+    L = _lib.lib()
+    return None, trans, F, int(L.hs_size(F)), np.dtype(np.complex128 if L.hs_is_complex(F) else np.float64)
+
+
+def _sens_block(name, M, n, dtype, ncols=None):
+    """A dense array or ``scipy.sparse`` matrix as an ``hs_block_arg``; returns ``(arg, nrhs, keep-alive objects)``."""
+    if sp.issparse(M):
+        if M.shape[0] != n:
+            raise _lib.DimensionMismatch(f"DimensionMismatch: {name} has {M.shape[0]} rows, F is {n} x {n}")
+        if M.dtype != dtype:
+            if dtype.kind == "f" and M.dtype.kind == "c":
+                raise TypeError(f"MethodError: no method matching sensitivity(::FactorNode{{Float64}}, {name}::SparseMatrixCSC{{ComplexF64}})")
+            M = M.astype(dtype)
+        M = sp.csc_matrix(M, copy=True)
+        M.sum_duplicates()
+        M.sort_indices()
+        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64) + 1
+        rowval = np.ascontiguousarray(M.indices, dtype=np.int64) + 1
+        vals = np.ascontiguousarray(M.data, dtype=dtype)
+        arg = _lib.hs_block_arg(None, 0, _p64(colptr), _p64(rowval), vals.ctypes.data)
+        nrhs, keep = M.shape[1], (colptr, rowval, vals)
+    else:
+        M = np.asarray(M)
+        if M.ndim == 1:
+            M = M.reshape(-1, 1)
+        if M.ndim != 2 or M.shape[0] != n:
+            raise _lib.DimensionMismatch(f"DimensionMismatch: {name} has {M.shape[0] if M.ndim else 0} rows, F is {n} x {n}")
+        if M.dtype != dtype:
+            if dtype.kind == "f" and M.dtype.kind == "c":
+                raise TypeError(f"MethodError: no method matching sensitivity(::FactorNode{{Float64}}, {name}::Array{{ComplexF64}})")
+            M = M.astype(dtype)
+        M = np.asfortranarray(M)
+        arg = _lib.hs_block_arg(M.ctypes.data, max(n, 1), None, None, None)
+        nrhs, keep = M.shape[1], (M,)
+    if ncols is not None and nrhs != ncols:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: {name} has {nrhs} columns, B has {ncols}")
+    return arg, nrhs, keep
+
+
+def _sens_pattern(pattern):
+    if pattern in ("A", 0):
+        return 0
+    if pattern in ("diag", 1):
+        return 1
+    raise ValueError(f"ArgumentError: pattern must be 'A' or 'diag', not {pattern!r}")
+
+
+def _sens_len(F, h, n, pcode):
+    if pcode == 1:
+        return n
+    if F is not None and F._pattern is not None:
+        return len(F._pattern[1])
+    return 0  # a raw handle: only the refusals are reachable
+
+
+def sensitivity(F, B, W, itmax=0, pattern="A", want=()):
+    """Adjoint-state sensitivity of a real objective on the pattern of the factored matrix ``A`` (``hs_sens_*``).  ``F`` is a
+    :class:`FactorNode`, ``transpose(F)`` or ``adjoint(F)``: with ``op(A)`` accordingly, ``X = op(A)^-1 B`` and ``W`` the cotangent
+    (``dJ = Re<W, dX>``), ``Lam = op(A)^-H W`` and the result ``G`` satisfies, for any ``E`` on the pattern of ``A``,
+    ``d/ds Re<W, op(A + sE)^-1 B> = Re sum(E.data * conj(G))`` at ``s = 0`` -- e.g. ``G_ij = -sum_c Lam_ic conj(X_jc)`` for a plain ``F``.
+    ``B`` and ``W`` are dense ``n x k`` arrays or ``scipy.sparse`` matrices (sparse blocks take the pruned sweeps of :func:`ldiv_sparse` and
+    give the bits of their dense expansion).  ``G`` is a 1-D array aligned with the ``data`` of the factored matrix (CSC, sorted indices;
+    :func:`sensitivity_matrix` wraps it), or of length ``n`` for ``pattern="diag"``.  ``itmax > 0`` solves both systems through
+    :func:`ldiv_refine_block` (compressed factorizations).  ``want`` may name ``"X"`` and ``"Lam"``: the result is then
+    ``(G, X, Lam)`` restricted to what was asked for, in that order.  Nothing but ``G`` and the requested blocks leaves the device.
+    Dtype rules and error classes are those of :func:`ldiv_block`."""
+    Fn, trans, h, n, dtype = _sens_handle(F)
+    pcode = _sens_pattern(pattern)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for w in want:
+        if w not in ("X", "Lam"):
+            raise ValueError(f"ArgumentError: want may name 'X' and 'Lam', not {w!r}")
+    if int(itmax) != itmax:
+        raise TypeError("itmax must be an integer")
+    argB, k, keepB = _sens_block("B", B, n, dtype)
+    argW, _, keepW = _sens_block("W", W, n, dtype, k)
+    G = np.zeros(_sens_len(Fn, h, n, pcode), dtype=dtype)
+    X = np.zeros((n, k), dtype=dtype, order="F") if "X" in want else None
+    Lam = np.zeros((n, k), dtype=dtype, order="F") if "Lam" in want else None
+    L = _lib.lib()
+    fn = L.hs_sens_z if dtype.kind == "c" else L.hs_sens_d
+    _lib.check(fn(h, trans, n, k, C.byref(argB), C.byref(argW), int(itmax), pcode, G.ctypes.data, None if X is None else X.ctypes.data, max(n, 1),
+                  None if Lam is None else Lam.ctypes.data, max(n, 1)))
+    del keepB, keepW
+    out = (G,) + ((X,) if X is not None else ()) + ((Lam,) if Lam is not None else ())
+    return out[0] if len(out) == 1 else out
+
+
+def sensitivity_matrix(F, G):
+    """``G`` of :func:`sensitivity` / :func:`misfit` (``pattern="A"``) as a ``scipy.sparse.csc_matrix`` on the pattern of the factored matrix."""
+    F, _ = _unwrap(F)
+    if F._pattern is None:
+        raise ValueError("ArgumentError: this FactorNode does not know the pattern of its matrix")
+    G = np.asarray(G)
+    if G.shape != (len(F._pattern[1]),):
+        raise _lib.DimensionMismatch(f"DimensionMismatch: G has shape {G.shape}, the factored matrix stores {len(F._pattern[1])} entries")
+    return sp.csc_matrix((G.copy(), F._pattern[1].copy(), F._pattern[0].copy()), shape=(F.n, F.n))
+
+
+def misfit(F, B, rows, D, itmax=0, pattern="A", want_residual=False):
+    """Least-squares misfit at receiver rows and its sensitivity (``hs_misfit_*``): with ``X = op(A)^-1 B``, ``R = X[rows, :] - D``
+    (``rows``: distinct 0-based indices, any order; ``D``: ``len(rows) x k``), ``J[c] = 0.5 ||R[:, c]||^2`` and ``G`` the sensitivity of
+    ``sum(J)`` as :func:`sensitivity` defines it for ``W = R`` scattered to ``rows``.  The cotangent is built on the device and is sparse, so
+    the adjoint solve takes the pruned path.  Returns ``(J, G)`` or, with ``want_residual``, ``(J, G, R)``.  Repeated rows raise
+    ``ValueError`` (ArgumentError)."""
+    Fn, trans, h, n, dtype = _sens_handle(F)
+    pcode = _sens_pattern(pattern)
+    if int(itmax) != itmax:
+        raise TypeError("itmax must be an integer")
+    argB, k, keepB = _sens_block("B", B, n, dtype)
+    rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= n):
+        raise _lib.DimensionMismatch(f"BoundsError: rows outside 0:{n - 1}")
+    rows1 = rows + 1
+    nr = len(rows1)
+    D = np.asarray(D)
+    if D.ndim == 1:
+        D = D.reshape(-1, 1)
+    if D.shape != (nr, k):
+        raise _lib.DimensionMismatch(f"DimensionMismatch: D has shape {D.shape}, expected {(nr, k)}")
+    if D.dtype != dtype:
+        if dtype.kind == "f" and D.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching misfit(::FactorNode{Float64}, D::Array{ComplexF64})")
+        D = D.astype(dtype)
+    D = np.asfortranarray(D)
+    G = np.zeros(_sens_len(Fn, h, n, pcode), dtype=dtype)
+    J = np.zeros(k)
+    R = np.zeros((nr, k), dtype=dtype, order="F") if want_residual else None
+    L = _lib.lib()
+    fn = L.hs_misfit_z if dtype.kind == "c" else L.hs_misfit_d
+    _lib.check(fn(h, trans, n, k, C.byref(argB), _p64(rows1), nr, D.ctypes.data, max(nr, 1), int(itmax), pcode, J.ctypes.data,
+                  None if R is None else R.ctypes.data, max(nr, 1), G.ctypes.data))
+    del keepB
+    return (J, G, R) if want_residual else (J, G)
+
+
+def sens_info(F):
+    """Figures of the last :func:`sensitivity` / :func:`misfit` call on ``F`` (``hs_sens_info``): device seconds in total, of the forward
+    solves, of the adjoint solves and of the reduction (staging included), column groups, stored entries x columns reduced, values moved
+    between host and device, workspace bytes."""
+    F, _ = _unwrap(F)
+    out = np.zeros(8)
+    _lib.check(_lib.lib().hs_sens_info(F._h, _pf64(out)))
+    return {"seconds": float(out[0]), "seconds_forward": float(out[1]), "seconds_adjoint": float(out[2]), "seconds_reduce": float(out[3]),
+            "groups": int(out[4]), "products": int(out[5]), "values_moved": int(out[6]), "workspace_bytes": int(out[7])}
 
 
 def _block_cols():

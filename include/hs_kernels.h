@@ -86,6 +86,20 @@ int hsk_spmm_op_d(int trans, int64_t n, const int64_t* colptr, const int64_t* ro
 int hsk_spmm_op_z(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb,
                   double* Y, int64_t ldy, int64_t nrhs);
 
+/* The reduction kernel of hs_sens_* (kernels_sens.hip) on host data: a sampled dense-dense product over the CSC pattern colptr / rowval
+ * (1-based, n columns, any order of the rows inside a column).  For every stored entry p = (i, j):
+ *   G[p] <- G[p] - sum over c = 0 .. kc-1 of f(L[a, c]) * g(R[b, c]),   (a, b) = (i, j), or (j, i) with swap != 0,
+ * f = conj with conjl != 0, g = conj with conjr != 0 (ComplexF64; ignored for Float64); L, R column-major n x kc (ldl, ldr >= n).  G holds
+ * the initial values on entry (nnz elements).  One chain per entry, the columns in order, continued from G[p], every step the same unfused
+ * expression: columns fed in several calls give the bits of one call.  diag != 0: G has n elements, G[j] continues its chain where (j, j) is
+ * stored and is set to 0 where it is not.  form: 0 = one lane per entry reading the column-major blocks (what hs_sens_* runs), 1 = the blocks
+ * transposed into row-major work blocks first (same bits; kept for measurements; ignored with diag).  seconds: NULL, or receives the median
+ * device time of three runs (after one warm-up, on a copy of G; form 1: the two transpositions included). */
+int hsk_sddmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const double* L, int64_t ldl, const double* R, int64_t ldr, int swap, int conjl,
+                int conjr, int diag, int form, double* G, double* seconds);
+int hsk_sddmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const double* L, int64_t ldl, const double* R, int64_t ldr, int swap, int conjl,
+                int conjr, int diag, int form, double* G, double* seconds);
+
 /* Host-only: the order in which the HSS form of a front's interior block lists its DOFs (hs_options.hss_d): recursive bisection of
  * the graph of A (1-based CSC pattern colptr / rowval of the n x n matrix) restricted to the ni DOFs `ids` (1-based), split where the
  * HSS cluster tree splits its index range.  perm_out[new position] = position in `ids` (0-based). */

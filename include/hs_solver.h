@@ -221,6 +221,60 @@ int hs_ldiv_sparse_plan(const hs_handle* F, int trans, int64_t n, int64_t nrhs, 
  * block-solve driver, so hs_ldiv_block_info then reports that driver's figures of it. */
 int hs_ldiv_sparse_info(const hs_handle* F, double* out8);
 
+/* ---- adjoint-state sensitivities on A's pattern for a block of sources (hs_sens.hip) ---------------------------------------------------
+ * op(A) = A, transpose(A), adjoint(A) for trans = 0 / 1 / 2; X = op(A)^-1 B with B n x nrhs; W (n x nrhs) is the cotangent of a real
+ * objective, dJ = Re<W, dX> = Re sum conj(W) .* dX.  With Lam = op(A)^-H W the sensitivity on the pattern of A is, for every stored (i, j):
+ *   trans 0:  Lam = adjoint(F) \ W       (Float64: transpose(F) \ W)   G_ij = -sum_c Lam_ic conj(X_jc)
+ *   trans 1:  Lam = conj(F \ conj(W))    (Float64: F \ W)              G_ij = -sum_c Lam_jc conj(X_ic)
+ *   trans 2:  Lam = F \ W                                              G_ij = -sum_c conj(Lam_jc) X_ic
+ * so that for any E on the pattern of A:  d/ds Re<W, op(A + sE)^-1 B> at s = 0  =  Re sum_p E_p conj(G_p).  Float64: no conj, G real.
+ * hs_misfit_* is the common objective: distinct receiver rows `rows` (1-based, any order), data D (nrows x nrhs, ldd); R = X[rows, :] - D,
+ * J[c] = 0.5 ||R[:, c]||^2, W = R scattered to the rows `rows`; R (may be NULL) is returned in the order of `rows`.
+ * A block (hs_block_arg) is dense (column-major, ld >= n) or, with dense == NULL, CSC with the rules of hs_ldiv_sparse_* (1-based, rows
+ * strictly increasing within a column).  pattern 0: G has nnz(A) values in the order of the nzval given to the factorization; 1: G has n
+ * values, G[j] for the stored (j, j) and 0 where A stores no diagonal entry.  X, Lam (may be NULL): the blocks, n x nrhs.
+ * The columns are processed in groups of Gc, a multiple of HS_LDIV_BLOCK_COLS: the widest group whose X and Lam blocks plus staging take at
+ * most half of the free device memory (HS_ERR_NOMEM when not even one chunk fits; HS_SENS_GROUP in the environment overrides Gc, read per
+ * call).  Per group: the forward solve (dense B: hs_ldiv_block_dev_t_*; sparse B: hs_ldiv_sparse_dev_* with all rows, i.e. the pruned forward
+ * sweep; itmax > 0: hs_ldiv_refine_block_dev_* without ferr, a sparse block expanded on the device first -- for compressed handles), W of the
+ * misfit form built on the device (sparse by construction: the pruned path when itmax = 0), the adjoint solve by the same choice of paths,
+ * and one reduction kernel that continues the sum of every stored entry.  X and Lam never leave the device unless asked for.  For
+ * ComplexF64 with trans = 1 the conjugation of W is folded into its copy and the one of the solution into the kernel.
+ * Determinism: X and Lam carry the bits of the entry points named above (X = hs_ldiv_block_t_*(op(F), B) for itmax = 0, dense or sparse);
+ * the sum of an entry is one chain over the columns in order, every step the same unfused products and sums, no atomics: two calls return
+ * the same bits, G does not depend on Gc, a sparse block gives the bits of its dense expansion, and pattern 1 returns the diagonal entries
+ * of pattern 0 bit for bit.  G is zero-filled first: nrhs = 0 returns G = 0 and HS_OK.
+ * Refused before any device work, every output untouched: what hs_ldiv_block_t_* refuses (HSS interior blocks, more than one rank), by its
+ * own check: HS_ERR_UNSUPPORTED; a null, plan-only or unfactored handle, a mismatched element type, trans outside 0..2, pattern outside 0..1,
+ * itmax < 0, null pointers with nonzero sizes, a CSC block hs_ldiv_sparse_* would refuse, repeated rows in the misfit form: HS_ERR_ARGUMENT;
+ * n != size(F), negative sizes, row indices outside 1..n, leading dimensions too small: HS_ERR_DIMENSION.
+ * The host forms move the blocks (or their stored values) up and G, J, R and the requested blocks down; in the _dev_ forms the values and
+ * the outputs are on the device, the index arrays (colptr, rowval, rows) on the host, and the call returns when the outputs are complete. */
+typedef struct {            /* an n x nrhs block, dense or CSC */
+  const double* dense; int64_t ld;                                     /* dense != NULL: column-major */
+  const int64_t* colptr; const int64_t* rowval; const double* nzval;   /* else CSC, 1-based, as hs_ldiv_sparse_* */
+} hs_block_arg;
+int hs_sens_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const hs_block_arg* W, int64_t itmax, int pattern, double* G, double* X, int64_t ldx,
+              double* Lam, int64_t ldl);
+int hs_sens_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const hs_block_arg* W, int64_t itmax, int pattern, double* G, double* X, int64_t ldx,
+              double* Lam, int64_t ldl); /* interleaved (re, im) */
+int hs_sens_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const hs_block_arg* W, int64_t itmax, int pattern, double* dG, double* dX,
+                  int64_t ldx, double* dLam, int64_t ldl, void* stream);
+int hs_sens_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const hs_block_arg* W, int64_t itmax, int pattern, double* dG, double* dX,
+                  int64_t ldx, double* dLam, int64_t ldl, void* stream);
+int hs_misfit_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const int64_t* rows, int64_t nrows, const double* D, int64_t ldd, int64_t itmax,
+                int pattern, double* J, double* R, int64_t ldr, double* G);
+int hs_misfit_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const int64_t* rows, int64_t nrows, const double* D, int64_t ldd, int64_t itmax,
+                int pattern, double* J, double* R, int64_t ldr, double* G);
+int hs_misfit_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const int64_t* rows, int64_t nrows, const double* dD, int64_t ldd,
+                    int64_t itmax, int pattern, double* dJ, double* dR, int64_t ldr, double* dG, void* stream);
+int hs_misfit_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const int64_t* rows, int64_t nrows, const double* dD, int64_t ldd,
+                    int64_t itmax, int pattern, double* dJ, double* dR, int64_t ldr, double* dG, void* stream);
+/* the last hs_sens_* / hs_misfit_* call of the handle: out8 = {seconds on the device in total, of the forward solves, of the adjoint solves,
+ * of the reduction (staging, the misfit kernel and the copies of requested blocks included), column groups, stored entries x columns
+ * reduced, values moved between host and device (0 for the _dev_ forms), workspace bytes} */
+int hs_sens_info(const hs_handle* F, double* out8);
+
 /* ---- accuracy tools: norm and condition estimates, refined solves with error bounds (hs_condest.hip) --------------------------
  * opnorm(A, 1), opnorm(A, Inf) of the handle's A (the values of the last hs_numeric_begin); p = 1 or 0 (= Inf).  The first call that needs
  * rows of A (p = 0, hs_condest p = 0, hs_ldiv_refine_* with trans = 0) builds a CSR map of A's pattern on the device and keeps it in the handle. */
