@@ -1,5 +1,7 @@
-// hs_condest.h -- what the accuracy tools of hs_condest.hip (norm and condition estimates, refined solves) read from a factorization handle,
-// and what hs_refine_block.hip shares with them.  hs_api.hip owns the handle; the two calls below are the whole interface to it.
+// hs_condest.h -- what the accuracy tools (hs_condest.hip: norm and condition estimates, refined solves; hs_refine_block.hip: refined solves
+// for a block in lockstep) read from a factorization handle: hs_api.hip owns the handle, and the two calls below are the whole interface to
+// it.  Behind HS_CONDEST_KERNELS: what the two files share besides the estimator (hs_normest.h) -- scalar helpers, the +-1 hash, the xGERFS
+// ratio, device buffers, the op(F)^-1 code table, the rows of op(A), and the argument checks of the refined solves.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -104,7 +106,7 @@ __host__ __device__ inline uint64_t sm64(uint64_t x) {  // splitmix64 finaliser
 }
 // the +-1 column `col` of draw `salt` (0: the start block; k * 64 + attempt: a re-drawn sign column of iteration k): entry i = low bit of
 // splitmix64(key ^ i)
-inline uint64_t col_key(int64_t seed, int col, int salt) { return sm64(sm64((uint64_t)seed) ^ ((uint64_t)salt << 8) ^ (uint64_t)col); }
+__host__ __device__ inline uint64_t col_key(int64_t seed, int col, int salt) { return sm64(sm64((uint64_t)seed) ^ ((uint64_t)salt << 8) ^ (uint64_t)col); }
 __device__ inline double pm1(uint64_t key, int64_t i) { return (sm64(key ^ (uint64_t)i) & 1) ? -1.0 : 1.0; }
 
 // the xGERFS ratio |r_i| / w_i with its safe1 / safe2 guard
@@ -150,6 +152,79 @@ constexpr double CE_SAFMIN = 2.2250738585072014e-308;  // dlamch('Safe minimum')
 int64_t max_col(const HsHandleView& v, hipStream_t s);
 template <class T>
 CsrMap* csr_of(const HsHandleView& v, hipStream_t s);
+
+// ---- op(F)^-1 by code ---------------------------------------------------------------------------------------------------------------------
+// 0 = F^-1, 1 = F^-T, 2 = F^-H, 3 = conj(F)^-1; adj() gives the code of the adjoint.  A solve takes trans = 0, 1, 2: real T folds 2 and 3 into
+// 1 and 0, and code 3 is conjugate, solve with trans = 0, conjugate.
+inline int adj(int code) { return code == 0 ? 2 : code == 1 ? 3 : code == 2 ? 0 : 1; }
+struct OpDir {
+  int trans;  // of the solve
+  bool conj;  // conjugate the block before and after it
+};
+template <class T>
+inline OpDir op_dir(int code) {
+  if (sizeof(T) == 8) code = (code == 2) ? 1 : (code == 3 ? 0 : code);
+  return {code == 3 ? 0 : code, code == 3};
+}
+
+// ---- the rows of op(A) ------------------------------------------------------------------------------------------------------------------
+// Row i of op(A) is row i of the CSR map (op = N) or column i of the CSC arrays (op = T, H: cj conjugates on load); nz = its longest row + 1
+// and the safe1 / safe2 guards of xGERFS go with it.
+template <class T>
+struct OpRows {
+  const int64_t* ptr;
+  const int32_t* idx;
+  const T* val;
+  int64_t maxlen;
+  bool cj;
+  double nz;
+  ResidArgs g;
+};
+template <class T>
+OpRows<T> op_rows(const HsHandleView& v, int trans, hipStream_t s) {
+  OpRows<T> r;
+  if (trans == 0) {
+    CsrMap* m = csr_of<T>(v, s);
+    r.ptr = m->rowptr;
+    r.idx = m->colind;
+    r.val = (const T*)m->valr;
+    r.maxlen = m->maxrow;
+  } else {
+    r.ptr = v.colptr;
+    r.idx = v.rowval;
+    r.val = (const T*)v.nz;
+    r.maxlen = max_col(v, s);
+  }
+  r.cj = trans == 2 && sizeof(T) == 16;
+  r.nz = (double)(r.maxlen + 1);
+  r.g = ResidArgs{r.nz * CE_SAFMIN, r.nz * CE_SAFMIN / CE_EPS};
+  return r;
+}
+
+// ---- argument checks of the refined solves: refuse, never drop ---------------------------------------------------------------------------
+// hs_ldiv_refine_* and hs_ldiv_refine_block_* refuse the same things with the same words (fn names the entry point), in the same order; what
+// differs -- ranks, a host-side plan, the HSS-D node, the probe of the block solve -- stays with each entry point, between these three.
+inline HsHandleView view_of(hs_handle* F, const char* fn) {
+  if (!F) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
+  HsHandleView v;
+  hs_handle_view(F, &v);
+  return v;
+}
+template <class T>
+void check_refine_args(const char* fn, const HsHandleView& v, int trans, const T* X, int64_t ldx, const T* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
+                       const double* berr, const int64_t* steps) {
+  if ((v.is_complex != 0) != (sizeof(T) == 16)) CE_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and B differ", fn);
+  if (trans < 0 || trans > 2) CE_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
+  if (n != v.n || nrhs < 0 || ldx < n || ldb < n)
+    CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: B has %lld rows (ldx %lld, ldb %lld, nrhs %lld), F is %lld x %lld", fn, (long long)n, (long long)ldx,
+            (long long)ldb, (long long)nrhs, (long long)v.n, (long long)v.n);
+  if (itmax < 0) CE_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: %s: itmax = %lld < 0", fn, (long long)itmax);
+  if (nrhs > 0 && (!X || !B || !berr || !steps)) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: X, B, berr and steps must not be NULL", fn);
+}
+template <class T>
+void check_no_alias(const char* fn, const T* X, int64_t ldx, const T* B, int64_t ldb, int64_t nrhs) {
+  if (nrhs > 0 && X < B + (size_t)ldb * nrhs && B < X + (size_t)ldx * nrhs) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: X may not alias B", fn);
+}
 
 }  // namespace hs_ce
 #endif  // HS_CONDEST_KERNELS

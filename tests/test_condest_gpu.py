@@ -84,6 +84,49 @@ def test_estimator_matches_the_mirror(hs, kind, shape, nmax):
     assert hs.condest(F, 1) == hs.condest(F, 1)
 
 
+def _replaced_values(A, cplx):
+    """A's pattern with standard normal values and 3 added to the diagonal.  With the PDE values the estimator stops after 3-4 half-steps with
+    the exact norm and never selects rows against a non-empty index history; with these it runs 4 half-steps for every op and t below, so the
+    history-exclusion branch of the top-t selection runs once."""
+    rng = np.random.default_rng(1)
+    vals = rng.standard_normal(A.nnz)
+    if cplx:
+        vals = vals + 1j * rng.standard_normal(A.nnz)
+    A2 = A.copy()
+    A2.data[:] = vals
+    A2.setdiag(A2.diagonal() + 3.0)
+    assert A2.nnz == A.nnz
+    return A2
+
+
+# n = 9: one more row than t = 8, the candidate lists are mostly sentinels; n = 810; n = 2250 > 2048 rows per workgroup: two workgroups'
+# candidate lists are merged
+WIDE = [((3, 3), 100), ((30, 27), 40), ((50, 45), 40)]
+
+
+@pytest.mark.parametrize("replaced", [False, True], ids=["pde", "randn"])
+@pytest.mark.parametrize("kind", ["convdiff", "convdiff_helmholtz"])
+@pytest.mark.parametrize("shape,nmax", WIDE)
+def test_wide_estimator_matches_the_mirror(hs, shape, nmax, kind, replaced):
+    """t = 8 with the largest itmax (the wide instantiation of the estimator kernels) and t = 2 at the same itmax, against the mirror."""
+    P = prepare(hs, shape, kind=kind, nmax=nmax, rhs="randn")
+    cplx = kind == "convdiff_helmholtz"
+    A = _replaced_values(P["A"], cplx) if replaced else P["A"]
+    n = A.shape[0]
+    F = hs.factor(A, P["nd"], P["nd_loc"], swlevel=0)
+    try:
+        for trans, op in ((0, F), (1, hs.transpose(F)), (2, hs.adjoint(F))):
+            for t in (8, 2):
+                est, ns = hs.opnormestinv(op, t=t, itmax=16, nsolves=True)
+                ref, nref = M.normestinv(lambda X, tr: F.solve(X, tr), n, trans=trans, t=t, itmax=16, seed=123, cplx=cplx)
+                print(f"{kind} {shape} replaced={replaced} trans={trans} t={t}: est {est:.17g} mirror {ref:.17g} nsolves {ns} mirror {nref}")
+                assert est == pytest.approx(ref, rel=1e-10), (trans, t)
+                assert ns == nref, (trans, t)
+                assert hs.opnormestinv(op, t=t, itmax=16, nsolves=True) == (est, ns)  # bitwise repeatable
+    finally:
+        F.free()
+
+
 COMPRESSED = [("convdiff", (20, 20, 20), 200, (0, 1)), ("convdiff_helmholtz", (20, 20, 20), 200, (0, 1, 2))]
 CKW = dict(swlevel=2, swsize=8, atol=1e-6, rtol=1e-6, leafsize=32)
 
