@@ -79,6 +79,7 @@ EXPORTS = [
     "hs_ldiv_t_d", "hs_ldiv_t_z", "hs_ldiv_dev_t_d", "hs_ldiv_dev_t_z",
     "hs_ldiv_block_d", "hs_ldiv_block_z", "hs_ldiv_block_dev_d", "hs_ldiv_block_dev_z", "hs_ldiv_block_info", "hsk_multi_prob_d", "hsk_multi_prob_z",
     "hs_ldiv_block_t_d", "hs_ldiv_block_t_z", "hs_ldiv_block_dev_t_d", "hs_ldiv_block_dev_t_z", "hsk_multi_prob_t_d", "hsk_multi_prob_t_z",
+    "hs_ldiv_ulv_d", "hs_ldiv_ulv_z", "hs_ldiv_ulv_dev_d", "hs_ldiv_ulv_dev_z",
     "hs_ldiv_sparse_d", "hs_ldiv_sparse_z", "hs_ldiv_sparse_dev_d", "hs_ldiv_sparse_dev_z", "hs_ldiv_sparse_plan", "hs_ldiv_sparse_info",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
@@ -94,7 +95,7 @@ EXPORTS = [
     "hs_comm_unique_id", "hs_comm_create_rccl", "hs_comm_create_host", "hs_comm_free", "hs_comm_kind", "hs_comm_selftest", "hs_comm_bandwidth", "hs_set_comm",
     "hs_symbolic_from_elimtree", "hs_symbolic_from_graph", "hs_symbolic_size", "hs_symbolic_perm", "hs_symbolic_tree", "hs_symbolic_free",
     "hs_hss_options_default", "hs_hss_compress_d", "hs_hss_compress_z", "hs_hss_compress_ex_d", "hs_hss_compress_ex_z", "hs_hss_compress_lru_d", "hs_hss_compress_lru_z", "hs_hss_compress_lru_multi_d", "hs_hss_compress_lru_multi_z", "hs_hss_set_stream", "hs_hss_rank", "hs_hss_size", "hs_hss_samples", "hs_hss_num_nodes",
-    "hs_hss_node_info", "hs_hss_node_data", "hs_hss_getindex", "hs_hss_basis", "hs_hss_expand", "hs_hss_mul", "hs_hss_mul_t", "hs_hss_child", "hs_hss_factor", "hs_hss_ldiv", "hs_hss_time", "hs_hss_trim", "hs_hss_free", "hs_node_schur_hss",
+    "hs_hss_node_info", "hs_hss_node_data", "hs_hss_getindex", "hs_hss_basis", "hs_hss_expand", "hs_hss_mul", "hs_hss_mul_t", "hs_hss_child", "hs_hss_factor", "hs_hss_ldiv", "hs_hss_ldiv_t", "hsk_ulv_t_group_d", "hsk_ulv_t_group_z", "hs_hss_time", "hs_hss_trim", "hs_hss_free", "hs_node_schur_hss",
     "hs_hss_offdiag", "hs_hss_bytes", "hs_hss_prune_leaves", "hs_hss_compatible", "hs_hss_depth", "hs_hss_compress_blockop_d", "hs_hss_compress_blockop_z", "hs_hss_blockop_apply",
     "hsk_gemm_d", "hsk_gemm_z", "hsk_lowrank_d", "hsk_lowrank_z", "hsk_front_factor_d", "hsk_front_factor_z", "hsk_front_batch_d", "hsk_front_batch_z", "hsk_mfma_f64_peak", "hsk_mfma_f64_peak_random", "hsk_flow_pingpong_us", "hsk_bisect_perm",
     "hs_probs_stats_mode", "hs_probs_stats", "hs_trim", "hs_stream_order",
@@ -160,6 +161,12 @@ def lib():
         f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
         f.restype = C.c_int
     for f in (L.hs_ldiv_block_dev_t_d, L.hs_ldiv_block_dev_t_z):
+        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
+        f.restype = C.c_int
+    for f in (L.hs_ldiv_ulv_d, L.hs_ldiv_ulv_z):
+        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
+        f.restype = C.c_int
+    for f in (L.hs_ldiv_ulv_dev_d, L.hs_ldiv_ulv_dev_z):
         f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
         f.restype = C.c_int
     L.hs_ldiv_block_info.argtypes = [vp, p_f64]
@@ -411,6 +418,11 @@ def lib():
     L.hs_hss_factor.restype = C.c_int
     L.hs_hss_ldiv.argtypes = [vp, vp, i64, i64, C.c_int]
     L.hs_hss_ldiv.restype = C.c_int
+    L.hs_hss_ldiv_t.argtypes = [vp, C.c_int, vp, i64, i64, C.c_int]
+    L.hs_hss_ldiv_t.restype = C.c_int
+    for f in (L.hsk_ulv_t_group_d, L.hsk_ulv_t_group_z):
+        f.argtypes = [i64, p_i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int]
+        f.restype = C.c_int
     L.hs_hss_time.argtypes = [vp, C.c_int]
     L.hs_hss_time.restype = C.c_double
     L.hs_hss_free.argtypes = [vp]

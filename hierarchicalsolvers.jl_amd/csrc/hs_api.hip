@@ -1765,6 +1765,10 @@ void hs_multi_view(hs_handle* h, HsMultiView* v) {
   for (size_t lv = 0; lv < h->levels.size(); ++lv) {
     const LevelH& L = h->levels[lv];
     HsMultiLevel& M = v->levels[lv];
+    for (int id : L.mine) {
+      const NodeH& x = h->nodes[id];
+      if ((x.hssd || (x.mf && !x.mfd)) && x.hss && x.ni > 0) M.hss.push_back(id);  // served by HsMultiView::hss_front (hs_ldiv_ulv_*)
+    }
     if (L.mine.empty() || L.maxni == 0 || !h->d_solve) continue;
     M.sn = (const char*)h->d_solve + L.desc_off * ssz;
     M.nfronts = (int)L.mine.size();
@@ -1774,7 +1778,11 @@ void hs_multi_view(hs_handle* h, HsMultiView* v) {
     for (int id : L.mine) {
       const NodeH& x = h->nodes[id];
       const bool lowrank = x.compressed || x.mf;
-      M.fronts.push_back({x.ni, x.nb, lowrank ? 0 : 1, x.woff});
+      const bool hssfront = x.hssd || (x.mf && !x.mfd);
+      if (hssfront)
+        M.fronts.push_back({0, 0, 0, x.woff});  // its SolveNode carries ni = 0: no dense work, no boundary segment
+      else
+        M.fronts.push_back({x.ni, x.nb, lowrank ? 0 : 1, x.woff});
       M.node.push_back(id);
       M.maxnb = std::max(M.maxnb, x.nb);
       if (x.ni > 0) {
@@ -1783,7 +1791,9 @@ void hs_multi_view(hs_handle* h, HsMultiView* v) {
       }
       v->wtotal = std::max(v->wtotal, x.woff + x.ni);
       v->sum_fac += (double)x.ni * x.ni + 2.0 * x.ni * x.nb;
-      if ((x.compressed || x.mfd) && (x.lrL || x.lrR)) M.lr.push_back({x.lrL, x.lrR, x.woff, x.batch_pos});
+      // (every front of a compressed level carries the flag, the ones with an HSS interior block too: their transforms belong to the hook of
+      // hs_ldiv_ulv_*, not to the level's low-rank products, which would read a y the dense sweeps never wrote and a boundary segment they do not have)
+      if ((x.compressed || x.mfd) && !hssfront && (x.lrL || x.lrR)) M.lr.push_back({x.lrL, x.lrR, x.woff, x.batch_pos});
     }
     M.wbase = std::max(lo, 0LL);
     M.wrows = std::max(hi - M.wbase, 0LL);
@@ -1887,6 +1897,205 @@ static void ldiv_block_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const 
   hs_multi_view(h, &v);
   if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
   hs_solve_multi_run_t<T>(v, trans, dC, ldc, nrhs, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// hs_ldiv_ulv_*: C = op(F)^-1 B for a block, fronts whose interior block D is an HSS matrix included (hs_options.hss_d, mf = 2, 3)
+// ------------------------------------------------------------------------------------------------
+// Such a front is served per chunk of columns on the caller's column-major block, between the grouped launches of its level's other fronts
+// (HsMultiView::hss_front).  With t = B[int, :], Abi ~ C_L Z_L, Aib ~ C_R Z_R and W = D^-1 C_R (x.hW):
+//   trans = 0   forward:  t = D^-1 t,  B[int] = t,  B[bnd] -= C_L (Z_L t)            backward:  B[int] = t - W (Z_R B[bnd])
+//   trans = 1,2 forward:  B[bnd] -= op(Z_R)^T (op(W)^T t)   (no solve with D)        backward:  B[int] = op(D)^-T (t - op(Z_L)^T (op(C_L)^T B[bnd]))
+// op(D)^-T is ONE transposed ULV solve (hs_hss_ldiv_t), or for the 2 x 2 block form (x.mfb: hss = A11, hss2 = S22, W12 = A11^-1 C12):
+//   b2 -= op(Z12)^T (op(W12)^T b1);  x2 = op(S22)^-T b2;  b1 -= op(Z21)^T (op(C21)^T x2);  x1 = op(A11)^-T b1.
+// t lives in B[int] between the sweeps: the interior rows of a front belong to it alone.  Products with a transposed factor run on the
+// grouped kernel of kernels_ulv_t.hip, the others on the MFMA GEMM.
+#include "hs_ulv_t.h"
+template <class T>
+struct UlvCtx {
+  hs_handle* h;
+  T *t, *xb, *u;           // ni x kc, nb x kc, r x kc (column-major, ld ldt / ldx / ldu)
+  int ldt, ldx, ldu;
+  void* desc;              // device: one job description at a time
+};
+template <class T>
+static void ulv_front(void* ctx_, int id, int sweep, int trans, void* B_, long long ldb, int kc, hipStream_t s) {
+  UlvCtx<T>& w = *(UlvCtx<T>*)ctx_;
+  hs_handle* h = w.h;
+  const NodeH& x = h->nodes[id];
+  T* B = (T*)B_;
+  const int ni = x.ni, nb = x.nb;
+  const int* iidx = h->d_int + x.off_fidx;
+  const int* bidx = iidx + ni;
+  const LowRank<T>* lrL = (const LowRank<T>*)x.lrL;
+  const LowRank<T>* lrR = (const LowRank<T>*)x.lrR;
+  const int rL = (nb > 0 && lrL) ? lrL->r : 0, rR = (nb > 0 && lrR && x.hW) ? lrR->r : 0;
+  const int cj = (trans == 2 && sizeof(T) == 16) ? 1 : 0;
+  // C = Cin - op(A)^T X / C = op(A)^T X, A stored K x M
+  auto prod_t = [&](const T* A, int lda, int K, int M, const T* X, int ldx, T* C, int ldc, bool minus) {
+    if (K <= 0 || M <= 0) return;
+    UlvTJob<T> j{A, X, minus ? C : nullptr, C, M, K, kc, lda, ldx, ldc, ldc, cj, HS_ULVT_FULL};
+    HS_HIP(hipMemcpyAsync(w.desc, &j, sizeof j, hipMemcpyHostToDevice, s));
+    HS_HIP(hipStreamSynchronize(s));
+    launch_ulv_t<T>((const UlvTJob<T>*)w.desc, 1, M, kc, s);
+  };
+  // C = A X / C -= A X, A stored M x K
+  auto prod_n = [&](const T* A, int lda, int M, int K, const T* X, int ldx, T* C, int ldc, bool minus) {
+    if (K <= 0 || M <= 0) return;
+    GemmProb<T> g{A, X, C, M, kc, K, lda, ldx, ldc};
+    HS_HIP(hipMemcpyAsync(w.desc, &g, sizeof g, hipMemcpyHostToDevice, s));
+    HS_HIP(hipStreamSynchronize(s));
+    launch_gemm_probs<T>((const GemmProb<T>*)w.desc, 1, M, kc, minus ? 1 : 0, s);
+  };
+  auto hsolve_t = [&](void* H, T* b) {
+    int st = hs_hss_set_stream((hs_hss*)H, (void*)s);
+    if (st == 0) st = hs_hss_ldiv_t((hs_hss*)H, trans, (double*)b, w.ldt, kc, 1);
+    if (st != 0) throw HsError{st};
+  };
+  T *t = w.t, *xb = w.xb, *u = w.u;
+  if (trans == 0) {
+    if (sweep == 0) {
+      launch_ulv_rows<T>(iidx, ni, kc, B, ldb, t, w.ldt, 0, s);
+      hss_d_solve<T>(h, x, t, w.ldt, kc, s);
+      launch_ulv_rows<T>(iidx, ni, kc, t, w.ldt, B, ldb, 1, s);
+      if (rL > 0) {
+        prod_n(lrL->Z, lrL->ldz, rL, ni, t, w.ldt, u, w.ldu, false);
+        launch_ulv_rows<T>(bidx, nb, kc, B, ldb, xb, w.ldx, 0, s);
+        prod_n(lrL->Cd, lrL->ldc, nb, rL, u, w.ldu, xb, w.ldx, true);
+        launch_ulv_rows<T>(bidx, nb, kc, xb, w.ldx, B, ldb, 1, s);
+      }
+    } else if (rR > 0) {
+      launch_ulv_rows<T>(bidx, nb, kc, B, ldb, xb, w.ldx, 0, s);
+      prod_n(lrR->Z, lrR->ldz, rR, nb, xb, w.ldx, u, w.ldu, false);
+      launch_ulv_rows<T>(iidx, ni, kc, B, ldb, t, w.ldt, 0, s);
+      prod_n((const T*)x.hW, x.hldw, ni, rR, u, w.ldu, t, w.ldt, true);
+      launch_ulv_rows<T>(iidx, ni, kc, t, w.ldt, B, ldb, 1, s);
+    }
+    return;
+  }
+  if (sweep == 0) {
+    if (rR > 0) {
+      launch_ulv_rows<T>(iidx, ni, kc, B, ldb, t, w.ldt, 0, s);
+      prod_t((const T*)x.hW, x.hldw, ni, rR, t, w.ldt, u, w.ldu, false);   // u = op(W)^T t
+      launch_ulv_rows<T>(bidx, nb, kc, B, ldb, xb, w.ldx, 0, s);
+      prod_t(lrR->Z, lrR->ldz, rR, nb, u, w.ldu, xb, w.ldx, true);         // B[bnd] -= op(Z_R)^T u
+      launch_ulv_rows<T>(bidx, nb, kc, xb, w.ldx, B, ldb, 1, s);
+    }
+    return;
+  }
+  launch_ulv_rows<T>(iidx, ni, kc, B, ldb, t, w.ldt, 0, s);
+  if (rL > 0) {
+    launch_ulv_rows<T>(bidx, nb, kc, B, ldb, xb, w.ldx, 0, s);
+    prod_t(lrL->Cd, lrL->ldc, nb, rL, xb, w.ldx, u, w.ldu, false);         // u = op(C_L)^T B[bnd]
+    prod_t(lrL->Z, lrL->ldz, rL, ni, u, w.ldu, t, w.ldt, true);            // t -= op(Z_L)^T u
+  }
+  if (!x.mfb) {
+    hsolve_t(x.hss, t);
+  } else {
+    const int n1 = x.ni1, n2 = ni - x.ni1, k12 = x.bk12, k21 = x.bk21;
+    T *b1 = t, *b2 = t + n1;
+    prod_t((const T*)x.bW12, x.bldw, n1, k12, b1, w.ldt, u, w.ldu, false);
+    prod_t((const T*)x.bZ12, x.bldz12, k12, n2, u, w.ldu, b2, w.ldt, true);
+    hsolve_t(x.hss2, b2);
+    prod_t((const T*)x.bC21, x.bldc21, n2, k21, b2, w.ldt, u, w.ldu, false);
+    prod_t((const T*)x.bZ21, x.bldz21, k21, n1, u, w.ldu, b1, w.ldt, true);
+    hsolve_t(x.hss, b1);
+  }
+  launch_ulv_rows<T>(iidx, ni, kc, t, w.ldt, B, ldb, 1, s);
+}
+// everything hs_ldiv_ulv_* refuses, before any device work and before C is written; true: the handle has fronts with an HSS interior block
+static bool check_solve_ulv(hs_handle* h, int trans, bool isz, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
+  check_handle(h);
+  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_ldiv_ulv_*: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", trans);
+  if (h->nranks > 1)  // (before the state of the handle: a host-side plan over several ranks is refused for its ranks)
+    HS_FAIL(HS_ERR_UNSUPPORTED, 0, "hs_ldiv_ulv_*: block solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", h->nranks);
+  check_solve_args(h, isz, ldc, ldb, n, nrhs);
+  bool any = false;
+  for (size_t i = 0; i < h->nodes.size(); ++i) {
+    const NodeH& x = h->nodes[i];
+    if (!(x.mine && (x.hssd || (x.mf && !x.mfd)))) continue;
+    any = true;
+    if (!x.hss || (x.mfb && !x.hss2)) HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_ldiv_ulv_*: node %d has no eliminated interior block (incomplete factorization)", (int)i);
+    bool nodense = false;
+    if (x.nb > 0 && x.lrL) {
+      if (isz) nodense = ((const LowRank<cplx>*)x.lrL)->r > 0 && !((const LowRank<cplx>*)x.lrL)->Cd;
+      else nodense = ((const LowRank<double>*)x.lrL)->r > 0 && !((const LowRank<double>*)x.lrL)->Cd;
+    }
+    if (nodense)
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_ldiv_ulv_*: the low-rank transform of node %d does not keep its dense factor C (only the packed sketch)", (int)i);
+  }
+  return any;
+}
+template <class T>
+static void ulv_run(hs_handle* h, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+  HsMultiView v;
+  hs_multi_view(h, &v);
+  const int KC = hs_ldiv_block_cols();
+  long long mni = 1, mnb = 1, mr = 1;
+  for (const HsMultiLevel& L : v.levels)
+    for (int id : L.hss) {
+      const NodeH& x = h->nodes[id];
+      mni = std::max<long long>(mni, x.ni);
+      mnb = std::max<long long>(mnb, x.nb);
+      if (x.lrL) mr = std::max<long long>(mr, ((const LowRank<T>*)x.lrL)->r);
+      if (x.lrR) mr = std::max<long long>(mr, ((const LowRank<T>*)x.lrR)->r);
+      mr = std::max<long long>(mr, std::max(x.bk12, x.bk21));
+    }
+  UlvCtx<T> w;
+  w.h = h;
+  w.ldt = (int)((mni + 1) / 2 * 2); w.ldx = (int)((mnb + 1) / 2 * 2); w.ldu = (int)((mr + 1) / 2 * 2);
+  const size_t el = ((size_t)w.ldt + w.ldx + w.ldu) * KC + 64;
+  const size_t bytes = el * sizeof(T) + 256;
+  char* slab = (char*)hs_scratch_take(bytes, "ULV block solve front scratch");
+  w.desc = slab;
+  w.t = (T*)(slab + 256);
+  w.xb = w.t + (size_t)w.ldt * KC;
+  w.u = w.xb + (size_t)w.ldx * KC;
+  static_assert(sizeof(UlvTJob<T>) <= 256 && sizeof(GemmProb<T>) <= 256, "job descriptions fit the head of the slab");
+  v.hss_front = &ulv_front<T>;
+  v.hss_ctx = &w;
+  try {
+    if (trans == 0)
+      hs_solve_multi_run<T>(v, dC, ldc, nrhs, s);
+    else
+      hs_solve_multi_run_t<T>(v, trans, dC, ldc, nrhs, s);
+    HS_HIP(hipStreamSynchronize(s));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    hs_scratch_give(slab, bytes);
+    throw;
+  }
+  hs_scratch_give(slab, bytes);
+}
+template <class T>
+static void ldiv_ulv_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return ldiv_block_host_t<T>(h, trans, C, ldc, B, ldb, n, nrhs);
+  if (nrhs == 0) return;
+  if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_ulv_*: null block");
+  hipStream_t s = h->stream;
+  const size_t bytes = (size_t)n * nrhs * sizeof(T);
+  T* d = (T*)hs_scratch_take(bytes, "block solve right-hand sides");
+  try {
+    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
+    ulv_run<T>(h, trans, d, n, nrhs, s);
+    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    hs_scratch_give(d, bytes);
+    throw;
+  }
+  hs_scratch_give(d, bytes);
+  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
+}
+template <class T>
+static void ldiv_ulv_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return ldiv_block_dev_t<T>(h, trans, dC, ldc, dB, ldb, n, nrhs, stream);
+  if (nrhs == 0) return;
+  if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_ulv_dev_*: null block");
+  hipStream_t s = (hipStream_t)stream;
+  if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
+  ulv_run<T>(h, trans, dC, ldc, nrhs, s);  // (waits for s: the HSS solves of the fronts synchronise it anyway)
 }
 
 // the handle as hs_condest.hip sees it (hs_condest.h)
@@ -2131,6 +2340,18 @@ extern "C" int hs_ldiv_block_dev_t_d(hs_handle* F, int trans, double* dC, int64_
 }
 extern "C" int hs_ldiv_block_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   HS_GUARD(ldiv_block_dev_t<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
+}
+extern "C" int hs_ldiv_ulv_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  HS_GUARD(ldiv_ulv_host<double>(F, trans, C, ldc, B, ldb, n, nrhs));
+}
+extern "C" int hs_ldiv_ulv_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  HS_GUARD(ldiv_ulv_host<cplx>(F, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
+}
+extern "C" int hs_ldiv_ulv_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  HS_GUARD(ldiv_ulv_dev<double>(F, trans, dC, ldc, dB, ldb, n, nrhs, stream));
+}
+extern "C" int hs_ldiv_ulv_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  HS_GUARD(ldiv_ulv_dev<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
 }
 extern "C" int hs_ldiv_block_info(const hs_handle* F, double* out6) {
   HS_GUARD(if (!F || !out6) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_info: null argument");

@@ -14,6 +14,8 @@
 //   * the elimination of a level's redundant positions: the fronts' batched recursive LU (Sched::factor_fronts) on
 //     fronts [R; S] -- LF = [X_RR; X_SR], UR = X_RS, SB = X_SS -> Schur complement on the skeleton;
 //   * triangular solves with blocks of right-hand sides: the fronts' TRSM-by-inverse-blocks (laswp / trsm_rec / utrsm_rec).
+//   * the transposed / adjoint solve (hs_hss_ldiv_t): every step a product C = Cin - op(A)^T X with a stored block read along its columns,
+//     the 32 x 32 inverse diagonal blocks included: the grouped kernel of kernels_ulv_t.hip.
 // New kernels here are the HBM-bound movers: row gather / scatter, indexed sub-matrix gather (also the transposes),
 // the interpolation matrices T = L21 * L11^-1 from the packed LU of the samples, index composition, Gaussian fill.
 #include <exception>
@@ -31,6 +33,7 @@
 #include "../../include/hs_hss.h"
 #include "hs_lowrank.h"
 #include "hs_sched.h"
+#include "hs_ulv_t.h"
 
 namespace {
 
@@ -2364,6 +2367,173 @@ void hss_ldiv_p(HssT<T>& H, T* B, int ldb, int q) {
   HSS_HIP(hipStreamSynchronize(s));
 }
 
+// ---- H^-T B / H^-H B from the same stored factors (hs_hss_ldiv_t; DESIGN.md, "transposed ULV solves") ----------------------------------
+// Every non-root node keeps ONE skeleton for rows and columns, so E^T = F and F^T = E for E = [I -T; 0 I], F = [I 0; -T^T I] and the local
+// matrix M = E^-1 X F^-1 has M^T = E^-1 X^T F^-1: the transposed elimination is the same tree walk with every stored block read along its
+// other index -- the grouped product C = Cin - op(A)^T X of kernels_ulv_t.hip, one launch per level and step.
+template <class T>
+void run_ulv_t(Pool& tmp, std::vector<UlvTJob<T>>& jobs, hipStream_t s) {
+  std::vector<UlvTJob<T>> live;
+  int mM = 0, mN = 0;
+  for (auto& j : jobs)
+    if (j.M > 0 && j.K > 0 && j.N > 0) {
+      live.push_back(j);
+      mM = std::max(mM, j.M);
+      mN = std::max(mN, j.N);
+    }
+  jobs.clear();
+  if (live.empty()) return;
+  UlvTJob<T>* d = upload(tmp, live, s);
+  for (size_t b = 0; b < live.size(); b += 32768) launch_ulv_t<T>(d + b, (int)std::min<size_t>(32768, live.size() - b), mM, mN, s);
+}
+// a front and two blocks of ni x q: the triangular sweeps read `in` (and use it up) and leave the result in `out`
+template <class T>
+struct UlvTri {
+  const NodeDesc<T>* f;
+  T* in;
+  int ldi;
+  T* out;
+  int ldo;
+};
+// out = op(U)^-T in (upper = true: U^T is lower triangular, 32-blocks first to last) or out = op(L)^-T in (L^T is upper triangular, last to
+// first), for a batch of fronts: per 32-block one launch with the transposed inverse diagonal blocks (invU / invL of the descriptors) and one
+// with the row panel of U right of / the column panel of L above the block
+template <class T>
+void ulv_t_tri(Pool& tmp, const std::vector<UlvTri<T>>& v, int q, int cj, bool upper, hipStream_t s) {
+  int maxni = 0;
+  for (auto& e : v) maxni = std::max(maxni, e.f->ni);
+  const int nblk = (maxni + HS_PB - 1) / HS_PB;
+  std::vector<UlvTJob<T>> diag, pan;
+  for (int step = 0; step < nblk; ++step) {
+    const int blk = upper ? step : nblk - 1 - step;
+    for (auto& e : v) {
+      const NodeDesc<T>& f = *e.f;
+      const int c0 = blk * HS_PB;
+      if (c0 >= f.ni) continue;
+      const int wl = std::min(HS_PB, f.ni - c0), c1 = c0 + wl;
+      const T* inv = (upper ? f.invU : f.invL) + (size_t)blk * HS_PB * HS_PB;
+      diag.push_back(UlvTJob<T>{inv, e.in + c0, nullptr, e.out + c0, wl, wl, q, HS_PB, e.ldi, 0, e.ldo, cj, upper ? HS_ULVT_UPPER : HS_ULVT_LOWER});
+      if (upper) {
+        if (c1 < f.ni)  // in[c1:] -= op(U[c0:c1, c1:])^T out[c0:c1]
+          pan.push_back(UlvTJob<T>{f.LF + c0 + (size_t)c1 * f.ldl, e.out + c0, e.in + c1, e.in + c1, f.ni - c1, wl, q, f.ldl, e.ldo, e.ldi, e.ldi, cj, HS_ULVT_FULL});
+      } else {
+        if (c0 > 0)  // in[:c0] -= op(L[c0:c1, :c0])^T out[c0:c1]
+          pan.push_back(UlvTJob<T>{f.LF + c0, e.out + c0, e.in, e.in, c0, wl, q, f.ldl, e.ldo, e.ldi, e.ldi, cj, HS_ULVT_FULL});
+      }
+    }
+    run_ulv_t(tmp, diag, s);
+    run_ulv_t(tmp, pan, s);
+  }
+}
+
+// B <- op(H)^-T B in the tree's own order, op = conj when cj
+template <class T>
+void hss_ldiv_t_p(HssT<T>& H, T* B, int ldb, int q, int cj) {
+  hipStream_t s = H.s;
+  auto& nd = H.nd;
+  const int N = (int)nd.size();
+  Pool tmp(global_cache());
+  std::vector<RowJob<T>> rows;
+  std::vector<UlvTJob<T>> j1, j2;
+  // the last block: M0^T x = b with P M0 = L0 U0, i.e. x = P^T op(L0)^-T op(U0)^-T b; `b` is used up, `z` is scratch, the result goes to b
+  auto root = [&](T* b, int ld) {
+    const int m = H.root_m, ldz = ev(m);
+    T* z = tmp.get<T>((size_t)ldz * q);
+    std::vector<UlvTri<T>> v{UlvTri<T>{&H.rootfd, b, ld, z, ldz}};
+    ulv_t_tri(tmp, v, q, cj, true, s);
+    T* w = tmp.get<T>((size_t)ldz * q);
+    v[0] = UlvTri<T>{&H.rootfd, z, ldz, w, ldz};
+    ulv_t_tri(tmp, v, q, cj, false, s);
+    rows.push_back(RowJob<T>{w, ldz, b, ld, H.rootfd.rperm, m, q, ROW_SCATTER});  // x[rperm[i]] = w[i]
+    run_rows(tmp, rows, s);
+  };
+  if (nd[0].left < 0) {
+    root(B, ldb);
+    HSS_HIP(hipStreamSynchronize(s));
+    return;
+  }
+  std::vector<T*> BH(N, nullptr), YR(N, nullptr), ZR(N, nullptr);
+  std::vector<int> ldh(N, 0), ldy(N, 0);
+  for (int i = 0; i < N; ++i) {
+    if (nd[i].left >= 0) {
+      ldh[i] = ev(nd[i].m);
+      BH[i] = tmp.get<T>((size_t)ldh[i] * q);
+    }
+    if (i != 0) {
+      ldy[i] = ev(nd[i].m - nd[i].r);
+      YR[i] = tmp.get<T>((size_t)ldy[i] * q);
+      ZR[i] = tmp.get<T>((size_t)ldy[i] * q);
+    }
+  }
+  std::vector<UlvTri<T>> tri;
+  // forward: leaves to root
+  for (int lv = H.nlev - 1; lv >= 1; --lv) {
+    for (int i : H.lev[lv]) {
+      const HNode<T>& x = nd[i];
+      const int par = x.parent, r = x.r, nR = x.m - r;
+      const T* src = x.left < 0 ? B + x.lo : BH[i];
+      const int lds = x.left < 0 ? ldb : ldh[i];
+      T* slot = BH[par] + x.off_in_parent;
+      rows.push_back(RowJob<T>{src, lds, slot, ldh[par], x.p, r, q, ROW_GATHER});
+      if (nR > 0) {
+        rows.push_back(RowJob<T>{src, lds, YR[i], ldy[i], x.p + r, nR, q, ROW_GATHER});
+        j1.push_back(UlvTJob<T>{x.Tt, slot, YR[i], YR[i], nR, r, q, x.ldtt, ldh[par], ldy[i], ldy[i], cj, HS_ULVT_FULL});  // b_R -= op(T) b_S
+        tri.push_back(UlvTri<T>{&x.fd, YR[i], ldy[i], ZR[i], ldy[i]});                                                      // z = op(U)^-T b_R
+        j2.push_back(UlvTJob<T>{x.fd.UR, ZR[i], slot, slot, r, nR, q, x.fd.ldu, ldy[i], ldh[par], ldh[par], cj, HS_ULVT_FULL});  // b_S -= op(UR)^T z
+      }
+    }
+    run_rows(tmp, rows, s);
+    run_ulv_t(tmp, j1, s);
+    ulv_t_tri(tmp, tri, q, cj, true, s);
+    tri.clear();
+    run_ulv_t(tmp, j2, s);
+  }
+  root(BH[0], ldh[0]);
+  // backward: root to leaves (YR is free again: it takes op(L)^-T z; ZR then takes x_R = P^T of it)
+  for (int lv = 1; lv < H.nlev; ++lv) {
+    std::vector<RowJob<T>> perm;
+    for (int i : H.lev[lv]) {
+      const HNode<T>& x = nd[i];
+      const int par = x.parent, r = x.r, nR = x.m - r;
+      T* slot = BH[par] + x.off_in_parent;
+      T* dst = x.left < 0 ? B + x.lo : BH[i];
+      const int ldd = x.left < 0 ? ldb : ldh[i];
+      if (nR > 0) {
+        j1.push_back(UlvTJob<T>{x.fd.LF + nR, slot, ZR[i], ZR[i], nR, r, q, x.fd.ldl, ldh[par], ldy[i], ldy[i], cj, HS_ULVT_FULL});  // z -= op(X_SR U^-1)^T x_S
+        tri.push_back(UlvTri<T>{&x.fd, ZR[i], ldy[i], YR[i], ldy[i]});                                                                // op(L)^-T z
+        perm.push_back(RowJob<T>{YR[i], ldy[i], ZR[i], ldy[i], x.fd.rperm, nR, q, ROW_SCATTER});                                      // x_R = P^T ...
+        j2.push_back(UlvTJob<T>{x.Tm, ZR[i], slot, slot, r, nR, q, x.ldt, ldy[i], ldh[par], ldh[par], cj, HS_ULVT_FULL});             // x_S -= op(T)^T x_R
+        rows.push_back(RowJob<T>{ZR[i], ldy[i], dst, ldd, x.p + r, nR, q, ROW_SCATTER});
+      }
+      rows.push_back(RowJob<T>{slot, ldh[par], dst, ldd, x.p, r, q, ROW_SCATTER});
+    }
+    run_ulv_t(tmp, j1, s);
+    ulv_t_tri(tmp, tri, q, cj, false, s);
+    tri.clear();
+    run_rows(tmp, perm, s);
+    run_ulv_t(tmp, j2, s);
+    run_rows(tmp, rows, s);
+  }
+  HSS_HIP(hipStreamSynchronize(s));
+}
+template <class T>
+void hss_ldiv_t(HssT<T>& H, T* B, int ldb, int q, int cj) {
+  if (!H.perm) {
+    hss_ldiv_t_p(H, B, ldb, q, cj);
+    return;
+  }
+  // H ~= A[perm, perm] and the permutation is symmetric: the same gather and scatter as hss_ldiv
+  Pool tmp(global_cache());
+  const int ld = ev(H.n);
+  T* Bp = tmp.get<T>((size_t)ld * q);
+  std::vector<RowJob<T>> rows{RowJob<T>{B, ldb, Bp, ld, H.perm, H.n, q, ROW_GATHER}};
+  run_rows(tmp, rows, H.s);
+  hss_ldiv_t_p(H, Bp, ld, q, cj);
+  rows.push_back(RowJob<T>{Bp, ld, B, ldb, H.perm, H.n, q, ROW_SCATTER});
+  run_rows(tmp, rows, H.s);
+  HSS_HIP(hipStreamSynchronize(H.s));
+}
+
 struct LruArgs {  // host-side description of the optional update  - C*M*Z  (pointers in the memory space `where` names)
   const void* C = nullptr;
   const void* M = nullptr;
@@ -3561,6 +3731,29 @@ extern "C" int hs_hss_ldiv(hs_hss* H, double* B, int64_t ldb, int64_t nrhs, int 
         hss_factor<double>(*HD(H));
         with_device_block<double>(HD(H)->n, B, ldb, B, ldb, (int)nrhs, where,
                                   [&](const double*, int la, double* b, int) { hss_ldiv<double>(*HD(H), b, la, (int)nrhs); });
+      });
+}
+
+extern "C" int hs_hss_ldiv_t(hs_hss* H, int trans, double* B, int64_t ldb, int64_t nrhs, int where) {
+  if (!H || !B || nrhs < 0) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_ldiv_t needs a right-hand side");
+    return HS_ERR_ARGUMENT;
+  }
+  if (trans < 0 || trans > 2) {
+    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_hss_ldiv_t: trans = %d (0: H^-1, 1: H^-T, 2: H^-H)", trans);
+    return HS_ERR_ARGUMENT;
+  }
+  if (trans == 0) return hs_hss_ldiv(H, B, ldb, nrhs, where);
+  if (nrhs == 0) return HS_OK;
+  HSS_GUARD(
+      if (H->is_complex) {
+        hss_factor<cplx>(*HZ(H));
+        with_device_block<cplx>(HZ(H)->n, (const cplx*)B, ldb, (cplx*)B, ldb, (int)nrhs, where,
+                                [&](const cplx*, int la, cplx* b, int) { hss_ldiv_t<cplx>(*HZ(H), b, la, (int)nrhs, trans == 2); });
+      } else {
+        hss_factor<double>(*HD(H));
+        with_device_block<double>(HD(H)->n, B, ldb, B, ldb, (int)nrhs, where,
+                                  [&](const double*, int la, double* b, int) { hss_ldiv_t<double>(*HD(H), b, la, (int)nrhs, 0); });
       });
 }
 

@@ -27,6 +27,8 @@ struct HsMultiLevel {
   std::vector<HsMultiFront> fronts;
   std::vector<HsMultiLR> lr;
   std::vector<int> node;  // the handle's internal node id of every front, in the order of sn / fronts
+  std::vector<int> hss;   // the level's fronts whose interior block D is an HSS matrix (internal node ids): their SolveNode carries ni = 0, so the
+                          // grouped dense kernels skip them; HsMultiView::hss_front serves them (hs_ldiv_ulv_* only)
 };
 struct HsMultiView {
   int64_t n = 0;
@@ -35,6 +37,10 @@ struct HsMultiView {
   std::vector<HsMultiLevel> levels;  // index = level (0 = root / pseudo-root)
   void** mx = nullptr;               // cache slot of hs_solve_multi.hip (work blocks, the last call's figures), freed by hs_free through *mx_free
   void (**mx_free)(void*) = nullptr;
+  // hs_ldiv_ulv_*: one sweep (0: leaves -> root, 1: root -> leaves) of one HSS front on the kc columns of the caller's column-major block B, which
+  // is what carries boundary rows between levels.  Null (every other entry point refuses such handles before it builds a view): no hook.
+  void (*hss_front)(void* ctx, int node, int sweep, int trans, void* B, long long ldb, int kc, hipStream_t s) = nullptr;
+  void* hss_ctx = nullptr;
 };
 void hs_multi_view(hs_handle* h, HsMultiView* v);
 

@@ -247,6 +247,8 @@ void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, 
     if (act && act->begin) act->begin(act->ctx, chunks, kc, s);
     for (int lv = nl - 1; lv >= 0; --lv) {  // leaves -> root
       const HsMultiLevel& L = v.levels[lv];
+      if (v.hss_front && !act)  // fronts with an HSS interior block (disjoint from the level's other fronts): on the caller's block
+        for (int id : L.hss) v.hss_front(v.hss_ctx, id, 0, 0, a.B, a.ldb, kc, s);
       if (L.nfronts == 0 || L.maxni == 0) continue;
       const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 0);
       if (q_.nf == 0 || q_.maxni == 0) continue;
@@ -282,6 +284,8 @@ void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, 
       launch_sparse_zero<T>((T*)mc->W2, kcw, kc, act->zseg + act->zoff[chunks], (int)(act->zoff[chunks + 1] - act->zoff[chunks]), act->zmaxni[chunks], s);
     for (int lv = 0; lv < nl; ++lv) {  // root -> leaves
       const HsMultiLevel& L = v.levels[lv];
+      if (v.hss_front && !act)
+        for (int id : L.hss) v.hss_front(v.hss_ctx, id, 1, 0, a.B, a.ldb, kc, s);
       if (L.nfronts == 0 || L.maxni == 0) continue;
       const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 1);
       if (q_.nf == 0 || q_.maxni == 0) continue;
@@ -353,6 +357,8 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
     if (act && act->begin) act->begin(act->ctx, chunks, kc, s);
     for (int lv = nl - 1; lv >= 0; --lv) {  // leaves -> root
       const HsMultiLevel& L = v.levels[lv];
+      if (v.hss_front && !act)  // fronts with an HSS interior block (disjoint from the level's other fronts): on the caller's block
+        for (int id : L.hss) v.hss_front(v.hss_ctx, id, 0, trans, a.B, a.ldb, kc, s);
       if (L.nfronts == 0 || L.maxni == 0) continue;
       const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 0);
       if (q_.nf == 0 || q_.maxni == 0) continue;
@@ -393,6 +399,8 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
       launch_sparse_zero<T>((T*)mc->W2, kcw, kc, act->zseg + act->zoff[chunks], (int)(act->zoff[chunks + 1] - act->zoff[chunks]), act->zmaxni[chunks], s);
     for (int lv = 0; lv < nl; ++lv) {  // root -> leaves
       const HsMultiLevel& L = v.levels[lv];
+      if (v.hss_front && !act)
+        for (int id : L.hss) v.hss_front(v.hss_ctx, id, 1, trans, a.B, a.ldb, kc, s);
       if (L.nfronts == 0 || L.maxni == 0) continue;
       const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 1);
       if (q_.nf == 0 || q_.maxni == 0) continue;

@@ -435,6 +435,78 @@ extern "C" int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double
   return multi_prob_t_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj);
 }
 
+// one grouped launch of the transposed ULV product (kernels_ulv_t.hip) on caller-supplied jobs (include/hs_kernels.h)
+#include "hs_ulv_t.h"
+template <class T>
+static int ulv_t_group_hook(int64_t njobs, const int64_t* desc, const T* Abuf, int64_t na, const T* Xbuf, int64_t nx, T* Cbuf, int64_t nc, int conj) {
+  if (njobs < 1 || njobs > 65535 || !desc || !Abuf || !Xbuf || !Cbuf || na < 1 || nx < 1 || nc < 1) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_ulv_t_group: 1..65535 jobs, their descriptions and non-empty buffers required");
+    return HS_ERR_ARGUMENT;
+  }
+  std::vector<UlvTJob<T>> jobs((size_t)njobs);
+  int maxM = 0, maxN = 0;
+  for (int64_t i = 0; i < njobs; ++i) {
+    const int64_t* d = desc + 10 * i;
+    const int64_t M = d[0], K = d[1], N = d[2], lda = d[3], ldx = d[4], ldc = d[5], ao = d[6], xo = d[7], co = d[8], fl = d[9];
+    const bool empty = M == 0 || K == 0 || N == 0;
+    bool ok = M >= 0 && K >= 0 && N >= 0 && M < (1 << 30) && K < (1 << 30) && N < (1 << 30) && ao >= 0 && xo >= 0 && co >= 0 && fl >= 0 && fl < 6;
+    if (ok && !empty)
+      ok = lda >= K && ldx >= K && ldc >= M && lda < (1 << 30) && ldx < (1 << 30) && ldc < (1 << 30) && ao + lda * (M - 1) + K <= na &&
+           xo + ldx * (N - 1) + K <= nx && co + ldc * (N - 1) + M <= nc;
+    if (!ok) {
+      hs_set_error(HS_ERR_ARGUMENT, i, "hsk_ulv_t_group: job %lld reaches outside its buffers", (long long)i);
+      return HS_ERR_ARGUMENT;
+    }
+    UlvTJob<T>& j = jobs[(size_t)i];
+    memset(&j, 0, sizeof j);
+    if (empty) continue;  // (stays in the launch with M = K = N = 0: the kernel skips it)
+    j.M = (int)M; j.K = (int)K; j.N = (int)N;
+    j.lda = (int)lda; j.ldx = (int)ldx; j.ldc = j.ldcin = (int)ldc;
+    j.conj = (conj && sizeof(T) == 16) ? 1 : 0;
+    j.tri = (int)(fl >> 1);
+    maxM = std::max(maxM, j.M);
+    maxN = std::max(maxN, j.N);
+  }
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
+    return HS_ERR_DEVICE;
+  }
+  T *dA = nullptr, *dX = nullptr, *dC = nullptr;
+  UlvTJob<T>* dJ = nullptr;
+  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)na));
+  CK(hipMalloc((void**)&dX, sizeof(T) * (size_t)nx));
+  CK(hipMalloc((void**)&dC, sizeof(T) * (size_t)nc));
+  CK(hipMalloc((void**)&dJ, sizeof(UlvTJob<T>) * jobs.size()));
+  for (int64_t i = 0; i < njobs; ++i) {
+    UlvTJob<T>& j = jobs[(size_t)i];
+    if (j.M == 0) continue;
+    const int64_t* d = desc + 10 * i;
+    j.A = dA + d[6];
+    j.X = dX + d[7];
+    j.C = dC + d[8];
+    j.Cin = (d[9] & 1) ? j.C : nullptr;
+  }
+  CK(hipMemcpy(dA, Abuf, sizeof(T) * (size_t)na, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dX, Xbuf, sizeof(T) * (size_t)nx, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dC, Cbuf, sizeof(T) * (size_t)nc, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dJ, jobs.data(), sizeof(UlvTJob<T>) * jobs.size(), hipMemcpyHostToDevice));
+  launch_ulv_t<T>(dJ, (int)njobs, maxM, maxN, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy(Cbuf, dC, sizeof(T) * (size_t)nc, hipMemcpyDeviceToHost));
+  (void)hipFree(dA);
+  (void)hipFree(dX);
+  (void)hipFree(dC);
+  (void)hipFree(dJ);
+  return HS_OK;
+}
+extern "C" int hsk_ulv_t_group_d(int64_t njobs, const int64_t* desc, const double* Abuf, int64_t na, const double* Xbuf, int64_t nx, double* Cbuf, int64_t nc, int conj) {
+  return ulv_t_group_hook<double>(njobs, desc, Abuf, na, Xbuf, nx, Cbuf, nc, conj);
+}
+extern "C" int hsk_ulv_t_group_z(int64_t njobs, const int64_t* desc, const double* Abuf, int64_t na, const double* Xbuf, int64_t nx, double* Cbuf, int64_t nc, int conj) {
+  return ulv_t_group_hook<cplx>(njobs, desc, (const cplx*)Abuf, na, (const cplx*)Xbuf, nx, (cplx*)Cbuf, nc, conj);
+}
+
 // The leaf-envelope builder of the analysis (hs_envelope.h), host only: tests compare it with a NumPy computation from A[idx][:, idx]
 // hsk_sddmm_*: the reduction kernel of hs_sens_* (kernels_sens.hip) alone on host data
 #include "hs_sens.h"

@@ -181,12 +181,18 @@ class HssMatrix:
         _lib.check(self.L.hs_hss_factor(self._h))
         return self
 
-    def ldiv(self, B):
-        """``H \\ B`` (the ULV-type elimination is computed on first use)."""
+    def ldiv(self, B, trans=None):
+        """``H \\ B`` (the ULV-type elimination is computed on first use).  ``trans``: ``None`` / ``"N"`` (the default), ``"T"``:
+        ``transpose(H) \\ B``, ``"C"``: ``adjoint(H) \\ B`` -- from the same stored factors (``hs_hss_ldiv_t``)."""
+        if trans not in (None, "N", "T", "C"):
+            raise ValueError(f"trans must be None, 'N', 'T' or 'C', got {trans!r}")
         B2, one = self._block(B)
         B2 = B2.copy(order="F")
         n, q = B2.shape
-        _lib.check(self.L.hs_hss_ldiv(self._h, B2.ctypes.data_as(C.c_void_p), n, q, 0))
+        if trans is None:
+            _lib.check(self.L.hs_hss_ldiv(self._h, B2.ctypes.data_as(C.c_void_p), n, q, 0))
+        else:
+            _lib.check(self.L.hs_hss_ldiv_t(self._h, "NTC".index(trans), B2.ctypes.data_as(C.c_void_p), n, q, 0))
         return B2[:, 0] if one else B2
 
     def pack(self, device="cuda:0"):

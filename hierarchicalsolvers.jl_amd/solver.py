@@ -464,6 +464,41 @@ def ldiv_block_t(*args):
     return res
 
 
+def ldiv_ulv(*args):
+    """``ldiv!(F, B)`` / ``ldiv!(C, F, B)`` for a block ``B`` with ``F`` a :class:`FactorNode`, ``transpose(F)`` or ``adjoint(F)``
+    (``hs_ldiv_ulv_*``): the block solve that also serves fronts whose interior block ``D`` is held as an HSS matrix (``hss_d``,
+    ``mf = 2, 3``) -- one ULV solve with ``D`` (transposed: from the same stored factors) per front and chunk of columns.  A handle
+    without such fronts returns the bits of :func:`ldiv_block_t`."""
+    if len(args) == 2:
+        F, B = args
+        Cout = None
+    elif len(args) == 3:
+        Cout, F, B = args
+    else:
+        raise TypeError("ldiv_ulv(F, B) or ldiv_ulv(C, F, B)")
+    trans = 0
+    if isinstance(F, TransposedFactor):
+        F, trans = F.parent, F.trans
+    B = np.asarray(B)
+    if B.shape[0] != F.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
+    if B.dtype != F.dtype:
+        if F.dtype.kind == "f" and B.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::FactorNode{Float64}, ::Array{ComplexF64})")
+        B = B.astype(F.dtype)
+    vec = B.ndim == 1
+    Bm = np.asfortranarray(B.reshape(F.n, -1))
+    Cm = np.empty_like(Bm, order="F")
+    L = _lib.lib()
+    fn = L.hs_ldiv_ulv_z if F.dtype.kind == "c" else L.hs_ldiv_ulv_d
+    _lib.check(fn(F._h, trans, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
+    res = Cm[:, 0] if vec else Cm
+    if Cout is not None:
+        Cout[...] = res
+        return Cout
+    return res
+
+
 def ldiv_block_info(F):
     """Figures of the last :func:`ldiv_block` / :func:`ldiv_block_t` call on ``F`` (``hs_ldiv_block_info``): device seconds, factor bytes read by the model
     (chunks x sum over fronts of ``(ni^2 + 2 ni nb) sizeof(T)``), flops executed on the matrix pipe (padding included), useful flops,

@@ -177,6 +177,13 @@ int64_t hs_hss_depth(const hs_hss* H); /* levels of the cluster tree (1 = a sing
 /* ULV-type elimination of the HSS matrix (once), then B <- H^-1 B in place */
 int hs_hss_factor(hs_hss* H);
 int hs_hss_ldiv(hs_hss* H, double* B, int64_t ldb, int64_t nrhs, int where);
+/* B <- op(H)^-1 B in place from the SAME stored factors: trans = 0: H^-1 (the bits of hs_hss_ldiv), 1: H^-T, 2: H^-H (a real matrix: the same
+ * as 1).  Any other value: HS_ERR_ARGUMENT, B untouched.  `where` and the in-place convention as for hs_hss_ldiv; factors on first use like
+ * hs_hss_ldiv.  There is no second elimination and no transposed or conjugated copy of a factor: every non-root node keeps one skeleton for
+ * rows and columns (A(I[p_R], far) ~ T A(I[p_S], far), A(far, I[p_R]) ~ A(far, I[p_S]) T^T), so with E = [I -T; 0 I], F = [I 0; -T^T I]
+ * E^T = F, and the local matrix M = E^-1 X F^-1 has M^T = E^-1 X^T F^-1: the same tree walk with each front's LU read along its other index
+ * (csrc/kernels_ulv_t.hip; DESIGN.md "Transposed and adjoint ULV solves").  Two calls return equal bits. */
+int hs_hss_ldiv_t(hs_hss* H, int trans, double* B, int64_t ldb, int64_t nrhs, int where);
 /* wall time of the last compress / factor on the device (seconds, host clock around a synchronised stream) */
 double hs_hss_time(const hs_hss* H, int what); /* 0: compress, 1: factor */
 /* The module recycles its device blocks (and those of the low-rank compressions of hs_factor_*) through process-wide caches, up to

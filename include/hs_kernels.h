@@ -71,6 +71,15 @@ int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_
 int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
                        int minus, int trap, int conj);
 
+/* ONE grouped launch of the product of the transposed ULV solves of the HSS module (kernels_ulv_t.hip) on host data.  Job i is described by
+ * the ten entries desc[10 i ..]: M, K, N, lda, ldx, ldc, aoff, xoff, coff, flags.  A = Abuf + aoff is K x M column-major (lda >= K), X = Xbuf +
+ * xoff K x N (ldx >= K), C = Cbuf + coff M x N (ldc >= M); offsets and buffer lengths (na, nx, nc) count elements (ComplexF64: pairs of
+ * doubles).  flags bit 0: C = C - op(A)^T X (otherwise C = op(A)^T X); bits 1-2: 0 all of A, 1 only its entries k >= m, 2 only k <= m.
+ * conj != 0: op = conj (ignored for Float64).  Jobs with M, K or N equal to 0 are skipped; their C is left as it is.  HS_ERR_ARGUMENT when a
+ * job reaches outside its buffers; the C blocks of different jobs must be disjoint (the caller's concern). */
+int hsk_ulv_t_group_d(int64_t njobs, const int64_t* desc, const double* Abuf, int64_t na, const double* Xbuf, int64_t nx, double* Cbuf, int64_t nc, int conj);
+int hsk_ulv_t_group_z(int64_t njobs, const int64_t* desc, const double* Abuf, int64_t na, const double* Xbuf, int64_t nx, double* Cbuf, int64_t nc, int conj);
+
 /* The CSR SpMM of hs_gmres_block_* (hs_gmres_block.hip) on host data: Y = A X (B == NULL) or Y = B - A X, A n x n CSC with 1-based colptr /
  * rowval, X, B, Y column-major n x nrhs blocks (ldx, ldb, ldy >= n; rows of Y beyond n are left as they are). */
 int hsk_spmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,

@@ -178,6 +178,22 @@ int hs_ldiv_block_t_d(hs_handle* F, int trans, double* C, int64_t ldc, const dou
 int hs_ldiv_block_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
 int hs_ldiv_block_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 int hs_ldiv_block_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+/* C = op(F)^-1 B for an n x nrhs block (trans = 0: F, 1: transpose(F), 2: adjoint(F)) on ANY complete single-rank handle, the ones whose fronts
+ * keep their interior block D as an HSS matrix included (hs_options.hss_d, mf = 2, 3): what hs_ldiv_block_* / hs_ldiv_block_t_* refuse.  Such a
+ * front is served per chunk of HS_LDIV_BLOCK_COLS columns on the caller's block, between the grouped launches of its level's other fronts.
+ * With t = B[int], Abi ~ C_L Z_L, Aib ~ C_R Z_R, W = D^-1 C_R:
+ *   trans = 0:     forward  t = D^-1 t, B[bnd] -= C_L (Z_L t);                backward  B[int] = t - W (Z_R B[bnd])
+ *   trans = 1, 2:  forward  B[bnd] -= op(Z_R)^T (op(W)^T t) (no solve with D); backward  B[int] = op(D)^-T (t - op(Z_L)^T (op(C_L)^T B[bnd]))
+ * op(D)^-T is one transposed ULV solve from the stored factors (hs_hss_ldiv_t, include/hs_hss.h; the 2 x 2 block form of mf = 3: two, around
+ * its stored couplings).  No factor memory is added; the scratch of a call (the largest such front x one chunk) comes from the library's
+ * scratch cache and goes back to it.  A handle WITHOUT such fronts goes through hs_ldiv_block_t_* and returns its bits.  Two calls return equal
+ * bits.  Refused before any device work and with C untouched: more than one rank (HS_ERR_UNSUPPORTED), trans outside 0..2, null blocks, a
+ * mismatched element type (HS_ERR_ARGUMENT), bad sizes (HS_ERR_DIMENSION), a low-rank transform that does not keep its dense C
+ * (HS_ERR_UNSUPPORTED).  C may alias B.  Both forms return when the result is complete (the ULV solves of the fronts synchronise `stream`). */
+int hs_ldiv_ulv_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_ldiv_ulv_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_ldiv_ulv_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+int hs_ldiv_ulv_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 /* last block solve of the handle, whichever direction it had (waits for it): out6 = {seconds on the device, factor bytes read by the model (column chunks x sum over
  * fronts of (ni^2 + 2 ni nb) sizeof(T), the factor term of hs_stats.bytes_solve), flops executed on the matrix pipe (padding included),
  * useful flops, column chunks, workspace bytes} */
