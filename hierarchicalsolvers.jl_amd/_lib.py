@@ -145,30 +145,15 @@ def lib():
     for f in (L.hs_ldiv_dev_d, L.hs_ldiv_dev_z):
         f.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp]
         f.restype = C.c_int
-    for f in (L.hs_ldiv_t_d, L.hs_ldiv_t_z):
-        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
-        f.restype = C.c_int
-    for f in (L.hs_ldiv_dev_t_d, L.hs_ldiv_dev_t_z):
-        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
-        f.restype = C.c_int
-    for f in (L.hs_ldiv_block_d, L.hs_ldiv_block_z):
-        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
-        f.restype = C.c_int
-    for f in (L.hs_ldiv_block_dev_d, L.hs_ldiv_block_dev_z):
-        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
-        f.restype = C.c_int
-    for f in (L.hs_ldiv_block_t_d, L.hs_ldiv_block_t_z):
-        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
-        f.restype = C.c_int
-    for f in (L.hs_ldiv_block_dev_t_d, L.hs_ldiv_block_dev_t_z):
-        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
-        f.restype = C.c_int
-    for f in (L.hs_ldiv_ulv_d, L.hs_ldiv_ulv_z):
-        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
-        f.restype = C.c_int
-    for f in (L.hs_ldiv_ulv_dev_d, L.hs_ldiv_ulv_dev_z):
-        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
-        f.restype = C.c_int
+    # (F, trans, C, ldc, B, ldb, n, nrhs) on the host, the same on the device with a stream
+    for host, dev in (("hs_ldiv_t", "hs_ldiv_dev_t"), ("hs_ldiv_block", "hs_ldiv_block_dev"), ("hs_ldiv_block_t", "hs_ldiv_block_dev_t"), ("hs_ldiv_ulv", "hs_ldiv_ulv_dev")):
+        for sfx in ("_d", "_z"):
+            f = getattr(L, host + sfx)
+            f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
+            f.restype = C.c_int
+            f = getattr(L, dev + sfx)
+            f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
+            f.restype = C.c_int
     L.hs_ldiv_block_info.argtypes = [vp, p_f64]
     L.hs_ldiv_block_info.restype = C.c_int
     for f in (L.hs_ldiv_sparse_d, L.hs_ldiv_sparse_z):

@@ -172,6 +172,8 @@ struct NodeH {
   void *hss2 = nullptr, *hss_keep = nullptr;
   void *bW12 = nullptr, *bZ12 = nullptr, *bC21 = nullptr, *bZ21 = nullptr;  // A11^-1*C12 (n1 x k12), Z12 (k12 x n2), C21 (n2 x k21), Z21 (k21 x n1)
   int bk12 = 0, bk21 = 0, bldw = 0, bldz12 = 0, bldc21 = 0, bldz21 = 0;
+  // the front keeps its interior block D as an HSS matrix (hss_d, mf = 2, 3): no dense LU of D, its solves are ULV solves
+  bool hss_interior() const { return hssd || (mf && !mfd); }
 };
 
 struct LevelH {
@@ -1592,24 +1594,37 @@ static void check_solve_args(hs_handle* h, bool cplx, int64_t ldc, int64_t ldb, 
     HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: B has %lld rows, F is %lld x %lld", (long long)n, (long long)h->n, (long long)h->n);
 }
 
-template <class T>
-static void ldiv_host(hs_handle* h, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  check_solve_args(h, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  const bool dsolve = h->nranks > 1 && h->opts.dist_top;
-  if (h->nranks > 1 && !dsolve) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "hs_ldiv_* on a distributed factorization without hs_options.dist_top: drive hs_solve_*_levels from the host layer");
+// ---- the pieces the ldiv entry points compose their refusals from, each in its own order (the order is observable, and the tests pin it).
+// fn: the entry point as its messages name it; what: the kind of solve the message says is not implemented
+static void check_trans(int trans, const char* fn) {
+  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
+}
+static void check_single_rank(const hs_handle* h, const char* fn, const char* what) {
+  if (h->nranks > 1) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: %s of a factorization over %d ranks are not implemented (single-rank factorizations only)", fn, what, h->nranks);
+}
+// the first front of this rank that keeps its interior block D as an HSS matrix (NodeH::hss_interior); -1: none
+static int first_hss_front(const hs_handle* h) {
+  for (size_t i = 0; i < h->nodes.size(); ++i)
+    if (h->nodes[i].mine && h->nodes[i].hss_interior()) return (int)i;
+  return -1;
+}
+static void check_no_hss_front(const hs_handle* h, const char* fn, const char* what) {
+  const int i = first_hss_front(h);
+  if (i >= 0)
+    HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): %s are not implemented", fn, i, what);
+}
+
+// ---- column by column: solve(c, s) is one single-vector solve in place on the device
+// host columns travel through d_b: upload, solve between the handle's events, download; t_solve = the sum of the device times
+template <class T, class Solve>
+static void each_column_host(hs_handle* h, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs, Solve solve) {
   hipStream_t s = h->stream;
   double tsum = 0.0;
-  const int nl = (int)h->levels.size();
   for (int64_t r = 0; r < nrhs; ++r) {
     T* db = (T*)h->d_b;
     HS_HIP(hipMemcpyAsync(db, B + r * ldb, n * sizeof(T), hipMemcpyHostToDevice, s));
     HS_HIP(hipEventRecord(h->ev0, s));
-    if (dsolve) {
-      solve_dist<T>(h, db, s);
-    } else {
-      solve_fwd<T>(h, db, nl - 1, 0, s);
-      solve_bwd<T>(h, db, 0, nl - 1, s);
-    }
+    solve(db, s);
     HS_HIP(hipEventRecord(h->ev1, s));
     HS_HIP(hipMemcpyAsync(C + r * ldc, db, n * sizeof(T), hipMemcpyDeviceToHost, s));
     HS_HIP(hipStreamSynchronize(s));
@@ -1620,25 +1635,41 @@ static void ldiv_host(hs_handle* h, T* C, int64_t ldc, const T* B, int64_t ldb, 
   }
   h->stats.t_solve = tsum;
 }
-
-template <class T>
-static void ldiv_dev(hs_handle* h, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  check_solve_args(h, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  const bool dsolve = h->nranks > 1 && h->opts.dist_top;
-  if (h->nranks > 1 && !dsolve) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "hs_ldiv_dev_* on a distributed factorization without hs_options.dist_top: drive hs_solve_*_levels from the host layer");
-  hipStream_t s = (hipStream_t)stream;
-  const int nl = (int)h->levels.size();
+// device columns are solved where they are (copied to C first unless C is B)
+template <class T, class Solve>
+static void each_column_dev(T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, hipStream_t s, Solve solve) {
   for (int64_t r = 0; r < nrhs; ++r) {
     T* c = dC + r * ldc;
     if (c != dB + r * ldb) HS_HIP(hipMemcpyAsync(c, dB + r * ldb, n * sizeof(T), hipMemcpyDeviceToDevice, s));
-    if (dsolve) {
-      solve_dist<T>(h, c, s);
-      continue;
-    }
-    solve_fwd<T>(h, c, nl - 1, 0, s);
-    solve_bwd<T>(h, c, 0, nl - 1, s);
+    solve(c, s);
   }
 }
+
+// what hs_ldiv_* / hs_ldiv_dev_* refuse; true: the factorization is spread over ranks with hs_options.dist_top (solve_dist)
+static bool check_solve_n(hs_handle* h, const char* fn, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
+  check_solve_args(h, cplx, ldc, ldb, n, nrhs);
+  const bool dsolve = h->nranks > 1 && h->opts.dist_top;
+  if (h->nranks > 1 && !dsolve) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s on a distributed factorization without hs_options.dist_top: drive hs_solve_*_levels from the host layer", fn);
+  return dsolve;
+}
+template <class T>
+static void solve_n(hs_handle* h, bool dsolve, T* db, hipStream_t s) {
+  if (dsolve) return solve_dist<T>(h, db, s);
+  const int nl = (int)h->levels.size();
+  solve_fwd<T>(h, db, nl - 1, 0, s);
+  solve_bwd<T>(h, db, 0, nl - 1, s);
+}
+template <class T>
+static void ldiv_host(hs_handle* h, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  const bool dsolve = check_solve_n(h, "hs_ldiv_*", sizeof(T) == 16, ldc, ldb, n, nrhs);
+  each_column_host<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* db, hipStream_t s) { solve_n<T>(h, dsolve, db, s); });
+}
+template <class T>
+static void ldiv_dev(hs_handle* h, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  const bool dsolve = check_solve_n(h, "hs_ldiv_dev_*", sizeof(T) == 16, ldc, ldb, n, nrhs);
+  each_column_dev<T>(dC, ldc, dB, ldb, n, nrhs, (hipStream_t)stream, [&](T* c, hipStream_t s) { solve_n<T>(h, dsolve, c, s); });
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // ldiv!(transpose(F), B), ldiv!(adjoint(F), B): the same factors read along their columns (kernels_solve_t.hip); CONJ = adjoint.
@@ -1701,53 +1732,25 @@ static void solve_t(hs_handle* h, int trans, T* db, hipStream_t s) {
 }
 // refuse, never drop: what the transposed sweeps do not cover is named before any device work
 static void check_solve_t(hs_handle* h, int trans, const char* fn) {
-  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
+  check_handle(h);
+  check_trans(trans, fn);
   if (trans == 0) return;
-  if (h->nranks > 1)
-    HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: transposed solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", fn, h->nranks);
-  for (size_t i = 0; i < h->nodes.size(); ++i) {
-    const NodeH& x = h->nodes[i];
-    if (!x.mine) continue;
-    if (x.hssd || (x.mf && !x.mfd))
-      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): transposed ULV solves are not implemented",
-              fn, (int)i);
-  }
+  check_single_rank(h, fn, "transposed solves");
+  check_no_hss_front(h, fn, "transposed ULV solves");
 }
 template <class T>
 static void ldiv_host_t(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  check_handle(h);
   check_solve_t(h, trans, "hs_ldiv_t_*");
   if (trans == 0) return ldiv_host<T>(h, C, ldc, B, ldb, n, nrhs);
   check_solve_args(h, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  hipStream_t s = h->stream;
-  double tsum = 0.0;
-  for (int64_t r = 0; r < nrhs; ++r) {
-    T* db = (T*)h->d_b;
-    HS_HIP(hipMemcpyAsync(db, B + r * ldb, n * sizeof(T), hipMemcpyHostToDevice, s));
-    HS_HIP(hipEventRecord(h->ev0, s));
-    solve_t<T>(h, trans, db, s);
-    HS_HIP(hipEventRecord(h->ev1, s));
-    HS_HIP(hipMemcpyAsync(C + r * ldc, db, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    HS_HIP(hipStreamSynchronize(s));
-    flow_check(h);
-    float ms = 0.f;
-    HS_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    tsum += ms * 1e-3;
-  }
-  h->stats.t_solve = tsum;
+  each_column_host<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* db, hipStream_t s) { solve_t<T>(h, trans, db, s); });
 }
 template <class T>
 static void ldiv_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  check_handle(h);
   check_solve_t(h, trans, "hs_ldiv_dev_t_*");
   if (trans == 0) return ldiv_dev<T>(h, dC, ldc, dB, ldb, n, nrhs, stream);
   check_solve_args(h, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  hipStream_t s = (hipStream_t)stream;
-  for (int64_t r = 0; r < nrhs; ++r) {
-    T* c = dC + r * ldc;
-    if (c != dB + r * ldb) HS_HIP(hipMemcpyAsync(c, dB + r * ldb, n * sizeof(T), hipMemcpyDeviceToDevice, s));
-    solve_t<T>(h, trans, c, s);
-  }
+  each_column_dev<T>(dC, ldc, dB, ldb, n, nrhs, (hipStream_t)stream, [&](T* c, hipStream_t s) { solve_t<T>(h, trans, c, s); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1767,7 +1770,7 @@ void hs_multi_view(hs_handle* h, HsMultiView* v) {
     HsMultiLevel& M = v->levels[lv];
     for (int id : L.mine) {
       const NodeH& x = h->nodes[id];
-      if ((x.hssd || (x.mf && !x.mfd)) && x.hss && x.ni > 0) M.hss.push_back(id);  // served by HsMultiView::hss_front (hs_ldiv_ulv_*)
+      if (x.hss_interior() && x.hss && x.ni > 0) M.hss.push_back(id);  // served by HsMultiView::hss_front (hs_ldiv_ulv_*)
     }
     if (L.mine.empty() || L.maxni == 0 || !h->d_solve) continue;
     M.sn = (const char*)h->d_solve + L.desc_off * ssz;
@@ -1778,7 +1781,7 @@ void hs_multi_view(hs_handle* h, HsMultiView* v) {
     for (int id : L.mine) {
       const NodeH& x = h->nodes[id];
       const bool lowrank = x.compressed || x.mf;
-      const bool hssfront = x.hssd || (x.mf && !x.mfd);
+      const bool hssfront = x.hss_interior();
       if (hssfront)
         M.fronts.push_back({0, 0, 0, x.woff});  // its SolveNode carries ni = 0: no dense work, no boundary segment
       else
@@ -1801,102 +1804,87 @@ void hs_multi_view(hs_handle* h, HsMultiView* v) {
 }
 // everything hs_ldiv_block_* refuses, before any device work and before C is written
 static void check_solve_block(hs_handle* h, int trans, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
+  const char* fn = "hs_ldiv_block_*";
   check_handle(h);
-  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_ldiv_block_*: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", trans);
+  check_trans(trans, fn);
   if (trans != 0) HS_FAIL(HS_ERR_UNSUPPORTED, trans, "hs_ldiv_block_*: transposed and adjoint block solves are not implemented (trans must be 0; hs_ldiv_t_* solves column by column)");
   check_solve_args(h, cplx, ldc, ldb, n, nrhs);
-  if (h->nranks > 1) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "hs_ldiv_block_*: block solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", h->nranks);
-  for (size_t i = 0; i < h->nodes.size(); ++i) {
-    const NodeH& x = h->nodes[i];
-    if (x.mine && (x.hssd || (x.mf && !x.mfd)))
-      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_ldiv_block_*: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): block solves are not implemented", (int)i);
+  check_single_rank(h, fn, "block solves");
+  check_no_hss_front(h, fn, "block solves");
+}
+// hs_ldiv_block_t_*: the block solve with transpose(F) (trans = 1) or adjoint(F) (trans = 2); trans = 0 is hs_ldiv_block_* itself.  The same
+// handles are served and the same ones refused, before any device work and before C is written
+static void check_solve_block_t(hs_handle* h, int trans, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
+  const char* fn = "hs_ldiv_block_t_*";
+  check_handle(h);
+  check_trans(trans, fn);
+  check_solve_args(h, cplx, ldc, ldb, n, nrhs);
+  check_single_rank(h, fn, "block solves");
+  check_no_hss_front(h, fn, "transposed ULV solves");
+}
+// a host block on the device: the whole block goes up and comes down once around run(d, ld, s), d the n x nrhs copy in scratch memory
+template <class T, class Run>
+static void stage_block(hs_handle* h, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs, Run run) {
+  hipStream_t s = h->stream;
+  const size_t bytes = (size_t)n * nrhs * sizeof(T);
+  T* d = (T*)hs_scratch_take(bytes, "block solve right-hand sides");
+  try {
+    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
+    run(d, n, s);
+    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    hs_scratch_give(d, bytes);
+    throw;
   }
+  hs_scratch_give(d, bytes);
+  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
+}
+// a device block is solved in place in C: what every device entry does between its checks and its solve
+template <class T>
+static hipStream_t block_in_place(const char* fn, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
+  hipStream_t s = (hipStream_t)stream;
+  if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
+  return s;
+}
+// the block solve of a checked handle without HSS interior blocks; trans = 0 speaks as hs_ldiv_block_*, whichever entry point came here
+template <class T>
+static void block_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
+  if (nrhs == 0) return;
+  if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", trans ? "hs_ldiv_block_t_*" : "hs_ldiv_block_*");
+  HsMultiView v;
+  hs_multi_view(h, &v);
+  stage_block<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { hs_solve_multi_run<T>(v, trans, d, ld, nrhs, s); });
+}
+template <class T>
+static void block_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+  if (nrhs == 0) return;
+  hipStream_t s = block_in_place<T>(trans ? "hs_ldiv_block_dev_t_*" : "hs_ldiv_block_dev_*", dC, ldc, dB, ldb, n, nrhs, stream);
+  HsMultiView v;
+  hs_multi_view(h, &v);
+  hs_solve_multi_run<T>(v, trans, dC, ldc, nrhs, s);
 }
 template <class T>
 static void ldiv_block_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
   check_solve_block(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  if (nrhs == 0) return;
-  if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_*: null block");
-  hipStream_t s = h->stream;
-  HsMultiView v;
-  hs_multi_view(h, &v);
-  const size_t bytes = (size_t)n * nrhs * sizeof(T);
-  T* d = (T*)hs_scratch_take(bytes, "block solve right-hand sides");
-  try {  // the whole block goes up and comes down once
-    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
-    hs_solve_multi_run<T>(v, d, n, nrhs, s);
-    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
-    HS_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    hs_scratch_give(d, bytes);
-    throw;
-  }
-  hs_scratch_give(d, bytes);
-  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
+  block_host<T>(h, 0, C, ldc, B, ldb, n, nrhs);
 }
 template <class T>
 static void ldiv_block_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   check_solve_block(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  if (nrhs == 0) return;
-  if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_dev_*: null block");
-  hipStream_t s = (hipStream_t)stream;
-  HsMultiView v;
-  hs_multi_view(h, &v);
-  if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
-  hs_solve_multi_run<T>(v, dC, ldc, nrhs, s);
-}
-
-// hs_ldiv_block_t_*: the block solve with transpose(F) (trans = 1) or adjoint(F) (trans = 2); trans = 0 is hs_ldiv_block_* itself.  The same
-// handles are served and the same ones refused, before any device work and before C is written
-static void check_solve_block_t(hs_handle* h, int trans, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
-  check_handle(h);
-  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_ldiv_block_t_*: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", trans);
-  check_solve_args(h, cplx, ldc, ldb, n, nrhs);
-  if (h->nranks > 1)
-    HS_FAIL(HS_ERR_UNSUPPORTED, 0, "hs_ldiv_block_t_*: block solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", h->nranks);
-  for (size_t i = 0; i < h->nodes.size(); ++i) {
-    const NodeH& x = h->nodes[i];
-    if (x.mine && (x.hssd || (x.mf && !x.mfd)))
-      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i,
-              "hs_ldiv_block_t_*: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): transposed ULV solves are not implemented", (int)i);
-  }
+  block_dev<T>(h, 0, dC, ldc, dB, ldb, n, nrhs, stream);
 }
 template <class T>
 static void ldiv_block_host_t(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
   check_solve_block_t(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  if (trans == 0) return ldiv_block_host<T>(h, 0, C, ldc, B, ldb, n, nrhs);
-  if (nrhs == 0) return;
-  if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_t_*: null block");
-  hipStream_t s = h->stream;
-  HsMultiView v;
-  hs_multi_view(h, &v);
-  const size_t bytes = (size_t)n * nrhs * sizeof(T);
-  T* d = (T*)hs_scratch_take(bytes, "block solve right-hand sides");
-  try {  // the whole block goes up and comes down once
-    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
-    hs_solve_multi_run_t<T>(v, trans, d, n, nrhs, s);
-    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
-    HS_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    hs_scratch_give(d, bytes);
-    throw;
-  }
-  hs_scratch_give(d, bytes);
-  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
+  block_host<T>(h, trans, C, ldc, B, ldb, n, nrhs);
 }
 template <class T>
 static void ldiv_block_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   check_solve_block_t(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  if (trans == 0) return ldiv_block_dev<T>(h, 0, dC, ldc, dB, ldb, n, nrhs, stream);
-  if (nrhs == 0) return;
-  if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_dev_t_*: null block");
-  hipStream_t s = (hipStream_t)stream;
-  HsMultiView v;
-  hs_multi_view(h, &v);
-  if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
-  hs_solve_multi_run_t<T>(v, trans, dC, ldc, nrhs, s);
+  block_dev<T>(h, trans, dC, ldc, dB, ldb, n, nrhs, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2005,16 +1993,16 @@ static void ulv_front(void* ctx_, int id, int sweep, int trans, void* B_, long l
 }
 // everything hs_ldiv_ulv_* refuses, before any device work and before C is written; true: the handle has fronts with an HSS interior block
 static bool check_solve_ulv(hs_handle* h, int trans, bool isz, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
+  const char* fn = "hs_ldiv_ulv_*";
   check_handle(h);
-  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_ldiv_ulv_*: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", trans);
-  if (h->nranks > 1)  // (before the state of the handle: a host-side plan over several ranks is refused for its ranks)
-    HS_FAIL(HS_ERR_UNSUPPORTED, 0, "hs_ldiv_ulv_*: block solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", h->nranks);
+  check_trans(trans, fn);
+  check_single_rank(h, fn, "block solves");  // (before the state of the handle: a host-side plan over several ranks is refused for its ranks)
   check_solve_args(h, isz, ldc, ldb, n, nrhs);
-  bool any = false;
-  for (size_t i = 0; i < h->nodes.size(); ++i) {
+  const int first = first_hss_front(h);
+  if (first < 0) return false;
+  for (size_t i = (size_t)first; i < h->nodes.size(); ++i) {  // every such front is complete and keeps its dense C
     const NodeH& x = h->nodes[i];
-    if (!(x.mine && (x.hssd || (x.mf && !x.mfd)))) continue;
-    any = true;
+    if (!(x.mine && x.hss_interior())) continue;
     if (!x.hss || (x.mfb && !x.hss2)) HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_ldiv_ulv_*: node %d has no eliminated interior block (incomplete factorization)", (int)i);
     bool nodense = false;
     if (x.nb > 0 && x.lrL) {
@@ -2024,7 +2012,7 @@ static bool check_solve_ulv(hs_handle* h, int trans, bool isz, int64_t ldc, int6
     if (nodense)
       HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_ldiv_ulv_*: the low-rank transform of node %d does not keep its dense factor C (only the packed sketch)", (int)i);
   }
-  return any;
+  return true;
 }
 template <class T>
 static void ulv_run(hs_handle* h, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
@@ -2055,10 +2043,7 @@ static void ulv_run(hs_handle* h, int trans, T* dC, int64_t ldc, int64_t nrhs, h
   v.hss_front = &ulv_front<T>;
   v.hss_ctx = &w;
   try {
-    if (trans == 0)
-      hs_solve_multi_run<T>(v, dC, ldc, nrhs, s);
-    else
-      hs_solve_multi_run_t<T>(v, trans, dC, ldc, nrhs, s);
+    hs_solve_multi_run<T>(v, trans, dC, ldc, nrhs, s);
     HS_HIP(hipStreamSynchronize(s));
   } catch (...) {
     (void)hipStreamSynchronize(s);
@@ -2069,32 +2054,16 @@ static void ulv_run(hs_handle* h, int trans, T* dC, int64_t ldc, int64_t nrhs, h
 }
 template <class T>
 static void ldiv_ulv_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return ldiv_block_host_t<T>(h, trans, C, ldc, B, ldb, n, nrhs);
+  if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return block_host<T>(h, trans, C, ldc, B, ldb, n, nrhs);
   if (nrhs == 0) return;
   if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_ulv_*: null block");
-  hipStream_t s = h->stream;
-  const size_t bytes = (size_t)n * nrhs * sizeof(T);
-  T* d = (T*)hs_scratch_take(bytes, "block solve right-hand sides");
-  try {
-    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
-    ulv_run<T>(h, trans, d, n, nrhs, s);
-    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
-    HS_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    hs_scratch_give(d, bytes);
-    throw;
-  }
-  hs_scratch_give(d, bytes);
-  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
+  stage_block<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { ulv_run<T>(h, trans, d, ld, nrhs, s); });
 }
 template <class T>
 static void ldiv_ulv_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return ldiv_block_dev_t<T>(h, trans, dC, ldc, dB, ldb, n, nrhs, stream);
+  if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return block_dev<T>(h, trans, dC, ldc, dB, ldb, n, nrhs, stream);
   if (nrhs == 0) return;
-  if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_ulv_dev_*: null block");
-  hipStream_t s = (hipStream_t)stream;
-  if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
+  hipStream_t s = block_in_place<T>("hs_ldiv_ulv_dev_*", dC, ldc, dB, ldb, n, nrhs, stream);
   ulv_run<T>(h, trans, dC, ldc, nrhs, s);  // (waits for s: the HSS solves of the fronts synchronise it anyway)
 }
 
@@ -2107,10 +2076,7 @@ void hs_handle_view(hs_handle* h, HsHandleView* v) {
   v->factored = h->factored ? 1 : 0;
   v->device = h->d_nodes ? 1 : 0;
   v->nranks = h->nranks;
-  for (size_t i = 0; i < h->nodes.size() && v->t_refused_node < 0; ++i) {
-    const NodeH& x = h->nodes[i];
-    if (x.mine && (x.hssd || (x.mf && !x.mfd))) v->t_refused_node = (int)i;  // what check_solve_t refuses
-  }
+  v->t_refused_node = first_hss_front(h);  // what check_solve_t refuses
   v->seed = h->opts.seed;
   v->colptr = h->d_colptr;
   v->rowval = h->d_rowval;
@@ -2154,7 +2120,7 @@ void hs_selinv_view(hs_handle* h, HsSelView* v) {
     f.ni = x.ni;
     f.nb = x.nb;
     if (x.ext_sb) sb_idle = false;
-    if (x.hssd || (x.mf && !x.mfd)) f.flags |= HS_SEL_NOLU;
+    if (x.hss_interior()) f.flags |= HS_SEL_NOLU;
     if (x.compressed || x.mf) f.flags |= HS_SEL_LOWRANK;
     if (x.kind != 0) f.flags |= HS_SEL_SLICE;
     const char* fac = (const char*)h->d_fac;
@@ -2542,18 +2508,12 @@ void hs_sparse_tree(const hs_handle* hc, HsSparseTree* t) {
     t->nb.push_back(x.nb);
   }
 }
-// what hs_ldiv_block_t_* refuses, before any device work and before X is written
+// what hs_ldiv_sparse_* refuses of a handle, before any device work and before X is written
 static void check_sparse_handle(const hs_handle* h, int trans, const char* fn) {
   check_handle(h);
-  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
-  if (h->nranks > 1)
-    HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: block solves of a factorization over %d ranks are not implemented (single-rank factorizations only)", fn, h->nranks);
-  for (size_t i = 0; i < h->nodes.size(); ++i) {
-    const NodeH& x = h->nodes[i];
-    if (x.mine && (x.hssd || (x.mf && !x.mfd)))
-      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): block solves are not implemented", fn,
-              (int)i);
-  }
+  check_trans(trans, fn);
+  check_single_rank(h, fn, "block solves");
+  check_no_hss_front(h, fn, "block solves");
 }
 // the CSC block and the row list; false: there is nothing to do (nrhs == 0, or an empty row list)
 static bool check_sparse_args(const hs_handle* h, const char* fn, int64_t n, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, const int64_t* rows, int64_t nrows) {

@@ -329,7 +329,7 @@ static void solve_lr_fwd(hs_handle* h, int lv, T* db, hipStream_t s) {
   T* w2 = (T*)h->d_w2;  // y = L11^-1 P rhs[int]
   for (int id : L.mine) {
     const NodeH& x = h->nodes[id];
-    if (!(x.compressed || x.mfd) || !x.lrL || x.hssd || (x.mf && !x.mfd)) continue;
+    if (!(x.compressed || x.mfd) || !x.lrL || x.hss_interior()) continue;
     const LowRank<T>& lr = *(const LowRank<T>*)x.lrL;
     if (lr.r == 0) continue;
     ensure_lr_workspace<T>(h, lr.r, lr.cols);
@@ -345,7 +345,7 @@ static void solve_lr_bwd(hs_handle* h, int lv, T* db, hipStream_t s) {
   T* w1 = (T*)h->d_w1;
   for (int id : L.mine) {
     const NodeH& x = h->nodes[id];
-    if (!(x.compressed || x.mfd) || !x.lrR || x.hssd || (x.mf && !x.mfd)) continue;
+    if (!(x.compressed || x.mfd) || !x.lrR || x.hss_interior()) continue;
     const LowRank<T>& lr = *(const LowRank<T>*)x.lrR;
     if (lr.r == 0) continue;
     ensure_lr_workspace<T>(h, lr.r, lr.cols);
@@ -374,7 +374,7 @@ static void solve_lr_fwd_t(hs_handle* h, int lv, T* db, hipStream_t s) {
   T* w2 = (T*)h->d_w2;
   for (int id : L.mine) {
     const NodeH& x = h->nodes[id];
-    if (!(x.compressed || x.mfd) || !x.lrR || x.hssd || (x.mf && !x.mfd)) continue;
+    if (!(x.compressed || x.mfd) || !x.lrR || x.hss_interior()) continue;
     const LowRank<T>& lr = *(const LowRank<T>*)x.lrR;
     if (lr.r == 0) continue;
     if (!lr.Cd) HS_FAIL(HS_ERR_UNSUPPORTED, id, "transposed ldiv!: node %d holds a low-rank transform without its dense C", id);
@@ -390,7 +390,7 @@ static void solve_lr_bwd_t(hs_handle* h, int lv, T* db, hipStream_t s) {
   T* w1 = (T*)h->d_w1;
   for (int id : L.mine) {
     const NodeH& x = h->nodes[id];
-    if (!(x.compressed || x.mfd) || !x.lrL || x.hssd || (x.mf && !x.mfd)) continue;
+    if (!(x.compressed || x.mfd) || !x.lrL || x.hss_interior()) continue;
     const LowRank<T>& lr = *(const LowRank<T>*)x.lrL;
     if (lr.r == 0) continue;
     if (!lr.Cd) HS_FAIL(HS_ERR_UNSUPPORTED, id, "transposed ldiv!: node %d holds a low-rank transform without its dense C", id);

@@ -44,7 +44,7 @@ struct HsMultiView {
 };
 void hs_multi_view(hs_handle* h, HsMultiView* v);
 
-// Optional active set of the two drivers below (hs_solve_sparse.hip builds it): which fronts each sweep of each chunk visits.  A level's
+// Optional active set of the driver below (hs_solve_sparse.hip builds it): which fronts each sweep of each chunk visits.  A level's
 // grouped launches then run over a compacted SolveNode / MultiAux array of its active fronts (their woff / boff segments stay where they
 // are), maxni / maxnb are taken over the subset, and a level without an active front launches nothing.
 struct MultiAux;
@@ -73,13 +73,10 @@ struct HsMultiActive {
   const HsMultiSubset& at(int chunk, int level, int sweep) const { return sub[((size_t)chunk * nlevels + level) * 2 + sweep]; }
 };
 
-// C[:, 0:nrhs] = F^-1 C[:, 0:nrhs] in place on the device (ld ldc), chunk by chunk, on stream s; events around the launches.  act == nullptr:
-// every front in both sweeps
+// C[:, 0:nrhs] = op(F)^-1 C[:, 0:nrhs] in place on the device (ld ldc), chunk by chunk, on stream s; events around the launches.  trans = 0: F
+// (kernels_solve_multi.hip), 1: transpose(F), 2: adjoint(F) (kernels_solve_multi_t.hip).  act == nullptr: every front in both sweeps
 template <class T>
-void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act = nullptr);
-// the same for transpose(F) (trans = 1) and adjoint(F) (trans = 2): C[:, 0:nrhs] = F^-T C / F^-H C (kernels_solve_multi_t.hip)
-template <class T>
-void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act = nullptr);
+void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act = nullptr);
 double hs_solve_multi_seconds(void* mx);  // waits for the last block solve and returns its device seconds
 void hs_solve_multi_info(void* mx, double* out6);
 int hs_ldiv_block_cols();  // KC: columns per chunk (HS_LDIV_BLOCK_COLS = 16 / 32 / 48 / 64, default 32)

@@ -1,5 +1,5 @@
 // hs_solve_multi.hip -- ldiv!(C, F, B) for an n x nrhs block with the factors read once per chunk of columns (hs_ldiv_block_*), and the
-// same for transpose(F) / adjoint(F) (hs_ldiv_block_t_*: hs_solve_multi_run_t at the end of this file).
+// same for transpose(F) / adjoint(F) (hs_ldiv_block_t_*): one driver, hs_solve_multi_run, whose trans argument picks the direction.
 //
 // The single-vector sweeps (kernels_solve_wide.hip) run at the HBM roofline, so k looped solves read the factors k times.  Here a chunk of
 // KC columns (HS_LDIV_BLOCK_COLS = 16 / 32 / 48 / 64, default 32; the last chunk may be ragged) travels through the tree together; every
@@ -226,105 +226,34 @@ bool multi_t_left_looking() {
   }();
   return left;
 }
+
+// the grouped launches of either direction: trans = 0 runs kernels_solve_multi.hip (mode n), trans = 1, 2 kernels_solve_multi_t.hip (mode t)
+template <class T>
+void level_move(int trans, const SolveNode<T>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s) {
+  if (trans)
+    launch_multi_move_t<T>(sn, nf, what, maxrows, a, s);
+  else
+    launch_multi_move<T>(sn, nf, what, maxrows, a, s);
+}
+template <class T>
+void level_step(int trans, int cj, const SolveNode<T>* sn, int nf, int mode_n, int mode_t, int blk, int maxM, const MultiArgs& a, hipStream_t s) {
+  if (trans)
+    launch_multi_level_t<T>(sn, nf, mode_t, blk, cj, maxM, a, s);
+  else
+    launch_multi_level<T>(sn, nf, mode_n, blk, maxM, a, s);
+}
+template <class T>
+void lr_apply_op(int trans, int cj, const LowRank<T>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
+  if (trans)
+    lr_apply_t<T>(lr, cj, x, dst, tbuf, kcw, kc, fc, s);
+  else
+    lr_apply<T>(lr, x, dst, tbuf, kcw, kc, fc, s);
+}
 }  // namespace
 
-template <class T>
-void hs_solve_multi_run(const HsMultiView& v, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act) {
-  const int KC = hs_ldiv_block_cols();
-  const int kcw = KC;
-  MultiCache* mc = multi_prepare<T>(v, kcw);
-  FlopCount fc;
-  fc.tr = hs_multi_rows_per_wg(sizeof(T) == 16);
-  fc.cmul = sizeof(T) == 16 ? 4 : 1;
-  const int nl = (int)v.levels.size();
-  int chunks = 0;
-  HS_HIP(hipEventRecord(mc->e0, s));
-  for (int64_t c0 = 0; c0 < nrhs; c0 += KC, ++chunks) {
-    const int kc = (int)std::min<int64_t>(KC, nrhs - c0);
-    MultiArgs a;
-    a.W1 = mc->W1; a.W2 = mc->W2; a.XB = mc->XB; a.kcw = kcw;
-    a.B = act ? dC : dC + c0 * ldc; a.ldb = ldc; a.kc = kc;  // an active set keeps every chunk in the same block
-    if (act && act->begin) act->begin(act->ctx, chunks, kc, s);
-    for (int lv = nl - 1; lv >= 0; --lv) {  // leaves -> root
-      const HsMultiLevel& L = v.levels[lv];
-      if (v.hss_front && !act)  // fronts with an HSS interior block (disjoint from the level's other fronts): on the caller's block
-        for (int id : L.hss) v.hss_front(v.hss_ctx, id, 0, 0, a.B, a.ldb, kc, s);
-      if (L.nfronts == 0 || L.maxni == 0) continue;
-      const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 0);
-      if (q_.nf == 0 || q_.maxni == 0) continue;
-      const SolveNode<T>* sn = (const SolveNode<T>*)q_.sn;
-      const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
-      a.wbase = L.wbase;
-      a.aux = q_.aux;
-      launch_multi_move<T>(sn, nf, 0, maxni, a, s);
-      launch_multi_move<T>(sn, nf, 1, maxnb, a, s);
-      const int nblk = (maxni + 255) / 256;
-      for (int j = 0; j < nblk; ++j) {
-        launch_multi_level<T>(sn, nf, HSM_DIAG_L, j, std::min(256, maxni - j * 256), a, s);
-        launch_multi_level<T>(sn, nf, HSM_BELOW_L, j, maxni - (j + 1) * 256, a, s);
-      }
-      launch_multi_level<T>(sn, nf, HSM_BND_L, 0, maxnb, a, s);
-      each_front(L, q_, [&](const HsMultiFront& f) {
-        for (int j = 0; j * 256 < f.ni; ++j) {
-          const double wl = std::min(256, f.ni - j * 256);
-          fc.add(wl, wl, kc, wl * (wl + 1) / 2);
-          fc.add(f.ni - (j + 1) * 256, 256, kc);
-        }
-        if (f.dense_bnd) fc.add(f.nb, f.ni, kc);
-      });
-      for (const HsMultiLR& q : L.lr) {
-        if (!q.lrL || !q_.has(q.pos)) continue;
-        const LowRank<T>& lr = *(const LowRank<T>*)q.lrL;
-        if (lr.r == 0) continue;
-        lr_apply<T>(lr, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
-      }
-      launch_multi_move<T>(sn, nf, 3, maxnb, a, s);
-    }
-    if (act && act->zoff[chunks + 1] > act->zoff[chunks])  // backward-only fronts: y = 0
-      launch_sparse_zero<T>((T*)mc->W2, kcw, kc, act->zseg + act->zoff[chunks], (int)(act->zoff[chunks + 1] - act->zoff[chunks]), act->zmaxni[chunks], s);
-    for (int lv = 0; lv < nl; ++lv) {  // root -> leaves
-      const HsMultiLevel& L = v.levels[lv];
-      if (v.hss_front && !act)
-        for (int id : L.hss) v.hss_front(v.hss_ctx, id, 1, 0, a.B, a.ldb, kc, s);
-      if (L.nfronts == 0 || L.maxni == 0) continue;
-      const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 1);
-      if (q_.nf == 0 || q_.maxni == 0) continue;
-      const SolveNode<T>* sn = (const SolveNode<T>*)q_.sn;
-      const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
-      a.wbase = L.wbase;
-      a.aux = q_.aux;
-      launch_multi_move<T>(sn, nf, 1, maxnb, a, s);
-      launch_multi_level<T>(sn, nf, HSM_UR, 0, maxni, a, s);
-      for (const HsMultiLR& q : L.lr) {
-        if (!q.lrR || !q_.has(q.pos)) continue;
-        const LowRank<T>& lr = *(const LowRank<T>*)q.lrR;
-        if (lr.r == 0) continue;
-        lr_apply<T>(lr, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
-      }
-      const int nblk = (maxni + 255) / 256;
-      for (int j = nblk - 1; j >= 0; --j) {
-        launch_multi_level<T>(sn, nf, HSM_DIAG_U, j, std::min(256, maxni - j * 256), a, s);
-        launch_multi_level<T>(sn, nf, HSM_ABOVE_U, j, j * 256, a, s);
-      }
-      launch_multi_move<T>(sn, nf, 2, maxni, a, s);
-      each_front(L, q_, [&](const HsMultiFront& f) {
-        if (f.dense_bnd) fc.add(f.ni, f.nb, kc);
-        for (int j = 0; j * 256 < f.ni; ++j) {
-          const double wl = std::min(256, f.ni - j * 256);
-          fc.add(wl, wl, kc, wl * (wl + 1) / 2);
-          fc.add(j * 256, wl, kc);
-        }
-      });
-    }
-    if (act && act->end) act->end(act->ctx, chunks, kc, s);
-  }
-  multi_finish(mc, v, fc, chunks, sizeof(T), s);
-}
-template void hs_solve_multi_run<double>(const HsMultiView&, double*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
-template void hs_solve_multi_run<cplx>(const HsMultiView&, cplx*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
-
-// transpose(F) \ B and adjoint(F) \ B: the same chunks, work blocks and stored blocks, every product with the factor panel transposed
-// (kernels_solve_multi_t.hip).  op(x) = x (trans = 1) or conj(x) (trans = 2: the factor entries are conjugated as they are loaded).  Per chunk:
+// op(F) \ B with op = identity (trans = 0), transpose (1) or adjoint (2): the same chunks, work blocks and stored blocks.  trans = 0 is the
+// schedule at the head of this file.  trans = 1, 2 run every product with the factor panel transposed (kernels_solve_multi_t.hip), U and L
+// changing places; op(x) = x or conj(x) (trans = 2: the factor entries are conjugated as they are loaded).  Per chunk:
 //
 //   forward, leaves -> root, per level:   W = B[int, :] (no permutation),  Xb = B[bnd, :];   per 256-block j:  Z_j = op(inv256U_j)^T W_j,
 //                                         W[below j] -= op(U11[j, below])^T Z_j;   Xb -= op(Uib)^T Z  (low-rank: -= op(Z_R)^T (op(G)^T Z));
@@ -334,14 +263,15 @@ template void hs_solve_multi_run<cplx>(const HsMultiView&, cplx*, int64_t, int64
 //                                         B[int[rperm[i]], :] = X[i, :]
 //
 // Right-looking like the forward solve: the update of a step reads the ROW panel U11[j, below] / L11[j, above] -- 256 contiguous doubles
-// per output row -- and has (ni - 256 (j + 1)) / 64 workgroups.  The left-looking order (HS_LDIV_BLOCK_T_LOOK=left) reads the column panel
-// above / below the block with K up to ni and 256 outputs: W is written once per block, by four workgroups per front (DESIGN.md section 4a⁗″).
+// per output row -- and has (ni - 256 (j + 1)) / 64 workgroups.  The left-looking order (HS_LDIV_BLOCK_T_LOOK=left, trans = 1, 2 only) reads the
+// column panel above / below the block with K up to ni and 256 outputs: W is written once per block, by four workgroups per front
+// (DESIGN.md section 4a⁗″).
 template <class T>
-void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act) {
+void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act) {
   const int KC = hs_ldiv_block_cols();
   const int kcw = KC;
   const int cj = (trans == 2 && sizeof(T) == 16) ? 1 : 0;
-  const bool left = multi_t_left_looking();
+  const bool left = trans && multi_t_left_looking();
   MultiCache* mc = multi_prepare<T>(v, kcw);
   FlopCount fc;
   fc.tr = hs_multi_rows_per_wg(sizeof(T) == 16);
@@ -366,16 +296,16 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
       const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
       a.aux = q_.aux;
-      launch_multi_move_t<T>(sn, nf, 0, maxni, a, s);
-      launch_multi_move_t<T>(sn, nf, 1, maxnb, a, s);
+      level_move<T>(trans, sn, nf, 0, maxni, a, s);
+      level_move<T>(trans, sn, nf, 1, maxnb, a, s);
       const int nblk = (maxni + 255) / 256;
       for (int j = 0; j < nblk; ++j) {
         const int wl = std::min(256, maxni - j * 256);
         if (left && j > 0) launch_multi_level_t<T>(sn, nf, HSMT_LEFT_U, j, cj, wl, a, s);
-        launch_multi_level_t<T>(sn, nf, HSMT_DIAG_U, j, cj, wl, a, s);
-        if (!left) launch_multi_level_t<T>(sn, nf, HSMT_BELOW_U, j, cj, maxni - (j + 1) * 256, a, s);
+        level_step<T>(trans, cj, sn, nf, HSM_DIAG_L, HSMT_DIAG_U, j, wl, a, s);
+        if (!left) level_step<T>(trans, cj, sn, nf, HSM_BELOW_L, HSMT_BELOW_U, j, maxni - (j + 1) * 256, a, s);
       }
-      launch_multi_level_t<T>(sn, nf, HSMT_BND_U, 0, cj, maxnb, a, s);
+      level_step<T>(trans, cj, sn, nf, HSM_BND_L, HSMT_BND_U, 0, maxnb, a, s);
       each_front(L, q_, [&](const HsMultiFront& f) {
         for (int j = 0; j * 256 < f.ni; ++j) {
           const double wl = std::min(256, f.ni - j * 256);
@@ -387,13 +317,14 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
         }
         if (f.dense_bnd) fc.add(f.nb, f.ni, kc);
       });
-      for (const HsMultiLR& q : L.lr) {
-        if (!q.lrR || !q_.has(q.pos)) continue;
-        const LowRank<T>& lr = *(const LowRank<T>*)q.lrR;
+      for (const HsMultiLR& q : L.lr) {  // the transform of this sweep: Lbi, transposed Uib
+        const void* tr = trans ? q.lrR : q.lrL;
+        if (!tr || !q_.has(q.pos)) continue;
+        const LowRank<T>& lr = *(const LowRank<T>*)tr;
         if (lr.r == 0) continue;
-        lr_apply_t<T>(lr, cj, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+        lr_apply_op<T>(trans, cj, lr, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
-      launch_multi_move_t<T>(sn, nf, 3, maxnb, a, s);
+      level_move<T>(trans, sn, nf, 3, maxnb, a, s);
     }
     if (act && act->zoff[chunks + 1] > act->zoff[chunks])  // backward-only fronts: y = 0
       launch_sparse_zero<T>((T*)mc->W2, kcw, kc, act->zseg + act->zoff[chunks], (int)(act->zoff[chunks + 1] - act->zoff[chunks]), act->zmaxni[chunks], s);
@@ -408,22 +339,23 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
       const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
       a.aux = q_.aux;
-      launch_multi_move_t<T>(sn, nf, 1, maxnb, a, s);
-      launch_multi_level_t<T>(sn, nf, HSMT_LB, 0, cj, maxni, a, s);
-      for (const HsMultiLR& q : L.lr) {
-        if (!q.lrL || !q_.has(q.pos)) continue;
-        const LowRank<T>& lr = *(const LowRank<T>*)q.lrL;
+      level_move<T>(trans, sn, nf, 1, maxnb, a, s);
+      level_step<T>(trans, cj, sn, nf, HSM_UR, HSMT_LB, 0, maxni, a, s);
+      for (const HsMultiLR& q : L.lr) {  // Uib, transposed Lbi
+        const void* tr = trans ? q.lrL : q.lrR;
+        if (!tr || !q_.has(q.pos)) continue;
+        const LowRank<T>& lr = *(const LowRank<T>*)tr;
         if (lr.r == 0) continue;
-        lr_apply_t<T>(lr, cj, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+        lr_apply_op<T>(trans, cj, lr, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
       const int nblk = (maxni + 255) / 256;
       for (int j = nblk - 1; j >= 0; --j) {
         const int wl = std::min(256, maxni - j * 256);
         if (left) launch_multi_level_t<T>(sn, nf, HSMT_LEFT_L, j, cj, 256, a, s);
-        launch_multi_level_t<T>(sn, nf, HSMT_DIAG_L, j, cj, wl, a, s);
-        if (!left) launch_multi_level_t<T>(sn, nf, HSMT_ABOVE_L, j, cj, j * 256, a, s);
+        level_step<T>(trans, cj, sn, nf, HSM_DIAG_U, HSMT_DIAG_L, j, wl, a, s);
+        if (!left) level_step<T>(trans, cj, sn, nf, HSM_ABOVE_U, HSMT_ABOVE_L, j, j * 256, a, s);
       }
-      launch_multi_move_t<T>(sn, nf, 2, maxni, a, s);
+      level_move<T>(trans, sn, nf, 2, maxni, a, s);
       each_front(L, q_, [&](const HsMultiFront& f) {
         if (f.dense_bnd) fc.add(f.ni, f.nb, kc);
         for (int j = 0; j * 256 < f.ni; ++j) {
@@ -440,8 +372,8 @@ void hs_solve_multi_run_t(const HsMultiView& v, int trans, T* dC, int64_t ldc, i
   }
   multi_finish(mc, v, fc, chunks, sizeof(T), s);
 }
-template void hs_solve_multi_run_t<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
-template void hs_solve_multi_run_t<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
+template void hs_solve_multi_run<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
+template void hs_solve_multi_run<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
 
 double hs_solve_multi_seconds(void* mx) {
   MultiCache* mc = (MultiCache*)mx;

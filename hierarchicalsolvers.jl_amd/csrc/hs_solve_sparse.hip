@@ -243,10 +243,7 @@ void hs_solve_sparse_run(const HsMultiView& v, const HsSparseTree& t, int trans,
     A.ctx = &cx;
     A.begin = chunk_begin<T>;
     A.end = chunk_end<T>;
-    if (trans == 0)
-      hs_solve_multi_run<T>(v, W, n, nrhs, s, &A);
-    else
-      hs_solve_multi_run_t<T>(v, trans, W, n, nrhs, s, &A);
+    hs_solve_multi_run<T>(v, trans, W, n, nrhs, s, &A);
     HS_HIP(hipStreamSynchronize(s));  // the lists and the chunk go back to the scratch cache
   } catch (...) {
     (void)hipStreamSynchronize(s);

@@ -355,18 +355,17 @@ def adjoint(F):
     return _wrap(F, True)
 
 
-def ldiv(*args):
-    """``ldiv!(F, B)`` / ``ldiv!(C, F, B)`` (factornode.jl:62-74): ``C = F^-1 B`` for a vector or an
-    ``n x nrhs`` matrix.  The 2-argument form returns a new array like the reference (which
-    allocates ``similar(B)``, factornode.jl:62); the 3-argument form writes into ``C`` (``C`` may be ``B``).
-    ``F`` may be ``transpose(F)`` or ``adjoint(F)``: then ``C = F^-T B`` / ``C = F^-H B``."""
+def _ldiv_dense(name, sym, args):
+    """The body of :func:`ldiv`, :func:`ldiv_block`, :func:`ldiv_block_t` and :func:`ldiv_ulv`: ``(F, B)`` or ``(C, F, B)`` with ``F`` possibly
+    wrapped by :func:`transpose` / :func:`adjoint`, the shape and dtype rules of ``ldiv!``, column-major staging, one call of
+    ``<sym>_d`` / ``<sym>_z`` with ``trans``.  ``sym`` None: ``hs_ldiv_*`` for a plain ``F``, ``hs_ldiv_t_*`` otherwise."""
     if len(args) == 2:
         F, B = args
         Cout = None
     elif len(args) == 3:
         Cout, F, B = args
     else:
-        raise TypeError("ldiv(F, B) or ldiv(C, F, B)")
+        raise TypeError(f"{name}(F, B) or {name}(C, F, B)")
     trans = 0
     if isinstance(F, TransposedFactor):
         F, trans = F.parent, F.trans
@@ -380,18 +379,24 @@ def ldiv(*args):
     vec = B.ndim == 1
     Bm = np.asfortranarray(B.reshape(F.n, -1))
     Cm = np.empty_like(Bm, order="F")
-    L = _lib.lib()
-    if trans:
-        fn = L.hs_ldiv_t_z if F.dtype.kind == "c" else L.hs_ldiv_t_d
-        _lib.check(fn(F._h, trans, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
-    else:
-        fn = L.hs_ldiv_z if F.dtype.kind == "c" else L.hs_ldiv_d
-        _lib.check(fn(F._h, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
+    if sym is None:
+        sym = "hs_ldiv_t" if trans else "hs_ldiv"
+    fn = getattr(_lib.lib(), sym + ("_z" if F.dtype.kind == "c" else "_d"))
+    head = (F._h,) if sym == "hs_ldiv" else (F._h, trans)  # hs_ldiv_* is the one entry without a trans argument
+    _lib.check(fn(*head, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
     res = Cm[:, 0] if vec else Cm
     if Cout is not None:
         Cout[...] = res
         return Cout
     return res
+
+
+def ldiv(*args):
+    """``ldiv!(F, B)`` / ``ldiv!(C, F, B)`` (factornode.jl:62-74): ``C = F^-1 B`` for a vector or an
+    ``n x nrhs`` matrix.  The 2-argument form returns a new array like the reference (which
+    allocates ``similar(B)``, factornode.jl:62); the 3-argument form writes into ``C`` (``C`` may be ``B``).
+    ``F`` may be ``transpose(F)`` or ``adjoint(F)``: then ``C = F^-T B`` / ``C = F^-H B``."""
+    return _ldiv_dense("ldiv", None, args)
 
 
 def ldiv_block(*args):
@@ -400,68 +405,14 @@ def ldiv_block(*args):
     the factors are read once per chunk instead of once per column.  ``F`` must be a plain :class:`FactorNode` whose fronts keep a dense LU
     of their interior block (``transpose(F)`` / ``adjoint(F)`` -- served by :func:`ldiv_block_t` -- and HSS interior blocks raise
     :class:`UnsupportedError`)."""
-    if len(args) == 2:
-        F, B = args
-        Cout = None
-    elif len(args) == 3:
-        Cout, F, B = args
-    else:
-        raise TypeError("ldiv_block(F, B) or ldiv_block(C, F, B)")
-    trans = 0
-    if isinstance(F, TransposedFactor):
-        F, trans = F.parent, F.trans
-    B = np.asarray(B)
-    if B.shape[0] != F.n:
-        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
-    if B.dtype != F.dtype:
-        if F.dtype.kind == "f" and B.dtype.kind == "c":
-            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::FactorNode{Float64}, ::Array{ComplexF64})")
-        B = B.astype(F.dtype)
-    vec = B.ndim == 1
-    Bm = np.asfortranarray(B.reshape(F.n, -1))
-    Cm = np.empty_like(Bm, order="F")
-    L = _lib.lib()
-    fn = L.hs_ldiv_block_z if F.dtype.kind == "c" else L.hs_ldiv_block_d
-    _lib.check(fn(F._h, trans, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
-    res = Cm[:, 0] if vec else Cm
-    if Cout is not None:
-        Cout[...] = res
-        return Cout
-    return res
+    return _ldiv_dense("ldiv_block", "hs_ldiv_block", args)
 
 
 def ldiv_block_t(*args):
     """``ldiv!(F, B)`` / ``ldiv!(C, F, B)`` with ``F`` a :class:`FactorNode`, ``transpose(F)`` or ``adjoint(F)``, through the block solve
     (``hs_ldiv_block_t_*``): the arguments and results of :func:`ldiv_block`, the columns travelling through the tree together in both
     directions.  A plain ``F`` returns the bits of :func:`ldiv_block`.  The same handles are served as there."""
-    if len(args) == 2:
-        F, B = args
-        Cout = None
-    elif len(args) == 3:
-        Cout, F, B = args
-    else:
-        raise TypeError("ldiv_block_t(F, B) or ldiv_block_t(C, F, B)")
-    trans = 0
-    if isinstance(F, TransposedFactor):
-        F, trans = F.parent, F.trans
-    B = np.asarray(B)
-    if B.shape[0] != F.n:
-        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
-    if B.dtype != F.dtype:
-        if F.dtype.kind == "f" and B.dtype.kind == "c":
-            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::FactorNode{Float64}, ::Array{ComplexF64})")
-        B = B.astype(F.dtype)
-    vec = B.ndim == 1
-    Bm = np.asfortranarray(B.reshape(F.n, -1))
-    Cm = np.empty_like(Bm, order="F")
-    L = _lib.lib()
-    fn = L.hs_ldiv_block_t_z if F.dtype.kind == "c" else L.hs_ldiv_block_t_d
-    _lib.check(fn(F._h, trans, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
-    res = Cm[:, 0] if vec else Cm
-    if Cout is not None:
-        Cout[...] = res
-        return Cout
-    return res
+    return _ldiv_dense("ldiv_block_t", "hs_ldiv_block_t", args)
 
 
 def ldiv_ulv(*args):
@@ -469,34 +420,7 @@ def ldiv_ulv(*args):
     (``hs_ldiv_ulv_*``): the block solve that also serves fronts whose interior block ``D`` is held as an HSS matrix (``hss_d``,
     ``mf = 2, 3``) -- one ULV solve with ``D`` (transposed: from the same stored factors) per front and chunk of columns.  A handle
     without such fronts returns the bits of :func:`ldiv_block_t`."""
-    if len(args) == 2:
-        F, B = args
-        Cout = None
-    elif len(args) == 3:
-        Cout, F, B = args
-    else:
-        raise TypeError("ldiv_ulv(F, B) or ldiv_ulv(C, F, B)")
-    trans = 0
-    if isinstance(F, TransposedFactor):
-        F, trans = F.parent, F.trans
-    B = np.asarray(B)
-    if B.shape[0] != F.n:
-        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {F.n} x {F.n}")
-    if B.dtype != F.dtype:
-        if F.dtype.kind == "f" and B.dtype.kind == "c":
-            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::FactorNode{Float64}, ::Array{ComplexF64})")
-        B = B.astype(F.dtype)
-    vec = B.ndim == 1
-    Bm = np.asfortranarray(B.reshape(F.n, -1))
-    Cm = np.empty_like(Bm, order="F")
-    L = _lib.lib()
-    fn = L.hs_ldiv_ulv_z if F.dtype.kind == "c" else L.hs_ldiv_ulv_d
-    _lib.check(fn(F._h, trans, Cm.ctypes.data_as(_lib.p_f64), F.n, Bm.ctypes.data_as(_lib.p_f64), F.n, F.n, Bm.shape[1]))
-    res = Cm[:, 0] if vec else Cm
-    if Cout is not None:
-        Cout[...] = res
-        return Cout
-    return res
+    return _ldiv_dense("ldiv_ulv", "hs_ldiv_ulv", args)
 
 
 def ldiv_block_info(F):

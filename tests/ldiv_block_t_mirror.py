@@ -1,4 +1,4 @@
-"""NumPy statement of the schedule of the transposed / adjoint block solve (csrc/hs_solve_multi.hip: hs_solve_multi_run_t) over the fronts
+"""NumPy statement of the schedule of the transposed / adjoint block solve (csrc/hs_solve_multi.hip: hs_solve_multi_run with trans = 1, 2) over the fronts
 of tests/ldiv_block_mirror.py (P D = L11 U11, Lbi = Abi U11^-1, Uib = L11^-1 P Aib, the inverses of the 256 x 256 diagonal blocks).
 
 With op(x) = x for transpose(F) and conj(x) for adjoint(F), per chunk of `kc` columns

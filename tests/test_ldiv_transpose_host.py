@@ -2,6 +2,7 @@
 problems, and the refusals that the library names from a host-side plan (hs_plan) before any device work."""
 import ctypes as C
 import hashlib
+import re
 
 import numpy as np
 import pytest
@@ -157,6 +158,95 @@ def test_refusals_are_named_before_device_work(hs):
         assert "not complete" in L.hs_last_error().decode()
     finally:
         L.hs_free(h)
+
+
+BLOCK_ENTRIES = ("hs_ldiv_block_d", "hs_ldiv_block_t_d", "hs_ldiv_ulv_d", "hs_ldiv_sparse_d")
+TRANS = (-1, 0, 1, 2, 3)
+
+
+_UNFACTORED = (-1, 0, None, "not complete")
+
+
+def _rows(name, t0, t12):
+    """trans = -1 and 3 are refused under the entry point's name with trans as the info value; t0 / t12: what trans = 0 / trans = 1, 2 return."""
+    t1, t2 = t12 if isinstance(t12, list) else (t12, t12)
+    return [(-1, -1, name, "trans"), t0, t1, t2, (-1, 3, name, "trans")]
+
+
+_BLOCK = _rows("hs_ldiv_block_*", _UNFACTORED, [(-8, 1, "hs_ldiv_block_*", "trans"), (-8, 2, "hs_ldiv_block_*", "trans")])
+_BLOCK_T = _rows("hs_ldiv_block_t_*", _UNFACTORED, _UNFACTORED)
+# recorded on the commit before the checks were folded (-1: HS_ERR_ARGUMENT, -8: HS_ERR_UNSUPPORTED)
+REFUSALS = {
+    ("rank0of2", "hs_ldiv_block_d"): _BLOCK,
+    ("rank0of2", "hs_ldiv_block_t_d"): _BLOCK_T,
+    ("rank0of2", "hs_ldiv_ulv_d"): _rows("hs_ldiv_ulv_*", (-8, 0, "hs_ldiv_ulv_*", "ranks"), (-8, 0, "hs_ldiv_ulv_*", "ranks")),
+    ("rank0of2", "hs_ldiv_sparse_d"): _rows("hs_ldiv_sparse_*", (-8, 0, "hs_ldiv_sparse_*", "ranks"), (-8, 0, "hs_ldiv_sparse_*", "ranks")),
+    ("rank1of2_dist_top", "hs_ldiv_block_d"): _BLOCK,
+    ("rank1of2_dist_top", "hs_ldiv_block_t_d"): _BLOCK_T,
+    ("rank1of2_dist_top", "hs_ldiv_ulv_d"): _rows("hs_ldiv_ulv_*", (-8, 0, "hs_ldiv_ulv_*", "ranks"), (-8, 0, "hs_ldiv_ulv_*", "ranks")),
+    ("rank1of2_dist_top", "hs_ldiv_sparse_d"): _rows("hs_ldiv_sparse_*", (-8, 0, "hs_ldiv_sparse_*", "ranks"), (-8, 0, "hs_ldiv_sparse_*", "ranks")),
+    ("single", "hs_ldiv_block_d"): _BLOCK,
+    ("single", "hs_ldiv_block_t_d"): _BLOCK_T,
+    ("single", "hs_ldiv_ulv_d"): _rows("hs_ldiv_ulv_*", _UNFACTORED, _UNFACTORED),
+    ("single", "hs_ldiv_sparse_d"): _rows("hs_ldiv_sparse_*", _UNFACTORED, _UNFACTORED),
+    ("mf2", "hs_ldiv_block_d"): _BLOCK,
+    ("mf2", "hs_ldiv_block_t_d"): _BLOCK_T,
+    ("mf2", "hs_ldiv_ulv_d"): _rows("hs_ldiv_ulv_*", _UNFACTORED, _UNFACTORED),
+    ("mf2", "hs_ldiv_sparse_d"): _rows("hs_ldiv_sparse_*", (-8, 126, "hs_ldiv_sparse_*", "HSS"), (-8, 126, "hs_ldiv_sparse_*", "HSS")),
+    ("mf3", "hs_ldiv_block_d"): _BLOCK,
+    ("mf3", "hs_ldiv_block_t_d"): _BLOCK_T,
+    ("mf3", "hs_ldiv_ulv_d"): _rows("hs_ldiv_ulv_*", _UNFACTORED, _UNFACTORED),
+    ("mf3", "hs_ldiv_sparse_d"): _rows("hs_ldiv_sparse_*", (-8, 62, "hs_ldiv_sparse_*", "HSS"), (-8, 62, "hs_ldiv_sparse_*", "HSS")),
+}
+
+
+def _refusal(hs, h, entry, trans, n):
+    """(status, hs_last_error_info(), the entry-point name the message prints, its discriminating word) of one call on a plan-only handle."""
+    L = hs._lib.lib()
+    pf, pi = hs._lib.p_f64, hs._lib.p_i64
+    b = np.zeros(n)
+    if entry == "hs_ldiv_sparse_d":
+        cp, rv, val = np.array([1, 2], dtype=np.int64), np.array([1], dtype=np.int64), np.ones(1)
+        st = L.hs_ldiv_sparse_d(h, trans, n, 1, cp.ctypes.data_as(pi), rv.ctypes.data_as(pi), val.ctypes.data_as(pf), None, 0, b.ctypes.data_as(pf), n)
+    else:
+        st = getattr(L, entry)(h, trans, b.ctypes.data_as(pf), n, b.ctypes.data_as(pf), n, n, 1)
+    msg = L.hs_last_error().decode()
+    name = re.search(r"hs_ldiv_\w+_\*", msg)
+    word = next((w for w in ("ranks", "HSS", "not complete", "trans") if w in msg), None)  # ("transposed" in the first two: they come first)
+    return (st, int(L.hs_last_error_info()), name.group(0) if name else None, word)
+
+
+def _refusal_table(hs):
+    P = prepare(hs, (20, 12), kind="convdiff", nmax=10)
+    P3 = prepare(hs, (32, 32, 32), kind="convdiff", nmax=512)
+    handles = [
+        ("rank0of2", P, dict(rank=0, nranks=2)),
+        ("rank1of2_dist_top", P, dict(rank=1, nranks=2, dist_top=True)),
+        ("single", P, dict()),
+        ("mf2", P3, dict(swlevel=2, swsize=8, atol=1e-6, rtol=1e-6, mf=2, leafsize=128)),
+        ("mf3", P3, dict(swlevel=3, swsize=8, atol=1e-6, rtol=1e-6, mf=3, leafsize=128)),
+    ]
+    table = {}
+    for hname, Pr, kw in handles:
+        h = _plan(hs, Pr, **kw)
+        try:
+            for entry in BLOCK_ENTRIES:
+                table[(hname, entry)] = [_refusal(hs, h, entry, t, Pr["A"].shape[0]) for t in TRANS]
+        finally:
+            hs._lib.lib().hs_free(h)
+    return table
+
+
+def test_block_refusals_keep_their_order_and_names(hs):
+    """What hs_ldiv_block_d / hs_ldiv_block_t_d / hs_ldiv_ulv_d / hs_ldiv_sparse_d answer on the plan-only handles of the test above for trans = -1, 0,
+    1, 2, 3: status, hs_last_error_info(), the entry point the message names and the word that tells the refusals apart.  The entry points run
+    their checks in different orders (e.g. hs_ldiv_block_* names an unfactored handle before its ranks, hs_ldiv_ulv_* the other way round);
+    the values are the ones recorded before the checks were folded into shared pieces."""
+    got = _refusal_table(hs)
+    assert sorted(got) == sorted(REFUSALS)
+    for key in sorted(REFUSALS):
+        for t, g, want in zip(TRANS, got[key], REFUSALS[key]):
+            assert g == want, (key, t, g, want)
 
 
 def test_plan_bytes_do_not_change(hs):
