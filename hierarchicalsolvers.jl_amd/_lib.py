@@ -85,6 +85,9 @@ EXPORTS = [
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
     "hs_logabsdet", "hs_selinv", "hs_selinv_info",
     "hs_sens_d", "hs_sens_z", "hs_sens_dev_d", "hs_sens_dev_z", "hs_misfit_d", "hs_misfit_z", "hs_misfit_dev_d", "hs_misfit_dev_z", "hs_sens_info", "hsk_sddmm_d", "hsk_sddmm_z",
+    "hs_mod_create_d", "hs_mod_create_z", "hs_mod_create_dev_d", "hs_mod_create_dev_z", "hs_mod_create_sparse_d", "hs_mod_create_sparse_z", "hs_mod_ldiv_d", "hs_mod_ldiv_z",
+    "hs_mod_ldiv_dev_d", "hs_mod_ldiv_dev_z", "hs_mod_info", "hs_mod_free", "hs_gmres_block_mod_d", "hs_gmres_block_mod_z",
+    "hsk_mod_inner_d", "hsk_mod_inner_z", "hsk_mod_apply_d", "hsk_mod_apply_z", "hsk_mod_gather_d", "hsk_mod_gather_z", "hsk_mod_cap_d", "hsk_mod_cap_z",
     "hs_maxrank", "hs_is_complex", "hs_size", "hs_free", "hs_last_error", "hs_last_error_info", "hs_get_stats",
     "hs_node_info", "hs_node_ranks", "hs_node_export", "hs_node_export_piv", "hs_device_info",
     "hs_analyze", "hs_plan", "hs_numeric_begin", "hs_numeric_levels", "hs_numeric_end", "hs_solve_fwd_levels", "hs_solve_bwd_levels",
@@ -209,6 +212,40 @@ def lib():
     L.hs_sens_info.restype = C.c_int
     for f in (L.hsk_sddmm_d, L.hsk_sddmm_z):
         f.argtypes = [i64, p_i64, p_i64, i64, vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, p_f64]
+        f.restype = C.c_int
+    for f in (L.hs_mod_create_d, L.hs_mod_create_z):
+        f.argtypes = [vp, i64, i64, vp, i64, vp, i64, C.POINTER(vp)]
+        f.restype = C.c_int
+    for f in (L.hs_mod_create_dev_d, L.hs_mod_create_dev_z):
+        f.argtypes = [vp, i64, i64, vp, i64, vp, i64, vp, C.POINTER(vp)]
+        f.restype = C.c_int
+    for f in (L.hs_mod_create_sparse_d, L.hs_mod_create_sparse_z):
+        f.argtypes = [vp, i64, p_i64, p_i64, vp, C.POINTER(vp)]
+        f.restype = C.c_int
+    for f in (L.hs_mod_ldiv_d, L.hs_mod_ldiv_z):
+        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
+        f.restype = C.c_int
+    for f in (L.hs_mod_ldiv_dev_d, L.hs_mod_ldiv_dev_z):
+        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
+        f.restype = C.c_int
+    L.hs_mod_info.argtypes = [vp, p_f64]
+    L.hs_mod_info.restype = C.c_int
+    L.hs_mod_free.argtypes = [vp]
+    L.hs_mod_free.restype = None
+    for f in (L.hs_gmres_block_mod_d, L.hs_gmres_block_mod_z):
+        f.argtypes = [vp, C.c_int, i64, p_i64, p_i64, vp, vp, i64, vp, i64, i64, C.c_int, C.c_int, C.c_double, C.c_double, i64, i64, p_f64, p_i64, C.POINTER(C.c_int), vp]
+        f.restype = C.c_int
+    for f in (L.hsk_mod_inner_d, L.hsk_mod_inner_z):
+        f.argtypes = [i64, i64, i64, vp, i64, vp, i64, C.c_int, vp, i64]
+        f.restype = C.c_int
+    for f in (L.hsk_mod_apply_d, L.hsk_mod_apply_z):
+        f.argtypes = [i64, i64, i64, vp, i64, vp, i64, vp, i64, C.c_int]
+        f.restype = C.c_int
+    for f in (L.hsk_mod_gather_d, L.hsk_mod_gather_z):
+        f.argtypes = [i64, i64, i64, vp, i64, p_i64, vp, i64]
+        f.restype = C.c_int
+    for f in (L.hsk_mod_cap_d, L.hsk_mod_cap_z):
+        f.argtypes = [i64, i64, vp, i64, C.c_int, vp, i64]
         f.restype = C.c_int
     L.hs_logabsdet.argtypes = [vp, p_f64, p_f64]
     L.hs_logabsdet.restype = C.c_int

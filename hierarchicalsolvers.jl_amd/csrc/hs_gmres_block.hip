@@ -18,7 +18,8 @@
 //
 // hs_gmres_block_t_* runs the same schedule on op(A) X = B right-preconditioned by op(Pr): gmres_group is a template on the operator (the CSR
 // SpMM below, or the SpMM over "entry ranges as rows" of hs_gmres_common.h) and on the preconditioner call (hs_ldiv_block_dev_* /
-// hs_ldiv_block_dev_t_*); A is passed as host CSC arrays or is the handle's own (hs_gmres_op.h).
+// hs_ldiv_block_dev_t_*); A is passed as host CSC arrays or is the handle's own (hs_gmres_op.h).  hs_gmres_block_mod_* is one more pair of
+// instantiations: op(A1) X = B with A1 = A + U V^H as host CSC arrays, the preconditioner call hs_mod_ldiv_dev_* (hs_mod.hip).
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -27,6 +28,7 @@
 #include "../../include/hs_kernels.h"
 #include "hs_gmres_common.h"
 #include "hs_solve_multi.h"
+#include "hs_mod.h"  // hs_mod_apply_prec, hs_mod_handle
 
 namespace {
 
@@ -324,6 +326,13 @@ template <class T>
 struct PrecBlockFwd {  // hs_ldiv_block_dev_*
   hs_handle* F;
   int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return prec_block<T>(F, out, in, ld, n, nc, s); }
+};
+template <class T>
+struct PrecBlockMod {  // hs_mod_ldiv_dev_*: op(A + U V^H)^-1 through the factors of A
+  hs_handle* F;       // the handle the modification was built on: what gmres_group reads as Pr.F (non-null: there is a preconditioner)
+  hs_mod* M;
+  int trans;
+  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return hs_mod_apply_prec(M, trans, out, ld, in, ld, n, nc, s); }
 };
 template <class T>
 struct PrecBlockOp {  // hs_ldiv_block_dev_t_*: op(F)
@@ -737,6 +746,48 @@ int gmres_block_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colpt
   return gmres_block_run<T>(make_op, PrecBlockOp<T>{F, trans}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
+// hs_gmres_block_mod_*: op(A1) X = B right-preconditioned by op(A1)^-1 as hs_mod_ldiv_dev_* applies it; A1 is the caller's CSC
+template <class T>
+int gmres_block_mod_entry(hs_mod* M, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs,
+                          int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  const char* fn = "hs_gmres_block_mod_*";
+  if (!M) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null hs_mod", fn);
+    return HS_ERR_ARGUMENT;
+  }
+  if (trans < 0 || trans > 2) {
+    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: A1, 1: transpose(A1), 2: adjoint(A1))", fn, trans);
+    return HS_ERR_ARGUMENT;
+  }
+  if (!colptr || !rowval || !nz) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: the modified matrix A1 must be given as CSC (the handle holds the unmodified A)", fn);
+    return HS_ERR_ARGUMENT;
+  }
+  if (n <= 0 || nrhs < 0) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs n >= 1 and nrhs >= 0", fn);
+    return HS_ERR_ARGUMENT;
+  }
+  if (nrhs == 0) {
+    for (double& v : g_info) v = 0.0;
+    return HS_OK;
+  }
+  hs_handle* F = hs_mod_handle(M);
+  if (const int st = gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
+  const PrecBlockMod<T> Pr{F, M, trans};
+  if (trans == 0) {
+    auto make_op = [&](DevBuf& buf, hipStream_t) {
+      int64_t* d_rp;
+      int32_t* d_ci;
+      T* d_v;
+      upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+      return CsrSpmm<T>{d_rp, d_ci, d_v};
+    };
+    return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  }
+  auto make_op = [&](DevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, false, n, colptr, rowval, nz, s)}; };
+  return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+
 // hsk_spmm_*: the SpMM kernel alone on host data
 template <class T>
 int spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy, int64_t nrhs) {
@@ -866,4 +917,16 @@ extern "C" int hsk_spmm_op_d(int trans, int64_t n, const int64_t* colptr, const 
 extern "C" int hsk_spmm_op_z(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B,
                              int64_t ldb, double* Y, int64_t ldy, int64_t nrhs) {
   return spmm_op_hook<cplx>(trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)X, ldx, (const cplx*)B, ldb, (cplx*)Y, ldy, nrhs);
+}
+extern "C" int hs_gmres_block_mod_d(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
+                                    double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
+                                    double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_block_mod_entry<double>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                                       stream);
+}
+extern "C" int hs_gmres_block_mod_z(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
+                                    double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
+                                    double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_block_mod_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
+                                     maxiter, resnorm, iters, converged, stream);
 }

@@ -633,3 +633,143 @@ extern "C" int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t
   hs_leaf_envelope(colptr, rowval, fidx, (int)ni, (int)nb, where.data(), firstL, firstU);
   return 0;
 }
+
+// the kernels of hs_mod_* (kernels_mod.hip) on host data (include/hs_kernels.h)
+#include "hs_mod.h"
+namespace {
+struct ModBufs {
+  std::vector<void*> p;
+  ~ModBufs() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  template <class T>
+  T* up(const T* src, int64_t ld, int64_t rows, int64_t cols) {  // a rows x cols block as ld = max(rows, 1) on the device
+    void* q = nullptr;
+    const int64_t r = std::max<int64_t>(rows, 1);
+    if (hipMalloc(&q, sizeof(T) * (size_t)(r * std::max<int64_t>(cols, 1))) != hipSuccess) return nullptr;
+    p.push_back(q);
+    if (src && rows > 0 && cols > 0 && hipMemcpy2D(q, r * sizeof(T), src, ld * sizeof(T), rows * sizeof(T), cols, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return (T*)q;
+  }
+};
+int mod_hook_device() {
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
+    return HS_ERR_DEVICE;
+  }
+  return HS_OK;
+}
+}  // namespace
+#define MOD_NULL(q)                                                     \
+  if (!(q)) {                                                           \
+    hs_set_error(HS_ERR_NOMEM, 0, "hsk_mod_*: device staging failed");  \
+    return HS_ERR_NOMEM;                                                \
+  }
+
+template <class T>
+static int mod_inner_hook(int64_t n, int64_t k, int64_t m, const T* P, int64_t ldp, const T* Y, int64_t ldy, int conj, T* Tm, int64_t ldt) {
+  if (n < 1 || k < 1 || k > HS_MOD_MAXRANK || m < 1 || m > HS_MOD_MAXCOLS || ldp < n || ldy < n || ldt < k || !P || !Y || !Tm) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_mod_inner: n >= 1, k in 1..256, m in 1..64, leading dimensions and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  if (int st = mod_hook_device()) return st;
+  ModBufs b;
+  T* dP = b.up<T>(P, ldp, n, k);
+  T* dY = b.up<T>(Y, ldy, n, m);
+  T* dT = b.up<T>(nullptr, k, k, m);
+  T* dPart = b.up<T>(nullptr, 1, hs_mod_slabs(n) * k * m, 1);
+  MOD_NULL(dP && dY && dT && dPart);
+  launch_mod_inner<T>(dP, n, dY, n, n, (int)k, (int)m, conj, dPart, dT, k, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy2D(Tm, ldt * sizeof(T), dT, k * sizeof(T), k * sizeof(T), m, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+extern "C" int hsk_mod_inner_d(int64_t n, int64_t k, int64_t m, const double* P, int64_t ldp, const double* Y, int64_t ldy, int conj, double* T, int64_t ldt) {
+  return mod_inner_hook<double>(n, k, m, P, ldp, Y, ldy, conj, T, ldt);
+}
+extern "C" int hsk_mod_inner_z(int64_t n, int64_t k, int64_t m, const double* P, int64_t ldp, const double* Y, int64_t ldy, int conj, double* T, int64_t ldt) {
+  return mod_inner_hook<cplx>(n, k, m, (const cplx*)P, ldp, (const cplx*)Y, ldy, conj, (cplx*)T, ldt);
+}
+
+template <class T>
+static int mod_apply_hook(int64_t n, int64_t k, int64_t m, T* Y, int64_t ldy, const T* Z, int64_t ldz, const T* Tm, int64_t ldt, int conj) {
+  if (n < 1 || k < 1 || k > HS_MOD_MAXRANK || m < 1 || m > HS_MOD_MAXCOLS || ldy < n || ldz < n || ldt < k || !Y || !Z || !Tm) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_mod_apply: n >= 1, k in 1..256, m in 1..64, leading dimensions and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  if (int st = mod_hook_device()) return st;
+  ModBufs b;
+  T* dY = b.up<T>(Y, ldy, n, m);
+  T* dZ = b.up<T>(Z, ldz, n, k);
+  T* dT = b.up<T>(Tm, ldt, k, m);
+  MOD_NULL(dY && dZ && dT);
+  launch_mod_apply<T>(dY, n, dZ, n, dT, k, n, (int)k, (int)m, conj, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy2D(Y, ldy * sizeof(T), dY, n * sizeof(T), n * sizeof(T), m, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+extern "C" int hsk_mod_apply_d(int64_t n, int64_t k, int64_t m, double* Y, int64_t ldy, const double* Z, int64_t ldz, const double* T, int64_t ldt, int conj) {
+  return mod_apply_hook<double>(n, k, m, Y, ldy, Z, ldz, T, ldt, conj);
+}
+extern "C" int hsk_mod_apply_z(int64_t n, int64_t k, int64_t m, double* Y, int64_t ldy, const double* Z, int64_t ldz, const double* T, int64_t ldt, int conj) {
+  return mod_apply_hook<cplx>(n, k, m, (cplx*)Y, ldy, (const cplx*)Z, ldz, (const cplx*)T, ldt, conj);
+}
+
+template <class T>
+static int mod_gather_hook(int64_t n, int64_t k, int64_t m, const T* Y, int64_t ldy, const int64_t* J, T* Tm, int64_t ldt) {
+  if (n < 1 || k < 1 || m < 1 || ldy < n || ldt < k || !Y || !J || !Tm) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_mod_gather: n, k, m >= 1, leading dimensions and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  for (int64_t j = 0; j < k; ++j)
+    if (J[j] < 0 || J[j] >= n) {
+      hs_set_error(HS_ERR_DIMENSION, j, "hsk_mod_gather: J[%lld] = %lld outside 0:%lld", (long long)j, (long long)J[j], (long long)n - 1);
+      return HS_ERR_DIMENSION;
+    }
+  if (int st = mod_hook_device()) return st;
+  ModBufs b;
+  T* dY = b.up<T>(Y, ldy, n, m);
+  int64_t* dJ = b.up<int64_t>(J, k, k, 1);
+  T* dT = b.up<T>(nullptr, k, k, m);
+  MOD_NULL(dY && dJ && dT);
+  launch_mod_gather<T>(dT, k, dY, n, dJ, (int)k, (int)m, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy2D(Tm, ldt * sizeof(T), dT, k * sizeof(T), k * sizeof(T), m, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+extern "C" int hsk_mod_gather_d(int64_t n, int64_t k, int64_t m, const double* Y, int64_t ldy, const int64_t* J, double* T, int64_t ldt) {
+  return mod_gather_hook<double>(n, k, m, Y, ldy, J, T, ldt);
+}
+extern "C" int hsk_mod_gather_z(int64_t n, int64_t k, int64_t m, const double* Y, int64_t ldy, const int64_t* J, double* T, int64_t ldt) {
+  return mod_gather_hook<cplx>(n, k, m, (const cplx*)Y, ldy, J, (cplx*)T, ldt);
+}
+
+template <class T>
+static int mod_cap_hook(int64_t k, int64_t m, const T* C, int64_t ldc, int op, T* Tm, int64_t ldt) {
+  if (k < 1 || k > HS_MOD_MAXRANK || m < 1 || ldc < k || ldt < k || op < 0 || op > 2 || !C || !Tm) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_mod_cap: k in 1..256, m >= 1, op in 0..2, leading dimensions and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  if (int st = mod_hook_device()) return st;
+  ModBufs b;
+  T* dC = b.up<T>(C, ldc, k, k);
+  T* dT = b.up<T>(Tm, ldt, k, m);
+  int* dPiv = b.up<int>(nullptr, k + 1, k + 1, 1);
+  MOD_NULL(dC && dT && dPiv);
+  launch_mod_cap_lu<T>(dC, (int)k, (int)k, dPiv, dPiv + k, 0);
+  int info = 0;
+  CK(hipMemcpy(&info, dPiv + k, sizeof(int), hipMemcpyDeviceToHost));
+  if (info != 0) {
+    hs_set_error(HS_ERR_SINGULAR, info, "SingularException(%d): hsk_mod_cap: zero pivot", info);
+    return HS_ERR_SINGULAR;
+  }
+  launch_mod_cap_solve<T>(dC, (int)k, (int)k, dPiv, op, dT, k, (int)m, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy2D(Tm, ldt * sizeof(T), dT, k * sizeof(T), k * sizeof(T), m, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+extern "C" int hsk_mod_cap_d(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt) { return mod_cap_hook<double>(k, m, C, ldc, op, T, ldt); }
+extern "C" int hsk_mod_cap_z(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt) {
+  return mod_cap_hook<cplx>(k, m, (const cplx*)C, ldc, op, (cplx*)T, ldt);
+}

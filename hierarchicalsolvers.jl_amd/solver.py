@@ -433,6 +433,141 @@ def ldiv_block_info(F):
             "chunks": int(out[4]), "workspace_bytes": int(out[5])}
 
 
+class ModifiedFactor:
+    """``A + U V^H`` (or ``A + dA``) solved from the factorization of ``A`` (``hs_mod``, include/hs_solver.h): made by :func:`modify`, consumed
+    by :func:`ldiv_mod` and by ``gmres_block(A1, B, Pr=M)``.  Holds ``F`` (which therefore outlives it) and, on the device, ``U``, ``V`` (or
+    the modified columns), ``Z = F^-1 U`` and the LU of the ``k x k`` capacitance matrix ``C = I + V^H Z``."""
+
+    def __init__(self, handle, parent, k):
+        self._h = handle
+        self.parent = parent
+        self.k = int(k)
+
+    def __del__(self):
+        self.free()
+
+    def free(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _lib.lib().hs_mod_free(h)
+
+    @property
+    def n(self):
+        return self.parent.n
+
+    @property
+    def dtype(self):
+        return self.parent.dtype
+
+    @property
+    def shape(self):
+        return self.parent.shape
+
+    @property
+    def rcond(self):
+        """``1 / (||C||_1 ||C^-1||_1)`` of the capacitance matrix (1 for ``k = 0``): what the correction costs in accuracy."""
+        return self.info()["rcond"]
+
+    def info(self):
+        """``hs_mod_info``: rank, ``rcond``, seconds to build, device seconds of the last solve, device bytes held, whether ``W = F^-H V`` exists
+        (built by the first transposed solve), block-solve calls issued so far."""
+        out = np.zeros(8)
+        _lib.check(_lib.lib().hs_mod_info(self._h, _pf64(out)))
+        return {"k": int(out[0]), "rcond": float(out[1]), "build_seconds": float(out[2]), "solve_seconds": float(out[3]), "bytes": int(out[4]),
+                "has_w": bool(out[5]), "block_solves": int(out[6])}
+
+    def __repr__(self):
+        return f"ModifiedFactor{{{repr(self.parent)}, k={self.k}}}"
+
+
+def modify(F, U=None, V=None, dA=None):
+    """A :class:`ModifiedFactor` of ``A1 = A + U V^H`` (``U``, ``V``: ``n x k`` arrays, ``k <= 256``; Float64: ``V^T``) or of ``A1 = A + dA``
+    (``dA``: an ``n x n`` ``scipy.sparse`` matrix; its nonempty columns ``J`` give ``U = dA[:, J]``, ``V = I[:, J]``) from the factorization
+    ``F`` of ``A``, without refactoring (``hs_mod_create_*``).  Indices refer to the factored (already permuted) matrix.  ``F`` must be a
+    plain :class:`FactorNode` that :func:`ldiv_block_t` serves (:class:`UnsupportedError` otherwise, and for ``k > 256``: refactor);
+    a singular ``A1`` raises :class:`SingularException`."""
+    if not isinstance(F, FactorNode):
+        raise TypeError(f"expected a FactorNode, got {type(F).__name__}")
+    if dA is not None and (U is not None or V is not None):
+        raise ValueError("ArgumentError: modify takes either U and V or dA, not both")
+    if dA is None and (U is None) != (V is None):
+        raise ValueError("ArgumentError: modify needs both U and V")
+    n = F.n
+    sfx = "_z" if F.dtype.kind == "c" else "_d"
+    h = C.c_void_p()
+    if dA is not None:
+        if not sp.issparse(dA):
+            raise TypeError(f"expected a scipy.sparse matrix for dA, got {type(dA).__name__}")
+        if dA.shape != (n, n):
+            raise _lib.DimensionMismatch(f"DimensionMismatch: dA is {dA.shape[0]} x {dA.shape[1]}, F is {n} x {n}")
+        if F.dtype.kind == "f" and dA.dtype.kind == "c":
+            raise TypeError("MethodError: a ComplexF64 modification of a FactorNode{Float64}")
+        dA = sp.csc_matrix(dA, copy=True).astype(F.dtype)
+        dA.sum_duplicates()
+        dA.sort_indices()
+        colptr = np.ascontiguousarray(dA.indptr, dtype=np.int64) + 1
+        rowval = np.ascontiguousarray(dA.indices, dtype=np.int64) + 1
+        vals = np.ascontiguousarray(dA.data, dtype=F.dtype)
+        k = int(np.count_nonzero(np.diff(colptr)))
+        _lib.check(getattr(_lib.lib(), "hs_mod_create_sparse" + sfx)(F._h, n, _p64(colptr), _p64(rowval), vals.ctypes.data_as(C.c_void_p), C.byref(h)))
+        return ModifiedFactor(h, F, k)
+    if U is None:
+        Um = Vm = np.zeros((n, 0), dtype=F.dtype, order="F")
+    else:
+        U, V = np.asarray(U), np.asarray(V)
+        if U.ndim == 1:
+            U = U.reshape(-1, 1)
+        if V.ndim == 1:
+            V = V.reshape(-1, 1)
+        if U.ndim != 2 or V.ndim != 2 or U.shape != V.shape or U.shape[0] != n:
+            raise _lib.DimensionMismatch(f"DimensionMismatch: U is {U.shape}, V is {V.shape}, F is {n} x {n}")
+        if F.dtype.kind == "f" and (U.dtype.kind == "c" or V.dtype.kind == "c"):
+            raise TypeError("MethodError: a ComplexF64 modification of a FactorNode{Float64}")
+        Um = np.asfortranarray(U, dtype=F.dtype)
+        Vm = np.asfortranarray(V, dtype=F.dtype)
+    k = Um.shape[1]
+    _lib.check(getattr(_lib.lib(), "hs_mod_create" + sfx)(F._h, n, k, Um.ctypes.data_as(C.c_void_p), max(n, 1), Vm.ctypes.data_as(C.c_void_p), max(n, 1), C.byref(h)))
+    return ModifiedFactor(h, F, k)
+
+
+_MOD_TRANS = {None: 0, "N": 0, "T": 1, "C": 2, "H": 2}
+
+
+def ldiv_mod(*args, trans="N"):
+    """``ldiv_mod(M, B, trans="N")`` / ``ldiv_mod(C, M, B, trans=...)``: ``C = op(A1)^-1 B`` for a :class:`ModifiedFactor` ``M`` of ``A1``
+    (``hs_mod_ldiv_*``), with the shape and dtype rules of :func:`ldiv`; ``trans`` as :meth:`hss.HssMatrix.ldiv` (``"N"``, ``"T"``:
+    ``transpose(A1)``, ``"C"`` or ``"H"``: ``adjoint(A1)``).  Per chunk of ``HS_LDIV_BLOCK_COLS`` columns: one block solve with ``F``, one
+    tall-skinny inner product, one ``k x k`` solve, one rank-``k`` correction.  ``k = 0`` returns the bits of :func:`ldiv_block_t`."""
+    if len(args) == 2:
+        M, B = args
+        Cout = None
+    elif len(args) == 3:
+        Cout, M, B = args
+    else:
+        raise TypeError("ldiv_mod(M, B) or ldiv_mod(C, M, B)")
+    if not isinstance(M, ModifiedFactor):
+        raise TypeError(f"expected a ModifiedFactor, got {type(M).__name__}")
+    if trans not in _MOD_TRANS:
+        raise ValueError(f"trans must be None, 'N', 'T', 'C' or 'H', got {trans!r}")
+    B = np.asarray(B)
+    if B.shape[0] != M.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, A1 is {M.n} x {M.n}")
+    if B.dtype != M.dtype:
+        if M.dtype.kind == "f" and B.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::ModifiedFactor{Float64}, ::Array{ComplexF64})")
+        B = B.astype(M.dtype)
+    vec = B.ndim == 1
+    Bm = np.asfortranarray(B.reshape(M.n, -1))
+    Cm = np.empty_like(Bm, order="F")
+    fn = getattr(_lib.lib(), "hs_mod_ldiv" + ("_z" if M.dtype.kind == "c" else "_d"))
+    _lib.check(fn(M._h, _MOD_TRANS[trans], Cm.ctypes.data_as(_lib.p_f64), M.n, Bm.ctypes.data_as(_lib.p_f64), M.n, M.n, Bm.shape[1]))
+    res = Cm[:, 0] if vec else Cm
+    if Cout is not None:
+        Cout[...] = res
+        return Cout
+    return res
+
+
 def _sparse_rhs(F, B):
     """``(F, trans, raw handle, B as canonical CSC, 1-based colptr, 1-based rowval)`` for the ``hs_ldiv_sparse_*`` calls."""
     trans = 0

@@ -141,6 +141,22 @@ int hsk_envelope_enable(int on);
 int hsk_op_flops_mode(int on);
 int hsk_op_flops(double* out);
 
+/* The kernels of hs_mod_* (kernels_mod.hip) on host data; every block column-major.
+ *   hsk_mod_inner:   T (k x m, ldt) = op(P)^H Y, P n x k, Y n x m; conj != 0: op = conj, i.e. T = P^T Y (ComplexF64; ignored for Float64).
+ *                    k in 1..256, m in 1..64.  Row slabs of 2048, partial sums added in slab order (csrc/hs_mod.h states the order).
+ *   hsk_mod_apply:   Y (n x m) -= op(Z) T, Z n x k, T k x m; conj != 0: op = conj.
+ *   hsk_mod_gather:  T[j, c] = Y[J[j], c], J 0-based.
+ *   hsk_mod_cap:     T (k x m, any m >= 1) = op(C)^-1 T by a partial-pivoting LU of C (k x k, not overwritten); op 0: C, 1: C^T, 2: C^H.
+ *                    HS_ERR_SINGULAR on an exactly zero pivot, T untouched. */
+int hsk_mod_inner_d(int64_t n, int64_t k, int64_t m, const double* P, int64_t ldp, const double* Y, int64_t ldy, int conj, double* T, int64_t ldt);
+int hsk_mod_inner_z(int64_t n, int64_t k, int64_t m, const double* P, int64_t ldp, const double* Y, int64_t ldy, int conj, double* T, int64_t ldt);
+int hsk_mod_apply_d(int64_t n, int64_t k, int64_t m, double* Y, int64_t ldy, const double* Z, int64_t ldz, const double* T, int64_t ldt, int conj);
+int hsk_mod_apply_z(int64_t n, int64_t k, int64_t m, double* Y, int64_t ldy, const double* Z, int64_t ldz, const double* T, int64_t ldt, int conj);
+int hsk_mod_gather_d(int64_t n, int64_t k, int64_t m, const double* Y, int64_t ldy, const int64_t* J, double* T, int64_t ldt);
+int hsk_mod_gather_z(int64_t n, int64_t k, int64_t m, const double* Y, int64_t ldy, const int64_t* J, double* T, int64_t ldt);
+int hsk_mod_cap_d(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt);
+int hsk_mod_cap_z(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt);
+
 /* Microseconds per ROUND TRIP (two exchanges) between workgroup 0 and workgroup `peer` of one launch through agent-scope atomic stores and polled
  * loads -- the exchange primitive of the dataflow sweeps of ldiv! (kernels_solve_wide.hip).  peer = 1: another XCD, peer = 8: the same XCD. */
 double hsk_flow_pingpong_us(int peer, int iters);

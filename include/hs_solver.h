@@ -291,6 +291,49 @@ int hs_misfit_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_b
  * reduced, values moved between host and device (0 for the _dev_ forms), workspace bytes} */
 int hs_sens_info(const hs_handle* F, double* out8);
 
+/* ---- solves with a low-rank or entry modification of A, without refactoring (hs_mod.hip) ------------------------------------------------
+ * A1 = A + U V^H with U, V n x k (Float64: V^T), k <= HS_MOD_MAXRANK = 256.  With Z = F^-1 U, W = F^-H V and the capacitance matrix
+ * C = I_k + V^H Z (Sherman-Morrison-Woodbury):
+ *   trans 0:  A1^-1 B = Y - Z C^-1 (V^H Y),              Y = F^-1 B
+ *   trans 2:  A1^-H B = Y - W C^-H (U^H Y),              Y = F^-H B
+ *   trans 1:  A1^-T B = Y - conj(W) C^-T (U^T Y),        Y = F^-T B
+ * hs_mod_create_* builds Z with the library's own solves (dense U: hs_ldiv_block_dev_t_*; the sparse form: hs_ldiv_sparse_dev_* with all rows,
+ * i.e. the pruned forward sweep), C with the inner-product kernel (the sparse form: a gather of Z[J, :]), factors C with partial pivoting
+ * (an exactly zero pivot: HS_ERR_SINGULAR) and records rcond_1(C) from C^-1 applied to the identity.  It keeps copies of U, V (or J), Z and
+ * LU(C) on the device; W (and, in the sparse form, the dense expansion of U) is built by the first call with trans = 1 or 2 and serves both.
+ * The sparse form takes dA (n x n) as 1-based CSC with the rows strictly increasing within a column (SparseMatrixCSC): k = its nonempty
+ * columns J, U = dA[:, J], V = I[:, J], so A1 = A + dA.
+ * hs_mod_ldiv_* solves op(A1) X = B chunk by chunk of HS_LDIV_BLOCK_COLS columns: per chunk one block solve with F (hs_ldiv_block_dev_t_*),
+ * one inner product (or gather), one solve with LU(C) and one rank-k correction.
+ * The object holds a pointer to F and never changes its factors; F must outlive it (freeing F first is the caller's error).  Calls on one
+ * object must not overlap (it owns one set of work blocks); the solve figures of F (hs_ldiv_block_info, hs_ldiv_sparse_info) are those of
+ * the solves run here.
+ * Properties: k = 0 returns the bits of hs_ldiv_block_t_*; two calls return the same bits; X[:, c] depends neither on the other columns
+ * nor on their number (no atomics, one summation order per element); C may alias B; nrhs = 0 touches nothing.
+ * Refused before any device work, with C unwritten: what hs_ldiv_block_t_* refuses (HSS interior blocks, more than one rank), found by a
+ * zero-column solve and reported with its message: HS_ERR_UNSUPPORTED; k > HS_MOD_MAXRANK: HS_ERR_UNSUPPORTED (refactor instead); null
+ * pointers, trans outside 0..2, a mismatched element type, a plan-only or unfactored handle, a malformed CSC: HS_ERR_ARGUMENT; n != size(F),
+ * leading dimensions below n, negative sizes, indices outside 1..n: HS_ERR_DIMENSION.  A singular C: HS_ERR_SINGULAR (no object is made).
+ * The _dev_ forms take device blocks and a stream and return when the object is built (create) or with the solve queued on the stream
+ * (ldiv): hs_mod_ldiv_dev_* itself waits for nothing on the host (a call on another stream than the last one waits for it on the device);
+ * the block solve inside it waits, as every hs_ldiv_block_dev_* call does, until the handle's previous block solve has left its work blocks. */
+#define HS_MOD_MAXRANK 256
+typedef struct hs_mod hs_mod;
+int hs_mod_create_d(hs_handle* F, int64_t n, int64_t k, const double* U, int64_t ldu, const double* V, int64_t ldv, hs_mod** M);
+int hs_mod_create_z(hs_handle* F, int64_t n, int64_t k, const double* U, int64_t ldu, const double* V, int64_t ldv, hs_mod** M);
+int hs_mod_create_dev_d(hs_handle* F, int64_t n, int64_t k, const double* dU, int64_t ldu, const double* dV, int64_t ldv, void* stream, hs_mod** M);
+int hs_mod_create_dev_z(hs_handle* F, int64_t n, int64_t k, const double* dU, int64_t ldu, const double* dV, int64_t ldv, void* stream, hs_mod** M);
+int hs_mod_create_sparse_d(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, hs_mod** M);
+int hs_mod_create_sparse_z(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, hs_mod** M);
+int hs_mod_ldiv_d(hs_mod* M, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_mod_ldiv_z(hs_mod* M, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_mod_ldiv_dev_d(hs_mod* M, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+int hs_mod_ldiv_dev_z(hs_mod* M, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+/* out8 = {k, rcond_1(C) (1 for k = 0), seconds to build, device seconds of the last hs_mod_ldiv_* (the block solves included), device bytes
+ * held, 1 when W exists, block-solve calls issued so far (create included), 0} */
+int hs_mod_info(hs_mod* M, double* out8);
+void hs_mod_free(hs_mod* M);
+
 /* ---- accuracy tools: norm and condition estimates, refined solves with error bounds (hs_condest.hip) --------------------------
  * opnorm(A, 1), opnorm(A, Inf) of the handle's A (the values of the last hs_numeric_begin); p = 1 or 0 (= Inf).  The first call that needs
  * rows of A (p = 0, hs_condest p = 0, hs_ldiv_refine_* with trans = 0) builds a CSR map of A's pattern on the device and keeps it in the handle. */
@@ -516,6 +559,16 @@ int hs_gmres_block_t_d(hs_handle* Pr, int trans, int64_t n, const int64_t* colpt
 int hs_gmres_block_t_z(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
                        int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
                        int* converged, void* stream);
+/* hs_gmres_block_t_* on the MODIFIED system: op(A1) X = B with A1 = A + U V^H given as CSC (1-based, as above), right-preconditioned by
+ * op(A1)^-1 as hs_mod_ldiv_dev_* applies it from the factors of A (hs_mod_*).  With a compressed (approximate) factorization this is how
+ * solutions of the modified system reach a residual tolerance.  colptr / rowval / nzval == NULL is refused (HS_ERR_ARGUMENT): the handle
+ * behind Pr holds the unmodified A.  Everything else as hs_gmres_block_t_*; hs_gmres_block_info reports the call. */
+int hs_gmres_block_mod_d(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
+                         int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
+                         int* converged, void* stream);
+int hs_gmres_block_mod_z(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
+                         int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
+                         int* converged, void* stream);
 /* the calling thread's last hs_gmres_block_* / hs_gmres_block_t_* call: out8 = {seconds on the device, block preconditioner calls, column-applications summed over
  * those calls, SpMM launches, restart cycles (summed over the groups), column groups, workspace bytes, the largest active-column count} */
 int hs_gmres_block_info(double* out8);
