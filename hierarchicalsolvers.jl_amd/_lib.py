@@ -103,6 +103,7 @@ EXPORTS = [
     "hsk_gemm_d", "hsk_gemm_z", "hsk_lowrank_d", "hsk_lowrank_z", "hsk_front_factor_d", "hsk_front_factor_z", "hsk_front_batch_d", "hsk_front_batch_z", "hsk_mfma_f64_peak", "hsk_mfma_f64_peak_random", "hsk_flow_pingpong_us", "hsk_bisect_perm",
     "hs_probs_stats_mode", "hs_probs_stats", "hs_trim", "hs_stream_order",
     "hsk_leaf_envelope", "hsk_envelope_enable", "hsk_op_flops_mode", "hsk_op_flops",
+    "hsk_gemm_op_d", "hsk_gemm_lds_enable", "hsk_gemm_lds_launches",
 ]
 
 _lib = None
@@ -374,6 +375,12 @@ def lib():
     for f in (L.hsk_gemm_d, L.hsk_gemm_z):
         f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, p_f64]
         f.restype = C.c_int
+    L.hsk_gemm_op_d.argtypes = [i64, p_i64, p_i64, i64, i64, i64, p_f64, p_f64, p_f64, p_i64, C.c_int, p_f64]
+    L.hsk_gemm_op_d.restype = C.c_int
+    L.hsk_gemm_lds_enable.argtypes = [C.c_int]
+    L.hsk_gemm_lds_enable.restype = C.c_int
+    L.hsk_gemm_lds_launches.argtypes = [C.c_int]
+    L.hsk_gemm_lds_launches.restype = C.c_longlong
     for f in (L.hsk_front_factor_d, L.hsk_front_factor_z):
         f.argtypes = [i64, i64, i64, p_f64, p_f64, p_f64, p_f64, p_i64, p_i64, p_f64]
         f.restype = C.c_int

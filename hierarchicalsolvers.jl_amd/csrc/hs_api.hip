@@ -191,6 +191,7 @@ struct LevelH {
   int nplain = 0;                          // of those, the first nplain keep a dense LU of D, the others an HSS form (hs_hssfront.h)
   int nmf = 0;                             // the last nmf entries of `mine` are matrix-free fronts (hs_mffront.h): never assembled
   int dmaxni = 0, dmaxnb = 0, dmaxm = 0;   // extents of the dense batch
+  bool aligned16 = true;                   // every front of the dense batch has LF / UR / SB 16-byte aligned and even ldl / ldu / lds (Sched::aligned16)
 };
 
 struct Exchange {
@@ -1142,6 +1143,8 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
           d.env = x.off_env >= 0 ? h->d_env + x.off_env : nullptr;
           d.finalize();
           hn.push_back(d);
+          if (x.batch_pos < L.ndense && ((((uintptr_t)d.LF | (uintptr_t)d.UR | (uintptr_t)d.SB) & 15) || ((d.ldl | d.ldu | d.lds) & 1)))
+            L.aligned16 = false;  // (the dense batch only: the compressed, HSS and matrix-free fronts of the level never reach Sched::gemm through it)
           SolveNode<T> q;
           memset(&q, 0, sizeof q);
           q.LF = d.LF; q.UR = d.UR; q.invL = d.invL; q.invU = d.invU;
@@ -1331,6 +1334,7 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
       Sched<T> sch{dn, L.ndense, L.dmaxni, L.dmaxnb, L.dmaxm, s, &h->prof, L.h_ni.data(), L.h_nb.data(), h->stream2, 0, h->stream_la, h->stream2m};
       sch.sn = (const SolveNode<T>*)h->d_solve + L.desc_off;  // lu_rec leaves the 256x256 inverse diagonal blocks behind
       sch.optimistic = try_opt && attempt == 0;
+      sch.aligned16 = L.aligned16 && h->nranks == 1;  // (a Schur complement handed in by another rank lives in the caller's buffer)
       // the block envelope of the leaves holds while rows are swapped inside 32-row diagonal blocks only: the redo of a level and
       // HS_OPTIMISTIC=0 (tournament pivoting) eliminate every front as a dense matrix
       if (sch.optimistic && !dx && !L.h_env.empty() && hs_envelope_enabled()) {

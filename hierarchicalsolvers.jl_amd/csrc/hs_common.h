@@ -204,8 +204,17 @@ __device__ inline void mat_of(const NodeDesc<T>* pn, int which, T*& p, int& ld, 
 }
 
 // ---- launch API (implemented in the kernels_*.hip files) -------------------------------------
+// lds_ok: every front of the batch passed hs_gemm_lds_front_ok for this op (Float64 plain updates only; decided on the host, Sched::gemm)
 template <class T>
-void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s);
+void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s, bool lds_ok = false);
+// May the plain update (cmat, r0, k0, k1) of a front with ni interior DOFs load its operands straight into LDS (gemm_op_lds_kernel)?  The
+// direct load moves 16 bytes per lane and is given 16-byte aligned sources only: with LF / UR / SB 16-byte aligned and even leading
+// dimensions (the caller's premise: Sched::aligned16) A = LF + r0 (+ ni when C is SB) + k0 ldl and B = B0 + k0 + c0 ldb are aligned when
+// the row offset and k0 are even.  K must be whole 16-column steps (the kernel has no zero-filling path).
+inline bool hs_gemm_lds_front_ok(int cmat, int r0, int k0, int k1, int ni) {
+  const int K = (k1 < ni ? k1 : ni) - k0, arow = r0 + (cmat == HS_MAT_SB ? ni : 0);
+  return K > 0 && (K & 15) == 0 && !(k0 & 1) && !(arow & 1);
+}
 bool hs_envelope_enabled();  // HS_LEAF_ENVELOPE (default on) / hsk_envelope_enable: leaf fronts are eliminated inside their block envelope
 template <class T>
 void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN, int accumulate_minus, hipStream_t s);

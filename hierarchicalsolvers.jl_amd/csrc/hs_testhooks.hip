@@ -72,6 +72,107 @@ extern "C" int hsk_gemm_z(int64_t M, int64_t N, int64_t K, const double* A, int6
   return gemm_hook<cplx>(M, N, K, (const cplx*)A, lda, (const cplx*)B, ldb, (cplx*)C, ldc, minus, repeat, ms_out);
 }
 
+// The plain update of a level, C -= A * B for a batch of `count` fronts, the way Sched::gemm issues the U12 update UR[r0.., :] -= LF[r0.., k0:k1) *
+// UR[k0:k1, :]: front f has K + M[f] (+ koff + roff) interior and N[f] boundary DOFs, A sits in LF at row r0 = koff + K + roff and column
+// k0 = koff, B in the rows k0.. of UR and C in its rows r0...  The schedule decides per launch between gemm_op_kernel and gemm_op_lds_kernel
+// exactly as in a factorization (hs_gemm_lds_front_ok, HS_GEMM_LDS / hsk_gemm_lds_enable); *routed says how many launches took the latter.
+// koff / roff = 1 shift B / A by one double (an operand the direct load may not take).
+static int gemm_op_hook(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A, const double* B,
+                        double* C, int64_t* routed, int repeat, double* ms_out) {
+  typedef double T;
+  if (count <= 0 || count > 65535 || !M || !N || !A || !B || !C || K <= 0 || koff < 0 || roff < 0) {
+    hs_set_error(HS_ERR_ARGUMENT, count, "hsk_gemm_op_d: count in [1, 65535], positive K, non-negative offsets and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  for (int64_t f = 0; f < count; ++f)
+    if (M[f] <= 0 || N[f] <= 0 || koff + K + roff + M[f] > (1 << 20) || N[f] > (1 << 20)) {
+      hs_set_error(HS_ERR_ARGUMENT, f, "hsk_gemm_op_d: front %lld has M = %lld, N = %lld", (long long)f, (long long)M[f], (long long)N[f]);
+      return HS_ERR_ARGUMENT;
+    }
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
+    return HS_ERR_DEVICE;
+  }
+  const int k0 = (int)koff, k1 = (int)(koff + K), r0 = (int)(koff + K + roff);
+  auto rup32 = [](size_t e) { return (e + 31) / 32 * 32; };
+  std::vector<NodeDesc<T>> hn(count);
+  std::vector<int> h_ni(count), h_nb(count);
+  std::vector<size_t> olf(count), our(count);
+  size_t nT = 0;
+  int maxni = 0, maxnb = 0;
+  for (int64_t f = 0; f < count; ++f) {
+    const int ni = r0 + (int)M[f], nb = (int)N[f], ld = (ni + 1) / 2 * 2;
+    h_ni[f] = ni; h_nb[f] = nb;
+    maxni = std::max(maxni, ni); maxnb = std::max(maxnb, nb);
+    olf[f] = nT; nT += rup32((size_t)ld * k1);  // only the columns [0, k1) of LF are read
+    our[f] = nT; nT += rup32((size_t)ld * nb);
+  }
+  T* dbuf = nullptr;
+  NodeDesc<T>* dn = nullptr;
+  CK(hipMalloc((void**)&dbuf, sizeof(T) * nT));
+  CK(hipMalloc((void**)&dn, sizeof(NodeDesc<T>) * count));
+  CK(hipMemset(dbuf, 0, sizeof(T) * nT));
+  bool aligned = true;
+  const T *Af = A, *Bf = B;
+  T* Cf = C;
+  for (int64_t f = 0; f < count; ++f) {
+    NodeDesc<T>& d = hn[f];
+    memset(&d, 0, sizeof d);
+    d.ni = h_ni[f]; d.nb = h_nb[f]; d.m = d.ni + d.nb;
+    d.ldl = d.ldu = (d.ni + 1) / 2 * 2;
+    d.lds = (d.nb + 1) / 2 * 2;
+    d.LF = dbuf + olf[f]; d.UR = dbuf + our[f];
+    d.SB = nullptr;  // (never addressed: C and B are UR)
+    d.ni1 = d.ni; d.nb1 = d.nb; d.node = (int)f;
+    d.finalize();
+    d.mrows[HS_MAT_SB] = d.mcols[HS_MAT_SB] = 0;
+    aligned = aligned && !((((uintptr_t)d.LF | (uintptr_t)d.UR) & 15) || ((d.ldl | d.ldu) & 1));
+    const int Mf = (int)M[f];
+    CK(hipMemcpy2D(d.LF + r0 + (size_t)k0 * d.ldl, sizeof(T) * d.ldl, Af, sizeof(T) * Mf, sizeof(T) * Mf, K, hipMemcpyHostToDevice));
+    CK(hipMemcpy2D(d.UR + k0, sizeof(T) * d.ldu, Bf, sizeof(T) * K, sizeof(T) * K, d.nb, hipMemcpyHostToDevice));
+    CK(hipMemcpy2D(d.UR + r0, sizeof(T) * d.ldu, Cf, sizeof(T) * Mf, sizeof(T) * Mf, d.nb, hipMemcpyHostToDevice));
+    Af += (size_t)Mf * K; Bf += (size_t)K * d.nb; Cf += (size_t)Mf * d.nb;
+  }
+  CK(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
+  Profiler prof;
+  Sched<T> sch{dn, (int)count, maxni, maxnb, maxni + maxnb, (hipStream_t) nullptr, &prof, h_ni.data(), h_nb.data()};
+  sch.aligned16 = aligned;
+  const long long before = hsk_gemm_lds_launches(0);
+  sch.gemm(HS_MAT_UR, HS_MAT_UR, r0, HS_BIG, 0, HS_BIG, k0, k1);
+  CK(hipDeviceSynchronize());
+  if (routed) *routed = (int64_t)(hsk_gemm_lds_launches(0) - before);
+  Cf = C;
+  for (int64_t f = 0; f < count; ++f) {
+    const NodeDesc<T>& d = hn[f];
+    const int Mf = (int)M[f];
+    CK(hipMemcpy2D(Cf, sizeof(T) * Mf, d.UR + r0, sizeof(T) * d.ldu, sizeof(T) * Mf, d.nb, hipMemcpyDeviceToHost));
+    Cf += (size_t)Mf * d.nb;
+  }
+  if (repeat > 0) {
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    CK(hipEventRecord(e0, 0));
+    for (int r = 0; r < repeat; ++r) sch.gemm(HS_MAT_UR, HS_MAT_UR, r0, HS_BIG, 0, HS_BIG, k0, k1);
+    CK(hipEventRecord(e1, 0));
+    CK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    if (ms_out) *ms_out = ms / repeat;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  prof.collect();
+  (void)hipFree(dbuf);
+  (void)hipFree(dn);
+  return HS_OK;
+}
+extern "C" int hsk_gemm_op_d(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A,
+                             const double* B, double* C, int64_t* routed, int repeat, double* ms_out) {
+  return gemm_op_hook(count, M, N, K, koff, roff, A, B, C, routed, repeat, ms_out);
+}
+
 // Factor a batch of `count` dense fronts F[k] ((ni[k]+nb[k])^2, column-major, front order [int;bnd], packed one after another) the way
 // hs_numeric factors a level: one Sched over the batch (batch maxima, per-front sizes on the host, the look-ahead streams).
 //   mode 0: tournament pivoting, no solve descriptors   1: optimistic, no descriptors (32-row TRSM base case, full-height panels)

@@ -381,6 +381,140 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
 }
 
 // ------------------------------------------------------------------------------------------------
+// real double, operands loaded STRAIGHT INTO LDS (global_load_lds, 16 bytes per lane): gemm_op_lds_kernel.  Tile, wave layout, BK, the two
+// stages, the transposed MFMA issue, the order in which every accumulator takes its k-steps and the epilogue are those of gemm_tile_d, so
+// every stored value keeps its bits; what is gone are the staging registers ra / rb and the LDS store pass behind the MFMAs.
+// A wave-instruction writes 64 lanes x 16 B = 1 KiB at a wave-uniform LDS base, lane-linear; only the SOURCE address is per lane:
+//   A image [k][LDS_LD], as before: one instruction fills one k-row of 128 doubles (the 16 padding doubles of a row are never written or
+//     read).  Wave w issues the k-rows w, w + 4, w + 8, w + 12; lane l brings the row pair 2l, 2l + 1, clamped to the last pair of A.
+//   B image [n][BK], 128 B per column, no padding (a lane-linear write cannot skip any): the eight 16-byte k-pair chunks of column n sit at
+//     chunk index c ^ ((n >> 1) & 7).  One instruction fills eight columns; the lane whose slot is (n, c') fetches chunk c' ^ ((n >> 1) & 7)
+//     of column min(n0 + n, N - 1).  The operand ds_read_b64 of a half-wave (16 columns n, two k of one pair) then meets every chunk index
+//     twice, at an even and an odd n (32 banks apart), with the two k in the two halves of the chunk: all 64 banks once.
+// The launch must qualify (launch_gemm_op): K a multiple of BK, A and B 16-byte aligned with even leading dimensions -- the row pair
+// (M - 1, M) of an odd M then lies inside A's column, and what it brings for row M feeds accumulators that are never stored.
+// ------------------------------------------------------------------------------------------------
+#define LDS_B_STAGE (BK * LDS_LD)             // doubles: the B image follows the A image of its stage
+#define LDS_STAGE_G (BK * LDS_LD + 128 * BK)  // doubles per stage: 18,432 + 16,384 bytes
+typedef __attribute__((address_space(3))) void* hs_lds_ptr;
+template <int BN_>
+__device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, int tile_n, bool minus, double* smem) {
+  constexpr int BN = BN_;  // 128
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave & 1, wn = wave >> 1;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const int M = p.M, N = p.N, K = p.K;
+
+  // per-lane sources of the first K-step; a K-step further is BK columns of A / BK doubles down B
+  const double* a_src = p.A + (size_t)min(m0 + 2 * lane, (M - 1) & ~1) + (size_t)wave * p.lda;  // + 4 i lda
+  const double* b_src[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int n = 8 * (wave + 4 * i) + (lane >> 3);
+    b_src[i] = p.B + (size_t)(2 * ((lane & 7) ^ ((n >> 1) & 7))) + (size_t)min(n0 + n, N - 1) * p.ldb;
+  }
+  const size_t a_row4 = (size_t)4 * p.lda;
+  auto issue_tile = [&](int k0, int stage) {
+    double* As = smem + stage * LDS_STAGE_G;
+    double* Bs = As + LDS_B_STAGE;
+    const double* a = a_src + (size_t)k0 * p.lda;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(a + i * a_row4), (hs_lds_ptr)(As + (wave + 4 * i) * LDS_LD), 16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(b_src[i] + k0), (hs_lds_ptr)(Bs + (wave + 4 * i) * (8 * BK)), 16, 0, 0);
+  };
+
+  double4_t acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int a_off = l4 * LDS_LD + wm * 64 + l15;
+  // B operand of k-step ks: k = l4 + 4 ks, chunk (k >> 1) ^ ((n >> 1) & 7) with (n >> 1) & 7 == l15 >> 1 for every j (n = wn 64 + j 16 + l15)
+  int b_off[BK / 4];
+#pragma unroll
+  for (int ks = 0; ks < BK / 4; ++ks)
+    b_off[ks] = LDS_B_STAGE + (wn * 64 + l15) * BK + 2 * ((2 * ks + (l4 >> 1)) ^ (l15 >> 1)) + (l4 & 1);
+
+  // Two LDS stages, ONE barrier per K-step: the loads of the next tile go into the other stage before the MFMAs of this one (every wave
+  // finished reading that stage before the previous barrier) and are waited for by the barrier that ends the step.
+  issue_tile(0, 0);
+  __syncthreads();
+  int cur = 0;
+  for (int k0 = 0; k0 < K; k0 += BK) {
+    if (k0 + BK < K) issue_tile(k0 + BK, cur ^ 1);
+    const double* s_rd = smem + cur * LDS_STAGE_G;
+    const double* a_rd = s_rd + a_off;
+    {
+      double bf[4][BK / 4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int ks = 0; ks < BK / 4; ++ks) bf[j][ks] = s_rd[b_off[ks] + (j * 16) * BK];
+      double af[BK / 4];
+#pragma unroll
+      for (int ks = 0; ks < BK / 4; ++ks) af[ks] = a_rd[(ks * 4) * LDS_LD];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        double afn[BK / 4];
+        if (i < 3) {
+#pragma unroll
+          for (int ks = 0; ks < BK / 4; ++ks) afn[ks] = a_rd[(ks * 4) * LDS_LD + (i + 1) * 16];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+          for (int ks = 0; ks < BK / 4; ++ks)
+            // transposed issue, as in gemm_tile_d.  No sched_barrier behind the chain here: the source order already gives every accumulator
+            // its k-steps in a row (and whatever the scheduler does, each accumulator still takes them in the same order: same bits), and
+            // unpinned the compiler spreads the operand reads of the next row block under the MFMAs -- 195 instead of 214 VGPRs and
+            // 3-6 % more TFLOP/s at every K
+            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[j][ks], af[ks], acc[i][j], 0, 0, 0);
+        }
+        if (i < 3) {
+#pragma unroll
+          for (int ks = 0; ks < BK / 4; ++ks) af[ks] = afn[ks];
+        }
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // epilogue: as in gemm_tile_d
+  double* __restrict__ C = p.C;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int mm = m0 + wm * 64 + i * 16 + l15;
+    const bool rok = mm < M;
+    double cv[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int nn = n0 + wn * 64 + j * 16 + l4 + 4 * r;
+        cv[j][r] = (minus && rok && nn < N) ? gld(C + (size_t)mm + (size_t)nn * p.ldc) : 0.0;
+      }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int nn = n0 + wn * 64 + j * 16 + l4 + 4 * r;
+        if (rok && nn < N) {
+          const double v = minus ? (cv[j][r] - acc[i][j][r]) : acc[i][j][r];
+          gst(C + (size_t)mm + (size_t)nn * p.ldc, v);
+          if (p.flag && mm < p.flag_rows && !(fabs(v) <= HS_GROWTH_MAX)) *p.flag = 1;
+        }
+      }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // real double, SKINNY problems (the grouped products of the HSS module: a 64-row window against 2,048 sample columns, 64 x 64 Gram
 // matrices over a long inner dimension, ...).  The same pipeline with a 64 x 128 or 64 x 64 tile: a lone workgroup pays 64 MFMAs per wave and
 // K-step of the 128 x 128 tile (1.7 us) whether its rows exist or not -- half or three quarters of them multiply padding when M, N <= 64 --
@@ -677,7 +811,7 @@ struct TileCfg<cplx> {
 // GemmOp::count is set -- launch_gemm_op then sends EVERY plain update there, dense ones included; gemm_op_kernel itself never counts
 __device__ double g_op_flops;
 
-template <class T>
+template <class T, bool GLDS = false>  // GLDS: the real tile with direct-to-LDS operand loads (gemm_op_lds_kernel)
 __device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* smem) {
   int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + TileCfg<T>::bn - 1) / TileCfg<T>::bn;
   int ntiles = tiles_m * tiles_n;
@@ -688,7 +822,9 @@ __device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* s
     int t = xcd_remap_shift(bid, ntiles, (gridDim.x & 7u) ? shift : 0);  // (a walking workgroup keeps its XCD only when gridDim.x is a multiple of 8: then shift == 0)
     int tm, tn;
     tile_coords(t, tiles_m, tiles_n, tm, tn);
-    if constexpr (sizeof(T) == 8)
+    if constexpr (GLDS)
+      gemm_tile_d_lds<128>(p, tm, tn, minus, smem);
+    else if constexpr (sizeof(T) == 8)
       gemm_tile_d<128>(p, tm, tn, minus, smem);
     else
       gemm_tile_z(p, tm, tn, minus, smem);
@@ -746,6 +882,18 @@ __global__ __launch_bounds__(256, 2) void gemm_op_kernel(const NodeDesc<T>* __re
   if (op.prio) __builtin_amdgcn_s_setprio(2);  // look-ahead panel work sharing CUs with the big trailing update
   if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
   gemm_dispatch<T>(p, true, smem);
+}
+// The plain dense update again with its operands loaded straight into LDS (gemm_tile_d_lds): launch_gemm_op sends a launch here when
+// every front of the batch qualifies (K a multiple of 16, 16-byte aligned A and B) and HS_GEMM_LDS is on.  A kernel of its own: the
+// register-staged kernels keep their code and with it their register allocation.
+template <class T>
+__global__ __launch_bounds__(256, 2) void gemm_op_lds_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
+  static_assert(sizeof(T) == 8, "real double only");
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  GemmProb<T> p;
+  if (op.prio) __builtin_amdgcn_s_setprio(2);
+  if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
+  gemm_dispatch<T, true>(p, true, smem);
 }
 // The TRSM base case (X <- inv(diagonal block) * X, in place) runs the same tile code under its own name, so that
 // profiles separate the trailing updates (gemm_op_kernel: the flops) from the 32-row solves (latency).
@@ -829,7 +977,27 @@ __global__ void resolve_dump_kernel(const NodeDesc<T>* __restrict__ nodes, GemmO
 namespace {
 std::atomic<int> g_env_on{-1};      // -1: not read yet (HS_LEAF_ENVELOPE, default on)
 std::atomic<int> g_op_count_on{0};
+std::atomic<int> g_lds_on{-1};      // -1: not read yet (HS_GEMM_LDS, default on)
+std::atomic<long long> g_lds_launches{0};
 }  // namespace
+// HS_GEMM_LDS=0 / hsk_gemm_lds_enable(0): every plain update runs the register-staged gemm_op_kernel
+static bool gemm_lds_enabled() {
+  int v = g_lds_on.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("HS_GEMM_LDS");
+    v = (e && e[0] == '0') ? 0 : 1;
+    g_lds_on.store(v);
+  }
+  return v != 0;
+}
+extern "C" int hsk_gemm_lds_enable(int on) {  // returns the previous setting
+  const int prev = gemm_lds_enabled() ? 1 : 0;
+  g_lds_on.store(on ? 1 : 0);
+  return prev;
+}
+extern "C" long long hsk_gemm_lds_launches(int reset) {  // launches sent to gemm_op_lds_kernel since the last reset
+  return reset ? g_lds_launches.exchange(0) : g_lds_launches.load();
+}
 bool hs_envelope_enabled() {
   int v = g_env_on.load();
   if (v < 0) {
@@ -857,7 +1025,7 @@ extern "C" int hsk_op_flops(double* out) {
 }
 
 template <class T>
-void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s) {
+void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s, bool lds_ok) {
   if (nbatch <= 0 || maxM <= 0 || maxN <= 0) return;
   GemmOp op = op_in;
   op.count = (!op.ainv && g_op_count_on.load(std::memory_order_relaxed)) ? 1 : 0;
@@ -914,8 +1082,19 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
       hipLaunchKernelGGL(gemm_op_env_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
   } else if (op.ainv)
     hipLaunchKernelGGL(trsm_inv_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
-  else
+  else {
+    if constexpr (sizeof(T) == 8) {
+      if (lds_ok && gemm_lds_enabled()) {  // (the caller vouches for K and the alignment of every front: hs_gemm_lds_front_ok)
+        constexpr int lds_bytes_g = 2 * LDS_STAGE_G * 8;
+        static std::once_flag attr_once_g;
+        std::call_once(attr_once_g, [] { (void)hipFuncSetAttribute((const void*)gemm_op_lds_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_g); });
+        g_lds_launches.fetch_add(1, std::memory_order_relaxed);
+        hipLaunchKernelGGL(gemm_op_lds_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes_g, s, dnodes, op);
+        return;
+      }
+    }
     hipLaunchKernelGGL(gemm_op_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
+  }
 }
 
 // hs_probs_stats: flops (counted by the kernels), launches and -- with timing on -- the summed launch durations of the grouped products,
@@ -1005,8 +1184,8 @@ void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN,
   hipLaunchKernelGGL(gemm_probs_kernel<T>, dim3(tiles, nprob), dim3(256), lds_bytes, s, dprobs, minus);
 }
 
-template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, const GemmOp&, hipStream_t);
-template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t);
+template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, const GemmOp&, hipStream_t, bool);
+template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t, bool);
 template void launch_gemm_probs<double>(const GemmProb<double>*, int, int, int, int, hipStream_t);
 template void launch_gemm_probs<cplx>(const GemmProb<cplx>*, int, int, int, int, hipStream_t);
 

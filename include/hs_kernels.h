@@ -141,6 +141,19 @@ int hsk_envelope_enable(int on);
 int hsk_op_flops_mode(int on);
 int hsk_op_flops(double* out);
 
+/* The plain update C -= A * B of a level through the launch path of a factorization (Sched::gemm -> launch_gemm_op; Float64), for a batch of
+ * `count` fronts with M[f] x N[f] results and a common K: the U12 update UR[r0.., :] -= LF[r0.., k0:k1) * UR[k0:k1, :] with k0 = koff,
+ * k1 = koff + K, r0 = k1 + roff.  A (M[f] x K), B (K x N[f]) and C (M[f] x N[f], overwritten) are packed column-major, front after front.
+ * A launch runs `gemm_op_lds_kernel` (operands loaded straight into LDS) when every front qualifies -- K a multiple of 16, A and B 16-byte
+ * aligned: koff / roff = 1 shift B / A by one double -- and `gemm_op_kernel` otherwise; *routed (may be null) receives the number of
+ * launches that took the former.  repeat / ms_out as in hsk_gemm_d.
+ *   hsk_gemm_lds_enable   : 0 sends every launch to gemm_op_kernel (default: on unless HS_GEMM_LDS=0); returns the previous setting.
+ *   hsk_gemm_lds_launches : launches sent to gemm_op_lds_kernel since the last call with reset != 0. */
+int hsk_gemm_op_d(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A, const double* B,
+                  double* C, int64_t* routed, int repeat, double* ms_out);
+int hsk_gemm_lds_enable(int on);
+long long hsk_gemm_lds_launches(int reset);
+
 /* The kernels of hs_mod_* (kernels_mod.hip) on host data; every block column-major.
  *   hsk_mod_inner:   T (k x m, ldt) = op(P)^H Y, P n x k, Y n x m; conj != 0: op = conj, i.e. T = P^T Y (ComplexF64; ignored for Float64).
  *                    k in 1..256, m in 1..64.  Row slabs of 2048, partial sums added in slab order (csrc/hs_mod.h states the order).
