@@ -874,3 +874,77 @@ extern "C" int hsk_mod_cap_d(int64_t k, int64_t m, const double* C, int64_t ldc,
 extern "C" int hsk_mod_cap_z(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt) {
   return mod_cap_hook<cplx>(k, m, (const cplx*)C, ldc, op, (cplx*)T, ldt);
 }
+
+// ---- the pieces of hs_eigs_* (kernels_eigs.hip, hs_small_eig.h) on host data (tests/test_eigs_gpu.py, tests/test_eigs_host.py) ---------------
+#include "hs_eigs.h"
+#include "hs_small_eig.h"
+
+template <class T>
+static int eigs_rotate_hook(int64_t n, int64_t K, int64_t N, const T* V, int64_t ldv, const T* Q, int64_t ldq, int inplace, T* Out, int64_t ldo) {
+  if (n < 1 || K < 1 || K > HS_EIGS_MAXBASIS || N < 1 || N > K || ldv < n || ldq < K || ldo < n || !V || !Q || !Out) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_eigs_rotate: n >= 1, K in 1..256, N in 1..K, leading dimensions and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  if (int st = mod_hook_device()) return st;
+  ModBufs b;
+  T* dV = b.up<T>(V, ldv, n, K);
+  T* dQ = b.up<T>(Q, ldq, K, N);
+  T* dO = inplace ? dV : b.up<T>(nullptr, n, n, N);
+  MOD_NULL(dV && dQ && dO);
+  launch_eigs_rotate<T>(dO, n, dV, n, dQ, K, n, (int)K, (int)N, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy2D(Out, ldo * sizeof(T), dO, n * sizeof(T), n * sizeof(T), N, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+extern "C" int hsk_eigs_rotate_d(int64_t n, int64_t K, int64_t N, const double* V, int64_t ldv, const double* Q, int64_t ldq, int inplace, double* Out, int64_t ldo) {
+  return eigs_rotate_hook<double>(n, K, N, V, ldv, Q, ldq, inplace, Out, ldo);
+}
+extern "C" int hsk_eigs_rotate_z(int64_t n, int64_t K, int64_t N, const double* V, int64_t ldv, const double* Q, int64_t ldq, int inplace, double* Out, int64_t ldo) {
+  return eigs_rotate_hook<cplx>(n, K, N, (const cplx*)V, ldv, (const cplx*)Q, ldq, inplace, (cplx*)Out, ldo);
+}
+
+template <class T>
+static int eigs_chol_inv_hook(int64_t p, const T* G, int64_t ldg, T* R, T* Rinv, int* info) {
+  if (p < 1 || p > HS_EIGS_MAXBLOCK || ldg < p || !G || !R || !Rinv || !info) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_eigs_chol_inv: p in 1..64, ldg >= p and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  if (int st = mod_hook_device()) return st;
+  ModBufs b;
+  T* dG = b.up<T>(G, ldg, p, p);
+  T* dR = b.up<T>(nullptr, p, p, p);
+  T* dRi = b.up<T>(nullptr, p, p, p);
+  int* dInfo = b.up<int>(nullptr, 1, 1, 1);
+  MOD_NULL(dG && dR && dRi && dInfo);
+  launch_eigs_chol_inv<T>(dG, (int)p, (int)p, dR, dRi, dInfo, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy(info, dInfo, sizeof(int), hipMemcpyDeviceToHost));
+  CK(hipMemcpy(R, dR, sizeof(T) * (size_t)(p * p), hipMemcpyDeviceToHost));
+  CK(hipMemcpy(Rinv, dRi, sizeof(T) * (size_t)(p * p), hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+extern "C" int hsk_eigs_chol_inv_d(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info) { return eigs_chol_inv_hook<double>(p, G, ldg, R, Rinv, info); }
+extern "C" int hsk_eigs_chol_inv_z(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info) {
+  return eigs_chol_inv_hook<cplx>(p, (const cplx*)G, ldg, (cplx*)R, (cplx*)Rinv, info);
+}
+
+extern "C" int hsk_small_eig_z(int64_t m, const double* H, int64_t ldh, double* w, double* Y, int64_t ldy) {
+  if (m < 1 || m > HS_EIGS_MAXBASIS || ldh < m || ldy < m || !H || !w || !Y) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_small_eig_z: m in 1..256, leading dimensions >= m and non-null arrays required");
+    return HS_ERR_ARGUMENT;
+  }
+  try {
+    std::vector<hs_se::zc> Hc((size_t)(m * m));
+    for (int64_t j = 0; j < m; ++j)
+      for (int64_t i = 0; i < m; ++i) Hc[(size_t)(j * m + i)] = hs_se::zc(H[2 * (j * ldh + i)], H[2 * (j * ldh + i) + 1]);
+    const int bad = hs_se::small_eig((int)m, Hc.data(), (int)m, (hs_se::zc*)w, (hs_se::zc*)Y, (int)ldy);
+    if (bad) {
+      hs_set_error(HS_ERR_SINGULAR, bad - 1, "hsk_small_eig_z: the QR iteration did not isolate eigenvalue %d", bad - 1);
+      return HS_ERR_SINGULAR;
+    }
+  } catch (const std::bad_alloc&) {
+    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
+    return HS_ERR_NOMEM;
+  }
+  return HS_OK;
+}

@@ -14,6 +14,7 @@ reference (Julia)                      here
 ``xGERFS`` (refine, berr, ferr)        :func:`ldiv_refine`, :func:`ldiv_refine_block`
 ``logabsdet(F)``, ``logdet``, ``det``  :func:`logabsdet`, :func:`logdet`, :func:`det` (``hs_selinv.hip``)
 selected inverse (no Julia name)       :func:`selinv`, :func:`selinv_diag`: ``diag(A^-1)`` and ``A^-1`` on the pattern of ``A``
+``eigs(A; nev, sigma)`` (Arpack)       :func:`eigs`: the eigenpairs of ``A`` nearest ``sigma`` from the factors of ``A - sigma*I`` (``hs_eigs.hip``)
 ``F \\ b``                              ``F.solve(b)``
 =====================================  ====================================================
 
@@ -32,7 +33,7 @@ from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
            "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info",
-           "sensitivity", "sensitivity_matrix", "misfit", "sens_info"]
+           "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "eigs", "eigs_info"]
 
 
 class SolverOptions:
@@ -565,6 +566,93 @@ def ldiv_mod(*args, trans="N"):
     if Cout is not None:
         Cout[...] = res
         return Cout
+    return res
+
+
+def eigs_info():
+    """Figures of this thread's last :func:`eigs` call (``hs_eigs_info``)."""
+    out = np.zeros(8)
+    _lib.check(_lib.lib().hs_eigs_info(_pf64(out)))
+    return {"seconds": float(out[0]), "block_solves": int(out[1]), "column_applications": int(out[2]), "restarts": int(out[3]), "orth_passes": int(out[4]),
+            "replaced": int(out[5]), "workspace_bytes": int(out[6]), "ncv": int(out[7])}
+
+
+def eigs(F, nev=6, sigma=0.0, ncv=None, block=None, tol=1e-10, maxrestart=100, v0=None, seed=0, vectors=True, log=False):
+    """The ``nev`` eigenvalues of ``A`` nearest ``sigma`` and their unit eigenvectors, from the factorization ``F`` of ``A - sigma*I``
+    (``hs_eigs_*``): shift-invert block Arnoldi with thick restart, one block solve of ``block`` columns per step.  ``sigma`` is bookkeeping:
+    the caller factors the shifted matrix.  ``F`` may be ``transpose(F)`` / ``adjoint(F)``: left eigenvectors (``y^T A = lambda y^T`` /
+    ``y^H A = lambda y^H``; the adjoint returns ``conj(lambda)``, the eigenvalues of ``A^H``).
+
+    Returns ``(lam, X)``, nearest first (``X`` is None with ``vectors=False``).  A Float64 factorization returns real arrays unless a
+    conjugate pair is among the results; then both are complex, and ``nev + 1`` pairs come back when the ``nev``-th would split a pair.
+    ``log=True`` adds a dict: ``resid`` (``||op(A_s) x - (lambda - sigma) x||_2`` with the factored matrix), ``est`` (the Ritz estimates the
+    iteration stopped on), ``restarts``, ``nsolves``, ``nconv``, ``seconds``, ``replaced`` (columns replaced after a rank deficiency).
+    ``ncv`` (basis columns, ``ncv + block <= 256``), ``block`` (<= 64): None selects the defaults (16, and the multiple of ``block`` at or above
+    ``max(2 nev + block, 4 block)``).  ``v0``: an ``n x block`` start block.  Fewer than the wanted pairs within ``tol`` after ``maxrestart``
+    restarts raises :class:`NoConvergence`, whose ``partial`` is the tuple that would have been returned (with the log)."""
+    F, trans = _unwrap(F)
+    n = F.n
+    cx = F.dtype.kind == "c"
+    sigma = complex(sigma)
+    if not cx and sigma.imag != 0.0:
+        raise ValueError("ArgumentError: eigs: a complex shift on a Float64 factorization (factor A - sigma*I as ComplexF64)")
+    nev = int(nev)
+    if nev < 1:
+        raise ValueError(f"ArgumentError: eigs: nev = {nev} < 1")
+    V0 = None
+    if v0 is not None:
+        V0 = np.asarray(v0)
+        if V0.ndim == 1:
+            V0 = V0.reshape(-1, 1)
+        if block is None:
+            block = V0.shape[1]
+        if V0.ndim != 2 or V0.shape != (n, int(block)):
+            raise _lib.DimensionMismatch(f"DimensionMismatch: eigs: v0 is {V0.shape}, expected ({n}, {int(block)})")
+        if not cx and V0.dtype.kind == "c":
+            raise TypeError("MethodError: eigs: a ComplexF64 start block for a FactorNode{Float64}")
+        V0 = np.asfortranarray(V0, dtype=F.dtype)
+    if block is not None and not 1 <= int(block) <= 64:
+        raise ValueError(f"ArgumentError: eigs: block = {block} outside 1:64")
+    if ncv is not None and block is not None:  # the library checks the same after filling in its defaults
+        if int(ncv) + int(block) > 256:
+            raise ValueError(f"ArgumentError: eigs: ncv + block = {int(ncv)} + {int(block)} exceeds the limit of 256 basis columns")
+        if int(ncv) < nev + int(block):
+            raise ValueError(f"ArgumentError: eigs: ncv = {int(ncv)} < nev + block = {nev} + {int(block)}")
+        if n < int(ncv) + int(block):
+            raise ValueError(f"ArgumentError: eigs: n = {n} < ncv + block = {int(ncv)} + {int(block)}")
+    nx = nev + 1
+    lam = np.zeros(2 * nx)
+    X = np.zeros((n, nx), dtype=F.dtype, order="F") if vectors else None
+    resid, est = np.zeros(nx), np.zeros(nx)
+    nout, nconv = _lib.i64(), _lib.i64()
+    fn = getattr(_lib.lib(), "hs_eigs_z" if cx else "hs_eigs_d")
+    _lib.check(fn(F._h, trans, n, nev, int(ncv or 0), int(block or 0), sigma.real, sigma.imag, float(tol), int(maxrestart),
+                  V0.ctypes.data_as(C.c_void_p) if V0 is not None else None, max(n, 1), int(seed), 0, _pf64(lam),
+                  X.ctypes.data_as(C.c_void_p) if vectors else None, max(n, 1), _pf64(resid), _pf64(est), C.byref(nout), C.byref(nconv), None))
+    k = int(nout.value)
+    lamc = lam[0:2 * k:2] + 1j * lam[1:2 * k:2]
+    Xo = X[:, :k] if vectors else None
+    if not cx:
+        if np.any(lamc.imag != 0.0):
+            if vectors:  # the pair columns (real part, imaginary part) become the two complex vectors
+                Xo = Xo.astype(np.complex128)
+                c = 0
+                while c < k:
+                    if lamc[c].imag != 0.0 and c + 1 < k:
+                        xr, xi = X[:, c], X[:, c + 1]
+                        Xo[:, c], Xo[:, c + 1] = xr + 1j * xi, xr - 1j * xi
+                        c += 2
+                    else:
+                        c += 1
+        else:
+            lamc = lamc.real.copy()
+    res = (lamc, Xo)
+    if log or nconv.value < k:
+        info = eigs_info()
+        res = res + ({"resid": resid[:k].copy(), "est": est[:k].copy(), "restarts": info["restarts"], "nsolves": info["block_solves"], "nconv": int(nconv.value),
+                      "seconds": info["seconds"], "replaced": info["replaced"], "ncv": info["ncv"]},)
+    if nconv.value < k:
+        raise _lib.NoConvergence(f"eigs: {int(nconv.value)} of {k} eigenpairs within tol = {tol:g} after {res[2]['restarts']} restarts", partial=res)
     return res
 
 

@@ -170,6 +170,26 @@ int hsk_mod_gather_z(int64_t n, int64_t k, int64_t m, const double* Y, int64_t l
 int hsk_mod_cap_d(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt);
 int hsk_mod_cap_z(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt);
 
+/* The pieces of hs_eigs_* (kernels_eigs.hip, csrc/hs_small_eig.h) on host data; every block column-major.
+ *   hsk_eigs_rotate:    Out (n x N, ldo) = V (n x K, ldv) Q (K x N, ldq), K in 1..256, N in 1..K, on v_mfma_f64_16x16x4_f64.  inplace != 0: the
+ *                       kernel runs with Out = V on the device (the first N columns of V are overwritten there) and Out receives them.
+ *   hsk_eigs_chol_inv:  G (p x p Gram matrix, ldg, p in 1..64) = R^H R: R and Rinv = R^-1 (p x p, ld p, upper), *info = -1, or the first
+ *                       column whose pivot is not above (64 eps)^2 times the largest diagonal entry of G (R and Rinv are then undefined).
+ *   hsk_small_eig_z:    host only.  H (m x m ComplexF64, ldh, m in 1..256, not overwritten) -> eigenvalues w (m) and unit eigenvectors Y
+ *                       (m x m, ldy) with H Y = Y diag(w): Hessenberg reduction, shifted QR, back substitution.  HS_ERR_SINGULAR when the QR
+ *                       iteration does not converge. */
+int hsk_eigs_rotate_d(int64_t n, int64_t K, int64_t N, const double* V, int64_t ldv, const double* Q, int64_t ldq, int inplace, double* Out, int64_t ldo);
+int hsk_eigs_rotate_z(int64_t n, int64_t K, int64_t N, const double* V, int64_t ldv, const double* Q, int64_t ldq, int inplace, double* Out, int64_t ldo);
+int hsk_eigs_chol_inv_d(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info);
+int hsk_eigs_chol_inv_z(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info);
+int hsk_small_eig_z(int64_t m, const double* H, int64_t ldh, double* w, double* Y, int64_t ldy);
+/* Host-clock seconds of this thread's last hs_eigs_* call by phase: out4 = {block solves, orthogonalisation, restarts (host eigenproblem
+ * and basis rotation), Ritz vectors and residuals}.  The block solve is timed apart only while hsk_eigs_phase_timing is on (it adds one
+ * stream synchronisation per block solve and changes no result; returns the previous setting); otherwise its time is counted with the
+ * orthogonalisation that follows it. */
+int hsk_eigs_phase_timing(int on);
+int hsk_eigs_phases(double* out4);
+
 /* Microseconds per ROUND TRIP (two exchanges) between workgroup 0 and workgroup `peer` of one launch through agent-scope atomic stores and polled
  * loads -- the exchange primitive of the dataflow sweeps of ldiv! (kernels_solve_wide.hip).  peer = 1: another XCD, peer = 8: the same XCD. */
 double hsk_flow_pingpong_us(int peer, int iters);

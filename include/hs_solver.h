@@ -334,6 +334,42 @@ int hs_mod_ldiv_dev_z(hs_mod* M, int trans, double* dC, int64_t ldc, const doubl
 int hs_mod_info(hs_mod* M, double* out8);
 void hs_mod_free(hs_mod* M);
 
+/* ---- eigenpairs nearest a shift from the stored factors (hs_eigs.hip) --------------------------------------------------------------
+ * F factors A_s = A - sigma I (the caller subtracts the shift before factoring; sigma is bookkeeping, so that lambda comes back unshifted).
+ * The call returns the nev eigenvalues of A nearest sigma -- the eigenvalues theta of op(F)^-1 of largest modulus, mu = 1 / theta,
+ * lambda = sigma + mu -- with unit eigenvectors, by block Arnoldi with thick restart on op(F)^-1: per step one block solve with `block`
+ * columns, two passes of classical Gram-Schmidt against the basis, CholQR twice; a restart when ncv basis columns are full, from the
+ * eigenpairs of the projected matrix (computed on the host).  A column that turns out dependent on the basis (an invariant subspace, a
+ * start block of eigenvectors) is replaced by a seeded random vector.
+ *   trans     0: A x = lambda x.  1, 2: transpose(F) / adjoint(F), i.e. left eigenvectors (y^T A = lambda y^T, y^H A = lambda y^H); trans = 2
+ *             returns the eigenvalues of A^H, conj(lambda).
+ *   ncv, block  0 selects the defaults: block = 16, ncv = the multiple of block >= max(2 nev + block, 4 block), capped by ncv + block <= 256
+ *             and by n.  block <= 64.
+ *   tol       a Ritz pair counts as converged when est = ||B y||_2 / |theta| <= tol (B: the last block row of the projected relation).
+ *   V0        the start block, n x block (ldv0), or NULL: a seeded random block.  where: 0 host pointers (V0, X), 1 device pointers.
+ *   lam       2 (nev + 1) doubles: (re, im) per eigenvalue, nearest first.  X (n x (nev + 1), ldx; may be NULL): the vectors, unit 2-norm.
+ *   _d        sigma_im must be 0; vectors in LAPACK's real convention: a conjugate pair occupies two columns, real part then imaginary part
+ *             of the vector of the eigenvalue with the positive imaginary part, and shares resid and est; *nout = nev, or nev + 1 when a
+ *             pair would otherwise be split.
+ *   resid     nev + 1 doubles: ||op(A_s) x - mu x||_2 with the handle's own matrix (the factored one); est: the estimates above.
+ *   *nconv    how many of the *nout pairs met tol; fewer than *nout after maxrestart restarts is HS_OK -- the caller decides.
+ * Served: what hs_ldiv_block_dev_t_* serves, exact and compressed (a compressed handle yields the eigenpairs of its own F^-1, resid tells
+ * how far they are from those of A_s); its refusals (HSS interior blocks, more than one rank) are found by a zero-column solve and passed
+ * on with its message as HS_ERR_UNSUPPORTED before anything is written.  HS_ERR_ARGUMENT: nev < 1, ncv + block > 256, block > 64,
+ * ncv < nev + block, n < ncv + block, null outputs, trans outside 0..2, a complex shift in hs_eigs_d, a plan-only or unfactored handle.
+ * HS_ERR_DIMENSION: n != size(F) or the element type of the other entry point.  Two calls return the same bits; nothing depends on the
+ * launch grid.  The call returns when the results are on the host (or in X); it owns its workspace: (ncv + block + 1 + 2 (nev + 1)) n
+ * elements and the slab partials.
+ * hs_eigs_info: out8 = {device seconds, block solves, column applications, restarts, Gram-Schmidt passes, replaced columns, workspace
+ * bytes, ncv used} of this thread's last call. */
+int hs_eigs_d(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart,
+              const double* V0, int64_t ldv0, int64_t seed, int where, double* lam, double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv,
+              void* stream);
+int hs_eigs_z(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart,
+              const double* V0, int64_t ldv0, int64_t seed, int where, double* lam, double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv,
+              void* stream);
+int hs_eigs_info(double* out8);
+
 /* ---- accuracy tools: norm and condition estimates, refined solves with error bounds (hs_condest.hip) --------------------------
  * opnorm(A, 1), opnorm(A, Inf) of the handle's A (the values of the last hs_numeric_begin); p = 1 or 0 (= Inf).  The first call that needs
  * rows of A (p = 0, hs_condest p = 0, hs_ldiv_refine_* with trans = 0) builds a CSR map of A's pattern on the device and keeps it in the handle. */
