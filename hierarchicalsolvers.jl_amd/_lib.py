@@ -105,6 +105,7 @@ EXPORTS = [
     "hs_probs_stats_mode", "hs_probs_stats", "hs_trim", "hs_stream_order",
     "hsk_leaf_envelope", "hsk_envelope_enable", "hsk_op_flops_mode", "hsk_op_flops",
     "hsk_gemm_op_d", "hsk_gemm_lds_enable", "hsk_gemm_lds_launches",
+    "hsk_gemm_lds_edge_launches", "hsk_gemm_reg_launches", "hsk_gemm_lds_route", "hsk_gemm_schur_d",
 ]
 
 _lib = None
@@ -397,8 +398,13 @@ def lib():
     L.hsk_gemm_op_d.restype = C.c_int
     L.hsk_gemm_lds_enable.argtypes = [C.c_int]
     L.hsk_gemm_lds_enable.restype = C.c_int
-    L.hsk_gemm_lds_launches.argtypes = [C.c_int]
-    L.hsk_gemm_lds_launches.restype = C.c_longlong
+    for f in (L.hsk_gemm_lds_launches, L.hsk_gemm_lds_edge_launches, L.hsk_gemm_reg_launches):
+        f.argtypes = [C.c_int]
+        f.restype = C.c_longlong
+    L.hsk_gemm_lds_route.argtypes = [C.c_int] * 5
+    L.hsk_gemm_lds_route.restype = C.c_int
+    L.hsk_gemm_schur_d.argtypes = [i64, p_i64, p_i64, p_f64, p_f64, p_f64, C.c_int, p_i64, p_i64, C.c_int, p_f64]
+    L.hsk_gemm_schur_d.restype = C.c_int
     for f in (L.hsk_front_factor_d, L.hsk_front_factor_z):
         f.argtypes = [i64, i64, i64, p_f64, p_f64, p_f64, p_f64, p_i64, p_i64, p_f64]
         f.restype = C.c_int

@@ -204,16 +204,28 @@ __device__ inline void mat_of(const NodeDesc<T>* pn, int which, T*& p, int& ld, 
 }
 
 // ---- launch API (implemented in the kernels_*.hip files) -------------------------------------
-// lds_ok: every front of the batch passed hs_gemm_lds_front_ok for this op (Float64 plain updates only; decided on the host, Sched::gemm)
+// route: the lowest HS_GEMM_ROUTE_* any front of the batch needs for this op (Float64 plain updates only; decided on the host, Sched::gemm);
+// shifted: some front of an HS_GEMM_ROUTE_EDGE launch has its A at an odd row (the kernel runs it one row higher: the grid covers M + 1 rows)
+enum { HS_GEMM_ROUTE_REG = 0, HS_GEMM_ROUTE_LDS = 1, HS_GEMM_ROUTE_EDGE = 2 };
 template <class T>
-void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s, bool lds_ok = false);
-// May the plain update (cmat, r0, k0, k1) of a front with ni interior DOFs load its operands straight into LDS (gemm_op_lds_kernel)?  The
-// direct load moves 16 bytes per lane and is given 16-byte aligned sources only: with LF / UR / SB 16-byte aligned and even leading
-// dimensions (the caller's premise: Sched::aligned16) A = LF + r0 (+ ni when C is SB) + k0 ldl and B = B0 + k0 + c0 ldb are aligned when
-// the row offset and k0 are even.  K must be whole 16-column steps (the kernel has no zero-filling path).
-inline bool hs_gemm_lds_front_ok(int cmat, int r0, int k0, int k1, int ni) {
+void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s, int route = HS_GEMM_ROUTE_REG,
+                    bool shifted = false);
+// Which kernel may run the plain update (cmat, r0, k0, k1) of a front with ni interior DOFs?  The direct-to-LDS load moves 16 bytes per
+// lane and is given 16-byte aligned sources only.  With LF / UR / SB 16-byte aligned and even leading dimensions (the caller's premise:
+// Sched::aligned16) B = B0 + k0 + c0 ldb is aligned when k0 is even, and A = LF + r0 (+ ni when C is SB) + k0 ldl when its row offset is even.
+//   HS_GEMM_ROUTE_LDS   K whole 16-column steps, even k0 and row offset: gemm_op_lds_kernel (no zero-filling path, no shift)
+//   HS_GEMM_ROUTE_EDGE  even k0, but a K tail and / or an odd row offset: gemm_op_lds_edge_kernel (enveloped: gemm_op_env_lds_kernel), which
+//                       zero-fills the last K-step and runs a front with an odd row offset one row higher
+//   HS_GEMM_ROUTE_REG   odd k0 (or nothing to do): the register-staged gemm_op_kernel / gemm_op_env_kernel
+// A launch takes the lowest class one of its fronts needs: REG before EDGE before LDS (hs_gemm_lds_route_join).
+inline int hs_gemm_lds_route(int cmat, int r0, int k0, int k1, int ni) {
   const int K = (k1 < ni ? k1 : ni) - k0, arow = r0 + (cmat == HS_MAT_SB ? ni : 0);
-  return K > 0 && (K & 15) == 0 && !(k0 & 1) && !(arow & 1);
+  if (K <= 0 || (k0 & 1)) return HS_GEMM_ROUTE_REG;
+  return ((K & 15) == 0 && !(arow & 1)) ? HS_GEMM_ROUTE_LDS : HS_GEMM_ROUTE_EDGE;
+}
+inline int hs_gemm_lds_route_join(int a, int b) {
+  if (a == HS_GEMM_ROUTE_REG || b == HS_GEMM_ROUTE_REG) return HS_GEMM_ROUTE_REG;
+  return (a == HS_GEMM_ROUTE_EDGE || b == HS_GEMM_ROUTE_EDGE) ? HS_GEMM_ROUTE_EDGE : HS_GEMM_ROUTE_LDS;
 }
 bool hs_envelope_enabled();  // HS_LEAF_ENVELOPE (default on) / hsk_envelope_enable: leaf fronts are eliminated inside their block envelope
 template <class T>

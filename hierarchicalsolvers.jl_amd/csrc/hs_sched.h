@@ -88,8 +88,8 @@ struct Sched {
   bool env = false;                  // leaf fronts of the batch are eliminated inside their block envelope (NodeDesc::env, hs_envelope.h).  Only with
                                      // `optimistic`: the tournament swaps rows across 32-blocks, which breaks the row envelope
   const int* const* h_env = nullptr; // the same tables on the host, one pointer per front (null: dense), for the flop / byte accounting
-  bool aligned16 = false;            // LF, UR and SB of every front are 16-byte aligned and ldl, ldu, lds even (needs h_ni / h_nb): plain updates whose
-                                     // fronts all pass hs_gemm_lds_front_ok run gemm_op_lds_kernel (Float64)
+  bool aligned16 = false;            // LF, UR and SB of every front are 16-byte aligned and ldl, ldu, lds even (needs h_ni / h_nb): plain updates then
+                                     // run the direct-to-LDS kernel all their fronts allow (hs_gemm_lds_route; Float64)
 
   // HS_DEBUG_SYNC=1: synchronise after every launch and report the first failing one (diagnostics only)
   void dbg(const char* what, int a = 0, int b = 0, int c = 0, int d = 0) {
@@ -117,17 +117,22 @@ struct Sched {
     int M = std::min(r1, rows_of(cmat)) - r0, N = std::min(c1, cols_of(cmat)) - c0, K = std::min(k1, maxni) - k0;
     if (M <= 0 || N <= 0 || K <= 0) return;
     double fl = 0.0;
-    bool lds_ok = sizeof(T) == 8 && aligned16 && h_ni && !env;
+    int route = (sizeof(T) == 8 && aligned16 && h_ni) ? HS_GEMM_ROUTE_LDS : HS_GEMM_ROUTE_REG;
+    bool shifted = false;
     if (h_ni) {
       for (int i = 0; i < nbatch; ++i) {
         int ni = h_ni[i], nb = h_nb[i], m = ni + nb;
         int rows = cmat == HS_MAT_LF ? m : (cmat == HS_MAT_UR ? ni : nb), cols = cmat == HS_MAT_LF ? ni : nb;
         double Mi = std::min(r1, rows) - r0, Ni = std::min(c1, cols) - c0, Ki = std::min(k1, ni) - k0;
         if (Mi > 0 && Ni > 0 && Ki > 0) {
-          lds_ok = lds_ok && hs_gemm_lds_front_ok(cmat, r0, k0, k1, ni);
+          route = hs_gemm_lds_route_join(route, hs_gemm_lds_route(cmat, r0, k0, k1, ni));
+          shifted = shifted || ((r0 + (cmat == HS_MAT_SB ? ni : 0)) & 1);
           if (env && h_env && h_env[i]) {
-            // the clipped ranges, by the rule of the kernel (gemm_dispatch_env, kernels_gemm.hip): per tile of 128 x (128 | 64) the K loop
-            // starts at max(k0, min firstL of its rows, min firstU of its columns).  Bytes: C of the tiles that run, A / B once per tile
+            // the clipped ranges, by the rule of gemm_op_env_kernel (gemm_dispatch_env, kernels_gemm.hip): per tile of 128 x (128 | 64) the K
+            // loop starts at max(k0, min firstL of its rows, min firstU of its columns).  This is what the device counter of a counted launch adds
+            // up, and it does not depend on the routing.  gemm_op_env_lds_kernel tiles a front whose A sits at an odd row from one row higher
+            // (M + 1 rows from row0 - 1): its tiles' clips can start earlier and its first tile row always meets the last interior block, so
+            // it may run more K-steps than counted here, all of them over exact zeros of L -- work the result does not need.  Bytes: C of the tiles that run, A / B once per tile
             // row / column over the longest K range one of its tiles reads.
             const int BMh = 128, BNh = sizeof(T) == 16 ? 64 : 128;
             const int M_ = (int)Mi, N_ = (int)Ni, K_ = (int)Ki;
@@ -163,7 +168,7 @@ struct Sched {
       if (sizeof(T) == 16) fl *= 4.0;
     }
     hipEvent_t e0 = pf->begin(s);
-    launch_gemm_op<T>(dn, nbatch, M, N, op, s, lds_ok);
+    launch_gemm_op<T>(dn, nbatch, M, N, op, s, route, shifted);
     pf->end(e0, HS_CAT_GEMM, s, fl, M, N, K, nbatch);
     dbg("gemm", cmat, r0, c0, k0);
   }

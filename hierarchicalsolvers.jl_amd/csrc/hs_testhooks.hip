@@ -8,6 +8,7 @@
 
 #include "../../include/hs_kernels.h"
 #include "hs_sched.h"
+#include "hs_envelope.h"
 #include "hs_lowrank.h"
 #include "hs_solve_multi.h"
 
@@ -75,7 +76,8 @@ extern "C" int hsk_gemm_z(int64_t M, int64_t N, int64_t K, const double* A, int6
 // The plain update of a level, C -= A * B for a batch of `count` fronts, the way Sched::gemm issues the U12 update UR[r0.., :] -= LF[r0.., k0:k1) *
 // UR[k0:k1, :]: front f has K + M[f] (+ koff + roff) interior and N[f] boundary DOFs, A sits in LF at row r0 = koff + K + roff and column
 // k0 = koff, B in the rows k0.. of UR and C in its rows r0...  The schedule decides per launch between gemm_op_kernel and gemm_op_lds_kernel
-// exactly as in a factorization (hs_gemm_lds_front_ok, HS_GEMM_LDS / hsk_gemm_lds_enable); *routed says how many launches took the latter.
+// exactly as in a factorization (hs_gemm_lds_route, HS_GEMM_LDS / hsk_gemm_lds_enable); *routed says how many launches took the latter (the
+// launches of the edge kernels have a counter of their own, hsk_gemm_lds_edge_launches).
 // koff / roff = 1 shift B / A by one double (an operand the direct load may not take).
 static int gemm_op_hook(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A, const double* B,
                         double* C, int64_t* routed, int repeat, double* ms_out) {
@@ -171,6 +173,141 @@ static int gemm_op_hook(int64_t count, const int64_t* M, const int64_t* N, int64
 extern "C" int hsk_gemm_op_d(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A,
                              const double* B, double* C, int64_t* routed, int repeat, double* ms_out) {
   return gemm_op_hook(count, M, N, K, koff, roff, A, B, C, routed, repeat, ms_out);
+}
+
+// The Schur update of a level, SB -= LF[ni.., 0:ni) * UR, for a batch of `count` fronts with their own ni[f] and nb[f] -- what hsk_gemm_op_d
+// cannot pose: there every front has the same K and the same row offset, here K = ni[f] and A's row offset is ni[f].  LF, UR and SB are laid
+// out as hs_analyze lays them out (even leading dimensions, every matrix at a multiple of 32 elements) and the launch is
+// Sched::gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG).  A (nb x ni), B (ni x nb) and C (nb x nb, overwritten) are packed
+// column-major, front after front; everything else of the fronts -- the interior rows of LF, the padding rows, the gaps -- holds a finite
+// non-zero value, so a load that should have been a zero fill shows in the result.  A == B == C == null: no host data, the operands hold
+// that value too (timing only).  env != 0: the launch is enveloped and every front carries the block envelope of the zeros its A and B
+// really have (firstL of a 32-row block of A: the first column, rounded down to 32, with a non-zero entry in one of its rows; firstU of
+// a 32-column block of B likewise by rows; the interior blocks, which this product does not address, get their diagonal).
+static int gemm_schur_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, const double* A, const double* B, double* C, int env,
+                           int64_t* routed_lds, int64_t* routed_edge, int repeat, double* ms_out) {
+  typedef double T;
+  const bool data = A && B && C;
+  if (count <= 0 || count > 65535 || !ni_ || !nb_ || (!data && (A || B || C)) || (env && !data)) {
+    hs_set_error(HS_ERR_ARGUMENT, count, "hsk_gemm_schur_d: count in [1, 65535], ni and nb non-null, A, B, C all given or all null (env needs them) required");
+    return HS_ERR_ARGUMENT;
+  }
+  for (int64_t f = 0; f < count; ++f)
+    if (ni_[f] <= 0 || nb_[f] <= 0 || ni_[f] + nb_[f] > (1 << 20)) {
+      hs_set_error(HS_ERR_ARGUMENT, f, "hsk_gemm_schur_d: front %lld has ni = %lld, nb = %lld", (long long)f, (long long)ni_[f], (long long)nb_[f]);
+      return HS_ERR_ARGUMENT;
+    }
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
+    return HS_ERR_DEVICE;
+  }
+  auto rup32 = [](size_t e) { return (e + 31) / 32 * 32; };
+  auto even = [](int v) { return (v + 1) / 2 * 2; };
+  std::vector<NodeDesc<T>> hn(count);
+  std::vector<int> h_ni(count), h_nb(count);
+  std::vector<size_t> olf(count), our(count), osb(count), oenv(count);
+  size_t nT = 0, nE = 0;
+  int maxni = 0, maxnb = 0, maxm = 0;
+  for (int64_t f = 0; f < count; ++f) {
+    const int ni = (int)ni_[f], nb = (int)nb_[f];
+    h_ni[f] = ni; h_nb[f] = nb;
+    maxni = std::max(maxni, ni); maxnb = std::max(maxnb, nb); maxm = std::max(maxm, ni + nb);
+    olf[f] = nT; nT += rup32((size_t)even(ni + nb) * ni);
+    our[f] = nT; nT += rup32((size_t)even(ni) * nb);
+    osb[f] = nT; nT += rup32((size_t)even(nb) * nb);
+    oenv[f] = nE; nE += 2 * (size_t)hs_env_nblocks(ni, nb);
+  }
+  T* dbuf = nullptr;
+  NodeDesc<T>* dn = nullptr;
+  int* denv = nullptr;
+  struct Free {  // an early return of CK leaves nothing behind
+    T*& a; NodeDesc<T>*& b; int*& c;
+    ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); }
+  } free_all{dbuf, dn, denv};
+  CK(hipMalloc((void**)&dbuf, sizeof(T) * nT));
+  CK(hipMalloc((void**)&dn, sizeof(NodeDesc<T>) * count));
+  CK(hipMemsetD32(dbuf, 0x3F800000, 2 * nT));  // every double 0x3F8000003F800000 = 0.0078125...: finite, non-zero
+  std::vector<int> henv(env ? nE : 0);
+  std::vector<const int*> h_envp(count, nullptr);
+  if (env) CK(hipMalloc((void**)&denv, sizeof(int) * nE));
+  bool aligned = true;
+  const T *Af = A, *Bf = B;
+  T* Cf = C;
+  for (int64_t f = 0; f < count; ++f) {
+    NodeDesc<T>& d = hn[f];
+    memset(&d, 0, sizeof d);
+    d.ni = h_ni[f]; d.nb = h_nb[f]; d.m = d.ni + d.nb;
+    d.ldl = even(d.m); d.ldu = even(d.ni); d.lds = even(d.nb);
+    d.LF = dbuf + olf[f]; d.UR = dbuf + our[f]; d.SB = dbuf + osb[f];
+    d.ni1 = d.ni; d.nb1 = d.nb; d.node = (int)f;
+    const int ni = d.ni, nb = d.nb;
+    if (env) {
+      const int nI = (ni + 31) / 32, nblk = hs_env_nblocks(ni, nb);
+      int* fL = henv.data() + oenv[f];
+      int* fU = fL + nblk;
+      for (int b = 0; b < nblk; ++b) fL[b] = fU[b] = b < nI ? 32 * b : HS_ENV_NONE;
+      for (int k = 0; k < ni; ++k)
+        for (int r = 0; r < nb; ++r)
+          if (Af[(size_t)r + (size_t)k * nb] != 0.0) { int& v = fL[nI + r / 32]; v = std::min(v, k & ~31); }
+      for (int c = 0; c < nb; ++c)
+        for (int k = 0; k < ni; ++k)
+          if (Bf[(size_t)k + (size_t)c * ni] != 0.0) { int& v = fU[nI + c / 32]; v = std::min(v, k & ~31); break; }
+      d.env = denv + oenv[f];
+      h_envp[f] = fL;
+    }
+    d.finalize();
+    aligned = aligned && !((((uintptr_t)d.LF | (uintptr_t)d.UR | (uintptr_t)d.SB) & 15) || ((d.ldl | d.ldu | d.lds) & 1));
+    if (data) {
+      CK(hipMemcpy2D(d.LF + ni, sizeof(T) * d.ldl, Af, sizeof(T) * nb, sizeof(T) * nb, ni, hipMemcpyHostToDevice));
+      CK(hipMemcpy2D(d.UR, sizeof(T) * d.ldu, Bf, sizeof(T) * ni, sizeof(T) * ni, nb, hipMemcpyHostToDevice));
+      CK(hipMemcpy2D(d.SB, sizeof(T) * d.lds, Cf, sizeof(T) * nb, sizeof(T) * nb, nb, hipMemcpyHostToDevice));
+      Af += (size_t)nb * ni; Bf += (size_t)ni * nb; Cf += (size_t)nb * nb;
+    }
+  }
+  if (env) CK(hipMemcpy(denv, henv.data(), sizeof(int) * nE, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
+  Profiler prof;
+  Sched<T> sch{dn, (int)count, maxni, maxnb, maxm, (hipStream_t) nullptr, &prof, h_ni.data(), h_nb.data()};
+  sch.aligned16 = aligned;
+  if (env) {
+    sch.optimistic = true;
+    sch.env = true;
+    sch.h_env = h_envp.data();
+  }
+  const long long lds0 = hsk_gemm_lds_launches(0), edge0 = hsk_gemm_lds_edge_launches(0);
+  sch.gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG);
+  CK(hipDeviceSynchronize());
+  if (routed_lds) *routed_lds = (int64_t)(hsk_gemm_lds_launches(0) - lds0);
+  if (routed_edge) *routed_edge = (int64_t)(hsk_gemm_lds_edge_launches(0) - edge0);
+  if (data) {
+    Cf = C;
+    for (int64_t f = 0; f < count; ++f) {
+      const NodeDesc<T>& d = hn[f];
+      CK(hipMemcpy2D(Cf, sizeof(T) * d.nb, d.SB, sizeof(T) * d.lds, sizeof(T) * d.nb, d.nb, hipMemcpyDeviceToHost));
+      Cf += (size_t)d.nb * d.nb;
+    }
+  }
+  if (repeat > 0) {
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    CK(hipEventRecord(e0, 0));
+    for (int r = 0; r < repeat; ++r) sch.gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG);
+    CK(hipEventRecord(e1, 0));
+    CK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    if (ms_out) *ms_out = ms / repeat;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  prof.collect();
+  return HS_OK;
+}
+extern "C" int hsk_gemm_schur_d(int64_t count, const int64_t* ni, const int64_t* nb, const double* A, const double* B, double* C, int env,
+                                int64_t* routed_lds, int64_t* routed_edge, int repeat, double* ms_out) {
+  return gemm_schur_hook(count, ni, nb, A, B, C, env, routed_lds, routed_edge, repeat, ms_out);
 }
 
 // Factor a batch of `count` dense fronts F[k] ((ni[k]+nb[k])^2, column-major, front order [int;bnd], packed one after another) the way

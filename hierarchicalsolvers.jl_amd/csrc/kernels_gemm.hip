@@ -397,8 +397,15 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
 #define LDS_B_STAGE (BK * LDS_LD)             // doubles: the B image follows the A image of its stage
 #define LDS_STAGE_G (BK * LDS_LD + 128 * BK)  // doubles per stage: 18,432 + 16,384 bytes
 typedef __attribute__((address_space(3))) void* hs_lds_ptr;
-template <int BN_>
-__device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, int tile_n, bool minus, double* smem) {
+// EDGE (gemm_op_lds_edge_kernel, gemm_op_env_lds_kernel): the same tile for a K that is no multiple of BK and for a problem that was
+// shifted one row up to make A 16-byte aligned (edge_shift_rows).  Only the last, partial K-step differs: its k-rows of the A image and
+// k-pair chunks of the B image with k >= K are filled with zeros by ordinary LDS stores, as gemm_tile_d fills them, and all four MFMA
+// k-steps run -- every stored value keeps the bits gemm_op_kernel gives.  For A the choice is wave-uniform per k-row; for B it is per
+// lane: a chunk below K takes the direct load, a chunk at or above K the zeros, and with an odd K the chunk (K - 1, K) an 8-byte load of
+// B[K - 1] and a stored (v, 0).  Nothing is read at k >= K.  mlo = 1: row 0 of the shifted problem is not C's; it is neither loaded
+// nor stored.
+template <int BN_, bool EDGE = false>
+__device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, int tile_n, bool minus, double* smem, int mlo = 0) {
   constexpr int BN = BN_;  // 128
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -419,6 +426,33 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
     double* As = smem + stage * LDS_STAGE_G;
     double* Bs = As + LDS_B_STAGE;
     const double* a = a_src + (size_t)k0 * p.lda;
+    if constexpr (EDGE) {
+      if (k0 + BK > K) {  // the partial K-step (uniform over the workgroup)
+        const double2_u zero2 = {0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          double* row = As + (wave + 4 * i) * LDS_LD;
+          if (k0 + wave + 4 * i < K)
+            __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(a + i * a_row4), (hs_lds_ptr)row, 16, 0, 0);
+          else
+            *(double2_u*)(row + 2 * lane) = zero2;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int n = 8 * (wave + 4 * i) + (lane >> 3);
+          const int kk = k0 + 2 * ((lane & 7) ^ ((n >> 1) & 7));  // this lane's slot holds k = kk, kk + 1
+          double* blk = Bs + (wave + 4 * i) * (8 * BK);
+          if (kk + 1 < K) {
+            __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(b_src[i] + k0), (hs_lds_ptr)blk, 16, 0, 0);
+          } else {
+            double2_u v = zero2;
+            if (kk < K) v.x = gld(b_src[i] + k0);  // kk == K - 1
+            *(double2_u*)(blk + 2 * lane) = v;
+          }
+        }
+        return;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(a + i * a_row4), (hs_lds_ptr)(As + (wave + 4 * i) * LDS_LD), 16, 0, 0);
@@ -491,7 +525,7 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int mm = m0 + wm * 64 + i * 16 + l15;
-    const bool rok = mm < M;
+    const bool rok = EDGE ? (mm < M && mm >= mlo) : (mm < M);
     double cv[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -811,8 +845,8 @@ struct TileCfg<cplx> {
 // GemmOp::count is set -- launch_gemm_op then sends EVERY plain update there, dense ones included; gemm_op_kernel itself never counts
 __device__ double g_op_flops;
 
-template <class T, bool GLDS = false>  // GLDS: the real tile with direct-to-LDS operand loads (gemm_op_lds_kernel)
-__device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* smem) {
+template <class T, bool GLDS = false, bool EDGE = false>  // GLDS: the real tile with direct-to-LDS operand loads (gemm_op_lds_kernel; EDGE: gemm_op_lds_edge_kernel)
+__device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* smem, int mlo = 0) {
   int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + TileCfg<T>::bn - 1) / TileCfg<T>::bn;
   int ntiles = tiles_m * tiles_n;
   // a launch may be capped to fewer workgroups than tiles (GemmOp::cap): each workgroup then walks the tiles
@@ -822,7 +856,9 @@ __device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* s
     int t = xcd_remap_shift(bid, ntiles, (gridDim.x & 7u) ? shift : 0);  // (a walking workgroup keeps its XCD only when gridDim.x is a multiple of 8: then shift == 0)
     int tm, tn;
     tile_coords(t, tiles_m, tiles_n, tm, tn);
-    if constexpr (GLDS)
+    if constexpr (GLDS && EDGE)
+      gemm_tile_d_lds<128, true>(p, tm, tn, minus, smem, mlo);
+    else if constexpr (GLDS)
       gemm_tile_d_lds<128>(p, tm, tn, minus, smem);
     else if constexpr (sizeof(T) == 8)
       gemm_tile_d<128>(p, tm, tn, minus, smem);
@@ -833,8 +869,8 @@ __device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* s
 }
 
 // The same walk for a launch whose fronts may carry a block envelope (gemm_op_env_kernel, trsm_inv_env_kernel below)
-template <class T>
-__device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* smem, const EnvClip* e, int count) {
+template <class T, bool GLDS = false>  // GLDS: the edge tile with direct-to-LDS operand loads (gemm_op_env_lds_kernel)
+__device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* smem, const EnvClip* e, int count, int mlo = 0) {
   int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + TileCfg<T>::bn - 1) / TileCfg<T>::bn;
   int ntiles = tiles_m * tiles_n;
   // a launch may be capped to fewer workgroups than tiles (GemmOp::cap): each workgroup then walks the tiles
@@ -865,7 +901,9 @@ __device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* sme
     p.K -= dk;
     if (ran) __syncthreads();  // this tile re-uses the LDS stages of the last one that ran
     ran = true;
-    if constexpr (sizeof(T) == 8)
+    if constexpr (GLDS)
+      gemm_tile_d_lds<128, true>(p, tm, tn, minus, smem, mlo);
+    else if constexpr (sizeof(T) == 8)
       gemm_tile_d<128>(p, tm, tn, minus, smem);
     else
       gemm_tile_z(p, tm, tn, minus, smem);
@@ -895,6 +933,30 @@ __global__ __launch_bounds__(256, 2) void gemm_op_lds_kernel(const NodeDesc<T>* 
   if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
   gemm_dispatch<T, true>(p, true, smem);
 }
+// A plain update whose A sits at an odd row (r0, plus ni when C is SB) has an A that is 8 but not 16 bytes off a 16-byte boundary.  The
+// edge kernels then run the problem one row higher: A' = A - 1 row, C' = C - 1 row, M' = M + 1 -- the extra row lies inside LF's column
+// (arow - 1 >= 0), its accumulators are never stored and C' row 0 is never touched (mlo = 1 in the tile).  Every entry of C still takes
+// its k-steps in the same order.  Decided per front from the resolved pointer, so a batch may mix odd and even ni.
+__device__ inline int edge_shift_rows(GemmProb<double>& p) {
+  if (!((uintptr_t)p.A & 15)) return 0;
+  p.A -= 1;
+  p.C -= 1;
+  p.M += 1;
+  p.flag_rows += 1;
+  return 1;
+}
+// The plain dense update with direct-to-LDS loads for the launches gemm_op_lds_kernel does not take: a K that is no multiple of 16
+// and / or an odd row offset of A (hs_gemm_lds_route: HS_GEMM_ROUTE_EDGE).  Again a kernel of its own, with its own instantiation of the tile.
+template <class T>
+__global__ __launch_bounds__(256, 2) void gemm_op_lds_edge_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
+  static_assert(sizeof(T) == 8, "real double only");
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  GemmProb<T> p;
+  if (op.prio) __builtin_amdgcn_s_setprio(2);
+  if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
+  const int mlo = edge_shift_rows(p);
+  gemm_dispatch<T, true, true>(p, true, smem, mlo);
+}
 // The TRSM base case (X <- inv(diagonal block) * X, in place) runs the same tile code under its own name, so that
 // profiles separate the trailing updates (gemm_op_kernel: the flops) from the 32-row solves (latency).
 template <class T>
@@ -917,6 +979,26 @@ __global__ __launch_bounds__(256, 2) void gemm_op_env_kernel(const NodeDesc<T>* 
   if (op.ainv) return;  // (launch_gemm_op sends those to trsm_inv_env_kernel: lets the compiler drop the in-place forms and their growth check here)
   if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
   gemm_dispatch_env<T>(p, true, smem, &e, op.count);
+}
+// The enveloped plain update on the edge tile (batches of leaf fronts whose k0 is even): the clip moves A and B by a multiple of 32
+// columns / rows, which keeps their alignment and the K tail.  A shifted front looks its rows up one position higher (row0 - 1): the
+// clip of a tile can only start earlier, over exact zeros of L.  The price of the shift: tile row 0 of a shifted front with C in SB begins
+// at front row ni - 1, the last interior block, whose firstL is its own diagonal -- the clip of those tiles starts no later than
+// 32 (ceil(ni / 32) - 1) and they are never skipped, where the unshifted tiling may skip them or start later.  Not measured on its own (at
+// Poisson 128^3 8 of the 512 leaves have an odd ni); the host accounting (Sched::gemm) keeps describing the unshifted tiling.
+// Counted launches (GemmOp::count) stay on gemm_op_env_kernel.
+template <class T>
+__global__ __launch_bounds__(256, 2) void gemm_op_env_lds_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
+  static_assert(sizeof(T) == 8, "real double only");
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  GemmProb<T> p;
+  EnvClip e;
+  if (op.prio) __builtin_amdgcn_s_setprio(2);
+  if (op.ainv) return;
+  if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
+  const int mlo = edge_shift_rows(p);
+  e.row0 -= mlo;
+  gemm_dispatch_env<T, true>(p, true, smem, &e, 0, mlo);
 }
 template <class T>
 __global__ __launch_bounds__(256, 2) void trsm_inv_env_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
@@ -979,8 +1061,10 @@ std::atomic<int> g_env_on{-1};      // -1: not read yet (HS_LEAF_ENVELOPE, defau
 std::atomic<int> g_op_count_on{0};
 std::atomic<int> g_lds_on{-1};      // -1: not read yet (HS_GEMM_LDS, default on)
 std::atomic<long long> g_lds_launches{0};
+std::atomic<long long> g_lds_edge_launches{0};
+std::atomic<long long> g_reg_launches{0};
 }  // namespace
-// HS_GEMM_LDS=0 / hsk_gemm_lds_enable(0): every plain update runs the register-staged gemm_op_kernel
+// HS_GEMM_LDS=0 / hsk_gemm_lds_enable(0): every plain update runs the register-staged gemm_op_kernel / gemm_op_env_kernel
 static bool gemm_lds_enabled() {
   int v = g_lds_on.load(std::memory_order_relaxed);
   if (v < 0) {
@@ -998,6 +1082,13 @@ extern "C" int hsk_gemm_lds_enable(int on) {  // returns the previous setting
 extern "C" long long hsk_gemm_lds_launches(int reset) {  // launches sent to gemm_op_lds_kernel since the last reset
   return reset ? g_lds_launches.exchange(0) : g_lds_launches.load();
 }
+extern "C" long long hsk_gemm_lds_edge_launches(int reset) {  // launches sent to gemm_op_lds_edge_kernel / gemm_op_env_lds_kernel
+  return reset ? g_lds_edge_launches.exchange(0) : g_lds_edge_launches.load();
+}
+extern "C" long long hsk_gemm_reg_launches(int reset) {  // plain, uncounted Float64 updates sent to gemm_op_kernel / gemm_op_env_kernel
+  return reset ? g_reg_launches.exchange(0) : g_reg_launches.load();
+}
+extern "C" int hsk_gemm_lds_route(int cmat, int r0, int k0, int k1, int ni) { return hs_gemm_lds_route(cmat, r0, k0, k1, ni); }
 bool hs_envelope_enabled() {
   int v = g_env_on.load();
   if (v < 0) {
@@ -1025,7 +1116,7 @@ extern "C" int hsk_op_flops(double* out) {
 }
 
 template <class T>
-void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s, bool lds_ok) {
+void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s, int route, bool shifted) {
   if (nbatch <= 0 || maxM <= 0 || maxN <= 0) return;
   GemmOp op = op_in;
   op.count = (!op.ainv && g_op_count_on.load(std::memory_order_relaxed)) ? 1 : 0;
@@ -1057,6 +1148,10 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
       (void)hipFree(dok);
     }
   }
+  // (the caller vouches for K and the alignment of every front: hs_gemm_lds_route)
+  if (sizeof(T) != 8 || op.ainv || op.count || !gemm_lds_enabled()) route = HS_GEMM_ROUTE_REG;
+  if (op.env && route == HS_GEMM_ROUTE_LDS) route = HS_GEMM_ROUTE_EDGE;  // one enveloped twin: the edge tile
+  if (route == HS_GEMM_ROUTE_EDGE && shifted) maxM += 1;  // a front whose A sits at an odd row runs one row higher (edge_shift_rows)
   int tiles = ((maxM + BM - 1) / BM) * ((maxN + TileCfg<T>::bn - 1) / TileCfg<T>::bn);
   if (op.cap > 0 && tiles > op.cap) tiles = std::max(8, op.cap / 8 * 8);
   // Enveloped launch (a batch of leaf fronts): most tiles of the bounding box are empty.  A workgroup per tile would start, read its
@@ -1075,6 +1170,29 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
     (void)hipFuncSetAttribute((const void*)trsm_inv_env_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     attr_set = true;
   }
+  if constexpr (sizeof(T) == 8) {
+    if (route != HS_GEMM_ROUTE_REG) {
+      constexpr int lds_bytes_g = 2 * LDS_STAGE_G * 8;
+      static std::once_flag attr_once_g;
+      std::call_once(attr_once_g, [] {
+        (void)hipFuncSetAttribute((const void*)gemm_op_lds_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_g);
+        (void)hipFuncSetAttribute((const void*)gemm_op_lds_edge_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_g);
+        (void)hipFuncSetAttribute((const void*)gemm_op_env_lds_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_g);
+      });
+      if (route == HS_GEMM_ROUTE_LDS) {
+        g_lds_launches.fetch_add(1, std::memory_order_relaxed);
+        hipLaunchKernelGGL(gemm_op_lds_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes_g, s, dnodes, op);
+      } else {
+        g_lds_edge_launches.fetch_add(1, std::memory_order_relaxed);
+        if (op.env)
+          hipLaunchKernelGGL(gemm_op_env_lds_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes_g, s, dnodes, op);
+        else
+          hipLaunchKernelGGL(gemm_op_lds_edge_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes_g, s, dnodes, op);
+      }
+      return;
+    }
+    if (!op.ainv && !op.count) g_reg_launches.fetch_add(1, std::memory_order_relaxed);
+  }
   if (op.env || op.count) {
     if (op.ainv)
       hipLaunchKernelGGL(trsm_inv_env_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
@@ -1082,19 +1200,8 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
       hipLaunchKernelGGL(gemm_op_env_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
   } else if (op.ainv)
     hipLaunchKernelGGL(trsm_inv_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
-  else {
-    if constexpr (sizeof(T) == 8) {
-      if (lds_ok && gemm_lds_enabled()) {  // (the caller vouches for K and the alignment of every front: hs_gemm_lds_front_ok)
-        constexpr int lds_bytes_g = 2 * LDS_STAGE_G * 8;
-        static std::once_flag attr_once_g;
-        std::call_once(attr_once_g, [] { (void)hipFuncSetAttribute((const void*)gemm_op_lds_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_g); });
-        g_lds_launches.fetch_add(1, std::memory_order_relaxed);
-        hipLaunchKernelGGL(gemm_op_lds_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes_g, s, dnodes, op);
-        return;
-      }
-    }
+  else
     hipLaunchKernelGGL(gemm_op_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
-  }
 }
 
 // hs_probs_stats: flops (counted by the kernels), launches and -- with timing on -- the summed launch durations of the grouped products,
@@ -1184,8 +1291,8 @@ void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN,
   hipLaunchKernelGGL(gemm_probs_kernel<T>, dim3(tiles, nprob), dim3(256), lds_bytes, s, dprobs, minus);
 }
 
-template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, const GemmOp&, hipStream_t, bool);
-template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t, bool);
+template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, const GemmOp&, hipStream_t, int, bool);
+template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t, int, bool);
 template void launch_gemm_probs<double>(const GemmProb<double>*, int, int, int, int, hipStream_t);
 template void launch_gemm_probs<cplx>(const GemmProb<cplx>*, int, int, int, int, hipStream_t);
 

@@ -147,12 +147,32 @@ int hsk_op_flops(double* out);
  * A launch runs `gemm_op_lds_kernel` (operands loaded straight into LDS) when every front qualifies -- K a multiple of 16, A and B 16-byte
  * aligned: koff / roff = 1 shift B / A by one double -- and `gemm_op_kernel` otherwise; *routed (may be null) receives the number of
  * launches that took the former.  repeat / ms_out as in hsk_gemm_d.
- *   hsk_gemm_lds_enable   : 0 sends every launch to gemm_op_kernel (default: on unless HS_GEMM_LDS=0); returns the previous setting.
- *   hsk_gemm_lds_launches : launches sent to gemm_op_lds_kernel since the last call with reset != 0. */
+ * A launch with an even koff that does not qualify -- a K tail, roff = 1 -- runs `gemm_op_lds_edge_kernel`, which is counted apart.
+ *   hsk_gemm_lds_enable        : 0 sends every launch to the register-staged gemm_op_kernel / gemm_op_env_kernel (default: on unless
+ *                                HS_GEMM_LDS=0); returns the previous setting.
+ *   hsk_gemm_lds_launches      : launches sent to gemm_op_lds_kernel since the last call with reset != 0.
+ *   hsk_gemm_lds_edge_launches : the same for gemm_op_lds_edge_kernel and its enveloped twin gemm_op_env_lds_kernel.
+ *   hsk_gemm_reg_launches      : the same for plain Float64 updates that went to gemm_op_kernel / gemm_op_env_kernel (not counted while
+ *                                hsk_op_flops_mode is on).
+ *   hsk_gemm_lds_route         : the routing rule itself, per front, on the host (no device needed): 0 register-staged (odd k0, or no K at
+ *                                all), 1 gemm_op_lds_kernel (K = min(k1, ni) - k0 a multiple of 16, k0 even, A's row offset r0 (+ ni when
+ *                                cmat is SB = 2) even), 2 the edge kernel (k0 even, K tail and / or odd row offset).  cmat: 0 LF, 1 UR, 2 SB.
+ *                                A launch takes the lowest class one of its fronts needs: 0 before 2 before 1. */
 int hsk_gemm_op_d(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A, const double* B,
                   double* C, int64_t* routed, int repeat, double* ms_out);
 int hsk_gemm_lds_enable(int on);
 long long hsk_gemm_lds_launches(int reset);
+long long hsk_gemm_lds_edge_launches(int reset);
+long long hsk_gemm_reg_launches(int reset);
+int hsk_gemm_lds_route(int cmat, int r0, int k0, int k1, int ni);
+
+/* The Schur update SB -= LF[ni.., 0:ni) * UR of a level through the same launch path, for `count` fronts with their own ni[f] and nb[f]
+ * (K = ni[f], A's row offset = ni[f]: a batch mixes K tails and odd / even offsets as a real level does).  A (nb x ni), B (ni x nb) and
+ * C (nb x nb, overwritten) are packed column-major, front after front; the rest of every front holds a finite non-zero value.  All three
+ * null: no host data, timing only.  env != 0: an enveloped launch, every front with the block envelope of the zeros of its A and B.
+ * *routed_lds / *routed_edge (may be null): launches that took gemm_op_lds_kernel / the edge kernels.  repeat / ms_out as in hsk_gemm_d. */
+int hsk_gemm_schur_d(int64_t count, const int64_t* ni, const int64_t* nb, const double* A, const double* B, double* C, int env,
+                     int64_t* routed_lds, int64_t* routed_edge, int repeat, double* ms_out);
 
 /* The kernels of hs_mod_* (kernels_mod.hip) on host data; every block column-major.
  *   hsk_mod_inner:   T (k x m, ldt) = op(P)^H Y, P n x k, Y n x m; conj != 0: op = conj, i.e. T = P^T Y (ComplexF64; ignored for Float64).
