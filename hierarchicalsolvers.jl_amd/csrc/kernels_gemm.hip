@@ -23,6 +23,7 @@
 #include <mutex>
 #include <vector>
 #include <algorithm>
+#include <initializer_list>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,10 +32,30 @@
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef hs_d2u double2_u;
 
-#define BM 128
-#define BK 16
-#define LDB_S 18   // B image is [n][k] with 16 + 2 padding: ds_write_b128 of a k-pair row segment and the MFMA-operand ds_read_b64 are both conflict-free
-#define LDS_LD 144  // 128 + 16: stride == 16 (mod 32) doubles => conflict-free ds_read_b64 across the two k rows of a half-wave
+// Tile geometry, one struct per element type: everything that sizes an LDS image, a stage or a launch is derived from these values.
+// A K-step is BK = 16 wide; a stage holds the A image [k][LDA] followed by the B image(s).
+template <class T>
+struct TileCfg;
+template <>
+struct TileCfg<double> {
+  static constexpr int BM = 128, BN = 128;  // output tile of the dense kernels (the skinny tiles cut 64 x 64 / 64 x 128 out of the same images)
+  static constexpr int BK = 16;
+  static constexpr int LDA = 144;  // 128 + 16: stride == 16 (mod 32) doubles => conflict-free ds_read_b64 across the two k rows of a half-wave
+  static constexpr int LDB = 18;   // B image is [n][k] with 16 + 2 padding: ds_write_b128 of a k-pair row segment and the MFMA-operand ds_read_b64 are both conflict-free
+  static constexpr int A_IMG = BK * LDA;                // doubles: the B image follows the A image of its stage
+  static constexpr int STAGE = A_IMG + BN * LDB;        // register-staged tiles: As [BK][LDA] then Bs [BN][LDB]
+  static constexpr int STAGE_LDS = A_IMG + BN * BK;     // direct-to-LDS tile: the B image is [n][BK], unpadded -- 18,432 + 16,384 bytes
+  static constexpr int smem_doubles = 2 * STAGE;        // two stages
+  static constexpr int smem_doubles_lds = 2 * STAGE_LDS;
+};
+template <>
+struct TileCfg<cplx> {
+  static constexpr int BM = 128, BN = 64;
+  static constexpr int BK = 16;
+  static constexpr int LDA = 144;  // planar A images [k][LDA], re then im
+  static constexpr int LDB = 18;   // planar B images [n][k], 16 + 2 padding as for the real tile
+  static constexpr int smem_doubles = 2 * BK * LDA + 2 * BN * LDB;  // one stage
+};
 
 // bijective XCD-aware remap of a 1-D block id (cdna guide section 5, "XCD swizzle must be bijective"):
 // blocks b and b+8 share an XCD; give each XCD a contiguous chunk of tile ids so neighbouring tiles
@@ -208,10 +229,77 @@ __device__ inline bool resolve_op(const NodeDesc<T>* pn, const GemmOp& op, GemmP
 // ------------------------------------------------------------------------------------------------
 // real double
 // ------------------------------------------------------------------------------------------------
-template <int BN_>
+// The pieces the real tiles share come first.  Left in copies ON PURPOSE, because the kernels sit at the register limit and the shared form
+// made some kernel worse (figures: profiles/r17_gemm_refactor.txt): gemm_tile_d_lds keeps its own epilogue (with real_epilogue its kernels go
+// from 195 / 198 to 211 / 222 VGPRs and run the Schur updates of Poisson 128^3 3-9 % slower, measured); the two 128 x 128 tiles keep their
+// own MFMA chain (one chain function: 108 -> 112 and 92 -> 108 bytes of scratch in the enveloped kernels); the edge loads are written out
+// in each load_tile (as a function they change the code of all five dense kernels).
+
+// Register staging of one K-step, shared by the register-staged real tiles: a thread holds PA row pairs of A (k rows KA apart) and PB k-pairs
+// of B (columns 32 apart); store() writes them into the LDS images As [k][LDA] / Bs [n][LDB] of a stage.
+template <int PA, int KA, int PB>
+struct RegStage {
+  double2_u ra[PA], rb[PB];
+  __device__ __forceinline__ void store(double* As, int a_k, int a_pair, int b_n, int b_kp) const {
+    using G = TileCfg<double>;
+    double* Bs = As + G::A_IMG;
+#pragma unroll
+    for (int i = 0; i < PA; ++i) {
+      double* dst = As + (a_k + KA * i) * G::LDA + 2 * a_pair;
+      dst[0] = ra[i].x;
+      dst[1] = ra[i].y;
+    }
+#pragma unroll
+    for (int i = 0; i < PB; ++i) {
+      double* dst = Bs + (b_n + 32 * i) * G::LDB + 2 * b_kp;  // 16-byte aligned: 144 n + 16 kp bytes
+      dst[0] = rb[i].x;
+      dst[1] = rb[i].y;
+    }
+  }
+};
+
+// C epilogue of the register-staged real tiles: acc[i][j][r] <-> C[mw + i*16 + l15][nw + j*16 + l4 + 4r], (mw, nw) the wave's corner of the tile.
+// All loads of a row block are issued before the first store (the compiler cannot prove the C addresses distinct and would otherwise
+// serialise load -> store -> load ...).  FLAG: the stored values may be multipliers (GemmProb::flag) and raise the growth flag.
+template <int MI, int NJ, bool FLAG>
+__device__ __forceinline__ void real_epilogue(const GemmProb<double>& p, const double4_t (&acc)[MI][NJ], int mw, int nw, int l15, int l4, bool minus) {
+  const int M = p.M, N = p.N;
+  double* __restrict__ C = p.C;
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int mm = mw + i * 16 + l15;
+    const bool rok = mm < M;
+    double cv[NJ][4];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int nn = nw + j * 16 + l4 + 4 * r;
+        cv[j][r] = (minus && rok && nn < N) ? gld(C + (size_t)mm + (size_t)nn * p.ldc) : 0.0;
+      }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int nn = nw + j * 16 + l4 + 4 * r;
+        if (rok && nn < N) {
+          // (value before address with the flag, address before value without: the order in which the tiles had it written out, which
+          // the compiler's schedule follows -- every kernel keeps its code)
+          if constexpr (FLAG) {
+            const double v = minus ? (cv[j][r] - acc[i][j][r]) : acc[i][j][r];
+            gst(C + (size_t)mm + (size_t)nn * p.ldc, v);
+            if (p.flag && mm < p.flag_rows && !(fabs(v) <= HS_GROWTH_MAX)) *p.flag = 1;  // uniform null test; NaN counts
+          } else {
+            gst(C + (size_t)mm + (size_t)nn * p.ldc, minus ? (cv[j][r] - acc[i][j][r]) : acc[i][j][r]);
+          }
+        }
+      }
+  }
+}
+
 __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int tile_n, bool minus, double* smem) {
-  constexpr int BN = BN_;  // 128
-  constexpr int STAGE = 2 * BK * LDS_LD;  // one LDS stage: As [BK][LDS_LD] then Bs [BK][LDS_LD]; two stages
+  using G = TileCfg<double>;
+  constexpr int BM = G::BM, BN = G::BN, BK = G::BK, LDA = G::LDA, LDB = G::LDB, STAGE = G::STAGE;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;
@@ -226,7 +314,7 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
   const int b_kp = tid & 7;     // k = 2*b_kp, 2*b_kp+1
   const int b_n = tid >> 3;     // + 32*i
 
-  double2_u ra[4], rb[4];
+  RegStage<4, 4, 4> st;
 
   // Global -> register staging.  Interior tiles take 16-byte loads with no guards.  Edge tiles use
   // clamped 8-byte loads + selects: a per-lane `if (in range) load` compiles to a branch with an
@@ -243,7 +331,7 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
     if ((rows_in || rows_even) && kfull) {  // an even row count: a row pair is inside or outside as a whole, outside pairs re-read the last one
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        ra[i] = gld2(A + (size_t)min(m0 + 2 * a_pair, M - 2) + (size_t)(k0 + a_k + 4 * i) * p.lda);
+        st.ra[i] = gld2(A + (size_t)min(m0 + 2 * a_pair, M - 2) + (size_t)(k0 + a_k + 4 * i) * p.lda);
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -251,14 +339,14 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
         const double* col = A + (size_t)min(kk, K - 1) * p.lda;
         double x = gld(col + min(mm, M - 1)), y = gld(col + min(mm + 1, M - 1));
         const bool kok = kk < K;
-        ra[i].x = (kok && mm < M) ? x : 0.0;
-        ra[i].y = (kok && mm + 1 < M) ? y : 0.0;
+        st.ra[i].x = (kok && mm < M) ? x : 0.0;
+        st.ra[i].y = (kok && mm + 1 < M) ? y : 0.0;
       }
     }
     if (kfull) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        rb[i] = gld2(B + (size_t)(k0 + 2 * b_kp) + (size_t)min(n0 + b_n + 32 * i, N - 1) * p.ldb);
+        st.rb[i] = gld2(B + (size_t)(k0 + 2 * b_kp) + (size_t)min(n0 + b_n + 32 * i, N - 1) * p.ldb);
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -266,27 +354,12 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
         const double* col = B + (size_t)min(nn, N - 1) * p.ldb;
         double x = gld(col + min(kk, K - 1)), y = gld(col + min(kk + 1, K - 1));
         const bool nok = nn < N;
-        rb[i].x = (nok && kk < K) ? x : 0.0;
-        rb[i].y = (nok && kk + 1 < K) ? y : 0.0;
+        st.rb[i].x = (nok && kk < K) ? x : 0.0;
+        st.rb[i].y = (nok && kk + 1 < K) ? y : 0.0;
       }
     }
   };
-  auto store_tile = [&](int stage) {
-    double* As = smem + stage * STAGE;
-    double* Bs = As + BK * LDS_LD;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      double* dst = As + (a_k + 4 * i) * LDS_LD + 2 * a_pair;
-      dst[0] = ra[i].x;
-      dst[1] = ra[i].y;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      double* dst = Bs + (b_n + 32 * i) * LDB_S + 2 * b_kp;  // 16-byte aligned: 144 n + 16 kp bytes
-      dst[0] = rb[i].x;
-      dst[1] = rb[i].y;
-    }
-  };
+  auto store_tile = [&](int stage) { st.store(smem + stage * STAGE, a_k, a_pair, b_n, b_kp); };
 
   double4_t acc[4][4];
 #pragma unroll
@@ -295,8 +368,8 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
     for (int j = 0; j < 4; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
 
   const int l15 = lane & 15, l4 = lane >> 4;
-  const int a_off = l4 * LDS_LD + wm * 64 + l15;
-  const int b_off = BK * LDS_LD + (wn * 64 + l15) * LDB_S + l4;
+  const int a_off = l4 * LDA + wm * 64 + l15;
+  const int b_off = G::A_IMG + (wn * 64 + l15) * LDB + l4;
 
   // Two LDS stages, ONE barrier per K-step: while the MFMAs of stage `cur` run, the next tile's global
   // loads are in flight; they are written to the other stage right after the MFMAs (every wave finished
@@ -320,16 +393,16 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int ks = 0; ks < BK / 4; ++ks) bf[j][ks] = b_rd[(j * 16) * LDB_S + ks * 4];
+        for (int ks = 0; ks < BK / 4; ++ks) bf[j][ks] = b_rd[(j * 16) * LDB + ks * 4];
       double af[BK / 4];
 #pragma unroll
-      for (int ks = 0; ks < BK / 4; ++ks) af[ks] = a_rd[(ks * 4) * LDS_LD];
+      for (int ks = 0; ks < BK / 4; ++ks) af[ks] = a_rd[(ks * 4) * LDA];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         double afn[BK / 4];
         if (i < 3) {
 #pragma unroll
-          for (int ks = 0; ks < BK / 4; ++ks) afn[ks] = a_rd[(ks * 4) * LDS_LD + (i + 1) * 16];
+          for (int ks = 0; ks < BK / 4; ++ks) afn[ks] = a_rd[(ks * 4) * LDA + (i + 1) * 16];
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -350,34 +423,7 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
     cur ^= 1;
   }
 
-  // epilogue: acc[i][j][r] <-> C[m0 + wm*64 + i*16 + l15][n0 + wn*64 + j*16 + l4 + 4r].
-  // All 16 loads of a row block are issued before the first store (the compiler cannot prove the C
-  // addresses distinct and would otherwise serialise load -> store -> load ...).
-  double* __restrict__ C = p.C;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int mm = m0 + wm * 64 + i * 16 + l15;
-    const bool rok = mm < M;
-    double cv[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int nn = n0 + wn * 64 + j * 16 + l4 + 4 * r;
-        cv[j][r] = (minus && rok && nn < N) ? gld(C + (size_t)mm + (size_t)nn * p.ldc) : 0.0;
-      }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int nn = n0 + wn * 64 + j * 16 + l4 + 4 * r;
-        if (rok && nn < N) {
-          const double v = minus ? (cv[j][r] - acc[i][j][r]) : acc[i][j][r];
-          gst(C + (size_t)mm + (size_t)nn * p.ldc, v);
-          if (p.flag && mm < p.flag_rows && !(fabs(v) <= HS_GROWTH_MAX)) *p.flag = 1;  // uniform null test; NaN counts
-        }
-      }
-  }
+  real_epilogue<4, 4, true>(p, acc, m0 + wm * 64, n0 + wn * 64, l15, l4, minus);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -385,7 +431,7 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
 // stages, the transposed MFMA issue, the order in which every accumulator takes its k-steps and the epilogue are those of gemm_tile_d, so
 // every stored value keeps its bits; what is gone are the staging registers ra / rb and the LDS store pass behind the MFMAs.
 // A wave-instruction writes 64 lanes x 16 B = 1 KiB at a wave-uniform LDS base, lane-linear; only the SOURCE address is per lane:
-//   A image [k][LDS_LD], as before: one instruction fills one k-row of 128 doubles (the 16 padding doubles of a row are never written or
+//   A image [k][LDA], as before: one instruction fills one k-row of 128 doubles (the 16 padding doubles of a row are never written or
 //     read).  Wave w issues the k-rows w, w + 4, w + 8, w + 12; lane l brings the row pair 2l, 2l + 1, clamped to the last pair of A.
 //   B image [n][BK], 128 B per column, no padding (a lane-linear write cannot skip any): the eight 16-byte k-pair chunks of column n sit at
 //     chunk index c ^ ((n >> 1) & 7).  One instruction fills eight columns; the lane whose slot is (n, c') fetches chunk c' ^ ((n >> 1) & 7)
@@ -394,8 +440,6 @@ __device__ inline void gemm_tile_d(const GemmProb<double>& p, int tile_m, int ti
 // The launch must qualify (launch_gemm_op): K a multiple of BK, A and B 16-byte aligned with even leading dimensions -- the row pair
 // (M - 1, M) of an odd M then lies inside A's column, and what it brings for row M feeds accumulators that are never stored.
 // ------------------------------------------------------------------------------------------------
-#define LDS_B_STAGE (BK * LDS_LD)             // doubles: the B image follows the A image of its stage
-#define LDS_STAGE_G (BK * LDS_LD + 128 * BK)  // doubles per stage: 18,432 + 16,384 bytes
 typedef __attribute__((address_space(3))) void* hs_lds_ptr;
 // EDGE (gemm_op_lds_edge_kernel, gemm_op_env_lds_kernel): the same tile for a K that is no multiple of BK and for a problem that was
 // shifted one row up to make A 16-byte aligned (edge_shift_rows).  Only the last, partial K-step differs: its k-rows of the A image and
@@ -404,9 +448,10 @@ typedef __attribute__((address_space(3))) void* hs_lds_ptr;
 // lane: a chunk below K takes the direct load, a chunk at or above K the zeros, and with an odd K the chunk (K - 1, K) an 8-byte load of
 // B[K - 1] and a stored (v, 0).  Nothing is read at k >= K.  mlo = 1: row 0 of the shifted problem is not C's; it is neither loaded
 // nor stored.
-template <int BN_, bool EDGE = false>
-__device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, int tile_n, bool minus, double* smem, int mlo = 0) {
-  constexpr int BN = BN_;  // 128
+template <bool EDGE>
+__device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, int tile_n, bool minus, double* smem, int mlo) {
+  using G = TileCfg<double>;
+  constexpr int BM = G::BM, BN = G::BN, BK = G::BK, LDA = G::LDA, STAGE = G::STAGE_LDS;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1;
@@ -423,15 +468,15 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
   }
   const size_t a_row4 = (size_t)4 * p.lda;
   auto issue_tile = [&](int k0, int stage) {
-    double* As = smem + stage * LDS_STAGE_G;
-    double* Bs = As + LDS_B_STAGE;
+    double* As = smem + stage * STAGE;
+    double* Bs = As + G::A_IMG;
     const double* a = a_src + (size_t)k0 * p.lda;
     if constexpr (EDGE) {
       if (k0 + BK > K) {  // the partial K-step (uniform over the workgroup)
         const double2_u zero2 = {0.0, 0.0};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          double* row = As + (wave + 4 * i) * LDS_LD;
+          double* row = As + (wave + 4 * i) * LDA;
           if (k0 + wave + 4 * i < K)
             __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(a + i * a_row4), (hs_lds_ptr)row, 16, 0, 0);
           else
@@ -455,7 +500,7 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(a + i * a_row4), (hs_lds_ptr)(As + (wave + 4 * i) * LDS_LD), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(a + i * a_row4), (hs_lds_ptr)(As + (wave + 4 * i) * LDA), 16, 0, 0);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       __builtin_amdgcn_global_load_lds((const void HS_AS_GLOBAL*)(b_src[i] + k0), (hs_lds_ptr)(Bs + (wave + 4 * i) * (8 * BK)), 16, 0, 0);
@@ -468,12 +513,12 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
     for (int j = 0; j < 4; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
 
   const int l15 = lane & 15, l4 = lane >> 4;
-  const int a_off = l4 * LDS_LD + wm * 64 + l15;
+  const int a_off = l4 * LDA + wm * 64 + l15;
   // B operand of k-step ks: k = l4 + 4 ks, chunk (k >> 1) ^ ((n >> 1) & 7) with (n >> 1) & 7 == l15 >> 1 for every j (n = wn 64 + j 16 + l15)
   int b_off[BK / 4];
 #pragma unroll
   for (int ks = 0; ks < BK / 4; ++ks)
-    b_off[ks] = LDS_B_STAGE + (wn * 64 + l15) * BK + 2 * ((2 * ks + (l4 >> 1)) ^ (l15 >> 1)) + (l4 & 1);
+    b_off[ks] = G::A_IMG + (wn * 64 + l15) * BK + 2 * ((2 * ks + (l4 >> 1)) ^ (l15 >> 1)) + (l4 & 1);
 
   // Two LDS stages, ONE barrier per K-step: the loads of the next tile go into the other stage before the MFMAs of this one (every wave
   // finished reading that stage before the previous barrier) and are waited for by the barrier that ends the step.
@@ -482,7 +527,7 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
   int cur = 0;
   for (int k0 = 0; k0 < K; k0 += BK) {
     if (k0 + BK < K) issue_tile(k0 + BK, cur ^ 1);
-    const double* s_rd = smem + cur * LDS_STAGE_G;
+    const double* s_rd = smem + cur * STAGE;
     const double* a_rd = s_rd + a_off;
     {
       double bf[4][BK / 4];
@@ -492,13 +537,13 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
         for (int ks = 0; ks < BK / 4; ++ks) bf[j][ks] = s_rd[b_off[ks] + (j * 16) * BK];
       double af[BK / 4];
 #pragma unroll
-      for (int ks = 0; ks < BK / 4; ++ks) af[ks] = a_rd[(ks * 4) * LDS_LD];
+      for (int ks = 0; ks < BK / 4; ++ks) af[ks] = a_rd[(ks * 4) * LDA];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         double afn[BK / 4];
         if (i < 3) {
 #pragma unroll
-          for (int ks = 0; ks < BK / 4; ++ks) afn[ks] = a_rd[(ks * 4) * LDS_LD + (i + 1) * 16];
+          for (int ks = 0; ks < BK / 4; ++ks) afn[ks] = a_rd[(ks * 4) * LDA + (i + 1) * 16];
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -520,7 +565,7 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
     cur ^= 1;
   }
 
-  // epilogue: as in gemm_tile_d
+  // epilogue: real_epilogue<4, 4, true> written out, plus the lower row bound of a shifted problem (see the top of this section)
   double* __restrict__ C = p.C;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -556,7 +601,8 @@ __device__ inline void gemm_tile_d_lds(const GemmProb<double>& p, int tile_m, in
 // ------------------------------------------------------------------------------------------------
 template <int BMs, int BNs>
 __device__ inline void gemm_tile_s_d(const GemmProb<double>& p, int tile_m, int tile_n, bool minus, double* smem) {
-  constexpr int STAGE = 2 * BK * LDS_LD;
+  using G = TileCfg<double>;
+  constexpr int BK = G::BK, LDA = G::LDA, LDB = G::LDB, STAGE = G::STAGE;
   constexpr int WM = BMs / 2, WN = BNs / 2, MI = WM / 16, NJ = WN / 16;
   constexpr int NP = BMs / 2, KA = 256 / NP, PA = BK / KA;  // A staging: row pairs, k rows per pass, passes
   constexpr int PB = BNs / 32;                               // B staging passes
@@ -569,14 +615,14 @@ __device__ inline void gemm_tile_s_d(const GemmProb<double>& p, int tile_m, int 
   const double* __restrict__ B = p.B;
   const int a_pair = tid % NP, a_k = tid / NP;
   const int b_kp = tid & 7, b_n = tid >> 3;
-  double2_u ra[PA], rb[PB];
+  RegStage<PA, KA, PB> st;
   const bool interior = (m0 + BMs <= M) && (n0 + BNs <= N);
   auto load_tile = [&](int k0) {
     if (interior && k0 + BK <= K) {
 #pragma unroll
-      for (int i = 0; i < PA; ++i) ra[i] = gld2(A + (size_t)(m0 + 2 * a_pair) + (size_t)(k0 + a_k + KA * i) * p.lda);
+      for (int i = 0; i < PA; ++i) st.ra[i] = gld2(A + (size_t)(m0 + 2 * a_pair) + (size_t)(k0 + a_k + KA * i) * p.lda);
 #pragma unroll
-      for (int i = 0; i < PB; ++i) rb[i] = gld2(B + (size_t)(k0 + 2 * b_kp) + (size_t)(n0 + b_n + 32 * i) * p.ldb);
+      for (int i = 0; i < PB; ++i) st.rb[i] = gld2(B + (size_t)(k0 + 2 * b_kp) + (size_t)(n0 + b_n + 32 * i) * p.ldb);
     } else {
 #pragma unroll
       for (int i = 0; i < PA; ++i) {
@@ -584,8 +630,8 @@ __device__ inline void gemm_tile_s_d(const GemmProb<double>& p, int tile_m, int 
         const double* col = A + (size_t)min(kk, K - 1) * p.lda;
         double x = gld(col + min(mm, M - 1)), y = gld(col + min(mm + 1, M - 1));
         const bool kok = kk < K;
-        ra[i].x = (kok && mm < M) ? x : 0.0;
-        ra[i].y = (kok && mm + 1 < M) ? y : 0.0;
+        st.ra[i].x = (kok && mm < M) ? x : 0.0;
+        st.ra[i].y = (kok && mm + 1 < M) ? y : 0.0;
       }
 #pragma unroll
       for (int i = 0; i < PB; ++i) {
@@ -593,35 +639,20 @@ __device__ inline void gemm_tile_s_d(const GemmProb<double>& p, int tile_m, int 
         const double* col = B + (size_t)min(nn, N - 1) * p.ldb;
         double x = gld(col + min(kk, K - 1)), y = gld(col + min(kk + 1, K - 1));
         const bool nok = nn < N;
-        rb[i].x = (nok && kk < K) ? x : 0.0;
-        rb[i].y = (nok && kk + 1 < K) ? y : 0.0;
+        st.rb[i].x = (nok && kk < K) ? x : 0.0;
+        st.rb[i].y = (nok && kk + 1 < K) ? y : 0.0;
       }
     }
   };
-  auto store_tile = [&](int stage) {
-    double* As = smem + stage * STAGE;
-    double* Bs = As + BK * LDS_LD;
-#pragma unroll
-    for (int i = 0; i < PA; ++i) {
-      double* dst = As + (a_k + KA * i) * LDS_LD + 2 * a_pair;
-      dst[0] = ra[i].x;
-      dst[1] = ra[i].y;
-    }
-#pragma unroll
-    for (int i = 0; i < PB; ++i) {
-      double* dst = Bs + (b_n + 32 * i) * LDB_S + 2 * b_kp;
-      dst[0] = rb[i].x;
-      dst[1] = rb[i].y;
-    }
-  };
+  auto store_tile = [&](int stage) { st.store(smem + stage * STAGE, a_k, a_pair, b_n, b_kp); };
   double4_t acc[MI][NJ];
 #pragma unroll
   for (int i = 0; i < MI; ++i)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
   const int l15 = lane & 15, l4 = lane >> 4;
-  const int a_off = l4 * LDS_LD + wm * WM + l15;
-  const int b_off = BK * LDS_LD + (wn * WN + l15) * LDB_S + l4;
+  const int a_off = l4 * LDA + wm * WM + l15;
+  const int b_off = G::A_IMG + (wn * WN + l15) * LDB + l4;
   load_tile(0);
   store_tile(0);
   __syncthreads();
@@ -636,11 +667,11 @@ __device__ inline void gemm_tile_s_d(const GemmProb<double>& p, int tile_m, int 
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int ks = 0; ks < BK / 4; ++ks) bf[j][ks] = b_rd[(j * 16) * LDB_S + ks * 4];
+        for (int ks = 0; ks < BK / 4; ++ks) bf[j][ks] = b_rd[(j * 16) * LDB + ks * 4];
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int ks = 0; ks < BK / 4; ++ks) af[i][ks] = a_rd[(ks * 4) * LDS_LD + i * 16];
+        for (int ks = 0; ks < BK / 4; ++ks) af[i][ks] = a_rd[(ks * 4) * LDA + i * 16];
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -654,43 +685,23 @@ __device__ inline void gemm_tile_s_d(const GemmProb<double>& p, int tile_m, int 
     __syncthreads();
     cur ^= 1;
   }
-  double* __restrict__ C = p.C;
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int mm = m0 + wm * WM + i * 16 + l15;
-    const bool rok = mm < M;
-    double cv[NJ][4];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int nn = n0 + wn * WN + j * 16 + l4 + 4 * r;
-        cv[j][r] = (minus && rok && nn < N) ? gld(C + (size_t)mm + (size_t)nn * p.ldc) : 0.0;
-      }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int nn = n0 + wn * WN + j * 16 + l4 + 4 * r;
-        if (rok && nn < N) gst(C + (size_t)mm + (size_t)nn * p.ldc, minus ? (cv[j][r] - acc[i][j][r]) : acc[i][j][r]);
-      }
-  }
+  real_epilogue<MI, NJ, false>(p, acc, m0 + wm * WM, n0 + wn * WN, l15, l4, minus);
 }
 
 // ------------------------------------------------------------------------------------------------
 // complex double (planar split in LDS)
 // ------------------------------------------------------------------------------------------------
-#define ZBN 64
-#define ZLDB 18  // B images are [n][k], 16 + 2 padding (see LDB_S)
 __device__ inline void gemm_tile_z(const GemmProb<cplx>& p, int tile_m, int tile_n, bool minus, double* smem) {
+  using G = TileCfg<cplx>;
+  constexpr int BM = G::BM, BN = G::BN, BK = G::BK, LDA = G::LDA, LDB = G::LDB;
   double* Ar = smem;
-  double* Ai = Ar + BK * LDS_LD;
-  double* Br = Ai + BK * LDS_LD;
-  double* Bi = Br + ZBN * ZLDB;
+  double* Ai = Ar + BK * LDA;
+  double* Br = Ai + BK * LDA;
+  double* Bi = Br + BN * LDB;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;
-  const int m0 = tile_m * BM, n0 = tile_n * ZBN;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int M = p.M, N = p.N, K = p.K;
   const cplx* __restrict__ A = p.A;
   const cplx* __restrict__ B = p.B;
@@ -723,13 +734,13 @@ __device__ inline void gemm_tile_z(const GemmProb<cplx>& p, int tile_m, int tile
   auto store_tile = [&]() {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      int o = (a_k + 2 * i) * LDS_LD + a_m;
+      int o = (a_k + 2 * i) * LDA + a_m;
       Ar[o] = ra[i].x;
       Ai[o] = ra[i].y;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      int o = (b_n + 16 * i) * ZLDB + b_k;
+      int o = (b_n + 16 * i) * LDB + b_k;
       Br[o] = rb[i].x;
       Bi[o] = rb[i].y;
     }
@@ -744,8 +755,8 @@ __device__ inline void gemm_tile_z(const GemmProb<cplx>& p, int tile_m, int tile
       acci[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
     }
   const int l15 = lane & 15, l4 = lane >> 4;
-  const int a_off = l4 * LDS_LD + wm * 64 + l15;
-  const int b_off = (wn * 32 + l15) * ZLDB + l4;
+  const int a_off = l4 * LDA + wm * 64 + l15;
+  const int b_off = (wn * 32 + l15) * LDB + l4;
 
   load_tile(0);
   store_tile();
@@ -759,16 +770,16 @@ __device__ inline void gemm_tile_z(const GemmProb<cplx>& p, int tile_m, int tile
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int ks = 0; ks < BK / 4; ++ks) {
-          bfr[j][ks] = Br[b_off + (j * 16) * ZLDB + ks * 4];
-          bfi[j][ks] = Bi[b_off + (j * 16) * ZLDB + ks * 4];
+          bfr[j][ks] = Br[b_off + (j * 16) * LDB + ks * 4];
+          bfi[j][ks] = Bi[b_off + (j * 16) * LDB + ks * 4];
         }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         double afr[BK / 4], afi[BK / 4];
 #pragma unroll
         for (int ks = 0; ks < BK / 4; ++ks) {
-          afr[ks] = Ar[a_off + (ks * 4) * LDS_LD + i * 16];
-          afi[ks] = Ai[a_off + (ks * 4) * LDS_LD + i * 16];
+          afr[ks] = Ar[a_off + (ks * 4) * LDA + i * 16];
+          afi[ks] = Ai[a_off + (ks * 4) * LDA + i * 16];
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -826,68 +837,64 @@ __device__ inline void gemm_tile_z(const GemmProb<cplx>& p, int tile_m, int tile
   }
 }
 
-template <class T>
-struct TileCfg;
-template <>
-struct TileCfg<double> {
-  static constexpr int bn = 128;
-  static constexpr int smem_doubles = 2 * (2 * BK * LDS_LD);  // two stages
-};
-template <>
-struct TileCfg<cplx> {
-  static constexpr int bn = ZBN;
-  static constexpr int smem_doubles = 2 * BK * LDS_LD + 2 * ZBN * ZLDB;
-};
-
-
-
 // Device-side flop count of the plain updates (hsk_op_flops): the K-steps the tiles really ran, added up by gemm_op_env_kernel while
 // GemmOp::count is set -- launch_gemm_op then sends EVERY plain update there, dense ones included; gemm_op_kernel itself never counts
 __device__ double g_op_flops;
 
-template <class T, bool GLDS = false, bool EDGE = false>  // GLDS: the real tile with direct-to-LDS operand loads (gemm_op_lds_kernel; EDGE: gemm_op_lds_edge_kernel)
-__device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* smem, int mlo = 0) {
-  int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + TileCfg<T>::bn - 1) / TileCfg<T>::bn;
-  int ntiles = tiles_m * tiles_n;
-  // a launch may be capped to fewer workgroups than tiles (GemmOp::cap): each workgroup then walks the tiles
-  // bid, bid + gridDim.x, ... -- with gridDim.x a multiple of 8 they all stay in the same XCD chunk of the remap
-  const int shift = (int)((gridDim.x * blockIdx.y) & 7u);
-  for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+// Which real tile a dispatch runs (ComplexF64 has one tile, gemm_tile_z, whatever the tag)
+enum class Tile {
+  Reg,      // operands staged through registers: gemm_tile_d
+  Lds,      // operands loaded straight into LDS: gemm_tile_d_lds<false> (gemm_op_lds_kernel)
+  LdsEdge,  // the same for a ragged K and a problem shifted one row up: gemm_tile_d_lds<true> (gemm_op_lds_edge_kernel, gemm_op_env_lds_kernel)
+};
+// The tile walk of a workgroup over the tiles of an M x N problem: tile counts, the XCD remap and the tile order.  A launch may have fewer
+// workgroups than tiles (GemmOp::cap, enveloped launches): each workgroup then walks the tiles bid, bid + gridDim.x, ... -- with gridDim.x a
+// multiple of 8 they all stay in the same XCD chunk of the remap.
+template <class T>
+struct TileWalk {
+  int tiles_m, tiles_n, ntiles, shift;
+  __device__ __forceinline__ TileWalk(int M, int N) {
+    tiles_m = (M + TileCfg<T>::BM - 1) / TileCfg<T>::BM, tiles_n = (N + TileCfg<T>::BN - 1) / TileCfg<T>::BN;
+    ntiles = tiles_m * tiles_n;
+    shift = (int)((gridDim.x * blockIdx.y) & 7u);
+  }
+  __device__ __forceinline__ void coords(int bid, int& tm, int& tn) const {
     int t = xcd_remap_shift(bid, ntiles, (gridDim.x & 7u) ? shift : 0);  // (a walking workgroup keeps its XCD only when gridDim.x is a multiple of 8: then shift == 0)
-    int tm, tn;
     tile_coords(t, tiles_m, tiles_n, tm, tn);
-    if constexpr (GLDS && EDGE)
-      gemm_tile_d_lds<128, true>(p, tm, tn, minus, smem, mlo);
-    else if constexpr (GLDS)
-      gemm_tile_d_lds<128>(p, tm, tn, minus, smem);
-    else if constexpr (sizeof(T) == 8)
-      gemm_tile_d<128>(p, tm, tn, minus, smem);
-    else
+  }
+  __device__ __forceinline__ bool more(int bid) const { return bid + (int)gridDim.x < ntiles; }  // this workgroup has a tile after `bid`
+};
+template <class T, Tile TILE = Tile::Reg>
+__device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* smem, int mlo = 0) {
+  const TileWalk<T> w(p.M, p.N);
+  for (int bid = blockIdx.x; bid < w.ntiles; bid += gridDim.x) {
+    int tm, tn;
+    w.coords(bid, tm, tn);
+    if constexpr (sizeof(T) == 16)
       gemm_tile_z(p, tm, tn, minus, smem);
-    if (bid + (int)gridDim.x < ntiles) __syncthreads();  // the next tile re-uses the LDS stages
+    else if constexpr (TILE == Tile::Reg)
+      gemm_tile_d(p, tm, tn, minus, smem);
+    else
+      gemm_tile_d_lds<TILE == Tile::LdsEdge>(p, tm, tn, minus, smem, mlo);
+    if (w.more(bid)) __syncthreads();  // the next tile re-uses the LDS stages
   }
 }
 
-// The same walk for a launch whose fronts may carry a block envelope (gemm_op_env_kernel, trsm_inv_env_kernel below)
-template <class T, bool GLDS = false>  // GLDS: the edge tile with direct-to-LDS operand loads (gemm_op_env_lds_kernel)
+// The same loop for a launch whose fronts may carry a block envelope (gemm_op_env_kernel, trsm_inv_env_kernel below)
+template <class T, Tile TILE = Tile::Reg>  // (enveloped launches have no Tile::Lds twin: launch_gemm_op sends them to the edge tile)
 __device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* smem, const EnvClip* e, int count, int mlo = 0) {
-  int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + TileCfg<T>::bn - 1) / TileCfg<T>::bn;
-  int ntiles = tiles_m * tiles_n;
-  // a launch may be capped to fewer workgroups than tiles (GemmOp::cap): each workgroup then walks the tiles
-  // bid, bid + gridDim.x, ... -- with gridDim.x a multiple of 8 they all stay in the same XCD chunk of the remap
-  const int shift = (int)((gridDim.x * blockIdx.y) & 7u);
+  const TileWalk<T> w(p.M, p.N);
   bool ran = false;
-  for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-    int t = xcd_remap_shift(bid, ntiles, (gridDim.x & 7u) ? shift : 0);  // (a walking workgroup keeps its XCD only when gridDim.x is a multiple of 8: then shift == 0)
+  for (int bid = blockIdx.x; bid < w.ntiles; bid += gridDim.x) {
     int tm, tn;
-    tile_coords(t, tiles_m, tiles_n, tm, tn);
+    w.coords(bid, tm, tn);
     int dk = 0;
     {
       // Leaf front with a block envelope: everything here is uniform over the workgroup and done once per tile; the tile code is handed a
       // problem whose A, B and K are already shifted.  dk is a multiple of 32: the 16-byte operand loads keep their alignment and the
       // remaining BK-steps hold the same k as before, in the same order -- every stored value keeps its bits.
-      const int m_lo = tm * BM, n_lo = tn * TileCfg<T>::bn;
-      const int m_hi = min(m_lo + BM, p.M), n_hi = min(n_lo + TileCfg<T>::bn, p.N);
+      const int m_lo = tm * TileCfg<T>::BM, n_lo = tn * TileCfg<T>::BN;
+      const int m_hi = min(m_lo + TileCfg<T>::BM, p.M), n_hi = min(n_lo + TileCfg<T>::BN, p.N);
       if (e->fL || e->fU) {
         dk = hs_env_kstart(*e, m_lo, m_hi, n_lo, n_hi) - e->kbase;
         if (dk >= p.K) continue;  // only exact zeros left: nothing to subtract / zeros stay zeros (no LDS touched, so no barrier either)
@@ -901,24 +908,31 @@ __device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* sme
     p.K -= dk;
     if (ran) __syncthreads();  // this tile re-uses the LDS stages of the last one that ran
     ran = true;
-    if constexpr (GLDS)
-      gemm_tile_d_lds<128, true>(p, tm, tn, minus, smem, mlo);
-    else if constexpr (sizeof(T) == 8)
-      gemm_tile_d<128>(p, tm, tn, minus, smem);
-    else
+    if constexpr (sizeof(T) == 16)
       gemm_tile_z(p, tm, tn, minus, smem);
+    else if constexpr (TILE == Tile::Reg)
+      gemm_tile_d(p, tm, tn, minus, smem);
+    else
+      gemm_tile_d_lds<true>(p, tm, tn, minus, smem, mlo);
     p.A -= da;
     p.B -= dk;
     p.K += dk;
   }
 }
 
+// What a kernel of launch_gemm_op does before its tiles: raise the wave priority (always for the 32-row solves; for a plain update when
+// GemmOp::prio asks -- look-ahead panel work sharing CUs with the big trailing update) and resolve the op for this front.  (The enveloped
+// kernels write the two steps out: their form filter sits between them, and wherever else it was put their code changed.)
+template <class T, bool TRSM>
+__device__ __forceinline__ bool op_prologue(const NodeDesc<T>* __restrict__ nodes, const GemmOp& op, GemmProb<T>& p) {
+  if (TRSM || op.prio) __builtin_amdgcn_s_setprio(2);
+  return resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr);
+}
 template <class T>
 __global__ __launch_bounds__(256, 2) void gemm_op_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   GemmProb<T> p;
-  if (op.prio) __builtin_amdgcn_s_setprio(2);  // look-ahead panel work sharing CUs with the big trailing update
-  if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
+  if (!op_prologue<T, false>(nodes, op, p)) return;
   gemm_dispatch<T>(p, true, smem);
 }
 // The plain dense update again with its operands loaded straight into LDS (gemm_tile_d_lds): launch_gemm_op sends a launch here when
@@ -929,9 +943,8 @@ __global__ __launch_bounds__(256, 2) void gemm_op_lds_kernel(const NodeDesc<T>* 
   static_assert(sizeof(T) == 8, "real double only");
   extern __shared__ __attribute__((aligned(16))) double smem[];
   GemmProb<T> p;
-  if (op.prio) __builtin_amdgcn_s_setprio(2);
-  if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
-  gemm_dispatch<T, true>(p, true, smem);
+  if (!op_prologue<T, false>(nodes, op, p)) return;
+  gemm_dispatch<T, Tile::Lds>(p, true, smem);
 }
 // A plain update whose A sits at an odd row (r0, plus ni when C is SB) has an A that is 8 but not 16 bytes off a 16-byte boundary.  The
 // edge kernels then run the problem one row higher: A' = A - 1 row, C' = C - 1 row, M' = M + 1 -- the extra row lies inside LF's column
@@ -952,10 +965,9 @@ __global__ __launch_bounds__(256, 2) void gemm_op_lds_edge_kernel(const NodeDesc
   static_assert(sizeof(T) == 8, "real double only");
   extern __shared__ __attribute__((aligned(16))) double smem[];
   GemmProb<T> p;
-  if (op.prio) __builtin_amdgcn_s_setprio(2);
-  if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
+  if (!op_prologue<T, false>(nodes, op, p)) return;
   const int mlo = edge_shift_rows(p);
-  gemm_dispatch<T, true, true>(p, true, smem, mlo);
+  gemm_dispatch<T, Tile::LdsEdge>(p, true, smem, mlo);
 }
 // The TRSM base case (X <- inv(diagonal block) * X, in place) runs the same tile code under its own name, so that
 // profiles separate the trailing updates (gemm_op_kernel: the flops) from the 32-row solves (latency).
@@ -963,8 +975,7 @@ template <class T>
 __global__ __launch_bounds__(256, 2) void trsm_inv_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   GemmProb<T> p;
-  __builtin_amdgcn_s_setprio(2);
-  if (!resolve_op<T, false>(nodes + blockIdx.y, op, p, nullptr)) return;
+  if (!op_prologue<T, true>(nodes, op, p)) return;
   gemm_dispatch<T>(p, false, smem);
 }
 // The two kernels again for launches with GemmOp::env (batches of leaf fronts under optimistic pivoting) or GemmOp::count: kernels of their
@@ -998,7 +1009,7 @@ __global__ __launch_bounds__(256, 2) void gemm_op_env_lds_kernel(const NodeDesc<
   if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
   const int mlo = edge_shift_rows(p);
   e.row0 -= mlo;
-  gemm_dispatch_env<T, true>(p, true, smem, &e, 0, mlo);
+  gemm_dispatch_env<T, Tile::LdsEdge>(p, true, smem, &e, 0, mlo);
 }
 template <class T>
 __global__ __launch_bounds__(256, 2) void trsm_inv_env_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
@@ -1045,7 +1056,6 @@ __global__ __launch_bounds__(256, 2) void gemm_probs_skinny_kernel(const GemmPro
     if (bid + (int)gridDim.x < nt) __syncthreads();
   }
 }
-
 
 template <class T>
 __global__ void resolve_dump_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op, GemmProb<T>* out, int* ok) {
@@ -1115,44 +1125,70 @@ extern "C" int hsk_op_flops(double* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_op_flops), sizeof *out) == hipSuccess ? 0 : -6;
 }
 
+// HS_DEBUG_SYNC=2: print what the first fronts of a batch resolve this op to (diagnostics, no arithmetic)
+template <class T>
+static void dump_resolved_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s) {
+  GemmProb<T>* dp;
+  int* dok;
+  (void)hipMalloc((void**)&dp, sizeof(GemmProb<T>) * nbatch);
+  (void)hipMalloc((void**)&dok, sizeof(int) * nbatch);
+  hipLaunchKernelGGL(resolve_dump_kernel<T>, dim3(nbatch), dim3(1), 0, s, dnodes, op, dp, dok);
+  (void)hipStreamSynchronize(s);
+  GemmProb<T> hp;
+  int hok;
+  NodeDesc<T> hn;
+  for (int i = 0; i < nbatch && i < 4; ++i) {
+    (void)hipMemcpy(&hp, dp + i, sizeof hp, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&hok, dok + i, sizeof hok, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&hn, dnodes + i, sizeof hn, hipMemcpyDeviceToHost);
+    fprintf(stderr, "[hs debug] gemm op c%d b%d r[%d,%d) c[%d,%d) k[%d,%d) node%d: ok=%d A=%p B=%p C=%p M=%d N=%d K=%d ld=%d,%d,%d | LF=%p UR=%p SB=%p ni=%d nb=%d m=%d ld=%d,%d,%d maxM=%d maxN=%d\n",
+            op.cmat, op.bmat, op.r0, op.r1, op.c0, op.c1, op.k0, op.k1, i, hok, (void*)hp.A, (void*)hp.B, (void*)hp.C, hp.M, hp.N, hp.K, hp.lda,
+            hp.ldb, hp.ldc, (void*)hn.LF, (void*)hn.UR, (void*)hn.SB, hn.ni, hn.nb, hn.m, hn.ldl, hn.ldu, hn.lds, maxM, maxN);
+  }
+  (void)hipFree(dp);
+  (void)hipFree(dok);
+}
+
+// > 64 KiB of LDS per workgroup needs the opt-in, once per kernel and process (launches come from several streams and threads)
+template <class K>
+static void opt_in_lds(std::once_flag& once, std::initializer_list<K> kernels, int lds_bytes) {
+  std::call_once(once, [&] {
+    for (K k : kernels) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  });
+}
+
+// The kernel a launch of launch_gemm_op gets, with its LDS size and the launch counter it feeds (nullptr: none)
+template <class T>
+struct OpKernel {
+  void (*fn)(const NodeDesc<T>*, GemmOp);
+  int lds_bytes;
+  std::atomic<long long>* launches;
+};
+template <class T>
+static OpKernel<T> pick_op_kernel(const GemmOp& op, int route) {
+  constexpr int lds_reg = TileCfg<T>::smem_doubles * 8;
+  if constexpr (sizeof(T) == 8) {
+    constexpr int lds_direct = TileCfg<T>::smem_doubles_lds * 8;
+    if (route == HS_GEMM_ROUTE_LDS) return {gemm_op_lds_kernel<T>, lds_direct, &g_lds_launches};
+    if (route != HS_GEMM_ROUTE_REG) return {op.env ? gemm_op_env_lds_kernel<T> : gemm_op_lds_edge_kernel<T>, lds_direct, &g_lds_edge_launches};
+  }
+  std::atomic<long long>* const reg = (sizeof(T) == 8 && !op.ainv && !op.count) ? &g_reg_launches : nullptr;
+  if (op.env || op.count) return {op.ainv ? trsm_inv_env_kernel<T> : gemm_op_env_kernel<T>, lds_reg, reg};
+  return {op.ainv ? trsm_inv_kernel<T> : gemm_op_kernel<T>, lds_reg, reg};
+}
+
 template <class T>
 void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s, int route, bool shifted) {
   if (nbatch <= 0 || maxM <= 0 || maxN <= 0) return;
   GemmOp op = op_in;
   op.count = (!op.ainv && g_op_count_on.load(std::memory_order_relaxed)) ? 1 : 0;
-  {
-    static int dbg = -1;
-    if (dbg < 0) {
-      const char* e = getenv("HS_DEBUG_SYNC");
-      dbg = (e && e[0] == '2') ? 1 : 0;
-    }
-    if (dbg) {  // diagnostics: print what every front resolves this op to (no arithmetic)
-      GemmProb<T>* dp;
-      int* dok;
-      (void)hipMalloc((void**)&dp, sizeof(GemmProb<T>) * nbatch);
-      (void)hipMalloc((void**)&dok, sizeof(int) * nbatch);
-      hipLaunchKernelGGL(resolve_dump_kernel<T>, dim3(nbatch), dim3(1), 0, s, dnodes, op, dp, dok);
-      (void)hipStreamSynchronize(s);
-      GemmProb<T> hp;
-      int hok;
-      NodeDesc<T> hn;
-      for (int i = 0; i < nbatch && i < 4; ++i) {
-        (void)hipMemcpy(&hp, dp + i, sizeof hp, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(&hok, dok + i, sizeof hok, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(&hn, dnodes + i, sizeof hn, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[hs debug] gemm op c%d b%d r[%d,%d) c[%d,%d) k[%d,%d) node%d: ok=%d A=%p B=%p C=%p M=%d N=%d K=%d ld=%d,%d,%d | LF=%p UR=%p SB=%p ni=%d nb=%d m=%d ld=%d,%d,%d maxM=%d maxN=%d\n",
-                op.cmat, op.bmat, op.r0, op.r1, op.c0, op.c1, op.k0, op.k1, i, hok, (void*)hp.A, (void*)hp.B, (void*)hp.C, hp.M, hp.N, hp.K, hp.lda,
-                hp.ldb, hp.ldc, (void*)hn.LF, (void*)hn.UR, (void*)hn.SB, hn.ni, hn.nb, hn.m, hn.ldl, hn.ldu, hn.lds, maxM, maxN);
-      }
-      (void)hipFree(dp);
-      (void)hipFree(dok);
-    }
-  }
+  static const bool dump = getenv("HS_DEBUG_SYNC") && getenv("HS_DEBUG_SYNC")[0] == '2';
+  if (dump) dump_resolved_op(dnodes, nbatch, maxM, maxN, op, s);
   // (the caller vouches for K and the alignment of every front: hs_gemm_lds_route)
   if (sizeof(T) != 8 || op.ainv || op.count || !gemm_lds_enabled()) route = HS_GEMM_ROUTE_REG;
   if (op.env && route == HS_GEMM_ROUTE_LDS) route = HS_GEMM_ROUTE_EDGE;  // one enveloped twin: the edge tile
   if (route == HS_GEMM_ROUTE_EDGE && shifted) maxM += 1;  // a front whose A sits at an odd row runs one row higher (edge_shift_rows)
-  int tiles = ((maxM + BM - 1) / BM) * ((maxN + TileCfg<T>::bn - 1) / TileCfg<T>::bn);
+  int tiles = ((maxM + TileCfg<T>::BM - 1) / TileCfg<T>::BM) * ((maxN + TileCfg<T>::BN - 1) / TileCfg<T>::BN);
   if (op.cap > 0 && tiles > op.cap) tiles = std::max(8, op.cap / 8 * 8);
   // Enveloped launch (a batch of leaf fronts): most tiles of the bounding box are empty.  A workgroup per tile would start, read its
   // descriptor and leave; instead a quarter as many workgroups (HS_ENV_WALK, 1: off) walk the tiles, so that an empty tile costs a table
@@ -1161,47 +1197,17 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
     static const int walk = getenv("HS_ENV_WALK") ? atoi(getenv("HS_ENV_WALK")) : 4;
     if (walk > 1 && tiles >= 32 && (long long)tiles * nbatch >= 4096) tiles = std::max(8, tiles / walk / 8 * 8);
   }
-  constexpr int lds_bytes = TileCfg<T>::smem_doubles * 8;
-  static bool attr_set = false;
-  if (!attr_set) {  // > 64 KiB of LDS per workgroup needs the opt-in
-    (void)hipFuncSetAttribute((const void*)gemm_op_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    (void)hipFuncSetAttribute((const void*)trsm_inv_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    (void)hipFuncSetAttribute((const void*)gemm_op_env_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    (void)hipFuncSetAttribute((const void*)trsm_inv_env_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    attr_set = true;
-  }
+  static std::once_flag once_reg;
+  opt_in_lds(once_reg, {gemm_op_kernel<T>, trsm_inv_kernel<T>, gemm_op_env_kernel<T>, trsm_inv_env_kernel<T>}, TileCfg<T>::smem_doubles * 8);
   if constexpr (sizeof(T) == 8) {
     if (route != HS_GEMM_ROUTE_REG) {
-      constexpr int lds_bytes_g = 2 * LDS_STAGE_G * 8;
-      static std::once_flag attr_once_g;
-      std::call_once(attr_once_g, [] {
-        (void)hipFuncSetAttribute((const void*)gemm_op_lds_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_g);
-        (void)hipFuncSetAttribute((const void*)gemm_op_lds_edge_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_g);
-        (void)hipFuncSetAttribute((const void*)gemm_op_env_lds_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_g);
-      });
-      if (route == HS_GEMM_ROUTE_LDS) {
-        g_lds_launches.fetch_add(1, std::memory_order_relaxed);
-        hipLaunchKernelGGL(gemm_op_lds_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes_g, s, dnodes, op);
-      } else {
-        g_lds_edge_launches.fetch_add(1, std::memory_order_relaxed);
-        if (op.env)
-          hipLaunchKernelGGL(gemm_op_env_lds_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes_g, s, dnodes, op);
-        else
-          hipLaunchKernelGGL(gemm_op_lds_edge_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes_g, s, dnodes, op);
-      }
-      return;
+      static std::once_flag once_direct;
+      opt_in_lds(once_direct, {gemm_op_lds_kernel<T>, gemm_op_lds_edge_kernel<T>, gemm_op_env_lds_kernel<T>}, TileCfg<T>::smem_doubles_lds * 8);
     }
-    if (!op.ainv && !op.count) g_reg_launches.fetch_add(1, std::memory_order_relaxed);
   }
-  if (op.env || op.count) {
-    if (op.ainv)
-      hipLaunchKernelGGL(trsm_inv_env_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
-    else
-      hipLaunchKernelGGL(gemm_op_env_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
-  } else if (op.ainv)
-    hipLaunchKernelGGL(trsm_inv_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
-  else
-    hipLaunchKernelGGL(gemm_op_kernel<T>, dim3(tiles, nbatch), dim3(256), lds_bytes, s, dnodes, op);
+  const OpKernel<T> k = pick_op_kernel<T>(op, route);
+  if (k.launches) k.launches->fetch_add(1, std::memory_order_relaxed);
+  hipLaunchKernelGGL(k.fn, dim3(tiles, nbatch), dim3(256), k.lds_bytes, s, dnodes, op);
 }
 
 // hs_probs_stats: flops (counted by the kernels), launches and -- with timing on -- the summed launch durations of the grouped products,
@@ -1267,23 +1273,17 @@ void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN,
     hipEvent_t e; hipStream_t s;
     ~Rec() { if (e) (void)hipEventRecord(e, s); }
   } rec{pe1, s};
-  int tiles = ((maxM + BM - 1) / BM) * ((maxN + TileCfg<T>::bn - 1) / TileCfg<T>::bn);
+  int tiles = ((maxM + TileCfg<T>::BM - 1) / TileCfg<T>::BM) * ((maxN + TileCfg<T>::BN - 1) / TileCfg<T>::BN);
   constexpr int lds_bytes = TileCfg<T>::smem_doubles * 8;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_probs_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    attr_set = true;
-  }
+  static std::once_flag once;
+  opt_in_lds(once, {gemm_probs_kernel<T>}, lds_bytes);
   if constexpr (sizeof(T) == 8) {
     static const bool skinny = !(getenv("HS_GEMM_SKINNY") && getenv("HS_GEMM_SKINNY")[0] == '0');
     static const int small_tiles = getenv("HS_GEMM_SMALL_TILES") ? atoi(getenv("HS_GEMM_SMALL_TILES")) : 128;  // lists of at most this many 128 x 128 tiles
     if (skinny && (maxM <= 64 || (long long)tiles * nprob <= small_tiles)) {
       if (maxM > 64) tiles = ((maxM + 63) / 64) * ((maxN + 63) / 64);
-      static bool attr_set_s = false;
-      if (!attr_set_s) {
-        (void)hipFuncSetAttribute((const void*)gemm_probs_skinny_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        attr_set_s = true;
-      }
+      static std::once_flag once_skinny;
+      opt_in_lds(once_skinny, {gemm_probs_skinny_kernel}, lds_bytes);
       hipLaunchKernelGGL(gemm_probs_skinny_kernel, dim3(tiles, nprob), dim3(256), lds_bytes, s, (const GemmProb<double>*)dprobs, minus);
       return;
     }
@@ -1295,101 +1295,3 @@ template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, con
 template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t, int, bool);
 template void launch_gemm_probs<double>(const GemmProb<double>*, int, int, int, int, hipStream_t);
 template void launch_gemm_probs<cplx>(const GemmProb<cplx>*, int, int, int, int, hipStream_t);
-
-// ------------------------------------------------------------------------------------------------
-// FP64 MFMA issue-rate microbenchmark: the guides list no f64 MFMA peak (MI355X_MICROARCH.md
-// "Matrix cores" has no f64 row), so the roofline denominator is measured (bench.py --mfma-peak).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mfma_f64_rate_kernel(double* out, int iters) {
-  double4_t acc[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  double a = 1.0 + threadIdx.x * 1e-9, b = 1.0 - threadIdx.x * 1e-9;
-  for (int it = 0; it < iters; ++it) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[i], 0, 0, 0);
-  }
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
-  out[blockIdx.x * blockDim.x + threadIdx.x] = s;
-}
-
-// The same loop on RANDOM operands that change every iteration: under such data the chip holds its clock below the 2.4 GHz the datasheet
-// peak assumes (MI355X_MICROARCH.md, "DVFS give-back"), so this is the FP64 MFMA rate a real GEMM can approach.
-__global__ __launch_bounds__(256) void mfma_f64_rate_random_kernel(double* out, int iters, unsigned long long seed) {
-  double4_t acc[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  unsigned long long x = seed + (unsigned long long)(blockIdx.x * blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
-  auto next = [&]() {
-    x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-    return (double)(long long)(x >> 11) * (1.0 / 9007199254740992.0) - 0.5;
-  };
-  double a[4], b[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { a[q] = next(); b[q] = next(); }
-  for (int it = 0; it < iters; it += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[(u + i) & 3], b[(u + 2 * i + (i >> 1)) & 3], acc[i], 0, 0, 0);
-    if ((it & 1023) == 1020) {  // refresh the operands now and then (outside the hot issue pattern)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { a[q] = next(); b[q] = next(); }
-    }
-  }
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
-  out[blockIdx.x * blockDim.x + threadIdx.x] = s;
-}
-extern "C" double hsk_mfma_f64_peak_random(int waves_per_simd, int iters) {
-  int dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1.0;
-  const int blocks = prop.multiProcessorCount * waves_per_simd;
-  double* out = nullptr;
-  if (hipMalloc(&out, sizeof(double) * blocks * 256) != hipSuccess) return -1.0;
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  hipLaunchKernelGGL(mfma_f64_rate_random_kernel, dim3(blocks), dim3(256), 0, 0, out, iters, 12345ull);  // warm-up: the clock settles under load
-  (void)hipEventRecord(e0, 0);
-  hipLaunchKernelGGL(mfma_f64_rate_random_kernel, dim3(blocks), dim3(256), 0, 0, out, iters, 67890ull);
-  (void)hipEventRecord(e1, 0);
-  (void)hipEventSynchronize(e1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(out);
-  const double flops = (double)blocks * 4.0 * (double)iters * 8.0 * 2.0 * 16 * 16 * 4;
-  return flops / (ms * 1e-3) / 1e12;
-}
-
-// returns measured TFLOP/s of back-to-back v_mfma_f64_16x16x4_f64 (every CU, waves_per_simd waves per SIMD)
-extern "C" double hsk_mfma_f64_peak(int waves_per_simd, int iters) {
-  int dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1.0;
-  int cus = prop.multiProcessorCount;
-  int blocks = cus * waves_per_simd;  // 256 threads = 4 waves = one per SIMD
-  double* out = nullptr;
-  if (hipMalloc(&out, sizeof(double) * blocks * 256) != hipSuccess) return -1.0;
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
-  hipLaunchKernelGGL(mfma_f64_rate_kernel, dim3(blocks), dim3(256), 0, 0, out, iters / 10 + 1);
-  hipEventRecord(e0, 0);
-  hipLaunchKernelGGL(mfma_f64_rate_kernel, dim3(blocks), dim3(256), 0, 0, out, iters);
-  hipEventRecord(e1, 0);
-  hipEventSynchronize(e1);
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  hipFree(out);
-  double flops = (double)blocks * 4.0 * (double)iters * 8.0 * 2.0 * 16 * 16 * 4;
-  return flops / (ms * 1e-3) / 1e12;
-}

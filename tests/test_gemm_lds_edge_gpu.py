@@ -1,5 +1,5 @@
 """gemm_op_lds_edge_kernel / gemm_op_env_lds_kernel -- the direct-to-LDS Float64 update for a K that is no multiple of 16 and for an A at an
-odd row (kernels_gemm.hip, gemm_tile_d_lds<128, true>) -- against the register-staged gemm_op_kernel / gemm_op_env_kernel and against NumPy.
+odd row (kernels_gemm.hip, gemm_tile_d_lds<true>) -- against the register-staged gemm_op_kernel / gemm_op_env_kernel and against NumPy.
 
 The edge tile zero-fills the last, partial K-step as gemm_tile_d does and runs a front with an odd row offset one row higher, so every
 entry of C takes the same MFMAs on the same operands in the same order: results must be EQUAL (np.array_equal).  Against float64 `A @ B`

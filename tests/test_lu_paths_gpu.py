@@ -347,6 +347,51 @@ def test_group256_fused_kernel():
     assert r.returncode == 0 and "FUSED OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
 
 
+# ---- a capped trailing update: workgroups that walk several tiles (HS_LA_GEMM_CAP, read once per process) ---------------------------------
+
+_CAP_CHILD = r"""
+import sys, hashlib
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import numpy as np, hsamd
+import test_lu_paths_gpu as T
+hs = hsamd.load()
+rng = np.random.default_rng(71)
+ni, nb = 640, 40
+F = rng.standard_normal((ni + nb, ni + nb))
+F[np.arange(ni), np.arange(ni)] = 0.0
+r = T.front_batch(hs, [F], [ni], 0)[0]
+assert r["info"] == 0, r["info"]
+L = np.tril(r["LF"][:ni], -1) + np.eye(ni)
+assert np.linalg.norm(L @ np.triu(r["LF"][:ni]) - F[:ni, :ni][r["rperm"]]) <= 1e-13 * np.linalg.norm(F[:ni, :ni])
+h = hashlib.sha256()
+for k in ("LF", "UR", "SB", "rperm"):
+    h.update(np.ascontiguousarray(r[k]).tobytes())
+print("CAP", h.hexdigest())
+"""
+
+
+def test_capped_update_walks_tiles_bitwise():
+    """A lone front (ni = 640, nb = 40: 680 rows) under tournament pivoting with look-ahead in 128-column blocks (HS_LA_MIN, HS_LA_NB): the
+    first trailing update that runs next to a panel covers rows 128.. and columns 256.. of LF, 552 x 384 = 5 x 3 = 15 tiles of 128 x 128.
+    HS_LA_GEMM_CAP=8 launches it with 8 workgroups, seven of which walk two tiles (GemmOp::cap, gemm_dispatch); the default cap (448) gives
+    every tile a workgroup.  Which workgroup computes a tile does not change what is computed: factors, Schur complement and pivots are equal
+    bit for bit.
+    The capped path is taken only while Sched::factor_fronts looks ahead for this front (a second stream, mode 0 = tournament pivoting,
+    ni >= HS_LA_MIN): nothing the library exposes tells the two children apart, so if those preconditions change both run the same launches
+    and this test passes without walking -- keep the front and the switches in step with them."""
+    code = _CAP_CHILD % (ROOT, os.path.join(ROOT, "tests"))
+    out = []
+    for cap in ("8", None):
+        env = dict(os.environ, HS_LA_MIN="256", HS_LA_NB="128")
+        env.pop("HS_LA_GEMM_CAP", None)
+        if cap:
+            env["HS_LA_GEMM_CAP"] = cap
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (cap, r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+        out.append([ln for ln in r.stdout.splitlines() if ln.startswith("CAP")])
+    assert len(out[0]) == 1 and out[0] == out[1], out
+
+
 # ---- a level that redoes itself (end to end) --------------------------------------------------------------------------------------------
 
 _REDO_CHILD = r"""
