@@ -173,10 +173,10 @@ def lib():
     L.hs_ldiv_sparse_info.argtypes = [vp, p_f64]
     L.hs_ldiv_sparse_info.restype = C.c_int
     for f in (L.hsk_multi_prob_d, L.hsk_multi_prob_z):
-        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int]
+        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         f.restype = C.c_int
     for f in (L.hsk_multi_prob_t_d, L.hsk_multi_prob_t_z):
-        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, C.c_int]
+        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         f.restype = C.c_int
     L.hs_opnorm.argtypes = [vp, C.c_int, p_f64]
     L.hs_opnorm.restype = C.c_int

@@ -165,9 +165,12 @@ template <class T>
 void launch_multi_level(const SolveNode<T>* sn, int nfronts, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s);
 template <class T>
 void launch_multi_prob(const MultiProb<T>& p, int kc, hipStream_t s);
-// what = 0: W1 = (P B)[int, :]   1: Xb = B[bnd, :]   2: B[int, :] = W2   3: B[bnd, :] = Xb
+// The caller's column-major block <-> the row-major work blocks, for every front of a level:
+//   what = 0: W1 = B[int, :]   1: Xb = B[bnd, :]   2: B[int, :] = W2   3: B[bnd, :] = Xb
+// perm_what names the one interior move that goes through the front's row permutation (B[int[rperm[i]], :] <-> row i of the work block):
+// 0 for the forward solve (W1 = (P B)[int, :]), 2 for the transposed / adjoint one (B[int, :] = P^T W2); no other value is served.
 template <class T>
-void launch_multi_move(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s);
+void launch_multi_move(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm_what);
 
 // ---- kernels_solve_multi_t.hip --------------------------------------------------------------------------------------------------------
 // The product of the transposed / adjoint block solve:  D = op(A)^T X  or  D = Cin - op(A)^T X  with A stored K x M column-major (the
@@ -200,6 +203,3 @@ template <class T>
 void launch_multi_level_t(const SolveNode<T>* sn, int nfronts, int mode, int blk, int conj, int maxM, const MultiArgs& a, hipStream_t s);
 template <class T>
 void launch_multi_prob_t(const MultiProbT<T>& p, int kc, hipStream_t s);
-// what = 0: W1 = B[int, :]   1: Xb = B[bnd, :]   2: B[int[rperm[i]], :] = W2[i, :]   3: B[bnd, :] = Xb
-template <class T>
-void launch_multi_move_t(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s);

@@ -230,10 +230,7 @@ bool multi_t_left_looking() {
 // the grouped launches of either direction: trans = 0 runs kernels_solve_multi.hip (mode n), trans = 1, 2 kernels_solve_multi_t.hip (mode t)
 template <class T>
 void level_move(int trans, const SolveNode<T>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s) {
-  if (trans)
-    launch_multi_move_t<T>(sn, nf, what, maxrows, a, s);
-  else
-    launch_multi_move<T>(sn, nf, what, maxrows, a, s);
+  launch_multi_move<T>(sn, nf, what, maxrows, a, s, trans ? 2 : 0);
 }
 template <class T>
 void level_step(int trans, int cj, const SolveNode<T>* sn, int nf, int mode_n, int mode_t, int blk, int maxM, const MultiArgs& a, hipStream_t s) {

@@ -572,12 +572,16 @@ extern "C" int hsk_lowrank_z(int64_t rows, int64_t cols, const double* X, double
   return lowrank_hook<cplx>(rows, cols, (const cplx*)X, atol, rtol, kinit, seed, r_out, (cplx*)Cout, (cplx*)Zout, cap);
 }
 
-// the panel product of the block solves (kernels_solve_multi.hip) on host data; X and C reach the kernel row-major with a pitch of 64, as
-// the work blocks of the driver do
-template <class T>
-static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap) {
-  if (M < 1 || K < 0 || kc < 1 || kc > 64 || lda < M || ldx < std::max<int64_t>(K, 1) || ldc < M || !A || !X || !C) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_multi_prob: M >= 1, K >= 0, kc in 1..64, leading dimensions and non-null arrays required");
+// The panel products of the block solves (kernels_solve_multi.hip, kernels_solve_multi_t.hip) on host data, staged by one helper: X and C
+// reach the kernel row-major with a pitch of 64, as the work blocks of the driver do.  A is lda x acols with arows rows in use (forward
+// M x K, transposed K x M); map (null: none) has nmap entries in 0..nmap-1; launch(dA, dX, dC, dmap, pitch) fills the problem struct.
+template <class T, class Launch>
+static int multi_prob_stage(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx,
+                            T* C, int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
+  bool ok = M >= 1 && K >= 0 && kc >= 1 && kc <= 64 && lda >= std::max<int64_t>(arows, 1) && ldx >= std::max<int64_t>(K, 1) && ldc >= M && A && X && C;
+  for (int64_t i = 0; ok && map && i < nmap; ++i) ok = map[i] >= 0 && map[i] < nmap;
+  if (!ok) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "%s: M >= 1, K >= 0, kc in 1..64, leading dimensions, non-null arrays and map entries inside their range required", name);
     return HS_ERR_ARGUMENT;
   }
   int cnt = 0;
@@ -592,19 +596,18 @@ static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t
     for (int64_t i = 0; i < M; ++i) hc[i * P + c] = C[i + c * ldc];
   }
   T *dA = nullptr, *dX = nullptr, *dC = nullptr;
-  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)lda * std::max<int64_t>(K, 1)));
+  int* dmap = nullptr;
+  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)lda * std::max<int64_t>(acols, 1)));
   CK(hipMalloc((void**)&dX, sizeof(T) * hx.size()));
   CK(hipMalloc((void**)&dC, sizeof(T) * hc.size()));
-  if (K > 0) CK(hipMemcpy(dA, A, sizeof(T) * (size_t)lda * K, hipMemcpyHostToDevice));
+  if (K > 0) CK(hipMemcpy(dA, A, sizeof(T) * ((size_t)lda * (acols - 1) + arows), hipMemcpyHostToDevice));
   CK(hipMemcpy(dX, hx.data(), sizeof(T) * hx.size(), hipMemcpyHostToDevice));
   CK(hipMemcpy(dC, hc.data(), sizeof(T) * hc.size(), hipMemcpyHostToDevice));
-  MultiProb<T> p;
-  memset(&p, 0, sizeof p);
-  p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0;
-  p.X = dX; p.xrs = P;
-  p.Cin = minus ? dC : nullptr;
-  p.C = dC; p.crs = P;
-  launch_multi_prob<T>(p, (int)kc, 0);
+  if (map && nmap > 0) {
+    CK(hipMalloc((void**)&dmap, sizeof(int) * (size_t)nmap));
+    CK(hipMemcpy(dmap, map, sizeof(int) * (size_t)nmap, hipMemcpyHostToDevice));
+  }
+  launch(dA, dX, dC, dmap, P);
   CK(hipDeviceSynchronize());
   CK(hipMemcpy(hc.data(), dC, sizeof(T) * hc.size(), hipMemcpyDeviceToHost));
   for (int64_t c = 0; c < kc; ++c)
@@ -612,65 +615,51 @@ static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t
   (void)hipFree(dA);
   (void)hipFree(dX);
   (void)hipFree(dC);
+  (void)hipFree(dmap);
   return HS_OK;
+}
+// C = A X or C - A X, A M x K; map: cmap, row i of the product goes to row map[i] of C
+template <class T>
+static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, const int32_t* map) {
+  return multi_prob_stage<T>("hsk_multi_prob", M, K, kc, A, lda, M, K, X, ldx, C, ldc, map, M, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
+    MultiProb<T> p;
+    memset(&p, 0, sizeof p);
+    p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0;
+    p.X = dX; p.xrs = P;
+    p.Cin = minus ? dC : nullptr;
+    p.C = dC; p.crs = P; p.cmap = dmap;
+    launch_multi_prob<T>(p, (int)kc, 0);
+  });
+}
+// C = op(A)^T X or C - op(A)^T X, A K x M; map: xmap, row k of A meets row map[k] of X
+template <class T>
+static int multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj,
+                             const int32_t* map) {
+  return multi_prob_stage<T>("hsk_multi_prob_t", M, K, kc, A, lda, K, M, X, ldx, C, ldc, map, K, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
+    MultiProbT<T> p;
+    memset(&p, 0, sizeof p);
+    p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
+    p.X = dX; p.xrs = P; p.xmap = dmap;
+    p.Cin = minus ? dC : nullptr;
+    p.C = dC; p.crs = P;
+    launch_multi_prob_t<T>(p, (int)kc, 0);
+  });
 }
 extern "C" int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
-                                int64_t ldc, int minus, int trap) {
-  return multi_prob_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap);
+                                int64_t ldc, int minus, int trap, const int32_t* map) {
+  return multi_prob_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map);
 }
 extern "C" int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
-                                int64_t ldc, int minus, int trap) {
-  return multi_prob_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap);
-}
-
-// the panel product of the transposed block solves (kernels_solve_multi_t.hip) on host data: A is K x M, C = C - op(A)^T X or op(A)^T X
-template <class T>
-static int multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj) {
-  if (M < 1 || K < 0 || kc < 1 || kc > 64 || lda < std::max<int64_t>(K, 1) || ldx < std::max<int64_t>(K, 1) || ldc < M || !A || !X || !C) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_multi_prob_t: M >= 1, K >= 0, kc in 1..64, leading dimensions and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
-  const int64_t P = 64;
-  std::vector<T> hx((size_t)std::max<int64_t>(K, 1) * P), hc((size_t)M * P);
-  for (int64_t c = 0; c < kc; ++c) {
-    for (int64_t k = 0; k < K; ++k) hx[k * P + c] = X[k + c * ldx];
-    for (int64_t i = 0; i < M; ++i) hc[i * P + c] = C[i + c * ldc];
-  }
-  T *dA = nullptr, *dX = nullptr, *dC = nullptr;
-  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)lda * M));
-  CK(hipMalloc((void**)&dX, sizeof(T) * hx.size()));
-  CK(hipMalloc((void**)&dC, sizeof(T) * hc.size()));
-  if (K > 0) CK(hipMemcpy(dA, A, sizeof(T) * ((size_t)lda * (M - 1) + K), hipMemcpyHostToDevice));
-  CK(hipMemcpy(dX, hx.data(), sizeof(T) * hx.size(), hipMemcpyHostToDevice));
-  CK(hipMemcpy(dC, hc.data(), sizeof(T) * hc.size(), hipMemcpyHostToDevice));
-  MultiProbT<T> p;
-  memset(&p, 0, sizeof p);
-  p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
-  p.X = dX; p.xrs = P;
-  p.Cin = minus ? dC : nullptr;
-  p.C = dC; p.crs = P;
-  launch_multi_prob_t<T>(p, (int)kc, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy(hc.data(), dC, sizeof(T) * hc.size(), hipMemcpyDeviceToHost));
-  for (int64_t c = 0; c < kc; ++c)
-    for (int64_t i = 0; i < M; ++i) C[i + c * ldc] = hc[i * P + c];
-  (void)hipFree(dA);
-  (void)hipFree(dX);
-  (void)hipFree(dC);
-  return HS_OK;
+                                int64_t ldc, int minus, int trap, const int32_t* map) {
+  return multi_prob_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map);
 }
 extern "C" int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
-                                  int64_t ldc, int minus, int trap, int conj) {
-  return multi_prob_t_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj);
+                                  int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
+  return multi_prob_t_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map);
 }
 extern "C" int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
-                                  int64_t ldc, int minus, int trap, int conj) {
-  return multi_prob_t_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj);
+                                  int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
+  return multi_prob_t_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
 }
 
 // one grouped launch of the transposed ULV product (kernels_ulv_t.hip) on caller-supplied jobs (include/hs_kernels.h)

@@ -25,205 +25,92 @@
 //    the same rows of X, so there is nothing to share through LDS.  LDS holds the partial sums only: 16 KB per 16 columns.
 //  * D is accumulated in registers over the wave's share of K in a fixed order, read once from Cin and written once: no atomics, and a
 //    column of D depends on its own column of X and Cin only (the MFMA keeps columns apart), whatever its position in the chunk.
-// C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 reg -- not the f32 map; hsk_multi_prob_* (hs_testhooks.hip) checks it with exact
-// integer data (tests/test_ldiv_block_gpu.py).
-#include "hs_solve_multi.h"
+// C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 reg -- not the f32 map; hsk_multi_prob_* (hs_testhooks.hip) checks it, and the
+// row map cmap, with exact integer data (tests/test_ldiv_block_gpu.py).
+//
+// This file holds what is the forward product's own: MultiFwd (which k a lane loads, the real MFMA chain, the strided split of K, the row
+// map of the row-pair tiles), the solve descriptors and the kernels.  The workgroup's body, the complex MFMA chain, the LDS exchange and the
+// choice of NT are shared with kernels_solve_multi_t.hip through hs_multi_tile.h; the copy kernel multi_move_kernel serves both directions.
+#include "hs_multi_tile.h"
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-// A chunk is 4 KS = 16 columns of A (4 k-steps of the MFMA) and a wave keeps two of them in flight.  Measured against 32-column chunks
-// (two in flight: 256 VGPRs and the accumulators in AGPRs, one wave per SIMD) and 8-column ones on Poisson / Helmholtz 64^3, 32 right-hand
-// sides: 9.1 / 15.2 ms with 16 columns, 10.3 / 28.7 ms with 32, 9.5 / 14.7 ms with 8 (DESIGN.md section 4a⁗′).  With 32 the ComplexF64
-// kernels for 48 and 64 right-hand sides did not fit 512 registers at all (scratch).
-#define HSM_KS 4
-// an element of X in registers: a double, or (re, im) as a 2-vector
+// The forward side of the shared workgroup body (multi_tile_body, hs_multi_tile.h).
 template <class T>
-struct MultiX {
-  typedef double type;
-  static __device__ __forceinline__ double load(const double* p) { return gld(p); }
-};
-template <>
-struct MultiX<cplx> {
-  typedef hs_d2u type;
-  static __device__ __forceinline__ hs_d2u load(const cplx* p) { return gld2(p); }
-};
+struct MultiFwd {
+  typedef MultiProb<T> Prob;
+  // every row of the workgroup's tile exists: the Float64 loads take whole row pairs then
+  static __device__ __forceinline__ bool full(const Prob& p, int r0) { return r0 + hs_multi_rows_per_wg_c(sizeof(T) == 16) <= p.M; }
+  // wave wv takes the chunks wv, wv + 4, ... of the nch 16-column chunks of A
+  static constexpr int STEP = 4;
+  static __device__ __forceinline__ int first(int wv, int nch) { return wv; }
+  static __device__ __forceinline__ int end(int wv, int nch) { return nch; }
 
-// the chunk of A starting at column kb -> registers (a[ks][h]: k-step ks, row half / row tile h), and its rows of X (x[ct][ks])
-template <class T, int NT>
-__device__ __forceinline__ void multi_load(const MultiProb<T>& p, int kb, int r0, bool fullrows, int l15, int l4, hs_d2u (&a)[HSM_KS][2], typename MultiX<T>::type (&x)[NT][HSM_KS]) {
-  constexpr bool CX = sizeof(T) == 16;
+  // the chunk of A starting at column kb -> registers (a[2 ks + h]: k-step ks, row half / row tile h), and its rows of X (x[ct][ks])
+  template <int NT>
+  static __device__ __forceinline__ void load(const Prob& p, int kb, int r0, bool fullrows, int l15, int l4, hs_d2u (&a)[2 * HSM_KS], typename MultiX<T>::type (&x)[NT][HSM_KS]) {
+    constexpr bool CX = sizeof(T) == 16;
 #pragma unroll
-  for (int ks = 0; ks < HSM_KS; ++ks) {
-    const int col = kb + 4 * ks + l4;
-    const T* ap = p.A + (size_t)min(col, p.K - 1) * p.lda;
+    for (int ks = 0; ks < HSM_KS; ++ks) {
+      const int col = kb + 4 * ks + l4;
+      const T* ap = p.A + (size_t)min(col, p.K - 1) * p.lda;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      hs_d2u v;
-      if constexpr (CX) {
-        const int rr = r0 + 16 * h + l15;
-        v = gld2(ap + min(rr, p.M - 1));
-        if (p.trap) {
-          if (col == rr) { v.x = 1.0; v.y = 0.0; }
-          if (col > rr) { v.x = 0.0; v.y = 0.0; }
-        }
-      } else {
-        const int rr = r0 + 32 * h + 2 * l15;
-        if (fullrows) {
-          v = gld2(ap + rr);
+      for (int h = 0; h < 2; ++h) {
+        hs_d2u v;
+        if constexpr (CX) {
+          const int rr = r0 + 16 * h + l15;
+          v = gld2(ap + min(rr, p.M - 1));
+          if (p.trap) {
+            if (col == rr) { v.x = 1.0; v.y = 0.0; }
+            if (col > rr) { v.x = 0.0; v.y = 0.0; }
+          }
         } else {
-          v.x = gld(ap + min(rr, p.M - 1));
-          v.y = gld(ap + min(rr + 1, p.M - 1));
-        }
-        if (p.trap) {
-          v.x = col < rr ? v.x : (col == rr ? 1.0 : 0.0);
-          v.y = col < rr + 1 ? v.y : (col == rr + 1 ? 1.0 : 0.0);
-        }
-      }
-      if (col >= p.K) { v.x = 0.0; v.y = 0.0; }
-      a[ks][h] = v;
-    }
-    // (columns past kc of a ragged chunk hold whatever the work block held: they stay in their own columns of D and are never stored)
-    const T* xp = p.X + (long long)min(col, p.K - 1) * p.xrs + l15;
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) {
-      typename MultiX<T>::type v = MultiX<T>::load(xp + ct * 16);
-      if (col >= p.K) v = (typename MultiX<T>::type)(0.0);
-      x[ct][ks] = p.Cin ? -v : v;
-    }
-  }
-}
-
-// acc += A_chunk * X_chunk.  Float64: acc[q] is row tile q = 2 h + parity.  ComplexF64: acc[q] re, acc[2 + q] im of row tile q.
-template <class T, int NT>
-__device__ __forceinline__ void multi_mfma(const hs_d2u (&a)[HSM_KS][2], const typename MultiX<T>::type (&x)[NT][HSM_KS], v4d (&acc)[4][NT]) {
-  if constexpr (sizeof(T) == 16) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) {
-#pragma unroll
-        for (int ks = 0; ks < HSM_KS; ++ks) {
-          acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks][q].x, x[ct][ks].x, acc[q][ct], 0, 0, 0);
-          acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks][q].y, -x[ct][ks].y, acc[q][ct], 0, 0, 0);
-        }
-#pragma unroll
-        for (int ks = 0; ks < HSM_KS; ++ks) {
-          acc[2 + q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks][q].x, x[ct][ks].y, acc[2 + q][ct], 0, 0, 0);
-          acc[2 + q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks][q].y, x[ct][ks].x, acc[2 + q][ct], 0, 0, 0);
-        }
-      }
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-        for (int ks = 0; ks < HSM_KS; ++ks)
-          acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64((q & 1) ? a[ks][q >> 1].y : a[ks][q >> 1].x, x[ct][ks], acc[q][ct], 0, 0, 0);
-  }
-}
-
-// row of D held in register g of row tile q
-template <class T>
-__device__ __forceinline__ int multi_drow(int r0, int q, int g, int l4) {
-  if constexpr (sizeof(T) == 16) return r0 + 16 * q + l4 + 4 * g;
-  return r0 + 32 * (q >> 1) + 2 * (l4 + 4 * g) + (q & 1);
-}
-
-template <int NT>
-__device__ __forceinline__ void multi_red_put(double* slot, int lane, const v4d (&acc)[4][NT]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) slot[((q * NT + ct) * 4 + g) * 64 + lane] = acc[q][ct][g];
-}
-template <int NT>
-__device__ __forceinline__ void multi_red_add(const double* slot, int lane, v4d (&acc)[4][NT]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[q][ct][g] += slot[((q * NT + ct) * 4 + g) * 64 + lane];
-}
-
-template <class T, int NT>
-__device__ __forceinline__ void multi_body(const MultiProb<T>& p, int kc, double* red) {
-  constexpr bool CX = sizeof(T) == 16;
-  constexpr int RW = hs_multi_rows_per_wg_c(CX), NQ = CX ? 2 : 4;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int l15 = lane & 15, l4 = lane >> 4;
-  const int r0 = blockIdx.x * RW;
-  const bool fullrows = r0 + RW <= p.M;
-  constexpr int KCH = 4 * HSM_KS;
-  const int nch = (p.K + KCH - 1) / KCH;
-  hs_d2u a0[HSM_KS][2], a1[HSM_KS][2];
-  typename MultiX<T>::type x0[NT][HSM_KS], x1[NT][HSM_KS];
-  if (wv < nch) multi_load<T, NT>(p, wv * KCH, r0, fullrows, l15, l4, a0, x0);
-  v4d acc[4][NT];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) acc[q][ct] = v4d{0.0, 0.0, 0.0, 0.0};
-  if (wv == 0 && p.Cin) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int row = multi_drow<T>(r0, q, g, l4);
-        if (row >= p.M) continue;
-        const T* src = p.Cin + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
-          const int col = ct * 16 + l15;
-          if (col >= kc) continue;
-          const T v = gld(src + col);
-          if constexpr (CX) {
-            acc[q][ct][g] = v.re;
-            acc[2 + q][ct][g] = v.im;
+          const int rr = r0 + 32 * h + 2 * l15;
+          if (fullrows) {
+            v = gld2(ap + rr);
           } else {
-            acc[q][ct][g] = v;
+            v.x = gld(ap + min(rr, p.M - 1));
+            v.y = gld(ap + min(rr + 1, p.M - 1));
+          }
+          if (p.trap) {
+            v.x = col < rr ? v.x : (col == rr ? 1.0 : 0.0);
+            v.y = col < rr + 1 ? v.y : (col == rr + 1 ? 1.0 : 0.0);
           }
         }
+        if (col >= p.K) { v.x = 0.0; v.y = 0.0; }
+        a[2 * ks + h] = v;
       }
-  }
-  for (int ch = wv; ch < nch; ch += 8) {
-    if (ch + 4 < nch) multi_load<T, NT>(p, (ch + 4) * KCH, r0, fullrows, l15, l4, a1, x1);
-    multi_mfma<T, NT>(a0, x0, acc);
-    if (ch + 4 < nch) {
-      if (ch + 8 < nch) multi_load<T, NT>(p, (ch + 8) * KCH, r0, fullrows, l15, l4, a0, x0);
-      multi_mfma<T, NT>(a1, x1, acc);
-    }
-  }
-  // (w0 + w2) + (w1 + w3)
-  double* slot = red + (size_t)(wv & 1) * (16 * NT * 64);
-  if (wv >= 2) multi_red_put<NT>(slot, lane, acc);
-  __syncthreads();
-  if (wv < 2) multi_red_add<NT>(slot, lane, acc);
-  __syncthreads();
-  if (wv == 1) multi_red_put<NT>(red, lane, acc);
-  __syncthreads();
-  if (wv != 0) return;
-  multi_red_add<NT>(red, lane, acc);
-#pragma unroll
-  for (int q = 0; q < NQ; ++q)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int row = multi_drow<T>(r0, q, g, l4);
-      if (row >= p.M) continue;
-      T* dst = p.C + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
+      // (columns past kc of a ragged chunk hold whatever the work block held: they stay in their own columns of D and are never stored)
+      const T* xp = p.X + (long long)min(col, p.K - 1) * p.xrs + l15;
 #pragma unroll
       for (int ct = 0; ct < NT; ++ct) {
-        const int col = ct * 16 + l15;
-        if (col >= kc) continue;
-        if constexpr (CX)
-          gst(dst + col, cplx{acc[q][ct][g], acc[2 + q][ct][g]});
-        else
-          gst(dst + col, acc[q][ct][g]);
+        typename MultiX<T>::type v = MultiX<T>::load(xp + ct * 16);
+        if (col >= p.K) v = (typename MultiX<T>::type)(0.0);
+        x[ct][ks] = p.Cin ? -v : v;
       }
     }
-}
+  }
+
+  // acc += A_chunk * X_chunk.  Float64: acc[q] is row tile q = 2 h + parity.  ComplexF64: acc[q] re, acc[2 + q] im of row tile q.
+  template <int NT>
+  static __device__ __forceinline__ void mfma(const hs_d2u (&a)[2 * HSM_KS], const typename MultiX<T>::type (&x)[NT][HSM_KS], v4d (&acc)[4][NT]) {
+    if constexpr (sizeof(T) == 16) {
+      multi_mfma_cplx<NT>(a, x, acc);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct)
+#pragma unroll
+          for (int ks = 0; ks < HSM_KS; ++ks)
+            acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64((q & 1) ? a[2 * ks + (q >> 1)].y : a[2 * ks + (q >> 1)].x, x[ct][ks], acc[q][ct], 0, 0, 0);
+    }
+  }
+
+  // row of D held in register g of row tile q
+  static __device__ __forceinline__ int row(int r0, int q, int g, int l4) {
+    if constexpr (sizeof(T) == 16) return r0 + 16 * q + l4 + 4 * g;
+    return r0 + 32 * (q >> 1) + 2 * (l4 + 4 * g) + (q & 1);
+  }
+};
 
 // the product of a sweep step for one front, from its solve descriptor (false: the front has no such step)
 template <class T>
@@ -298,16 +185,17 @@ __global__ __launch_bounds__(256) void multi_level_kernel(const SolveNode<T>* __
   MultiProb<T> p;
   if (!multi_resolve<T>(nd, a.aux[blockIdx.y], mode, blk, a, p)) return;
   if ((int)blockIdx.x * hs_multi_rows_per_wg_c(sizeof(T) == 16) >= p.M) return;
-  multi_body<T, NT>(p, a.kc, red);
+  multi_tile_body<MultiFwd<T>, T, NT>(p, a.kc, red);
 }
 template <class T, int NT>
 __global__ __launch_bounds__(256) void multi_prob_kernel(MultiProb<T> p, int kc) {
   __shared__ double red[2 * 16 * NT * 64];
-  multi_body<T, NT>(p, kc, red);
+  multi_tile_body<MultiFwd<T>, T, NT>(p, kc, red);
 }
 
-// the caller's column-major block <-> the row-major work blocks (what: see launch_multi_move)
-template <class T>
+// the caller's column-major block <-> the row-major work blocks of either direction (what, perm_what: hs_solve_multi.h).  perm_what is a
+// template argument: as a kernel argument it cost nothing measurable, but the code of both directions' kernel was no longer the parent's
+template <class T, int PERM_WHAT>
 __global__ __launch_bounds__(256) void multi_move_kernel(const SolveNode<T>* __restrict__ nodes, int what, MultiArgs a) {
   const SolveNode<T> nd = nodes[blockIdx.y];
   const MultiAux ax = a.aux[blockIdx.y];
@@ -315,7 +203,7 @@ __global__ __launch_bounds__(256) void multi_move_kernel(const SolveNode<T>* __r
   if (nd.ni <= 0) return;
   const bool bnd = what & 1;
   if (i >= (bnd ? ax.nb : nd.ni)) return;
-  T* b = (T*)a.B + gld(nd.fidx + (bnd ? nd.ni + i : (what == 0 ? gld(nd.rperm + i) : i)));
+  T* b = (T*)a.B + gld(nd.fidx + (bnd ? nd.ni + i : (what == PERM_WHAT ? gld(nd.rperm + i) : i)));
   T* w = bnd ? (T*)a.XB + (ax.boff + i) * a.kcw : (what == 0 ? (T*)a.W1 + (nd.woff - a.wbase + i) * a.kcw : (T*)a.W2 + (nd.woff + i) * a.kcw);
   if (what < 2)
     for (int c = 0; c < a.kc; ++c) gst(w + c, gld(b + (long long)c * a.ldb));
@@ -330,34 +218,32 @@ void launch_multi_level(const SolveNode<T>* sn, int nfronts, int mode, int blk, 
   if (nfronts <= 0 || maxM <= 0 || a.kc <= 0) return;
   const int tr = hs_multi_rows_per_wg(sizeof(T) == 16);
   const dim3 grid((maxM + tr - 1) / tr, nfronts);
-  switch ((a.kc + 15) / 16) {
-    case 1: hipLaunchKernelGGL((multi_level_kernel<T, 1>), grid, dim3(256), 0, s, sn, mode, blk, a); break;
-    case 2: hipLaunchKernelGGL((multi_level_kernel<T, 2>), grid, dim3(256), 0, s, sn, mode, blk, a); break;
-    case 3: hipLaunchKernelGGL((multi_level_kernel<T, 3>), grid, dim3(256), 0, s, sn, mode, blk, a); break;
-    default: hipLaunchKernelGGL((multi_level_kernel<T, 4>), grid, dim3(256), 0, s, sn, mode, blk, a); break;
-  }
+  hs_with_nt((a.kc + 15) / 16, [&](auto nt) {
+    hipLaunchKernelGGL((multi_level_kernel<T, decltype(nt)::value>), grid, dim3(256), 0, s, sn, mode, blk, a);
+  });
 }
 template <class T>
 void launch_multi_prob(const MultiProb<T>& p, int kc, hipStream_t s) {
   if (p.M <= 0 || kc <= 0) return;
   const int tr = hs_multi_rows_per_wg(sizeof(T) == 16);
   const dim3 grid((p.M + tr - 1) / tr);
-  switch ((kc + 15) / 16) {
-    case 1: hipLaunchKernelGGL((multi_prob_kernel<T, 1>), grid, dim3(256), 0, s, p, kc); break;
-    case 2: hipLaunchKernelGGL((multi_prob_kernel<T, 2>), grid, dim3(256), 0, s, p, kc); break;
-    case 3: hipLaunchKernelGGL((multi_prob_kernel<T, 3>), grid, dim3(256), 0, s, p, kc); break;
-    default: hipLaunchKernelGGL((multi_prob_kernel<T, 4>), grid, dim3(256), 0, s, p, kc); break;
-  }
+  hs_with_nt((kc + 15) / 16, [&](auto nt) {
+    hipLaunchKernelGGL((multi_prob_kernel<T, decltype(nt)::value>), grid, dim3(256), 0, s, p, kc);
+  });
 }
 template <class T>
-void launch_multi_move(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s) {
+void launch_multi_move(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm_what) {
   if (nfronts <= 0 || maxrows <= 0 || a.kc <= 0) return;
-  hipLaunchKernelGGL(multi_move_kernel<T>, dim3((maxrows + 255) / 256, nfronts), dim3(256), 0, s, sn, what, a);
+  const dim3 grid((maxrows + 255) / 256, nfronts);
+  if (perm_what == 0)
+    hipLaunchKernelGGL((multi_move_kernel<T, 0>), grid, dim3(256), 0, s, sn, what, a);
+  else
+    hipLaunchKernelGGL((multi_move_kernel<T, 2>), grid, dim3(256), 0, s, sn, what, a);
 }
 
 #define INST(T)                                                                                                  \
   template void launch_multi_level<T>(const SolveNode<T>*, int, int, int, int, const MultiArgs&, hipStream_t);  \
   template void launch_multi_prob<T>(const MultiProb<T>&, int, hipStream_t);                                    \
-  template void launch_multi_move<T>(const SolveNode<T>*, int, int, int, const MultiArgs&, hipStream_t);
+  template void launch_multi_move<T>(const SolveNode<T>*, int, int, int, const MultiArgs&, hipStream_t, int);
 INST(double)
 INST(cplx)

@@ -5,8 +5,12 @@
 // A a stored factor panel read along its columns (a row panel of U11 / L11, Uib, Lbi, a 256 x 256 inverse diagonal block, a factor of a
 // low-rank Gauss transform), X, Cin and D rows of the row-major work blocks of the driver, kc <= 64 right-hand sides.
 //
-// A translation unit of its own: multi_level_kernel / multi_prob_kernel (kernels_solve_multi.hip) sit at their register limit and keep
-// their allocation only as long as nothing else is compiled into their functions (DESIGN.md section 4a⁗″).
+// A translation unit of its own, with its own kernels: multi_level_kernel / multi_prob_kernel (kernels_solve_multi.hip) sit at their
+// register limit and keep their allocation only as long as nothing else is compiled into their functions (DESIGN.md section 4a⁗″).  What
+// the two products have in common -- the workgroup's body (accumulators, chunks in flight, LDS exchange, the read and the store of D), the
+// complex MFMA chain, MultiX, the choice of NT -- is source shared through hs_multi_tile.h and instantiated here over MultiTr, this
+// file's own operand loads, real MFMA chain, contiguous split of K and row map; the column-major <-> row-major copies of both directions
+// are launch_multi_move of kernels_solve_multi.hip.
 //
 // The forward kernel reads A[M x K] with the OUTPUT rows contiguous; here the REDUCTION index k is the contiguous one.  The A operand of
 // v_mfma_f64_16x16x4_f64 wants lane (m = lane & 15, group = lane >> 4) to hold op(A)^T[m, k] = A[k, m] for one k of the group's four per
@@ -24,217 +28,106 @@
 //    form of a low-rank C: C^T x = trap(Lp)^T (P x)).
 //  * No atomics, one summation order per output element that depends on K alone, and a column of D depends on its own column of X and Cin
 //    only, wherever it sits in the chunk.
-// C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 reg; hsk_multi_prob_t_* (hs_testhooks.hip) checks the maps with exact integer
-// data (tests/test_ldiv_block_t_gpu.py).
-#include "hs_solve_multi.h"
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-#define HSMT_KS 4  // k-steps of a chunk: 16 consecutive k
-
-template <class T>
-struct MultiTX {
-  typedef double type;
-  static __device__ __forceinline__ double load(const double* p) { return gld(p); }
-};
-template <>
-struct MultiTX<cplx> {
-  typedef hs_d2u type;
-  static __device__ __forceinline__ hs_d2u load(const cplx* p) { return gld2(p); }
-};
+// C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 reg; hsk_multi_prob_t_* (hs_testhooks.hip) checks the maps, xmap included,
+// with exact integer data (tests/test_ldiv_block_t_gpu.py).
+#include "hs_multi_tile.h"
 
 // value of the unit lower trapezoid at (k, m) given the stored value
 __device__ __forceinline__ double multi_t_trap(double v, int k, int m, double diag) { return k > m ? v : (k == m ? diag : 0.0); }
 
-// the 16 rows kb .. kb + 15 of the workgroup's columns of A -> registers, and the matching rows of X (x[ct][ks]).
-// Float64: a[2 i + .x/.y ... ] = a[i * 4 + q] holds k-steps 2 i (.x) and 2 i + 1 (.y) of column tile q.  ComplexF64: a[ks * 2 + q] = (re, im).
-template <class T, int NT>
-__device__ __forceinline__ void multi_t_load(const MultiProbT<T>& p, int kb, int m0, int l15, int l4, hs_d2u (&a)[8], typename MultiTX<T>::type (&x)[NT][HSMT_KS]) {
-  constexpr bool CX = sizeof(T) == 16;
-  if constexpr (CX) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int m = m0 + 16 * q + l15;
-      const T* ap = p.A + (size_t)min(m, p.M - 1) * p.lda;
-#pragma unroll
-      for (int ks = 0; ks < HSMT_KS; ++ks) {
-        const int k = kb + 4 * ks + l4;
-        hs_d2u v = gld2(ap + min(k, p.K - 1));
-        if (p.conj) v.y = -v.y;
-        if (p.trap) {
-          v.x = multi_t_trap(v.x, k, m, 1.0);
-          v.y = multi_t_trap(v.y, k, m, 0.0);
-        }
-        if (k >= p.K) { v.x = 0.0; v.y = 0.0; }
-        a[ks * 2 + q] = v;
-      }
-    }
-  } else {
-    const bool fullk = kb + 4 * HSMT_KS <= p.K;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int m = m0 + 16 * q + l15;
-      const T* ap = p.A + (size_t)min(m, p.M - 1) * p.lda;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int k = kb + 8 * i + 2 * l4;
-        hs_d2u v;
-        if (fullk) {
-          v = gld2(ap + k);
-        } else {
-          v.x = gld(ap + min(k, p.K - 1));
-          v.y = gld(ap + min(k + 1, p.K - 1));
-        }
-        if (p.trap) {
-          v.x = multi_t_trap(v.x, k, m, 1.0);
-          v.y = multi_t_trap(v.y, k + 1, m, 1.0);
-        }
-        if (k >= p.K) v.x = 0.0;
-        if (k + 1 >= p.K) v.y = 0.0;
-        a[i * 4 + q] = v;
-      }
-    }
-  }
-  // (columns past kc of a ragged chunk hold whatever the work block held: they stay in their own columns of D and are never stored)
-#pragma unroll
-  for (int ks = 0; ks < HSMT_KS; ++ks) {
-    const int k = CX ? kb + 4 * ks + l4 : kb + 8 * (ks >> 1) + 2 * l4 + (ks & 1);
-    const int kk = min(k, p.K - 1);
-    const T* xp = p.X + (long long)(p.xmap ? gld(p.xmap + kk) : kk) * p.xrs + l15;
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) {
-      typename MultiTX<T>::type v = MultiTX<T>::load(xp + ct * 16);
-      if (k >= p.K) v = (typename MultiTX<T>::type)(0.0);
-      x[ct][ks] = p.Cin ? -v : v;
-    }
-  }
-}
+// The transposed side of the shared workgroup body (multi_tile_body, hs_multi_tile.h).
+template <class T>
+struct MultiTr {
+  typedef MultiProbT<T> Prob;
+  static __device__ __forceinline__ bool full(const Prob& p, int m0) { return false; }  // (the loads below decide per chunk: fullk)
+  // wave wv takes the contiguous quarter [first, end) of the nch 16-row chunks of A
+  static constexpr int STEP = 1;
+  static __device__ __forceinline__ int first(int wv, int nch) { return wv * ((nch + 3) / 4); }
+  static __device__ __forceinline__ int end(int wv, int nch) { return min(nch, first(wv, nch) + (nch + 3) / 4); }
 
-// acc += op(A_chunk)^T X_chunk.  Float64: acc[q] is column tile q.  ComplexF64: acc[q] re, acc[2 + q] im of column tile q.
-template <class T, int NT>
-__device__ __forceinline__ void multi_t_mfma(const hs_d2u (&a)[8], const typename MultiTX<T>::type (&x)[NT][HSMT_KS], v4d (&acc)[4][NT]) {
-  if constexpr (sizeof(T) == 16) {
+  // the 16 rows kb .. kb + 15 of the workgroup's columns of A -> registers, and the matching rows of X (x[ct][ks]).
+  // Float64: a[i * 4 + q] holds k-steps 2 i (.x) and 2 i + 1 (.y) of column tile q.  ComplexF64: a[ks * 2 + q] = (re, im).
+  template <int NT>
+  static __device__ __forceinline__ void load(const Prob& p, int kb, int m0, bool, int l15, int l4, hs_d2u (&a)[8], typename MultiX<T>::type (&x)[NT][HSM_KS]) {
+    constexpr bool CX = sizeof(T) == 16;
+    if constexpr (CX) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q)
+      for (int q = 0; q < 2; ++q) {
+        const int m = m0 + 16 * q + l15;
+        const T* ap = p.A + (size_t)min(m, p.M - 1) * p.lda;
 #pragma unroll
-      for (int ct = 0; ct < NT; ++ct) {
-#pragma unroll
-        for (int ks = 0; ks < HSMT_KS; ++ks) {
-          acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks * 2 + q].x, x[ct][ks].x, acc[q][ct], 0, 0, 0);
-          acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks * 2 + q].y, -x[ct][ks].y, acc[q][ct], 0, 0, 0);
-        }
-#pragma unroll
-        for (int ks = 0; ks < HSMT_KS; ++ks) {
-          acc[2 + q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks * 2 + q].x, x[ct][ks].y, acc[2 + q][ct], 0, 0, 0);
-          acc[2 + q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks * 2 + q].y, x[ct][ks].x, acc[2 + q][ct], 0, 0, 0);
-        }
-      }
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-        for (int ks = 0; ks < HSMT_KS; ++ks)
-          acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64((ks & 1) ? a[(ks >> 1) * 4 + q].y : a[(ks >> 1) * 4 + q].x, x[ct][ks], acc[q][ct], 0, 0, 0);
-  }
-}
-
-template <int NT>
-__device__ __forceinline__ void multi_t_red_put(double* slot, int lane, const v4d (&acc)[4][NT]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) slot[((q * NT + ct) * 4 + g) * 64 + lane] = acc[q][ct][g];
-}
-template <int NT>
-__device__ __forceinline__ void multi_t_red_add(const double* slot, int lane, v4d (&acc)[4][NT]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[q][ct][g] += slot[((q * NT + ct) * 4 + g) * 64 + lane];
-}
-
-template <class T, int NT>
-__device__ __forceinline__ void multi_t_body(const MultiProbT<T>& p, int kc, double* red) {
-  constexpr bool CX = sizeof(T) == 16;
-  constexpr int RW = hs_multi_rows_per_wg_c(CX), NQ = CX ? 2 : 4;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int l15 = lane & 15, l4 = lane >> 4;
-  const int m0 = blockIdx.x * RW;
-  constexpr int KCH = 4 * HSMT_KS;
-  const int nch = (p.K + KCH - 1) / KCH;
-  const int per = (nch + 3) / 4;  // wave wv takes the contiguous chunks [cb, ce)
-  const int cb = wv * per, ce = min(nch, cb + per);
-  hs_d2u a0[8], a1[8];
-  typename MultiTX<T>::type x0[NT][HSMT_KS], x1[NT][HSMT_KS];
-  if (cb < ce) multi_t_load<T, NT>(p, cb * KCH, m0, l15, l4, a0, x0);
-  v4d acc[4][NT];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) acc[q][ct] = v4d{0.0, 0.0, 0.0, 0.0};
-  if (wv == 0 && p.Cin) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int row = m0 + 16 * q + l4 + 4 * g;
-        if (row >= p.M) continue;
-        const T* src = p.Cin + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
-          const int col = ct * 16 + l15;
-          if (col >= kc) continue;
-          const T v = gld(src + col);
-          if constexpr (CX) {
-            acc[q][ct][g] = v.re;
-            acc[2 + q][ct][g] = v.im;
-          } else {
-            acc[q][ct][g] = v;
+        for (int ks = 0; ks < HSM_KS; ++ks) {
+          const int k = kb + 4 * ks + l4;
+          hs_d2u v = gld2(ap + min(k, p.K - 1));
+          if (p.conj) v.y = -v.y;
+          if (p.trap) {
+            v.x = multi_t_trap(v.x, k, m, 1.0);
+            v.y = multi_t_trap(v.y, k, m, 0.0);
           }
+          if (k >= p.K) { v.x = 0.0; v.y = 0.0; }
+          a[ks * 2 + q] = v;
         }
       }
-  }
-  for (int ch = cb; ch < ce; ch += 2) {
-    if (ch + 1 < ce) multi_t_load<T, NT>(p, (ch + 1) * KCH, m0, l15, l4, a1, x1);
-    multi_t_mfma<T, NT>(a0, x0, acc);
-    if (ch + 1 < ce) {
-      if (ch + 2 < ce) multi_t_load<T, NT>(p, (ch + 2) * KCH, m0, l15, l4, a0, x0);
-      multi_t_mfma<T, NT>(a1, x1, acc);
-    }
-  }
-  // (w0 + w2) + (w1 + w3)
-  double* slot = red + (size_t)(wv & 1) * (16 * NT * 64);
-  if (wv >= 2) multi_t_red_put<NT>(slot, lane, acc);
-  __syncthreads();
-  if (wv < 2) multi_t_red_add<NT>(slot, lane, acc);
-  __syncthreads();
-  if (wv == 1) multi_t_red_put<NT>(red, lane, acc);
-  __syncthreads();
-  if (wv != 0) return;
-  multi_t_red_add<NT>(red, lane, acc);
+    } else {
+      const bool fullk = kb + 4 * HSM_KS <= p.K;
 #pragma unroll
-  for (int q = 0; q < NQ; ++q)
+      for (int q = 0; q < 4; ++q) {
+        const int m = m0 + 16 * q + l15;
+        const T* ap = p.A + (size_t)min(m, p.M - 1) * p.lda;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int row = m0 + 16 * q + l4 + 4 * g;
-      if (row >= p.M) continue;
-      T* dst = p.C + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) {
-        const int col = ct * 16 + l15;
-        if (col >= kc) continue;
-        if constexpr (CX)
-          gst(dst + col, cplx{acc[q][ct][g], acc[2 + q][ct][g]});
-        else
-          gst(dst + col, acc[q][ct][g]);
+        for (int i = 0; i < 2; ++i) {
+          const int k = kb + 8 * i + 2 * l4;
+          hs_d2u v;
+          if (fullk) {
+            v = gld2(ap + k);
+          } else {
+            v.x = gld(ap + min(k, p.K - 1));
+            v.y = gld(ap + min(k + 1, p.K - 1));
+          }
+          if (p.trap) {
+            v.x = multi_t_trap(v.x, k, m, 1.0);
+            v.y = multi_t_trap(v.y, k + 1, m, 1.0);
+          }
+          if (k >= p.K) v.x = 0.0;
+          if (k + 1 >= p.K) v.y = 0.0;
+          a[i * 4 + q] = v;
+        }
       }
     }
-}
+    // (columns past kc of a ragged chunk hold whatever the work block held: they stay in their own columns of D and are never stored)
+#pragma unroll
+    for (int ks = 0; ks < HSM_KS; ++ks) {
+      const int k = CX ? kb + 4 * ks + l4 : kb + 8 * (ks >> 1) + 2 * l4 + (ks & 1);
+      const int kk = min(k, p.K - 1);
+      const T* xp = p.X + (long long)(p.xmap ? gld(p.xmap + kk) : kk) * p.xrs + l15;
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) {
+        typename MultiX<T>::type v = MultiX<T>::load(xp + ct * 16);
+        if (k >= p.K) v = (typename MultiX<T>::type)(0.0);
+        x[ct][ks] = p.Cin ? -v : v;
+      }
+    }
+  }
+
+  // acc += op(A_chunk)^T X_chunk.  Float64: acc[q] is column tile q.  ComplexF64: acc[q] re, acc[2 + q] im of column tile q.
+  template <int NT>
+  static __device__ __forceinline__ void mfma(const hs_d2u (&a)[8], const typename MultiX<T>::type (&x)[NT][HSM_KS], v4d (&acc)[4][NT]) {
+    if constexpr (sizeof(T) == 16) {
+      multi_mfma_cplx<NT>(a, x, acc);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct)
+#pragma unroll
+          for (int ks = 0; ks < HSM_KS; ++ks)
+            acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64((ks & 1) ? a[(ks >> 1) * 4 + q].y : a[(ks >> 1) * 4 + q].x, x[ct][ks], acc[q][ct], 0, 0, 0);
+    }
+  }
+
+  // row of D (column of A) held in register g of column tile q
+  static __device__ __forceinline__ int row(int m0, int q, int g, int l4) { return m0 + 16 * q + l4 + 4 * g; }
+};
 
 // the product of a step of the transposed sweeps for one front, from its solve descriptor (false: the front has no such step)
 template <class T>
@@ -328,29 +221,12 @@ __global__ __launch_bounds__(256) void multi_t_level_kernel(const SolveNode<T>* 
   MultiProbT<T> p;
   if (!multi_t_resolve<T>(nd, a.aux[blockIdx.y], mode, blk, conj, a, p)) return;
   if ((int)blockIdx.x * hs_multi_rows_per_wg_c(sizeof(T) == 16) >= p.M) return;
-  multi_t_body<T, NT>(p, a.kc, red);
+  multi_tile_body<MultiTr<T>, T, NT>(p, a.kc, red);
 }
 template <class T, int NT>
 __global__ __launch_bounds__(256) void multi_t_prob_kernel(MultiProbT<T> p, int kc) {
   __shared__ double red[2 * 16 * NT * 64];
-  multi_t_body<T, NT>(p, kc, red);
-}
-
-// the caller's column-major block <-> the row-major work blocks (what: see launch_multi_move_t)
-template <class T>
-__global__ __launch_bounds__(256) void multi_t_move_kernel(const SolveNode<T>* __restrict__ nodes, int what, MultiArgs a) {
-  const SolveNode<T> nd = nodes[blockIdx.y];
-  const MultiAux ax = a.aux[blockIdx.y];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (nd.ni <= 0) return;
-  const bool bnd = what & 1;
-  if (i >= (bnd ? ax.nb : nd.ni)) return;
-  T* b = (T*)a.B + gld(nd.fidx + (bnd ? nd.ni + i : (what == 2 ? gld(nd.rperm + i) : i)));
-  T* w = bnd ? (T*)a.XB + (ax.boff + i) * a.kcw : (what == 0 ? (T*)a.W1 + (nd.woff - a.wbase + i) * a.kcw : (T*)a.W2 + (nd.woff + i) * a.kcw);
-  if (what < 2)
-    for (int c = 0; c < a.kc; ++c) gst(w + c, gld(b + (long long)c * a.ldb));
-  else
-    for (int c = 0; c < a.kc; ++c) gst(b + (long long)c * a.ldb, gld(w + c));
+  multi_tile_body<MultiTr<T>, T, NT>(p, kc, red);
 }
 
 template <class T>
@@ -358,34 +234,21 @@ void launch_multi_level_t(const SolveNode<T>* sn, int nfronts, int mode, int blk
   if (nfronts <= 0 || maxM <= 0 || a.kc <= 0) return;
   const int tr = hs_multi_rows_per_wg_c(sizeof(T) == 16);
   const dim3 grid((maxM + tr - 1) / tr, nfronts);
-  switch ((a.kc + 15) / 16) {
-    case 1: hipLaunchKernelGGL((multi_t_level_kernel<T, 1>), grid, dim3(256), 0, s, sn, mode, blk, conj, a); break;
-    case 2: hipLaunchKernelGGL((multi_t_level_kernel<T, 2>), grid, dim3(256), 0, s, sn, mode, blk, conj, a); break;
-    case 3: hipLaunchKernelGGL((multi_t_level_kernel<T, 3>), grid, dim3(256), 0, s, sn, mode, blk, conj, a); break;
-    default: hipLaunchKernelGGL((multi_t_level_kernel<T, 4>), grid, dim3(256), 0, s, sn, mode, blk, conj, a); break;
-  }
+  hs_with_nt((a.kc + 15) / 16, [&](auto nt) {
+    hipLaunchKernelGGL((multi_t_level_kernel<T, decltype(nt)::value>), grid, dim3(256), 0, s, sn, mode, blk, conj, a);
+  });
 }
 template <class T>
 void launch_multi_prob_t(const MultiProbT<T>& p, int kc, hipStream_t s) {
   if (p.M <= 0 || kc <= 0) return;
   const int tr = hs_multi_rows_per_wg_c(sizeof(T) == 16);
   const dim3 grid((p.M + tr - 1) / tr);
-  switch ((kc + 15) / 16) {
-    case 1: hipLaunchKernelGGL((multi_t_prob_kernel<T, 1>), grid, dim3(256), 0, s, p, kc); break;
-    case 2: hipLaunchKernelGGL((multi_t_prob_kernel<T, 2>), grid, dim3(256), 0, s, p, kc); break;
-    case 3: hipLaunchKernelGGL((multi_t_prob_kernel<T, 3>), grid, dim3(256), 0, s, p, kc); break;
-    default: hipLaunchKernelGGL((multi_t_prob_kernel<T, 4>), grid, dim3(256), 0, s, p, kc); break;
-  }
+  hs_with_nt((kc + 15) / 16, [&](auto nt) {
+    hipLaunchKernelGGL((multi_t_prob_kernel<T, decltype(nt)::value>), grid, dim3(256), 0, s, p, kc);
+  });
 }
-template <class T>
-void launch_multi_move_t(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s) {
-  if (nfronts <= 0 || maxrows <= 0 || a.kc <= 0) return;
-  hipLaunchKernelGGL(multi_t_move_kernel<T>, dim3((maxrows + 255) / 256, nfronts), dim3(256), 0, s, sn, what, a);
-}
-
 #define INST(T)                                                                                                         \
   template void launch_multi_level_t<T>(const SolveNode<T>*, int, int, int, int, int, const MultiArgs&, hipStream_t);  \
-  template void launch_multi_prob_t<T>(const MultiProbT<T>&, int, hipStream_t);                                        \
-  template void launch_multi_move_t<T>(const SolveNode<T>*, int, int, int, const MultiArgs&, hipStream_t);
+  template void launch_multi_prob_t<T>(const MultiProbT<T>&, int, hipStream_t);
 INST(double)
 INST(cplx)

@@ -23,9 +23,8 @@
 //  * Rows past M, columns past N and k past K are clamped for the address and zeroed in the operand, so nothing outside the blocks is read.
 // Plain launches only: workgroups never wait for each other.  hsk_ulv_t_group_* (hs_testhooks.hip) checks the maps with exact integer
 // data (tests/test_ulv_t_gpu.py).
+#include "hs_multi_tile.h"  // v4d, hs_with_nt
 #include "hs_ulv_t.h"
-
-typedef double v4d __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ bool ulv_t_keep(int tri, int k, int m) { return tri == HS_ULVT_FULL || (tri == HS_ULVT_LOWER ? k >= m : k <= m); }
 
@@ -158,12 +157,9 @@ void launch_ulv_t(const UlvTJob<T>* djobs, int njobs, int maxM, int maxN, hipStr
   if (njobs <= 0 || maxM <= 0 || maxN <= 0) return;
   const int nt = std::min(4, (maxN + 15) / 16);
   const dim3 grid((maxM + 63) / 64, (maxN + 16 * nt - 1) / (16 * nt), njobs);
-  switch (nt) {
-    case 1: hipLaunchKernelGGL((ulv_t_kernel<T, 1>), grid, dim3(256), 0, s, djobs); break;
-    case 2: hipLaunchKernelGGL((ulv_t_kernel<T, 2>), grid, dim3(256), 0, s, djobs); break;
-    case 3: hipLaunchKernelGGL((ulv_t_kernel<T, 3>), grid, dim3(256), 0, s, djobs); break;
-    default: hipLaunchKernelGGL((ulv_t_kernel<T, 4>), grid, dim3(256), 0, s, djobs); break;
-  }
+  hs_with_nt(nt, [&](auto c) {
+    hipLaunchKernelGGL((ulv_t_kernel<T, decltype(c)::value>), grid, dim3(256), 0, s, djobs);
+  });
 }
 
 template <class T>

@@ -57,19 +57,23 @@ int hsk_lowrank_z(int64_t rows, int64_t cols, const double* X, double atol, doub
 
 /* The tall-skinny panel product of the block solves (kernels_solve_multi.hip) on host data: C = A X (minus == 0) or C = C - A X, A M x K
  * (column-major, lda), X K x kc and C M x kc column-major with kc in 1..64 (they reach the kernel row-major with a pitch of 64, as the work
- * blocks of hs_ldiv_block_* do).  trap != 0: A stands for its unit lower trapezoid. */
+ * blocks of hs_ldiv_block_* do).  trap != 0: A stands for its unit lower trapezoid.  map (NULL: none): M entries in 0..M-1, row i of the
+ * product belongs to row map[i] of C (the kernel's cmap: C[map[i], :] = C[map[i], :] - (A X)[i, :]); an entry outside that range gives
+ * HS_ERR_ARGUMENT. */
 int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
-                     int minus, int trap);
+                     int minus, int trap, const int32_t* map);
 int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
-                     int minus, int trap);
+                     int minus, int trap, const int32_t* map);
 
 /* The panel product of the transposed block solves (kernels_solve_multi_t.hip) on host data: C = op(A)^T X (minus == 0) or C = C - op(A)^T X,
  * A K x M (column-major, lda >= K), X K x kc and C M x kc column-major with kc in 1..64 (row-major with a pitch of 64 on the device).
- * trap != 0: A stands for its unit lower trapezoid (K x M); conj != 0: op = conj (ComplexF64; ignored for Float64). */
+ * trap != 0: A stands for its unit lower trapezoid (K x M); conj != 0: op = conj (ComplexF64; ignored for Float64).  map (NULL: none): K
+ * entries in 0..K-1, row k of A meets row map[k] of X (the kernel's xmap: C = C - op(A)^T X[map, :]); an entry outside that range gives
+ * HS_ERR_ARGUMENT. */
 int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
-                       int minus, int trap, int conj);
+                       int minus, int trap, int conj, const int32_t* map);
 int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
-                       int minus, int trap, int conj);
+                       int minus, int trap, int conj, const int32_t* map);
 
 /* ONE grouped launch of the product of the transposed ULV solves of the HSS module (kernels_ulv_t.hip) on host data.  Job i is described by
  * the ten entries desc[10 i ..]: M, K, N, lda, ldx, ldc, aoff, xoff, coff, flags.  A = Abuf + aoff is K x M column-major (lda >= K), X = Xbuf +

@@ -285,7 +285,7 @@ def test_panel_product_kernel_lane_map_exact(hs, cplx):
             X[:K] += (np.arange(K)[:, None] * 2 - np.arange(kc)[None, :]) % 5  # asymmetric
             C0 = np.asfortranarray(ints((M + 1, kc)))
             Cm = C0.copy(order="F")
-            hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), M + 3, X.ctypes.data_as(pf), K + 2, Cm.ctypes.data_as(pf), M + 1, minus, 0))
+            hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), M + 3, X.ctypes.data_as(pf), K + 2, Cm.ctypes.data_as(pf), M + 1, minus, 0, None))
             want = (C0[:M] - A[:M] @ X[:K]) if minus else A[:M] @ X[:K]
             assert np.array_equal(Cm[:M], want), (M, K, kc, minus)
             assert np.array_equal(Cm[M:], C0[M:])
@@ -295,10 +295,32 @@ def test_panel_product_kernel_lane_map_exact(hs, cplx):
     X = np.asfortranarray(ints((K, kc)))
     C0 = np.asfortranarray(ints((M, kc)))
     Cm = C0.copy(order="F")
-    hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), M, X.ctypes.data_as(pf), K, Cm.ctypes.data_as(pf), M, 1, 1))
+    hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), M, X.ctypes.data_as(pf), K, Cm.ctypes.data_as(pf), M, 1, 1, None))
     T = np.tril(A, -1)
     T[np.arange(K), np.arange(K)] = 1
     assert np.array_equal(Cm, C0 - T @ X)
+    # the row map that goes with the trapezoid (MultiProb::cmap = LowRank::rperm): row i of the product belongs to row map[i] of C
+    pi = C.POINTER(C.c_int32)
+    cmap = rng.permutation(M).astype(np.int32)
+    Cm = C0.copy(order="F")
+    hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), M, X.ctypes.data_as(pf), K, Cm.ctypes.data_as(pf), M, 1, 1, cmap.ctypes.data_as(pi)))
+    want = C0.copy()
+    want[cmap] = C0[cmap] - T @ X
+    assert np.array_equal(Cm, want)
+    # ... and without the trapezoid, ragged against every tile: with minus = 0 every row of C is written exactly once, rows past M stay
+    M, K, kc = 65, 33, 17
+    A = np.asfortranarray(ints((M + 3, K)))
+    X = np.asfortranarray(ints((K + 2, kc)))
+    X[:K] += (np.arange(K)[:, None] * 2 - np.arange(kc)[None, :]) % 5
+    C0 = np.asfortranarray(ints((M + 1, kc)))
+    cmap = rng.permutation(M).astype(np.int32)
+    for minus in (0, 1):
+        Cm = C0.copy(order="F")
+        hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), M + 3, X.ctypes.data_as(pf), K + 2, Cm.ctypes.data_as(pf), M + 1, minus, 0, cmap.ctypes.data_as(pi)))
+        want = C0.copy()
+        want[cmap] = (C0[cmap] - A[:M] @ X[:K]) if minus else A[:M] @ X[:K]
+        assert np.array_equal(Cm, want), minus
+        assert np.array_equal(Cm[M:], C0[M:])
 
 
 def test_factors_are_not_read_once_per_column(hs):

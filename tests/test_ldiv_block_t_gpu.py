@@ -322,6 +322,7 @@ def test_transposed_panel_product_kernel_lane_map_exact(hs, cplx):
     L = hs._lib.lib()
     fn = L.hsk_multi_prob_t_z if cplx else L.hsk_multi_prob_t_d
     pf = hs._lib.p_f64
+    pi = C.POINTER(C.c_int32)
     dt = np.complex128 if cplx else np.float64
     rng = np.random.default_rng(17)
 
@@ -339,7 +340,7 @@ def test_transposed_panel_product_kernel_lane_map_exact(hs, cplx):
                     X[:K] += (np.arange(K)[:, None] * 2 - np.arange(kc)[None, :]) % 5  # asymmetric
                     C0 = np.asfortranarray(ints((M + 1, kc)))
                     Cm = C0.copy(order="F")
-                    hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), lda, X.ctypes.data_as(pf), K + 2, Cm.ctypes.data_as(pf), M + 1, minus, 0, conj))
+                    hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), lda, X.ctypes.data_as(pf), K + 2, Cm.ctypes.data_as(pf), M + 1, minus, 0, conj, None))
                     At = (np.conj(A[:K]) if conj else A[:K]).T
                     want = (C0[:M] - At @ X[:K]) if minus else At @ X[:K]
                     assert np.array_equal(Cm[:M], want), (M, K, kc, lda, minus, conj)
@@ -351,10 +352,31 @@ def test_transposed_panel_product_kernel_lane_map_exact(hs, cplx):
         X = np.asfortranarray(ints((K, kc)))
         C0 = np.asfortranarray(ints((M, kc)))
         Cm = C0.copy(order="F")
-        hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), K, X.ctypes.data_as(pf), K, Cm.ctypes.data_as(pf), M, 1, 1, conj))
+        hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), K, X.ctypes.data_as(pf), K, Cm.ctypes.data_as(pf), M, 1, 1, conj, None))
         T = np.tril(np.conj(A) if conj else A, -1)
         T[np.arange(M), np.arange(M)] = 1
         assert np.array_equal(Cm, C0 - T.T @ X)
+        # the row map that goes with the trapezoid (MultiProbT::xmap = LowRank::rperm): row k of A meets row map[k] of X
+        xmap = rng.permutation(K).astype(np.int32)
+        Cm = C0.copy(order="F")
+        hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), K, X.ctypes.data_as(pf), K, Cm.ctypes.data_as(pf), M, 1, 1, conj, xmap.ctypes.data_as(pi)))
+        assert np.array_equal(Cm, C0 - T.T @ X[xmap])
+    # ... and without the trapezoid, ragged against every tile, odd and even lda
+    M, K, kc = 65, 33, 17
+    for lda in (K + 3, K + 4):
+        for minus in (0, 1):
+            for conj in (0, 1) if cplx else (0,):
+                A = np.asfortranarray(ints((lda, M)))
+                X = np.asfortranarray(ints((K + 2, kc)))
+                X[:K] += (np.arange(K)[:, None] * 2 - np.arange(kc)[None, :]) % 5
+                C0 = np.asfortranarray(ints((M + 1, kc)))
+                xmap = rng.permutation(K).astype(np.int32)
+                Cm = C0.copy(order="F")
+                hs._lib.check(fn(M, K, kc, A.ctypes.data_as(pf), lda, X.ctypes.data_as(pf), K + 2, Cm.ctypes.data_as(pf), M + 1, minus, 0, conj, xmap.ctypes.data_as(pi)))
+                At = (np.conj(A[:K]) if conj else A[:K]).T
+                want = (C0[:M] - At @ X[:K][xmap]) if minus else At @ X[:K][xmap]
+                assert np.array_equal(Cm[:M], want), (lda, minus, conj)
+                assert np.array_equal(Cm[M:], C0[M:])
 
 
 def test_factors_are_not_read_once_per_column(hs):

@@ -70,6 +70,13 @@ def test_new_entry_points_are_declared_exported_and_bound(hs):
             assert fn(None, trans, None, 2, None, 2, 2, 1, None) == hs._lib.HS_ERR_ARGUMENT
     # the hooks refuse bad arguments before they look for a device
     for fn in (lib.hsk_multi_prob_t_d, lib.hsk_multi_prob_t_z):
-        assert fn(0, 1, 1, pb, 1, pb, 1, pb, 1, 0, 0, 0) == hs._lib.HS_ERR_ARGUMENT
-        assert fn(2, 2, 65, pb, 2, pb, 2, pb, 2, 0, 0, 0) == hs._lib.HS_ERR_ARGUMENT
+        assert fn(0, 1, 1, pb, 1, pb, 1, pb, 1, 0, 0, 0, None) == hs._lib.HS_ERR_ARGUMENT
+        assert fn(2, 2, 65, pb, 2, pb, 2, pb, 2, 0, 0, 0, None) == hs._lib.HS_ERR_ARGUMENT
+    # ... and a row map with an entry outside its range: K entries in 0..K-1 (transposed), M entries in 0..M-1 (forward)
+    for bad in ([0, 2], [-1, 0]):
+        m = (C.c_int32 * 2)(*bad)
+        for fn in (lib.hsk_multi_prob_t_d, lib.hsk_multi_prob_t_z):
+            assert fn(1, 2, 1, pb, 2, pb, 2, pb, 1, 0, 0, 0, m) == hs._lib.HS_ERR_ARGUMENT
+        for fn in (lib.hsk_multi_prob_d, lib.hsk_multi_prob_z):
+            assert fn(2, 1, 1, pb, 2, pb, 1, pb, 2, 0, 0, m) == hs._lib.HS_ERR_ARGUMENT
     assert np.all(b == 0)
