@@ -87,7 +87,7 @@ EXPORTS = [
     "hs_sens_d", "hs_sens_z", "hs_sens_dev_d", "hs_sens_dev_z", "hs_misfit_d", "hs_misfit_z", "hs_misfit_dev_d", "hs_misfit_dev_z", "hs_sens_info", "hsk_sddmm_d", "hsk_sddmm_z",
     "hs_mod_create_d", "hs_mod_create_z", "hs_mod_create_dev_d", "hs_mod_create_dev_z", "hs_mod_create_sparse_d", "hs_mod_create_sparse_z", "hs_mod_ldiv_d", "hs_mod_ldiv_z",
     "hs_mod_ldiv_dev_d", "hs_mod_ldiv_dev_z", "hs_mod_info", "hs_mod_free", "hs_gmres_block_mod_d", "hs_gmres_block_mod_z",
-    "hs_eigs_d", "hs_eigs_z", "hs_eigs_info", "hsk_eigs_rotate_d", "hsk_eigs_rotate_z", "hsk_eigs_chol_inv_d", "hsk_eigs_chol_inv_z", "hsk_small_eig_z", "hsk_eigs_phase_timing", "hsk_eigs_phases",
+    "hs_eigs_d", "hs_eigs_z", "hs_eigs_info", "hs_eigs_gen_d", "hs_eigs_gen_z", "hs_eigs_gen_info", "hsk_eigs_coldot_d", "hsk_eigs_coldot_z", "hsk_eigs_rotate_d", "hsk_eigs_rotate_z", "hsk_eigs_chol_inv_d", "hsk_eigs_chol_inv_z", "hsk_small_eig_z", "hsk_eigs_phase_timing", "hsk_eigs_phases", "hsk_eigs_gen_mprod_seconds",
     "hsk_mod_inner_d", "hsk_mod_inner_z", "hsk_mod_apply_d", "hsk_mod_apply_z", "hsk_mod_gather_d", "hsk_mod_gather_z", "hsk_mod_cap_d", "hsk_mod_cap_z",
     "hs_maxrank", "hs_is_complex", "hs_size", "hs_free", "hs_last_error", "hs_last_error_info", "hs_get_stats",
     "hs_node_info", "hs_node_ranks", "hs_node_export", "hs_node_export_piv", "hs_device_info",
@@ -255,6 +255,15 @@ def lib():
         f.restype = C.c_int
     L.hs_eigs_info.argtypes = [p_f64]
     L.hs_eigs_info.restype = C.c_int
+    for f in (L.hs_eigs_gen_d, L.hs_eigs_gen_z):
+        f.argtypes = [vp, C.c_int, i64, p_i64, p_i64, vp, C.c_int, i64, i64, i64, C.c_double, C.c_double, C.c_double, i64, vp, i64, i64, C.c_int, p_f64, vp, i64, p_f64, p_f64,
+                      p_i64, p_i64, vp]
+        f.restype = C.c_int
+    L.hs_eigs_gen_info.argtypes = [p_f64]
+    L.hs_eigs_gen_info.restype = C.c_int
+    for f in (L.hsk_eigs_coldot_d, L.hsk_eigs_coldot_z):
+        f.argtypes = [i64, i64, vp, i64, vp, i64, C.POINTER(C.c_int), p_f64]
+        f.restype = C.c_int
     for f in (L.hsk_eigs_rotate_d, L.hsk_eigs_rotate_z):
         f.argtypes = [i64, i64, i64, vp, i64, vp, i64, C.c_int, vp, i64]
         f.restype = C.c_int
@@ -267,6 +276,8 @@ def lib():
     L.hsk_eigs_phase_timing.restype = C.c_int
     L.hsk_eigs_phases.argtypes = [p_f64]
     L.hsk_eigs_phases.restype = C.c_int
+    L.hsk_eigs_gen_mprod_seconds.argtypes = []
+    L.hsk_eigs_gen_mprod_seconds.restype = C.c_double
     L.hs_logabsdet.argtypes = [vp, p_f64, p_f64]
     L.hs_logabsdet.restype = C.c_int
     L.hs_selinv.argtypes = [vp, C.c_int, vp, vp, C.c_int, i64, vp]

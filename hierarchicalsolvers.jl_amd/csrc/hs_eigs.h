@@ -34,6 +34,14 @@ void launch_eigs_chol_inv(const T* G, int ldg, int p, T* R, T* Rinv, int* info, 
 // [re -im; im re] of the first.  A pair shares one figure: the norm of the complex vector.  part: hs_eigs_slabs(n) * nc doubles.
 template <class T>
 void launch_eigs_resid(T* Y, int64_t ldy, const T* X, int64_t ldx, const double* mu, const int* pair, int64_t n, int nc, double* part, double* nrm, hipStream_t s);
+// d[c] = Re sum_i conj(X[i, c]) Y[i, c], the slab scheme of launch_eigs_resid: HS_EIGS_SLAB rows per workgroup, a thread adds its rows in
+// order, the partials fold by halves, the slabs are added in slab order.  pair as above (may be nullptr): a Float64 pair shares one figure,
+// the sum over both columns.  With Y = op(M) X this is x^H op(M) x of the generalized problem (hs_eigs_gen_*); any nc, unlike
+// launch_mod_inner.  part: hs_eigs_slabs(n) * nc doubles.
+template <class T>
+void launch_eigs_coldot(const T* X, int64_t ldx, const T* Y, int64_t ldy, const int* pair, int64_t n, int nc, double* part, double* d, hipStream_t s);
+// d[c] = sqrt(d[c]) where d[c] > 0, else 0 (launch_eigs_scale then leaves the column)
+void launch_eigs_sqrt(double* d, int nc, hipStream_t s);
 // X[:, c] /= nrm[c] (a zero norm leaves the column)
 template <class T>
 void launch_eigs_scale(T* X, int64_t ldx, const double* nrm, int64_t n, int nc, hipStream_t s);

@@ -1,5 +1,6 @@
 // hs_eigs.hip -- eigenpairs of A nearest a shift from the stored factorization of A_s = A - sigma I (hs_eigs_*; include/hs_solver.h): block
-// Arnoldi on op(F)^-1 with thick restart, in Krylov-decomposition form.
+// Arnoldi on op(F)^-1 with thick restart, in Krylov-decomposition form.  hs_eigs_gen_* is the same loop for the pencil (A, M) with
+// A_s = A - sigma M: the operator is C = op(F)^-1 op(M) (see "generalized" below); hs_eigs_* is that body with M = NULL.
 //
 // State: an orthonormal basis V (n x (m + p), on the device) and the host matrix G ((m + p) x m) with  op(F)^-1 V[:, :m] = V G.
 //
@@ -14,6 +15,11 @@
 //               V[:, :keep] <- V[:, :m] Q in place (launch_eigs_rotate), the last block moves down behind them.
 //   finish      X = V[:, :m] Y normalised, mu = 1 / theta, lambda = sigma + mu, true residuals ||op(A_s) X - X diag(mu)|| with the handle's
 //               own A_s (hs_gmres_own_rows, spmm_op_kernel, launch_eigs_resid).
+//
+//   generalized an expansion first forms T = op(M) V[:, m:m+p] (launch_spmm_op over the rows of op(M): a CSR of M for trans = 0, the CSC arrays
+//               of M read in place otherwise, conjugated on load for trans = 2) and solves from T.  inner = 1: every inner product of
+//               orth_block is taken against MW = op(M) W, recomputed by SpMM after every change of W, so V is op(M)-orthonormal; the Ritz
+//               vectors are scaled to x^H op(M) x = 1 (launch_eigs_coldot).  The residual is op(A_s) X - (op(M) X) diag(mu).
 //
 // Everything the device computes has one summation order per element and the host part is sequential, so two calls return the same bits.
 #include <chrono>
@@ -33,6 +39,9 @@ using hs_se::zc;
 
 enum { EI_SECONDS = 0, EI_SOLVES, EI_COLAPPS, EI_RESTARTS, EI_ORTH, EI_REPLACED, EI_WORK_BYTES, EI_NCV };
 thread_local double g_einfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+enum { GI_PRODUCTS = 0, GI_COLUMNS, GI_BYTES, GI_INNER };  // hs_eigs_gen_info
+thread_local double g_ginfo[4] = {0, 0, 0, 0};
+thread_local double g_mprod_seconds = 0.0;  // host-clock seconds of the products with op(M), taken only while hsk_eigs_phase_timing is on
 // host-clock seconds of the last call by phase (hsk_eigs_phases): block solves, orthogonalisation, restarts (host eigenproblem and rotation),
 // Ritz vectors and residuals.  Every phase ends in a synchronisation of its own except the block solve, which gets one only while
 // hsk_eigs_phase_timing is on (off: its time is counted with the orthogonalisation that follows).
@@ -86,18 +95,45 @@ struct Eigs {
   int* dInfo = nullptr;
   std::vector<S> G;  // (mcap + p) x mcap, ld = mcap + p
   int ldg = 0, draws = 0;
+  // the generalized problem: the rows of op(M) (has_m), the op(M) inner product (minner, only with has_m) and its block MW = op(M) W
+  RowsOf<T> M;
+  bool has_m = false, minner = false;
+  T* MW = nullptr;
 
   S& g(int i, int j) { return G[(size_t)j * ldg + i]; }
 
+  // Y (n x nc, ld n) = op(M) X
+  void mult_m(const T* X, int64_t ldx, T* Y, int nc) {
+    if (g_phase_sync) {  // a synchronisation before and behind each product, so that the clock sees the product alone
+      GM_HIP(hipStreamSynchronize(s));
+      const auto t0 = std::chrono::steady_clock::now();
+      launch_spmm_op<T>(M, X, ldx, nullptr, Y, n, nullptr, 0, nullptr, n, nc, s);
+      GM_HIP(hipStreamSynchronize(s));
+      g_mprod_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+      launch_spmm_op<T>(M, X, ldx, nullptr, Y, n, nullptr, 0, nullptr, n, nc, s);
+    }
+    g_ginfo[GI_PRODUCTS] += 1;
+    g_ginfo[GI_COLUMNS] += nc;
+  }
+  // the right-hand block of an inner product with W: W itself, or op(M) W computed now (never updated: one summation order per element)
+  const T* metric(const T* W) {
+    if (!minner) return W;
+    mult_m(W, ldv, MW, p);
+    return MW;
+  }
+
   // Orthonormalise W = V[:, k:k+p] against V[:, :k] and in itself, in place: W_in = V[:, :k] h + W_out R; h (k x p) and R (p x p) go to
-  // G[0:k, col0:col0+p] and G[k:k+p, col0:col0+p] (col0 < 0: the start block, nothing is recorded)
+  // G[0:k, col0:col0+p] and G[k:k+p, col0:col0+p] (col0 < 0: the start block, nothing is recorded).  With minner "orthonormal" is meant in
+  // the op(M) inner product, and the deficiency rule of chol_inv applies to the M-Gram matrix.
   void orth_block(int k, int col0) {
     T* W = V + (size_t)k * ldv;
     std::vector<S> Racc((size_t)p * p, S(0.0)), Hacc((size_t)k * p, S(0.0)), h((size_t)k * p), R((size_t)p * p), tmp((size_t)p * p);
     for (int i = 0; i < p; ++i) Racc[(size_t)i * p + i] = S(1.0);
     for (int attempt = 0; attempt <= p; ++attempt) {
       for (int pass = 0; pass < 2 && k > 0; ++pass) {
-        launch_mod_inner<T>(V, ldv, W, ldv, n, k, p, 0, part, dh, k, s);
+        const T* mw = metric(W);
+        launch_mod_inner<T>(V, ldv, mw, minner ? n : ldv, n, k, p, 0, part, dh, k, s);
         launch_mod_apply<T>(W, ldv, V, ldv, dh, k, n, k, p, 0, s);
         GM_HIP(hipMemcpyAsync(h.data(), dh, sizeof(T) * (size_t)k * p, hipMemcpyDeviceToHost, s));
         GM_HIP(hipStreamSynchronize(s));
@@ -111,7 +147,16 @@ struct Eigs {
       }
       int bad = -1;
       for (int round = 0; round < 2; ++round) {
-        launch_mod_inner<T>(W, ldv, W, ldv, n, p, p, 0, part, dG, p, s);
+        const T* mw = metric(W);
+        launch_mod_inner<T>(W, ldv, mw, minner ? n : ldv, n, p, p, 0, part, dG, p, s);
+        if (minner && col0 < 0 && attempt == 0 && round == 0) {  // the start block as given: a diagonal entry v^H op(M) v that is not positive
+          GM_HIP(hipMemcpyAsync(tmp.data(), dG, sizeof(T) * (size_t)p * p, hipMemcpyDeviceToHost, s));
+          GM_HIP(hipStreamSynchronize(s));
+          for (int c = 0; c < p; ++c)
+            if (!(std::real(tmp[(size_t)c * p + c]) > 0.0))
+              EG_FAIL(HS_ERR_ARGUMENT, c, "ArgumentError: hs_eigs_gen_*: inner = 1 needs a Hermitian positive definite M: v^H op(M) v = %g for column %d of the start block",
+                      std::real(tmp[(size_t)c * p + c]), c + 1);
+        }
         launch_eigs_chol_inv<T>(dG, p, p, dR, dRi, dInfo, s);
         GM_HIP(hipMemcpyAsync(&bad, dInfo, sizeof(int), hipMemcpyDeviceToHost, s));
         GM_HIP(hipMemcpyAsync(R.data(), dR, sizeof(T) * (size_t)p * p, hipMemcpyDeviceToHost, s));
@@ -217,8 +262,38 @@ int refused_by_block_solve(hs_handle* F, int trans, int64_t n) {
   return block_solve<T>(F, trans, nullptr, n, nullptr, n, n, 0, nullptr);
 }
 
+// The CSC arrays of M as the caller passed them (1-based SparseMatrixCSC fields); all null: M = I
 template <class T>
-void eigs_run(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const T* V0,
+struct HostCsc {
+  const int64_t* colptr = nullptr;
+  const int64_t* rowval = nullptr;
+  const T* nzval = nullptr;
+};
+
+// What upload_csr / upload_csc would find, found on the host before anything else is touched -- and what they do not look at (a colptr that
+// is not monotone).  Returns whether M is given.
+template <class T>
+bool check_m_args(const char* fn, const HostCsc<T>& M, int inner, int64_t n) {
+  if (inner < 0 || inner > 1) EG_FAIL(HS_ERR_ARGUMENT, inner, "ArgumentError: %s: inner = %d (0: Euclidean, 1: the op(M) inner product)", fn, inner);
+  const int given = (M.colptr ? 1 : 0) + (M.rowval ? 1 : 0) + (M.nzval ? 1 : 0);
+  if (given != 0 && given != 3) EG_FAIL(HS_ERR_ARGUMENT, given, "ArgumentError: %s: mcolptr, mrowval and mnzval must all be given, or all be NULL (M = I)", fn);
+  if (given == 0) return false;
+  if (n > (int64_t)INT32_MAX)
+    EG_FAIL(HS_ERR_ARGUMENT, n, "ArgumentError: %s: n = %lld exceeds the 32-bit indices of the device matrix (limit %d)", fn, (long long)n, INT32_MAX);
+  if (M.colptr[0] != 1) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: mcolptr must be 1-based (SparseMatrixCSC)", fn);
+  for (int64_t c = 0; c < n; ++c)
+    if (M.colptr[c + 1] < M.colptr[c])
+      EG_FAIL(HS_ERR_ARGUMENT, c + 1, "ArgumentError: %s: mcolptr[%lld] = %lld is below mcolptr[%lld] = %lld", fn, (long long)c + 2, (long long)M.colptr[c + 1], (long long)c + 1,
+              (long long)M.colptr[c]);
+  const int64_t nnz = M.colptr[n] - 1;
+  for (int64_t e = 0; e < nnz; ++e)
+    if (M.rowval[e] < 1 || M.rowval[e] > n)
+      EG_FAIL(HS_ERR_ARGUMENT, e, "ArgumentError: %s: mrowval[%lld] = %lld outside 1:%lld", fn, (long long)e + 1, (long long)M.rowval[e], (long long)n);
+  return true;
+}
+
+template <class T>
+void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inner, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const T* V0,
               int64_t ldv0, int64_t seed, int where, double* lam, T* X, int64_t ldx, double* resid, double* est, int64_t* nout_, int64_t* nconv_, void* stream, DevBuf& buf,
               hipEvent_t* e0, hipEvent_t* e1) {
   typedef typename HostOf<T>::type S;
@@ -252,6 +327,7 @@ void eigs_run(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int6
   if (real_h && sigma_im != 0.0) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: a complex shift on a Float64 factorization (factor A - sigma I as ComplexF64)", fn);
   if (!(tol >= 0.0) || maxrestart < 0 || !std::isfinite(sigma_re) || !std::isfinite(sigma_im))
     EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: tol = %g, maxrestart = %lld, sigma = (%g, %g)", fn, tol, (long long)maxrestart, sigma_re, sigma_im);
+  const bool has_m = check_m_args<T>(fn, Mh, inner, n);
   if (const int st = hs_gmres_own_check(F, fn, 1)) throw st;  // more than one rank: neither the block solve nor the handle's own A
   {  // what hs_ldiv_block_dev_t_* refuses is refused here, with its words
     const int st = refused_by_block_solve<T>(F, trans, n);
@@ -304,6 +380,31 @@ void eigs_run(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int6
   int* dpair = buf.get<int>(take((size_t)nx, sizeof(int)));
   for (double& q : g_einfo) q = 0.0;
   for (double& q : g_ephase) q = 0.0;
+  for (double& q : g_ginfo) q = 0.0;
+  g_mprod_seconds = 0.0;
+  // ---- M on the device, once per call, and the blocks only the generalized problem needs: T = op(M) V[:, m:m+p], MX = op(M) X, MW
+  T *dT = nullptr, *dMX = nullptr;
+  if (has_m) {
+    E.has_m = true;
+    E.minner = inner == 1;
+    dT = buf.get<T>(take((size_t)n * p, sizeof(T)));
+    dMX = buf.get<T>(take((size_t)n * nx, sizeof(T)));
+    if (E.minner) E.MW = buf.get<T>(take((size_t)n * p, sizeof(T)));
+    int64_t* mp = nullptr;
+    int32_t* mi = nullptr;
+    T* mv = nullptr;
+    if (trans == 0)
+      upload_csr<T>(buf, n, Mh.colptr, Mh.rowval, Mh.nzval, &mp, &mi, &mv);
+    else
+      upload_csc<T>(buf, n, Mh.colptr, Mh.rowval, Mh.nzval, &mp, &mi, &mv);
+    E.M.ptr = mp;
+    E.M.idx = mi;
+    E.M.val = mv;
+    E.M.conj = trans == 2;
+    const size_t nnz = (size_t)(Mh.colptr[n] - 1);
+    g_ginfo[GI_BYTES] = (double)(std::max<size_t>(sizeof(int64_t) * ((size_t)n + 1), 256) + std::max<size_t>(sizeof(int32_t) * nnz, 256) + std::max<size_t>(sizeof(T) * nnz, 256));
+    g_ginfo[GI_INNER] = E.minner ? 1.0 : 0.0;
+  }
   g_einfo[EI_WORK_BYTES] = (double)bytes;
   g_einfo[EI_NCV] = (double)ncv;
   GM_HIP(hipEventCreate(e0));
@@ -327,7 +428,12 @@ void eigs_run(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int6
   std::vector<double> estv;
   for (;;) {
     while (m + p <= lim && m + 2 * p <= ncols) {
-      const int st = block_solve<T>(F, trans, E.V + (size_t)(m + p) * ldv, ldv, E.V + (size_t)m * ldv, ldv, n, p, s);
+      const T* rhs = E.V + (size_t)m * ldv;
+      if (has_m) {
+        E.mult_m(rhs, ldv, dT, p);
+        rhs = dT;
+      }
+      const int st = block_solve<T>(F, trans, E.V + (size_t)(m + p) * ldv, ldv, rhs, has_m ? n : ldv, n, p, s);
       if (st != HS_OK) throw st;
       g_einfo[EI_SOLVES] += 1;
       g_einfo[EI_COLAPPS] += p;
@@ -428,8 +534,15 @@ void eigs_run(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int6
   GM_HIP(hipMemcpyAsync(dmu, mu.data(), sizeof(double) * 2 * (size_t)nx, hipMemcpyHostToDevice, s));
   GM_HIP(hipMemcpyAsync(dpair, pr.data(), sizeof(int) * (size_t)nx, hipMemcpyHostToDevice, s));
   launch_eigs_rotate<T>(dX, n, E.V, ldv, E.dQ, m, n, m, nout, s);
-  launch_eigs_resid<T>(dX, n, nullptr, 0, nullptr, dpair, n, nout, E.dpart, E.dnrm, s);
+  if (E.minner) {  // x^H op(M) x = 1
+    E.mult_m(dX, n, dMX, nout);
+    launch_eigs_coldot<T>(dX, n, dMX, n, dpair, n, nout, E.dpart, E.dnrm, s);
+    launch_eigs_sqrt(E.dnrm, nout, s);
+  } else {
+    launch_eigs_resid<T>(dX, n, nullptr, 0, nullptr, dpair, n, nout, E.dpart, E.dnrm, s);
+  }
   launch_eigs_scale<T>(dX, n, E.dnrm, n, nout, s);
+  if (has_m) E.mult_m(dX, n, dMX, nout);
   HsGmresRows rows;
   if (const int st = hs_gmres_own_rows(F, trans, s, &rows)) throw st;
   RowsOf<T> A;
@@ -438,7 +551,7 @@ void eigs_run(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int6
   A.val = (const T*)rows.val;
   A.conj = trans == 2;
   launch_spmm_op<T>(A, dX, n, nullptr, dAX, n, nullptr, 0, nullptr, n, nout, s);
-  launch_eigs_resid<T>(dAX, n, dX, n, dmu, dpair, n, nout, E.dpart, E.dnrm, s);
+  launch_eigs_resid<T>(dAX, n, has_m ? dMX : dX, n, dmu, dpair, n, nout, E.dpart, E.dnrm, s);
   GM_HIP(hipMemcpyAsync(nrm.data(), E.dnrm, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s));
   GM_HIP(hipEventRecord(*e1, s));
   GM_HIP(hipStreamSynchronize(s));
@@ -461,13 +574,13 @@ void eigs_run(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int6
 }
 
 template <class T>
-int eigs_entry(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const T* V0,
+int eigs_entry(hs_handle* F, int trans, int64_t n, const HostCsc<T>& M, int inner, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const T* V0,
                int64_t ldv0, int64_t seed, int where, double* lam, T* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv, void* stream) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = HS_OK;
   DevBuf buf;  // outlives the try block: after a throw the stream is drained below before the workspace is freed
   try {
-    eigs_run<T>(F, trans, n, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, V0, ldv0, seed, where, lam, X, ldx, resid, est, nout, nconv, stream, buf, &e0, &e1);
+    eigs_run<T>(F, trans, n, M, inner, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, V0, ldv0, seed, where, lam, X, ldx, resid, est, nout, nconv, stream, buf, &e0, &e1);
   } catch (int code) {
     rc = code;
   } catch (const std::bad_alloc&) {
@@ -485,13 +598,41 @@ int eigs_entry(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int
 extern "C" int hs_eigs_d(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart,
                          const double* V0, int64_t ldv0, int64_t seed, int where, double* lam, double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv,
                          void* stream) {
-  return eigs_entry<double>(F, trans, n, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, V0, ldv0, seed, where, lam, X, ldx, resid, est, nout, nconv, stream);
+  return eigs_entry<double>(F, trans, n, HostCsc<double>(), 0, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, V0, ldv0, seed, where, lam, X, ldx, resid, est, nout, nconv,
+                            stream);
 }
 extern "C" int hs_eigs_z(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart,
                          const double* V0, int64_t ldv0, int64_t seed, int where, double* lam, double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv,
                          void* stream) {
-  return eigs_entry<cplx>(F, trans, n, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, (const cplx*)V0, ldv0, seed, where, lam, (cplx*)X, ldx, resid, est, nout, nconv,
-                          stream);
+  return eigs_entry<cplx>(F, trans, n, HostCsc<cplx>(), 0, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, (const cplx*)V0, ldv0, seed, where, lam, (cplx*)X, ldx, resid, est,
+                          nout, nconv, stream);
+}
+extern "C" int hs_eigs_gen_d(hs_handle* F, int trans, int64_t n, const int64_t* mcolptr, const int64_t* mrowval, const double* mnzval, int inner, int64_t nev, int64_t ncv,
+                             int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const double* V0, int64_t ldv0, int64_t seed, int where, double* lam,
+                             double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv, void* stream) {
+  HostCsc<double> M;
+  M.colptr = mcolptr;
+  M.rowval = mrowval;
+  M.nzval = mnzval;
+  return eigs_entry<double>(F, trans, n, M, inner, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, V0, ldv0, seed, where, lam, X, ldx, resid, est, nout, nconv, stream);
+}
+extern "C" int hs_eigs_gen_z(hs_handle* F, int trans, int64_t n, const int64_t* mcolptr, const int64_t* mrowval, const double* mnzval, int inner, int64_t nev, int64_t ncv,
+                             int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const double* V0, int64_t ldv0, int64_t seed, int where, double* lam,
+                             double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv, void* stream) {
+  HostCsc<cplx> M;
+  M.colptr = mcolptr;
+  M.rowval = mrowval;
+  M.nzval = (const cplx*)mnzval;
+  return eigs_entry<cplx>(F, trans, n, M, inner, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, (const cplx*)V0, ldv0, seed, where, lam, (cplx*)X, ldx, resid, est, nout,
+                          nconv, stream);
+}
+extern "C" int hs_eigs_gen_info(double* out4) {
+  if (!out4) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_eigs_gen_info: out4 == NULL");
+    return HS_ERR_ARGUMENT;
+  }
+  for (int k = 0; k < 4; ++k) out4[k] = g_ginfo[k];
+  return HS_OK;
 }
 extern "C" int hs_eigs_info(double* out8) {
   if (!out8) {
@@ -506,6 +647,7 @@ extern "C" int hsk_eigs_phase_timing(int on) {
   g_phase_sync = on != 0;
   return was;
 }
+extern "C" double hsk_eigs_gen_mprod_seconds(void) { return g_mprod_seconds; }
 extern "C" int hsk_eigs_phases(double* out4) {
   if (!out4) {
     hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hsk_eigs_phases: out4 == NULL");

@@ -1054,6 +1054,35 @@ extern "C" int hsk_eigs_chol_inv_z(int64_t p, const double* G, int64_t ldg, doub
   return eigs_chol_inv_hook<cplx>(p, (const cplx*)G, ldg, (cplx*)R, (cplx*)Rinv, info);
 }
 
+template <class T>
+static int eigs_coldot_hook(int64_t n, int64_t nc, const T* X, int64_t ldx, const T* Y, int64_t ldy, const int* pair, double* d) {
+  bool ok = n >= 1 && nc >= 1 && nc <= HS_EIGS_MAXBASIS && ldx >= n && ldy >= n && X && Y && d;
+  for (int64_t c = 0; ok && pair && c < nc; ++c)  // a pair is two adjacent columns of a Float64 block
+    ok = pair[c] == 0 || (sizeof(T) == 8 && ((pair[c] == 1 && c + 1 < nc && pair[c + 1] == -1) || (pair[c] == -1 && c > 0 && pair[c - 1] == 1)));
+  if (!ok) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_eigs_coldot: n >= 1, nc in 1..256, leading dimensions >= n, non-null arrays and whole Float64 pairs required");
+    return HS_ERR_ARGUMENT;
+  }
+  if (int st = mod_hook_device()) return st;
+  ModBufs b;
+  T* dX = b.up<T>(X, ldx, n, nc);
+  T* dY = b.up<T>(Y, ldy, n, nc);
+  int* dPair = pair ? b.up<int>(pair, nc, nc, 1) : nullptr;
+  double* dPart = b.up<double>(nullptr, 1, hs_eigs_slabs(n) * nc, 1);
+  double* dD = b.up<double>(nullptr, nc, nc, 1);
+  MOD_NULL(dX && dY && (dPair || !pair) && dPart && dD);
+  launch_eigs_coldot<T>(dX, n, dY, n, dPair, n, (int)nc, dPart, dD, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy(d, dD, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+extern "C" int hsk_eigs_coldot_d(int64_t n, int64_t nc, const double* X, int64_t ldx, const double* Y, int64_t ldy, const int* pair, double* d) {
+  return eigs_coldot_hook<double>(n, nc, X, ldx, Y, ldy, pair, d);
+}
+extern "C" int hsk_eigs_coldot_z(int64_t n, int64_t nc, const double* X, int64_t ldx, const double* Y, int64_t ldy, const int* pair, double* d) {
+  return eigs_coldot_hook<cplx>(n, nc, (const cplx*)X, ldx, (const cplx*)Y, ldy, pair, d);
+}
+
 extern "C" int hsk_small_eig_z(int64_t m, const double* H, int64_t ldh, double* w, double* Y, int64_t ldy) {
   if (m < 1 || m > HS_EIGS_MAXBASIS || ldh < m || ldy < m || !H || !w || !Y) {
     hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_small_eig_z: m in 1..256, leading dimensions >= m and non-null arrays required");

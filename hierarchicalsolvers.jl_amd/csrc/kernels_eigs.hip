@@ -3,7 +3,8 @@
 //   eigs_rotate     Out[:, :N] = V[:, :K] Q     the basis rotation of a restart, W <- W R^-1 of CholQR and the Ritz vectors; in place or not
 //   eigs_chol_inv   G = R^H R, R^-1             the p x p Cholesky factor of a Gram matrix and its inverse, with the first dependent column
 //   eigs_colsq      Y -= X diag(mu), ||.||_2    the residual of the Ritz pairs and column norms, row slabs + an ordered second pass
-//   eigs_scale, eigs_init                       column normalisation, the seeded start block
+//   eigs_coldot     Re x_c^H y_c                the x^H op(M) x of the generalized problem (hs_eigs_gen_*), the same slabs and order
+//   eigs_scale, eigs_init                    column normalisation, the seeded start block
 //
 // eigs_rotate computes the TRANSPOSED tile like mod_apply (kernels_mod.hip gives the lane maps of v_mfma_f64_16x16x4_f64): Q^T is the A operand
 // (lane: column c0 + (lane & 15) of Q, row j0 + (lane >> 4)), the rows of V sit on lane & 15 of the B operand and of C/D, so the stores of Out
@@ -223,6 +224,68 @@ void launch_eigs_resid(T* Y, int64_t ldy, const T* X, int64_t ldx, const double*
 }
 template void launch_eigs_resid<double>(double*, int64_t, const double*, int64_t, const double*, const int*, int64_t, int, double*, double*, hipStream_t);
 template void launch_eigs_resid<cplx>(cplx*, int64_t, const cplx*, int64_t, const double*, const int*, int64_t, int, double*, double*, hipStream_t);
+
+// ---- eigs_coldot ----------------------------------------------------------------------------------------------------------------------------
+// The workgroup (slab, c) of eigs_colsq on two blocks: Re conj(x) y per row (ComplexF64: re*re then im*im), the second column of a Float64
+// pair added in the same row step; the workgroup of the second member of a pair writes a zero that nothing reads.
+template <class T>
+__global__ __launch_bounds__(256) void eigs_coldot_kernel(const T* X, long long ldx, const T* Y, long long ldy, const int* pair, long long n, int nc, double* part) {
+  __shared__ double red[256];
+  const int t = threadIdx.x, c = blockIdx.y;
+  const int pc = pair ? gld(pair + c) : 0;
+  const long long r0 = (long long)blockIdx.x * HS_EIGS_SLAB, r1 = min(n, r0 + (long long)HS_EIGS_SLAB);
+  double acc = 0.0;
+  if (pc >= 0) {
+    const T* x = X + (size_t)c * ldx;
+    const T* y = Y + (size_t)c * ldy;
+    for (long long r = r0 + t; r < r1; r += 256) {
+      if constexpr (sizeof(T) == 16) {
+        const cplx a = gld(x + r), b = gld(y + r);
+        acc += a.re * b.re + a.im * b.im;
+      } else {  // the expressions of eigs_colsq with its two equal factors apart: Y == X gives the bits of its squared norm
+        const double a = gld(x + r), b = gld(y + r);
+        if (pc == 0) {
+          acc += a * b;
+        } else {
+          const double a2 = gld(x + ldx + r), b2 = gld(y + ldy + r);
+          acc += a * b + a2 * b2;
+        }
+      }
+    }
+  }
+  red[t] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) red[t] += red[t + s];
+    __syncthreads();
+  }
+  if (t == 0) gst(part + (size_t)blockIdx.x * nc + c, red[0]);
+}
+__global__ __launch_bounds__(256) void eigs_slabsum_kernel(const double* part, long long nslab, int nc, const int* pair, double* d) {
+  const int c = threadIdx.x;
+  if (c >= nc) return;
+  const int cc = (pair && gld(pair + c) < 0) ? c - 1 : c;  // the second of a pair takes the figure of the first
+  double acc = gld(part + cc);
+  for (long long s = 1; s < nslab; ++s) acc += gld(part + s * nc + cc);
+  gst(d + c, acc);
+}
+template <class T>
+void launch_eigs_coldot(const T* X, int64_t ldx, const T* Y, int64_t ldy, const int* pair, int64_t n, int nc, double* part, double* d, hipStream_t s) {
+  if (n <= 0 || nc <= 0) return;
+  hipLaunchKernelGGL(eigs_coldot_kernel<T>, dim3((unsigned)hs_eigs_slabs(n), (unsigned)nc), dim3(256), 0, s, X, (long long)ldx, Y, (long long)ldy, pair, (long long)n, nc, part);
+  hipLaunchKernelGGL(eigs_slabsum_kernel, dim3(1), dim3(256), 0, s, (const double*)part, (long long)hs_eigs_slabs(n), nc, pair, d);
+}
+template void launch_eigs_coldot<double>(const double*, int64_t, const double*, int64_t, const int*, int64_t, int, double*, double*, hipStream_t);
+template void launch_eigs_coldot<cplx>(const cplx*, int64_t, const cplx*, int64_t, const int*, int64_t, int, double*, double*, hipStream_t);
+__global__ __launch_bounds__(256) void eigs_sqrt_kernel(double* d, int nc) {
+  const int c = threadIdx.x;
+  if (c >= nc) return;
+  const double v = gld(d + c);
+  gst(d + c, v > 0.0 ? sqrt(v) : 0.0);
+}
+void launch_eigs_sqrt(double* d, int nc, hipStream_t s) {
+  if (nc > 0) hipLaunchKernelGGL(eigs_sqrt_kernel, dim3(1), dim3(256), 0, s, d, nc);
+}
 
 // ---- eigs_scale, eigs_init ------------------------------------------------------------------------------------------------------------------
 template <class T>

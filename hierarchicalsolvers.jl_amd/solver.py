@@ -15,6 +15,7 @@ reference (Julia)                      here
 ``logabsdet(F)``, ``logdet``, ``det``  :func:`logabsdet`, :func:`logdet`, :func:`det` (``hs_selinv.hip``)
 selected inverse (no Julia name)       :func:`selinv`, :func:`selinv_diag`: ``diag(A^-1)`` and ``A^-1`` on the pattern of ``A``
 ``eigs(A; nev, sigma)`` (Arpack)       :func:`eigs`: the eigenpairs of ``A`` nearest ``sigma`` from the factors of ``A - sigma*I`` (``hs_eigs.hip``)
+``eigs(A, B; nev, sigma)`` (Arpack)    :func:`eigs` with ``M=B``: ``A x = lambda B x`` from the factors of ``A - sigma*B``
 ``F \\ b``                              ``F.solve(b)``
 =====================================  ====================================================
 
@@ -33,7 +34,7 @@ from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
            "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info",
-           "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "eigs", "eigs_info"]
+           "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "eigs", "eigs_info", "eigs_gen_info"]
 
 
 class SolverOptions:
@@ -577,7 +578,15 @@ def eigs_info():
             "replaced": int(out[5]), "workspace_bytes": int(out[6]), "ncv": int(out[7])}
 
 
-def eigs(F, nev=6, sigma=0.0, ncv=None, block=None, tol=1e-10, maxrestart=100, v0=None, seed=0, vectors=True, log=False):
+def eigs_gen_info():
+    """Figures of the generalized part of this thread's last :func:`eigs` call (``hs_eigs_gen_info``): products with ``op(M)``, the columns
+    they multiplied, the device bytes held for ``M``, and whether the ``op(M)`` inner product was used."""
+    out = np.zeros(4)
+    _lib.check(_lib.lib().hs_eigs_gen_info(_pf64(out)))
+    return {"m_products": int(out[0]), "m_columns": int(out[1]), "m_bytes": int(out[2]), "inner": "M" if out[3] else "euclid"}
+
+
+def eigs(F, nev=6, sigma=0.0, ncv=None, block=None, tol=1e-10, maxrestart=100, v0=None, seed=0, vectors=True, log=False, M=None, inner="euclid"):
     """The ``nev`` eigenvalues of ``A`` nearest ``sigma`` and their unit eigenvectors, from the factorization ``F`` of ``A - sigma*I``
     (``hs_eigs_*``): shift-invert block Arnoldi with thick restart, one block solve of ``block`` columns per step.  ``sigma`` is bookkeeping:
     the caller factors the shifted matrix.  ``F`` may be ``transpose(F)`` / ``adjoint(F)``: left eigenvectors (``y^T A = lambda y^T`` /
@@ -589,10 +598,33 @@ def eigs(F, nev=6, sigma=0.0, ncv=None, block=None, tol=1e-10, maxrestart=100, v
     iteration stopped on), ``restarts``, ``nsolves``, ``nconv``, ``seconds``, ``replaced`` (columns replaced after a rank deficiency).
     ``ncv`` (basis columns, ``ncv + block <= 256``), ``block`` (<= 64): None selects the defaults (16, and the multiple of ``block`` at or above
     ``max(2 nev + block, 4 block)``).  ``v0``: an ``n x block`` start block.  Fewer than the wanted pairs within ``tol`` after ``maxrestart``
-    restarts raises :class:`NoConvergence`, whose ``partial`` is the tuple that would have been returned (with the log)."""
+    restarts raises :class:`NoConvergence`, whose ``partial`` is the tuple that would have been returned (with the log).
+
+    ``M`` (any square ``scipy.sparse`` matrix of order ``n``, in the factored ordering) poses the generalized problem ``A x = lambda M x``
+    (``hs_eigs_gen_*``); ``F`` then factors ``A - sigma*M``.  ``M`` is only multiplied with: it may be singular (infinite eigenvalues are
+    never returned), non-symmetric, or wider than ``A``'s pattern.  ``transpose(F)`` / ``adjoint(F)`` solve the pencils ``(A^T, M^T)`` /
+    ``(A^H, M^H)``.  ``inner="euclid"``: vectors of unit 2-norm, ``est`` as without ``M``.  ``inner="M"`` (Hermitian positive definite
+    ``M``): the basis is ``M``-orthonormal, the vectors come back with ``x^H op(M) x = 1`` and ``est`` is measured in the ``M``-norm; an
+    ``M`` that is not positive on the start block is a ``ValueError``.  ``resid`` is ``||op(A_s) x - (lambda - sigma) op(M) x||_2`` in both
+    modes, and the log gains ``nmprod``, the products with ``op(M)``."""
     F, trans = _unwrap(F)
     n = F.n
     cx = F.dtype.kind == "c"
+    if inner not in ("euclid", "M"):
+        raise ValueError(f"ArgumentError: eigs: inner = {inner!r} (\"euclid\" or \"M\")")
+    Mc = mcolptr = mrowval = None
+    if M is not None:
+        if not sp.issparse(M):
+            raise TypeError(f"eigs: M must be a scipy.sparse matrix, got {type(M).__name__}")
+        if M.shape != (n, n):
+            raise _lib.DimensionMismatch(f"DimensionMismatch: eigs: M is {M.shape[0]} x {M.shape[1]}, F is {n} x {n}")
+        if not cx and M.dtype.kind == "c":
+            raise TypeError("MethodError: eigs: a ComplexF64 M for a FactorNode{Float64}")
+        Mc = sp.csc_matrix(M, dtype=F.dtype, copy=True)
+        Mc.sum_duplicates()
+        Mc.sort_indices()
+        mcolptr = np.ascontiguousarray(Mc.indptr, dtype=np.int64) + 1
+        mrowval = np.ascontiguousarray(Mc.indices, dtype=np.int64) + 1
     sigma = complex(sigma)
     if not cx and sigma.imag != 0.0:
         raise ValueError("ArgumentError: eigs: a complex shift on a Float64 factorization (factor A - sigma*I as ComplexF64)")
@@ -625,10 +657,14 @@ def eigs(F, nev=6, sigma=0.0, ncv=None, block=None, tol=1e-10, maxrestart=100, v
     X = np.zeros((n, nx), dtype=F.dtype, order="F") if vectors else None
     resid, est = np.zeros(nx), np.zeros(nx)
     nout, nconv = _lib.i64(), _lib.i64()
-    fn = getattr(_lib.lib(), "hs_eigs_z" if cx else "hs_eigs_d")
-    _lib.check(fn(F._h, trans, n, nev, int(ncv or 0), int(block or 0), sigma.real, sigma.imag, float(tol), int(maxrestart),
-                  V0.ctypes.data_as(C.c_void_p) if V0 is not None else None, max(n, 1), int(seed), 0, _pf64(lam),
-                  X.ctypes.data_as(C.c_void_p) if vectors else None, max(n, 1), _pf64(resid), _pf64(est), C.byref(nout), C.byref(nconv), None))
+    tail = (nev, int(ncv or 0), int(block or 0), sigma.real, sigma.imag, float(tol), int(maxrestart), V0.ctypes.data_as(C.c_void_p) if V0 is not None else None, max(n, 1),
+            int(seed), 0, _pf64(lam), X.ctypes.data_as(C.c_void_p) if vectors else None, max(n, 1), _pf64(resid), _pf64(est), C.byref(nout), C.byref(nconv), None)
+    if Mc is None:
+        _lib.check(getattr(_lib.lib(), "hs_eigs_z" if cx else "hs_eigs_d")(F._h, trans, n, *tail))
+    else:
+        mnz = np.ascontiguousarray(Mc.data, dtype=F.dtype)
+        _lib.check(getattr(_lib.lib(), "hs_eigs_gen_z" if cx else "hs_eigs_gen_d")(F._h, trans, n, mcolptr.ctypes.data_as(_lib.p_i64), mrowval.ctypes.data_as(_lib.p_i64),
+                                                                                  mnz.ctypes.data_as(C.c_void_p), 1 if inner == "M" else 0, *tail))
     k = int(nout.value)
     lamc = lam[0:2 * k:2] + 1j * lam[1:2 * k:2]
     Xo = X[:, :k] if vectors else None
@@ -650,7 +686,7 @@ def eigs(F, nev=6, sigma=0.0, ncv=None, block=None, tol=1e-10, maxrestart=100, v
     if log or nconv.value < k:
         info = eigs_info()
         res = res + ({"resid": resid[:k].copy(), "est": est[:k].copy(), "restarts": info["restarts"], "nsolves": info["block_solves"], "nconv": int(nconv.value),
-                      "seconds": info["seconds"], "replaced": info["replaced"], "ncv": info["ncv"]},)
+                      "seconds": info["seconds"], "replaced": info["replaced"], "ncv": info["ncv"], "nmprod": eigs_gen_info()["m_products"]},)
     if nconv.value < k:
         raise _lib.NoConvergence(f"eigs: {int(nconv.value)} of {k} eigenpairs within tol = {tol:g} after {res[2]['restarts']} restarts", partial=res)
     return res

@@ -207,12 +207,21 @@ int hsk_eigs_rotate_z(int64_t n, int64_t K, int64_t N, const double* V, int64_t 
 int hsk_eigs_chol_inv_d(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info);
 int hsk_eigs_chol_inv_z(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info);
 int hsk_small_eig_z(int64_t m, const double* H, int64_t ldh, double* w, double* Y, int64_t ldy);
+/* hsk_eigs_coldot: d[c] = Re sum_i conj(X[i, c]) Y[i, c] for the nc columns of two n x nc blocks (launch_eigs_coldot, the x^H op(M) x of
+ * hs_eigs_gen_*): row slabs of 2048, a thread adds its rows in order, partials fold by halves, slabs are added in slab order -- the bits of
+ * a slab do not depend on the rows behind it.  pair (nc ints, or NULL): 0 a column of its own; +1 / -1 the two columns of a Float64
+ * conjugate pair, which share one figure, the sum over both columns. */
+int hsk_eigs_coldot_d(int64_t n, int64_t nc, const double* X, int64_t ldx, const double* Y, int64_t ldy, const int* pair, double* d);
+int hsk_eigs_coldot_z(int64_t n, int64_t nc, const double* X, int64_t ldx, const double* Y, int64_t ldy, const int* pair, double* d);
 /* Host-clock seconds of this thread's last hs_eigs_* call by phase: out4 = {block solves, orthogonalisation, restarts (host eigenproblem
  * and basis rotation), Ritz vectors and residuals}.  The block solve is timed apart only while hsk_eigs_phase_timing is on (it adds one
  * stream synchronisation per block solve and changes no result; returns the previous setting); otherwise its time is counted with the
  * orthogonalisation that follows it. */
 int hsk_eigs_phase_timing(int on);
 int hsk_eigs_phases(double* out4);
+/* Host-clock seconds of the products with op(M) of this thread's last hs_eigs_gen_* call, taken only while hsk_eigs_phase_timing is on (it
+ * then puts a stream synchronisation before and behind every product); 0 otherwise.  They are part of the phases above they occur in. */
+double hsk_eigs_gen_mprod_seconds(void);
 
 /* Microseconds per ROUND TRIP (two exchanges) between workgroup 0 and workgroup `peer` of one launch through agent-scope atomic stores and polled
  * loads -- the exchange primitive of the dataflow sweeps of ldiv! (kernels_solve_wide.hip).  peer = 1: another XCD, peer = 8: the same XCD. */

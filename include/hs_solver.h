@@ -369,6 +369,37 @@ int hs_eigs_z(hs_handle* F, int trans, int64_t n, int64_t nev, int64_t ncv, int6
               const double* V0, int64_t ldv0, int64_t seed, int where, double* lam, double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv,
               void* stream);
 int hs_eigs_info(double* out8);
+/* The generalized problem A x = lambda M x from the factors of A_s = A - sigma M (the caller forms and factors the shifted pencil; sigma is
+ * bookkeeping as above).  M: host CSC arrays (SparseMatrixCSC fields, 1-based; mnzval interleaved complex in _z) in the factored ordering
+ * -- the rows and columns the caller gave the factorization; it is only multiplied with, so it may be singular, non-symmetric or have
+ * entries outside A's pattern.  `where` concerns V0 and X alone.  All three arrays NULL: M = I, the call is hs_eigs_* (which are this
+ * call with M = NULL) bit for bit.  The call returns the nev eigenvalues of the pencil (A, M) nearest sigma: theta the eigenvalues of
+ * largest modulus of op(F)^-1 op(M), mu = 1 / theta, lambda = sigma + mu; an infinite eigenvalue is theta = 0 and never selected.
+ *   trans     0: A x = lambda M x.  1: the pencil (A^T, M^T), y^T A = lambda y^T M.  2: (A^H, M^H), returns conj(lambda).
+ *   inner     0: the Euclidean inner product.  An expansion forms T = op(M) V[:, m:m+p] and solves from T; vectors have unit 2-norm, est and
+ *             the stopping test are those of hs_eigs_*.
+ *             1: the op(M) inner product, for Hermitian positive definite M: every inner product of the Gram-Schmidt and CholQR passes is
+ *             taken against MW = op(M) W, recomputed by one SpMM after every correction of W (never updated: one summation order per
+ *             element); the basis is M-orthonormal, a Hermitian pencil gives a Hermitian projected matrix, the vectors come back with
+ *             x^H op(M) x = 1 (a Float64 pair scaled as the complex vector it stands for), est is an M-norm quantity:
+ *             ||B y||_2 / |theta| is the M-norm of the residual of the Ritz pair of op(F)^-1 op(M).  The rank-deficiency rule applies to
+ *             the M-Gram matrix.  A Gram diagonal entry of the start block that is not positive: M is not positive definite on it,
+ *             HS_ERR_ARGUMENT.  With M = NULL inner = 1 is the Euclidean run.
+ *   resid     ||op(A_s) x - mu op(M) x||_2 with the handle's own A_s, in both modes.
+ * HS_ERR_ARGUMENT in addition to hs_eigs_*: inner outside 0..1; one or two of the three M arrays; mcolptr[0] != 1 or not monotone; a row
+ * index outside 1..n; n beyond 32-bit indices -- all found with the other argument checks, before the handle's own refusals (which are
+ * those of hs_eigs_*, in the same order and words) and before anything is written.  Workspace beyond hs_eigs_*: (block + nev + 1) n
+ * elements (T and op(M) X), (2 block + nev + 1) n with inner = 1 (MW), and M on the device (CSR for trans = 0, the CSC arrays read in
+ * place as rows of op(M) otherwise; uploaded once per call).
+ * hs_eigs_gen_info: out4 = {products with op(M), columns multiplied, device bytes held for M, inner used} of this thread's last
+ * hs_eigs_gen_* / hs_eigs_* call. */
+int hs_eigs_gen_d(hs_handle* F, int trans, int64_t n, const int64_t* mcolptr, const int64_t* mrowval, const double* mnzval, int inner, int64_t nev, int64_t ncv,
+                  int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const double* V0, int64_t ldv0, int64_t seed, int where, double* lam,
+                  double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv, void* stream);
+int hs_eigs_gen_z(hs_handle* F, int trans, int64_t n, const int64_t* mcolptr, const int64_t* mrowval, const double* mnzval, int inner, int64_t nev, int64_t ncv,
+                  int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const double* V0, int64_t ldv0, int64_t seed, int where, double* lam,
+                  double* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv, void* stream);
+int hs_eigs_gen_info(double* out4);
 
 /* ---- accuracy tools: norm and condition estimates, refined solves with error bounds (hs_condest.hip) --------------------------
  * opnorm(A, 1), opnorm(A, Inf) of the handle's A (the values of the last hs_numeric_begin); p = 1 or 0 (= Inf).  The first call that needs
