@@ -4,7 +4,7 @@
 //
 // The Higham-Tisseur estimator is est_run of hs_normest.h, shared with hs_refine_block.hip: here it runs a single estimator (ne = 1) whose
 // application of op(F)^-1 is one hs_ldiv_dev_t_* call on its t columns -- <8> for hs_normestinv and hs_condest, <2> on diag(v) op(F)^-H for
-// ferr.  Every n-vector operation is a kernel; the host reads a few scalars per half-step (like hs_gmres.hip) and checks the dataflow-sweep
+// ferr.  Every n-vector operation is a kernel; the host reads a few scalars per half-step (like hs_gmres_block.hip) and checks the dataflow-sweep
 // error flag after every synchronisation, so a timed-out sweep becomes an error and never an estimate.
 //
 // Determinism: the estimator's is stated in hs_normest.h; the residual, the weights and the norms here are per-workgroup partials in LDS and

@@ -1,11 +1,21 @@
-// hs_gmres_block.hip -- right-preconditioned restarted GMRES on a block of right-hand sides in lockstep (hs_gmres_block_*, include/hs_solver.h).
+// hs_gmres_block.hip -- right-preconditioned restarted GMRES behind the C ABI (include/hs_solver.h), every vector on the device: one
+// right-hand side (hs_gmres_*, hs_gmres_t_*) or a block of them in lockstep (hs_gmres_block_*), on one driver.
+//
+// Reference scenario (test/rungmres.jl:47-48):  x, ch = gmres(A, b; Pr=F, reltol=1e-9, restart=30, log=true, maxiter=30)
+// IterativeSolvers.jl (0.9.0) is not part of the reference tree: the algorithm is the textbook one (Saad & Schultz 1986; Arnoldi with
+// classical Gram-Schmidt + one re-orthogonalisation pass, Givens rotations on the Hessenberg matrix, right preconditioning
+// x = x0 + Pr^-1 V y) and matches the Python mirror tests/gmres_mirror.py step for step (same iteration counts).
+// PARITY UNPINNED against the Julia package.
 //
 // nrhs independent Arnoldi processes advance together: every column keeps its own Krylov space, Hessenberg matrix, rotations and stopping
-// test, exactly the iteration of hs_gmres.hip (classical Gram-Schmidt with one re-orthogonalisation pass, Givens rotations,
-// x = x0 + Pr^-1 V y), but a step applies the preconditioner to all active columns with ONE hs_ldiv_block_dev_* call (the factors are read
+// test, but a step applies the preconditioner to all active columns with ONE hs_ldiv_block_dev_* call (the factors are read
 // once per 32 columns, not once per column), multiplies by A with ONE CSR SpMM, runs the orthogonalisations as batched kernels (column =
-// blockIdx.y) and reads 2 nact doubles to the host with one synchronisation.  This is not block-Krylov: a column returns what hs_gmres_*
-// returns for it alone (to the rounding by which hs_ldiv_block_* and hs_ldiv_* differ).
+// blockIdx.y; all HBM-bound n-vector kernels, the Hessenberg / Givens recurrences and the triangular solve one thread per column on
+// device-resident H, c, s, g) and reads 2 nact doubles (||w|| and the residual estimate per column) to the host with one synchronisation:
+// a preconditioner application costs three orders of magnitude more than that read, and an iteration that is not needed costs a whole
+// `ldiv!`.  This is not block-Krylov.  hs_gmres_* is the same driver on one column in a group of width 1, with the single-right-hand-side
+// solve hs_ldiv_dev_* as the preconditioner call (which also serves the handles the block solve refuses): a column of a block returns what
+// hs_gmres_* returns for it alone, to the rounding by which hs_ldiv_block_* and hs_ldiv_* differ, and the same bits without a preconditioner.
 //
 // Layout: every n x nact object is a column-major block with leading dimension ldv (n rounded up to an even value); the basis is
 // V[(j G + c) ldv + i] (G: group width), so V_j is directly the dB argument of hs_ldiv_block_dev_*.  A column that converges, breaks down or
@@ -16,10 +26,12 @@
 // Determinism: no atomics, every reduction in a fixed order that depends on the row index alone, so a column's results do not depend on its
 // slot, on the other columns, on G or on compaction.
 //
-// hs_gmres_block_t_* runs the same schedule on op(A) X = B right-preconditioned by op(Pr): gmres_group is a template on the operator (the CSR
-// SpMM below, or the SpMM over "entry ranges as rows" of hs_gmres_common.h) and on the preconditioner call (hs_ldiv_block_dev_* /
-// hs_ldiv_block_dev_t_*); A is passed as host CSC arrays or is the handle's own (hs_gmres_op.h).  hs_gmres_block_mod_* is one more pair of
+// hs_gmres_t_* / hs_gmres_block_t_* run the same schedule on op(A) X = B right-preconditioned by op(Pr): gmres_group is a template on the
+// operator (the CSR SpMM below, or the SpMM over "entry ranges as rows" of hs_gmres_common.h) and on the preconditioner call (hs_ldiv_dev_* /
+// hs_ldiv_dev_t_* for one column, hs_ldiv_block_dev_* / hs_ldiv_block_dev_t_* for a block); A is passed as host CSC arrays or is the
+// handle's own (hs_gmres_op.h).  hs_gmres_block_mod_* is one more pair of
 // instantiations: op(A1) X = B with A1 = A + U V^H as host CSC arrays, the preconditioner call hs_mod_ldiv_dev_* (hs_mod.hip).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -36,7 +48,7 @@ namespace {
 // A workgroup owns 256 rows and walks the columns CB at a time, lanes along rows: X[:, c] and Y[:, c] are read and written contiguously, and
 // rowptr / colind / val of the row tile are read once per chunk of CB columns, not once per column (the chunks after the first follow it in
 // the same workgroup and should find them in L2; that is not measured).  Per (row, column) the sum runs over e in
-// stored order with Scal<T>::fma, as the single-vector product of hs_gmres.hip (spmv_op_kernel) does.
+// stored order with Scal<T>::fma; with one column (hs_gmres_*) this is the one-thread-per-row product.
 // The kernel is spmm_op_kernel<T, CB, false> (hs_gmres_common.h): a CSR is the plain case of its "entry ranges as rows".
 template <class T>
 void launch_spmm(const int64_t* rowptr, const int32_t* colind, const T* val, const T* X, int64_t ldx, const int64_t* xmap, T* Y, int64_t ldy, const T* B, int64_t ldb,
@@ -45,7 +57,7 @@ void launch_spmm(const int64_t* rowptr, const int32_t* colind, const T* val, con
   hipLaunchKernelGGL((spmm_op_kernel<T, CB, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rowptr, colind, val, X, ldx, xmap, Y, ldy, B, ldb, bmap, n, nc);
 }
 
-// The batched forms of the kernels of hs_gmres.hip: the column (slot) is blockIdx.y, a frozen column (mask[c] == 0) is skipped.
+// The kernels of the iteration: the column (slot) is blockIdx.y, a frozen column (mask[c] == 0) is skipped.
 // part[(c nblk + blockIdx.x) k1 + j] = sum over the block's 1024 rows of conj(V_j[i, c]) W[i, c],  j = 0..k;  w stays in registers
 template <class T>
 __global__ __launch_bounds__(256) void bdot_kernel(const T* __restrict__ V, int64_t ldv, int64_t jstride, int k1, const T* __restrict__ W, T* __restrict__ part, int64_t n,
@@ -135,7 +147,7 @@ __global__ __launch_bounds__(256) void bcombine_kernel(const T* __restrict__ V, 
   for (int j = 0; j < k; ++j) acc = Scal<T>::fma(sh[j], Vc[(size_t)j * jstride + i], acc);
   dst[i] = acc;
 }
-// X[:, xmap[c]] += Z[:, c]   (the preconditioned update; what combine_kernel of hs_gmres.hip computes with y = 1)
+// X[:, xmap[c]] += Z[:, c]   (the preconditioned update, as one fma with 1)
 template <class T>
 __global__ __launch_bounds__(256) void badd_kernel(const T* __restrict__ Z, int64_t ldz, T* __restrict__ X, int64_t ldx, const int64_t* __restrict__ xmap, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -211,8 +223,8 @@ struct GbSmall {
   int64_t* col;   // slot -> column of the caller's B / X
   int ld, sH, s1, s2;  // strides: H, (m+1)-arrays, (m+2)-arrays
 };
-// one thread per slot: the rotations of givens_kernel (hs_gmres.hip) on the slot's own state, then the freezing decision the host repeats from
-// the same two doubles
+// one thread per slot: applies the previous rotations to column k of the slot's H, creates the one that annihilates H[k+1, k] and updates g,
+// then takes the freezing decision the host repeats from the same two doubles
 template <class T>
 __global__ __launch_bounds__(64) void bgivens_kernel(GbSmall<T> S, int k, int nact) {
   const int c = blockIdx.x * 64 + threadIdx.x;
@@ -341,7 +353,27 @@ struct PrecBlockOp {  // hs_ldiv_block_dev_t_*: op(F)
   int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return prec_block_t<T>(F, trans, out, in, ld, n, nc, s); }
 };
 
-// figures of the calling thread's last hs_gmres_block_* call (hs_gmres_block_info)
+// hs_gmres_* / hs_gmres_t_*: the single-right-hand-side solves, which also serve the handles the block solve refuses (their columns are
+// solved one after the other: a group of width 1 hands them one)
+template <class T>
+struct PrecFwd {  // hs_ldiv_dev_*
+  hs_handle* F;
+  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const {
+    if constexpr (sizeof(T) == 16) return hs_ldiv_dev_z(F, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
+    else return hs_ldiv_dev_d(F, out, ld, in, ld, n, nc, (void*)s);
+  }
+};
+template <class T>
+struct PrecOp {  // hs_ldiv_dev_t_*: op(F)
+  hs_handle* F;
+  int trans;
+  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const {
+    if constexpr (sizeof(T) == 16) return hs_ldiv_dev_t_z(F, trans, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
+    else return hs_ldiv_dev_t_d(F, trans, out, ld, in, ld, n, nc, (void*)s);
+  }
+};
+
+// figures of the calling thread's last hs_gmres_block_* call (hs_gmres_block_info); a run counts into the array its caller gives it
 enum { GI_SECONDS = 0, GI_PREC_CALLS, GI_COL_APPS, GI_SPMM, GI_CYCLES, GI_GROUPS, GI_WORK_BYTES, GI_MAX_ACTIVE };
 thread_local double g_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -372,7 +404,7 @@ size_t bytes_per_column(int64_t n, int m) {
 // one group of gc <= G columns (g0 .. g0 + gc of the caller's B and X, device pointers) from start to finish
 template <class T, class Op, class Prec>
 void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t g0, int gc, int use_x0, double reltol, double abstol,
-                 int64_t maxiter, Workspace<T>& ws, Column* cols, hipStream_t s) {
+                 int64_t maxiter, Workspace<T>& ws, Column* cols, double* info, hipStream_t s) {
   hs_handle* const F = Pr.F;
   const int m = ws.m, nblk = ws.nblk;
   const int64_t ldv = ws.ldv, jstride = ws.G * ldv;
@@ -392,7 +424,7 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
   };
   auto residual = [&](int nc) {  // R[:, c] = B[:, col[c]] - A X[:, col[c]]
     A((const T*)X, ldx, (const int64_t*)S.col, ws.R, ldv, B, ldb, (const int64_t*)S.col, n, nc, s);
-    g_info[GI_SPMM] += 1;
+    info[GI_SPMM] += 1;
   };
   // r0 = b - A x0, slots in the order of the columns
   for (int c = 0; c < gc; ++c) hcol[(size_t)c] = g0 + c;
@@ -447,8 +479,8 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
     GM_HIP(hipMemcpyAsync(S.tol, htol.data(), sizeof(double) * (size_t)nact, hipMemcpyHostToDevice, s));
     GM_HIP(hipMemcpyAsync(S.itleft, hleft.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
     GM_HIP(hipStreamSynchronize(s));  // the host arrays are reused
-    g_info[GI_CYCLES] += 1;
-    g_info[GI_MAX_ACTIVE] = std::max(g_info[GI_MAX_ACTIVE], (double)nact);
+    info[GI_CYCLES] += 1;
+    info[GI_MAX_ACTIVE] = std::max(info[GI_MAX_ACTIVE], (double)nact);
     const unsigned gs = (unsigned)((nact + 63) / 64);
     hipLaunchKernelGGL(bscale_into_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.R, ldv, (const double*)S.beta, 1, ws.V, ldv, n, (const int*)nullptr);
     hipLaunchKernelGGL(breset_kernel<T>, dim3(gs), dim3(64), 0, s, S, m, nact);
@@ -459,12 +491,12 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
       if (F) {
         const int st = Pr(ws.Z, Vk, ldv, n, nact, s);
         if (st != 0) throw st;
-        g_info[GI_PREC_CALLS] += 1;
-        g_info[GI_COL_APPS] += nact;
+        info[GI_PREC_CALLS] += 1;
+        info[GI_COL_APPS] += nact;
         zz = ws.Z;
       }
       A(zz, ldv, (const int64_t*)nullptr, ws.W, ldv, (const T*)nullptr, (int64_t)0, (const int64_t*)nullptr, n, nact, s);
-      g_info[GI_SPMM] += 1;
+      info[GI_SPMM] += 1;
       // classical Gram-Schmidt with one re-orthogonalisation pass, per column: h = V^H w; w -= V h; h2 = V^H w; w -= V h2; H[:, k] = h + h2
       const int k1 = k + 1;
       const int* mask = S.mask;
@@ -498,8 +530,8 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
                          (const int64_t*)nullptr, ws.W, ldv, n);
       const int st = Pr(ws.Z, ws.W, ldv, n, nact, s);
       if (st != 0) throw st;
-      g_info[GI_PREC_CALLS] += 1;
-      g_info[GI_COL_APPS] += nact;
+      info[GI_PREC_CALLS] += 1;
+      info[GI_COL_APPS] += nact;
       hipLaunchKernelGGL(badd_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.Z, ldv, X, ldx, (const int64_t*)S.col, n);
     } else {
       hipLaunchKernelGGL(bcombine_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.V, ldv, jstride, (const T*)S.y, S.s1, (const int*)S.kused, X, ldx,
@@ -543,6 +575,24 @@ int refused_by_block_solve(hs_handle* F, int trans, int64_t n) {  // zero column
   return sizeof(T) == 16 ? hs_ldiv_block_dev_t_z(F, trans, nullptr, n, nullptr, n, n, 0, nullptr) : hs_ldiv_block_dev_t_d(F, trans, nullptr, n, nullptr, n, n, 0, nullptr);
 }
 
+// the dimension test and the defaults every GMRES entry point applies after its own argument checks
+template <class T>
+int gmres_defaults(hs_handle* F, int64_t n, int64_t* restart, int64_t* maxiter, double* reltol) {
+  if (F && (hs_size(F) != n || (hs_is_complex(F) != 0) != (sizeof(T) == 16))) {
+    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld", (long long)hs_size(F), (long long)hs_size(F),
+                 hs_is_complex(F) ? "ComplexF64" : "Float64", (long long)n, (long long)n);
+    return HS_ERR_DIMENSION;
+  }
+  // defaults of IterativeSolvers 0.9: restart = min(20, n), maxiter = n, reltol = sqrt(eps)
+  if (*restart <= 0) *restart = std::min<int64_t>(20, n);
+  if (*restart > GM_MAXK) {
+    hs_set_error(HS_ERR_ARGUMENT, *restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)*restart, GM_MAXK);
+    return HS_ERR_ARGUMENT;
+  }
+  if (*maxiter < 0) *maxiter = n;
+  if (!(*reltol >= 0.0)) *reltol = 1.4901161193847656e-08;
+  return HS_OK;
+}
 // the checks and defaults hs_gmres_block_* and hs_gmres_block_t_* share (A and nrhs = 0 apart)
 template <class T>
 int gmres_block_check(hs_handle* F, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int where, int64_t* restart, int64_t* maxiter, double* reltol, int64_t* iters,
@@ -559,26 +609,14 @@ int gmres_block_check(hs_handle* F, int64_t n, const T* B, int64_t ldb, T* X, in
     hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block: ldb = %lld, ldx = %lld below n = %lld", (long long)ldb, (long long)ldx, (long long)n);
     return HS_ERR_ARGUMENT;
   }
-  if (F && (hs_size(F) != n || (hs_is_complex(F) != 0) != (sizeof(T) == 16))) {
-    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld", (long long)hs_size(F), (long long)hs_size(F),
-                 hs_is_complex(F) ? "ComplexF64" : "Float64", (long long)n, (long long)n);
-    return HS_ERR_DIMENSION;
-  }
-  // defaults of IterativeSolvers 0.9, as hs_gmres_*
-  if (*restart <= 0) *restart = std::min<int64_t>(20, n);
-  if (*restart > GM_MAXK) {
-    hs_set_error(HS_ERR_ARGUMENT, *restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)*restart, GM_MAXK);
-    return HS_ERR_ARGUMENT;
-  }
-  if (*maxiter < 0) *maxiter = n;
-  if (!(*reltol >= 0.0)) *reltol = 1.4901161193847656e-08;
-  return HS_OK;
+  return gmres_defaults<T>(F, n, restart, maxiter, reltol);
 }
 
-// from the device check to the results; make_op(buf, s) puts A on the device (or finds it there) and returns the operator
-template <class T, class MakeOp, class Prec>
-int gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol,
-                    int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+// Every GMRES entry point from the device check to the results.  make_op(buf, s) puts A on the device (or finds it there) and returns the
+// operator; width(bytes per column) is the group width the caller wants, asked after the device check; info receives the eight figures.
+template <class T, class MakeOp, class Prec, class Width>
+int gmres_run(MakeOp make_op, const Prec& Pr, Width width, double* info, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where, int use_x0,
+              double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
   int cnt = 0;
   if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
     hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
@@ -588,7 +626,7 @@ int gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64
   int rc = HS_OK;
   DevBuf buf;  // outlives the try block: after a throw the stream is drained below before the workspace is freed
   try {
-    for (double& v : g_info) v = 0.0;
+    std::fill(info, info + 8, 0.0);
     hipStream_t s = (hipStream_t)stream;
     const auto A = make_op(buf, s);
     const T* dB = B;
@@ -606,17 +644,18 @@ int gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64
     const int m = (int)restart;
     Workspace<T> ws;
     const size_t per_col = bytes_per_column<T>(n, m);
-    ws.G = std::min<int64_t>(group_width(per_col, nrhs), nrhs);
+    ws.G = std::min<int64_t>(width(per_col), nrhs);
     ws.m = m;
     ws.ldv = (n + 1) / 2 * 2;
     ws.nblk = (int)((n + 1023) / 1024);
     const size_t G = (size_t)ws.G, blk = G * (size_t)ws.ldv;
-    T* big = buf.get<T>((size_t)(m + 5) * blk);
+    const size_t nvec = (size_t)m + (G > 1 ? 5 : 4);  // R2 serves compaction, which one column never sees
+    T* big = buf.get<T>(nvec * blk);
     ws.V = big;
     ws.W = big + (size_t)(m + 1) * blk;
     ws.Z = ws.W + blk;
     ws.R = ws.Z + blk;
-    ws.R2 = ws.R + blk;
+    ws.R2 = G > 1 ? ws.R + blk : nullptr;
     ws.part = buf.get<T>(G * ws.nblk * (m + 2));
     ws.dpart = buf.get<double>(G * ws.nblk);
     ws.src = buf.get<int>(G);
@@ -639,23 +678,23 @@ int gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64
     S.mask = buf.get<int>(G);
     S.kused = buf.get<int>(G);
     S.col = buf.get<int64_t>(G);
-    g_info[GI_WORK_BYTES] = (double)(per_col * G);
+    info[GI_WORK_BYTES] = (double)(per_col * G - ((size_t)m + 5 - nvec) * blk * sizeof(T));
     GM_HIP(hipEventCreate(&e0));
     GM_HIP(hipEventCreate(&e1));
     GM_HIP(hipEventRecord(e0, s));
     // a frozen column's basis vectors still travel through the block solve: they must be finite from the first step on
-    GM_HIP(hipMemsetAsync(big, 0, sizeof(T) * (size_t)(m + 5) * blk, s));
+    GM_HIP(hipMemsetAsync(big, 0, sizeof(T) * nvec * blk, s));
     std::vector<Column> cols((size_t)nrhs);
     for (int64_t g0 = 0; g0 < nrhs; g0 += ws.G) {
       const int gc = (int)std::min<int64_t>(ws.G, nrhs - g0);
-      gmres_group<T>(A, Pr, n, dB, dldb, dX, dldx, g0, gc, use_x0, reltol, abstol, maxiter, ws, cols.data() + g0, s);
-      g_info[GI_GROUPS] += 1;
+      gmres_group<T>(A, Pr, n, dB, dldb, dX, dldx, g0, gc, use_x0, reltol, abstol, maxiter, ws, cols.data() + g0, info, s);
+      info[GI_GROUPS] += 1;
     }
     GM_HIP(hipEventRecord(e1, s));
     GM_HIP(hipEventSynchronize(e1));
     float ms = 0.f;
     GM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    g_info[GI_SECONDS] = ms * 1e-3;
+    info[GI_SECONDS] = ms * 1e-3;
     if (where == 0) GM_HIP(hipMemcpy2D(X, sizeof(T) * (size_t)ldx, dX, sizeof(T) * (size_t)n, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyDeviceToHost));
     for (int64_t c = 0; c < nrhs; ++c) {
       const Column& q = cols[(size_t)c];
@@ -674,6 +713,67 @@ int gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
   return rc;
+}
+
+// hs_gmres_block_*: groups as wide as the free device memory allows, the figures for hs_gmres_block_info
+template <class T, class MakeOp, class Prec>
+int gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol,
+                    int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_run<T>(make_op, Pr, [nrhs](size_t per_col) { return group_width(per_col, nrhs); }, g_info, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
+                      maxiter, resnorm, iters, converged, stream);
+}
+// hs_gmres_* / hs_gmres_t_*: one column in a group of width 1; the figures are nobody's
+template <class T, class MakeOp, class Prec>
+int gmres_one_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* b, T* x, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
+                  double* resnorm, int64_t* iters, int* converged, void* stream) {
+  double unused[8];
+  return gmres_run<T>(make_op, Pr, [](size_t) { return (int64_t)1; }, unused, n, b, n, x, n, (int64_t)1, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters,
+                      converged, stream);
+}
+
+// the CSR upload of the caller's CSC arrays as the operator
+template <class T>
+auto csr_op_of(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz) {
+  return [=](DevBuf& buf, hipStream_t) {
+    int64_t* d_rp;
+    int32_t* d_ci;
+    T* d_v;
+    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+    return CsrSpmm<T>{d_rp, d_ci, d_v};
+  };
+}
+
+template <class T>
+int gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol, double abstol,
+                int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  if (n <= 0 || !colptr || !rowval || !nz || !b || !x || !iters || !converged) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres needs A (CSC), b, x and the two result slots");
+    return HS_ERR_ARGUMENT;
+  }
+  if (const int st = gmres_defaults<T>(F, n, &restart, &maxiter, &reltol)) return st;
+  return gmres_one_run<T>(csr_op_of<T>(n, colptr, rowval, nz), PrecFwd<T>{F}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+
+// hs_gmres_t_*: op(A) x = b right-preconditioned by op(Pr); A explicit or the handle's own
+template <class T>
+int gmres_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol,
+                  double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  bool own = false;
+  if (const int st = gm_check_op_args("hs_gmres_t_*", F, trans, colptr, rowval, nz, &own)) return st;
+  if (trans == 0 && !own) return gmres_entry<T>(F, n, colptr, rowval, nz, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  if (n <= 0 || !b || !x || !iters || !converged) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_t needs n >= 1, b, x and the two result slots");
+    return HS_ERR_ARGUMENT;
+  }
+  if (const int st = gmres_defaults<T>(F, n, &restart, &maxiter, &reltol)) return st;
+  if (own)
+    if (const int st = hs_gmres_own_check(F, "hs_gmres_t_*", 1)) return st;
+  if (F)  // what hs_ldiv_t_* refuses (or an unfactored handle) is refused here, before any device work: zero columns are solved
+    if (const int st = PrecOp<T>{F, trans}((T*)nullptr, (const T*)nullptr, n, n, 0, nullptr)) return st;
+  if (own)
+    if (const int st = hs_gmres_own_check(F, "hs_gmres_t_*", 0)) return st;
+  auto make_op = [&](DevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
+  return gmres_one_run<T>(make_op, PrecOp<T>{F, trans}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
 template <class T>
@@ -698,14 +798,8 @@ int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int6
     }
     if (st != 0) return st;
   }
-  auto make_op = [&](DevBuf& buf, hipStream_t) {
-    int64_t* d_rp;
-    int32_t* d_ci;
-    T* d_v;
-    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
-    return CsrSpmm<T>{d_rp, d_ci, d_v};
-  };
-  return gmres_block_run<T>(make_op, PrecBlockFwd<T>{F}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  return gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), PrecBlockFwd<T>{F}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters,
+                            converged, stream);
 }
 
 // hs_gmres_block_t_*: op(A) X = B right-preconditioned by op(Pr); A explicit or the handle's own
@@ -774,16 +868,9 @@ int gmres_block_mod_entry(hs_mod* M, int trans, int64_t n, const int64_t* colptr
   hs_handle* F = hs_mod_handle(M);
   if (const int st = gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
   const PrecBlockMod<T> Pr{F, M, trans};
-  if (trans == 0) {
-    auto make_op = [&](DevBuf& buf, hipStream_t) {
-      int64_t* d_rp;
-      int32_t* d_ci;
-      T* d_v;
-      upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
-      return CsrSpmm<T>{d_rp, d_ci, d_v};
-    };
-    return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
-  }
+  if (trans == 0)
+    return gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                              stream);
   auto make_op = [&](DevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, false, n, colptr, rowval, nz, s)}; };
   return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
@@ -871,6 +958,24 @@ int spmm_op_hook(int trans, int64_t n, const int64_t* colptr, const int64_t* row
 
 }  // namespace
 
+extern "C" int hs_gmres_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
+                          double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_entry<double>(Pr, n, colptr, rowval, nzval, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+extern "C" int hs_gmres_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
+                          double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_entry<cplx>(Pr, n, colptr, rowval, (const cplx*)nzval, (const cplx*)b, (cplx*)x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                           stream);
+}
+extern "C" int hs_gmres_t_d(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where,
+                            int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_t_entry<double>(Pr, trans, n, colptr, rowval, nzval, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+extern "C" int hs_gmres_t_z(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where,
+                            int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_t_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)b, (cplx*)x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters,
+                             converged, stream);
+}
 extern "C" int hs_gmres_block_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
                                 int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
                                 int64_t* iters, int* converged, void* stream) {

@@ -1,7 +1,7 @@
-// hs_gmres_common.h -- what the two GMRES drivers share (hs_gmres.hip: one vector, hs_gmres_block.hip: a block in lockstep): the restart
-// limit, the scalar helpers of the kernels, the device-buffer holder, the CSC -> CSR upload, and what the hs_gmres_t_* / hs_gmres_block_t_*
-// calls add: the products with op(A) over "entry ranges as rows", the 0-based CSC upload and the checks of their arguments.  Everything has
-// internal linkage.
+// hs_gmres_common.h -- what the GMRES driver (hs_gmres_block.hip: hs_gmres_* and hs_gmres_block_*) shares with the other Krylov code
+// (hs_eigs.hip): the restart limit, the scalar helpers of the kernels, the device-buffer holder, the CSC -> CSR upload, and what the
+// hs_gmres_t_* / hs_gmres_block_t_* calls add: the product with op(A) over "entry ranges as rows", the 0-based CSC upload and the checks of
+// their arguments.  Everything has internal linkage.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -124,19 +124,8 @@ __device__ inline T opval_(T a) {
   if constexpr (CJ) return conj_(a);
   return a;
 }
-// y = op(A) x, or y = b - op(A) x with b; one thread per row, the sum over the stored entries in order.  CJ = false on a
-// CSR is the product of hs_gmres_*.
-template <class T, bool CJ>
-__global__ __launch_bounds__(256) void spmv_op_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const T* __restrict__ val,
-                                                      const T* __restrict__ x, T* __restrict__ y, const T* __restrict__ b, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  T acc = Scal<T>::zero();
-  for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) acc = Scal<T>::fma(opval_<CJ>(val[e]), x[idx[e]], acc);
-  y[i] = b ? b[i] - acc : acc;
-}
 // Y[:, c] = op(A) X[:, xmap[c]]   or, with B,   Y[:, c] = B[:, bmap[c]] - op(A) X[:, xmap[c]]   (null map: identity), c < nc.  CJ = false on a
-// CSR is the product of hs_gmres_block_* (launch_spmm, hs_gmres_block.hip).  256 rows per workgroup, lanes along rows, CB columns of accumulators in registers, the row's
+// CSR is the product of hs_gmres_* and hs_gmres_block_* (launch_spmm, hs_gmres_block.hip).  256 rows per workgroup, lanes along rows, CB columns of accumulators in registers, the row's
 // entries read once per chunk of CB columns; per (row, column) the sum runs over the stored entries in order with Scal<T>::fma.
 template <class T, int CB, bool CJ>
 __global__ __launch_bounds__(256) void spmm_op_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, const T* __restrict__ val,
@@ -166,16 +155,6 @@ __global__ __launch_bounds__(256) void spmm_op_kernel(const int64_t* __restrict_
       if (cc < nc) Y[(size_t)cc * ldy + i] = B ? B[(size_t)(bmap ? bmap[cc] : cc) * ldb + i] - acc[c] : acc[c];
     }
   }
-}
-template <class T>
-void launch_spmv_op(const RowsOf<T>& A, const T* x, T* y, const T* b, int64_t n, hipStream_t s) {
-  const dim3 g((unsigned)((n + 255) / 256));
-  if constexpr (sizeof(T) == 16)  // Float64: the adjoint is the transpose
-    if (A.conj) {
-      hipLaunchKernelGGL((spmv_op_kernel<T, true>), g, dim3(256), 0, s, A.ptr, A.idx, A.val, x, y, b, n);
-      return;
-    }
-  hipLaunchKernelGGL((spmv_op_kernel<T, false>), g, dim3(256), 0, s, A.ptr, A.idx, A.val, x, y, b, n);
 }
 template <class T>
 void launch_spmm_op(const RowsOf<T>& A, const T* X, int64_t ldx, const int64_t* xmap, T* Y, int64_t ldy, const T* B, int64_t ldb, const int64_t* bmap, int64_t n, int nc,

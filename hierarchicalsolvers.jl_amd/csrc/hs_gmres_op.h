@@ -1,6 +1,6 @@
-// hs_gmres_op.h -- the handle's own A as the GMRES drivers read it (hs_gmres_t_*, hs_gmres_block_t_* with colptr = rowval = nzval = NULL).
-// Plain declarations: hs_gmres.hip and hs_gmres_block.hip do not include hs_condest.h, whose kernel section switches floating-point
-// contraction off for the rest of the including file; hs_gmres_op.hip is the one translation unit that reaches hs_ce::csr_of for them.
+// hs_gmres_op.h -- the handle's own A as the GMRES driver reads it (hs_gmres_t_*, hs_gmres_block_t_* with colptr = rowval = nzval = NULL).
+// Plain declarations: hs_gmres_block.hip does not include hs_condest.h, whose kernel section switches floating-point
+// contraction off for the rest of the including file; hs_gmres_op.hip is the one translation unit that reaches hs_ce::csr_of for it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

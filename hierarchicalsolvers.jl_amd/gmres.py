@@ -5,8 +5,9 @@ The call the reference's scenario makes (``test/rungmres.jl:47-48``)::
     x, ch = gmres(A, b; Pr=F, reltol=1e-9, restart=30, log=true, maxiter=30)
 
 ``IterativeSolvers.gmres`` (0.9.0, not part of the reference tree) uses the preconditioner only through ``ldiv!``.  ``gmres`` here is
-``hs_gmres_{d,z}`` of the C ABI (include/hs_solver.h, csrc/hs_gmres.hip): hand-written CSR SpMV, Gram-Schmidt and Givens kernels, the
-preconditioner applied through ``hs_ldiv_dev_*`` on device pointers -- what a Julia host calls instead of ``IterativeSolvers.gmres``.
+``hs_gmres_{d,z}`` of the C ABI (include/hs_solver.h, csrc/hs_gmres_block.hip: the lockstep driver on one column): hand-written CSR product,
+Gram-Schmidt and Givens kernels, the preconditioner applied through ``hs_ldiv_dev_*`` on device pointers -- what a Julia host calls instead
+of ``IterativeSolvers.gmres``.
 ``trans="T"`` / ``"C"`` (or ``Pr=transpose(F)`` / ``adjoint(F)``) solve ``transpose(A) x = b`` / ``A' x = b`` with the same factorization
 (``hs_gmres_t_*``, ``hs_gmres_block_t_*``); ``A=None`` takes the matrix the handle already holds on the device.
 (An independent torch restatement of the same iteration lives under tests/gmres_mirror.py: test infrastructure, not product.)

@@ -563,7 +563,8 @@ int hs_set_comm(hs_handle* F, hs_comm* c);
  * the device, the preconditioner applied through hs_ldiv_dev_*.  A is n x n CSC with 1-based colptr / rowval as Julia holds them (host arrays);
  * b, x: host (where = 0) or device (where = 1) vectors; use_x0 != 0: x holds the initial guess, else zero.  Defaults as in the package for
  * restart <= 0 (min(20, n)), maxiter < 0 (n), reltol < 0 (sqrt(eps)).  Convergence: ||b - A x|| <= max(reltol * ||r0||, abstol).
- * resnorm (may be NULL) receives iters + 1 residual norms (the `log=true` history, resnorm[0] = ||r0||); it must hold maxiter + 1 doubles. */
+ * resnorm (may be NULL) receives iters + 1 residual norms (the `log=true` history, resnorm[0] = ||r0||); it must hold maxiter + 1 doubles.
+ * (hs_gmres_block.hip: the lockstep driver below on one column, with hs_ldiv_dev_* in place of the block solve.) */
 int hs_gmres_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
                double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream);
 int hs_gmres_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,

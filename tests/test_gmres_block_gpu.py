@@ -1,6 +1,7 @@
 """Lockstep GMRES on a block of right-hand sides (hs_gmres_block_*, csrc/hs_gmres_block.hip) on the MI355X: per column against `hs.gmres`
 on the scenarios of test_gmres_gpu.py, the lockstep schedule through hs_gmres_block_info, bitwise determinism and column independence,
-the other paths of the ABI, the refusals, and the SpMM kernel alone on exact integer data."""
+one column bitwise against `hs.gmres` (the same driver at width 1), the other paths of the ABI, the refusals, and the SpMM kernel alone on
+exact integer data."""
 import ctypes as C
 
 import numpy as np
@@ -158,6 +159,24 @@ def test_determinism_and_column_independence_bitwise(hs, si, monkeypatch):
     assert _same((Xq, cq), (r0[0][:, perm], [r0[1][j] for j in perm]))
 
 
+@pytest.mark.parametrize("shape,kind,nmax", [((15, 15), "poisson", 20), ((15, 15), "helmholtz", 20), ((20, 20, 20), "helmholtz", 512)])
+def test_one_column_is_one_column_bitwise(hs, shape, kind, nmax):
+    """Without a preconditioner `hs.gmres` (hs_gmres_*, hs_gmres_t_*) and `hs.gmres_block` on a 1-D b do the same arithmetic: equal x,
+    history, iteration count and flag, over several restart cycles, for A, transpose(A) and adjoint(A), from zero and from a guess.
+    n = 225 is less than one 256-row workgroup, n = 8000 is ragged against the 256-row and the 1024-row tiles."""
+    A, b, _ = hs.problems.make_problem(shape, kind=kind, nmax=nmax, rhs="randn")
+    x0 = np.random.default_rng(5).standard_normal(A.shape[0]).astype(b.dtype)
+    kw = dict(Pr=None, reltol=1e-3, restart=5, maxiter=20, log=True)
+    for trans in (None, "T", "C"):
+        for guess in (None, x0):
+            x1, c1 = hs.gmres(A, b, x0=guess, trans=trans, **kw)
+            x2, c2 = hs.gmres_block(A, b, X0=guess, trans=trans, **kw)
+            what = (kind, shape, trans, guess is not None, c1["iters"], c2["iters"])
+            assert c1["iters"] > kw["restart"], what  # more than one cycle
+            assert np.array_equal(x1, x2), what
+            assert c1["resnorm"] == c2["resnorm"] and c1["iters"] == c2["iters"] and c1["isconverged"] == c2["isconverged"], what
+
+
 @pytest.mark.parametrize("si", [0, 1])
 def test_other_paths_and_edge_cases(hs, si):
     import torch
@@ -239,7 +258,9 @@ def test_other_paths_and_edge_cases(hs, si):
     b2 = rhs_mix(n, 2, cplx, seed=8)[:, ::-1].copy() + 1.0
     x0, X0b, g0 = hs.ldiv(Fc, b2), hs.ldiv_block(Fc, B), hs.gmres(A, b2[:, 0], Pr=Fc, reltol=1e-9, restart=30, maxiter=30, log=True)
     again = hs.gmres_block(A, B, **kw)
+    info = hs.gmres_block_info()
     x1, X1b, g1 = hs.ldiv(Fc, b2), hs.ldiv_block(Fc, B), hs.gmres(A, b2[:, 0], Pr=Fc, reltol=1e-9, restart=30, maxiter=30, log=True)
+    assert info["cycles"] >= 1 and hs.gmres_block_info() == info  # the figures are those of the last hs_gmres_block_* call: hs.gmres leaves them
     assert np.array_equal(again[0], ref) and np.array_equal(x0, x1) and np.array_equal(X0b, X1b)
     assert np.array_equal(g0[0], g1[0]) and g0[1]["resnorm"] == g1[1]["resnorm"]
     # the exact preconditioner: one step for every column

@@ -1,5 +1,5 @@
-"""GMRES on transposed and adjoint systems, and on the handle's own A (hs_gmres_t_*, hs_gmres_block_t_*, csrc/hs_gmres.hip,
-hs_gmres_block.hip, hs_gmres_op.hip) on the MI355X: the single-vector calls against the NumPy GMRES of tests/gmres_block_mirror.py on op(A)
+"""GMRES on transposed and adjoint systems, and on the handle's own A (hs_gmres_t_*, hs_gmres_block_t_*,
+csrc/hs_gmres_block.hip, hs_gmres_op.hip) on the MI355X: the single-vector calls against the NumPy GMRES of tests/gmres_block_mirror.py on op(A)
 with hs.ldiv(op(F), .) as preconditioner, every column of the block calls against the single-vector call, the lockstep schedule, bitwise
 determinism, own-A against explicit-A, the other paths of the ABI, the refusals on real handles, and the op(A) SpMM kernel alone on exact
 integer data.  Both problems are nonsymmetric: a dropped `trans` cannot pass."""

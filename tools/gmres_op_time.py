@@ -9,8 +9,8 @@ helmholtz3d_64:kind=convdiff_helmholtz,swlevel=4,tol=1e-4).  Every call takes de
 (it returns after its last device read); the device part is the library's own event pair (hs_gmres_block_info: from the first kernel of the
 iteration to the last, after A is on the device), so host - device is what a call spends before and after the iteration: the conversion and
 upload of A, the workspace, the result arrays.  The explicit-A call with trans = 0 is hs_gmres_block_*, the path without this tool's
-subject.  For k = 1 the single-vector entry point hs_gmres_t_* is timed as well (host clock only: it has no event pair).  One JSON line per
-(workload, k, trans): both paths' times with all samples, their spreads, the ratio of the device part to that of trans = 0 of the same k,
+subject.  For k = 1 the single-vector entry point hs_gmres_t_* is timed as well (host clock only:
+hs_gmres_block_info reports block calls alone).  One JSON line per (workload, k, trans): both paths' times with all samples, their spreads, the ratio of the device part to that of trans = 0 of the same k,
 iteration counts, whether the two paths returned the same bits, and the worst residual of op(A) x = b."""
 import argparse
 import ctypes as C
