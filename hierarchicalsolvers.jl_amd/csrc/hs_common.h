@@ -303,8 +303,13 @@ void launch_inv256(const SolveNode<T>* dn, int nbatch, int maxni, hipStream_t s,
 int hs_solve_wide_cols();
 // the sweeps of a whole level in ONE launch (dataflow over published values; kernels_solve_wide.hip).  E1, E2: exchange vectors laid out like w,
 // filled with 0xFF bytes (the sentinel) before the launch
+// hs_fwd_flow_tall: 1 where the forward sweep walks the rows of the Gauss transform in tall tiles (the level has enough boundary blocks to fill the
+// chip), else 0; force_tall = 0 / 1 overrides the rule (tests/ only: hsk_sweep_level_*)
 template <class T>
-void launch_fwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, int maxnb, T* w, T* y, T* b, T* E1, T* E2, int* counter, int* err, hipStream_t s);
+int hs_fwd_flow_tall(int nbatch, int maxnb);
+template <class T>
+void launch_fwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, int maxnb, T* w, T* y, T* b, T* E1, T* E2, int* counter, int* err, hipStream_t s,
+                     int force_tall = -1);
 template <class T>
 void launch_bwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, T* w, T* x, T* E1, T* E2, int* counter, int* err, hipStream_t s);
 template <class T>

@@ -317,39 +317,66 @@ extern "C" int hsk_gemm_schur_d(int64_t count, const int64_t* ni, const int64_t*
 //        3: tournament with descriptors -- what a redone level runs
 // Outputs (any may be null) are packed per front in the same order: LF m x ni, UR ni x nb, SB nb x nb, rperm ni, info, growth;
 // invL / invU ceil(ni/32) blocks of 32 x 32, inv256L / inv256U ceil(ni/256) blocks of 256 x 256 (column-major; modes 2, 3 only).
+// The batch itself -- device buffers, descriptors, copy-in, factorization, copy-out -- is FrontBatch, shared with hsk_sweep_level_* below.
 template <class T>
-static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, T* outLF, T* outUR, T* outSB,
-                            int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U,
-                            double* ms_out) {
-  if (count <= 0 || count > 65535 || !ni_ || !nb_ || !F || mode < 0 || mode > 3) {
-    hs_set_error(HS_ERR_ARGUMENT, count, "hsk_front_batch: count in [1, 65535], ni, nb and F non-null and mode in 0..3 required");
-    return HS_ERR_ARGUMENT;
+struct FrontBatch {
+  // per-front layout of one device buffer of T and one of int, laid out as hs_analyze lays out the factor arenas
+  struct Off {
+    int ni, nb, m, ldl, ldu, lds, nblk, nb256, ncand;
+    size_t lf, ur, sb, inv, inv256, ip, cand;
+  };
+  int64_t count = 0;
+  std::vector<Off> o;
+  std::vector<int> h_ni, h_nb;
+  int maxni = 0, maxnb = 0, maxm = 0;
+  T* dbuf = nullptr;
+  int* dint = nullptr;
+  NodeDesc<T>* dn = nullptr;
+  SolveNode<T>* dsn = nullptr;
+  std::vector<NodeDesc<T>> hn;
+  std::vector<SolveNode<T>> hs;  // filled by setup, reaches the device with upload_solve (a caller may complete it in between)
+  ~FrontBatch() {  // an early return of CK leaves nothing behind
+    (void)hipFree(dbuf);
+    (void)hipFree(dint);
+    (void)hipFree(dn);
+    (void)hipFree(dsn);
   }
-  for (int64_t k = 0; k < count; ++k)
-    if (ni_[k] < 0 || nb_[k] < 0 || ni_[k] + nb_[k] > (1 << 16)) {
-      hs_set_error(HS_ERR_ARGUMENT, k, "hsk_front_batch: front %lld has ni = %lld, nb = %lld (need 0 <= ni, nb and ni + nb <= 65536)", (long long)k,
-                   (long long)ni_[k], (long long)nb_[k]);
+  // the argument checks both hooks share; nothing on the device yet
+  static int check(const char* name, int64_t count, const int64_t* ni_, const int64_t* nb_, const T* F, int mode, int mode_lo) {
+    if (count <= 0 || count > 65535 || !ni_ || !nb_ || !F || mode < mode_lo || mode > 3) {
+      hs_set_error(HS_ERR_ARGUMENT, count, "%s: count in [1, 65535], ni, nb and F non-null and mode in %d..3 required", name, mode_lo);
       return HS_ERR_ARGUMENT;
     }
-  if ((outInvL || outInvU || outInv256L || outInv256U) && mode < 2) {
-    hs_set_error(HS_ERR_ARGUMENT, mode, "hsk_front_batch: the stored inverses are returned by modes 2 and 3 only");
-    return HS_ERR_ARGUMENT;
+    for (int64_t k = 0; k < count; ++k)
+      if (ni_[k] < 0 || nb_[k] < 0 || ni_[k] + nb_[k] > (1 << 16)) {
+        hs_set_error(HS_ERR_ARGUMENT, k, "%s: front %lld has ni = %lld, nb = %lld (need 0 <= ni, nb and ni + nb <= 65536)", name, (long long)k,
+                     (long long)ni_[k], (long long)nb_[k]);
+        return HS_ERR_ARGUMENT;
+      }
+    return HS_OK;
   }
+  int setup(int64_t count_, const int64_t* ni_, const int64_t* nb_, const T* F);
+  int upload_solve() {
+    CK(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice));
+    return HS_OK;
+  }
+  int factor(int mode, double* ms_out);
+  int copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U);
+};
+
+template <class T>
+int FrontBatch<T>::setup(int64_t count_, const int64_t* ni_, const int64_t* nb_, const T* F) {
+  count = count_;
   int cnt = 0;
   if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
     hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
     return HS_ERR_DEVICE;
   }
   auto rup32 = [](size_t e) { return (e + 31) / 32 * 32; };
-  // per-front layout of one device buffer of T and one of int, laid out as hs_analyze lays out the factor arenas
-  struct Off {
-    int ni, nb, m, ldl, ldu, lds, nblk, nb256, ncand;
-    size_t lf, ur, sb, inv, inv256, ip, cand;
-  };
-  std::vector<Off> o(count);
-  std::vector<int> h_ni(count), h_nb(count);
+  o.resize(count);
+  h_ni.resize(count);
+  h_nb.resize(count);
   size_t nT = 0, nI = 0;
-  int maxni = 0, maxnb = 0, maxm = 0;
   for (int64_t k = 0; k < count; ++k) {
     Off& x = o[k];
     x.ni = (int)ni_[k]; x.nb = (int)nb_[k]; x.m = x.ni + x.nb;
@@ -367,18 +394,14 @@ static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb
     h_ni[k] = x.ni; h_nb[k] = x.nb;
     maxni = std::max(maxni, x.ni); maxnb = std::max(maxnb, x.nb); maxm = std::max(maxm, x.m);
   }
-  T* dbuf = nullptr;
-  int* dint = nullptr;
-  NodeDesc<T>* dn = nullptr;
-  SolveNode<T>* dsn = nullptr;
   CK(hipMalloc((void**)&dbuf, sizeof(T) * nT));
   CK(hipMalloc((void**)&dint, sizeof(int) * nI));
   CK(hipMalloc((void**)&dn, sizeof(NodeDesc<T>) * count));
   CK(hipMalloc((void**)&dsn, sizeof(SolveNode<T>) * count));
   CK(hipMemset(dbuf, 0, sizeof(T) * nT));
   CK(hipMemset(dint, 0, sizeof(int) * nI));
-  std::vector<NodeDesc<T>> hn(count);
-  std::vector<SolveNode<T>> hs(count);
+  hn.resize(count);
+  hs.resize(count);
   const T* Fk = F;
   for (int64_t k = 0; k < count; ++k) {
     const Off& x = o[k];
@@ -415,7 +438,11 @@ static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb
     Fk += (size_t)m * m;
   }
   CK(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice));
+  return HS_OK;
+}
+
+template <class T>
+int FrontBatch<T>::factor(int mode, double* ms_out) {
   Profiler prof;
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
@@ -439,6 +466,18 @@ static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb
   CK(hipEventElapsedTime(&ms, e0, e1));
   if (ms_out) *ms_out = ms;
   CK(hipDeviceSynchronize());
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipStreamDestroy(s_main);
+  if (s_side) (void)hipStreamDestroy(s_side);
+  if (s_la) (void)hipStreamDestroy(s_la);
+  if (s_sidem) (void)hipStreamDestroy(s_sidem);
+  return HS_OK;
+}
+
+template <class T>
+int FrontBatch<T>::copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L,
+                            T* outInv256U) {
   std::vector<int> ip;
   size_t pLF = 0, pUR = 0, pSB = 0, pR = 0, pInv = 0, pInv256 = 0;
   for (int64_t k = 0; k < count; ++k) {
@@ -461,17 +500,230 @@ static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb
     if (outInv256U && n256) CK(hipMemcpy(outInv256U + pInv256, d.inv256U, sizeof(T) * n256, hipMemcpyDeviceToHost));
     pLF += (size_t)m * ni; pUR += (size_t)ni * nb; pSB += (size_t)nb * nb; pR += ni; pInv += n32; pInv256 += n256;
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipStreamDestroy(s_main);
-  if (s_side) (void)hipStreamDestroy(s_side);
-  if (s_la) (void)hipStreamDestroy(s_la);
-  if (s_sidem) (void)hipStreamDestroy(s_sidem);
-  (void)hipFree(dbuf);
-  (void)hipFree(dint);
-  (void)hipFree(dn);
-  (void)hipFree(dsn);
   return HS_OK;
+}
+
+template <class T>
+static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, T* outLF, T* outUR, T* outSB,
+                            int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U,
+                            double* ms_out) {
+  if (int st = FrontBatch<T>::check("hsk_front_batch", count, ni_, nb_, F, mode, 0)) return st;
+  if ((outInvL || outInvU || outInv256L || outInv256U) && mode < 2) {
+    hs_set_error(HS_ERR_ARGUMENT, mode, "hsk_front_batch: the stored inverses are returned by modes 2 and 3 only");
+    return HS_ERR_ARGUMENT;
+  }
+  FrontBatch<T> fb;
+  if (int st = fb.setup(count, ni_, nb_, F)) return st;
+  if (int st = fb.upload_solve()) return st;
+  if (int st = fb.factor(mode, ms_out)) return st;
+  return fb.copy_out(outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U);
+}
+
+// One tree level of ldiv!: the batch above, factored in mode 2 or 3, then the level's forward and backward sweeps on a global vector (the
+// contract is in include/hs_kernels.h).  The launches and their order are those of solve_fwd / solve_bwd / solve_fwd_t / solve_bwd_t
+// (hs_api.hip) for one level, without the low-rank and HSS calls; `path` stands for the switches HS_SOLVE_FLOW / HS_SOLVE_WIDE.
+template <class T>
+static int sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, const int64_t* flags, int64_t n,
+                            const int64_t* fidx, const T* b, int path, int trans, int tall, T* outLF, T* outUR, int64_t* out_rperm, int64_t* info,
+                            int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U, T* out_y, T* out_bfwd, T* out_x, T* out_bbwd,
+                            int* tall_used) {
+  const char* name = "hsk_sweep_level";
+  if (int st = FrontBatch<T>::check(name, count, ni_, nb_, F, mode, 2)) return st;
+  if (!fidx || !b || n <= 0 || n > 0x7fffffff || path < 0 || path > 2 || trans < 0 || trans > 2 || tall < -1 || tall > 1) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "%s: fidx and b non-null, n in [1, 2^31), path in 0..2, trans in 0..2 and tall in -1..1 required", name);
+    return HS_ERR_ARGUMENT;
+  }
+  if (path == 2 && trans != 0) {
+    hs_set_error(HS_ERR_ARGUMENT, trans, "%s: the 32-column sweeps (path 2) exist for trans = 0 only", name);
+    return HS_ERR_ARGUMENT;
+  }
+  if (trans == 2 && sizeof(T) == 8) {
+    hs_set_error(HS_ERR_ARGUMENT, trans, "%s: trans = 2 (adjoint) is for ComplexF64; Float64 has trans = 1", name);
+    return HS_ERR_ARGUMENT;
+  }
+  size_t nidx = 0;
+  for (int64_t k = 0; k < count; ++k) nidx += (size_t)(ni_[k] + nb_[k]);
+  std::vector<int> hidx(nidx + 1, 0);
+  {
+    std::vector<char> seen((size_t)n, 0);
+    for (size_t p = 0; p < nidx; ++p) {
+      if (fidx[p] < 0 || fidx[p] >= n || seen[(size_t)fidx[p]]) {
+        hs_set_error(HS_ERR_ARGUMENT, (int64_t)p, "%s: fidx[%lld] = %lld is outside 0:%lld or occurs twice (the fronts of a level are disjoint)", name,
+                     (long long)p, (long long)fidx[p], (long long)n - 1);
+        return HS_ERR_ARGUMENT;
+      }
+      seen[(size_t)fidx[p]] = 1;
+      hidx[p] = (int)fidx[p];
+    }
+  }
+  FrontBatch<T> fb;
+  if (int st = fb.setup(count, ni_, nb_, F)) return st;
+  struct Bufs {  // an early return of CK leaves nothing behind
+    int *fidx = nullptr, *counter = nullptr, *err = nullptr;
+    T *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr, *part = nullptr, *b = nullptr;
+    ~Bufs() {
+      for (void* q : {(void*)fidx, (void*)counter, (void*)w1, (void*)w2, (void*)e1, (void*)e2, (void*)part, (void*)b}) (void)hipFree(q);
+      if (err) (void)hipHostFree(err);
+    }
+  } d;
+  CK(hipMalloc((void**)&d.fidx, sizeof(int) * (nidx + 1)));
+  CK(hipMemcpy(d.fidx, hidx.data(), sizeof(int) * (nidx + 1), hipMemcpyHostToDevice));
+  // woff / poff as hs_analyze lays them out: packed, one entry of slack at the end of the buffers
+  long long woff = 0, poff = 0;
+  size_t ioff = 0;
+  for (int64_t k = 0; k < count; ++k) {
+    SolveNode<T>& q = fb.hs[k];
+    q.fidx = d.fidx + ioff;
+    q.woff = woff;
+    q.poff = poff;
+    if (flags && (flags[k] & 1)) {
+      q.compressed = 1;
+      q.mrows = q.ni;
+    }
+    ioff += (size_t)q.m;
+    woff += q.ni;
+    poff += (long long)((q.nb + 511) / 512) * q.ni;
+  }
+  if (int st = fb.upload_solve()) return st;
+  if (int st = fb.factor(mode, nullptr)) return st;
+  if (int st = fb.copy_out(outLF, outUR, nullptr, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U)) return st;
+  bool blanked = false;
+  for (int64_t k = 0; k < count; ++k)
+    if (flags && (flags[k] & 2)) {  // as hs_analyze blanks the descriptor of a front whose interior block is an HSS matrix
+      SolveNode<T>& q = fb.hs[k];
+      q.ni = q.nb = q.m = q.mrows = 0;
+      blanked = true;
+    }
+  if (blanked)
+    if (int st = fb.upload_solve()) return st;
+  const size_t wbytes = sizeof(T) * (size_t)(woff + 1);
+  CK(hipMalloc((void**)&d.w1, wbytes));
+  CK(hipMalloc((void**)&d.w2, wbytes));
+  CK(hipMalloc((void**)&d.e1, wbytes));
+  CK(hipMalloc((void**)&d.e2, wbytes));
+  CK(hipMalloc((void**)&d.part, sizeof(T) * (size_t)(poff + 1)));
+  CK(hipMalloc((void**)&d.b, sizeof(T) * (size_t)n));
+  CK(hipMalloc((void**)&d.counter, sizeof(int)));
+  CK(hipHostMalloc((void**)&d.err, sizeof(int), hipHostMallocMapped));
+  *d.err = 0;
+  CK(hipMemset(d.w1, 0, wbytes));
+  CK(hipMemset(d.w2, 0, wbytes));
+  CK(hipMemset(d.part, 0, sizeof(T) * (size_t)(poff + 1)));
+  CK(hipMemcpy(d.b, b, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+  const SolveNode<T>* dn = fb.dsn;
+  const int nf = (int)count, maxni = fb.maxni, maxnb = fb.maxnb, maxm = fb.maxm;
+  const hipStream_t s = nullptr;
+  const int tall_rule = hs_fwd_flow_tall<T>(nf, maxnb);
+  if (tall_used) *tall_used = (path == 0 && trans == 0) ? (tall >= 0 ? tall : tall_rule) : 0;
+  auto arm = [&]() -> int {  // flow_arm and a fresh workgroup-id counter
+    CK(hipMemsetAsync(d.e1, 0xFF, wbytes, s));
+    CK(hipMemsetAsync(d.e2, 0xFF, wbytes, s));
+    CK(hipMemsetAsync(d.counter, 0, sizeof(int), s));
+    return HS_OK;
+  };
+  auto finish = [&](const char* dir) -> int {  // flow_check
+    CK(hipDeviceSynchronize());
+    if (*d.err) {
+      hs_set_error(HS_ERR_DEVICE, 0, "%s: a workgroup of the %s sweep waited for a block that never arrived", name, dir);
+      return HS_ERR_DEVICE;
+    }
+    return HS_OK;
+  };
+  auto copy_w = [&](T* out) -> int {  // the level's w2, packed per front (ni entries each)
+    if (out && woff > 0) CK(hipMemcpy(out, d.w2, sizeof(T) * (size_t)woff, hipMemcpyDeviceToHost));
+    return HS_OK;
+  };
+  auto copy_b = [&](T* out) -> int {
+    if (out) CK(hipMemcpy(out, d.b, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost));
+    return HS_OK;
+  };
+  const bool level_on = maxni > 0;  // (solve_fwd / solve_bwd skip a level without interior DOFs)
+  // forward
+  if (level_on) {
+    if (int st = arm()) return st;
+    if (trans == 0) {
+      launch_fwd_gather<T>(dn, nf, maxni, d.b, d.w1, s);
+      if (path == 0) {
+        launch_fwd_flow<T>(dn, nf, maxni, maxnb, d.w1, d.w2, d.b, d.e1, d.e2, d.counter, d.err, s, tall);
+      } else if (path == 1) {
+        const int nblk = (maxni + hs_solve_wide_cols() - 1) / hs_solve_wide_cols();
+        for (int blk = 0; blk < nblk; ++blk) launch_fwd_wide<T>(dn, nf, blk, maxm, d.w1, d.w2, d.b, s);
+      } else {
+        const int nblk = (maxni + HS_PB - 1) / HS_PB;
+        for (int blk = 0; blk < nblk; ++blk) launch_fwd_step<T>(dn, nf, blk, maxm, d.w1, d.w2, d.b, s);
+      }
+    } else {
+      launch_t_gather<T>(dn, nf, maxni, d.b, d.w1, s);
+      const int nblk = (maxni + hs_solve_t_cols() - 1) / hs_solve_t_cols();
+      if constexpr (sizeof(T) == 16) {
+        if (trans == 2) {
+          if (path == 0) launch_t_fwd_flow<T, true>(dn, nf, maxni, maxnb, d.w1, d.w2, d.b, d.e1, d.e2, d.counter, d.err, s);
+          else for (int blk = 0; blk < nblk; ++blk) launch_t_fwd_step<T, true>(dn, nf, blk, maxm, d.w1, d.w2, d.b, s);
+        }
+      }
+      if (trans == 1) {
+        if (path == 0) launch_t_fwd_flow<T, false>(dn, nf, maxni, maxnb, d.w1, d.w2, d.b, d.e1, d.e2, d.counter, d.err, s);
+        else for (int blk = 0; blk < nblk; ++blk) launch_t_fwd_step<T, false>(dn, nf, blk, maxm, d.w1, d.w2, d.b, s);
+      }
+    }
+    if (int st = finish("forward")) return st;
+  }
+  if (int st = copy_w(out_y)) return st;
+  if (int st = copy_b(out_bfwd)) return st;
+  // backward, on the b and y the forward sweep left
+  if (level_on) {
+    if (int st = arm()) return st;
+    if (trans == 0) {
+      launch_int_update<T>(dn, nf, maxni, maxnb, d.b, d.part, d.w2, d.w1, s);
+      if (path == 0) {
+        launch_bwd_flow<T>(dn, nf, maxni, d.w1, d.w2, d.e1, d.e2, d.counter, d.err, s);
+      } else if (path == 1) {
+        const int nw = (maxni + hs_solve_wide_cols() - 1) / hs_solve_wide_cols();
+        for (int blk = nw - 1; blk >= 0; --blk) launch_bwd_wide<T>(dn, nf, blk, d.w1, d.w2, s, blk == nw - 1);
+      } else {
+        const int nblk = (maxni + HS_PB - 1) / HS_PB;
+        for (int blk = nblk - 1; blk >= 0; --blk) launch_bwd_step<T>(dn, nf, blk, d.w1, d.w2, s);
+      }
+      launch_bwd_scatter<T>(dn, nf, maxni, d.b, d.w2, s);
+    } else {
+      const int nblk = (maxni + hs_solve_t_cols() - 1) / hs_solve_t_cols();
+      if constexpr (sizeof(T) == 16) {
+        if (trans == 2) {
+          launch_t_int_update<T, true>(dn, nf, maxni, d.b, d.w2, d.w1, s);
+          if (path == 0) launch_t_bwd_flow<T, true>(dn, nf, maxni, d.w1, d.w2, d.e1, d.e2, d.counter, d.err, s);
+          else for (int blk = nblk - 1; blk >= 0; --blk) launch_t_bwd_step<T, true>(dn, nf, blk, d.w1, d.w2, s);
+        }
+      }
+      if (trans == 1) {
+        launch_t_int_update<T, false>(dn, nf, maxni, d.b, d.w2, d.w1, s);
+        if (path == 0) launch_t_bwd_flow<T, false>(dn, nf, maxni, d.w1, d.w2, d.e1, d.e2, d.counter, d.err, s);
+        else for (int blk = nblk - 1; blk >= 0; --blk) launch_t_bwd_step<T, false>(dn, nf, blk, d.w1, d.w2, s);
+      }
+      launch_t_scatter<T>(dn, nf, maxni, d.b, d.w2, s);
+    }
+    if (int st = finish("backward")) return st;
+  }
+  if (int st = copy_w(out_x)) return st;
+  return copy_b(out_bbwd);
+}
+extern "C" int hsk_sweep_level_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int64_t* flags, int64_t n,
+                                 const int64_t* fidx, const double* b, int path, int trans, int tall, double* outLF, double* outUR,
+                                 int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU, double* outInv256L,
+                                 double* outInv256U, double* y, double* b_fwd, double* x, double* b_bwd, int* tall_used) {
+  return sweep_level_hook<double>(count, ni, nb, mode, F, flags, n, fidx, b, path, trans, tall, outLF, outUR, out_rperm, info, growth, outInvL,
+                                  outInvU, outInv256L, outInv256U, y, b_fwd, x, b_bwd, tall_used);
+}
+extern "C" int hsk_sweep_level_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int64_t* flags, int64_t n,
+                                 const int64_t* fidx, const double* b, int path, int trans, int tall, double* outLF, double* outUR,
+                                 int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU, double* outInv256L,
+                                 double* outInv256U, double* y, double* b_fwd, double* x, double* b_bwd, int* tall_used) {
+  return sweep_level_hook<cplx>(count, ni, nb, mode, (const cplx*)F, flags, n, fidx, (const cplx*)b, path, trans, tall, (cplx*)outLF, (cplx*)outUR,
+                                out_rperm, info, growth, (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, (cplx*)y,
+                                (cplx*)b_fwd, (cplx*)x, (cplx*)b_bwd, tall_used);
+}
+extern "C" int hsk_flow_tall_rule(int is_complex, int64_t nbatch, int64_t maxnb) {
+  if (nbatch < 0 || nbatch > 0x7fffffff || maxnb < 0 || maxnb > 0x7fffffff) return -1;
+  return is_complex ? hs_fwd_flow_tall<cplx>((int)nbatch, (int)maxnb) : hs_fwd_flow_tall<double>((int)nbatch, (int)maxnb);
 }
 
 extern "C" int hsk_front_batch_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,

@@ -722,13 +722,21 @@ __global__ __launch_bounds__(HS_FLOW_NT) void flow_sweep_kernel(const SolveNode<
   }
 }
 
+// tall boundary tiles (2 KB column segments) where the level has enough boundary blocks to fill the chip several times; at the top of the tree a
+// tall block is a serial walk over ni/64 rounds with too few workgroups beside it (measured: levels 2-4 of Poisson 128^3 20 % slower, the leaf level 4 % faster)
 template <class T>
-void launch_fwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, int maxnb, T* w, T* y, T* b, T* E1, T* E2, int* counter, int* err, hipStream_t s) {
+int hs_fwd_flow_tall(int nbatch, int maxnb) {
+  constexpr int FBB = FlowBCfg<T>::FBB;
+  return (long long)nbatch * ((std::max(maxnb, 0) + FBB - 1) / FBB) >= 1536 ? 1 : 0;
+}
+template int hs_fwd_flow_tall<double>(int, int);
+template int hs_fwd_flow_tall<cplx>(int, int);
+template <class T>
+void launch_fwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, int maxnb, T* w, T* y, T* b, T* E1, T* E2, int* counter, int* err, hipStream_t s,
+                     int force_tall) {
   if (nbatch <= 0 || maxni <= 0) return;
   constexpr int FB = FlowCfg<T>::FB, FBB = FlowBCfg<T>::FBB;
-  // tall boundary tiles (2 KB column segments) where the level has enough boundary blocks to fill the chip several times; at the top of the tree a
-  // tall block is a serial walk over ni/64 rounds with too few workgroups beside it (measured: levels 2-4 of Poisson 128^3 20 % slower, the leaf level 4 % faster)
-  const int tall = (long long)nbatch * ((std::max(maxnb, 0) + FBB - 1) / FBB) >= 1536 ? 1 : 0;
+  const int tall = force_tall >= 0 ? (force_tall ? 1 : 0) : hs_fwd_flow_tall<T>(nbatch, maxnb);
   const int fbb = tall ? FBB : FB;
   const int nsb = (HS_SW / FB) * ((maxni + HS_SW - 1) / HS_SW) + (std::max(maxnb, 0) + fbb - 1) / fbb;
   hipLaunchKernelGGL((flow_sweep_kernel<T, false>), dim3((unsigned)nsb * (unsigned)nbatch), dim3(FlowCfg<T>::NT), 0, s, dn, nbatch, w, y, b, E1, E2, counter, err, tall);
@@ -739,8 +747,8 @@ void launch_bwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, T* w, T* x, 
   const int nsb = (HS_SW / FlowCfg<T>::FB) * ((maxni + HS_SW - 1) / HS_SW);
   hipLaunchKernelGGL((flow_sweep_kernel<T, true>), dim3((unsigned)nsb * (unsigned)nbatch), dim3(FlowCfg<T>::NT), 0, s, dn, nbatch, w, x, (T*)nullptr, E1, E2, counter, err, 0);
 }
-template void launch_fwd_flow<double>(const SolveNode<double>*, int, int, int, double*, double*, double*, double*, double*, int*, int*, hipStream_t);
-template void launch_fwd_flow<cplx>(const SolveNode<cplx>*, int, int, int, cplx*, cplx*, cplx*, cplx*, cplx*, int*, int*, hipStream_t);
+template void launch_fwd_flow<double>(const SolveNode<double>*, int, int, int, double*, double*, double*, double*, double*, int*, int*, hipStream_t, int);
+template void launch_fwd_flow<cplx>(const SolveNode<cplx>*, int, int, int, cplx*, cplx*, cplx*, cplx*, cplx*, int*, int*, hipStream_t, int);
 template void launch_bwd_flow<double>(const SolveNode<double>*, int, int, double*, double*, double*, double*, int*, int*, hipStream_t);
 template void launch_bwd_flow<cplx>(const SolveNode<cplx>*, int, int, cplx*, cplx*, cplx*, cplx*, int*, int*, hipStream_t);
 

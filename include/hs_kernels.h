@@ -46,6 +46,38 @@ int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t* nb, int m
                       double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
                       double* outInv256L, double* outInv256U, double* ms_out);
 
+/* One tree level of ldiv!: the batch of hsk_front_batch_* (same packing of ni, nb, F), factored in mode 2 or 3 so that the stored inverses are
+ * the production ones, then the level's forward and backward sweeps on the global vector b (length n), with the launches and the launch
+ * order of ldiv! (N), ldiv!(transpose(F), .) and ldiv!(adjoint(F), .) for one level, without the low-rank and HSS parts.
+ *   flags[k] (NULL: all 0)  bit 0 `compressed`: the descriptor carries compressed = 1, mrows = ni (the dense sweeps leave the front's boundary
+ *                           alone and the backward sweep starts from v = y); bit 1 `blank`: after the factorization the descriptor gets
+ *                           ni = nb = m = mrows = 0 (a front whose interior block is an HSS matrix): the sweeps skip it
+ *   fidx                    the global ids (0-based, < n) of every front, m = ni + nb per front in front order [int; bnd], one front after
+ *                           another; no id may occur twice (the fronts of a level are disjoint)
+ *   path                    0: dataflow sweeps, one launch per level and direction; 1: 256 columns per launch; 2: 32 columns per launch
+ *                           (trans = 0 only)
+ *   trans                   0: N, 1: T, 2: H (ComplexF64 only; Float64 refuses it: use 1)
+ *   tall                    -1: the forward dataflow sweep chooses its boundary tiles by its own rule (hsk_flow_tall_rule), 0 / 1: forced
+ *                           (path 0, trans 0; ignored elsewhere)
+ * The work vectors are laid out as hs_analyze lays them out (packed: woff += ni, poff += ceil(nb/512) * ni).  Per call: forward sweep
+ * (gather, sweep), y = the level's solved vector (sum of ni entries, packed per front; T / H: z) and b_fwd = b after it; backward sweep on
+ * those (interior update, sweep, scatter), x (packed like y) and b_bwd.  outLF .. outInv256U as in hsk_front_batch_*.  *tall_used: the tile
+ * shape the forward sweep ran with (0 when path != 0 or trans != 0).  Every output may be null.
+ * HS_ERR_ARGUMENT before any device work and with the outputs untouched: mode outside 2..3, path / trans / tall out of range, path = 2 with
+ * trans != 0, trans = 2 for Float64, an id outside [0, n) or one that occurs twice.  HS_ERR_DEVICE: a workgroup of a dataflow sweep ran
+ * out of its bounded wait (checked after each direction; nothing is launched after it). */
+int hsk_sweep_level_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int64_t* flags, int64_t n,
+                      const int64_t* fidx, const double* b, int path, int trans, int tall, double* outLF, double* outUR, int64_t* out_rperm,
+                      int64_t* info, int64_t* growth, double* outInvL, double* outInvU, double* outInv256L, double* outInv256U, double* y,
+                      double* b_fwd, double* x, double* b_bwd, int* tall_used);
+int hsk_sweep_level_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int64_t* flags, int64_t n,
+                      const int64_t* fidx, const double* b, int path, int trans, int tall, double* outLF, double* outUR, int64_t* out_rperm,
+                      int64_t* info, int64_t* growth, double* outInvL, double* outInvU, double* outInv256L, double* outInv256U, double* y,
+                      double* b_fwd, double* x, double* b_bwd, int* tall_used);
+/* The rule by which the forward dataflow sweep of a level of nbatch fronts with at most maxnb boundary DOFs takes tall boundary tiles
+ * (1) or not (0); -1 for arguments out of range.  Host only. */
+int hsk_flow_tall_rule(int is_complex, int64_t nbatch, int64_t maxnb);
+
 /* Low-rank compression X (rows x cols) ~= C (rows x r) * Z (r x cols) to tolerance max(atol, rtol*|u_11|): the
  * device primitive behind the compressed Gauss transforms (`_lgauss_transform` / `_rgauss_transform`,
  * src/factorization.jl:171-182, which call LowRankApprox.pqrfact).  cap = capacity (in columns of C / rows of Z)
