@@ -29,6 +29,7 @@
 #include "../../include/hs_solver.h"
 #include "../../include/hs_hss.h"
 #include "hs_common.h"
+#include "hs_sweep.h"
 #include "hs_condest.h"
 #include "hs_selinv.h"
 #include "hs_solve_multi.h"
@@ -1456,11 +1457,10 @@ static void numeric_end(hs_handle* h) {
 // ------------------------------------------------------------------------------------------------
 // ldiv!
 // ------------------------------------------------------------------------------------------------
-// dataflow sweeps (kernels_solve_wide.hip): HS_SOLVE_FLOW=0 goes back to one launch per 256 columns
-static bool solve_flow_on() {
-  static const bool on = !(getenv("HS_SOLVE_FLOW") && getenv("HS_SOLVE_FLOW")[0] == '0');
-  return on;
-}
+// ldiv!(F, B) (trans = 0), ldiv!(transpose(F), B) (1) and ldiv!(adjoint(F), B) (2; the same factors read along their columns,
+// kernels_solve_t.hip) share their two level loops; the launches of one level are sweep_level_fwd / sweep_level_bwd (hs_sweep.h), on the path
+// hs_sweep_path() reads from HS_SOLVE_FLOW / HS_SOLVE_WIDE (dataflow unless HS_SOLVE_FLOW=0).  analyze_impl allocates the exchange vectors
+// next to d_w1 for every handle that can be factored, so N and T select the dataflow sweeps by the path alone.
 // the workgroup-id counter of the next sweep launch: a ring of 64, cleared (in stream order) every time it wraps
 static int* flow_counter(hs_handle* h, hipStream_t s) {
   const int slot = h->flow_seq++ % 64;
@@ -1470,7 +1470,7 @@ static int* flow_counter(hs_handle* h, hipStream_t s) {
 // the exchange vectors hold the sentinel (all bits set) wherever nothing has been published yet: once per sweep direction, every level of
 // the sweep has its own range of them
 static void flow_arm(hs_handle* h, hipStream_t s) {
-  if (!solve_flow_on() || !h->d_e1) return;
+  if (hs_sweep_path() != 0 || !h->d_e1) return;  // (no vectors: a host-side plan, hs_plan)
   HS_HIP(hipMemsetAsync(h->d_e1, 0xFF, h->flow_bytes, s));
   HS_HIP(hipMemsetAsync(h->d_e2, 0xFF, h->flow_bytes, s));
 }
@@ -1481,63 +1481,46 @@ static void flow_check(hs_handle* h) {
   }
 }
 template <class T>
-static void solve_fwd(hs_handle* h, T* db, int lv_from, int lv_to, hipStream_t s) {
+static SweepLevel<T> sweep_level_of(hs_handle* h, const LevelH& L, T* db) {
+  return {(const SolveNode<T>*)h->d_solve + L.desc_off, (int)L.mine.size(), L.maxni, L.maxnb, L.maxm, (T*)h->d_w1, (T*)h->d_w2, (T*)h->d_part, db,
+          (T*)h->d_e1, (T*)h->d_e2, h->h_flow_err};
+}
+// leaves -> root (-> pseudo-root).  trans = 0: y = L11^-1 P rhs[int], rhs[bnd] -= Lbi y;  else: z = U11^-T rhs[int], rhs[bnd] -= Uib^T z
+template <class T>
+static void solve_fwd(hs_handle* h, int trans, T* db, int lv_from, int lv_to, hipStream_t s) {
   flow_arm(h, s);
-  const SolveNode<T>* sn = (const SolveNode<T>*)h->d_solve;
-  T* w1 = (T*)h->d_w1;
-  T* w2 = (T*)h->d_w2;
-  const int nl = (int)h->levels.size();
-  lv_from = std::min(lv_from, nl - 1);
+  const int path = hs_sweep_path();
+  lv_from = std::min(lv_from, (int)h->levels.size() - 1);
   lv_to = std::max(lv_to, 0);
-  for (int lv = lv_from; lv >= lv_to; --lv) {  // leaves -> root (-> pseudo-root)
+  for (int lv = lv_from; lv >= lv_to; --lv) {
     const LevelH& L = h->levels[lv];
     if (L.mine.empty() || L.maxni == 0) continue;
-    const SolveNode<T>* dn = sn + L.desc_off;
-    const int nb_ = (int)L.mine.size();
-    launch_fwd_gather<T>(dn, nb_, L.maxni, db, w1, s);
-    static const bool wide = !(getenv("HS_SOLVE_WIDE") && getenv("HS_SOLVE_WIDE")[0] == '0');  // 256 columns per launch (kernels_solve_wide.hip)
-    if (solve_flow_on()) {  // the whole level in one launch
-      launch_fwd_flow<T>(dn, nb_, L.maxni, L.maxnb, w1, w2, db, (T*)h->d_e1, (T*)h->d_e2, flow_counter(h, s), h->h_flow_err, s);
-    } else if (wide) {
-      const int nblk = (L.maxni + hs_solve_wide_cols() - 1) / hs_solve_wide_cols();
-      for (int blk = 0; blk < nblk; ++blk) launch_fwd_wide<T>(dn, nb_, blk, L.maxm, w1, w2, db, s);
+    sweep_level_fwd<T>(sweep_level_of<T>(h, L, db), path, trans, path == 0 ? flow_counter(h, s) : nullptr, s);
+    if (trans == 0) {
+      solve_lr_fwd<T>(h, lv, db, s);
+      solve_hss_fwd<T>(h, lv, db, s);
     } else {
-      const int nblk = (L.maxni + HS_PB - 1) / HS_PB;
-      for (int blk = 0; blk < nblk; ++blk) launch_fwd_step<T>(dn, nb_, blk, L.maxm, w1, w2, db, s);
+      sweep_with_conj<T>(trans, [&](auto conj) { solve_lr_fwd_t<T, decltype(conj)::value>(h, lv, db, s); });
     }
-    solve_lr_fwd<T>(h, lv, db, s);
-    solve_hss_fwd<T>(h, lv, db, s);
   }
 }
+// root -> leaves.  trans = 0: rhs[int] = U11^-1 (y - Uib rhs[bnd]);  else: v = z - Lbi^T rhs[bnd], rhs[int[rperm]] = L11^-T v
 template <class T>
-static void solve_bwd(hs_handle* h, T* db, int lv_from, int lv_to, hipStream_t s) {
+static void solve_bwd(hs_handle* h, int trans, T* db, int lv_from, int lv_to, hipStream_t s) {
   flow_arm(h, s);
-  const SolveNode<T>* sn = (const SolveNode<T>*)h->d_solve;
-  T* w1 = (T*)h->d_w1;
-  T* w2 = (T*)h->d_w2;
-  T* part = (T*)h->d_part;
-  const int nl = (int)h->levels.size();
+  const int path = hs_sweep_path();
   lv_from = std::max(lv_from, 0);
-  lv_to = std::min(lv_to, nl - 1);
-  for (int lv = lv_from; lv <= lv_to; ++lv) {  // root -> leaves
+  lv_to = std::min(lv_to, (int)h->levels.size() - 1);
+  for (int lv = lv_from; lv <= lv_to; ++lv) {
     const LevelH& L = h->levels[lv];
     if (L.mine.empty() || L.maxni == 0) continue;
-    const SolveNode<T>* dn = sn + L.desc_off;
-    const int nb_ = (int)L.mine.size();
-    launch_int_update<T>(dn, nb_, L.maxni, L.maxnb, db, part, w2, w1, s);
-    solve_lr_bwd<T>(h, lv, db, s);
-    const int nblk = (L.maxni + HS_PB - 1) / HS_PB;
-    static const bool wide = !(getenv("HS_SOLVE_WIDE") && getenv("HS_SOLVE_WIDE")[0] == '0');
-    if (solve_flow_on()) {
-      launch_bwd_flow<T>(dn, nb_, L.maxni, w1, w2, (T*)h->d_e1, (T*)h->d_e2, flow_counter(h, s), h->h_flow_err, s);
-    } else if (wide) {
-      const int nw = (L.maxni + hs_solve_wide_cols() - 1) / hs_solve_wide_cols();
-      for (int blk = nw - 1; blk >= 0; --blk) launch_bwd_wide<T>(dn, nb_, blk, w1, w2, s, blk == nw - 1);
-    } else {
-      for (int blk = nblk - 1; blk >= 0; --blk) launch_bwd_step<T>(dn, nb_, blk, w1, w2, s);
-    }
-    launch_bwd_scatter<T>(dn, nb_, L.maxni, db, w2, s);
-    solve_hss_bwd<T>(h, lv, db, s);
+    sweep_level_bwd<T>(sweep_level_of<T>(h, L, db), path, trans, path == 0 ? flow_counter(h, s) : nullptr, s, [&] {
+      if (trans == 0)
+        solve_lr_bwd<T>(h, lv, db, s);
+      else
+        sweep_with_conj<T>(trans, [&](auto conj) { solve_lr_bwd_t<T, decltype(conj)::value>(h, lv, db, s); });
+    });
+    if (trans == 0) solve_hss_bwd<T>(h, lv, db, s);
   }
 }
 
@@ -1555,7 +1538,7 @@ template <class T>
 static void solve_dist(hs_handle* h, T* db, hipStream_t s) {
   if (!h->comm) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: ldiv! on a dist_top factorization needs the communicator (hs_set_comm)");
   const int nl = (int)h->levels.size(), cut = h->cut_level, esz = (int)sizeof(T);
-  solve_fwd<T>(h, db, nl - 1, cut, s);
+  solve_fwd<T>(h, 0, db, nl - 1, cut, s);
   for (int lv = cut - 1; lv >= 1; --lv) {
     const LevelH& L = h->levels[lv];
     if (L.mine.size() != 1 || !h->nodes[L.mine[0]].dist) HS_FAIL(HS_ERR_UNSUPPORTED, lv, "internal: level %d above the cut holds no group front", lv);
@@ -1571,9 +1554,9 @@ static void solve_dist(hs_handle* h, T* db, hipStream_t s) {
     if (co.nb > 0) recvs.push_back({partner, h->d_xr, (size_t)co.nb * sizeof(T)});
     comm_transfer_on(h, sends, recvs, s);
     if (co.nb > 0) launch_unpack_idx(h->d_int + co.off_fidx + co.ni, co.nb, db, h->d_xr, esz, s);
-    solve_fwd<T>(h, db, lv, lv, s);
+    solve_fwd<T>(h, 0, db, lv, lv, s);
   }
-  solve_bwd<T>(h, db, 1, nl - 1, s);
+  solve_bwd<T>(h, 0, db, 1, nl - 1, s);
   // gather: all[off[r] ..] = b[owned(r)] on rank r, exchanged all-to-all, scattered back
   T* all = (T*)h->d_xall;
   const int64_t* off = h->owned_off.data();
@@ -1656,12 +1639,17 @@ static bool check_solve_n(hs_handle* h, const char* fn, bool cplx, int64_t ldc, 
   if (h->nranks > 1 && !dsolve) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s on a distributed factorization without hs_options.dist_top: drive hs_solve_*_levels from the host layer", fn);
   return dsolve;
 }
+// one single-vector solve with op(F) on this rank's whole tree
+template <class T>
+static void solve_t(hs_handle* h, int trans, T* db, hipStream_t s) {
+  const int nl = (int)h->levels.size();
+  solve_fwd<T>(h, trans, db, nl - 1, 0, s);
+  solve_bwd<T>(h, trans, db, 0, nl - 1, s);
+}
 template <class T>
 static void solve_n(hs_handle* h, bool dsolve, T* db, hipStream_t s) {
   if (dsolve) return solve_dist<T>(h, db, s);
-  const int nl = (int)h->levels.size();
-  solve_fwd<T>(h, db, nl - 1, 0, s);
-  solve_bwd<T>(h, db, 0, nl - 1, s);
+  solve_t<T>(h, 0, db, s);
 }
 template <class T>
 static void ldiv_host(hs_handle* h, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
@@ -1676,64 +1664,8 @@ static void ldiv_dev(hs_handle* h, T* dC, int64_t ldc, const T* dB, int64_t ldb,
 
 
 // ------------------------------------------------------------------------------------------------
-// ldiv!(transpose(F), B), ldiv!(adjoint(F), B): the same factors read along their columns (kernels_solve_t.hip); CONJ = adjoint.
-// The triangular sweeps of a level are one dataflow launch; HS_SOLVE_FLOW=0 selects the launch-per-step sweeps, as for ldiv!
+// ldiv!(transpose(F), B), ldiv!(adjoint(F), B): solve_t with trans = 1, 2 (the level loops above)
 // ------------------------------------------------------------------------------------------------
-template <class T, bool CONJ>
-static void solve_fwd_t(hs_handle* h, T* db, hipStream_t s) {  // leaves -> root:  z = U11^-T rhs[int];  rhs[bnd] -= Uib^T z
-  flow_arm(h, s);
-  const bool flow = solve_flow_on() && h->d_e1;
-  const SolveNode<T>* sn = (const SolveNode<T>*)h->d_solve;
-  T* w1 = (T*)h->d_w1;
-  T* w2 = (T*)h->d_w2;
-  for (int lv = (int)h->levels.size() - 1; lv >= 0; --lv) {
-    const LevelH& L = h->levels[lv];
-    if (L.mine.empty() || L.maxni == 0) continue;
-    const SolveNode<T>* dn = sn + L.desc_off;
-    const int nb_ = (int)L.mine.size();
-    launch_t_gather<T>(dn, nb_, L.maxni, db, w1, s);
-    if (flow) {  // the whole level in one launch
-      launch_t_fwd_flow<T, CONJ>(dn, nb_, L.maxni, L.maxnb, w1, w2, db, (T*)h->d_e1, (T*)h->d_e2, flow_counter(h, s), h->h_flow_err, s);
-    } else {
-      const int nblk = (L.maxni + hs_solve_t_cols() - 1) / hs_solve_t_cols();
-      for (int blk = 0; blk < nblk; ++blk) launch_t_fwd_step<T, CONJ>(dn, nb_, blk, L.maxm, w1, w2, db, s);
-    }
-    solve_lr_fwd_t<T, CONJ>(h, lv, db, s);
-  }
-}
-template <class T, bool CONJ>
-static void solve_bwd_t(hs_handle* h, T* db, hipStream_t s) {  // root -> leaves:  v = z - Lbi^T rhs[bnd];  rhs[int[rperm]] = L11^-T v
-  flow_arm(h, s);
-  const bool flow = solve_flow_on() && h->d_e1;
-  const SolveNode<T>* sn = (const SolveNode<T>*)h->d_solve;
-  T* w1 = (T*)h->d_w1;
-  T* w2 = (T*)h->d_w2;
-  for (int lv = 0; lv < (int)h->levels.size(); ++lv) {
-    const LevelH& L = h->levels[lv];
-    if (L.mine.empty() || L.maxni == 0) continue;
-    const SolveNode<T>* dn = sn + L.desc_off;
-    const int nb_ = (int)L.mine.size();
-    launch_t_int_update<T, CONJ>(dn, nb_, L.maxni, db, w2, w1, s);
-    solve_lr_bwd_t<T, CONJ>(h, lv, db, s);
-    if (flow) {
-      launch_t_bwd_flow<T, CONJ>(dn, nb_, L.maxni, w1, w2, (T*)h->d_e1, (T*)h->d_e2, flow_counter(h, s), h->h_flow_err, s);
-    } else {
-      const int nblk = (L.maxni + hs_solve_t_cols() - 1) / hs_solve_t_cols();
-      for (int blk = nblk - 1; blk >= 0; --blk) launch_t_bwd_step<T, CONJ>(dn, nb_, blk, w1, w2, s);
-    }
-    launch_t_scatter<T>(dn, nb_, L.maxni, db, w2, s);
-  }
-}
-template <class T>
-static void solve_t(hs_handle* h, int trans, T* db, hipStream_t s) {
-  if (trans == 2 && sizeof(T) == 16) {
-    solve_fwd_t<T, true>(h, db, s);
-    solve_bwd_t<T, true>(h, db, s);
-  } else {
-    solve_fwd_t<T, false>(h, db, s);
-    solve_bwd_t<T, false>(h, db, s);
-  }
-}
 // refuse, never drop: what the transposed sweeps do not cover is named before any device work
 static void check_solve_t(hs_handle* h, int trans, const char* fn) {
   check_handle(h);
@@ -2329,12 +2261,12 @@ extern "C" int hs_ldiv_block_info(const hs_handle* F, double* out6) {
 }
 
 extern "C" int hs_solve_fwd_levels(hs_handle* h, void* d_b, int64_t lv_from, int64_t lv_to, void* stream) {
-  HS_GUARD(check_handle(h); if (h->is_complex) solve_fwd<cplx>(h, (cplx*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream);
-           else solve_fwd<double>(h, (double*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream));
+  HS_GUARD(check_handle(h); if (h->is_complex) solve_fwd<cplx>(h, 0, (cplx*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream);
+           else solve_fwd<double>(h, 0, (double*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream));
 }
 extern "C" int hs_solve_bwd_levels(hs_handle* h, void* d_b, int64_t lv_from, int64_t lv_to, void* stream) {
-  HS_GUARD(check_handle(h); if (h->is_complex) solve_bwd<cplx>(h, (cplx*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream);
-           else solve_bwd<double>(h, (double*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream));
+  HS_GUARD(check_handle(h); if (h->is_complex) solve_bwd<cplx>(h, 0, (cplx*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream);
+           else solve_bwd<double>(h, 0, (double*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream));
 }
 
 // ---- multi-rank plumbing: who owns what, which Schur complements / boundary vectors cross ranks ----------------

@@ -285,8 +285,13 @@ struct SolveNode {
   long long woff;    // offset of this node's ni-segment in the work vectors
   long long poff;    // offset of this node's partial-sum scratch (ceil(nb/512) * ni entries)
 };
+// The launches below are put together, one tree level at a time, by sweep_level_fwd / sweep_level_bwd (hs_sweep.h).
+// gather at the start of a level's forward sweep, scatter at the end of its backward sweep; perm: through the front's row permutation
+// (ldiv!(F, B): the gather; transposed and adjoint: the scatter)
 template <class T>
-void launch_fwd_gather(const SolveNode<T>* dn, int nbatch, int maxni, const T* b, T* w, hipStream_t s);
+void launch_sweep_gather(const SolveNode<T>* dn, int nbatch, int maxni, const T* b, T* w, bool perm, hipStream_t s);
+template <class T>
+void launch_sweep_scatter(const SolveNode<T>* dn, int nbatch, int maxni, T* b, const T* x, bool perm, hipStream_t s);
 template <class T>
 void launch_fwd_step(const SolveNode<T>* dn, int nbatch, int blk, int maxm, T* w, T* y, T* b, hipStream_t s);
 template <class T>
@@ -312,8 +317,6 @@ void launch_fwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, int maxnb, T
                      int force_tall = -1);
 template <class T>
 void launch_bwd_flow(const SolveNode<T>* dn, int nbatch, int maxni, T* w, T* x, T* E1, T* E2, int* counter, int* err, hipStream_t s);
-template <class T>
-void launch_bwd_scatter(const SolveNode<T>* dn, int nbatch, int maxni, T* b, const T* x, hipStream_t s);
 
 // low-rank Gauss transform  X ~= P' * trap(Lp[:, :r]) * Z  applied to a vector (one front per call):
 //   t = Z * x  (x contiguous, or gathered through xidx when xidx != nullptr)      -> launch_lr_zmul
@@ -323,13 +326,9 @@ void launch_lr_zmul(const T* Z, int ldz, int r, int cols, const T* x, const int*
 template <class T>
 void launch_lr_trap(const T* Lp, int ldp, int rows, int r, const int* rp, const T* t, T* dst, const int* didx, hipStream_t s);
 // ldiv!(transpose(F), B) / ldiv!(adjoint(F), B) (kernels_solve_t.hip; CONJ: adjoint).  The same descriptors and work vectors as the sweeps above:
-//   forward:  w = rhs[int] (launch_t_gather);  per 256-column block: z_blk = inv256U^T w_blk, then w[j] / rhs[bnd_j] -= (U11 | Uib)[blk, j]^T z_blk
+//   forward:  w = rhs[int] (launch_sweep_gather);  per 256-column block: z_blk = inv256U^T w_blk, then w[j] / rhs[bnd_j] -= (U11 | Uib)[blk, j]^T z_blk
 //   backward: v = z - Lbi^T rhs[bnd] (launch_t_int_update);  per block, last first: x_blk = inv256L^T v_blk, v[j] -= L11[blk, j]^T x_blk;
-//             rhs[int[rperm[i]]] = x[i] (launch_t_scatter)
-template <class T>
-void launch_t_gather(const SolveNode<T>* dn, int nbatch, int maxni, const T* b, T* w, hipStream_t s);
-template <class T>
-void launch_t_scatter(const SolveNode<T>* dn, int nbatch, int maxni, T* b, const T* x, hipStream_t s);
+//             rhs[int[rperm[i]]] = x[i] (launch_sweep_scatter, perm)
 template <class T, bool CONJ>
 void launch_t_fwd_step(const SolveNode<T>* dn, int nbatch, int blk, int maxm, T* w, T* z, T* b, hipStream_t s);
 template <class T, bool CONJ>

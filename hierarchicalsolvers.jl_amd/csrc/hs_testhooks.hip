@@ -11,6 +11,7 @@
 #include "hs_envelope.h"
 #include "hs_lowrank.h"
 #include "hs_solve_multi.h"
+#include "hs_sweep.h"
 
 #define CK(call)                                                                                   \
   do {                                                                                             \
@@ -520,8 +521,9 @@ static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb
 }
 
 // One tree level of ldiv!: the batch above, factored in mode 2 or 3, then the level's forward and backward sweeps on a global vector (the
-// contract is in include/hs_kernels.h).  The launches and their order are those of solve_fwd / solve_bwd / solve_fwd_t / solve_bwd_t
-// (hs_api.hip) for one level, without the low-rank and HSS calls; `path` stands for the switches HS_SOLVE_FLOW / HS_SOLVE_WIDE.
+// contract is in include/hs_kernels.h).  The sweeps are sweep_level_fwd / sweep_level_bwd (hs_sweep.h), the functions the level loops of
+// hs_api.hip call for every level -- here without the low-rank and HSS calls around and between them, and with `path` given instead of read
+// from HS_SOLVE_FLOW / HS_SOLVE_WIDE (hs_sweep_path).
 template <class T>
 static int sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, const int64_t* flags, int64_t n,
                             const int64_t* fidx, const T* b, int path, int trans, int tall, T* outLF, T* outUR, int64_t* out_rperm, int64_t* info,
@@ -610,10 +612,9 @@ static int sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb
   CK(hipMemset(d.w2, 0, wbytes));
   CK(hipMemset(d.part, 0, sizeof(T) * (size_t)(poff + 1)));
   CK(hipMemcpy(d.b, b, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
-  const SolveNode<T>* dn = fb.dsn;
-  const int nf = (int)count, maxni = fb.maxni, maxnb = fb.maxnb, maxm = fb.maxm;
+  const SweepLevel<T> lvl = {fb.dsn, (int)count, fb.maxni, fb.maxnb, fb.maxm, d.w1, d.w2, d.part, d.b, d.e1, d.e2, d.err};
   const hipStream_t s = nullptr;
-  const int tall_rule = hs_fwd_flow_tall<T>(nf, maxnb);
+  const int tall_rule = hs_fwd_flow_tall<T>(lvl.nfronts, lvl.maxnb);
   if (tall_used) *tall_used = (path == 0 && trans == 0) ? (tall >= 0 ? tall : tall_rule) : 0;
   auto arm = [&]() -> int {  // flow_arm and a fresh workgroup-id counter
     CK(hipMemsetAsync(d.e1, 0xFF, wbytes, s));
@@ -637,35 +638,11 @@ static int sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb
     if (out) CK(hipMemcpy(out, d.b, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost));
     return HS_OK;
   };
-  const bool level_on = maxni > 0;  // (solve_fwd / solve_bwd skip a level without interior DOFs)
+  const bool level_on = lvl.maxni > 0;  // (solve_fwd / solve_bwd skip a level without interior DOFs)
   // forward
   if (level_on) {
     if (int st = arm()) return st;
-    if (trans == 0) {
-      launch_fwd_gather<T>(dn, nf, maxni, d.b, d.w1, s);
-      if (path == 0) {
-        launch_fwd_flow<T>(dn, nf, maxni, maxnb, d.w1, d.w2, d.b, d.e1, d.e2, d.counter, d.err, s, tall);
-      } else if (path == 1) {
-        const int nblk = (maxni + hs_solve_wide_cols() - 1) / hs_solve_wide_cols();
-        for (int blk = 0; blk < nblk; ++blk) launch_fwd_wide<T>(dn, nf, blk, maxm, d.w1, d.w2, d.b, s);
-      } else {
-        const int nblk = (maxni + HS_PB - 1) / HS_PB;
-        for (int blk = 0; blk < nblk; ++blk) launch_fwd_step<T>(dn, nf, blk, maxm, d.w1, d.w2, d.b, s);
-      }
-    } else {
-      launch_t_gather<T>(dn, nf, maxni, d.b, d.w1, s);
-      const int nblk = (maxni + hs_solve_t_cols() - 1) / hs_solve_t_cols();
-      if constexpr (sizeof(T) == 16) {
-        if (trans == 2) {
-          if (path == 0) launch_t_fwd_flow<T, true>(dn, nf, maxni, maxnb, d.w1, d.w2, d.b, d.e1, d.e2, d.counter, d.err, s);
-          else for (int blk = 0; blk < nblk; ++blk) launch_t_fwd_step<T, true>(dn, nf, blk, maxm, d.w1, d.w2, d.b, s);
-        }
-      }
-      if (trans == 1) {
-        if (path == 0) launch_t_fwd_flow<T, false>(dn, nf, maxni, maxnb, d.w1, d.w2, d.b, d.e1, d.e2, d.counter, d.err, s);
-        else for (int blk = 0; blk < nblk; ++blk) launch_t_fwd_step<T, false>(dn, nf, blk, maxm, d.w1, d.w2, d.b, s);
-      }
-    }
+    sweep_level_fwd<T>(lvl, path, trans, d.counter, s, tall);
     if (int st = finish("forward")) return st;
   }
   if (int st = copy_w(out_y)) return st;
@@ -673,34 +650,7 @@ static int sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb
   // backward, on the b and y the forward sweep left
   if (level_on) {
     if (int st = arm()) return st;
-    if (trans == 0) {
-      launch_int_update<T>(dn, nf, maxni, maxnb, d.b, d.part, d.w2, d.w1, s);
-      if (path == 0) {
-        launch_bwd_flow<T>(dn, nf, maxni, d.w1, d.w2, d.e1, d.e2, d.counter, d.err, s);
-      } else if (path == 1) {
-        const int nw = (maxni + hs_solve_wide_cols() - 1) / hs_solve_wide_cols();
-        for (int blk = nw - 1; blk >= 0; --blk) launch_bwd_wide<T>(dn, nf, blk, d.w1, d.w2, s, blk == nw - 1);
-      } else {
-        const int nblk = (maxni + HS_PB - 1) / HS_PB;
-        for (int blk = nblk - 1; blk >= 0; --blk) launch_bwd_step<T>(dn, nf, blk, d.w1, d.w2, s);
-      }
-      launch_bwd_scatter<T>(dn, nf, maxni, d.b, d.w2, s);
-    } else {
-      const int nblk = (maxni + hs_solve_t_cols() - 1) / hs_solve_t_cols();
-      if constexpr (sizeof(T) == 16) {
-        if (trans == 2) {
-          launch_t_int_update<T, true>(dn, nf, maxni, d.b, d.w2, d.w1, s);
-          if (path == 0) launch_t_bwd_flow<T, true>(dn, nf, maxni, d.w1, d.w2, d.e1, d.e2, d.counter, d.err, s);
-          else for (int blk = nblk - 1; blk >= 0; --blk) launch_t_bwd_step<T, true>(dn, nf, blk, d.w1, d.w2, s);
-        }
-      }
-      if (trans == 1) {
-        launch_t_int_update<T, false>(dn, nf, maxni, d.b, d.w2, d.w1, s);
-        if (path == 0) launch_t_bwd_flow<T, false>(dn, nf, maxni, d.w1, d.w2, d.e1, d.e2, d.counter, d.err, s);
-        else for (int blk = nblk - 1; blk >= 0; --blk) launch_t_bwd_step<T, false>(dn, nf, blk, d.w1, d.w2, s);
-      }
-      launch_t_scatter<T>(dn, nf, maxni, d.b, d.w2, s);
-    }
+    sweep_level_bwd<T>(lvl, path, trans, d.counter, s);
     if (int st = finish("backward")) return st;
   }
   if (int st = copy_w(out_x)) return st;
@@ -721,6 +671,7 @@ extern "C" int hsk_sweep_level_z(int64_t count, const int64_t* ni, const int64_t
                                 out_rperm, info, growth, (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, (cplx*)y,
                                 (cplx*)b_fwd, (cplx*)x, (cplx*)b_bwd, tall_used);
 }
+extern "C" int hsk_sweep_path() { return hs_sweep_path(); }
 extern "C" int hsk_flow_tall_rule(int is_complex, int64_t nbatch, int64_t maxnb) {
   if (nbatch < 0 || nbatch > 0x7fffffff || maxnb < 0 || maxnb > 0x7fffffff) return -1;
   return is_complex ? hs_fwd_flow_tall<cplx>((int)nbatch, (int)maxnb) : hs_fwd_flow_tall<double>((int)nbatch, (int)maxnb);

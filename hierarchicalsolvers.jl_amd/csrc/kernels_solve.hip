@@ -14,14 +14,25 @@
 // 32-vector from the stored inverse diagonal block (32x32 matvec in LDS), then updates its own 256
 // rows with the 32-column panel below (forward; rows >= ni are the Lbi rows and update rhs[bnd]
 // through the front's index list) or above (backward).  One right-hand side per launch.
+// Which of these launches, and of those of kernels_solve_wide.hip / kernels_solve_t.hip, make up a level's sweep: hs_sweep.h.
 #include "hs_common.h"
 
-template <class T>
-__global__ __launch_bounds__(256) void fwd_gather_kernel(const SolveNode<T>* __restrict__ nodes, const T* __restrict__ b, T* __restrict__ w) {
+// w = rhs[int] of every front of the level at the start of its forward sweep, rhs[int] = x at the end of its backward sweep.  PERM: through
+// the row permutation rperm of the front's LU -- ldiv!(F, B) permutes on the gather (y = L11^-1 P rhs[int]), the transposed and adjoint sweeps
+// (kernels_solve_t.hip) on the scatter (rhs[int[rperm[i]]] = x[i])
+template <class T, bool PERM>
+__global__ __launch_bounds__(256) void sweep_gather_kernel(const SolveNode<T>* __restrict__ nodes, const T* __restrict__ b, T* __restrict__ w) {
   const SolveNode<T> nd = nodes[blockIdx.y];
-  int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= nd.ni) return;
-  w[nd.woff + i] = b[gld(nd.fidx + gld(nd.rperm + i))];
+  w[nd.woff + i] = b[gld(nd.fidx + (PERM ? gld(nd.rperm + i) : i))];
+}
+template <class T, bool PERM>
+__global__ __launch_bounds__(256) void sweep_scatter_kernel(const SolveNode<T>* __restrict__ nodes, T* __restrict__ b, const T* __restrict__ x) {
+  const SolveNode<T> nd = nodes[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nd.ni) return;
+  b[gld(nd.fidx + (PERM ? gld(nd.rperm + i) : i))] = x[nd.woff + i];
 }
 
 // forward step on column block `blk`: y_blk = invL * w_blk ; rows below -= L[:, blk] * y_blk
@@ -122,14 +133,6 @@ __global__ __launch_bounds__(256) void bwd_step_kernel(const SolveNode<T>* __res
 #pragma unroll 32
   for (int j = 0; j < wl; ++j) acc = Scal<T>::fma(gld(a + (size_t)j * nd.ldl), s_x[j], acc);
   w[nd.woff + r] = w[nd.woff + r] - acc;
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void bwd_scatter_kernel(const SolveNode<T>* __restrict__ nodes, T* __restrict__ b, const T* __restrict__ x) {
-  const SolveNode<T> nd = nodes[blockIdx.y];
-  int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nd.ni) return;
-  b[gld(nd.fidx + i)] = x[nd.woff + i];
 }
 
 // ---- low-rank Gauss transforms (compressed fronts) ---------------------------------------------------
@@ -242,9 +245,10 @@ void launch_unpack_idx(const int* idx, int cnt, void* b, const void* buf, int es
 
 // ---- launchers ---------------------------------------------------------------------------------
 template <class T>
-void launch_fwd_gather(const SolveNode<T>* dn, int nbatch, int maxni, const T* b, T* w, hipStream_t s) {
+void launch_sweep_gather(const SolveNode<T>* dn, int nbatch, int maxni, const T* b, T* w, bool perm, hipStream_t s) {
   if (nbatch <= 0 || maxni <= 0) return;
-  hipLaunchKernelGGL(fwd_gather_kernel<T>, dim3((maxni + 255) / 256, nbatch), dim3(256), 0, s, dn, b, w);
+  const auto k = perm ? sweep_gather_kernel<T, true> : sweep_gather_kernel<T, false>;
+  hipLaunchKernelGGL(k, dim3((maxni + 255) / 256, nbatch), dim3(256), 0, s, dn, b, w);
 }
 template <class T>
 void launch_fwd_step(const SolveNode<T>* dn, int nbatch, int blk, int maxm, T* w, T* y, T* b, hipStream_t s) {
@@ -269,16 +273,17 @@ void launch_bwd_step(const SolveNode<T>* dn, int nbatch, int blk, T* w, T* x, hi
   hipLaunchKernelGGL(bwd_step_kernel<T>, dim3(gx, nbatch), dim3(256), 0, s, dn, blk, w, x);
 }
 template <class T>
-void launch_bwd_scatter(const SolveNode<T>* dn, int nbatch, int maxni, T* b, const T* x, hipStream_t s) {
+void launch_sweep_scatter(const SolveNode<T>* dn, int nbatch, int maxni, T* b, const T* x, bool perm, hipStream_t s) {
   if (nbatch <= 0 || maxni <= 0) return;
-  hipLaunchKernelGGL(bwd_scatter_kernel<T>, dim3((maxni + 255) / 256, nbatch), dim3(256), 0, s, dn, b, x);
+  const auto k = perm ? sweep_scatter_kernel<T, true> : sweep_scatter_kernel<T, false>;
+  hipLaunchKernelGGL(k, dim3((maxni + 255) / 256, nbatch), dim3(256), 0, s, dn, b, x);
 }
 
 #define INST(T)                                                                                              \
-  template void launch_fwd_gather<T>(const SolveNode<T>*, int, int, const T*, T*, hipStream_t);              \
+  template void launch_sweep_gather<T>(const SolveNode<T>*, int, int, const T*, T*, bool, hipStream_t);      \
   template void launch_fwd_step<T>(const SolveNode<T>*, int, int, int, T*, T*, T*, hipStream_t);             \
   template void launch_int_update<T>(const SolveNode<T>*, int, int, int, const T*, T*, const T*, T*, hipStream_t); \
   template void launch_bwd_step<T>(const SolveNode<T>*, int, int, T*, T*, hipStream_t);                      \
-  template void launch_bwd_scatter<T>(const SolveNode<T>*, int, int, T*, const T*, hipStream_t);
+  template void launch_sweep_scatter<T>(const SolveNode<T>*, int, int, T*, const T*, bool, hipStream_t);
 INST(double)
 INST(cplx)

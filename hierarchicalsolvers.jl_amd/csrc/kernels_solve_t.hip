@@ -19,6 +19,7 @@
 #include "hs_flow.h"
 
 #define HS_TW 256  // columns per sweep step (the stored inverses of the 256 x 256 diagonal blocks)
+static_assert(HS_TW == HS_FLOW_W, "flow_interior decodes sub-blocks of HS_FLOW_W columns");
 #define HS_TCPW 8  // output columns per wavefront and pass of a workgroup (4 wavefronts: 32 columns per workgroup)
 #define HS_TCH 1024  // reduction entries staged in LDS per chunk
 
@@ -37,21 +38,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 __device__ __forceinline__ cplx wave_sum(cplx v) { return {wave_sum(v.re), wave_sum(v.im)}; }
 
-// ---- gather / scatter ----------------------------------------------------------------------------
-template <class T>
-__global__ __launch_bounds__(256) void t_gather_kernel(const SolveNode<T>* __restrict__ nodes, const T* __restrict__ b, T* __restrict__ w) {
-  const SolveNode<T> nd = nodes[blockIdx.y];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nd.ni) return;
-  w[nd.woff + i] = b[gld(nd.fidx + i)];
-}
-template <class T>
-__global__ __launch_bounds__(256) void t_scatter_kernel(const SolveNode<T>* __restrict__ nodes, T* __restrict__ b, const T* __restrict__ x) {
-  const SolveNode<T> nd = nodes[blockIdx.y];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nd.ni) return;
-  b[gld(nd.fidx + gld(nd.rperm + i))] = x[nd.woff + i];
-}
+// (gather and scatter: sweep_gather_kernel / sweep_scatter_kernel of kernels_solve.hip, with the row permutation on the scatter)
 
 // ---- diagonal block: dst[c0 + c] = sum_k cj(inv[k + c * 256]) * src[c0 + k] ------------------------------
 // UPPER: inv = inv256U of block blk (upper triangular: k <= c), else inv256L (lower: k >= c).  grid.x = 8 (32 output columns each).
@@ -228,7 +215,7 @@ __global__ __launch_bounds__(256) void t_lr_zt_kernel(const T* __restrict__ Z, i
 
 // ---- the dataflow sweep of one level (HS_SOLVE_FLOW=1, the default) ------------------------------------------------------------
 // FWD: z = U11^-T w (w = rhs[int] gathered) and rhs[bnd] -= Uib^T z;  !FWD: x = L11^-T v (v = z - Lbi^T rhs[bnd]).  The skeleton of
-// flow_sweep_kernel: workgroup ids from an atomic counter in start order (block-major, front-minor), values published into the sentinel-armed
+// flow_sweep_kernel, shared through hs_flow.h (flow_claim, flow_interior, flow_poll, flow_rounds, flow_raise, flow_publish): workgroup ids from an atomic counter in start order (block-major, front-minor), values published into the sentinel-armed
 // exchange vectors (E1: z / x, E2: the finished w of a diagonal block) and polled with bounded waits (*err on run-out), the tile of the next
 // round requested before this round's vector is waited for.  What changes is the tile: a workgroup OWNS FB output columns [rs, rs + FB) --
 // columns of U11 (Uib, L11) -- and reads them over the rows of one 256-block per round, so the 256 threads run along the rows (the contiguous,
@@ -241,34 +228,6 @@ struct TFlowCfg {
   static constexpr int FB = sizeof(T) == 8 ? 32 : 16;  // output columns a workgroup owns: 32 data registers per thread and tile either way
   static constexpr int Q = HS_TW / FB;                 // sub-blocks per 256-column block
 };
-// thread t's element of a published vector (cnt entries; zero beyond); false when the wait ran out
-__device__ __forceinline__ bool t_poll(const double* src, int cnt, int t, double& v) {
-  v = 0.0;
-  if (t >= cnt) return true;
-  for (int it = 0; it < HS_FLOW_SPIN; ++it) {
-    const unsigned long long x = flow_ldbits(src + t);
-    if (x != HS_SENT) {
-      v = __longlong_as_double((long long)x);
-      return true;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return false;
-}
-__device__ __forceinline__ bool t_poll(const cplx* src, int cnt, int t, cplx& v) {
-  v = cplx{0.0, 0.0};
-  if (t >= cnt) return true;
-  const double* p = reinterpret_cast<const double*>(src + t);
-  for (int it = 0; it < HS_FLOW_SPIN; ++it) {
-    const unsigned long long a = flow_ldbits(p), b = flow_ldbits(p + 1);
-    if (a != HS_SENT && b != HS_SENT) {
-      v = cplx{__longlong_as_double((long long)a), __longlong_as_double((long long)b)};
-      return true;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return false;
-}
 // the thread's row of a tile: element (row t, column c) of base (ld), rows clamped to nrow, columns to ncol (what a clamped load brings in is
 // multiplied by a zero of the vector or lands in a column nobody stores).  `base` and `ld` are workgroup-uniform: scalar column offsets.
 template <class T, int FB>
@@ -296,30 +255,24 @@ template <class T, bool CONJ, bool FWD>
 __global__ __launch_bounds__(256) void t_flow_kernel(const SolveNode<T>* __restrict__ nodes, int nbatch, const T* __restrict__ w, T* __restrict__ out,
                                                      T* __restrict__ b, T* __restrict__ E1, T* __restrict__ E2, int* __restrict__ counter, int* __restrict__ err) {
   constexpr int FB = TFlowCfg<T>::FB, Q = TFlowCfg<T>::Q;
-  __shared__ int s_id;
   __shared__ T s_red[4 * FB];
   __shared__ T s_own[FB];
   const int t = threadIdx.x;
-  if (t == 0) s_id = atomicAdd(counter, 1);
-  __syncthreads();
-  const int id = __builtin_amdgcn_readfirstlane(s_id), f = id % nbatch, sb = id / nbatch;
-  const SolveNode<T> nd = nodes[f];
+  const FlowId id = flow_claim(counter, nbatch);
+  const int sb = id.sb;
+  const SolveNode<T> nd = nodes[id.f];
   if (nd.ni <= 0) return;
   const int ncb = (nd.ni + HS_TW - 1) / HS_TW;
-  bool interior = true;
+  const bool interior = sb < Q * ncb;
+  if (!FWD && !interior) return;
   int jb, q, rs, rl;
-  if (FWD && sb >= Q * ncb) {  // boundary columns [rs, rs + FB) of Uib: every interior block feeds them
-    interior = false;
+  if (interior) {
+    flow_interior<FB>(sb, ncb, nd.ni, !FWD, jb, q, rs, rl);
+  } else {  // boundary columns [rs, rs + FB) of Uib: every interior block feeds them
     jb = ncb;
     q = 0;
     rs = (sb - Q * ncb) * FB;
     rl = min(FB, nd.mrows - nd.ni - rs);
-  } else {
-    if (sb >= Q * ncb) return;
-    jb = FWD ? sb / Q : ncb - 1 - sb / Q;
-    q = FWD ? sb % Q : Q - 1 - sb % Q;
-    rs = jb * HS_TW + q * FB;
-    rl = min(FB, nd.ni - rs);
   }
   if (rl <= 0) return;
   // the tile of round c: rows of block kb(c) of the owned columns (FWD: U11 / Uib above the block, !FWD: L11 below it)
@@ -337,31 +290,13 @@ __global__ __launch_bounds__(256) void t_flow_kernel(const SolveNode<T>* __restr
   auto round = [&](const T(&v)[FB], int c) -> bool {
     const int kb = FWD ? c : ncb - 1 - c;
     T x;
-    const bool ok = t_poll(E1 + nd.woff + (size_t)kb * HS_TW, min(HS_TW, nd.ni - kb * HS_TW), t, x);
+    const bool ok = flow_poll(E1 + nd.woff + (size_t)kb * HS_TW, min(HS_TW, nd.ni - kb * HS_TW), t, x);
     if (__builtin_amdgcn_readfirstlane(__syncthreads_or(ok ? 0 : 1))) return false;
 #pragma unroll
     for (int cc = 0; cc < FB; ++cc) acc[cc] = Scal<T>::fma(cj<CONJ>(v[cc]), x, acc[cc]);
     return true;
   };
-  bool alive = true;
-  int c = 0;
-  if (nr & 1) {
-    request(va, 0);
-    alive = round(va, 0);
-    c = 1;
-  }
-  request(va, c);
-  while (c < nr && alive) {
-    request(vb, c + 1);
-    alive = round(va, c);
-    request(va, c + 2);
-    if (alive) alive = round(vb, c + 1);
-    c += 2;
-  }
-  if (!alive) {
-    if (t == 0) *(volatile int*)err = 1;  // pinned host memory: a plain store
-    return;
-  }
+  if (!flow_rounds(nr, va, vb, request, round)) return flow_raise(err, t);
   const int wlj = interior ? min(HS_TW, nd.ni - jb * HS_TW) : 1;
   const T* inv = (FWD ? nd.inv256U : nd.inv256L) + (size_t)jb * HS_TW * HS_TW + (size_t)(q * FB) * HS_TW;
   if (interior) t_load<T, FB>(va, inv, HS_TW, rl, wlj, t);  // the slab of the inverse, in flight during the reduction
@@ -386,11 +321,8 @@ __global__ __launch_bounds__(256) void t_flow_kernel(const SolveNode<T>* __restr
   if (t >= own_lo && t < own_lo + rl)
     x = s_own[t - own_lo];
   else if (t >= lo && t < hi)
-    ok = t_poll(E2 + nd.woff + (size_t)jb * HS_TW, hi, t, x);
-  if (__builtin_amdgcn_readfirstlane(__syncthreads_or(ok ? 0 : 1))) {
-    if (t == 0) *(volatile int*)err = 1;
-    return;
-  }
+    ok = flow_poll(E2 + nd.woff + (size_t)jb * HS_TW, hi, t, x);
+  if (__builtin_amdgcn_readfirstlane(__syncthreads_or(ok ? 0 : 1))) return flow_raise(err, t);
 #pragma unroll
   for (int cc = 0; cc < FB; ++cc) {
     const int col = own_lo + cc;
@@ -407,16 +339,6 @@ __global__ __launch_bounds__(256) void t_flow_kernel(const SolveNode<T>* __restr
 // ---- launchers ------------------------------------------------------------------------------------------------------------
 static inline int t_groups(int cols) { return (cols + 4 * HS_TCPW - 1) / (4 * HS_TCPW); }
 
-template <class T>
-void launch_t_gather(const SolveNode<T>* dn, int nbatch, int maxni, const T* b, T* w, hipStream_t s) {
-  if (nbatch <= 0 || maxni <= 0) return;
-  hipLaunchKernelGGL(t_gather_kernel<T>, dim3((maxni + 255) / 256, nbatch), dim3(256), 0, s, dn, b, w);
-}
-template <class T>
-void launch_t_scatter(const SolveNode<T>* dn, int nbatch, int maxni, T* b, const T* x, hipStream_t s) {
-  if (nbatch <= 0 || maxni <= 0) return;
-  hipLaunchKernelGGL(t_scatter_kernel<T>, dim3((maxni + 255) / 256, nbatch), dim3(256), 0, s, dn, b, x);
-}
 int hs_solve_t_cols() { return HS_TW; }
 template <class T, bool CONJ>
 void launch_t_fwd_step(const SolveNode<T>* dn, int nbatch, int blk, int maxm, T* w, T* z, T* b, hipStream_t s) {
@@ -465,9 +387,6 @@ void launch_t_lr_zt(const T* Z, int ldz, int r, int cols, const T* t, T* dst, co
   hipLaunchKernelGGL((t_lr_zt_kernel<T, CONJ>), dim3(t_groups(cols)), dim3(256), 0, s, Z, ldz, r, cols, t, dst, didx);
 }
 
-#define INST_T(T)                                                                                  \
-  template void launch_t_gather<T>(const SolveNode<T>*, int, int, const T*, T*, hipStream_t);     \
-  template void launch_t_scatter<T>(const SolveNode<T>*, int, int, T*, const T*, hipStream_t);
 #define INST_TC(T, C)                                                                                                                   \
   template void launch_t_fwd_step<T, C>(const SolveNode<T>*, int, int, int, T*, T*, T*, hipStream_t);                                  \
   template void launch_t_bwd_step<T, C>(const SolveNode<T>*, int, int, T*, T*, hipStream_t);                                           \
@@ -476,8 +395,6 @@ void launch_t_lr_zt(const T* Z, int ldz, int r, int cols, const T* t, T* dst, co
   template void launch_t_int_update<T, C>(const SolveNode<T>*, int, int, const T*, const T*, T*, hipStream_t);                        \
   template void launch_t_lr_ct<T, C>(const T*, int, int, int, const T*, const int*, T*, T*, hipStream_t);                            \
   template void launch_t_lr_zt<T, C>(const T*, int, int, int, const T*, T*, const int*, hipStream_t);
-INST_T(double)
-INST_T(cplx)
 INST_TC(double, false)
 INST_TC(cplx, false)
 INST_TC(cplx, true)

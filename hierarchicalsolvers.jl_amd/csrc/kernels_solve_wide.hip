@@ -1,6 +1,7 @@
 // kernels_solve_wide.hip -- the triangular sweeps of ldiv!: inverses of the 256 x 256 diagonal blocks (inv256_kernel), the sweeps advancing 256
 // columns per launch (fwd_wide / bwd_wide: HS_SOLVE_FLOW=0), and -- the default since round 3 -- the sweeps of a whole tree level as ONE
-// dataflow launch (flow_sweep_kernel, second half of the file; DESIGN.md section 4a').
+// dataflow launch (flow_sweep_kernel, second half of the file; DESIGN.md section 4a'; what it shares with the transposed t_flow_kernel --
+// exchange, workgroup-id claim, sub-block decode, round loop -- is hs_flow.h).  hs_sweep.h picks among the three per level (hs_sweep_path).
 //
 // Reference: `_lsolve!` / `_dsolve!` / `_rsolve!` (src/factornode.jl:77-99); kernels_solve.hip has the 32-column
 // version of the same right-looking sweeps.  A 32-column step moves at most 8 MB (a 32,768-row panel), far too little to
@@ -11,9 +12,10 @@
 // redundantly, the block comes from L2) followed by the 256-column panel update of the workgroup's own 256 rows:
 // up to 64 MB per launch and 8x fewer launches.
 #include "hs_common.h"
-#include "hs_flow.h"  // HS_FLOW_SPIN, HS_SENT, flow_ldbits, flow_publish (shared with kernels_solve_t.hip)
+#include "hs_flow.h"  // the skeleton of the dataflow sweeps: exchange, workgroup-id claim, round loop (shared with kernels_solve_t.hip)
 
 #define HS_SW 256  // columns per launch
+static_assert(HS_SW == HS_FLOW_W, "flow_interior decodes sub-blocks of HS_FLOW_W columns");
 
 // ------------------------------------------------------------------------------------------------
 // inverses of the 256 x 256 diagonal blocks.  grid.x = (256-block, block column j of it), grid.y = front, grid.z = L / U
@@ -375,45 +377,20 @@ struct FlowCfg {
   static constexpr int Q = HS_SW / FB;                  // sub-blocks per 256-block
 };
 // thread t < 256 fetches element t of a published vector (cnt <= 256 entries) into dst[t], zero beyond cnt; false when the wait ran out
-__device__ __forceinline__ bool flow_poll(const double* src, int cnt, double* dst, int t) {
+template <class T>
+__device__ __forceinline__ bool flow_poll_lds(const T* src, int cnt, T* dst, int t) {
   if (t >= HS_SW) return true;
-  if (t >= cnt) {
-    dst[t] = 0.0;
-    return true;
-  }
-  for (int it = 0; it < HS_FLOW_SPIN; ++it) {
-    const unsigned long long v = flow_ldbits(src + t);
-    if (v != HS_SENT) {
-      dst[t] = __longlong_as_double((long long)v);
-      return true;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return false;
-}
-__device__ __forceinline__ bool flow_poll(const cplx* src, int cnt, cplx* dst, int t) {
-  if (t >= HS_SW) return true;
-  if (t >= cnt) {
-    dst[t] = cplx{0.0, 0.0};
-    return true;
-  }
-  const double* q = reinterpret_cast<const double*>(src + t);
-  for (int it = 0; it < HS_FLOW_SPIN; ++it) {
-    const unsigned long long a = flow_ldbits(q), b = flow_ldbits(q + 1);
-    if (a != HS_SENT && b != HS_SENT) {
-      dst[t] = cplx{__longlong_as_double((long long)a), __longlong_as_double((long long)b)};
-      return true;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return false;
+  T v;
+  const bool ok = flow_poll(src, cnt, t, v);
+  dst[t] = v;
+  return ok;
 }
 // The thread's share of a tile, in registers: every load issued before anything uses it and none depending on the data the workgroup waits
 // for -- so the tile of the NEXT round is requested before this round's vector is polled (the loop below keeps two of them).  Measured on
 // the way here: with the loads in a loop the compiler issued them in small dependent groups and a 64 x 256 tile cost ~8 us on an idle chip;
 // as one batch ~2.5 us.  Addresses are clamped instead of guarded (rows past rl, columns past `ncol`): what they bring in is multiplied by
 // a zero of the vector or lands in a row nobody stores.  `base` is workgroup-uniform.
-// (buffer loads: the tile base goes into a 128-bit descriptor held in SGPRs, the lane's part of the address is ONE 32-bit byte offset and the
+// (buffer loads: the tile base goes into a 128-bit descriptor held in SGPRs (flow_rsrc, hs_flow.h), the lane's part of the address is ONE 32-bit byte offset and the
 // column's a scalar offset -- with 64-bit flat addresses the 32 loads in flight of two tiles took 128 address registers and the kernel spilled)
 typedef unsigned int flow_u2 __attribute__((ext_vector_type(2)));
 typedef unsigned int flow_u4 __attribute__((ext_vector_type(4)));
@@ -430,13 +407,7 @@ __device__ __forceinline__ void flow_load(T (&v)[FlowCfg<T>::GC], const T* base,
   constexpr int FB = FlowCfg<T>::FB, SC = FlowCfg<T>::SC, GC = FlowCfg<T>::GC;
   const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
   const unsigned row = (unsigned)min(lane % FB, rl - 1);
-  // (the descriptor must be PROVABLY uniform or every load becomes a waterfall loop: readfirstlane its inputs)
-  const unsigned long long pb = (unsigned long long)base;
-  const unsigned plo = __builtin_amdgcn_readfirstlane((unsigned)pb), phi = __builtin_amdgcn_readfirstlane((unsigned)(pb >> 32));
-  ld = __builtin_amdgcn_readfirstlane(ld);
-  ncol = __builtin_amdgcn_readfirstlane(ncol);
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(((unsigned long long)phi << 32) | plo), 0, 0x7FFFFFFF, 0x00020000);  // (256 columns of a front: < 2^31 bytes)
+  const __amdgpu_buffer_rsrc_t r = flow_rsrc(base, ld, ncol);
   if constexpr (SC == 1) {
     const unsigned voff = row * (unsigned)sizeof(T);
 #pragma unroll
@@ -491,11 +462,7 @@ __device__ __forceinline__ void flow_load_b(T (&v)[FlowBCfg<T>::GC], const T* ba
   constexpr int RG = FlowBCfg<T>::RG, GC = FlowBCfg<T>::GC;
   const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), rg = wv % RG, cg = wv / RG;
   const unsigned row = (unsigned)min(rg * 64 + lane, rl - 1);
-  const unsigned long long pb = (unsigned long long)base;
-  const unsigned plo = __builtin_amdgcn_readfirstlane((unsigned)pb), phi = __builtin_amdgcn_readfirstlane((unsigned)(pb >> 32));
-  ld = __builtin_amdgcn_readfirstlane(ld);
-  ncol = __builtin_amdgcn_readfirstlane(ncol);
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(((unsigned long long)phi << 32) | plo), 0, 0x7FFFFFFF, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r = flow_rsrc(base, ld, ncol);
   const unsigned voff = row * (unsigned)sizeof(T);
 #pragma unroll
   for (int j = 0; j < GC; ++j) {
@@ -526,39 +493,25 @@ __global__ __launch_bounds__(HS_FLOW_NT) void flow_sweep_kernel(const SolveNode<
                                                          int* __restrict__ err, int tall) {
   constexpr int FB = FlowCfg<T>::FB, Q = FlowCfg<T>::Q, GC = FlowCfg<T>::GC;
   using V = T;
-  __shared__ int s_id;
   __shared__ T s_v[HS_SW];
   __shared__ T s_red[FB * FlowCfg<T>::NP];
   const int t = threadIdx.x;
-  if (t == 0) s_id = atomicAdd(counter, 1);
-  __syncthreads();
-  const int id = __builtin_amdgcn_readfirstlane(s_id), f = id % nbatch, sb = id / nbatch;  // (scalar: the front's descriptor and every tile base stay in SGPRs)
+  const FlowId id = flow_claim(counter, nbatch);
+  const int f = id.f, sb = id.sb;
   const SolveNode<T> nd = nodes[f];
   if (nd.ni <= 0) return;
   const int ncb = (nd.ni + HS_SW - 1) / HS_SW;
+  const bool interior = sb < Q * ncb;
+  if (UPPER && !interior) return;
   int jb, q, rs, rl;
-  bool interior;
-  if (!UPPER) {
-    interior = sb < Q * ncb;
-    if (interior) {
-      jb = sb / Q;
-      q = sb % Q;
-      rs = jb * HS_SW + q * FB;
-      rl = min(FB, nd.ni - rs);
-    } else {
-      jb = ncb;  // all column blocks
-      q = 0;
-      const int fbb = tall ? FlowBCfg<T>::FBB : FB;  // tall boundary tiles only where the level has enough of them to fill the chip (launch_fwd_flow)
-      rs = nd.ni + (sb - Q * ncb) * fbb;
-      rl = min(fbb, nd.mrows - rs);
-    }
+  if (interior) {
+    flow_interior<FB>(sb, ncb, nd.ni, UPPER, jb, q, rs, rl);
   } else {
-    interior = true;
-    if (sb >= Q * ncb) return;
-    jb = ncb - 1 - sb / Q;
-    q = Q - 1 - sb % Q;
-    rs = jb * HS_SW + q * FB;
-    rl = min(FB, nd.ni - rs);
+    jb = ncb;  // all column blocks
+    q = 0;
+    const int fbb = tall ? FlowBCfg<T>::FBB : FB;  // tall boundary tiles only where the level has enough of them to fill the chip (launch_fwd_flow)
+    rs = nd.ni + (sb - Q * ncb) * fbb;
+    rl = min(fbb, nd.mrows - rs);
   }
   if (rl <= 0) return;
   if (!UPPER && !interior && tall) {  // tall tiles: FBB rows x 64 columns (FlowBCfg)
@@ -580,31 +533,13 @@ __global__ __launch_bounds__(HS_FLOW_NT) void flow_sweep_kernel(const SolveNode<
     };
     auto round_b = [&](const T(&v)[GB], int c) -> bool {
       const int wl = min(CT, nd.ni - c * CT);
-      const bool ok = t < CT ? flow_poll(E1 + nd.woff + (size_t)c * CT, wl, s_v, t) : true;
+      const bool ok = t < CT ? flow_poll_lds(E1 + nd.woff + (size_t)c * CT, wl, s_v, t) : true;
       if (__builtin_amdgcn_readfirstlane(__syncthreads_or(ok ? 0 : 1))) return false;
       flow_fma_b<T>(v, s_v, t, sb_);
       __syncthreads();
       return true;
     };
-    bool alive_b = true;
-    int c = 0;
-    if (nr & 1) {
-      request_b(ua, 0);
-      alive_b = round_b(ua, 0);
-      c = 1;
-    }
-    request_b(ua, c);
-    while (c < nr && alive_b) {
-      request_b(ub, c + 1);
-      alive_b = round_b(ua, c);
-      request_b(ua, c + 2);
-      if (alive_b) alive_b = round_b(ub, c + 1);
-      c += 2;
-    }
-    if (!alive_b) {
-      if (t == 0) *(volatile int*)err = 1;
-      return;
-    }
+    if (!flow_rounds(nr, ua, ub, request_b, round_b)) return flow_raise(err, t);
     {  // partial sums of the CG column groups meet in LDS
       const int lane = t & 63, wv = t >> 6, rg = wv % RG, cg = wv / RG;
       s_red[cg * FBB + rg * 64 + lane] = sb_;
@@ -652,33 +587,16 @@ __global__ __launch_bounds__(HS_FLOW_NT) void flow_sweep_kernel(const SolveNode<
   auto round = [&](const V(&v)[GC], int c) -> bool {
     const int k = kfirst + c * kstep;
     const int wl = min(HS_SW, nd.ni - k * HS_SW);
-    const bool ok = flow_poll(E1 + nd.woff + (size_t)k * HS_SW, wl, s_v, t);
+    const bool ok = flow_poll_lds(E1 + nd.woff + (size_t)k * HS_SW, wl, s_v, t);
     if (__builtin_amdgcn_readfirstlane(__syncthreads_or(ok ? 0 : 1))) return false;  // (also publishes s_v to the workgroup; readfirstlane: the loop
                                                                                         // counter must stay provably uniform, or every buffer load turns into a waterfall loop)
     flow_fma<T>(v, s_v, t, s);
     __syncthreads();  // s_v is refilled by the next round
     return true;
   };
-  bool alive = true;
-  int c = 0;
-  if (kcount & 1) {  // an odd count: one round on its own first, so that the pairs below always end with the inverse in `va`
-    request(va, 0);
-    alive = round(va, 0);
-    c = 1;
-  }
-  request(va, c);
-  while (c < kcount && alive) {
-    request(vb, c + 1);
-    alive = round(va, c);
-    request(va, c + 2);  // (c + 2 == kcount: the slab of the inverse, requested before the last y is waited for)
-    if (alive) alive = round(vb, c + 1);
-    c += 2;
-  }
+  const bool alive = flow_rounds(kcount, va, vb, request, round);  // (ends with the slab of the inverse in `va`)
   FLOW_T(0);  // last round done (y of the block before arrived, FMAs done)
-  if (!alive) {
-    if (t == 0) *(volatile int*)err = 1;  // pinned host memory: a plain store
-    return;
-  }
+  if (!alive) return flow_raise(err, t);
   flow_put<T>(s_red, t, s);
   __syncthreads();
   T wfin = Scal<T>::zero();
@@ -696,16 +614,13 @@ __global__ __launch_bounds__(HS_FLOW_NT) void flow_sweep_kernel(const SolveNode<
     const bool own = t >= own_lo && t < own_lo + FB;
     if (!own) {
       if (t >= c_lo && t < c_hi)
-        ok = flow_poll(E2 + nd.woff + (size_t)jb * HS_SW, c_hi, s_v, t);  // element t of the block's finished w
+        ok = flow_poll_lds(E2 + nd.woff + (size_t)jb * HS_SW, c_hi, s_v, t);  // element t of the block's finished w
       else
         s_v[t] = Scal<T>::zero();
     }
     if (t < FB) s_v[own_lo + t] = wfin;  // own rows: no round trip (zero beyond rl)
   }
-  if (__builtin_amdgcn_readfirstlane(__syncthreads_or(ok ? 0 : 1))) {
-    if (t == 0) *(volatile int*)err = 1;
-    return;
-  }
+  if (__builtin_amdgcn_readfirstlane(__syncthreads_or(ok ? 0 : 1))) return flow_raise(err, t);
   FLOW_T(2);  // w of the block arrived
   {
     T s2 = Scal<T>::zero();
@@ -816,12 +731,17 @@ void launch_inv256(const SolveNode<T>* dn, int nbatch, int maxni, hipStream_t s,
   }
   hipLaunchKernelGGL(inv256_kernel<T>, dim3(nb256 * 8 * Inv256Cfg<T>::H, nbatch, 2), dim3(256), lds_bytes, s, dn, first);
 }
+// wide_first_kernel before the first step of a sweep (HS_SOLVE_FIRST=0: the step kernels compute the first block's product themselves)
+static bool wide_first_on() {
+  static const bool on = !(getenv("HS_SOLVE_FIRST") && getenv("HS_SOLVE_FIRST")[0] == '0');
+  return on;
+}
 template <class T>
 void launch_fwd_wide(const SolveNode<T>* dn, int nbatch, int blk, int maxm, T* w, T* y, T* b, hipStream_t s) {
   if (nbatch <= 0) return;
   const int rows = maxm - blk * HS_SW;
   const int gx = rows > 0 ? (rows + 255) / 256 : 1;
-  static const bool first = !(getenv("HS_SOLVE_FIRST") && getenv("HS_SOLVE_FIRST")[0] == '0');
+  const bool first = wide_first_on();
   if (first && blk == 0) hipLaunchKernelGGL((wide_first_kernel<T, true>), dim3(nbatch), dim3(1024), 0, s, dn, (const T*)w, y);
   hipLaunchKernelGGL(fwd_wide_kernel<T>, dim3(gx, nbatch), dim3(1024), 0, s, dn, blk, w, y, b, first ? 1 : 0);
 }
@@ -830,7 +750,7 @@ void launch_bwd_wide(const SolveNode<T>* dn, int nbatch, int blk, T* w, T* x, hi
   if (nbatch <= 0) return;
   const int rows = blk * HS_SW;
   const int gx = rows > 0 ? (rows + 255) / 256 : 1;
-  static const bool first = !(getenv("HS_SOLVE_FIRST") && getenv("HS_SOLVE_FIRST")[0] == '0');
+  const bool first = wide_first_on();
   if (first && first_call) hipLaunchKernelGGL((wide_first_kernel<T, false>), dim3(nbatch), dim3(1024), 0, s, dn, (const T*)w, x);  // every front's own last block
   hipLaunchKernelGGL(bwd_wide_kernel<T>, dim3(gx, nbatch), dim3(1024), 0, s, dn, blk, w, x, first ? 1 : 0);
 }

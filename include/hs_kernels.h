@@ -47,8 +47,8 @@ int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t* nb, int m
                       double* outInv256L, double* outInv256U, double* ms_out);
 
 /* One tree level of ldiv!: the batch of hsk_front_batch_* (same packing of ni, nb, F), factored in mode 2 or 3 so that the stored inverses are
- * the production ones, then the level's forward and backward sweeps on the global vector b (length n), with the launches and the launch
- * order of ldiv! (N), ldiv!(transpose(F), .) and ldiv!(adjoint(F), .) for one level, without the low-rank and HSS parts.
+ * the production ones, then the level's forward and backward sweeps on the global vector b (length n), through the per-level driver that
+ * ldiv! (N), ldiv!(transpose(F), .) and ldiv!(adjoint(F), .) call for every level, without the low-rank and HSS parts.
  *   flags[k] (NULL: all 0)  bit 0 `compressed`: the descriptor carries compressed = 1, mrows = ni (the dense sweeps leave the front's boundary
  *                           alone and the backward sweep starts from v = y); bit 1 `blank`: after the factorization the descriptor gets
  *                           ni = nb = m = mrows = 0 (a front whose interior block is an HSS matrix): the sweeps skip it
@@ -77,6 +77,9 @@ int hsk_sweep_level_z(int64_t count, const int64_t* ni, const int64_t* nb, int m
 /* The rule by which the forward dataflow sweep of a level of nbatch fronts with at most maxnb boundary DOFs takes tall boundary tiles
  * (1) or not (0); -1 for arguments out of range.  Host only. */
 int hsk_flow_tall_rule(int is_complex, int64_t nbatch, int64_t maxnb);
+/* The `path` ldiv! takes in this process, read once from the environment: 0 dataflow (the default; HS_SOLVE_FLOW unset or not 0, whatever
+ * HS_SOLVE_WIDE says), 1 (HS_SOLVE_FLOW=0) 256 columns per launch, 2 (HS_SOLVE_FLOW=0 HS_SOLVE_WIDE=0) 32 columns per launch.  Host only. */
+int hsk_sweep_path(void);
 
 /* Low-rank compression X (rows x cols) ~= C (rows x r) * Z (r x cols) to tolerance max(atol, rtol*|u_11|): the
  * device primitive behind the compressed Gauss transforms (`_lgauss_transform` / `_rgauss_transform`,

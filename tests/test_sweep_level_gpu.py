@@ -3,8 +3,8 @@
 level at a time through hsk_sweep_level_{d,z} (include/hs_kernels.h), held to the local recurrence of tests/sweep_mirror.py.
 
 The hook factors a batch of fronts the way a level is factored (mode 2: the default optimistic path, mode 3: tournament pivoting), so the
-stored inverses and their padding are the production ones, and runs the level's forward and backward sweeps on a global vector with the
-launches of solve_fwd / solve_bwd / solve_fwd_t / solve_bwd_t.  The batches sit on the tile edges of every implementation: HS_PB = 32,
+stored inverses and their padding are the production ones, and runs the level's forward and backward sweeps on a global vector through
+the per-level driver the level loops of ldiv! call (sweep_level_fwd / sweep_level_bwd, csrc/hs_sweep.h).  The batches sit on the tile edges of every implementation: HS_PB = 32,
 HS_SW = 256, the dataflow tiles FB = 64 / 32 (transposed 32 / 16) rows, the tall boundary tiles FBB = 256 / 128 rows by CT = 64 columns,
 UPD_CS = 512 and HS_TCH = 1024 boundary entries per chunk, and 1..4 column blocks for the odd and the even round counts.  Every entry of
 every front is held to the mirror's bound or required bitwise unchanged (blank fronts, fronts without interior DOFs, the boundary of a

@@ -1,6 +1,11 @@
 """tests/sweep_mirror.py guards itself (no GPU): a float64 NumPy implementation of one level's sweeps -- SciPy LU factors, NumPy inverses of the
 diagonal blocks -- passes check_level for both block sizes, N / T / H, real and complex, and the same implementation with ONE planted defect
-fails it.  The conditions on what the check leaves out live here too."""
+fails it.  The conditions on what the check leaves out live here too, and the one place that maps HS_SOLVE_FLOW / HS_SOLVE_WIDE to the
+`path` of the sweeps (hs_sweep_path, csrc/hs_sweep.h)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -96,3 +101,17 @@ def test_every_entry_is_bounded_or_bitwise():
     bad = dict(out, y=[v.copy() for v in out["y"]])
     bad["y"][0][7] = np.nan
     assert sm.check_level(lv, bad, 0, 256).fails
+
+
+# ---- hs_sweep_path: the switches are read once per process, so every setting is asked of a fresh child process ------------------------
+# (the child loads the library alone, without the package: nothing here touches a device)
+_PATH_CHILD = "import ctypes, sys; print('PATH', ctypes.CDLL(sys.argv[1]).hsk_sweep_path())"
+
+
+@pytest.mark.parametrize("env,want", [({}, 0), ({"HS_SOLVE_FLOW": "0"}, 1), ({"HS_SOLVE_FLOW": "0", "HS_SOLVE_WIDE": "0"}, 2),
+                                      ({"HS_SOLVE_WIDE": "0"}, 0)])
+def test_sweep_path_from_the_environment(hs, env, want):
+    """0: dataflow, whatever HS_SOLVE_WIDE says; HS_SOLVE_FLOW=0: 1 (256 columns per launch), with HS_SOLVE_WIDE=0 on top: 2 (32 columns)."""
+    base = {k: v for k, v in os.environ.items() if k not in ("HS_SOLVE_FLOW", "HS_SOLVE_WIDE")}
+    r = subprocess.run([sys.executable, "-c", _PATH_CHILD, hs._lib.LIB_PATH], env=dict(base, **env), capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.split() == ["PATH", str(want)], (env, r.returncode, r.stdout[-500:], r.stderr[-2000:])

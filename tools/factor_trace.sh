@@ -9,10 +9,10 @@ kt=glob.glob("gpurun_out/ftrace/**/*kernel_trace.csv",recursive=True)[0]
 rows=[r for r in csv.DictReader(open(kt))]
 rows.sort(key=lambda r:int(r["Start_Timestamp"]))
 def short(n): return n.split("<")[0].replace("void ","").split("(")[0]
-# one factorization = from the first init_fronts to the first fwd_gather
+# one factorization = from the first init_fronts to the first sweep_gather
 names=[short(r["Kernel_Name"]) for r in rows]
 i0=next(i for i,n in enumerate(names) if n=="init_fronts_kernel")
-i1=next(i for i,n in enumerate(names) if n=="fwd_gather_kernel" and i>i0)
+i1=next(i for i,n in enumerate(names) if n=="sweep_gather_kernel" and i>i0)
 sel=rows[i0:i1]
 lev=collections.OrderedDict()
 cur=None

@@ -9,8 +9,8 @@ kt=glob.glob("gpurun_out/ldivprof/**/*kernel_trace.csv",recursive=True)[0]
 rows=[r for r in csv.DictReader(open(kt))]
 rows.sort(key=lambda r:int(r["Start_Timestamp"]))
 names=[r["Kernel_Name"] for r in rows]
-# the last solve starts at the last fwd_gather group
-starts=[i for i,n in enumerate(names) if "fwd_gather" in n and (i==0 or "fwd_gather" not in names[i-1])]
+# the last solve starts at the last sweep_gather group
+starts=[i for i,n in enumerate(names) if "sweep_gather" in n and (i==0 or "sweep_gather" not in names[i-1])]
 i0=starts[-1]
 sel=rows[i0:]
 t0=int(sel[0]["Start_Timestamp"]); t1=max(int(r["End_Timestamp"]) for r in sel)

@@ -14,7 +14,7 @@ rows.sort()
 pg=[i for i,r in enumerate(rows) if "perm_gather" in r[2]]
 start=pg[-1] if pg else 0
 rows=rows[start:]
-front=("gemm_op_kernel","panel_pivot","panel_l21","trsm_inv","laswp","inv256","scatter_kernel","gather_kernel","mark_kernel","init_fronts","fwd_wide","bwd_wide","int_update","fwd_gather","bwd_scatter","mfma_f64","perm_gather")
+front=("gemm_op_kernel","panel_pivot","panel_l21","trsm_inv","laswp","inv256","scatter_kernel","gather_kernel","mark_kernel","init_fronts","fwd_wide","bwd_wide","int_update","sweep_gather","sweep_scatter","mfma_f64","perm_gather")
 def union(iv):
     iv=sorted(iv); b=0; cs,ce=iv[0]
     for s,e in iv[1:]:
