@@ -84,6 +84,10 @@ EXPORTS = [
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
     "hs_logabsdet", "hs_selinv", "hs_selinv_info",
+    "hs_interface_size", "hs_interface_indices", "hs_interface_matrix_d", "hs_interface_matrix_z", "hs_interface_info", "hsk_lu_product_d", "hsk_lu_product_z",
+    "hs_interface_condense_d", "hs_interface_condense_z", "hs_interface_condense_dev_d", "hs_interface_condense_dev_z",
+    "hs_interface_solve_d", "hs_interface_solve_z", "hs_interface_solve_dev_d", "hs_interface_solve_dev_z",
+    "hs_interface_expand_d", "hs_interface_expand_z", "hs_interface_expand_dev_d", "hs_interface_expand_dev_z",
     "hs_sens_d", "hs_sens_z", "hs_sens_dev_d", "hs_sens_dev_z", "hs_misfit_d", "hs_misfit_z", "hs_misfit_dev_d", "hs_misfit_dev_z", "hs_sens_info", "hsk_sddmm_d", "hsk_sddmm_z",
     "hs_mod_create_d", "hs_mod_create_z", "hs_mod_create_dev_d", "hs_mod_create_dev_z", "hs_mod_create_sparse_d", "hs_mod_create_sparse_z", "hs_mod_ldiv_d", "hs_mod_ldiv_z",
     "hs_mod_ldiv_dev_d", "hs_mod_ldiv_dev_z", "hs_mod_info", "hs_mod_free", "hs_gmres_block_mod_d", "hs_gmres_block_mod_z",
@@ -284,6 +288,26 @@ def lib():
     L.hs_selinv.restype = C.c_int
     L.hs_selinv_info.argtypes = [vp, p_f64]
     L.hs_selinv_info.restype = C.c_int
+    L.hs_interface_size.argtypes = [vp, p_i64]
+    L.hs_interface_size.restype = C.c_int
+    L.hs_interface_indices.argtypes = [vp, p_i64]
+    L.hs_interface_indices.restype = C.c_int
+    for f in (L.hs_interface_matrix_d, L.hs_interface_matrix_z):  # (F, S, lds, where, stream): S a host or a device address
+        f.argtypes = [vp, vp, i64, C.c_int, vp]
+        f.restype = C.c_int
+    for ph in ("condense", "solve", "expand"):  # (F, trans, C, ldc, n, nrhs) on the host, the same on the device with a stream
+        for sfx in ("_d", "_z"):
+            f = getattr(L, "hs_interface_" + ph + sfx)
+            f.argtypes = [vp, C.c_int, p_f64, i64, i64, i64]
+            f.restype = C.c_int
+            f = getattr(L, "hs_interface_" + ph + "_dev" + sfx)
+            f.argtypes = [vp, C.c_int, vp, i64, i64, i64, vp]
+            f.restype = C.c_int
+    L.hs_interface_info.argtypes = [vp, p_f64]
+    L.hs_interface_info.restype = C.c_int
+    for f in (L.hsk_lu_product_d, L.hsk_lu_product_z):
+        f.argtypes = [i64, p_f64, i64, C.POINTER(C.c_int32), p_f64, i64, p_f64]
+        f.restype = C.c_int
     L.hs_analyze.argtypes = [C.c_int, i64, p_i64, p_i64, C.POINTER(hs_tree), C.POINTER(hs_options), i64, i64, C.POINTER(vp)]
     L.hs_analyze.restype = C.c_int
     L.hs_plan.argtypes = [C.c_int, i64, C.POINTER(hs_tree), C.POINTER(hs_options), i64, i64, C.POINTER(vp)]

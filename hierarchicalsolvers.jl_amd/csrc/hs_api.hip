@@ -32,6 +32,7 @@
 #include "hs_sweep.h"
 #include "hs_condest.h"
 #include "hs_selinv.h"
+#include "hs_interface.h"
 #include "hs_solve_multi.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -295,6 +296,8 @@ struct hs_handle {
   void (*sx_free)(void*) = nullptr;
   void* mx = nullptr;  // hs_solve_multi.hip: the work blocks of the block solves, the figures of the last hs_ldiv_block_* call
   void (*mx_free)(void*) = nullptr;
+  void* ix = nullptr;  // hs_interface.hip: the events and the figures of the last hs_interface_* calls
+  void (*ix_free)(void*) = nullptr;
   std::vector<int> sp_owner;  // hs_ldiv_sparse_*: per row the internal node whose int holds it (built by the first call that needs it)
   double sp_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the figures of the last hs_ldiv_sparse_* call
   double sens_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the figures of the last hs_sens_* / hs_misfit_* call (hs_sens.hip)
@@ -376,6 +379,7 @@ static void free_handle(hs_handle* h) {
   if (h->cx && h->cx_free) h->cx_free(h->cx);
   if (h->sx && h->sx_free) h->sx_free(h->sx);
   if (h->mx && h->mx_free) h->mx_free(h->mx);
+  if (h->ix && h->ix_free) h->ix_free(h->ix);
   for (auto& x : h->nodes)
     if (x.S_hss) {
       hs_hss_free((hs_hss*)x.S_hss);
@@ -2082,6 +2086,31 @@ void hs_selinv_view(hs_handle* h, HsSelView* v) {
     v->sb = h->d_sb;
     v->sb_bytes = h->sb_bytes;
   }
+}
+// the handle as hs_interface.hip sees it (hs_interface.h): the pseudo-root -- the level-0 front whose interior is root.bnd -- and what its
+// refusals are decided from; a plan-only handle has the sizes and the ids
+void hs_interface_view(hs_handle* h, HsInterfaceView* v) {
+  *v = HsInterfaceView();
+  v->n = h->n;
+  v->is_complex = h->is_complex ? 1 : 0;
+  v->factored = h->factored ? 1 : 0;
+  v->device = h->d_nodes ? 1 : 0;
+  v->nranks = h->nranks;
+  v->hss_node = first_hss_front(h);
+  v->stream = h->stream;
+  v->ix = &h->ix;
+  v->ix_free = &h->ix_free;
+  if (h->nodes.empty() || h->nodes.back().level != 0) return;  // the root keeps no boundary
+  const NodeH& x = h->nodes.back();
+  v->nb = x.ni;
+  v->idx = h->fidx_host.data() + x.off_fidx;
+  if (x.kind != 0) v->flags |= HS_IF_SLICED;
+  if (x.hss_interior() || x.mf || x.cfront || x.compressed || x.dist) v->flags |= HS_IF_NOLU;
+  if (!v->device) return;
+  const size_t esz = h->is_complex ? sizeof(cplx) : sizeof(double);
+  v->LU = (const char*)h->d_fac + x.off_LF * esz;
+  v->ldlu = x.ldl;
+  v->rperm = h->d_int + x.off_rperm;
 }
 void* hs_scratch_take(size_t bytes, const char* what) {
   bytes = std::max<size_t>(bytes, 256);

@@ -74,9 +74,16 @@ struct HsMultiActive {
 };
 
 // C[:, 0:nrhs] = op(F)^-1 C[:, 0:nrhs] in place on the device (ld ldc), chunk by chunk, on stream s; events around the launches.  trans = 0: F
-// (kernels_solve_multi.hip), 1: transpose(F), 2: adjoint(F) (kernels_solve_multi_t.hip).  act == nullptr: every front in both sweeps
+// (kernels_solve_multi.hip), 1: transpose(F), 2: adjoint(F) (kernels_solve_multi_t.hip).  act == nullptr: every front in both sweeps.
+// phase (hs_interface.hip; no active set then) runs a part of every chunk's schedule, split at level 0 (the pseudo-root):
+//   HS_MULTI_CONDENSE  the forward sweep of levels nlevels-1 .. 1; every front's y is then copied from work block 2 to C[int, :]
+//   HS_MULTI_ROOT      both sweeps of level 0
+//   HS_MULTI_EXPAND    work block 2 is reloaded from C[int, :] level by level, then the backward sweep of levels 1 .. nlevels-1
+// The two copies are exact, so the three in a row leave the bits of HS_MULTI_ALL, which is the schedule without them.
+enum { HS_MULTI_ALL = 0, HS_MULTI_CONDENSE, HS_MULTI_ROOT, HS_MULTI_EXPAND };
 template <class T>
-void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act = nullptr);
+void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act = nullptr,
+                        int phase = HS_MULTI_ALL);
 double hs_solve_multi_seconds(void* mx);  // waits for the last block solve and returns its device seconds
 void hs_solve_multi_info(void* mx, double* out6);
 int hs_ldiv_block_cols();  // KC: columns per chunk (HS_LDIV_BLOCK_COLS = 16 / 32 / 48 / 64, default 32)

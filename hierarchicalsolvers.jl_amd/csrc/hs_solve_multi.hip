@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "hs_solve_multi.h"
+#include "hs_interface.h"
 #include "hs_lowrank.h"
 #include "hs_selinv.h"  // hs_scratch_take / hs_scratch_give
 
@@ -264,7 +265,7 @@ void lr_apply_op(int trans, int cj, const LowRank<T>& lr, const T* x, T* dst, T*
 // column panel above / below the block with K up to ni and 256 outputs: W is written once per block, by four workgroups per front
 // (DESIGN.md section 4a⁗″).
 template <class T>
-void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act) {
+void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act, int phase) {
   const int KC = hs_ldiv_block_cols();
   const int kcw = KC;
   const int cj = (trans == 2 && sizeof(T) == 16) ? 1 : 0;
@@ -283,6 +284,7 @@ void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int
     a.B = act ? dC : dC + c0 * ldc; a.ldb = ldc; a.kc = kc;  // an active set keeps every chunk in the same block
     if (act && act->begin) act->begin(act->ctx, chunks, kc, s);
     for (int lv = nl - 1; lv >= 0; --lv) {  // leaves -> root
+      if (phase == HS_MULTI_EXPAND || (phase == HS_MULTI_CONDENSE && lv == 0) || (phase == HS_MULTI_ROOT && lv != 0)) continue;
       const HsMultiLevel& L = v.levels[lv];
       if (v.hss_front && !act)  // fronts with an HSS interior block (disjoint from the level's other fronts): on the caller's block
         for (int id : L.hss) v.hss_front(v.hss_ctx, id, 0, trans, a.B, a.ldb, kc, s);
@@ -322,10 +324,12 @@ void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int
         lr_apply_op<T>(trans, cj, lr, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
       level_move<T>(trans, sn, nf, 3, maxnb, a, s);
+      if (phase == HS_MULTI_CONDENSE) launch_interface_park<T>(sn, nf, 0, maxni, a, s);  // C[int, :] = y
     }
     if (act && act->zoff[chunks + 1] > act->zoff[chunks])  // backward-only fronts: y = 0
       launch_sparse_zero<T>((T*)mc->W2, kcw, kc, act->zseg + act->zoff[chunks], (int)(act->zoff[chunks + 1] - act->zoff[chunks]), act->zmaxni[chunks], s);
     for (int lv = 0; lv < nl; ++lv) {  // root -> leaves
+      if (phase == HS_MULTI_CONDENSE || (phase == HS_MULTI_EXPAND && lv == 0) || (phase == HS_MULTI_ROOT && lv != 0)) continue;
       const HsMultiLevel& L = v.levels[lv];
       if (v.hss_front && !act)
         for (int id : L.hss) v.hss_front(v.hss_ctx, id, 1, trans, a.B, a.ldb, kc, s);
@@ -336,6 +340,7 @@ void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int
       const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
       a.aux = q_.aux;
+      if (phase == HS_MULTI_EXPAND) launch_interface_park<T>(sn, nf, 1, maxni, a, s);  // y = C[int, :]
       level_move<T>(trans, sn, nf, 1, maxnb, a, s);
       level_step<T>(trans, cj, sn, nf, HSM_UR, HSMT_LB, 0, maxni, a, s);
       for (const HsMultiLR& q : L.lr) {  // Uib, transposed Lbi
@@ -369,8 +374,8 @@ void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int
   }
   multi_finish(mc, v, fc, chunks, sizeof(T), s);
 }
-template void hs_solve_multi_run<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
-template void hs_solve_multi_run<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t, const HsMultiActive*);
+template void hs_solve_multi_run<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t, const HsMultiActive*, int);
+template void hs_solve_multi_run<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t, const HsMultiActive*, int);
 
 double hs_solve_multi_seconds(void* mx) {
   MultiCache* mc = (MultiCache*)mx;

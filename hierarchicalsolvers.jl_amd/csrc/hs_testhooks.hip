@@ -1306,3 +1306,49 @@ extern "C" int hsk_small_eig_z(int64_t m, const double* H, int64_t ldh, double* 
   }
   return HS_OK;
 }
+
+// ---- hs_interface_matrix_*: the product S = P^T (L U) of a packed LU (kernels_interface.hip) on host data ------------------------------------
+#include "hs_interface.h"
+template <class T>
+static int lu_product_hook(int64_t nb, const T* LF, int64_t ldl, const int32_t* rperm, T* S, int64_t lds, double* flops_out) {
+  bool ok = nb >= 1 && nb <= (1 << 20) && LF && rperm && S && ldl >= nb && lds >= nb;
+  if (ok) {
+    std::vector<char> seen((size_t)nb, 0);
+    for (int64_t i = 0; ok && i < nb; ++i) {
+      ok = rperm[i] >= 0 && rperm[i] < nb && !seen[(size_t)rperm[i]];
+      if (ok) seen[(size_t)rperm[i]] = 1;
+    }
+  }
+  if (!ok) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_lu_product: nb >= 1, non-null arrays, ldl >= nb, lds >= nb and rperm a permutation of 0..nb-1 required");
+    return HS_ERR_ARGUMENT;
+  }
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
+    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
+    return HS_ERR_DEVICE;
+  }
+  T *dL = nullptr, *dS = nullptr;
+  int* dp = nullptr;
+  const size_t nl = (size_t)ldl * (nb - 1) + nb, ns = (size_t)lds * (nb - 1) + nb;
+  CK(hipMalloc((void**)&dL, sizeof(T) * nl));
+  CK(hipMalloc((void**)&dS, sizeof(T) * ns));
+  CK(hipMalloc((void**)&dp, sizeof(int) * (size_t)nb));
+  CK(hipMemcpy(dL, LF, sizeof(T) * nl, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dS, S, sizeof(T) * ns, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dp, rperm, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
+  const double fl = launch_lu_product<T>((int)nb, dL, ldl, dp, dS, lds, 0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy(S, dS, sizeof(T) * ns, hipMemcpyDeviceToHost));
+  (void)hipFree(dL);
+  (void)hipFree(dS);
+  (void)hipFree(dp);
+  if (flops_out) *flops_out = fl;
+  return HS_OK;
+}
+extern "C" int hsk_lu_product_d(int64_t nb, const double* LF, int64_t ldl, const int32_t* rperm, double* S, int64_t lds, double* flops_out) {
+  return lu_product_hook<double>(nb, LF, ldl, rperm, S, lds, flops_out);
+}
+extern "C" int hsk_lu_product_z(int64_t nb, const double* LF, int64_t ldl, const int32_t* rperm, double* S, int64_t lds, double* flops_out) {
+  return lu_product_hook<cplx>(nb, (const cplx*)LF, ldl, (const int32_t*)rperm, (cplx*)S, lds, flops_out);
+}

@@ -157,7 +157,7 @@ def grid_nested_dissection(shape, nmax):
     return build(tuple([0] * d), shape)
 
 
-def graph_nested_dissection(A, nmax=100):
+def graph_nested_dissection(A, nmax=100, interface=None):
     """Nested dissection of a GENERAL sparse matrix from its graph alone (no coordinates): the raw :class:`NDNode` tree in the
     disjoint-ownership form the reference consumes (``nesteddissection.jl:19-21,105-148``; the generator that made the
     reference's ``.mat`` trees is not part of it) -- every DOF belongs to exactly one leaf, ``bnd(B)`` = DOFs of ``B`` with a
@@ -165,7 +165,11 @@ def graph_nested_dissection(A, nmax=100):
 
     A set is halved by a breadth-first sweep of its induced subgraph from a pseudo-peripheral vertex (the first half of the
     sweep against the rest; further components follow the first one), until it holds at most ``nmax`` DOFs.  Global ids are
-    1-based and ascending inside every index vector, like the grid generator's."""
+    1-based and ascending inside every index vector, like the grid generator's.
+
+    ``interface`` (0-based DOF ids, default none): these DOFs count as having a neighbour outside EVERY set, so they stay in ``bnd`` all
+    the way up and the root keeps them: ``root.bnd`` is the interface (ascending).  A factorization of such a tree eliminates everything
+    else and holds the Schur complement on the interface (:func:`schur_complement`, :func:`condense`, :func:`expand`)."""
     from scipy.sparse.csgraph import breadth_first_order
 
     A = sp.csr_matrix(A)
@@ -176,6 +180,14 @@ def graph_nested_dissection(A, nmax=100):
     G = sp.csr_matrix(G)
     G.eliminate_zeros()
     deg = np.diff(G.indptr)
+    forced = np.zeros(n, dtype=bool)
+    if interface is not None:
+        ids = np.asarray(interface, dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= n):
+            raise ValueError(f"ArgumentError: interface ids must lie in 0..{n - 1}")
+        if np.unique(ids).size != ids.size:
+            raise ValueError("ArgumentError: interface ids must be distinct")
+        forced[ids] = True
 
     def sweep(H, start):
         """Breadth-first order of every vertex of H: the component of `start` first, then the others."""
@@ -194,7 +206,7 @@ def graph_nested_dissection(A, nmax=100):
     def build(V, H):
         """V: ascending global 0-based ids, H: induced subgraph on V."""
         inside = np.diff(H.indptr)
-        bmask = deg[V] > inside  # a neighbour outside V
+        bmask = (deg[V] > inside) | forced[V]  # a neighbour outside V (an interface DOF counts as having one)
         if len(V) <= nmax or len(V) < 2:
             return NDNode(V[~bmask] + 1, V[bmask] + 1)
         start = 0
@@ -208,8 +220,8 @@ def graph_nested_dissection(A, nmax=100):
         H1, H2 = H[i1][:, i1], H[i2][:, i2]
         left, right = build(V[i1], H1), build(V[i2], H2)
         cb = np.zeros(len(V), dtype=bool)  # boundary of either child, in V's numbering
-        cb[i1] = deg[V[i1]] > np.diff(H1.indptr)
-        cb[i2] = deg[V[i2]] > np.diff(H2.indptr)
+        cb[i1] = (deg[V[i1]] > np.diff(H1.indptr)) | forced[V[i1]]
+        cb[i2] = (deg[V[i2]] > np.diff(H2.indptr)) | forced[V[i2]]
         return NDNode(V[cb & ~bmask] + 1, V[bmask] + 1, left, right)
 
     import sys

@@ -16,6 +16,7 @@ reference (Julia)                      here
 selected inverse (no Julia name)       :func:`selinv`, :func:`selinv_diag`: ``diag(A^-1)`` and ``A^-1`` on the pattern of ``A``
 ``eigs(A; nev, sigma)`` (Arpack)       :func:`eigs`: the eigenpairs of ``A`` nearest ``sigma`` from the factors of ``A - sigma*I`` (``hs_eigs.hip``)
 ``eigs(A, B; nev, sigma)`` (Arpack)    :func:`eigs` with ``M=B``: ``A x = lambda B x`` from the factors of ``A - sigma*B``
+partial factorization (no Julia name)  :func:`schur_complement`, :func:`condense`, :func:`interface_solve`, :func:`expand` (``hs_interface.hip``)
 ``F \\ b``                              ``F.solve(b)``
 =====================================  ====================================================
 
@@ -34,7 +35,7 @@ from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
            "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info",
-           "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "eigs", "eigs_info", "eigs_gen_info"]
+           "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "eigs", "eigs_info", "eigs_gen_info", "interface_indices", "schur_complement", "condense", "interface_solve", "expand", "interface_info"]
 
 
 class SolverOptions:
@@ -1176,3 +1177,100 @@ def selinv_info(F):
     out = np.zeros(4)
     _lib.check(_lib.lib().hs_selinv_info(F._h, _pf64(out)))
     return dict(seconds=float(out[0]), flops=float(out[1]), peak_bytes=float(out[2]), batches=int(out[3]))
+
+
+# ---- Schur-complement mode (hs_interface.hip): the interface matrix, condense and expand solves --------------------------------------
+def interface_indices(F):
+    """The interface of ``F``: the 0-based ids of the boundary the root of its tree keeps (``root.bnd``, e.g. from
+    ``problems.graph_nested_dissection(A, nmax, interface=...)``), in the order of the rows and columns of :func:`schur_complement`.
+    Empty for an ordinary tree."""
+    F, _ = _unwrap(F)
+    nb = _lib.i64()
+    _lib.check(_lib.lib().hs_interface_size(F._h, C.byref(nb)))
+    idx = np.zeros(nb.value, dtype=np.int64)
+    if nb.value:
+        _lib.check(_lib.lib().hs_interface_indices(F._h, _p64(idx)))
+    return idx - 1
+
+
+def schur_complement(F, device=False):
+    """The dense Schur complement ``S = A_bb - A_bi A_ii^-1 A_ib`` of ``F`` on its interface ``b`` (:func:`interface_indices`), rebuilt on
+    the device from the pivoted LU the factorization keeps of it (``hs_interface_matrix_*``): no second factorization, the factors are only
+    read, two calls return the same bits.  ``transpose(F)`` / ``adjoint(F)`` give ``S^T`` / ``S^H``.  ``device=True`` returns a device
+    tensor (column-major) instead of a NumPy array.  For a compressed factorization this is the Schur complement of the compressed
+    factorization."""
+    F, trans = _unwrap(F)
+    nb = len(interface_indices(F))
+    fn = getattr(_lib.lib(), "hs_interface_matrix" + ("_z" if F.dtype.kind == "c" else "_d"))
+    if device:
+        import torch
+
+        St = torch.zeros((nb, nb), dtype=torch.complex128 if F.dtype.kind == "c" else torch.float64, device="cuda")  # its transpose is column-major
+        _lib.check(fn(F._h, St.data_ptr() if nb else None, max(nb, 1), 1, None))
+        S = St.t()
+        return S if trans == 0 else (S.t() if trans == 1 else S.t().conj())
+    S = np.zeros((nb, nb), dtype=F.dtype, order="F")
+    _lib.check(fn(F._h, S.ctypes.data if nb else None, max(nb, 1), 0, None))
+    return S if trans == 0 else (S.T if trans == 1 else S.conj().T)
+
+
+def _interface_phase(name, F, Cb):
+    """One of the three phases in place on the ``n x nrhs`` block ``Cb``: a column-major NumPy array or device tensor of ``F``'s dtype."""
+    F, trans = _unwrap(F)
+    sfx = "_z" if F.dtype.kind == "c" else "_d"
+    if hasattr(Cb, "data_ptr"):  # a device tensor
+        import torch
+
+        want = torch.complex128 if F.dtype.kind == "c" else torch.float64
+        if not Cb.is_cuda or Cb.dtype != want:
+            raise TypeError(f"{name}: the block must be a {F.dtype} array or a device tensor of that type (it is updated in place)")
+        if Cb.dim() not in (1, 2) or Cb.shape[0] != F.n:
+            raise _lib.DimensionMismatch(f"DimensionMismatch: the block has {tuple(Cb.shape)[:1]} rows, F is {F.n} x {F.n}")
+        nrhs = 1 if Cb.dim() == 1 else Cb.shape[1]
+        ld = F.n if (Cb.dim() == 1 or nrhs == 1) else Cb.stride(1)
+        if Cb.stride(0) != 1 or ld < F.n:
+            raise ValueError(f"{name}: the device block must be column-major (stride 1 down a column): it is updated in place")
+        fn = getattr(_lib.lib(), "hs_interface_" + name + "_dev" + sfx)
+        _lib.check(fn(F._h, trans, Cb.data_ptr(), ld, F.n, nrhs, torch.cuda.current_stream().cuda_stream))
+        return Cb
+    if not isinstance(Cb, np.ndarray) or Cb.dtype != F.dtype:
+        raise TypeError(f"{name}: the block must be a {F.dtype} array or a device tensor of that type (it is updated in place)")
+    if Cb.ndim not in (1, 2) or Cb.shape[0] != F.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: the block has {Cb.shape[:1]} rows, F is {F.n} x {F.n}")
+    if not (Cb.flags.f_contiguous and Cb.flags.writeable):
+        raise ValueError(f"{name}: the block must be a writeable column-major array (np.asfortranarray): it is updated in place")
+    nrhs = 1 if Cb.ndim == 1 else Cb.shape[1]
+    fn = getattr(_lib.lib(), "hs_interface_" + name + sfx)
+    _lib.check(fn(F._h, trans, Cb.ctypes.data_as(_lib.p_f64), F.n, F.n, nrhs))
+    return Cb
+
+
+def condense(F, B):
+    """First phase of a solve split at the interface (``hs_interface_condense_*``), in place on the column-major block ``B`` (NumPy or
+    device tensor), which is returned: afterwards ``B[idx] = g = B_b - op(A)_bi op(A)_ii^-1 B_i`` with ``idx = interface_indices(F)``;
+    the other rows hold the forward intermediates :func:`expand` needs (opaque).  ``F`` may be ``transpose(F)`` / ``adjoint(F)``."""
+    return _interface_phase("condense", F, B)
+
+
+def interface_solve(F, Cb):
+    """Second phase (``hs_interface_solve_*``), in place: ``C[idx] = op(S)^-1 C[idx]`` with the factors the handle keeps of ``S``; the other
+    rows are left alone.  A caller with its own interface system (``(S + K) y = g + h``) overwrites ``C[idx]`` itself instead."""
+    return _interface_phase("solve", F, Cb)
+
+
+def expand(F, Cb):
+    """Third phase (``hs_interface_expand_*``), in place on a block :func:`condense` has filled: reads ``C[idx]`` as the interface values
+    ``y`` and leaves ``op(A)_ii^-1 (B_i - op(A)_ib y)`` in the other rows; ``C[idx]`` is not changed.
+    ``expand(F, interface_solve(F, condense(F, B)))`` returns the bits of ``ldiv_block_t(F, B)``."""
+    return _interface_phase("expand", F, Cb)
+
+
+def interface_info(F):
+    """Figures of the last interface calls on ``F`` (``hs_interface_info``): device seconds and executed real flops of the last
+    :func:`schur_complement`, the interface size, the device seconds of the last condense / solve / expand, the column chunks of the last
+    phase call."""
+    F, _ = _unwrap(F)
+    out = np.zeros(8)
+    _lib.check(_lib.lib().hs_interface_info(F._h, _pf64(out)))
+    return dict(matrix_seconds=float(out[0]), matrix_flops=float(out[1]), nb=int(out[2]), condense_seconds=float(out[3]), solve_seconds=float(out[4]),
+                expand_seconds=float(out[5]), chunks=int(out[6]))

@@ -110,6 +110,13 @@ int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_
 int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
                        int minus, int trap, int conj, const int32_t* map);
 
+/* The product of hs_interface_matrix_* (kernels_interface.hip) on host data: S[rperm[i], j] = sum over k <= min(i, j) of L[i, k] U[k, j] for the
+ * packed factors LF (nb x nb, column-major, ldl >= nb; unit lower L below the diagonal, U on and above it), rperm nb distinct entries in
+ * 0..nb-1 ((P x)[i] = x[rperm[i]]; an entry outside gives HS_ERR_ARGUMENT), S nb x nb column-major with lds >= nb (rows past nb are left as
+ * they are).  *flops_out (may be NULL) = the real flops the launch executed on the matrix pipe, K padding included. */
+int hsk_lu_product_d(int64_t nb, const double* LF, int64_t ldl, const int32_t* rperm, double* S, int64_t lds, double* flops_out);
+int hsk_lu_product_z(int64_t nb, const double* LF, int64_t ldl, const int32_t* rperm, double* S, int64_t lds, double* flops_out);
+
 /* ONE grouped launch of the product of the transposed ULV solves of the HSS module (kernels_ulv_t.hip) on host data.  Job i is described by
  * the ten entries desc[10 i ..]: M, K, N, lda, ldx, ldc, aoff, xoff, coff, flags.  A = Abuf + aoff is K x M column-major (lda >= K), X = Xbuf +
  * xoff K x N (ldx >= K), C = Cbuf + coff M x N (ldc >= M); offsets and buffer lengths (na, nx, nc) count elements (ComplexF64: pairs of

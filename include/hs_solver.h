@@ -482,6 +482,53 @@ int hs_selinv(hs_handle* F, int trans, void* diag, void* zval, int where, int64_
 /* the last hs_selinv call of the handle: out4 = {seconds on the device, flops executed (real), peak scratch bytes, batches of fronts} */
 int hs_selinv_info(const hs_handle* F, double* out4);
 
+/* ---- Schur-complement mode: the interface matrix, condense and expand solves (hs_interface.hip) --------------------------------------
+ * The interface b is the boundary the ROOT of the tree keeps (root.bnd; hs.problems.graph_nested_dissection(..., interface=...) builds such
+ * trees), everything else (i) is eliminated.  The handle's pseudo-root -- the level-0 front whose interior is root.bnd -- holds the pivoted
+ * LU of the dense Schur complement S = A_bb - A_bi A_ii^-1 A_ib; these calls open it:
+ *   hs_interface_size     *nb = |root.bnd| (0 when the root keeps no boundary); also on a plan-only handle (hs_plan)
+ *   hs_interface_indices  the nb ids of the interface, 1-based, in the order of S's rows and columns (= root.bnd as given); plan-only too
+ *   hs_interface_matrix   S (nb x nb, column-major, lds >= nb) = P^T (L U) from the stored factors of the pseudo-root: one product on the
+ *                         matrix pipe that walks only the k <= min(i, j) part of K (about a third of the flops of a full product); no second
+ *                         factorization, no copy of S kept by the handle; the factors are only read; two calls return the same bits.
+ *                         where: 0 S is a host array, 1 a device array; stream: NULL = the handle's.  nb = 0 touches nothing.  For a
+ *                         compressed handle (swlevel > 0) S is the Schur complement of the COMPRESSED factorization: it approximates A's only
+ *                         as well as F approximates A.
+ * The three phases split the block solve hs_ldiv_block_t_* at the pseudo-root, in place on one n x nrhs column-major block C (ldc >= n):
+ *   condense  forward sweep of tree levels nlevels .. 1: on return C[idx, :] = g = B_b - op(A)_bi op(A)_ii^-1 B_i; the interior rows of C hold
+ *             every front's forward intermediate at the front's own int ids -- opaque values only expand reads; nothing stays in the handle
+ *   solve     level 0 only: C[idx, :] = op(S)^-1 C[idx, :]
+ *   expand    reads C[idx, :] as the interface values y, reloads the intermediates from the interior rows and runs the backward sweep of
+ *             levels 1 .. nlevels: C[interior, :] = op(A)_ii^-1 (B_i - op(A)_ib y); C[idx, :] is left as it is
+ * condense; solve; expand returns the bits of hs_ldiv_block_t_* for the same trans (the same chunks and launches, two exact copies per front
+ * more).  Between condense and expand the caller may overwrite C[idx, :] (its own interface solve, e.g. (S + K) y = g + h).  trans: 0 F, 1
+ * transpose(F), 2 adjoint(F).  The _dev_ forms take a device block and a stream and return without waiting.  Active sets (hs_ldiv_sparse_*)
+ * are not served in this mode.  A phase call runs on the block solve's work blocks and files its figures as the handle's last block solve
+ * (hs_ldiv_block_info) as well.
+ * Refused before any device work, outputs untouched: HS_ERR_UNSUPPORTED for what hs_ldiv_block_t_* refuses (fronts that keep D as an HSS
+ * matrix, more than one rank) and, for hs_interface_matrix_*, a pseudo-root eliminated in slices (hs_options.split) or not kept as one dense
+ * LU; HS_ERR_ARGUMENT for null pointers, trans outside 0..2, where outside 0..1, a plan-only or unfactored handle (all but size / indices), a
+ * mismatched element type; HS_ERR_DIMENSION for n != size(F), ldc < n, lds < nb, nrhs < 0.
+ * hs_interface_info: out8 = {seconds and executed real flops of the last hs_interface_matrix_* call, nb, seconds of the last condense, solve
+ * and expand, column chunks of the last phase call, 0}. */
+int hs_interface_size(const hs_handle* F, int64_t* nb);
+int hs_interface_indices(const hs_handle* F, int64_t* idx);
+int hs_interface_matrix_d(hs_handle* F, double* S, int64_t lds, int where, void* stream);
+int hs_interface_matrix_z(hs_handle* F, double* S, int64_t lds, int where, void* stream);
+int hs_interface_condense_d(hs_handle* F, int trans, double* C, int64_t ldc, int64_t n, int64_t nrhs);
+int hs_interface_condense_z(hs_handle* F, int trans, double* C, int64_t ldc, int64_t n, int64_t nrhs);
+int hs_interface_solve_d(hs_handle* F, int trans, double* C, int64_t ldc, int64_t n, int64_t nrhs);
+int hs_interface_solve_z(hs_handle* F, int trans, double* C, int64_t ldc, int64_t n, int64_t nrhs);
+int hs_interface_expand_d(hs_handle* F, int trans, double* C, int64_t ldc, int64_t n, int64_t nrhs);
+int hs_interface_expand_z(hs_handle* F, int trans, double* C, int64_t ldc, int64_t n, int64_t nrhs);
+int hs_interface_condense_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, int64_t n, int64_t nrhs, void* stream);
+int hs_interface_condense_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, int64_t n, int64_t nrhs, void* stream);
+int hs_interface_solve_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, int64_t n, int64_t nrhs, void* stream);
+int hs_interface_solve_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, int64_t n, int64_t nrhs, void* stream);
+int hs_interface_expand_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, int64_t n, int64_t nrhs, void* stream);
+int hs_interface_expand_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, int64_t n, int64_t nrhs, void* stream);
+int hs_interface_info(const hs_handle* F, double* out8);
+
 /* ---- phased form of factor (hs_factor_* = hs_analyze + hs_numeric_* over all levels) -------------------------
  * hs_analyze builds the plan and uploads the sparsity pattern, so a later numeric factorization starts with
  * every input resident in HBM; the pattern (colptr, rowval, tree) is reused for new values of A.
