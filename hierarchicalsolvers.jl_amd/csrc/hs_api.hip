@@ -29,6 +29,7 @@
 #include "../../include/hs_solver.h"
 #include "../../include/hs_hss.h"
 #include "hs_common.h"
+#include "hs_host.h"
 #include "hs_sweep.h"
 #include "hs_condest.h"
 #include "hs_selinv.h"
@@ -41,37 +42,26 @@
 static thread_local std::string g_err;
 static thread_local long long g_err_info = 0;
 
-void hs_set_error(int code, long long info, const char* fmt, ...) {
+static void set_error_v(long long info, const char* fmt, va_list ap) {
   char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
   vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
   g_err = buf;
   g_err_info = info;
+}
+void hs_set_error(int code, long long info, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  set_error_v(info, fmt, ap);
+  va_end(ap);
   (void)code;
 }
-struct HsError {
-  int code;
-};
-#define HS_FAIL(code, info, ...)           \
-  do {                                     \
-    hs_set_error(code, info, __VA_ARGS__); \
-    throw HsError{code};                   \
-  } while (0)
-
-#define HS_GUARD(...)                                        \
-  try {                                                      \
-    __VA_ARGS__;                                             \
-    return HS_OK;                                            \
-  } catch (const HsError& e) {                               \
-    return e.code;                                           \
-  } catch (int code) {                                       \
-    return code;                                             \
-  } catch (const std::bad_alloc&) {                          \
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed"); \
-    return HS_ERR_NOMEM;                                     \
-  }
+void hs_fail(int code, long long info, const char* fmt, ...) {  // HS_FAIL (hs_host.h)
+  va_list ap;
+  va_start(ap, fmt);
+  set_error_v(info, fmt, ap);
+  va_end(ap);
+  throw code;
+}
 
 extern "C" const char* hs_last_error(void) { return g_err.c_str(); }
 extern "C" int64_t hs_last_error_info(void) { return g_err_info; }
@@ -1587,9 +1577,6 @@ static void check_solve_args(hs_handle* h, bool cplx, int64_t ldc, int64_t ldb, 
 
 // ---- the pieces the ldiv entry points compose their refusals from, each in its own order (the order is observable, and the tests pin it).
 // fn: the entry point as its messages name it; what: the kind of solve the message says is not implemented
-static void check_trans(int trans, const char* fn) {
-  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
-}
 static void check_single_rank(const hs_handle* h, const char* fn, const char* what) {
   if (h->nranks > 1) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: %s of a factorization over %d ranks are not implemented (single-rank factorizations only)", fn, what, h->nranks);
 }
@@ -1673,7 +1660,7 @@ static void ldiv_dev(hs_handle* h, T* dC, int64_t ldc, const T* dB, int64_t ldb,
 // refuse, never drop: what the transposed sweeps do not cover is named before any device work
 static void check_solve_t(hs_handle* h, int trans, const char* fn) {
   check_handle(h);
-  check_trans(trans, fn);
+  hs_check_trans(fn, trans);
   if (trans == 0) return;
   check_single_rank(h, fn, "transposed solves");
   check_no_hss_front(h, fn, "transposed ULV solves");
@@ -1746,7 +1733,7 @@ void hs_multi_view(hs_handle* h, HsMultiView* v) {
 static void check_solve_block(hs_handle* h, int trans, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
   const char* fn = "hs_ldiv_block_*";
   check_handle(h);
-  check_trans(trans, fn);
+  hs_check_trans(fn, trans);
   if (trans != 0) HS_FAIL(HS_ERR_UNSUPPORTED, trans, "hs_ldiv_block_*: transposed and adjoint block solves are not implemented (trans must be 0; hs_ldiv_t_* solves column by column)");
   check_solve_args(h, cplx, ldc, ldb, n, nrhs);
   check_single_rank(h, fn, "block solves");
@@ -1757,29 +1744,10 @@ static void check_solve_block(hs_handle* h, int trans, bool cplx, int64_t ldc, i
 static void check_solve_block_t(hs_handle* h, int trans, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
   const char* fn = "hs_ldiv_block_t_*";
   check_handle(h);
-  check_trans(trans, fn);
+  hs_check_trans(fn, trans);
   check_solve_args(h, cplx, ldc, ldb, n, nrhs);
   check_single_rank(h, fn, "block solves");
   check_no_hss_front(h, fn, "transposed ULV solves");
-}
-// a host block on the device: the whole block goes up and comes down once around run(d, ld, s), d the n x nrhs copy in scratch memory
-template <class T, class Run>
-static void stage_block(hs_handle* h, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs, Run run) {
-  hipStream_t s = h->stream;
-  const size_t bytes = (size_t)n * nrhs * sizeof(T);
-  T* d = (T*)hs_scratch_take(bytes, "block solve right-hand sides");
-  try {
-    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
-    run(d, n, s);
-    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
-    HS_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    hs_scratch_give(d, bytes);
-    throw;
-  }
-  hs_scratch_give(d, bytes);
-  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
 }
 // a device block is solved in place in C: what every device entry does between its checks and its solve
 template <class T>
@@ -1796,7 +1764,8 @@ static void block_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, i
   if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", trans ? "hs_ldiv_block_t_*" : "hs_ldiv_block_*");
   HsMultiView v;
   hs_multi_view(h, &v);
-  stage_block<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { hs_solve_multi_run<T>(v, trans, d, ld, nrhs, s); });
+  hs_stage_block<T>(h->stream, "block solve right-hand sides", C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { hs_solve_multi_run<T>(v, trans, d, ld, nrhs, s); });
+  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
 }
 template <class T>
 static void block_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
@@ -1878,7 +1847,7 @@ static void ulv_front(void* ctx_, int id, int sweep, int trans, void* B_, long l
   auto hsolve_t = [&](void* H, T* b) {
     int st = hs_hss_set_stream((hs_hss*)H, (void*)s);
     if (st == 0) st = hs_hss_ldiv_t((hs_hss*)H, trans, (double*)b, w.ldt, kc, 1);
-    if (st != 0) throw HsError{st};
+    HS_CHECK(st);
   };
   T *t = w.t, *xb = w.xb, *u = w.u;
   if (trans == 0) {
@@ -1935,7 +1904,7 @@ static void ulv_front(void* ctx_, int id, int sweep, int trans, void* B_, long l
 static bool check_solve_ulv(hs_handle* h, int trans, bool isz, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
   const char* fn = "hs_ldiv_ulv_*";
   check_handle(h);
-  check_trans(trans, fn);
+  hs_check_trans(fn, trans);
   check_single_rank(h, fn, "block solves");  // (before the state of the handle: a host-side plan over several ranks is refused for its ranks)
   check_solve_args(h, isz, ldc, ldb, n, nrhs);
   const int first = first_hss_front(h);
@@ -1974,7 +1943,9 @@ static void ulv_run(hs_handle* h, int trans, T* dC, int64_t ldc, int64_t nrhs, h
   w.ldt = (int)((mni + 1) / 2 * 2); w.ldx = (int)((mnb + 1) / 2 * 2); w.ldu = (int)((mr + 1) / 2 * 2);
   const size_t el = ((size_t)w.ldt + w.ldx + w.ldu) * KC + 64;
   const size_t bytes = el * sizeof(T) + 256;
-  char* slab = (char*)hs_scratch_take(bytes, "ULV block solve front scratch");
+  HsScratch scratch(bytes, "ULV block solve front scratch");
+  HsDrain drain{s};
+  char* slab = (char*)scratch.p;
   w.desc = slab;
   w.t = (T*)(slab + 256);
   w.xb = w.t + (size_t)w.ldt * KC;
@@ -1982,22 +1953,16 @@ static void ulv_run(hs_handle* h, int trans, T* dC, int64_t ldc, int64_t nrhs, h
   static_assert(sizeof(UlvTJob<T>) <= 256 && sizeof(GemmProb<T>) <= 256, "job descriptions fit the head of the slab");
   v.hss_front = &ulv_front<T>;
   v.hss_ctx = &w;
-  try {
-    hs_solve_multi_run<T>(v, trans, dC, ldc, nrhs, s);
-    HS_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    hs_scratch_give(slab, bytes);
-    throw;
-  }
-  hs_scratch_give(slab, bytes);
+  hs_solve_multi_run<T>(v, trans, dC, ldc, nrhs, s);
+  HS_HIP(hipStreamSynchronize(s));
 }
 template <class T>
 static void ldiv_ulv_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
   if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return block_host<T>(h, trans, C, ldc, B, ldb, n, nrhs);
   if (nrhs == 0) return;
   if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_ulv_*: null block");
-  stage_block<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { ulv_run<T>(h, trans, d, ld, nrhs, s); });
+  hs_stage_block<T>(h->stream, "block solve right-hand sides", C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { ulv_run<T>(h, trans, d, ld, nrhs, s); });
+  h->stats.t_solve = hs_solve_multi_seconds(h->mx);
 }
 template <class T>
 static void ldiv_ulv_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
@@ -2115,13 +2080,7 @@ void hs_interface_view(hs_handle* h, HsInterfaceView* v) {
 void* hs_scratch_take(size_t bytes, const char* what) {
   bytes = std::max<size_t>(bytes, 256);
   void* p = arena_take(bytes);
-  if (!p) {
-    try {
-      dmalloc(&p, bytes, what);
-    } catch (const HsError& e) {  // (the callers outside this file carry error codes as plain ints)
-      throw (int)e.code;
-    }
-  }
+  if (!p) dmalloc(&p, bytes, what);
   return p;
 }
 void hs_scratch_give(void* p, size_t bytes) { arena_give(p, std::max<size_t>(bytes, 256)); }
@@ -2200,9 +2159,6 @@ static int factor_entry(int64_t n, const int64_t* colptr, const int64_t* rowval,
     lap("free of the Schur scratch");
     *out = h;
     return HS_OK;
-  } catch (const HsError& e) {
-    free_handle(h);
-    return e.code;
   } catch (int code) {
     free_handle(h);
     return code;
@@ -2235,55 +2191,10 @@ extern "C" int hs_ldiv_dev_z(hs_handle* F, double* dC, int64_t ldc, const double
   HS_GUARD(ldiv_dev<cplx>(F, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
 }
 
-extern "C" int hs_ldiv_t_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  HS_GUARD(ldiv_host_t<double>(F, trans, C, ldc, B, ldb, n, nrhs));
-}
-extern "C" int hs_ldiv_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  HS_GUARD(ldiv_host_t<cplx>(F, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
-}
-extern "C" int hs_ldiv_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  HS_GUARD(ldiv_dev_t<double>(F, trans, dC, ldc, dB, ldb, n, nrhs, stream));
-}
-extern "C" int hs_ldiv_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  HS_GUARD(ldiv_dev_t<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
-}
-
-extern "C" int hs_ldiv_block_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  HS_GUARD(ldiv_block_host<double>(F, trans, C, ldc, B, ldb, n, nrhs));
-}
-extern "C" int hs_ldiv_block_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  HS_GUARD(ldiv_block_host<cplx>(F, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
-}
-extern "C" int hs_ldiv_block_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  HS_GUARD(ldiv_block_dev<double>(F, trans, dC, ldc, dB, ldb, n, nrhs, stream));
-}
-extern "C" int hs_ldiv_block_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  HS_GUARD(ldiv_block_dev<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
-}
-extern "C" int hs_ldiv_block_t_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  HS_GUARD(ldiv_block_host_t<double>(F, trans, C, ldc, B, ldb, n, nrhs));
-}
-extern "C" int hs_ldiv_block_t_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  HS_GUARD(ldiv_block_host_t<cplx>(F, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
-}
-extern "C" int hs_ldiv_block_dev_t_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  HS_GUARD(ldiv_block_dev_t<double>(F, trans, dC, ldc, dB, ldb, n, nrhs, stream));
-}
-extern "C" int hs_ldiv_block_dev_t_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  HS_GUARD(ldiv_block_dev_t<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
-}
-extern "C" int hs_ldiv_ulv_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  HS_GUARD(ldiv_ulv_host<double>(F, trans, C, ldc, B, ldb, n, nrhs));
-}
-extern "C" int hs_ldiv_ulv_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  HS_GUARD(ldiv_ulv_host<cplx>(F, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
-}
-extern "C" int hs_ldiv_ulv_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  HS_GUARD(ldiv_ulv_dev<double>(F, trans, dC, ldc, dB, ldb, n, nrhs, stream));
-}
-extern "C" int hs_ldiv_ulv_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  HS_GUARD(ldiv_ulv_dev<cplx>(F, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
-}
+HS_LDIV_FAMILY(hs_handle, hs_ldiv_t, hs_ldiv_dev_t, ldiv_host_t, ldiv_dev_t)
+HS_LDIV_FAMILY(hs_handle, hs_ldiv_block, hs_ldiv_block_dev, ldiv_block_host, ldiv_block_dev)
+HS_LDIV_FAMILY(hs_handle, hs_ldiv_block_t, hs_ldiv_block_dev_t, ldiv_block_host_t, ldiv_block_dev_t)
+HS_LDIV_FAMILY(hs_handle, hs_ldiv_ulv, hs_ldiv_ulv_dev, ldiv_ulv_host, ldiv_ulv_dev)
 extern "C" int hs_ldiv_block_info(const hs_handle* F, double* out6) {
   HS_GUARD(if (!F || !out6) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_block_info: null argument");
            hs_solve_multi_info(F->mx, out6));
@@ -2336,11 +2247,11 @@ static NodeH& schur_hss_node(hs_handle* h, int64_t node, bool need_matrix) {
 extern "C" int hs_schur_pack_size(hs_handle* h, int64_t node, int64_t* bytes) {
   HS_GUARD(if (!bytes) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: bytes == NULL"); NodeH& x = schur_hss_node(h, node, true);
            HS_HIP(hipStreamSynchronize(h->stream));  // the compression that produced it ran on the handle's (or a worker's, already joined) stream
-           const int st = hs_hss_pack_size((hs_hss*)x.S_hss, bytes); if (st != 0) throw HsError{st});
+           const int st = hs_hss_pack_size((hs_hss*)x.S_hss, bytes); HS_CHECK(st));
 }
 extern "C" int hs_schur_pack(hs_handle* h, int64_t node, void* dev_buf, int64_t bytes, void* stream) {
   HS_GUARD(NodeH& x = schur_hss_node(h, node, true);
-           const int st = hs_hss_pack((hs_hss*)x.S_hss, dev_buf, bytes, stream ? stream : (void*)h->stream); if (st != 0) throw HsError{st};
+           const int st = hs_hss_pack((hs_hss*)x.S_hss, dev_buf, bytes, stream ? stream : (void*)h->stream); HS_CHECK(st);
            if (!h->opts.keep_schur && !(x.parent >= 0 && h->nodes[(size_t)x.parent].mine)) {  // sent away: nothing on this rank reads it again
              hs_hss_free((hs_hss*)x.S_hss);
              x.S_hss = nullptr;
@@ -2351,7 +2262,7 @@ extern "C" int hs_schur_unpack(hs_handle* h, int64_t node, const void* dev_buf, 
            if (!x.ghost && !x.mine) HS_FAIL(HS_ERR_ARGUMENT, node, "ArgumentError: node %lld is neither owned nor received by rank %d", (long long)node, h->rank);
            if (x.S_hss) { hs_hss_free((hs_hss*)x.S_hss); x.S_hss = nullptr; }
            hs_hss* H = nullptr;
-           const int st = hs_hss_unpack(dev_buf, bytes, h->is_complex ? 1 : 0, stream ? stream : (void*)h->stream, &H); if (st != 0) throw HsError{st};
+           const int st = hs_hss_unpack(dev_buf, bytes, h->is_complex ? 1 : 0, stream ? stream : (void*)h->stream, &H); HS_CHECK(st);
            if (hs_hss_size(H) != x.nb) { hs_hss_free(H); HS_FAIL(HS_ERR_DIMENSION, node, "DimensionMismatch: received an HSS matrix of order %lld for node %lld with |bnd| = %d",
                                                                   (long long)hs_hss_size(H), (long long)node, x.nb); }
            x.S_hss = H;
@@ -2476,7 +2387,7 @@ void hs_sparse_tree(const hs_handle* hc, HsSparseTree* t) {
 // what hs_ldiv_sparse_* refuses of a handle, before any device work and before X is written
 static void check_sparse_handle(const hs_handle* h, int trans, const char* fn) {
   check_handle(h);
-  check_trans(trans, fn);
+  hs_check_trans(fn, trans);
   check_single_rank(h, fn, "block solves");
   check_no_hss_front(h, fn, "block solves");
 }
@@ -2523,21 +2434,13 @@ static void ldiv_sparse(hs_handle* h, int trans, int64_t n, int64_t nrhs, const 
   } else {
     hipStream_t s = h->stream;
     const size_t vbytes = (size_t)std::max<int64_t>(nnzb, 1) * sizeof(T), xbytes = (size_t)nout * nrhs * sizeof(T);
-    T* dv = (T*)hs_scratch_take(vbytes, "sparse solve values");
-    T* dx = nullptr;
-    try {  // nnz values go up, nrows x nrhs come down
-      dx = (T*)hs_scratch_take(xbytes, "sparse solve result");
-      if (nnzb > 0) HS_HIP(hipMemcpy(dv, bnzval, (size_t)nnzb * sizeof(T), hipMemcpyHostToDevice));
-      hs_solve_sparse_run<T>(v, t, trans, nrhs, bcolptr, browval, dv, rows, nrows, dx, nout, s, out8);
-      HS_HIP(hipMemcpy2D(X, ldx * sizeof(T), dx, nout * sizeof(T), nout * sizeof(T), nrhs, hipMemcpyDeviceToHost));
-    } catch (...) {
-      (void)hipStreamSynchronize(s);
-      if (dx) hs_scratch_give(dx, xbytes);
-      hs_scratch_give(dv, vbytes);
-      throw;
+    {  // nnz values go up, nrows x nrhs come down
+      HsScratch dv(vbytes, "sparse solve values"), dx(xbytes, "sparse solve result");
+      HsDrain drain{s};  // (the blocking copy below waits for s, a blocking stream: on success it is idle here)
+      if (nnzb > 0) HS_HIP(hipMemcpy(dv.p, bnzval, (size_t)nnzb * sizeof(T), hipMemcpyHostToDevice));
+      hs_solve_sparse_run<T>(v, t, trans, nrhs, bcolptr, browval, (const T*)dv.p, rows, nrows, (T*)dx.p, nout, s, out8);
+      HS_HIP(hipMemcpy2D(X, ldx * sizeof(T), dx.p, nout * sizeof(T), nout * sizeof(T), nrhs, hipMemcpyDeviceToHost));
     }
-    hs_scratch_give(dx, xbytes);
-    hs_scratch_give(dv, vbytes);
     out8[6] = (double)nnzb + (double)nout * nrhs;
     out8[7] += (double)(vbytes + xbytes);
   }
@@ -2737,7 +2640,7 @@ extern "C" int hs_node_schur_hss(const hs_handle* F, int64_t node, const hs_hss_
            const void* base = x.ext_sb ? x.ext_sb : (F->is_complex ? (const void*)((const cplx*)F->d_sb + x.off_SB) : (const void*)((const double*)F->d_sb + x.off_SB));
            const int st = F->is_complex ? hs_hss_compress_ex_z(x.nb, (const double*)base, x.lds, 1, perm.data(), &oo, nullptr, out)
                                         : hs_hss_compress_ex_d(x.nb, (const double*)base, x.lds, 1, perm.data(), &oo, nullptr, out);
-           if (st != 0) throw HsError{st});
+           HS_CHECK(st));
 }
 
 extern "C" int hs_node_export(const hs_handle* F, int64_t node, int which, double* out) {

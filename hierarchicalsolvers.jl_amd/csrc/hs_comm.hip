@@ -7,12 +7,7 @@
 #include <cstring>
 #include <map>
 #include "hs_common.h"
-
-#define HS_COMM_FAIL(code, ...)         \
-  do {                                  \
-    hs_set_error(code, 0, __VA_ARGS__); \
-    throw (int)(code);                  \
-  } while (0)
+#include "hs_host.h"
 
 // ------------------------------------------------------------------------------------------------
 // RCCL over xGMI: grouped ncclSend / ncclRecv on one world communicator, stream-ordered
@@ -39,10 +34,10 @@ RcclApi& rccl_api() {
     api.so = dlopen(nm, RTLD_NOW | RTLD_GLOBAL);
     if (api.so) break;
   }
-  if (!api.so) HS_COMM_FAIL(HS_ERR_DEVICE, "librccl.so could not be loaded: %s", dlerror());
+  if (!api.so) HS_FAIL(HS_ERR_DEVICE, 0, "librccl.so could not be loaded: %s", dlerror());
   auto sym = [&](const char* nm) {
     void* p = dlsym(api.so, nm);
-    if (!p) HS_COMM_FAIL(HS_ERR_DEVICE, "librccl.so lacks %s", nm);
+    if (!p) HS_FAIL(HS_ERR_DEVICE, 0, "librccl.so lacks %s", nm);
     return p;
   };
   api.GetUniqueId = (decltype(api.GetUniqueId))sym("ncclGetUniqueId");
@@ -59,7 +54,7 @@ RcclApi& rccl_api() {
 #define HS_NCCL(call)                                                                                         \
   do {                                                                                                        \
     ncclResult_t r__ = (call);                                                                                \
-    if (r__ != ncclSuccess) HS_COMM_FAIL(HS_ERR_DEVICE, "%s failed: %s", #call, rccl_api().GetErrorString(r__)); \
+    if (r__ != ncclSuccess) HS_FAIL(HS_ERR_DEVICE, 0, "%s failed: %s", #call, rccl_api().GetErrorString(r__)); \
   } while (0)
 
 struct RcclComm : hs_comm {
@@ -90,8 +85,8 @@ struct RcclComm : hs_comm {
         what = "ncclRecv";
       }
     const ncclResult_t endr = R.GroupEnd();
-    if (bad != ncclSuccess) HS_COMM_FAIL(HS_ERR_DEVICE, "%s failed inside a grouped transfer: %s", what, R.GetErrorString(bad));
-    if (endr != ncclSuccess) HS_COMM_FAIL(HS_ERR_DEVICE, "ncclGroupEnd failed: %s", R.GetErrorString(endr));
+    if (bad != ncclSuccess) HS_FAIL(HS_ERR_DEVICE, 0, "%s failed inside a grouped transfer: %s", what, R.GetErrorString(bad));
+    if (endr != ncclSuccess) HS_FAIL(HS_ERR_DEVICE, 0, "ncclGroupEnd failed: %s", R.GetErrorString(endr));
   }
 };
 
@@ -160,7 +155,7 @@ struct HostComm : hs_comm {
         rptr.push_back(rb + roff[kv.first]);
       }
     int st = fn(user, (int64_t)speer.size(), speer.data(), sptr.data(), sbyte.data(), (int64_t)rpeer.size(), rpeer.data(), rptr.data(), rbyte.data());
-    if (st != 0) HS_COMM_FAIL(HS_ERR_DEVICE, "the host layer's transfer callback returned %d", st);
+    if (st != 0) HS_FAIL(HS_ERR_DEVICE, 0, "the host layer's transfer callback returned %d", st);
     {
       std::map<int, size_t> cur = roff;
       for (auto& p : recvs) {
@@ -191,7 +186,7 @@ hs_comm* hs_comm_make_rccl(const void* id128, int rank, int nranks) {
   if (r != ncclSuccess) {
     c->comm = nullptr;
     delete c;
-    HS_COMM_FAIL(HS_ERR_DEVICE, "ncclCommInitRank(rank %d of %d) failed: %s", rank, nranks, R.GetErrorString(r));
+    HS_FAIL(HS_ERR_DEVICE, 0, "ncclCommInitRank(rank %d of %d) failed: %s", rank, nranks, R.GetErrorString(r));
   }
   return c;
 }
@@ -206,30 +201,20 @@ hs_comm* hs_comm_make_host(hs_transfer_fn fn, void* user, int rank, int nranks) 
 }
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------
-#define HS_COMM_GUARD(...)                                   \
-  try {                                                      \
-    __VA_ARGS__;                                             \
-    return HS_OK;                                            \
-  } catch (int code) {                                       \
-    return code;                                             \
-  } catch (const std::bad_alloc&) {                          \
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed"); \
-    return HS_ERR_NOMEM;                                     \
-  }
 
 static void check_rank(int64_t rank, int64_t nranks) {
-  if (nranks < 1 || rank < 0 || rank >= nranks) HS_COMM_FAIL(HS_ERR_ARGUMENT, "ArgumentError: rank %lld of %lld", (long long)rank, (long long)nranks);
+  if (nranks < 1 || rank < 0 || rank >= nranks) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: rank %lld of %lld", (long long)rank, (long long)nranks);
 }
 
 extern "C" int hs_comm_unique_id(void* id128) {
-  HS_COMM_GUARD(if (!id128) HS_COMM_FAIL(HS_ERR_ARGUMENT, "ArgumentError: id128 == NULL"); hs_comm_rccl_unique_id(id128));
+  HS_GUARD(if (!id128) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: id128 == NULL"); hs_comm_rccl_unique_id(id128));
 }
 extern "C" int hs_comm_create_rccl(const void* id128, int64_t rank, int64_t nranks, hs_comm** out) {
-  HS_COMM_GUARD(if (!id128 || !out) HS_COMM_FAIL(HS_ERR_ARGUMENT, "ArgumentError: null argument"); *out = nullptr; check_rank(rank, nranks);
+  HS_GUARD(if (!id128 || !out) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: null argument"); *out = nullptr; check_rank(rank, nranks);
                 *out = hs_comm_make_rccl(id128, (int)rank, (int)nranks));
 }
 extern "C" int hs_comm_create_host(hs_transfer_fn fn, void* user, int64_t rank, int64_t nranks, hs_comm** out) {
-  HS_COMM_GUARD(if (!fn || !out) HS_COMM_FAIL(HS_ERR_ARGUMENT, "ArgumentError: null argument"); *out = nullptr; check_rank(rank, nranks);
+  HS_GUARD(if (!fn || !out) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: null argument"); *out = nullptr; check_rank(rank, nranks);
                 *out = hs_comm_make_host(fn, user, (int)rank, (int)nranks));
 }
 extern "C" void hs_comm_free(hs_comm* c) { delete c; }
@@ -270,8 +255,8 @@ struct ProbeRes {
 }  // namespace
 
 extern "C" int hs_comm_selftest(hs_comm* c, int64_t bytes) {
-  HS_COMM_GUARD(
-      if (!c || bytes <= 0) HS_COMM_FAIL(HS_ERR_ARGUMENT, "ArgumentError: communicator / byte count");
+  HS_GUARD(
+      if (!c || bytes <= 0) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: communicator / byte count");
       ProbeRes R; unsigned char* d = R.buf((size_t)bytes); unsigned char* r = R.buf((size_t)bytes); HS_HIP(hipStreamCreate(&R.s)); hipStream_t s = R.s;
       const int next = (c->rank + 1) % c->nranks, prev = (c->rank - 1 + c->nranks) % c->nranks;
       hs_comm_fill_kernel<<<(unsigned)((bytes + 255) / 256), 256, 0, s>>>(d, (size_t)bytes, 17u * (unsigned)c->rank + 1u);
@@ -280,14 +265,14 @@ extern "C" int hs_comm_selftest(hs_comm* c, int64_t bytes) {
       hs_comm_fill_kernel<<<(unsigned)((bytes + 255) / 256), 256, 0, s>>>(d, (size_t)bytes, 17u * (unsigned)prev + 1u);  // what prev sent
       std::vector<unsigned char> a(bytes), b(bytes); HS_HIP(hipMemcpyAsync(a.data(), d, bytes, hipMemcpyDeviceToHost, s));
       HS_HIP(hipMemcpyAsync(b.data(), r, bytes, hipMemcpyDeviceToHost, s)); HS_HIP(hipStreamSynchronize(s));
-      if (memcmp(a.data(), b.data(), bytes) != 0) HS_COMM_FAIL(HS_ERR_DEVICE, "communicator self-test: received bytes differ from the sender's"));
+      if (memcmp(a.data(), b.data(), bytes) != 0) HS_FAIL(HS_ERR_DEVICE, 0, "communicator self-test: received bytes differ from the sender's"));
 }
 
 // Point-to-point rate of the transport: `reps` ring shifts of `bytes` bytes (rank r -> r+1), device to device, timed with HIP events on
 // the stream the transfers are enqueued on.  *gbps = bytes sent per rank / time (GB/s; one xGMI link per direction under RCCL).
 extern "C" int hs_comm_bandwidth(hs_comm* c, int64_t bytes, int64_t reps, double* gbps) {
-  HS_COMM_GUARD(
-      if (!c || bytes <= 0 || reps <= 0 || !gbps) HS_COMM_FAIL(HS_ERR_ARGUMENT, "ArgumentError: communicator / sizes"); *gbps = 0.0;
+  HS_GUARD(
+      if (!c || bytes <= 0 || reps <= 0 || !gbps) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: communicator / sizes"); *gbps = 0.0;
       if (c->nranks < 2) return HS_OK;
       ProbeRes R; unsigned char* d = R.buf((size_t)bytes); unsigned char* r = R.buf((size_t)bytes); HS_HIP(hipStreamCreate(&R.s)); hipStream_t s = R.s;
       hipEvent_t e0 = R.event(); hipEvent_t e1 = R.event();

@@ -369,12 +369,3 @@ template <class T>
 void launch_negate(T* A, int ld, int rows, int cols, hipStream_t s);
 
 void hs_set_error(int code, long long info, const char* fmt, ...);
-
-#define HS_HIP(call)                                                                          \
-  do {                                                                                        \
-    hipError_t e__ = (call);                                                                  \
-    if (e__ != hipSuccess) {                                                                  \
-      hs_set_error(-6, 0, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-      throw (int)-6;                                                                          \
-    }                                                                                         \
-  } while (0)

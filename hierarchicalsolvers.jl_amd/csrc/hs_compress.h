@@ -146,7 +146,7 @@ static void factor_compressed_level(hs_handle* h, const int* ids, int count, con
     static const bool lr_qr = !(getenv("HS_LR_QR") && getenv("HS_LR_QR")[0] == '0');
     int st = lr_qr ? lowrank_id_batch<T>(jobs.data(), 2 * count, 0.5 * h->opts.atol, 0.5 * h->opts.rtol, s)
                    : lowrank_compress_batch<T>(jobs.data(), 2 * count, 0.5 * h->opts.atol, 0.5 * h->opts.rtol, s);
-    if (st != 0) throw HsError{st};
+    HS_CHECK(st);
   }
   for (int i = 0; i < count; ++i) {
     NodeH& x = h->nodes[ids[i]];

@@ -1,7 +1,8 @@
 // hs_condest.h -- what the accuracy tools (hs_condest.hip: norm and condition estimates, refined solves; hs_refine_block.hip: refined solves
 // for a block in lockstep) read from a factorization handle: hs_api.hip owns the handle, and the two calls below are the whole interface to
 // it.  Behind HS_CONDEST_KERNELS: what the two files share besides the estimator (hs_normest.h) -- scalar helpers, the +-1 hash, the xGERFS
-// ratio, device buffers, the op(F)^-1 code table, the rows of op(A), and the argument checks of the refined solves.
+// ratio, the op(F)^-1 code table, the rows of op(A), and the argument checks of the refined solves.  Errors, device buffers and the
+// refusals every module words alike are hs_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,37 +36,13 @@ int hs_handle_flow_check(hs_handle* h);
 #ifdef HS_CONDEST_KERNELS
 #include <algorithm>
 #include <vector>
+
+#include "hs_host.h"
 // No contraction of a*b + c into an fma from here to the end of the including file: residuals and weights are the plain products and sums,
 // entry by entry, in both files (see hs_condest.hip).
 #pragma clang fp contract(off)
 
 #define CE_ROWS 2048    // rows per workgroup of the reduction kernels (256 threads x 8)
-
-#define CE_FAIL(code, info, ...)                \
-  do {                                          \
-    hs_set_error((code), (info), __VA_ARGS__);  \
-    throw (int)(code);                          \
-  } while (0)
-#define CE_HIP(call)                                                                                              \
-  do {                                                                                                            \
-    hipError_t e__ = (call);                                                                                      \
-    if (e__ != hipSuccess) CE_FAIL(HS_ERR_DEVICE, 0, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-  } while (0)
-#define CE_CHECK(st)            \
-  do {                          \
-    int s__ = (st);             \
-    if (s__ != HS_OK) throw s__; \
-  } while (0)
-#define CE_GUARD(...)                                         \
-  try {                                                       \
-    __VA_ARGS__;                                              \
-    return HS_OK;                                             \
-  } catch (int code) {                                        \
-    return code;                                              \
-  } catch (const std::bad_alloc&) {                           \
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");  \
-    return HS_ERR_NOMEM;                                      \
-  }
 
 namespace hs_ce {
 
@@ -117,21 +94,6 @@ __device__ inline double berr_ratio(double ra, double wa, ResidArgs g) { return 
 
 inline unsigned nb256(int64_t cnt) { return (unsigned)std::max<int64_t>(1, (cnt + 255) / 256); }
 inline unsigned nbrows(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + CE_ROWS - 1) / CE_ROWS); }
-
-struct DevBuf {
-  std::vector<void*> p;
-  ~DevBuf() {
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-  }
-  template <class U>
-  U* get(size_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(count * sizeof(U), 256)) != hipSuccess) CE_FAIL(HS_ERR_NOMEM, 0, "hipMalloc of %zu bytes failed (condest workspace)", count * sizeof(U));
-    p.push_back(q);
-    return (U*)q;
-  }
-};
 
 // kept in the handle (hs_handle::cx): the CSR map of A (borrowed from the matrix-free fronts when hs_options.mf built one), a buffer for its
 // values, and the longest row / column of A
@@ -204,26 +166,20 @@ OpRows<T> op_rows(const HsHandleView& v, int trans, hipStream_t s) {
 // ---- argument checks of the refined solves: refuse, never drop ---------------------------------------------------------------------------
 // hs_ldiv_refine_* and hs_ldiv_refine_block_* refuse the same things with the same words (fn names the entry point), in the same order; what
 // differs -- ranks, a host-side plan, the HSS-D node, the probe of the block solve -- stays with each entry point, between these three.
-inline HsHandleView view_of(hs_handle* F, const char* fn) {
-  if (!F) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
-  HsHandleView v;
-  hs_handle_view(F, &v);
-  return v;
-}
 template <class T>
 void check_refine_args(const char* fn, const HsHandleView& v, int trans, const T* X, int64_t ldx, const T* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                        const double* berr, const int64_t* steps) {
-  if ((v.is_complex != 0) != (sizeof(T) == 16)) CE_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and B differ", fn);
-  if (trans < 0 || trans > 2) CE_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
+  if ((v.is_complex != 0) != (sizeof(T) == 16)) HS_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and B differ", fn);
+  hs_check_trans(fn, trans);
   if (n != v.n || nrhs < 0 || ldx < n || ldb < n)
-    CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: B has %lld rows (ldx %lld, ldb %lld, nrhs %lld), F is %lld x %lld", fn, (long long)n, (long long)ldx,
+    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: B has %lld rows (ldx %lld, ldb %lld, nrhs %lld), F is %lld x %lld", fn, (long long)n, (long long)ldx,
             (long long)ldb, (long long)nrhs, (long long)v.n, (long long)v.n);
-  if (itmax < 0) CE_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: %s: itmax = %lld < 0", fn, (long long)itmax);
-  if (nrhs > 0 && (!X || !B || !berr || !steps)) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: X, B, berr and steps must not be NULL", fn);
+  if (itmax < 0) HS_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: %s: itmax = %lld < 0", fn, (long long)itmax);
+  if (nrhs > 0 && (!X || !B || !berr || !steps)) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: X, B, berr and steps must not be NULL", fn);
 }
 template <class T>
 void check_no_alias(const char* fn, const T* X, int64_t ldx, const T* B, int64_t ldb, int64_t nrhs) {
-  if (nrhs > 0 && X < B + (size_t)ldb * nrhs && B < X + (size_t)ldx * nrhs) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: X may not alias B", fn);
+  if (nrhs > 0 && X < B + (size_t)ldb * nrhs && B < X + (size_t)ldx * nrhs) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: X may not alias B", fn);
 }
 
 }  // namespace hs_ce

@@ -253,13 +253,13 @@ CsrMap* cache_of(const HsHandleView& v) {
   return (CsrMap*)*v.cx;
 }
 int64_t seg_max(const int64_t* ptr, int64_t n, hipStream_t s) {
-  DevBuf buf;
+  HsDevBuf buf("condest workspace");
   unsigned long long* d = buf.get<unsigned long long>(1);
-  CE_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), s));
+  HS_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), s));
   hipLaunchKernelGGL(seglen_max_kernel, dim3(nb256(n)), dim3(256), 0, s, ptr, n, d);
   unsigned long long m = 0;
-  CE_HIP(hipMemcpyAsync(&m, d, sizeof m, hipMemcpyDeviceToHost, s));
-  CE_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipMemcpyAsync(&m, d, sizeof m, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
   return (int64_t)m;
 }
 }  // namespace
@@ -284,32 +284,32 @@ CsrMap* csr_of(const HsHandleView& v, hipStream_t s) {
       int64_t* rp = nullptr;
       int32_t* ci = nullptr;
       int64_t* tp = nullptr;
-      CE_HIP(hipMalloc((void**)&rp, sizeof(int64_t) * (size_t)(n + 1)));
+      HS_HIP(hipMalloc((void**)&rp, sizeof(int64_t) * (size_t)(n + 1)));
       if (hipMalloc((void**)&ci, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)) != hipSuccess ||
           hipMalloc((void**)&tp, sizeof(int64_t) * (size_t)std::max<int64_t>(nnz, 1)) != hipSuccess) {
         (void)hipFree(rp);
         if (ci) (void)hipFree(ci);
-        CE_FAIL(HS_ERR_NOMEM, 0, "hipMalloc of the CSR map of A failed");
+        HS_FAIL(HS_ERR_NOMEM, 0, "hipMalloc of the CSR map of A failed");
       }
       m->rowptr = rp;
       m->colind = ci;
       m->tperm = tp;
       m->owned = true;
-      DevBuf buf;
+      HsDevBuf buf("condest workspace");
       unsigned long long* cur = buf.get<unsigned long long>((size_t)n);
-      CE_HIP(hipMemsetAsync(rp, 0, sizeof(int64_t) * (size_t)(n + 1), s));
+      HS_HIP(hipMemsetAsync(rp, 0, sizeof(int64_t) * (size_t)(n + 1), s));
       hipLaunchKernelGGL(csr_count_kernel, dim3(nb256(nnz)), dim3(256), 0, s, v.rowval, nnz, (unsigned long long*)rp);
       hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, rp, n + 1);
-      CE_HIP(hipMemcpyAsync(cur, rp, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+      HS_HIP(hipMemcpyAsync(cur, rp, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
       hipLaunchKernelGGL(csr_place_kernel, dim3(nb256(n)), dim3(256), 0, s, v.colptr, v.rowval, n, cur, ci, tp);
       hipLaunchKernelGGL(csr_sort_kernel, dim3(nb256(n)), dim3(256), 0, s, (const int64_t*)rp, ci, tp, n);
-      CE_HIP(hipStreamSynchronize(s));  // `cur` goes with buf
+      HS_HIP(hipStreamSynchronize(s));  // `cur` goes with buf
     }
     m->maxrow = seg_max(m->rowptr, n, s);
   }
   if (!m->valr) {
     void* q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (size_t)std::max<int64_t>(nnz, 1)) != hipSuccess) CE_FAIL(HS_ERR_NOMEM, 0, "hipMalloc of the CSR values of A failed");
+    if (hipMalloc(&q, sizeof(T) * (size_t)std::max<int64_t>(nnz, 1)) != hipSuccess) HS_FAIL(HS_ERR_NOMEM, 0, "hipMalloc of the CSR values of A failed");
     m->valr = q;
   }
   launch_perm_gather<T>((const T*)v.nz, m->tperm, (T*)m->valr, nnz, s);
@@ -325,35 +325,35 @@ namespace {
 template <class T>
 void solve_dev(hs_handle* F, int tr, T* X, int64_t n, int64_t nc, hipStream_t s) {
   if (sizeof(T) == 16)
-    CE_CHECK(hs_ldiv_dev_t_z(F, tr, (double*)X, n, (const double*)X, n, n, nc, (void*)s));
+    HS_CHECK(hs_ldiv_dev_t_z(F, tr, (double*)X, n, (const double*)X, n, n, nc, (void*)s));
   else
-    CE_CHECK(hs_ldiv_dev_t_d(F, tr, (double*)X, n, (const double*)X, n, n, nc, (void*)s));
+    HS_CHECK(hs_ldiv_dev_t_d(F, tr, (double*)X, n, (const double*)X, n, n, nc, (void*)s));
 }
 
 // ---- argument checks: refuse, never drop ----------------------------------------------------------------------------------------------
 HsHandleView checked_view(hs_handle* F, const char* fn) {
-  const HsHandleView v = view_of(F, fn);
-  if (!v.device) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
-  if (v.nranks > 1) CE_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: a factorization over %d ranks is not supported (single-rank factorizations only)", fn, v.nranks);
+  const HsHandleView v = hs_view_of(F, fn);
+  if (!v.device) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
+  if (v.nranks > 1) HS_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: a factorization over %d ranks is not supported (single-rank factorizations only)", fn, v.nranks);
   return v;
 }
 void check_factored(const HsHandleView& v, const char* fn) {
-  if (!v.factored) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
+  if (!v.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
 }
 void check_t_solves(const HsHandleView& v, const char* fn, const char* what) {
   if (v.t_refused_node >= 0)
-    CE_FAIL(HS_ERR_UNSUPPORTED, v.t_refused_node, "%s: %s needs transposed solves, and node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): "
+    HS_FAIL(HS_ERR_UNSUPPORTED, v.t_refused_node, "%s: %s needs transposed solves, and node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): "
             "transposed ULV solves are not implemented", fn, what, v.t_refused_node);
 }
 void check_t(const HsHandleView& v, int64_t t, const char* fn) {
   const int64_t tmax = std::min<int64_t>(CE_MAXT, v.n);
-  if (t < 1 || t > tmax) CE_FAIL(HS_ERR_ARGUMENT, t, "ArgumentError: %s: t = %lld outside 1:%lld (min(8, n))", fn, (long long)t, (long long)tmax);
+  if (t < 1 || t > tmax) HS_FAIL(HS_ERR_ARGUMENT, t, "ArgumentError: %s: t = %lld outside 1:%lld (min(8, n))", fn, (long long)t, (long long)tmax);
 }
 
 // ---- drivers -------------------------------------------------------------------------------------------------------------------------
 template <class T>
 double opnorm_impl(hs_handle* F, const HsHandleView& v, int p, hipStream_t s) {
-  DevBuf buf;
+  HsDevBuf buf("condest workspace");
   const int64_t n = v.n;
   double* sums = buf.get<double>((size_t)n);
   double* part = buf.get<double>((size_t)nbrows(n));
@@ -367,15 +367,15 @@ double opnorm_impl(hs_handle* F, const HsHandleView& v, int p, hipStream_t s) {
   hipLaunchKernelGGL(dmax_part_kernel, dim3(nbrows(n)), dim3(256), 0, s, (const double*)sums, n, part);
   hipLaunchKernelGGL(max_final_kernel, dim3(1), dim3(256), 0, s, (const double*)part, (int64_t)nbrows(n), out);
   double r = 0.0;
-  CE_HIP(hipMemcpyAsync(&r, out, sizeof r, hipMemcpyDeviceToHost, s));
-  CE_HIP(hipStreamSynchronize(s));
-  CE_CHECK(hs_handle_flow_check(F));
+  HS_HIP(hipMemcpyAsync(&r, out, sizeof r, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  HS_CHECK(hs_handle_flow_check(F));
   return r;
 }
 
 template <class T>
 double normestinv_impl(hs_handle* F, const HsHandleView& v, int trans, int t, int itmax, int64_t* nsolves, hipStream_t s) {
-  DevBuf buf;
+  HsDevBuf buf("condest workspace");
   HostIo io{F, s};
   EstWork<T, CE_MAXT> ew;
   ew.alloc(buf, v.n, t, 1);
@@ -393,7 +393,7 @@ template <class T>
 void refine_dev(hs_handle* F, const HsHandleView& v, int trans, T* dX, int64_t ldx, const T* dB, int64_t ldb, int64_t nrhs, int64_t itmax, double* berr,
                 double* ferr, int64_t* steps, hipStream_t s) {
   const int64_t n = v.n;
-  DevBuf buf;
+  HsDevBuf buf("condest workspace");
   HostIo io{F, s};
   double* res = buf.get<double>(1);  // the scalar the host reads
   T* r = buf.get<T>((size_t)n);
@@ -420,7 +420,7 @@ void refine_dev(hs_handle* F, const HsHandleView& v, int trans, T* dX, int64_t l
   for (int64_t col = 0; col < nrhs; ++col) {
     T* x = dX + col * ldx;
     const T* b = dB + col * ldb;
-    CE_HIP(hipMemcpyAsync(x, b, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    HS_HIP(hipMemcpyAsync(x, b, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, s));
     solve_dev<T>(F, tr, x, n, 1, s);
     double lst = 3.0, be = 0.0;
     int64_t cnt = 0;
@@ -429,7 +429,7 @@ void refine_dev(hs_handle* F, const HsHandleView& v, int trans, T* dX, int64_t l
       io.read(res, 1);
       be = io.hd[0];
       if (!(be > CE_EPS && 2.0 * be <= lst && cnt < itmax)) break;
-      CE_HIP(hipMemcpyAsync(d, r, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, s));
+      HS_HIP(hipMemcpyAsync(d, r, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, s));
       solve_dev<T>(F, tr, d, n, 1, s);
       hipLaunchKernelGGL(axpy1_kernel<T>, dim3(nb256(n)), dim3(256), 0, s, x, (const T*)d, n);
       lst = be;
@@ -449,8 +449,8 @@ void refine_dev(hs_handle* F, const HsHandleView& v, int trans, T* dX, int64_t l
       ferr[col] = xn != 0.0 ? est / xn : est;
     }
   }
-  CE_HIP(hipStreamSynchronize(s));
-  CE_CHECK(hs_handle_flow_check(F));
+  HS_HIP(hipStreamSynchronize(s));
+  HS_CHECK(hs_handle_flow_check(F));
 }
 
 template <class T>
@@ -468,39 +468,39 @@ void refine_entry(hs_handle* F, int trans, T* X, int64_t ldx, const T* B, int64_
     return refine_dev<T>(F, v, trans, X, ldx, B, ldb, nrhs, itmax, berr, ferr, steps, (hipStream_t)stream);
   }
   hipStream_t s = v.stream;
-  DevBuf buf;
+  HsDevBuf buf("condest workspace");
   T* dX = buf.get<T>((size_t)n * nrhs);
   T* dB = buf.get<T>((size_t)n * nrhs);
-  CE_HIP(hipMemcpy2DAsync(dB, sizeof(T) * n, B, sizeof(T) * ldb, sizeof(T) * n, nrhs, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpy2DAsync(dB, sizeof(T) * n, B, sizeof(T) * ldb, sizeof(T) * n, nrhs, hipMemcpyHostToDevice, s));
   refine_dev<T>(F, v, trans, dX, n, dB, n, nrhs, itmax, berr, ferr, steps, s);
-  CE_HIP(hipMemcpy2DAsync(X, sizeof(T) * ldx, dX, sizeof(T) * n, sizeof(T) * n, nrhs, hipMemcpyDeviceToHost, s));
-  CE_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipMemcpy2DAsync(X, sizeof(T) * ldx, dX, sizeof(T) * n, sizeof(T) * n, nrhs, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------------
 extern "C" int hs_opnorm(hs_handle* F, int p, double* norm) {
-  CE_GUARD(const HsHandleView v = checked_view(F, "hs_opnorm"); if (p != 0 && p != 1) CE_FAIL(HS_ERR_ARGUMENT, p, "ArgumentError: hs_opnorm: p = %d (1 or 0 = Inf)", p);
-           if (!norm) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_opnorm: norm == NULL");
+  HS_GUARD(const HsHandleView v = checked_view(F, "hs_opnorm"); if (p != 0 && p != 1) HS_FAIL(HS_ERR_ARGUMENT, p, "ArgumentError: hs_opnorm: p = %d (1 or 0 = Inf)", p);
+           if (!norm) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_opnorm: norm == NULL");
            *norm = v.is_complex ? opnorm_impl<cplx>(F, v, p, v.stream) : opnorm_impl<double>(F, v, p, v.stream));
 }
 
 extern "C" int hs_normestinv(hs_handle* F, int trans, int64_t t, int64_t itmax, double* est, int64_t* nsolves, void* stream) {
-  CE_GUARD(const HsHandleView v = checked_view(F, "hs_normestinv"); check_factored(v, "hs_normestinv");
-           if (trans < 0 || trans > 2) CE_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_normestinv: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", trans);
+  HS_GUARD(const HsHandleView v = checked_view(F, "hs_normestinv"); check_factored(v, "hs_normestinv");
+           if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_normestinv: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", trans);
            check_t(v, t, "hs_normestinv");
-           if (itmax < 1 || itmax > CE_MAXIT) CE_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: hs_normestinv: itmax = %lld outside 1:%d", (long long)itmax, CE_MAXIT);
-           if (!est) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_normestinv: est == NULL");
+           if (itmax < 1 || itmax > CE_MAXIT) HS_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: hs_normestinv: itmax = %lld outside 1:%d", (long long)itmax, CE_MAXIT);
+           if (!est) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_normestinv: est == NULL");
            check_t_solves(v, "hs_normestinv", "the estimator");
            hipStream_t s = (hipStream_t)stream;
            *est = v.is_complex ? normestinv_impl<cplx>(F, v, trans, (int)t, (int)itmax, nsolves, s) : normestinv_impl<double>(F, v, trans, (int)t, (int)itmax, nsolves, s));
 }
 
 extern "C" int hs_condest(hs_handle* F, int p, int64_t t, double* cond, double* normA, double* normFinv, void* stream) {
-  CE_GUARD(const HsHandleView v = checked_view(F, "hs_condest"); check_factored(v, "hs_condest");
-           if (p != 0 && p != 1) CE_FAIL(HS_ERR_ARGUMENT, p, "ArgumentError: hs_condest: p = %d (1 or 0 = Inf)", p);
-           check_t(v, t, "hs_condest"); if (!cond) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_condest: cond == NULL");
+  HS_GUARD(const HsHandleView v = checked_view(F, "hs_condest"); check_factored(v, "hs_condest");
+           if (p != 0 && p != 1) HS_FAIL(HS_ERR_ARGUMENT, p, "ArgumentError: hs_condest: p = %d (1 or 0 = Inf)", p);
+           check_t(v, t, "hs_condest"); if (!cond) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_condest: cond == NULL");
            check_t_solves(v, "hs_condest", "the estimator");
            hipStream_t s = (hipStream_t)stream;
            const int trans = p == 1 ? 0 : 1;  // ||F^-1||_Inf = ||F^-T||_1
@@ -511,17 +511,17 @@ extern "C" int hs_condest(hs_handle* F, int p, int64_t t, double* cond, double* 
 
 extern "C" int hs_ldiv_refine_d(hs_handle* F, int trans, double* X, int64_t ldx, const double* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                                 double* berr, double* ferr, int64_t* steps) {
-  CE_GUARD(refine_entry<double>(F, trans, X, ldx, B, ldb, n, nrhs, itmax, berr, ferr, steps, false, nullptr));
+  HS_GUARD(refine_entry<double>(F, trans, X, ldx, B, ldb, n, nrhs, itmax, berr, ferr, steps, false, nullptr));
 }
 extern "C" int hs_ldiv_refine_z(hs_handle* F, int trans, double* X, int64_t ldx, const double* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                                 double* berr, double* ferr, int64_t* steps) {
-  CE_GUARD(refine_entry<cplx>(F, trans, (cplx*)X, ldx, (const cplx*)B, ldb, n, nrhs, itmax, berr, ferr, steps, false, nullptr));
+  HS_GUARD(refine_entry<cplx>(F, trans, (cplx*)X, ldx, (const cplx*)B, ldb, n, nrhs, itmax, berr, ferr, steps, false, nullptr));
 }
 extern "C" int hs_ldiv_refine_dev_d(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                                     double* berr, double* ferr, int64_t* steps, void* stream) {
-  CE_GUARD(refine_entry<double>(F, trans, dX, ldx, dB, ldb, n, nrhs, itmax, berr, ferr, steps, true, stream));
+  HS_GUARD(refine_entry<double>(F, trans, dX, ldx, dB, ldb, n, nrhs, itmax, berr, ferr, steps, true, stream));
 }
 extern "C" int hs_ldiv_refine_dev_z(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                                     double* berr, double* ferr, int64_t* steps, void* stream) {
-  CE_GUARD(refine_entry<cplx>(F, trans, (cplx*)dX, ldx, (const cplx*)dB, ldb, n, nrhs, itmax, berr, ferr, steps, true, stream));
+  HS_GUARD(refine_entry<cplx>(F, trans, (cplx*)dX, ldx, (const cplx*)dB, ldb, n, nrhs, itmax, berr, ferr, steps, true, stream));
 }

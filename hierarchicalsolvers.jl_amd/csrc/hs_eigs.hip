@@ -27,8 +27,7 @@
 #include <new>
 #include <string>
 
-#include "hs_gmres_common.h"  // DevBuf, GM_HIP, RowsOf, launch_spmm_op; includes hs_solver.h, hs_common.h, hs_gmres_op.h
-#include "hs_condest.h"       // HsHandleView
+#include "hs_gmres_common.h"  // RowsOf, launch_spmm_op; includes hs_solver.h, hs_common.h, hs_host.h, hs_gmres_op.h
 #include "hs_eigs.h"
 #include "hs_small_eig.h"
 #include "../../include/hs_kernels.h"
@@ -56,12 +55,6 @@ struct PhaseClock {
     t0 = t1;
   }
 };
-
-#define EG_FAIL(code, info, ...)                \
-  do {                                          \
-    hs_set_error((code), (info), __VA_ARGS__);  \
-    throw (int)(code);                          \
-  } while (0)
 
 template <class T>
 struct HostOf;
@@ -105,10 +98,10 @@ struct Eigs {
   // Y (n x nc, ld n) = op(M) X
   void mult_m(const T* X, int64_t ldx, T* Y, int nc) {
     if (g_phase_sync) {  // a synchronisation before and behind each product, so that the clock sees the product alone
-      GM_HIP(hipStreamSynchronize(s));
+      HS_HIP(hipStreamSynchronize(s));
       const auto t0 = std::chrono::steady_clock::now();
       launch_spmm_op<T>(M, X, ldx, nullptr, Y, n, nullptr, 0, nullptr, n, nc, s);
-      GM_HIP(hipStreamSynchronize(s));
+      HS_HIP(hipStreamSynchronize(s));
       g_mprod_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     } else {
       launch_spmm_op<T>(M, X, ldx, nullptr, Y, n, nullptr, 0, nullptr, n, nc, s);
@@ -135,8 +128,8 @@ struct Eigs {
         const T* mw = metric(W);
         launch_mod_inner<T>(V, ldv, mw, minner ? n : ldv, n, k, p, 0, part, dh, k, s);
         launch_mod_apply<T>(W, ldv, V, ldv, dh, k, n, k, p, 0, s);
-        GM_HIP(hipMemcpyAsync(h.data(), dh, sizeof(T) * (size_t)k * p, hipMemcpyDeviceToHost, s));
-        GM_HIP(hipStreamSynchronize(s));
+        HS_HIP(hipMemcpyAsync(h.data(), dh, sizeof(T) * (size_t)k * p, hipMemcpyDeviceToHost, s));
+        HS_HIP(hipStreamSynchronize(s));
         for (int c = 0; c < p; ++c)  // Hacc += h Racc (Racc upper)
           for (int l = 0; l <= c; ++l) {
             const S r = Racc[(size_t)c * p + l];
@@ -150,17 +143,17 @@ struct Eigs {
         const T* mw = metric(W);
         launch_mod_inner<T>(W, ldv, mw, minner ? n : ldv, n, p, p, 0, part, dG, p, s);
         if (minner && col0 < 0 && attempt == 0 && round == 0) {  // the start block as given: a diagonal entry v^H op(M) v that is not positive
-          GM_HIP(hipMemcpyAsync(tmp.data(), dG, sizeof(T) * (size_t)p * p, hipMemcpyDeviceToHost, s));
-          GM_HIP(hipStreamSynchronize(s));
+          HS_HIP(hipMemcpyAsync(tmp.data(), dG, sizeof(T) * (size_t)p * p, hipMemcpyDeviceToHost, s));
+          HS_HIP(hipStreamSynchronize(s));
           for (int c = 0; c < p; ++c)
             if (!(std::real(tmp[(size_t)c * p + c]) > 0.0))
-              EG_FAIL(HS_ERR_ARGUMENT, c, "ArgumentError: hs_eigs_gen_*: inner = 1 needs a Hermitian positive definite M: v^H op(M) v = %g for column %d of the start block",
+              HS_FAIL(HS_ERR_ARGUMENT, c, "ArgumentError: hs_eigs_gen_*: inner = 1 needs a Hermitian positive definite M: v^H op(M) v = %g for column %d of the start block",
                       std::real(tmp[(size_t)c * p + c]), c + 1);
         }
         launch_eigs_chol_inv<T>(dG, p, p, dR, dRi, dInfo, s);
-        GM_HIP(hipMemcpyAsync(&bad, dInfo, sizeof(int), hipMemcpyDeviceToHost, s));
-        GM_HIP(hipMemcpyAsync(R.data(), dR, sizeof(T) * (size_t)p * p, hipMemcpyDeviceToHost, s));
-        GM_HIP(hipStreamSynchronize(s));
+        HS_HIP(hipMemcpyAsync(&bad, dInfo, sizeof(int), hipMemcpyDeviceToHost, s));
+        HS_HIP(hipMemcpyAsync(R.data(), dR, sizeof(T) * (size_t)p * p, hipMemcpyDeviceToHost, s));
+        HS_HIP(hipStreamSynchronize(s));
         if (bad >= 0) break;
         launch_eigs_rotate<T>(W, ldv, W, ldv, dRi, p, n, p, p, s);
         for (int c = 0; c < p; ++c)  // Racc <- R Racc
@@ -187,7 +180,7 @@ struct Eigs {
       for (int c = 0; c < p; ++c) Racc[(size_t)c * p + bad] = S(0.0);
       g_einfo[EI_REPLACED] += 1;
     }
-    EG_FAIL(HS_ERR_SINGULAR, k, "hs_eigs_*: the block at column %d stays rank deficient after %d replaced columns", k, p + 1);
+    HS_FAIL(HS_ERR_SINGULAR, k, "hs_eigs_*: the block at column %d stays rank deficient after %d replaced columns", k, p + 1);
   }
 };
 
@@ -274,43 +267,41 @@ struct HostCsc {
 // is not monotone).  Returns whether M is given.
 template <class T>
 bool check_m_args(const char* fn, const HostCsc<T>& M, int inner, int64_t n) {
-  if (inner < 0 || inner > 1) EG_FAIL(HS_ERR_ARGUMENT, inner, "ArgumentError: %s: inner = %d (0: Euclidean, 1: the op(M) inner product)", fn, inner);
+  if (inner < 0 || inner > 1) HS_FAIL(HS_ERR_ARGUMENT, inner, "ArgumentError: %s: inner = %d (0: Euclidean, 1: the op(M) inner product)", fn, inner);
   const int given = (M.colptr ? 1 : 0) + (M.rowval ? 1 : 0) + (M.nzval ? 1 : 0);
-  if (given != 0 && given != 3) EG_FAIL(HS_ERR_ARGUMENT, given, "ArgumentError: %s: mcolptr, mrowval and mnzval must all be given, or all be NULL (M = I)", fn);
+  if (given != 0 && given != 3) HS_FAIL(HS_ERR_ARGUMENT, given, "ArgumentError: %s: mcolptr, mrowval and mnzval must all be given, or all be NULL (M = I)", fn);
   if (given == 0) return false;
   if (n > (int64_t)INT32_MAX)
-    EG_FAIL(HS_ERR_ARGUMENT, n, "ArgumentError: %s: n = %lld exceeds the 32-bit indices of the device matrix (limit %d)", fn, (long long)n, INT32_MAX);
-  if (M.colptr[0] != 1) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: mcolptr must be 1-based (SparseMatrixCSC)", fn);
+    HS_FAIL(HS_ERR_ARGUMENT, n, "ArgumentError: %s: n = %lld exceeds the 32-bit indices of the device matrix (limit %d)", fn, (long long)n, INT32_MAX);
+  if (M.colptr[0] != 1) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: mcolptr must be 1-based (SparseMatrixCSC)", fn);
   for (int64_t c = 0; c < n; ++c)
     if (M.colptr[c + 1] < M.colptr[c])
-      EG_FAIL(HS_ERR_ARGUMENT, c + 1, "ArgumentError: %s: mcolptr[%lld] = %lld is below mcolptr[%lld] = %lld", fn, (long long)c + 2, (long long)M.colptr[c + 1], (long long)c + 1,
+      HS_FAIL(HS_ERR_ARGUMENT, c + 1, "ArgumentError: %s: mcolptr[%lld] = %lld is below mcolptr[%lld] = %lld", fn, (long long)c + 2, (long long)M.colptr[c + 1], (long long)c + 1,
               (long long)M.colptr[c]);
   const int64_t nnz = M.colptr[n] - 1;
   for (int64_t e = 0; e < nnz; ++e)
     if (M.rowval[e] < 1 || M.rowval[e] > n)
-      EG_FAIL(HS_ERR_ARGUMENT, e, "ArgumentError: %s: mrowval[%lld] = %lld outside 1:%lld", fn, (long long)e + 1, (long long)M.rowval[e], (long long)n);
+      HS_FAIL(HS_ERR_ARGUMENT, e, "ArgumentError: %s: mrowval[%lld] = %lld outside 1:%lld", fn, (long long)e + 1, (long long)M.rowval[e], (long long)n);
   return true;
 }
 
 template <class T>
 void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inner, int64_t nev, int64_t ncv, int64_t block, double sigma_re, double sigma_im, double tol, int64_t maxrestart, const T* V0,
-              int64_t ldv0, int64_t seed, int where, double* lam, T* X, int64_t ldx, double* resid, double* est, int64_t* nout_, int64_t* nconv_, void* stream, DevBuf& buf,
+              int64_t ldv0, int64_t seed, int where, double* lam, T* X, int64_t ldx, double* resid, double* est, int64_t* nout_, int64_t* nconv_, void* stream, HsDevBuf& buf,
               hipEvent_t* e0, hipEvent_t* e1) {
   typedef typename HostOf<T>::type S;
   const char* fn = "hs_eigs_*";
   const bool real_h = sizeof(T) == 8;
   // ---- arguments: nothing is written before all of them (and the handle) have passed
-  if (!F) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
-  if (trans < 0 || trans > 2) EG_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
-  HsHandleView v;
-  hs_handle_view(F, &v);
+  const HsHandleView v = hs_view_of(F, fn);
+  hs_check_trans(fn, trans);
   if ((v.is_complex != 0) != !real_h || n != v.n)
-    EG_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: called for %s with n = %lld, F is %lld x %lld %s", fn, real_h ? "Float64" : "ComplexF64", (long long)n, (long long)v.n,
+    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: called for %s with n = %lld, F is %lld x %lld %s", fn, real_h ? "Float64" : "ComplexF64", (long long)n, (long long)v.n,
             (long long)v.n, v.is_complex ? "ComplexF64" : "Float64");
-  if (nev < 1) EG_FAIL(HS_ERR_ARGUMENT, nev, "ArgumentError: %s: nev = %lld < 1", fn, (long long)nev);
-  if (block < 0 || ncv < 0) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: ncv = %lld, block = %lld (0 selects the default)", fn, (long long)ncv, (long long)block);
+  if (nev < 1) HS_FAIL(HS_ERR_ARGUMENT, nev, "ArgumentError: %s: nev = %lld < 1", fn, (long long)nev);
+  if (block < 0 || ncv < 0) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: ncv = %lld, block = %lld (0 selects the default)", fn, (long long)ncv, (long long)block);
   if (block == 0) block = 16;
-  if (block > HS_EIGS_MAXBLOCK) EG_FAIL(HS_ERR_ARGUMENT, block, "ArgumentError: %s: block = %lld exceeds the limit of %d", fn, (long long)block, HS_EIGS_MAXBLOCK);
+  if (block > HS_EIGS_MAXBLOCK) HS_FAIL(HS_ERR_ARGUMENT, block, "ArgumentError: %s: block = %lld exceeds the limit of %d", fn, (long long)block, HS_EIGS_MAXBLOCK);
   if (ncv == 0) {  // the multiple of block >= max(2 nev + block, 4 block), capped by ncv + block <= 256
     const int64_t want = std::max<int64_t>(2 * nev + block, 4 * block);
     ncv = (want + block - 1) / block * block;
@@ -318,28 +309,28 @@ void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inne
     if (ncv > cap) ncv = cap;
   }
   if (ncv + block > HS_EIGS_MAXBASIS)
-    EG_FAIL(HS_ERR_ARGUMENT, ncv, "ArgumentError: %s: ncv + block = %lld + %lld exceeds the limit of %d basis columns", fn, (long long)ncv, (long long)block, HS_EIGS_MAXBASIS);
-  if (ncv < nev + block) EG_FAIL(HS_ERR_ARGUMENT, ncv, "ArgumentError: %s: ncv = %lld < nev + block = %lld + %lld", fn, (long long)ncv, (long long)nev, (long long)block);
-  if (n < ncv + block) EG_FAIL(HS_ERR_ARGUMENT, n, "ArgumentError: %s: n = %lld < ncv + block = %lld + %lld", fn, (long long)n, (long long)ncv, (long long)block);
-  if (!lam || !resid || !est || !nout_ || !nconv_) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: lam, resid, est, nout and nconv must not be NULL", fn);
-  if (where != 0 && where != 1) EG_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: %s: where = %d (0: host pointers, 1: device pointers)", fn, where);
-  if ((V0 && ldv0 < n) || (X && ldx < n)) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: ldv0 = %lld, ldx = %lld below n = %lld", fn, (long long)ldv0, (long long)ldx, (long long)n);
-  if (real_h && sigma_im != 0.0) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: a complex shift on a Float64 factorization (factor A - sigma I as ComplexF64)", fn);
+    HS_FAIL(HS_ERR_ARGUMENT, ncv, "ArgumentError: %s: ncv + block = %lld + %lld exceeds the limit of %d basis columns", fn, (long long)ncv, (long long)block, HS_EIGS_MAXBASIS);
+  if (ncv < nev + block) HS_FAIL(HS_ERR_ARGUMENT, ncv, "ArgumentError: %s: ncv = %lld < nev + block = %lld + %lld", fn, (long long)ncv, (long long)nev, (long long)block);
+  if (n < ncv + block) HS_FAIL(HS_ERR_ARGUMENT, n, "ArgumentError: %s: n = %lld < ncv + block = %lld + %lld", fn, (long long)n, (long long)ncv, (long long)block);
+  if (!lam || !resid || !est || !nout_ || !nconv_) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: lam, resid, est, nout and nconv must not be NULL", fn);
+  if (where != 0 && where != 1) HS_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: %s: where = %d (0: host pointers, 1: device pointers)", fn, where);
+  if ((V0 && ldv0 < n) || (X && ldx < n)) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: ldv0 = %lld, ldx = %lld below n = %lld", fn, (long long)ldv0, (long long)ldx, (long long)n);
+  if (real_h && sigma_im != 0.0) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: a complex shift on a Float64 factorization (factor A - sigma I as ComplexF64)", fn);
   if (!(tol >= 0.0) || maxrestart < 0 || !std::isfinite(sigma_re) || !std::isfinite(sigma_im))
-    EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: tol = %g, maxrestart = %lld, sigma = (%g, %g)", fn, tol, (long long)maxrestart, sigma_re, sigma_im);
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: tol = %g, maxrestart = %lld, sigma = (%g, %g)", fn, tol, (long long)maxrestart, sigma_re, sigma_im);
   const bool has_m = check_m_args<T>(fn, Mh, inner, n);
   if (const int st = hs_gmres_own_check(F, fn, 1)) throw st;  // more than one rank: neither the block solve nor the handle's own A
   {  // what hs_ldiv_block_dev_t_* refuses is refused here, with its words
     const int st = refused_by_block_solve<T>(F, trans, n);
     if (st == HS_ERR_UNSUPPORTED) {
       const std::string why = hs_last_error();
-      EG_FAIL(HS_ERR_UNSUPPORTED, hs_last_error_info(), "%s: the block solve does not serve this handle (%s)", fn, why.c_str());
+      HS_FAIL(HS_ERR_UNSUPPORTED, hs_last_error_info(), "%s: the block solve does not serve this handle (%s)", fn, why.c_str());
     }
     if (st != HS_OK) throw st;
   }
   if (const int st = hs_gmres_own_check(F, fn, 0)) throw st;
   int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) EG_FAIL(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) HS_FAIL(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
 
   // ---- workspace
   Eigs<T> E;
@@ -407,13 +398,13 @@ void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inne
   }
   g_einfo[EI_WORK_BYTES] = (double)bytes;
   g_einfo[EI_NCV] = (double)ncv;
-  GM_HIP(hipEventCreate(e0));
-  GM_HIP(hipEventCreate(e1));
-  GM_HIP(hipEventRecord(*e0, s));
+  HS_HIP(hipEventCreate(e0));
+  HS_HIP(hipEventCreate(e1));
+  HS_HIP(hipEventRecord(*e0, s));
 
   // ---- the start block
   if (V0)
-    GM_HIP(hipMemcpy2DAsync(E.V, ldv * sizeof(T), V0, ldv0 * sizeof(T), n * sizeof(T), p, where ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpy2DAsync(E.V, ldv * sizeof(T), V0, ldv0 * sizeof(T), n * sizeof(T), p, where ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   else
     launch_eigs_init<T>(E.V, ldv, n, p, seed, 0, 0, s);
   PhaseClock clk;
@@ -438,7 +429,7 @@ void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inne
       g_einfo[EI_SOLVES] += 1;
       g_einfo[EI_COLAPPS] += p;
       if (g_phase_sync) {
-        GM_HIP(hipStreamSynchronize(s));
+        HS_HIP(hipStreamSynchronize(s));
         clk.lap(EP_SOLVE);
       }
       E.orth_block(m + p, m);
@@ -451,7 +442,7 @@ void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inne
     for (int j = 0; j < m; ++j)
       for (int i = 0; i < m; ++i) Hc[(size_t)j * m + i] = zc(E.g(i, j));
     const int bad = hs_se::small_eig(m, Hc.data(), m, w.data(), Y.data(), m);
-    if (bad) EG_FAIL(HS_ERR_SINGULAR, bad - 1, "%s: the QR iteration on the %d x %d projected matrix did not converge", fn, m, m);
+    if (bad) HS_FAIL(HS_ERR_SINGULAR, bad - 1, "%s: the QR iteration on the %d x %d projected matrix did not converge", fn, m, m);
     sort_ritz(m, real_h, w, order, pair);
     estv.assign((size_t)m, 0.0);
     for (int c = 0; c < m; ++c) {
@@ -478,7 +469,7 @@ void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inne
       keep += more ? 1 : -1;
       if (more) lim = ncv + 1;
     }
-    if (keep < 1) EG_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: ncv = %lld leaves no room to restart", fn, (long long)ncv);
+    if (keep < 1) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: ncv = %lld leaves no room to restart", fn, (long long)ncv);
     std::vector<S> Z((size_t)m * keep), Q((size_t)m * keep), HQ((size_t)m * keep), Gn((size_t)(keep + p) * keep, S(0.0));
     for (int c = 0; c < keep; ++c) ritz_column(m, Y.data(), m, order, pair, c, Z.data() + (size_t)c * m);
     hs_se::house_q<S>(m, keep, Z.data(), m, Q.data(), m);
@@ -501,11 +492,11 @@ void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inne
         Gn[(size_t)c * ldn + keep + i] = acc;
       }
     }
-    GM_HIP(hipMemcpyAsync(E.dQ, Q.data(), sizeof(T) * (size_t)m * keep, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(E.dQ, Q.data(), sizeof(T) * (size_t)m * keep, hipMemcpyHostToDevice, s));
     launch_eigs_rotate<T>(E.V, ldv, E.V, ldv, E.dQ, m, n, m, keep, s);
     for (int c = 0; c < p; ++c)  // ascending: a destination column never lies behind a source column still to be read
-      GM_HIP(hipMemcpyAsync(E.V + (size_t)(keep + c) * ldv, E.V + (size_t)(m + c) * ldv, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    GM_HIP(hipStreamSynchronize(s));
+      HS_HIP(hipMemcpyAsync(E.V + (size_t)(keep + c) * ldv, E.V + (size_t)(m + c) * ldv, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    HS_HIP(hipStreamSynchronize(s));
     std::fill(E.G.begin(), E.G.end(), S(0.0));
     for (int c = 0; c < keep; ++c)
       for (int i = 0; i < keep + p; ++i) E.g(i, c) = Gn[(size_t)c * ldn + i];
@@ -530,9 +521,9 @@ void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inne
     lamv[(size_t)2 * c] = sigma_re + mu[(size_t)2 * c];
     lamv[(size_t)2 * c + 1] = sg_im + mu[(size_t)2 * c + 1];
   }
-  GM_HIP(hipMemcpyAsync(E.dQ, Yo.data(), sizeof(T) * (size_t)m * nout, hipMemcpyHostToDevice, s));
-  GM_HIP(hipMemcpyAsync(dmu, mu.data(), sizeof(double) * 2 * (size_t)nx, hipMemcpyHostToDevice, s));
-  GM_HIP(hipMemcpyAsync(dpair, pr.data(), sizeof(int) * (size_t)nx, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(E.dQ, Yo.data(), sizeof(T) * (size_t)m * nout, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(dmu, mu.data(), sizeof(double) * 2 * (size_t)nx, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(dpair, pr.data(), sizeof(int) * (size_t)nx, hipMemcpyHostToDevice, s));
   launch_eigs_rotate<T>(dX, n, E.V, ldv, E.dQ, m, n, m, nout, s);
   if (E.minner) {  // x^H op(M) x = 1
     E.mult_m(dX, n, dMX, nout);
@@ -552,17 +543,17 @@ void eigs_run(hs_handle* F, int trans, int64_t n, const HostCsc<T>& Mh, int inne
   A.conj = trans == 2;
   launch_spmm_op<T>(A, dX, n, nullptr, dAX, n, nullptr, 0, nullptr, n, nout, s);
   launch_eigs_resid<T>(dAX, n, has_m ? dMX : dX, n, dmu, dpair, n, nout, E.dpart, E.dnrm, s);
-  GM_HIP(hipMemcpyAsync(nrm.data(), E.dnrm, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s));
-  GM_HIP(hipEventRecord(*e1, s));
-  GM_HIP(hipStreamSynchronize(s));
-  GM_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(nrm.data(), E.dnrm, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipEventRecord(*e1, s));
+  HS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipGetLastError());
   if (const int st = hs_handle_flow_check(F)) throw st;
   float ms = 0.f;
-  GM_HIP(hipEventElapsedTime(&ms, *e0, *e1));
+  HS_HIP(hipEventElapsedTime(&ms, *e0, *e1));
   g_einfo[EI_SECONDS] = ms * 1e-3;
   clk.lap(EP_FINISH);
   // ---- results
-  if (X) GM_HIP(hipMemcpy2D(X, ldx * sizeof(T), dX, n * sizeof(T), n * sizeof(T), nout, where ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+  if (X) HS_HIP(hipMemcpy2D(X, ldx * sizeof(T), dX, n * sizeof(T), n * sizeof(T), nout, where ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
   for (int c = 0; c < nx; ++c) {
     lam[2 * c] = c < nout ? lamv[(size_t)2 * c] : 0.0;
     lam[2 * c + 1] = c < nout ? lamv[(size_t)2 * c + 1] : 0.0;
@@ -578,7 +569,7 @@ int eigs_entry(hs_handle* F, int trans, int64_t n, const HostCsc<T>& M, int inne
                int64_t ldv0, int64_t seed, int where, double* lam, T* X, int64_t ldx, double* resid, double* est, int64_t* nout, int64_t* nconv, void* stream) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = HS_OK;
-  DevBuf buf;  // outlives the try block: after a throw the stream is drained below before the workspace is freed
+  HsDevBuf buf("GMRES workspace");  // outlives the try block: after a throw the stream is drained below before the workspace is freed
   try {
     eigs_run<T>(F, trans, n, M, inner, nev, ncv, block, sigma_re, sigma_im, tol, maxrestart, V0, ldv0, seed, where, lam, X, ldx, resid, est, nout, nconv, stream, buf, &e0, &e1);
   } catch (int code) {

@@ -415,8 +415,8 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
   std::vector<double> hbeta((size_t)gc), htol((size_t)gc);
   std::vector<int> hleft((size_t)gc), hsrc((size_t)gc);
   auto read = [&](const double* d, int cnt) {
-    GM_HIP(hipMemcpyAsync(hd.data(), d, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s));
-    GM_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipMemcpyAsync(hd.data(), d, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
   };
   auto norms = [&](const T* Wb, double* out, int ostride, int nc, const int* mask) {
     hipLaunchKernelGGL(bnorm2_part_kernel<T>, dim3(nblk, nc), dim3(256), 0, s, Wb, ldv, ws.dpart, n, mask);
@@ -428,13 +428,13 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
   };
   // r0 = b - A x0, slots in the order of the columns
   for (int c = 0; c < gc; ++c) hcol[(size_t)c] = g0 + c;
-  GM_HIP(hipMemcpyAsync(S.col, hcol.data(), sizeof(int64_t) * (size_t)gc, hipMemcpyHostToDevice, s));
-  GM_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipMemcpyAsync(S.col, hcol.data(), sizeof(int64_t) * (size_t)gc, hipMemcpyHostToDevice, s));
+  HS_HIP(hipStreamSynchronize(s));
   if (use_x0) {
     residual(gc);
   } else {
-    GM_HIP(hipMemset2DAsync(X + (size_t)g0 * ldx, sizeof(T) * (size_t)ldx, 0, sizeof(T) * (size_t)n, (size_t)gc, s));
-    GM_HIP(hipMemcpy2DAsync(ws.R, sizeof(T) * (size_t)ldv, B + (size_t)g0 * ldb, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)gc, hipMemcpyDeviceToDevice, s));
+    HS_HIP(hipMemset2DAsync(X + (size_t)g0 * ldx, sizeof(T) * (size_t)ldx, 0, sizeof(T) * (size_t)n, (size_t)gc, s));
+    HS_HIP(hipMemcpy2DAsync(ws.R, sizeof(T) * (size_t)ldv, B + (size_t)g0 * ldb, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)gc, hipMemcpyDeviceToDevice, s));
   }
   norms(ws.R, S.beta, 1, gc, nullptr);
   read(S.beta, gc);
@@ -461,7 +461,7 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
     if (next.empty()) break;
     const int nact = (int)next.size();
     if (moved) {
-      GM_HIP(hipMemcpyAsync(ws.src, hsrc.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
+      HS_HIP(hipMemcpyAsync(ws.src, hsrc.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
       hipLaunchKernelGGL(bgather_kernel<T>, dim3(gn, nact), dim3(256), 0, s, (const T*)ws.R, ws.R2, ldv, (const int*)ws.src, n);
       std::swap(ws.R, ws.R2);
     }
@@ -474,11 +474,11 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
       hleft[(size_t)c] = (int)std::min<int64_t>(maxiter - q.it, 1 << 30);
       q.frozen = false;
     }
-    GM_HIP(hipMemcpyAsync(S.col, hcol.data(), sizeof(int64_t) * (size_t)nact, hipMemcpyHostToDevice, s));
-    GM_HIP(hipMemcpyAsync(S.beta, hbeta.data(), sizeof(double) * (size_t)nact, hipMemcpyHostToDevice, s));
-    GM_HIP(hipMemcpyAsync(S.tol, htol.data(), sizeof(double) * (size_t)nact, hipMemcpyHostToDevice, s));
-    GM_HIP(hipMemcpyAsync(S.itleft, hleft.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
-    GM_HIP(hipStreamSynchronize(s));  // the host arrays are reused
+    HS_HIP(hipMemcpyAsync(S.col, hcol.data(), sizeof(int64_t) * (size_t)nact, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(S.beta, hbeta.data(), sizeof(double) * (size_t)nact, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(S.tol, htol.data(), sizeof(double) * (size_t)nact, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(S.itleft, hleft.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
+    HS_HIP(hipStreamSynchronize(s));  // the host arrays are reused
     info[GI_CYCLES] += 1;
     info[GI_MAX_ACTIVE] = std::max(info[GI_MAX_ACTIVE], (double)nact);
     const unsigned gs = (unsigned)((nact + 63) / 64);
@@ -546,7 +546,7 @@ void gmres_group(const Op& A, const Prec& Pr, int64_t n, const T* B, int64_t ldb
       q.conv = q.conv || q.beta <= q.tol;
     }
   }
-  GM_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 
 // G: the widest group (a multiple of the block solve's chunk width) whose workspace fits half of the free memory, HS_GMRES_BLOCK_GROUP overrides
@@ -558,14 +558,12 @@ int64_t group_width(size_t per_col, int64_t nrhs) {
     if (v > 0) return std::min<int64_t>(all, (v + KC - 1) / KC * KC);
   }
   size_t fr = 0, tot = 0;
-  GM_HIP(hipMemGetInfo(&fr, &tot));
+  HS_HIP(hipMemGetInfo(&fr, &tot));
   const int64_t fit = (int64_t)(fr / 2 / per_col);
   if (fit >= all) return all;
-  if (fit < std::min<int64_t>(KC, nrhs)) {
-    hs_set_error(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_gmres_block_* needs %zu bytes for one group of %lld columns, half of the free device memory is %zu bytes",
-                 per_col * (size_t)std::min<int64_t>(KC, nrhs), (long long)std::min<int64_t>(KC, nrhs), fr / 2);
-    throw (int)HS_ERR_NOMEM;
-  }
+  if (fit < std::min<int64_t>(KC, nrhs))
+    HS_FAIL(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_gmres_block_* needs %zu bytes for one group of %lld columns, half of the free device memory is %zu bytes",
+            per_col * (size_t)std::min<int64_t>(KC, nrhs), (long long)std::min<int64_t>(KC, nrhs), fr / 2);
   return std::max<int64_t>(fit / KC * KC, std::min<int64_t>(KC, nrhs));
 }
 
@@ -624,7 +622,7 @@ int gmres_run(MakeOp make_op, const Prec& Pr, Width width, double* info, int64_t
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = HS_OK;
-  DevBuf buf;  // outlives the try block: after a throw the stream is drained below before the workspace is freed
+  HsDevBuf buf("GMRES workspace");  // outlives the try block: after a throw the stream is drained below before the workspace is freed
   try {
     std::fill(info, info + 8, 0.0);
     hipStream_t s = (hipStream_t)stream;
@@ -635,8 +633,8 @@ int gmres_run(MakeOp make_op, const Prec& Pr, Width width, double* info, int64_t
     if (where == 0) {  // the whole block goes up and comes down once
       T* tb = buf.get<T>((size_t)n * nrhs);
       T* tx = buf.get<T>((size_t)n * nrhs);
-      GM_HIP(hipMemcpy2D(tb, sizeof(T) * (size_t)n, B, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
-      if (use_x0) GM_HIP(hipMemcpy2D(tx, sizeof(T) * (size_t)n, X, sizeof(T) * (size_t)ldx, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
+      HS_HIP(hipMemcpy2D(tb, sizeof(T) * (size_t)n, B, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
+      if (use_x0) HS_HIP(hipMemcpy2D(tx, sizeof(T) * (size_t)n, X, sizeof(T) * (size_t)ldx, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
       dB = tb;
       dX = tx;
       dldb = dldx = n;
@@ -679,23 +677,23 @@ int gmres_run(MakeOp make_op, const Prec& Pr, Width width, double* info, int64_t
     S.kused = buf.get<int>(G);
     S.col = buf.get<int64_t>(G);
     info[GI_WORK_BYTES] = (double)(per_col * G - ((size_t)m + 5 - nvec) * blk * sizeof(T));
-    GM_HIP(hipEventCreate(&e0));
-    GM_HIP(hipEventCreate(&e1));
-    GM_HIP(hipEventRecord(e0, s));
+    HS_HIP(hipEventCreate(&e0));
+    HS_HIP(hipEventCreate(&e1));
+    HS_HIP(hipEventRecord(e0, s));
     // a frozen column's basis vectors still travel through the block solve: they must be finite from the first step on
-    GM_HIP(hipMemsetAsync(big, 0, sizeof(T) * nvec * blk, s));
+    HS_HIP(hipMemsetAsync(big, 0, sizeof(T) * nvec * blk, s));
     std::vector<Column> cols((size_t)nrhs);
     for (int64_t g0 = 0; g0 < nrhs; g0 += ws.G) {
       const int gc = (int)std::min<int64_t>(ws.G, nrhs - g0);
       gmres_group<T>(A, Pr, n, dB, dldb, dX, dldx, g0, gc, use_x0, reltol, abstol, maxiter, ws, cols.data() + g0, info, s);
       info[GI_GROUPS] += 1;
     }
-    GM_HIP(hipEventRecord(e1, s));
-    GM_HIP(hipEventSynchronize(e1));
+    HS_HIP(hipEventRecord(e1, s));
+    HS_HIP(hipEventSynchronize(e1));
     float ms = 0.f;
-    GM_HIP(hipEventElapsedTime(&ms, e0, e1));
+    HS_HIP(hipEventElapsedTime(&ms, e0, e1));
     info[GI_SECONDS] = ms * 1e-3;
-    if (where == 0) GM_HIP(hipMemcpy2D(X, sizeof(T) * (size_t)ldx, dX, sizeof(T) * (size_t)n, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyDeviceToHost));
+    if (where == 0) HS_HIP(hipMemcpy2D(X, sizeof(T) * (size_t)ldx, dX, sizeof(T) * (size_t)n, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyDeviceToHost));
     for (int64_t c = 0; c < nrhs; ++c) {
       const Column& q = cols[(size_t)c];
       iters[c] = q.it;
@@ -734,7 +732,7 @@ int gmres_one_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* b, T* x, i
 // the CSR upload of the caller's CSC arrays as the operator
 template <class T>
 auto csr_op_of(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz) {
-  return [=](DevBuf& buf, hipStream_t) {
+  return [=](HsDevBuf& buf, hipStream_t) {
     int64_t* d_rp;
     int32_t* d_ci;
     T* d_v;
@@ -772,7 +770,7 @@ int gmres_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, con
     if (const int st = PrecOp<T>{F, trans}((T*)nullptr, (const T*)nullptr, n, n, 0, nullptr)) return st;
   if (own)
     if (const int st = hs_gmres_own_check(F, "hs_gmres_t_*", 0)) return st;
-  auto make_op = [&](DevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
+  auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
   return gmres_one_run<T>(make_op, PrecOp<T>{F, trans}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
@@ -836,7 +834,7 @@ int gmres_block_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colpt
   }
   if (own)
     if (const int st = hs_gmres_own_check(F, "hs_gmres_block_t_*", 0)) return st;
-  auto make_op = [&](DevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
+  auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
   return gmres_block_run<T>(make_op, PrecBlockOp<T>{F, trans}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
@@ -871,7 +869,7 @@ int gmres_block_mod_entry(hs_mod* M, int trans, int64_t n, const int64_t* colptr
   if (trans == 0)
     return gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
                               stream);
-  auto make_op = [&](DevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, false, n, colptr, rowval, nz, s)}; };
+  auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, false, n, colptr, rowval, nz, s)}; };
   return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
@@ -888,7 +886,7 @@ int spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* 
       hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
       return HS_ERR_DEVICE;
     }
-    DevBuf buf;
+    HsDevBuf buf("GMRES workspace");
     int64_t* d_rp;
     int32_t* d_ci;
     T* d_v;
@@ -896,12 +894,12 @@ int spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* 
     T* dX = buf.get<T>((size_t)ldx * nrhs);
     T* dY = buf.get<T>((size_t)ldy * nrhs);
     T* dB = B ? buf.get<T>((size_t)ldb * nrhs) : nullptr;
-    GM_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
-    GM_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
-    if (B) GM_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
+    if (B) HS_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
     launch_spmm<T>(d_rp, d_ci, d_v, dX, ldx, (const int64_t*)nullptr, dY, ldy, dB, ldb, (const int64_t*)nullptr, n, (int)nrhs, (hipStream_t)0);
-    GM_HIP(hipDeviceSynchronize());
-    GM_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
+    HS_HIP(hipDeviceSynchronize());
+    HS_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
     return HS_OK;
   } catch (int code) {
     return code;
@@ -925,7 +923,7 @@ int spmm_op_hook(int trans, int64_t n, const int64_t* colptr, const int64_t* row
       hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
       return HS_ERR_DEVICE;
     }
-    DevBuf buf;
+    HsDevBuf buf("GMRES workspace");
     int64_t* d_p;
     int32_t* d_i;
     T* d_v;
@@ -941,12 +939,12 @@ int spmm_op_hook(int trans, int64_t n, const int64_t* colptr, const int64_t* row
     T* dX = buf.get<T>((size_t)ldx * nrhs);
     T* dY = buf.get<T>((size_t)ldy * nrhs);
     T* dB = B ? buf.get<T>((size_t)ldb * nrhs) : nullptr;
-    GM_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
-    GM_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
-    if (B) GM_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
+    if (B) HS_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
     launch_spmm_op<T>(A, dX, ldx, (const int64_t*)nullptr, dY, ldy, dB, ldb, (const int64_t*)nullptr, n, (int)nrhs, (hipStream_t)0);
-    GM_HIP(hipDeviceSynchronize());
-    GM_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
+    HS_HIP(hipDeviceSynchronize());
+    HS_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
     return HS_OK;
   } catch (int code) {
     return code;

@@ -1,5 +1,5 @@
 // hs_gmres_common.h -- what the GMRES driver (hs_gmres_block.hip: hs_gmres_* and hs_gmres_block_*) shares with the other Krylov code
-// (hs_eigs.hip): the restart limit, the scalar helpers of the kernels, the device-buffer holder, the CSC -> CSR upload, and what the
+// (hs_eigs.hip): the restart limit, the scalar helpers of the kernels, the CSC -> CSR upload, and what the
 // hs_gmres_t_* / hs_gmres_block_t_* calls add: the product with op(A) over "entry ranges as rows", the 0-based CSC upload and the checks of
 // their arguments.  Everything has internal linkage.
 #pragma once
@@ -10,6 +10,7 @@
 
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
+#include "hs_host.h"
 #include "hs_gmres_op.h"
 
 #define GM_MAXK 64  // restart length limit (Krylov vectors held: restart + 1)
@@ -38,58 +39,22 @@ __device__ inline cplx scale_<cplx>(cplx a, double s) { return {a.re * s, a.im *
 __device__ inline double absT(double a) { return fabs(a); }
 __device__ inline double absT(cplx a) { return sqrt(a.re * a.re + a.im * a.im); }
 
-struct DevBuf {
-  std::vector<void*> p;
-  ~DevBuf() {
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-  }
-  template <class U>
-  U* get(size_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(count * sizeof(U), 256)) != hipSuccess) {
-      hs_set_error(HS_ERR_NOMEM, 0, "hipMalloc of %zu bytes failed (GMRES workspace)", count * sizeof(U));
-      throw (int)HS_ERR_NOMEM;
-    }
-    p.push_back(q);
-    return (U*)q;
-  }
-};
-
-#define GM_HIP(call)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (call);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      hs_set_error(HS_ERR_DEVICE, 0, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-      throw (int)HS_ERR_DEVICE;                                                                   \
-    }                                                                                             \
-  } while (0)
-
 // the device forms of A hold row / column indices in 32 bits
 inline void gm_check_index_width(int64_t n) {
-  if (n > (int64_t)INT32_MAX) {
-    hs_set_error(HS_ERR_ARGUMENT, n, "ArgumentError: n = %lld exceeds the 32-bit indices of the device matrix (limit %d)", (long long)n, INT32_MAX);
-    throw (int)HS_ERR_ARGUMENT;
-  }
+  if (n > (int64_t)INT32_MAX) HS_FAIL(HS_ERR_ARGUMENT, n, "ArgumentError: n = %lld exceeds the 32-bit indices of the device matrix (limit %d)", (long long)n, INT32_MAX);
 }
 
 // CSR (0-based, device) of a host CSC matrix given with 1-based Julia fields
 template <class T>
-void upload_csr(DevBuf& buf, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, int64_t** d_rp, int32_t** d_ci, T** d_v) {
+void upload_csr(HsDevBuf& buf, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, int64_t** d_rp, int32_t** d_ci, T** d_v) {
   gm_check_index_width(n);
-  if (colptr[0] != 1) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: colptr must be 1-based (SparseMatrixCSC)");
-    throw (int)HS_ERR_ARGUMENT;
-  }
+  if (colptr[0] != 1) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: colptr must be 1-based (SparseMatrixCSC)");
   const int64_t nnz = colptr[n] - 1;
   std::vector<int64_t> rp((size_t)n + 1, 0);
   std::vector<int32_t> ci((size_t)nnz);
   std::vector<T> v((size_t)nnz);
   for (int64_t e = 0; e < nnz; ++e) {
-    if (rowval[e] < 1 || rowval[e] > n) {
-      hs_set_error(HS_ERR_DIMENSION, e, "BoundsError: rowval[%lld] = %lld outside 1:%lld", (long long)e + 1, (long long)rowval[e], (long long)n);
-      throw (int)HS_ERR_DIMENSION;
-    }
+    if (rowval[e] < 1 || rowval[e] > n) HS_FAIL(HS_ERR_DIMENSION, e, "BoundsError: rowval[%lld] = %lld outside 1:%lld", (long long)e + 1, (long long)rowval[e], (long long)n);
     rp[(size_t)rowval[e]]++;
   }
   for (int64_t r = 0; r < n; ++r) rp[(size_t)r + 1] += rp[(size_t)r];
@@ -103,9 +68,9 @@ void upload_csr(DevBuf& buf, int64_t n, const int64_t* colptr, const int64_t* ro
   *d_rp = buf.get<int64_t>((size_t)n + 1);
   *d_ci = buf.get<int32_t>((size_t)nnz);
   *d_v = buf.get<T>((size_t)nnz);
-  GM_HIP(hipMemcpy(*d_rp, rp.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(*d_ci, ci.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(*d_v, v.data(), sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(*d_rp, rp.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(*d_ci, ci.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(*d_v, v.data(), sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice));
 }
 
 // ---- op(A) over "entry ranges as rows" (hs_gmres_t_*, hs_gmres_block_t_*) -------------------------------------------------------------
@@ -172,35 +137,26 @@ void launch_spmm_op(const RowsOf<T>& A, const T* X, int64_t ldx, const int64_t* 
 // The CSC arrays of a host matrix (1-based Julia fields) on the device, 0-based with 32-bit row indices -- the form the handle keeps its
 // own A in.  The host rebases the indices and nothing else: no transposition, no pass that reorders the values.
 template <class T>
-void upload_csc(DevBuf& buf, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, int64_t** d_cp, int32_t** d_ri, T** d_v) {
+void upload_csc(HsDevBuf& buf, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, int64_t** d_cp, int32_t** d_ri, T** d_v) {
   gm_check_index_width(n);
-  if (colptr[0] != 1) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: colptr must be 1-based (SparseMatrixCSC)");
-    throw (int)HS_ERR_ARGUMENT;
-  }
+  if (colptr[0] != 1) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: colptr must be 1-based (SparseMatrixCSC)");
   const int64_t nnz = colptr[n] - 1;
   std::vector<int64_t> cp((size_t)n + 1);
   std::vector<int32_t> ri((size_t)nnz);
   for (int64_t c = 0; c <= n; ++c) {
     cp[(size_t)c] = colptr[c] - 1;
-    if (cp[(size_t)c] < (c ? cp[(size_t)c - 1] : 0) || cp[(size_t)c] > nnz) {
-      hs_set_error(HS_ERR_ARGUMENT, c, "ArgumentError: colptr[%lld] = %lld is not monotone within 1:%lld", (long long)c + 1, (long long)colptr[c], (long long)nnz + 1);
-      throw (int)HS_ERR_ARGUMENT;
-    }
+    if (cp[(size_t)c] < (c ? cp[(size_t)c - 1] : 0) || cp[(size_t)c] > nnz) HS_FAIL(HS_ERR_ARGUMENT, c, "ArgumentError: colptr[%lld] = %lld is not monotone within 1:%lld", (long long)c + 1, (long long)colptr[c], (long long)nnz + 1);
   }
   for (int64_t e = 0; e < nnz; ++e) {
-    if (rowval[e] < 1 || rowval[e] > n) {
-      hs_set_error(HS_ERR_DIMENSION, e, "BoundsError: rowval[%lld] = %lld outside 1:%lld", (long long)e + 1, (long long)rowval[e], (long long)n);
-      throw (int)HS_ERR_DIMENSION;
-    }
+    if (rowval[e] < 1 || rowval[e] > n) HS_FAIL(HS_ERR_DIMENSION, e, "BoundsError: rowval[%lld] = %lld outside 1:%lld", (long long)e + 1, (long long)rowval[e], (long long)n);
     ri[(size_t)e] = (int32_t)(rowval[e] - 1);
   }
   *d_cp = buf.get<int64_t>((size_t)n + 1);
   *d_ri = buf.get<int32_t>((size_t)nnz);
   *d_v = buf.get<T>((size_t)nnz);
-  GM_HIP(hipMemcpy(*d_cp, cp.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(*d_ri, ri.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(*d_v, nz, sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(*d_cp, cp.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(*d_ri, ri.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(*d_v, nz, sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice));
 }
 
 // What hs_gmres_t_* and hs_gmres_block_t_* check first, with no device work: trans, and how A is passed (all three arrays, or none of them
@@ -224,7 +180,7 @@ inline int gm_check_op_args(const char* fn, hs_handle* F, int trans, const void*
 }
 // the rows of op(A): the handle's own A (no host pass, no upload), or an upload of the caller's CSC arrays (trans != 0 only)
 template <class T>
-RowsOf<T> gm_rows_of_op(DevBuf& buf, hs_handle* F, int trans, bool own, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, hipStream_t s) {
+RowsOf<T> gm_rows_of_op(HsDevBuf& buf, hs_handle* F, int trans, bool own, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, hipStream_t s) {
   RowsOf<T> A;
   A.conj = trans == 2;
   if (own) {

@@ -33,7 +33,7 @@ int hs_gmres_own_check(hs_handle* F, const char* fn, int ranks_only) {
 }
 
 int hs_gmres_own_rows(hs_handle* F, int trans, hipStream_t s, HsGmresRows* out) {
-  CE_GUARD(HsHandleView v; hs_handle_view(F, &v); if (trans == 0) {
+  HS_GUARD(HsHandleView v; hs_handle_view(F, &v); if (trans == 0) {
     hs_ce::CsrMap* m = v.is_complex ? hs_ce::csr_of<cplx>(v, s) : hs_ce::csr_of<double>(v, s);
     out->ptr = m->rowptr;
     out->idx = m->colind;

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/hs_hss.h"
+#include "hs_host.h"
 #include "hs_lowrank.h"
 #include "hs_sched.h"
 #include "hs_ulv_t.h"
@@ -341,15 +342,6 @@ struct Pool {
   }
 };
 
-#define HSS_HIP(call)                                                                             \
-  do {                                                                                            \
-    hipError_t e__ = (call);                                                                      \
-    if (e__ != hipSuccess) {                                                                      \
-      hs_set_error(HS_ERR_DEVICE, 0, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-      throw (int)HS_ERR_DEVICE;                                                                   \
-    }                                                                                             \
-  } while (0)
-
 inline int ev(int x) { return std::max(2, (x + 1) / 2 * 2); }
 
 template <class T>
@@ -406,13 +398,13 @@ J* upload(Pool& pool, const std::vector<J>& v, hipStream_t s) {
   const size_t bytes = sizeof(J) * v.size();
   void* h = pool.get_pinned(bytes);
   memcpy(h, v.data(), bytes);
-  HSS_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
   return d;
 }
 template <class J>
 J* upload(Pool& pool, const std::vector<J>& v) {
   J* d = pool.get<J>(std::max<size_t>(v.size(), 1));
-  if (!v.empty()) HSS_HIP(hipMemcpy(d, v.data(), sizeof(J) * v.size(), hipMemcpyHostToDevice));
+  if (!v.empty()) HS_HIP(hipMemcpy(d, v.data(), sizeof(J) * v.size(), hipMemcpyHostToDevice));
   return d;
 }
 
@@ -1102,9 +1094,9 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
     CholJob<T>* dcj = upload(tmp, cj, s);
     launch_chol<T>(dcj, (unsigned)cj.size(), s);
     // how many candidates each job accepted
-    HSS_HIP(hipMemcpyAsync(hacc.data(), dnacc, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, s));
-    HSS_HIP(hipMemcpyAsync(hmax.data(), dmaxall, sizeof(double) * 2 * (size_t)nj, hipMemcpyDeviceToHost, s));
-    HSS_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipMemcpyAsync(hacc.data(), dnacc, sizeof(int) * (size_t)nj, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipMemcpyAsync(hmax.data(), dmaxall, sizeof(double) * 2 * (size_t)nj, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
     // Q[done : done+b', :] = LinvP * W, its conjugate transpose, and the rows of L against the earlier blocks (in accepted order)
     each([&](int a, QrJob<T>& J, St& S, int b) {
       const int na = hacc[a];
@@ -1133,7 +1125,7 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
       });
       run_norms();
     }
-    HSS_HIP(hipStreamSynchronize(s));  // lperm / nacc are rewritten by the next window
+    HS_HIP(hipStreamSynchronize(s));  // lperm / nacc are rewritten by the next window
     for (int a = 0; a < nj; ++a) {
       St& S = st[a];
       if (!S.active) continue;
@@ -1194,9 +1186,9 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
     J.ldt = ev(J.m - J.r);
     J.Tm = out_pool.get<T>((size_t)J.ldt * std::max(J.r, 1));
     maxblocks = std::max(maxblocks, (int)S.blocks.size());
-    if (S.top) HSS_HIP(hipMemcpyAsync(&J.top, S.top, sizeof(double), hipMemcpyDeviceToHost, s));
+    if (S.top) HS_HIP(hipMemcpyAsync(&J.top, S.top, sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
   for (int a = 0; a < nj; ++a)
     if (jobs[a].r == 0) jobs[a].top = std::max(jobs[a].top, 0.0);
   static const bool qdebug = getenv("HS_QR_DEBUG") != nullptr;  // diagnostics: the accepted d_j of the job of largest rank, window by window
@@ -1206,7 +1198,7 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
       if (jobs[a].r > jobs[am].r) am = a;
     const QrJob<T>& J = jobs[am];
     std::vector<double> hd((size_t)std::max(J.r, 1));
-    if (J.r > 0) HSS_HIP(hipMemcpy(hd.data(), st[am].d, sizeof(double) * (size_t)J.r, hipMemcpyDeviceToHost));
+    if (J.r > 0) HS_HIP(hipMemcpy(hd.data(), st[am].d, sizeof(double) * (size_t)J.r, hipMemcpyDeviceToHost));
     fprintf(stderr, "[hs qr debug] %d jobs; job %d: m %d q %d rmax %d -> r %d, top %.3e, tau_abs %.3e tau_rel %.3e floor %.3e; windows (offset:width d_first..d_last):", nj, am, J.m, J.q, J.rmax, J.r, J.top,
             atol * J.atol_scale, rtol * J.top, J.floor_abs);
     for (auto& b : st[am].blocks) fprintf(stderr, " %d:%d %.2e..%.2e", b.first, b.second, hd[b.first], hd[b.first + b.second - 1]);
@@ -1226,7 +1218,7 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
     }
     YR[a] = tmp.get<T>((size_t)ev(nR) * J.q);
     rows.push_back(RowJob<T>{J.M, J.ldm, YR[a], ev(nR), J.p + J.r, nR, J.q, ROW_GATHER});
-    HSS_HIP(hipMemsetAsync(J.Tm, 0, sizeof(T) * (size_t)J.ldt * J.r, s));
+    HS_HIP(hipMemsetAsync(J.Tm, 0, sizeof(T) * (size_t)J.ldt * J.r, s));
     g.push_back(GemmProb<T>{YR[a], S.Qh, J.Tm, nR, J.r, J.q, ev(nR), S.ldqh, J.ldt});
   }
   run_rows(tmp, rows, s);
@@ -1248,7 +1240,7 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
     run_gemms(tmp, g2, 0, s);
     run_subs(tmp, back, s);
   }
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
   if (qtime) {
     auto tq2 = std::chrono::steady_clock::now();
     int mr = 0, mm = 0, mq = 0;
@@ -1394,7 +1386,7 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
     x.D = H.keep.template get<T>((size_t)x.ldd * n);
     subs.push_back(SubJob<T>{cb[0].A, cb[0].lda, cb[0].perm, cb[0].perm, 0, 0, n, n, x.D, x.ldd, 0, cb[0].hperm, cb[0].hperm});
     gather_A();
-    HSS_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipStreamSynchronize(s));
     return true;
   }
   // test matrices OP = [Omega | Psi] (n x 2k) and samples Y = [B*Omega | B^T*Psi] of B = A[perm, perm]:
@@ -1467,8 +1459,8 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
 
   sample_scale(Y, k2);
   std::vector<double> noise(F, 0.0);
-  HSS_HIP(hipMemcpyAsync(noise.data(), dynorm, sizeof(double) * (size_t)F, hipMemcpyDeviceToHost, s));
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipMemcpyAsync(noise.data(), dynorm, sizeof(double) * (size_t)F, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
   double noise_max = 0.0;
   for (double& x : noise) {
     x *= noise_rel();
@@ -1624,7 +1616,7 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
               nj, mm, mr, (double)sr / nj, mlu, full, enough ? "" : "  -> more samples");
     }
     if (!enough) {
-      HSS_HIP(hipStreamSynchronize(s));
+      HS_HIP(hipStreamSynchronize(s));
       free_lr();
       return false;
     }
@@ -1636,7 +1628,7 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
         HNode<T>& x = nd[i];
         const int m = x.m, r = x.r, nR = m - r;
         x.p = H.keep.template get<int>(m);
-        HSS_HIP(hipMemcpyAsync(x.p, porder[a], sizeof(int) * m, hipMemcpyDeviceToDevice, s));
+        HS_HIP(hipMemcpyAsync(x.p, porder[a], sizeof(int) * m, hipMemcpyDeviceToDevice, s));
         x.sk = H.keep.template get<int>(r);
         x.ldt = ev(nR);
         x.ldtt = ev(r);
@@ -1648,7 +1640,7 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
           if (!qr_on && lr[a].r >= 1)
             subs.push_back(SubJob<T>{lr[a].Lp, lr[a].ldp, nullptr, nullptr, r, 0, nR, r, x.Tm, x.ldt, 0});  // T <- L21
           else  // the sample block is zero (the node does not couple to the rest at all): one nominal skeleton position, T = 0 --
-            HSS_HIP(hipMemsetAsync(x.Tm, 0, sizeof(T) * (size_t)x.ldt * r, s));  // the L\U of a zero sketch holds nothing usable
+            HS_HIP(hipMemsetAsync(x.Tm, 0, sizeof(T) * (size_t)x.ldt * r, s));  // the L\U of a zero sketch holds nothing usable
         }
         {
           const CBlock<T>& B = cb[nblk[i]];
@@ -1701,14 +1693,14 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
         run_subs(tmp, subs, s);
       }
       if (verbose) {  // growth of the interpolation matrices (an LU-based ID bounds |L21| <= 1, not |L21 * L11^-1|)
-        HSS_HIP(hipStreamSynchronize(s));
+        HS_HIP(hipStreamSynchronize(s));
         double tmax = 0.0;
         for (int i : L) {
           const HNode<T>& x = nd[i];
           const int nR = x.m - x.r;
           if (nR <= 0 || x.r <= 0) continue;
           std::vector<T> ht((size_t)x.ldt * x.r);
-          HSS_HIP(hipMemcpy(ht.data(), x.Tm, sizeof(T) * ht.size(), hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy(ht.data(), x.Tm, sizeof(T) * ht.size(), hipMemcpyDeviceToHost));
           for (int c = 0; c < x.r; ++c)
             for (int rr = 0; rr < nR; ++rr) tmax = std::max(tmax, Scal<T>::abs1(ht[(size_t)rr + (size_t)c * x.ldt]));
         }
@@ -1719,9 +1711,9 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
       if (bop) {  // the matrix-free operator routes entry requests on the host: it needs the skeleton indices there
         for (int i : L) {
           nd[i].hsk.resize((size_t)nd[i].r);
-          HSS_HIP(hipMemcpyAsync(nd[i].hsk.data(), nd[i].sk, sizeof(int) * (size_t)nd[i].r, hipMemcpyDeviceToHost, s));
+          HS_HIP(hipMemcpyAsync(nd[i].hsk.data(), nd[i].sk, sizeof(int) * (size_t)nd[i].r, hipMemcpyDeviceToHost, s));
         }
-        HSS_HIP(hipStreamSynchronize(s));
+        HS_HIP(hipStreamSynchronize(s));
       }
       // ---- d. hand the skeleton rows of the samples and the compressed test matrices to the parents ------------------------
       if (lv > 1) {
@@ -1750,14 +1742,14 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
             rows.push_back(RowJob<T>{Ol[i], ldl[i], GR[i], ev(nR), x.p + r, nR, k2, ROW_GATHER_NEG});
             gemms.push_back(GemmProb<T>{x.Tt, GR[i], Ol[par] + off, r, k2, nR, x.ldtt, ev(nR), ldl[par]});  // += T^T * (rows p_R)
           }
-          HSS_HIP(hipMemcpyAsync(Jidx[par] + off, x.sk, sizeof(int) * r, hipMemcpyDeviceToDevice, s));
+          HS_HIP(hipMemcpyAsync(Jidx[par] + off, x.sk, sizeof(int) * r, hipMemcpyDeviceToDevice, s));
         }
         run_rows(tmp, rows, s);
         run_gemms(tmp, gemms, 1, s);
       } else {
         for (int i : L) nd[i].off_in_parent = nd[nd[i].parent].left == i ? 0 : nd[nd[nd[i].parent].left].r;
       }
-      HSS_HIP(hipStreamSynchronize(s));
+      HS_HIP(hipStreamSynchronize(s));
     } catch (...) {
       (void)hipStreamSynchronize(s);
       free_lr();
@@ -1779,7 +1771,7 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
     subs.push_back(SubJob<T>{cb[b].A, cb[b].lda, r.sk, l.sk, 0, 0, r.r, l.r, x.B21, x.ld21, 0, r.hsk.data(), l.hsk.data(), b});
   }
   gather_A();
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
   return true;
 }
 
@@ -1804,7 +1796,7 @@ void hss_mul(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans =
   hss_mul_p(H, Xp, ld, Yp, ld, q, trans);
   rows.push_back(RowJob<T>{Yp, ld, Y, ldy, H.perm, H.n, q, ROW_SCATTER});
   run_rows(tmp, rows, H.s);
-  HSS_HIP(hipStreamSynchronize(H.s));
+  HS_HIP(hipStreamSynchronize(H.s));
 }
 template <class T>
 void hss_mul_p(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans) {
@@ -1833,10 +1825,10 @@ void hss_mul_p(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans
     run_subs(tmp, tj, s);
   }
   if (nd[0].left < 0) {
-    HSS_HIP(hipMemset2DAsync(Y, sizeof(T) * ldy, 0, sizeof(T) * H.n, q, s));
+    HS_HIP(hipMemset2DAsync(Y, sizeof(T) * ldy, 0, sizeof(T) * H.n, q, s));
     gemms.push_back(GemmProb<T>{trans ? nd[0].DTt : nd[0].D, X, Y, H.n, q, H.n, nd[0].ldd, ldx, ldy});
     run_gemms(tmp, gemms, 0, s);
-    HSS_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipStreamSynchronize(s));
     return;
   }
   // upward pass: XT[i] = [x~_left; x~_right] of every inner node
@@ -1851,7 +1843,7 @@ void hss_mul_p(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans
       if (i != 0 && nd[i].m - nd[i].r > 0) zel += (size_t)ev(nd[i].m - nd[i].r) * q;
     }
     T* z = tmp.get<T>(zel + 2);
-    HSS_HIP(hipMemsetAsync(z, 0, sizeof(T) * zel, s));
+    HS_HIP(hipMemsetAsync(z, 0, sizeof(T) * zel, s));
     for (int i = 0; i < N; ++i) {
       if (nd[i].left >= 0) {
         ldx_[i] = ev(nd[i].m);
@@ -1864,7 +1856,7 @@ void hss_mul_p(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans
         z += (size_t)ev(nd[i].m - nd[i].r) * q;
       }
     }
-    HSS_HIP(hipMemset2DAsync(Y, sizeof(T) * ldy, 0, sizeof(T) * H.n, q, s));  // the leaves' output blocks tile Y
+    HS_HIP(hipMemset2DAsync(Y, sizeof(T) * ldy, 0, sizeof(T) * H.n, q, s));  // the leaves' output blocks tile Y
   }
   for (int lv = H.nlev - 1; lv >= 1; --lv) {
     for (int i : H.lev[lv]) {
@@ -1920,7 +1912,7 @@ void hss_mul_p(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans
     run_gemms(tmp, gemms, 0, s);
     run_rows(tmp, adds, s);
   }
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 
 #include "hs_hss_op.h"
@@ -2004,8 +1996,8 @@ static void hss_bases_impl(HssT<T>& H, Pool& tmp, int node, T* out, int ldo, std
       if (x.left < 0) {
         if (x.hinvp.empty()) {
           std::vector<int> hp(x.m);
-          HSS_HIP(hipMemcpyAsync(hp.data(), x.p, sizeof(int) * x.m, hipMemcpyDeviceToHost, s));
-          HSS_HIP(hipStreamSynchronize(s));
+          HS_HIP(hipMemcpyAsync(hp.data(), x.p, sizeof(int) * x.m, hipMemcpyDeviceToHost, s));
+          HS_HIP(hipStreamSynchronize(s));
           x.hinvp.assign(x.m, 0);
           for (int a = 0; a < x.m; ++a) x.hinvp[hp[a]] = a;
         }
@@ -2052,7 +2044,7 @@ void hss_basis(HssT<T>& H, int node, T* out, int ldo) {
   std::vector<T*> E;
   std::vector<int> lde;
   hss_bases_impl<T>(H, tmp, node, out, ldo, E, lde);
-  HSS_HIP(hipStreamSynchronize(H.s));
+  HS_HIP(hipStreamSynchronize(H.s));
 }
 
 // `Matrix(H)` / `full(H)` of HssMatrices.jl: out (n x n, device) = the matrix H represents, in H's own index order (for a compressed matrix
@@ -2065,13 +2057,13 @@ void hss_expand(HssT<T>& H, T* out, int ldo) {
   auto& nd = H.nd;
   const int N = (int)nd.size();
   Pool tmp(global_cache());
-  HSS_HIP(hipMemset2DAsync(out, sizeof(T) * ldo, 0, sizeof(T) * H.n, H.n, s));
+  HS_HIP(hipMemset2DAsync(out, sizeof(T) * ldo, 0, sizeof(T) * H.n, H.n, s));
   std::vector<SubJob<T>> copies, tr;
   std::vector<GemmProb<T>> g1, g2;
   if (nd[0].left < 0) {
     copies.push_back(SubJob<T>{nd[0].D, nd[0].ldd, nullptr, nullptr, 0, 0, H.n, H.n, out, ldo, 0});
     run_subs(tmp, copies, s);
-    HSS_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipStreamSynchronize(s));
     return;
   }
   std::vector<T*> E;
@@ -2104,7 +2096,7 @@ void hss_expand(HssT<T>& H, T* out, int ldo) {
   run_subs(tmp, copies, s);
   run_gemms(tmp, g1, 0, s);
   run_gemms(tmp, g2, 0, s);
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2125,7 +2117,7 @@ void alloc_front(Pool& pool, NodeDesc<T>& d, int ni, int nb, int node, hipStream
   int* ints = pool.get<int>((size_t)2 * ni + 2 * ncand + HS_PB + 8);
   // (on the caller's stream: a synchronous memset runs on the null stream, which waits for -- and holds up -- every blocking stream of the process,
   // i.e. the other fronts that are being compressed on their own host threads)
-  HSS_HIP(hipMemsetAsync(ints, 0, sizeof(int) * ((size_t)2 * ni + 2 * ncand + HS_PB + 8), s));
+  HS_HIP(hipMemsetAsync(ints, 0, sizeof(int) * ((size_t)2 * ni + 2 * ncand + HS_PB + 8), s));
   d.ipiv = ints;
   d.rperm = d.ipiv + ni;
   d.cand0 = d.rperm + ni;
@@ -2225,14 +2217,14 @@ void hss_factor(HssT<T>& H) {
     run_subs(tmp, subs, s);
     finish_root(M[0], ldm[0], nd[0].m);
   }
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
   // exactly singular pivots (the reference's `\` would throw SingularException)
   std::vector<const NodeDesc<T>*> all{&H.rootfd};
   for (auto& x : nd)
     if (x.has_front) all.push_back(&x.fd);
   std::vector<int> infos(all.size(), 0);
-  for (size_t a = 0; a < all.size(); ++a) HSS_HIP(hipMemcpyAsync(&infos[a], all[a]->info, sizeof(int), hipMemcpyDeviceToHost, s));
-  HSS_HIP(hipStreamSynchronize(s));
+  for (size_t a = 0; a < all.size(); ++a) HS_HIP(hipMemcpyAsync(&infos[a], all[a]->info, sizeof(int), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
   for (size_t a = 0; a < all.size(); ++a)
     if (infos[a] != 0) {
       hs_set_error(HS_ERR_SINGULAR, all[a]->node, "SingularException: HSS node %d hit an exactly zero pivot", all[a]->node);
@@ -2289,7 +2281,7 @@ void hss_ldiv(HssT<T>& H, T* B, int ldb, int q) {
   hss_ldiv_p(H, Bp, ld, q);
   rows.push_back(RowJob<T>{Bp, ld, B, ldb, H.perm, H.n, q, ROW_SCATTER});
   run_rows(tmp, rows, H.s);
-  HSS_HIP(hipStreamSynchronize(H.s));
+  HS_HIP(hipStreamSynchronize(H.s));
 }
 template <class T>
 void hss_ldiv_p(HssT<T>& H, T* B, int ldb, int q) {
@@ -2303,7 +2295,7 @@ void hss_ldiv_p(HssT<T>& H, T* B, int ldb, int q) {
   if (nd[0].left < 0) {
     descs.push_back(rhs_desc(H.rootfd, B, ldb, q));
     tri_solve_batch(tmp, descs, q, true, true, s);
-    HSS_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipStreamSynchronize(s));
     return;
   }
   std::vector<T*> BH(N, nullptr), YR(N, nullptr);
@@ -2364,7 +2356,7 @@ void hss_ldiv_p(HssT<T>& H, T* B, int ldb, int q) {
     run_gemms(tmp, g2, 1, s);
     run_rows(tmp, rows, s);
   }
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 
 // ---- H^-T B / H^-H B from the same stored factors (hs_hss_ldiv_t; DESIGN.md, "transposed ULV solves") ----------------------------------
@@ -2449,7 +2441,7 @@ void hss_ldiv_t_p(HssT<T>& H, T* B, int ldb, int q, int cj) {
   };
   if (nd[0].left < 0) {
     root(B, ldb);
-    HSS_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipStreamSynchronize(s));
     return;
   }
   std::vector<T*> BH(N, nullptr), YR(N, nullptr), ZR(N, nullptr);
@@ -2514,7 +2506,7 @@ void hss_ldiv_t_p(HssT<T>& H, T* B, int ldb, int q, int cj) {
     run_ulv_t(tmp, j2, s);
     run_rows(tmp, rows, s);
   }
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 template <class T>
 void hss_ldiv_t(HssT<T>& H, T* B, int ldb, int q, int cj) {
@@ -2531,7 +2523,7 @@ void hss_ldiv_t(HssT<T>& H, T* B, int ldb, int q, int cj) {
   hss_ldiv_t_p(H, Bp, ld, q, cj);
   rows.push_back(RowJob<T>{Bp, ld, B, ldb, H.perm, H.n, q, ROW_SCATTER});
   run_rows(tmp, rows, H.s);
-  HSS_HIP(hipStreamSynchronize(H.s));
+  HS_HIP(hipStreamSynchronize(H.s));
 }
 
 struct LruArgs {  // host-side description of the optional update  - C*M*Z  (pointers in the memory space `where` names)
@@ -2567,7 +2559,7 @@ HssT<T>* compress_impl(int64_t n, const T* A, int64_t lda, int where, const hs_h
   if (stream) {
     H->s = (hipStream_t)stream;
   } else {
-    HSS_HIP(hipStreamCreate(&H->s));
+    HS_HIP(hipStreamCreate(&H->s));
     H->own_stream = true;
   }
   if (perm) {  // must be a permutation of 0..n-1
@@ -2585,8 +2577,8 @@ HssT<T>* compress_impl(int64_t n, const T* A, int64_t lda, int where, const hs_h
     for (int64_t i = 0; i < n; ++i) H->hinvperm[(size_t)hp[(size_t)i]] = (int)i;
     H->hperm = hp;
     H->perm = H->permpool.template get<int>((size_t)n);
-    HSS_HIP(hipMemcpyAsync(H->perm, hp.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, H->s));
-    HSS_HIP(hipStreamSynchronize(H->s));
+    HS_HIP(hipMemcpyAsync(H->perm, hp.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, H->s));
+    HS_HIP(hipStreamSynchronize(H->s));
   }
   Pool in(global_cache());
   const T* dA = A;
@@ -2594,7 +2586,7 @@ HssT<T>* compress_impl(int64_t n, const T* A, int64_t lda, int where, const hs_h
   if (where == 0 && !bop) {
     ld = ev((int)n);
     T* d = in.get<T>((size_t)ld * n);
-    HSS_HIP(hipMemcpy2D(d, sizeof(T) * ld, A, sizeof(T) * lda, sizeof(T) * n, n, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy2D(d, sizeof(T) * ld, A, sizeof(T) * lda, sizeof(T) * n, n, hipMemcpyHostToDevice));
     dA = d;
   }
   Lru<T> lru;
@@ -2610,9 +2602,9 @@ HssT<T>* compress_impl(int64_t n, const T* A, int64_t lda, int where, const hs_h
       T* dC = in.get<T>((size_t)ev((int)n) * la->r1);
       T* dM = in.get<T>((size_t)ev(lru.r1) * la->r2);
       T* dZ = in.get<T>((size_t)ev(lru.r2) * n);
-      HSS_HIP(hipMemcpy2D(dC, sizeof(T) * ev((int)n), la->C, sizeof(T) * la->ldc, sizeof(T) * n, la->r1, hipMemcpyHostToDevice));
-      HSS_HIP(hipMemcpy2D(dM, sizeof(T) * ev(lru.r1), la->M, sizeof(T) * la->ldm, sizeof(T) * la->r1, la->r2, hipMemcpyHostToDevice));
-      HSS_HIP(hipMemcpy2D(dZ, sizeof(T) * ev(lru.r2), la->Z, sizeof(T) * la->ldz, sizeof(T) * la->r2, n, hipMemcpyHostToDevice));
+      HS_HIP(hipMemcpy2D(dC, sizeof(T) * ev((int)n), la->C, sizeof(T) * la->ldc, sizeof(T) * n, la->r1, hipMemcpyHostToDevice));
+      HS_HIP(hipMemcpy2D(dM, sizeof(T) * ev(lru.r1), la->M, sizeof(T) * la->ldm, sizeof(T) * la->r1, la->r2, hipMemcpyHostToDevice));
+      HS_HIP(hipMemcpy2D(dZ, sizeof(T) * ev(lru.r2), la->Z, sizeof(T) * la->ldz, sizeof(T) * la->r2, n, hipMemcpyHostToDevice));
       lru.C = dC; lru.ldc = ev((int)n);
       lru.M = dM; lru.ldm = ev(lru.r1);
       lru.Z = dZ; lru.ldz = ev(lru.r2);
@@ -2727,7 +2719,7 @@ int lowrank_id_batch(LowRankJob<T>* jobs, int njobs, double atol, double rtol, h
         o.Y0 = nullptr;
       }
       run_rows(tmp, rows, s);
-      HSS_HIP(hipStreamSynchronize(s));
+      HS_HIP(hipStreamSynchronize(s));
       todo.swap(again);
     }
   } catch (int code) {
@@ -2743,17 +2735,6 @@ struct hs_hss {
   void* impl;
 };
 
-#define HSS_GUARD(...)                \
-  try {                               \
-    __VA_ARGS__;                      \
-    return HS_OK;                     \
-  } catch (int code) {                \
-    return code;                      \
-  } catch (const std::bad_alloc&) {   \
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed"); \
-    return HS_ERR_NOMEM;              \
-  }
-
 extern "C" void hs_hss_options_default(hs_hss_options* o) {
   o->leafsize = 64;
   o->first_split = 0;
@@ -2768,12 +2749,12 @@ extern "C" void hs_hss_options_default(hs_hss_options* o) {
 extern "C" int hs_hss_compress_d(int64_t n, const double* A, int64_t lda, int where, const hs_hss_options* o, hs_hss** out) {
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
-  HSS_GUARD(*out = new hs_hss{0, compress_impl<double>(n, A, lda, where, o)});
+  HS_GUARD(*out = new hs_hss{0, compress_impl<double>(n, A, lda, where, o)});
 }
 extern "C" int hs_hss_compress_z(int64_t n, const double* A, int64_t lda, int where, const hs_hss_options* o, hs_hss** out) {
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
-  HSS_GUARD(*out = new hs_hss{1, compress_impl<cplx>(n, (const cplx*)A, lda, where, o)});
+  HS_GUARD(*out = new hs_hss{1, compress_impl<cplx>(n, (const cplx*)A, lda, where, o)});
 }
 
 #define HSS_DISPATCH(H, expr_d, expr_z) ((H)->is_complex ? (expr_z) : (expr_d))
@@ -2784,13 +2765,13 @@ extern "C" int hs_hss_compress_ex_d(int64_t n, const double* A, int64_t lda, int
                                     hs_hss** out) {
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
-  HSS_GUARD(*out = new hs_hss{0, compress_impl<double>(n, A, lda, where, o, perm, stream)});
+  HS_GUARD(*out = new hs_hss{0, compress_impl<double>(n, A, lda, where, o, perm, stream)});
 }
 extern "C" int hs_hss_compress_ex_z(int64_t n, const double* A, int64_t lda, int where, const int64_t* perm, const hs_hss_options* o, void* stream,
                                     hs_hss** out) {
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
-  HSS_GUARD(*out = new hs_hss{1, compress_impl<cplx>(n, (const cplx*)A, lda, where, o, perm, stream)});
+  HS_GUARD(*out = new hs_hss{1, compress_impl<cplx>(n, (const cplx*)A, lda, where, o, perm, stream)});
 }
 
 // H ~= (B - C*M*Z)[perm, perm] without forming the matrix: the Schur complement of a compressed front as the reference samples it
@@ -2800,14 +2781,14 @@ extern "C" int hs_hss_compress_lru_d(int64_t n, const double* B, int64_t ldb, co
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
   LruArgs la{C_, M, Z, ldc, ldm, ldz, r1, r2};
-  HSS_GUARD(*out = new hs_hss{0, compress_impl<double>(n, B, ldb, where, o, perm, stream, &la)});
+  HS_GUARD(*out = new hs_hss{0, compress_impl<double>(n, B, ldb, where, o, perm, stream, &la)});
 }
 extern "C" int hs_hss_compress_lru_z(int64_t n, const double* B, int64_t ldb, const double* C_, int64_t ldc, const double* M, int64_t ldm, const double* Z,
                                      int64_t ldz, int64_t r1, int64_t r2, int where, const int64_t* perm, const hs_hss_options* o, void* stream, hs_hss** out) {
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
   LruArgs la{C_, M, Z, ldc, ldm, ldz, r1, r2};
-  HSS_GUARD(*out = new hs_hss{1, compress_impl<cplx>(n, (const cplx*)B, ldb, where, o, perm, stream, &la)});
+  HS_GUARD(*out = new hs_hss{1, compress_impl<cplx>(n, (const cplx*)B, ldb, where, o, perm, stream, &la)});
 }
 
 extern "C" int hs_hss_set_stream(hs_hss* H, void* stream) {
@@ -2872,20 +2853,20 @@ static void node_data(const HssT<T>* H, int64_t i, int64_t* p, T* Tm, T* D, T* B
   const int m = x.m, r = x.r, nR = m - r;
   if (p && x.p) {
     std::vector<int> hp(m);
-    HSS_HIP(hipMemcpy(hp.data(), x.p, sizeof(int) * m, hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(hp.data(), x.p, sizeof(int) * m, hipMemcpyDeviceToHost));
     for (int a = 0; a < m; ++a) p[a] = hp[a];
   }
-  if (Tm && x.Tm && nR > 0 && r > 0) HSS_HIP(hipMemcpy2D(Tm, sizeof(T) * nR, x.Tm, sizeof(T) * x.ldt, sizeof(T) * nR, r, hipMemcpyDeviceToHost));
-  if (D && x.D) HSS_HIP(hipMemcpy2D(D, sizeof(T) * m, x.D, sizeof(T) * x.ldd, sizeof(T) * m, m, hipMemcpyDeviceToHost));
+  if (Tm && x.Tm && nR > 0 && r > 0) HS_HIP(hipMemcpy2D(Tm, sizeof(T) * nR, x.Tm, sizeof(T) * x.ldt, sizeof(T) * nR, r, hipMemcpyDeviceToHost));
+  if (D && x.D) HS_HIP(hipMemcpy2D(D, sizeof(T) * m, x.D, sizeof(T) * x.ldd, sizeof(T) * m, m, hipMemcpyDeviceToHost));
   if (x.left >= 0) {
     const int rl = H->nd[x.left].r, rr = H->nd[x.right].r;
-    if (B12 && rl > 0 && rr > 0) HSS_HIP(hipMemcpy2D(B12, sizeof(T) * rl, x.B12, sizeof(T) * x.ld12, sizeof(T) * rl, rr, hipMemcpyDeviceToHost));
-    if (B21 && rl > 0 && rr > 0) HSS_HIP(hipMemcpy2D(B21, sizeof(T) * rr, x.B21, sizeof(T) * x.ld21, sizeof(T) * rr, rl, hipMemcpyDeviceToHost));
+    if (B12 && rl > 0 && rr > 0) HS_HIP(hipMemcpy2D(B12, sizeof(T) * rl, x.B12, sizeof(T) * x.ld12, sizeof(T) * rl, rr, hipMemcpyDeviceToHost));
+    if (B21 && rl > 0 && rr > 0) HS_HIP(hipMemcpy2D(B21, sizeof(T) * rr, x.B21, sizeof(T) * x.ld21, sizeof(T) * rr, rl, hipMemcpyDeviceToHost));
   }
 }
 extern "C" int hs_hss_node_data(const hs_hss* H, int64_t node, int64_t* p, double* T_, double* D, double* B12, double* B21) {
   if (!H) return HS_ERR_ARGUMENT;
-  HSS_GUARD(if (H->is_complex) node_data<cplx>(HZ(H), node, p, (cplx*)T_, (cplx*)D, (cplx*)B12, (cplx*)B21);
+  HS_GUARD(if (H->is_complex) node_data<cplx>(HZ(H), node, p, (cplx*)T_, (cplx*)D, (cplx*)B12, (cplx*)B21);
             else node_data<double>(HD(H), node, p, T_, D, B12, B21));
 }
 
@@ -2900,9 +2881,9 @@ static void with_device_block(int n, const T* Bin, int64_t ldin, T* Bout, int64_
   const int ld = ev(n);
   T* dI = st.get<T>((size_t)ld * q);
   T* dO = (Bout == Bin) ? dI : st.get<T>((size_t)ld * q);
-  HSS_HIP(hipMemcpy2D(dI, sizeof(T) * ld, Bin, sizeof(T) * ldin, sizeof(T) * n, q, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy2D(dI, sizeof(T) * ld, Bin, sizeof(T) * ldin, sizeof(T) * n, q, hipMemcpyHostToDevice));
   f(dI, ld, dO, ld);
-  HSS_HIP(hipMemcpy2D(Bout, sizeof(T) * ldout, dO, sizeof(T) * ld, sizeof(T) * n, q, hipMemcpyDeviceToHost));
+  HS_HIP(hipMemcpy2D(Bout, sizeof(T) * ldout, dO, sizeof(T) * ld, sizeof(T) * n, q, hipMemcpyDeviceToHost));
 }
 
 static int hss_mul_abi(bool trans, hs_hss* H, const double* X, int64_t ldx, double* Y, int64_t ldy, int64_t nrhs, int where) {
@@ -2911,7 +2892,7 @@ static int hss_mul_abi(bool trans, hs_hss* H, const double* X, int64_t ldx, doub
     return HS_ERR_ARGUMENT;
   }
   if (nrhs == 0) return HS_OK;
-  HSS_GUARD(
+  HS_GUARD(
       if (H->is_complex) with_device_block<cplx>(HZ(H)->n, (const cplx*)X, ldx, (cplx*)Y, ldy, (int)nrhs, where,
                                                  [&](const cplx* a, int la, cplx* b, int lb) { hss_mul<cplx>(*HZ(H), a, la, b, lb, (int)nrhs, trans); });
       else with_device_block<double>(HD(H)->n, X, ldx, Y, ldy, (int)nrhs, where,
@@ -3051,10 +3032,10 @@ static HssT<T>* prune_impl(HssT<T>* P) {
     subs.push_back(SubJob<T>{Ul, ev(ml), nullptr, nullptr, 0, 0, ml, rl, UlT, ev(rl), 1});
     T* t12 = tmp.get<T>((size_t)ev(ml) * std::max(rr, 1));
     T* t21 = tmp.get<T>((size_t)ev(mr) * std::max(rl, 1));
-    HSS_HIP(hipMemsetAsync(t12, 0, sizeof(T) * (size_t)ev(ml) * std::max(rr, 1), s));
-    HSS_HIP(hipMemsetAsync(t21, 0, sizeof(T) * (size_t)ev(mr) * std::max(rl, 1), s));
-    HSS_HIP(hipMemset2DAsync(y.D + (size_t)ml * y.ldd, sizeof(T) * y.ldd, 0, sizeof(T) * ml, mr, s));
-    HSS_HIP(hipMemset2DAsync(y.D + ml, sizeof(T) * y.ldd, 0, sizeof(T) * mr, ml, s));
+    HS_HIP(hipMemsetAsync(t12, 0, sizeof(T) * (size_t)ev(ml) * std::max(rr, 1), s));
+    HS_HIP(hipMemsetAsync(t21, 0, sizeof(T) * (size_t)ev(mr) * std::max(rl, 1), s));
+    HS_HIP(hipMemset2DAsync(y.D + (size_t)ml * y.ldd, sizeof(T) * y.ldd, 0, sizeof(T) * ml, mr, s));
+    HS_HIP(hipMemset2DAsync(y.D + ml, sizeof(T) * y.ldd, 0, sizeof(T) * mr, ml, s));
     g1.push_back(GemmProb<T>{Ul, nd[i].B12, t12, ml, rr, rl, ev(ml), nd[i].ld12, ev(ml)});
     g1.push_back(GemmProb<T>{Ur, nd[i].B21, t21, mr, rl, rr, ev(mr), nd[i].ld21, ev(mr)});
     g2.push_back(GemmProb<T>{t12, UrT, y.D + (size_t)ml * y.ldd, ml, mr, rr, ev(ml), ev(rr), y.ldd});
@@ -3063,9 +3044,9 @@ static HssT<T>* prune_impl(HssT<T>* P) {
       // the node's basis over the merged leaf: E = blkdiag(U_l, U_r) U_node; its skeleton rows are identity rows of E
       const int rk = nd[i].r;
       std::vector<int> pp(nd[i].m), pl(ml), pr(mr);
-      HSS_HIP(hipMemcpy(pp.data(), nd[i].p, sizeof(int) * nd[i].m, hipMemcpyDeviceToHost));
-      HSS_HIP(hipMemcpy(pl.data(), l.p, sizeof(int) * ml, hipMemcpyDeviceToHost));
-      HSS_HIP(hipMemcpy(pr.data(), r.p, sizeof(int) * mr, hipMemcpyDeviceToHost));
+      HS_HIP(hipMemcpy(pp.data(), nd[i].p, sizeof(int) * nd[i].m, hipMemcpyDeviceToHost));
+      HS_HIP(hipMemcpy(pl.data(), l.p, sizeof(int) * ml, hipMemcpyDeviceToHost));
+      HS_HIP(hipMemcpy(pr.data(), r.p, sizeof(int) * mr, hipMemcpyDeviceToHost));
       std::vector<int> np(m);
       std::vector<char> isk(m, 0);
       for (int a = 0; a < rk; ++a) {
@@ -3081,7 +3062,7 @@ static HssT<T>* prune_impl(HssT<T>* P) {
       hss_basis<T>(*P, i, E, ev(m));
       y.m = m;
       y.p = C->keep.template get<int>(m);
-      HSS_HIP(hipMemcpy(y.p, np.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+      HS_HIP(hipMemcpy(y.p, np.data(), sizeof(int) * m, hipMemcpyHostToDevice));
       y.ldt = ev(m - rk);
       y.ldtt = ev(rk);
       y.Tm = C->keep.template get<T>((size_t)y.ldt * std::max(rk, 1));
@@ -3097,7 +3078,7 @@ static HssT<T>* prune_impl(HssT<T>* P) {
   run_subs(tmp, subs, s);  // diagonal blocks, transposed bases, interpolation rows
   run_gemms(tmp, g1, 0, s);
   run_gemms(tmp, g2, 0, s);
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
   C->nlev = 0;
   for (auto& x : C->nd) C->nlev = std::max(C->nlev, x.level + 1);
   C->lev.assign(C->nlev, {});
@@ -3109,7 +3090,7 @@ static HssT<T>* prune_impl(HssT<T>* P) {
 extern "C" int hs_hss_prune_leaves(hs_hss* H, hs_hss** out) {
   if (!H || !out) return HS_ERR_ARGUMENT;
   *out = nullptr;
-  HSS_GUARD(*out = H->is_complex ? new hs_hss{1, prune_impl<cplx>(HZ(H))} : new hs_hss{0, prune_impl<double>(HD(H))});
+  HS_GUARD(*out = H->is_complex ? new hs_hss{1, prune_impl<cplx>(HZ(H))} : new hs_hss{0, prune_impl<double>(HD(H))});
 }
 // `compatible(cl1, cl2)`: the two cluster trees have the same shape (what HSS-by-HSS arithmetic needs of its operands)
 template <class T>
@@ -3211,11 +3192,11 @@ static void pack_impl(HssT<T>* H, void* buf, int64_t bytes, hipStream_t s) {
   void* hp = tmp.get_pinned(sizeof(PackHdr) + sizeof(PackNode) * pn.size());
   memcpy(hp, &hd, sizeof hd);
   memcpy((char*)hp + sizeof hd, pn.data(), sizeof(PackNode) * pn.size());
-  HSS_HIP(hipMemcpyAsync(base, hp, sizeof hd, hipMemcpyHostToDevice, s));
-  HSS_HIP(hipMemcpyAsync(base + hd.off_nodes, (char*)hp + sizeof hd, sizeof(PackNode) * pn.size(), hipMemcpyHostToDevice, s));
-  if (H->perm) HSS_HIP(hipMemcpyAsync(base + hd.off_perm, H->perm, sizeof(int) * (size_t)H->n, hipMemcpyDeviceToDevice, s));
+  HS_HIP(hipMemcpyAsync(base, hp, sizeof hd, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(base + hd.off_nodes, (char*)hp + sizeof hd, sizeof(PackNode) * pn.size(), hipMemcpyHostToDevice, s));
+  if (H->perm) HS_HIP(hipMemcpyAsync(base + hd.off_perm, H->perm, sizeof(int) * (size_t)H->n, hipMemcpyDeviceToDevice, s));
   auto put = [&](int64_t off, const void* src, int64_t nbytes) {
-    if (off >= 0) HSS_HIP(hipMemcpyAsync(base + off, src, (size_t)nbytes, hipMemcpyDeviceToDevice, s));
+    if (off >= 0) HS_HIP(hipMemcpyAsync(base + off, src, (size_t)nbytes, hipMemcpyDeviceToDevice, s));
   };
   for (size_t i = 0; i < pn.size(); ++i) {
     const HNode<T>& x = H->nd[i];
@@ -3228,7 +3209,7 @@ static void pack_impl(HssT<T>* H, void* buf, int64_t bytes, hipStream_t s) {
     put(q.o_B12, x.B12, (int64_t)sizeof(T) * x.ld12 * q.rr);
     put(q.o_B21, x.B21, (int64_t)sizeof(T) * x.ld21 * q.rl);
   }
-  HSS_HIP(hipStreamSynchronize(s));  // the pinned staging block goes back to its cache with `tmp`
+  HS_HIP(hipStreamSynchronize(s));  // the pinned staging block goes back to its cache with `tmp`
 }
 
 template <class T>
@@ -3238,33 +3219,33 @@ static HssT<T>* unpack_impl(const void* buf, int64_t bytes, hipStream_t s) {
     hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_unpack: buffer of %lld bytes holds no header", (long long)bytes);
     throw (int)HS_ERR_ARGUMENT;
   }
-  HSS_HIP(hipMemcpyAsync(&hd, buf, sizeof hd, hipMemcpyDeviceToHost, s));
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipMemcpyAsync(&hd, buf, sizeof hd, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
   if (hd.magic != HS_PACK_MAGIC || hd.bytes > bytes || hd.is_complex != (int64_t)(sizeof(T) == 16) || hd.nnodes <= 0 || hd.n <= 0 ||
       hd.off_nodes + (int64_t)sizeof(PackNode) * hd.nnodes > hd.bytes) {
     hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_unpack: not a packed %s HSS matrix of at most %lld bytes", sizeof(T) == 16 ? "ComplexF64" : "Float64", (long long)bytes);
     throw (int)HS_ERR_ARGUMENT;
   }
   std::vector<PackNode> pn((size_t)hd.nnodes);
-  HSS_HIP(hipMemcpyAsync(pn.data(), (const char*)buf + hd.off_nodes, sizeof(PackNode) * pn.size(), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipMemcpyAsync(pn.data(), (const char*)buf + hd.off_nodes, sizeof(PackNode) * pn.size(), hipMemcpyDeviceToHost, s));
   std::unique_ptr<HssT<T>> H(new HssT<T>());
   H->n = (int)hd.n; H->k = (int)hd.k; H->nlev = (int)hd.nlev;
   H->opt = hd.opt;
   H->s = s;
   H->own_stream = false;
   if (!s) {
-    HSS_HIP(hipStreamCreate(&H->s));
+    HS_HIP(hipStreamCreate(&H->s));
     H->own_stream = true;
     s = H->s;
   }
   char* base = H->keep.template get<char>((size_t)hd.bytes);
-  HSS_HIP(hipMemcpyAsync(base, buf, (size_t)hd.bytes, hipMemcpyDeviceToDevice, s));
+  HS_HIP(hipMemcpyAsync(base, buf, (size_t)hd.bytes, hipMemcpyDeviceToDevice, s));
   if (hd.has_perm) {
     H->perm = (int*)(base + hd.off_perm);
     H->hperm.assign((size_t)hd.n, 0);
-    HSS_HIP(hipMemcpyAsync(H->hperm.data(), (const char*)buf + hd.off_perm, sizeof(int) * (size_t)hd.n, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipMemcpyAsync(H->hperm.data(), (const char*)buf + hd.off_perm, sizeof(int) * (size_t)hd.n, hipMemcpyDeviceToHost, s));
   }
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
   if (hd.has_perm) {
     H->hinvperm.assign((size_t)hd.n, 0);
     for (int64_t i = 0; i < hd.n; ++i) {
@@ -3309,22 +3290,22 @@ static HssT<T>* unpack_impl(const void* buf, int64_t bytes, hipStream_t s) {
 
 extern "C" int hs_hss_pack_size(const hs_hss* H, int64_t* bytes) {
   if (!H || !bytes) return HS_ERR_ARGUMENT;
-  HSS_GUARD(*bytes = HSS_DISPATCH(H, pack_size_impl(HD(H)), pack_size_impl(HZ(H))));
+  HS_GUARD(*bytes = HSS_DISPATCH(H, pack_size_impl(HD(H)), pack_size_impl(HZ(H))));
 }
 extern "C" int hs_hss_pack(hs_hss* H, void* dev_buf, int64_t bytes, void* stream) {
   if (!H) return HS_ERR_ARGUMENT;
-  HSS_GUARD(if (H->is_complex) pack_impl(HZ(H), dev_buf, bytes, (hipStream_t)stream); else pack_impl(HD(H), dev_buf, bytes, (hipStream_t)stream));
+  HS_GUARD(if (H->is_complex) pack_impl(HZ(H), dev_buf, bytes, (hipStream_t)stream); else pack_impl(HD(H), dev_buf, bytes, (hipStream_t)stream));
 }
 extern "C" int hs_hss_unpack(const void* dev_buf, int64_t bytes, int is_complex, void* stream, hs_hss** out) {
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
-  HSS_GUARD(*out = is_complex ? new hs_hss{1, unpack_impl<cplx>(dev_buf, bytes, (hipStream_t)stream)} : new hs_hss{0, unpack_impl<double>(dev_buf, bytes, (hipStream_t)stream)});
+  HS_GUARD(*out = is_complex ? new hs_hss{1, unpack_impl<cplx>(dev_buf, bytes, (hipStream_t)stream)} : new hs_hss{0, unpack_impl<double>(dev_buf, bytes, (hipStream_t)stream)});
 }
 
 extern "C" int hs_hss_child(hs_hss* H, int which, hs_hss** out) {
   if (!H || !out || which < 0 || which > 2) return HS_ERR_ARGUMENT;
   *out = nullptr;
-  HSS_GUARD(*out = H->is_complex ? new hs_hss{1, child_impl<cplx>(HZ(H), which)} : new hs_hss{0, child_impl<double>(HD(H), which)});
+  HS_GUARD(*out = H->is_complex ? new hs_hss{1, child_impl<cplx>(HZ(H), which)} : new hs_hss{0, child_impl<double>(HD(H), which)});
 }
 
 extern "C" int hs_hss_getindex(hs_hss* H, const int64_t* I, int64_t ni, const int64_t* J, int64_t nj, double* out, int64_t ldo, int where) {
@@ -3333,7 +3314,7 @@ extern "C" int hs_hss_getindex(hs_hss* H, const int64_t* I, int64_t ni, const in
     return HS_ERR_ARGUMENT;
   }
   if (ni == 0 || nj == 0) return HS_OK;
-  HSS_GUARD(
+  HS_GUARD(
       if (where != 0) {
         if (H->is_complex) hss_getindex<cplx>(*HZ(H), I, (int)ni, J, (int)nj, (cplx*)out, (int)ldo);
         else hss_getindex<double>(*HD(H), I, (int)ni, J, (int)nj, out, (int)ldo);
@@ -3343,18 +3324,18 @@ extern "C" int hs_hss_getindex(hs_hss* H, const int64_t* I, int64_t ni, const in
         if (H->is_complex) {
           cplx* d = st.get<cplx>((size_t)ld * nj);
           hss_getindex<cplx>(*HZ(H), I, (int)ni, J, (int)nj, d, ld);
-          HSS_HIP(hipMemcpy2D(out, sizeof(cplx) * ldo, d, sizeof(cplx) * ld, sizeof(cplx) * ni, nj, hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy2D(out, sizeof(cplx) * ldo, d, sizeof(cplx) * ld, sizeof(cplx) * ni, nj, hipMemcpyDeviceToHost));
         } else {
           double* d = st.get<double>((size_t)ld * nj);
           hss_getindex<double>(*HD(H), I, (int)ni, J, (int)nj, d, ld);
-          HSS_HIP(hipMemcpy2D(out, sizeof(double) * ldo, d, sizeof(double) * ld, sizeof(double) * ni, nj, hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy2D(out, sizeof(double) * ldo, d, sizeof(double) * ld, sizeof(double) * ni, nj, hipMemcpyDeviceToHost));
         }
       });
 }
 
 extern "C" int hs_hss_basis(hs_hss* H, int64_t node, double* out, int64_t ldo, int where) {
   if (!H || !out) return HS_ERR_ARGUMENT;
-  HSS_GUARD(
+  HS_GUARD(
       const int64_t nn = hs_hss_num_nodes(H);
       if (node <= 0 || node >= nn) {
         hs_set_error(HS_ERR_ARGUMENT, node, "ArgumentError: HSS node %lld has no basis", (long long)node);
@@ -3376,11 +3357,11 @@ extern "C" int hs_hss_basis(hs_hss* H, int64_t node, double* out, int64_t ldo, i
         if (H->is_complex) {
           cplx* d = st.get<cplx>((size_t)ld * r);
           hss_basis<cplx>(*HZ(H), (int)node, d, ld);
-          HSS_HIP(hipMemcpy2D(out, sizeof(cplx) * ldo, d, sizeof(cplx) * ld, sizeof(cplx) * rows, r, hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy2D(out, sizeof(cplx) * ldo, d, sizeof(cplx) * ld, sizeof(cplx) * rows, r, hipMemcpyDeviceToHost));
         } else {
           double* d = st.get<double>((size_t)ld * r);
           hss_basis<double>(*HD(H), (int)node, d, ld);
-          HSS_HIP(hipMemcpy2D(out, sizeof(double) * ldo, d, sizeof(double) * ld, sizeof(double) * rows, r, hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy2D(out, sizeof(double) * ldo, d, sizeof(double) * ld, sizeof(double) * rows, r, hipMemcpyDeviceToHost));
         }
       });
 }
@@ -3409,12 +3390,12 @@ static void offdiag_impl(HssT<T>& H, int which, T* C_, int ldc, T* Z, int ldz) {
   hss_basis<T>(H, b, Ub, ev(nb));
   const T* Bc = which == 0 ? H.nd[0].B12 : H.nd[0].B21;
   const int ldb = which == 0 ? H.nd[0].ld12 : H.nd[0].ld21;
-  HSS_HIP(hipMemset2DAsync(C_, sizeof(T) * ldc, 0, sizeof(T) * na, rb, s));
+  HS_HIP(hipMemset2DAsync(C_, sizeof(T) * ldc, 0, sizeof(T) * na, rb, s));
   std::vector<GemmProb<T>> g{GemmProb<T>{Ua, Bc, C_, na, rb, ra, ev(na), ldb, ldc}};
   run_gemms(tmp, g, 0, s);
   std::vector<SubJob<T>> t{SubJob<T>{Ub, ev(nb), nullptr, nullptr, 0, 0, nb, rb, Z, ldz, 1}};
   run_subs(tmp, t, s);
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 // Batched compression of `count` matrices B_b - C_b*M_b*Z_b (device operands), each with its own permutation, first split and leaf size:
 // ONE forest compressed level by level (compress_fixed), then one view per matrix that shares the forest's generators and keeps it alive.
@@ -3453,7 +3434,7 @@ static void compress_multi_impl(int64_t count, const int64_t* n, const T* const*
   if (stream) {
     H->s = (hipStream_t)stream;
   } else {
-    HSS_HIP(hipStreamCreate(&H->s));
+    HS_HIP(hipStreamCreate(&H->s));
     H->own_stream = true;
   }
   std::vector<CBlock<T>> cb((size_t)count);
@@ -3479,8 +3460,8 @@ static void compress_multi_impl(int64_t count, const int64_t* n, const T* const*
         seen[(size_t)perm[b][i]] = 1;
         hp[(size_t)i] = (int)perm[b][i];
       }
-      HSS_HIP(hipMemcpyAsync(dperm + off, hp.data(), sizeof(int) * (size_t)n[b], hipMemcpyHostToDevice, H->s));
-      HSS_HIP(hipStreamSynchronize(H->s));
+      HS_HIP(hipMemcpyAsync(dperm + off, hp.data(), sizeof(int) * (size_t)n[b], hipMemcpyHostToDevice, H->s));
+      HS_HIP(hipStreamSynchronize(H->s));
       B.perm = dperm + off;
       B.hperm = hp.data();
     }
@@ -3538,7 +3519,7 @@ extern "C" int hs_hss_compress_lru_multi_d(int64_t count, const int64_t* n, cons
                                            const double* const* M, const int64_t* ldm, const double* const* Z, const int64_t* ldz, const int64_t* r1, const int64_t* r2,
                                            const int64_t* const* perm, const hs_hss_options* const* opts, void* stream, hs_hss** out) {
   if (!out || count <= 0) return HS_ERR_ARGUMENT;
-  HSS_GUARD(
+  HS_GUARD(
       std::vector<LruArgs> la((size_t)count);
       for (int64_t b = 0; b < count; ++b)
         if (r1 && r2 && r1[b] > 0 && r2[b] > 0) la[(size_t)b] = LruArgs{C_[b], M ? M[b] : nullptr, Z[b], ldc[b], ldm ? ldm[b] : 0, ldz[b], r1[b], r2[b]};
@@ -3548,7 +3529,7 @@ extern "C" int hs_hss_compress_lru_multi_z(int64_t count, const int64_t* n, cons
                                            const double* const* M, const int64_t* ldm, const double* const* Z, const int64_t* ldz, const int64_t* r1, const int64_t* r2,
                                            const int64_t* const* perm, const hs_hss_options* const* opts, void* stream, hs_hss** out) {
   if (!out || count <= 0) return HS_ERR_ARGUMENT;
-  HSS_GUARD(
+  HS_GUARD(
       std::vector<LruArgs> la((size_t)count);
       for (int64_t b = 0; b < count; ++b)
         if (r1 && r2 && r1[b] > 0 && r2[b] > 0) la[(size_t)b] = LruArgs{C_[b], M ? M[b] : nullptr, Z[b], ldc[b], ldm ? ldm[b] : 0, ldz[b], r1[b], r2[b]};
@@ -3560,7 +3541,7 @@ extern "C" int hs_hss_expand(hs_hss* H, double* out, int64_t ldo, int where) {
     hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_expand needs an n x n result (ldo >= n)");
     return HS_ERR_ARGUMENT;
   }
-  HSS_GUARD(
+  HS_GUARD(
       if (where != 0) {
         if (H->is_complex) hss_expand<cplx>(*HZ(H), (cplx*)out, (int)ldo);
         else hss_expand<double>(*HD(H), out, (int)ldo);
@@ -3570,11 +3551,11 @@ extern "C" int hs_hss_expand(hs_hss* H, double* out, int64_t ldo, int where) {
         if (H->is_complex) {
           cplx* d = st.get<cplx>((size_t)ld * n);
           hss_expand<cplx>(*HZ(H), d, ld);
-          HSS_HIP(hipMemcpy2D(out, sizeof(cplx) * ldo, d, sizeof(cplx) * ld, sizeof(cplx) * n, n, hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy2D(out, sizeof(cplx) * ldo, d, sizeof(cplx) * ld, sizeof(cplx) * n, n, hipMemcpyDeviceToHost));
         } else {
           double* d = st.get<double>((size_t)ld * n);
           hss_expand<double>(*HD(H), d, ld);
-          HSS_HIP(hipMemcpy2D(out, sizeof(double) * ldo, d, sizeof(double) * ld, sizeof(double) * n, n, hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy2D(out, sizeof(double) * ldo, d, sizeof(double) * ld, sizeof(double) * n, n, hipMemcpyDeviceToHost));
         }
       });
 }
@@ -3584,7 +3565,7 @@ extern "C" int hs_hss_offdiag(hs_hss* H, int which, double* C_, int64_t ldc, dou
     hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_offdiag needs which in {0, 1} and two output blocks");
     return HS_ERR_ARGUMENT;
   }
-  HSS_GUARD(
+  HS_GUARD(
       int64_t ia[8]; int64_t ib[8];
       const int64_t l = HSS_DISPATCH(H, HD(H)->nd[0].left, HZ(H)->nd[0].left), r = HSS_DISPATCH(H, HD(H)->nd[0].right, HZ(H)->nd[0].right);
       if (l < 0) {
@@ -3605,8 +3586,8 @@ extern "C" int hs_hss_offdiag(hs_hss* H, int which, double* C_, int64_t ldc, dou
         if (H->is_complex) offdiag_impl<cplx>(*HZ(H), which, (cplx*)dC, lc, (cplx*)dZ, lz);
         else offdiag_impl<double>(*HD(H), which, (double*)dC, lc, (double*)dZ, lz);
         if (rb > 0) {
-          HSS_HIP(hipMemcpy2D(C_, esz * ldc, dC, esz * lc, esz * na, rb, hipMemcpyDeviceToHost));
-          HSS_HIP(hipMemcpy2D(Z, esz * ldz, dZ, esz * lz, esz * rb, nb, hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy2D(C_, esz * ldc, dC, esz * lc, esz * na, rb, hipMemcpyDeviceToHost));
+          HS_HIP(hipMemcpy2D(Z, esz * ldz, dZ, esz * lz, esz * rb, nb, hipMemcpyDeviceToHost));
         }
       });
 }
@@ -3654,14 +3635,14 @@ extern "C" int hs_hss_compress_blockop_d(const hs_hss_blockop* op, const double*
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
   LruArgs la{C_, M, Z, ldc, ldm, ldz, r1, r2};
-  HSS_GUARD(*out = compress_blockop<double>(op, la, perm, o, stream));
+  HS_GUARD(*out = compress_blockop<double>(op, la, perm, o, stream));
 }
 extern "C" int hs_hss_compress_blockop_z(const hs_hss_blockop* op, const double* C_, int64_t ldc, const double* M, int64_t ldm, const double* Z, int64_t ldz,
                                          int64_t r1, int64_t r2, const int64_t* perm, const hs_hss_options* o, void* stream, hs_hss** out) {
   if (!out) return HS_ERR_ARGUMENT;
   *out = nullptr;
   LruArgs la{C_, M, Z, ldc, ldm, ldz, r1, r2};
-  HSS_GUARD(*out = compress_blockop<cplx>(op, la, perm, o, stream));
+  HS_GUARD(*out = compress_blockop<cplx>(op, la, perm, o, stream));
 }
 // Y = Op * X (trans != 0: Op^T * X) for device blocks of nrhs columns in the operator's index order
 template <class T>
@@ -3670,7 +3651,7 @@ static void blockop_apply(const hs_hss_blockop* d, const T* X, int ldx, T* Y, in
   make_blockop<T>(d, op);
   op.begin(s);
   try {
-    HSS_HIP(hipMemset2DAsync(Y, sizeof(T) * ldy, 0, sizeof(T) * op.n, q, s));
+    HS_HIP(hipMemset2DAsync(Y, sizeof(T) * ldy, 0, sizeof(T) * op.n, q, s));
     op.mul(X, ldx, Y, ldy, q, trans != 0, s);
   } catch (...) {
     op.end(s);
@@ -3684,7 +3665,7 @@ extern "C" int hs_hss_blockop_apply(const hs_hss_blockop* op, int is_complex, co
     return HS_ERR_ARGUMENT;
   }
   if (nrhs == 0) return HS_OK;
-  HSS_GUARD(if (is_complex) blockop_apply<cplx>(op, (const cplx*)X, (int)ldx, (cplx*)Y, (int)ldy, (int)nrhs, trans, (hipStream_t)stream);
+  HS_GUARD(if (is_complex) blockop_apply<cplx>(op, (const cplx*)X, (int)ldx, (cplx*)Y, (int)ldy, (int)nrhs, trans, (hipStream_t)stream);
             else blockop_apply<double>(op, X, (int)ldx, Y, (int)ldy, (int)nrhs, trans, (hipStream_t)stream));
 }
 
@@ -3713,7 +3694,7 @@ extern "C" int64_t hs_hss_trim(void) {
 
 extern "C" int hs_hss_factor(hs_hss* H) {
   if (!H) return HS_ERR_ARGUMENT;
-  HSS_GUARD(if (H->is_complex) hss_factor<cplx>(*HZ(H)); else hss_factor<double>(*HD(H)));
+  HS_GUARD(if (H->is_complex) hss_factor<cplx>(*HZ(H)); else hss_factor<double>(*HD(H)));
 }
 
 extern "C" int hs_hss_ldiv(hs_hss* H, double* B, int64_t ldb, int64_t nrhs, int where) {
@@ -3722,7 +3703,7 @@ extern "C" int hs_hss_ldiv(hs_hss* H, double* B, int64_t ldb, int64_t nrhs, int 
     return HS_ERR_ARGUMENT;
   }
   if (nrhs == 0) return HS_OK;
-  HSS_GUARD(
+  HS_GUARD(
       if (H->is_complex) {
         hss_factor<cplx>(*HZ(H));
         with_device_block<cplx>(HZ(H)->n, (const cplx*)B, ldb, (cplx*)B, ldb, (int)nrhs, where,
@@ -3745,7 +3726,7 @@ extern "C" int hs_hss_ldiv_t(hs_hss* H, int trans, double* B, int64_t ldb, int64
   }
   if (trans == 0) return hs_hss_ldiv(H, B, ldb, nrhs, where);
   if (nrhs == 0) return HS_OK;
-  HSS_GUARD(
+  HS_GUARD(
       if (H->is_complex) {
         hss_factor<cplx>(*HZ(H));
         with_device_block<cplx>(HZ(H)->n, (const cplx*)B, ldb, (cplx*)B, ldb, (int)nrhs, where,

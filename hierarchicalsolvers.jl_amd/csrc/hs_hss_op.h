@@ -146,7 +146,7 @@ struct IntArena {
     if (h.empty()) return;
     void* ph = pool.get_pinned(sizeof(int) * h.size());
     memcpy(ph, h.data(), sizeof(int) * h.size());
-    HSS_HIP(hipMemcpyAsync(d, ph, sizeof(int) * h.size(), hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(d, ph, sizeof(int) * h.size(), hipMemcpyHostToDevice, s));
   }
 };
 
@@ -233,8 +233,8 @@ void hss_getindex_batch(HssT<T>& H, const std::vector<GiJob<T>>& jobs) {
     if (!touched) continue;
     if (i != 0 && x.hinvp.empty()) {
       std::vector<int> hp(x.m);
-      HSS_HIP(hipMemcpyAsync(hp.data(), x.p, sizeof(int) * x.m, hipMemcpyDeviceToHost, s));
-      HSS_HIP(hipStreamSynchronize(s));
+      HS_HIP(hipMemcpyAsync(hp.data(), x.p, sizeof(int) * x.m, hipMemcpyDeviceToHost, s));
+      HS_HIP(hipStreamSynchronize(s));
       x.hinvp.assign(x.m, 0);
       for (int a = 0; a < x.m; ++a) x.hinvp[hp[a]] = a;
     }
@@ -359,7 +359,7 @@ void hss_getindex_batch(HssT<T>& H, const std::vector<GiJob<T>>& jobs) {
   for (int b = 0; b < B; ++b)
     if (js[b].outS) subs.push_back(SubJob<T>{js[b].outS, js[b].ldS, drI[b], drJ[b], 0, 0, jobs[b].ni, jobs[b].nj, jobs[b].out, jobs[b].ldo, 0});
   run_subs(tmp, subs, s);
-  HSS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 
 // ---- the operator ---------------------------------------------------------------------------------------------------
@@ -387,13 +387,13 @@ struct BlockOp {
 
   void begin(hipStream_t s) {
     gid = own.get<int>((size_t)std::max(n, 1));
-    HSS_HIP(hipMemcpyAsync(gid, hgid.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-    HSS_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipMemcpyAsync(gid, hgid.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+    HS_HIP(hipStreamSynchronize(s));
     if (n > 0) hipLaunchKernelGGL(lpos_set_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const int*)gid, n, lpos, 0);
   }
   void end(hipStream_t s) {
     if (n > 0 && gid) hipLaunchKernelGGL(lpos_set_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const int*)gid, n, lpos, 1);
-    HSS_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipStreamSynchronize(s));
   }
   // Y = Op * X (trans: Op^T * X), n x k blocks in the operator's index order
   void mul(const T* X, int ldx, T* Y, int ldy, int k, bool trans, hipStream_t s) {
@@ -471,6 +471,6 @@ struct BlockOp {
       hipLaunchKernelGGL(blockop_spget_kernel<T>, grid, dim3(64), 0, s, d, Ad.colptr, Ad.rowval, Ad.nz);
     }, s);
     run_z_batched(tmp, scat, [&](dim3 grid, const ScatJob<T>* d) { hipLaunchKernelGGL(sub_scatter_kernel<T>, grid, dim3(64), 0, s, d); }, s);
-    HSS_HIP(hipStreamSynchronize(s));  // `keep` and the descriptors die with this call
+    HS_HIP(hipStreamSynchronize(s));  // `keep` and the descriptors die with this call
   }
 };

@@ -200,13 +200,13 @@ static void factor_hss_fronts(hs_handle* h, const int* ids, int count, const Nod
     const int64_t* q = x.ilv.empty() ? nullptr : x.ilv.data();
     int st = h->is_complex ? hs_hss_compress_ex_z(hd[i].ni, (const double*)hd[i].LF, hd[i].ldl, 1, q, &o, s, &H)
                            : hs_hss_compress_ex_d(hd[i].ni, (const double*)hd[i].LF, hd[i].ldl, 1, q, &o, s, &H);
-    if (st != 0) throw HsError{st};
+    HS_CHECK(st);
     x.hss = H;
     lap("HSS compress(Aii)", ids[i]);
     st = hs_hss_factor(H);
     if (st != 0) {
       if (st == HS_ERR_SINGULAR) hs_set_error(HS_ERR_SINGULAR, ids[i], "SingularException: the HSS form of the interior block of node %d is singular", ids[i]);
-      throw HsError{st};
+      throw st;
     }
     lap("HSS elimination", ids[i]);
     x.last_k = (int)hs_hss_samples(H);
@@ -239,7 +239,7 @@ static void factor_hss_fronts(hs_handle* h, const int* ids, int count, const Nod
     static const bool lr_qr = !(getenv("HS_LR_QR") && getenv("HS_LR_QR")[0] == '0');
     const int st = lr_qr ? lowrank_id_batch<T>(jobs.data(), 2 * nw, 0.5 * h->opts.atol, 0.5 * h->opts.rtol, s)
                          : lowrank_compress_batch<T>(jobs.data(), 2 * nw, 0.5 * h->opts.atol, 0.5 * h->opts.rtol, s);  // factorization.jl:99-100
-    if (st != 0) throw HsError{st};
+    HS_CHECK(st);
   }
   std::vector<T*> W2(nw, nullptr), W3(nw, nullptr);
   GemmProb<T>* dgp = nullptr;
@@ -274,7 +274,7 @@ static void factor_hss_fronts(hs_handle* h, const int* ids, int count, const Nod
       x.hldw = lrR->ldc;
       HS_HIP(hipMemcpyAsync(x.hW, lrR->Cd, wel * sizeof(T), hipMemcpyDeviceToDevice, s));
       const int st = hs_hss_ldiv((hs_hss*)x.hss, (double*)x.hW, x.hldw, rR, 1);
-      if (st != 0) throw HsError{st};
+      HS_CHECK(st);
       if (rL == 0) continue;
       const int ldw2 = (rL + 1) / 2 * 2;
       dmalloc((void**)&W2[a], ((size_t)ldw2 * rR + 32) * sizeof(T), "Z_L*W");
@@ -320,7 +320,7 @@ static void hss_d_solve(hs_handle* h, const NodeH& x, T* B, int ldb, int q, hipS
   auto hsolve = [&](void* H, T* b) {
     int st = hs_hss_set_stream((hs_hss*)H, (void*)s);
     if (st == 0) st = hs_hss_ldiv((hs_hss*)H, (double*)b, ldb, q, 1);
-    if (st != 0) throw HsError{st};
+    HS_CHECK(st);
   };
   if (!x.mfb) {
     hsolve(x.hss, B);

@@ -25,26 +25,10 @@
 #include "../../include/hs_solver.h"
 #include "../../include/hs_kernels.h"
 #include "hs_common.h"
+#include "hs_host.h"
 #include "hs_interface.h"
-#include "hs_selinv.h"  // hs_scratch_take / hs_scratch_give
 
 namespace {
-
-#define IF_FAIL(code, info, ...)               \
-  do {                                         \
-    hs_set_error((code), (info), __VA_ARGS__); \
-    throw (int)(code);                         \
-  } while (0)
-#define IF_GUARD(...)                                        \
-  try {                                                      \
-    __VA_ARGS__;                                             \
-    return HS_OK;                                            \
-  } catch (int code) {                                       \
-    return code;                                             \
-  } catch (const std::bad_alloc&) {                          \
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed"); \
-    return HS_ERR_NOMEM;                                     \
-  }
 
 struct InterfaceCache {
   hipEvent_t e0 = nullptr, e1 = nullptr;  // around the last hs_interface_matrix_* launch
@@ -80,31 +64,31 @@ void close_phase(InterfaceCache* c, void* mx) {
 // ---- checks: everything here happens before any device work ---------------------------------------------------------------------------
 void check_served(const HsInterfaceView& v, const char* fn) {
   if (v.nranks > 1)
-    IF_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: interfaces of a factorization over %d ranks are not implemented (single-rank factorizations only)", fn, v.nranks);
+    HS_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: interfaces of a factorization over %d ranks are not implemented (single-rank factorizations only)", fn, v.nranks);
   if (v.hss_node >= 0)
-    IF_FAIL(HS_ERR_UNSUPPORTED, v.hss_node, "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): interface solves are not implemented",
+    HS_FAIL(HS_ERR_UNSUPPORTED, v.hss_node, "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): interface solves are not implemented",
             fn, v.hss_node);
 }
 
 void check_factored(hs_handle* F, HsInterfaceView& v, bool cplx, const char* fn) {
-  if (!F) IF_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
+  if (!F) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
   hs_interface_view(F, &v);
   check_served(v, fn);
   if (!v.device || !v.factored)
-    IF_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs a completed numeric factorization (the handle is a plan, or hs_numeric_end has not run)", fn);
-  if ((v.is_complex != 0) != cplx) IF_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and of the block differ", fn);
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs a completed numeric factorization (the handle is a plan, or hs_numeric_end has not run)", fn);
+  if ((v.is_complex != 0) != cplx) HS_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and of the block differ", fn);
 }
 template <class T>
 void matrix_impl(hs_handle* F, T* S, int64_t lds, int where, void* stream) {
   const char* fn = "hs_interface_matrix_*";
   HsInterfaceView v;
   check_factored(F, v, sizeof(T) == 16, fn);
-  if (where < 0 || where > 1) IF_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: %s: where = %d (0: host, 1: device)", fn, where);
-  if (v.flags & HS_IF_SLICED) IF_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: the pseudo-root is eliminated in slices (hs_options.split): it has no single L, U", fn);
-  if (v.flags & HS_IF_NOLU) IF_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: the pseudo-root does not keep one dense pivoted LU of the interface block", fn);
+  if (where < 0 || where > 1) HS_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: %s: where = %d (0: host, 1: device)", fn, where);
+  if (v.flags & HS_IF_SLICED) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: the pseudo-root is eliminated in slices (hs_options.split): it has no single L, U", fn);
+  if (v.flags & HS_IF_NOLU) HS_FAIL(HS_ERR_UNSUPPORTED, 0, "%s: the pseudo-root does not keep one dense pivoted LU of the interface block", fn);
   const int64_t nb = v.nb;
-  if (nb > 0 && !S) IF_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: S == NULL", fn);
-  if (lds < std::max<int64_t>(nb, 1)) IF_FAIL(HS_ERR_DIMENSION, lds, "DimensionMismatch: %s: lds = %lld, S is %lld x %lld", fn, (long long)lds, (long long)nb, (long long)nb);
+  if (nb > 0 && !S) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: S == NULL", fn);
+  if (lds < std::max<int64_t>(nb, 1)) HS_FAIL(HS_ERR_DIMENSION, lds, "DimensionMismatch: %s: lds = %lld, S is %lld x %lld", fn, (long long)lds, (long long)nb, (long long)nb);
   InterfaceCache* c = cache_of(v);
   if (c->pending && c->e1) (void)hipEventSynchronize(c->e1);
   c->pending = false;
@@ -126,21 +110,16 @@ void matrix_impl(hs_handle* F, T* S, int64_t lds, int where, void* stream) {
     return;
   }
   const size_t bytes = (size_t)nb * nb * sizeof(T);
-  T* d = (T*)hs_scratch_take(bytes, "interface matrix");
-  try {
-    HS_HIP(hipEventRecord(c->e0, s));
-    c->flops = launch_lu_product<T>((int)nb, (const T*)v.LU, v.ldlu, v.rperm, d, nb, s);
-    HS_HIP(hipEventRecord(c->e1, s));
-    HS_HIP(hipGetLastError());
-    c->pending = true;
-    HS_HIP(hipMemcpy2DAsync(S, lds * sizeof(T), d, nb * sizeof(T), nb * sizeof(T), nb, hipMemcpyDeviceToHost, s));
-    HS_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    hs_scratch_give(d, bytes);
-    throw;
-  }
-  hs_scratch_give(d, bytes);
+  HsScratch buf(bytes, "interface matrix");
+  HsDrain drain{s};
+  T* d = (T*)buf.p;
+  HS_HIP(hipEventRecord(c->e0, s));
+  c->flops = launch_lu_product<T>((int)nb, (const T*)v.LU, v.ldlu, v.rperm, d, nb, s);
+  HS_HIP(hipEventRecord(c->e1, s));
+  HS_HIP(hipGetLastError());
+  c->pending = true;
+  HS_HIP(hipMemcpy2DAsync(S, lds * sizeof(T), d, nb * sizeof(T), nb * sizeof(T), nb, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
 }
 
 // phase: HS_MULTI_CONDENSE / ROOT / EXPAND; dev: C is a device block and the call returns without waiting
@@ -150,12 +129,12 @@ void phase_impl(hs_handle* F, int phase, int trans, T* C, int64_t ldc, int64_t n
   const char* fn = names[phase - HS_MULTI_CONDENSE];
   HsInterfaceView v;
   check_factored(F, v, sizeof(T) == 16, fn);
-  if (trans < 0 || trans > 2) IF_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
+  hs_check_trans(fn, trans);
   if (n != v.n || ldc < n || nrhs < 0)
-    IF_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the block has %lld rows (ld %lld, %lld columns), F is %lld x %lld", fn, (long long)n, (long long)ldc,
+    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the block has %lld rows (ld %lld, %lld columns), F is %lld x %lld", fn, (long long)n, (long long)ldc,
             (long long)nrhs, (long long)v.n, (long long)v.n);
-  if (nrhs > 0 && !C) IF_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
-  if (hs_handle_flow_check(F) != HS_OK) throw (int)HS_ERR_DEVICE;
+  if (nrhs > 0 && !C) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
+  HS_CHECK(hs_handle_flow_check(F));
   if (nrhs == 0) return;
   HsMultiView mv;
   hs_multi_view(F, &mv);
@@ -166,58 +145,47 @@ void phase_impl(hs_handle* F, int phase, int trans, T* C, int64_t ldc, int64_t n
     c->open_phase = phase - HS_MULTI_CONDENSE;
     return;
   }
-  hipStream_t s = v.stream;
-  const size_t bytes = (size_t)n * nrhs * sizeof(T);
-  T* d = (T*)hs_scratch_take(bytes, "interface block");
-  try {
-    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), C, ldc * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
-    hs_solve_multi_run<T>(mv, trans, d, n, nrhs, s, nullptr, phase);
+  hs_stage_block<T>(v.stream, "interface block", C, ldc, (const T*)C, ldc, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) {
+    hs_solve_multi_run<T>(mv, trans, d, ld, nrhs, s, nullptr, phase);
     c->open_phase = phase - HS_MULTI_CONDENSE;
-    HS_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
-    HS_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    hs_scratch_give(d, bytes);
-    throw;
-  }
-  hs_scratch_give(d, bytes);
+  });
   close_phase(c, *mv.mx);
 }
 }  // namespace
 
 extern "C" int hs_interface_size(const hs_handle* F, int64_t* nb) {
-  IF_GUARD(if (!F || !nb) IF_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_interface_size: null %s", F ? "output" : "factorization handle");
+  HS_GUARD(if (!F || !nb) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_interface_size: null %s", F ? "output" : "factorization handle");
            HsInterfaceView v; hs_interface_view(const_cast<hs_handle*>(F), &v);
            *nb = v.nb);
 }
 extern "C" int hs_interface_indices(const hs_handle* F, int64_t* idx) {
-  IF_GUARD(if (!F) IF_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_interface_indices: null factorization handle");
+  HS_GUARD(if (!F) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_interface_indices: null factorization handle");
            HsInterfaceView v; hs_interface_view(const_cast<hs_handle*>(F), &v);
-           if (v.nb > 0 && !idx) IF_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_interface_indices: idx == NULL");
+           if (v.nb > 0 && !idx) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_interface_indices: idx == NULL");
            for (int64_t i = 0; i < v.nb; ++i) idx[i] = (int64_t)v.idx[i] + 1);
 }
-extern "C" int hs_interface_matrix_d(hs_handle* F, double* S, int64_t lds, int where, void* stream) { IF_GUARD(matrix_impl<double>(F, S, lds, where, stream)); }
-extern "C" int hs_interface_matrix_z(hs_handle* F, double* S, int64_t lds, int where, void* stream) { IF_GUARD(matrix_impl<cplx>(F, (cplx*)S, lds, where, stream)); }
+extern "C" int hs_interface_matrix_d(hs_handle* F, double* S, int64_t lds, int where, void* stream) { HS_GUARD(matrix_impl<double>(F, S, lds, where, stream)); }
+extern "C" int hs_interface_matrix_z(hs_handle* F, double* S, int64_t lds, int where, void* stream) { HS_GUARD(matrix_impl<cplx>(F, (cplx*)S, lds, where, stream)); }
 
 #define IF_PHASE(name, phase)                                                                                                                   \
   extern "C" int hs_interface_##name##_d(hs_handle* F, int trans, double* C, int64_t ldc, int64_t n, int64_t nrhs) {                            \
-    IF_GUARD(phase_impl<double>(F, phase, trans, C, ldc, n, nrhs, false, nullptr));                                                             \
+    HS_GUARD(phase_impl<double>(F, phase, trans, C, ldc, n, nrhs, false, nullptr));                                                             \
   }                                                                                                                                             \
   extern "C" int hs_interface_##name##_z(hs_handle* F, int trans, double* C, int64_t ldc, int64_t n, int64_t nrhs) {                            \
-    IF_GUARD(phase_impl<cplx>(F, phase, trans, (cplx*)C, ldc, n, nrhs, false, nullptr));                                                        \
+    HS_GUARD(phase_impl<cplx>(F, phase, trans, (cplx*)C, ldc, n, nrhs, false, nullptr));                                                        \
   }                                                                                                                                             \
   extern "C" int hs_interface_##name##_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, int64_t n, int64_t nrhs, void* stream) {         \
-    IF_GUARD(phase_impl<double>(F, phase, trans, dC, ldc, n, nrhs, true, stream));                                                              \
+    HS_GUARD(phase_impl<double>(F, phase, trans, dC, ldc, n, nrhs, true, stream));                                                              \
   }                                                                                                                                             \
   extern "C" int hs_interface_##name##_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, int64_t n, int64_t nrhs, void* stream) {         \
-    IF_GUARD(phase_impl<cplx>(F, phase, trans, (cplx*)dC, ldc, n, nrhs, true, stream));                                                         \
+    HS_GUARD(phase_impl<cplx>(F, phase, trans, (cplx*)dC, ldc, n, nrhs, true, stream));                                                         \
   }
 IF_PHASE(condense, HS_MULTI_CONDENSE)
 IF_PHASE(solve, HS_MULTI_ROOT)
 IF_PHASE(expand, HS_MULTI_EXPAND)
 
 extern "C" int hs_interface_info(const hs_handle* F, double* out8) {
-  IF_GUARD(if (!F || !out8) IF_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_interface_info: null %s", F ? "output" : "factorization handle");
+  HS_GUARD(if (!F || !out8) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_interface_info: null %s", F ? "output" : "factorization handle");
            HsInterfaceView v; hs_interface_view(const_cast<hs_handle*>(F), &v);
            for (int k = 0; k < 8; ++k) out8[k] = 0.0;
            out8[2] = (double)v.nb;

@@ -174,13 +174,13 @@ static hs_hss_options mf_options(const hs_handle* h, int node, double scale, int
 }
 
 static void mf_check(int st) {
-  if (st != 0) throw HsError{st};
+  HS_CHECK(st);
 }
 
 // The compressions of the fronts of one level are independent chains of small dependent launches (tree levels x windows of rows): run
 // alone, each leaves most of the chip idle.  Up to HS_MF_THREADS (default 2: the chains are bound by the host side of the launches, which does not scale over threads) of them run concurrently, one host thread and one HIP stream
 // each (the HSS module is synchronous per call; its block caches are mutex-guarded, its error state thread-local).  body(i, stream) may
-// throw HsError / int; the first failure is re-raised on the calling thread with its message.
+// throw an int (HS_FAIL, HS_HIP, HS_CHECK); the first failure is re-raised on the calling thread with its message.
 static std::mutex g_mf_mu;  // guards hs_handle::maxrank and verbose output ordering
 template <class F>
 static void mf_parallel(hs_handle* h, int count, F&& body) {
@@ -209,10 +209,8 @@ static void mf_parallel(hs_handle* h, int count, F&& body) {
       try {
         for (int i = next.fetch_add(1); i < count; i = next.fetch_add(1)) {
           body(i, st);
-          if (hipStreamSynchronize(st) != hipSuccess) throw HsError{HS_ERR_DEVICE};
+          if (hipStreamSynchronize(st) != hipSuccess) throw (int)HS_ERR_DEVICE;
         }
-      } catch (const HsError& e) {
-        codes[t] = e.code;
       } catch (int c) {
         codes[t] = c;
       } catch (const std::bad_alloc&) {
@@ -230,7 +228,7 @@ static void mf_parallel(hs_handle* h, int count, F&& body) {
   for (int t = 0; t < nth; ++t)
     if (codes[t] != 0) {
       hs_set_error(codes[t], infos[t], "%s", msgs[t].c_str());
-      throw HsError{codes[t]};
+      throw codes[t];
     }
 }
 static void mf_maxrank(hs_handle* h, int64_t r) {
@@ -653,7 +651,7 @@ static void factor_mf_fronts(hs_handle* h, const int* ids, int count) {
         if (st == 0 && k12 > 0) st = hs_hss_ldiv((hs_hss*)x.hss, (double*)W12, x.bldw, k12, 1);
         if (st != 0) {
           if (st == HS_ERR_SINGULAR) hs_set_error(HS_ERR_SINGULAR, id, "SingularException: the block A11 of the interior block of node %d is singular", id);
-          throw HsError{st};
+          throw st;
         }
         lap("D: A11 eliminated, A11^-1 A12");
         T* M22 = nullptr;
@@ -691,7 +689,7 @@ static void factor_mf_fronts(hs_handle* h, const int* ids, int count) {
         st = hs_hss_factor(S22);
         if (st != 0) {
           if (st == HS_ERR_SINGULAR) hs_set_error(HS_ERR_SINGULAR, id, "SingularException: the Schur complement S22 of the interior block of node %d is singular", id);
-          throw HsError{st};
+          throw st;
         }
         lap("D: S22 eliminated");
         x.last_k = (int)hs_hss_samples(S22);
@@ -714,7 +712,7 @@ static void factor_mf_fronts(hs_handle* h, const int* ids, int count) {
         int st = hs_hss_factor(D);
         if (st != 0) {
           if (st == HS_ERR_SINGULAR) hs_set_error(HS_ERR_SINGULAR, id, "SingularException: the HSS form of the interior block of node %d is singular", id);
-          throw HsError{st};
+          throw st;
         }
         lap("D: HSS elimination");
         x.last_k = (int)hs_hss_samples(D);

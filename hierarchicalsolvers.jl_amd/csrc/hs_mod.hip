@@ -19,12 +19,10 @@
 
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
-#define HS_CONDEST_KERNELS
-#include "hs_condest.h"
+#include "hs_host.h"
+#pragma clang fp contract(off)  // host arithmetic only (no kernel lives here): the plain products and sums
 #include "hs_solve_multi.h"  // hs_ldiv_block_cols
 #include "hs_mod.h"
-
-using namespace hs_ce;
 
 struct hs_mod {
   hs_handle* F = nullptr;
@@ -53,7 +51,7 @@ struct hs_mod {
   U_* take(size_t count) {
     void* p = nullptr;
     const size_t b = std::max<size_t>(count * sizeof(U_), 256);
-    if (hipMalloc(&p, b) != hipSuccess) CE_FAIL(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_mod_*: hipMalloc of %zu bytes failed", b);
+    if (hipMalloc(&p, b) != hipSuccess) HS_FAIL(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_mod_*: hipMalloc of %zu bytes failed", b);
     owned.push_back(p);
     bytes += b;
     return (U_*)p;
@@ -89,17 +87,17 @@ double norm1_host(const std::vector<T>& A, int k) {
 // what every create refuses of the handle and the sizes; the zero-column solve speaks for the block solve
 template <class T>
 HsHandleView check_create(const char* fn, hs_handle* F, int64_t n, int64_t k, hs_mod** out) {
-  if (!out) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: M == NULL", fn);
+  if (!out) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: M == NULL", fn);
   *out = nullptr;
-  HsHandleView v = view_of(F, fn);
-  if ((v.is_complex != 0) != (sizeof(T) == 16)) CE_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and of the modification differ", fn);
-  if (!v.device) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan); use hs_analyze", fn);
-  if (!v.factored) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds no numeric factorization", fn);
-  if (n != v.n || k < 0) CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the modification has %lld rows and rank %lld, F is %lld x %lld", fn, (long long)n, (long long)k, (long long)v.n, (long long)v.n);
+  HsHandleView v = hs_view_of(F, fn);
+  if ((v.is_complex != 0) != (sizeof(T) == 16)) HS_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and of the modification differ", fn);
+  if (!v.device) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan); use hs_analyze", fn);
+  if (!v.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds no numeric factorization", fn);
+  if (n != v.n || k < 0) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the modification has %lld rows and rank %lld, F is %lld x %lld", fn, (long long)n, (long long)k, (long long)v.n, (long long)v.n);
   if (k > HS_MOD_MAXRANK)
-    CE_FAIL(HS_ERR_UNSUPPORTED, k, "%s: rank %lld > HS_MOD_MAXRANK = %d: a modification of this rank is not applied through the capacitance matrix; refactor (hs_factor_*)", fn,
+    HS_FAIL(HS_ERR_UNSUPPORTED, k, "%s: rank %lld > HS_MOD_MAXRANK = %d: a modification of this rank is not applied through the capacitance matrix; refactor (hs_factor_*)", fn,
             (long long)k, HS_MOD_MAXRANK);
-  CE_CHECK(block_solve<T>(F, 0, nullptr, n, nullptr, n, n, 0, v.stream));
+  HS_CHECK(block_solve<T>(F, 0, nullptr, n, nullptr, n, n, 0, v.stream));
   return v;
 }
 
@@ -112,8 +110,8 @@ void common_buffers(hs_mod* M) {
   M->dT = M->take<T>((size_t)k * KC);
   M->dPiv = M->take<int>((size_t)k);
   M->dInfo = M->take<int>(1);
-  CE_HIP(hipEventCreate(&M->e0));
-  CE_HIP(hipEventCreate(&M->e1));
+  HS_HIP(hipEventCreate(&M->e0));
+  HS_HIP(hipEventCreate(&M->e1));
 }
 
 // C (k x k in dLU, before its identity) -> LU(C), rcond_1(C); waits for s
@@ -123,22 +121,22 @@ void factor_cap(const char* fn, hs_mod* M, hipStream_t s) {
   T* C = (T*)M->dLU;
   launch_mod_add_eye<T>(C, k, k, s);
   std::vector<T> hC((size_t)k * k), hI((size_t)k * k);
-  CE_HIP(hipMemcpyAsync(hC.data(), C, hC.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipMemcpyAsync(hC.data(), C, hC.size() * sizeof(T), hipMemcpyDeviceToHost, s));
   launch_mod_cap_lu<T>(C, k, k, M->dPiv, M->dInfo, s);
   int info = 0;
-  CE_HIP(hipMemcpyAsync(&info, M->dInfo, sizeof(int), hipMemcpyDeviceToHost, s));
-  CE_HIP(hipStreamSynchronize(s));
-  CE_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(&info, M->dInfo, sizeof(int), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipGetLastError());
   if (info != 0)
-    CE_FAIL(HS_ERR_SINGULAR, info, "SingularException(%d): %s: the capacitance matrix I + V^H F^-1 U is singular (A + U V^H is, if A is not)", info, fn);
-  DevBuf tmp;
+    HS_FAIL(HS_ERR_SINGULAR, info, "SingularException(%d): %s: the capacitance matrix I + V^H F^-1 U is singular (A + U V^H is, if A is not)", info, fn);
+  HsDevBuf tmp("condest workspace");
   T* dI = tmp.get<T>((size_t)k * k);
   std::vector<T> eye((size_t)k * k, Scal<T>::zero());
   for (int j = 0; j < k; ++j) eye[(size_t)j * k + j] = Scal<T>::one();
-  CE_HIP(hipMemcpyAsync(dI, eye.data(), eye.size() * sizeof(T), hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(dI, eye.data(), eye.size() * sizeof(T), hipMemcpyHostToDevice, s));
   launch_mod_cap_solve<T>(C, k, k, M->dPiv, 0, dI, k, k, s);
-  CE_HIP(hipMemcpyAsync(hI.data(), dI, hI.size() * sizeof(T), hipMemcpyDeviceToHost, s));
-  CE_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipMemcpyAsync(hI.data(), dI, hI.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
   const double a = norm1_host(hC, k), b = norm1_host(hI, k);
   M->rcond = (a > 0.0 && b > 0.0 && std::isfinite(a) && std::isfinite(b)) ? 1.0 / (a * b) : 0.0;
 }
@@ -151,7 +149,7 @@ void build_dense(const char* fn, hs_mod* M, hipStream_t s) {
   if (k == 0) return;
   const int KC = hs_ldiv_block_cols();
   M->dPart = M->take<T>((size_t)hs_mod_slabs(n) * k * KC);
-  CE_CHECK(block_solve<T>(M->F, 0, (T*)M->dZ, n, (const T*)M->dU, n, n, k, s));
+  HS_CHECK(block_solve<T>(M->F, 0, (T*)M->dZ, n, (const T*)M->dU, n, n, k, s));
   ++M->solves;
   for (int c0 = 0; c0 < k; c0 += KC) {
     const int mc = std::min(KC, k - c0);
@@ -164,8 +162,8 @@ template <class T>
 void create_dense(hs_handle* F, int64_t n, int64_t k, const T* U, int64_t ldu, const T* V, int64_t ldv, bool on_device, void* stream, hs_mod** out) {
   const char* fn = on_device ? "hs_mod_create_dev_*" : "hs_mod_create_*";
   const HsHandleView v = check_create<T>(fn, F, n, k, out);
-  if (k > 0 && (!U || !V)) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: U and V must not be NULL", fn);
-  if (k > 0 && (ldu < n || ldv < n)) CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldu = %lld, ldv = %lld, n = %lld", fn, (long long)ldu, (long long)ldv, (long long)n);
+  if (k > 0 && (!U || !V)) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: U and V must not be NULL", fn);
+  if (k > 0 && (ldu < n || ldv < n)) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldu = %lld, ldv = %lld, n = %lld", fn, (long long)ldu, (long long)ldv, (long long)n);
   const auto t0 = std::chrono::steady_clock::now();
   std::unique_ptr<hs_mod> M(new hs_mod());
   M->F = F;
@@ -178,9 +176,9 @@ void create_dense(hs_handle* F, int64_t n, int64_t k, const T* U, int64_t ldu, c
     M->dU = M->take<T>((size_t)n * k);
     M->dV = M->take<T>((size_t)n * k);
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    CE_HIP(hipMemcpy2DAsync(M->dU, n * sizeof(T), U, ldu * sizeof(T), n * sizeof(T), k, kind, s));
-    CE_HIP(hipMemcpy2DAsync(M->dV, n * sizeof(T), V, ldv * sizeof(T), n * sizeof(T), k, kind, s));
-    if (!on_device) CE_HIP(hipStreamSynchronize(s));  // the host blocks may go once the call returns
+    HS_HIP(hipMemcpy2DAsync(M->dU, n * sizeof(T), U, ldu * sizeof(T), n * sizeof(T), k, kind, s));
+    HS_HIP(hipMemcpy2DAsync(M->dV, n * sizeof(T), V, ldv * sizeof(T), n * sizeof(T), k, kind, s));
+    if (!on_device) HS_HIP(hipStreamSynchronize(s));  // the host blocks may go once the call returns
     build_dense<T>(fn, M.get(), s);
   }
   M->t_build = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -191,21 +189,21 @@ template <class T>
 void create_sparse(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nzval, hs_mod** out) {
   const char* fn = "hs_mod_create_sparse_*";
   if (out) *out = nullptr;
-  if (!colptr) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: colptr == NULL", fn);
-  if (n < 0) CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: n = %lld", fn, (long long)n);
-  if (colptr[0] != 1) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: colptr must be 1-based (SparseMatrixCSC)", fn);
+  if (!colptr) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: colptr == NULL", fn);
+  if (n < 0) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: n = %lld", fn, (long long)n);
+  if (colptr[0] != 1) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: colptr must be 1-based (SparseMatrixCSC)", fn);
   int64_t k = 0;
   for (int64_t j = 0; j < n; ++j) {
-    if (colptr[j + 1] < colptr[j] || colptr[j + 1] - colptr[j] > n) CE_FAIL(HS_ERR_ARGUMENT, j, "ArgumentError: %s: colptr is inconsistent at column %lld", fn, (long long)j + 1);
+    if (colptr[j + 1] < colptr[j] || colptr[j + 1] - colptr[j] > n) HS_FAIL(HS_ERR_ARGUMENT, j, "ArgumentError: %s: colptr is inconsistent at column %lld", fn, (long long)j + 1);
     if (colptr[j + 1] > colptr[j]) ++k;
   }
   const int64_t nnz = colptr[n] - 1;
-  if (nnz > 0 && (!rowval || !nzval)) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: rowval and nzval must not be NULL", fn);
+  if (nnz > 0 && (!rowval || !nzval)) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: rowval and nzval must not be NULL", fn);
   for (int64_t j = 0; j < n; ++j)
     for (int64_t e = colptr[j] - 1; e < colptr[j + 1] - 1; ++e) {
-      if (rowval[e] < 1 || rowval[e] > n) CE_FAIL(HS_ERR_DIMENSION, e, "BoundsError: %s: rowval[%lld] = %lld outside 1:%lld", fn, (long long)e + 1, (long long)rowval[e], (long long)n);
+      if (rowval[e] < 1 || rowval[e] > n) HS_FAIL(HS_ERR_DIMENSION, e, "BoundsError: %s: rowval[%lld] = %lld outside 1:%lld", fn, (long long)e + 1, (long long)rowval[e], (long long)n);
       if (e > colptr[j] - 1 && rowval[e] <= rowval[e - 1])
-        CE_FAIL(HS_ERR_ARGUMENT, e, "ArgumentError: %s: the rows of column %lld of dA are not strictly increasing", fn, (long long)j + 1);
+        HS_FAIL(HS_ERR_ARGUMENT, e, "ArgumentError: %s: the rows of column %lld of dA are not strictly increasing", fn, (long long)j + 1);
     }
   const HsHandleView v = check_create<T>(fn, F, n, k, out);
   const auto t0 = std::chrono::steady_clock::now();
@@ -229,10 +227,10 @@ void create_sparse(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t
     M->urv.assign(rowval, rowval + nnz);
     M->dUval = M->take<T>((size_t)nnz);
     M->dJ = M->take<int64_t>((size_t)k);
-    CE_HIP(hipMemcpyAsync(M->dUval, nzval, (size_t)nnz * sizeof(T), hipMemcpyHostToDevice, s));
-    CE_HIP(hipMemcpyAsync(M->dJ, j0.data(), (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    CE_HIP(hipStreamSynchronize(s));
-    CE_CHECK(sparse_solve<T>(F, 0, n, k, M->ucp.data(), M->urv.data(), (const T*)M->dUval, (T*)M->dZ, n, s));
+    HS_HIP(hipMemcpyAsync(M->dUval, nzval, (size_t)nnz * sizeof(T), hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(M->dJ, j0.data(), (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HS_HIP(hipStreamSynchronize(s));
+    HS_CHECK(sparse_solve<T>(F, 0, n, k, M->ucp.data(), M->urv.data(), (const T*)M->dUval, (T*)M->dZ, n, s));
     ++M->solves;
     launch_mod_gather<T>((T*)M->dLU, k, (const T*)M->dZ, n, M->dJ, (int)k, (int)k, s);
     factor_cap<T>(fn, M.get(), s);
@@ -266,7 +264,7 @@ void build_w_blocks(hs_mod* M, hipStream_t s) {
   const int64_t n = M->n;
   T* W = M->take<T>((size_t)n * k);
   if (!M->sparse) {
-    CE_CHECK(block_solve<T>(M->F, 2, W, n, (const T*)M->dV, n, n, k, s));
+    HS_CHECK(block_solve<T>(M->F, 2, W, n, (const T*)M->dV, n, n, k, s));
   } else {
     const int64_t nnz = (int64_t)M->urv.size();
     std::vector<T> ones((size_t)k, Scal<T>::one());
@@ -278,19 +276,19 @@ void build_w_blocks(hs_mod* M, hipStream_t s) {
         er[(size_t)e] = (int32_t)(M->urv[(size_t)e] - 1);
         ec[(size_t)e] = j;
       }
-    DevBuf tmp;
+    HsDevBuf tmp("condest workspace");
     T* d1 = tmp.get<T>((size_t)k);
     int32_t* der = tmp.get<int32_t>((size_t)nnz);
     int32_t* dec = tmp.get<int32_t>((size_t)nnz);
-    CE_HIP(hipMemcpyAsync(d1, ones.data(), (size_t)k * sizeof(T), hipMemcpyHostToDevice, s));
-    CE_HIP(hipMemcpyAsync(der, er.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    CE_HIP(hipMemcpyAsync(dec, ec.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(d1, ones.data(), (size_t)k * sizeof(T), hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(der, er.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(dec, ec.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
     T* U = M->take<T>((size_t)n * k);
     T* part = M->take<T>((size_t)hs_mod_slabs(n) * k * hs_ldiv_block_cols());
-    CE_HIP(hipMemsetAsync(U, 0, (size_t)n * k * sizeof(T), s));
+    HS_HIP(hipMemsetAsync(U, 0, (size_t)n * k * sizeof(T), s));
     launch_mod_scatter<T>(U, n, der, dec, (const T*)M->dUval, nnz, s);
-    CE_HIP(hipStreamSynchronize(s));
-    CE_CHECK(sparse_solve<T>(M->F, 2, n, k, cp.data(), M->J.data(), d1, W, n, s));  // waits for s
+    HS_HIP(hipStreamSynchronize(s));
+    HS_CHECK(sparse_solve<T>(M->F, 2, n, k, cp.data(), M->J.data(), d1, W, n, s));  // waits for s
     M->dU = U;
     M->dPart = part;
   }
@@ -300,11 +298,11 @@ void build_w_blocks(hs_mod* M, hipStream_t s) {
 
 template <class T>
 void check_ldiv(const char* fn, hs_mod* M, int trans, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
-  if (!M) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null hs_mod", fn);
-  if ((M->cx != 0) != (sizeof(T) == 16)) CE_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of M and B differ", fn);
-  if (trans < 0 || trans > 2) CE_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: A1, 1: transpose(A1), 2: adjoint(A1))", fn, trans);
+  if (!M) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null hs_mod", fn);
+  if ((M->cx != 0) != (sizeof(T) == 16)) HS_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of M and B differ", fn);
+  if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: A1, 1: transpose(A1), 2: adjoint(A1))", fn, trans);
   if (n != M->n || nrhs < 0 || ldc < n || ldb < n)
-    CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: B has %lld rows (ldc %lld, ldb %lld, nrhs %lld), A1 is %lld x %lld", fn, (long long)n, (long long)ldc, (long long)ldb,
+    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: B has %lld rows (ldc %lld, ldb %lld, nrhs %lld), A1 is %lld x %lld", fn, (long long)n, (long long)ldc, (long long)ldb,
             (long long)nrhs, (long long)M->n, (long long)M->n);
 }
 
@@ -316,14 +314,14 @@ void ldiv_core(hs_mod* M, int trans, T* dC, int64_t ldc, const T* dB, int64_t ld
   const int KC = hs_ldiv_block_cols();
   // the intermediates (dT, dPart) are reused: a call queued on the same stream is ordered behind the last one by the stream, one on another
   // stream waits for it on the device
-  if (M->pending && s != M->last) CE_HIP(hipStreamWaitEvent(s, M->e1, 0));
+  if (M->pending && s != M->last) HS_HIP(hipStreamWaitEvent(s, M->e1, 0));
   M->last = s;
   if (trans != 0 && k > 0 && !M->dW) build_w<T>(M, s);
-  CE_HIP(hipEventRecord(M->e0, s));
+  HS_HIP(hipEventRecord(M->e0, s));
   for (int64_t c0 = 0; c0 < nrhs; c0 += KC) {
     const int kc = (int)std::min<int64_t>(KC, nrhs - c0);
     T* Y = dC + (size_t)c0 * ldc;
-    CE_CHECK(block_solve<T>(M->F, trans, Y, ldc, dB + (size_t)c0 * ldb, ldb, n, kc, s));
+    HS_CHECK(block_solve<T>(M->F, trans, Y, ldc, dB + (size_t)c0 * ldb, ldb, n, kc, s));
     ++M->solves;
     if (k == 0) continue;
     T* Tm = (T*)M->dT;
@@ -334,8 +332,8 @@ void ldiv_core(hs_mod* M, int trans, T* dC, int64_t ldc, const T* dB, int64_t ld
     launch_mod_cap_solve<T>((const T*)M->dLU, k, k, M->dPiv, trans, Tm, k, kc, s);
     launch_mod_apply<T>(Y, ldc, (const T*)(trans == 0 ? M->dZ : M->dW), n, Tm, k, n, k, kc, trans == 1, s);
   }
-  CE_HIP(hipEventRecord(M->e1, s));
-  CE_HIP(hipGetLastError());
+  HS_HIP(hipEventRecord(M->e1, s));
+  HS_HIP(hipGetLastError());
   M->pending = true;
 }
 
@@ -344,7 +342,7 @@ void ldiv_dev(hs_mod* M, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb
   const char* fn = "hs_mod_ldiv_dev_*";
   check_ldiv<T>(fn, M, trans, ldc, ldb, n, nrhs);
   if (nrhs == 0) return;
-  if (!dC || !dB) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
+  if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
   ldiv_core<T>(M, trans, dC, ldc, dB, ldb, nrhs, (hipStream_t)stream);
 }
 
@@ -353,21 +351,11 @@ void ldiv_host(hs_mod* M, int trans, T* C, int64_t ldc, const T* B, int64_t ldb,
   const char* fn = "hs_mod_ldiv_*";
   check_ldiv<T>(fn, M, trans, ldc, ldb, n, nrhs);
   if (nrhs == 0) return;
-  if (!C || !B) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
+  if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
   HsHandleView v;
   hs_handle_view(M->F, &v);
-  hipStream_t s = v.stream;
-  DevBuf tmp;
-  T* d = tmp.get<T>((size_t)n * nrhs);
-  CE_HIP(hipMemcpy2DAsync(d, n * sizeof(T), B, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
-  try {
-    ldiv_core<T>(M, trans, d, n, d, n, nrhs, s);
-    CE_HIP(hipMemcpy2DAsync(C, ldc * sizeof(T), d, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, s));
-    CE_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    throw;
-  }
+  HsDevBuf tmp("condest workspace");
+  hs_stage_block_on<T>(v.stream, tmp.get<T>((size_t)n * nrhs), C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { ldiv_core<T>(M, trans, d, ld, d, ld, nrhs, s); });
 }
 
 }  // namespace
@@ -380,35 +368,24 @@ int hs_mod_apply_prec(hs_mod* M, int trans, void* dC, int64_t ldc, const void* d
 hs_handle* hs_mod_handle(hs_mod* M) { return M ? M->F : nullptr; }
 
 extern "C" int hs_mod_create_d(hs_handle* F, int64_t n, int64_t k, const double* U, int64_t ldu, const double* V, int64_t ldv, hs_mod** M) {
-  CE_GUARD(create_dense<double>(F, n, k, U, ldu, V, ldv, false, nullptr, M));
+  HS_GUARD(create_dense<double>(F, n, k, U, ldu, V, ldv, false, nullptr, M));
 }
 extern "C" int hs_mod_create_z(hs_handle* F, int64_t n, int64_t k, const double* U, int64_t ldu, const double* V, int64_t ldv, hs_mod** M) {
-  CE_GUARD(create_dense<cplx>(F, n, k, (const cplx*)U, ldu, (const cplx*)V, ldv, false, nullptr, M));
+  HS_GUARD(create_dense<cplx>(F, n, k, (const cplx*)U, ldu, (const cplx*)V, ldv, false, nullptr, M));
 }
 extern "C" int hs_mod_create_dev_d(hs_handle* F, int64_t n, int64_t k, const double* dU, int64_t ldu, const double* dV, int64_t ldv, void* stream, hs_mod** M) {
-  CE_GUARD(create_dense<double>(F, n, k, dU, ldu, dV, ldv, true, stream, M));
+  HS_GUARD(create_dense<double>(F, n, k, dU, ldu, dV, ldv, true, stream, M));
 }
 extern "C" int hs_mod_create_dev_z(hs_handle* F, int64_t n, int64_t k, const double* dU, int64_t ldu, const double* dV, int64_t ldv, void* stream, hs_mod** M) {
-  CE_GUARD(create_dense<cplx>(F, n, k, (const cplx*)dU, ldu, (const cplx*)dV, ldv, true, stream, M));
+  HS_GUARD(create_dense<cplx>(F, n, k, (const cplx*)dU, ldu, (const cplx*)dV, ldv, true, stream, M));
 }
 extern "C" int hs_mod_create_sparse_d(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, hs_mod** M) {
-  CE_GUARD(create_sparse<double>(F, n, colptr, rowval, nzval, M));
+  HS_GUARD(create_sparse<double>(F, n, colptr, rowval, nzval, M));
 }
 extern "C" int hs_mod_create_sparse_z(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, hs_mod** M) {
-  CE_GUARD(create_sparse<cplx>(F, n, colptr, rowval, (const cplx*)nzval, M));
+  HS_GUARD(create_sparse<cplx>(F, n, colptr, rowval, (const cplx*)nzval, M));
 }
-extern "C" int hs_mod_ldiv_d(hs_mod* M, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  CE_GUARD(ldiv_host<double>(M, trans, C, ldc, B, ldb, n, nrhs));
-}
-extern "C" int hs_mod_ldiv_z(hs_mod* M, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs) {
-  CE_GUARD(ldiv_host<cplx>(M, trans, (cplx*)C, ldc, (const cplx*)B, ldb, n, nrhs));
-}
-extern "C" int hs_mod_ldiv_dev_d(hs_mod* M, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  CE_GUARD(ldiv_dev<double>(M, trans, dC, ldc, dB, ldb, n, nrhs, stream));
-}
-extern "C" int hs_mod_ldiv_dev_z(hs_mod* M, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
-  CE_GUARD(ldiv_dev<cplx>(M, trans, (cplx*)dC, ldc, (const cplx*)dB, ldb, n, nrhs, stream));
-}
+HS_LDIV_FAMILY(hs_mod, hs_mod_ldiv, hs_mod_ldiv_dev, ldiv_host, ldiv_dev)
 extern "C" int hs_mod_info(hs_mod* M, double* out8) {
   if (!M || !out8) {
     hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_mod_info: null argument");

@@ -41,14 +41,14 @@ struct HostIo {
   void upload(void* dst, const void* src, size_t bytes) {
     if (!bytes) return;
     pending.emplace_back((const char*)src, (const char*)src + bytes);
-    CE_HIP(hipMemcpyAsync(dst, pending.back().data(), bytes, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(dst, pending.back().data(), bytes, hipMemcpyHostToDevice, s));
   }
   void read(const void* d, size_t cnt) {
     if (hd.size() < cnt) hd.resize(cnt);
-    CE_HIP(hipMemcpyAsync(hd.data(), d, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
-    CE_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipMemcpyAsync(hd.data(), d, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
     pending.clear();
-    CE_CHECK(hs_handle_flow_check(F));
+    HS_CHECK(hs_handle_flow_check(F));
   }
 };
 
@@ -375,7 +375,7 @@ struct EstWork {
     return 5 * t * (size_t)n * sizeof(T) + nblk * (t * sizeof(double) + MAXT * (sizeof(double) + sizeof(long long)) + sizeof(double)) + Dim::RES * sizeof(double) +
            (Dim::HIST + 1 + MAXT) * sizeof(long long) + 2 * MAXT * MAXT * sizeof(unsigned long long) + sizeof(int) + sizeof(int2);
   }
-  void alloc(DevBuf& buf, int64_t n_, int t_, size_t ne) {
+  void alloc(HsDevBuf& buf, int64_t n_, int t_, size_t ne) {
     n = n_;
     t = t_;
     nblk = (int)nbrows(n);
@@ -410,7 +410,7 @@ void est_run(HostIo& io, EstWork<T, MAXT> w, int64_t seed, int fwd, const double
   const int64_t n = w.n;
   const int t = w.t, nblk = w.nblk;
   if (t < 1 || t > MAXT || t > n || itmax < 1 || itmax > Dim::ITMAX)
-    CE_FAIL(HS_ERR_ARGUMENT, t, "ArgumentError: the 1-norm estimator takes t in 1:min(%d, n) and itmax in 1:%d, got t = %d, itmax = %d", MAXT, Dim::ITMAX, t, itmax);
+    HS_FAIL(HS_ERR_ARGUMENT, t, "ArgumentError: the 1-norm estimator takes t in 1:min(%d, n) and itmax in 1:%d, got t = %d, itmax = %d", MAXT, Dim::ITMAX, t, itmax);
   hipStream_t s = io.s;
   const unsigned gn = nb256(n);
   const bool real = sizeof(T) == 8;
@@ -440,7 +440,7 @@ void est_run(HostIo& io, EstWork<T, MAXT> w, int64_t seed, int fwd, const double
     const int np = (j1 - j0) * 2 * t;
     const size_t cnt = L.size() * (size_t)np;
     set_act(L);
-    CE_HIP(hipMemsetAsync(w.dots, 0, sizeof(unsigned long long) * cnt, s));
+    HS_HIP(hipMemsetAsync(w.dots, 0, sizeof(unsigned long long) * cnt, s));
     hipLaunchKernelGGL(est_pm_dots_kernel, dim3(nblk, (unsigned)cnt), dim3(256), 0, s, (const double*)w.S, (const double*)w.So, n, t, j0, np, (const int2*)w.act,
                        w.dots);
     io.read(w.dots, cnt);
@@ -450,7 +450,7 @@ void est_run(HostIo& io, EstWork<T, MAXT> w, int64_t seed, int fwd, const double
   };
   // 1. start
   hipLaunchKernelGGL(est_init_kernel<T>, dim3(gn, ne), dim3(256), 0, s, w.X, n, t, seed, 1.0 / (double)n);
-  CE_HIP(hipMemsetAsync(w.hcnt, 0, sizeof(int) * (size_t)ne, s));
+  HS_HIP(hipMemsetAsync(w.hcnt, 0, sizeof(int) * (size_t)ne, s));
   for (int k = 1; !A.empty(); ++k) {
     // 2. Y = B X, est = max_j ||Y[:, j]||_1, for every active estimator with one application
     int na = (int)A.size();

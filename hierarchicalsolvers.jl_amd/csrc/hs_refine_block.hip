@@ -195,9 +195,9 @@ struct Driver {
 
   void bsolve(int tr, T* X, int64_t ld, int64_t nc) {
     if (sizeof(T) == 16)
-      CE_CHECK(hs_ldiv_block_dev_t_z(F, tr, (double*)X, ld, (const double*)X, ld, v.n, nc, (void*)s));
+      HS_CHECK(hs_ldiv_block_dev_t_z(F, tr, (double*)X, ld, (const double*)X, ld, v.n, nc, (void*)s));
     else
-      CE_CHECK(hs_ldiv_block_dev_t_d(F, tr, (double*)X, ld, (const double*)X, ld, v.n, nc, (void*)s));
+      HS_CHECK(hs_ldiv_block_dev_t_d(F, tr, (double*)X, ld, (const double*)X, ld, v.n, nc, (void*)s));
     g_info[RI_SOLVES] += 1;
     g_info[RI_COL_APPS] += (double)nc;
   }
@@ -230,7 +230,7 @@ struct Driver {
     io.upload(ws.col, hcol.data(), sizeof(int64_t) * (size_t)gc);
     io.upload(ws.vcol, hv.data(), sizeof(int) * (size_t)gc);
     // x = op(F) \ b
-    CE_HIP(hipMemcpy2DAsync(X + (size_t)g0 * ldx, sizeof(T) * (size_t)ldx, B + (size_t)g0 * ldb, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)gc,
+    HS_HIP(hipMemcpy2DAsync(X + (size_t)g0 * ldx, sizeof(T) * (size_t)ldx, B + (size_t)g0 * ldb, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)gc,
                             hipMemcpyDeviceToDevice, s));
     bsolve(trans, X + (size_t)g0 * ldx, ldx, gc);
     for (;;) {
@@ -298,19 +298,19 @@ int64_t group_width(size_t per_col, int64_t nrhs) {
     if (w > 0) return std::min<int64_t>(all, (w + KC - 1) / KC * KC);
   }
   size_t fr = 0, tot = 0;
-  CE_HIP(hipMemGetInfo(&fr, &tot));
+  HS_HIP(hipMemGetInfo(&fr, &tot));
   const int64_t fit = (int64_t)(fr / 2 / per_col);
   if (fit >= all) return all;
   const int64_t least = std::min<int64_t>(KC, nrhs);
   if (fit < least)
-    CE_FAIL(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_ldiv_refine_block_* needs %zu bytes for one group of %lld columns, half of the free device memory is %zu bytes",
+    HS_FAIL(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_ldiv_refine_block_* needs %zu bytes for one group of %lld columns, half of the free device memory is %zu bytes",
             per_col * (size_t)least, (long long)least, fr / 2);
   return std::max<int64_t>(fit / KC * KC, least);
 }
 
 template <class T>
 void refine_block_dev(hs_handle* F, const HsHandleView& v, int trans, T* dX, int64_t ldx, const T* dB, int64_t ldb, int64_t nrhs, int64_t itmax, double* berr,
-                      double* ferr, int64_t* steps, hipStream_t s, DevBuf& buf) {
+                      double* ferr, int64_t* steps, hipStream_t s, HsDevBuf& buf) {
   const int64_t n = v.n;
   Driver<T> d{F, v, s, trans};
   d.A = op_rows<T>(v, trans, s);
@@ -331,29 +331,19 @@ void refine_block_dev(hs_handle* F, const HsHandleView& v, int trans, T* dX, int
   ws.vcol = buf.get<int>(G);
   if (ferr) ws.est.alloc(buf, n, (int)std::min<int64_t>(RB_T, n), G);
   g_info[RI_WORK_BYTES] = (double)(per_col * G);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  try {
-    CE_HIP(hipEventCreate(&e0));
-    CE_HIP(hipEventCreate(&e1));
-    CE_HIP(hipEventRecord(e0, s));
-    for (int64_t g0 = 0; g0 < nrhs; g0 += ws.G) {
-      d.group(dX, ldx, dB, ldb, g0, (int)std::min<int64_t>(ws.G, nrhs - g0), itmax, berr, ferr, steps);
-      g_info[RI_GROUPS] += 1;
-    }
-    CE_HIP(hipEventRecord(e1, s));
-    CE_HIP(hipEventSynchronize(e1));
-    CE_CHECK(hs_handle_flow_check(F));
-    float ms = 0.f;
-    CE_HIP(hipEventElapsedTime(&ms, e0, e1));
-    g_info[RI_SECONDS] = ms * 1e-3;
-  } catch (...) {
-    (void)hipStreamSynchronize(s);  // nothing in flight may outlive the workspace or the host sides of the uploads
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    throw;
+  HsEvents<2> ev;
+  HsDrain drain{s};  // nothing in flight may outlive the workspace or the host sides of the uploads
+  HS_HIP(hipEventRecord(ev[0], s));
+  for (int64_t g0 = 0; g0 < nrhs; g0 += ws.G) {
+    d.group(dX, ldx, dB, ldb, g0, (int)std::min<int64_t>(ws.G, nrhs - g0), itmax, berr, ferr, steps);
+    g_info[RI_GROUPS] += 1;
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  HS_HIP(hipEventRecord(ev[1], s));
+  HS_HIP(hipEventSynchronize(ev[1]));
+  HS_CHECK(hs_handle_flow_check(F));
+  float ms = 0.f;
+  HS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  g_info[RI_SECONDS] = ms * 1e-3;
 }
 
 template <class T>
@@ -361,19 +351,19 @@ void refine_block_entry(hs_handle* F, int trans, T* X, int64_t ldx, const T* B, 
                         int64_t* steps, bool on_device, void* stream) {
   const char* fn = on_device ? "hs_ldiv_refine_block_dev_*" : "hs_ldiv_refine_block_*";
   // refusals: before any device work, X untouched
-  const HsHandleView v = view_of(F, fn);
+  const HsHandleView v = hs_view_of(F, fn);
   check_refine_args<T>(fn, v, trans, X, ldx, B, ldb, n, nrhs, itmax, berr, steps);
   check_no_alias<T>(fn, X, ldx, B, ldb, nrhs);
   // what hs_ldiv_block_t_* refuses, whatever trans and ferr are (a host-side plan names these too)
   if (v.nranks > 1)
-    CE_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: a factorization over %d ranks is not supported (single-rank factorizations only)", fn, v.nranks);
+    HS_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: a factorization over %d ranks is not supported (single-rank factorizations only)", fn, v.nranks);
   if (v.t_refused_node >= 0)
-    CE_FAIL(HS_ERR_UNSUPPORTED, v.t_refused_node,
+    HS_FAIL(HS_ERR_UNSUPPORTED, v.t_refused_node,
             "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): block solves and transposed ULV solves are not implemented; "
             "hs_ldiv_refine_* serves this handle with trans = 0 and without ferr",
             fn, v.t_refused_node);
-  if (!v.device) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
-  if (!v.factored) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
+  if (!v.device) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
+  if (!v.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
   {  // whatever else the block solve refuses is refused here: nothing is silently looped
     const int st = sizeof(T) == 16 ? hs_ldiv_block_dev_t_z(F, trans, nullptr, n, nullptr, n, n, 0, nullptr) : hs_ldiv_block_dev_t_d(F, trans, nullptr, n, nullptr, n, n, 0, nullptr);
     if (st != HS_OK) {
@@ -384,26 +374,22 @@ void refine_block_entry(hs_handle* F, int trans, T* X, int64_t ldx, const T* B, 
   }
   for (double& x : g_info) x = 0.0;
   if (nrhs == 0) return;
-  DevBuf buf;  // freed after the stream is drained, on every path
+  HsDevBuf buf("condest workspace");  // freed after the stream is drained, on every path
   if (on_device) return refine_block_dev<T>(F, v, trans, X, ldx, B, ldb, nrhs, itmax, berr, ferr, steps, (hipStream_t)stream, buf);
   hipStream_t s = v.stream;
   T* dX = buf.get<T>((size_t)n * nrhs);
   T* dB = buf.get<T>((size_t)n * nrhs);
-  try {
-    CE_HIP(hipMemcpy2DAsync(dB, sizeof(T) * n, B, sizeof(T) * ldb, sizeof(T) * n, nrhs, hipMemcpyHostToDevice, s));
-    // results go to the caller's arrays only when the whole call succeeded
-    std::vector<double> be((size_t)nrhs), fe((size_t)nrhs);
-    std::vector<int64_t> st((size_t)nrhs);
-    refine_block_dev<T>(F, v, trans, dX, n, dB, n, nrhs, itmax, be.data(), ferr ? fe.data() : nullptr, st.data(), s, buf);
-    CE_HIP(hipMemcpy2DAsync(X, sizeof(T) * ldx, dX, sizeof(T) * n, sizeof(T) * n, nrhs, hipMemcpyDeviceToHost, s));
-    CE_HIP(hipStreamSynchronize(s));
-    std::copy(be.begin(), be.end(), berr);
-    if (ferr) std::copy(fe.begin(), fe.end(), ferr);
-    std::copy(st.begin(), st.end(), steps);
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    throw;
-  }
+  HsDrain drain{s};
+  HS_HIP(hipMemcpy2DAsync(dB, sizeof(T) * n, B, sizeof(T) * ldb, sizeof(T) * n, nrhs, hipMemcpyHostToDevice, s));
+  // results go to the caller's arrays only when the whole call succeeded
+  std::vector<double> be((size_t)nrhs), fe((size_t)nrhs);
+  std::vector<int64_t> st((size_t)nrhs);
+  refine_block_dev<T>(F, v, trans, dX, n, dB, n, nrhs, itmax, be.data(), ferr ? fe.data() : nullptr, st.data(), s, buf);
+  HS_HIP(hipMemcpy2DAsync(X, sizeof(T) * ldx, dX, sizeof(T) * n, sizeof(T) * n, nrhs, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  std::copy(be.begin(), be.end(), berr);
+  if (ferr) std::copy(fe.begin(), fe.end(), ferr);
+  std::copy(st.begin(), st.end(), steps);
 }
 
 }  // namespace
@@ -411,19 +397,19 @@ void refine_block_entry(hs_handle* F, int trans, T* X, int64_t ldx, const T* B, 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------------
 extern "C" int hs_ldiv_refine_block_d(hs_handle* F, int trans, double* X, int64_t ldx, const double* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                                       double* berr, double* ferr, int64_t* steps) {
-  CE_GUARD(refine_block_entry<double>(F, trans, X, ldx, B, ldb, n, nrhs, itmax, berr, ferr, steps, false, nullptr));
+  HS_GUARD(refine_block_entry<double>(F, trans, X, ldx, B, ldb, n, nrhs, itmax, berr, ferr, steps, false, nullptr));
 }
 extern "C" int hs_ldiv_refine_block_z(hs_handle* F, int trans, double* X, int64_t ldx, const double* B, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                                       double* berr, double* ferr, int64_t* steps) {
-  CE_GUARD(refine_block_entry<cplx>(F, trans, (cplx*)X, ldx, (const cplx*)B, ldb, n, nrhs, itmax, berr, ferr, steps, false, nullptr));
+  HS_GUARD(refine_block_entry<cplx>(F, trans, (cplx*)X, ldx, (const cplx*)B, ldb, n, nrhs, itmax, berr, ferr, steps, false, nullptr));
 }
 extern "C" int hs_ldiv_refine_block_dev_d(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                                           double* berr, double* ferr, int64_t* steps, void* stream) {
-  CE_GUARD(refine_block_entry<double>(F, trans, dX, ldx, dB, ldb, n, nrhs, itmax, berr, ferr, steps, true, stream));
+  HS_GUARD(refine_block_entry<double>(F, trans, dX, ldx, dB, ldb, n, nrhs, itmax, berr, ferr, steps, true, stream));
 }
 extern "C" int hs_ldiv_refine_block_dev_z(hs_handle* F, int trans, double* dX, int64_t ldx, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, int64_t itmax,
                                           double* berr, double* ferr, int64_t* steps, void* stream) {
-  CE_GUARD(refine_block_entry<cplx>(F, trans, (cplx*)dX, ldx, (const cplx*)dB, ldb, n, nrhs, itmax, berr, ferr, steps, true, stream));
+  HS_GUARD(refine_block_entry<cplx>(F, trans, (cplx*)dX, ldx, (const cplx*)dB, ldb, n, nrhs, itmax, berr, ferr, steps, true, stream));
 }
 extern "C" int hs_ldiv_refine_block_info(double* out8) {
   if (!out8) {

@@ -44,9 +44,6 @@ struct HsSelView {
 };
 
 void hs_selinv_view(hs_handle* h, HsSelView* v);
-// device scratch through the library's arena cache (a parked block of about that size, else hipMalloc with the library's retry); throws on failure
-void* hs_scratch_take(size_t bytes, const char* what);
-void hs_scratch_give(void* p, size_t bytes);
 
 // ---- kernels_selinv.hip ---------------------------------------------------------------------------------------------------------------
 struct LogdetFront {  // input of the log-determinant reduction

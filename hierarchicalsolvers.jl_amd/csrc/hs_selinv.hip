@@ -30,52 +30,13 @@
 
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
+#include "hs_host.h"
 #include "hs_selinv.h"
 
 namespace {
 
-#define SI_FAIL(code, info, ...)               \
-  do {                                         \
-    hs_set_error((code), (info), __VA_ARGS__); \
-    throw (int)(code);                         \
-  } while (0)
-#define SI_HIP(call)                                                                                                                \
-  do {                                                                                                                              \
-    hipError_t e__ = (call);                                                                                                        \
-    if (e__ != hipSuccess) SI_FAIL(HS_ERR_DEVICE, 0, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-  } while (0)
-#define SI_GUARD(...)                                        \
-  try {                                                      \
-    __VA_ARGS__;                                             \
-    return HS_OK;                                            \
-  } catch (int code) {                                       \
-    return code;                                             \
-  } catch (const std::bad_alloc&) {                          \
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed"); \
-    return HS_ERR_NOMEM;                                     \
-  }
-
 inline int rup2(int x) { return (std::max(x, 1) + 1) / 2 * 2; }
 inline size_t rup32(size_t x) { return (x + 31) / 32 * 32; }
-
-struct DevBuf {  // a device block from the library's arena cache, given back on scope exit
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void take(size_t b, const char* what) {
-    give();
-    p = hs_scratch_take(b, what);
-    bytes = b;
-  }
-  void give() {
-    if (p) hs_scratch_give(p, bytes);
-    p = nullptr;
-    bytes = 0;
-  }
-  ~DevBuf() { give(); }
-};
 
 // What the first hs_selinv call of a handle builds and keeps: which front owns which stored entry of A, and where every front's boundary
 // sits in its parent's front.  Both depend on the pattern and the tree only.
@@ -112,8 +73,8 @@ void build_cache(const HsSelView& v, SelCache* c) {
   const int64_t n = v.n, nnz = v.nnz;
   std::vector<int64_t> cp((size_t)n + 1);
   std::vector<int32_t> rv((size_t)std::max<int64_t>(nnz, 1));
-  SI_HIP(hipMemcpy(cp.data(), v.colptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (nnz) SI_HIP(hipMemcpy(rv.data(), v.rowval, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HS_HIP(hipMemcpy(cp.data(), v.colptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (nnz) HS_HIP(hipMemcpy(rv.data(), v.rowval, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
   // the front that eliminates each DOF
   std::vector<int> elim((size_t)n, -1);
   for (int f = 0; f < nf; ++f) {
@@ -194,28 +155,28 @@ void build_cache(const HsSelView& v, SelCache* c) {
     if (v.fronts[f].parent < 0 && v.fronts[f].nb > 0 && c->hole_front < 0) c->hole_front = f;
   if (c->hole < 0 && c->hole_front < 0) {
     const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
-    SI_HIP(hipMalloc((void**)&c->d_epr, ne * sizeof(int)));
-    SI_HIP(hipMalloc((void**)&c->d_epc, ne * sizeof(int)));
-    SI_HIP(hipMalloc((void**)&c->d_ee, ne * sizeof(int64_t)));
-    SI_HIP(hipMalloc((void**)&c->d_cmap, cm.size() * sizeof(int)));
-    SI_HIP(hipMemcpy(c->d_epr, epr.data(), ne * sizeof(int), hipMemcpyHostToDevice));
-    SI_HIP(hipMemcpy(c->d_epc, epc.data(), ne * sizeof(int), hipMemcpyHostToDevice));
-    SI_HIP(hipMemcpy(c->d_ee, ee.data(), ne * sizeof(int64_t), hipMemcpyHostToDevice));
-    SI_HIP(hipMemcpy(c->d_cmap, cm.data(), cm.size() * sizeof(int), hipMemcpyHostToDevice));
+    HS_HIP(hipMalloc((void**)&c->d_epr, ne * sizeof(int)));
+    HS_HIP(hipMalloc((void**)&c->d_epc, ne * sizeof(int)));
+    HS_HIP(hipMalloc((void**)&c->d_ee, ne * sizeof(int64_t)));
+    HS_HIP(hipMalloc((void**)&c->d_cmap, cm.size() * sizeof(int)));
+    HS_HIP(hipMemcpy(c->d_epr, epr.data(), ne * sizeof(int), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(c->d_epc, epc.data(), ne * sizeof(int), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(c->d_ee, ee.data(), ne * sizeof(int64_t), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(c->d_cmap, cm.data(), cm.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   c->built = true;
 }
 
 // ---- checks shared by the entry points: everything here happens before any device work ---------------------------------------------
 void check_common(hs_handle* F, HsSelView& v, const char* fn) {
-  if (!F) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
+  if (!F) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
   hs_selinv_view(F, &v);
   if (v.nranks > 1)
-    SI_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: the factorization is spread over %d ranks; this call needs all fronts in one process", fn, v.nranks);
-  if (!v.device || !v.factored) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs a completed numeric factorization (the handle is a plan, or hs_numeric_end has not run)", fn);
+    HS_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: the factorization is spread over %d ranks; this call needs all fronts in one process", fn, v.nranks);
+  if (!v.device || !v.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs a completed numeric factorization (the handle is a plan, or hs_numeric_end has not run)", fn);
   for (size_t i = 0; i < v.fronts.size(); ++i)
     if (v.fronts[i].flags & HS_SEL_NOLU)
-      SI_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d keeps its interior block D as an HSS matrix (ULV factors; hs_options.hss_d, mf = 2, 3): it has no pivoted LU whose diagonal could be read", fn, (int)i);
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d keeps its interior block D as an HSS matrix (ULV factors; hs_options.hss_d, mf = 2, 3): it has no pivoted LU whose diagonal could be read", fn, (int)i);
 }
 
 // ---- log-determinant ------------------------------------------------------------------------------------------------------------------
@@ -229,16 +190,16 @@ void logabsdet_impl(const HsSelView& v, double* logabs, double* sign2) {
   long long flips = 0;
   bool zero = false;
   if (nf > 0) {
-    DevBuf din, dout;
+    HsScratch din, dout;
     din.take(sizeof(LogdetFront) * (size_t)nf, "log-determinant descriptors");
     dout.take(sizeof(LogdetOut) * (size_t)nf, "log-determinant partial results");
     std::vector<LogdetOut> out((size_t)nf);
-    SI_HIP(hipStreamSynchronize(v.stream));  // the factors are written on the handle's stream
-    SI_HIP(hipMemcpy(din.p, lf.data(), sizeof(LogdetFront) * (size_t)nf, hipMemcpyHostToDevice));
+    HS_HIP(hipStreamSynchronize(v.stream));  // the factors are written on the handle's stream
+    HS_HIP(hipMemcpy(din.p, lf.data(), sizeof(LogdetFront) * (size_t)nf, hipMemcpyHostToDevice));
     launch_logdet<T>((const LogdetFront*)din.p, nf, (LogdetOut*)dout.p, v.stream);
-    SI_HIP(hipGetLastError());
-    SI_HIP(hipStreamSynchronize(v.stream));
-    SI_HIP(hipMemcpy(out.data(), dout.p, sizeof(LogdetOut) * (size_t)nf, hipMemcpyDeviceToHost));
+    HS_HIP(hipGetLastError());
+    HS_HIP(hipStreamSynchronize(v.stream));
+    HS_HIP(hipMemcpy(out.data(), dout.p, sizeof(LogdetOut) * (size_t)nf, hipMemcpyDeviceToHost));
     const double twopi = 6.283185307179586476925286766559;
     for (int i = 0; i < nf; ++i) {  // post-order, always the same
       la += out[(size_t)i].logabs;
@@ -282,12 +243,12 @@ struct SelRun {
   size_t alive = 0, peak = 0;
   double flops = 0.0;
   int batches = 0;
-  DevBuf work, descs;  // work blocks and descriptors of the current batch (reused, grown on demand)
+  HsScratch work, descs;  // work blocks and descriptors of the current batch (reused, grown on demand)
 
   struct Batch {
     std::vector<int> fronts;
     std::vector<size_t> zoff;  // element offset of every front's block
-    DevBuf Z;
+    HsScratch Z;
     int pending = 0;  // batches of children that still have to gather from Z
   };
 
@@ -490,24 +451,24 @@ struct SelRun {
     if (descs.bytes < dbytes + pbytes + 256) descs.take(2 * (dbytes + pbytes) + 256, "descriptors of the selected inversion");
     SelDesc<T>* dD = (SelDesc<T>*)descs.p;
     GemmProb<T>* dP = (GemmProb<T>*)((char*)descs.p + (dbytes + 255) / 256 * 256);
-    SI_HIP(hipMemcpy(dD, D.data(), dbytes, hipMemcpyHostToDevice));  // (the stream is idle: every batch ends with a synchronisation)
-    if (!P.empty()) SI_HIP(hipMemcpy(dP, P.data(), sizeof(GemmProb<T>) * P.size(), hipMemcpyHostToDevice));
-    SI_HIP(hipMemsetAsync(W, 0, wtot * sizeof(T), s));
+    HS_HIP(hipMemcpy(dD, D.data(), dbytes, hipMemcpyHostToDevice));  // (the stream is idle: every batch ends with a synchronisation)
+    if (!P.empty()) HS_HIP(hipMemcpy(dP, P.data(), sizeof(GemmProb<T>) * P.size(), hipMemcpyHostToDevice));
+    HS_HIP(hipMemsetAsync(W, 0, wtot * sizeof(T), s));
     launch_zinit<T>(dD, nbt, maxni, s);
     if (parent) launch_zgather<T>(dD, nbt, maxnb, s);
     for (const Launch& l : L) launch_gemm_probs<T>(dP + l.off, l.cnt, l.maxM, l.maxN, l.minus, s);
     launch_zpermute_cols<T>(dD, nbt, maxm, maxni, s);
     launch_zextract<T>(dD, nbt, maxni, maxe, trans, d_diag, d_zval, s);
-    SI_HIP(hipGetLastError());
-    SI_HIP(hipStreamSynchronize(s));
+    HS_HIP(hipGetLastError());
+    HS_HIP(hipStreamSynchronize(s));
   }
 };
 
 template <class T>
 void selinv_impl(const HsSelView& v, SelCache* c, int trans, void* diag, void* zval, int where, int64_t budget_bytes, hipStream_t s) {
   const int nf = (int)v.fronts.size();
-  SI_HIP(hipStreamSynchronize(v.stream));  // the factors are written on the handle's stream
-  DevBuf odiag, ozval;
+  HS_HIP(hipStreamSynchronize(v.stream));  // the factors are written on the handle's stream
+  HsScratch odiag, ozval;
   T *d_diag = nullptr, *d_zval = nullptr;
   if (diag) {
     if (where) d_diag = (T*)diag;
@@ -526,7 +487,7 @@ void selinv_impl(const HsSelView& v, SelCache* c, int trans, void* diag, void* z
   size_t budget = (size_t)std::max<int64_t>(budget_bytes, 0);
   if (budget == 0) {  // what the device can give right now, with a margin for the allocator
     size_t fr = 0, tot = 0;
-    SI_HIP(hipMemGetInfo(&fr, &tot));
+    HS_HIP(hipMemGetInfo(&fr, &tot));
     budget = (size_t)((double)fr * 0.85) + (v.sb ? v.sb_bytes : 0);
   }
   SelRun<T> R{v, c, s, trans, d_diag, d_zval, budget};
@@ -536,29 +497,16 @@ void selinv_impl(const HsSelView& v, SelCache* c, int trans, void* diag, void* z
     if (v.fronts[f].parent >= 0) R.kids[(size_t)v.fronts[f].parent].push_back(f);
     else roots.push_back(f);
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  SI_HIP(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) {
-    (void)hipEventDestroy(e0);
-    SI_FAIL(HS_ERR_DEVICE, 0, "hipEventCreate failed");
-  }
+  HsEvents<2> ev;
+  HsDrain drain{s};  // nothing may still be reading the blocks the unwinding gives back
   float ms = 0.f;
-  try {
-    SI_HIP(hipEventRecord(e0, s));
-    R.run_level(roots, nullptr, nullptr);
-    SI_HIP(hipEventRecord(e1, s));
-    SI_HIP(hipEventSynchronize(e1));
-    SI_HIP(hipEventElapsedTime(&ms, e0, e1));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);  // nothing may still be reading the blocks the unwinding gives back
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    throw;
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (diag && !where) SI_HIP(hipMemcpy(diag, d_diag, sizeof(T) * (size_t)v.n, hipMemcpyDeviceToHost));
-  if (zval && !where && v.nnz) SI_HIP(hipMemcpy(zval, d_zval, sizeof(T) * (size_t)v.nnz, hipMemcpyDeviceToHost));
+  HS_HIP(hipEventRecord(ev[0], s));
+  R.run_level(roots, nullptr, nullptr);
+  HS_HIP(hipEventRecord(ev[1], s));
+  HS_HIP(hipEventSynchronize(ev[1]));
+  HS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  if (diag && !where) HS_HIP(hipMemcpy(diag, d_diag, sizeof(T) * (size_t)v.n, hipMemcpyDeviceToHost));
+  if (zval && !where && v.nnz) HS_HIP(hipMemcpy(zval, d_zval, sizeof(T) * (size_t)v.nnz, hipMemcpyDeviceToHost));
   c->info[0] = ms * 1e-3;
   c->info[1] = R.flops;
   c->info[2] = (double)R.peak;
@@ -568,37 +516,37 @@ void selinv_impl(const HsSelView& v, SelCache* c, int trans, void* diag, void* z
 }  // namespace
 
 extern "C" int hs_logabsdet(hs_handle* F, double* logabs, double* sign2) {
-  SI_GUARD(HsSelView v; check_common(F, v, "hs_logabsdet");
-           if (!logabs || !sign2) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_logabsdet: logabs and sign2 must not be NULL");
+  HS_GUARD(HsSelView v; check_common(F, v, "hs_logabsdet");
+           if (!logabs || !sign2) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_logabsdet: logabs and sign2 must not be NULL");
            if (v.is_complex) logabsdet_impl<cplx>(v, logabs, sign2); else logabsdet_impl<double>(v, logabs, sign2));
 }
 
 extern "C" int hs_selinv(hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream) {
-  SI_GUARD(HsSelView v; check_common(F, v, "hs_selinv");
-           if (trans != 0 && trans != 1) SI_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_selinv: trans = %d must be 0 (entries of A^-1) or 1 (of its transpose)", trans);
-           if (where != 0 && where != 1) SI_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: hs_selinv: where = %d must be 0 (host pointers) or 1 (device pointers)", where);
-           if (!diag && !zval) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_selinv: diag and zval are both NULL, nothing to compute");
-           if (budget_bytes < 0) SI_FAIL(HS_ERR_ARGUMENT, budget_bytes, "ArgumentError: hs_selinv: budget_bytes < 0");
+  HS_GUARD(HsSelView v; check_common(F, v, "hs_selinv");
+           if (trans != 0 && trans != 1) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_selinv: trans = %d must be 0 (entries of A^-1) or 1 (of its transpose)", trans);
+           if (where != 0 && where != 1) HS_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: hs_selinv: where = %d must be 0 (host pointers) or 1 (device pointers)", where);
+           if (!diag && !zval) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_selinv: diag and zval are both NULL, nothing to compute");
+           if (budget_bytes < 0) HS_FAIL(HS_ERR_ARGUMENT, budget_bytes, "ArgumentError: hs_selinv: budget_bytes < 0");
            for (size_t i = 0; i < v.fronts.size(); ++i) {
              const int fl = v.fronts[i].flags;
              if (fl & HS_SEL_LOWRANK)
-               SI_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_selinv: front %d keeps low-rank Gauss transforms L / R (compressed factorization); selected inversion needs the exact path (swlevel = 0)", (int)i);
+               HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_selinv: front %d keeps low-rank Gauss transforms L / R (compressed factorization); selected inversion needs the exact path (swlevel = 0)", (int)i);
              if (fl & HS_SEL_SLICE)
-               SI_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_selinv: front %d is eliminated in slices (hs_options.split)", (int)i);
+               HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_selinv: front %d is eliminated in slices (hs_options.split)", (int)i);
            }
            SelCache* c = cache_of(v);
            if (!c->built) build_cache(v, c);  // (host work and uploads of index lists only)
            if (c->hole >= 0)
-             SI_FAIL(HS_ERR_UNSUPPORTED, c->hole, "hs_selinv: stored entry %lld of A (CSC order) lies outside every front's [int; bnd] block: the tree does not cover A's pattern, the pattern values of the inverse would have a hole", c->hole);
+             HS_FAIL(HS_ERR_UNSUPPORTED, c->hole, "hs_selinv: stored entry %lld of A (CSC order) lies outside every front's [int; bnd] block: the tree does not cover A's pattern, the pattern values of the inverse would have a hole", c->hole);
            if (c->hole_front >= 0)
-             SI_FAIL(HS_ERR_UNSUPPORTED, c->hole_front, "hs_selinv: the boundary of front %d is not contained in its parent's front (a root that keeps a boundary without a pseudo-root, or an inconsistent tree)", c->hole_front);
+             HS_FAIL(HS_ERR_UNSUPPORTED, c->hole_front, "hs_selinv: the boundary of front %d is not contained in its parent's front (a root that keeps a boundary without a pseudo-root, or an inconsistent tree)", c->hole_front);
            hipStream_t s = stream ? (hipStream_t)stream : v.stream;
            if (v.is_complex) selinv_impl<cplx>(v, c, trans, diag, zval, where, budget_bytes, s);
            else selinv_impl<double>(v, c, trans, diag, zval, where, budget_bytes, s));
 }
 
 extern "C" int hs_selinv_info(const hs_handle* F, double* out4) {
-  SI_GUARD(if (!F || !out4) SI_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_selinv_info: null argument");
+  HS_GUARD(if (!F || !out4) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_selinv_info: null argument");
            HsSelView v; hs_selinv_view(const_cast<hs_handle*>(F), &v);
            const SelCache* c = (const SelCache*)*v.sx;
            for (int k = 0; k < 4; ++k) out4[k] = c ? c->info[k] : 0.0);

@@ -30,12 +30,10 @@
 
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
-#define HS_CONDEST_KERNELS
-#include "hs_condest.h"
+#include "hs_host.h"
+#pragma clang fp contract(off)  // host arithmetic only (no kernel lives here): the plain products and sums
 #include "hs_solve_multi.h"  // hs_ldiv_block_cols
 #include "hs_sens.h"
-
-using namespace hs_ce;
 
 namespace {
 
@@ -100,12 +98,12 @@ int64_t group_width(size_t per_col, int64_t nrhs) {
     if (w > 0) return std::min<int64_t>(all, (w + KC - 1) / KC * KC);
   }
   size_t fr = 0, tot = 0;
-  CE_HIP(hipMemGetInfo(&fr, &tot));
+  HS_HIP(hipMemGetInfo(&fr, &tot));
   const int64_t fit = (int64_t)(fr / 2 / per_col);
   if (fit >= all) return all;
   const int64_t least = std::min<int64_t>(KC, nrhs);
   if (fit < least)
-    CE_FAIL(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_sens_* needs %zu bytes for one group of %lld columns, half of the free device memory is %zu bytes",
+    HS_FAIL(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_sens_* needs %zu bytes for one group of %lld columns, half of the free device memory is %zu bytes",
             per_col * (size_t)least, (long long)least, fr / 2);
   return std::max<int64_t>(fit / KC * KC, least);
 }
@@ -113,7 +111,7 @@ int64_t group_width(size_t per_col, int64_t nrhs) {
 template <class T>
 struct Driver {
   const Call<T>& c;
-  DevBuf& buf;
+  HsDevBuf& buf;
   int64_t n, Gc = 0;
   T* Xg = nullptr;      // n x Gc
   T* Lg = nullptr;      // n x Gc: Lam, or M = conj(Lam) (ComplexF64, trans = 1)
@@ -145,9 +143,9 @@ struct Driver {
         const T* src = b.dense + (size_t)g0 * b.ld;
         if (cjin) {
           launch_sens_copy<T>(out, n, src, b.ld, n, gc, 1, s);
-          CE_CHECK(block_solve<T>(c.F, t, out, n, out, n, n, gc, s));
+          HS_CHECK(block_solve<T>(c.F, t, out, n, out, n, n, gc, s));
         } else {
-          CE_CHECK(block_solve<T>(c.F, t, out, n, src, b.ld, n, gc, s));
+          HS_CHECK(block_solve<T>(c.F, t, out, n, src, b.ld, n, gc, s));
         }
         return;
       }
@@ -156,7 +154,7 @@ struct Driver {
         launch_sens_copy<T>(vstage, cnt, val, cnt, cnt, 1, 1, s);
         val = vstage;
       }
-      CE_CHECK(sparse_solve<T>(c.F, t, n, gc, cp.data(), b.rowval + off, val, out, n, s));
+      HS_CHECK(sparse_solve<T>(c.F, t, n, gc, cp.data(), b.rowval + off, val, out, n, s));
       return;
     }
     const T* src;
@@ -170,7 +168,7 @@ struct Driver {
       if (!b.sparse()) {
         launch_sens_copy<T>(stage, n, b.dense + (size_t)g0 * b.ld, b.ld, n, gc, 1, s);
       } else {
-        CE_HIP(hipMemsetAsync(stage, 0, (size_t)n * gc * sizeof(T), s));
+        HS_HIP(hipMemsetAsync(stage, 0, (size_t)n * gc * sizeof(T), s));
         if (cnt > 0) {
           er.resize((size_t)cnt);
           ec.resize((size_t)cnt);
@@ -179,16 +177,16 @@ struct Driver {
               er[(size_t)e] = (int32_t)(b.rowval[off + e] - 1);
               ec[(size_t)e] = j;
             }
-          CE_HIP(hipStreamSynchronize(s));  // the lists of the previous expansion are no longer read
-          CE_HIP(hipMemcpy(d_er, er.data(), (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
-          CE_HIP(hipMemcpy(d_ec, ec.data(), (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
+          HS_HIP(hipStreamSynchronize(s));  // the lists of the previous expansion are no longer read
+          HS_HIP(hipMemcpy(d_er, er.data(), (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
+          HS_HIP(hipMemcpy(d_ec, ec.data(), (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
           launch_sens_expand<T>(stage, n, d_er, d_ec, b.nzval + off, cnt, cjin ? 1 : 0, s);
         }
       }
     }
     berr.resize((size_t)gc);
     steps.resize((size_t)gc);
-    CE_CHECK(refine_solve<T>(c.F, t, out, n, src, lds, n, gc, c.itmax, berr.data(), steps.data(), s));
+    HS_CHECK(refine_solve<T>(c.F, t, out, n, src, lds, n, gc, c.itmax, berr.data(), steps.data(), s));
   }
 
   void run(double* info) {
@@ -198,9 +196,9 @@ struct Driver {
     const bool cjw = cplx_ && c.trans == 1;  // the adjoint solve runs on conj(W) and returns conj(Lam)
     const int tadj = c.trans == 0 ? 2 : 0;
     const int64_t nnz = c.v.nnz, glen = c.pattern == 0 ? nnz : n;
-    CE_HIP(hipMemsetAsync(c.dG, 0, (size_t)glen * sizeof(T), s));
+    HS_HIP(hipMemsetAsync(c.dG, 0, (size_t)glen * sizeof(T), s));
     if (c.nrhs == 0) {
-      CE_HIP(hipStreamSynchronize(s));
+      HS_HIP(hipStreamSynchronize(s));
       return;
     }
     const bool wsparse = c.misfit || c.W.sparse();
@@ -253,8 +251,8 @@ struct Driver {
       Wv = buf.get<T>((size_t)(nr * Gc));
       extra += (size_t)nr * 2 * sizeof(int32_t);
       if (nr > 0) {
-        CE_HIP(hipMemcpy(d_rows, r0.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice));
-        CE_HIP(hipMemcpy(d_slot, slot.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice));
+        HS_HIP(hipMemcpy(d_rows, r0.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice));
+        HS_HIP(hipMemcpy(d_slot, slot.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice));
       }
       Wm.colptr = wcp.data();
       Wm.rowval = wrv.data();
@@ -266,61 +264,53 @@ struct Driver {
     fl.swap = c.trans != 0;
     fl.conjl = cplx_ && c.trans != 0;  // trans 1: L holds M = conj(Lam); trans 2: conj(Lam) is what the sum takes
     fl.conjr = cplx_ && c.trans != 2;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    try {
-      for (hipEvent_t& e : ev) CE_HIP(hipEventCreate(&e));
-      for (int64_t g0 = 0; g0 < c.nrhs; g0 += Gc) {
-        const int gc = (int)std::min<int64_t>(Gc, c.nrhs - g0);
-        CE_HIP(hipEventRecord(ev[0], s));
-        solve(c.trans, c.B, g0, gc, false, Xg);
-        CE_HIP(hipEventRecord(ev[1], s));
-        if (c.dX) CE_HIP(hipMemcpy2DAsync(c.dX + (size_t)g0 * c.ldx, c.ldx * sizeof(T), Xg, n * sizeof(T), n * sizeof(T), gc, hipMemcpyDeviceToDevice, s));
-        if (c.misfit)
-          launch_sens_misfit<T>(Xg, n, d_rows, d_slot, c.dD + (size_t)g0 * c.ldd, c.ldd, c.nrows, gc, c.dR ? c.dR + (size_t)g0 * c.ldr : nullptr, c.ldr, Wv, cjw ? 1 : 0,
-                                c.dJ + g0, s);
-        CE_HIP(hipEventRecord(ev[2], s));
-        if (c.misfit)
-          solve(tadj, Wm, 0, gc, false, Lg);  // the conjugation is in Wv already
-        else
-          solve(tadj, c.W, g0, gc, cjw, Lg);
-        CE_HIP(hipEventRecord(ev[3], s));
-        if (c.dLam) launch_sens_copy<T>(c.dLam + (size_t)g0 * c.ldl, c.ldl, Lg, n, n, gc, cjw ? 1 : 0, s);
-        if (c.pattern == 0)
-          launch_sddmm<T>(c.v.rowval, ecol, nnz, Lg, n, Xg, n, gc, fl, c.dG, s);
-        else
-          launch_sddmm_diag<T>(c.v.colptr, c.v.rowval, n, Lg, n, Xg, n, gc, fl, c.dG, s);
-        CE_HIP(hipEventRecord(ev[4], s));
-        CE_HIP(hipEventSynchronize(ev[4]));
-        CE_CHECK(hs_handle_flow_check(c.F));
-        float ms[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k = 0; k < 4; ++k) CE_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-        info[SI_FORWARD] += ms[0] * 1e-3;
-        info[SI_ADJOINT] += ms[2] * 1e-3;
-        info[SI_REDUCE] += (ms[1] + ms[3]) * 1e-3;
-        info[SI_SECONDS] += (ms[0] + ms[1] + ms[2] + ms[3]) * 1e-3;
-        info[SI_GROUPS] += 1;
-        info[SI_PRODUCTS] += (double)glen * gc;
-      }
-    } catch (...) {
-      (void)hipStreamSynchronize(s);  // nothing in flight may outlive the workspace
-      for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-      throw;
+    HsEvents<5> ev;
+    HsDrain drain{s};  // nothing in flight may outlive the workspace
+    for (int64_t g0 = 0; g0 < c.nrhs; g0 += Gc) {
+      const int gc = (int)std::min<int64_t>(Gc, c.nrhs - g0);
+      HS_HIP(hipEventRecord(ev[0], s));
+      solve(c.trans, c.B, g0, gc, false, Xg);
+      HS_HIP(hipEventRecord(ev[1], s));
+      if (c.dX) HS_HIP(hipMemcpy2DAsync(c.dX + (size_t)g0 * c.ldx, c.ldx * sizeof(T), Xg, n * sizeof(T), n * sizeof(T), gc, hipMemcpyDeviceToDevice, s));
+      if (c.misfit)
+        launch_sens_misfit<T>(Xg, n, d_rows, d_slot, c.dD + (size_t)g0 * c.ldd, c.ldd, c.nrows, gc, c.dR ? c.dR + (size_t)g0 * c.ldr : nullptr, c.ldr, Wv, cjw ? 1 : 0,
+                              c.dJ + g0, s);
+      HS_HIP(hipEventRecord(ev[2], s));
+      if (c.misfit)
+        solve(tadj, Wm, 0, gc, false, Lg);  // the conjugation is in Wv already
+      else
+        solve(tadj, c.W, g0, gc, cjw, Lg);
+      HS_HIP(hipEventRecord(ev[3], s));
+      if (c.dLam) launch_sens_copy<T>(c.dLam + (size_t)g0 * c.ldl, c.ldl, Lg, n, n, gc, cjw ? 1 : 0, s);
+      if (c.pattern == 0)
+        launch_sddmm<T>(c.v.rowval, ecol, nnz, Lg, n, Xg, n, gc, fl, c.dG, s);
+      else
+        launch_sddmm_diag<T>(c.v.colptr, c.v.rowval, n, Lg, n, Xg, n, gc, fl, c.dG, s);
+      HS_HIP(hipEventRecord(ev[4], s));
+      HS_HIP(hipEventSynchronize(ev[4]));
+      HS_CHECK(hs_handle_flow_check(c.F));
+      float ms[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < 4; ++k) HS_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+      info[SI_FORWARD] += ms[0] * 1e-3;
+      info[SI_ADJOINT] += ms[2] * 1e-3;
+      info[SI_REDUCE] += (ms[1] + ms[3]) * 1e-3;
+      info[SI_SECONDS] += (ms[0] + ms[1] + ms[2] + ms[3]) * 1e-3;
+      info[SI_GROUPS] += 1;
+      info[SI_PRODUCTS] += (double)glen * gc;
     }
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   }
 };
 
 // ---- refusals: before any device work, every output untouched ------------------------------------------------------------------------
 template <class T>
 void check_block(hs_handle* F, int trans, const char* fn, const char* name, const hs_block_arg* b, int64_t n, int64_t nrhs) {
-  if (!b) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s == NULL", fn, name);
+  if (!b) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s == NULL", fn, name);
   if (nrhs == 0) return;
   if (b->dense) {
-    if (b->ld < n) CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the leading dimension of %s is %lld, it has %lld rows", fn, name, (long long)b->ld, (long long)n);
+    if (b->ld < n) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the leading dimension of %s is %lld, it has %lld rows", fn, name, (long long)b->ld, (long long)n);
     return;
   }
-  if (!b->colptr) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s has neither dense values nor a colptr", fn, name);
+  if (!b->colptr) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s has neither dense values nor a colptr", fn, name);
   // the rules of hs_ldiv_sparse_* through its own host-only check
   const int st = hs_ldiv_sparse_plan(F, trans, n, nrhs, b->colptr, b->rowval, nullptr, 0, nullptr, nullptr, nullptr);
   if (st != HS_OK) {
@@ -328,19 +318,18 @@ void check_block(hs_handle* F, int trans, const char* fn, const char* name, cons
     hs_set_error(st, hs_last_error_info(), "%s: %s is not a valid sparse block (%s)", fn, name, why.c_str());
     throw st;
   }
-  if (b->colptr[nrhs] > 1 && !b->nzval) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s has stored entries and nzval == NULL", fn, name);
+  if (b->colptr[nrhs] > 1 && !b->nzval) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s has stored entries and nzval == NULL", fn, name);
 }
 
 template <class T>
 void check_common(hs_handle* F, const char* fn, int trans, int64_t n, int64_t nrhs, int64_t itmax, int pattern, HsHandleView* v) {
-  if (!F) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
-  hs_handle_view(F, v);
-  if ((v->is_complex != 0) != (sizeof(T) == 16)) CE_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and of the blocks differ", fn);
-  if (trans < 0 || trans > 2) CE_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
-  if (pattern < 0 || pattern > 1) CE_FAIL(HS_ERR_ARGUMENT, pattern, "ArgumentError: %s: pattern = %d (0: the stored entries of A, 1: the diagonal)", fn, pattern);
-  if (itmax < 0) CE_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: %s: itmax = %lld < 0", fn, (long long)itmax);
-  if (!v->device) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
-  if (!v->factored) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
+  *v = hs_view_of(F, fn);
+  if ((v->is_complex != 0) != (sizeof(T) == 16)) HS_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and of the blocks differ", fn);
+  hs_check_trans(fn, trans);
+  if (pattern < 0 || pattern > 1) HS_FAIL(HS_ERR_ARGUMENT, pattern, "ArgumentError: %s: pattern = %d (0: the stored entries of A, 1: the diagonal)", fn, pattern);
+  if (itmax < 0) HS_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: %s: itmax = %lld < 0", fn, (long long)itmax);
+  if (!v->device) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
+  if (!v->factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
   {  // what hs_ldiv_block_t_* refuses is refused here, by its own check: a block solve of no columns
     const int st = block_solve<T>(F, trans, nullptr, v->n, nullptr, v->n, v->n, 0, nullptr);
     if (st != HS_OK) {
@@ -350,7 +339,7 @@ void check_common(hs_handle* F, const char* fn, int trans, int64_t n, int64_t nr
     }
   }
   if (n != v->n || nrhs < 0)
-    CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the blocks have %lld rows and %lld columns, F is %lld x %lld", fn, (long long)n, (long long)nrhs, (long long)v->n,
+    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the blocks have %lld rows and %lld columns, F is %lld x %lld", fn, (long long)n, (long long)nrhs, (long long)v->n,
             (long long)v->n);
 }
 
@@ -364,19 +353,19 @@ void to_blk(const hs_block_arg* a, Blk<T>* b) {
 }
 // a host block on the device: dense with ld = n, or the stored values
 template <class T>
-void upload(const hs_block_arg* a, int64_t n, int64_t nrhs, Blk<T>* b, DevBuf& buf, hipStream_t s, double* moved) {
+void upload(const hs_block_arg* a, int64_t n, int64_t nrhs, Blk<T>* b, HsDevBuf& buf, hipStream_t s, double* moved) {
   to_blk<T>(a, b);
   if (nrhs == 0) return;
   if (a->dense) {
     T* d = buf.get<T>((size_t)n * nrhs);
-    CE_HIP(hipMemcpy2DAsync(d, n * sizeof(T), a->dense, a->ld * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), a->dense, a->ld * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
     b->dense = d;
     b->ld = n;
     *moved += (double)n * nrhs;
   } else {
     const int64_t cnt = a->colptr[nrhs] - 1;
     T* d = buf.get<T>((size_t)cnt);
-    if (cnt > 0) CE_HIP(hipMemcpyAsync(d, a->nzval, (size_t)cnt * sizeof(T), hipMemcpyHostToDevice, s));
+    if (cnt > 0) HS_HIP(hipMemcpyAsync(d, a->nzval, (size_t)cnt * sizeof(T), hipMemcpyHostToDevice, s));
     b->nzval = d;
     *moved += (double)cnt;
   }
@@ -392,11 +381,11 @@ void sens_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block
   check_common<T>(F, fn, trans, n, nrhs, itmax, pattern, &c.v);
   check_block<T>(F, trans, fn, "B", B, n, nrhs);
   check_block<T>(F, trans, fn, "W", W, n, nrhs);
-  if (!G) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: G == NULL", fn);
-  if ((X && ldx < n) || (Lam && ldl < n)) CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldx = %lld, ldl = %lld, the blocks have %lld rows", fn, (long long)ldx, (long long)ldl, (long long)n);
+  if (!G) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: G == NULL", fn);
+  if ((X && ldx < n) || (Lam && ldl < n)) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldx = %lld, ldl = %lld, the blocks have %lld rows", fn, (long long)ldx, (long long)ldl, (long long)n);
   c.F = F; c.trans = trans; c.pattern = pattern; c.n = n; c.nrhs = nrhs; c.itmax = itmax;
   double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  DevBuf buf;  // freed after the stream is drained, on every path
+  HsDevBuf buf("condest workspace");  // freed after the stream is drained, on every path
   const int64_t glen = pattern == 0 ? c.v.nnz : n;
   if (on_device) {
     to_blk<T>(B, &c.B);
@@ -408,7 +397,8 @@ void sens_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block
     return finish(F, info);
   }
   c.s = c.v.stream;
-  try {
+  {
+    HsDrain drain{c.s};
     upload<T>(B, n, nrhs, &c.B, buf, c.s, &info[SI_MOVED]);
     upload<T>(W, n, nrhs, &c.W, buf, c.s, &info[SI_MOVED]);
     c.dG = buf.get<T>((size_t)glen);
@@ -417,14 +407,11 @@ void sens_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block
     Driver<T> d{c, buf};
     d.run(info);
     // results go to the caller's arrays only when the whole call succeeded
-    if (glen > 0) CE_HIP(hipMemcpyAsync(G, c.dG, (size_t)glen * sizeof(T), hipMemcpyDeviceToHost, c.s));
-    if (c.dX) CE_HIP(hipMemcpy2DAsync(X, ldx * sizeof(T), c.dX, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, c.s));
-    if (c.dLam) CE_HIP(hipMemcpy2DAsync(Lam, ldl * sizeof(T), c.dLam, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, c.s));
-    CE_HIP(hipStreamSynchronize(c.s));
+    if (glen > 0) HS_HIP(hipMemcpyAsync(G, c.dG, (size_t)glen * sizeof(T), hipMemcpyDeviceToHost, c.s));
+    if (c.dX) HS_HIP(hipMemcpy2DAsync(X, ldx * sizeof(T), c.dX, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, c.s));
+    if (c.dLam) HS_HIP(hipMemcpy2DAsync(Lam, ldl * sizeof(T), c.dLam, n * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToHost, c.s));
+    HS_HIP(hipStreamSynchronize(c.s));
     info[SI_MOVED] += (double)glen + (c.dX ? (double)n * nrhs : 0.0) + (c.dLam ? (double)n * nrhs : 0.0);
-  } catch (...) {
-    (void)hipStreamSynchronize(c.s);
-    throw;
   }
   finish(F, info);
 }
@@ -436,22 +423,22 @@ void misfit_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_blo
   Call<T> c;
   check_common<T>(F, fn, trans, n, nrhs, itmax, pattern, &c.v);
   check_block<T>(F, trans, fn, "B", B, n, nrhs);
-  if (nrows < 0 || nrows > n) CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: nrows = %lld, F is %lld x %lld", fn, (long long)nrows, (long long)n, (long long)n);
-  if (!G || (nrows > 0 && !rows) || (nrhs > 0 && !J) || (nrows > 0 && nrhs > 0 && !D)) CE_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: G, rows, D and J must not be NULL", fn);
+  if (nrows < 0 || nrows > n) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: nrows = %lld, F is %lld x %lld", fn, (long long)nrows, (long long)n, (long long)n);
+  if (!G || (nrows > 0 && !rows) || (nrhs > 0 && !J) || (nrows > 0 && nrhs > 0 && !D)) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: G, rows, D and J must not be NULL", fn);
   if (ldd < nrows || (R && ldr < nrows))
-    CE_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldd = %lld, ldr = %lld, D and R have %lld rows", fn, (long long)ldd, (long long)ldr, (long long)nrows);
+    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldd = %lld, ldr = %lld, D and R have %lld rows", fn, (long long)ldd, (long long)ldr, (long long)nrows);
   {
     std::vector<unsigned char> seen((size_t)n, 0);
     for (int64_t q = 0; q < nrows; ++q) {
-      if (rows[q] < 1 || rows[q] > n) CE_FAIL(HS_ERR_DIMENSION, q, "BoundsError: %s: rows[%lld] = %lld outside 1:%lld", fn, (long long)q + 1, (long long)rows[q], (long long)n);
-      if (seen[(size_t)(rows[q] - 1)]) CE_FAIL(HS_ERR_ARGUMENT, q, "ArgumentError: %s: row %lld is listed twice (the receiver rows must be distinct)", fn, (long long)rows[q]);
+      if (rows[q] < 1 || rows[q] > n) HS_FAIL(HS_ERR_DIMENSION, q, "BoundsError: %s: rows[%lld] = %lld outside 1:%lld", fn, (long long)q + 1, (long long)rows[q], (long long)n);
+      if (seen[(size_t)(rows[q] - 1)]) HS_FAIL(HS_ERR_ARGUMENT, q, "ArgumentError: %s: row %lld is listed twice (the receiver rows must be distinct)", fn, (long long)rows[q]);
       seen[(size_t)(rows[q] - 1)] = 1;
     }
   }
   c.F = F; c.trans = trans; c.pattern = pattern; c.n = n; c.nrhs = nrhs; c.itmax = itmax;
   c.misfit = true; c.rows = rows; c.nrows = nrows;
   double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  DevBuf buf;
+  HsDevBuf buf("condest workspace");
   const int64_t glen = pattern == 0 ? c.v.nnz : n;
   if (on_device) {
     to_blk<T>(B, &c.B);
@@ -462,25 +449,23 @@ void misfit_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_blo
     return finish(F, info);
   }
   c.s = c.v.stream;
-  try {
+  {
+    HsDrain drain{c.s};
     upload<T>(B, n, nrhs, &c.B, buf, c.s, &info[SI_MOVED]);
     const size_t dn = (size_t)nrows * nrhs;
     T* dD = buf.get<T>(dn);
-    if (dn > 0) CE_HIP(hipMemcpy2DAsync(dD, nrows * sizeof(T), D, ldd * sizeof(T), nrows * sizeof(T), nrhs, hipMemcpyHostToDevice, c.s));
+    if (dn > 0) HS_HIP(hipMemcpy2DAsync(dD, nrows * sizeof(T), D, ldd * sizeof(T), nrows * sizeof(T), nrhs, hipMemcpyHostToDevice, c.s));
     c.dD = dD; c.ldd = nrows;
     c.dG = buf.get<T>((size_t)glen);
     c.dJ = buf.get<double>((size_t)nrhs);
     if (R) { c.dR = buf.get<T>(dn); c.ldr = nrows; }
     Driver<T> d{c, buf};
     d.run(info);
-    if (glen > 0) CE_HIP(hipMemcpyAsync(G, c.dG, (size_t)glen * sizeof(T), hipMemcpyDeviceToHost, c.s));
-    if (nrhs > 0) CE_HIP(hipMemcpyAsync(J, c.dJ, (size_t)nrhs * sizeof(double), hipMemcpyDeviceToHost, c.s));
-    if (R && dn > 0) CE_HIP(hipMemcpy2DAsync(R, ldr * sizeof(T), c.dR, nrows * sizeof(T), nrows * sizeof(T), nrhs, hipMemcpyDeviceToHost, c.s));
-    CE_HIP(hipStreamSynchronize(c.s));
+    if (glen > 0) HS_HIP(hipMemcpyAsync(G, c.dG, (size_t)glen * sizeof(T), hipMemcpyDeviceToHost, c.s));
+    if (nrhs > 0) HS_HIP(hipMemcpyAsync(J, c.dJ, (size_t)nrhs * sizeof(double), hipMemcpyDeviceToHost, c.s));
+    if (R && dn > 0) HS_HIP(hipMemcpy2DAsync(R, ldr * sizeof(T), c.dR, nrows * sizeof(T), nrows * sizeof(T), nrhs, hipMemcpyDeviceToHost, c.s));
+    HS_HIP(hipStreamSynchronize(c.s));
     info[SI_MOVED] += (double)dn + (double)glen + (double)nrhs + (R ? (double)dn : 0.0);
-  } catch (...) {
-    (void)hipStreamSynchronize(c.s);
-    throw;
   }
   finish(F, info);
 }
@@ -490,35 +475,35 @@ void misfit_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_blo
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------------
 extern "C" int hs_sens_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const hs_block_arg* W, int64_t itmax, int pattern, double* G, double* X,
                          int64_t ldx, double* Lam, int64_t ldl) {
-  CE_GUARD(sens_entry<double>(F, trans, n, nrhs, B, W, itmax, pattern, G, X, ldx, Lam, ldl, false, nullptr));
+  HS_GUARD(sens_entry<double>(F, trans, n, nrhs, B, W, itmax, pattern, G, X, ldx, Lam, ldl, false, nullptr));
 }
 extern "C" int hs_sens_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const hs_block_arg* W, int64_t itmax, int pattern, double* G, double* X,
                          int64_t ldx, double* Lam, int64_t ldl) {
-  CE_GUARD(sens_entry<cplx>(F, trans, n, nrhs, B, W, itmax, pattern, (cplx*)G, (cplx*)X, ldx, (cplx*)Lam, ldl, false, nullptr));
+  HS_GUARD(sens_entry<cplx>(F, trans, n, nrhs, B, W, itmax, pattern, (cplx*)G, (cplx*)X, ldx, (cplx*)Lam, ldl, false, nullptr));
 }
 extern "C" int hs_sens_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const hs_block_arg* W, int64_t itmax, int pattern, double* dG,
                              double* dX, int64_t ldx, double* dLam, int64_t ldl, void* stream) {
-  CE_GUARD(sens_entry<double>(F, trans, n, nrhs, B, W, itmax, pattern, dG, dX, ldx, dLam, ldl, true, stream));
+  HS_GUARD(sens_entry<double>(F, trans, n, nrhs, B, W, itmax, pattern, dG, dX, ldx, dLam, ldl, true, stream));
 }
 extern "C" int hs_sens_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const hs_block_arg* W, int64_t itmax, int pattern, double* dG,
                              double* dX, int64_t ldx, double* dLam, int64_t ldl, void* stream) {
-  CE_GUARD(sens_entry<cplx>(F, trans, n, nrhs, B, W, itmax, pattern, (cplx*)dG, (cplx*)dX, ldx, (cplx*)dLam, ldl, true, stream));
+  HS_GUARD(sens_entry<cplx>(F, trans, n, nrhs, B, W, itmax, pattern, (cplx*)dG, (cplx*)dX, ldx, (cplx*)dLam, ldl, true, stream));
 }
 extern "C" int hs_misfit_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const int64_t* rows, int64_t nrows, const double* D, int64_t ldd,
                            int64_t itmax, int pattern, double* J, double* R, int64_t ldr, double* G) {
-  CE_GUARD(misfit_entry<double>(F, trans, n, nrhs, B, rows, nrows, D, ldd, itmax, pattern, J, R, ldr, G, false, nullptr));
+  HS_GUARD(misfit_entry<double>(F, trans, n, nrhs, B, rows, nrows, D, ldd, itmax, pattern, J, R, ldr, G, false, nullptr));
 }
 extern "C" int hs_misfit_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const int64_t* rows, int64_t nrows, const double* D, int64_t ldd,
                            int64_t itmax, int pattern, double* J, double* R, int64_t ldr, double* G) {
-  CE_GUARD(misfit_entry<cplx>(F, trans, n, nrhs, B, rows, nrows, (const cplx*)D, ldd, itmax, pattern, J, (cplx*)R, ldr, (cplx*)G, false, nullptr));
+  HS_GUARD(misfit_entry<cplx>(F, trans, n, nrhs, B, rows, nrows, (const cplx*)D, ldd, itmax, pattern, J, (cplx*)R, ldr, (cplx*)G, false, nullptr));
 }
 extern "C" int hs_misfit_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const int64_t* rows, int64_t nrows, const double* dD, int64_t ldd,
                                int64_t itmax, int pattern, double* dJ, double* dR, int64_t ldr, double* dG, void* stream) {
-  CE_GUARD(misfit_entry<double>(F, trans, n, nrhs, B, rows, nrows, dD, ldd, itmax, pattern, dJ, dR, ldr, dG, true, stream));
+  HS_GUARD(misfit_entry<double>(F, trans, n, nrhs, B, rows, nrows, dD, ldd, itmax, pattern, dJ, dR, ldr, dG, true, stream));
 }
 extern "C" int hs_misfit_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const int64_t* rows, int64_t nrows, const double* dD, int64_t ldd,
                                int64_t itmax, int pattern, double* dJ, double* dR, int64_t ldr, double* dG, void* stream) {
-  CE_GUARD(misfit_entry<cplx>(F, trans, n, nrhs, B, rows, nrows, (const cplx*)dD, ldd, itmax, pattern, dJ, (cplx*)dR, ldr, (cplx*)dG, true, stream));
+  HS_GUARD(misfit_entry<cplx>(F, trans, n, nrhs, B, rows, nrows, (const cplx*)dD, ldd, itmax, pattern, dJ, (cplx*)dR, ldr, (cplx*)dG, true, stream));
 }
 extern "C" int hs_sens_info(const hs_handle* F, double* out8) {
   if (!F || !out8) {

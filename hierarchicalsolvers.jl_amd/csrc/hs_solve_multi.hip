@@ -31,7 +31,8 @@
 #include "hs_solve_multi.h"
 #include "hs_interface.h"
 #include "hs_lowrank.h"
-#include "hs_selinv.h"  // hs_scratch_take / hs_scratch_give
+#include "../../include/hs_solver.h"
+#include "hs_host.h"
 
 int hs_ldiv_block_cols() {
   static const int kc = [] {

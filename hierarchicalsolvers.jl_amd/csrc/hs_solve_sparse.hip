@@ -27,7 +27,8 @@
 #include <vector>
 
 #include "hs_solve_multi.h"
-#include "hs_selinv.h"  // hs_scratch_take / hs_scratch_give
+#include "../../include/hs_solver.h"
+#include "hs_host.h"
 
 void hs_sparse_plan(const HsSparseTree& t, int64_t nrhs, const int64_t* bcolptr, const int64_t* browval, int64_t base, const int64_t* rows, int64_t nrows,
                     HsSparsePlan* p) {
@@ -220,10 +221,11 @@ void hs_solve_sparse_run(const HsMultiView& v, const HsSparseTree& t, int trans,
   const size_t lbytes = o_sn + std::max<size_t>(idx.size(), 1) * sizeof(SolveNode<T>);
   const size_t wbytes = (size_t)n * KC * sizeof(T);
 
-  char* dl = (char*)hs_scratch_take(lbytes, "sparse solve lists");
-  T* W = nullptr;
-  try {
-    W = (T*)hs_scratch_take(wbytes, "sparse solve chunk");
+  {
+    HsScratch lists(lbytes, "sparse solve lists"), chunk(wbytes, "sparse solve chunk");
+    HsDrain drain{s};
+    char* dl = (char*)lists.p;
+    T* W = (T*)chunk.p;
     if (!pk.buf.empty()) HS_HIP(hipMemcpy(dl, pk.buf.data(), pk.buf.size(), hipMemcpyHostToDevice));
     launch_sparse_compact<T>((SolveNode<T>*)(dl + o_sn), (const SolveNode<T>*)base, (const long long*)(dl + o_idx), (long long)idx.size(), s);
     for (size_t k = 0; k < A.sub.size(); ++k) {
@@ -245,14 +247,7 @@ void hs_solve_sparse_run(const HsMultiView& v, const HsSparseTree& t, int trans,
     A.end = chunk_end<T>;
     hs_solve_multi_run<T>(v, trans, W, n, nrhs, s, &A);
     HS_HIP(hipStreamSynchronize(s));  // the lists and the chunk go back to the scratch cache
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    if (W) hs_scratch_give(W, wbytes);
-    hs_scratch_give(dl, lbytes);
-    throw;
   }
-  hs_scratch_give(W, wbytes);
-  hs_scratch_give(dl, lbytes);
   out8[0] = 0.0;
   out8[1] = p.model * sizeof(T);
   out8[2] = p.visits[0];

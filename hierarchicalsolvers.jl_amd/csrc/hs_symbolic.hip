@@ -17,8 +17,7 @@
 
 #include "../../include/hs_solver.h"
 #include "../../include/hs_symbolic.h"
-
-void hs_set_error(int code, long long info, const char* fmt, ...);
+#include "hs_host.h"
 
 struct hs_symbolic {
   int64_t n = 0;  // number of DOFs
@@ -28,14 +27,6 @@ struct hs_symbolic {
 };
 
 namespace {
-struct SymErr {
-  int code;
-};
-#define SYM_FAIL(code, info, ...)          \
-  do {                                     \
-    hs_set_error(code, info, __VA_ARGS__); \
-    throw SymErr{code};                    \
-  } while (0)
 
 struct Node {
   int left = -1, right = -1;
@@ -48,7 +39,7 @@ extern "C" int hs_symbolic_from_elimtree(int64_t nnodes, const int64_t* fathers,
                                          hs_symbolic** out) {
   if (out) *out = nullptr;
   try {
-    if (!out || nnodes <= 0 || !fathers || !lsons || !rsons || !ninter || !nbound) SYM_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: empty elimination tree");
+    if (!out || nnodes <= 0 || !fathers || !lsons || !rsons || !ninter || !nbound) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: empty elimination tree");
     const int nn = (int)nnodes;
     // ---- parse_elimtree: node table, one root ------------------------------------------------------------------
     int root = -1, nroots = 0;
@@ -57,24 +48,24 @@ extern "C" int hs_symbolic_from_elimtree(int64_t nnodes, const int64_t* fathers,
         root = i;
         ++nroots;
       }
-    if (nroots != 1) SYM_FAIL(HS_ERR_ARGUMENT, nroots, "ArgumentError: found either less than or more than one root.");  // :111
+    if (nroots != 1) HS_FAIL(HS_ERR_ARGUMENT, nroots, "ArgumentError: found either less than or more than one root.");  // :111
     std::vector<Node> N(nn);
     int64_t maxdof = 0;
     for (int i = 0; i < nn; ++i) {
       const int64_t ls = lsons[i], rs = rsons[i];
-      if ((ls != -1 && (ls < 1 || ls > nn)) || (rs != -1 && (rs < 1 || rs > nn))) SYM_FAIL(HS_ERR_ARGUMENT, i + 1, "BoundsError: son of node %d outside 1:%d", i + 1, nn);
+      if ((ls != -1 && (ls < 1 || ls > nn)) || (rs != -1 && (rs < 1 || rs > nn))) HS_FAIL(HS_ERR_ARGUMENT, i + 1, "BoundsError: son of node %d outside 1:%d", i + 1, nn);
       N[i].left = ls == -1 ? -1 : (int)ls - 1;
       N[i].right = rs == -1 ? -1 : (int)rs - 1;
       if (ninter[i] < 0 || ninter[i] > ld_inter || nbound[i] < 0 || nbound[i] > ld_bound)
-        SYM_FAIL(HS_ERR_DIMENSION, i + 1, "DimensionMismatch: dimensions inconsistent among inputs (node %d)", i + 1);  // :107
+        HS_FAIL(HS_ERR_DIMENSION, i + 1, "DimensionMismatch: dimensions inconsistent among inputs (node %d)", i + 1);  // :107
       N[i].in.assign(inter + (size_t)i * ld_inter, inter + (size_t)i * ld_inter + ninter[i]);
       N[i].bd.assign(bound + (size_t)i * ld_bound, bound + (size_t)i * ld_bound + nbound[i]);
       for (int64_t g : N[i].in) {
-        if (g < 1) SYM_FAIL(HS_ERR_DIMENSION, i + 1, "BoundsError: DOF id %lld of node %d", (long long)g, i + 1);
+        if (g < 1) HS_FAIL(HS_ERR_DIMENSION, i + 1, "BoundsError: DOF id %lld of node %d", (long long)g, i + 1);
         maxdof = std::max(maxdof, g);
       }
       for (int64_t g : N[i].bd) {
-        if (g < 1) SYM_FAIL(HS_ERR_DIMENSION, i + 1, "BoundsError: DOF id %lld of node %d", (long long)g, i + 1);
+        if (g < 1) HS_FAIL(HS_ERR_DIMENSION, i + 1, "BoundsError: DOF id %lld of node %d", (long long)g, i + 1);
         maxdof = std::max(maxdof, g);
       }
     }
@@ -92,13 +83,13 @@ extern "C" int hs_symbolic_from_elimtree(int64_t nnodes, const int64_t* fathers,
           order.push_back(x);
           continue;
         }
-        if (visited[x]) SYM_FAIL(HS_ERR_TREE, x + 1, "ArgumentError: node %d is reachable twice (not a tree)", x + 1);
+        if (visited[x]) HS_FAIL(HS_ERR_TREE, x + 1, "ArgumentError: node %d is reachable twice (not a tree)", x + 1);
         visited[x] = 1;
         stack.push_back({x, 1});
         if (N[x].right >= 0) stack.push_back({N[x].right, 0});
         if (N[x].left >= 0) stack.push_back({N[x].left, 0});
       }
-      if ((int)order.size() != nn) SYM_FAIL(HS_ERR_TREE, (long long)order.size(), "ArgumentError: %d of %d nodes are not reachable from the root", nn - (int)order.size(), nn);
+      if ((int)order.size() != nn) HS_FAIL(HS_ERR_TREE, (long long)order.size(), "ArgumentError: %d of %d nodes are not reachable from the root", nn - (int)order.size(), nn);
     }
     // ---- symfact! ---------------------------------------------------------------------------------------------------
     std::vector<signed char> mark((size_t)maxdof + 2, 0);
@@ -129,7 +120,7 @@ extern "C" int hs_symbolic_from_elimtree(int64_t nnodes, const int64_t* fathers,
       }
       // validation the reference lacks: the children must carry every DOF of the node exactly once
       if (ni.size() != P.in.size() || nb.size() != P.bd.size())
-        SYM_FAIL(HS_ERR_DIMENSION, x + 1, "DimensionMismatch: the children of node %d carry (%lld, %lld) of its (%lld, %lld) int/bnd DOFs", x + 1, (long long)ni.size(),
+        HS_FAIL(HS_ERR_DIMENSION, x + 1, "DimensionMismatch: the children of node %d carry (%lld, %lld) of its (%lld, %lld) int/bnd DOFs", x + 1, (long long)ni.size(),
                  (long long)nb.size(), (long long)P.in.size(), (long long)P.bd.size());
       for (int64_t g : P.in) mark[g] = 0;
       for (int64_t g : P.bd) mark[g] = 0;
@@ -152,7 +143,7 @@ extern "C" int hs_symbolic_from_elimtree(int64_t nnodes, const int64_t* fathers,
       const int64_t g = S->perm[k];
       if (iperm[g] != 0) {
         delete S;
-        SYM_FAIL(HS_ERR_DIMENSION, g, "DimensionMismatch: DOF %lld is eliminated twice", (long long)g);
+        HS_FAIL(HS_ERR_DIMENSION, g, "DimensionMismatch: DOF %lld is eliminated twice", (long long)g);
       }
       iperm[g] = (int64_t)k + 1;
     }
@@ -177,7 +168,7 @@ extern "C" int hs_symbolic_from_elimtree(int64_t nnodes, const int64_t* fathers,
       for (int64_t g : X.bd) {
         if (iperm[g] == 0) {
           delete S;
-          SYM_FAIL(HS_ERR_DIMENSION, g, "DimensionMismatch: boundary DOF %lld of node %d is never eliminated", (long long)g, order[k] + 1);
+          HS_FAIL(HS_ERR_DIMENSION, g, "DimensionMismatch: boundary DOF %lld of node %d is never eliminated", (long long)g, order[k] + 1);
         }
         S->bnd_idx.push_back(iperm[g]);
       }
@@ -186,8 +177,8 @@ extern "C" int hs_symbolic_from_elimtree(int64_t nnodes, const int64_t* fathers,
     }
     *out = S;
     return HS_OK;
-  } catch (const SymErr& e) {
-    return e.code;
+  } catch (int code) {
+    return code;
   } catch (const std::bad_alloc&) {
     hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
     return HS_ERR_NOMEM;
@@ -305,8 +296,8 @@ struct GraphND {
 extern "C" int hs_symbolic_from_graph(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t nmax, hs_symbolic** out) {
   if (out) *out = nullptr;
   try {
-    if (!out || n <= 0 || !colptr || !rowval || nmax < 1) SYM_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_symbolic_from_graph needs a pattern and nmax >= 1");
-    if (n > 2000000000LL) SYM_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: more than 2^31 DOFs");
+    if (!out || n <= 0 || !colptr || !rowval || nmax < 1) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_symbolic_from_graph needs a pattern and nmax >= 1");
+    if (n > 2000000000LL) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: more than 2^31 DOFs");
     GraphND G;
     G.n = n;
     G.nmax = (int)std::min<int64_t>(nmax, n);
@@ -316,7 +307,7 @@ extern "C" int hs_symbolic_from_graph(int64_t n, const int64_t* colptr, const in
     for (int64_t c = 0; c < n; ++c)
       for (int64_t a = colptr[c] - 1; a < colptr[c + 1] - 1; ++a) {
         const int64_t r = rowval[a] - 1;
-        if (r < 0 || r >= n) SYM_FAIL(HS_ERR_DIMENSION, a, "BoundsError: row index %lld outside 1:%lld", (long long)(r + 1), (long long)n);
+        if (r < 0 || r >= n) HS_FAIL(HS_ERR_DIMENSION, a, "BoundsError: row index %lld outside 1:%lld", (long long)(r + 1), (long long)n);
         if (r == c) continue;
         cnt[(size_t)r + 1]++;
         cnt[(size_t)c + 1]++;
@@ -371,8 +362,8 @@ extern "C" int hs_symbolic_from_graph(int64_t n, const int64_t* colptr, const in
       std::copy(G.nodes[i].bd.begin(), G.nodes[i].bd.end(), bound.begin() + (size_t)mb * i);
     }
     return hs_symbolic_from_elimtree(nn, fathers.data(), lsons.data(), rsons.data(), ninter.data(), inter.data(), mi, nbound.data(), bound.data(), mb, out);
-  } catch (const SymErr& e) {
-    return e.code;
+  } catch (int code) {
+    return code;
   } catch (const std::bad_alloc&) {
     hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
     return HS_ERR_NOMEM;
