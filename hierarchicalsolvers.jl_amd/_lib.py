@@ -92,6 +92,8 @@ EXPORTS = [
     "hs_mod_create_d", "hs_mod_create_z", "hs_mod_create_dev_d", "hs_mod_create_dev_z", "hs_mod_create_sparse_d", "hs_mod_create_sparse_z", "hs_mod_ldiv_d", "hs_mod_ldiv_z",
     "hs_mod_ldiv_dev_d", "hs_mod_ldiv_dev_z", "hs_mod_info", "hs_mod_free", "hs_gmres_block_mod_d", "hs_gmres_block_mod_z",
     "hs_eigs_d", "hs_eigs_z", "hs_eigs_info", "hs_eigs_gen_d", "hs_eigs_gen_z", "hs_eigs_gen_info", "hsk_eigs_coldot_d", "hsk_eigs_coldot_z", "hsk_eigs_rotate_d", "hsk_eigs_rotate_z", "hsk_eigs_chol_inv_d", "hsk_eigs_chol_inv_z", "hsk_small_eig_z", "hsk_eigs_phase_timing", "hsk_eigs_phases", "hsk_eigs_gen_mprod_seconds",
+    "hs_f32_create", "hs_f32_ldiv_d", "hs_f32_ldiv_z", "hs_f32_ldiv_dev_d", "hs_f32_ldiv_dev_z", "hs_f32_info", "hs_f32_free", "hs_gmres_block_f32_d", "hs_gmres_block_f32_z",
+    "hsk_multi_prob_f32_d", "hsk_multi_prob_f32_z", "hsk_multi_prob_t_f32_d", "hsk_multi_prob_t_f32_z", "hsk_round_factors_f32",
     "hsk_mod_inner_d", "hsk_mod_inner_z", "hsk_mod_apply_d", "hsk_mod_apply_z", "hsk_mod_gather_d", "hsk_mod_gather_z", "hsk_mod_cap_d", "hsk_mod_cap_z",
     "hs_maxrank", "hs_is_complex", "hs_size", "hs_free", "hs_last_error", "hs_last_error_info", "hs_get_stats",
     "hs_node_info", "hs_node_ranks", "hs_node_export", "hs_node_export_piv", "hs_device_info",
@@ -242,6 +244,29 @@ def lib():
     for f in (L.hs_gmres_block_mod_d, L.hs_gmres_block_mod_z):
         f.argtypes = [vp, C.c_int, i64, p_i64, p_i64, vp, vp, i64, vp, i64, i64, C.c_int, C.c_int, C.c_double, C.c_double, i64, i64, p_f64, p_i64, C.POINTER(C.c_int), vp]
         f.restype = C.c_int
+    L.hs_f32_create.argtypes = [vp, vp, C.POINTER(vp)]
+    L.hs_f32_create.restype = C.c_int
+    for f in (L.hs_f32_ldiv_d, L.hs_f32_ldiv_z):
+        f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
+        f.restype = C.c_int
+    for f in (L.hs_f32_ldiv_dev_d, L.hs_f32_ldiv_dev_z):
+        f.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, vp]
+        f.restype = C.c_int
+    L.hs_f32_info.argtypes = [vp, p_f64]
+    L.hs_f32_info.restype = C.c_int
+    L.hs_f32_free.argtypes = [vp]
+    L.hs_f32_free.restype = None
+    for f in (L.hs_gmres_block_f32_d, L.hs_gmres_block_f32_z):
+        f.argtypes = [vp, C.c_int, i64, p_i64, p_i64, vp, vp, i64, vp, i64, i64, C.c_int, C.c_int, C.c_double, C.c_double, i64, i64, p_f64, p_i64, C.POINTER(C.c_int), vp]
+        f.restype = C.c_int
+    for f in (L.hsk_multi_prob_f32_d, L.hsk_multi_prob_f32_z):
+        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        f.restype = C.c_int
+    for f in (L.hsk_multi_prob_t_f32_d, L.hsk_multi_prob_t_f32_z):
+        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        f.restype = C.c_int
+    L.hsk_round_factors_f32.argtypes = [vp, p_i64]
+    L.hsk_round_factors_f32.restype = C.c_int
     for f in (L.hsk_mod_inner_d, L.hsk_mod_inner_z):
         f.argtypes = [i64, i64, i64, vp, i64, vp, i64, C.c_int, vp, i64]
         f.restype = C.c_int

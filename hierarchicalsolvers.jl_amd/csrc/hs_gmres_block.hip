@@ -41,6 +41,7 @@
 #include "hs_gmres_common.h"
 #include "hs_solve_multi.h"
 #include "hs_mod.h"  // hs_mod_apply_prec, hs_mod_handle
+#include "hs_f32.h"  // hs_f32_apply_prec, hs_f32_size, hs_f32_is_complex
 
 namespace {
 
@@ -345,6 +346,13 @@ struct PrecBlockMod {  // hs_mod_ldiv_dev_*: op(A + U V^H)^-1 through the factor
   hs_mod* M;
   int trans;
   int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return hs_mod_apply_prec(M, trans, out, ld, in, ld, n, nc, s); }
+};
+template <class T>
+struct PrecBlockF32 {  // hs_f32_ldiv_dev_*: op(F)^-1 from the Float32 copy of the factors
+  hs_handle* F;        // never dereferenced: the object itself, which gmres_group reads as "there is a preconditioner"
+  hs_f32* G;
+  int trans;
+  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return hs_f32_apply_prec(G, trans, out, ld, in, ld, n, nc, s); }
 };
 template <class T>
 struct PrecBlockOp {  // hs_ldiv_block_dev_t_*: op(F)
@@ -873,6 +881,46 @@ int gmres_block_mod_entry(hs_mod* M, int trans, int64_t n, const int64_t* colptr
   return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
+// hs_gmres_block_f32_*: op(A) X = B right-preconditioned by op(F)^-1 as hs_f32_ldiv_dev_* applies it; A is the caller's CSC (the object holds
+// no matrix)
+template <class T>
+int gmres_block_f32_entry(hs_f32* G, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs,
+                          int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  const char* fn = "hs_gmres_block_f32_*";
+  if (!G) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null hs_f32", fn);
+    return HS_ERR_ARGUMENT;
+  }
+  if (trans < 0 || trans > 2) {
+    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: A, 1: transpose(A), 2: adjoint(A))", fn, trans);
+    return HS_ERR_ARGUMENT;
+  }
+  if (!colptr || !rowval || !nz) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: A must be given as CSC (a demoted factorization holds no matrix)", fn);
+    return HS_ERR_ARGUMENT;
+  }
+  if (n <= 0 || nrhs < 0) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs n >= 1 and nrhs >= 0", fn);
+    return HS_ERR_ARGUMENT;
+  }
+  if (hs_f32_size(G) != n || (hs_f32_is_complex(G) != 0) != (sizeof(T) == 16)) {
+    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld %s", (long long)hs_f32_size(G), (long long)hs_f32_size(G),
+                 hs_f32_is_complex(G) ? "ComplexF64" : "Float64", (long long)n, (long long)n, sizeof(T) == 16 ? "ComplexF64" : "Float64");
+    return HS_ERR_DIMENSION;
+  }
+  if (nrhs == 0) {
+    for (double& v : g_info) v = 0.0;
+    return HS_OK;
+  }
+  if (const int st = gmres_block_check<T>(nullptr, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
+  const PrecBlockF32<T> Pr{reinterpret_cast<hs_handle*>(G), G, trans};
+  if (trans == 0)
+    return gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                              stream);
+  auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, nullptr, trans, false, n, colptr, rowval, nz, s)}; };
+  return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+
 // hsk_spmm_*: the SpMM kernel alone on host data
 template <class T>
 int spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy, int64_t nrhs) {
@@ -1031,5 +1079,17 @@ extern "C" int hs_gmres_block_mod_z(hs_mod* Pr, int trans, int64_t n, const int6
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
   return gmres_block_mod_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
+                                     maxiter, resnorm, iters, converged, stream);
+}
+extern "C" int hs_gmres_block_f32_d(hs_f32* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
+                                    double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
+                                    double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_block_f32_entry<double>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                                       stream);
+}
+extern "C" int hs_gmres_block_f32_z(hs_f32* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
+                                    double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
+                                    double* resnorm, int64_t* iters, int* converged, void* stream) {
+  return gmres_block_f32_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
                                      maxiter, resnorm, iters, converged, stream);
 }

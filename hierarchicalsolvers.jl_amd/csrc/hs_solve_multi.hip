@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "hs_solve_multi.h"
+#include "hs_f32.h"
 #include "hs_interface.h"
 #include "hs_lowrank.h"
 #include "../../include/hs_solver.h"
@@ -97,15 +98,39 @@ struct FlopCount {
   }
 };
 
-// t = Z x (r x kc, in T1), then dst -= C t with C dense or the unit trapezoid of the packed sketch; x, dst: rows of the work blocks
+// The factor scalar S of a run: T itself (the handle's own factors), or F32Of<T>::type (a demoted copy, hs_f32.h) -- the problem structs and
+// launches of the second are those of kernels_solve_multi_f32.hip.  Everything below is written once over the pair.
+template <class T, class S>
+struct MultiSide {
+  typedef MultiProb<T> Prob;
+  typedef MultiProbT<T> ProbT;
+  static void prob(const Prob& p, int kc, hipStream_t s) { launch_multi_prob<T>(p, kc, s); }
+  static void prob_t(const ProbT& p, int kc, hipStream_t s) { launch_multi_prob_t<T>(p, kc, s); }
+  static void move(const SolveNode<S>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm) { launch_multi_move<T>(sn, nf, what, maxrows, a, s, perm); }
+  static void level(const SolveNode<S>* sn, int nf, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s) { launch_multi_level<T>(sn, nf, mode, blk, maxM, a, s); }
+  static void level_t(const SolveNode<S>* sn, int nf, int mode, int blk, int cj, int maxM, const MultiArgs& a, hipStream_t s) { launch_multi_level_t<T>(sn, nf, mode, blk, cj, maxM, a, s); }
+};
 template <class T>
-void lr_apply(const LowRank<T>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
-  MultiProb<T> p;
+struct MultiSide<T, typename F32Of<T>::type> {
+  typedef typename F32Of<T>::type S;
+  typedef MultiProbF32<T> Prob;
+  typedef MultiProbTF32<T> ProbT;
+  static void prob(const Prob& p, int kc, hipStream_t s) { launch_multi_prob_f32<T>(p, kc, s); }
+  static void prob_t(const ProbT& p, int kc, hipStream_t s) { launch_multi_prob_t_f32<T>(p, kc, s); }
+  static void move(const SolveNode<S>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm) { launch_multi_move_f32<T>(sn, nf, what, maxrows, a, s, perm); }
+  static void level(const SolveNode<S>* sn, int nf, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s) { launch_multi_level_f32<T>(sn, nf, mode, blk, maxM, a, s); }
+  static void level_t(const SolveNode<S>* sn, int nf, int mode, int blk, int cj, int maxM, const MultiArgs& a, hipStream_t s) { launch_multi_level_t_f32<T>(sn, nf, mode, blk, cj, maxM, a, s); }
+};
+
+// t = Z x (r x kc, in T1), then dst -= C t with C dense or the unit trapezoid of the packed sketch; x, dst: rows of the work blocks
+template <class T, class S>
+void lr_apply(const LowRank<S>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
+  typename MultiSide<T, S>::Prob p;
   memset(&p, 0, sizeof p);
   p.A = lr.Z; p.lda = lr.ldz; p.M = lr.r; p.K = lr.cols;
   p.X = x; p.xrs = kcw;
   p.C = tbuf; p.crs = kcw;
-  launch_multi_prob<T>(p, kc, s);
+  MultiSide<T, S>::prob(p, kc, s);
   fc.add(lr.r, lr.cols, kc);
   memset(&p, 0, sizeof p);
   if (lr.Cd) {
@@ -116,12 +141,12 @@ void lr_apply(const LowRank<T>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc
   p.M = lr.rows; p.K = lr.r;
   p.X = tbuf; p.xrs = kcw;
   p.Cin = dst; p.C = dst; p.crs = kcw;
-  launch_multi_prob<T>(p, kc, s);
+  MultiSide<T, S>::prob(p, kc, s);
   fc.add(lr.rows, lr.r, kc);
 }
 
 // the work blocks and the boundary segments of the handle, sized for a chunk of kcw columns (shared by both directions of the block solve)
-template <class T>
+template <class T, class S>
 MultiCache* multi_prepare(const HsMultiView& v, int kcw) {
   MultiCache* mc = cache_of(v);
   long long wmax = 1, rmax = 1, bmax = 1;
@@ -145,8 +170,8 @@ MultiCache* multi_prepare(const HsMultiView& v, int kcw) {
     for (const HsMultiFront& f : L.fronts) bsum += f.nb;
     bmax = std::max(bmax, bsum);
     for (const HsMultiLR& q : L.lr) {
-      if (q.lrL) rmax = std::max<long long>(rmax, ((const LowRank<T>*)q.lrL)->r);
-      if (q.lrR) rmax = std::max<long long>(rmax, ((const LowRank<T>*)q.lrR)->r);
+      if (q.lrL) rmax = std::max<long long>(rmax, ((const LowRank<S>*)q.lrL)->r);
+      if (q.lrR) rmax = std::max<long long>(rmax, ((const LowRank<S>*)q.lrR)->r);
     }
   }
   if (mc->pending && mc->e1) (void)hipEventSynchronize(mc->e1);  // a call on another stream may still use the work blocks
@@ -176,9 +201,9 @@ void multi_finish(MultiCache* mc, const HsMultiView& v, const FlopCount& fc, int
 
 // dst -= op(Z)^T (op(C)^T x): the transposed low-rank transform.  C dense, or the unit trapezoid of the packed sketch: C = P' trap(Lp), so
 // C^T x = trap(Lp)^T (P x) -- the INPUT rows are gathered through rperm, where lr_apply scatters its output
-template <class T>
-void lr_apply_t(const LowRank<T>& lr, int conj, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
-  MultiProbT<T> p;
+template <class T, class S>
+void lr_apply_t(const LowRank<S>& lr, int conj, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
+  typename MultiSide<T, S>::ProbT p;
   memset(&p, 0, sizeof p);
   if (lr.Cd) {
     p.A = lr.Cd; p.lda = lr.ldc;
@@ -188,13 +213,13 @@ void lr_apply_t(const LowRank<T>& lr, int conj, const T* x, T* dst, T* tbuf, int
   p.M = lr.r; p.K = lr.rows; p.conj = conj;
   p.X = x; p.xrs = kcw;
   p.C = tbuf; p.crs = kcw;
-  launch_multi_prob_t<T>(p, kc, s);
+  MultiSide<T, S>::prob_t(p, kc, s);
   fc.add(lr.r, lr.rows, kc);
   memset(&p, 0, sizeof p);
   p.A = lr.Z; p.lda = lr.ldz; p.M = lr.cols; p.K = lr.r; p.conj = conj;
   p.X = tbuf; p.xrs = kcw;
   p.Cin = dst; p.C = dst; p.crs = kcw;
-  launch_multi_prob_t<T>(p, kc, s);
+  MultiSide<T, S>::prob_t(p, kc, s);
   fc.add(lr.cols, lr.r, kc);
 }
 
@@ -230,25 +255,24 @@ bool multi_t_left_looking() {
 }
 
 // the grouped launches of either direction: trans = 0 runs kernels_solve_multi.hip (mode n), trans = 1, 2 kernels_solve_multi_t.hip (mode t)
-template <class T>
-void level_move(int trans, const SolveNode<T>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s) {
-  launch_multi_move<T>(sn, nf, what, maxrows, a, s, trans ? 2 : 0);
+template <class T, class S>
+void level_move(int trans, const SolveNode<S>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s) {
+  MultiSide<T, S>::move(sn, nf, what, maxrows, a, s, trans ? 2 : 0);
 }
-template <class T>
-void level_step(int trans, int cj, const SolveNode<T>* sn, int nf, int mode_n, int mode_t, int blk, int maxM, const MultiArgs& a, hipStream_t s) {
+template <class T, class S>
+void level_step(int trans, int cj, const SolveNode<S>* sn, int nf, int mode_n, int mode_t, int blk, int maxM, const MultiArgs& a, hipStream_t s) {
   if (trans)
-    launch_multi_level_t<T>(sn, nf, mode_t, blk, cj, maxM, a, s);
+    MultiSide<T, S>::level_t(sn, nf, mode_t, blk, cj, maxM, a, s);
   else
-    launch_multi_level<T>(sn, nf, mode_n, blk, maxM, a, s);
+    MultiSide<T, S>::level(sn, nf, mode_n, blk, maxM, a, s);
 }
-template <class T>
-void lr_apply_op(int trans, int cj, const LowRank<T>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
+template <class T, class S>
+void lr_apply_op(int trans, int cj, const LowRank<S>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
   if (trans)
-    lr_apply_t<T>(lr, cj, x, dst, tbuf, kcw, kc, fc, s);
+    lr_apply_t<T, S>(lr, cj, x, dst, tbuf, kcw, kc, fc, s);
   else
-    lr_apply<T>(lr, x, dst, tbuf, kcw, kc, fc, s);
+    lr_apply<T, S>(lr, x, dst, tbuf, kcw, kc, fc, s);
 }
-}  // namespace
 
 // op(F) \ B with op = identity (trans = 0), transpose (1) or adjoint (2): the same chunks, work blocks and stored blocks.  trans = 0 is the
 // schedule at the head of this file.  trans = 1, 2 run every product with the factor panel transposed (kernels_solve_multi_t.hip), U and L
@@ -265,13 +289,16 @@ void lr_apply_op(int trans, int cj, const LowRank<T>& lr, const T* x, T* dst, T*
 // per output row -- and has (ni - 256 (j + 1)) / 64 workgroups.  The left-looking order (HS_LDIV_BLOCK_T_LOOK=left, trans = 1, 2 only) reads the
 // column panel above / below the block with K up to ni and 256 outputs: W is written once per block, by four workgroups per front
 // (DESIGN.md section 4a⁗″).
-template <class T>
-void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act, int phase) {
+//
+// S: the scalar the factors are stored in (MultiSide).  A demoted copy (S != T) has no active set, no phases and no HSS fronts.
+template <class T, class S>
+void multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act, int phase) {
+  constexpr bool OWN = std::is_same<T, S>::value;
   const int KC = hs_ldiv_block_cols();
   const int kcw = KC;
   const int cj = (trans == 2 && sizeof(T) == 16) ? 1 : 0;
   const bool left = trans && multi_t_left_looking();
-  MultiCache* mc = multi_prepare<T>(v, kcw);
+  MultiCache* mc = multi_prepare<T, S>(v, kcw);
   FlopCount fc;
   fc.tr = hs_multi_rows_per_wg(sizeof(T) == 16);
   fc.cmul = sizeof(T) == 16 ? 4 : 1;
@@ -292,20 +319,20 @@ void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int
       if (L.nfronts == 0 || L.maxni == 0) continue;
       const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 0);
       if (q_.nf == 0 || q_.maxni == 0) continue;
-      const SolveNode<T>* sn = (const SolveNode<T>*)q_.sn;
+      const SolveNode<S>* sn = (const SolveNode<S>*)q_.sn;
       const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
       a.aux = q_.aux;
-      level_move<T>(trans, sn, nf, 0, maxni, a, s);
-      level_move<T>(trans, sn, nf, 1, maxnb, a, s);
+      level_move<T, S>(trans, sn, nf, 0, maxni, a, s);
+      level_move<T, S>(trans, sn, nf, 1, maxnb, a, s);
       const int nblk = (maxni + 255) / 256;
       for (int j = 0; j < nblk; ++j) {
         const int wl = std::min(256, maxni - j * 256);
-        if (left && j > 0) launch_multi_level_t<T>(sn, nf, HSMT_LEFT_U, j, cj, wl, a, s);
-        level_step<T>(trans, cj, sn, nf, HSM_DIAG_L, HSMT_DIAG_U, j, wl, a, s);
-        if (!left) level_step<T>(trans, cj, sn, nf, HSM_BELOW_L, HSMT_BELOW_U, j, maxni - (j + 1) * 256, a, s);
+        if (left && j > 0) MultiSide<T, S>::level_t(sn, nf, HSMT_LEFT_U, j, cj, wl, a, s);
+        level_step<T, S>(trans, cj, sn, nf, HSM_DIAG_L, HSMT_DIAG_U, j, wl, a, s);
+        if (!left) level_step<T, S>(trans, cj, sn, nf, HSM_BELOW_L, HSMT_BELOW_U, j, maxni - (j + 1) * 256, a, s);
       }
-      level_step<T>(trans, cj, sn, nf, HSM_BND_L, HSMT_BND_U, 0, maxnb, a, s);
+      level_step<T, S>(trans, cj, sn, nf, HSM_BND_L, HSMT_BND_U, 0, maxnb, a, s);
       each_front(L, q_, [&](const HsMultiFront& f) {
         for (int j = 0; j * 256 < f.ni; ++j) {
           const double wl = std::min(256, f.ni - j * 256);
@@ -320,12 +347,13 @@ void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int
       for (const HsMultiLR& q : L.lr) {  // the transform of this sweep: Lbi, transposed Uib
         const void* tr = trans ? q.lrR : q.lrL;
         if (!tr || !q_.has(q.pos)) continue;
-        const LowRank<T>& lr = *(const LowRank<T>*)tr;
+        const LowRank<S>& lr = *(const LowRank<S>*)tr;
         if (lr.r == 0) continue;
-        lr_apply_op<T>(trans, cj, lr, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+        lr_apply_op<T, S>(trans, cj, lr, (const T*)mc->W2 + q.woff * kcw, (T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
-      level_move<T>(trans, sn, nf, 3, maxnb, a, s);
-      if (phase == HS_MULTI_CONDENSE) launch_interface_park<T>(sn, nf, 0, maxni, a, s);  // C[int, :] = y
+      level_move<T, S>(trans, sn, nf, 3, maxnb, a, s);
+      if constexpr (OWN)
+        if (phase == HS_MULTI_CONDENSE) launch_interface_park<T>(sn, nf, 0, maxni, a, s);  // C[int, :] = y
     }
     if (act && act->zoff[chunks + 1] > act->zoff[chunks])  // backward-only fronts: y = 0
       launch_sparse_zero<T>((T*)mc->W2, kcw, kc, act->zseg + act->zoff[chunks], (int)(act->zoff[chunks + 1] - act->zoff[chunks]), act->zmaxni[chunks], s);
@@ -337,28 +365,29 @@ void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int
       if (L.nfronts == 0 || L.maxni == 0) continue;
       const LevelSel q_ = level_sel(L, mc->d_aux + mc->aux_off[lv], act, chunks, lv, 1);
       if (q_.nf == 0 || q_.maxni == 0) continue;
-      const SolveNode<T>* sn = (const SolveNode<T>*)q_.sn;
+      const SolveNode<S>* sn = (const SolveNode<S>*)q_.sn;
       const int nf = q_.nf, maxni = q_.maxni, maxnb = q_.maxnb;
       a.wbase = L.wbase;
       a.aux = q_.aux;
-      if (phase == HS_MULTI_EXPAND) launch_interface_park<T>(sn, nf, 1, maxni, a, s);  // y = C[int, :]
-      level_move<T>(trans, sn, nf, 1, maxnb, a, s);
-      level_step<T>(trans, cj, sn, nf, HSM_UR, HSMT_LB, 0, maxni, a, s);
+      if constexpr (OWN)
+        if (phase == HS_MULTI_EXPAND) launch_interface_park<T>(sn, nf, 1, maxni, a, s);  // y = C[int, :]
+      level_move<T, S>(trans, sn, nf, 1, maxnb, a, s);
+      level_step<T, S>(trans, cj, sn, nf, HSM_UR, HSMT_LB, 0, maxni, a, s);
       for (const HsMultiLR& q : L.lr) {  // Uib, transposed Lbi
         const void* tr = trans ? q.lrL : q.lrR;
         if (!tr || !q_.has(q.pos)) continue;
-        const LowRank<T>& lr = *(const LowRank<T>*)tr;
+        const LowRank<S>& lr = *(const LowRank<S>*)tr;
         if (lr.r == 0) continue;
-        lr_apply_op<T>(trans, cj, lr, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+        lr_apply_op<T, S>(trans, cj, lr, (const T*)mc->XB + boff_of(L, q.pos) * kcw, (T*)mc->W1 + (q.woff - L.wbase) * kcw, (T*)mc->T1, kcw, kc, fc, s);
       }
       const int nblk = (maxni + 255) / 256;
       for (int j = nblk - 1; j >= 0; --j) {
         const int wl = std::min(256, maxni - j * 256);
-        if (left) launch_multi_level_t<T>(sn, nf, HSMT_LEFT_L, j, cj, 256, a, s);
-        level_step<T>(trans, cj, sn, nf, HSM_DIAG_U, HSMT_DIAG_L, j, wl, a, s);
-        if (!left) level_step<T>(trans, cj, sn, nf, HSM_ABOVE_U, HSMT_ABOVE_L, j, j * 256, a, s);
+        if (left) MultiSide<T, S>::level_t(sn, nf, HSMT_LEFT_L, j, cj, 256, a, s);
+        level_step<T, S>(trans, cj, sn, nf, HSM_DIAG_U, HSMT_DIAG_L, j, wl, a, s);
+        if (!left) level_step<T, S>(trans, cj, sn, nf, HSM_ABOVE_U, HSMT_ABOVE_L, j, j * 256, a, s);
       }
-      level_move<T>(trans, sn, nf, 2, maxni, a, s);
+      level_move<T, S>(trans, sn, nf, 2, maxni, a, s);
       each_front(L, q_, [&](const HsMultiFront& f) {
         if (f.dense_bnd) fc.add(f.ni, f.nb, kc);
         for (int j = 0; j * 256 < f.ni; ++j) {
@@ -373,8 +402,20 @@ void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int
     }
     if (act && act->end) act->end(act->ctx, chunks, kc, s);
   }
-  multi_finish(mc, v, fc, chunks, sizeof(T), s);
+  multi_finish(mc, v, fc, chunks, sizeof(S), s);
 }
+}  // namespace
+
+template <class T>
+void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act, int phase) {
+  multi_run<T, T>(v, trans, dC, ldc, nrhs, s, act, phase);
+}
+template <class T>
+void hs_solve_multi_run_f32(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+  multi_run<T, typename F32Of<T>::type>(v, trans, dC, ldc, nrhs, s, nullptr, HS_MULTI_ALL);
+}
+template void hs_solve_multi_run_f32<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t);
+template void hs_solve_multi_run_f32<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t);
 template void hs_solve_multi_run<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t, const HsMultiActive*, int);
 template void hs_solve_multi_run<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t, const HsMultiActive*, int);
 

@@ -865,6 +865,94 @@ extern "C" int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double
   return multi_prob_t_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
 }
 
+// The same two products over a Float32 panel (kernels_solve_multi_f32.hip): A arrives in Float64, is demoted on the device by the library's
+// demotion kernel (kernels_f32.hip) into a copy with the leading dimension hs_f32_create would give it, and the product reads the copy.
+#include "hs_f32.h"
+template <class T, class Launch>
+static int multi_prob_f32_stage(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx, T* C,
+                                int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
+  typedef typename F32Of<T>::type S;
+  constexpr int RE = sizeof(T) / 8;
+  const long long ldd = RE == 2 ? std::max<long long>(arows, 1) : hs_f32_ld(arows);
+  S* dS = nullptr;
+  unsigned long long* dcnt = nullptr;
+  F32Job* djob = nullptr;
+  int gpus = 0;
+  if (hipGetDeviceCount(&gpus) == hipSuccess && gpus > 0 && arows >= 1 && acols >= 0 && lda >= arows) {  // (the staging below refuses everything else)
+    CK(hipMalloc((void**)&dS, sizeof(S) * (size_t)ldd * std::max<int64_t>(acols, 1)));
+    CK(hipMalloc((void**)&dcnt, 2 * sizeof(unsigned long long)));
+    CK(hipMalloc((void**)&djob, sizeof(F32Job)));
+    CK(hipMemset(dcnt, 0, 2 * sizeof(unsigned long long)));
+  }
+  const int st = multi_prob_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
+    if (K > 0) {
+      const F32Job job{(const double*)dA, (void*)dS, (long long)lda * RE, ldd * RE, (int)arows * RE, (int)acols};
+      (void)hipMemcpy(djob, &job, sizeof job, hipMemcpyHostToDevice);
+      launch_f32_demote(djob, 1, job.rows, job.cols, false, dcnt, 0);
+    }
+    launch(dS, (int)ldd, dX, dC, dmap, P);
+  });
+  (void)hipFree(dS);
+  (void)hipFree(dcnt);
+  (void)hipFree(djob);
+  return st;
+}
+template <class T>
+static int multi_prob_f32_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, const int32_t* map) {
+  typedef typename F32Of<T>::type S;
+  return multi_prob_f32_stage<T>("hsk_multi_prob_f32", M, K, kc, A, lda, M, K, X, ldx, C, ldc, map, M, [&](const S* dA, int ldd, const T* dX, T* dC, const int* dmap, int64_t P) {
+    MultiProbF32<T> p;
+    memset(&p, 0, sizeof p);
+    p.A = dA; p.lda = ldd; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0;
+    p.X = dX; p.xrs = P;
+    p.Cin = minus ? dC : nullptr;
+    p.C = dC; p.crs = P; p.cmap = dmap;
+    launch_multi_prob_f32<T>(p, (int)kc, 0);
+  });
+}
+template <class T>
+static int multi_prob_t_f32_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj,
+                                 const int32_t* map) {
+  typedef typename F32Of<T>::type S;
+  return multi_prob_f32_stage<T>("hsk_multi_prob_t_f32", M, K, kc, A, lda, K, M, X, ldx, C, ldc, map, K, [&](const S* dA, int ldd, const T* dX, T* dC, const int* dmap, int64_t P) {
+    MultiProbTF32<T> p;
+    memset(&p, 0, sizeof p);
+    p.A = dA; p.lda = ldd; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
+    p.X = dX; p.xrs = P; p.xmap = dmap;
+    p.Cin = minus ? dC : nullptr;
+    p.C = dC; p.crs = P;
+    launch_multi_prob_t_f32<T>(p, (int)kc, 0);
+  });
+}
+extern "C" int hsk_multi_prob_f32_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                    int64_t ldc, int minus, int trap, const int32_t* map) {
+  return multi_prob_f32_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map);
+}
+extern "C" int hsk_multi_prob_f32_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                    int64_t ldc, int minus, int trap, const int32_t* map) {
+  return multi_prob_f32_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map);
+}
+extern "C" int hsk_multi_prob_t_f32_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                      int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
+  return multi_prob_t_f32_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map);
+}
+extern "C" int hsk_multi_prob_t_f32_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                      int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
+  return multi_prob_t_f32_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
+}
+// x <- (double)(float)x for every stored element hs_f32_create would demote, in place in the handle (hs_f32.hip)
+extern "C" int hsk_round_factors_f32(hs_handle* F, int64_t* counts2) {
+  try {
+    hs_f32_round_in_place(F, counts2);
+    return HS_OK;
+  } catch (int code) {
+    return code;
+  } catch (const std::bad_alloc&) {
+    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
+    return HS_ERR_NOMEM;
+  }
+}
+
 // one grouped launch of the transposed ULV product (kernels_ulv_t.hip) on caller-supplied jobs (include/hs_kernels.h)
 #include "hs_ulv_t.h"
 template <class T>

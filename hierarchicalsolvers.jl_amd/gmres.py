@@ -131,11 +131,20 @@ def gmres_block(A, B, Pr=None, reltol=None, abstol=0.0, restart=None, maxiter=No
     ``maxiter`` when ``n`` and ``nrhs`` are both large (the default is ``n``).  ``trans``, ``Pr=transpose(F)`` / ``adjoint(F)`` and ``A=None``
     as in :func:`gmres` (``hs_gmres_block_t_{d,z}``, the block solve ``hs_ldiv_block_dev_t_*``).  ``Pr`` may be a :class:`ModifiedFactor`
     (:func:`modify`): ``A`` is then the modified matrix ``A1`` itself (``A=None`` raises ``ValueError``: the handle holds the old ``A``) and
-    every step applies ``op(A1)^-1`` through ``hs_mod_ldiv_dev_*`` (``hs_gmres_block_mod_{d,z}``)."""
-    from .solver import ModifiedFactor
+    every step applies ``op(A1)^-1`` through ``hs_mod_ldiv_dev_*`` (``hs_gmres_block_mod_{d,z}``).  ``Pr`` may be a :class:`DemotedFactor`
+    (:func:`demote`): every step applies ``op(F)^-1`` from the Float32 copy of the factors (``hs_gmres_block_f32_{d,z}``) while the Krylov
+    solver stays Float64; ``A`` must be given (``A=None`` raises ``ValueError``: the copy holds no matrix)."""
+    from .solver import DemotedFactor, ModifiedFactor
 
     mod = Pr if isinstance(Pr, ModifiedFactor) else None
-    if mod is not None:  # Pr = hs.modify(F, ...): A is the MODIFIED matrix, the preconditioner hs_mod_ldiv_dev_* (hs_gmres_block_mod_*)
+    dem = Pr if isinstance(Pr, DemotedFactor) else None
+    if dem is not None:  # Pr = hs.demote(F): the preconditioner hs_f32_ldiv_dev_* (hs_gmres_block_f32_*)
+        if trans is not None and trans not in _TRANS:
+            raise ValueError(f"trans must be 'N', 'T' or 'C', not {trans!r}")
+        if A is None:
+            raise ValueError("ArgumentError: A=None with Pr a DemotedFactor: a demoted factorization holds no matrix; pass A")
+        tcode = 0 if trans is None else _TRANS[trans]
+    elif mod is not None:  # Pr = hs.modify(F, ...): A is the MODIFIED matrix, the preconditioner hs_mod_ldiv_dev_* (hs_gmres_block_mod_*)
         if trans is not None and trans not in _TRANS:
             raise ValueError(f"trans must be 'N', 'T' or 'C', not {trans!r}")
         if A is None:
@@ -170,7 +179,10 @@ def gmres_block(A, B, Pr=None, reltol=None, abstol=0.0, restart=None, maxiter=No
     tail = (vp(Bm), n, vp(X), n, k, 0, int(X0 is not None), -1.0 if reltol is None else float(reltol), float(abstol), -1 if restart is None else int(restart), maxit,
             hist.ctypes.data_as(_lib.p_f64) if log else None, iters.ctypes.data_as(_lib.p_i64), conv.ctypes.data_as(C.POINTER(C.c_int)), None)
     h = Pr._h if Pr is not None else None
-    if mod is not None:
+    if dem is not None:
+        fn = L.hs_gmres_block_f32_z if cplx else L.hs_gmres_block_f32_d
+        _lib.check(fn(h, tcode, n, colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz), *tail))
+    elif mod is not None:
         fn = L.hs_gmres_block_mod_z if cplx else L.hs_gmres_block_mod_d
         _lib.check(fn(h, tcode, n, colptr.ctypes.data_as(_lib.p_i64), rowval.ctypes.data_as(_lib.p_i64), vp(nz), *tail))
     elif tcode == 0 and A is not None:

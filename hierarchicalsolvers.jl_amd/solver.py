@@ -571,6 +571,100 @@ def ldiv_mod(*args, trans="N"):
     return res
 
 
+class DemotedFactor:
+    """A stand-alone copy of a factorization with its stored factors in Float32 (ComplexF32 for a ComplexF64 ``F``): made by :func:`demote`,
+    consumed by :func:`ldiv_f32` and by ``gmres_block(A, B, Pr=G)`` (``hs_f32``, include/hs_solver.h).  It keeps no reference to ``F``,
+    which may be freed; right-hand sides, results and every accumulation stay Float64 / ComplexF64."""
+
+    def __init__(self, handle, dtype, n):
+        self._h = handle
+        self.dtype = np.dtype(dtype)
+        self.n = int(n)
+
+    def __del__(self):
+        self.free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def free(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _lib.lib().hs_f32_free(h)
+
+    @property
+    def shape(self):
+        return (self.n, self.n)
+
+    @property
+    def nbytes(self):
+        """Device bytes the copy holds: Float32 values plus indices, descriptors and padding (the work blocks of the solve apart)."""
+        i = self.info()
+        return i["value_bytes"] + i["index_bytes"]
+
+    def info(self):
+        """``hs_f32_info``: device seconds of the last solve, Float32 value bytes, the Float64 bytes of the same elements in ``F`` (twice
+        that), index / descriptor / padding bytes, work-block bytes, elements flushed to zero or a subnormal, chunks of the last solve,
+        seconds of the demotion."""
+        out = np.zeros(8)
+        _lib.check(_lib.lib().hs_f32_info(self._h, _pf64(out)))
+        return {"solve_seconds": float(out[0]), "value_bytes": int(out[1]), "f64_bytes": int(out[2]), "index_bytes": int(out[3]), "workspace_bytes": int(out[4]),
+                "flushed": int(out[5]), "chunks": int(out[6]), "demote_seconds": float(out[7])}
+
+    def __repr__(self):
+        return f"DemotedFactor{{{'ComplexF32' if self.dtype.kind == 'c' else 'Float32'}}}({self.n} x {self.n})"
+
+
+def demote(F):
+    """A :class:`DemotedFactor` of the plain :class:`FactorNode` ``F`` (``hs_f32_create``): every stored factor element rounded once to
+    Float32.  ``F`` must be a handle :func:`ldiv_block_t` serves (:class:`UnsupportedError` otherwise, and when a stored element overflows
+    Float32: scale the matrix).  ``F`` is left as it is and may be freed afterwards."""
+    if not isinstance(F, FactorNode):
+        raise TypeError(f"expected a FactorNode, got {type(F).__name__}")
+    h = C.c_void_p()
+    _lib.check(_lib.lib().hs_f32_create(F._h, None, C.byref(h)))
+    return DemotedFactor(h, F.dtype, F.n)
+
+
+def ldiv_f32(*args, trans="N"):
+    """``ldiv_f32(G, B, trans="N")`` / ``ldiv_f32(C, G, B, trans=...)``: ``C = op(F)^-1 B`` from the Float32 factors of a
+    :class:`DemotedFactor` ``G`` (``hs_f32_ldiv_*``), with the shape and dtype rules of :func:`ldiv_block_t`; ``trans`` as in
+    :func:`ldiv_mod`.  The result is Float64 / ComplexF64 and carries the rounding of the factors (about ``cond(A) 2^-24`` relative):
+    ``gmres_block(A, B, Pr=G)`` recovers full accuracy."""
+    if len(args) == 2:
+        G, B = args
+        Cout = None
+    elif len(args) == 3:
+        Cout, G, B = args
+    else:
+        raise TypeError("ldiv_f32(G, B) or ldiv_f32(C, G, B)")
+    if not isinstance(G, DemotedFactor):
+        raise TypeError(f"expected a DemotedFactor, got {type(G).__name__}")
+    if trans not in _MOD_TRANS:
+        raise ValueError(f"trans must be None, 'N', 'T', 'C' or 'H', got {trans!r}")
+    B = np.asarray(B)
+    if B.shape[0] != G.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {B.shape[0]} rows, F is {G.n} x {G.n}")
+    if B.dtype != G.dtype:
+        if G.dtype.kind == "f" and B.dtype.kind == "c":
+            raise TypeError("MethodError: no method matching ldiv!(::Array{ComplexF64}, ::DemotedFactor{Float32}, ::Array{ComplexF64})")
+        B = B.astype(G.dtype)
+    vec = B.ndim == 1
+    Bm = np.asfortranarray(B.reshape(G.n, -1))
+    Cm = np.empty_like(Bm, order="F")
+    fn = getattr(_lib.lib(), "hs_f32_ldiv" + ("_z" if G.dtype.kind == "c" else "_d"))
+    _lib.check(fn(G._h, _MOD_TRANS[trans], Cm.ctypes.data_as(_lib.p_f64), G.n, Bm.ctypes.data_as(_lib.p_f64), G.n, G.n, Bm.shape[1]))
+    res = Cm[:, 0] if vec else Cm
+    if Cout is not None:
+        Cout[...] = res
+        return Cout
+    return res
+
+
 def eigs_info():
     """Figures of this thread's last :func:`eigs` call (``hs_eigs_info``)."""
     out = np.zeros(8)

@@ -110,6 +110,24 @@ int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_
 int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
                        int minus, int trap, int conj, const int32_t* map);
 
+/* The two panel products over a Float32 panel (kernels_solve_multi_f32.hip; hs_f32_*, include/hs_solver.h) on host data: the arguments of
+ * hsk_multi_prob_* / hsk_multi_prob_t_*.  A is given in Float64 (ComplexF64) and demoted on the device by the library's demotion kernel
+ * (round to nearest even, real and imaginary parts separately) before the product reads it; X, C and the accumulation stay Float64.  On
+ * the same rounded values the result has the bits of hsk_multi_prob_* / hsk_multi_prob_t_*. */
+int hsk_multi_prob_f32_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                         int minus, int trap, const int32_t* map);
+int hsk_multi_prob_f32_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                         int minus, int trap, const int32_t* map);
+int hsk_multi_prob_t_f32_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                           int minus, int trap, int conj, const int32_t* map);
+int hsk_multi_prob_t_f32_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                           int minus, int trap, int conj, const int32_t* map);
+/* Rounds IN PLACE, through the job list and the conversion of hs_f32_create, every stored element of F that a demoted copy would hold:
+ * x <- (double)(float)x.  F stays an ordinary Float64 handle (to be thrown away afterwards): hs_ldiv_block_t_* on it returns the bits
+ * hs_f32_ldiv_* returns on a copy demoted from the unrounded factors.  counts2 = {elements finite in Float64 that overflow Float32 (they
+ * become +-Inf here), nonzero elements that became zero or subnormal}.  Refuses what hs_f32_create refuses of the handle. */
+int hsk_round_factors_f32(hs_handle* F, int64_t* counts2);
+
 /* The product of hs_interface_matrix_* (kernels_interface.hip) on host data: S[rperm[i], j] = sum over k <= min(i, j) of L[i, k] U[k, j] for the
  * packed factors LF (nb x nb, column-major, ldl >= nb; unit lower L below the diagonal, U on and above it), rperm nb distinct entries in
  * 0..nb-1 ((P x)[i] = x[rperm[i]]; an entry outside gives HS_ERR_ARGUMENT), S nb x nb column-major with lds >= nb (rows past nb are left as

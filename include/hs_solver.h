@@ -334,6 +334,40 @@ int hs_mod_ldiv_dev_z(hs_mod* M, int trans, double* dC, int64_t ldc, const doubl
 int hs_mod_info(hs_mod* M, double* out8);
 void hs_mod_free(hs_mod* M);
 
+/* ---- a factorization with its stored factors in Float32 (hs_f32.hip) ----------------------------------------------------------------------
+ * hs_f32_create makes a stand-alone DEMOTED COPY G of a factorization F: everything the block solve reads, stored in Float32 (ComplexF32
+ * for a ComplexF64 handle) -- per front the packed LU of the interior block with the boundary rows of L below it, the boundary columns of
+ * U (where the Gauss transforms are dense), the inverted 256 x 256 diagonal blocks of L and U; per low-rank Gauss transform its two
+ * generators; the row permutations and index lists as they are.  Every element is rounded once, to nearest even.  G keeps no pointer into
+ * F: F may be freed (hs_free, hs_trim) and G goes on solving, with the same bits.  F itself is not changed.
+ * hs_f32_ldiv_* solves op(F) X = B (trans 0: F, 1: transpose(F), 2: adjoint(F)) with the schedule of hs_ldiv_block_t_*: chunks of
+ * HS_LDIV_BLOCK_COLS columns, the same work blocks, the same products.  Right-hand sides, work blocks, accumulators and results are
+ * Float64 / ComplexF64; a factor element is widened in a register on its way into v_mfma_f64_16x16x4_f64, which is exact.  What is lost is
+ * the rounding of the factors: one solve carries a relative error of about cond(A) 2^-24.  hs_gmres_block_f32_* puts a full-precision
+ * Krylov solver on top.
+ * Bitwise statements: the summation order of every output element is that of hs_ldiv_block_t_*, so G returns the bits hs_ldiv_block_t_*
+ * returns on a handle whose stored factors hold the rounded values (hsk_round_factors_f32, include/hs_kernels.h, makes one); two calls
+ * return the same bits; X[:, c] depends neither on the other columns nor on their number; C may alias B; nrhs = 0 touches nothing.
+ * Refused, with *G = NULL: what hs_ldiv_block_dev_t_* refuses (HSS interior blocks, more than one rank, an unfactored or plan-only handle),
+ * found by a zero-column solve and reported with its status and message; a stored element that is finite in Float64 and overflows Float32:
+ * HS_ERR_UNSUPPORTED, the count in the message and in hs_last_error_info (scale the matrix).  Elements that become zero or subnormal are
+ * counted and reported (hs_f32_info), not refused.  The solves refuse a null object, trans outside 0..2, an element type that does not
+ * match the _d / _z suffix (HS_ERR_ARGUMENT) and n != size(F), leading dimensions below n, negative sizes (HS_ERR_DIMENSION), before any
+ * device work and with C unwritten.  Calls on one object must not overlap (it owns one set of work blocks).
+ * hs_f32_create returns when the copy is complete (stream: where the demotion runs); the _dev_ solves take device blocks and return with
+ * the solve queued on their stream. */
+typedef struct hs_f32 hs_f32;
+int hs_f32_create(hs_handle* F, void* stream, hs_f32** G);
+int hs_f32_ldiv_d(hs_f32* G, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_f32_ldiv_z(hs_f32* G, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_f32_ldiv_dev_d(hs_f32* G, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+int hs_f32_ldiv_dev_z(hs_f32* G, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+/* out8 = {device seconds of the last solve, Float32 value bytes held (the demoted elements, 4 bytes per real scalar), the Float64 bytes of
+ * the same elements in F (exactly twice that), index, descriptor and alignment-padding bytes, work-block bytes, elements flushed to zero
+ * or to a subnormal, column chunks of the last solve, seconds of the demotion} */
+int hs_f32_info(hs_f32* G, double* out8);
+void hs_f32_free(hs_f32* G);
+
 /* ---- eigenpairs nearest a shift from the stored factors (hs_eigs.hip) --------------------------------------------------------------
  * F factors A_s = A - sigma I (the caller subtracts the shift before factoring; sigma is bookkeeping, so that lambda comes back unshifted).
  * The call returns the nev eigenvalues of A nearest sigma -- the eigenvalues theta of op(F)^-1 of largest modulus, mu = 1 / theta,
@@ -682,6 +716,16 @@ int hs_gmres_block_mod_d(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr
                          int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
                          int* converged, void* stream);
 int hs_gmres_block_mod_z(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
+                         int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
+                         int* converged, void* stream);
+/* hs_gmres_block_t_* right-preconditioned by a demoted copy of the factorization: op(A) X = B with op(F)^-1 applied by hs_f32_ldiv_dev_*
+ * from Float32 factors, the Krylov spaces, residuals and the solution in Float64 / ComplexF64.  A must be given (CSC, 1-based, as above): the
+ * object holds no matrix, and colptr / rowval / nzval == NULL is HS_ERR_ARGUMENT.  A size or element type of A and B that is not the
+ * object's: HS_ERR_DIMENSION.  Everything else as hs_gmres_block_t_*; hs_gmres_block_info reports the call. */
+int hs_gmres_block_f32_d(hs_f32* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
+                         int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
+                         int* converged, void* stream);
+int hs_gmres_block_f32_z(hs_f32* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
                          int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters,
                          int* converged, void* stream);
 /* the calling thread's last hs_gmres_block_* / hs_gmres_block_t_* call: out8 = {seconds on the device, block preconditioner calls, column-applications summed over
