@@ -1,11 +1,7 @@
-// hs_f32.h -- a factorization demoted to Float32 storage (hs_f32_*, hs_f32.hip; include/hs_solver.h): the element types, the launch API of
-// kernels_f32.hip (the demotion) and of kernels_solve_multi_f32.hip (the panel products of the block solve with the factor panel read as
-// Float32 / ComplexF32 and everything else -- X, Cin, D, the accumulators -- as Float64 / ComplexF64), and what hs_solve_multi.hip,
-// hs_gmres_block.hip and the test hooks see of the object.
-//
-// T is the element type of the work blocks (double, cplx), S = F32Of<T>::type that of the stored factors (float, cplxf).  A SolveNode<S> and
-// a LowRank<S> have the layout of their <T> forms (pointers and integers only): the demoted object keeps arrays of them, filled with its
-// own copies.
+// hs_f32.h -- a factorization demoted to Float32 storage (hs_f32_*, hs_f32.hip; include/hs_solver.h): the launch API of kernels_f32.hip
+// (the demotion), and what hs_solve_multi.hip, hs_gmres_block.hip and the test hooks see of the object.  The element types (cplxf,
+// F32Of<T>) and the panel products over a Float32 / ComplexF32 panel are those of hs_solve_multi.h with S = F32Of<T>::type: the demoted
+// object keeps arrays of SolveNode<S> and LowRank<S>, filled with its own copies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,21 +11,6 @@
 #include "hs_common.h"
 #include "hs_lowrank.h"
 #include "hs_solve_multi.h"
-
-struct cplxf {
-  float re, im;
-};
-template <class T>
-struct F32Of;
-template <>
-struct F32Of<double> {
-  typedef float type;
-};
-template <>
-struct F32Of<cplx> {
-  typedef cplxf type;
-};
-static_assert(sizeof(SolveNode<float>) == sizeof(SolveNode<double>) && sizeof(SolveNode<cplxf>) == sizeof(SolveNode<cplx>), "SolveNode<S> has the layout of SolveNode<T>");
 
 // ---- kernels_f32.hip: the demotion ------------------------------------------------------------------------------------------------------
 // One block of REAL scalars (a ComplexF64 block is one of twice as many rows): rows x cols, column-major.  dst is Float32 with ld ldd (even,
@@ -50,47 +31,6 @@ struct F32IntJob {
   int count, pad;
 };
 void launch_f32_copy_int(const F32IntJob* jobs, int njobs, int maxcount, hipStream_t s);
-
-// ---- kernels_solve_multi_f32.hip ---------------------------------------------------------------------------------------------------------
-// MultiProb<T> / MultiProbT<T> (hs_solve_multi.h) with A stored as S
-template <class T>
-struct MultiProbF32 {
-  const typename F32Of<T>::type* A;
-  int lda, M, K;
-  int trap;
-  const T* X;
-  long long xrs;
-  const T* Cin;
-  T* C;
-  long long crs;
-  const int* cmap;
-};
-template <class T>
-struct MultiProbTF32 {
-  const typename F32Of<T>::type* A;
-  int lda, M, K;
-  int trap;
-  int conj;
-  const T* X;
-  long long xrs;
-  const int* xmap;
-  const T* Cin;
-  T* C;
-  long long crs;
-  const int* cmap;
-};
-// the launches of hs_solve_multi.h over SolveNode<S>: the same modes (HSM_*, HSMT_*), grids and arguments
-template <class T>
-void launch_multi_level_f32(const SolveNode<typename F32Of<T>::type>* sn, int nfronts, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s);
-template <class T>
-void launch_multi_prob_f32(const MultiProbF32<T>& p, int kc, hipStream_t s);
-template <class T>
-void launch_multi_level_t_f32(const SolveNode<typename F32Of<T>::type>* sn, int nfronts, int mode, int blk, int conj, int maxM, const MultiArgs& a, hipStream_t s);
-template <class T>
-void launch_multi_prob_t_f32(const MultiProbTF32<T>& p, int kc, hipStream_t s);
-// launch_multi_move<T> (kernels_solve_multi.hip, unchanged) on the descriptors of a demoted object: it reads ni, woff, rperm and fidx only
-template <class T>
-void launch_multi_move_f32(const SolveNode<typename F32Of<T>::type>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm_what);
 
 // ---- hs_solve_multi.hip --------------------------------------------------------------------------------------------------------------------
 // hs_solve_multi_run on a view whose descriptors (HsMultiLevel::sn, HsMultiLR::lrL / lrR) are SolveNode<S> / LowRank<S>: the same schedule,

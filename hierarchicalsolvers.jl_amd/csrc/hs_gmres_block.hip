@@ -846,34 +846,62 @@ int gmres_block_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colpt
   return gmres_block_run<T>(make_op, PrecBlockOp<T>{F, trans}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
-// hs_gmres_block_mod_*: op(A1) X = B right-preconditioned by op(A1)^-1 as hs_mod_ldiv_dev_* applies it; A1 is the caller's CSC
+// What the entry below needs of a preconditioner object other than a handle: its names in the messages (fn, obj; mat: what the messages
+// call the matrix; csc: why it must be given), the object's own size / element type check, the handle gmres_block_check and the row form
+// of op(A) read (null: none), and the functor.
 template <class T>
-int gmres_block_mod_entry(hs_mod* M, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs,
-                          int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  const char* fn = "hs_gmres_block_mod_*";
-  if (!M) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null hs_mod", fn);
+struct PrecObjMod {  // hs_gmres_block_mod_*: op(A1) X = B right-preconditioned by op(A1)^-1 as hs_mod_ldiv_dev_* applies it
+  typedef hs_mod Obj;
+  static constexpr const char *fn = "hs_gmres_block_mod_*", *obj = "hs_mod", *mat = "A1";
+  static constexpr const char* csc = "the modified matrix A1 must be given as CSC (the handle holds the unmodified A)";
+  static int check(hs_mod*, int64_t) { return HS_OK; }
+  static hs_handle* handle(hs_mod* M) { return hs_mod_handle(M); }
+  static PrecBlockMod<T> prec(hs_mod* M, int trans) { return {hs_mod_handle(M), M, trans}; }
+};
+template <class T>
+struct PrecObjF32 {  // hs_gmres_block_f32_*: op(A) X = B right-preconditioned by op(F)^-1 as hs_f32_ldiv_dev_* applies it
+  typedef hs_f32 Obj;
+  static constexpr const char *fn = "hs_gmres_block_f32_*", *obj = "hs_f32", *mat = "A";
+  static constexpr const char* csc = "A must be given as CSC (a demoted factorization holds no matrix)";
+  static int check(hs_f32* G, int64_t n) {
+    if (hs_f32_size(G) == n && (hs_f32_is_complex(G) != 0) == (sizeof(T) == 16)) return HS_OK;
+    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld %s", (long long)hs_f32_size(G), (long long)hs_f32_size(G),
+                 hs_f32_is_complex(G) ? "ComplexF64" : "Float64", (long long)n, (long long)n, sizeof(T) == 16 ? "ComplexF64" : "Float64");
+    return HS_ERR_DIMENSION;
+  }
+  static hs_handle* handle(hs_f32*) { return nullptr; }
+  static PrecBlockF32<T> prec(hs_f32* G, int trans) { return {reinterpret_cast<hs_handle*>(G), G, trans}; }
+};
+
+// op(A) X = B right-preconditioned by a preconditioner object other than a handle (O: above); A is the caller's CSC
+template <class T, class O>
+int gmres_block_obj_entry(typename O::Obj* P, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx,
+                          int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged,
+                          void* stream) {
+  if (!P) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null %s", O::fn, O::obj);
     return HS_ERR_ARGUMENT;
   }
   if (trans < 0 || trans > 2) {
-    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: A1, 1: transpose(A1), 2: adjoint(A1))", fn, trans);
+    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: %s, 1: transpose(%s), 2: adjoint(%s))", O::fn, trans, O::mat, O::mat, O::mat);
     return HS_ERR_ARGUMENT;
   }
   if (!colptr || !rowval || !nz) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: the modified matrix A1 must be given as CSC (the handle holds the unmodified A)", fn);
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s", O::fn, O::csc);
     return HS_ERR_ARGUMENT;
   }
   if (n <= 0 || nrhs < 0) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs n >= 1 and nrhs >= 0", fn);
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs n >= 1 and nrhs >= 0", O::fn);
     return HS_ERR_ARGUMENT;
   }
+  if (const int st = O::check(P, n)) return st;
   if (nrhs == 0) {
     for (double& v : g_info) v = 0.0;
     return HS_OK;
   }
-  hs_handle* F = hs_mod_handle(M);
+  hs_handle* F = O::handle(P);
   if (const int st = gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
-  const PrecBlockMod<T> Pr{F, M, trans};
+  const auto Pr = O::prec(P, trans);
   if (trans == 0)
     return gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
                               stream);
@@ -881,45 +909,6 @@ int gmres_block_mod_entry(hs_mod* M, int trans, int64_t n, const int64_t* colptr
   return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
-// hs_gmres_block_f32_*: op(A) X = B right-preconditioned by op(F)^-1 as hs_f32_ldiv_dev_* applies it; A is the caller's CSC (the object holds
-// no matrix)
-template <class T>
-int gmres_block_f32_entry(hs_f32* G, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs,
-                          int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  const char* fn = "hs_gmres_block_f32_*";
-  if (!G) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null hs_f32", fn);
-    return HS_ERR_ARGUMENT;
-  }
-  if (trans < 0 || trans > 2) {
-    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: A, 1: transpose(A), 2: adjoint(A))", fn, trans);
-    return HS_ERR_ARGUMENT;
-  }
-  if (!colptr || !rowval || !nz) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: A must be given as CSC (a demoted factorization holds no matrix)", fn);
-    return HS_ERR_ARGUMENT;
-  }
-  if (n <= 0 || nrhs < 0) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs n >= 1 and nrhs >= 0", fn);
-    return HS_ERR_ARGUMENT;
-  }
-  if (hs_f32_size(G) != n || (hs_f32_is_complex(G) != 0) != (sizeof(T) == 16)) {
-    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld %s", (long long)hs_f32_size(G), (long long)hs_f32_size(G),
-                 hs_f32_is_complex(G) ? "ComplexF64" : "Float64", (long long)n, (long long)n, sizeof(T) == 16 ? "ComplexF64" : "Float64");
-    return HS_ERR_DIMENSION;
-  }
-  if (nrhs == 0) {
-    for (double& v : g_info) v = 0.0;
-    return HS_OK;
-  }
-  if (const int st = gmres_block_check<T>(nullptr, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
-  const PrecBlockF32<T> Pr{reinterpret_cast<hs_handle*>(G), G, trans};
-  if (trans == 0)
-    return gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
-                              stream);
-  auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, nullptr, trans, false, n, colptr, rowval, nz, s)}; };
-  return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
-}
 
 // hsk_spmm_*: the SpMM kernel alone on host data
 template <class T>
@@ -1072,24 +1061,24 @@ extern "C" int hsk_spmm_op_z(int trans, int64_t n, const int64_t* colptr, const 
 extern "C" int hs_gmres_block_mod_d(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_block_mod_entry<double>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+  return gmres_block_obj_entry<double, PrecObjMod<double>>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
                                        stream);
 }
 extern "C" int hs_gmres_block_mod_z(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_block_mod_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
+  return gmres_block_obj_entry<cplx, PrecObjMod<cplx>>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
                                      maxiter, resnorm, iters, converged, stream);
 }
 extern "C" int hs_gmres_block_f32_d(hs_f32* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_block_f32_entry<double>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+  return gmres_block_obj_entry<double, PrecObjF32<double>>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
                                        stream);
 }
 extern "C" int hs_gmres_block_f32_z(hs_f32* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_block_f32_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
+  return gmres_block_obj_entry<cplx, PrecObjF32<cplx>>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
                                      maxiter, resnorm, iters, converged, stream);
 }

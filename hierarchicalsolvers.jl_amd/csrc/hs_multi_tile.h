@@ -1,8 +1,9 @@
-// hs_multi_tile.h -- what the panel-product kernels of the block solves share: kernels_solve_multi.hip (D = Cin - A X) and
-// kernels_solve_multi_t.hip (D = Cin - op(A)^T X) hold the same 64- / 32-row tile of D in the same registers, so the workgroup's body -- the
-// accumulators, the two chunks in flight, the exchange of the partial sums through LDS, the way D is read and written -- is written once,
-// here, over the operand loads and MFMA chains of the two files.  Device-side __forceinline__ pieces only (and the host-side choice of NT):
-// nothing in this header is a kernel, the two files stay separate translation units and every kernel stays in its own.
+// hs_multi_tile.h -- what the panel-product kernels of the block solves share: the forward product (D = Cin - A X, hs_multi_fwd.h) and the
+// transposed one (D = Cin - op(A)^T X, hs_multi_tr.h) hold the same 64- / 32-row tile of D in the same registers, so the workgroup's body --
+// the accumulators, the two chunks in flight, the exchange of the partial sums through LDS, the way D is read and written -- is written
+// once, here, over the operand loads and MFMA chains of the two sides, and the sides once over the scalar the factor panel is stored in
+// (MultiElem).  Device-side __forceinline__ pieces only (and the host-side choice of NT): nothing in this header is a kernel;
+// kernels_solve_multi.hip, kernels_solve_multi_t.hip and kernels_solve_multi_f32.hip stay separate translation units.
 //
 // The tile: acc[q][ct][g] is register g of the MFMA result of row tile q and column tile ct, i.e. column 16 ct + (lane & 15) and the row the
 // kernel's row map gives for (q, g) (C/D of v_mfma_f64_16x16x4_f64: row (lane >> 4) + 4 g of the tile).  Float64 has four row tiles,
@@ -30,6 +31,40 @@ struct MultiX<cplx> {
   typedef hs_d2u type;
   static __device__ __forceinline__ hs_d2u load(const cplx* p) { return gld2(p); }
 };
+
+// An element pair of the factor panel A, stored as S, on its way to the MFMA's A operand: the lane's row pair (forward) / k pair
+// (transposed) of a Float64 / Float32 panel, or (re, im) of one ComplexF64 / ComplexF32 element.
+//   pair, real   the loaded pair and its component type      ld2    the pair at p as one access
+//   pack         the pair -> the body's hs_d2u operand register, as raw bytes      widen    those bytes -> two doubles, at the MFMA
+// S = double, cplx: the pair is the hs_d2u itself, one 16-byte access, pack and widen are the identity.
+template <class S>
+struct MultiElem {
+  typedef hs_d2u pair;
+  typedef double real;
+  static __device__ __forceinline__ pair ld2(const S* p) { return gld2(p); }
+  static __device__ __forceinline__ hs_d2u pack(pair v) { return v; }
+  static __device__ __forceinline__ hs_d2u widen(hs_d2u a) { return a; }
+};
+// S = float, cplxf: one 8-byte access.  The demoted copies have even leading dimensions (hs_f32_ld), but a panel may start at an odd row
+// (the boundary rows of LF start at ni), so the pair type is 4-byte aligned.  The pair travels through the operand registers as its 8 raw
+// bytes (in .x of the hs_d2u; .y is dead) and is widened (v_cvt_f64_f32, exact) where the MFMAs consume it.  Widening inside load would
+// make every load's result due at once -- the convert depends on it -- and the loads of a chunk are issued before the MFMAs of the previous
+// one precisely so that they are not: 4.53 against 3.08 ms at Poisson 40^3.
+typedef float hs_f2u __attribute__((ext_vector_type(2), aligned(4)));
+struct MultiElemF32 {
+  typedef hs_f2u pair;
+  typedef float real;
+  static __device__ __forceinline__ pair ld2(const void* p) { return *(const hs_f2u HS_AS_GLOBAL*)p; }
+  static __device__ __forceinline__ hs_d2u pack(pair f) { return hs_d2u{__builtin_bit_cast(double, f), 0.0}; }
+  static __device__ __forceinline__ hs_d2u widen(hs_d2u a) {
+    const hs_f2u f = __builtin_bit_cast(hs_f2u, (double)a.x);
+    return hs_d2u{(double)f.x, (double)f.y};
+  }
+};
+template <>
+struct MultiElem<float> : MultiElemF32 {};
+template <>
+struct MultiElem<cplxf> : MultiElemF32 {};
 
 // the complex product of a chunk, four real MFMAs per k-step: a[2 ks + q] = (re, im) of the A operand of k-step ks and row tile q
 template <int NT>
@@ -71,8 +106,8 @@ __device__ __forceinline__ void multi_red_add(const double* slot, int lane, v4d 
       for (int g = 0; g < 4; ++g) acc[q][ct][g] += slot[((q * NT + ct) * 4 + g) * 64 + lane];
 }
 
-// The product of one workgroup.  K is the kernel's side of it (kernels_solve_multi.hip: MultiFwd<T>, kernels_solve_multi_t.hip: MultiTr<T>):
-//   K::Prob                               MultiProb<T> / MultiProbT<T>
+// The product of one workgroup.  K is the kernel's side of it (hs_multi_fwd.h: MultiFwd<T, S>, hs_multi_tr.h: MultiTr<T, S>):
+//   K::Prob                               MultiProb<T, S> / MultiProbT<T, S>
 //   K::STEP, K::first / K::end(wv, nch)   wave wv takes the 16-k chunks first, first + STEP, ... < end of the nch chunks of K
 //   K::load<NT>(p, kb, r0, l15, l4, a, x) the chunk at kb -> the operand registers a (A) and x (X, negated when the product is subtracted)
 //   K::mfma<NT>(a, x, acc)                acc += that chunk's product
@@ -80,10 +115,11 @@ __device__ __forceinline__ void multi_red_add(const double* slot, int lane, v4d 
 // Two chunks are in flight in two register arrays (the loads of a chunk are all issued before the MFMAs of the previous one); the partial
 // sums of the four waves meet in LDS (red: 2 x 16 NT x 64 doubles) in the fixed order (w0 + w2) + (w1 + w3); wave 0 reads Cin into its
 // accumulators before the first MFMA and stores D through cmap after the last sum: D is read once and written once, no atomics.
-// The BODY is the shared piece and its callees live in the files, not the other way round: the compiler optimizes an always-inline callee
+// The BODY is the shared piece and its callees live with the sides, not the other way round: the compiler optimizes an always-inline callee
 // on its own before it inlines it, so an accumulator-initialise or a reduce-and-store function called from two written-out bodies changes
-// the generated code of both (tried in four forms), while one body over the files' own callees compiles to the parent's instructions,
-// kernel by kernel (profiles/r18_solve_multi_refactor.txt; the argument order of K::row is part of that).
+// the generated code of both (tried in four forms), while one body over the sides' own callees compiles to the parent's instructions,
+// kernel by kernel (profiles/r18_solve_multi_refactor.txt; the argument order of K::row is part of that; the sides over S:
+// profiles/r23_solve_multi_sides.txt).
 template <class K, class T, int NT>
 __device__ __forceinline__ void multi_tile_body(const typename K::Prob& p, int kc, double* red) {
   constexpr bool CX = sizeof(T) == 16;

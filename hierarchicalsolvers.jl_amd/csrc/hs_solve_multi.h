@@ -128,12 +128,32 @@ void launch_sparse_compact(SolveNode<T>* dst, const SolveNode<T>* src, const lon
 template <class T>
 void launch_sparse_zero(T* W2, int kcw, int kc, const HsZeroSeg* seg, int nseg, int maxni, hipStream_t s);
 
+// ---- the factor scalar --------------------------------------------------------------------------------------------------------------------
+// T is the element type of the work blocks (double, cplx); S that of the stored factor panels: T itself (the handle's own factors) or
+// F32Of<T>::type (a copy demoted to Float32 storage, hs_f32.h).  A SolveNode<S> and a LowRank<S> have the layout of their <T> forms
+// (pointers and integers only).  Every problem struct, kernel and launch below is written once over the pair; kernels_solve_multi.hip and
+// kernels_solve_multi_t.hip instantiate S = T, kernels_solve_multi_f32.hip S = F32Of<T>::type.
+struct cplxf {
+  float re, im;
+};
+template <class T>
+struct F32Of;
+template <>
+struct F32Of<double> {
+  typedef float type;
+};
+template <>
+struct F32Of<cplx> {
+  typedef cplxf type;
+};
+static_assert(sizeof(SolveNode<float>) == sizeof(SolveNode<double>) && sizeof(SolveNode<cplxf>) == sizeof(SolveNode<cplx>), "SolveNode<S> has the layout of SolveNode<T>");
+
 // ---- kernels_solve_multi.hip ----------------------------------------------------------------------------------------------------------
 // One tall-skinny product  D = A X  or  D = Cin - A X  with A (M x K, column-major, a stored factor panel) read once and fed to
 // v_mfma_f64_16x16x4_f64 from registers.  X (K x kc, kc <= 64), Cin and D are rows of row-major work blocks (one pitch for all columns).
-template <class T>
+template <class T, class S = T>
 struct MultiProb {
-  const T* A;
+  const S* A;
   int lda, M, K;
   int trap;  // 1: A is the unit lower trapezoid of what is stored (LowRank::Lp)
   const T* X;
@@ -168,23 +188,24 @@ struct MultiArgs {  // what the grouped kernels need besides the level's SolveNo
 };
 __host__ __device__ constexpr int hs_multi_rows_per_wg_c(bool is_complex) { return is_complex ? 32 : 64; }  // 4 waves split K over these rows
 int hs_multi_rows_per_wg(bool is_complex);
-template <class T>
-void launch_multi_level(const SolveNode<T>* sn, int nfronts, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s);
-template <class T>
-void launch_multi_prob(const MultiProb<T>& p, int kc, hipStream_t s);
+template <class T, class S>
+void launch_multi_level(const SolveNode<S>* sn, int nfronts, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s);
+template <class T, class S>
+void launch_multi_prob(const MultiProb<T, S>& p, int kc, hipStream_t s);
 // The caller's column-major block <-> the row-major work blocks, for every front of a level:
 //   what = 0: W1 = B[int, :]   1: Xb = B[bnd, :]   2: B[int, :] = W2   3: B[bnd, :] = Xb
 // perm_what names the one interior move that goes through the front's row permutation (B[int[rperm[i]], :] <-> row i of the work block):
 // 0 for the forward solve (W1 = (P B)[int, :]), 2 for the transposed / adjoint one (B[int, :] = P^T W2); no other value is served.
-template <class T>
-void launch_multi_move(const SolveNode<T>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm_what);
+// One kernel per T whatever S is: it reads ni, woff, rperm and fidx of a descriptor, which SolveNode<S> holds where SolveNode<T> does.
+template <class T, class S>
+void launch_multi_move(const SolveNode<S>* sn, int nfronts, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm_what);
 
 // ---- kernels_solve_multi_t.hip --------------------------------------------------------------------------------------------------------
 // The product of the transposed / adjoint block solve:  D = op(A)^T X  or  D = Cin - op(A)^T X  with A stored K x M column-major (the
 // reduction index is the contiguous one), op = identity or conj; X, Cin and D as above.
-template <class T>
+template <class T, class S = T>
 struct MultiProbT {
-  const T* A;
+  const S* A;
   int lda, M, K;    // M outputs = columns of A, K = rows of A
   int trap;         // 1: A is the unit lower trapezoid of what is stored (LowRank::Lp, K x M)
   int conj;         // 1: op = conj (ComplexF64)
@@ -206,7 +227,7 @@ enum {
   HSMT_ABOVE_L,     // W[above j] -= op(L11[j, above])^T X_j              (right-looking)
   HSMT_LEFT_L,      // W_j -= op(L11[below j, j])^T X[below j]            (left-looking)
 };
-template <class T>
-void launch_multi_level_t(const SolveNode<T>* sn, int nfronts, int mode, int blk, int conj, int maxM, const MultiArgs& a, hipStream_t s);
-template <class T>
-void launch_multi_prob_t(const MultiProbT<T>& p, int kc, hipStream_t s);
+template <class T, class S>
+void launch_multi_level_t(const SolveNode<S>* sn, int nfronts, int mode, int blk, int conj, int maxM, const MultiArgs& a, hipStream_t s);
+template <class T, class S>
+void launch_multi_prob_t(const MultiProbT<T, S>& p, int kc, hipStream_t s);

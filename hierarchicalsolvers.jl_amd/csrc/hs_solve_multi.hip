@@ -98,39 +98,15 @@ struct FlopCount {
   }
 };
 
-// The factor scalar S of a run: T itself (the handle's own factors), or F32Of<T>::type (a demoted copy, hs_f32.h) -- the problem structs and
-// launches of the second are those of kernels_solve_multi_f32.hip.  Everything below is written once over the pair.
-template <class T, class S>
-struct MultiSide {
-  typedef MultiProb<T> Prob;
-  typedef MultiProbT<T> ProbT;
-  static void prob(const Prob& p, int kc, hipStream_t s) { launch_multi_prob<T>(p, kc, s); }
-  static void prob_t(const ProbT& p, int kc, hipStream_t s) { launch_multi_prob_t<T>(p, kc, s); }
-  static void move(const SolveNode<S>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm) { launch_multi_move<T>(sn, nf, what, maxrows, a, s, perm); }
-  static void level(const SolveNode<S>* sn, int nf, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s) { launch_multi_level<T>(sn, nf, mode, blk, maxM, a, s); }
-  static void level_t(const SolveNode<S>* sn, int nf, int mode, int blk, int cj, int maxM, const MultiArgs& a, hipStream_t s) { launch_multi_level_t<T>(sn, nf, mode, blk, cj, maxM, a, s); }
-};
-template <class T>
-struct MultiSide<T, typename F32Of<T>::type> {
-  typedef typename F32Of<T>::type S;
-  typedef MultiProbF32<T> Prob;
-  typedef MultiProbTF32<T> ProbT;
-  static void prob(const Prob& p, int kc, hipStream_t s) { launch_multi_prob_f32<T>(p, kc, s); }
-  static void prob_t(const ProbT& p, int kc, hipStream_t s) { launch_multi_prob_t_f32<T>(p, kc, s); }
-  static void move(const SolveNode<S>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s, int perm) { launch_multi_move_f32<T>(sn, nf, what, maxrows, a, s, perm); }
-  static void level(const SolveNode<S>* sn, int nf, int mode, int blk, int maxM, const MultiArgs& a, hipStream_t s) { launch_multi_level_f32<T>(sn, nf, mode, blk, maxM, a, s); }
-  static void level_t(const SolveNode<S>* sn, int nf, int mode, int blk, int cj, int maxM, const MultiArgs& a, hipStream_t s) { launch_multi_level_t_f32<T>(sn, nf, mode, blk, cj, maxM, a, s); }
-};
-
 // t = Z x (r x kc, in T1), then dst -= C t with C dense or the unit trapezoid of the packed sketch; x, dst: rows of the work blocks
 template <class T, class S>
 void lr_apply(const LowRank<S>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
-  typename MultiSide<T, S>::Prob p;
+  MultiProb<T, S> p;
   memset(&p, 0, sizeof p);
   p.A = lr.Z; p.lda = lr.ldz; p.M = lr.r; p.K = lr.cols;
   p.X = x; p.xrs = kcw;
   p.C = tbuf; p.crs = kcw;
-  MultiSide<T, S>::prob(p, kc, s);
+  launch_multi_prob<T, S>(p, kc, s);
   fc.add(lr.r, lr.cols, kc);
   memset(&p, 0, sizeof p);
   if (lr.Cd) {
@@ -141,7 +117,7 @@ void lr_apply(const LowRank<S>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc
   p.M = lr.rows; p.K = lr.r;
   p.X = tbuf; p.xrs = kcw;
   p.Cin = dst; p.C = dst; p.crs = kcw;
-  MultiSide<T, S>::prob(p, kc, s);
+  launch_multi_prob<T, S>(p, kc, s);
   fc.add(lr.rows, lr.r, kc);
 }
 
@@ -203,7 +179,7 @@ void multi_finish(MultiCache* mc, const HsMultiView& v, const FlopCount& fc, int
 // C^T x = trap(Lp)^T (P x) -- the INPUT rows are gathered through rperm, where lr_apply scatters its output
 template <class T, class S>
 void lr_apply_t(const LowRank<S>& lr, int conj, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
-  typename MultiSide<T, S>::ProbT p;
+  MultiProbT<T, S> p;
   memset(&p, 0, sizeof p);
   if (lr.Cd) {
     p.A = lr.Cd; p.lda = lr.ldc;
@@ -213,13 +189,13 @@ void lr_apply_t(const LowRank<S>& lr, int conj, const T* x, T* dst, T* tbuf, int
   p.M = lr.r; p.K = lr.rows; p.conj = conj;
   p.X = x; p.xrs = kcw;
   p.C = tbuf; p.crs = kcw;
-  MultiSide<T, S>::prob_t(p, kc, s);
+  launch_multi_prob_t<T, S>(p, kc, s);
   fc.add(lr.r, lr.rows, kc);
   memset(&p, 0, sizeof p);
   p.A = lr.Z; p.lda = lr.ldz; p.M = lr.cols; p.K = lr.r; p.conj = conj;
   p.X = tbuf; p.xrs = kcw;
   p.Cin = dst; p.C = dst; p.crs = kcw;
-  MultiSide<T, S>::prob_t(p, kc, s);
+  launch_multi_prob_t<T, S>(p, kc, s);
   fc.add(lr.cols, lr.r, kc);
 }
 
@@ -257,14 +233,14 @@ bool multi_t_left_looking() {
 // the grouped launches of either direction: trans = 0 runs kernels_solve_multi.hip (mode n), trans = 1, 2 kernels_solve_multi_t.hip (mode t)
 template <class T, class S>
 void level_move(int trans, const SolveNode<S>* sn, int nf, int what, int maxrows, const MultiArgs& a, hipStream_t s) {
-  MultiSide<T, S>::move(sn, nf, what, maxrows, a, s, trans ? 2 : 0);
+  launch_multi_move<T, S>(sn, nf, what, maxrows, a, s, trans ? 2 : 0);
 }
 template <class T, class S>
 void level_step(int trans, int cj, const SolveNode<S>* sn, int nf, int mode_n, int mode_t, int blk, int maxM, const MultiArgs& a, hipStream_t s) {
   if (trans)
-    MultiSide<T, S>::level_t(sn, nf, mode_t, blk, cj, maxM, a, s);
+    launch_multi_level_t<T, S>(sn, nf, mode_t, blk, cj, maxM, a, s);
   else
-    MultiSide<T, S>::level(sn, nf, mode_n, blk, maxM, a, s);
+    launch_multi_level<T, S>(sn, nf, mode_n, blk, maxM, a, s);
 }
 template <class T, class S>
 void lr_apply_op(int trans, int cj, const LowRank<S>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {
@@ -290,7 +266,7 @@ void lr_apply_op(int trans, int cj, const LowRank<S>& lr, const T* x, T* dst, T*
 // column panel above / below the block with K up to ni and 256 outputs: W is written once per block, by four workgroups per front
 // (DESIGN.md section 4a⁗″).
 //
-// S: the scalar the factors are stored in (MultiSide).  A demoted copy (S != T) has no active set, no phases and no HSS fronts.
+// S: the scalar the factors are stored in (hs_solve_multi.h).  A demoted copy (S != T) has no active set, no phases and no HSS fronts.
 template <class T, class S>
 void multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act, int phase) {
   constexpr bool OWN = std::is_same<T, S>::value;
@@ -328,7 +304,7 @@ void multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs
       const int nblk = (maxni + 255) / 256;
       for (int j = 0; j < nblk; ++j) {
         const int wl = std::min(256, maxni - j * 256);
-        if (left && j > 0) MultiSide<T, S>::level_t(sn, nf, HSMT_LEFT_U, j, cj, wl, a, s);
+        if (left && j > 0) launch_multi_level_t<T, S>(sn, nf, HSMT_LEFT_U, j, cj, wl, a, s);
         level_step<T, S>(trans, cj, sn, nf, HSM_DIAG_L, HSMT_DIAG_U, j, wl, a, s);
         if (!left) level_step<T, S>(trans, cj, sn, nf, HSM_BELOW_L, HSMT_BELOW_U, j, maxni - (j + 1) * 256, a, s);
       }
@@ -383,7 +359,7 @@ void multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs
       const int nblk = (maxni + 255) / 256;
       for (int j = nblk - 1; j >= 0; --j) {
         const int wl = std::min(256, maxni - j * 256);
-        if (left) MultiSide<T, S>::level_t(sn, nf, HSMT_LEFT_L, j, cj, 256, a, s);
+        if (left) launch_multi_level_t<T, S>(sn, nf, HSMT_LEFT_L, j, cj, 256, a, s);
         level_step<T, S>(trans, cj, sn, nf, HSM_DIAG_U, HSMT_DIAG_L, j, wl, a, s);
         if (!left) level_step<T, S>(trans, cj, sn, nf, HSM_ABOVE_U, HSMT_ABOVE_L, j, j * 256, a, s);
       }

@@ -821,52 +821,9 @@ static int multi_prob_stage(const char* name, int64_t M, int64_t K, int64_t kc, 
   (void)hipFree(dmap);
   return HS_OK;
 }
-// C = A X or C - A X, A M x K; map: cmap, row i of the product goes to row map[i] of C
-template <class T>
-static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_stage<T>("hsk_multi_prob", M, K, kc, A, lda, M, K, X, ldx, C, ldc, map, M, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
-    MultiProb<T> p;
-    memset(&p, 0, sizeof p);
-    p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0;
-    p.X = dX; p.xrs = P;
-    p.Cin = minus ? dC : nullptr;
-    p.C = dC; p.crs = P; p.cmap = dmap;
-    launch_multi_prob<T>(p, (int)kc, 0);
-  });
-}
-// C = op(A)^T X or C - op(A)^T X, A K x M; map: xmap, row k of A meets row map[k] of X
-template <class T>
-static int multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj,
-                             const int32_t* map) {
-  return multi_prob_stage<T>("hsk_multi_prob_t", M, K, kc, A, lda, K, M, X, ldx, C, ldc, map, K, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
-    MultiProbT<T> p;
-    memset(&p, 0, sizeof p);
-    p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
-    p.X = dX; p.xrs = P; p.xmap = dmap;
-    p.Cin = minus ? dC : nullptr;
-    p.C = dC; p.crs = P;
-    launch_multi_prob_t<T>(p, (int)kc, 0);
-  });
-}
-extern "C" int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
-                                int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map);
-}
-extern "C" int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
-                                int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map);
-}
-extern "C" int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
-                                  int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
-  return multi_prob_t_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map);
-}
-extern "C" int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
-                                  int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
-  return multi_prob_t_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
-}
-
-// The same two products over a Float32 panel (kernels_solve_multi_f32.hip): A arrives in Float64, is demoted on the device by the library's
-// demotion kernel (kernels_f32.hip) into a copy with the leading dimension hs_f32_create would give it, and the product reads the copy.
+// The same staging for the two products over a Float32 panel (kernels_solve_multi_f32.hip): A arrives in Float64, is demoted on the device
+// by the library's demotion kernel (kernels_f32.hip) into a copy with the leading dimension hs_f32_create would give it, and the product
+// reads the copy.
 #include "hs_f32.h"
 template <class T, class Launch>
 static int multi_prob_f32_stage(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx, T* C,
@@ -897,48 +854,76 @@ static int multi_prob_f32_stage(const char* name, int64_t M, int64_t K, int64_t 
   (void)hipFree(djob);
   return st;
 }
-template <class T>
-static int multi_prob_f32_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, const int32_t* map) {
-  typedef typename F32Of<T>::type S;
-  return multi_prob_f32_stage<T>("hsk_multi_prob_f32", M, K, kc, A, lda, M, K, X, ldx, C, ldc, map, M, [&](const S* dA, int ldd, const T* dX, T* dC, const int* dmap, int64_t P) {
-    MultiProbF32<T> p;
+// the staging of a hook whose panel is stored as S: launch(dA as S, its leading dimension, dX, dC, dmap, pitch)
+template <class T, class S, class Launch>
+static int multi_prob_stage_as(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx, T* C,
+                               int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
+  if constexpr (std::is_same<T, S>::value)
+    return multi_prob_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap,
+                               [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) { launch(dA, (int)lda, dX, dC, dmap, P); });
+  else
+    return multi_prob_f32_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap, launch);
+}
+// C = A X or C - A X, A M x K; map: cmap, row i of the product goes to row map[i] of C
+template <class T, class S>
+static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, const int32_t* map) {
+  const char* name = std::is_same<T, S>::value ? "hsk_multi_prob" : "hsk_multi_prob_f32";
+  return multi_prob_stage_as<T, S>(name, M, K, kc, A, lda, M, K, X, ldx, C, ldc, map, M, [&](const S* dA, int ld, const T* dX, T* dC, const int* dmap, int64_t P) {
+    MultiProb<T, S> p;
     memset(&p, 0, sizeof p);
-    p.A = dA; p.lda = ldd; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0;
+    p.A = dA; p.lda = ld; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0;
     p.X = dX; p.xrs = P;
     p.Cin = minus ? dC : nullptr;
     p.C = dC; p.crs = P; p.cmap = dmap;
-    launch_multi_prob_f32<T>(p, (int)kc, 0);
+    launch_multi_prob<T, S>(p, (int)kc, 0);
   });
 }
-template <class T>
-static int multi_prob_t_f32_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj,
-                                 const int32_t* map) {
-  typedef typename F32Of<T>::type S;
-  return multi_prob_f32_stage<T>("hsk_multi_prob_t_f32", M, K, kc, A, lda, K, M, X, ldx, C, ldc, map, K, [&](const S* dA, int ldd, const T* dX, T* dC, const int* dmap, int64_t P) {
-    MultiProbTF32<T> p;
+// C = op(A)^T X or C - op(A)^T X, A K x M; map: xmap, row k of A meets row map[k] of X
+template <class T, class S>
+static int multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj,
+                             const int32_t* map) {
+  const char* name = std::is_same<T, S>::value ? "hsk_multi_prob_t" : "hsk_multi_prob_t_f32";
+  return multi_prob_stage_as<T, S>(name, M, K, kc, A, lda, K, M, X, ldx, C, ldc, map, K, [&](const S* dA, int ld, const T* dX, T* dC, const int* dmap, int64_t P) {
+    MultiProbT<T, S> p;
     memset(&p, 0, sizeof p);
-    p.A = dA; p.lda = ldd; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
+    p.A = dA; p.lda = ld; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
     p.X = dX; p.xrs = P; p.xmap = dmap;
     p.Cin = minus ? dC : nullptr;
     p.C = dC; p.crs = P;
-    launch_multi_prob_t_f32<T>(p, (int)kc, 0);
+    launch_multi_prob_t<T, S>(p, (int)kc, 0);
   });
+}
+extern "C" int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                int64_t ldc, int minus, int trap, const int32_t* map) {
+  return multi_prob_hook<double, double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map);
+}
+extern "C" int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                int64_t ldc, int minus, int trap, const int32_t* map) {
+  return multi_prob_hook<cplx, cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map);
+}
+extern "C" int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                  int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
+  return multi_prob_t_hook<double, double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map);
+}
+extern "C" int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
+                                  int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
+  return multi_prob_t_hook<cplx, cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
 }
 extern "C" int hsk_multi_prob_f32_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                     int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_f32_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map);
+  return multi_prob_hook<double, float>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map);
 }
 extern "C" int hsk_multi_prob_f32_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                     int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_f32_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map);
+  return multi_prob_hook<cplx, cplxf>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map);
 }
 extern "C" int hsk_multi_prob_t_f32_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                       int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
-  return multi_prob_t_f32_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map);
+  return multi_prob_t_hook<double, float>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map);
 }
 extern "C" int hsk_multi_prob_t_f32_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                       int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
-  return multi_prob_t_f32_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
+  return multi_prob_t_hook<cplx, cplxf>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
 }
 // x <- (double)(float)x for every stored element hs_f32_create would demote, in place in the handle (hs_f32.hip)
 extern "C" int hsk_round_factors_f32(hs_handle* F, int64_t* counts2) {

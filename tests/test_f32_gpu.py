@@ -66,7 +66,7 @@ def _opmat(A, t):
 
 
 # ---- 1, 2. the kernels alone ------------------------------------------------------------------------------------------------------------------
-SHAPES = [(64, 16, 16), (70, 37, 5), (257, 256, 33), (33, 300, 64)]
+SHAPES = [(64, 16, 16), (70, 37, 5), (257, 256, 33), (33, 300, 64), (70, 37, 17)]  # the last: trap and a map at ragged M, K with a ragged second column tile
 
 
 def _call(hs, name, cplx, M, K, kc, A, X, C0, minus, trap, conj, cmap):
