@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../include/hs_kernels.h"
+#include "hs_host.h"
 #include "hs_gmres_common.h"
 #include "hs_solve_multi.h"
 #include "hs_mod.h"  // hs_mod_apply_prec, hs_mod_handle
@@ -583,158 +584,132 @@ int refused_by_block_solve(hs_handle* F, int trans, int64_t n) {  // zero column
 
 // the dimension test and the defaults every GMRES entry point applies after its own argument checks
 template <class T>
-int gmres_defaults(hs_handle* F, int64_t n, int64_t* restart, int64_t* maxiter, double* reltol) {
-  if (F && (hs_size(F) != n || (hs_is_complex(F) != 0) != (sizeof(T) == 16))) {
-    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld", (long long)hs_size(F), (long long)hs_size(F),
-                 hs_is_complex(F) ? "ComplexF64" : "Float64", (long long)n, (long long)n);
-    return HS_ERR_DIMENSION;
-  }
+void gmres_defaults(hs_handle* F, int64_t n, int64_t* restart, int64_t* maxiter, double* reltol) {
+  if (F && (hs_size(F) != n || (hs_is_complex(F) != 0) != (sizeof(T) == 16)))
+    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld", (long long)hs_size(F), (long long)hs_size(F),
+            hs_is_complex(F) ? "ComplexF64" : "Float64", (long long)n, (long long)n);
   // defaults of IterativeSolvers 0.9: restart = min(20, n), maxiter = n, reltol = sqrt(eps)
   if (*restart <= 0) *restart = std::min<int64_t>(20, n);
-  if (*restart > GM_MAXK) {
-    hs_set_error(HS_ERR_ARGUMENT, *restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)*restart, GM_MAXK);
-    return HS_ERR_ARGUMENT;
-  }
+  if (*restart > GM_MAXK) HS_FAIL(HS_ERR_ARGUMENT, *restart, "ArgumentError: restart = %lld exceeds the limit of %d", (long long)*restart, GM_MAXK);
   if (*maxiter < 0) *maxiter = n;
   if (!(*reltol >= 0.0)) *reltol = 1.4901161193847656e-08;
-  return HS_OK;
 }
 // the checks and defaults hs_gmres_block_* and hs_gmres_block_t_* share (A and nrhs = 0 apart)
 template <class T>
-int gmres_block_check(hs_handle* F, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int where, int64_t* restart, int64_t* maxiter, double* reltol, int64_t* iters,
-                      int* converged) {
-  if (!B || !X || !iters || !converged || (const void*)B == (const void*)X) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs B, X (not aliasing B) and the two result arrays");
-    return HS_ERR_ARGUMENT;
-  }
-  if (where != 0 && where != 1) {
-    hs_set_error(HS_ERR_ARGUMENT, where, "ArgumentError: hs_gmres_block: where = %d (0: host pointers, 1: device pointers)", where);
-    return HS_ERR_ARGUMENT;
-  }
-  if (ldb < n || ldx < n) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block: ldb = %lld, ldx = %lld below n = %lld", (long long)ldb, (long long)ldx, (long long)n);
-    return HS_ERR_ARGUMENT;
-  }
-  return gmres_defaults<T>(F, n, restart, maxiter, reltol);
+void gmres_block_check(hs_handle* F, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int where, int64_t* restart, int64_t* maxiter, double* reltol, int64_t* iters,
+                       int* converged) {
+  if (!B || !X || !iters || !converged || (const void*)B == (const void*)X)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs B, X (not aliasing B) and the two result arrays");
+  if (where != 0 && where != 1) HS_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: hs_gmres_block: where = %d (0: host pointers, 1: device pointers)", where);
+  if (ldb < n || ldx < n)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block: ldb = %lld, ldx = %lld below n = %lld", (long long)ldb, (long long)ldx, (long long)n);
+  gmres_defaults<T>(F, n, restart, maxiter, reltol);
+}
+void need_device() {
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) HS_FAIL(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
 }
 
 // Every GMRES entry point from the device check to the results.  make_op(buf, s) puts A on the device (or finds it there) and returns the
 // operator; width(bytes per column) is the group width the caller wants, asked after the device check; info receives the eight figures.
 template <class T, class MakeOp, class Prec, class Width>
-int gmres_run(MakeOp make_op, const Prec& Pr, Width width, double* info, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where, int use_x0,
-              double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
-    return HS_ERR_DEVICE;
+void gmres_run(MakeOp make_op, const Prec& Pr, Width width, double* info, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where, int use_x0,
+               double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  need_device();
+  hipStream_t s = (hipStream_t)stream;
+  HsDevBuf buf("GMRES workspace");
+  HsEvents<2> ev;
+  HsDrain drain{s};  // after a throw nothing in flight outlives the workspace
+  std::fill(info, info + 8, 0.0);
+  const auto A = make_op(buf, s);
+  const T* dB = B;
+  T* dX = X;
+  int64_t dldb = ldb, dldx = ldx;
+  if (where == 0) {  // the whole block goes up and comes down once
+    T* tb = buf.get<T>((size_t)n * nrhs);
+    T* tx = buf.get<T>((size_t)n * nrhs);
+    HS_HIP(hipMemcpy2D(tb, sizeof(T) * (size_t)n, B, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
+    if (use_x0) HS_HIP(hipMemcpy2D(tx, sizeof(T) * (size_t)n, X, sizeof(T) * (size_t)ldx, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
+    dB = tb;
+    dX = tx;
+    dldb = dldx = n;
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = HS_OK;
-  HsDevBuf buf("GMRES workspace");  // outlives the try block: after a throw the stream is drained below before the workspace is freed
-  try {
-    std::fill(info, info + 8, 0.0);
-    hipStream_t s = (hipStream_t)stream;
-    const auto A = make_op(buf, s);
-    const T* dB = B;
-    T* dX = X;
-    int64_t dldb = ldb, dldx = ldx;
-    if (where == 0) {  // the whole block goes up and comes down once
-      T* tb = buf.get<T>((size_t)n * nrhs);
-      T* tx = buf.get<T>((size_t)n * nrhs);
-      HS_HIP(hipMemcpy2D(tb, sizeof(T) * (size_t)n, B, sizeof(T) * (size_t)ldb, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
-      if (use_x0) HS_HIP(hipMemcpy2D(tx, sizeof(T) * (size_t)n, X, sizeof(T) * (size_t)ldx, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyHostToDevice));
-      dB = tb;
-      dX = tx;
-      dldb = dldx = n;
-    }
-    const int m = (int)restart;
-    Workspace<T> ws;
-    const size_t per_col = bytes_per_column<T>(n, m);
-    ws.G = std::min<int64_t>(width(per_col), nrhs);
-    ws.m = m;
-    ws.ldv = (n + 1) / 2 * 2;
-    ws.nblk = (int)((n + 1023) / 1024);
-    const size_t G = (size_t)ws.G, blk = G * (size_t)ws.ldv;
-    const size_t nvec = (size_t)m + (G > 1 ? 5 : 4);  // R2 serves compaction, which one column never sees
-    T* big = buf.get<T>(nvec * blk);
-    ws.V = big;
-    ws.W = big + (size_t)(m + 1) * blk;
-    ws.Z = ws.W + blk;
-    ws.R = ws.Z + blk;
-    ws.R2 = G > 1 ? ws.R + blk : nullptr;
-    ws.part = buf.get<T>(G * ws.nblk * (m + 2));
-    ws.dpart = buf.get<double>(G * ws.nblk);
-    ws.src = buf.get<int>(G);
-    GbSmall<T>& S = ws.S;
-    S.ld = m + 1;
-    S.sH = (m + 1) * m;
-    S.s1 = m + 1;
-    S.s2 = m + 2;
-    S.H = buf.get<T>(G * S.sH);
-    S.cs = buf.get<T>(G * S.s1);
-    S.sn = buf.get<T>(G * S.s1);
-    S.y = buf.get<T>(G * S.s1);
-    S.g = buf.get<T>(G * S.s2);
-    S.h = buf.get<T>(G * S.s2);
-    S.h2 = buf.get<T>(G * S.s2);
-    S.hnres = buf.get<double>(2 * G);
-    S.beta = buf.get<double>(G);
-    S.tol = buf.get<double>(G);
-    S.itleft = buf.get<int>(G);
-    S.mask = buf.get<int>(G);
-    S.kused = buf.get<int>(G);
-    S.col = buf.get<int64_t>(G);
-    info[GI_WORK_BYTES] = (double)(per_col * G - ((size_t)m + 5 - nvec) * blk * sizeof(T));
-    HS_HIP(hipEventCreate(&e0));
-    HS_HIP(hipEventCreate(&e1));
-    HS_HIP(hipEventRecord(e0, s));
-    // a frozen column's basis vectors still travel through the block solve: they must be finite from the first step on
-    HS_HIP(hipMemsetAsync(big, 0, sizeof(T) * nvec * blk, s));
-    std::vector<Column> cols((size_t)nrhs);
-    for (int64_t g0 = 0; g0 < nrhs; g0 += ws.G) {
-      const int gc = (int)std::min<int64_t>(ws.G, nrhs - g0);
-      gmres_group<T>(A, Pr, n, dB, dldb, dX, dldx, g0, gc, use_x0, reltol, abstol, maxiter, ws, cols.data() + g0, info, s);
-      info[GI_GROUPS] += 1;
-    }
-    HS_HIP(hipEventRecord(e1, s));
-    HS_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HS_HIP(hipEventElapsedTime(&ms, e0, e1));
-    info[GI_SECONDS] = ms * 1e-3;
-    if (where == 0) HS_HIP(hipMemcpy2D(X, sizeof(T) * (size_t)ldx, dX, sizeof(T) * (size_t)n, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyDeviceToHost));
-    for (int64_t c = 0; c < nrhs; ++c) {
-      const Column& q = cols[(size_t)c];
-      iters[c] = q.it;
-      converged[c] = q.conv ? 1 : 0;
-      if (resnorm)
-        for (int64_t i = 0; i <= q.it; ++i) resnorm[(size_t)c * ((size_t)maxiter + 1) + (size_t)i] = q.hist[(size_t)i];
-    }
-  } catch (int code) {
-    rc = code;
-  } catch (const std::bad_alloc&) {
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
-    rc = HS_ERR_NOMEM;
+  const int m = (int)restart;
+  Workspace<T> ws;
+  const size_t per_col = bytes_per_column<T>(n, m);
+  ws.G = std::min<int64_t>(width(per_col), nrhs);
+  ws.m = m;
+  ws.ldv = (n + 1) / 2 * 2;
+  ws.nblk = (int)((n + 1023) / 1024);
+  const size_t G = (size_t)ws.G, blk = G * (size_t)ws.ldv;
+  const size_t nvec = (size_t)m + (G > 1 ? 5 : 4);  // R2 serves compaction, which one column never sees
+  T* big = buf.get<T>(nvec * blk);
+  ws.V = big;
+  ws.W = big + (size_t)(m + 1) * blk;
+  ws.Z = ws.W + blk;
+  ws.R = ws.Z + blk;
+  ws.R2 = G > 1 ? ws.R + blk : nullptr;
+  ws.part = buf.get<T>(G * ws.nblk * (m + 2));
+  ws.dpart = buf.get<double>(G * ws.nblk);
+  ws.src = buf.get<int>(G);
+  GbSmall<T>& S = ws.S;
+  S.ld = m + 1;
+  S.sH = (m + 1) * m;
+  S.s1 = m + 1;
+  S.s2 = m + 2;
+  S.H = buf.get<T>(G * S.sH);
+  S.cs = buf.get<T>(G * S.s1);
+  S.sn = buf.get<T>(G * S.s1);
+  S.y = buf.get<T>(G * S.s1);
+  S.g = buf.get<T>(G * S.s2);
+  S.h = buf.get<T>(G * S.s2);
+  S.h2 = buf.get<T>(G * S.s2);
+  S.hnres = buf.get<double>(2 * G);
+  S.beta = buf.get<double>(G);
+  S.tol = buf.get<double>(G);
+  S.itleft = buf.get<int>(G);
+  S.mask = buf.get<int>(G);
+  S.kused = buf.get<int>(G);
+  S.col = buf.get<int64_t>(G);
+  info[GI_WORK_BYTES] = (double)(per_col * G - ((size_t)m + 5 - nvec) * blk * sizeof(T));
+  HS_HIP(hipEventRecord(ev[0], s));
+  // a frozen column's basis vectors still travel through the block solve: they must be finite from the first step on
+  HS_HIP(hipMemsetAsync(big, 0, sizeof(T) * nvec * blk, s));
+  std::vector<Column> cols((size_t)nrhs);
+  for (int64_t g0 = 0; g0 < nrhs; g0 += ws.G) {
+    const int gc = (int)std::min<int64_t>(ws.G, nrhs - g0);
+    gmres_group<T>(A, Pr, n, dB, dldb, dX, dldx, g0, gc, use_x0, reltol, abstol, maxiter, ws, cols.data() + g0, info, s);
+    info[GI_GROUPS] += 1;
   }
-  if (rc != HS_OK) (void)hipStreamSynchronize((hipStream_t)stream);  // nothing in flight may outlive the workspace
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  return rc;
+  HS_HIP(hipEventRecord(ev[1], s));
+  HS_HIP(hipEventSynchronize(ev[1]));
+  float ms = 0.f;
+  HS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  info[GI_SECONDS] = ms * 1e-3;
+  if (where == 0) HS_HIP(hipMemcpy2D(X, sizeof(T) * (size_t)ldx, dX, sizeof(T) * (size_t)n, sizeof(T) * (size_t)n, (size_t)nrhs, hipMemcpyDeviceToHost));
+  for (int64_t c = 0; c < nrhs; ++c) {
+    const Column& q = cols[(size_t)c];
+    iters[c] = q.it;
+    converged[c] = q.conv ? 1 : 0;
+    if (resnorm)
+      for (int64_t i = 0; i <= q.it; ++i) resnorm[(size_t)c * ((size_t)maxiter + 1) + (size_t)i] = q.hist[(size_t)i];
+  }
 }
 
 // hs_gmres_block_*: groups as wide as the free device memory allows, the figures for hs_gmres_block_info
 template <class T, class MakeOp, class Prec>
-int gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol,
-                    int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_run<T>(make_op, Pr, [nrhs](size_t per_col) { return group_width(per_col, nrhs); }, g_info, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
-                      maxiter, resnorm, iters, converged, stream);
+void gmres_block_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol,
+                     int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  gmres_run<T>(make_op, Pr, [nrhs](size_t per_col) { return group_width(per_col, nrhs); }, g_info, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter,
+               resnorm, iters, converged, stream);
 }
 // hs_gmres_* / hs_gmres_t_*: one column in a group of width 1; the figures are nobody's
 template <class T, class MakeOp, class Prec>
-int gmres_one_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* b, T* x, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
-                  double* resnorm, int64_t* iters, int* converged, void* stream) {
+void gmres_one_run(MakeOp make_op, const Prec& Pr, int64_t n, const T* b, T* x, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
+                   double* resnorm, int64_t* iters, int* converged, void* stream) {
   double unused[8];
-  return gmres_run<T>(make_op, Pr, [](size_t) { return (int64_t)1; }, unused, n, b, n, x, n, (int64_t)1, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters,
-                      converged, stream);
+  gmres_run<T>(make_op, Pr, [](size_t) { return (int64_t)1; }, unused, n, b, n, x, n, (int64_t)1, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+               stream);
 }
 
 // the CSR upload of the caller's CSC arrays as the operator
@@ -750,100 +725,78 @@ auto csr_op_of(int64_t n, const int64_t* colptr, const int64_t* rowval, const T*
 }
 
 template <class T>
-int gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol, double abstol,
-                int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  if (n <= 0 || !colptr || !rowval || !nz || !b || !x || !iters || !converged) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres needs A (CSC), b, x and the two result slots");
-    return HS_ERR_ARGUMENT;
-  }
-  if (const int st = gmres_defaults<T>(F, n, &restart, &maxiter, &reltol)) return st;
-  return gmres_one_run<T>(csr_op_of<T>(n, colptr, rowval, nz), PrecFwd<T>{F}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+void gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol, double abstol,
+                 int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  if (n <= 0 || !colptr || !rowval || !nz || !b || !x || !iters || !converged)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres needs A (CSC), b, x and the two result slots");
+  gmres_defaults<T>(F, n, &restart, &maxiter, &reltol);
+  gmres_one_run<T>(csr_op_of<T>(n, colptr, rowval, nz), PrecFwd<T>{F}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
 // hs_gmres_t_*: op(A) x = b right-preconditioned by op(Pr); A explicit or the handle's own
 template <class T>
-int gmres_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol,
-                  double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+void gmres_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* b, T* x, int where, int use_x0, double reltol,
+                   double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
   bool own = false;
-  if (const int st = gm_check_op_args("hs_gmres_t_*", F, trans, colptr, rowval, nz, &own)) return st;
+  HS_CHECK(gm_check_op_args("hs_gmres_t_*", F, trans, colptr, rowval, nz, &own));
   if (trans == 0 && !own) return gmres_entry<T>(F, n, colptr, rowval, nz, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
-  if (n <= 0 || !b || !x || !iters || !converged) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_t needs n >= 1, b, x and the two result slots");
-    return HS_ERR_ARGUMENT;
-  }
-  if (const int st = gmres_defaults<T>(F, n, &restart, &maxiter, &reltol)) return st;
-  if (own)
-    if (const int st = hs_gmres_own_check(F, "hs_gmres_t_*", 1)) return st;
-  if (F)  // what hs_ldiv_t_* refuses (or an unfactored handle) is refused here, before any device work: zero columns are solved
-    if (const int st = PrecOp<T>{F, trans}((T*)nullptr, (const T*)nullptr, n, n, 0, nullptr)) return st;
-  if (own)
-    if (const int st = hs_gmres_own_check(F, "hs_gmres_t_*", 0)) return st;
+  if (n <= 0 || !b || !x || !iters || !converged) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_t needs n >= 1, b, x and the two result slots");
+  gmres_defaults<T>(F, n, &restart, &maxiter, &reltol);
+  if (own) HS_CHECK(hs_gmres_own_check(F, "hs_gmres_t_*", 1));
+  // what hs_ldiv_t_* refuses (or an unfactored handle) is refused here, before any device work: zero columns are solved
+  if (F) HS_CHECK((PrecOp<T>{F, trans}((T*)nullptr, (const T*)nullptr, n, n, 0, nullptr)));
+  if (own) HS_CHECK(hs_gmres_own_check(F, "hs_gmres_t_*", 0));
   auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
-  return gmres_one_run<T>(make_op, PrecOp<T>{F, trans}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  gmres_one_run<T>(make_op, PrecOp<T>{F, trans}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+}
+
+// What the block solve refuses is refused before any device work, so nothing is silently looped: an "unsupported" is reworded for the caller
+// of `fn` (`hint` says who serves such a handle), any other status travels on as it is.
+template <class T>
+void refuse_what_block_solve_refuses(hs_handle* F, int trans, int64_t n, const char* fn, const char* hint) {
+  const int st = refused_by_block_solve<T>(F, trans, n);
+  if (st == HS_ERR_UNSUPPORTED) {
+    const std::string why = hs_last_error();
+    HS_FAIL(st, hs_last_error_info(), "%s: the block solve does not serve this preconditioner (%s)%s", fn, why.c_str(), hint);
+  }
+  HS_CHECK(st);
 }
 
 template <class T>
-int gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where,
-                      int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  if (n <= 0 || nrhs < 0 || !colptr || !rowval || !nz) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs A (CSC) and nrhs >= 0");
-    return HS_ERR_ARGUMENT;
-  }
+void gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs, int where,
+                       int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+  if (n <= 0 || nrhs < 0 || !colptr || !rowval || !nz) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block needs A (CSC) and nrhs >= 0");
   if (nrhs == 0) {
     for (double& v : g_info) v = 0.0;
-    return HS_OK;
+    return;
   }
-  if (const int st = gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
-  if (F) {  // what hs_ldiv_block_* refuses is refused here, before any device work: nothing is silently looped
-    const int st = refused_by_block_solve<T>(F, 0, n);
-    if (st == HS_ERR_UNSUPPORTED) {
-      const std::string why = hs_last_error();
-      hs_set_error(HS_ERR_UNSUPPORTED, hs_last_error_info(), "hs_gmres_block_*: the block solve does not serve this preconditioner (%s); hs_gmres_* serves it, one right-hand side at a time",
-                   why.c_str());
-      return st;
-    }
-    if (st != 0) return st;
-  }
-  return gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), PrecBlockFwd<T>{F}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters,
-                            converged, stream);
+  gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged);
+  if (F) refuse_what_block_solve_refuses<T>(F, 0, n, "hs_gmres_block_*", "; hs_gmres_* serves it, one right-hand side at a time");
+  gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), PrecBlockFwd<T>{F}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                     stream);
 }
 
 // hs_gmres_block_t_*: op(A) X = B right-preconditioned by op(Pr); A explicit or the handle's own
 template <class T>
-int gmres_block_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs,
-                        int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
+void gmres_block_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx, int64_t nrhs,
+                         int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
   bool own = false;
-  if (const int st = gm_check_op_args("hs_gmres_block_t_*", F, trans, colptr, rowval, nz, &own)) return st;
+  HS_CHECK(gm_check_op_args("hs_gmres_block_t_*", F, trans, colptr, rowval, nz, &own));
   if (trans == 0 && !own)
     return gmres_block_entry<T>(F, n, colptr, rowval, nz, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
-  if (n <= 0 || nrhs < 0) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block_t needs n >= 1 and nrhs >= 0");
-    return HS_ERR_ARGUMENT;
-  }
-  if (own && hs_size(F) != n) {
-    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the handle's own A is %lld x %lld, n = %lld", (long long)hs_size(F), (long long)hs_size(F), (long long)n);
-    return HS_ERR_DIMENSION;
-  }
+  if (n <= 0 || nrhs < 0) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block_t needs n >= 1 and nrhs >= 0");
+  if (own && hs_size(F) != n)
+    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: the handle's own A is %lld x %lld, n = %lld", (long long)hs_size(F), (long long)hs_size(F), (long long)n);
   if (nrhs == 0) {
     for (double& v : g_info) v = 0.0;
-    return HS_OK;
+    return;
   }
-  if (const int st = gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
-  if (own)
-    if (const int st = hs_gmres_own_check(F, "hs_gmres_block_t_*", 1)) return st;
-  if (F) {  // what hs_ldiv_block_t_* refuses is refused here whatever trans is, before any device work
-    const int st = refused_by_block_solve<T>(F, trans, n);
-    if (st == HS_ERR_UNSUPPORTED) {
-      const std::string why = hs_last_error();
-      hs_set_error(HS_ERR_UNSUPPORTED, hs_last_error_info(), "hs_gmres_block_t_*: the block solve does not serve this preconditioner (%s)", why.c_str());
-      return st;
-    }
-    if (st != 0) return st;
-  }
-  if (own)
-    if (const int st = hs_gmres_own_check(F, "hs_gmres_block_t_*", 0)) return st;
+  gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged);
+  if (own) HS_CHECK(hs_gmres_own_check(F, "hs_gmres_block_t_*", 1));
+  if (F) refuse_what_block_solve_refuses<T>(F, trans, n, "hs_gmres_block_t_*", "");  // (whatever trans is)
+  if (own) HS_CHECK(hs_gmres_own_check(F, "hs_gmres_block_t_*", 0));
   auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
-  return gmres_block_run<T>(make_op, PrecBlockOp<T>{F, trans}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  gmres_block_run<T>(make_op, PrecBlockOp<T>{F, trans}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
 // What the entry below needs of a preconditioner object other than a handle: its names in the messages (fn, obj; mat: what the messages
@@ -854,7 +807,7 @@ struct PrecObjMod {  // hs_gmres_block_mod_*: op(A1) X = B right-preconditioned 
   typedef hs_mod Obj;
   static constexpr const char *fn = "hs_gmres_block_mod_*", *obj = "hs_mod", *mat = "A1";
   static constexpr const char* csc = "the modified matrix A1 must be given as CSC (the handle holds the unmodified A)";
-  static int check(hs_mod*, int64_t) { return HS_OK; }
+  static void check(hs_mod*, int64_t) {}
   static hs_handle* handle(hs_mod* M) { return hs_mod_handle(M); }
   static PrecBlockMod<T> prec(hs_mod* M, int trans) { return {hs_mod_handle(M), M, trans}; }
 };
@@ -863,11 +816,10 @@ struct PrecObjF32 {  // hs_gmres_block_f32_*: op(A) X = B right-preconditioned b
   typedef hs_f32 Obj;
   static constexpr const char *fn = "hs_gmres_block_f32_*", *obj = "hs_f32", *mat = "A";
   static constexpr const char* csc = "A must be given as CSC (a demoted factorization holds no matrix)";
-  static int check(hs_f32* G, int64_t n) {
-    if (hs_f32_size(G) == n && (hs_f32_is_complex(G) != 0) == (sizeof(T) == 16)) return HS_OK;
-    hs_set_error(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld %s", (long long)hs_f32_size(G), (long long)hs_f32_size(G),
-                 hs_f32_is_complex(G) ? "ComplexF64" : "Float64", (long long)n, (long long)n, sizeof(T) == 16 ? "ComplexF64" : "Float64");
-    return HS_ERR_DIMENSION;
+  static void check(hs_f32* G, int64_t n) {
+    if (hs_f32_size(G) != n || (hs_f32_is_complex(G) != 0) != (sizeof(T) == 16))
+      HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: the preconditioner is %lld x %lld %s, A is %lld x %lld %s", (long long)hs_f32_size(G), (long long)hs_f32_size(G),
+              hs_f32_is_complex(G) ? "ComplexF64" : "Float64", (long long)n, (long long)n, sizeof(T) == 16 ? "ComplexF64" : "Float64");
   }
   static hs_handle* handle(hs_f32*) { return nullptr; }
   static PrecBlockF32<T> prec(hs_f32* G, int trans) { return {reinterpret_cast<hs_handle*>(G), G, trans}; }
@@ -875,210 +827,170 @@ struct PrecObjF32 {  // hs_gmres_block_f32_*: op(A) X = B right-preconditioned b
 
 // op(A) X = B right-preconditioned by a preconditioner object other than a handle (O: above); A is the caller's CSC
 template <class T, class O>
-int gmres_block_obj_entry(typename O::Obj* P, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx,
-                          int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged,
-                          void* stream) {
-  if (!P) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null %s", O::fn, O::obj);
-    return HS_ERR_ARGUMENT;
-  }
-  if (trans < 0 || trans > 2) {
-    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: %s, 1: transpose(%s), 2: adjoint(%s))", O::fn, trans, O::mat, O::mat, O::mat);
-    return HS_ERR_ARGUMENT;
-  }
-  if (!colptr || !rowval || !nz) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s", O::fn, O::csc);
-    return HS_ERR_ARGUMENT;
-  }
-  if (n <= 0 || nrhs < 0) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs n >= 1 and nrhs >= 0", O::fn);
-    return HS_ERR_ARGUMENT;
-  }
-  if (const int st = O::check(P, n)) return st;
+void gmres_block_obj_entry(typename O::Obj* P, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* B, int64_t ldb, T* X, int64_t ldx,
+                           int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged,
+                           void* stream) {
+  if (!P) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null %s", O::fn, O::obj);
+  if (trans < 0 || trans > 2)
+    HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: %s, 1: transpose(%s), 2: adjoint(%s))", O::fn, trans, O::mat, O::mat, O::mat);
+  if (!colptr || !rowval || !nz) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s", O::fn, O::csc);
+  if (n <= 0 || nrhs < 0) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs n >= 1 and nrhs >= 0", O::fn);
+  O::check(P, n);
   if (nrhs == 0) {
     for (double& v : g_info) v = 0.0;
-    return HS_OK;
+    return;
   }
   hs_handle* F = O::handle(P);
-  if (const int st = gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged)) return st;
+  gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged);
   const auto Pr = O::prec(P, trans);
   if (trans == 0)
     return gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
                               stream);
   auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, false, n, colptr, rowval, nz, s)}; };
-  return gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  gmres_block_run<T>(make_op, Pr, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
+// What hsk_spmm_* and hsk_spmm_op_* share once A is on the device: X, Y and B (null: none) go up as they are, launch(dX, dY, dB) runs on
+// the null stream, Y comes down.
+template <class T, class Launch>
+void spmm_on_host_blocks(HsDevBuf& buf, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy, int64_t nrhs, Launch launch) {
+  T* dX = buf.get<T>((size_t)ldx * nrhs);
+  T* dY = buf.get<T>((size_t)ldy * nrhs);
+  T* dB = B ? buf.get<T>((size_t)ldb * nrhs) : nullptr;
+  HS_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
+  if (B) HS_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
+  launch(dX, dY, dB);
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
+}
 
 // hsk_spmm_*: the SpMM kernel alone on host data
 template <class T>
-int spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy, int64_t nrhs) {
-  if (n <= 0 || nrhs < 1 || !colptr || !rowval || !nz || !X || !Y || ldx < n || ldy < n || (B && ldb < n)) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_spmm: n >= 1, nrhs >= 1, leading dimensions >= n and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  try {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-      hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
-      return HS_ERR_DEVICE;
-    }
-    HsDevBuf buf("GMRES workspace");
-    int64_t* d_rp;
-    int32_t* d_ci;
-    T* d_v;
-    upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
-    T* dX = buf.get<T>((size_t)ldx * nrhs);
-    T* dY = buf.get<T>((size_t)ldy * nrhs);
-    T* dB = B ? buf.get<T>((size_t)ldb * nrhs) : nullptr;
-    HS_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
-    HS_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
-    if (B) HS_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
+void spmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy, int64_t nrhs) {
+  if (n <= 0 || nrhs < 1 || !colptr || !rowval || !nz || !X || !Y || ldx < n || ldy < n || (B && ldb < n))
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_spmm: n >= 1, nrhs >= 1, leading dimensions >= n and non-null arrays required");
+  need_device();
+  HsDevBuf buf("GMRES workspace");
+  int64_t* d_rp;
+  int32_t* d_ci;
+  T* d_v;
+  upload_csr<T>(buf, n, colptr, rowval, nz, &d_rp, &d_ci, &d_v);
+  spmm_on_host_blocks<T>(buf, X, ldx, B, ldb, Y, ldy, nrhs, [&](const T* dX, T* dY, const T* dB) {
     launch_spmm<T>(d_rp, d_ci, d_v, dX, ldx, (const int64_t*)nullptr, dY, ldy, dB, ldb, (const int64_t*)nullptr, n, (int)nrhs, (hipStream_t)0);
-    HS_HIP(hipDeviceSynchronize());
-    HS_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
-    return HS_OK;
-  } catch (int code) {
-    return code;
-  } catch (const std::bad_alloc&) {
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
-    return HS_ERR_NOMEM;
-  }
+  });
 }
 
 // hsk_spmm_op_*: the op(A) SpMM kernel alone on host data.  trans = 0 reads the CSR upload of A, trans = 1, 2 the 0-based CSC upload itself.
 template <class T>
-int spmm_op_hook(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy,
-                 int64_t nrhs) {
-  if (trans < 0 || trans > 2 || n <= 0 || nrhs < 1 || !colptr || !rowval || !nz || !X || !Y || ldx < n || ldy < n || (B && ldb < n)) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_spmm_op: trans in 0:2, n >= 1, nrhs >= 1, leading dimensions >= n and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  try {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-      hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available: this library has no CPU fallback");
-      return HS_ERR_DEVICE;
-    }
-    HsDevBuf buf("GMRES workspace");
-    int64_t* d_p;
-    int32_t* d_i;
-    T* d_v;
-    if (trans == 0)
-      upload_csr<T>(buf, n, colptr, rowval, nz, &d_p, &d_i, &d_v);
-    else
-      upload_csc<T>(buf, n, colptr, rowval, nz, &d_p, &d_i, &d_v);
-    RowsOf<T> A;
-    A.ptr = d_p;
-    A.idx = d_i;
-    A.val = d_v;
-    A.conj = trans == 2;
-    T* dX = buf.get<T>((size_t)ldx * nrhs);
-    T* dY = buf.get<T>((size_t)ldy * nrhs);
-    T* dB = B ? buf.get<T>((size_t)ldb * nrhs) : nullptr;
-    HS_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * nrhs, hipMemcpyHostToDevice));
-    HS_HIP(hipMemcpy(dY, Y, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyHostToDevice));
-    if (B) HS_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * nrhs, hipMemcpyHostToDevice));
+void spmm_op_hook(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* nz, const T* X, int64_t ldx, const T* B, int64_t ldb, T* Y, int64_t ldy,
+                  int64_t nrhs) {
+  if (trans < 0 || trans > 2 || n <= 0 || nrhs < 1 || !colptr || !rowval || !nz || !X || !Y || ldx < n || ldy < n || (B && ldb < n))
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_spmm_op: trans in 0:2, n >= 1, nrhs >= 1, leading dimensions >= n and non-null arrays required");
+  need_device();
+  HsDevBuf buf("GMRES workspace");
+  int64_t* d_p;
+  int32_t* d_i;
+  T* d_v;
+  if (trans == 0)
+    upload_csr<T>(buf, n, colptr, rowval, nz, &d_p, &d_i, &d_v);
+  else
+    upload_csc<T>(buf, n, colptr, rowval, nz, &d_p, &d_i, &d_v);
+  RowsOf<T> A;
+  A.ptr = d_p;
+  A.idx = d_i;
+  A.val = d_v;
+  A.conj = trans == 2;
+  spmm_on_host_blocks<T>(buf, X, ldx, B, ldb, Y, ldy, nrhs, [&](const T* dX, T* dY, const T* dB) {
     launch_spmm_op<T>(A, dX, ldx, (const int64_t*)nullptr, dY, ldy, dB, ldb, (const int64_t*)nullptr, n, (int)nrhs, (hipStream_t)0);
-    HS_HIP(hipDeviceSynchronize());
-    HS_HIP(hipMemcpy(Y, dY, sizeof(T) * (size_t)ldy * nrhs, hipMemcpyDeviceToHost));
-    return HS_OK;
-  } catch (int code) {
-    return code;
-  } catch (const std::bad_alloc&) {
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
-    return HS_ERR_NOMEM;
-  }
+  });
 }
 
 }  // namespace
 
 extern "C" int hs_gmres_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
                           double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_entry<double>(Pr, n, colptr, rowval, nzval, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  HS_GUARD(gmres_entry<double>(Pr, n, colptr, rowval, nzval, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream));
 }
 extern "C" int hs_gmres_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where, int use_x0,
                           double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_entry<cplx>(Pr, n, colptr, rowval, (const cplx*)nzval, (const cplx*)b, (cplx*)x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
-                           stream);
+  HS_GUARD(gmres_entry<cplx>(Pr, n, colptr, rowval, (const cplx*)nzval, (const cplx*)b, (cplx*)x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                             stream));
 }
 extern "C" int hs_gmres_t_d(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where,
                             int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_t_entry<double>(Pr, trans, n, colptr, rowval, nzval, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  HS_GUARD(gmres_t_entry<double>(Pr, trans, n, colptr, rowval, nzval, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream));
 }
 extern "C" int hs_gmres_t_z(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* b, double* x, int where,
                             int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_t_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)b, (cplx*)x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters,
-                             converged, stream);
+  HS_GUARD(gmres_t_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)b, (cplx*)x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters,
+                               converged, stream));
 }
 extern "C" int hs_gmres_block_d(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
                                 int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
                                 int64_t* iters, int* converged, void* stream) {
-  return gmres_block_entry<double>(Pr, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
+  HS_GUARD(gmres_block_entry<double>(Pr, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream));
 }
 extern "C" int hs_gmres_block_z(hs_handle* Pr, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb, double* X,
                                 int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
                                 int64_t* iters, int* converged, void* stream) {
-  return gmres_block_entry<cplx>(Pr, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm,
-                                 iters, converged, stream);
+  HS_GUARD(gmres_block_entry<cplx>(Pr, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm,
+                                   iters, converged, stream));
 }
-extern "C" int hs_gmres_block_info(double* out8) {
-  if (!out8) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block_info: null argument");
-    return HS_ERR_ARGUMENT;
-  }
+static void gmres_block_info(double* out8) {
+  if (!out8) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres_block_info: null argument");
   for (int i = 0; i < 8; ++i) out8[i] = g_info[i];
-  return HS_OK;
 }
+extern "C" int hs_gmres_block_info(double* out8) { HS_GUARD(gmres_block_info(out8)); }
 extern "C" int hsk_spmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,
                           int64_t ldy, int64_t nrhs) {
-  return spmm_hook<double>(n, colptr, rowval, nzval, X, ldx, B, ldb, Y, ldy, nrhs);
+  HS_GUARD(spmm_hook<double>(n, colptr, rowval, nzval, X, ldx, B, ldb, Y, ldy, nrhs));
 }
 extern "C" int hsk_spmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B, int64_t ldb, double* Y,
                           int64_t ldy, int64_t nrhs) {
-  return spmm_hook<cplx>(n, colptr, rowval, (const cplx*)nzval, (const cplx*)X, ldx, (const cplx*)B, ldb, (cplx*)Y, ldy, nrhs);
+  HS_GUARD(spmm_hook<cplx>(n, colptr, rowval, (const cplx*)nzval, (const cplx*)X, ldx, (const cplx*)B, ldb, (cplx*)Y, ldy, nrhs));
 }
 extern "C" int hs_gmres_block_t_d(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                   double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
                                   int64_t* iters, int* converged, void* stream) {
-  return gmres_block_t_entry<double>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
-                                     stream);
+  HS_GUARD(gmres_block_t_entry<double>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                                       stream));
 }
 extern "C" int hs_gmres_block_t_z(hs_handle* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                   double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter, double* resnorm,
                                   int64_t* iters, int* converged, void* stream) {
-  return gmres_block_t_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter,
-                                   resnorm, iters, converged, stream);
+  HS_GUARD(gmres_block_t_entry<cplx>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter,
+                                     resnorm, iters, converged, stream));
 }
 extern "C" int hsk_spmm_op_d(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B,
                              int64_t ldb, double* Y, int64_t ldy, int64_t nrhs) {
-  return spmm_op_hook<double>(trans, n, colptr, rowval, nzval, X, ldx, B, ldb, Y, ldy, nrhs);
+  HS_GUARD(spmm_op_hook<double>(trans, n, colptr, rowval, nzval, X, ldx, B, ldb, Y, ldy, nrhs));
 }
 extern "C" int hsk_spmm_op_z(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* X, int64_t ldx, const double* B,
                              int64_t ldb, double* Y, int64_t ldy, int64_t nrhs) {
-  return spmm_op_hook<cplx>(trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)X, ldx, (const cplx*)B, ldb, (cplx*)Y, ldy, nrhs);
+  HS_GUARD(spmm_op_hook<cplx>(trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)X, ldx, (const cplx*)B, ldb, (cplx*)Y, ldy, nrhs));
 }
 extern "C" int hs_gmres_block_mod_d(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_block_obj_entry<double, PrecObjMod<double>>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
-                                       stream);
+  HS_GUARD(gmres_block_obj_entry<double, PrecObjMod<double>>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                                         stream));
 }
 extern "C" int hs_gmres_block_mod_z(hs_mod* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_block_obj_entry<cplx, PrecObjMod<cplx>>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
-                                     maxiter, resnorm, iters, converged, stream);
+  HS_GUARD(gmres_block_obj_entry<cplx, PrecObjMod<cplx>>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
+                                       maxiter, resnorm, iters, converged, stream));
 }
 extern "C" int hs_gmres_block_f32_d(hs_f32* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_block_obj_entry<double, PrecObjF32<double>>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
-                                       stream);
+  HS_GUARD(gmres_block_obj_entry<double, PrecObjF32<double>>(Pr, trans, n, colptr, rowval, nzval, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
+                                         stream));
 }
 extern "C" int hs_gmres_block_f32_z(hs_f32* Pr, int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, const double* B, int64_t ldb,
                                     double* X, int64_t ldx, int64_t nrhs, int where, int use_x0, double reltol, double abstol, int64_t restart, int64_t maxiter,
                                     double* resnorm, int64_t* iters, int* converged, void* stream) {
-  return gmres_block_obj_entry<cplx, PrecObjF32<cplx>>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
-                                     maxiter, resnorm, iters, converged, stream);
+  HS_GUARD(gmres_block_obj_entry<cplx, PrecObjF32<cplx>>(Pr, trans, n, colptr, rowval, (const cplx*)nzval, (const cplx*)B, ldb, (cplx*)X, ldx, nrhs, where, use_x0, reltol, abstol, restart,
+                                       maxiter, resnorm, iters, converged, stream));
 }

@@ -3,8 +3,9 @@
 // uses these and writes no macros, buffer holders or try / catch of its own.
 //
 // Errors travel as a thrown int (the HS_ERR_* code) with the text in hs_last_error: HS_FAIL sets both, HS_GUARD turns them into the
-// entry point's return value.  Code that sets the error and RETURNS a status (hs_lowrank*.hip, hs_gmres_block.hip, hs_hss.hip,
-// hs_testhooks.hip) is a different contract and does not use this header for it.
+// entry point's return value.  Code that sets the error and RETURNS a status (hs_lowrank*.hip and hs_hss.hip, whose functions are called
+// from inside the factorization) is a different contract and does not use this header for it; a caller on this contract passes such a
+// status on with HS_CHECK.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -7,71 +7,76 @@
 #include <vector>
 
 #include "../../include/hs_kernels.h"
+#include "hs_host.h"
 #include "hs_sched.h"
 #include "hs_envelope.h"
 #include "hs_lowrank.h"
 #include "hs_solve_multi.h"
 #include "hs_sweep.h"
 
-#define CK(call)                                                                                   \
-  do {                                                                                             \
-    hipError_t e__ = (call);                                                                       \
-    if (e__ != hipSuccess) {                                                                       \
-      hs_set_error(HS_ERR_DEVICE, 0, "%s failed: %s", #call, hipGetErrorString(e__));              \
-      return HS_ERR_DEVICE;                                                                        \
-    }                                                                                              \
-  } while (0)
+// Every hook below is a void template that refuses through HS_FAIL / HS_HIP / HS_CHECK, in the order arguments, device, allocation; its
+// hsk_* entry points are HS_GUARD(hook<T>(...)).  Device memory belongs to an HsDevBuf, so it is freed on every path.
+namespace {
+void need_device() {
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) HS_FAIL(HS_ERR_DEVICE, 0, "no HIP device available");
+}
+size_t rup32(size_t e) { return (e + 31) / 32 * 32; }
+// A rows x cols host block (leading dimension ld; null: nothing is copied) goes up with leading dimension max(rows, 1) ...
+template <class T>
+T* put_block(HsDevBuf& buf, const T* src, int64_t ld, int64_t rows, int64_t cols) {
+  const int64_t r = std::max<int64_t>(rows, 1);
+  T* d = buf.get<T>((size_t)(r * std::max<int64_t>(cols, 1)));
+  if (src && rows > 0 && cols > 0) HS_HIP(hipMemcpy2D(d, r * sizeof(T), src, ld * sizeof(T), rows * sizeof(T), cols, hipMemcpyHostToDevice));
+  return d;
+}
+// ... and a rows x cols device block (leading dimension dld) comes down into dst (leading dimension ld).
+template <class T>
+void bring_block(T* dst, int64_t ld, const T* d, int64_t dld, int64_t rows, int64_t cols) {
+  HS_HIP(hipMemcpy2D(dst, ld * sizeof(T), d, dld * sizeof(T), rows * sizeof(T), cols, hipMemcpyDeviceToHost));
+}
+// the mean time of `repeat` runs on the null stream (repeat <= 0: none)
+template <class Run>
+void time_repeats(int repeat, double* ms_out, Run run) {
+  if (repeat <= 0) return;
+  HsEvents<2> ev;
+  HS_HIP(hipEventRecord(ev[0], 0));
+  for (int r = 0; r < repeat; ++r) run();
+  HS_HIP(hipEventRecord(ev[1], 0));
+  HS_HIP(hipEventSynchronize(ev[1]));
+  float ms = 0.f;
+  HS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  if (ms_out) *ms_out = ms / repeat;
+}
+}  // namespace
 
 template <class T>
-static int gemm_hook(int64_t M, int64_t N, int64_t K, const T* A, int64_t lda, const T* B, int64_t ldb, T* C, int64_t ldc, int minus,
-                     int repeat, double* ms_out) {
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
-  T *dA = nullptr, *dB = nullptr, *dC = nullptr;
-  GemmProb<T>* dp = nullptr;
-  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)lda * K + 16));
-  CK(hipMalloc((void**)&dB, sizeof(T) * (size_t)ldb * N + 16));
-  CK(hipMalloc((void**)&dC, sizeof(T) * (size_t)ldc * N + 16));
-  CK(hipMalloc((void**)&dp, sizeof(GemmProb<T>)));
-  CK(hipMemcpy(dA, A, sizeof(T) * (size_t)lda * K, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * N, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dC, C, sizeof(T) * (size_t)ldc * N, hipMemcpyHostToDevice));
+static void gemm_hook(int64_t M, int64_t N, int64_t K, const T* A, int64_t lda, const T* B, int64_t ldb, T* C, int64_t ldc, int minus,
+                      int repeat, double* ms_out) {
+  need_device();
+  HsDevBuf buf("hsk_gemm");
+  T* dA = (T*)buf.get<char>(sizeof(T) * (size_t)lda * K + 16);
+  T* dB = (T*)buf.get<char>(sizeof(T) * (size_t)ldb * N + 16);
+  T* dC = (T*)buf.get<char>(sizeof(T) * (size_t)ldc * N + 16);
+  GemmProb<T>* dp = buf.get<GemmProb<T>>(1);
+  HS_HIP(hipMemcpy(dA, A, sizeof(T) * (size_t)lda * K, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)ldb * N, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dC, C, sizeof(T) * (size_t)ldc * N, hipMemcpyHostToDevice));
   GemmProb<T> p{dA, dB, dC, (int)M, (int)N, (int)K, (int)lda, (int)ldb, (int)ldc};
-  CK(hipMemcpy(dp, &p, sizeof p, hipMemcpyHostToDevice));
-  hipEvent_t e0, e1;
-  CK(hipEventCreate(&e0));
-  CK(hipEventCreate(&e1));
+  HS_HIP(hipMemcpy(dp, &p, sizeof p, hipMemcpyHostToDevice));
   launch_gemm_probs<T>(dp, 1, (int)M, (int)N, minus, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy(C, dC, sizeof(T) * (size_t)ldc * N, hipMemcpyDeviceToHost));
-  if (repeat > 0) {
-    CK(hipEventRecord(e0, 0));
-    for (int r = 0; r < repeat; ++r) launch_gemm_probs<T>(dp, 1, (int)M, (int)N, minus, 0);
-    CK(hipEventRecord(e1, 0));
-    CK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    CK(hipEventElapsedTime(&ms, e0, e1));
-    if (ms_out) *ms_out = ms / repeat;
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(dA);
-  (void)hipFree(dB);
-  (void)hipFree(dC);
-  (void)hipFree(dp);
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(C, dC, sizeof(T) * (size_t)ldc * N, hipMemcpyDeviceToHost));
+  time_repeats(repeat, ms_out, [&] { launch_gemm_probs<T>(dp, 1, (int)M, (int)N, minus, 0); });
 }
 
 extern "C" int hsk_gemm_d(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
                           int64_t ldc, int minus, int repeat, double* ms_out) {
-  return gemm_hook<double>(M, N, K, A, lda, B, ldb, C, ldc, minus, repeat, ms_out);
+  HS_GUARD(gemm_hook<double>(M, N, K, A, lda, B, ldb, C, ldc, minus, repeat, ms_out));
 }
 extern "C" int hsk_gemm_z(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
                           int64_t ldc, int minus, int repeat, double* ms_out) {
-  return gemm_hook<cplx>(M, N, K, (const cplx*)A, lda, (const cplx*)B, ldb, (cplx*)C, ldc, minus, repeat, ms_out);
+  HS_GUARD(gemm_hook<cplx>(M, N, K, (const cplx*)A, lda, (const cplx*)B, ldb, (cplx*)C, ldc, minus, repeat, ms_out));
 }
 
 // The plain update of a level, C -= A * B for a batch of `count` fronts, the way Sched::gemm issues the U12 update UR[r0.., :] -= LF[r0.., k0:k1) *
@@ -80,25 +85,16 @@ extern "C" int hsk_gemm_z(int64_t M, int64_t N, int64_t K, const double* A, int6
 // exactly as in a factorization (hs_gemm_lds_route, HS_GEMM_LDS / hsk_gemm_lds_enable); *routed says how many launches took the latter (the
 // launches of the edge kernels have a counter of their own, hsk_gemm_lds_edge_launches).
 // koff / roff = 1 shift B / A by one double (an operand the direct load may not take).
-static int gemm_op_hook(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A, const double* B,
-                        double* C, int64_t* routed, int repeat, double* ms_out) {
+static void gemm_op_hook(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A, const double* B,
+                         double* C, int64_t* routed, int repeat, double* ms_out) {
   typedef double T;
-  if (count <= 0 || count > 65535 || !M || !N || !A || !B || !C || K <= 0 || koff < 0 || roff < 0) {
-    hs_set_error(HS_ERR_ARGUMENT, count, "hsk_gemm_op_d: count in [1, 65535], positive K, non-negative offsets and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
+  if (count <= 0 || count > 65535 || !M || !N || !A || !B || !C || K <= 0 || koff < 0 || roff < 0)
+    HS_FAIL(HS_ERR_ARGUMENT, count, "hsk_gemm_op_d: count in [1, 65535], positive K, non-negative offsets and non-null arrays required");
   for (int64_t f = 0; f < count; ++f)
-    if (M[f] <= 0 || N[f] <= 0 || koff + K + roff + M[f] > (1 << 20) || N[f] > (1 << 20)) {
-      hs_set_error(HS_ERR_ARGUMENT, f, "hsk_gemm_op_d: front %lld has M = %lld, N = %lld", (long long)f, (long long)M[f], (long long)N[f]);
-      return HS_ERR_ARGUMENT;
-    }
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
+    if (M[f] <= 0 || N[f] <= 0 || koff + K + roff + M[f] > (1 << 20) || N[f] > (1 << 20))
+      HS_FAIL(HS_ERR_ARGUMENT, f, "hsk_gemm_op_d: front %lld has M = %lld, N = %lld", (long long)f, (long long)M[f], (long long)N[f]);
+  need_device();
   const int k0 = (int)koff, k1 = (int)(koff + K), r0 = (int)(koff + K + roff);
-  auto rup32 = [](size_t e) { return (e + 31) / 32 * 32; };
   std::vector<NodeDesc<T>> hn(count);
   std::vector<int> h_ni(count), h_nb(count);
   std::vector<size_t> olf(count), our(count);
@@ -111,11 +107,10 @@ static int gemm_op_hook(int64_t count, const int64_t* M, const int64_t* N, int64
     olf[f] = nT; nT += rup32((size_t)ld * k1);  // only the columns [0, k1) of LF are read
     our[f] = nT; nT += rup32((size_t)ld * nb);
   }
-  T* dbuf = nullptr;
-  NodeDesc<T>* dn = nullptr;
-  CK(hipMalloc((void**)&dbuf, sizeof(T) * nT));
-  CK(hipMalloc((void**)&dn, sizeof(NodeDesc<T>) * count));
-  CK(hipMemset(dbuf, 0, sizeof(T) * nT));
+  HsDevBuf buf("hsk_gemm_op_d");
+  T* dbuf = buf.get<T>(nT);
+  NodeDesc<T>* dn = buf.get<NodeDesc<T>>((size_t)count);
+  HS_HIP(hipMemset(dbuf, 0, sizeof(T) * nT));
   bool aligned = true;
   const T *Af = A, *Bf = B;
   T* Cf = C;
@@ -132,48 +127,32 @@ static int gemm_op_hook(int64_t count, const int64_t* M, const int64_t* N, int64
     d.mrows[HS_MAT_SB] = d.mcols[HS_MAT_SB] = 0;
     aligned = aligned && !((((uintptr_t)d.LF | (uintptr_t)d.UR) & 15) || ((d.ldl | d.ldu) & 1));
     const int Mf = (int)M[f];
-    CK(hipMemcpy2D(d.LF + r0 + (size_t)k0 * d.ldl, sizeof(T) * d.ldl, Af, sizeof(T) * Mf, sizeof(T) * Mf, K, hipMemcpyHostToDevice));
-    CK(hipMemcpy2D(d.UR + k0, sizeof(T) * d.ldu, Bf, sizeof(T) * K, sizeof(T) * K, d.nb, hipMemcpyHostToDevice));
-    CK(hipMemcpy2D(d.UR + r0, sizeof(T) * d.ldu, Cf, sizeof(T) * Mf, sizeof(T) * Mf, d.nb, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy2D(d.LF + r0 + (size_t)k0 * d.ldl, sizeof(T) * d.ldl, Af, sizeof(T) * Mf, sizeof(T) * Mf, K, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy2D(d.UR + k0, sizeof(T) * d.ldu, Bf, sizeof(T) * K, sizeof(T) * K, d.nb, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy2D(d.UR + r0, sizeof(T) * d.ldu, Cf, sizeof(T) * Mf, sizeof(T) * Mf, d.nb, hipMemcpyHostToDevice));
     Af += (size_t)Mf * K; Bf += (size_t)K * d.nb; Cf += (size_t)Mf * d.nb;
   }
-  CK(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
   Profiler prof;
   Sched<T> sch{dn, (int)count, maxni, maxnb, maxni + maxnb, (hipStream_t) nullptr, &prof, h_ni.data(), h_nb.data()};
   sch.aligned16 = aligned;
   const long long before = hsk_gemm_lds_launches(0);
   sch.gemm(HS_MAT_UR, HS_MAT_UR, r0, HS_BIG, 0, HS_BIG, k0, k1);
-  CK(hipDeviceSynchronize());
+  HS_HIP(hipDeviceSynchronize());
   if (routed) *routed = (int64_t)(hsk_gemm_lds_launches(0) - before);
   Cf = C;
   for (int64_t f = 0; f < count; ++f) {
     const NodeDesc<T>& d = hn[f];
     const int Mf = (int)M[f];
-    CK(hipMemcpy2D(Cf, sizeof(T) * Mf, d.UR + r0, sizeof(T) * d.ldu, sizeof(T) * Mf, d.nb, hipMemcpyDeviceToHost));
+    bring_block(Cf, Mf, d.UR + r0, d.ldu, Mf, d.nb);
     Cf += (size_t)Mf * d.nb;
   }
-  if (repeat > 0) {
-    hipEvent_t e0, e1;
-    CK(hipEventCreate(&e0));
-    CK(hipEventCreate(&e1));
-    CK(hipEventRecord(e0, 0));
-    for (int r = 0; r < repeat; ++r) sch.gemm(HS_MAT_UR, HS_MAT_UR, r0, HS_BIG, 0, HS_BIG, k0, k1);
-    CK(hipEventRecord(e1, 0));
-    CK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    CK(hipEventElapsedTime(&ms, e0, e1));
-    if (ms_out) *ms_out = ms / repeat;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  time_repeats(repeat, ms_out, [&] { sch.gemm(HS_MAT_UR, HS_MAT_UR, r0, HS_BIG, 0, HS_BIG, k0, k1); });
   prof.collect();
-  (void)hipFree(dbuf);
-  (void)hipFree(dn);
-  return HS_OK;
 }
 extern "C" int hsk_gemm_op_d(int64_t count, const int64_t* M, const int64_t* N, int64_t K, int64_t koff, int64_t roff, const double* A,
                              const double* B, double* C, int64_t* routed, int repeat, double* ms_out) {
-  return gemm_op_hook(count, M, N, K, koff, roff, A, B, C, routed, repeat, ms_out);
+  HS_GUARD(gemm_op_hook(count, M, N, K, koff, roff, A, B, C, routed, repeat, ms_out));
 }
 
 // The Schur update of a level, SB -= LF[ni.., 0:ni) * UR, for a batch of `count` fronts with their own ni[f] and nb[f] -- what hsk_gemm_op_d
@@ -185,25 +164,16 @@ extern "C" int hsk_gemm_op_d(int64_t count, const int64_t* M, const int64_t* N, 
 // that value too (timing only).  env != 0: the launch is enveloped and every front carries the block envelope of the zeros its A and B
 // really have (firstL of a 32-row block of A: the first column, rounded down to 32, with a non-zero entry in one of its rows; firstU of
 // a 32-column block of B likewise by rows; the interior blocks, which this product does not address, get their diagonal).
-static int gemm_schur_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, const double* A, const double* B, double* C, int env,
-                           int64_t* routed_lds, int64_t* routed_edge, int repeat, double* ms_out) {
+static void gemm_schur_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, const double* A, const double* B, double* C, int env,
+                            int64_t* routed_lds, int64_t* routed_edge, int repeat, double* ms_out) {
   typedef double T;
   const bool data = A && B && C;
-  if (count <= 0 || count > 65535 || !ni_ || !nb_ || (!data && (A || B || C)) || (env && !data)) {
-    hs_set_error(HS_ERR_ARGUMENT, count, "hsk_gemm_schur_d: count in [1, 65535], ni and nb non-null, A, B, C all given or all null (env needs them) required");
-    return HS_ERR_ARGUMENT;
-  }
+  if (count <= 0 || count > 65535 || !ni_ || !nb_ || (!data && (A || B || C)) || (env && !data))
+    HS_FAIL(HS_ERR_ARGUMENT, count, "hsk_gemm_schur_d: count in [1, 65535], ni and nb non-null, A, B, C all given or all null (env needs them) required");
   for (int64_t f = 0; f < count; ++f)
-    if (ni_[f] <= 0 || nb_[f] <= 0 || ni_[f] + nb_[f] > (1 << 20)) {
-      hs_set_error(HS_ERR_ARGUMENT, f, "hsk_gemm_schur_d: front %lld has ni = %lld, nb = %lld", (long long)f, (long long)ni_[f], (long long)nb_[f]);
-      return HS_ERR_ARGUMENT;
-    }
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
-  auto rup32 = [](size_t e) { return (e + 31) / 32 * 32; };
+    if (ni_[f] <= 0 || nb_[f] <= 0 || ni_[f] + nb_[f] > (1 << 20))
+      HS_FAIL(HS_ERR_ARGUMENT, f, "hsk_gemm_schur_d: front %lld has ni = %lld, nb = %lld", (long long)f, (long long)ni_[f], (long long)nb_[f]);
+  need_device();
   auto even = [](int v) { return (v + 1) / 2 * 2; };
   std::vector<NodeDesc<T>> hn(count);
   std::vector<int> h_ni(count), h_nb(count);
@@ -219,19 +189,13 @@ static int gemm_schur_hook(int64_t count, const int64_t* ni_, const int64_t* nb_
     osb[f] = nT; nT += rup32((size_t)even(nb) * nb);
     oenv[f] = nE; nE += 2 * (size_t)hs_env_nblocks(ni, nb);
   }
-  T* dbuf = nullptr;
-  NodeDesc<T>* dn = nullptr;
-  int* denv = nullptr;
-  struct Free {  // an early return of CK leaves nothing behind
-    T*& a; NodeDesc<T>*& b; int*& c;
-    ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); }
-  } free_all{dbuf, dn, denv};
-  CK(hipMalloc((void**)&dbuf, sizeof(T) * nT));
-  CK(hipMalloc((void**)&dn, sizeof(NodeDesc<T>) * count));
-  CK(hipMemsetD32(dbuf, 0x3F800000, 2 * nT));  // every double 0x3F8000003F800000 = 0.0078125...: finite, non-zero
+  HsDevBuf buf("hsk_gemm_schur_d");
+  T* dbuf = buf.get<T>(nT);
+  NodeDesc<T>* dn = buf.get<NodeDesc<T>>((size_t)count);
+  HS_HIP(hipMemsetD32(dbuf, 0x3F800000, 2 * nT));  // every double 0x3F8000003F800000 = 0.0078125...: finite, non-zero
   std::vector<int> henv(env ? nE : 0);
   std::vector<const int*> h_envp(count, nullptr);
-  if (env) CK(hipMalloc((void**)&denv, sizeof(int) * nE));
+  int* denv = env ? buf.get<int>(nE) : nullptr;
   bool aligned = true;
   const T *Af = A, *Bf = B;
   T* Cf = C;
@@ -260,14 +224,14 @@ static int gemm_schur_hook(int64_t count, const int64_t* ni_, const int64_t* nb_
     d.finalize();
     aligned = aligned && !((((uintptr_t)d.LF | (uintptr_t)d.UR | (uintptr_t)d.SB) & 15) || ((d.ldl | d.ldu | d.lds) & 1));
     if (data) {
-      CK(hipMemcpy2D(d.LF + ni, sizeof(T) * d.ldl, Af, sizeof(T) * nb, sizeof(T) * nb, ni, hipMemcpyHostToDevice));
-      CK(hipMemcpy2D(d.UR, sizeof(T) * d.ldu, Bf, sizeof(T) * ni, sizeof(T) * ni, nb, hipMemcpyHostToDevice));
-      CK(hipMemcpy2D(d.SB, sizeof(T) * d.lds, Cf, sizeof(T) * nb, sizeof(T) * nb, nb, hipMemcpyHostToDevice));
+      HS_HIP(hipMemcpy2D(d.LF + ni, sizeof(T) * d.ldl, Af, sizeof(T) * nb, sizeof(T) * nb, ni, hipMemcpyHostToDevice));
+      HS_HIP(hipMemcpy2D(d.UR, sizeof(T) * d.ldu, Bf, sizeof(T) * ni, sizeof(T) * ni, nb, hipMemcpyHostToDevice));
+      HS_HIP(hipMemcpy2D(d.SB, sizeof(T) * d.lds, Cf, sizeof(T) * nb, sizeof(T) * nb, nb, hipMemcpyHostToDevice));
       Af += (size_t)nb * ni; Bf += (size_t)ni * nb; Cf += (size_t)nb * nb;
     }
   }
-  if (env) CK(hipMemcpy(denv, henv.data(), sizeof(int) * nE, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
+  if (env) HS_HIP(hipMemcpy(denv, henv.data(), sizeof(int) * nE, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
   Profiler prof;
   Sched<T> sch{dn, (int)count, maxni, maxnb, maxm, (hipStream_t) nullptr, &prof, h_ni.data(), h_nb.data()};
   sch.aligned16 = aligned;
@@ -278,37 +242,23 @@ static int gemm_schur_hook(int64_t count, const int64_t* ni_, const int64_t* nb_
   }
   const long long lds0 = hsk_gemm_lds_launches(0), edge0 = hsk_gemm_lds_edge_launches(0);
   sch.gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG);
-  CK(hipDeviceSynchronize());
+  HS_HIP(hipDeviceSynchronize());
   if (routed_lds) *routed_lds = (int64_t)(hsk_gemm_lds_launches(0) - lds0);
   if (routed_edge) *routed_edge = (int64_t)(hsk_gemm_lds_edge_launches(0) - edge0);
   if (data) {
     Cf = C;
     for (int64_t f = 0; f < count; ++f) {
       const NodeDesc<T>& d = hn[f];
-      CK(hipMemcpy2D(Cf, sizeof(T) * d.nb, d.SB, sizeof(T) * d.lds, sizeof(T) * d.nb, d.nb, hipMemcpyDeviceToHost));
+      bring_block(Cf, d.nb, d.SB, d.lds, d.nb, d.nb);
       Cf += (size_t)d.nb * d.nb;
     }
   }
-  if (repeat > 0) {
-    hipEvent_t e0, e1;
-    CK(hipEventCreate(&e0));
-    CK(hipEventCreate(&e1));
-    CK(hipEventRecord(e0, 0));
-    for (int r = 0; r < repeat; ++r) sch.gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG);
-    CK(hipEventRecord(e1, 0));
-    CK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    CK(hipEventElapsedTime(&ms, e0, e1));
-    if (ms_out) *ms_out = ms / repeat;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  time_repeats(repeat, ms_out, [&] { sch.gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG); });
   prof.collect();
-  return HS_OK;
 }
 extern "C" int hsk_gemm_schur_d(int64_t count, const int64_t* ni, const int64_t* nb, const double* A, const double* B, double* C, int env,
                                 int64_t* routed_lds, int64_t* routed_edge, int repeat, double* ms_out) {
-  return gemm_schur_hook(count, ni, nb, A, B, C, env, routed_lds, routed_edge, repeat, ms_out);
+  HS_GUARD(gemm_schur_hook(count, ni, nb, A, B, C, env, routed_lds, routed_edge, repeat, ms_out));
 }
 
 // Factor a batch of `count` dense fronts F[k] ((ni[k]+nb[k])^2, column-major, front order [int;bnd], packed one after another) the way
@@ -330,50 +280,32 @@ struct FrontBatch {
   std::vector<Off> o;
   std::vector<int> h_ni, h_nb;
   int maxni = 0, maxnb = 0, maxm = 0;
+  HsDevBuf buf{"front batch"};  // owns the four device blocks below
   T* dbuf = nullptr;
   int* dint = nullptr;
   NodeDesc<T>* dn = nullptr;
   SolveNode<T>* dsn = nullptr;
   std::vector<NodeDesc<T>> hn;
   std::vector<SolveNode<T>> hs;  // filled by setup, reaches the device with upload_solve (a caller may complete it in between)
-  ~FrontBatch() {  // an early return of CK leaves nothing behind
-    (void)hipFree(dbuf);
-    (void)hipFree(dint);
-    (void)hipFree(dn);
-    (void)hipFree(dsn);
-  }
   // the argument checks both hooks share; nothing on the device yet
-  static int check(const char* name, int64_t count, const int64_t* ni_, const int64_t* nb_, const T* F, int mode, int mode_lo) {
-    if (count <= 0 || count > 65535 || !ni_ || !nb_ || !F || mode < mode_lo || mode > 3) {
-      hs_set_error(HS_ERR_ARGUMENT, count, "%s: count in [1, 65535], ni, nb and F non-null and mode in %d..3 required", name, mode_lo);
-      return HS_ERR_ARGUMENT;
-    }
+  static void check(const char* name, int64_t count, const int64_t* ni_, const int64_t* nb_, const T* F, int mode, int mode_lo) {
+    if (count <= 0 || count > 65535 || !ni_ || !nb_ || !F || mode < mode_lo || mode > 3)
+      HS_FAIL(HS_ERR_ARGUMENT, count, "%s: count in [1, 65535], ni, nb and F non-null and mode in %d..3 required", name, mode_lo);
     for (int64_t k = 0; k < count; ++k)
-      if (ni_[k] < 0 || nb_[k] < 0 || ni_[k] + nb_[k] > (1 << 16)) {
-        hs_set_error(HS_ERR_ARGUMENT, k, "%s: front %lld has ni = %lld, nb = %lld (need 0 <= ni, nb and ni + nb <= 65536)", name, (long long)k,
-                     (long long)ni_[k], (long long)nb_[k]);
-        return HS_ERR_ARGUMENT;
-      }
-    return HS_OK;
+      if (ni_[k] < 0 || nb_[k] < 0 || ni_[k] + nb_[k] > (1 << 16))
+        HS_FAIL(HS_ERR_ARGUMENT, k, "%s: front %lld has ni = %lld, nb = %lld (need 0 <= ni, nb and ni + nb <= 65536)", name, (long long)k,
+                (long long)ni_[k], (long long)nb_[k]);
   }
-  int setup(int64_t count_, const int64_t* ni_, const int64_t* nb_, const T* F);
-  int upload_solve() {
-    CK(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice));
-    return HS_OK;
-  }
-  int factor(int mode, double* ms_out);
-  int copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U);
+  void setup(int64_t count_, const int64_t* ni_, const int64_t* nb_, const T* F);
+  void upload_solve() { HS_HIP(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice)); }
+  void factor(int mode, double* ms_out);
+  void copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U);
 };
 
 template <class T>
-int FrontBatch<T>::setup(int64_t count_, const int64_t* ni_, const int64_t* nb_, const T* F) {
+void FrontBatch<T>::setup(int64_t count_, const int64_t* ni_, const int64_t* nb_, const T* F) {
   count = count_;
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
-  auto rup32 = [](size_t e) { return (e + 31) / 32 * 32; };
+  need_device();
   o.resize(count);
   h_ni.resize(count);
   h_nb.resize(count);
@@ -395,12 +327,12 @@ int FrontBatch<T>::setup(int64_t count_, const int64_t* ni_, const int64_t* nb_,
     h_ni[k] = x.ni; h_nb[k] = x.nb;
     maxni = std::max(maxni, x.ni); maxnb = std::max(maxnb, x.nb); maxm = std::max(maxm, x.m);
   }
-  CK(hipMalloc((void**)&dbuf, sizeof(T) * nT));
-  CK(hipMalloc((void**)&dint, sizeof(int) * nI));
-  CK(hipMalloc((void**)&dn, sizeof(NodeDesc<T>) * count));
-  CK(hipMalloc((void**)&dsn, sizeof(SolveNode<T>) * count));
-  CK(hipMemset(dbuf, 0, sizeof(T) * nT));
-  CK(hipMemset(dint, 0, sizeof(int) * nI));
+  dbuf = buf.get<T>(nT);
+  dint = buf.get<int>(nI);
+  dn = buf.get<NodeDesc<T>>((size_t)count);
+  dsn = buf.get<SolveNode<T>>((size_t)count);
+  HS_HIP(hipMemset(dbuf, 0, sizeof(T) * nT));
+  HS_HIP(hipMemset(dint, 0, sizeof(int) * nI));
   hn.resize(count);
   hs.resize(count);
   const T* Fk = F;
@@ -433,91 +365,84 @@ int FrontBatch<T>::setup(int64_t count_, const int64_t* ni_, const int64_t* nb_,
     q.ni = x.ni; q.nb = x.nb; q.m = x.m; q.ldl = x.ldl; q.ldu = x.ldu;
     q.mrows = x.m;
     const int m = x.m;
-    if (x.ni > 0) CK(hipMemcpy2D(d.LF, sizeof(T) * x.ldl, Fk, sizeof(T) * m, sizeof(T) * m, x.ni, hipMemcpyHostToDevice));
-    if (x.ni > 0 && x.nb > 0) CK(hipMemcpy2D(d.UR, sizeof(T) * x.ldu, Fk + (size_t)m * x.ni, sizeof(T) * m, sizeof(T) * x.ni, x.nb, hipMemcpyHostToDevice));
-    if (x.nb > 0) CK(hipMemcpy2D(d.SB, sizeof(T) * x.lds, Fk + (size_t)m * x.ni + x.ni, sizeof(T) * m, sizeof(T) * x.nb, x.nb, hipMemcpyHostToDevice));
+    if (x.ni > 0) HS_HIP(hipMemcpy2D(d.LF, sizeof(T) * x.ldl, Fk, sizeof(T) * m, sizeof(T) * m, x.ni, hipMemcpyHostToDevice));
+    if (x.ni > 0 && x.nb > 0) HS_HIP(hipMemcpy2D(d.UR, sizeof(T) * x.ldu, Fk + (size_t)m * x.ni, sizeof(T) * m, sizeof(T) * x.ni, x.nb, hipMemcpyHostToDevice));
+    if (x.nb > 0) HS_HIP(hipMemcpy2D(d.SB, sizeof(T) * x.lds, Fk + (size_t)m * x.ni + x.ni, sizeof(T) * m, sizeof(T) * x.nb, x.nb, hipMemcpyHostToDevice));
     Fk += (size_t)m * m;
   }
-  CK(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
-  return HS_OK;
+  HS_HIP(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
 }
 
 template <class T>
-int FrontBatch<T>::factor(int mode, double* ms_out) {
+void FrontBatch<T>::factor(int mode, double* ms_out) {
   Profiler prof;
-  hipEvent_t e0, e1;
-  CK(hipEventCreate(&e0));
-  CK(hipEventCreate(&e1));
   // same stream set-up as hs_analyze: a main stream and a high-priority side stream for look-ahead panels
-  hipStream_t s_main = nullptr, s_side = nullptr, s_la = nullptr, s_sidem = nullptr;
-  CK(hipStreamCreate(&s_main));
-  hs_create_lookahead_streams(&s_la, &s_sidem, &s_side);
-  CK(hipEventRecord(e0, s_main));
-  launch_init_fronts<T>(dn, (int)count, maxni, s_main);
-  Sched<T> sch{dn, (int)count, maxni, maxnb, maxm, s_main, &prof, h_ni.data(), h_nb.data(), s_side, 0, s_la, s_sidem};
+  struct Streams {
+    hipStream_t main = nullptr, side = nullptr, la = nullptr, sidem = nullptr;
+    ~Streams() {
+      for (hipStream_t s : {main, side, la, sidem})
+        if (s) (void)hipStreamDestroy(s);
+    }
+  } st;
+  HsEvents<2> ev;
+  HS_HIP(hipStreamCreate(&st.main));
+  hs_create_lookahead_streams(&st.la, &st.sidem, &st.side);
+  HS_HIP(hipEventRecord(ev[0], st.main));
+  launch_init_fronts<T>(dn, (int)count, maxni, st.main);
+  Sched<T> sch{dn, (int)count, maxni, maxnb, maxm, st.main, &prof, h_ni.data(), h_nb.data(), st.side, 0, st.la, st.sidem};
   if (mode >= 2) sch.sn = dsn;
   sch.optimistic = (mode == 1 || mode == 2);
   const auto h0 = std::chrono::steady_clock::now();
   sch.factor_fronts();
-  CK(hipEventRecord(e1, s_main));
+  HS_HIP(hipEventRecord(ev[1], st.main));
   if (getenv("HS_HOOK_VERBOSE"))
     fprintf(stderr, "[hook] host enqueue time %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count());
-  CK(hipEventSynchronize(e1));
+  HS_HIP(hipEventSynchronize(ev[1]));
   float ms = 0.f;
-  CK(hipEventElapsedTime(&ms, e0, e1));
+  HS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
   if (ms_out) *ms_out = ms;
-  CK(hipDeviceSynchronize());
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipStreamDestroy(s_main);
-  if (s_side) (void)hipStreamDestroy(s_side);
-  if (s_la) (void)hipStreamDestroy(s_la);
-  if (s_sidem) (void)hipStreamDestroy(s_sidem);
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
 }
 
 template <class T>
-int FrontBatch<T>::copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L,
-                            T* outInv256U) {
+void FrontBatch<T>::copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L,
+                             T* outInv256U) {
   std::vector<int> ip;
   size_t pLF = 0, pUR = 0, pSB = 0, pR = 0, pInv = 0, pInv256 = 0;
   for (int64_t k = 0; k < count; ++k) {
     const Off& x = o[k];
     const NodeDesc<T>& d = hn[k];
     const int ni = x.ni, nb = x.nb, m = x.m;
-    if (ni > 0 && outLF) CK(hipMemcpy2D(outLF + pLF, sizeof(T) * m, d.LF, sizeof(T) * x.ldl, sizeof(T) * m, ni, hipMemcpyDeviceToHost));
-    if (ni > 0 && nb > 0 && outUR) CK(hipMemcpy2D(outUR + pUR, sizeof(T) * ni, d.UR, sizeof(T) * x.ldu, sizeof(T) * ni, nb, hipMemcpyDeviceToHost));
-    if (nb > 0 && outSB) CK(hipMemcpy2D(outSB + pSB, sizeof(T) * nb, d.SB, sizeof(T) * x.lds, sizeof(T) * nb, nb, hipMemcpyDeviceToHost));
+    if (ni > 0 && outLF) bring_block(outLF + pLF, m, d.LF, x.ldl, m, ni);
+    if (ni > 0 && nb > 0 && outUR) bring_block(outUR + pUR, ni, d.UR, x.ldu, ni, nb);
+    if (nb > 0 && outSB) bring_block(outSB + pSB, nb, d.SB, x.lds, nb, nb);
     ip.resize((size_t)ni + 2);
-    CK(hipMemcpy(ip.data(), d.rperm, sizeof(int) * ((size_t)ni + 2), hipMemcpyDeviceToHost));  // rperm, info, growth
+    HS_HIP(hipMemcpy(ip.data(), d.rperm, sizeof(int) * ((size_t)ni + 2), hipMemcpyDeviceToHost));  // rperm, info, growth
     if (out_rperm)
       for (int i = 0; i < ni; ++i) out_rperm[pR + i] = ip[i];
     if (info) info[k] = ip[ni];
     if (growth) growth[k] = ip[ni + 1];
     const size_t n32 = (size_t)x.nblk * HS_PB * HS_PB, n256 = (size_t)x.nb256 * 65536;
-    if (outInvL && n32) CK(hipMemcpy(outInvL + pInv, d.invL, sizeof(T) * n32, hipMemcpyDeviceToHost));
-    if (outInvU && n32) CK(hipMemcpy(outInvU + pInv, d.invU, sizeof(T) * n32, hipMemcpyDeviceToHost));
-    if (outInv256L && n256) CK(hipMemcpy(outInv256L + pInv256, d.inv256L, sizeof(T) * n256, hipMemcpyDeviceToHost));
-    if (outInv256U && n256) CK(hipMemcpy(outInv256U + pInv256, d.inv256U, sizeof(T) * n256, hipMemcpyDeviceToHost));
+    if (outInvL && n32) HS_HIP(hipMemcpy(outInvL + pInv, d.invL, sizeof(T) * n32, hipMemcpyDeviceToHost));
+    if (outInvU && n32) HS_HIP(hipMemcpy(outInvU + pInv, d.invU, sizeof(T) * n32, hipMemcpyDeviceToHost));
+    if (outInv256L && n256) HS_HIP(hipMemcpy(outInv256L + pInv256, d.inv256L, sizeof(T) * n256, hipMemcpyDeviceToHost));
+    if (outInv256U && n256) HS_HIP(hipMemcpy(outInv256U + pInv256, d.inv256U, sizeof(T) * n256, hipMemcpyDeviceToHost));
     pLF += (size_t)m * ni; pUR += (size_t)ni * nb; pSB += (size_t)nb * nb; pR += ni; pInv += n32; pInv256 += n256;
   }
-  return HS_OK;
 }
 
 template <class T>
-static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, T* outLF, T* outUR, T* outSB,
-                            int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U,
-                            double* ms_out) {
-  if (int st = FrontBatch<T>::check("hsk_front_batch", count, ni_, nb_, F, mode, 0)) return st;
-  if ((outInvL || outInvU || outInv256L || outInv256U) && mode < 2) {
-    hs_set_error(HS_ERR_ARGUMENT, mode, "hsk_front_batch: the stored inverses are returned by modes 2 and 3 only");
-    return HS_ERR_ARGUMENT;
-  }
+static void front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, T* outLF, T* outUR, T* outSB,
+                             int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U,
+                             double* ms_out) {
+  FrontBatch<T>::check("hsk_front_batch", count, ni_, nb_, F, mode, 0);
+  if ((outInvL || outInvU || outInv256L || outInv256U) && mode < 2)
+    HS_FAIL(HS_ERR_ARGUMENT, mode, "hsk_front_batch: the stored inverses are returned by modes 2 and 3 only");
   FrontBatch<T> fb;
-  if (int st = fb.setup(count, ni_, nb_, F)) return st;
-  if (int st = fb.upload_solve()) return st;
-  if (int st = fb.factor(mode, ms_out)) return st;
-  return fb.copy_out(outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U);
+  fb.setup(count, ni_, nb_, F);
+  fb.upload_solve();
+  fb.factor(mode, ms_out);
+  fb.copy_out(outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U);
 }
 
 // One tree level of ldiv!: the batch above, factored in mode 2 or 3, then the level's forward and backward sweeps on a global vector (the
@@ -525,57 +450,46 @@ static int front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb
 // hs_api.hip call for every level -- here without the low-rank and HSS calls around and between them, and with `path` given instead of read
 // from HS_SOLVE_FLOW / HS_SOLVE_WIDE (hs_sweep_path).
 template <class T>
-static int sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, const int64_t* flags, int64_t n,
-                            const int64_t* fidx, const T* b, int path, int trans, int tall, T* outLF, T* outUR, int64_t* out_rperm, int64_t* info,
-                            int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U, T* out_y, T* out_bfwd, T* out_x, T* out_bbwd,
-                            int* tall_used) {
+static void sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, const int64_t* flags, int64_t n,
+                             const int64_t* fidx, const T* b, int path, int trans, int tall, T* outLF, T* outUR, int64_t* out_rperm, int64_t* info,
+                             int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U, T* out_y, T* out_bfwd, T* out_x, T* out_bbwd,
+                             int* tall_used) {
   const char* name = "hsk_sweep_level";
-  if (int st = FrontBatch<T>::check(name, count, ni_, nb_, F, mode, 2)) return st;
-  if (!fidx || !b || n <= 0 || n > 0x7fffffff || path < 0 || path > 2 || trans < 0 || trans > 2 || tall < -1 || tall > 1) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "%s: fidx and b non-null, n in [1, 2^31), path in 0..2, trans in 0..2 and tall in -1..1 required", name);
-    return HS_ERR_ARGUMENT;
-  }
-  if (path == 2 && trans != 0) {
-    hs_set_error(HS_ERR_ARGUMENT, trans, "%s: the 32-column sweeps (path 2) exist for trans = 0 only", name);
-    return HS_ERR_ARGUMENT;
-  }
-  if (trans == 2 && sizeof(T) == 8) {
-    hs_set_error(HS_ERR_ARGUMENT, trans, "%s: trans = 2 (adjoint) is for ComplexF64; Float64 has trans = 1", name);
-    return HS_ERR_ARGUMENT;
-  }
+  FrontBatch<T>::check(name, count, ni_, nb_, F, mode, 2);
+  if (!fidx || !b || n <= 0 || n > 0x7fffffff || path < 0 || path > 2 || trans < 0 || trans > 2 || tall < -1 || tall > 1)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "%s: fidx and b non-null, n in [1, 2^31), path in 0..2, trans in 0..2 and tall in -1..1 required", name);
+  if (path == 2 && trans != 0) HS_FAIL(HS_ERR_ARGUMENT, trans, "%s: the 32-column sweeps (path 2) exist for trans = 0 only", name);
+  if (trans == 2 && sizeof(T) == 8) HS_FAIL(HS_ERR_ARGUMENT, trans, "%s: trans = 2 (adjoint) is for ComplexF64; Float64 has trans = 1", name);
   size_t nidx = 0;
   for (int64_t k = 0; k < count; ++k) nidx += (size_t)(ni_[k] + nb_[k]);
   std::vector<int> hidx(nidx + 1, 0);
   {
     std::vector<char> seen((size_t)n, 0);
     for (size_t p = 0; p < nidx; ++p) {
-      if (fidx[p] < 0 || fidx[p] >= n || seen[(size_t)fidx[p]]) {
-        hs_set_error(HS_ERR_ARGUMENT, (int64_t)p, "%s: fidx[%lld] = %lld is outside 0:%lld or occurs twice (the fronts of a level are disjoint)", name,
-                     (long long)p, (long long)fidx[p], (long long)n - 1);
-        return HS_ERR_ARGUMENT;
-      }
+      if (fidx[p] < 0 || fidx[p] >= n || seen[(size_t)fidx[p]])
+        HS_FAIL(HS_ERR_ARGUMENT, (int64_t)p, "%s: fidx[%lld] = %lld is outside 0:%lld or occurs twice (the fronts of a level are disjoint)", name,
+                (long long)p, (long long)fidx[p], (long long)n - 1);
       seen[(size_t)fidx[p]] = 1;
       hidx[p] = (int)fidx[p];
     }
   }
   FrontBatch<T> fb;
-  if (int st = fb.setup(count, ni_, nb_, F)) return st;
-  struct Bufs {  // an early return of CK leaves nothing behind
-    int *fidx = nullptr, *counter = nullptr, *err = nullptr;
-    T *w1 = nullptr, *w2 = nullptr, *e1 = nullptr, *e2 = nullptr, *part = nullptr, *b = nullptr;
-    ~Bufs() {
-      for (void* q : {(void*)fidx, (void*)counter, (void*)w1, (void*)w2, (void*)e1, (void*)e2, (void*)part, (void*)b}) (void)hipFree(q);
-      if (err) (void)hipHostFree(err);
+  fb.setup(count, ni_, nb_, F);
+  struct MappedWord {  // the error word the sweep kernels write: host memory the device sees (freed after the device buffers, as before)
+    int* p = nullptr;
+    ~MappedWord() {
+      if (p) (void)hipHostFree(p);
     }
-  } d;
-  CK(hipMalloc((void**)&d.fidx, sizeof(int) * (nidx + 1)));
-  CK(hipMemcpy(d.fidx, hidx.data(), sizeof(int) * (nidx + 1), hipMemcpyHostToDevice));
+  } err;
+  HsDevBuf buf(name);
+  int* dfidx = buf.get<int>(nidx + 1);
+  HS_HIP(hipMemcpy(dfidx, hidx.data(), sizeof(int) * (nidx + 1), hipMemcpyHostToDevice));
   // woff / poff as hs_analyze lays them out: packed, one entry of slack at the end of the buffers
   long long woff = 0, poff = 0;
   size_t ioff = 0;
   for (int64_t k = 0; k < count; ++k) {
     SolveNode<T>& q = fb.hs[k];
-    q.fidx = d.fidx + ioff;
+    q.fidx = dfidx + ioff;
     q.woff = woff;
     q.poff = poff;
     if (flags && (flags[k] & 1)) {
@@ -586,9 +500,9 @@ static int sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb
     woff += q.ni;
     poff += (long long)((q.nb + 511) / 512) * q.ni;
   }
-  if (int st = fb.upload_solve()) return st;
-  if (int st = fb.factor(mode, nullptr)) return st;
-  if (int st = fb.copy_out(outLF, outUR, nullptr, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U)) return st;
+  fb.upload_solve();
+  fb.factor(mode, nullptr);
+  fb.copy_out(outLF, outUR, nullptr, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U);
   bool blanked = false;
   for (int64_t k = 0; k < count; ++k)
     if (flags && (flags[k] & 2)) {  // as hs_analyze blanks the descriptor of a front whose interior block is an HSS matrix
@@ -596,80 +510,72 @@ static int sweep_level_hook(int64_t count, const int64_t* ni_, const int64_t* nb
       q.ni = q.nb = q.m = q.mrows = 0;
       blanked = true;
     }
-  if (blanked)
-    if (int st = fb.upload_solve()) return st;
-  const size_t wbytes = sizeof(T) * (size_t)(woff + 1);
-  CK(hipMalloc((void**)&d.w1, wbytes));
-  CK(hipMalloc((void**)&d.w2, wbytes));
-  CK(hipMalloc((void**)&d.e1, wbytes));
-  CK(hipMalloc((void**)&d.e2, wbytes));
-  CK(hipMalloc((void**)&d.part, sizeof(T) * (size_t)(poff + 1)));
-  CK(hipMalloc((void**)&d.b, sizeof(T) * (size_t)n));
-  CK(hipMalloc((void**)&d.counter, sizeof(int)));
-  CK(hipHostMalloc((void**)&d.err, sizeof(int), hipHostMallocMapped));
-  *d.err = 0;
-  CK(hipMemset(d.w1, 0, wbytes));
-  CK(hipMemset(d.w2, 0, wbytes));
-  CK(hipMemset(d.part, 0, sizeof(T) * (size_t)(poff + 1)));
-  CK(hipMemcpy(d.b, b, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
-  const SweepLevel<T> lvl = {fb.dsn, (int)count, fb.maxni, fb.maxnb, fb.maxm, d.w1, d.w2, d.part, d.b, d.e1, d.e2, d.err};
+  if (blanked) fb.upload_solve();
+  const size_t nw = (size_t)(woff + 1), wbytes = sizeof(T) * nw;
+  T* w1 = buf.get<T>(nw);
+  T* w2 = buf.get<T>(nw);
+  T* e1 = buf.get<T>(nw);
+  T* e2 = buf.get<T>(nw);
+  T* part = buf.get<T>((size_t)(poff + 1));
+  T* db = buf.get<T>((size_t)n);
+  int* counter = buf.get<int>(1);
+  HS_HIP(hipHostMalloc((void**)&err.p, sizeof(int), hipHostMallocMapped));
+  *err.p = 0;
+  HS_HIP(hipMemset(w1, 0, wbytes));
+  HS_HIP(hipMemset(w2, 0, wbytes));
+  HS_HIP(hipMemset(part, 0, sizeof(T) * (size_t)(poff + 1)));
+  HS_HIP(hipMemcpy(db, b, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+  const SweepLevel<T> lvl = {fb.dsn, (int)count, fb.maxni, fb.maxnb, fb.maxm, w1, w2, part, db, e1, e2, err.p};
   const hipStream_t s = nullptr;
   const int tall_rule = hs_fwd_flow_tall<T>(lvl.nfronts, lvl.maxnb);
   if (tall_used) *tall_used = (path == 0 && trans == 0) ? (tall >= 0 ? tall : tall_rule) : 0;
-  auto arm = [&]() -> int {  // flow_arm and a fresh workgroup-id counter
-    CK(hipMemsetAsync(d.e1, 0xFF, wbytes, s));
-    CK(hipMemsetAsync(d.e2, 0xFF, wbytes, s));
-    CK(hipMemsetAsync(d.counter, 0, sizeof(int), s));
-    return HS_OK;
+  auto arm = [&] {  // flow_arm and a fresh workgroup-id counter
+    HS_HIP(hipMemsetAsync(e1, 0xFF, wbytes, s));
+    HS_HIP(hipMemsetAsync(e2, 0xFF, wbytes, s));
+    HS_HIP(hipMemsetAsync(counter, 0, sizeof(int), s));
   };
-  auto finish = [&](const char* dir) -> int {  // flow_check
-    CK(hipDeviceSynchronize());
-    if (*d.err) {
-      hs_set_error(HS_ERR_DEVICE, 0, "%s: a workgroup of the %s sweep waited for a block that never arrived", name, dir);
-      return HS_ERR_DEVICE;
-    }
-    return HS_OK;
+  auto finish = [&](const char* dir) {  // flow_check
+    HS_HIP(hipDeviceSynchronize());
+    if (*err.p) HS_FAIL(HS_ERR_DEVICE, 0, "%s: a workgroup of the %s sweep waited for a block that never arrived", name, dir);
   };
-  auto copy_w = [&](T* out) -> int {  // the level's w2, packed per front (ni entries each)
-    if (out && woff > 0) CK(hipMemcpy(out, d.w2, sizeof(T) * (size_t)woff, hipMemcpyDeviceToHost));
-    return HS_OK;
+  auto copy_w = [&](T* out) {  // the level's w2, packed per front (ni entries each)
+    if (out && woff > 0) HS_HIP(hipMemcpy(out, w2, sizeof(T) * (size_t)woff, hipMemcpyDeviceToHost));
   };
-  auto copy_b = [&](T* out) -> int {
-    if (out) CK(hipMemcpy(out, d.b, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost));
-    return HS_OK;
+  auto copy_b = [&](T* out) {
+    if (out) HS_HIP(hipMemcpy(out, db, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost));
   };
   const bool level_on = lvl.maxni > 0;  // (solve_fwd / solve_bwd skip a level without interior DOFs)
   // forward
   if (level_on) {
-    if (int st = arm()) return st;
-    sweep_level_fwd<T>(lvl, path, trans, d.counter, s, tall);
-    if (int st = finish("forward")) return st;
+    arm();
+    sweep_level_fwd<T>(lvl, path, trans, counter, s, tall);
+    finish("forward");
   }
-  if (int st = copy_w(out_y)) return st;
-  if (int st = copy_b(out_bfwd)) return st;
+  copy_w(out_y);
+  copy_b(out_bfwd);
   // backward, on the b and y the forward sweep left
   if (level_on) {
-    if (int st = arm()) return st;
-    sweep_level_bwd<T>(lvl, path, trans, d.counter, s);
-    if (int st = finish("backward")) return st;
+    arm();
+    sweep_level_bwd<T>(lvl, path, trans, counter, s);
+    finish("backward");
   }
-  if (int st = copy_w(out_x)) return st;
-  return copy_b(out_bbwd);
+  copy_w(out_x);
+  copy_b(out_bbwd);
 }
 extern "C" int hsk_sweep_level_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int64_t* flags, int64_t n,
                                  const int64_t* fidx, const double* b, int path, int trans, int tall, double* outLF, double* outUR,
                                  int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU, double* outInv256L,
                                  double* outInv256U, double* y, double* b_fwd, double* x, double* b_bwd, int* tall_used) {
-  return sweep_level_hook<double>(count, ni, nb, mode, F, flags, n, fidx, b, path, trans, tall, outLF, outUR, out_rperm, info, growth, outInvL,
-                                  outInvU, outInv256L, outInv256U, y, b_fwd, x, b_bwd, tall_used);
+  HS_GUARD(sweep_level_hook<double>(count, ni, nb, mode, F, flags, n, fidx, b, path, trans, tall, outLF, outUR, out_rperm, info, growth, outInvL,
+                                    outInvU, outInv256L, outInv256U, y, b_fwd, x, b_bwd, tall_used));
 }
 extern "C" int hsk_sweep_level_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int64_t* flags, int64_t n,
                                  const int64_t* fidx, const double* b, int path, int trans, int tall, double* outLF, double* outUR,
                                  int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU, double* outInv256L,
                                  double* outInv256U, double* y, double* b_fwd, double* x, double* b_bwd, int* tall_used) {
-  return sweep_level_hook<cplx>(count, ni, nb, mode, (const cplx*)F, flags, n, fidx, (const cplx*)b, path, trans, tall, (cplx*)outLF, (cplx*)outUR,
-                                out_rperm, info, growth, (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, (cplx*)y,
-                                (cplx*)b_fwd, (cplx*)x, (cplx*)b_bwd, tall_used);
+  HS_GUARD(sweep_level_hook<cplx>(count, ni, nb, mode, (const cplx*)F, flags, n, fidx, (const cplx*)b, path, trans, tall, (cplx*)outLF, (cplx*)outUR,
+                                  out_rperm, info, growth, (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, (cplx*)y,
+                                  (cplx*)b_fwd, (cplx*)x, (cplx*)b_bwd, tall_used));
 }
 extern "C" int hsk_sweep_path() { return hs_sweep_path(); }
 extern "C" int hsk_flow_tall_rule(int is_complex, int64_t nbatch, int64_t maxnb) {
@@ -680,195 +586,164 @@ extern "C" int hsk_flow_tall_rule(int is_complex, int64_t nbatch, int64_t maxnb)
 extern "C" int hsk_front_batch_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
                                  double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
                                  double* outInv256L, double* outInv256U, double* ms_out) {
-  return front_batch_hook<double>(count, ni, nb, mode, F, outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U, ms_out);
+  HS_GUARD(front_batch_hook<double>(count, ni, nb, mode, F, outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U, ms_out));
 }
 extern "C" int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
                                  double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
                                  double* outInv256L, double* outInv256U, double* ms_out) {
-  return front_batch_hook<cplx>(count, ni, nb, mode, (const cplx*)F, (cplx*)outLF, (cplx*)outUR, (cplx*)outSB, out_rperm, info, growth,
-                                (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, ms_out);
+  HS_GUARD(front_batch_hook<cplx>(count, ni, nb, mode, (const cplx*)F, (cplx*)outLF, (cplx*)outUR, (cplx*)outSB, out_rperm, info, growth,
+                                  (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, ms_out));
 }
 
 // `count` fronts of one shape, tournament pivoting without solve descriptors (mode 0); HS_HOOK_OPTIMISTIC=1: mode 1, and a raised growth
 // flag comes back through `info` as -1
 template <class T>
-static int front_hook(int64_t count, int64_t ni, int64_t nb, const T* F, T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info,
-                      double* ms_out) {
-  if (count <= 0) {
-    hs_set_error(HS_ERR_ARGUMENT, count, "hsk_front_factor: count must be positive");
-    return HS_ERR_ARGUMENT;
-  }
+static void front_hook(int64_t count, int64_t ni, int64_t nb, const T* F, T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info,
+                       double* ms_out) {
+  if (count <= 0) HS_FAIL(HS_ERR_ARGUMENT, count, "hsk_front_factor: count must be positive");
   const bool hook_opt = getenv("HS_HOOK_OPTIMISTIC") != nullptr;
   std::vector<int64_t> vni(count, ni), vnb(count, nb), inf(count), gr(count);
-  const int st = front_batch_hook<T>(count, vni.data(), vnb.data(), hook_opt ? 1 : 0, F, outLF, outUR, outSB, out_rperm, inf.data(), gr.data(),
-                                     nullptr, nullptr, nullptr, nullptr, ms_out);
-  if (st != HS_OK) return st;
+  front_batch_hook<T>(count, vni.data(), vnb.data(), hook_opt ? 1 : 0, F, outLF, outUR, outSB, out_rperm, inf.data(), gr.data(), nullptr, nullptr,
+                      nullptr, nullptr, ms_out);
   if (info)
     for (int64_t k = 0; k < count; ++k) info[k] = hook_opt ? ((inf[k] != 0 || gr[k] != 0) ? -1 : 0) : inf[k];
-  return HS_OK;
 }
 
 extern "C" int hsk_front_factor_d(int64_t count, int64_t ni, int64_t nb, const double* F, double* outLF, double* outUR, double* outSB,
                                   int64_t* out_rperm, int64_t* info, double* ms_out) {
-  return front_hook<double>(count, ni, nb, F, outLF, outUR, outSB, out_rperm, info, ms_out);
+  HS_GUARD(front_hook<double>(count, ni, nb, F, outLF, outUR, outSB, out_rperm, info, ms_out));
 }
 extern "C" int hsk_front_factor_z(int64_t count, int64_t ni, int64_t nb, const double* F, double* outLF, double* outUR, double* outSB,
                                   int64_t* out_rperm, int64_t* info, double* ms_out) {
-  return front_hook<cplx>(count, ni, nb, (const cplx*)F, (cplx*)outLF, (cplx*)outUR, (cplx*)outSB, out_rperm, info, ms_out);
+  HS_GUARD(front_hook<cplx>(count, ni, nb, (const cplx*)F, (cplx*)outLF, (cplx*)outUR, (cplx*)outSB, out_rperm, info, ms_out));
 }
 
 // Low-rank compression of a dense rows x cols block (column-major host array): returns the rank r and
 // the dense factors C (rows x r) and Z (r x cols), X ~= C * Z, built from the device representation.
 template <class T>
-static int lowrank_hook(int64_t rows, int64_t cols, const T* X, double atol, double rtol, int64_t kinit, int64_t seed, int64_t* r_out, T* Cout,
-                        T* Zout, int64_t cap) {
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
-  T* dX = nullptr;
+static void lowrank_hook(int64_t rows, int64_t cols, const T* X, double atol, double rtol, int64_t kinit, int64_t seed, int64_t* r_out, T* Cout,
+                         T* Zout, int64_t cap) {
+  need_device();
+  HsDevBuf buf("hsk_lowrank");
   const int ldx = ((int)rows + 1) / 2 * 2;
-  CK(hipMalloc((void**)&dX, sizeof(T) * ((size_t)ldx * cols + 32)));
-  CK(hipMemcpy2D(dX, sizeof(T) * ldx, X, sizeof(T) * rows, sizeof(T) * rows, cols, hipMemcpyHostToDevice));
+  T* dX = buf.get<T>((size_t)ldx * cols + 32);
+  HS_HIP(hipMemcpy2D(dX, sizeof(T) * ldx, X, sizeof(T) * rows, sizeof(T) * rows, cols, hipMemcpyHostToDevice));
   // the primitive the compressed fronts use (hs_compress.h): interpolative form, rank and interpolation from the orthogonalisation of
   // the sketch rows in tournament-pivot order (lowrank_id_batch); HS_LR_QR=0: the LU-based factors of hs_lowrank.hip
   static const bool lr_qr = !(getenv("HS_LR_QR") && getenv("HS_LR_QR")[0] == '0');
   LowRank<T> lr;
-  int st;
+  struct Release {  // whatever the compression has allocated by the time this scope is left
+    LowRank<T>& lr;
+    ~Release() { lowrank_free(lr); }
+  } release{lr};
   if (lr_qr) {
     LowRankJob<T> job{dX, ldx, (int)rows, (int)cols, (int)kinit, (uint64_t)seed, &lr, 0};
-    st = lowrank_id_batch<T>(&job, 1, atol, rtol, 0);
+    HS_CHECK(lowrank_id_batch<T>(&job, 1, atol, rtol, 0));
   } else {
-    st = lowrank_compress<T>(dX, ldx, (int)rows, (int)cols, atol, rtol, (int)kinit, (uint64_t)seed, 0, &lr);
+    HS_CHECK(lowrank_compress<T>(dX, ldx, (int)rows, (int)cols, atol, rtol, (int)kinit, (uint64_t)seed, 0, &lr));
   }
-  if (st != 0) return st;
   *r_out = lr.r;
-  if (lr.r > cap) {
-    hs_set_error(HS_ERR_ARGUMENT, lr.r, "rank %d exceeds the output capacity %lld", lr.r, (long long)cap);
-    return HS_ERR_ARGUMENT;
-  }
+  if (lr.r > cap) HS_FAIL(HS_ERR_ARGUMENT, lr.r, "rank %d exceeds the output capacity %lld", lr.r, (long long)cap);
   if (lr.Cd) {
-    if (lr.r > 0) CK(hipMemcpy2D(Cout, sizeof(T) * rows, lr.Cd, sizeof(T) * lr.ldc, sizeof(T) * rows, lr.r, hipMemcpyDeviceToHost));
+    if (lr.r > 0) bring_block(Cout, rows, lr.Cd, lr.ldc, rows, lr.r);
   } else {
     std::vector<T> hL((size_t)lr.ldp * lr.k);
     std::vector<int> rp(rows);
-    CK(hipMemcpy(hL.data(), lr.Lp, sizeof(T) * hL.size(), hipMemcpyDeviceToHost));
-    CK(hipMemcpy(rp.data(), lr.rperm, sizeof(int) * rows, hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(hL.data(), lr.Lp, sizeof(T) * hL.size(), hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(rp.data(), lr.rperm, sizeof(int) * rows, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < rows; ++i)
       for (int64_t j = 0; j < lr.r; ++j) {
         T v = (i == j) ? Scal<T>::one() : (i > j ? hL[(size_t)i + (size_t)j * lr.ldp] : Scal<T>::zero());
         Cout[(size_t)rp[i] + (size_t)j * rows] = v;
       }
   }
-  if (lr.r > 0) CK(hipMemcpy2D(Zout, sizeof(T) * lr.r, lr.Z, sizeof(T) * lr.ldz, sizeof(T) * lr.r, cols, hipMemcpyDeviceToHost));
-  lowrank_free(lr);
-  (void)hipFree(dX);
-  return HS_OK;
+  if (lr.r > 0) bring_block(Zout, lr.r, lr.Z, lr.ldz, lr.r, cols);
 }
 extern "C" int hsk_lowrank_d(int64_t rows, int64_t cols, const double* X, double atol, double rtol, int64_t kinit, int64_t seed, int64_t* r_out,
                              double* Cout, double* Zout, int64_t cap) {
-  return lowrank_hook<double>(rows, cols, X, atol, rtol, kinit, seed, r_out, Cout, Zout, cap);
+  HS_GUARD(lowrank_hook<double>(rows, cols, X, atol, rtol, kinit, seed, r_out, Cout, Zout, cap));
 }
 extern "C" int hsk_lowrank_z(int64_t rows, int64_t cols, const double* X, double atol, double rtol, int64_t kinit, int64_t seed, int64_t* r_out,
                              double* Cout, double* Zout, int64_t cap) {
-  return lowrank_hook<cplx>(rows, cols, (const cplx*)X, atol, rtol, kinit, seed, r_out, (cplx*)Cout, (cplx*)Zout, cap);
+  HS_GUARD(lowrank_hook<cplx>(rows, cols, (const cplx*)X, atol, rtol, kinit, seed, r_out, (cplx*)Cout, (cplx*)Zout, cap));
 }
 
 // The panel products of the block solves (kernels_solve_multi.hip, kernels_solve_multi_t.hip) on host data, staged by one helper: X and C
 // reach the kernel row-major with a pitch of 64, as the work blocks of the driver do.  A is lda x acols with arows rows in use (forward
 // M x K, transposed K x M); map (null: none) has nmap entries in 0..nmap-1; launch(dA, dX, dC, dmap, pitch) fills the problem struct.
 template <class T, class Launch>
-static int multi_prob_stage(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx,
-                            T* C, int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
+static void multi_prob_stage(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx,
+                             T* C, int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
   bool ok = M >= 1 && K >= 0 && kc >= 1 && kc <= 64 && lda >= std::max<int64_t>(arows, 1) && ldx >= std::max<int64_t>(K, 1) && ldc >= M && A && X && C;
   for (int64_t i = 0; ok && map && i < nmap; ++i) ok = map[i] >= 0 && map[i] < nmap;
-  if (!ok) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "%s: M >= 1, K >= 0, kc in 1..64, leading dimensions, non-null arrays and map entries inside their range required", name);
-    return HS_ERR_ARGUMENT;
-  }
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
+  if (!ok) HS_FAIL(HS_ERR_ARGUMENT, 0, "%s: M >= 1, K >= 0, kc in 1..64, leading dimensions, non-null arrays and map entries inside their range required", name);
+  need_device();
   const int64_t P = 64;
   std::vector<T> hx((size_t)std::max<int64_t>(K, 1) * P), hc((size_t)M * P);
   for (int64_t c = 0; c < kc; ++c) {
     for (int64_t k = 0; k < K; ++k) hx[k * P + c] = X[k + c * ldx];
     for (int64_t i = 0; i < M; ++i) hc[i * P + c] = C[i + c * ldc];
   }
-  T *dA = nullptr, *dX = nullptr, *dC = nullptr;
+  HsDevBuf buf(name);
+  T* dA = buf.get<T>((size_t)lda * std::max<int64_t>(acols, 1));
+  T* dX = buf.get<T>(hx.size());
+  T* dC = buf.get<T>(hc.size());
+  if (K > 0) HS_HIP(hipMemcpy(dA, A, sizeof(T) * ((size_t)lda * (acols - 1) + arows), hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dX, hx.data(), sizeof(T) * hx.size(), hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dC, hc.data(), sizeof(T) * hc.size(), hipMemcpyHostToDevice));
   int* dmap = nullptr;
-  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)lda * std::max<int64_t>(acols, 1)));
-  CK(hipMalloc((void**)&dX, sizeof(T) * hx.size()));
-  CK(hipMalloc((void**)&dC, sizeof(T) * hc.size()));
-  if (K > 0) CK(hipMemcpy(dA, A, sizeof(T) * ((size_t)lda * (acols - 1) + arows), hipMemcpyHostToDevice));
-  CK(hipMemcpy(dX, hx.data(), sizeof(T) * hx.size(), hipMemcpyHostToDevice));
-  CK(hipMemcpy(dC, hc.data(), sizeof(T) * hc.size(), hipMemcpyHostToDevice));
   if (map && nmap > 0) {
-    CK(hipMalloc((void**)&dmap, sizeof(int) * (size_t)nmap));
-    CK(hipMemcpy(dmap, map, sizeof(int) * (size_t)nmap, hipMemcpyHostToDevice));
+    dmap = buf.get<int>((size_t)nmap);
+    HS_HIP(hipMemcpy(dmap, map, sizeof(int) * (size_t)nmap, hipMemcpyHostToDevice));
   }
   launch(dA, dX, dC, dmap, P);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy(hc.data(), dC, sizeof(T) * hc.size(), hipMemcpyDeviceToHost));
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(hc.data(), dC, sizeof(T) * hc.size(), hipMemcpyDeviceToHost));
   for (int64_t c = 0; c < kc; ++c)
     for (int64_t i = 0; i < M; ++i) C[i + c * ldc] = hc[i * P + c];
-  (void)hipFree(dA);
-  (void)hipFree(dX);
-  (void)hipFree(dC);
-  (void)hipFree(dmap);
-  return HS_OK;
 }
 // The same staging for the two products over a Float32 panel (kernels_solve_multi_f32.hip): A arrives in Float64, is demoted on the device
 // by the library's demotion kernel (kernels_f32.hip) into a copy with the leading dimension hs_f32_create would give it, and the product
 // reads the copy.
 #include "hs_f32.h"
 template <class T, class Launch>
-static int multi_prob_f32_stage(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx, T* C,
-                                int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
+static void multi_prob_f32_stage(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx, T* C,
+                                 int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
   typedef typename F32Of<T>::type S;
   constexpr int RE = sizeof(T) / 8;
   const long long ldd = RE == 2 ? std::max<long long>(arows, 1) : hs_f32_ld(arows);
-  S* dS = nullptr;
-  unsigned long long* dcnt = nullptr;
-  F32Job* djob = nullptr;
-  int gpus = 0;
-  if (hipGetDeviceCount(&gpus) == hipSuccess && gpus > 0 && arows >= 1 && acols >= 0 && lda >= arows) {  // (the staging below refuses everything else)
-    CK(hipMalloc((void**)&dS, sizeof(S) * (size_t)ldd * std::max<int64_t>(acols, 1)));
-    CK(hipMalloc((void**)&dcnt, 2 * sizeof(unsigned long long)));
-    CK(hipMalloc((void**)&djob, sizeof(F32Job)));
-    CK(hipMemset(dcnt, 0, 2 * sizeof(unsigned long long)));
-  }
-  const int st = multi_prob_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
-    if (K > 0) {
-      const F32Job job{(const double*)dA, (void*)dS, (long long)lda * RE, ldd * RE, (int)arows * RE, (int)acols};
-      (void)hipMemcpy(djob, &job, sizeof job, hipMemcpyHostToDevice);
-      launch_f32_demote(djob, 1, job.rows, job.cols, false, dcnt, 0);
+  HsDevBuf buf(name);
+  multi_prob_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
+    S* dS = nullptr;
+    if (arows >= 1) {  // (a transposed product with K = 0 has no panel)
+      dS = buf.get<S>((size_t)ldd * std::max<int64_t>(acols, 1));
+      unsigned long long* dcnt = buf.get<unsigned long long>(2);
+      F32Job* djob = buf.get<F32Job>(1);
+      HS_HIP(hipMemset(dcnt, 0, 2 * sizeof(unsigned long long)));
+      if (K > 0) {
+        const F32Job job{(const double*)dA, (void*)dS, (long long)lda * RE, ldd * RE, (int)arows * RE, (int)acols};
+        HS_HIP(hipMemcpy(djob, &job, sizeof job, hipMemcpyHostToDevice));
+        launch_f32_demote(djob, 1, job.rows, job.cols, false, dcnt, 0);
+      }
     }
     launch(dS, (int)ldd, dX, dC, dmap, P);
   });
-  (void)hipFree(dS);
-  (void)hipFree(dcnt);
-  (void)hipFree(djob);
-  return st;
 }
 // the staging of a hook whose panel is stored as S: launch(dA as S, its leading dimension, dX, dC, dmap, pitch)
 template <class T, class S, class Launch>
-static int multi_prob_stage_as(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx, T* C,
-                               int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
+static void multi_prob_stage_as(const char* name, int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, int64_t arows, int64_t acols, const T* X, int64_t ldx, T* C,
+                                int64_t ldc, const int32_t* map, int64_t nmap, Launch launch) {
   if constexpr (std::is_same<T, S>::value)
-    return multi_prob_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap,
-                               [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) { launch(dA, (int)lda, dX, dC, dmap, P); });
+    multi_prob_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap,
+                        [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) { launch(dA, (int)lda, dX, dC, dmap, P); });
   else
-    return multi_prob_f32_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap, launch);
+    multi_prob_f32_stage<T>(name, M, K, kc, A, lda, arows, acols, X, ldx, C, ldc, map, nmap, launch);
 }
 // C = A X or C - A X, A M x K; map: cmap, row i of the product goes to row map[i] of C
 template <class T, class S>
-static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, const int32_t* map) {
+static void multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, const int32_t* map) {
   const char* name = std::is_same<T, S>::value ? "hsk_multi_prob" : "hsk_multi_prob_f32";
-  return multi_prob_stage_as<T, S>(name, M, K, kc, A, lda, M, K, X, ldx, C, ldc, map, M, [&](const S* dA, int ld, const T* dX, T* dC, const int* dmap, int64_t P) {
+  multi_prob_stage_as<T, S>(name, M, K, kc, A, lda, M, K, X, ldx, C, ldc, map, M, [&](const S* dA, int ld, const T* dX, T* dC, const int* dmap, int64_t P) {
     MultiProb<T, S> p;
     memset(&p, 0, sizeof p);
     p.A = dA; p.lda = ld; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0;
@@ -880,10 +755,10 @@ static int multi_prob_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t
 }
 // C = op(A)^T X or C - op(A)^T X, A K x M; map: xmap, row k of A meets row map[k] of X
 template <class T, class S>
-static int multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj,
-                             const int32_t* map) {
+static void multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int minus, int trap, int conj,
+                              const int32_t* map) {
   const char* name = std::is_same<T, S>::value ? "hsk_multi_prob_t" : "hsk_multi_prob_t_f32";
-  return multi_prob_stage_as<T, S>(name, M, K, kc, A, lda, K, M, X, ldx, C, ldc, map, K, [&](const S* dA, int ld, const T* dX, T* dC, const int* dmap, int64_t P) {
+  multi_prob_stage_as<T, S>(name, M, K, kc, A, lda, K, M, X, ldx, C, ldc, map, K, [&](const S* dA, int ld, const T* dX, T* dC, const int* dmap, int64_t P) {
     MultiProbT<T, S> p;
     memset(&p, 0, sizeof p);
     p.A = dA; p.lda = ld; p.M = (int)M; p.K = (int)K; p.trap = trap ? 1 : 0; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
@@ -895,57 +770,45 @@ static int multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64
 }
 extern "C" int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                 int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_hook<double, double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map);
+  HS_GUARD(multi_prob_hook<double, double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map));
 }
 extern "C" int hsk_multi_prob_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                 int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_hook<cplx, cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map);
+  HS_GUARD(multi_prob_hook<cplx, cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map));
 }
 extern "C" int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                   int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
-  return multi_prob_t_hook<double, double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map);
+  HS_GUARD(multi_prob_t_hook<double, double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map));
 }
 extern "C" int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                   int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
-  return multi_prob_t_hook<cplx, cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
+  HS_GUARD(multi_prob_t_hook<cplx, cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map));
 }
 extern "C" int hsk_multi_prob_f32_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                     int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_hook<double, float>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map);
+  HS_GUARD(multi_prob_hook<double, float>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map));
 }
 extern "C" int hsk_multi_prob_f32_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                     int64_t ldc, int minus, int trap, const int32_t* map) {
-  return multi_prob_hook<cplx, cplxf>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map);
+  HS_GUARD(multi_prob_hook<cplx, cplxf>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, map));
 }
 extern "C" int hsk_multi_prob_t_f32_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                       int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
-  return multi_prob_t_hook<double, float>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map);
+  HS_GUARD(multi_prob_t_hook<double, float>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, conj, map));
 }
 extern "C" int hsk_multi_prob_t_f32_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                       int64_t ldc, int minus, int trap, int conj, const int32_t* map) {
-  return multi_prob_t_hook<cplx, cplxf>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map);
+  HS_GUARD(multi_prob_t_hook<cplx, cplxf>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, minus, trap, conj, map));
 }
 // x <- (double)(float)x for every stored element hs_f32_create would demote, in place in the handle (hs_f32.hip)
-extern "C" int hsk_round_factors_f32(hs_handle* F, int64_t* counts2) {
-  try {
-    hs_f32_round_in_place(F, counts2);
-    return HS_OK;
-  } catch (int code) {
-    return code;
-  } catch (const std::bad_alloc&) {
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
-    return HS_ERR_NOMEM;
-  }
-}
+extern "C" int hsk_round_factors_f32(hs_handle* F, int64_t* counts2) { HS_GUARD(hs_f32_round_in_place(F, counts2)); }
 
 // one grouped launch of the transposed ULV product (kernels_ulv_t.hip) on caller-supplied jobs (include/hs_kernels.h)
 #include "hs_ulv_t.h"
 template <class T>
-static int ulv_t_group_hook(int64_t njobs, const int64_t* desc, const T* Abuf, int64_t na, const T* Xbuf, int64_t nx, T* Cbuf, int64_t nc, int conj) {
-  if (njobs < 1 || njobs > 65535 || !desc || !Abuf || !Xbuf || !Cbuf || na < 1 || nx < 1 || nc < 1) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_ulv_t_group: 1..65535 jobs, their descriptions and non-empty buffers required");
-    return HS_ERR_ARGUMENT;
-  }
+static void ulv_t_group_hook(int64_t njobs, const int64_t* desc, const T* Abuf, int64_t na, const T* Xbuf, int64_t nx, T* Cbuf, int64_t nc, int conj) {
+  if (njobs < 1 || njobs > 65535 || !desc || !Abuf || !Xbuf || !Cbuf || na < 1 || nx < 1 || nc < 1)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_ulv_t_group: 1..65535 jobs, their descriptions and non-empty buffers required");
   std::vector<UlvTJob<T>> jobs((size_t)njobs);
   int maxM = 0, maxN = 0;
   for (int64_t i = 0; i < njobs; ++i) {
@@ -956,10 +819,7 @@ static int ulv_t_group_hook(int64_t njobs, const int64_t* desc, const T* Abuf, i
     if (ok && !empty)
       ok = lda >= K && ldx >= K && ldc >= M && lda < (1 << 30) && ldx < (1 << 30) && ldc < (1 << 30) && ao + lda * (M - 1) + K <= na &&
            xo + ldx * (N - 1) + K <= nx && co + ldc * (N - 1) + M <= nc;
-    if (!ok) {
-      hs_set_error(HS_ERR_ARGUMENT, i, "hsk_ulv_t_group: job %lld reaches outside its buffers", (long long)i);
-      return HS_ERR_ARGUMENT;
-    }
+    if (!ok) HS_FAIL(HS_ERR_ARGUMENT, i, "hsk_ulv_t_group: job %lld reaches outside its buffers", (long long)i);
     UlvTJob<T>& j = jobs[(size_t)i];
     memset(&j, 0, sizeof j);
     if (empty) continue;  // (stays in the launch with M = K = N = 0: the kernel skips it)
@@ -970,17 +830,12 @@ static int ulv_t_group_hook(int64_t njobs, const int64_t* desc, const T* Abuf, i
     maxM = std::max(maxM, j.M);
     maxN = std::max(maxN, j.N);
   }
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
-  T *dA = nullptr, *dX = nullptr, *dC = nullptr;
-  UlvTJob<T>* dJ = nullptr;
-  CK(hipMalloc((void**)&dA, sizeof(T) * (size_t)na));
-  CK(hipMalloc((void**)&dX, sizeof(T) * (size_t)nx));
-  CK(hipMalloc((void**)&dC, sizeof(T) * (size_t)nc));
-  CK(hipMalloc((void**)&dJ, sizeof(UlvTJob<T>) * jobs.size()));
+  need_device();
+  HsDevBuf buf("hsk_ulv_t_group");
+  T* dA = buf.get<T>((size_t)na);
+  T* dX = buf.get<T>((size_t)nx);
+  T* dC = buf.get<T>((size_t)nc);
+  UlvTJob<T>* dJ = buf.get<UlvTJob<T>>(jobs.size());
   for (int64_t i = 0; i < njobs; ++i) {
     UlvTJob<T>& j = jobs[(size_t)i];
     if (j.M == 0) continue;
@@ -990,50 +845,29 @@ static int ulv_t_group_hook(int64_t njobs, const int64_t* desc, const T* Abuf, i
     j.C = dC + d[8];
     j.Cin = (d[9] & 1) ? j.C : nullptr;
   }
-  CK(hipMemcpy(dA, Abuf, sizeof(T) * (size_t)na, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dX, Xbuf, sizeof(T) * (size_t)nx, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dC, Cbuf, sizeof(T) * (size_t)nc, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dJ, jobs.data(), sizeof(UlvTJob<T>) * jobs.size(), hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dA, Abuf, sizeof(T) * (size_t)na, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dX, Xbuf, sizeof(T) * (size_t)nx, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dC, Cbuf, sizeof(T) * (size_t)nc, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dJ, jobs.data(), sizeof(UlvTJob<T>) * jobs.size(), hipMemcpyHostToDevice));
   launch_ulv_t<T>(dJ, (int)njobs, maxM, maxN, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy(Cbuf, dC, sizeof(T) * (size_t)nc, hipMemcpyDeviceToHost));
-  (void)hipFree(dA);
-  (void)hipFree(dX);
-  (void)hipFree(dC);
-  (void)hipFree(dJ);
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(Cbuf, dC, sizeof(T) * (size_t)nc, hipMemcpyDeviceToHost));
 }
 extern "C" int hsk_ulv_t_group_d(int64_t njobs, const int64_t* desc, const double* Abuf, int64_t na, const double* Xbuf, int64_t nx, double* Cbuf, int64_t nc, int conj) {
-  return ulv_t_group_hook<double>(njobs, desc, Abuf, na, Xbuf, nx, Cbuf, nc, conj);
+  HS_GUARD(ulv_t_group_hook<double>(njobs, desc, Abuf, na, Xbuf, nx, Cbuf, nc, conj));
 }
 extern "C" int hsk_ulv_t_group_z(int64_t njobs, const int64_t* desc, const double* Abuf, int64_t na, const double* Xbuf, int64_t nx, double* Cbuf, int64_t nc, int conj) {
-  return ulv_t_group_hook<cplx>(njobs, desc, (const cplx*)Abuf, na, (const cplx*)Xbuf, nx, (cplx*)Cbuf, nc, conj);
+  HS_GUARD(ulv_t_group_hook<cplx>(njobs, desc, (const cplx*)Abuf, na, (const cplx*)Xbuf, nx, (cplx*)Cbuf, nc, conj));
 }
 
 // The leaf-envelope builder of the analysis (hs_envelope.h), host only: tests compare it with a NumPy computation from A[idx][:, idx]
 // hsk_sddmm_*: the reduction kernel of hs_sens_* (kernels_sens.hip) alone on host data
 #include "hs_sens.h"
-namespace {
-struct SddmmBufs {
-  std::vector<void*> p;
-  ~SddmmBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  void* get(size_t bytes) {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
-    p.push_back(q);
-    return q;
-  }
-};
-}  // namespace
 template <class T>
-static int sddmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const T* L, int64_t ldl, const T* R, int64_t ldr, int swap, int conjl, int conjr,
-                      int diag, int form, T* G, double* seconds) {
-  if (n < 1 || n > 0x7fffffff || kc < 1 || kc > 4096 || !colptr || !L || !R || !G || ldl < n || ldr < n || form < 0 || form > 1 || colptr[0] != 1) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_sddmm: n >= 1, kc in 1..4096, 1-based colptr, leading dimensions >= n, form in 0:1 and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
+static void sddmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const T* L, int64_t ldl, const T* R, int64_t ldr, int swap, int conjl, int conjr,
+                       int diag, int form, T* G, double* seconds) {
+  if (n < 1 || n > 0x7fffffff || kc < 1 || kc > 4096 || !colptr || !L || !R || !G || ldl < n || ldr < n || form < 0 || form > 1 || colptr[0] != 1)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_sddmm: n >= 1, kc in 1..4096, 1-based colptr, leading dimensions >= n, form in 0:1 and non-null arrays required");
   const int64_t nnz = colptr[n] - 1;
   std::vector<int64_t> cp((size_t)n + 1);
   std::vector<int32_t> rv((size_t)std::max<int64_t>(nnz, 0));
@@ -1046,36 +880,25 @@ static int sddmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, i
     ok = rowval[e] >= 1 && rowval[e] <= n;
     rv[(size_t)e] = (int32_t)(rowval[e] - 1);
   }
-  if (!ok) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_sddmm: colptr decreases or rowval is outside 1:n");
-    return HS_ERR_ARGUMENT;
-  }
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
+  if (!ok) HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_sddmm: colptr decreases or rowval is outside 1:n");
+  need_device();
   const int64_t glen = diag ? n : nnz, stride = hs_sens_row_stride((int)kc, sizeof(T) == 16);
   const bool staged = form == 1 && !diag;
-  SddmmBufs b;
-  int64_t* dcp = (int64_t*)b.get(sizeof(int64_t) * (size_t)(n + 1));
-  int32_t* drv = (int32_t*)b.get(sizeof(int32_t) * (size_t)nnz);
-  int32_t* dec = (int32_t*)b.get(sizeof(int32_t) * (size_t)nnz);
-  T* dL = (T*)b.get(sizeof(T) * (size_t)ldl * kc);
-  T* dR = (T*)b.get(sizeof(T) * (size_t)ldr * kc);
-  T* dG = (T*)b.get(sizeof(T) * (size_t)glen);
-  T* dG2 = seconds ? (T*)b.get(sizeof(T) * (size_t)glen) : dG;
-  T* dLt = staged ? (T*)b.get(sizeof(T) * (size_t)n * stride) : dL;
-  T* dRt = staged ? (T*)b.get(sizeof(T) * (size_t)n * stride) : dR;
-  if (!dcp || !drv || !dec || !dL || !dR || !dG || !dG2 || !dLt || !dRt) {
-    hs_set_error(HS_ERR_NOMEM, 0, "hsk_sddmm: hipMalloc failed");
-    return HS_ERR_NOMEM;
-  }
-  CK(hipMemcpy(dcp, cp.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-  if (nnz > 0) CK(hipMemcpy(drv, rv.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dL, L, sizeof(T) * (size_t)ldl * kc, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dR, R, sizeof(T) * (size_t)ldr * kc, hipMemcpyHostToDevice));
-  if (glen > 0) CK(hipMemcpy(dG, G, sizeof(T) * (size_t)glen, hipMemcpyHostToDevice));
+  HsDevBuf b("hsk_sddmm");
+  int64_t* dcp = b.get<int64_t>((size_t)(n + 1));
+  int32_t* drv = b.get<int32_t>((size_t)nnz);
+  int32_t* dec = b.get<int32_t>((size_t)nnz);
+  T* dL = b.get<T>((size_t)ldl * kc);
+  T* dR = b.get<T>((size_t)ldr * kc);
+  T* dG = b.get<T>((size_t)glen);
+  T* dG2 = seconds ? b.get<T>((size_t)glen) : dG;
+  T* dLt = staged ? b.get<T>((size_t)n * stride) : dL;
+  T* dRt = staged ? b.get<T>((size_t)n * stride) : dR;
+  HS_HIP(hipMemcpy(dcp, cp.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+  if (nnz > 0) HS_HIP(hipMemcpy(drv, rv.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dL, L, sizeof(T) * (size_t)ldl * kc, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dR, R, sizeof(T) * (size_t)ldr * kc, hipMemcpyHostToDevice));
+  if (glen > 0) HS_HIP(hipMemcpy(dG, G, sizeof(T) * (size_t)glen, hipMemcpyHostToDevice));
   const HsSddmmFlags f{swap ? 1 : 0, conjl ? 1 : 0, conjr ? 1 : 0};
   launch_sens_entry_cols(dcp, n, nnz, dec, 0);
   auto run = [&](T* g) {
@@ -1090,35 +913,30 @@ static int sddmm_hook(int64_t n, const int64_t* colptr, const int64_t* rowval, i
     }
   };
   if (seconds) {  // one warm-up and three timed runs on a copy of G; the median
-    hipEvent_t e0, e1;
-    CK(hipEventCreate(&e0));
-    CK(hipEventCreate(&e1));
+    HsEvents<2> ev;
     float ms[4] = {0.f, 0.f, 0.f, 0.f};
-    if (glen > 0) CK(hipMemcpy(dG2, dG, sizeof(T) * (size_t)glen, hipMemcpyDeviceToDevice));
+    if (glen > 0) HS_HIP(hipMemcpy(dG2, dG, sizeof(T) * (size_t)glen, hipMemcpyDeviceToDevice));
     for (int k = 0; k < 4; ++k) {
-      CK(hipEventRecord(e0, 0));
+      HS_HIP(hipEventRecord(ev[0], 0));
       run(dG2);
-      CK(hipEventRecord(e1, 0));
-      CK(hipEventSynchronize(e1));
-      CK(hipEventElapsedTime(&ms[k], e0, e1));
+      HS_HIP(hipEventRecord(ev[1], 0));
+      HS_HIP(hipEventSynchronize(ev[1]));
+      HS_HIP(hipEventElapsedTime(&ms[k], ev[0], ev[1]));
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     std::sort(ms + 1, ms + 4);
     *seconds = ms[2] * 1e-3;
   }
   run(dG);
-  CK(hipDeviceSynchronize());
-  if (glen > 0) CK(hipMemcpy(G, dG, sizeof(T) * (size_t)glen, hipMemcpyDeviceToHost));
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  if (glen > 0) HS_HIP(hipMemcpy(G, dG, sizeof(T) * (size_t)glen, hipMemcpyDeviceToHost));
 }
 extern "C" int hsk_sddmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const double* L, int64_t ldl, const double* R, int64_t ldr, int swap,
                            int conjl, int conjr, int diag, int form, double* G, double* seconds) {
-  return sddmm_hook<double>(n, colptr, rowval, kc, L, ldl, R, ldr, swap, conjl, conjr, diag, form, G, seconds);
+  HS_GUARD(sddmm_hook<double>(n, colptr, rowval, kc, L, ldl, R, ldr, swap, conjl, conjr, diag, form, G, seconds));
 }
 extern "C" int hsk_sddmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const double* L, int64_t ldl, const double* R, int64_t ldr, int swap,
                            int conjl, int conjr, int diag, int form, double* G, double* seconds) {
-  return sddmm_hook<cplx>(n, colptr, rowval, kc, (const cplx*)L, ldl, (const cplx*)R, ldr, swap, conjl, conjr, diag, form, (cplx*)G, seconds);
+  HS_GUARD(sddmm_hook<cplx>(n, colptr, rowval, kc, (const cplx*)L, ldl, (const cplx*)R, ldr, swap, conjl, conjr, diag, form, (cplx*)G, seconds));
 }
 
 #include "hs_envelope.h"
@@ -1139,142 +957,92 @@ extern "C" int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t
 
 // the kernels of hs_mod_* (kernels_mod.hip) on host data (include/hs_kernels.h)
 #include "hs_mod.h"
-namespace {
-struct ModBufs {
-  std::vector<void*> p;
-  ~ModBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <class T>
-  T* up(const T* src, int64_t ld, int64_t rows, int64_t cols) {  // a rows x cols block as ld = max(rows, 1) on the device
-    void* q = nullptr;
-    const int64_t r = std::max<int64_t>(rows, 1);
-    if (hipMalloc(&q, sizeof(T) * (size_t)(r * std::max<int64_t>(cols, 1))) != hipSuccess) return nullptr;
-    p.push_back(q);
-    if (src && rows > 0 && cols > 0 && hipMemcpy2D(q, r * sizeof(T), src, ld * sizeof(T), rows * sizeof(T), cols, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return (T*)q;
-  }
-};
-int mod_hook_device() {
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
-  return HS_OK;
-}
-}  // namespace
-#define MOD_NULL(q)                                                     \
-  if (!(q)) {                                                           \
-    hs_set_error(HS_ERR_NOMEM, 0, "hsk_mod_*: device staging failed");  \
-    return HS_ERR_NOMEM;                                                \
-  }
 
 template <class T>
-static int mod_inner_hook(int64_t n, int64_t k, int64_t m, const T* P, int64_t ldp, const T* Y, int64_t ldy, int conj, T* Tm, int64_t ldt) {
-  if (n < 1 || k < 1 || k > HS_MOD_MAXRANK || m < 1 || m > HS_MOD_MAXCOLS || ldp < n || ldy < n || ldt < k || !P || !Y || !Tm) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_mod_inner: n >= 1, k in 1..256, m in 1..64, leading dimensions and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  if (int st = mod_hook_device()) return st;
-  ModBufs b;
-  T* dP = b.up<T>(P, ldp, n, k);
-  T* dY = b.up<T>(Y, ldy, n, m);
-  T* dT = b.up<T>(nullptr, k, k, m);
-  T* dPart = b.up<T>(nullptr, 1, hs_mod_slabs(n) * k * m, 1);
-  MOD_NULL(dP && dY && dT && dPart);
+static void mod_inner_hook(int64_t n, int64_t k, int64_t m, const T* P, int64_t ldp, const T* Y, int64_t ldy, int conj, T* Tm, int64_t ldt) {
+  if (n < 1 || k < 1 || k > HS_MOD_MAXRANK || m < 1 || m > HS_MOD_MAXCOLS || ldp < n || ldy < n || ldt < k || !P || !Y || !Tm)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_mod_inner: n >= 1, k in 1..256, m in 1..64, leading dimensions and non-null arrays required");
+  need_device();
+  HsDevBuf b("hsk_mod_inner");
+  T* dP = put_block<T>(b, P, ldp, n, k);
+  T* dY = put_block<T>(b, Y, ldy, n, m);
+  T* dT = put_block<T>(b, nullptr, k, k, m);
+  T* dPart = put_block<T>(b, nullptr, 1, hs_mod_slabs(n) * k * m, 1);
   launch_mod_inner<T>(dP, n, dY, n, n, (int)k, (int)m, conj, dPart, dT, k, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy2D(Tm, ldt * sizeof(T), dT, k * sizeof(T), k * sizeof(T), m, hipMemcpyDeviceToHost));
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  bring_block(Tm, ldt, dT, k, k, m);
 }
 extern "C" int hsk_mod_inner_d(int64_t n, int64_t k, int64_t m, const double* P, int64_t ldp, const double* Y, int64_t ldy, int conj, double* T, int64_t ldt) {
-  return mod_inner_hook<double>(n, k, m, P, ldp, Y, ldy, conj, T, ldt);
+  HS_GUARD(mod_inner_hook<double>(n, k, m, P, ldp, Y, ldy, conj, T, ldt));
 }
 extern "C" int hsk_mod_inner_z(int64_t n, int64_t k, int64_t m, const double* P, int64_t ldp, const double* Y, int64_t ldy, int conj, double* T, int64_t ldt) {
-  return mod_inner_hook<cplx>(n, k, m, (const cplx*)P, ldp, (const cplx*)Y, ldy, conj, (cplx*)T, ldt);
+  HS_GUARD(mod_inner_hook<cplx>(n, k, m, (const cplx*)P, ldp, (const cplx*)Y, ldy, conj, (cplx*)T, ldt));
 }
 
 template <class T>
-static int mod_apply_hook(int64_t n, int64_t k, int64_t m, T* Y, int64_t ldy, const T* Z, int64_t ldz, const T* Tm, int64_t ldt, int conj) {
-  if (n < 1 || k < 1 || k > HS_MOD_MAXRANK || m < 1 || m > HS_MOD_MAXCOLS || ldy < n || ldz < n || ldt < k || !Y || !Z || !Tm) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_mod_apply: n >= 1, k in 1..256, m in 1..64, leading dimensions and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  if (int st = mod_hook_device()) return st;
-  ModBufs b;
-  T* dY = b.up<T>(Y, ldy, n, m);
-  T* dZ = b.up<T>(Z, ldz, n, k);
-  T* dT = b.up<T>(Tm, ldt, k, m);
-  MOD_NULL(dY && dZ && dT);
+static void mod_apply_hook(int64_t n, int64_t k, int64_t m, T* Y, int64_t ldy, const T* Z, int64_t ldz, const T* Tm, int64_t ldt, int conj) {
+  if (n < 1 || k < 1 || k > HS_MOD_MAXRANK || m < 1 || m > HS_MOD_MAXCOLS || ldy < n || ldz < n || ldt < k || !Y || !Z || !Tm)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_mod_apply: n >= 1, k in 1..256, m in 1..64, leading dimensions and non-null arrays required");
+  need_device();
+  HsDevBuf b("hsk_mod_apply");
+  T* dY = put_block<T>(b, Y, ldy, n, m);
+  T* dZ = put_block<T>(b, Z, ldz, n, k);
+  T* dT = put_block<T>(b, Tm, ldt, k, m);
   launch_mod_apply<T>(dY, n, dZ, n, dT, k, n, (int)k, (int)m, conj, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy2D(Y, ldy * sizeof(T), dY, n * sizeof(T), n * sizeof(T), m, hipMemcpyDeviceToHost));
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  bring_block(Y, ldy, dY, n, n, m);
 }
 extern "C" int hsk_mod_apply_d(int64_t n, int64_t k, int64_t m, double* Y, int64_t ldy, const double* Z, int64_t ldz, const double* T, int64_t ldt, int conj) {
-  return mod_apply_hook<double>(n, k, m, Y, ldy, Z, ldz, T, ldt, conj);
+  HS_GUARD(mod_apply_hook<double>(n, k, m, Y, ldy, Z, ldz, T, ldt, conj));
 }
 extern "C" int hsk_mod_apply_z(int64_t n, int64_t k, int64_t m, double* Y, int64_t ldy, const double* Z, int64_t ldz, const double* T, int64_t ldt, int conj) {
-  return mod_apply_hook<cplx>(n, k, m, (cplx*)Y, ldy, (const cplx*)Z, ldz, (const cplx*)T, ldt, conj);
+  HS_GUARD(mod_apply_hook<cplx>(n, k, m, (cplx*)Y, ldy, (const cplx*)Z, ldz, (const cplx*)T, ldt, conj));
 }
 
 template <class T>
-static int mod_gather_hook(int64_t n, int64_t k, int64_t m, const T* Y, int64_t ldy, const int64_t* J, T* Tm, int64_t ldt) {
-  if (n < 1 || k < 1 || m < 1 || ldy < n || ldt < k || !Y || !J || !Tm) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_mod_gather: n, k, m >= 1, leading dimensions and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
+static void mod_gather_hook(int64_t n, int64_t k, int64_t m, const T* Y, int64_t ldy, const int64_t* J, T* Tm, int64_t ldt) {
+  if (n < 1 || k < 1 || m < 1 || ldy < n || ldt < k || !Y || !J || !Tm)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_mod_gather: n, k, m >= 1, leading dimensions and non-null arrays required");
   for (int64_t j = 0; j < k; ++j)
-    if (J[j] < 0 || J[j] >= n) {
-      hs_set_error(HS_ERR_DIMENSION, j, "hsk_mod_gather: J[%lld] = %lld outside 0:%lld", (long long)j, (long long)J[j], (long long)n - 1);
-      return HS_ERR_DIMENSION;
-    }
-  if (int st = mod_hook_device()) return st;
-  ModBufs b;
-  T* dY = b.up<T>(Y, ldy, n, m);
-  int64_t* dJ = b.up<int64_t>(J, k, k, 1);
-  T* dT = b.up<T>(nullptr, k, k, m);
-  MOD_NULL(dY && dJ && dT);
+    if (J[j] < 0 || J[j] >= n) HS_FAIL(HS_ERR_DIMENSION, j, "hsk_mod_gather: J[%lld] = %lld outside 0:%lld", (long long)j, (long long)J[j], (long long)n - 1);
+  need_device();
+  HsDevBuf b("hsk_mod_gather");
+  T* dY = put_block<T>(b, Y, ldy, n, m);
+  int64_t* dJ = put_block<int64_t>(b, J, k, k, 1);
+  T* dT = put_block<T>(b, nullptr, k, k, m);
   launch_mod_gather<T>(dT, k, dY, n, dJ, (int)k, (int)m, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy2D(Tm, ldt * sizeof(T), dT, k * sizeof(T), k * sizeof(T), m, hipMemcpyDeviceToHost));
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  bring_block(Tm, ldt, dT, k, k, m);
 }
 extern "C" int hsk_mod_gather_d(int64_t n, int64_t k, int64_t m, const double* Y, int64_t ldy, const int64_t* J, double* T, int64_t ldt) {
-  return mod_gather_hook<double>(n, k, m, Y, ldy, J, T, ldt);
+  HS_GUARD(mod_gather_hook<double>(n, k, m, Y, ldy, J, T, ldt));
 }
 extern "C" int hsk_mod_gather_z(int64_t n, int64_t k, int64_t m, const double* Y, int64_t ldy, const int64_t* J, double* T, int64_t ldt) {
-  return mod_gather_hook<cplx>(n, k, m, (const cplx*)Y, ldy, J, (cplx*)T, ldt);
+  HS_GUARD(mod_gather_hook<cplx>(n, k, m, (const cplx*)Y, ldy, J, (cplx*)T, ldt));
 }
 
 template <class T>
-static int mod_cap_hook(int64_t k, int64_t m, const T* C, int64_t ldc, int op, T* Tm, int64_t ldt) {
-  if (k < 1 || k > HS_MOD_MAXRANK || m < 1 || ldc < k || ldt < k || op < 0 || op > 2 || !C || !Tm) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_mod_cap: k in 1..256, m >= 1, op in 0..2, leading dimensions and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  if (int st = mod_hook_device()) return st;
-  ModBufs b;
-  T* dC = b.up<T>(C, ldc, k, k);
-  T* dT = b.up<T>(Tm, ldt, k, m);
-  int* dPiv = b.up<int>(nullptr, k + 1, k + 1, 1);
-  MOD_NULL(dC && dT && dPiv);
+static void mod_cap_hook(int64_t k, int64_t m, const T* C, int64_t ldc, int op, T* Tm, int64_t ldt) {
+  if (k < 1 || k > HS_MOD_MAXRANK || m < 1 || ldc < k || ldt < k || op < 0 || op > 2 || !C || !Tm)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_mod_cap: k in 1..256, m >= 1, op in 0..2, leading dimensions and non-null arrays required");
+  need_device();
+  HsDevBuf b("hsk_mod_cap");
+  T* dC = put_block<T>(b, C, ldc, k, k);
+  T* dT = put_block<T>(b, Tm, ldt, k, m);
+  int* dPiv = put_block<int>(b, nullptr, k + 1, k + 1, 1);
   launch_mod_cap_lu<T>(dC, (int)k, (int)k, dPiv, dPiv + k, 0);
   int info = 0;
-  CK(hipMemcpy(&info, dPiv + k, sizeof(int), hipMemcpyDeviceToHost));
-  if (info != 0) {
-    hs_set_error(HS_ERR_SINGULAR, info, "SingularException(%d): hsk_mod_cap: zero pivot", info);
-    return HS_ERR_SINGULAR;
-  }
+  HS_HIP(hipMemcpy(&info, dPiv + k, sizeof(int), hipMemcpyDeviceToHost));
+  if (info != 0) HS_FAIL(HS_ERR_SINGULAR, info, "SingularException(%d): hsk_mod_cap: zero pivot", info);
   launch_mod_cap_solve<T>(dC, (int)k, (int)k, dPiv, op, dT, k, (int)m, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy2D(Tm, ldt * sizeof(T), dT, k * sizeof(T), k * sizeof(T), m, hipMemcpyDeviceToHost));
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  bring_block(Tm, ldt, dT, k, k, m);
 }
-extern "C" int hsk_mod_cap_d(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt) { return mod_cap_hook<double>(k, m, C, ldc, op, T, ldt); }
+extern "C" int hsk_mod_cap_d(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt) {
+  HS_GUARD(mod_cap_hook<double>(k, m, C, ldc, op, T, ldt));
+}
 extern "C" int hsk_mod_cap_z(int64_t k, int64_t m, const double* C, int64_t ldc, int op, double* T, int64_t ldt) {
-  return mod_cap_hook<cplx>(k, m, (const cplx*)C, ldc, op, (cplx*)T, ldt);
+  HS_GUARD(mod_cap_hook<cplx>(k, m, (const cplx*)C, ldc, op, (cplx*)T, ldt));
 }
 
 // ---- the pieces of hs_eigs_* (kernels_eigs.hip, hs_small_eig.h) on host data (tests/test_eigs_gpu.py, tests/test_eigs_host.py) ---------------
@@ -1282,108 +1050,87 @@ extern "C" int hsk_mod_cap_z(int64_t k, int64_t m, const double* C, int64_t ldc,
 #include "hs_small_eig.h"
 
 template <class T>
-static int eigs_rotate_hook(int64_t n, int64_t K, int64_t N, const T* V, int64_t ldv, const T* Q, int64_t ldq, int inplace, T* Out, int64_t ldo) {
-  if (n < 1 || K < 1 || K > HS_EIGS_MAXBASIS || N < 1 || N > K || ldv < n || ldq < K || ldo < n || !V || !Q || !Out) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_eigs_rotate: n >= 1, K in 1..256, N in 1..K, leading dimensions and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  if (int st = mod_hook_device()) return st;
-  ModBufs b;
-  T* dV = b.up<T>(V, ldv, n, K);
-  T* dQ = b.up<T>(Q, ldq, K, N);
-  T* dO = inplace ? dV : b.up<T>(nullptr, n, n, N);
-  MOD_NULL(dV && dQ && dO);
+static void eigs_rotate_hook(int64_t n, int64_t K, int64_t N, const T* V, int64_t ldv, const T* Q, int64_t ldq, int inplace, T* Out, int64_t ldo) {
+  if (n < 1 || K < 1 || K > HS_EIGS_MAXBASIS || N < 1 || N > K || ldv < n || ldq < K || ldo < n || !V || !Q || !Out)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_eigs_rotate: n >= 1, K in 1..256, N in 1..K, leading dimensions and non-null arrays required");
+  need_device();
+  HsDevBuf b("hsk_eigs_rotate");
+  T* dV = put_block<T>(b, V, ldv, n, K);
+  T* dQ = put_block<T>(b, Q, ldq, K, N);
+  T* dO = inplace ? dV : put_block<T>(b, nullptr, n, n, N);
   launch_eigs_rotate<T>(dO, n, dV, n, dQ, K, n, (int)K, (int)N, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy2D(Out, ldo * sizeof(T), dO, n * sizeof(T), n * sizeof(T), N, hipMemcpyDeviceToHost));
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  bring_block(Out, ldo, dO, n, n, N);
 }
 extern "C" int hsk_eigs_rotate_d(int64_t n, int64_t K, int64_t N, const double* V, int64_t ldv, const double* Q, int64_t ldq, int inplace, double* Out, int64_t ldo) {
-  return eigs_rotate_hook<double>(n, K, N, V, ldv, Q, ldq, inplace, Out, ldo);
+  HS_GUARD(eigs_rotate_hook<double>(n, K, N, V, ldv, Q, ldq, inplace, Out, ldo));
 }
 extern "C" int hsk_eigs_rotate_z(int64_t n, int64_t K, int64_t N, const double* V, int64_t ldv, const double* Q, int64_t ldq, int inplace, double* Out, int64_t ldo) {
-  return eigs_rotate_hook<cplx>(n, K, N, (const cplx*)V, ldv, (const cplx*)Q, ldq, inplace, (cplx*)Out, ldo);
+  HS_GUARD(eigs_rotate_hook<cplx>(n, K, N, (const cplx*)V, ldv, (const cplx*)Q, ldq, inplace, (cplx*)Out, ldo));
 }
 
 template <class T>
-static int eigs_chol_inv_hook(int64_t p, const T* G, int64_t ldg, T* R, T* Rinv, int* info) {
-  if (p < 1 || p > HS_EIGS_MAXBLOCK || ldg < p || !G || !R || !Rinv || !info) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_eigs_chol_inv: p in 1..64, ldg >= p and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  if (int st = mod_hook_device()) return st;
-  ModBufs b;
-  T* dG = b.up<T>(G, ldg, p, p);
-  T* dR = b.up<T>(nullptr, p, p, p);
-  T* dRi = b.up<T>(nullptr, p, p, p);
-  int* dInfo = b.up<int>(nullptr, 1, 1, 1);
-  MOD_NULL(dG && dR && dRi && dInfo);
+static void eigs_chol_inv_hook(int64_t p, const T* G, int64_t ldg, T* R, T* Rinv, int* info) {
+  if (p < 1 || p > HS_EIGS_MAXBLOCK || ldg < p || !G || !R || !Rinv || !info)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_eigs_chol_inv: p in 1..64, ldg >= p and non-null arrays required");
+  need_device();
+  HsDevBuf b("hsk_eigs_chol_inv");
+  T* dG = put_block<T>(b, G, ldg, p, p);
+  T* dR = put_block<T>(b, nullptr, p, p, p);
+  T* dRi = put_block<T>(b, nullptr, p, p, p);
+  int* dInfo = put_block<int>(b, nullptr, 1, 1, 1);
   launch_eigs_chol_inv<T>(dG, (int)p, (int)p, dR, dRi, dInfo, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy(info, dInfo, sizeof(int), hipMemcpyDeviceToHost));
-  CK(hipMemcpy(R, dR, sizeof(T) * (size_t)(p * p), hipMemcpyDeviceToHost));
-  CK(hipMemcpy(Rinv, dRi, sizeof(T) * (size_t)(p * p), hipMemcpyDeviceToHost));
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(info, dInfo, sizeof(int), hipMemcpyDeviceToHost));
+  HS_HIP(hipMemcpy(R, dR, sizeof(T) * (size_t)(p * p), hipMemcpyDeviceToHost));
+  HS_HIP(hipMemcpy(Rinv, dRi, sizeof(T) * (size_t)(p * p), hipMemcpyDeviceToHost));
 }
-extern "C" int hsk_eigs_chol_inv_d(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info) { return eigs_chol_inv_hook<double>(p, G, ldg, R, Rinv, info); }
+extern "C" int hsk_eigs_chol_inv_d(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info) {
+  HS_GUARD(eigs_chol_inv_hook<double>(p, G, ldg, R, Rinv, info));
+}
 extern "C" int hsk_eigs_chol_inv_z(int64_t p, const double* G, int64_t ldg, double* R, double* Rinv, int* info) {
-  return eigs_chol_inv_hook<cplx>(p, (const cplx*)G, ldg, (cplx*)R, (cplx*)Rinv, info);
+  HS_GUARD(eigs_chol_inv_hook<cplx>(p, (const cplx*)G, ldg, (cplx*)R, (cplx*)Rinv, info));
 }
 
 template <class T>
-static int eigs_coldot_hook(int64_t n, int64_t nc, const T* X, int64_t ldx, const T* Y, int64_t ldy, const int* pair, double* d) {
+static void eigs_coldot_hook(int64_t n, int64_t nc, const T* X, int64_t ldx, const T* Y, int64_t ldy, const int* pair, double* d) {
   bool ok = n >= 1 && nc >= 1 && nc <= HS_EIGS_MAXBASIS && ldx >= n && ldy >= n && X && Y && d;
   for (int64_t c = 0; ok && pair && c < nc; ++c)  // a pair is two adjacent columns of a Float64 block
     ok = pair[c] == 0 || (sizeof(T) == 8 && ((pair[c] == 1 && c + 1 < nc && pair[c + 1] == -1) || (pair[c] == -1 && c > 0 && pair[c - 1] == 1)));
-  if (!ok) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_eigs_coldot: n >= 1, nc in 1..256, leading dimensions >= n, non-null arrays and whole Float64 pairs required");
-    return HS_ERR_ARGUMENT;
-  }
-  if (int st = mod_hook_device()) return st;
-  ModBufs b;
-  T* dX = b.up<T>(X, ldx, n, nc);
-  T* dY = b.up<T>(Y, ldy, n, nc);
-  int* dPair = pair ? b.up<int>(pair, nc, nc, 1) : nullptr;
-  double* dPart = b.up<double>(nullptr, 1, hs_eigs_slabs(n) * nc, 1);
-  double* dD = b.up<double>(nullptr, nc, nc, 1);
-  MOD_NULL(dX && dY && (dPair || !pair) && dPart && dD);
+  if (!ok) HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_eigs_coldot: n >= 1, nc in 1..256, leading dimensions >= n, non-null arrays and whole Float64 pairs required");
+  need_device();
+  HsDevBuf b("hsk_eigs_coldot");
+  T* dX = put_block<T>(b, X, ldx, n, nc);
+  T* dY = put_block<T>(b, Y, ldy, n, nc);
+  int* dPair = pair ? put_block<int>(b, pair, nc, nc, 1) : nullptr;
+  double* dPart = put_block<double>(b, nullptr, 1, hs_eigs_slabs(n) * nc, 1);
+  double* dD = put_block<double>(b, nullptr, nc, nc, 1);
   launch_eigs_coldot<T>(dX, n, dY, n, dPair, n, (int)nc, dPart, dD, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy(d, dD, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost));
-  return HS_OK;
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(d, dD, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost));
 }
 extern "C" int hsk_eigs_coldot_d(int64_t n, int64_t nc, const double* X, int64_t ldx, const double* Y, int64_t ldy, const int* pair, double* d) {
-  return eigs_coldot_hook<double>(n, nc, X, ldx, Y, ldy, pair, d);
+  HS_GUARD(eigs_coldot_hook<double>(n, nc, X, ldx, Y, ldy, pair, d));
 }
 extern "C" int hsk_eigs_coldot_z(int64_t n, int64_t nc, const double* X, int64_t ldx, const double* Y, int64_t ldy, const int* pair, double* d) {
-  return eigs_coldot_hook<cplx>(n, nc, (const cplx*)X, ldx, (const cplx*)Y, ldy, pair, d);
+  HS_GUARD(eigs_coldot_hook<cplx>(n, nc, (const cplx*)X, ldx, (const cplx*)Y, ldy, pair, d));
 }
 
-extern "C" int hsk_small_eig_z(int64_t m, const double* H, int64_t ldh, double* w, double* Y, int64_t ldy) {
-  if (m < 1 || m > HS_EIGS_MAXBASIS || ldh < m || ldy < m || !H || !w || !Y) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_small_eig_z: m in 1..256, leading dimensions >= m and non-null arrays required");
-    return HS_ERR_ARGUMENT;
-  }
-  try {
-    std::vector<hs_se::zc> Hc((size_t)(m * m));
-    for (int64_t j = 0; j < m; ++j)
-      for (int64_t i = 0; i < m; ++i) Hc[(size_t)(j * m + i)] = hs_se::zc(H[2 * (j * ldh + i)], H[2 * (j * ldh + i) + 1]);
-    const int bad = hs_se::small_eig((int)m, Hc.data(), (int)m, (hs_se::zc*)w, (hs_se::zc*)Y, (int)ldy);
-    if (bad) {
-      hs_set_error(HS_ERR_SINGULAR, bad - 1, "hsk_small_eig_z: the QR iteration did not isolate eigenvalue %d", bad - 1);
-      return HS_ERR_SINGULAR;
-    }
-  } catch (const std::bad_alloc&) {
-    hs_set_error(HS_ERR_NOMEM, 0, "host allocation failed");
-    return HS_ERR_NOMEM;
-  }
-  return HS_OK;
+static void small_eig_hook(int64_t m, const double* H, int64_t ldh, double* w, double* Y, int64_t ldy) {
+  if (m < 1 || m > HS_EIGS_MAXBASIS || ldh < m || ldy < m || !H || !w || !Y)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_small_eig_z: m in 1..256, leading dimensions >= m and non-null arrays required");
+  std::vector<hs_se::zc> Hc((size_t)(m * m));
+  for (int64_t j = 0; j < m; ++j)
+    for (int64_t i = 0; i < m; ++i) Hc[(size_t)(j * m + i)] = hs_se::zc(H[2 * (j * ldh + i)], H[2 * (j * ldh + i) + 1]);
+  const int bad = hs_se::small_eig((int)m, Hc.data(), (int)m, (hs_se::zc*)w, (hs_se::zc*)Y, (int)ldy);
+  if (bad) HS_FAIL(HS_ERR_SINGULAR, bad - 1, "hsk_small_eig_z: the QR iteration did not isolate eigenvalue %d", bad - 1);
 }
+extern "C" int hsk_small_eig_z(int64_t m, const double* H, int64_t ldh, double* w, double* Y, int64_t ldy) { HS_GUARD(small_eig_hook(m, H, ldh, w, Y, ldy)); }
 
 // ---- hs_interface_matrix_*: the product S = P^T (L U) of a packed LU (kernels_interface.hip) on host data ------------------------------------
 #include "hs_interface.h"
 template <class T>
-static int lu_product_hook(int64_t nb, const T* LF, int64_t ldl, const int32_t* rperm, T* S, int64_t lds, double* flops_out) {
+static void lu_product_hook(int64_t nb, const T* LF, int64_t ldl, const int32_t* rperm, T* S, int64_t lds, double* flops_out) {
   bool ok = nb >= 1 && nb <= (1 << 20) && LF && rperm && S && ldl >= nb && lds >= nb;
   if (ok) {
     std::vector<char> seen((size_t)nb, 0);
@@ -1392,36 +1139,24 @@ static int lu_product_hook(int64_t nb, const T* LF, int64_t ldl, const int32_t* 
       if (ok) seen[(size_t)rperm[i]] = 1;
     }
   }
-  if (!ok) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "hsk_lu_product: nb >= 1, non-null arrays, ldl >= nb, lds >= nb and rperm a permutation of 0..nb-1 required");
-    return HS_ERR_ARGUMENT;
-  }
-  int cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) {
-    hs_set_error(HS_ERR_DEVICE, 0, "no HIP device available");
-    return HS_ERR_DEVICE;
-  }
-  T *dL = nullptr, *dS = nullptr;
-  int* dp = nullptr;
+  if (!ok) HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_lu_product: nb >= 1, non-null arrays, ldl >= nb, lds >= nb and rperm a permutation of 0..nb-1 required");
+  need_device();
   const size_t nl = (size_t)ldl * (nb - 1) + nb, ns = (size_t)lds * (nb - 1) + nb;
-  CK(hipMalloc((void**)&dL, sizeof(T) * nl));
-  CK(hipMalloc((void**)&dS, sizeof(T) * ns));
-  CK(hipMalloc((void**)&dp, sizeof(int) * (size_t)nb));
-  CK(hipMemcpy(dL, LF, sizeof(T) * nl, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dS, S, sizeof(T) * ns, hipMemcpyHostToDevice));
-  CK(hipMemcpy(dp, rperm, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
+  HsDevBuf b("hsk_lu_product");
+  T* dL = b.get<T>(nl);
+  T* dS = b.get<T>(ns);
+  int* dp = b.get<int>((size_t)nb);
+  HS_HIP(hipMemcpy(dL, LF, sizeof(T) * nl, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dS, S, sizeof(T) * ns, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dp, rperm, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
   const double fl = launch_lu_product<T>((int)nb, dL, ldl, dp, dS, lds, 0);
-  CK(hipDeviceSynchronize());
-  CK(hipMemcpy(S, dS, sizeof(T) * ns, hipMemcpyDeviceToHost));
-  (void)hipFree(dL);
-  (void)hipFree(dS);
-  (void)hipFree(dp);
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(S, dS, sizeof(T) * ns, hipMemcpyDeviceToHost));
   if (flops_out) *flops_out = fl;
-  return HS_OK;
 }
 extern "C" int hsk_lu_product_d(int64_t nb, const double* LF, int64_t ldl, const int32_t* rperm, double* S, int64_t lds, double* flops_out) {
-  return lu_product_hook<double>(nb, LF, ldl, rperm, S, lds, flops_out);
+  HS_GUARD(lu_product_hook<double>(nb, LF, ldl, rperm, S, lds, flops_out));
 }
 extern "C" int hsk_lu_product_z(int64_t nb, const double* LF, int64_t ldl, const int32_t* rperm, double* S, int64_t lds, double* flops_out) {
-  return lu_product_hook<cplx>(nb, (const cplx*)LF, ldl, (const int32_t*)rperm, (cplx*)S, lds, flops_out);
+  HS_GUARD(lu_product_hook<cplx>(nb, (const cplx*)LF, ldl, (const int32_t*)rperm, (cplx*)S, lds, flops_out));
 }

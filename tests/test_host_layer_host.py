@@ -30,6 +30,24 @@ def test_comm_refusal_travels_as_code_and_message(hs):
     assert _last(L) == ("ArgumentError: null argument", 0)
 
 
+def test_testhook_refusal_travels_as_code_and_message(hs):
+    L, lib = hs._lib.lib(), hs._lib
+    a = (C.c_double * 4)()
+    st = L.hsk_mod_inner_d(2, 0, 1, a, 2, a, 2, 0, a, 1)  # k = 0
+    assert st == lib.HS_ERR_ARGUMENT
+    assert _last(L) == ("hsk_mod_inner: n >= 1, k in 1..256, m in 1..64, leading dimensions and non-null arrays required", 0)
+
+
+def test_gmres_block_refusal_travels_as_code_and_message(hs):
+    L, lib = hs._lib.lib(), hs._lib
+    colptr, rowval = (C.c_int64 * 2)(1, 2), (C.c_int64 * 1)(1)
+    nz, b, x = (C.c_double * 1)(1.0), (C.c_double * 1)(1.0), (C.c_double * 1)()
+    iters, conv = (C.c_int64 * 1)(), (C.c_int * 1)()
+    st = L.hs_gmres_block_d(None, 1, colptr, rowval, nz, b, 1, x, 1, 1, 2, 0, 1e-9, 0.0, 0, -1, None, iters, conv, None)  # where = 2
+    assert st == lib.HS_ERR_ARGUMENT
+    assert _last(L) == ("ArgumentError: hs_gmres_block: where = 2 (0: host pointers, 1: device pointers)", 2)
+
+
 def test_hss_refusal_travels_as_code_and_message(hs):
     L, lib = hs._lib.lib(), hs._lib
     out = C.c_void_p(1)
