@@ -112,6 +112,7 @@ EXPORTS = [
     "hsk_leaf_envelope", "hsk_envelope_enable", "hsk_op_flops_mode", "hsk_op_flops",
     "hsk_gemm_op_d", "hsk_gemm_lds_enable", "hsk_gemm_lds_launches",
     "hsk_gemm_lds_edge_launches", "hsk_gemm_reg_launches", "hsk_gemm_lds_route", "hsk_gemm_schur_d",
+    "hsk_trsm_inv_d", "hsk_trsm_strip_enable", "hsk_trsm_strip_launches", "hsk_trsm_half_launches",
 ]
 
 _lib = None
@@ -465,6 +466,13 @@ def lib():
     L.hsk_gemm_lds_route.restype = C.c_int
     L.hsk_gemm_schur_d.argtypes = [i64, p_i64, p_i64, p_f64, p_f64, p_f64, C.c_int, p_i64, p_i64, C.c_int, p_f64]
     L.hsk_gemm_schur_d.restype = C.c_int
+    L.hsk_trsm_inv_d.argtypes = [i64, p_i64, p_i64, i64, i64, i64, i64, i64, p_f64, p_f64, C.c_int, p_i64]
+    L.hsk_trsm_inv_d.restype = C.c_int
+    L.hsk_trsm_strip_enable.argtypes = [C.c_int]
+    L.hsk_trsm_strip_enable.restype = C.c_int
+    for f in (L.hsk_trsm_strip_launches, L.hsk_trsm_half_launches):
+        f.argtypes = [C.c_int]
+        f.restype = C.c_longlong
     for f in (L.hsk_front_factor_d, L.hsk_front_factor_z):
         f.argtypes = [i64, i64, i64, p_f64, p_f64, p_f64, p_f64, p_i64, p_i64, p_f64]
         f.restype = C.c_int

@@ -227,6 +227,12 @@ inline int hs_gemm_lds_route_join(int a, int b) {
   if (a == HS_GEMM_ROUTE_REG || b == HS_GEMM_ROUTE_REG) return HS_GEMM_ROUTE_REG;
   return (a == HS_GEMM_ROUTE_EDGE || b == HS_GEMM_ROUTE_EDGE) ? HS_GEMM_ROUTE_EDGE : HS_GEMM_ROUTE_LDS;
 }
+// The 256-row TRSM base case X[r0 : r0 + 256, c0 : c1) <- inv256L[r0 / 256] * X of a batch in ONE launch (kernels_trsm.hip; Float64, lower):
+// op as for GemmOp::ainv 3 (cmat, r0, c0, c1, env); every stored value has the bits the two half products (ainv 3 then 4) give it.
+// Operands of any alignment and leading dimension.  hs_trsm_strip_enabled: HS_TRSM_STRIP (default on) / hsk_trsm_strip_enable.
+bool hs_trsm_strip_enabled();
+void hs_trsm_half_note();  // one Float64 lower half product (ainv 3 or 4) was launched instead (hsk_trsm_half_launches)
+void launch_trsm_strip(const NodeDesc<double>* dnodes, int nbatch, int maxN, const GemmOp& op, hipStream_t s);
 bool hs_envelope_enabled();  // HS_LEAF_ENVELOPE (default on) / hsk_envelope_enable: leaf fronts are eliminated inside their block envelope
 template <class T>
 void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN, int accumulate_minus, hipStream_t s);

@@ -23,6 +23,8 @@ struct Profiler {
     int cat;
     double fl;
     int M, N, K, nbatch, tag;
+    int form, side;  // in-place TRSM products: GemmOp::ainv of the launch (9: the strip kernel, both halves at once) and 1 on the look-ahead side stream
+    double bytes;    // the bytes the launch must move at least (X read once, the stored rows written once)
   };
   int tag = 0;                          // set by the caller (tree level): per-level sums for HS_VERBOSE_LEVELS
   double ms_tag[64][HS_NCAT] = {};
@@ -39,18 +41,23 @@ struct Profiler {
     }
     return e;
   }
-  void end(hipEvent_t e0, int cat, hipStream_t s, double fl = 0.0, int M = 0, int N = 0, int K = 0, int nbatch = 0) {
+  void end(hipEvent_t e0, int cat, hipStream_t s, double fl = 0.0, int M = 0, int N = 0, int K = 0, int nbatch = 0, int form = 0, int side = 0,
+           double bytes = 0.0) {
     launches[cat]++;
     flops[cat] += fl;
     if (!on) return;
     hipEvent_t e1;
     (void)hipEventCreate(&e1);
     (void)hipEventRecord(e1, s);
-    recs.push_back({e0, e1, cat, fl, M, N, K, nbatch, tag});
+    recs.push_back({e0, e1, cat, fl, M, N, K, nbatch, tag, form, side, bytes});
   }
   void collect() {  // call after the stream has been synchronised
     const char* logf = getenv("HS_GEMM_LOG");  // diagnostics: one line per GEMM launch (max M, N, K of the batch, flops, ms)
     FILE* lf = (logf && on) ? fopen(logf, "a") : nullptr;
+    // HS_LAUNCH_LOG: one line per profiled launch of EVERY category -- tree level, category, form and stream of the in-place products, fronts,
+    // least bytes, ms (tools/trsm_forms.py adds them up per level, form and stream)
+    const char* logl = getenv("HS_LAUNCH_LOG");
+    FILE* ll = (logl && on) ? fopen(logl, "a") : nullptr;
     for (auto& r : recs) {
       float t = 0.f;
       if (hipEventElapsedTime(&t, r.e0, r.e1) == hipSuccess) {
@@ -58,10 +65,12 @@ struct Profiler {
         if (r.tag >= 0 && r.tag < 64) ms_tag[r.tag][r.cat] += t;
       }
       if (lf && r.cat == HS_CAT_GEMM) fprintf(lf, "%d %d %d %d %.6g %.6f\n", r.M, r.N, r.K, r.nbatch, r.fl, t);
+      if (ll) fprintf(ll, "%d %d %d %d %d %.6g %.6f\n", r.tag, r.cat, r.form, r.side, r.nbatch, r.bytes, t);
       (void)hipEventDestroy(r.e0);
       (void)hipEventDestroy(r.e1);
     }
     if (lf) fclose(lf);
+    if (ll) fclose(ll);
     recs.clear();
   }
 };
@@ -169,7 +178,7 @@ struct Sched {
     }
     hipEvent_t e0 = pf->begin(s);
     launch_gemm_op<T>(dn, nbatch, M, N, op, s, route, shifted);
-    pf->end(e0, HS_CAT_GEMM, s, fl, M, N, K, nbatch);
+    pf->end(e0, HS_CAT_GEMM, s, fl, M, N, K, nbatch, 0, hiprio);
     dbg("gemm", cmat, r0, c0, k0);
   }
   void panel(int pb, int fuse = 0) {
@@ -205,25 +214,59 @@ struct Sched {
     dbg("panel_pivot", pb);
     launch_panel_l21<T>(dn, nbatch, pb, std::min(maxm, rlim) - c0, fuse, s, rlim);
     dbg("panel_l21", pb);
-    pf->end(e0, HS_CAT_PANEL, s);
+    pf->end(e0, HS_CAT_PANEL, s, 0.0, 0, 0, 0, nbatch, 0, hiprio);
   }
   void laswp(int mat, int c0, int c1, int k0, int k1) {
     int nc = std::min(c1, cols_of(mat)) - c0;
     if (nc <= 0 || k0 >= maxni) return;
     hipEvent_t e0 = pf->begin(s);
     launch_laswp<T>(dn, nbatch, mat, c0, c1, k0, k1, nc, s);
-    pf->end(e0, HS_CAT_LASWP, s);
+    pf->end(e0, HS_CAT_LASWP, s, 0.0, 0, 0, 0, nbatch, 0, hiprio);
     dbg("laswp", mat, c0, k0, k1);
   }
+  // The bytes an in-place product must move at least, over the fronts of the batch (profiled runs only: the HS_LAUNCH_LOG line of the launch).
+  // The inverse block covers [blk0, blk0 + blkw) of the interior, clipped to ni; of that extent the launch reads [0, rd_hi) and writes
+  // [wr_lo, wr_hi), once per position of the free direction [f0, f1): the columns of `mat` (X <- inv * X), or with `below` the rows of LF
+  // (L_below <- A_below * inv).  The inverse itself (L2-resident, shared by the workgroups of a front) is not counted.
+  double trsm_bytes(int mat, bool below, int blk0, int blkw, int f0, int f1, int rd_hi, int wr_lo, int wr_hi) const {
+    if (!pf->on || !h_ni) return 0.0;
+    double b = 0.0;
+    for (int i = 0; i < nbatch; ++i) {
+      const int ni = h_ni[i], nb = h_nb[i];
+      const int w = std::min(blkw, ni - blk0);
+      const int ext = std::min(f1, below ? ni + nb : (mat == HS_MAT_LF ? ni : nb)) - f0;
+      if (w <= 0 || ext <= 0) continue;
+      b += (double)ext * (std::min(rd_hi, w) + std::max(0, std::min(wr_hi, w) - wr_lo)) * sizeof(T);
+    }
+    return b;
+  }
   // X[r0:r1, c0:c1) <- L[r0:r1, r0:r1]^-1 X
-  // 256-row base case: multiply by the stored inverse of the 256x256 diagonal block, two in-place half products
+  // 256-row base case: multiply by the stored inverse of the 256x256 diagonal block, in place.  Float64, lower: ONE launch of the strip kernel
+  // (kernels_trsm.hip: a workgroup owns 32 columns, reads its 256 x 32 piece of X once and forms both halves from it), while HS_TRSM_STRIP /
+  // hsk_trsm_strip_enable leave it on; otherwise two in-place half products on the GEMM tile (GemmOp::ainv 3 then 4, upper 5 then 6).
   void trsm256(int mat, int r0, int c0, int c1, int nc, bool upper) {
+    if constexpr (sizeof(T) == 8) {
+      if (!upper && hs_trsm_strip_enabled()) {
+        GemmOp op{mat, mat, r0, r0 + 256, c0, c1, 0, 0, 3, 0, 0, env ? 1 : 0};
+        hipEvent_t e0 = pf->begin(s);
+        launch_trsm_strip(reinterpret_cast<const NodeDesc<double>*>(dn), nbatch, nc, op, s);
+        pf->end(e0, HS_CAT_TRSM, s, 0.0, 0, 0, 0, nbatch, 9, hiprio, trsm_bytes(mat, false, r0, 256, c0, c1, 256, 0, 256));
+        dbg("trsm_strip", mat, r0, c0, c1);
+        return;
+      }
+    }
     const int first = upper ? 5 : 3, second = upper ? 6 : 4;
     for (int code : {first, second}) {
       GemmOp op{mat, mat, r0, r0 + 256, c0, c1, 0, 0, code, 0, 0, env ? 1 : 0};
       hipEvent_t e0 = pf->begin(s);
       launch_gemm_op<T>(dn, nbatch, 128, nc, op, s);
-      pf->end(e0, HS_CAT_TRSM, s);
+      if (sizeof(T) == 8 && !upper) hs_trsm_half_note();
+      // (3: all rows read, rows 128.. written; 4: rows 0..127 read and written; 5: all read, 0..127 written; 6: rows 128.. read and written)
+      const double by = code == 3   ? trsm_bytes(mat, false, r0, 256, c0, c1, 256, 128, 256)
+                        : code == 4 ? trsm_bytes(mat, false, r0, 256, c0, c1, 128, 0, 128)
+                        : code == 5 ? trsm_bytes(mat, false, r0, 256, c0, c1, 256, 0, 128)
+                                    : 2.0 * trsm_bytes(mat, false, r0, 256, c0, c1, 0, 128, 256);
+      pf->end(e0, HS_CAT_TRSM, s, 0.0, 0, 0, 0, nbatch, code, hiprio, by);
       dbg("trsm256", mat, r0, c0, code);
     }
   }
@@ -239,7 +282,7 @@ struct Sched {
       // 64 / 128 rows (the solves inside a 256-column group): one launch instead of the 3 / 7 of the recursion below
       hipEvent_t e0 = pf->begin(s);
       if (launch_trsm_small<T>(dn, nbatch, mat, r0, r1 - r0, c0, c1, nc, s)) {
-        pf->end(e0, HS_CAT_TRSM, s);
+        pf->end(e0, HS_CAT_TRSM, s, 0.0, 0, 0, 0, nbatch, 11, hiprio, trsm_bytes(mat, false, r0, r1 - r0, c0, c1, r1 - r0, 0, r1 - r0));  // (11: trsm_small)
         dbg("trsm_small", mat, r0, c0, c1);
         return;
       }
@@ -250,7 +293,7 @@ struct Sched {
       GemmOp op{mat, mat, r0, r0 + HS_PB, c0, c1, 0, 0, 1, 0, 0, env ? 1 : 0};
       hipEvent_t e0 = pf->begin(s);
       launch_gemm_op<T>(dn, nbatch, HS_PB, nc, op, s);
-      pf->end(e0, HS_CAT_TRSM, s);
+      pf->end(e0, HS_CAT_TRSM, s, 0.0, 0, 0, 0, nbatch, 1, hiprio, trsm_bytes(mat, false, r0, HS_PB, c0, c1, HS_PB, 0, HS_PB));
       dbg("trsm_blk", mat, r0, c0, c1);
       return;
     }
@@ -303,7 +346,7 @@ struct Sched {
     if (c1 - c0 == 256 && diag_first()) {
       hipEvent_t eg = pf->begin(s);
       if (launch_group256<T>(dn, nbatch, c0 / 256, s)) {  // the whole chain of the diagonal block in one launch (kernels_panel.hip)
-        pf->end(eg, HS_CAT_PANEL, s);
+        pf->end(eg, HS_CAT_PANEL, s, 0.0, 0, 0, 0, nbatch, 0, hiprio);
         dbg("group256", c0);
       } else {
         if (eg) (void)hipEventDestroy(eg);
@@ -319,7 +362,9 @@ struct Sched {
             GemmOp op{HS_MAT_LF, HS_MAT_LF, r0, HS_BIG, c0, c1, c0, c1, code, 0, hiprio, env ? 1 : 0};
             hipEvent_t e0 = pf->begin(s);
             launch_gemm_op<T>(dn, nbatch, maxm - r0, 128, op, s);
-            pf->end(e0, HS_CAT_TRSM, s);
+            // (7: all columns of the group read, columns 128.. written; 8: columns 0..127 read and written)
+            pf->end(e0, HS_CAT_TRSM, s, 0.0, 0, 0, 0, nbatch, code, hiprio,
+                    code == 7 ? trsm_bytes(HS_MAT_LF, true, c0, 256, r0, HS_BIG, 256, 128, 256) : trsm_bytes(HS_MAT_LF, true, c0, 256, r0, HS_BIG, 128, 0, 128));
             dbg("l_below", c0, r0, code);
           }
         } else {

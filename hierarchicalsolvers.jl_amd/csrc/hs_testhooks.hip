@@ -261,6 +261,104 @@ extern "C" int hsk_gemm_schur_d(int64_t count, const int64_t* ni, const int64_t*
   HS_GUARD(gemm_schur_hook(count, ni, nb, A, B, C, env, routed_lds, routed_edge, repeat, ms_out));
 }
 
+// The 256-row TRSM base case of a level, UR[r0 : r0 + wl, c0 : c1) <- inv256L[r0 / 256] * UR, for a batch of `count` fronts with their own
+// ni[f] and nb[f], issued as a factorization issues it: Sched::trsm_rec(HS_MAT_UR, r0, r0 + 256, c0, c1) with the descriptors' inverses
+// valid -- ONE launch of trsm_strip_kernel while the strip kernel is on, the two half products (GemmOp::ainv 3, 4) otherwise.  X holds the
+// whole ni[f] x nb[f] matrix UR of every front (column-major, leading dimension ni[f], front after front; overwritten with what the device
+// holds afterwards, so the caller sees everything outside the block too), inv one 256 x 256 block per front (the one the launch reads).
+// On the device UR has the leading dimension ni[f] + ldpad and starts `shift` doubles past a 16-byte boundary (ldpad making it odd,
+// shift = 1: operands the 16-byte loads meet unaligned).  env != 0: an enveloped launch, every front with the firstU of the zeros X really
+// has.  *strips (may be null): launches that took the strip kernel.
+static void trsm_inv_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int64_t r0, int64_t c0, int64_t c1, int64_t ldpad, int64_t shift,
+                          const double* inv, double* X, int env, int64_t* strips) {
+  typedef double T;
+  if (count <= 0 || count > 65535 || !ni_ || !nb_ || !inv || !X || r0 < 0 || (r0 & 255) || c0 < 0 || c1 <= c0 || ldpad < 0 || shift < 0 || shift > 1)
+    HS_FAIL(HS_ERR_ARGUMENT, count, "hsk_trsm_inv_d: count in [1, 65535], r0 a multiple of 256, 0 <= c0 < c1, ldpad >= 0, shift 0 or 1 and non-null arrays required");
+  for (int64_t f = 0; f < count; ++f)
+    if (ni_[f] <= 0 || nb_[f] <= 0 || ni_[f] + nb_[f] > (1 << 20))
+      HS_FAIL(HS_ERR_ARGUMENT, f, "hsk_trsm_inv_d: front %lld has ni = %lld, nb = %lld", (long long)f, (long long)ni_[f], (long long)nb_[f]);
+  need_device();
+  std::vector<NodeDesc<T>> hn(count);
+  std::vector<SolveNode<T>> hs(count);
+  std::vector<int> h_ni(count), h_nb(count);
+  std::vector<size_t> our(count), oenv(count);
+  size_t nT = 0, nE = 0;
+  int maxni = 0, maxnb = 0, maxm = 0;
+  const size_t nblk = (size_t)(r0 / 256) + 1;
+  for (int64_t f = 0; f < count; ++f) {
+    const int ni = (int)ni_[f], nb = (int)nb_[f];
+    h_ni[f] = ni; h_nb[f] = nb;
+    maxni = std::max(maxni, ni); maxnb = std::max(maxnb, nb); maxm = std::max(maxm, ni + nb);
+    our[f] = nT + (size_t)shift; nT += rup32((size_t)(ni + ldpad) * nb + 2);
+    oenv[f] = nE; nE += 2 * (size_t)hs_env_nblocks(ni, nb);
+  }
+  HsDevBuf buf("hsk_trsm_inv_d");
+  T* dbuf = buf.get<T>(nT);
+  T* dinv = buf.get<T>((size_t)count * nblk * 65536);
+  NodeDesc<T>* dn = buf.get<NodeDesc<T>>((size_t)count);
+  SolveNode<T>* dsn = buf.get<SolveNode<T>>((size_t)count);
+  HS_HIP(hipMemsetD32(dbuf, 0x3F800000, 2 * nT));  // the padding rows and the gaps: finite, non-zero
+  HS_HIP(hipMemsetD32(dinv, 0x3F800000, 2 * (size_t)count * nblk * 65536));
+  std::vector<int> henv(env ? nE : 0);
+  std::vector<const int*> h_envp(count, nullptr);
+  int* denv = env ? buf.get<int>(nE) : nullptr;
+  const T* Xf = X;
+  for (int64_t f = 0; f < count; ++f) {
+    NodeDesc<T>& d = hn[f];
+    memset(&d, 0, sizeof d);
+    memset(&hs[f], 0, sizeof hs[f]);
+    const int ni = h_ni[f], nb = h_nb[f];
+    d.ni = ni; d.nb = nb; d.m = ni + nb;
+    d.ldl = d.m; d.ldu = ni + (int)ldpad; d.lds = nb;
+    d.UR = dbuf + our[f];  // (LF and SB are never addressed)
+    d.inv256L = dinv + (size_t)f * nblk * 65536;
+    d.ni1 = ni; d.nb1 = nb; d.node = (int)f;
+    if (env) {
+      const int nI = (ni + 31) / 32, nb_all = hs_env_nblocks(ni, nb);
+      int* fL = henv.data() + oenv[f];
+      int* fU = fL + nb_all;
+      for (int b = 0; b < nb_all; ++b) fL[b] = fU[b] = b < nI ? 32 * b : HS_ENV_NONE;
+      for (int c = 0; c < nb; ++c)
+        for (int k = 0; k < ni; ++k)
+          if (Xf[(size_t)k + (size_t)c * ni] != 0.0) { int& v = fU[nI + c / 32]; v = std::min(v, k & ~31); break; }
+      d.env = denv + oenv[f];
+      h_envp[f] = fL;
+    }
+    d.finalize();
+    d.mrows[HS_MAT_LF] = d.mcols[HS_MAT_LF] = d.mrows[HS_MAT_SB] = d.mcols[HS_MAT_SB] = 0;
+    HS_HIP(hipMemcpy2D(d.UR, sizeof(T) * d.ldu, Xf, sizeof(T) * ni, sizeof(T) * ni, nb, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(d.inv256L + (nblk - 1) * 65536, inv + (size_t)f * 65536, sizeof(T) * 65536, hipMemcpyHostToDevice));
+    Xf += (size_t)ni * nb;
+  }
+  if (env) HS_HIP(hipMemcpy(denv, henv.data(), sizeof(int) * nE, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice));
+  Profiler prof;
+  Sched<T> sch{dn, (int)count, maxni, maxnb, maxm, (hipStream_t) nullptr, &prof, h_ni.data(), h_nb.data()};
+  sch.sn = dsn;  // (never read by the solve: it only says that the descriptors carry inv256L)
+  sch.wide = true;
+  if (env) {
+    sch.optimistic = true;
+    sch.env = true;
+    sch.h_env = h_envp.data();
+  }
+  const long long before = hsk_trsm_strip_launches(0);
+  sch.trsm_rec(HS_MAT_UR, (int)r0, (int)r0 + 256, (int)c0, (int)std::min<int64_t>(c1, HS_BIG));
+  HS_HIP(hipDeviceSynchronize());
+  if (strips) *strips = (int64_t)(hsk_trsm_strip_launches(0) - before);
+  T* Xo = X;
+  for (int64_t f = 0; f < count; ++f) {
+    const NodeDesc<T>& d = hn[f];
+    bring_block(Xo, d.ni, d.UR, d.ldu, d.ni, d.nb);
+    Xo += (size_t)d.ni * d.nb;
+  }
+  prof.collect();
+}
+extern "C" int hsk_trsm_inv_d(int64_t count, const int64_t* ni, const int64_t* nb, int64_t r0, int64_t c0, int64_t c1, int64_t ldpad, int64_t shift,
+                              const double* inv, double* X, int env, int64_t* strips) {
+  HS_GUARD(trsm_inv_hook(count, ni, nb, r0, c0, c1, ldpad, shift, inv, X, env, strips));
+}
+
 // Factor a batch of `count` dense fronts F[k] ((ni[k]+nb[k])^2, column-major, front order [int;bnd], packed one after another) the way
 // hs_numeric factors a level: one Sched over the batch (batch maxima, per-front sizes on the host, the look-ahead streams).
 //   mode 0: tournament pivoting, no solve descriptors   1: optimistic, no descriptors (32-row TRSM base case, full-height panels)

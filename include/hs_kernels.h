@@ -238,6 +238,24 @@ int hsk_gemm_lds_route(int cmat, int r0, int k0, int k1, int ni);
 int hsk_gemm_schur_d(int64_t count, const int64_t* ni, const int64_t* nb, const double* A, const double* B, double* C, int env,
                      int64_t* routed_lds, int64_t* routed_edge, int repeat, double* ms_out);
 
+/* The 256-row TRSM base case UR[r0 : r0 + wl, c0 : c1) <- inv256L[r0 / 256] * UR (wl = min(256, ni[f] - r0); Float64) of a level through the
+ * launch path of a factorization (Sched::trsm_rec), for `count` fronts with their own ni[f] and nb[f]: one launch of `trsm_strip_kernel`
+ * (kernels_trsm.hip) while the strip kernel is on, the two half products on the GEMM tile (`trsm_inv_kernel`, enveloped:
+ * `trsm_inv_env_kernel`) otherwise -- the stored values have the same bits either way.  X: the whole ni[f] x nb[f] UR of every front,
+ * column-major with leading dimension ni[f], front after front, overwritten with what the device holds afterwards; inv: one 256 x 256
+ * block per front.  r0 a multiple of 256; a front with ni[f] <= r0 is left untouched.  On the device UR has the leading dimension
+ * ni[f] + ldpad and starts `shift` (0 or 1) doubles past a 16-byte boundary.  env != 0: an enveloped launch, every front with the firstU
+ * of the leading zeros its columns really have.  *strips (may be null): launches that took the strip kernel.
+ *   hsk_trsm_strip_enable   : 0 sends the base case to the two half products again (default: on unless HS_TRSM_STRIP=0); returns the
+ *                             previous setting.
+ *   hsk_trsm_strip_launches : launches of trsm_strip_kernel since the last call with reset != 0 (each replaces a pair of half products).
+ *   hsk_trsm_half_launches  : the same for the Float64 lower half products (GemmOp::ainv 3 and 4, one count per launch). */
+int hsk_trsm_inv_d(int64_t count, const int64_t* ni, const int64_t* nb, int64_t r0, int64_t c0, int64_t c1, int64_t ldpad, int64_t shift,
+                   const double* inv, double* X, int env, int64_t* strips);
+int hsk_trsm_strip_enable(int on);
+long long hsk_trsm_strip_launches(int reset);
+long long hsk_trsm_half_launches(int reset);
+
 /* The kernels of hs_mod_* (kernels_mod.hip) on host data; every block column-major.
  *   hsk_mod_inner:   T (k x m, ldt) = op(P)^H Y, P n x k, Y n x m; conj != 0: op = conj, i.e. T = P^T Y (ComplexF64; ignored for Float64).
  *                    k in 1..256, m in 1..64.  Row slabs of 2048, partial sums added in slab order (csrc/hs_mod.h states the order).
