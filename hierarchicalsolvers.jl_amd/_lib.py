@@ -80,6 +80,8 @@ EXPORTS = [
     "hs_ldiv_block_d", "hs_ldiv_block_z", "hs_ldiv_block_dev_d", "hs_ldiv_block_dev_z", "hs_ldiv_block_info", "hsk_multi_prob_d", "hsk_multi_prob_z",
     "hs_ldiv_block_t_d", "hs_ldiv_block_t_z", "hs_ldiv_block_dev_t_d", "hs_ldiv_block_dev_t_z", "hsk_multi_prob_t_d", "hsk_multi_prob_t_z",
     "hs_ldiv_ulv_d", "hs_ldiv_ulv_z", "hs_ldiv_ulv_dev_d", "hs_ldiv_ulv_dev_z",
+    "hs_mul_d", "hs_mul_z", "hs_mul_dev_d", "hs_mul_dev_z", "hs_mul_info", "hs_factor_error_d", "hs_factor_error_z",
+    "hsk_multi_tri_d", "hsk_multi_tri_z", "hsk_multi_tri_t_d", "hsk_multi_tri_t_z",
     "hs_ldiv_sparse_d", "hs_ldiv_sparse_z", "hs_ldiv_sparse_dev_d", "hs_ldiv_sparse_dev_z", "hs_ldiv_sparse_plan", "hs_ldiv_sparse_info",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
@@ -159,7 +161,8 @@ def lib():
         f.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp]
         f.restype = C.c_int
     # (F, trans, C, ldc, B, ldb, n, nrhs) on the host, the same on the device with a stream
-    for host, dev in (("hs_ldiv_t", "hs_ldiv_dev_t"), ("hs_ldiv_block", "hs_ldiv_block_dev"), ("hs_ldiv_block_t", "hs_ldiv_block_dev_t"), ("hs_ldiv_ulv", "hs_ldiv_ulv_dev")):
+    for host, dev in (("hs_ldiv_t", "hs_ldiv_dev_t"), ("hs_ldiv_block", "hs_ldiv_block_dev"), ("hs_ldiv_block_t", "hs_ldiv_block_dev_t"), ("hs_ldiv_ulv", "hs_ldiv_ulv_dev"),
+                      ("hs_mul", "hs_mul_dev")):
         for sfx in ("_d", "_z"):
             f = getattr(L, host + sfx)
             f.argtypes = [vp, C.c_int, p_f64, i64, p_f64, i64, i64, i64]
@@ -169,6 +172,17 @@ def lib():
             f.restype = C.c_int
     L.hs_ldiv_block_info.argtypes = [vp, p_f64]
     L.hs_ldiv_block_info.restype = C.c_int
+    L.hs_mul_info.argtypes = [vp, p_f64]
+    L.hs_mul_info.restype = C.c_int
+    for f in (L.hs_factor_error_d, L.hs_factor_error_z):  # Omega: a host or a device address (where)
+        f.argtypes = [vp, C.c_int, vp, i64, i64, i64, C.c_int, p_f64]
+        f.restype = C.c_int
+    for f in (L.hsk_multi_tri_d, L.hsk_multi_tri_z):
+        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        f.restype = C.c_int
+    for f in (L.hsk_multi_tri_t_d, L.hsk_multi_tri_t_z):
+        f.argtypes = [i64, i64, i64, p_f64, i64, p_f64, i64, p_f64, i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        f.restype = C.c_int
     for f in (L.hs_ldiv_sparse_d, L.hs_ldiv_sparse_z):
         f.argtypes = [vp, C.c_int, i64, i64, p_i64, p_i64, p_f64, p_i64, i64, p_f64, i64]
         f.restype = C.c_int

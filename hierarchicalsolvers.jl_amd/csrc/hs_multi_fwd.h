@@ -7,9 +7,11 @@
 #include "hs_multi_tile.h"
 
 // The forward side of the shared workgroup body (multi_tile_body, hs_multi_tile.h).
-template <class T, class S>
+// MULV = 1: the side of hs_mul_*'s products (MultiProbMul, hs_solve_multi.h); 0: the solves', whose code does not change with it.
+template <class T, class S, int MULV = 0>
 struct MultiFwd {
-  typedef MultiProb<T, S> Prob;
+  static constexpr bool MUL = MULV != 0, SPLITC = MULV != 0;
+  typedef typename std::conditional<MUL, MultiProbMul<T, S>, MultiProb<T, S>>::type Prob;
   typedef MultiElem<S> E;
   typedef typename E::real R;
   // every row of the workgroup's tile exists: the real loads take whole row pairs then
@@ -18,6 +20,18 @@ struct MultiFwd {
   static constexpr int STEP = 4;
   static __device__ __forceinline__ int first(int wv, int nch) { return wv; }
   static __device__ __forceinline__ int end(int wv, int nch) { return nch; }
+  static __device__ __forceinline__ bool cin(const Prob& p) {
+    if constexpr (MUL)
+      return p.Cin || p.C2;
+    else
+      return p.Cin;
+  }
+  // MUL: the chunks of A's columns that meet rows r0 .. r0 + RW - 1 of a triangular operand.  trap = 1 keeps col <= row: columns below
+  // min(K, r0 + RW); trap = 2 keeps col >= row: columns from r0 on
+  static __device__ __forceinline__ int lo(const Prob& p, int r0, int nch) { return p.trap == 2 ? min(r0 / (4 * HSM_KS), nch) : 0; }
+  static __device__ __forceinline__ int hi(const Prob& p, int r0, int nch) {
+    return p.trap == 1 ? min((r0 + hs_multi_rows_per_wg_c(sizeof(T) == 16) + 4 * HSM_KS - 1) / (4 * HSM_KS), nch) : nch;
+  }
 
   // the chunk of A starting at column kb -> registers (a[2 ks + h]: k-step ks, row half / row tile h), and its rows of X (x[ct][ks])
   template <int NT>
@@ -33,7 +47,14 @@ struct MultiFwd {
         if constexpr (CX) {
           const int rr = r0 + 16 * h + l15;
           v = E::ld2(ap + min(rr, p.M - 1));
-          if (p.trap) {
+          if constexpr (MUL) {
+            if (p.trap == 1) {
+              if (col == rr) { v.x = R(1); v.y = R(0); }
+              if (col > rr) { v.x = R(0); v.y = R(0); }
+            } else if (p.trap == 2) {
+              if (col < rr) { v.x = R(0); v.y = R(0); }
+            }
+          } else if (p.trap) {
             if (col == rr) { v.x = R(1); v.y = R(0); }
             if (col > rr) { v.x = R(0); v.y = R(0); }
           }
@@ -45,7 +66,15 @@ struct MultiFwd {
             v.x = gld(ap + min(rr, p.M - 1));
             v.y = gld(ap + min(rr + 1, p.M - 1));
           }
-          if (p.trap) {
+          if constexpr (MUL) {
+            if (p.trap == 1) {
+              v.x = col < rr ? v.x : (col == rr ? R(1) : R(0));
+              v.y = col < rr + 1 ? v.y : (col == rr + 1 ? R(1) : R(0));
+            } else if (p.trap == 2) {
+              v.x = col >= rr ? v.x : R(0);
+              v.y = col >= rr + 1 ? v.y : R(0);
+            }
+          } else if (p.trap) {
             v.x = col < rr ? v.x : (col == rr ? R(1) : R(0));
             v.y = col < rr + 1 ? v.y : (col == rr + 1 ? R(1) : R(0));
           }
@@ -59,7 +88,10 @@ struct MultiFwd {
       for (int ct = 0; ct < NT; ++ct) {
         typename MultiX<T>::type v = MultiX<T>::load(xp + ct * 16);
         if (col >= p.K) v = (typename MultiX<T>::type)(0.0);
-        x[ct][ks] = p.Cin ? -v : v;
+        if constexpr (MUL)
+          x[ct][ks] = p.minus ? -v : v;
+        else
+          x[ct][ks] = p.Cin ? -v : v;
       }
     }
   }
@@ -151,6 +183,54 @@ __device__ __forceinline__ bool multi_resolve(const SolveNode<S>& nd, const Mult
       p.X = w2 + (long long)c0 * a.kcw;
       p.C = w1;
       p.Cin = w1;
+      return true;
+  }
+  return false;
+}
+
+// the product of a step of hs_mul_run (trans = 0) for one front, from its solve descriptor (false: the front has no such step)
+template <class T>
+__device__ __forceinline__ bool mul_resolve(const SolveNode<T>& nd, const MultiAux& ax, int mode, const MultiArgs& a, MultiProbMul<T, T>& p) {
+  if (nd.ni <= 0) return false;
+  T* w1 = (T*)a.W1 + (nd.woff - a.wbase) * a.kcw;
+  T* w2 = (T*)a.W2 + nd.woff * a.kcw;
+  T* xb = (T*)a.XB + ax.boff * a.kcw;
+  p.trap = 0;
+  p.cmap = nullptr;
+  p.xrs = a.kcw;
+  p.crs = a.kcw;
+  p.Cin = nullptr;
+  p.minus = 0;
+  p.split = 0;
+  p.C2 = nullptr;
+  p.lda = nd.ldl;
+  switch (mode) {
+    case HSMM_TRIU:
+      p.A = nd.LF;
+      p.M = p.K = nd.ni;
+      p.trap = 2;
+      p.X = w1;
+      p.C = w2;
+      return true;
+    case HSMM_UR:
+      if (nd.compressed || nd.nb <= 0) return false;
+      p.A = nd.UR;
+      p.lda = nd.ldu;
+      p.M = nd.ni;
+      p.K = nd.nb;
+      p.X = xb;
+      p.Cin = w2;
+      p.C = w2;
+      return true;
+    case HSMM_TRAP:
+      p.A = nd.LF;
+      p.M = max(nd.mrows, nd.ni);
+      p.K = nd.ni;
+      p.trap = 1;
+      p.X = w2;
+      p.C = w1;
+      p.split = nd.ni;
+      p.C2 = xb;
       return true;
   }
   return false;

@@ -3,7 +3,7 @@
 // include this header, each a translation unit of its own (the kernels sit at their register limit and keep their allocation only as long
 // as nothing else is compiled into their functions, DESIGN.md section 4a⁗″):
 //   kernels_solve_multi.hip      HS_MULTI_INST_FWD(T, T)              kernels_solve_multi_t.hip    HS_MULTI_INST_TR(T, T)
-//   kernels_solve_multi_f32.hip  both, S = F32Of<T>::type
+//   kernels_solve_multi_f32.hip  both, S = F32Of<T>::type            kernels_solve_multi_mul.hip  HS_MULTI_INST_MUL(T): the products of hs_mul_*
 // level: one workgroup column per front of a tree level, the product resolved from the front's descriptor; prob: one given product (the
 // low-rank transforms, the test hooks).
 #pragma once
@@ -64,6 +64,57 @@ void launch_multi_prob_t(const MultiProbT<T, S>& p, int kc, hipStream_t s) {
   multi_launch<T>(p.M, 1, kc, [&](auto nt, dim3 grid) { hipLaunchKernelGGL((multi_t_prob_kernel<T, S, decltype(nt)::value>), grid, dim3(256), 0, s, p, kc); });
 }
 
+// ---- the products of hs_mul_* (C = op(F) B): the same body over the MUL sides, S = T, a unit of their own (kernels_solve_multi_mul.hip) ----
+template <class T, int NT>
+__global__ __launch_bounds__(256) void mul_level_kernel(const SolveNode<T>* __restrict__ nodes, int mode, MultiArgs a) {
+  __shared__ double red[2 * 16 * NT * 64];
+  const SolveNode<T> nd = nodes[blockIdx.y];
+  MultiProbMul<T, T> p;
+  if (!mul_resolve<T>(nd, a.aux[blockIdx.y], mode, a, p)) return;
+  if ((int)blockIdx.x * hs_multi_rows_per_wg_c(sizeof(T) == 16) >= p.M) return;
+  multi_tile_body<MultiFwd<T, T, 1>, T, NT>(p, a.kc, red);
+}
+template <class T, int NT>
+__global__ __launch_bounds__(256) void mul_prob_kernel(MultiProbMul<T, T> p, int kc) {
+  __shared__ double red[2 * 16 * NT * 64];
+  multi_tile_body<MultiFwd<T, T, 1>, T, NT>(p, kc, red);
+}
+template <class T, int NT>
+__global__ __launch_bounds__(256) void mul_t_level_kernel(const SolveNode<T>* __restrict__ nodes, int mode, int conj, MultiArgs a) {
+  __shared__ double red[2 * 16 * NT * 64];
+  const SolveNode<T> nd = nodes[blockIdx.y];
+  MultiProbMulT<T, T> p;
+  if (!mul_t_resolve<T>(nd, a.aux[blockIdx.y], mode, conj, a, p)) return;
+  if ((int)blockIdx.x * hs_multi_rows_per_wg_c(sizeof(T) == 16) >= p.M) return;
+  multi_tile_body<MultiTr<T, T, 1>, T, NT>(p, a.kc, red);
+}
+template <class T, int NT>
+__global__ __launch_bounds__(256) void mul_t_prob_kernel(MultiProbMulT<T, T> p, int kc) {
+  __shared__ double red[2 * 16 * NT * 64];
+  multi_tile_body<MultiTr<T, T, 1>, T, NT>(p, kc, red);
+}
+template <class T>
+void launch_mul_level(const SolveNode<T>* sn, int nfronts, int mode, int maxM, const MultiArgs& a, hipStream_t s) {
+  multi_launch<T>(maxM, nfronts, a.kc, [&](auto nt, dim3 grid) { hipLaunchKernelGGL((mul_level_kernel<T, decltype(nt)::value>), grid, dim3(256), 0, s, sn, mode, a); });
+}
+template <class T>
+void launch_mul_prob(const MultiProbMul<T, T>& p, int kc, hipStream_t s) {
+  multi_launch<T>(p.M, 1, kc, [&](auto nt, dim3 grid) { hipLaunchKernelGGL((mul_prob_kernel<T, decltype(nt)::value>), grid, dim3(256), 0, s, p, kc); });
+}
+template <class T>
+void launch_mul_level_t(const SolveNode<T>* sn, int nfronts, int mode, int conj, int maxM, const MultiArgs& a, hipStream_t s) {
+  multi_launch<T>(maxM, nfronts, a.kc, [&](auto nt, dim3 grid) { hipLaunchKernelGGL((mul_t_level_kernel<T, decltype(nt)::value>), grid, dim3(256), 0, s, sn, mode, conj, a); });
+}
+template <class T>
+void launch_mul_prob_t(const MultiProbMulT<T, T>& p, int kc, hipStream_t s) {
+  multi_launch<T>(p.M, 1, kc, [&](auto nt, dim3 grid) { hipLaunchKernelGGL((mul_t_prob_kernel<T, decltype(nt)::value>), grid, dim3(256), 0, s, p, kc); });
+}
+
+#define HS_MULTI_INST_MUL(T)                                                                                      \
+  template void launch_mul_level<T>(const SolveNode<T>*, int, int, int, const MultiArgs&, hipStream_t);         \
+  template void launch_mul_prob<T>(const MultiProbMul<T, T>&, int, hipStream_t);                                 \
+  template void launch_mul_level_t<T>(const SolveNode<T>*, int, int, int, int, const MultiArgs&, hipStream_t);  \
+  template void launch_mul_prob_t<T>(const MultiProbMulT<T, T>&, int, hipStream_t);
 #define HS_MULTI_INST_FWD(T, S)                                                                                    \
   template void launch_multi_level<T, S>(const SolveNode<S>*, int, int, int, int, const MultiArgs&, hipStream_t); \
   template void launch_multi_prob<T, S>(const MultiProb<T, S>&, int, hipStream_t);

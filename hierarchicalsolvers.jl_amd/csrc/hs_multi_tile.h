@@ -112,6 +112,9 @@ __device__ __forceinline__ void multi_red_add(const double* slot, int lane, v4d 
 //   K::load<NT>(p, kb, r0, l15, l4, a, x) the chunk at kb -> the operand registers a (A) and x (X, negated when the product is subtracted)
 //   K::mfma<NT>(a, x, acc)                acc += that chunk's product
 //   K::row(r0, q, g, l4)                  the row of D in register g of row tile q
+//   K::cin(p)                             D starts from stored values (Cin, or a second block that is added into)
+//   K::MUL, K::lo / K::hi(p, r0, nch)     a side of hs_mul_*'s products (hs_solve_multi.h): the chunks [lo, hi) of a triangular operand that meet the
+//                                         workgroup's rows are split over the waves, the others are not read; K::SPLITC: D has a second block (C2)
 // Two chunks are in flight in two register arrays (the loads of a chunk are all issued before the MFMAs of the previous one); the partial
 // sums of the four waves meet in LDS (red: 2 x 16 NT x 64 doubles) in the fixed order (w0 + w2) + (w1 + w3); wave 0 reads Cin into its
 // accumulators before the first MFMA and stores D through cmap after the last sum: D is read once and written once, no atomics.
@@ -130,7 +133,15 @@ __device__ __forceinline__ void multi_tile_body(const typename K::Prob& p, int k
   constexpr int KCH = 4 * HSM_KS, ST = K::STEP;
   const bool full = K::full(p, r0);
   const int nch = (p.K + KCH - 1) / KCH;
-  const int cb = K::first(wv, nch), ce = K::end(wv, nch);
+  int cb, ce;
+  if constexpr (K::MUL) {  // a triangular operand: the chunks [lo, hi) that meet the workgroup's rows, split over the waves like a whole K
+    const int lo = K::lo(p, r0, nch), hi = K::hi(p, r0, nch), nc = max(hi - lo, 0);
+    cb = lo + K::first(wv, nc);
+    ce = lo + K::end(wv, nc);
+  } else {
+    cb = K::first(wv, nch);
+    ce = K::end(wv, nch);
+  }
   hs_d2u a0[2 * HSM_KS], a1[2 * HSM_KS];
   typename MultiX<T>::type x0[NT][HSM_KS], x1[NT][HSM_KS];
   if (cb < ce) K::template load<NT>(p, cb * KCH, r0, full, l15, l4, a0, x0);
@@ -139,14 +150,24 @@ __device__ __forceinline__ void multi_tile_body(const typename K::Prob& p, int k
   for (int q = 0; q < 4; ++q)
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct) acc[q][ct] = v4d{0.0, 0.0, 0.0, 0.0};
-  if (wv == 0 && p.Cin) {
+  if (wv == 0 && K::cin(p)) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int row = K::row(r0, q, g, l4);
         if (row >= p.M) continue;
-        const T* src = p.Cin + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
+        const T* src;
+        if constexpr (K::SPLITC) {
+          if (p.C2 && row >= p.split)
+            src = p.C2 + (long long)(row - p.split) * p.crs;
+          else if (p.Cin)
+            src = p.Cin + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
+          else
+            continue;
+        } else {
+          src = p.Cin + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
+        }
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
           const int col = ct * 16 + l15;
@@ -185,7 +206,11 @@ __device__ __forceinline__ void multi_tile_body(const typename K::Prob& p, int k
     for (int g = 0; g < 4; ++g) {
       const int row = K::row(r0, q, g, l4);
       if (row >= p.M) continue;
-      T* dst = p.C + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
+      T* dst;
+      if constexpr (K::SPLITC)
+        dst = (p.C2 && row >= p.split) ? p.C2 + (long long)(row - p.split) * p.crs : p.C + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
+      else
+        dst = p.C + (long long)(p.cmap ? gld(p.cmap + row) : row) * p.crs;
 #pragma unroll
       for (int ct = 0; ct < NT; ++ct) {
         const int col = ct * 16 + l15;

@@ -12,9 +12,11 @@ template <class R>
 __device__ __forceinline__ R multi_trap(R v, int k, int m, R diag) { return k > m ? v : (k == m ? diag : R(0)); }
 
 // The transposed side of the shared workgroup body (multi_tile_body, hs_multi_tile.h).
-template <class T, class S>
+// MULV = 1: the side of hs_mul_*'s products (MultiProbMulT, hs_solve_multi.h); 0: the solves', whose code does not change with it.
+template <class T, class S, int MULV = 0>
 struct MultiTr {
-  typedef MultiProbT<T, S> Prob;
+  static constexpr bool MUL = MULV != 0, SPLITC = false;
+  typedef typename std::conditional<MUL, MultiProbMulT<T, S>, MultiProbT<T, S>>::type Prob;
   typedef MultiElem<S> E;
   typedef typename E::real R;
   static __device__ __forceinline__ bool full(const Prob& p, int m0) { return false; }  // (the loads below decide per chunk: fullk)
@@ -22,6 +24,13 @@ struct MultiTr {
   static constexpr int STEP = 1;
   static __device__ __forceinline__ int first(int wv, int nch) { return wv * ((nch + 3) / 4); }
   static __device__ __forceinline__ int end(int wv, int nch) { return min(nch, first(wv, nch) + (nch + 3) / 4); }
+  static __device__ __forceinline__ bool cin(const Prob& p) { return p.Cin; }
+  // MUL: the chunks of A's rows that meet columns m0 .. m0 + RW - 1 of a triangular operand.  trap = 1 keeps k >= m: rows from m0 on;
+  // trap = 2 keeps k <= m: rows below min(K, m0 + RW)
+  static __device__ __forceinline__ int lo(const Prob& p, int m0, int nch) { return p.trap == 1 ? min(m0 / (4 * HSM_KS), nch) : 0; }
+  static __device__ __forceinline__ int hi(const Prob& p, int m0, int nch) {
+    return p.trap == 2 ? min((m0 + hs_multi_rows_per_wg_c(sizeof(T) == 16) + 4 * HSM_KS - 1) / (4 * HSM_KS), nch) : nch;
+  }
 
   // the 16 rows kb .. kb + 15 of the workgroup's columns of A -> registers, and the matching rows of X (x[ct][ks]).
   // Float64: a[i * 4 + q] holds k-steps 2 i (.x) and 2 i + 1 (.y) of column tile q.  ComplexF64: a[ks * 2 + q] = (re, im).
@@ -38,7 +47,14 @@ struct MultiTr {
           const int k = kb + 4 * ks + l4;
           typename E::pair v = E::ld2(ap + min(k, p.K - 1));
           if (p.conj) v.y = -v.y;
-          if (p.trap) {
+          if constexpr (MUL) {
+            if (p.trap == 1) {
+              v.x = multi_trap<R>(v.x, k, m, R(1));
+              v.y = multi_trap<R>(v.y, k, m, R(0));
+            } else if (p.trap == 2) {
+              if (k > m) { v.x = R(0); v.y = R(0); }
+            }
+          } else if (p.trap) {
             v.x = multi_trap<R>(v.x, k, m, R(1));
             v.y = multi_trap<R>(v.y, k, m, R(0));
           }
@@ -62,7 +78,15 @@ struct MultiTr {
             v.x = gld(ap + min(k, p.K - 1));
             v.y = gld(ap + min(k + 1, p.K - 1));
           }
-          if (p.trap) {
+          if constexpr (MUL) {
+            if (p.trap == 1) {
+              v.x = multi_trap<R>(v.x, k, m, R(1));
+              v.y = multi_trap<R>(v.y, k + 1, m, R(1));
+            } else if (p.trap == 2) {
+              v.x = k <= m ? v.x : R(0);
+              v.y = k + 1 <= m ? v.y : R(0);
+            }
+          } else if (p.trap) {
             v.x = multi_trap<R>(v.x, k, m, R(1));
             v.y = multi_trap<R>(v.y, k + 1, m, R(1));
           }
@@ -77,12 +101,19 @@ struct MultiTr {
     for (int ks = 0; ks < HSM_KS; ++ks) {
       const int k = CX ? kb + 4 * ks + l4 : kb + 8 * (ks >> 1) + 2 * l4 + (ks & 1);
       const int kk = min(k, p.K - 1);
-      const T* xp = p.X + (long long)(p.xmap ? gld(p.xmap + kk) : kk) * p.xrs + l15;
+      const T* xp;
+      if constexpr (MUL)
+        xp = ((p.X2 && kk >= p.split) ? p.X2 + (long long)(kk - p.split) * p.xrs : p.X + (long long)(p.xmap ? gld(p.xmap + kk) : kk) * p.xrs) + l15;
+      else
+        xp = p.X + (long long)(p.xmap ? gld(p.xmap + kk) : kk) * p.xrs + l15;
 #pragma unroll
       for (int ct = 0; ct < NT; ++ct) {
         typename MultiX<T>::type v = MultiX<T>::load(xp + ct * 16);
         if (k >= p.K) v = (typename MultiX<T>::type)(0.0);
-        x[ct][ks] = p.Cin ? -v : v;
+        if constexpr (MUL)
+          x[ct][ks] = p.minus ? -v : v;
+        else
+          x[ct][ks] = p.Cin ? -v : v;
       }
     }
   }
@@ -190,6 +221,56 @@ __device__ __forceinline__ bool multi_t_resolve(const SolveNode<S>& nd, const Mu
       p.X = w2 + (long long)c1 * a.kcw;
       p.C = w1 + (long long)c0 * a.kcw;
       p.Cin = p.C;
+      return true;
+  }
+  return false;
+}
+
+// the product of a step of hs_mul_run (trans = 1, 2) for one front, from its solve descriptor (false: the front has no such step)
+template <class T>
+__device__ __forceinline__ bool mul_t_resolve(const SolveNode<T>& nd, const MultiAux& ax, int mode, int conj, const MultiArgs& a, MultiProbMulT<T, T>& p) {
+  if (nd.ni <= 0) return false;
+  T* w1 = (T*)a.W1 + (nd.woff - a.wbase) * a.kcw;
+  T* w2 = (T*)a.W2 + nd.woff * a.kcw;
+  T* xb = (T*)a.XB + ax.boff * a.kcw;
+  p.trap = 0;
+  p.conj = conj;
+  p.cmap = nullptr;
+  p.xmap = nullptr;
+  p.xrs = a.kcw;
+  p.crs = a.kcw;
+  p.Cin = nullptr;
+  p.minus = 0;
+  p.split = 0;
+  p.X2 = nullptr;
+  p.lda = nd.ldl;
+  switch (mode) {
+    case HSMMT_TRAP:
+      p.A = nd.LF;
+      p.M = nd.ni;
+      p.K = max(nd.mrows, nd.ni);
+      p.trap = 1;
+      p.X = w1;
+      p.split = nd.ni;
+      p.X2 = xb;
+      p.C = w2;
+      return true;
+    case HSMMT_TRIU:
+      p.A = nd.LF;
+      p.M = p.K = nd.ni;
+      p.trap = 2;
+      p.X = w2;
+      p.C = w1;
+      return true;
+    case HSMMT_BND_U:
+      if (nd.compressed || nd.nb <= 0) return false;
+      p.A = nd.UR;
+      p.lda = nd.ldu;
+      p.M = nd.nb;
+      p.K = nd.ni;
+      p.X = w2;
+      p.Cin = xb;
+      p.C = xb;
       return true;
   }
   return false;

@@ -155,7 +155,7 @@ template <class T, class S = T>
 struct MultiProb {
   const S* A;
   int lda, M, K;
-  int trap;  // 1: A is the unit lower trapezoid of what is stored (LowRank::Lp)
+  int trap;  // 1: A is the unit lower trapezoid of what is stored (LowRank::Lp); 2 (the products of hs_mul_* only): its upper triangle, diagonal included
   const T* X;
   long long xrs;    // X(k, c) = X[k * xrs + c]
   const T* Cin;     // null: D = A X; else D = Cin - A X, addressed like C
@@ -207,7 +207,7 @@ template <class T, class S = T>
 struct MultiProbT {
   const S* A;
   int lda, M, K;    // M outputs = columns of A, K = rows of A
-  int trap;         // 1: A is the unit lower trapezoid of what is stored (LowRank::Lp, K x M)
+  int trap;         // 1: A is the unit lower trapezoid of what is stored (LowRank::Lp, K x M); 2 (hs_mul_* only): its upper triangle with the diagonal
   int conj;         // 1: op = conj (ComplexF64)
   const T* X;
   long long xrs;    // X(k, c) = X[(xmap ? xmap[k] : k) * xrs + c]
@@ -231,3 +231,46 @@ template <class T, class S>
 void launch_multi_level_t(const SolveNode<S>* sn, int nfronts, int mode, int blk, int conj, int maxM, const MultiArgs& a, hipStream_t s);
 template <class T, class S>
 void launch_multi_prob_t(const MultiProbT<T, S>& p, int kc, hipStream_t s);
+
+// ---- kernels_solve_multi_mul.hip: the products of hs_mul_* (C = op(F) B, hs_mul_run) ----------------------------------------------------------
+// The same tile body, sides and lane maps with what the product with F needs and the solves do not (a template argument of the sides, so the
+// kernels of the solves keep their code): trap = 2; a triangular operand is read between the 16-column chunks that meet the workgroup's rows and
+// nowhere else; the sign of the product is a field of its own (minus), so D = Cin + A X exists beside Cin - A X and A X; and one product may
+// write (forward: C2) or read (transposed: X2) two work blocks, split at a row: the trapezoid [L11; Lbi] is ONE panel of LF.
+template <class T, class S = T>
+struct MultiProbMul : MultiProb<T, S> {
+  int minus;   // 1: the product is subtracted (D = Cin - A X); 0: added to Cin, or stored when there is none
+  int split;   // with C2: rows >= split of D are C2[(row - split) * crs + c] += (cmap does not reach them); rows below it go through C / Cin
+  T* C2;       // null: no second block
+};
+template <class T, class S = T>
+struct MultiProbMulT : MultiProbT<T, S> {
+  int minus;
+  int split;     // with X2: X(k, c) for k >= split is X2[(k - split) * xrs + c] (xmap does not reach them)
+  const T* X2;   // null: no second block
+};
+enum {
+  HSMM_TRIU = 0,  // Y = triu(LF[0:ni, 0:ni]) W                              (W: work block 1, Y: work block 2)
+  HSMM_UR,        // Y += Uib Xb
+  HSMM_TRAP,      // [W; Xb +=] = unit-trapezoid(LF[0:mrows, 0:ni]) Y        (rows < ni -> W, rows >= ni are added into Xb)
+};
+enum {
+  HSMMT_TRAP = 0,  // Z = op(unit-trapezoid(LF[0:mrows, 0:ni]))^T [W; Xb]    (W: work block 1, Z: work block 2)
+  HSMMT_TRIU,      // W = op(triu(LF[0:ni, 0:ni]))^T Z
+  HSMMT_BND_U,     // Xb += op(Uib)^T Z
+};
+template <class T>
+void launch_mul_level(const SolveNode<T>* sn, int nfronts, int mode, int maxM, const MultiArgs& a, hipStream_t s);
+template <class T>
+void launch_mul_prob(const MultiProbMul<T, T>& p, int kc, hipStream_t s);
+template <class T>
+void launch_mul_level_t(const SolveNode<T>* sn, int nfronts, int mode, int conj, int maxM, const MultiArgs& a, hipStream_t s);
+template <class T>
+void launch_mul_prob_t(const MultiProbMulT<T, T>& p, int kc, hipStream_t s);
+
+// C[:, 0:nrhs] = op(F) C[:, 0:nrhs] in place on the device (ld ldc), in chunks of hs_ldiv_block_cols() columns on the work blocks of the block
+// solve, on stream s (the schedule: hs_solve_multi.hip).  Its figures are hs_mul_figures', never the handle's last block solve.
+template <class T>
+void hs_mul_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s);
+// seconds (waits for the product), factor bytes read, executed flops, useful flops, chunks, work-block bytes of the last hs_mul_run
+void hs_mul_figures(void* mx, double* out6);

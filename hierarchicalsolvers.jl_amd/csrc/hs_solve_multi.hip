@@ -53,8 +53,15 @@ struct MultiCache {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   bool pending = false;  // the events of the last call have not been read yet
   double info[6] = {0, 0, 0, 0, 0, 0};
+  // the last product with the factors (hs_mul_run): its own events and figures, so that it never shows as the handle's last block solve
+  hipEvent_t m0 = nullptr, m1 = nullptr;
+  bool mpending = false;
+  double minfo[6] = {0, 0, 0, 0, 0, 0};
   ~MultiCache() {
     if (e1 && pending) (void)hipEventSynchronize(e1);
+    if (m1 && mpending) (void)hipEventSynchronize(m1);
+    if (m0) (void)hipEventDestroy(m0);
+    if (m1) (void)hipEventDestroy(m1);
     if (W1) hs_scratch_give(W1, b1);
     if (W2) hs_scratch_give(W2, b2);
     if (T1) hs_scratch_give(T1, bt);
@@ -151,6 +158,7 @@ MultiCache* multi_prepare(const HsMultiView& v, int kcw) {
     }
   }
   if (mc->pending && mc->e1) (void)hipEventSynchronize(mc->e1);  // a call on another stream may still use the work blocks
+  if (mc->mpending && mc->m1) (void)hipEventSynchronize(mc->m1);
   mc->pending = false;
   ensure(&mc->W1, &mc->b1, (size_t)wmax * kcw * sizeof(T), "block solve work block");
   ensure(&mc->W2, &mc->b2, (size_t)std::max<long long>(v.wtotal, 1) * kcw * sizeof(T), "block solve work block");
@@ -380,7 +388,185 @@ void multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs
   }
   multi_finish(mc, v, fc, chunks, sizeof(S), s);
 }
+
+// ---- C = op(F) B: the stored factorization applied as an operator (hs_mul_*) ---------------------------------------------------------------
+// F = P' L U front by front, so with Y_f an intermediate per front (work block 2 holds one segment per front) a chunk of columns takes two
+// passes over the tree and no triangular solve:
+//
+//   trans = 0   U pass, every front on its own:   Y_f = triu(U11) X[int] + Uib X[bnd]                 (low-rank fronts: + G (Z_R X[bnd]))
+//               L pass, root -> leaves:           B[int[rperm]] = unit-tril(L11) Y_f,  B[bnd] += Lbi Y_f      (+= C_L (Z_L Y_f))
+//   trans = 1,2 first pass, every front:          Z_f = op(L11)^T X[int[rperm]] + op(Lbi)^T X[bnd]     (+ op(Z_L)^T (op(C_L)^T X[bnd]))
+//               second pass, root -> leaves:      B[int] = op(U11)^T Z_f,  B[bnd] += op(Uib)^T Z_f            (+= op(Z_R)^T (op(G)^T Z_f))
+//
+// The first pass reads X only (it runs level by level on the stream because the levels share work block 1 and the boundary block, in the
+// order of the loop below, but no level waits for another's result); it has consumed all of X before the second writes a row, so the
+// product is in place.  The second pass sets the interior rows of a front and ADDS into its boundary rows, which are interior rows of its
+// ancestors: root first, one stream, so every row is set once and then takes its additions in one fixed order.  Per level and pass: the two
+// moves, the triangle, the boundary product (the trapezoid [L11; Lbi] is one product), the low-rank pairs.
+template <class T>
+void lr_mul(const LowRank<T>& lr, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {  // dst += C (Z x)
+  MultiProb<T, T> q;
+  memset(&q, 0, sizeof q);
+  q.A = lr.Z; q.lda = lr.ldz; q.M = lr.r; q.K = lr.cols;
+  q.X = x; q.xrs = kcw;
+  q.C = tbuf; q.crs = kcw;
+  launch_multi_prob<T, T>(q, kc, s);
+  fc.add(lr.r, lr.cols, kc);
+  MultiProbMul<T, T> p;
+  memset(&p, 0, sizeof p);
+  if (lr.Cd) {
+    p.A = lr.Cd; p.lda = lr.ldc;
+  } else {
+    p.A = lr.Lp; p.lda = lr.ldp; p.trap = 1; p.cmap = lr.rperm;
+  }
+  p.M = lr.rows; p.K = lr.r;
+  p.X = tbuf; p.xrs = kcw;
+  p.Cin = dst; p.C = dst; p.crs = kcw;
+  launch_mul_prob<T>(p, kc, s);
+  fc.add(lr.rows, lr.r, kc);
+}
+template <class T>
+void lr_mul_t(const LowRank<T>& lr, int conj, const T* x, T* dst, T* tbuf, int kcw, int kc, FlopCount& fc, hipStream_t s) {  // dst += op(Z)^T (op(C)^T x)
+  MultiProbT<T, T> q;
+  memset(&q, 0, sizeof q);
+  if (lr.Cd) {
+    q.A = lr.Cd; q.lda = lr.ldc;
+  } else {
+    q.A = lr.Lp; q.lda = lr.ldp; q.trap = 1; q.xmap = lr.rperm;
+  }
+  q.M = lr.r; q.K = lr.rows; q.conj = conj;
+  q.X = x; q.xrs = kcw;
+  q.C = tbuf; q.crs = kcw;
+  launch_multi_prob_t<T, T>(q, kc, s);
+  fc.add(lr.r, lr.rows, kc);
+  MultiProbMulT<T, T> p;
+  memset(&p, 0, sizeof p);
+  p.A = lr.Z; p.lda = lr.ldz; p.M = lr.cols; p.K = lr.r; p.conj = conj;
+  p.X = tbuf; p.xrs = kcw;
+  p.Cin = dst; p.C = dst; p.crs = kcw;
+  launch_mul_prob_t<T>(p, kc, s);
+  fc.add(lr.cols, lr.r, kc);
+}
+// executed flops of a triangular ni x ni product whose workgroups read the chunks that meet their rows only
+void add_tri(FlopCount& fc, int ni, int kc) {
+  if (ni <= 0) return;
+  const double nt16 = (double)((kc + 15) / 16 * 16);
+  double cols = 0.0;
+  for (int r0 = 0; r0 < ni; r0 += fc.tr) cols += std::min((r0 + fc.tr + 15) / 16 * 16, (ni + 15) / 16 * 16);
+  fc.exec += 2.0 * fc.cmul * fc.tr * cols * nt16;
+  fc.useful += 2.0 * fc.cmul * (0.5 * ni * (ni + 1.0)) * kc;
+}
+
+template <class T>
+void mul_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+  const int KC = hs_ldiv_block_cols();
+  const int kcw = KC;
+  const int cj = (trans == 2 && sizeof(T) == 16) ? 1 : 0;
+  if (*v.mx) (void)hs_solve_multi_seconds(*v.mx);  // the last block solve keeps its seconds: multi_prepare closes its events
+  MultiCache* mc = multi_prepare<T, T>(v, kcw);
+  if (!mc->m0) {
+    HS_HIP(hipEventCreate(&mc->m0));
+    HS_HIP(hipEventCreate(&mc->m1));
+  }
+  FlopCount fc;
+  fc.tr = hs_multi_rows_per_wg(sizeof(T) == 16);
+  fc.cmul = sizeof(T) == 16 ? 4 : 1;
+  const int nl = (int)v.levels.size();
+  int chunks = 0;
+  HS_HIP(hipEventRecord(mc->m0, s));
+  for (int64_t c0 = 0; c0 < nrhs; c0 += KC, ++chunks) {
+    const int kc = (int)std::min<int64_t>(KC, nrhs - c0);
+    MultiArgs a;
+    a.W1 = mc->W1; a.W2 = mc->W2; a.XB = mc->XB; a.kcw = kcw;
+    a.B = dC + c0 * ldc; a.ldb = ldc; a.kc = kc;
+    for (int pass = 0; pass < 2; ++pass)
+      for (int lv = 0; lv < nl; ++lv) {  // (the first pass may take its levels in any order; the second: root first)
+        const HsMultiLevel& L = v.levels[lv];
+        if (L.nfronts == 0 || L.maxni == 0) continue;
+        const SolveNode<T>* sn = (const SolveNode<T>*)L.sn;
+        const int nf = L.nfronts, maxni = L.maxni, maxnb = L.maxnb;
+        a.wbase = L.wbase;
+        a.aux = mc->d_aux + mc->aux_off[lv];
+        T* w1 = (T*)mc->W1;
+        T* w2 = (T*)mc->W2;
+        T* xb = (T*)mc->XB;
+        launch_multi_move<T, T>(sn, nf, 1, maxnb, a, s, 0);  // Xb = X[bnd] (first pass), B[bnd] as it stands (second)
+        if (pass == 0) {
+          // W = X[int] (trans = 0) or X[int[rperm]] (trans = 1, 2): move 0 goes through rperm when it is the permuted one
+          launch_multi_move<T, T>(sn, nf, 0, maxni, a, s, trans ? 0 : 2);
+          if (!trans) {
+            launch_mul_level<T>(sn, nf, HSMM_TRIU, maxni, a, s);
+            launch_mul_level<T>(sn, nf, HSMM_UR, maxni, a, s);
+          } else {
+            launch_mul_level_t<T>(sn, nf, HSMMT_TRAP, cj, maxni, a, s);
+          }
+          for (const HsMultiLR& q : L.lr) {
+            const void* tr = trans ? q.lrL : q.lrR;
+            if (!tr) continue;
+            const LowRank<T>& lr = *(const LowRank<T>*)tr;
+            if (lr.r == 0) continue;
+            if (!trans)
+              lr_mul<T>(lr, xb + boff_of(L, q.pos) * kcw, w2 + q.woff * kcw, (T*)mc->T1, kcw, kc, fc, s);
+            else
+              lr_mul_t<T>(lr, cj, xb + boff_of(L, q.pos) * kcw, w2 + q.woff * kcw, (T*)mc->T1, kcw, kc, fc, s);
+          }
+        } else {
+          if (!trans) {
+            launch_mul_level<T>(sn, nf, HSMM_TRAP, maxni + maxnb, a, s);
+          } else {
+            launch_mul_level_t<T>(sn, nf, HSMMT_TRIU, cj, maxni, a, s);
+            launch_mul_level_t<T>(sn, nf, HSMMT_BND_U, cj, maxnb, a, s);
+          }
+          for (const HsMultiLR& q : L.lr) {
+            const void* tr = trans ? q.lrR : q.lrL;
+            if (!tr) continue;
+            const LowRank<T>& lr = *(const LowRank<T>*)tr;
+            if (lr.r == 0) continue;
+            if (!trans)
+              lr_mul<T>(lr, w2 + q.woff * kcw, xb + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+            else
+              lr_mul_t<T>(lr, cj, w2 + q.woff * kcw, xb + boff_of(L, q.pos) * kcw, (T*)mc->T1, kcw, kc, fc, s);
+          }
+          // B[int[rperm]] (trans = 0) or B[int] = W: move 2 reads the segment at woff of "work block 2", which is given as the level's work
+          // block 1 shifted back by the level's base
+          MultiArgs m = a;
+          m.W2 = w1 - L.wbase * kcw;
+          launch_multi_move<T, T>(sn, nf, 2, maxni, m, s, trans ? 0 : 2);
+          launch_multi_move<T, T>(sn, nf, 3, maxnb, a, s, 0);
+        }
+        for (const HsMultiFront& f : L.fronts) {
+          add_tri(fc, f.ni, kc);
+          if (f.dense_bnd) fc.add(pass == 0 ? f.ni : f.nb, pass == 0 ? f.nb : f.ni, kc);
+        }
+      }
+  }
+  HS_HIP(hipEventRecord(mc->m1, s));
+  HS_HIP(hipGetLastError());
+  mc->mpending = true;
+  mc->minfo[0] = 0.0;
+  mc->minfo[1] = (double)chunks * v.sum_fac * sizeof(T);
+  mc->minfo[2] = fc.exec;
+  mc->minfo[3] = fc.useful;
+  mc->minfo[4] = (double)chunks;
+  mc->minfo[5] = (double)(mc->b1 + mc->b2 + mc->bt + mc->bx);
+}
 }  // namespace
+
+template <class T>
+void hs_mul_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s) {
+  mul_run<T>(v, trans, dC, ldc, nrhs, s);
+}
+template void hs_mul_run<double>(const HsMultiView&, int, double*, int64_t, int64_t, hipStream_t);
+template void hs_mul_run<cplx>(const HsMultiView&, int, cplx*, int64_t, int64_t, hipStream_t);
+void hs_mul_figures(void* mx, double* out6) {
+  MultiCache* mc = (MultiCache*)mx;
+  if (mc && mc->mpending) {
+    float ms = 0.f;
+    if (hipEventSynchronize(mc->m1) == hipSuccess && hipEventElapsedTime(&ms, mc->m0, mc->m1) == hipSuccess) mc->minfo[0] = ms * 1e-3;
+    mc->mpending = false;
+  }
+  for (int k = 0; k < 6; ++k) out6[k] = mc ? mc->minfo[k] : 0.0;
+}
 
 template <class T>
 void hs_solve_multi_run(const HsMultiView& v, int trans, T* dC, int64_t ldc, int64_t nrhs, hipStream_t s, const HsMultiActive* act, int phase) {

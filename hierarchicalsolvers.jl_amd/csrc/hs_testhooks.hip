@@ -866,6 +866,50 @@ static void multi_prob_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int6
     launch_multi_prob_t<T, S>(p, (int)kc, 0);
   });
 }
+// one triangular product of hs_mul_* (kernels_solve_multi_mul.hip): C = tri(A) X or C + tri(A) X, and the transposed counterpart
+template <class T>
+static void multi_tri_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int plus, int tri, const int32_t* map) {
+  if (tri != 1 && tri != 2) HS_FAIL(HS_ERR_ARGUMENT, tri, "hsk_multi_tri: tri = %d (1: unit lower trapezoid, 2: upper triangle with the diagonal)", tri);
+  multi_prob_stage<T>("hsk_multi_tri", M, K, kc, A, lda, M, K, X, ldx, C, ldc, map, M, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
+    MultiProbMul<T, T> p;
+    memset(&p, 0, sizeof p);
+    p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = tri;
+    p.X = dX; p.xrs = P;
+    p.Cin = plus ? dC : nullptr;
+    p.C = dC; p.crs = P; p.cmap = dmap;
+    launch_mul_prob<T>(p, (int)kc, 0);
+  });
+}
+template <class T>
+static void multi_tri_t_hook(int64_t M, int64_t K, int64_t kc, const T* A, int64_t lda, const T* X, int64_t ldx, T* C, int64_t ldc, int plus, int tri, int conj,
+                             const int32_t* map) {
+  if (tri != 1 && tri != 2) HS_FAIL(HS_ERR_ARGUMENT, tri, "hsk_multi_tri_t: tri = %d (1: unit lower trapezoid, 2: upper triangle with the diagonal)", tri);
+  multi_prob_stage<T>("hsk_multi_tri_t", M, K, kc, A, lda, K, M, X, ldx, C, ldc, map, K, [&](const T* dA, const T* dX, T* dC, const int* dmap, int64_t P) {
+    MultiProbMulT<T, T> p;
+    memset(&p, 0, sizeof p);
+    p.A = dA; p.lda = (int)lda; p.M = (int)M; p.K = (int)K; p.trap = tri; p.conj = (conj && sizeof(T) == 16) ? 1 : 0;
+    p.X = dX; p.xrs = P; p.xmap = dmap;
+    p.Cin = plus ? dC : nullptr;
+    p.C = dC; p.crs = P;
+    launch_mul_prob_t<T>(p, (int)kc, 0);
+  });
+}
+extern "C" int hsk_multi_tri_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc, int plus, int tri,
+                               const int32_t* map) {
+  HS_GUARD(multi_tri_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, plus, tri, map));
+}
+extern "C" int hsk_multi_tri_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc, int plus, int tri,
+                               const int32_t* map) {
+  HS_GUARD(multi_tri_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, plus, tri, map));
+}
+extern "C" int hsk_multi_tri_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc, int plus, int tri,
+                                 int conj, const int32_t* map) {
+  HS_GUARD(multi_tri_t_hook<double>(M, K, kc, A, lda, X, ldx, C, ldc, plus, tri, conj, map));
+}
+extern "C" int hsk_multi_tri_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc, int plus, int tri,
+                                 int conj, const int32_t* map) {
+  HS_GUARD(multi_tri_t_hook<cplx>(M, K, kc, (const cplx*)A, lda, (const cplx*)X, ldx, (cplx*)C, ldc, plus, tri, conj, map));
+}
 extern "C" int hsk_multi_prob_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                                 int64_t ldc, int minus, int trap, const int32_t* map) {
   HS_GUARD(multi_prob_hook<double, double>(M, K, kc, A, lda, X, ldx, C, ldc, minus, trap, map));

@@ -436,6 +436,96 @@ def ldiv_block_info(F):
             "chunks": int(out[4]), "workspace_bytes": int(out[5])}
 
 
+def _mul_operand(F, what):
+    """``(FactorNode, trans)`` of the operand of :func:`mul` / :func:`factor_error`; the other factor objects are refused."""
+    if isinstance(F, (ModifiedFactor, DemotedFactor)):
+        raise _lib.UnsupportedError(f"{what}: a {type(F).__name__} is not served (products with the stored factors of a FactorNode, transpose(F) or adjoint(F) only)")
+    return _unwrap(F)
+
+
+def _device_block(name, F, X):
+    """``(address, ld, nrhs)`` of a column-major device tensor with ``F.n`` rows and ``F``'s element type."""
+    import torch
+
+    want = torch.complex128 if F.dtype.kind == "c" else torch.float64
+    if not X.is_cuda or X.dtype != want:
+        raise TypeError(f"{name}: a device block must be a device tensor of {F.dtype}")
+    if X.dim() not in (1, 2) or X.shape[0] != F.n:
+        raise _lib.DimensionMismatch(f"DimensionMismatch: B has {tuple(X.shape)[:1]} rows, F is {F.n} x {F.n}")
+    nrhs = 1 if X.dim() == 1 else X.shape[1]
+    ld = F.n if (X.dim() == 1 or nrhs == 1) else X.stride(1)
+    if (F.n > 1 and X.stride(0) != 1) or ld < F.n:
+        raise ValueError(f"{name}: a device block must be column-major (stride 1 down a column)")
+    return X.data_ptr(), ld, nrhs
+
+
+def mul(*args):
+    """``mul(F, X)`` / ``mul(C, F, X)``: ``C = op(F) X`` with the STORED factorization as an operator (``hs_mul_*``; ``lmul!``-style, the
+    counterpart of :func:`ldiv_block_t`).  ``F`` is a :class:`FactorNode`, ``transpose(F)`` or ``adjoint(F)``; ``X`` a vector, an
+    ``n x nrhs`` NumPy block (the shape and dtype rules of :func:`ldiv`) or a column-major device tensor (``hs_mul_dev_*`` on the current
+    stream; the result is a new device tensor, or ``C``, which may be ``X``).  For an exact factorization ``F X = A X`` to rounding; for a
+    compressed one it is the product with the approximation the solves invert.  Two calls return the same bits and a column does not depend
+    on its neighbours.  The handles :func:`ldiv_block_t` refuses are refused; so are :class:`ModifiedFactor` and :class:`DemotedFactor`."""
+    if len(args) == 2:
+        Fo, X = args
+        Cout = None
+    elif len(args) == 3:
+        Cout, Fo, X = args
+    else:
+        raise TypeError("mul(F, X) or mul(C, F, X)")
+    F, trans = _mul_operand(Fo, "mul")
+    if hasattr(X, "data_ptr"):  # a device tensor
+        import torch
+
+        px, ldx, nrhs = _device_block("mul", F, X)
+        if Cout is None:
+            Cout = torch.empty((nrhs, F.n), dtype=X.dtype, device=X.device).T if X.dim() == 2 else torch.empty_like(X)
+        elif not hasattr(Cout, "data_ptr") or tuple(Cout.shape) != tuple(X.shape):
+            raise TypeError("mul: C must be a device tensor of X's shape")
+        pc, ldc, _ = _device_block("mul", F, Cout)
+        fn = getattr(_lib.lib(), "hs_mul_dev" + ("_z" if F.dtype.kind == "c" else "_d"))
+        _lib.check(fn(F._h, trans, pc, ldc, px, ldx, F.n, nrhs, torch.cuda.current_stream().cuda_stream))
+        return Cout
+    return _ldiv_dense("mul", "hs_mul", args)
+
+
+def mul_info(F):
+    """Figures of the last :func:`mul` (or :func:`factor_error`) on ``F`` (``hs_mul_info``), the keys of :func:`ldiv_block_info`.  A product
+    is never filed as the handle's last block solve."""
+    F, _ = _mul_operand(F, "mul_info")
+    out = np.zeros(6)
+    _lib.check(_lib.lib().hs_mul_info(F._h, _pf64(out)))
+    return {"seconds": float(out[0]), "factor_bytes": float(out[1]), "flops_executed": float(out[2]), "flops_useful": float(out[3]),
+            "chunks": int(out[4]), "workspace_bytes": int(out[5])}
+
+
+def factor_error(F, k=32, seed=0, probes=None, full=False):
+    """``||op(A) W - op(F) W||_F / ||op(A) W||_F`` on the device (``hs_factor_error_*``): how far the stored factorization is from the
+    matrix it was made from, a property of the handle alone -- no solve, no right-hand side, no conditioning.  ``probes`` (``n x k`` NumPy
+    block or column-major device tensor) gives ``W``; otherwise ``W`` is the library's ``k`` seeded +-1 columns (no generator state: two
+    calls return the same bits), for which the figure estimates ``||op(A) - op(F)||_F / ||op(A)||_F`` (Hutchinson: relative deviation of
+    the squared norm about ``sqrt(2 / k)``).  ``full=True`` returns ``{"error", "norm_r", "norm_aw", "seconds"}``."""
+    F, trans = _mul_operand(F, "factor_error")
+    fn = getattr(_lib.lib(), "hs_factor_error" + ("_z" if F.dtype.kind == "c" else "_d"))
+    out = np.zeros(4)
+    if probes is None:
+        _lib.check(fn(F._h, trans, None, 0, int(k), int(seed), 0, _pf64(out)))
+    elif hasattr(probes, "data_ptr"):
+        pw, ldw, kk = _device_block("factor_error", F, probes)
+        _lib.check(fn(F._h, trans, pw, ldw, kk, int(seed), 1, _pf64(out)))
+    else:
+        W = np.asarray(probes)
+        if W.ndim not in (1, 2) or W.shape[0] != F.n:
+            raise _lib.DimensionMismatch(f"DimensionMismatch: probes has {W.shape[:1]} rows, F is {F.n} x {F.n}")
+        if W.dtype.kind == "c" and F.dtype.kind != "c":
+            raise TypeError("MethodError: ComplexF64 probes for a Float64 factorization")
+        W = np.asfortranarray(W.reshape(F.n, -1).astype(F.dtype, copy=False))
+        _lib.check(fn(F._h, trans, W.ctypes.data, F.n, W.shape[1], int(seed), 0, _pf64(out)))
+    if full:
+        return {"error": float(out[0]), "norm_r": float(out[1]), "norm_aw": float(out[2]), "seconds": float(out[3])}
+    return float(out[0])
+
+
 class ModifiedFactor:
     """``A + U V^H`` (or ``A + dA``) solved from the factorization of ``A`` (``hs_mod``, include/hs_solver.h): made by :func:`modify`, consumed
     by :func:`ldiv_mod` and by ``gmres_block(A1, B, Pr=M)``.  Holds ``F`` (which therefore outlives it) and, on the device, ``U``, ``V`` (or

@@ -110,6 +110,22 @@ int hsk_multi_prob_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_
 int hsk_multi_prob_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
                        int minus, int trap, int conj, const int32_t* map);
 
+/* One triangular product of hs_mul_* (kernels_solve_multi_mul.hip) on host data, staged like hsk_multi_prob_*: C = tri(A) X (plus == 0) or
+ * C = C + tri(A) X, A M x K (column-major, lda), X K x kc, C M x kc, kc in 1..64.  tri = 1: the unit lower trapezoid of A (entries above the
+ * diagonal and the diagonal itself are not used), tri = 2: its upper triangle with the diagonal (entries below it are not used); the
+ * kernel does not read a 16-column chunk that lies wholly in the unused part for a workgroup's rows.  map (NULL: none): M entries in
+ * 0..M-1, row i of the product belongs to row map[i] of C. */
+int hsk_multi_tri_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                    int plus, int tri, const int32_t* map);
+int hsk_multi_tri_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                    int plus, int tri, const int32_t* map);
+/* The transposed counterpart: C = op(tri(A))^T X or C + op(tri(A))^T X with A K x M (column-major, lda >= K), tri as above (of the K x M
+ * matrix), conj != 0: op = conj (ComplexF64).  map (NULL: none): K entries in 0..K-1, row k of A meets row map[k] of X. */
+int hsk_multi_tri_t_d(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                      int plus, int tri, int conj, const int32_t* map);
+int hsk_multi_tri_t_z(int64_t M, int64_t K, int64_t kc, const double* A, int64_t lda, const double* X, int64_t ldx, double* C, int64_t ldc,
+                      int plus, int tri, int conj, const int32_t* map);
+
 /* The two panel products over a Float32 panel (kernels_solve_multi_f32.hip; hs_f32_*, include/hs_solver.h) on host data: the arguments of
  * hsk_multi_prob_* / hsk_multi_prob_t_*.  A is given in Float64 (ComplexF64) and demoted on the device by the library's demotion kernel
  * (round to nearest even, real and imaginary parts separately) before the product reads it; X, C and the accumulation stay Float64.  On

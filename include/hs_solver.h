@@ -199,6 +199,34 @@ int hs_ldiv_ulv_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const do
  * useful flops, column chunks, workspace bytes} */
 int hs_ldiv_block_info(const hs_handle* F, double* out6);
 
+/* ---- the stored factorization as an operator (hs_mul.hip; the schedule: hs_solve_multi.hip) ------------------------------------------
+ * C = op(F) B for an n x nrhs block (trans = 0: F, 1: transpose(F), 2: adjoint(F)), where F = P' L U front by front is what the handle
+ * stores -- A itself for an exact factorization, the compressed approximation otherwise: lmul!-style, the counterpart of
+ * hs_ldiv_block_t_* with the same arguments, status codes and chunks of HS_LDIV_BLOCK_COLS columns, on the same work blocks (no workspace
+ * and no factor memory is added).  Two passes over the tree per chunk and no triangular solve: every front forms Y = triu(U11) B[int] +
+ * Uib B[bnd] on its own, then, root first, C[int[rperm]] = unit-tril(L11) Y and C[bnd] += Lbi Y (low-rank Gauss transforms through their
+ * factors; trans = 1, 2: the transposed / conjugated products with L and U changing places).  The triangles are read in place, each
+ * workgroup only the 16-column chunks that meet its rows.  No atomics and one summation order: two calls return the same bits and a column
+ * of C depends neither on the other columns nor on its position.  C may alias B; nrhs = 0 touches nothing; the _dev_ forms are
+ * asynchronous on `stream`.  Refused before any device work with C untouched, under the name hs_mul_* / hs_mul_dev_*, what
+ * hs_ldiv_block_t_* refuses and in its order: a null handle, trans outside 0..2, a plan-only or unfinished handle, a mismatched element
+ * type (HS_ERR_ARGUMENT), bad sizes (HS_ERR_DIMENSION), more than one rank, fronts that keep D as an HSS matrix (HS_ERR_UNSUPPORTED). */
+int hs_mul_d(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_mul_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
+int hs_mul_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+int hs_mul_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+/* last product of the handle (waits for it): out6 as hs_ldiv_block_info's.  A product never shows as the handle's last block solve. */
+int hs_mul_info(const hs_handle* F, double* out6);
+/* How far the stored factorization is from A, a property of the handle alone: R = op(A) W - op(F) W on the device for k probe columns W
+ * (the handle's own A, one product with the factors, the ordered column sums of squares) and
+ *   out4 = {||R||_F / ||op(A) W||_F, ||R||_F, ||op(A) W||_F, seconds on the device}.
+ * Omega (n x k, ld ldo; where = 0: host, 1: device pointer) gives the probes; Omega == NULL: column j is the +-1 column
+ * pm1(col_key(seed, j, 0), i) of the library's estimators -- no generator state, two calls return the same bits.  With +-1 probes
+ * ||R||_F^2 / k is the Hutchinson estimate of ||op(A) - op(F)||_F^2.  Refused like hs_mul_*, under the name hs_factor_error_*; k < 1, a
+ * null out4, another `where`: HS_ERR_ARGUMENT. */
+int hs_factor_error_d(hs_handle* F, int trans, const double* Omega, int64_t ldo, int64_t k, int64_t seed, int where, double* out4);
+int hs_factor_error_z(hs_handle* F, int trans, const double* Omega, int64_t ldo, int64_t k, int64_t seed, int where, double* out4);
+
 /* ---- sparse right-hand sides, selected rows of the solution (hs_solve_sparse.hip) ---------------------------------------------------
  * X[r, j] = (op(F)^-1 B)[rows[r], j] for a sparse B and a list of wanted rows.  B is n x nrhs in CSC form, 1-based like A, rows strictly
  * increasing within a column (stored zeros count as entries); rows: 1-based, any order, repeats allowed; rows == NULL: all n rows (nrows is
