@@ -114,7 +114,7 @@ EXPORTS = [
     "hsk_leaf_envelope", "hsk_envelope_enable", "hsk_op_flops_mode", "hsk_op_flops",
     "hsk_gemm_op_d", "hsk_gemm_lds_enable", "hsk_gemm_lds_launches",
     "hsk_gemm_lds_edge_launches", "hsk_gemm_reg_launches", "hsk_gemm_lds_route", "hsk_gemm_schur_d",
-    "hsk_trsm_inv_d", "hsk_trsm_strip_enable", "hsk_trsm_strip_launches", "hsk_trsm_half_launches",
+    "hsk_trsm_inv_d", "hsk_trsm_strip_enable", "hsk_trsm_strip_launches", "hsk_trsm_half_launches", "hsk_lookahead_runs",
 ]
 
 _lib = None
@@ -484,7 +484,7 @@ def lib():
     L.hsk_trsm_inv_d.restype = C.c_int
     L.hsk_trsm_strip_enable.argtypes = [C.c_int]
     L.hsk_trsm_strip_enable.restype = C.c_int
-    for f in (L.hsk_trsm_strip_launches, L.hsk_trsm_half_launches):
+    for f in (L.hsk_trsm_strip_launches, L.hsk_trsm_half_launches, L.hsk_lookahead_runs):
         f.argtypes = [C.c_int]
         f.restype = C.c_longlong
     for f in (L.hsk_front_factor_d, L.hsk_front_factor_z):

@@ -232,6 +232,7 @@ inline int hs_gemm_lds_route_join(int a, int b) {
 // Operands of any alignment and leading dimension.  hs_trsm_strip_enabled: HS_TRSM_STRIP (default on) / hsk_trsm_strip_enable.
 bool hs_trsm_strip_enabled();
 void hs_trsm_half_note();  // one Float64 lower half product (ainv 3 or 4) was launched instead (hsk_trsm_half_launches)
+void hs_lookahead_note();  // Sched::factor_fronts sent one batch to factor_fronts_lookahead (hsk_lookahead_runs; hs_testhooks.hip)
 void launch_trsm_strip(const NodeDesc<double>* dnodes, int nbatch, int maxN, const GemmOp& op, hipStream_t s);
 bool hs_envelope_enabled();  // HS_LEAF_ENVELOPE (default on) / hsk_envelope_enable: leaf fronts are eliminated inside their block envelope
 template <class T>

@@ -494,7 +494,11 @@ struct Sched {
     // ComplexF64: block columns of 512 (a complex product has 4x the flops per byte, K = 512 costs it nothing) and look-ahead from 1,200 interior
     // columns on -- the 1,458-column fronts of levels 6-7 of Helmholtz 112^3 ran without any: metric workload 3.87 -> 3.82 s.  Float64 loses 2 % with 512
     static const int la_min = env_int("HS_LA_MIN", sizeof(T) == 16 ? 1200 : 1536), la_nb = env_int("HS_LA_NB", sizeof(T) == 16 ? 512 : 1024);
-    if (s2 && la_nb >= HS_PB && (la_nb & (la_nb - 1)) == 0 && maxni >= la_min && maxni > la_nb) {
+    // With solve descriptors the block column must hold whole 256-column groups: lu_rec leaves inv256L / inv256U behind only where it meets a
+    // range of exactly 256 columns, and a look-ahead block below 256 (HS_LA_NB = 32, 64, 128) never hands it one.  Such a batch takes the recursive schedule below.
+    const bool la_inv_ok = !sn || la_nb >= 256;
+    if (s2 && la_nb >= HS_PB && (la_nb & (la_nb - 1)) == 0 && maxni >= la_min && maxni > la_nb && la_inv_ok) {
+      hs_lookahead_note();
       factor_fronts_lookahead(la_nb);
       return;
     }

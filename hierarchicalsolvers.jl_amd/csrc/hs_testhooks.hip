@@ -2,6 +2,7 @@
 // They drive exactly the kernels hs_factor_* uses, on caller-supplied dense data, so every kernel
 // can be checked against the oracle in isolation.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <chrono>
 #include <vector>
@@ -364,6 +365,8 @@ extern "C" int hsk_trsm_inv_d(int64_t count, const int64_t* ni, const int64_t* n
 //   mode 0: tournament pivoting, no solve descriptors   1: optimistic, no descriptors (32-row TRSM base case, full-height panels)
 //        2: optimistic WITH descriptors -- the production default: diagonal-block-first 256-column groups, inv256, ainv 3..8 / 16..19
 //        3: tournament with descriptors -- what a redone level runs
+//   + 4 (bit 2): the batch runs with Sched::aligned16 = true, as hs_numeric sets it for the dense batch of a level: Float64 plain updates take
+//        gemm_op_lds_kernel or the edge kernels where hs_gemm_lds_route lets them (ComplexF64 accepts the bit; the route needs sizeof(T) == 8)
 // Outputs (any may be null) are packed per front in the same order: LF m x ni, UR ni x nb, SB nb x nb, rperm ni, info, growth;
 // invL / invU ceil(ni/32) blocks of 32 x 32, inv256L / inv256U ceil(ni/256) blocks of 256 x 256 (column-major; modes 2, 3 only).
 // The batch itself -- device buffers, descriptors, copy-in, factorization, copy-out -- is FrontBatch, shared with hsk_sweep_level_* below.
@@ -386,9 +389,9 @@ struct FrontBatch {
   std::vector<NodeDesc<T>> hn;
   std::vector<SolveNode<T>> hs;  // filled by setup, reaches the device with upload_solve (a caller may complete it in between)
   // the argument checks both hooks share; nothing on the device yet
-  static void check(const char* name, int64_t count, const int64_t* ni_, const int64_t* nb_, const T* F, int mode, int mode_lo) {
-    if (count <= 0 || count > 65535 || !ni_ || !nb_ || !F || mode < mode_lo || mode > 3)
-      HS_FAIL(HS_ERR_ARGUMENT, count, "%s: count in [1, 65535], ni, nb and F non-null and mode in %d..3 required", name, mode_lo);
+  static void check(const char* name, int64_t count, const int64_t* ni_, const int64_t* nb_, const T* F, int mode, int mode_lo, int mode_hi = 3) {
+    if (count <= 0 || count > 65535 || !ni_ || !nb_ || !F || mode < mode_lo || mode > mode_hi)
+      HS_FAIL(HS_ERR_ARGUMENT, count, "%s: count in [1, 65535], ni, nb and F non-null and mode in %d..%d required", name, mode_lo, mode_hi);
     for (int64_t k = 0; k < count; ++k)
       if (ni_[k] < 0 || nb_[k] < 0 || ni_[k] + nb_[k] > (1 << 16))
         HS_FAIL(HS_ERR_ARGUMENT, k, "%s: front %lld has ni = %lld, nb = %lld (need 0 <= ni, nb and ni + nb <= 65536)", name, (long long)k,
@@ -396,6 +399,7 @@ struct FrontBatch {
   }
   void setup(int64_t count_, const int64_t* ni_, const int64_t* nb_, const T* F);
   void upload_solve() { HS_HIP(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice)); }
+  int aligned16_status() const;
   void factor(int mode, double* ms_out);
   void copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U);
 };
@@ -471,8 +475,26 @@ void FrontBatch<T>::setup(int64_t count_, const int64_t* ni_, const int64_t* nb_
   HS_HIP(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
 }
 
+// The premise of Sched::aligned16, which hs_numeric sets for the dense batch of a level: setup lays LF / UR / SB of every front out at multiples
+// of 32 elements of a hipMalloc block (so 16-byte aligned) with even ldl / ldu / lds.  HS_OK when that holds for the whole batch.
+template <class T>
+int FrontBatch<T>::aligned16_status() const {
+  for (int64_t k = 0; k < count; ++k) {
+    const NodeDesc<T>& d = hn[k];
+    if ((((uintptr_t)d.LF | (uintptr_t)d.UR | (uintptr_t)d.SB) & 15) || ((d.ldl | d.ldu | d.lds) & 1)) {
+      hs_set_error(HS_ERR_UNSUPPORTED, k, "front batch: LF / UR / SB of front %lld are not 16-byte aligned with even leading dimensions", (long long)k);
+      return HS_ERR_UNSUPPORTED;
+    }
+  }
+  return HS_OK;
+}
+
+// mode & 3: the pivoting and the descriptors (hsk_front_batch_*); mode & 4: Sched::aligned16, the routing of the plain updates hs_numeric runs with
 template <class T>
 void FrontBatch<T>::factor(int mode, double* ms_out) {
+  const bool aligned = (mode & 4) != 0;
+  mode &= 3;
+  if (aligned) HS_CHECK(aligned16_status());
   Profiler prof;
   // same stream set-up as hs_analyze: a main stream and a high-priority side stream for look-ahead panels
   struct Streams {
@@ -490,6 +512,7 @@ void FrontBatch<T>::factor(int mode, double* ms_out) {
   Sched<T> sch{dn, (int)count, maxni, maxnb, maxm, st.main, &prof, h_ni.data(), h_nb.data(), st.side, 0, st.la, st.sidem};
   if (mode >= 2) sch.sn = dsn;
   sch.optimistic = (mode == 1 || mode == 2);
+  sch.aligned16 = aligned;
   const auto h0 = std::chrono::steady_clock::now();
   sch.factor_fronts();
   HS_HIP(hipEventRecord(ev[1], st.main));
@@ -533,8 +556,8 @@ template <class T>
 static void front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, T* outLF, T* outUR, T* outSB,
                              int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U,
                              double* ms_out) {
-  FrontBatch<T>::check("hsk_front_batch", count, ni_, nb_, F, mode, 0);
-  if ((outInvL || outInvU || outInv256L || outInv256U) && mode < 2)
+  FrontBatch<T>::check("hsk_front_batch", count, ni_, nb_, F, mode, 0, 7);
+  if ((outInvL || outInvU || outInv256L || outInv256U) && (mode & 3) < 2)
     HS_FAIL(HS_ERR_ARGUMENT, mode, "hsk_front_batch: the stored inverses are returned by modes 2 and 3 only");
   FrontBatch<T> fb;
   fb.setup(count, ni_, nb_, F);
@@ -692,6 +715,13 @@ extern "C" int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t
   HS_GUARD(front_batch_hook<cplx>(count, ni, nb, mode, (const cplx*)F, (cplx*)outLF, (cplx*)outUR, (cplx*)outSB, out_rperm, info, growth,
                                   (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, ms_out));
 }
+
+// Batches Sched::factor_fronts has sent to factor_fronts_lookahead since the last reset (process-wide, host only): one note per batch.
+namespace {
+std::atomic<long long> g_lookahead_runs{0};
+}
+void hs_lookahead_note() { g_lookahead_runs.fetch_add(1, std::memory_order_relaxed); }
+extern "C" long long hsk_lookahead_runs(int reset) { return reset ? g_lookahead_runs.exchange(0) : g_lookahead_runs.load(); }
 
 // `count` fronts of one shape, tournament pivoting without solve descriptors (mode 0); HS_HOOK_OPTIMISTIC=1: mode 1, and a raised growth
 // flag comes back through `info` as -1

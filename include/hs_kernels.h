@@ -38,7 +38,15 @@ int hsk_front_factor_z(int64_t count, int64_t ni, int64_t nb, const double* F, d
  * packed per front in batch order: outLF m x ni, outUR ni x nb, outSB nb x nb, out_rperm ni, info[k], growth[k] (1: optimistic
  * pivoting met a multiplier above HS_GROWTH_MAX = 4, a NaN multiplier or a diagonal block singular on its own rows), outInvL / outInvU
  * ceil(ni/32) column-major 32 x 32 inverses of the diagonal blocks of L (unit lower) and U, outInv256L / outInv256U ceil(ni/256)
- * 256 x 256 ones (modes 2 and 3 only). */
+ * 256 x 256 ones (modes 2 and 3 only).
+ * mode + 4 (bit 2; mode & 3 is the mode above): the batch runs with Sched::aligned16 = true, as hs_numeric runs the dense batch of a level --
+ * the hook lays LF / UR / SB out at multiples of 32 elements with even leading dimensions, so the Float64 plain updates go to
+ * gemm_op_lds_kernel or the edge kernels wherever hs_gemm_lds_route allows (hsk_gemm_lds_enable still decides).  ComplexF64 accepts the bit
+ * and runs what it runs without it.  Modes outside 0..7: HS_ERR_ARGUMENT.
+ *   hsk_lookahead_runs : batches that Sched::factor_fronts has sent to the look-ahead schedule (factor_fronts_lookahead: maxni >= HS_LA_MIN,
+ *                        block columns of HS_LA_NB, a side stream) since the last call with reset != 0; process-wide, counted on the host,
+ *                        factorizations through hs_numeric included. */
+long long hsk_lookahead_runs(int reset);
 int hsk_front_batch_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
                       double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
                       double* outInv256L, double* outInv256U, double* ms_out);

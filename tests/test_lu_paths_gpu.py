@@ -308,7 +308,8 @@ def test_hook_argument_checks(hs):
     nb = np.array([0], dtype=np.int64)
     F = np.eye(4)
     inv = np.zeros(1024)
-    assert L.hsk_front_batch_d(1, _pi(ni), _pi(nb), 4, _pd(F), None, None, None, None, None, None, None, None, None, None, None) != 0
+    for mode in (-1, 8):  # (0..3 with or without bit 2, Sched::aligned16: tests/test_lu_lookahead_gpu.py)
+        assert L.hsk_front_batch_d(1, _pi(ni), _pi(nb), mode, _pd(F), None, None, None, None, None, None, None, None, None, None, None) != 0
     assert L.hsk_front_batch_d(0, _pi(ni), _pi(nb), 1, _pd(F), None, None, None, None, None, None, None, None, None, None, None) != 0
     assert L.hsk_front_batch_d(1, _pi(ni), _pi(nb), 1, _pd(F), None, None, None, None, None, None, _pd(inv), None, None, None, None) != 0
     bad = np.array([-1], dtype=np.int64)
@@ -367,6 +368,7 @@ h = hashlib.sha256()
 for k in ("LF", "UR", "SB", "rperm"):
     h.update(np.ascontiguousarray(r[k]).tobytes())
 print("CAP", h.hexdigest())
+print("RUNS", hs._lib.lib().hsk_lookahead_runs(0))
 """
 
 
@@ -377,8 +379,7 @@ def test_capped_update_walks_tiles_bitwise():
     every tile a workgroup.  Which workgroup computes a tile does not change what is computed: factors, Schur complement and pivots are equal
     bit for bit.
     The capped path is taken only while Sched::factor_fronts looks ahead for this front (a second stream, mode 0 = tournament pivoting,
-    ni >= HS_LA_MIN): nothing the library exposes tells the two children apart, so if those preconditions change both run the same launches
-    and this test passes without walking -- keep the front and the switches in step with them."""
+    ni >= HS_LA_MIN): both children report hsk_lookahead_runs, and it must show that they did."""
     code = _CAP_CHILD % (ROOT, os.path.join(ROOT, "tests"))
     out = []
     for cap in ("8", None):
@@ -389,6 +390,8 @@ def test_capped_update_walks_tiles_bitwise():
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, (cap, r.returncode, r.stdout[-2000:], r.stderr[-3000:])
         out.append([ln for ln in r.stdout.splitlines() if ln.startswith("CAP")])
+        runs = [int(ln.split()[1]) for ln in r.stdout.splitlines() if ln.startswith("RUNS")]
+        assert len(runs) == 1 and runs[0] >= 1, (cap, r.stdout[-2000:])
     assert len(out[0]) == 1 and out[0] == out[1], out
 
 
