@@ -115,6 +115,7 @@ EXPORTS = [
     "hsk_gemm_op_d", "hsk_gemm_lds_enable", "hsk_gemm_lds_launches",
     "hsk_gemm_lds_edge_launches", "hsk_gemm_reg_launches", "hsk_gemm_lds_route", "hsk_gemm_schur_d",
     "hsk_trsm_inv_d", "hsk_trsm_strip_enable", "hsk_trsm_strip_launches", "hsk_trsm_half_launches", "hsk_lookahead_runs",
+    "hsk_qr_params", "hsk_qr_chol_d", "hsk_qr_chol_z", "hsk_qr_select", "hsk_qr_refine_d", "hsk_qr_refine_z",
 ]
 
 _lib = None
@@ -501,6 +502,17 @@ def lib():
     L.hsk_flow_tall_rule.restype = C.c_int
     for f in (L.hsk_lowrank_d, L.hsk_lowrank_z):
         f.argtypes = [i64, i64, p_f64, C.c_double, C.c_double, i64, i64, p_i64, p_f64, p_f64, i64]
+        f.restype = C.c_int
+    p_i32 = C.POINTER(C.c_int32)
+    L.hsk_qr_params.argtypes = [p_f64]
+    L.hsk_qr_params.restype = C.c_int
+    for f in (L.hsk_qr_chol_d, L.hsk_qr_chol_z):
+        f.argtypes = [i64, p_i32, p_i32, p_f64, p_f64, p_f64, p_i32, p_f64, p_f64, p_f64, p_f64, p_i32, p_i32]
+        f.restype = C.c_int
+    L.hsk_qr_select.argtypes = [i64, p_i32, p_i32, p_i32, p_i32, p_f64, p_f64]
+    L.hsk_qr_select.restype = C.c_int
+    for f in (L.hsk_qr_refine_d, L.hsk_qr_refine_z):
+        f.argtypes = [i64, p_i32, p_i32, p_f64, p_i32, p_i32, p_f64, p_f64, C.c_int, C.c_double, C.c_double, C.c_double, p_i32, p_f64, p_f64, p_f64, p_i32, p_i32, p_i64]
         f.restype = C.c_int
     L.hs_hss_options_default.argtypes = [C.POINTER(hs_hss_options)]
     L.hs_hss_options_default.restype = None

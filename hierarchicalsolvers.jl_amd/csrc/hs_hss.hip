@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/hs_hss.h"
+#include "../../include/hs_kernels.h"
 #include "hs_host.h"
 #include "hs_lowrank.h"
 #include "hs_sched.h"
@@ -639,7 +640,7 @@ struct Lru {
 // least-squares sense -- measured: ranks 1.4-2x a pivoted QR's, and at the upper levels of a nested compression the children's
 // truncation noise, sitting just below the threshold, was counted as rank).
 //
-// Block classical Gram-Schmidt with re-orthogonalisation over blocks of 32 rows, every block finished by a Cholesky-QR of the 32
+// Block classical Gram-Schmidt with re-orthogonalisation over windows of HS_QW = 64 rows, every window finished by a Cholesky-QR of its
 // residual rows (one wave per block): M[p, :] = L * Q with orthonormal rows of Q; d_j = L_jj is the distance of row j from the span of
 // the rows before it -- the |R_jj| of the pivoted QR of M^H in that order.  Rank = rows with d_j > tau; the remaining rows are
 // interpolated in the least-squares sense: M[p_R, :] ~= (M[p_R, :] Q_S^H) Q_S = T * M[p_S, :] with T = L_RS * L_SS^-1.
@@ -648,11 +649,11 @@ struct Lru {
 // ------------------------------------------------------------------------------------------------
 template <class T>
 struct CholJob {
-  T* G;          // b x b Gram matrix of the candidate rows (ld 32), destroyed
+  T* G;          // b x b Gram matrix of the candidate rows (ld HS_QW), destroyed
   T* Lout;       // -> L[done : done+b', done : done+b'] (ld ldl)
   int ldl;
-  T* Linv;       // b' x b': inverse of the accepted Cholesky factor (ld 32) -- the triangular solves of the interpolation matrix
-  T* LinvP;      // b' x b : the same times the block's pivoting, Q_new = LinvP * W with W in candidate order (ld 32)
+  T* Linv;       // b' x b': inverse of the accepted Cholesky factor (ld HS_QW) -- the triangular solves of the interpolation matrix
+  T* LinvP;      // b' x b : the same times the block's pivoting, Q_new = LinvP * W with W in candidate order (ld HS_QW)
   double* d;     // accepted diagonal entries (b' of them)
   double* top;   // in/out: d_0 of the job (written by the first block)
   int* p;        // the job's candidate order at this window (b entries), permuted in place: accepted rows first
@@ -678,8 +679,8 @@ __device__ inline double from_real<double>(double a) { return a; }
 template <>
 __device__ inline cplx from_real<cplx>(double a) { return {a, 0.0}; }
 
-// Diagonally pivoted Cholesky of the Gram matrix of <= 32 candidate rows (one wave): the candidates are re-ordered by residual norm,
-// and only a well-conditioned prefix is ACCEPTED -- d_k above the truncation threshold and above 1e-5 of the block's first pivot (what a
+// Diagonally pivoted Cholesky of the Gram matrix of <= HS_QW = 64 candidate rows (one wave): the candidates are re-ordered by residual norm,
+// and only a well-conditioned prefix is ACCEPTED -- d_k above the truncation threshold and above HS_CHOL_COND of the block's first pivot (what a
 // Gram matrix resolves reliably in double precision is d_k / |w_k| >~ 1e-8).  Rejected candidates stay next in line: the following
 // window orthogonalises them against the rows accepted here before judging them again.
 #define HS_CHOL_COND 1e-2
@@ -832,8 +833,10 @@ struct SelJob {
   double* outmax;    // [0] largest res2 among the unaccepted rows, [1] largest res2 among those NOT selected for the window
   int done, m, want;
 };
-// one workgroup per job: (1) largest res2 of the tail, (2) histogram of log2(max / res2), (3) stable partition of the tail: the first `want`
-// rows of the buckets up to the cutoff in front (the cutoff is the smallest bucket that fills the window, at most 14: 2^-7 in norm)
+// one workgroup per job: (1) largest res2 of the tail, (2) histogram of log2(max / res2), (3) stable partition of the tail: every row of the
+// buckets below the cutoff and the first rows of the cutoff bucket that still fit in front (the cutoff is the smallest bucket that fills the
+// window, at most 14: 2^-7 in norm).  The lower buckets go first whatever their place in the list: the window then always holds the rows
+// of largest res2, so its first pivot -- which chol_block_kernel accepts unconditionally -- is the greedy one.
 __global__ __launch_bounds__(256) void qr_select_kernel(const SelJob* __restrict__ jobs) {
   const SelJob j = jobs[blockIdx.x];
   const int t = threadIdx.x, nt = j.m - j.done;
@@ -874,19 +877,21 @@ __global__ __launch_bounds__(256) void qr_select_kernel(const SelJob* __restrict
       if (cum >= j.want) { cut = b; break; }
     }
     s_cut = cut;
-    s_base[0] = 0;  // selected so far
-    s_base[1] = 0;  // unselected so far
+    s_base[0] = 0;  // rows below the cutoff bucket so far
+    s_base[1] = 0;  // rows in the cutoff bucket so far
   }
   __syncthreads();
   const int cut = s_cut;
-  // pass A: how many rows qualify (capped at `want`): the rest of the tail starts behind them
-  int nsel_total = 0;
-  for (int b = 0; b <= cut; ++b) nsel_total += s_hist[b];
-  nsel_total = min(nsel_total, j.want);
+  // how many rows are taken: all of the buckets below the cutoff (fewer than `want`) and up to `quota` of the cutoff bucket; the rest of the
+  // tail starts behind them
+  int nlow = 0;
+  for (int b = 0; b < cut; ++b) nlow += s_hist[b];
+  const int quota = j.want - nlow, nsel_total = min(nlow + s_hist[cut], j.want);
   for (int c0 = 0; c0 < nt; c0 += 256) {
     const int e = c0 + t;
     const int row = e < nt ? tail[e] : -1;
-    int f = (row >= 0 && bucket(j.res2[row]) <= cut) ? 1 : 0;
+    const int bk = row >= 0 ? bucket(j.res2[row]) : 16;
+    const int f = (bk < cut ? 1 << 16 : 0) | (bk == cut ? 1 : 0);  // two counters in one scan of 256 flags: rows below the cutoff (high half), rows at it (low half)
     s_scan[t] = f;
     __syncthreads();
     for (int off = 1; off < 256; off <<= 1) {  // inclusive scan of the flags
@@ -896,19 +901,19 @@ __global__ __launch_bounds__(256) void qr_select_kernel(const SelJob* __restrict
       __syncthreads();
     }
     const int incl = s_scan[t], tot = s_scan[255];
-    const int sel_before = s_base[0], uns_before = s_base[1];
+    const int low_base = s_base[0], eq_base = s_base[1];
     __syncthreads();
     if (row >= 0) {
-      const int rank_sel = sel_before + incl - f;  // selected rows before this one
-      const bool take = f && rank_sel < j.want;
+      const int low_before = low_base + ((incl - f) >> 16), eq_before = eq_base + ((incl - f) & 0xffff);  // such rows before this one
+      const bool take = bk < cut || (bk == cut && eq_before < quota);
       // position: selected rows in front; everything else behind them in the original order
-      const int taken_before = min(rank_sel, j.want);
+      const int taken_before = low_before + min(eq_before, quota);
       const int untaken_before = (e - taken_before);  // rows before this one that are not taken = index - taken
       j.tmp[take ? taken_before : nsel_total + untaken_before] = row;
     }
     if (t == 0) {
-      s_base[0] = sel_before + tot;
-      s_base[1] = uns_before + (min(256, nt - c0) - tot);
+      s_base[0] = low_base + (tot >> 16);
+      s_base[1] = eq_base + (tot & 0xffff);
     }
     __syncthreads();
   }
@@ -927,6 +932,17 @@ __global__ __launch_bounds__(256) void qr_select_kernel(const SelJob* __restrict
   }
   if (t == 0) j.outmax[1] = s_red[0];
 }
+
+// read once per process (hsk_qr_params reports them to the tests)
+static double qr_theta() {
+  static const double v = getenv("HS_QR_THETA") ? atof(getenv("HS_QR_THETA")) : 0.5;  // relaxation of the greedy order (1: strict)
+  return v;
+}
+static double qr_chol_cond() {
+  static const double v = getenv("HS_CHOL_COND") ? atof(getenv("HS_CHOL_COND")) : HS_CHOL_COND;  // diagnostics
+  return v;
+}
+static void launch_select(const SelJob* d, unsigned n, hipStream_t s) { hipLaunchKernelGGL(qr_select_kernel, dim3(n), dim3(256), 0, s, d); }
 
 static std::atomic<int> g_qr_order{-1};  // -1: not read yet (HS_QR_ORDER=norm in the environment), 0: the tournament order, 1: residual norms
 static bool qr_norm_order() {
@@ -959,16 +975,24 @@ struct QrJob {
   int ldt = 2;
 };
 
-// rank = number of accepted rows: d_j > max(atol, rtol * max(d_0, scale_floor)) in a windowed-pivoted order (window: 32 candidates)
+// What a call of qr_refine did, for the tests (hsk_qr_refine_*): filled only when the caller passes one.
+struct QrTrace {
+  long long windows = 0;    // windows run (one pivoted Cholesky each), over all jobs
+  long long refreshes = 0;  // residual norms recomputed from the explicit residual (norm_select), over all jobs
+  std::vector<std::vector<double>> d;                     // per job: the accepted d_j (r of them)
+  std::vector<std::vector<std::pair<int, int>>> blocks;  // per job: (offset, width) of the accepted blocks
+};
+
+// rank = number of accepted rows: d_j > max(atol, rtol * max(d_0, scale_floor)) in a windowed-pivoted order (window: HS_QW = 64 candidates)
 template <class T>
-void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double atol, double rtol, double scale_floor, hipStream_t s) {
+void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double atol, double rtol, double scale_floor, hipStream_t s, QrTrace* trace = nullptr) {
   const int nj = (int)jobs.size();
   if (nj == 0) return;
   struct St {
     T *Q = nullptr, *Qh = nullptr, *L = nullptr, *Linv = nullptr, *LinvP = nullptr, *W = nullptr, *Wh = nullptr, *C1 = nullptr, *C2 = nullptr, *G = nullptr;
     double *d = nullptr, *top = nullptr;
     int *lperm = nullptr, *nacc = nullptr;
-    T* slab = nullptr;  // 32 x 32 slots for the blocks' inverse factors
+    T* slab = nullptr;  // pairs of HS_QW x HS_QW slots for the blocks' inverse factors (Linv, LinvP)
     int nslab = 0, used = 0;
     int ldq = 2, ldqh = 2, ldl = 2, done = 0, active = 1, maxblk = 0, stall = 0;
     std::vector<std::pair<int, int>> blocks;  // (offset, width) of the accepted blocks
@@ -1029,15 +1053,15 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
   run_norms();
   std::vector<double> hmax(2 * (size_t)nj, 0.0);
   double* dmaxall = tmp.get<double>(2 * (size_t)nj);
-  static const double theta = getenv("HS_QR_THETA") ? atof(getenv("HS_QR_THETA")) : 0.5;  // relaxation of the greedy order (1: strict)
+  static const double theta = qr_theta();
   int* dnacc = tmp.get<int>((size_t)nj);
   for (int a = 0; a < nj; ++a) st[a].nacc = dnacc + a;
   std::vector<int> hacc(nj, 0);
   std::vector<RowJob<T>> rows;
   std::vector<SubJob<T>> subs;
   std::vector<GemmProb<T>> g;
-  std::vector<std::vector<T*>> linv(nj), linvp(nj);  // one 32 x 32 slot per accepted block
-  static const double chol_cond = getenv("HS_CHOL_COND") ? atof(getenv("HS_CHOL_COND")) : HS_CHOL_COND;  // diagnostics
+  std::vector<std::vector<T*>> linv(nj), linvp(nj);  // one HS_QW x HS_QW slot per accepted block
+  static const double chol_cond = qr_chol_cond();
   static const bool qtime = getenv("HS_QR_TIMING") != nullptr;  // diagnostics: wall time of the phases (adds nothing: every step syncs anyway)
   auto tq0 = std::chrono::steady_clock::now();
   int nsteps = 0;
@@ -1054,7 +1078,7 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
       });
       if (!sj.empty()) {
         SelJob* dsj = upload(tmp, sj, s);
-        hipLaunchKernelGGL(qr_select_kernel, dim3((unsigned)sj.size()), dim3(256), 0, s, (const SelJob*)dsj);
+        launch_select(dsj, (unsigned)sj.size(), s);
       }
     }
     // W = M[p[done : done+b], :]
@@ -1091,6 +1115,7 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
                               rtol, scale_floor, b, S.done == 0 ? 1 : 0, J.floor_abs, chol_cond, noise_rel(), J.norm_select ? dmaxall + 2 * a + 1 : nullptr, theta * theta});
     });
     run_gemms(tmp, g, 0, s);
+    if (trace) trace->windows += (long long)cj.size();
     CholJob<T>* dcj = upload(tmp, cj, s);
     launch_chol<T>(dcj, (unsigned)cj.size(), s);
     // how many candidates each job accepted
@@ -1152,6 +1177,7 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
         if (S.refmax == 0.0) S.refmax = hmax[2 * a];
         if (hmax[2 * a] < 1e-10 * S.refmax && S.done > 0) fresh.push_back(a);
       }
+      if (trace) trace->refreshes += (long long)fresh.size();
       if (!fresh.empty()) {
         std::vector<T*> Rt(fresh.size(), nullptr);
         std::vector<SubJob<T>> cp;
@@ -1191,6 +1217,15 @@ void qr_refine(Pool& tmp, Pool& out_pool, std::vector<QrJob<T>>& jobs, double at
   HS_HIP(hipStreamSynchronize(s));
   for (int a = 0; a < nj; ++a)
     if (jobs[a].r == 0) jobs[a].top = std::max(jobs[a].top, 0.0);
+  if (trace) {
+    trace->d.assign(nj, {});
+    trace->blocks.assign(nj, {});
+    for (int a = 0; a < nj; ++a) {
+      trace->blocks[a] = st[a].blocks;
+      trace->d[a].resize((size_t)jobs[a].r);
+      if (jobs[a].r > 0) HS_HIP(hipMemcpy(trace->d[a].data(), st[a].d, sizeof(double) * (size_t)jobs[a].r, hipMemcpyDeviceToHost));
+    }
+  }
   static const bool qdebug = getenv("HS_QR_DEBUG") != nullptr;  // diagnostics: the accepted d_j of the job of largest rank, window by window
   if (qdebug) {
     int am = 0;
@@ -1576,7 +1611,7 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
         qj[a].q = k2;
         qj[a].p = porder[a];
         qj[a].norm_select = norm_order;
-        qj[a].rmax = norm_order ? std::min(nd[i].m, k) : lr[a].k;  // the pivoted LU ordered the first k (sketch width) rows; the orthogonalisation stops by itself once a block of 32 rows is below the threshold
+        qj[a].rmax = norm_order ? std::min(nd[i].m, k) : lr[a].k;  // the pivoted LU ordered the first k (sketch width) rows; the orthogonalisation stops by itself once a window of HS_QW rows is below the threshold
         qj[a].atol_scale = std::max(H.opt.atol, H.opt.rtol * cb[nblk[i]].gscale_q);  // absolute threshold of ITS matrix (times lsc below)
         qj[a].floor_abs = noise[nblk[i]];
       }
@@ -3745,4 +3780,202 @@ extern "C" void hs_hss_free(hs_hss* H) {
   else
     delete HD(H);
   delete H;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test hooks of the rank-revealing orthogonalisation (include/hs_kernels.h; tests/test_qr_refine_gpu.py): the production launches of
+// chol_block_kernel and qr_select_kernel on caller-supplied jobs, and qr_refine itself on a batch of host matrices.  Every array a kernel
+// writes is uploaded first, so the caller sees what was left untouched.
+// ------------------------------------------------------------------------------------------------
+namespace {
+void qr_need_device() {
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) HS_FAIL(HS_ERR_DEVICE, 0, "no HIP device available");
+}
+template <class U>
+U* qr_put(HsDevBuf& buf, const U* h, size_t count) {
+  U* d = buf.get<U>(std::max<size_t>(count, 1));
+  if (count > 0) HS_HIP(hipMemcpy(d, h, sizeof(U) * count, hipMemcpyHostToDevice));
+  return d;
+}
+template <class U>
+void qr_bring(U* h, const U* d, size_t count) {
+  if (count > 0) HS_HIP(hipMemcpy(h, d, sizeof(U) * count, hipMemcpyDeviceToHost));
+}
+
+template <class T>
+void qr_chol_hook(int64_t njobs, const int32_t* b, const int32_t* first, const T* G, const double* thr, double* top, int32_t* p, T* L, T* Linv, T* LinvP, double* d,
+                  int32_t* lperm, int32_t* nacc) {
+  if (njobs < 1 || njobs > 65535 || !b || !first || !G || !thr || !top || !p || !L || !Linv || !LinvP || !d || !lperm || !nacc)
+    HS_FAIL(HS_ERR_ARGUMENT, njobs, "hsk_qr_chol: njobs in [1, 65535] and non-null arrays required");
+  for (int64_t a = 0; a < njobs; ++a)
+    if (b[a] < 1 || b[a] > HS_QW) HS_FAIL(HS_ERR_ARGUMENT, a, "hsk_qr_chol: job %lld has b = %d (1 .. %d)", (long long)a, b[a], HS_QW);
+  qr_need_device();
+  constexpr size_t W = HS_QW, WW = (size_t)HS_QW * HS_QW;
+  const size_t n = (size_t)njobs;
+  HsDevBuf buf("hsk_qr_chol");
+  T* dG = qr_put(buf, G, n * WW);
+  T* dL = qr_put(buf, L, n * WW);
+  T* dLi = qr_put(buf, Linv, n * WW);
+  T* dLp = qr_put(buf, LinvP, n * WW);
+  double* dd = qr_put(buf, d, n * W);
+  double* dtop = qr_put(buf, top, n);
+  int32_t* dp = qr_put(buf, p, n * W);
+  int32_t* dlp = qr_put(buf, lperm, n * W);
+  int32_t* dna = qr_put(buf, nacc, n);
+  std::vector<double> hnext(n);
+  for (size_t a = 0; a < n; ++a) hnext[a] = thr[5 * a + 4];
+  double* dnext = qr_put(buf, hnext.data(), n);
+  std::vector<CholJob<T>> cj;
+  for (size_t a = 0; a < n; ++a)
+    cj.push_back(CholJob<T>{dG + a * WW, dL + a * WW, HS_QW, dLi + a * WW, dLp + a * WW, dd + a * W, dtop + a, (int*)dp + a * W, (int*)dlp + a * W, (int*)dna + a, thr[5 * a], thr[5 * a + 1],
+                            thr[5 * a + 2], b[a], first[a] ? 1 : 0, thr[5 * a + 3], qr_chol_cond(), noise_rel(), thr[5 * a + 4] < 0.0 ? nullptr : dnext + a,
+                            qr_theta() * qr_theta()});
+  CholJob<T>* dcj = qr_put(buf, cj.data(), n);
+  launch_chol<T>(dcj, (unsigned)n, 0);
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipDeviceSynchronize());
+  qr_bring(L, dL, n * WW);
+  qr_bring(Linv, dLi, n * WW);
+  qr_bring(LinvP, dLp, n * WW);
+  qr_bring(d, dd, n * W);
+  qr_bring(top, dtop, n);
+  qr_bring(p, dp, n * W);
+  qr_bring(lperm, dlp, n * W);
+  qr_bring(nacc, dna, n);
+}
+
+void qr_select_hook(int64_t njobs, const int32_t* m, const int32_t* done, const int32_t* want, int32_t* p, const double* res2, double* outmax) {
+  if (njobs < 1 || njobs > 65535 || !m || !done || !want || !p || !res2 || !outmax) HS_FAIL(HS_ERR_ARGUMENT, njobs, "hsk_qr_select: njobs in [1, 65535] and non-null arrays required");
+  size_t tot = 0;
+  for (int64_t a = 0; a < njobs; ++a) {
+    if (m[a] < 1 || done[a] < 0 || done[a] > m[a] || want[a] < 1 || want[a] > HS_QW)
+      HS_FAIL(HS_ERR_ARGUMENT, a, "hsk_qr_select: job %lld has m = %d, done = %d, want = %d", (long long)a, m[a], done[a], want[a]);
+    for (int i = 0; i < m[a]; ++i)
+      if (p[tot + i] < 0 || p[tot + i] >= m[a]) HS_FAIL(HS_ERR_ARGUMENT, a, "hsk_qr_select: job %lld: p[%d] = %d is outside 0 .. m - 1", (long long)a, i, p[tot + i]);
+    tot += (size_t)m[a];
+  }
+  qr_need_device();
+  HsDevBuf buf("hsk_qr_select");
+  int32_t* dp = qr_put(buf, p, tot);
+  int32_t* dtmp = buf.get<int32_t>(tot);
+  double* dres = qr_put(buf, res2, tot);
+  double* dmax = qr_put(buf, outmax, 2 * (size_t)njobs);
+  std::vector<SelJob> sj;
+  size_t off = 0;
+  for (int64_t a = 0; a < njobs; ++a) {
+    sj.push_back(SelJob{(int*)dp + off, (int*)dtmp + off, dres + off, dmax + 2 * a, done[a], m[a], want[a]});
+    off += (size_t)m[a];
+  }
+  SelJob* dsj = qr_put(buf, sj.data(), sj.size());
+  launch_select(dsj, (unsigned)njobs, 0);
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipDeviceSynchronize());
+  qr_bring(p, dp, tot);
+  qr_bring(outmax, dmax, 2 * (size_t)njobs);
+}
+
+// Packing (job a): M at sum m*q, p and d at sum m, T ((m - r) x r, column-major, leading dimension m - r) at sum m*min(m, q), blocks
+// (offset, width pairs) at 2 * sum m.
+template <class T>
+void qr_refine_hook(int64_t njobs, const int32_t* m, const int32_t* q, const T* M, int32_t* p, const int32_t* rmax, const double* atol_scale, const double* floor_abs,
+                    int norm_select, double atol, double rtol, double scale_floor, int32_t* r, double* top, double* d, T* Tout, int32_t* blocks, int32_t* nblocks,
+                    int64_t* counters) {
+  if (njobs < 1 || njobs > 4096 || !m || !q || !M || !p || !rmax || !atol_scale || !floor_abs || !r || !top || !d || !Tout || !blocks || !nblocks || !counters)
+    HS_FAIL(HS_ERR_ARGUMENT, njobs, "hsk_qr_refine: njobs in [1, 4096] and non-null arrays required");
+  size_t totm = 0;
+  for (int64_t a = 0; a < njobs; ++a) {
+    if (m[a] < 1 || q[a] < 1 || m[a] > (1 << 20) || q[a] > (1 << 20)) HS_FAIL(HS_ERR_ARGUMENT, a, "hsk_qr_refine: job %lld has m = %d, q = %d", (long long)a, m[a], q[a]);
+    std::vector<char> seen((size_t)m[a], 0);
+    for (int i = 0; i < m[a]; ++i) {
+      const int v = p[totm + i];
+      if (v < 0 || v >= m[a] || seen[v]) HS_FAIL(HS_ERR_ARGUMENT, a, "hsk_qr_refine: job %lld: p is no permutation of 0 .. m - 1", (long long)a);
+      seen[v] = 1;
+    }
+    totm += (size_t)m[a];
+  }
+  qr_need_device();
+  Pool tmp(global_cache()), keep(global_cache()), in(global_cache());
+  std::vector<QrJob<T>> qj((size_t)njobs);
+  int32_t* dp = in.get<int32_t>(totm);
+  HS_HIP(hipMemcpy(dp, p, sizeof(int32_t) * totm, hipMemcpyHostToDevice));
+  size_t offm = 0, offM = 0;
+  for (int64_t a = 0; a < njobs; ++a) {
+    QrJob<T>& J = qj[a];
+    const int ld = ev(m[a]);
+    T* dM = in.get<T>((size_t)ld * q[a]);
+    HS_HIP(hipMemcpy2D(dM, sizeof(T) * ld, M + offM, sizeof(T) * m[a], sizeof(T) * m[a], q[a], hipMemcpyHostToDevice));
+    J.M = dM;
+    J.ldm = ld;
+    J.m = m[a];
+    J.q = q[a];
+    J.p = (int*)dp + offm;
+    J.rmax = rmax[a];
+    J.atol_scale = atol_scale[a];
+    J.floor_abs = floor_abs[a];
+    J.norm_select = norm_select != 0;
+    offm += (size_t)m[a];
+    offM += (size_t)m[a] * q[a];
+  }
+  QrTrace tr;
+  struct Drain {  // the pools are recycled on scope exit: nothing may be in flight then, on any path
+    ~Drain() { (void)hipDeviceSynchronize(); }
+  } drain;
+  qr_refine<T>(tmp, keep, qj, atol, rtol, scale_floor, 0, &tr);
+  HS_HIP(hipDeviceSynchronize());
+  counters[0] = tr.windows;
+  counters[1] = tr.refreshes;
+  HS_HIP(hipMemcpy(p, dp, sizeof(int32_t) * totm, hipMemcpyDeviceToHost));
+  offm = 0;
+  size_t offT = 0;
+  for (int64_t a = 0; a < njobs; ++a) {
+    const QrJob<T>& J = qj[a];
+    r[a] = J.r;
+    top[a] = J.top;
+    for (int i = 0; i < J.r; ++i) d[offm + i] = tr.d[a][i];
+    nblocks[a] = (int32_t)tr.blocks[a].size();
+    for (size_t i = 0; i < tr.blocks[a].size(); ++i) {
+      blocks[2 * offm + 2 * i] = tr.blocks[a][i].first;
+      blocks[2 * offm + 2 * i + 1] = tr.blocks[a][i].second;
+    }
+    const int nR = J.m - J.r;
+    if (nR > 0 && J.r > 0) HS_HIP(hipMemcpy2D(Tout + offT, sizeof(T) * nR, J.Tm, sizeof(T) * J.ldt, sizeof(T) * nR, J.r, hipMemcpyDeviceToHost));
+    offm += (size_t)m[a];
+    offT += (size_t)m[a] * std::min(m[a], q[a]);
+  }
+}
+}  // namespace
+
+extern "C" int hsk_qr_params(double* out4) {
+  if (!out4) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hsk_qr_params: out4 == NULL");
+    return HS_ERR_ARGUMENT;
+  }
+  out4[0] = HS_QW;
+  out4[1] = qr_chol_cond();
+  out4[2] = qr_theta();
+  out4[3] = noise_rel();
+  return HS_OK;
+}
+extern "C" int hsk_qr_chol_d(int64_t njobs, const int32_t* b, const int32_t* first, const double* G, const double* thr, double* top, int32_t* p, double* L, double* Linv,
+                             double* LinvP, double* d, int32_t* lperm, int32_t* nacc) {
+  HS_GUARD(qr_chol_hook<double>(njobs, b, first, G, thr, top, p, L, Linv, LinvP, d, lperm, nacc));
+}
+extern "C" int hsk_qr_chol_z(int64_t njobs, const int32_t* b, const int32_t* first, const double* G, const double* thr, double* top, int32_t* p, double* L, double* Linv,
+                             double* LinvP, double* d, int32_t* lperm, int32_t* nacc) {
+  HS_GUARD(qr_chol_hook<cplx>(njobs, b, first, (const cplx*)G, thr, top, p, (cplx*)L, (cplx*)Linv, (cplx*)LinvP, d, lperm, nacc));
+}
+extern "C" int hsk_qr_select(int64_t njobs, const int32_t* m, const int32_t* done, const int32_t* want, int32_t* p, const double* res2, double* outmax) {
+  HS_GUARD(qr_select_hook(njobs, m, done, want, p, res2, outmax));
+}
+extern "C" int hsk_qr_refine_d(int64_t njobs, const int32_t* m, const int32_t* q, const double* M, int32_t* p, const int32_t* rmax, const double* atol_scale,
+                               const double* floor_abs, int norm_select, double atol, double rtol, double scale_floor, int32_t* r, double* top, double* d, double* T,
+                               int32_t* blocks, int32_t* nblocks, int64_t* counters) {
+  HS_GUARD(qr_refine_hook<double>(njobs, m, q, M, p, rmax, atol_scale, floor_abs, norm_select, atol, rtol, scale_floor, r, top, d, T, blocks, nblocks, counters));
+}
+extern "C" int hsk_qr_refine_z(int64_t njobs, const int32_t* m, const int32_t* q, const double* M, int32_t* p, const int32_t* rmax, const double* atol_scale,
+                               const double* floor_abs, int norm_select, double atol, double rtol, double scale_floor, int32_t* r, double* top, double* d, double* T,
+                               int32_t* blocks, int32_t* nblocks, int64_t* counters) {
+  HS_GUARD(qr_refine_hook<cplx>(njobs, m, q, (const cplx*)M, p, rmax, atol_scale, floor_abs, norm_select, atol, rtol, scale_floor, r, top, d, (cplx*)T, blocks, nblocks,
+                                counters));
 }

@@ -98,6 +98,34 @@ int hsk_lowrank_d(int64_t rows, int64_t cols, const double* X, double atol, doub
 int hsk_lowrank_z(int64_t rows, int64_t cols, const double* X, double atol, double rtol, int64_t kinit, int64_t seed,
                   int64_t* r_out, double* Cout, double* Zout, int64_t cap);
 
+/* The rank-revealing orthogonalisation behind every HSS rank and interpolation matrix (qr_refine, csrc/hs_hss.hip), piece by piece
+ * (tests/qr_mirror.py restates it; tests/test_qr_refine_gpu.py).  W = 64 below is the window width hsk_qr_params reports.
+ *   hsk_qr_params : out4 = window width (HS_QW), conditioning cut-off (HS_CHOL_COND), theta (HS_QR_THETA), noise_rel (HS_NOISE_REL) as this
+ *                   process runs them.  Host only.
+ *   hsk_qr_chol_* : chol_block_kernel on njobs windows in one launch.  Per job a: b[a] in 1..W candidates, their Gram matrix G + a*W*W
+ *                   (column-major, leading dimension W), first[a], thr + 5*a = (atol [already times atol_scale], rtol, scale_floor, floor_abs,
+ *                   next2 [negative: none]), top[a] (read when first[a] == 0, written when it is not), p + a*W (b candidates, re-ordered in
+ *                   place: accepted first).  Outputs, W x W each with leading dimension W: L, Linv, LinvP; d + a*W, lperm + a*W, nacc[a].
+ *                   Every output array is read first: what the kernel does not write comes back as it went in.
+ *   hsk_qr_select : qr_select_kernel on njobs lists in one launch.  Per job: m, done (0..m), want (1..W); p (m entries of 0..m-1) and res2
+ *                   (m doubles) packed one job after another; outmax + 2*a.
+ *   hsk_qr_refine_* : one qr_refine call on njobs blocks.  Packed one job after another: M (m x q column-major, leading dimension m), p and d
+ *                   (m entries per job; p a permutation of 0..m-1, with norm_select the identity), T ((m - r) x r column-major, leading
+ *                   dimension m - r, in a slot of m * min(m, q)), blocks ((offset, width) pairs in a slot of 2*m ints), nblocks[a].
+ *                   counters[0] = windows run, counters[1] = residual-norm recomputations, over the whole call. */
+int hsk_qr_params(double* out4);
+int hsk_qr_chol_d(int64_t njobs, const int32_t* b, const int32_t* first, const double* G, const double* thr, double* top, int32_t* p, double* L,
+                  double* Linv, double* LinvP, double* d, int32_t* lperm, int32_t* nacc);
+int hsk_qr_chol_z(int64_t njobs, const int32_t* b, const int32_t* first, const double* G, const double* thr, double* top, int32_t* p, double* L,
+                  double* Linv, double* LinvP, double* d, int32_t* lperm, int32_t* nacc);
+int hsk_qr_select(int64_t njobs, const int32_t* m, const int32_t* done, const int32_t* want, int32_t* p, const double* res2, double* outmax);
+int hsk_qr_refine_d(int64_t njobs, const int32_t* m, const int32_t* q, const double* M, int32_t* p, const int32_t* rmax, const double* atol_scale,
+                    const double* floor_abs, int norm_select, double atol, double rtol, double scale_floor, int32_t* r, double* top, double* d,
+                    double* T, int32_t* blocks, int32_t* nblocks, int64_t* counters);
+int hsk_qr_refine_z(int64_t njobs, const int32_t* m, const int32_t* q, const double* M, int32_t* p, const int32_t* rmax, const double* atol_scale,
+                    const double* floor_abs, int norm_select, double atol, double rtol, double scale_floor, int32_t* r, double* top, double* d,
+                    double* T, int32_t* blocks, int32_t* nblocks, int64_t* counters);
+
 /* The tall-skinny panel product of the block solves (kernels_solve_multi.hip) on host data: C = A X (minus == 0) or C = C - A X, A M x K
  * (column-major, lda), X K x kc and C M x kc column-major with kc in 1..64 (they reach the kernel row-major with a pitch of 64, as the work
  * blocks of hs_ldiv_block_* do).  trap != 0: A stands for its unit lower trapezoid.  map (NULL: none): M entries in 0..M-1, row i of the
