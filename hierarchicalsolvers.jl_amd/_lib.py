@@ -52,7 +52,7 @@ class hs_sparse_dev(C.Structure):
 
 
 class hs_block_arg(C.Structure):
-    """An n x nrhs block of ``hs_sens_*`` / ``hs_misfit_*``: dense (``dense``, ``ld``) or, with ``dense`` NULL, 1-based CSC."""
+    """An n x nrhs block of ``hs_sens_*`` / ``hs_misfit_*`` / ``hs_tangent_*`` / ``hs_gn_*``: dense (``dense``, ``ld``) or, with ``dense`` NULL, 1-based CSC."""
     _fields_ = [("dense", C.c_void_p), ("ld", i64), ("colptr", p_i64), ("rowval", p_i64), ("nzval", C.c_void_p)]
 
 
@@ -91,6 +91,8 @@ EXPORTS = [
     "hs_interface_solve_d", "hs_interface_solve_z", "hs_interface_solve_dev_d", "hs_interface_solve_dev_z",
     "hs_interface_expand_d", "hs_interface_expand_z", "hs_interface_expand_dev_d", "hs_interface_expand_dev_z",
     "hs_sens_d", "hs_sens_z", "hs_sens_dev_d", "hs_sens_dev_z", "hs_misfit_d", "hs_misfit_z", "hs_misfit_dev_d", "hs_misfit_dev_z", "hs_sens_info", "hsk_sddmm_d", "hsk_sddmm_z",
+    "hs_tangent_d", "hs_tangent_z", "hs_tangent_dev_d", "hs_tangent_dev_z", "hs_gn_hessvec_d", "hs_gn_hessvec_z", "hs_gn_hessvec_dev_d", "hs_gn_hessvec_dev_z",
+    "hs_gn_diag_d", "hs_gn_diag_z", "hs_gn_diag_dev_d", "hs_gn_diag_dev_z", "hs_gn_info", "hsk_gn_rhs_d", "hsk_gn_rhs_z", "hsk_gn_rowsq_d", "hsk_gn_rowsq_z",
     "hs_mod_create_d", "hs_mod_create_z", "hs_mod_create_dev_d", "hs_mod_create_dev_z", "hs_mod_create_sparse_d", "hs_mod_create_sparse_z", "hs_mod_ldiv_d", "hs_mod_ldiv_z",
     "hs_mod_ldiv_dev_d", "hs_mod_ldiv_dev_z", "hs_mod_info", "hs_mod_free", "hs_gmres_block_mod_d", "hs_gmres_block_mod_z",
     "hs_eigs_d", "hs_eigs_z", "hs_eigs_info", "hs_eigs_gen_d", "hs_eigs_gen_z", "hs_eigs_gen_info", "hsk_eigs_coldot_d", "hsk_eigs_coldot_z", "hsk_eigs_rotate_d", "hsk_eigs_rotate_z", "hsk_eigs_chol_inv_d", "hsk_eigs_chol_inv_z", "hsk_small_eig_z", "hsk_eigs_phase_timing", "hsk_eigs_phases", "hsk_eigs_gen_mprod_seconds",
@@ -237,6 +239,35 @@ def lib():
     L.hs_sens_info.restype = C.c_int
     for f in (L.hsk_sddmm_d, L.hsk_sddmm_z):
         f.argtypes = [i64, p_i64, p_i64, i64, vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, p_f64]
+        f.restype = C.c_int
+    # (F, trans, n, nrhs, B, Xin, ldxin, E, pattern, itmax, rows, nrows, dX, lddx, X, ldx)
+    for f in (L.hs_tangent_d, L.hs_tangent_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, vp, i64, vp, C.c_int, i64, p_i64, i64, vp, i64, vp, i64]
+        f.restype = C.c_int
+    for f in (L.hs_tangent_dev_d, L.hs_tangent_dev_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, vp, i64, vp, C.c_int, i64, p_i64, i64, vp, i64, vp, i64, vp]
+        f.restype = C.c_int
+    # (..., rows, nrows, HE, JE, ldje, X, ldx)
+    for f in (L.hs_gn_hessvec_d, L.hs_gn_hessvec_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, vp, i64, vp, C.c_int, i64, p_i64, i64, vp, vp, i64, vp, i64]
+        f.restype = C.c_int
+    for f in (L.hs_gn_hessvec_dev_d, L.hs_gn_hessvec_dev_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, vp, i64, vp, C.c_int, i64, p_i64, i64, vp, vp, i64, vp, i64, vp]
+        f.restype = C.c_int
+    # (F, trans, n, nrhs, B, Xin, ldxin, rows, nrows, pattern, itmax, Hd, z2, x2)
+    for f in (L.hs_gn_diag_d, L.hs_gn_diag_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, vp, i64, p_i64, i64, C.c_int, i64, vp, vp, vp]
+        f.restype = C.c_int
+    for f in (L.hs_gn_diag_dev_d, L.hs_gn_diag_dev_z):
+        f.argtypes = [vp, C.c_int, i64, i64, pb, vp, i64, p_i64, i64, C.c_int, i64, vp, vp, vp, vp]
+        f.restype = C.c_int
+    L.hs_gn_info.argtypes = [vp, p_f64]
+    L.hs_gn_info.restype = C.c_int
+    for f in (L.hsk_gn_rhs_d, L.hsk_gn_rhs_z):
+        f.argtypes = [C.c_int, i64, p_i64, p_i64, vp, C.c_int, vp, i64, i64, vp, i64]
+        f.restype = C.c_int
+    for f in (L.hsk_gn_rowsq_d, L.hsk_gn_rowsq_z):
+        f.argtypes = [i64, i64, vp, i64, vp]
         f.restype = C.c_int
     for f in (L.hs_mod_create_d, L.hs_mod_create_z):
         f.argtypes = [vp, i64, i64, vp, i64, vp, i64, C.POINTER(vp)]

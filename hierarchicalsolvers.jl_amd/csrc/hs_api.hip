@@ -291,6 +291,7 @@ struct hs_handle {
   std::vector<int> sp_owner;  // hs_ldiv_sparse_*: per row the internal node whose int holds it (built by the first call that needs it)
   double sp_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the figures of the last hs_ldiv_sparse_* call
   double sens_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the figures of the last hs_sens_* / hs_misfit_* call (hs_sens.hip)
+  double gn_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // the figures of the last hs_tangent_* / hs_gn_* call (hs_gn.hip)
 };
 
 static inline int rup(int x, int a) { return (x + a - 1) / a * a; }
@@ -1997,6 +1998,7 @@ void hs_handle_view(hs_handle* h, HsHandleView* v) {
 }
 int hs_handle_flow_check(hs_handle* h) { HS_GUARD(flow_check(h)); }
 double* hs_handle_sens_info(hs_handle* h) { return h->sens_info; }  // hs_sens.h
+double* hs_handle_gn_info(hs_handle* h) { return h->gn_info; }      // hs_gn.h
 
 // the handle as hs_selinv.hip sees it (hs_selinv.h): the owned fronts in post-order with the blocks their pivoted LU lives in
 void hs_selinv_view(hs_handle* h, HsSelView* v) {

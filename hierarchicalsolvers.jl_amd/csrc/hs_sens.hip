@@ -34,21 +34,11 @@
 #pragma clang fp contract(off)  // host arithmetic only (no kernel lives here): the plain products and sums
 #include "hs_solve_multi.h"  // hs_ldiv_block_cols
 #include "hs_sens.h"
+#include "hs_sens_solve.h"
 
 namespace {
 
 enum { SI_SECONDS = 0, SI_FORWARD, SI_ADJOINT, SI_REDUCE, SI_GROUPS, SI_PRODUCTS, SI_MOVED, SI_WORK_BYTES };
-
-template <class T>
-struct Blk {  // an n x nrhs block: the values on the device, the index arrays on the host
-  const T* dense = nullptr;
-  int64_t ld = 0;
-  const int64_t* colptr = nullptr;
-  const int64_t* rowval = nullptr;
-  const T* nzval = nullptr;
-  bool sparse() const { return !dense; }
-  int64_t nnz(int64_t c0, int64_t c1) const { return colptr[c1] - colptr[c0]; }
-};
 
 template <class T>
 struct Call {
@@ -74,124 +64,25 @@ struct Call {
 };
 
 template <class T>
-int block_solve(hs_handle* F, int t, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nc, hipStream_t s) {
-  if (sizeof(T) == 16) return hs_ldiv_block_dev_t_z(F, t, (double*)C, ldc, (const double*)B, ldb, n, nc, (void*)s);
-  return hs_ldiv_block_dev_t_d(F, t, (double*)C, ldc, (const double*)B, ldb, n, nc, (void*)s);
-}
-template <class T>
-int sparse_solve(hs_handle* F, int t, int64_t n, int64_t nc, const int64_t* cp, const int64_t* rv, const T* dv, T* X, int64_t ldx, hipStream_t s) {
-  if (sizeof(T) == 16) return hs_ldiv_sparse_dev_z(F, t, n, nc, cp, rv, (const double*)dv, nullptr, 0, (double*)X, ldx, (void*)s);
-  return hs_ldiv_sparse_dev_d(F, t, n, nc, cp, rv, (const double*)dv, nullptr, 0, (double*)X, ldx, (void*)s);
-}
-template <class T>
-int refine_solve(hs_handle* F, int t, T* X, int64_t ldx, const T* B, int64_t ldb, int64_t n, int64_t nc, int64_t itmax, double* berr, int64_t* steps, hipStream_t s) {
-  if (sizeof(T) == 16) return hs_ldiv_refine_block_dev_z(F, t, (double*)X, ldx, (const double*)B, ldb, n, nc, itmax, berr, nullptr, steps, (void*)s);
-  return hs_ldiv_refine_block_dev_d(F, t, (double*)X, ldx, (const double*)B, ldb, n, nc, itmax, berr, nullptr, steps, (void*)s);
-}
-
-// Gc: the widest group (a multiple of the block solve's chunk width) whose blocks fit half of the free memory; HS_SENS_GROUP overrides
-int64_t group_width(size_t per_col, int64_t nrhs) {
-  const int64_t KC = hs_ldiv_block_cols();
-  const int64_t all = std::min<int64_t>((nrhs + KC - 1) / KC * KC, 4096);
-  if (const char* e = getenv("HS_SENS_GROUP")) {
-    const long long w = atoll(e);
-    if (w > 0) return std::min<int64_t>(all, (w + KC - 1) / KC * KC);
-  }
-  size_t fr = 0, tot = 0;
-  HS_HIP(hipMemGetInfo(&fr, &tot));
-  const int64_t fit = (int64_t)(fr / 2 / per_col);
-  if (fit >= all) return all;
-  const int64_t least = std::min<int64_t>(KC, nrhs);
-  if (fit < least)
-    HS_FAIL(HS_ERR_NOMEM, 0, "OutOfMemoryError: hs_sens_* needs %zu bytes for one group of %lld columns, half of the free device memory is %zu bytes",
-            per_col * (size_t)least, (long long)least, fr / 2);
-  return std::max<int64_t>(fit / KC * KC, least);
-}
-
-template <class T>
 struct Driver {
   const Call<T>& c;
   HsDevBuf& buf;
   int64_t n, Gc = 0;
   T* Xg = nullptr;      // n x Gc
   T* Lg = nullptr;      // n x Gc: Lam, or M = conj(Lam) (ComplexF64, trans = 1)
-  T* stage = nullptr;   // n x Gc: the dense right-hand side of a refined solve that is not the caller's block as it stands
-  T* vstage = nullptr;  // conjugated values of a sparse W (ComplexF64, trans = 1, itmax = 0)
-  int32_t* d_er = nullptr;  // entries of a sparse group for the expansion (itmax > 0)
-  int32_t* d_ec = nullptr;
   int32_t* ecol = nullptr;  // the column of every stored entry of A
-  // misfit: the wanted rows in the caller's order (0-based), their slot in ascending order, W's values and W's host index arrays
-  int32_t* d_rows = nullptr;
-  int32_t* d_slot = nullptr;
-  T* Wv = nullptr;
-  std::vector<int64_t> wcp, wrv;
-  std::vector<int64_t> cp;  // rebased column pointers of a sparse group
-  std::vector<int32_t> er, ec;
-  std::vector<double> berr;
-  std::vector<int64_t> steps;
+  HsGroupSolve<T> gs;       // the solve of one group, with its staging (hs_sens_solve.h)
+  HsReceiverRows<T> rr;     // misfit: the receiver rows and the sparse cotangent built on them
 
-  // out (n x gc, ld n) = op_t(F)^-1 S, S = columns [g0, g0 + gc) of b, conjugated when cjin
-  void solve(int t, const Blk<T>& b, int64_t g0, int gc, bool cjin, T* out) {
-    hipStream_t s = c.s;
-    const int64_t off = b.sparse() ? b.colptr[g0] - 1 : 0, cnt = b.sparse() ? b.nnz(g0, g0 + gc) : 0;
-    if (b.sparse()) {
-      cp.resize((size_t)gc + 1);
-      for (int j = 0; j <= gc; ++j) cp[(size_t)j] = b.colptr[g0 + j] - off;
-    }
-    if (c.itmax == 0) {
-      if (!b.sparse()) {
-        const T* src = b.dense + (size_t)g0 * b.ld;
-        if (cjin) {
-          launch_sens_copy<T>(out, n, src, b.ld, n, gc, 1, s);
-          HS_CHECK(block_solve<T>(c.F, t, out, n, out, n, n, gc, s));
-        } else {
-          HS_CHECK(block_solve<T>(c.F, t, out, n, src, b.ld, n, gc, s));
-        }
-        return;
-      }
-      const T* val = b.nzval + off;
-      if (cjin && cnt > 0) {
-        launch_sens_copy<T>(vstage, cnt, val, cnt, cnt, 1, 1, s);
-        val = vstage;
-      }
-      HS_CHECK(sparse_solve<T>(c.F, t, n, gc, cp.data(), b.rowval + off, val, out, n, s));
-      return;
-    }
-    const T* src;
-    int64_t lds;
-    if (!b.sparse() && !cjin) {
-      src = b.dense + (size_t)g0 * b.ld;
-      lds = b.ld;
-    } else {
-      src = stage;
-      lds = n;
-      if (!b.sparse()) {
-        launch_sens_copy<T>(stage, n, b.dense + (size_t)g0 * b.ld, b.ld, n, gc, 1, s);
-      } else {
-        HS_HIP(hipMemsetAsync(stage, 0, (size_t)n * gc * sizeof(T), s));
-        if (cnt > 0) {
-          er.resize((size_t)cnt);
-          ec.resize((size_t)cnt);
-          for (int j = 0; j < gc; ++j)
-            for (int64_t e = cp[(size_t)j] - 1; e < cp[(size_t)j + 1] - 1; ++e) {
-              er[(size_t)e] = (int32_t)(b.rowval[off + e] - 1);
-              ec[(size_t)e] = j;
-            }
-          HS_HIP(hipStreamSynchronize(s));  // the lists of the previous expansion are no longer read
-          HS_HIP(hipMemcpy(d_er, er.data(), (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
-          HS_HIP(hipMemcpy(d_ec, ec.data(), (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
-          launch_sens_expand<T>(stage, n, d_er, d_ec, b.nzval + off, cnt, cjin ? 1 : 0, s);
-        }
-      }
-    }
-    berr.resize((size_t)gc);
-    steps.resize((size_t)gc);
-    HS_CHECK(refine_solve<T>(c.F, t, out, n, src, lds, n, gc, c.itmax, berr.data(), steps.data(), s));
-  }
+  void solve(int t, const Blk<T>& b, int64_t g0, int gc, bool cjin, T* out) { gs.solve(t, b, g0, gc, cjin, out); }
 
   void run(double* info) {
     hipStream_t s = c.s;
     n = c.n;
+    gs.F = c.F;
+    gs.n = n;
+    gs.itmax = c.itmax;
+    gs.s = s;
     const bool cplx_ = sizeof(T) == 16;
     const bool cjw = cplx_ && c.trans == 1;  // the adjoint solve runs on conj(W) and returns conj(Lam)
     const int tadj = c.trans == 0 ? 2 : 0;
@@ -204,10 +95,10 @@ struct Driver {
     const bool wsparse = c.misfit || c.W.sparse();
     const bool need_stage = c.itmax > 0 && (c.B.sparse() || wsparse || cjw);
     const size_t per_col = (size_t)n * sizeof(T) * (need_stage ? 3 : 2) + (c.misfit ? (size_t)c.nrows * sizeof(T) : 0);
-    Gc = std::min<int64_t>(group_width(per_col, c.nrhs), c.nrhs);
+    Gc = std::min<int64_t>(group_width(per_col, c.nrhs, "HS_SENS_GROUP", "hs_sens_*"), c.nrhs);
     Xg = buf.get<T>((size_t)n * Gc);
     Lg = buf.get<T>((size_t)n * Gc);
-    if (need_stage) stage = buf.get<T>((size_t)n * Gc);
+    if (need_stage) gs.stage = buf.get<T>((size_t)n * Gc);
     size_t extra = 0;
     int64_t maxw = 0, maxe = 0;  // the most stored entries a group of W / of either block holds
     for (int64_t g0 = 0; g0 < c.nrhs; g0 += Gc) {
@@ -218,12 +109,12 @@ struct Driver {
     if (c.misfit) maxw = c.nrows * Gc;
     maxe = std::max(maxe, maxw);
     if (cjw && !c.misfit && c.W.sparse() && c.itmax == 0) {
-      vstage = buf.get<T>((size_t)maxw);
+      gs.vstage = buf.get<T>((size_t)maxw);
       extra += (size_t)maxw * sizeof(T);
     }
     if (c.itmax > 0 && (c.B.sparse() || wsparse)) {
-      d_er = buf.get<int32_t>((size_t)maxe);
-      d_ec = buf.get<int32_t>((size_t)maxe);
+      gs.d_er = buf.get<int32_t>((size_t)maxe);
+      gs.d_ec = buf.get<int32_t>((size_t)maxe);
       extra += (size_t)maxe * 2 * sizeof(int32_t);
     }
     if (c.pattern == 0) {
@@ -231,33 +122,7 @@ struct Driver {
       extra += (size_t)nnz * sizeof(int32_t);
       launch_sens_entry_cols(c.v.colptr, n, nnz, ecol, s);
     }
-    Blk<T> Wm;
-    if (c.misfit) {
-      const int64_t nr = c.nrows;
-      std::vector<int32_t> r0((size_t)nr), slot((size_t)nr), ord((size_t)nr);
-      std::iota(ord.begin(), ord.end(), 0);
-      std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return c.rows[a] < c.rows[b]; });
-      for (int64_t q = 0; q < nr; ++q) {
-        r0[(size_t)q] = (int32_t)(c.rows[q] - 1);
-        slot[(size_t)ord[(size_t)q]] = (int32_t)q;
-      }
-      wcp.resize((size_t)Gc + 1);
-      wrv.resize((size_t)(Gc * nr));
-      for (int64_t j = 0; j <= Gc; ++j) wcp[(size_t)j] = 1 + j * nr;
-      for (int64_t j = 0; j < Gc; ++j)
-        for (int64_t q = 0; q < nr; ++q) wrv[(size_t)(j * nr + q)] = c.rows[ord[(size_t)q]];
-      d_rows = buf.get<int32_t>((size_t)nr);
-      d_slot = buf.get<int32_t>((size_t)nr);
-      Wv = buf.get<T>((size_t)(nr * Gc));
-      extra += (size_t)nr * 2 * sizeof(int32_t);
-      if (nr > 0) {
-        HS_HIP(hipMemcpy(d_rows, r0.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice));
-        HS_HIP(hipMemcpy(d_slot, slot.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice));
-      }
-      Wm.colptr = wcp.data();
-      Wm.rowval = wrv.data();
-      Wm.nzval = Wv;
-    }
+    if (c.misfit) extra += rr.setup(c.rows, c.nrows, Gc, buf);
     info[SI_WORK_BYTES] = (double)(per_col * (size_t)Gc + extra);
 
     HsSddmmFlags fl;
@@ -273,11 +138,11 @@ struct Driver {
       HS_HIP(hipEventRecord(ev[1], s));
       if (c.dX) HS_HIP(hipMemcpy2DAsync(c.dX + (size_t)g0 * c.ldx, c.ldx * sizeof(T), Xg, n * sizeof(T), n * sizeof(T), gc, hipMemcpyDeviceToDevice, s));
       if (c.misfit)
-        launch_sens_misfit<T>(Xg, n, d_rows, d_slot, c.dD + (size_t)g0 * c.ldd, c.ldd, c.nrows, gc, c.dR ? c.dR + (size_t)g0 * c.ldr : nullptr, c.ldr, Wv, cjw ? 1 : 0,
+        launch_sens_misfit<T>(Xg, n, rr.d_rows, rr.d_slot, c.dD + (size_t)g0 * c.ldd, c.ldd, c.nrows, gc, c.dR ? c.dR + (size_t)g0 * c.ldr : nullptr, c.ldr, rr.Wv, cjw ? 1 : 0,
                               c.dJ + g0, s);
       HS_HIP(hipEventRecord(ev[2], s));
       if (c.misfit)
-        solve(tadj, Wm, 0, gc, false, Lg);  // the conjugation is in Wv already
+        solve(tadj, rr.W, 0, gc, false, Lg);  // the conjugation is in Wv already
       else
         solve(tadj, c.W, g0, gc, cjw, Lg);
       HS_HIP(hipEventRecord(ev[3], s));
@@ -300,76 +165,6 @@ struct Driver {
     }
   }
 };
-
-// ---- refusals: before any device work, every output untouched ------------------------------------------------------------------------
-template <class T>
-void check_block(hs_handle* F, int trans, const char* fn, const char* name, const hs_block_arg* b, int64_t n, int64_t nrhs) {
-  if (!b) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s == NULL", fn, name);
-  if (nrhs == 0) return;
-  if (b->dense) {
-    if (b->ld < n) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the leading dimension of %s is %lld, it has %lld rows", fn, name, (long long)b->ld, (long long)n);
-    return;
-  }
-  if (!b->colptr) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s has neither dense values nor a colptr", fn, name);
-  // the rules of hs_ldiv_sparse_* through its own host-only check
-  const int st = hs_ldiv_sparse_plan(F, trans, n, nrhs, b->colptr, b->rowval, nullptr, 0, nullptr, nullptr, nullptr);
-  if (st != HS_OK) {
-    const std::string why = hs_last_error();
-    hs_set_error(st, hs_last_error_info(), "%s: %s is not a valid sparse block (%s)", fn, name, why.c_str());
-    throw st;
-  }
-  if (b->colptr[nrhs] > 1 && !b->nzval) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: %s has stored entries and nzval == NULL", fn, name);
-}
-
-template <class T>
-void check_common(hs_handle* F, const char* fn, int trans, int64_t n, int64_t nrhs, int64_t itmax, int pattern, HsHandleView* v) {
-  *v = hs_view_of(F, fn);
-  if ((v->is_complex != 0) != (sizeof(T) == 16)) HS_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and of the blocks differ", fn);
-  hs_check_trans(fn, trans);
-  if (pattern < 0 || pattern > 1) HS_FAIL(HS_ERR_ARGUMENT, pattern, "ArgumentError: %s: pattern = %d (0: the stored entries of A, 1: the diagonal)", fn, pattern);
-  if (itmax < 0) HS_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: %s: itmax = %lld < 0", fn, (long long)itmax);
-  if (!v->device) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
-  if (!v->factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
-  {  // what hs_ldiv_block_t_* refuses is refused here, by its own check: a block solve of no columns
-    const int st = block_solve<T>(F, trans, nullptr, v->n, nullptr, v->n, v->n, 0, nullptr);
-    if (st != HS_OK) {
-      const std::string why = hs_last_error();
-      hs_set_error(st, hs_last_error_info(), "%s: the block solve does not serve this handle (%s)", fn, why.c_str());
-      throw st;
-    }
-  }
-  if (n != v->n || nrhs < 0)
-    HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the blocks have %lld rows and %lld columns, F is %lld x %lld", fn, (long long)n, (long long)nrhs, (long long)v->n,
-            (long long)v->n);
-}
-
-template <class T>
-void to_blk(const hs_block_arg* a, Blk<T>* b) {
-  b->dense = (const T*)a->dense;
-  b->ld = a->ld;
-  b->colptr = a->colptr;
-  b->rowval = a->rowval;
-  b->nzval = (const T*)a->nzval;
-}
-// a host block on the device: dense with ld = n, or the stored values
-template <class T>
-void upload(const hs_block_arg* a, int64_t n, int64_t nrhs, Blk<T>* b, HsDevBuf& buf, hipStream_t s, double* moved) {
-  to_blk<T>(a, b);
-  if (nrhs == 0) return;
-  if (a->dense) {
-    T* d = buf.get<T>((size_t)n * nrhs);
-    HS_HIP(hipMemcpy2DAsync(d, n * sizeof(T), a->dense, a->ld * sizeof(T), n * sizeof(T), nrhs, hipMemcpyHostToDevice, s));
-    b->dense = d;
-    b->ld = n;
-    *moved += (double)n * nrhs;
-  } else {
-    const int64_t cnt = a->colptr[nrhs] - 1;
-    T* d = buf.get<T>((size_t)cnt);
-    if (cnt > 0) HS_HIP(hipMemcpyAsync(d, a->nzval, (size_t)cnt * sizeof(T), hipMemcpyHostToDevice, s));
-    b->nzval = d;
-    *moved += (double)cnt;
-  }
-}
 
 void finish(hs_handle* F, const double* info) { memcpy(hs_handle_sens_info(F), info, 8 * sizeof(double)); }
 
@@ -427,14 +222,7 @@ void misfit_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_blo
   if (!G || (nrows > 0 && !rows) || (nrhs > 0 && !J) || (nrows > 0 && nrhs > 0 && !D)) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: G, rows, D and J must not be NULL", fn);
   if (ldd < nrows || (R && ldr < nrows))
     HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldd = %lld, ldr = %lld, D and R have %lld rows", fn, (long long)ldd, (long long)ldr, (long long)nrows);
-  {
-    std::vector<unsigned char> seen((size_t)n, 0);
-    for (int64_t q = 0; q < nrows; ++q) {
-      if (rows[q] < 1 || rows[q] > n) HS_FAIL(HS_ERR_DIMENSION, q, "BoundsError: %s: rows[%lld] = %lld outside 1:%lld", fn, (long long)q + 1, (long long)rows[q], (long long)n);
-      if (seen[(size_t)(rows[q] - 1)]) HS_FAIL(HS_ERR_ARGUMENT, q, "ArgumentError: %s: row %lld is listed twice (the receiver rows must be distinct)", fn, (long long)rows[q]);
-      seen[(size_t)(rows[q] - 1)] = 1;
-    }
-  }
+  check_rows(fn, rows, nrows, n);
   c.F = F; c.trans = trans; c.pattern = pattern; c.n = n; c.nrhs = nrhs; c.itmax = itmax;
   c.misfit = true; c.rows = rows; c.nrows = nrows;
   double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};

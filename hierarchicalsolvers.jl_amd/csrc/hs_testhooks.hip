@@ -1111,6 +1111,94 @@ extern "C" int hsk_sddmm_z(int64_t n, const int64_t* colptr, const int64_t* rowv
   HS_GUARD(sddmm_hook<cplx>(n, colptr, rowval, kc, (const cplx*)L, ldl, (const cplx*)R, ldr, swap, conjl, conjr, diag, form, (cplx*)G, seconds));
 }
 
+// hsk_gn_rhs_*, hsk_gn_rowsq_*: the right-hand side and row square sum kernels of hs_tangent_* / hs_gn_* (kernels_gn.hip) alone on host data
+#include "hs_gn.h"
+template <class T>
+static void gn_rhs_hook(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const T* E, int pattern, const T* X, int64_t ldx, int64_t kc, T* P, int64_t ldp) {
+  if (trans < 0 || trans > 2 || pattern < 0 || pattern > 1 || n < 1 || n > 0x7fffffff || kc < 1 || kc > 4096 || !colptr || !E || !X || !P || ldx < n || ldp < n ||
+      colptr[0] != 1)
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_gn_rhs: trans in 0:2, pattern in 0:1, n >= 1, kc in 1..4096, 1-based colptr, leading dimensions >= n and non-null arrays required");
+  const int64_t nnz = colptr[n] - 1;
+  std::vector<int64_t> cp((size_t)n + 1), rp((size_t)n + 1, 0), tp((size_t)std::max<int64_t>(nnz, 0));
+  std::vector<int32_t> rv((size_t)std::max<int64_t>(nnz, 0)), ci((size_t)std::max<int64_t>(nnz, 0));
+  bool ok = nnz >= 0 && (nnz == 0 || rowval);
+  for (int64_t j = 0; ok && j <= n; ++j) {
+    cp[(size_t)j] = colptr[j] - 1;
+    ok = j == 0 || cp[(size_t)j] >= cp[(size_t)j - 1];
+  }
+  for (int64_t j = 0; ok && j < n; ++j)
+    for (int64_t e = cp[(size_t)j]; ok && e < cp[(size_t)j + 1]; ++e) {
+      ok = rowval[e] >= 1 && rowval[e] <= n && (e == cp[(size_t)j] || rowval[e] > rowval[e - 1]);
+      rv[(size_t)e] = (int32_t)(rowval[e] - 1);
+    }
+  if (!ok) HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_gn_rhs: colptr decreases, rowval is outside 1:n or the rows of a column do not ascend");
+  // the CSR map: rows in column order, CSR entry -> CSC entry
+  for (int64_t e = 0; e < nnz; ++e) ++rp[(size_t)rv[(size_t)e] + 1];
+  for (int64_t i = 0; i < n; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
+  {
+    std::vector<int64_t> cur(rp.begin(), rp.end() - 1);
+    for (int64_t j = 0; j < n; ++j)
+      for (int64_t e = cp[(size_t)j]; e < cp[(size_t)j + 1]; ++e) {
+        const int64_t at = cur[(size_t)rv[(size_t)e]]++;
+        ci[(size_t)at] = (int32_t)j;
+        tp[(size_t)at] = e;
+      }
+  }
+  need_device();
+  const int64_t elen = pattern == 0 ? nnz : n;
+  HsDevBuf b("hsk_gn_rhs");
+  int64_t* dcp = b.get<int64_t>((size_t)(n + 1));
+  int64_t* drp = b.get<int64_t>((size_t)(n + 1));
+  int64_t* dtp = b.get<int64_t>((size_t)nnz);
+  int32_t* drv = b.get<int32_t>((size_t)nnz);
+  int32_t* dci = b.get<int32_t>((size_t)nnz);
+  T* dE = b.get<T>((size_t)elen);
+  T* dX = b.get<T>((size_t)ldx * kc);
+  T* dP = b.get<T>((size_t)ldp * kc);
+  HS_HIP(hipMemcpy(dcp, cp.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(drp, rp.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+  if (nnz > 0) {
+    HS_HIP(hipMemcpy(dtp, tp.data(), sizeof(int64_t) * (size_t)nnz, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(drv, rv.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(dci, ci.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+  }
+  if (elen > 0) HS_HIP(hipMemcpy(dE, E, sizeof(T) * (size_t)elen, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * kc, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(dP, P, sizeof(T) * (size_t)ldp * kc, hipMemcpyHostToDevice));
+  const int cjE = (sizeof(T) == 16 && trans == 2) ? 1 : 0;
+  if (pattern == 1)
+    launch_gn_rhs_diag<T>(dcp, drv, dE, cjE, n, dX, ldx, (int)kc, dP, ldp, 0);
+  else if (trans == 0)
+    launch_gn_rhs<T>(HsGnRows{drp, dci, dtp, 0}, dE, n, dX, ldx, (int)kc, dP, ldp, 0);
+  else
+    launch_gn_rhs<T>(HsGnRows{dcp, drv, nullptr, cjE}, dE, n, dX, ldx, (int)kc, dP, ldp, 0);
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(P, dP, sizeof(T) * (size_t)ldp * kc, hipMemcpyDeviceToHost));
+}
+extern "C" int hsk_gn_rhs_d(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* E, int pattern, const double* X, int64_t ldx, int64_t kc,
+                            double* P, int64_t ldp) {
+  HS_GUARD(gn_rhs_hook<double>(trans, n, colptr, rowval, E, pattern, X, ldx, kc, P, ldp));
+}
+extern "C" int hsk_gn_rhs_z(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* E, int pattern, const double* X, int64_t ldx, int64_t kc,
+                            double* P, int64_t ldp) {
+  HS_GUARD(gn_rhs_hook<cplx>(trans, n, colptr, rowval, (const cplx*)E, pattern, (const cplx*)X, ldx, kc, (cplx*)P, ldp));
+}
+template <class T>
+static void gn_rowsq_hook(int64_t n, int64_t kc, const T* X, int64_t ldx, double* acc) {
+  if (n < 1 || kc < 1 || kc > 4096 || !X || !acc || ldx < n) HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_gn_rowsq: n >= 1, kc in 1..4096, ldx >= n and non-null arrays required");
+  need_device();
+  HsDevBuf b("hsk_gn_rowsq");
+  T* dX = b.get<T>((size_t)ldx * kc);
+  double* da = b.get<double>((size_t)n);
+  HS_HIP(hipMemcpy(dX, X, sizeof(T) * (size_t)ldx * kc, hipMemcpyHostToDevice));
+  HS_HIP(hipMemcpy(da, acc, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  launch_gn_rowsq<T>(dX, ldx, n, (int)kc, da, 0);
+  HS_HIP(hipDeviceSynchronize());
+  HS_HIP(hipMemcpy(acc, da, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+}
+extern "C" int hsk_gn_rowsq_d(int64_t n, int64_t kc, const double* X, int64_t ldx, double* acc) { HS_GUARD(gn_rowsq_hook<double>(n, kc, X, ldx, acc)); }
+extern "C" int hsk_gn_rowsq_z(int64_t n, int64_t kc, const double* X, int64_t ldx, double* acc) { HS_GUARD(gn_rowsq_hook<cplx>(n, kc, (const cplx*)X, ldx, acc)); }
+
 #include "hs_envelope.h"
 extern "C" int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL,
                                  int32_t* firstU) {

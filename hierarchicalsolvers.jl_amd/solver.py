@@ -35,7 +35,7 @@ from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
            "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info",
-           "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "eigs", "eigs_info", "eigs_gen_info", "interface_indices", "schur_complement", "condense", "interface_solve", "expand", "interface_info"]
+           "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "tangent", "gn_hessvec", "gn_diag", "gn_info", "eigs", "eigs_info", "eigs_gen_info", "interface_indices", "schur_complement", "condense", "interface_solve", "expand", "interface_info"]
 
 
 class SolverOptions:
@@ -1120,6 +1120,137 @@ def sens_info(F):
     _lib.check(_lib.lib().hs_sens_info(F._h, _pf64(out)))
     return {"seconds": float(out[0]), "seconds_forward": float(out[1]), "seconds_adjoint": float(out[2]), "seconds_reduce": float(out[3]),
             "groups": int(out[4]), "products": int(out[5]), "values_moved": int(out[6]), "workspace_bytes": int(out[7])}
+
+
+def _gn_inputs(fname, F, B, X, itmax, pattern):
+    """The arguments :func:`tangent`, :func:`gn_hessvec` and :func:`gn_diag` share: ``(Fn, trans, h, n, dtype, pcode, argB or None, k, Xin or
+    None, keep-alive objects)``.  ``X`` (the fields of an earlier call) replaces ``B``, which may then be ``None``."""
+    Fn, trans, h, n, dtype = _sens_handle(F)
+    pcode = _sens_pattern(pattern)
+    if int(itmax) != itmax:
+        raise TypeError("itmax must be an integer")
+    if B is None and X is None:
+        raise ValueError(f"ArgumentError: {fname}: B and X are both None")
+    argB, k, keep, Xin = None, None, (), None
+    if B is not None:
+        argB, k, keep = _sens_block("B", B, n, dtype)
+    if X is not None:
+        Xin = np.asarray(X)
+        if Xin.ndim == 1:
+            Xin = Xin.reshape(-1, 1)
+        if Xin.ndim != 2 or Xin.shape[0] != n or (k is not None and Xin.shape[1] != k):
+            raise _lib.DimensionMismatch(f"DimensionMismatch: X has shape {Xin.shape}, expected {(n, k if k is not None else Xin.shape[-1])}")
+        if Xin.dtype != dtype:
+            if dtype.kind == "f" and Xin.dtype.kind == "c":
+                raise TypeError(f"MethodError: no method matching {fname}(::FactorNode{{Float64}}, X::Array{{ComplexF64}})")
+            Xin = Xin.astype(dtype)
+        Xin = np.asfortranarray(Xin)
+        k = Xin.shape[1]
+    return Fn, trans, h, n, dtype, pcode, argB, k, Xin, keep
+
+
+def _gn_direction(fname, E, length, dtype):
+    E = np.asarray(E).reshape(-1)
+    if E.shape != (length,):
+        raise _lib.DimensionMismatch(f"DimensionMismatch: E has {E.size} values, expected {length}")
+    if E.dtype != dtype:
+        if dtype.kind == "f" and E.dtype.kind == "c":
+            raise TypeError(f"MethodError: no method matching {fname}(::FactorNode{{Float64}}, E::Vector{{ComplexF64}})")
+        E = E.astype(dtype)
+    return np.ascontiguousarray(E)
+
+
+def _gn_rows(rows, n):
+    rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= n):
+        raise _lib.DimensionMismatch(f"BoundsError: rows outside 0:{n - 1}")
+    return rows + 1
+
+
+def _gn_want(want, allowed):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for w in want:
+        if w not in allowed:
+            raise ValueError("ArgumentError: want may name " + " and ".join(repr(a) for a in allowed) + f", not {w!r}")
+    return want
+
+
+def tangent(F, B, E, rows=None, itmax=0, pattern="A", X=None, want=()):
+    """Tangent-linear (Born) solve (``hs_tangent_*``): with ``op(A)`` as in :func:`sensitivity`, ``X = op(A)^-1 B`` and ``E`` a perturbation of
+    the stored entries of ``A`` (aligned with the ``data`` of the factored matrix; ``n`` diagonal values for ``pattern="diag"``), returns
+    ``dX = d/ds op(A + sE)^-1 B`` at ``s = 0``, i.e. ``-op(A)^-1 op(E) X``: ``n x k``, or the rows ``rows`` (distinct 0-based indices, any
+    order) of it.  It is the forward mode of :func:`sensitivity`: ``Re<W, dX> = Re sum(E * conj(G))`` for that function's ``G``.  ``X=`` takes
+    the fields of an earlier call (``want="X"``) and skips the forward solve; ``B`` may then be ``None``.  ``want`` may name ``"X"``: the result
+    is then ``(dX, X)``.  Blocks, dtype rules and error classes are those of :func:`sensitivity`."""
+    Fn, trans, h, n, dtype, pcode, argB, k, Xin, keep = _gn_inputs("tangent", F, B, X, itmax, pattern)
+    want = _gn_want(want, ("X",))
+    E = _gn_direction("tangent", E, _sens_len(Fn, h, n, pcode), dtype)
+    rows1 = None if rows is None else _gn_rows(rows, n)
+    m = n if rows1 is None else len(rows1)
+    rbuf = None if rows1 is None else (rows1 if m else np.zeros(1, dtype=np.int64))  # an empty list is still a list: never a null pointer
+    dX = np.zeros((m, k), dtype=dtype, order="F")
+    Xo = np.zeros((n, k), dtype=dtype, order="F") if "X" in want else None
+    L = _lib.lib()
+    fn = L.hs_tangent_z if dtype.kind == "c" else L.hs_tangent_d
+    _lib.check(fn(h, trans, n, k, None if argB is None else C.byref(argB), None if Xin is None else Xin.ctypes.data, max(n, 1), E.ctypes.data, pcode, int(itmax),
+                  None if rbuf is None else _p64(rbuf), 0 if rows1 is None else m, dX.ctypes.data, max(m, 1), None if Xo is None else Xo.ctypes.data, max(n, 1)))
+    del keep
+    return (dX, Xo) if Xo is not None else dX
+
+
+def gn_hessvec(F, B, rows, E, itmax=0, pattern="A", X=None, want=()):
+    """Gauss-Newton Hessian-vector product of the least-squares misfit at the receiver rows ``rows`` (``hs_gn_hessvec_*``): with
+    ``J E = tangent(F, B, E, rows)``, returns ``H E = J* J E`` (the adjoint in the real inner product), which is the ``G`` of
+    :func:`sensitivity` for ``W = J E`` scattered to ``rows`` -- aligned with the ``data`` of the factored matrix like ``E``
+    (:func:`sensitivity_matrix` wraps it), or of length ``n`` for ``pattern="diag"``.  ``Re<E1, H E2> = Re<J E1, J E2>``.  ``X=`` takes the
+    fields of an earlier call and skips the forward solve: a product then costs two block solves instead of three (a CG loop on a fixed ``A``
+    and ``B`` asks for ``want="X"`` once).  ``want`` may name ``"JE"`` and ``"X"``: the result is then ``(HE, JE, X)`` restricted to what
+    was asked for, in that order.  Nothing else of size ``n x k`` leaves the device."""
+    Fn, trans, h, n, dtype, pcode, argB, k, Xin, keep = _gn_inputs("gn_hessvec", F, B, X, itmax, pattern)
+    want = _gn_want(want, ("JE", "X"))
+    E = _gn_direction("gn_hessvec", E, _sens_len(Fn, h, n, pcode), dtype)
+    rows1 = _gn_rows(rows, n)
+    nr = len(rows1)
+    HE = np.zeros(len(E), dtype=dtype)
+    JE = np.zeros((nr, k), dtype=dtype, order="F") if "JE" in want else None
+    Xo = np.zeros((n, k), dtype=dtype, order="F") if "X" in want else None
+    L = _lib.lib()
+    fn = L.hs_gn_hessvec_z if dtype.kind == "c" else L.hs_gn_hessvec_d
+    _lib.check(fn(h, trans, n, k, None if argB is None else C.byref(argB), None if Xin is None else Xin.ctypes.data, max(n, 1), E.ctypes.data, pcode, int(itmax),
+                  _p64(rows1), nr, HE.ctypes.data, None if JE is None else JE.ctypes.data, max(nr, 1), None if Xo is None else Xo.ctypes.data, max(n, 1)))
+    del keep
+    out = (HE,) + ((JE,) if JE is not None else ()) + ((Xo,) if Xo is not None else ())
+    return out[0] if len(out) == 1 else out
+
+
+def gn_diag(F, B, rows, itmax=0, pattern="A", X=None, factors=False):
+    """Diagonal of the Gauss-Newton Hessian of :func:`gn_hessvec` (``hs_gn_diag_*``), the usual preconditioner of a Gauss-Newton loop: a real
+    array aligned with the ``data`` of the factored matrix (length ``n`` for ``pattern="diag"``), ``Hd[p] = z2[a] * x2[b]`` for the stored
+    entry ``p = (i, j)`` with ``(a, b) = (i, j)`` for a plain ``F`` and ``(j, i)`` for ``transpose(F)`` / ``adjoint(F)``, where
+    ``x2 = sum(|X|^2, axis=1)`` and ``z2 = sum(|Z|^2, axis=1)`` for the adjoint states ``Z = op(A)^-H S`` of the unit columns of ``rows``.
+    Costs one forward block solve (none with ``X=``) and ``len(rows)`` adjoint columns on the pruned path.  ``factors=True`` returns
+    ``(Hd, z2, x2)``."""
+    Fn, trans, h, n, dtype, pcode, argB, k, Xin, keep = _gn_inputs("gn_diag", F, B, X, itmax, pattern)
+    rows1 = _gn_rows(rows, n)
+    nr = len(rows1)
+    Hd = np.zeros(_sens_len(Fn, h, n, pcode))
+    z2, x2 = (np.zeros(n), np.zeros(n)) if factors else (None, None)
+    L = _lib.lib()
+    fn = L.hs_gn_diag_z if dtype.kind == "c" else L.hs_gn_diag_d
+    _lib.check(fn(h, trans, n, k, None if argB is None else C.byref(argB), None if Xin is None else Xin.ctypes.data, max(n, 1), _p64(rows1), nr, pcode, int(itmax),
+                  Hd.ctypes.data, None if z2 is None else z2.ctypes.data, None if x2 is None else x2.ctypes.data))
+    del keep
+    return (Hd, z2, x2) if factors else Hd
+
+
+def gn_info(F):
+    """Figures of the last :func:`tangent` / :func:`gn_hessvec` / :func:`gn_diag` call on ``F`` (``hs_gn_info``): device seconds in total, of
+    the forward, tangent and adjoint solves and of the products and reductions, column groups, block solves issued, workspace bytes."""
+    F, _ = _unwrap(F)
+    out = np.zeros(8)
+    _lib.check(_lib.lib().hs_gn_info(F._h, _pf64(out)))
+    return {"seconds": float(out[0]), "seconds_forward": float(out[1]), "seconds_tangent": float(out[2]), "seconds_adjoint": float(out[3]),
+            "seconds_products": float(out[4]), "groups": int(out[5]), "block_solves": int(out[6]), "workspace_bytes": int(out[7])}
 
 
 def _block_cols():

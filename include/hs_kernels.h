@@ -225,6 +225,22 @@ int hsk_sddmm_d(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t
 int hsk_sddmm_z(int64_t n, const int64_t* colptr, const int64_t* rowval, int64_t kc, const double* L, int64_t ldl, const double* R, int64_t ldr, int swap, int conjl,
                 int conjr, int diag, int form, double* G, double* seconds);
 
+/* The right-hand side kernel of hs_tangent_* / hs_gn_hessvec_* (kernels_gn.hip) on host data: P = -op(E) X for a perturbation E on the CSC
+ * pattern colptr / rowval (1-based, n columns, rows ascending within a column) and X column-major n x kc (ldx >= n); P is n x kc (ldp >= n,
+ * the padding rows are left as they are).  pattern 0: E has nnz values in CSC order; op(E) = E, E^T, E^H for trans = 0 / 1 / 2 and
+ *   P[i, c] = 0 - sum over the stored entries of row i of op(E), by ascending column of op(E), of op(E)[i, j] X[j, c],
+ * one lane per row, every step the unfused acc - e * x.  pattern 1: E has n values, P[i, c] = 0 - e_i X[i, c] (e_i conjugated for trans = 2)
+ * where (i, i) is stored, 0 elsewhere.  The hook builds the CSR map for trans = 0 on the host as the handle keeps it on the device. */
+int hsk_gn_rhs_d(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* E, int pattern, const double* X, int64_t ldx, int64_t kc, double* P,
+                 int64_t ldp);
+int hsk_gn_rhs_z(int trans, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* E, int pattern, const double* X, int64_t ldx, int64_t kc, double* P,
+                 int64_t ldp);
+/* The row square sums of hs_gn_diag_* (kernels_gn.hip) on host data: acc[i] <- acc[i] + |X[i, c]|^2 for c = 0 .. kc-1 in order (Float64:
+ * x * x; ComplexF64: re^2 + im^2), X column-major n x kc (ldx >= n), acc n doubles holding the initial values on entry.  One lane per row,
+ * unfused: columns fed in several calls give the bits of one call. */
+int hsk_gn_rowsq_d(int64_t n, int64_t kc, const double* X, int64_t ldx, double* acc);
+int hsk_gn_rowsq_z(int64_t n, int64_t kc, const double* X, int64_t ldx, double* acc);
+
 /* Host-only: the order in which the HSS form of a front's interior block lists its DOFs (hs_options.hss_d): recursive bisection of
  * the graph of A (1-based CSC pattern colptr / rowval of the n x n matrix) restricted to the ni DOFs `ids` (1-based), split where the
  * HSS cluster tree splits its index range.  perm_out[new position] = position in `ids` (0-based). */

@@ -319,6 +319,72 @@ int hs_misfit_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_b
  * reduced, values moved between host and device (0 for the _dev_ forms), workspace bytes} */
 int hs_sens_info(const hs_handle* F, double* out8);
 
+/* ---- tangent-linear solves and Gauss-Newton Hessian products on A's pattern (hs_gn.hip) --------------------------------------------------
+ * The forward mode next to hs_sens_*.  op(A), X = op(A)^-1 B and hs_block_arg as above.  E is a perturbation on the stored pattern of A:
+ * pattern 0: nnz(A) values in the order of the nzval given to the factorization; pattern 1: n diagonal values (a value at a j whose (j, j) is
+ * not stored counts as 0).  op(E) = E, E^T, E^H for trans = 0 / 1 / 2.
+ *   tangent       dX(E) = d/ds op(A + sE)^-1 B at s = 0 = -op(A)^-1 op(E) X      (real-linear in E; antilinear for trans = 2)
+ *   identity      Re<W, dX(E)> = Re sum_p E_p conj(G_p) for the G of hs_sens_* with cotangent W
+ *   Gauss-Newton  J E = dX(E)[rows, :] for distinct receiver rows; H E = J* J E with the adjoint in the real inner product: the G of
+ *                 hs_sens_* for W = J E scattered to `rows`, so Re<E1, H E2> = Re<J E1, J E2>
+ *   diagonal      Z = op(A)^-H S, S the unit columns of `rows`; z2[q] = sum_r |Z[q, r]|^2, x2[q] = sum_c |X[q, c]|^2; the diagonal of H at
+ *                 the stored (i, j) is z2[i] x2[j] (trans 0) or z2[j] x2[i] (trans 1, 2): real, the same for the directions e_p and i e_p
+ * hs_tangent_*: dX is n x nrhs (rows == NULL; nrows is ignored) or nrows x nrhs in the order of `rows` (1-based, distinct), leading
+ * dimension lddx; X (may be NULL) receives the fields.  hs_gn_hessvec_*: HE has nnz(A) or n values like the G of hs_sens_* and is
+ * zero-filled first; JE (nrows x nrhs, ldje) and X may be NULL.  hs_gn_diag_*: Hd is a REAL array of nnz(A) or n doubles (pattern 1:
+ * z2[j] x2[j] where (j, j) is stored, 0 elsewhere); z2, x2 (n doubles each) may be NULL.
+ * Xin (n x nrhs, ldxin) is the X of an earlier call on the same A and B: when it is given the forward solve is skipped -- a product then
+ * costs two block solves instead of three -- and B is not read and may be NULL.
+ * The columns go in groups of Gc sized as hs_sens_* sizes them (HS_GN_GROUP in the environment overrides Gc, read per call).  Per group: the
+ * forward solve, P = -op(E) X (one lane per row of op(E), E read in place through the handle's CSR map for trans = 0 and in CSC order
+ * otherwise), the tangent solve, the receiver rows (returned, or made the sparse cotangent on the device), the adjoint solve on the pruned
+ * path and the reduction kernel of hs_sens_*; every solve is chosen as hs_sens_* chooses it (dense block: hs_ldiv_block_dev_t_*; sparse B:
+ * hs_ldiv_sparse_dev_* with all rows; itmax > 0: hs_ldiv_refine_block_dev_* without ferr).  hs_gn_diag_* accumulates x2 over the forward
+ * groups, then sends the unit columns of `rows` in groups through the adjoint path and accumulates z2.  Nothing of size n x nrhs leaves
+ * the device unless asked for.
+ * Determinism: X carries the bits of the entry points named above, P the bits of one chain per (row, column) over the row's entries by
+ * ascending column of op(E), every step the unfused acc - e * x, and dX = hs_ldiv_block_t_*(op(F), P) bit for bit (itmax = 0); JE are rows
+ * of dX; HE has the bits of hs_sens_*(op(F), B, W = scatter(JE)); z2 and x2 are one chain per row over the columns in order
+ * (acc + (re^2 + im^2), unfused) and Hd their rounded product.  So two calls return the same bits, no result depends on Gc, a sparse B
+ * gives the bits of its dense expansion, a supplied Xin the bits of the computed X, and pattern 1 the diagonal entries of pattern 0 (HE,
+ * Hd).  NOT guaranteed bitwise: agreement with any host composition that forms op(E) X in another order, and of Hd[p] with
+ * (H e_p)_p, which sums the same terms in another order.
+ * Refused before any device work, every output untouched: what hs_ldiv_block_t_* refuses (HSS interior blocks, more than one rank), by its
+ * own check: HS_ERR_UNSUPPORTED; a null, plan-only or unfactored handle, a mismatched element type, trans outside 0..2, pattern outside 0..1,
+ * itmax < 0, null pointers with nonzero sizes, B and Xin both NULL, repeated rows, a CSC block hs_ldiv_sparse_* would refuse:
+ * HS_ERR_ARGUMENT; n != size(F), negative sizes, rows outside 1..n, leading dimensions too small: HS_ERR_DIMENSION.  nrhs = 0, or nrows = 0
+ * where rows are given, returns zero-filled outputs and HS_OK.
+ * The host forms move B (or its stored values, or Xin) and E up and the outputs down; in the _dev_ forms the values, E and the outputs are
+ * on the device, the index arrays (colptr, rowval, rows) on the host, and the call returns when the outputs are complete. */
+int hs_tangent_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* Xin, int64_t ldxin, const double* E, int pattern, int64_t itmax,
+                 const int64_t* rows, int64_t nrows, double* dX, int64_t lddx, double* X, int64_t ldx);
+int hs_tangent_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* Xin, int64_t ldxin, const double* E, int pattern, int64_t itmax,
+                 const int64_t* rows, int64_t nrows, double* dX, int64_t lddx, double* X, int64_t ldx); /* interleaved (re, im) */
+int hs_tangent_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* dXin, int64_t ldxin, const double* dE, int pattern,
+                     int64_t itmax, const int64_t* rows, int64_t nrows, double* ddX, int64_t lddx, double* dX, int64_t ldx, void* stream);
+int hs_tangent_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* dXin, int64_t ldxin, const double* dE, int pattern,
+                     int64_t itmax, const int64_t* rows, int64_t nrows, double* ddX, int64_t lddx, double* dX, int64_t ldx, void* stream);
+int hs_gn_hessvec_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* Xin, int64_t ldxin, const double* E, int pattern, int64_t itmax,
+                    const int64_t* rows, int64_t nrows, double* HE, double* JE, int64_t ldje, double* X, int64_t ldx);
+int hs_gn_hessvec_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* Xin, int64_t ldxin, const double* E, int pattern, int64_t itmax,
+                    const int64_t* rows, int64_t nrows, double* HE, double* JE, int64_t ldje, double* X, int64_t ldx);
+int hs_gn_hessvec_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* dXin, int64_t ldxin, const double* dE, int pattern,
+                        int64_t itmax, const int64_t* rows, int64_t nrows, double* dHE, double* dJE, int64_t ldje, double* dX, int64_t ldx, void* stream);
+int hs_gn_hessvec_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* dXin, int64_t ldxin, const double* dE, int pattern,
+                        int64_t itmax, const int64_t* rows, int64_t nrows, double* dHE, double* dJE, int64_t ldje, double* dX, int64_t ldx, void* stream);
+int hs_gn_diag_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* Xin, int64_t ldxin, const int64_t* rows, int64_t nrows, int pattern,
+                 int64_t itmax, double* Hd, double* z2, double* x2);
+int hs_gn_diag_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* Xin, int64_t ldxin, const int64_t* rows, int64_t nrows, int pattern,
+                 int64_t itmax, double* Hd, double* z2, double* x2);
+int hs_gn_diag_dev_d(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* dXin, int64_t ldxin, const int64_t* rows, int64_t nrows,
+                     int pattern, int64_t itmax, double* dHd, double* dz2, double* dx2, void* stream);
+int hs_gn_diag_dev_z(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block_arg* B, const double* dXin, int64_t ldxin, const int64_t* rows, int64_t nrows,
+                     int pattern, int64_t itmax, double* dHd, double* dz2, double* dx2, void* stream);
+/* the last hs_tangent_* / hs_gn_* call of the handle: out8 = {seconds on the device in total, of the forward solves, of the tangent solves,
+ * of the adjoint solves, of the products and reductions (the copies of requested blocks included), column groups, block solves issued,
+ * workspace bytes} */
+int hs_gn_info(const hs_handle* F, double* out8);
+
 /* ---- solves with a low-rank or entry modification of A, without refactoring (hs_mod.hip) ------------------------------------------------
  * A1 = A + U V^H with U, V n x k (Float64: V^T), k <= HS_MOD_MAXRANK = 256.  With Z = F^-1 U, W = F^-H V and the capacitance matrix
  * C = I_k + V^H Z (Sherman-Morrison-Woodbury):
