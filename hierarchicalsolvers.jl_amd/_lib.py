@@ -85,7 +85,7 @@ EXPORTS = [
     "hs_ldiv_sparse_d", "hs_ldiv_sparse_z", "hs_ldiv_sparse_dev_d", "hs_ldiv_sparse_dev_z", "hs_ldiv_sparse_plan", "hs_ldiv_sparse_info",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
-    "hs_logabsdet", "hs_selinv", "hs_selinv_info",
+    "hs_logabsdet", "hs_selinv", "hs_selinv_info", "hs_selinv_lr", "hs_selinv_lr_info",
     "hs_interface_size", "hs_interface_indices", "hs_interface_matrix_d", "hs_interface_matrix_z", "hs_interface_info", "hsk_lu_product_d", "hsk_lu_product_z",
     "hs_interface_condense_d", "hs_interface_condense_z", "hs_interface_condense_dev_d", "hs_interface_condense_dev_z",
     "hs_interface_solve_d", "hs_interface_solve_z", "hs_interface_solve_dev_d", "hs_interface_solve_dev_z",
@@ -360,6 +360,10 @@ def lib():
     L.hs_selinv.restype = C.c_int
     L.hs_selinv_info.argtypes = [vp, p_f64]
     L.hs_selinv_info.restype = C.c_int
+    L.hs_selinv_lr.argtypes = [vp, C.c_int, vp, vp, C.c_int, i64, vp]
+    L.hs_selinv_lr.restype = C.c_int
+    L.hs_selinv_lr_info.argtypes = [vp, p_f64]
+    L.hs_selinv_lr_info.restype = C.c_int
     L.hs_interface_size.argtypes = [vp, p_i64]
     L.hs_interface_size.restype = C.c_int
     L.hs_interface_indices.argtypes = [vp, p_i64]

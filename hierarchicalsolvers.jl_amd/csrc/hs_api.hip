@@ -2030,6 +2030,10 @@ void hs_selinv_view(hs_handle* h, HsSelView* v) {
     if (x.hss_interior()) f.flags |= HS_SEL_NOLU;
     if (x.compressed || x.mf) f.flags |= HS_SEL_LOWRANK;
     if (x.kind != 0) f.flags |= HS_SEL_SLICE;
+    if ((x.compressed || x.mfd) && !x.hss_interior() && (x.lrL || x.lrR)) {  // the fronts hs_multi_view lists in HsMultiLevel::lr (hs_selinv_lr)
+      f.lrL = x.lrL;
+      f.lrR = x.lrR;
+    }
     const char* fac = (const char*)h->d_fac;
     if (x.mf) {
       f.LU = x.mfd_LF;

@@ -27,6 +27,10 @@ struct HsSelFront {          // one owned front, every pointer a device pointer
   const int* rperm = nullptr;
   const int* fidx = nullptr;  // m global ids, front order [int; bnd]
   size_t off_fidx_host = 0;   // the same ids in HsSelView::fidx_host
+  // hs_selinv_lr only (hs_selinv never reads them): the LowRank<T> objects of a compressed front that keeps a dense pivoted LU of Aii,
+  // Lbi ~= C_L Z_L' (lrL: Cd nb x rL, Z rL x ni) and Uib ~= G Z_R (lrR: Cd ni x rR, Z rR x nb); null: dense front, or a front the call refuses
+  const void* lrL = nullptr;
+  const void* lrR = nullptr;
 };
 
 struct HsSelView {
@@ -73,9 +77,28 @@ struct SelDesc {  // one front of a selected-inversion batch
   const int64_t* ee;
   int ecnt;
   int ni, nb, m, ldz, ldzp, ldv;
+  // a low-rank front of hs_selinv_lr (rR = rL = 0 and null pointers: dense front).  The stored factors are only read: zload_lr copies G
+  // into Vg = Vi + ni ldv and Z_L' into rows nit.. of Tm, the right-hand sides the substitutions overwrite
+  int rR, rL;      // ranks of Uib ~= G Z_R and Lbi ~= C_L Z_L'
+  int ldg, ldzr, ldcl, ldzl;
+  const T* G;      // ni x rR
+  const T* ZR;     // rR x nb
+  const T* CL;     // nb x rL
+  const T* ZL;     // rL x ni (Z_L' = Z_L U^-1)
+  int ldt, nit;    // Tm of a low-rank front: (nit + rL) x ni, ld ldt, nit = ni rounded up to even (the tail starts 16-byte aligned)
+  int ld1, ld2;    // ld of T1 / T3 (rR rows) and of T2 (nb rows); Wg and WT3 use ldv, Yp uses ldy
+  int ldy, pad;
+  T* Wg;           // W = U^-1 G (ni x rR)
+  T* Yp;           // Y' = Z_L' L^-1 (rL x ni)
+  T* T1;           // -Z_R Zbb (rR x nb)
+  T* T2;           // -Zbb C_L (nb x rL)
+  T* T3;           // T1 C_L (rR x rL)
+  T* WT3;          // W T3 (ni x rL)
 };
 template <class T>
 void launch_zinit(const SelDesc<T>* d, int nbatch, int maxni, hipStream_t s);                 // Vi = I
+template <class T>
+void launch_zload_lr(const SelDesc<T>* d, int nbatch, int maxni, int maxr, hipStream_t s);   // Vg = G, Tm[nit.., :] = Z_L' for the low-rank fronts
 template <class T>
 void launch_zgather(const SelDesc<T>* d, int nbatch, int maxnb, hipStream_t s);               // Z[bnd, bnd] = Zp[cmap, cmap]
 template <class T>

@@ -1,4 +1,4 @@
-// hs_selinv.hip -- log|det| and selected inversion from the stored factors (include/hs_solver.h: hs_logabsdet, hs_selinv, hs_selinv_info).
+// hs_selinv.hip -- log|det| and selected inversion from the stored factors (include/hs_solver.h: hs_logabsdet, hs_selinv, hs_selinv_info, hs_selinv_lr, hs_selinv_lr_info).
 //
 // det.  Every front keeps P Aii = L U, and the Gauss transforms between fronts are unit block-triangular, so
 //   det(F) = prod over fronts of sign(P) * prod diag(U).
@@ -21,6 +21,10 @@
 // Memory.  A batch holds the m x m blocks of its fronts and 2 m ni work elements per front (the Schur scratch of the handle serves as work
 // space when it is idle).  A parent batch's blocks live until the last batch of its children has gathered from them; a level that does not
 // fit the byte budget is cut into several batches of fronts, each followed by its own subtree before the next one starts.
+//
+// Compressed factorizations (hs_selinv_lr, hs_selinv_lr_info).  A compressed front keeps Uib ~= G Z_R and Lbi ~= C_L Z_L' (hs_compress.h) and
+// the pivoted LU of Aii; the same recurrence runs through the r-wide factors (the comment at SelRun), the operator the block solves apply,
+// so the result is F^-1 to rounding.  Dense and low-rank fronts share a batch's launches.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -31,6 +35,7 @@
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
 #include "hs_host.h"
+#include "hs_lowrank.h"
 #include "hs_selinv.h"
 
 namespace {
@@ -51,6 +56,7 @@ struct SelCache {
   int64_t* d_ee = nullptr;
   int* d_cmap = nullptr;
   double info[4] = {0, 0, 0, 0};  // last call: seconds, flops, peak scratch bytes, batches
+  double info_lr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // last hs_selinv_lr call (hs_selinv_lr_info); neither call touches the other's figures
   ~SelCache() {
     if (d_epr) (void)hipFree(d_epr);
     if (d_epc) (void)hipFree(d_epc);
@@ -229,7 +235,35 @@ struct Launch {
   size_t off;
   int cnt, maxM, maxN, minus;
 };
+struct Fill {  // a block a low-rank front of rank 0 leaves unwritten: cleared before (Z[int, bnd]) or after (X2[bnd, :]) the products
+  void* p;
+  size_t pitch, width, height;
+};
 
+// Flops of the dense-form recurrence of one front, the products run_batch issues for a dense front (real flops, 256-blocks counted as
+// they are launched); nothing is launched here
+template <class T>
+double dense_form_flops(int ni, int nb) {
+  const double m = (double)ni + nb, n = (double)ni, b = (double)nb;
+  double f = n * b * b + m * n * b;  // Vb = -Uib Zbb;  Tm -= Z[:, bnd] Lbi
+  for (int kb = (ni + 255) / 256 - 1; kb >= 0; --kb) {
+    const double k0 = (double)kb * 256, wk = std::min(256.0, n - k0);
+    f += wk * b * wk + wk * (n - k0) * wk + k0 * b * wk + k0 * (n - k0) * wk;  // U^-1 [Vi | Vb]
+    f += m * wk * wk + m * k0 * wk;                                            // Tm L^-1
+  }
+  return (sizeof(T) == 16 ? 8.0 : 2.0) * f;
+}
+
+// Selected inversion over the tree.  lrmode = false is hs_selinv: every front dense, the low-rank pointers of the view are never read.
+// lrmode = true is hs_selinv_lr: a front with low-rank objects runs the rank-structured form below, every other front the dense one, in
+// the same launches; on a handle without low-rank fronts the two modes issue the same launches.
+//
+// Low-rank front (Uib ~= G Z_R, Lbi ~= C_L Z_L'; W = U^-1 G, Y' = Z_L' L^-1):
+//   T1 = -Z_R Zbb,  T2 = -Zbb C_L,  T3 = T1 C_L                         (products through r-wide blocks)
+//   [Tm[int, :] | W] = U^-1 [Vi | Vg],  Vg a copy of G                   (the blocked back substitution, rR columns instead of nb)
+//   [X2[int, :]; Y'] = [Tm[int, :]; Z_L' copy] L^-1                      (the right substitution on ni + rL rows, written as two row groups)
+//   Z[int, bnd] = W T1,   X2[bnd, :] = T2 Y',   X2[int, :] -= (W T3) Y'
+// No substitution and no product has an nb-wide or m-tall operand except T1, T2 and the writes into Z / X2.
 template <class T>
 struct SelRun {
   const HsSelView& v;
@@ -239,10 +273,11 @@ struct SelRun {
   T* d_diag;
   T* d_zval;
   size_t budget;
+  bool lrmode = false;
   std::vector<std::vector<int>> kids;
   size_t alive = 0, peak = 0;
-  double flops = 0.0;
-  int batches = 0;
+  double flops = 0.0, flops_dense = 0.0;  // executed; what the dense form would execute on the same front shapes
+  int batches = 0, lr_fronts = 0, max_rank = 0;
   HsScratch work, descs;  // work blocks and descriptors of the current batch (reused, grown on demand)
 
   struct Batch {
@@ -251,6 +286,46 @@ struct SelRun {
     HsScratch Z;
     int pending = 0;  // batches of children that still have to gather from Z
   };
+
+  struct LrOf {  // the low-rank transforms of a front as this run sees them (on = false: dense recurrence)
+    bool on = false;
+    const LowRank<T>* R = nullptr;
+    const LowRank<T>* L = nullptr;
+    int rR = 0, rL = 0;
+  };
+  LrOf lr_of(const HsSelFront& x) const {
+    LrOf o;
+    if (!lrmode || (!x.lrL && !x.lrR) || x.nb <= 0 || x.ni <= 0) return o;
+    o.on = true;
+    o.R = (const LowRank<T>*)x.lrR;
+    o.L = (const LowRank<T>*)x.lrL;
+    o.rR = o.R ? o.R->r : 0;
+    o.rL = o.L ? o.L->r : 0;
+    return o;
+  }
+  struct Work {  // element counts of a front's work blocks, in the order they are laid out
+    size_t r1 = 0, r2 = 0, wg = 0, yp = 0, t1 = 0, t2 = 0, t3 = 0, wt3 = 0;
+    size_t total() const { return r1 + r2 + wg + yp + t1 + t2 + t3 + wt3; }
+  };
+  static size_t blk(int ld, int cols) { return cols > 0 ? rup32((size_t)ld * (size_t)cols + 32) : 0; }
+  Work work_of(const HsSelFront& x) const {
+    Work w;
+    w.r1 = r1elems(x);
+    const LrOf o = lr_of(x);
+    if (!o.on) {
+      w.r2 = r2elems(x);
+      return w;
+    }
+    w.r1 = std::max(w.r1, rup32((size_t)rup2(x.ni) * (size_t)(x.ni + o.rR) + 32));  // [Vi | Vg] (a matrix-free front's rank is not bounded by nb)
+    w.r2 = rup32((size_t)(rup2(x.ni) + rup2(o.rL)) * (size_t)x.ni + 32);
+    w.wg = blk(rup2(x.ni), o.rR);
+    w.yp = o.rL > 0 ? blk(rup2(o.rL), x.ni) : 0;
+    w.t1 = o.rR > 0 ? blk(rup2(o.rR), x.nb) : 0;
+    w.t2 = blk(rup2(x.nb), o.rL);
+    w.t3 = o.rR > 0 ? blk(rup2(o.rR), o.rL) : 0;
+    w.wt3 = o.rR > 0 ? blk(rup2(x.ni), o.rL) : 0;
+    return w;
+  }
 
   static size_t zelems(const HsSelFront& x) {
     const int m = x.ni + x.nb;
@@ -261,7 +336,7 @@ struct SelRun {
     return rup32(std::max((size_t)rup2(m) * (size_t)x.ni, (size_t)rup2(x.ni) * (size_t)m) + 32);
   }
   static size_t r2elems(const HsSelFront& x) { return rup32((size_t)rup2(x.ni + x.nb) * (size_t)x.ni + 32); }
-  static size_t cost(const HsSelFront& x) { return (zelems(x) + r1elems(x) + r2elems(x)) * sizeof(T); }
+  size_t cost(const HsSelFront& x) const { return (zelems(x) + work_of(x).total()) * sizeof(T); }
 
   void note_alive(long long delta) {
     alive = (size_t)((long long)alive + delta);
@@ -284,15 +359,16 @@ struct SelRun {
     std::vector<std::vector<int>> cuts;
     {
       const size_t room = budget > alive ? budget - alive : 0;
-      size_t used = 0;
+      size_t used = 0, pairs = 0;  // pairs: a front brings two GEMM problems to a launch, a low-rank front up to four; grid.y <= 65535
       for (int f : fronts) {
-        const size_t cst = cost(v.fronts[f]);
-        if (cuts.empty() || (used + cst > room && !cuts.back().empty()) || cuts.back().size() >= 16384) {  // (two GEMM problems per front, grid.y <= 65535)
+        const size_t cst = cost(v.fronts[f]), pr = lr_of(v.fronts[f]).on ? 2 : 1;
+        if (cuts.empty() || (used + cst > room && !cuts.back().empty()) || pairs + pr > 16384) {
           cuts.emplace_back();
-          used = 0;
+          used = pairs = 0;
         }
         cuts.back().push_back(f);
         used += cst;
+        pairs += pr;
       }
     }
     if (parent) parent->pending = (int)cuts.size();
@@ -329,7 +405,7 @@ struct SelRun {
       b.zoff[(size_t)i] = ztot;
       ztot += zelems(x);
       woff[(size_t)i] = wtot;
-      wtot += r1elems(x) + r2elems(x);
+      wtot += work_of(x).total();
     }
     b.Z.take(ztot * sizeof(T), "blocks of the selected inverse");
     note_alive((long long)b.Z.bytes);
@@ -349,7 +425,9 @@ struct SelRun {
     std::vector<SelDesc<T>> D((size_t)nbt);
     std::vector<GemmProb<T>> P;
     std::vector<Launch> L;
-    int maxni = 0, maxnb = 0, maxm = 0, maxe = 0, maxblk = 0;
+    std::vector<Fill> fill_before, fill_after;
+    std::vector<LrOf> lro((size_t)nbt);
+    int maxni = 0, maxnb = 0, maxm = 0, maxe = 0, maxblk = 0, maxr = 0;
     for (int i = 0; i < nbt; ++i) {
       const int f = b.fronts[(size_t)i];
       const HsSelFront& x = v.fronts[f];
@@ -369,7 +447,29 @@ struct SelRun {
       d.fidx = x.fidx;
       d.Vi = W + woff[(size_t)i];
       d.X2 = d.Vi;                            // (Vi and Vb are dead when X2 is written)
-      d.Tm = W + woff[(size_t)i] + r1elems(x);
+      const Work w = work_of(x);
+      d.Tm = W + woff[(size_t)i] + w.r1;
+      const LrOf o = lro[(size_t)i] = lr_of(x);
+      if (o.on) {
+        d.rR = o.rR; d.rL = o.rL;
+        d.nit = rup2(d.ni);
+        d.ldt = d.nit + rup2(o.rL);
+        d.ld1 = rup2(o.rR); d.ld2 = rup2(d.nb); d.ldy = rup2(o.rL);
+        if (o.rR > 0) { d.G = o.R->Cd; d.ldg = o.R->ldc; d.ZR = o.R->Z; d.ldzr = o.R->ldz; }
+        if (o.rL > 0) { d.CL = o.L->Cd; d.ldcl = o.L->ldc; d.ZL = o.L->Z; d.ldzl = o.L->ldz; }
+        d.Wg = d.Tm + w.r2;
+        d.Yp = d.Wg + w.wg;
+        d.T1 = d.Yp + w.yp;
+        d.T2 = d.T1 + w.t1;
+        d.T3 = d.T2 + w.t2;
+        d.WT3 = d.T3 + w.t3;
+        if (o.rR == 0) fill_before.push_back(Fill{d.Z + (size_t)d.ni * d.ldz, (size_t)d.ldz * sizeof(T), (size_t)d.ni * sizeof(T), (size_t)d.nb});  // Z[int, bnd] = 0
+        if (o.rL == 0) fill_after.push_back(Fill{d.X2 + d.ni, (size_t)d.ldz * sizeof(T), (size_t)d.nb * sizeof(T), (size_t)d.ni});                  // Z[bnd, int] = 0
+        ++lr_fronts;
+        max_rank = std::max(max_rank, std::max(o.rR, o.rL));
+        maxr = std::max(maxr, std::max(o.rR, o.rL));
+      }
+      flops_dense += dense_form_flops<T>(x.ni, x.nb);
       d.epr = c->d_epr + c->eptr[(size_t)f];
       d.epc = c->d_epc + c->eptr[(size_t)f];
       d.ee = c->d_ee + c->eptr[(size_t)f];
@@ -386,10 +486,18 @@ struct SelRun {
       }
       L.push_back(l);
     };
-    auto each = [&](auto&& body) {
+    auto each = [&](auto&& body) {  // the dense fronts of the batch
       for (int i = 0; i < nbt; ++i) {
+        if (lro[(size_t)i].on) continue;
         const HsSelFront& x = v.fronts[b.fronts[(size_t)i]];
         body(D[(size_t)i], x, (const T*)x.LU, (const T*)x.UR, D[(size_t)i].Vi + (size_t)D[(size_t)i].ldv * D[(size_t)i].ni);
+      }
+    };
+    auto each_lr = [&](auto&& body) {  // its low-rank fronts; Vg sits where a dense front keeps Vb
+      for (int i = 0; i < nbt; ++i) {
+        if (!lro[(size_t)i].on) continue;
+        const HsSelFront& x = v.fronts[b.fronts[(size_t)i]];
+        body(D[(size_t)i], x, (const T*)x.LU, D[(size_t)i].Vi + (size_t)D[(size_t)i].ldv * D[(size_t)i].ni);
       }
     };
     size_t from = P.size();
@@ -397,8 +505,14 @@ struct SelRun {
     each([&](SelDesc<T>& d, const HsSelFront& x, const T*, const T* UR, T* Vb) {
       add(P, UR, x.ldu, d.Z + d.ni + (size_t)d.ni * d.ldz, d.ldz, Vb, d.ldv, d.ni, d.nb, d.nb);
     });
+    // T1 = -Z_R Zbb, T2 = -Zbb C_L
+    each_lr([&](SelDesc<T>& d, const HsSelFront&, const T*, T*) {
+      const T* Zbb = d.Z + d.ni + (size_t)d.ni * d.ldz;
+      add(P, d.ZR, d.ldzr, Zbb, d.ldz, d.T1, d.ld1, d.rR, d.nb, d.nb);
+      add(P, Zbb, d.ldz, d.CL, d.ldcl, d.T2, d.ld2, d.nb, d.rL, d.nb);
+    });
     close(from, 1);
-    // [Tm[int, :] | Z[int, bnd]] = U^-1 [Vi | Vb], the last 256-block of every front first
+    // [Tm[int, :] | Z[int, bnd]] = U^-1 [Vi | Vb], the last 256-block of every front first; a low-rank front: [Tm[int, :] | W] = U^-1 [Vi | Vg]
     for (int st = 0; st < maxblk; ++st) {
       from = P.size();
       each([&](SelDesc<T>& d, const HsSelFront& x, const T*, const T*, T* Vb) {
@@ -408,6 +522,15 @@ struct SelRun {
         const T* iU = (const T*)x.inv256U + (size_t)kb * 65536;
         add(P, iU, 256, Vb + k0, d.ldv, d.Z + k0 + (size_t)d.ni * d.ldz, d.ldz, wk, d.nb, wk);
         add(P, iU, 256, d.Vi + k0 + (size_t)k0 * d.ldv, d.ldv, d.Tm + k0 + (size_t)k0 * d.ldz, d.ldz, wk, d.ni - k0, wk);
+      });
+      each_lr([&](SelDesc<T>& d, const HsSelFront& x, const T*, T* Vg) {
+        if (st == 0) add(P, d.T1, d.ld1, d.CL, d.ldcl, d.T3, d.ld1, d.rR, d.rL, d.nb);  // T3 = T1 C_L rides in the first launch after T1
+        const int kb = (d.ni + 255) / 256 - 1 - st;
+        if (kb < 0) return;
+        const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
+        const T* iU = (const T*)x.inv256U + (size_t)kb * 65536;
+        add(P, iU, 256, Vg + k0, d.ldv, d.Wg + k0, d.ldv, wk, d.rR, wk);
+        add(P, iU, 256, d.Vi + k0 + (size_t)k0 * d.ldv, d.ldv, d.Tm + k0 + (size_t)k0 * d.ldt, d.ldt, wk, d.ni - k0, wk);
       });
       close(from, 0);
       from = P.size();
@@ -419,6 +542,14 @@ struct SelRun {
         add(P, U01, x.ldlu, d.Z + k0 + (size_t)d.ni * d.ldz, d.ldz, Vb, d.ldv, k0, d.nb, wk);
         add(P, U01, x.ldlu, d.Tm + k0 + (size_t)k0 * d.ldz, d.ldz, d.Vi + (size_t)k0 * d.ldv, d.ldv, k0, d.ni - k0, wk);
       });
+      each_lr([&](SelDesc<T>& d, const HsSelFront& x, const T* LU, T* Vg) {
+        const int kb = (d.ni + 255) / 256 - 1 - st;
+        if (kb <= 0) return;
+        const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
+        const T* U01 = LU + (size_t)k0 * x.ldlu;
+        add(P, U01, x.ldlu, d.Wg + k0, d.ldv, Vg, d.ldv, k0, d.rR, wk);
+        add(P, U01, x.ldlu, d.Tm + k0 + (size_t)k0 * d.ldt, d.ldt, d.Vi + (size_t)k0 * d.ldv, d.ldv, k0, d.ni - k0, wk);
+      });
       close(from, 1);
     }
     // Tm -= Z[:, bnd] Lbi
@@ -427,7 +558,7 @@ struct SelRun {
       add(P, d.Z + (size_t)d.ni * d.ldz, d.ldz, LU + d.ni, x.ldlu, d.Tm, d.ldz, d.m, d.ni, d.nb);
     });
     close(from, 1);
-    // X2 = Tm L^-1
+    // X2 = Tm L^-1; a low-rank front: [X2[int, :]; Y'] = [Tm[int, :]; Z_L' copy] L^-1, its two row groups as two problems
     for (int st = 0; st < maxblk; ++st) {
       from = P.size();
       each([&](SelDesc<T>& d, const HsSelFront& x, const T*, const T*, T*) {
@@ -435,6 +566,18 @@ struct SelRun {
         if (kb < 0) return;
         const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
         add(P, d.Tm + (size_t)k0 * d.ldz, d.ldz, (const T*)x.inv256L + (size_t)kb * 65536, 256, d.X2 + (size_t)k0 * d.ldz, d.ldz, d.m, wk, wk);
+      });
+      each_lr([&](SelDesc<T>& d, const HsSelFront& x, const T*, T*) {
+        if (st == 0) {  // W is complete: Z[int, bnd] = W T1, WT3 = W T3
+          add(P, d.Wg, d.ldv, d.T1, d.ld1, d.Z + (size_t)d.ni * d.ldz, d.ldz, d.ni, d.nb, d.rR);
+          add(P, d.Wg, d.ldv, d.T3, d.ld1, d.WT3, d.ldv, d.ni, d.rL, d.rR);
+        }
+        const int kb = (d.ni + 255) / 256 - 1 - st;
+        if (kb < 0) return;
+        const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
+        const T* iL = (const T*)x.inv256L + (size_t)kb * 65536;
+        add(P, d.Tm + (size_t)k0 * d.ldt, d.ldt, iL, 256, d.X2 + (size_t)k0 * d.ldz, d.ldz, d.ni, wk, wk);
+        add(P, d.Tm + d.nit + (size_t)k0 * d.ldt, d.ldt, iL, 256, d.Yp + (size_t)k0 * d.ldy, d.ldy, d.rL, wk, wk);
       });
       close(from, 0);
       from = P.size();
@@ -444,8 +587,24 @@ struct SelRun {
         const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
         add(P, d.X2 + (size_t)k0 * d.ldz, d.ldz, LU + k0, x.ldlu, d.Tm, d.ldz, d.m, k0, wk);
       });
+      each_lr([&](SelDesc<T>& d, const HsSelFront& x, const T* LU, T*) {
+        const int kb = (d.ni + 255) / 256 - 1 - st;
+        if (kb <= 0) return;
+        const int k0 = kb * 256, wk = std::min(256, d.ni - k0);
+        add(P, d.X2 + (size_t)k0 * d.ldz, d.ldz, LU + k0, x.ldlu, d.Tm, d.ldt, d.ni, k0, wk);
+        add(P, d.Yp + (size_t)k0 * d.ldy, d.ldy, LU + k0, x.ldlu, d.Tm + d.nit, d.ldt, d.rL, k0, wk);
+      });
       close(from, 1);
     }
+    // X2[bnd, :] = T2 Y', then X2[int, :] -= (W T3) Y'
+    from = P.size();
+    each_lr([&](SelDesc<T>& d, const HsSelFront&, const T*, T*) { add(P, d.T2, d.ld2, d.Yp, d.ldy, d.X2 + d.ni, d.ldz, d.nb, d.ni, d.rL); });
+    close(from, 0);
+    from = P.size();
+    each_lr([&](SelDesc<T>& d, const HsSelFront&, const T*, T*) {
+      if (d.rR > 0) add(P, d.WT3, d.ldv, d.Yp, d.ldy, d.X2, d.ldz, d.ni, d.ni, d.rL);  // (rR = 0: there is no WT3 block)
+    });
+    close(from, 1);
 
     const size_t dbytes = sizeof(SelDesc<T>) * (size_t)nbt, pbytes = sizeof(GemmProb<T>) * std::max<size_t>(P.size(), 1);
     if (descs.bytes < dbytes + pbytes + 256) descs.take(2 * (dbytes + pbytes) + 256, "descriptors of the selected inversion");
@@ -455,8 +614,11 @@ struct SelRun {
     if (!P.empty()) HS_HIP(hipMemcpy(dP, P.data(), sizeof(GemmProb<T>) * P.size(), hipMemcpyHostToDevice));
     HS_HIP(hipMemsetAsync(W, 0, wtot * sizeof(T), s));
     launch_zinit<T>(dD, nbt, maxni, s);
+    launch_zload_lr<T>(dD, nbt, maxni, maxr, s);  // (maxr = 0 without low-rank fronts: no launch)
+    for (const Fill& f : fill_before) HS_HIP(hipMemset2DAsync(f.p, f.pitch, 0, f.width, f.height, s));
     if (parent) launch_zgather<T>(dD, nbt, maxnb, s);
     for (const Launch& l : L) launch_gemm_probs<T>(dP + l.off, l.cnt, l.maxM, l.maxN, l.minus, s);
+    for (const Fill& f : fill_after) HS_HIP(hipMemset2DAsync(f.p, f.pitch, 0, f.width, f.height, s));
     launch_zpermute_cols<T>(dD, nbt, maxm, maxni, s);
     launch_zextract<T>(dD, nbt, maxni, maxe, trans, d_diag, d_zval, s);
     HS_HIP(hipGetLastError());
@@ -465,7 +627,7 @@ struct SelRun {
 };
 
 template <class T>
-void selinv_impl(const HsSelView& v, SelCache* c, int trans, void* diag, void* zval, int where, int64_t budget_bytes, hipStream_t s) {
+void selinv_impl(const HsSelView& v, SelCache* c, bool lrmode, int trans, void* diag, void* zval, int where, int64_t budget_bytes, hipStream_t s) {
   const int nf = (int)v.fronts.size();
   HS_HIP(hipStreamSynchronize(v.stream));  // the factors are written on the handle's stream
   HsScratch odiag, ozval;
@@ -490,7 +652,7 @@ void selinv_impl(const HsSelView& v, SelCache* c, int trans, void* diag, void* z
     HS_HIP(hipMemGetInfo(&fr, &tot));
     budget = (size_t)((double)fr * 0.85) + (v.sb ? v.sb_bytes : 0);
   }
-  SelRun<T> R{v, c, s, trans, d_diag, d_zval, budget};
+  SelRun<T> R{v, c, s, trans, d_diag, d_zval, budget, lrmode};
   R.kids.assign((size_t)nf, {});
   std::vector<int> roots;
   for (int f = 0; f < nf; ++f) {
@@ -507,6 +669,11 @@ void selinv_impl(const HsSelView& v, SelCache* c, int trans, void* diag, void* z
   HS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
   if (diag && !where) HS_HIP(hipMemcpy(diag, d_diag, sizeof(T) * (size_t)v.n, hipMemcpyDeviceToHost));
   if (zval && !where && v.nnz) HS_HIP(hipMemcpy(zval, d_zval, sizeof(T) * (size_t)v.nnz, hipMemcpyDeviceToHost));
+  if (lrmode) {
+    const double out[8] = {ms * 1e-3, R.flops, (double)R.peak, (double)R.batches, (double)R.lr_fronts, (double)R.max_rank, R.flops_dense, 0.0};
+    std::copy(out, out + 8, c->info_lr);
+    return;
+  }
   c->info[0] = ms * 1e-3;
   c->info[1] = R.flops;
   c->info[2] = (double)R.peak;
@@ -521,28 +688,56 @@ extern "C" int hs_logabsdet(hs_handle* F, double* logabs, double* sign2) {
            if (v.is_complex) logabsdet_impl<cplx>(v, logabs, sign2); else logabsdet_impl<double>(v, logabs, sign2));
 }
 
+// hs_selinv (lrmode = false) and hs_selinv_lr (true): the same arguments, the same checks before any device work; they differ in what
+// they do with a front that keeps low-rank Gauss transforms
+static void selinv_entry(const char* fn, bool lrmode, hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream) {
+  HsSelView v;
+  check_common(F, v, fn);
+  if (trans != 0 && trans != 1) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d must be 0 (entries of A^-1) or 1 (of its transpose)", fn, trans);
+  if (where != 0 && where != 1) HS_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: %s: where = %d must be 0 (host pointers) or 1 (device pointers)", fn, where);
+  if (!diag && !zval) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: diag and zval are both NULL, nothing to compute", fn);
+  if (budget_bytes < 0) HS_FAIL(HS_ERR_ARGUMENT, budget_bytes, "ArgumentError: %s: budget_bytes < 0", fn);
+  for (size_t i = 0; i < v.fronts.size(); ++i) {
+    const HsSelFront& x = v.fronts[i];
+    const int fl = x.flags;
+    if ((fl & HS_SEL_LOWRANK) && !lrmode)
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d keeps low-rank Gauss transforms L / R (compressed factorization); selected inversion needs the exact path (swlevel = 0)", fn, (int)i);
+    if (fl & HS_SEL_SLICE)
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d is eliminated in slices (hs_options.split)", fn, (int)i);
+    if (!(fl & HS_SEL_LOWRANK) || x.nb <= 0 || x.ni <= 0) continue;  // (without a boundary there are no transforms: the LU alone serves)
+    if (!x.lrL && !x.lrR)
+      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d is flagged for compression but holds no low-rank objects, and its dense panels Lbi / Uib do not survive the factorization", fn, (int)i);
+    // (LowRank<double> and LowRank<cplx> share their layout: pointers and ints)
+    for (const LowRank<double>* lr : {(const LowRank<double>*)x.lrL, (const LowRank<double>*)x.lrR}) {
+      if (!lr || lr->r <= 0) continue;
+      if (!lr->Cd || !lr->Z)
+        HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d holds a low-rank transform of rank %d without its dense factor (only the packed sketch is kept, HS_LR_QR=0 diagnostics)", fn, (int)i, lr->r);
+    }
+  }
+  SelCache* c = cache_of(v);
+  if (!c->built) build_cache(v, c);  // (host work and uploads of index lists only)
+  if (c->hole >= 0)
+    HS_FAIL(HS_ERR_UNSUPPORTED, c->hole, "%s: stored entry %lld of A (CSC order) lies outside every front's [int; bnd] block: the tree does not cover A's pattern, the pattern values of the inverse would have a hole", fn, c->hole);
+  if (c->hole_front >= 0)
+    HS_FAIL(HS_ERR_UNSUPPORTED, c->hole_front, "%s: the boundary of front %d is not contained in its parent's front (a root that keeps a boundary without a pseudo-root, or an inconsistent tree)", fn, c->hole_front);
+  hipStream_t s = stream ? (hipStream_t)stream : v.stream;
+  if (v.is_complex) selinv_impl<cplx>(v, c, lrmode, trans, diag, zval, where, budget_bytes, s);
+  else selinv_impl<double>(v, c, lrmode, trans, diag, zval, where, budget_bytes, s);
+}
+
 extern "C" int hs_selinv(hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream) {
-  HS_GUARD(HsSelView v; check_common(F, v, "hs_selinv");
-           if (trans != 0 && trans != 1) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_selinv: trans = %d must be 0 (entries of A^-1) or 1 (of its transpose)", trans);
-           if (where != 0 && where != 1) HS_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: hs_selinv: where = %d must be 0 (host pointers) or 1 (device pointers)", where);
-           if (!diag && !zval) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_selinv: diag and zval are both NULL, nothing to compute");
-           if (budget_bytes < 0) HS_FAIL(HS_ERR_ARGUMENT, budget_bytes, "ArgumentError: hs_selinv: budget_bytes < 0");
-           for (size_t i = 0; i < v.fronts.size(); ++i) {
-             const int fl = v.fronts[i].flags;
-             if (fl & HS_SEL_LOWRANK)
-               HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_selinv: front %d keeps low-rank Gauss transforms L / R (compressed factorization); selected inversion needs the exact path (swlevel = 0)", (int)i);
-             if (fl & HS_SEL_SLICE)
-               HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "hs_selinv: front %d is eliminated in slices (hs_options.split)", (int)i);
-           }
-           SelCache* c = cache_of(v);
-           if (!c->built) build_cache(v, c);  // (host work and uploads of index lists only)
-           if (c->hole >= 0)
-             HS_FAIL(HS_ERR_UNSUPPORTED, c->hole, "hs_selinv: stored entry %lld of A (CSC order) lies outside every front's [int; bnd] block: the tree does not cover A's pattern, the pattern values of the inverse would have a hole", c->hole);
-           if (c->hole_front >= 0)
-             HS_FAIL(HS_ERR_UNSUPPORTED, c->hole_front, "hs_selinv: the boundary of front %d is not contained in its parent's front (a root that keeps a boundary without a pseudo-root, or an inconsistent tree)", c->hole_front);
-           hipStream_t s = stream ? (hipStream_t)stream : v.stream;
-           if (v.is_complex) selinv_impl<cplx>(v, c, trans, diag, zval, where, budget_bytes, s);
-           else selinv_impl<double>(v, c, trans, diag, zval, where, budget_bytes, s));
+  HS_GUARD(selinv_entry("hs_selinv", false, F, trans, diag, zval, where, budget_bytes, stream));
+}
+
+extern "C" int hs_selinv_lr(hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream) {
+  HS_GUARD(selinv_entry("hs_selinv_lr", true, F, trans, diag, zval, where, budget_bytes, stream));
+}
+
+extern "C" int hs_selinv_lr_info(const hs_handle* F, double* out8) {
+  HS_GUARD(if (!F || !out8) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_selinv_lr_info: null argument");
+           HsSelView v; hs_selinv_view(const_cast<hs_handle*>(F), &v);
+           const SelCache* c = (const SelCache*)*v.sx;
+           for (int k = 0; k < 8; ++k) out8[k] = c ? c->info_lr[k] : 0.0);
 }
 
 extern "C" int hs_selinv_info(const hs_handle* F, double* out4) {

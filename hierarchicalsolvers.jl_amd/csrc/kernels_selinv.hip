@@ -2,6 +2,7 @@
 //
 //   logdet_kernel        per front: sum log|u_kk|, the phase of prod u_kk, the parity of the row permutation   (one launch per handle)
 //   zinit_kernel         Vi = I                                  (the right-hand side of U X = I; the rest of the work blocks is cleared by a memset)
+//   zload_lr_kernel      Vg = G, Tm[nit.., :] = Z_L'             (hs_selinv_lr: the stored low-rank factors are copied, the substitutions overwrite the copies)
 //   zgather_kernel       child Z[bnd, bnd] = parent Z[cmap, cmap]   (the reverse of scatter_kernel's extend-add)
 //   zpermute_cols_kernel Z[:, rperm[i]] = X2[:, i]                  (the trailing P of (T L^-1) P, fused with the write into the Z block)
 //   zextract_kernel      diag[fidx[i]] = Z[i, i];  zval[e] = Z[pr, pc] (or its transpose) for the entries of A the front owns
@@ -94,6 +95,55 @@ void launch_zinit(const SelDesc<T>* d, int nbatch, int maxni, hipStream_t s) {
   hipLaunchKernelGGL(zinit_kernel<T>, dim3((maxni + 255) / 256, nbatch), dim3(256), 0, s, d);
 }
 
+// hs_selinv_lr: the right-hand sides of a low-rank front's substitutions are COPIES of its stored factors (the substitutions overwrite
+// them): part 0 (blockIdx.z) copies G (ni x rR) into Vg = Vi + ni ldv, part 1 copies Z_L' (rL x ni) into rows nit.. of Tm.  A wave owns a
+// column at a time, its lanes run along the leading dimension.  Float64 moves two rows per lane as one 16-byte access when source and
+// destination column share their 16-byte phase (every ld is even, so all columns of a block have the phase of the first one): a scalar
+// head element up to the boundary, the pairs, a scalar tail; with different phases every access is 8 bytes.  ComplexF64 elements are
+// 16 bytes each.  A dense front of a mixed batch has rR = rL = 0 and leaves at once.
+template <class T>
+__device__ inline void zload_col(const T* __restrict__ src, T* __restrict__ dst, int rows, int lane) {
+  for (int r = lane; r < rows; r += 64) gst(dst + r, gld(src + r));
+}
+template <>
+__device__ inline void zload_col<double>(const double* __restrict__ src, double* __restrict__ dst, int rows, int lane) {
+  const unsigned ps = (unsigned)((uintptr_t)src & 15), pd = (unsigned)((uintptr_t)dst & 15);
+  if (ps != pd) {
+    for (int r = lane; r < rows; r += 64) gst(dst + r, gld(src + r));
+    return;
+  }
+  const int head = ps ? 1 : 0;  // (elements are 8-byte aligned: the phase is 0 or 8)
+  if (head && lane == 0 && rows > 0) gst(dst, gld(src));
+  const int pairs = (rows - head) / 2;
+  for (int q = lane; q < pairs; q += 64) {
+    const hs_d2u v = gld2(src + head + 2 * q);
+    *(hs_d2u HS_AS_GLOBAL*)(dst + head + 2 * q) = v;
+  }
+  const int done = head + 2 * pairs;
+  if (done < rows && lane == 0) gst(dst + done, gld(src + done));
+}
+template <class T>
+__global__ __launch_bounds__(256) void zload_lr_kernel(const SelDesc<T>* __restrict__ descs) {
+  const SelDesc<T> d = descs[blockIdx.y];
+  const T* src;
+  T* dst;
+  int rows, cols, lds, ldd;
+  if (blockIdx.z == 0) {
+    src = d.G; lds = d.ldg; dst = d.Vi + (size_t)d.ldv * d.ni; ldd = d.ldv; rows = d.ni; cols = d.rR;
+  } else {
+    src = d.ZL; lds = d.ldzl; dst = d.Tm + d.nit; ldd = d.ldt; rows = d.rL; cols = d.ni;
+  }
+  if (!src || rows <= 0 || cols <= 0) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = blockIdx.x * 4 + wave; c < cols; c += gridDim.x * 4) zload_col<T>(src + (size_t)c * lds, dst + (size_t)c * ldd, rows, lane);
+}
+template <class T>
+void launch_zload_lr(const SelDesc<T>* d, int nbatch, int maxni, int maxr, hipStream_t s) {
+  if (nbatch <= 0 || maxni <= 0 || maxr <= 0) return;
+  const int gx = std::min((std::max(maxni, maxr) + 3) / 4, 256);
+  hipLaunchKernelGGL(zload_lr_kernel<T>, dim3(gx, nbatch, 2), dim3(256), 0, s, d);
+}
+
 // A workgroup owns 256 destination rows a and ZG_COLS destination columns b: cmap of both ranges is staged in LDS once, then every
 // column is one contiguous store of 256 elements (the loads follow cmap, which is piecewise contiguous: the child's boundary keeps its
 // order inside the parent's interior and boundary parts).
@@ -169,6 +219,7 @@ void launch_zextract(const SelDesc<T>* d, int nbatch, int maxni, int maxe, int t
 
 #define HS_SEL_INST(T)                                                                          \
   template void launch_zinit<T>(const SelDesc<T>*, int, int, hipStream_t);                      \
+  template void launch_zload_lr<T>(const SelDesc<T>*, int, int, int, hipStream_t);              \
   template void launch_zgather<T>(const SelDesc<T>*, int, int, hipStream_t);                    \
   template void launch_zpermute_cols<T>(const SelDesc<T>*, int, int, int, hipStream_t);         \
   template void launch_zextract<T>(const SelDesc<T>*, int, int, int, int, T*, T*, hipStream_t);

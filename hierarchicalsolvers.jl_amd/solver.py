@@ -13,7 +13,8 @@ reference (Julia)                      here
 ``cond(A, p)`` (estimated)             :func:`condest`
 ``xGERFS`` (refine, berr, ferr)        :func:`ldiv_refine`, :func:`ldiv_refine_block`
 ``logabsdet(F)``, ``logdet``, ``det``  :func:`logabsdet`, :func:`logdet`, :func:`det` (``hs_selinv.hip``)
-selected inverse (no Julia name)       :func:`selinv`, :func:`selinv_diag`: ``diag(A^-1)`` and ``A^-1`` on the pattern of ``A``
+selected inverse (no Julia name)       :func:`selinv`, :func:`selinv_diag`: ``diag(A^-1)`` and ``A^-1`` on the pattern of ``A``;
+                                       :func:`selinv_lr`, :func:`selinv_lr_diag` for compressed factorizations
 ``eigs(A; nev, sigma)`` (Arpack)       :func:`eigs`: the eigenpairs of ``A`` nearest ``sigma`` from the factors of ``A - sigma*I`` (``hs_eigs.hip``)
 ``eigs(A, B; nev, sigma)`` (Arpack)    :func:`eigs` with ``M=B``: ``A x = lambda B x`` from the factors of ``A - sigma*B``
 partial factorization (no Julia name)  :func:`schur_complement`, :func:`condense`, :func:`interface_solve`, :func:`expand` (``hs_interface.hip``)
@@ -34,7 +35,7 @@ from . import _lib
 from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
-           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info",
+           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info", "selinv_lr", "selinv_lr_diag", "selinv_lr_info",
            "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "tangent", "gn_hessvec", "gn_diag", "gn_info", "eigs", "eigs_info", "eigs_gen_info", "interface_indices", "schur_complement", "condense", "interface_solve", "expand", "interface_info"]
 
 
@@ -1462,17 +1463,22 @@ def selinv(F, diag=True, pattern=True, budget=0):
     leaves, without the dense inverse.  ``diag=False`` / ``pattern=False`` return ``None`` in that place.  ``budget``: bytes of device
     scratch alive at a time (0: what the device has free).  ``transpose(F)`` / ``adjoint(F)`` give the selected inverse of ``A^T`` /
     ``A^H`` on the pattern of ``A`` (``Z[i, j] = (A^-1)[j, i]``, conjugated for the adjoint).  Compressed factorizations are refused
-    (``UnsupportedError``)."""
+    (``UnsupportedError``; :func:`selinv_lr` serves them)."""
+    return _selinv_call(_lib.lib().hs_selinv, "selinv", F, diag, pattern, budget)
+
+
+def _selinv_call(entry, name, F, diag, pattern, budget):
+    """What :func:`selinv` and :func:`selinv_lr` share: the output arrays, the call of ``entry`` and the return value."""
     F, trans = _unwrap(F)
     if not diag and not pattern:
-        raise ValueError("ArgumentError: selinv with diag=False and pattern=False computes nothing")
+        raise ValueError(f"ArgumentError: {name} with diag=False and pattern=False computes nothing")
     d = np.zeros(F.n, dtype=F.dtype) if diag else None
     z = None
     if pattern:
         if F._pattern is None:
             raise ValueError("ArgumentError: this FactorNode does not know the pattern of its matrix")
         z = np.zeros(len(F._pattern[1]), dtype=F.dtype)
-    _lib.check(_lib.lib().hs_selinv(F._h, 1 if trans else 0, d.ctypes.data if diag else None, z.ctypes.data if pattern else None, 0, int(budget), None))
+    _lib.check(entry(F._h, 1 if trans else 0, d.ctypes.data if diag else None, z.ctypes.data if pattern else None, 0, int(budget), None))
     if trans == 2 and F.dtype.kind == "c":
         d = d.conj() if diag else None
         z = z.conj() if pattern else None
@@ -1492,6 +1498,32 @@ def selinv_info(F):
     out = np.zeros(4)
     _lib.check(_lib.lib().hs_selinv_info(F._h, _pf64(out)))
     return dict(seconds=float(out[0]), flops=float(out[1]), peak_bytes=float(out[2]), batches=int(out[3]))
+
+
+def selinv_lr(F, diag=True, pattern=True, budget=0):
+    """Selected inverse of a compressed factorization (``hs_selinv_lr``), with the arguments and the return value of :func:`selinv`:
+    ``diag(F^-1)`` and ``F^-1`` on the pattern of ``A``, ``F`` being the operator the solves apply.  The recurrence runs through the
+    low-rank Gauss transforms of the compressed fronts (substitutions on ``rank`` columns instead of ``|bnd|``), dense fronts run
+    :func:`selinv`'s; on an exact factorization it returns :func:`selinv`'s bits.  ``transpose(F)`` gives ``F^-T`` on the pattern: the
+    gradient of :func:`logabsdet` with respect to the entries of ``A``.  Refused (``UnsupportedError``): HSS interior blocks
+    (``mf = 2, 3``, ``hss_d``), sliced fronts, several ranks."""
+    return _selinv_call(_lib.lib().hs_selinv_lr, "selinv_lr", F, diag, pattern, budget)
+
+
+def selinv_lr_diag(F, budget=0):
+    """``diag(F^-1)`` of a compressed factorization by :func:`selinv_lr`."""
+    return selinv_lr(F, diag=True, pattern=False, budget=budget)[0]
+
+
+def selinv_lr_info(F):
+    """Figures of the last :func:`selinv_lr` call on ``F`` (``hs_selinv_lr_info``): device seconds, real flops executed, peak scratch
+    bytes, batches of fronts, fronts served through low-rank transforms, the largest rank used, and the flops :func:`selinv`'s dense-form
+    recurrence would execute on the same front shapes (a host count).  :func:`selinv_info` keeps its own figures."""
+    F, _ = _unwrap(F)
+    out = np.zeros(8)
+    _lib.check(_lib.lib().hs_selinv_lr_info(F._h, _pf64(out)))
+    return dict(seconds=float(out[0]), flops=float(out[1]), peak_bytes=float(out[2]), batches=int(out[3]), lowrank_fronts=int(out[4]),
+                max_rank=int(out[5]), flops_dense_form=float(out[6]))
 
 
 # ---- Schur-complement mode (hs_interface.hip): the interface matrix, condense and expand solves --------------------------------------

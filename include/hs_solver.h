@@ -609,6 +609,22 @@ int hs_logabsdet(hs_handle* F, double* logabs, double* sign2);
 int hs_selinv(hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream);
 /* the last hs_selinv call of the handle: out4 = {seconds on the device, flops executed (real), peak scratch bytes, batches of fronts} */
 int hs_selinv_info(const hs_handle* F, double* out4);
+/* Selected inverse of a compressed factorization (swlevel != 0): the arguments, their meanings and their checks are hs_selinv's; the result
+ * is diag(F^-1) and F^-1 on A's pattern, F the operator the solves apply (trans = 1 with hs_logabsdet gives the gradient of log|det F| with
+ * respect to A's entries).  A compressed front keeps Uib ~= G Z_R (ni x rR, rR x nb), Lbi ~= C_L Z_L' (nb x rL, rL x ni) and the pivoted LU
+ * of Aii; with W = U^-1 G and Y = Z_L' L^-1 P the recurrence reads Z[int, bnd] = -W (Z_R Zbb), Z[bnd, int] = -(Zbb C_L) Y,
+ * Z[int, int] = Aii^-1 + W (Z_R Zbb C_L) Y: the substitutions run on rR columns and ni + rL rows, the products through r-wide blocks.  Dense
+ * fronts of the same handle (leaves, fronts below swsize) run hs_selinv's recurrence in the same launches; on an exact handle the call
+ * issues hs_selinv's launches and returns its bits.  The factors are only read (their low-rank parts are copied before a substitution
+ * overwrites them).  Served: single-rank handles whose fronts keep a dense pivoted LU of Aii and are dense or low-rank with dense factors
+ * (the default compressed flow and hs_options.mf = 1).  Refused with HS_ERR_UNSUPPORTED before any device work: fronts that keep D as an
+ * HSS matrix (hs_options.hss_d, mf = 2, 3), fronts eliminated in slices, factorizations over more than one rank, a low-rank transform that
+ * keeps only its packed sketch (HS_LR_QR=0 diagnostics), and the two pattern / tree holes hs_selinv reports. */
+int hs_selinv_lr(hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream);
+/* the last hs_selinv_lr call of the handle: out8 = {seconds on the device, flops executed (real), peak scratch bytes, batches of fronts,
+ * fronts served through low-rank transforms, largest rank used, flops the dense-form recurrence of hs_selinv would execute on the same front
+ * shapes (counted on the host), 0}.  hs_selinv_info and hs_selinv_lr_info keep separate figures. */
+int hs_selinv_lr_info(const hs_handle* F, double* out8);
 
 /* ---- Schur-complement mode: the interface matrix, condense and expand solves (hs_interface.hip) --------------------------------------
  * The interface b is the boundary the ROOT of the tree keeps (root.bnd; hs.problems.graph_nested_dissection(..., interface=...) builds such
