@@ -1804,11 +1804,9 @@ static void ldiv_block_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const 
 // (HsMultiView::hss_front).  With t = B[int, :], Abi ~ C_L Z_L, Aib ~ C_R Z_R and W = D^-1 C_R (x.hW):
 //   trans = 0   forward:  t = D^-1 t,  B[int] = t,  B[bnd] -= C_L (Z_L t)            backward:  B[int] = t - W (Z_R B[bnd])
 //   trans = 1,2 forward:  B[bnd] -= op(Z_R)^T (op(W)^T t)   (no solve with D)        backward:  B[int] = op(D)^-T (t - op(Z_L)^T (op(C_L)^T B[bnd]))
-// op(D)^-T is ONE transposed ULV solve (hs_hss_ldiv_t), or for the 2 x 2 block form (x.mfb: hss = A11, hss2 = S22, W12 = A11^-1 C12):
-//   b2 -= op(Z12)^T (op(W12)^T b1);  x2 = op(S22)^-T b2;  b1 -= op(Z21)^T (op(C21)^T x2);  x1 = op(A11)^-T b1.
-// t lives in B[int] between the sweeps: the interior rows of a front belong to it alone.  Products with a transposed factor run on the
-// grouped kernel of kernels_ulv_t.hip, the others on the MFMA GEMM.
-#include "hs_ulv_t.h"
+// The solve with D in either direction is hss_d_solve (hs_hssfront.h): one ULV solve, or the 2 x 2 block form of mf = 3.  t lives in B[int]
+// between the sweeps: the interior rows of a front belong to it alone.  Every product is one hss_front_prod: with a transposed factor on the
+// grouped kernel of kernels_ulv_t.hip, else on the MFMA GEMM.
 template <class T>
 struct UlvCtx {
   hs_handle* h;
@@ -1828,45 +1826,27 @@ static void ulv_front(void* ctx_, int id, int sweep, int trans, void* B_, long l
   const LowRank<T>* lrL = (const LowRank<T>*)x.lrL;
   const LowRank<T>* lrR = (const LowRank<T>*)x.lrR;
   const int rL = (nb > 0 && lrL) ? lrL->r : 0, rR = (nb > 0 && lrR && x.hW) ? lrR->r : 0;
-  const int cj = (trans == 2 && sizeof(T) == 16) ? 1 : 0;
-  // C = Cin - op(A)^T X / C = op(A)^T X, A stored K x M
-  auto prod_t = [&](const T* A, int lda, int K, int M, const T* X, int ldx, T* C, int ldc, bool minus) {
-    if (K <= 0 || M <= 0) return;
-    UlvTJob<T> j{A, X, minus ? C : nullptr, C, M, K, kc, lda, ldx, ldc, ldc, cj, HS_ULVT_FULL};
-    HS_HIP(hipMemcpyAsync(w.desc, &j, sizeof j, hipMemcpyHostToDevice, s));
-    HS_HIP(hipStreamSynchronize(s));
-    launch_ulv_t<T>((const UlvTJob<T>*)w.desc, 1, M, kc, s);
-  };
-  // C = A X / C -= A X, A stored M x K
-  auto prod_n = [&](const T* A, int lda, int M, int K, const T* X, int ldx, T* C, int ldc, bool minus) {
-    if (K <= 0 || M <= 0) return;
-    GemmProb<T> g{A, X, C, M, kc, K, lda, ldx, ldc};
-    HS_HIP(hipMemcpyAsync(w.desc, &g, sizeof g, hipMemcpyHostToDevice, s));
-    HS_HIP(hipStreamSynchronize(s));
-    launch_gemm_probs<T>((const GemmProb<T>*)w.desc, 1, M, kc, minus ? 1 : 0, s);
-  };
-  auto hsolve_t = [&](void* H, T* b) {
-    int st = hs_hss_set_stream((hs_hss*)H, (void*)s);
-    if (st == 0) st = hs_hss_ldiv_t((hs_hss*)H, trans, (double*)b, w.ldt, kc, 1);
-    HS_CHECK(st);
+  // C (-)= A X (trans = 0) / C (-)= op(A)^T X, A stored rows x cols: one product at a time through the slot at the head of the slab
+  auto prod = [&](const T* A, int lda, int rows, int cols, const T* X, int ldx, T* C, int ldc, bool minus) {
+    hss_front_prod<T>(w.desc, trans, A, lda, rows, cols, X, ldx, C, ldc, kc, minus, s);
   };
   T *t = w.t, *xb = w.xb, *u = w.u;
   if (trans == 0) {
     if (sweep == 0) {
       launch_ulv_rows<T>(iidx, ni, kc, B, ldb, t, w.ldt, 0, s);
-      hss_d_solve<T>(h, x, t, w.ldt, kc, s);
+      hss_d_solve<T>(h, x, 0, t, w.ldt, kc, s);
       launch_ulv_rows<T>(iidx, ni, kc, t, w.ldt, B, ldb, 1, s);
       if (rL > 0) {
-        prod_n(lrL->Z, lrL->ldz, rL, ni, t, w.ldt, u, w.ldu, false);
+        prod(lrL->Z, lrL->ldz, rL, ni, t, w.ldt, u, w.ldu, false);
         launch_ulv_rows<T>(bidx, nb, kc, B, ldb, xb, w.ldx, 0, s);
-        prod_n(lrL->Cd, lrL->ldc, nb, rL, u, w.ldu, xb, w.ldx, true);
+        prod(lrL->Cd, lrL->ldc, nb, rL, u, w.ldu, xb, w.ldx, true);
         launch_ulv_rows<T>(bidx, nb, kc, xb, w.ldx, B, ldb, 1, s);
       }
     } else if (rR > 0) {
       launch_ulv_rows<T>(bidx, nb, kc, B, ldb, xb, w.ldx, 0, s);
-      prod_n(lrR->Z, lrR->ldz, rR, nb, xb, w.ldx, u, w.ldu, false);
+      prod(lrR->Z, lrR->ldz, rR, nb, xb, w.ldx, u, w.ldu, false);
       launch_ulv_rows<T>(iidx, ni, kc, B, ldb, t, w.ldt, 0, s);
-      prod_n((const T*)x.hW, x.hldw, ni, rR, u, w.ldu, t, w.ldt, true);
+      prod((const T*)x.hW, x.hldw, ni, rR, u, w.ldu, t, w.ldt, true);
       launch_ulv_rows<T>(iidx, ni, kc, t, w.ldt, B, ldb, 1, s);
     }
     return;
@@ -1874,9 +1854,9 @@ static void ulv_front(void* ctx_, int id, int sweep, int trans, void* B_, long l
   if (sweep == 0) {
     if (rR > 0) {
       launch_ulv_rows<T>(iidx, ni, kc, B, ldb, t, w.ldt, 0, s);
-      prod_t((const T*)x.hW, x.hldw, ni, rR, t, w.ldt, u, w.ldu, false);   // u = op(W)^T t
+      prod((const T*)x.hW, x.hldw, ni, rR, t, w.ldt, u, w.ldu, false);   // u = op(W)^T t
       launch_ulv_rows<T>(bidx, nb, kc, B, ldb, xb, w.ldx, 0, s);
-      prod_t(lrR->Z, lrR->ldz, rR, nb, u, w.ldu, xb, w.ldx, true);         // B[bnd] -= op(Z_R)^T u
+      prod(lrR->Z, lrR->ldz, rR, nb, u, w.ldu, xb, w.ldx, true);         // B[bnd] -= op(Z_R)^T u
       launch_ulv_rows<T>(bidx, nb, kc, xb, w.ldx, B, ldb, 1, s);
     }
     return;
@@ -1884,21 +1864,10 @@ static void ulv_front(void* ctx_, int id, int sweep, int trans, void* B_, long l
   launch_ulv_rows<T>(iidx, ni, kc, B, ldb, t, w.ldt, 0, s);
   if (rL > 0) {
     launch_ulv_rows<T>(bidx, nb, kc, B, ldb, xb, w.ldx, 0, s);
-    prod_t(lrL->Cd, lrL->ldc, nb, rL, xb, w.ldx, u, w.ldu, false);         // u = op(C_L)^T B[bnd]
-    prod_t(lrL->Z, lrL->ldz, rL, ni, u, w.ldu, t, w.ldt, true);            // t -= op(Z_L)^T u
+    prod(lrL->Cd, lrL->ldc, nb, rL, xb, w.ldx, u, w.ldu, false);         // u = op(C_L)^T B[bnd]
+    prod(lrL->Z, lrL->ldz, rL, ni, u, w.ldu, t, w.ldt, true);            // t -= op(Z_L)^T u
   }
-  if (!x.mfb) {
-    hsolve_t(x.hss, t);
-  } else {
-    const int n1 = x.ni1, n2 = ni - x.ni1, k12 = x.bk12, k21 = x.bk21;
-    T *b1 = t, *b2 = t + n1;
-    prod_t((const T*)x.bW12, x.bldw, n1, k12, b1, w.ldt, u, w.ldu, false);
-    prod_t((const T*)x.bZ12, x.bldz12, k12, n2, u, w.ldu, b2, w.ldt, true);
-    hsolve_t(x.hss2, b2);
-    prod_t((const T*)x.bC21, x.bldc21, n2, k21, b2, w.ldt, u, w.ldu, false);
-    prod_t((const T*)x.bZ21, x.bldz21, k21, n1, u, w.ldu, b1, w.ldt, true);
-    hsolve_t(x.hss, b1);
-  }
+  hss_d_solve<T>(h, x, trans, t, w.ldt, kc, s);
   launch_ulv_rows<T>(iidx, ni, kc, t, w.ldt, B, ldb, 1, s);
 }
 // everything hs_ldiv_ulv_* refuses, before any device work and before C is written; true: the handle has fronts with an HSS interior block
@@ -1943,15 +1912,14 @@ static void ulv_run(hs_handle* h, int trans, T* dC, int64_t ldc, int64_t nrhs, h
   w.h = h;
   w.ldt = (int)((mni + 1) / 2 * 2); w.ldx = (int)((mnb + 1) / 2 * 2); w.ldu = (int)((mr + 1) / 2 * 2);
   const size_t el = ((size_t)w.ldt + w.ldx + w.ldu) * KC + 64;
-  const size_t bytes = el * sizeof(T) + 256;
+  const size_t bytes = el * sizeof(T) + HS_FRONT_SLOT;
   HsScratch scratch(bytes, "ULV block solve front scratch");
   HsDrain drain{s};
   char* slab = (char*)scratch.p;
   w.desc = slab;
-  w.t = (T*)(slab + 256);
+  w.t = (T*)(slab + HS_FRONT_SLOT);
   w.xb = w.t + (size_t)w.ldt * KC;
   w.u = w.xb + (size_t)w.ldx * KC;
-  static_assert(sizeof(UlvTJob<T>) <= 256 && sizeof(GemmProb<T>) <= 256, "job descriptions fit the head of the slab");
   v.hss_front = &ulv_front<T>;
   v.hss_ctx = &w;
   hs_solve_multi_run<T>(v, trans, dC, ldc, nrhs, s);

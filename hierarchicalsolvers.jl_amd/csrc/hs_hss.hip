@@ -1813,25 +1813,32 @@ bool compress_fixed(HssT<T>& H, std::vector<CBlock<T>>& cb, int k, BlockOp<T>* b
 // ------------------------------------------------------------------------------------------------
 // Y = H * X
 // ------------------------------------------------------------------------------------------------
-template <class T>
-void hss_mul_p(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans);
-// Y = H * X (trans: H^T * X, plain transpose) in the caller's index order: the tree works on the permuted vectors
-template <class T>
-void hss_mul(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans = false) {
+// The tree works in its own order (H ~= A[perm, perm], a symmetric permutation): body(X', ldx', Y', ldy') runs on the caller's blocks when H
+// keeps no permutation, else on gathered copies whose result is scattered back into Y.  X == Y: in place, one copy serves both.
+template <class T, class F>
+void in_tree_order(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, F&& body) {
   if (!H.perm) {
-    hss_mul_p(H, X, ldx, Y, ldy, q, trans);
+    body(X, ldx, Y, ldy);
     return;
   }
   Pool tmp(global_cache());
   const int ld = ev(H.n);
   T* Xp = tmp.get<T>((size_t)ld * q);
-  T* Yp = tmp.get<T>((size_t)ld * q);
+  T* Yp = X == Y ? Xp : tmp.get<T>((size_t)ld * q);
   std::vector<RowJob<T>> rows{RowJob<T>{X, ldx, Xp, ld, H.perm, H.n, q, ROW_GATHER}};
   run_rows(tmp, rows, H.s);
-  hss_mul_p(H, Xp, ld, Yp, ld, q, trans);
+  body(Xp, ld, Yp, ld);
   rows.push_back(RowJob<T>{Yp, ld, Y, ldy, H.perm, H.n, q, ROW_SCATTER});
   run_rows(tmp, rows, H.s);
   HS_HIP(hipStreamSynchronize(H.s));
+}
+
+template <class T>
+void hss_mul_p(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans);
+// Y = H * X (trans: H^T * X, plain transpose) in the caller's index order
+template <class T>
+void hss_mul(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans = false) {
+  in_tree_order(H, X, ldx, Y, ldy, q, [&](const T* x, int lx, T* y, int ly) { hss_mul_p(H, x, lx, y, ly, q, trans); });
 }
 template <class T>
 void hss_mul_p(HssT<T>& H, const T* X, int ldx, T* Y, int ldy, int q, bool trans) {
@@ -2300,106 +2307,9 @@ NodeDesc<T> rhs_desc(const NodeDesc<T>& f, T* B, int ldb, int q) {
   return d;
 }
 
+// the grouped product C = Cin - op(A)^T X of kernels_ulv_t.hip (a stored block read along its columns), one launch per level and step
 template <class T>
-void hss_ldiv_p(HssT<T>& H, T* B, int ldb, int q);
-template <class T>
-void hss_ldiv(HssT<T>& H, T* B, int ldb, int q) {
-  if (!H.perm) {
-    hss_ldiv_p(H, B, ldb, q);
-    return;
-  }
-  Pool tmp(global_cache());
-  const int ld = ev(H.n);
-  T* Bp = tmp.get<T>((size_t)ld * q);
-  std::vector<RowJob<T>> rows{RowJob<T>{B, ldb, Bp, ld, H.perm, H.n, q, ROW_GATHER}};
-  run_rows(tmp, rows, H.s);
-  hss_ldiv_p(H, Bp, ld, q);
-  rows.push_back(RowJob<T>{Bp, ld, B, ldb, H.perm, H.n, q, ROW_SCATTER});
-  run_rows(tmp, rows, H.s);
-  HS_HIP(hipStreamSynchronize(H.s));
-}
-template <class T>
-void hss_ldiv_p(HssT<T>& H, T* B, int ldb, int q) {
-  hipStream_t s = H.s;
-  auto& nd = H.nd;
-  const int N = (int)nd.size();
-  Pool tmp(global_cache());
-  std::vector<RowJob<T>> rows;
-  std::vector<GemmProb<T>> gemms;
-  std::vector<NodeDesc<T>> descs;
-  if (nd[0].left < 0) {
-    descs.push_back(rhs_desc(H.rootfd, B, ldb, q));
-    tri_solve_batch(tmp, descs, q, true, true, s);
-    HS_HIP(hipStreamSynchronize(s));
-    return;
-  }
-  std::vector<T*> BH(N, nullptr), YR(N, nullptr);
-  std::vector<int> ldh(N, 0), ldy(N, 0);
-  for (int i = 0; i < N; ++i) {
-    if (nd[i].left >= 0) {
-      ldh[i] = ev(nd[i].m);
-      BH[i] = tmp.get<T>((size_t)ldh[i] * q);
-    }
-    if (i != 0) {
-      ldy[i] = ev(nd[i].m - nd[i].r);
-      YR[i] = tmp.get<T>((size_t)ldy[i] * q);
-    }
-  }
-  // forward: leaves to root
-  for (int lv = H.nlev - 1; lv >= 1; --lv) {
-    std::vector<GemmProb<T>> g2;
-    for (int i : H.lev[lv]) {
-      const HNode<T>& x = nd[i];
-      const int par = x.parent, r = x.r, nR = x.m - r;
-      const T* src = x.left < 0 ? B + x.lo : BH[i];
-      const int lds = x.left < 0 ? ldb : ldh[i];
-      T* slot = BH[par] + x.off_in_parent;
-      rows.push_back(RowJob<T>{src, lds, slot, ldh[par], x.p, r, q, ROW_GATHER});
-      if (nR > 0) {
-        rows.push_back(RowJob<T>{src, lds, YR[i], ldy[i], x.p + r, nR, q, ROW_GATHER});
-        gemms.push_back(GemmProb<T>{x.Tm, slot, YR[i], nR, q, r, x.ldt, ldh[par], ldy[i]});  // b_R -= T b_S
-        descs.push_back(rhs_desc(x.fd, YR[i], ldy[i], q));                                    // y = L^-1 P b_R
-        g2.push_back(GemmProb<T>{x.fd.LF + nR, YR[i], slot, r, q, nR, x.fd.ldl, ldy[i], ldh[par]});  // b_S -= (X_SR U^-1) y
-      }
-    }
-    run_rows(tmp, rows, s);
-    run_gemms(tmp, gemms, 1, s);
-    tri_solve_batch(tmp, descs, q, true, false, s);
-    run_gemms(tmp, g2, 1, s);
-  }
-  descs.push_back(rhs_desc(H.rootfd, BH[0], ldh[0], q));
-  tri_solve_batch(tmp, descs, q, true, true, s);
-  // backward: root to leaves
-  for (int lv = 1; lv < H.nlev; ++lv) {
-    std::vector<GemmProb<T>> g2;
-    for (int i : H.lev[lv]) {
-      const HNode<T>& x = nd[i];
-      const int par = x.parent, r = x.r, nR = x.m - r;
-      T* slot = BH[par] + x.off_in_parent;
-      T* dst = x.left < 0 ? B + x.lo : BH[i];
-      const int ldd = x.left < 0 ? ldb : ldh[i];
-      if (nR > 0) {
-        gemms.push_back(GemmProb<T>{x.fd.UR, slot, YR[i], nR, q, r, x.fd.ldu, ldh[par], ldy[i]});  // y -= (L^-1 P X_RS) x'_S
-        descs.push_back(rhs_desc(x.fd, YR[i], ldy[i], q));                                          // x'_R = U^-1 y
-        g2.push_back(GemmProb<T>{x.Tt, YR[i], slot, r, q, nR, x.ldtt, ldy[i], ldh[par]});           // x_S = x'_S - T^T x'_R
-        rows.push_back(RowJob<T>{YR[i], ldy[i], dst, ldd, x.p + r, nR, q, ROW_SCATTER});
-      }
-      rows.push_back(RowJob<T>{slot, ldh[par], dst, ldd, x.p, r, q, ROW_SCATTER});
-    }
-    run_gemms(tmp, gemms, 1, s);
-    tri_solve_batch(tmp, descs, q, false, true, s);
-    run_gemms(tmp, g2, 1, s);
-    run_rows(tmp, rows, s);
-  }
-  HS_HIP(hipStreamSynchronize(s));
-}
-
-// ---- H^-T B / H^-H B from the same stored factors (hs_hss_ldiv_t; DESIGN.md, "transposed ULV solves") ----------------------------------
-// Every non-root node keeps ONE skeleton for rows and columns, so E^T = F and F^T = E for E = [I -T; 0 I], F = [I 0; -T^T I] and the local
-// matrix M = E^-1 X F^-1 has M^T = E^-1 X^T F^-1: the transposed elimination is the same tree walk with every stored block read along its
-// other index -- the grouped product C = Cin - op(A)^T X of kernels_ulv_t.hip, one launch per level and step.
-template <class T>
-void run_ulv_t(Pool& tmp, std::vector<UlvTJob<T>>& jobs, hipStream_t s) {
+void run_ulv_t(Pool& tmp,std::vector<UlvTJob<T>>& jobs, hipStream_t s) {
   std::vector<UlvTJob<T>> live;
   int mM = 0, mN = 0;
   for (auto& j : jobs)
@@ -2453,32 +2363,89 @@ void ulv_t_tri(Pool& tmp, const std::vector<UlvTri<T>>& v, int q, int cj, bool u
   }
 }
 
-// B <- op(H)^-T B in the tree's own order, op = conj when cj
+// ---- B <- H^-1 B, H^-T B, H^-H B: one walk over the tree, from one set of stored factors ("transposed ULV solves") --------------
+// A non-root node keeps its r skeleton rows S in its parent's block and eliminates its nR = m - r other rows R with its front P X_RR = L U.
+// Leaves to root and root to leaves alike, a node runs   y -= A1 b_S;   the triangular step y -> z;   b_S -= A2 z   (y, z: nR rows).  A node
+// stores two pairs of blocks, (Tm = T | Tt = T^T) and (LF[nR:] = X_SR U^-1 | UR = L^-1 P X_RS).  It keeps ONE skeleton for rows and columns, so
+// E^T = F and F^T = E for E = [I -T; 0 I], F = [I 0; -T^T I], and M = E^-1 X F^-1 has M^T = E^-1 X^T F^-1: the transposed elimination reads the
+// other block of each pair, along its other index.  A direction supplies only that choice, its kind of product and its triangular step:
+//           up: A1   step              A2         down: A1       step                         A2     product
+//   UlvN        Tm   y <- L^-1 P y     LF[nR:]          UR       y <- U^-1 y                  Tt     C -= A X, the MFMA GEMM
+//   UlvT        Tt   z = op(U)^-T y    UR               LF[nR:]  z <- P^T op(L)^-T z (via y)  Tm     C -= op(A)^T X, kernels_ulv_t.hip
+// UlvN works in place (z is y), UlvT out of place; the root block is one full solve of the direction's own (`root`).
 template <class T>
-void hss_ldiv_t_p(HssT<T>& H, T* B, int ldb, int q, int cj) {
+struct Blk {
+  const T* p;
+  int ld;
+};
+template <class T>
+struct UlvN {
+  static constexpr bool in_place = true;
+  static constexpr int up = 0;  // which block of a pair the sweep to the root reads; the sweep back reads the other
+  Pool& tmp;
+  int q;
+  hipStream_t s;
+  std::vector<GemmProb<T>> g[2];
+  std::vector<NodeDesc<T>> descs;
+  void prod(int k, Blk<T> A, const T* X, int ldx, T* C, int ldc, int M, int K) { g[k].push_back(GemmProb<T>{A.p, X, C, M, q, K, A.ld, ldx, ldc}); }
+  void tri(const NodeDesc<T>& f, T* y, T*, int ld, bool) { descs.push_back(rhs_desc(f, y, ld, q)); }
+  void run_prod(int k) { run_gemms(tmp, g[k], 1, s); }
+  void run_tri(bool down) { tri_solve_batch(tmp, descs, q, !down, down, s); }
+  void root(const NodeDesc<T>& f, T* b, int ld) {
+    descs.push_back(rhs_desc(f, b, ld, q));
+    tri_solve_batch(tmp, descs, q, true, true, s);
+  }
+};
+template <class T>
+struct UlvT {
+  static constexpr bool in_place = false;
+  static constexpr int up = 1;
+  Pool& tmp;
+  int q;
+  hipStream_t s;
+  int cj;  // op = conj
+  std::vector<UlvTJob<T>> j[2];
+  std::vector<UlvTri<T>> tris;
+  std::vector<RowJob<T>> perm;
+  void prod(int k, Blk<T> A, const T* X, int ldx, T* C, int ldc, int M, int K) {
+    j[k].push_back(UlvTJob<T>{A.p, X, C, C, M, K, q, A.ld, ldx, ldc, ldc, cj, HS_ULVT_FULL});
+  }
+  void tri(const NodeDesc<T>& f, T* y, T* z, int ld, bool down) {
+    if (!down) {
+      tris.push_back(UlvTri<T>{&f, y, ld, z, ld});
+      return;
+    }
+    tris.push_back(UlvTri<T>{&f, z, ld, y, ld});  // y is free again: it takes op(L)^-T z, z then takes P^T of it
+    perm.push_back(RowJob<T>{y, ld, z, ld, f.rperm, f.ni, q, ROW_SCATTER});
+  }
+  void run_prod(int k) { run_ulv_t(tmp, j[k], s); }
+  void run_tri(bool down) {
+    ulv_t_tri(tmp, tris, q, cj, !down, s);
+    tris.clear();
+    run_rows(tmp, perm, s);
+  }
+  // M0^T x = b with P M0 = L0 U0, i.e. x = P^T op(L0)^-T op(U0)^-T b: `b` is used up, `z` and `w` are scratch, the result goes to b
+  void root(const NodeDesc<T>& f, T* b, int ld) {
+    const int ldz = ev(f.ni);
+    T* z = tmp.get<T>((size_t)ldz * q);
+    tris.assign(1, UlvTri<T>{&f, b, ld, z, ldz});
+    ulv_t_tri(tmp, tris, q, cj, true, s);
+    T* w = tmp.get<T>((size_t)ldz * q);
+    tris.assign(1, UlvTri<T>{&f, z, ldz, w, ldz});
+    ulv_t_tri(tmp, tris, q, cj, false, s);
+    tris.clear();
+    perm.push_back(RowJob<T>{w, ldz, b, ld, f.rperm, f.ni, q, ROW_SCATTER});  // x[rperm[i]] = w[i]
+    run_rows(tmp, perm, s);
+  }
+};
+
+// B <- op(H)^-1 B in the tree's own order, op as `op` has it
+template <class T, class Ops>
+void ulv_walk(HssT<T>& H, T* B, int ldb, int q, Pool& tmp, Ops& op) {
   hipStream_t s = H.s;
   auto& nd = H.nd;
   const int N = (int)nd.size();
-  Pool tmp(global_cache());
   std::vector<RowJob<T>> rows;
-  std::vector<UlvTJob<T>> j1, j2;
-  // the last block: M0^T x = b with P M0 = L0 U0, i.e. x = P^T op(L0)^-T op(U0)^-T b; `b` is used up, `z` is scratch, the result goes to b
-  auto root = [&](T* b, int ld) {
-    const int m = H.root_m, ldz = ev(m);
-    T* z = tmp.get<T>((size_t)ldz * q);
-    std::vector<UlvTri<T>> v{UlvTri<T>{&H.rootfd, b, ld, z, ldz}};
-    ulv_t_tri(tmp, v, q, cj, true, s);
-    T* w = tmp.get<T>((size_t)ldz * q);
-    v[0] = UlvTri<T>{&H.rootfd, z, ldz, w, ldz};
-    ulv_t_tri(tmp, v, q, cj, false, s);
-    rows.push_back(RowJob<T>{w, ldz, b, ld, H.rootfd.rperm, m, q, ROW_SCATTER});  // x[rperm[i]] = w[i]
-    run_rows(tmp, rows, s);
-  };
-  if (nd[0].left < 0) {
-    root(B, ldb);
-    HS_HIP(hipStreamSynchronize(s));
-    return;
-  }
   std::vector<T*> BH(N, nullptr), YR(N, nullptr), ZR(N, nullptr);
   std::vector<int> ldh(N, 0), ldy(N, 0);
   for (int i = 0; i < N; ++i) {
@@ -2489,76 +2456,79 @@ void hss_ldiv_t_p(HssT<T>& H, T* B, int ldb, int q, int cj) {
     if (i != 0) {
       ldy[i] = ev(nd[i].m - nd[i].r);
       YR[i] = tmp.get<T>((size_t)ldy[i] * q);
-      ZR[i] = tmp.get<T>((size_t)ldy[i] * q);
+      ZR[i] = Ops::in_place ? YR[i] : tmp.get<T>((size_t)ldy[i] * q);
     }
   }
-  std::vector<UlvTri<T>> tri;
-  // forward: leaves to root
+  // the m rows of a node: a leaf's lie in B, an inner node's in its own block (a single leaf is the root block itself)
+  auto own = [&](int i) { return nd[i].left < 0 ? std::pair<T*, int>(B + nd[i].lo, ldb) : std::pair<T*, int>(BH[i], ldh[i]); };
+  auto pairs = [&](const HNode<T>& x, Blk<T>* t, Blk<T>* f) {
+    t[0] = Blk<T>{x.Tm, x.ldt}, t[1] = Blk<T>{x.Tt, x.ldtt};
+    f[0] = Blk<T>{x.fd.LF + (x.m - x.r), x.fd.ldl}, f[1] = Blk<T>{x.fd.UR, x.fd.ldu};
+  };
+  constexpr int up = Ops::up, dn = 1 - Ops::up;
+  Blk<T> t[2], f[2];
+  // leaves to root
   for (int lv = H.nlev - 1; lv >= 1; --lv) {
     for (int i : H.lev[lv]) {
       const HNode<T>& x = nd[i];
       const int par = x.parent, r = x.r, nR = x.m - r;
-      const T* src = x.left < 0 ? B + x.lo : BH[i];
-      const int lds = x.left < 0 ? ldb : ldh[i];
+      const std::pair<T*, int> src = own(i);
       T* slot = BH[par] + x.off_in_parent;
-      rows.push_back(RowJob<T>{src, lds, slot, ldh[par], x.p, r, q, ROW_GATHER});
+      rows.push_back(RowJob<T>{src.first, src.second, slot, ldh[par], x.p, r, q, ROW_GATHER});
       if (nR > 0) {
-        rows.push_back(RowJob<T>{src, lds, YR[i], ldy[i], x.p + r, nR, q, ROW_GATHER});
-        j1.push_back(UlvTJob<T>{x.Tt, slot, YR[i], YR[i], nR, r, q, x.ldtt, ldh[par], ldy[i], ldy[i], cj, HS_ULVT_FULL});  // b_R -= op(T) b_S
-        tri.push_back(UlvTri<T>{&x.fd, YR[i], ldy[i], ZR[i], ldy[i]});                                                      // z = op(U)^-T b_R
-        j2.push_back(UlvTJob<T>{x.fd.UR, ZR[i], slot, slot, r, nR, q, x.fd.ldu, ldy[i], ldh[par], ldh[par], cj, HS_ULVT_FULL});  // b_S -= op(UR)^T z
+        rows.push_back(RowJob<T>{src.first, src.second, YR[i], ldy[i], x.p + r, nR, q, ROW_GATHER});
+        pairs(x, t, f);
+        op.prod(0, t[up], slot, ldh[par], YR[i], ldy[i], nR, r);  // N: b_R -= T b_S                 T: b_R -= op(T) b_S
+        op.tri(x.fd, YR[i], ZR[i], ldy[i], false);                //    z = L^-1 P b_R                  z = op(U)^-T b_R
+        op.prod(1, f[up], ZR[i], ldy[i], slot, ldh[par], r, nR);  //    b_S -= (X_SR U^-1) z            b_S -= op(UR)^T z
       }
     }
     run_rows(tmp, rows, s);
-    run_ulv_t(tmp, j1, s);
-    ulv_t_tri(tmp, tri, q, cj, true, s);
-    tri.clear();
-    run_ulv_t(tmp, j2, s);
+    op.run_prod(0);
+    op.run_tri(false);
+    op.run_prod(1);
   }
-  root(BH[0], ldh[0]);
-  // backward: root to leaves (YR is free again: it takes op(L)^-T z; ZR then takes x_R = P^T of it)
+  const std::pair<T*, int> top = own(0);
+  op.root(H.rootfd, top.first, top.second);
+  // root to leaves
   for (int lv = 1; lv < H.nlev; ++lv) {
-    std::vector<RowJob<T>> perm;
     for (int i : H.lev[lv]) {
       const HNode<T>& x = nd[i];
       const int par = x.parent, r = x.r, nR = x.m - r;
+      const std::pair<T*, int> dst = own(i);
       T* slot = BH[par] + x.off_in_parent;
-      T* dst = x.left < 0 ? B + x.lo : BH[i];
-      const int ldd = x.left < 0 ? ldb : ldh[i];
       if (nR > 0) {
-        j1.push_back(UlvTJob<T>{x.fd.LF + nR, slot, ZR[i], ZR[i], nR, r, q, x.fd.ldl, ldh[par], ldy[i], ldy[i], cj, HS_ULVT_FULL});  // z -= op(X_SR U^-1)^T x_S
-        tri.push_back(UlvTri<T>{&x.fd, ZR[i], ldy[i], YR[i], ldy[i]});                                                                // op(L)^-T z
-        perm.push_back(RowJob<T>{YR[i], ldy[i], ZR[i], ldy[i], x.fd.rperm, nR, q, ROW_SCATTER});                                      // x_R = P^T ...
-        j2.push_back(UlvTJob<T>{x.Tm, ZR[i], slot, slot, r, nR, q, x.ldt, ldy[i], ldh[par], ldh[par], cj, HS_ULVT_FULL});             // x_S -= op(T)^T x_R
-        rows.push_back(RowJob<T>{ZR[i], ldy[i], dst, ldd, x.p + r, nR, q, ROW_SCATTER});
+        pairs(x, t, f);
+        op.prod(0, f[dn], slot, ldh[par], ZR[i], ldy[i], nR, r);  // N: z -= (L^-1 P X_RS) x'_S      T: z -= op(X_SR U^-1)^T x_S
+        op.tri(x.fd, YR[i], ZR[i], ldy[i], true);                 //    x'_R = U^-1 z                   x_R = P^T op(L)^-T z
+        op.prod(1, t[dn], ZR[i], ldy[i], slot, ldh[par], r, nR);  //    x_S = x'_S - T^T x'_R           x_S -= op(T)^T x_R
+        rows.push_back(RowJob<T>{ZR[i], ldy[i], dst.first, dst.second, x.p + r, nR, q, ROW_SCATTER});
       }
-      rows.push_back(RowJob<T>{slot, ldh[par], dst, ldd, x.p, r, q, ROW_SCATTER});
+      rows.push_back(RowJob<T>{slot, ldh[par], dst.first, dst.second, x.p, r, q, ROW_SCATTER});
     }
-    run_ulv_t(tmp, j1, s);
-    ulv_t_tri(tmp, tri, q, cj, false, s);
-    tri.clear();
-    run_rows(tmp, perm, s);
-    run_ulv_t(tmp, j2, s);
+    op.run_prod(0);
+    op.run_tri(true);
+    op.run_prod(1);
     run_rows(tmp, rows, s);
   }
   HS_HIP(hipStreamSynchronize(s));
 }
+// trans = 0: H^-1, 1: H^-T, 2: H^-H (a real matrix: the same as 1)
 template <class T>
-void hss_ldiv_t(HssT<T>& H, T* B, int ldb, int q, int cj) {
-  if (!H.perm) {
-    hss_ldiv_t_p(H, B, ldb, q, cj);
-    return;
-  }
-  // H ~= A[perm, perm] and the permutation is symmetric: the same gather and scatter as hss_ldiv
+void hss_ldiv_p(HssT<T>& H, T* B, int ldb, int q, int trans) {
   Pool tmp(global_cache());
-  const int ld = ev(H.n);
-  T* Bp = tmp.get<T>((size_t)ld * q);
-  std::vector<RowJob<T>> rows{RowJob<T>{B, ldb, Bp, ld, H.perm, H.n, q, ROW_GATHER}};
-  run_rows(tmp, rows, H.s);
-  hss_ldiv_t_p(H, Bp, ld, q, cj);
-  rows.push_back(RowJob<T>{Bp, ld, B, ldb, H.perm, H.n, q, ROW_SCATTER});
-  run_rows(tmp, rows, H.s);
-  HS_HIP(hipStreamSynchronize(H.s));
+  if (trans == 0) {
+    UlvN<T> op{tmp, q, H.s};
+    ulv_walk(H, B, ldb, q, tmp, op);
+  } else {
+    UlvT<T> op{tmp, q, H.s, (trans == 2 && sizeof(T) == 16) ? 1 : 0};
+    ulv_walk(H, B, ldb, q, tmp, op);
+  }
+}
+// the same in the caller's index order
+template <class T>
+void hss_ldiv(HssT<T>& H, T* B, int ldb, int q, int trans) {
+  in_tree_order(H, (const T*)B, ldb, B, ldb, q, [&](const T*, int, T* b, int ld) { hss_ldiv_p(H, b, ld, q, trans); });
 }
 
 struct LruArgs {  // host-side description of the optional update  - C*M*Z  (pointers in the memory space `where` names)
@@ -3732,45 +3702,28 @@ extern "C" int hs_hss_factor(hs_hss* H) {
   HS_GUARD(if (H->is_complex) hss_factor<cplx>(*HZ(H)); else hss_factor<double>(*HD(H)));
 }
 
-extern "C" int hs_hss_ldiv(hs_hss* H, double* B, int64_t ldb, int64_t nrhs, int where) {
-  if (!H || !B || nrhs < 0) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_ldiv needs a right-hand side");
-    return HS_ERR_ARGUMENT;
-  }
-  if (nrhs == 0) return HS_OK;
-  HS_GUARD(
-      if (H->is_complex) {
-        hss_factor<cplx>(*HZ(H));
-        with_device_block<cplx>(HZ(H)->n, (const cplx*)B, ldb, (cplx*)B, ldb, (int)nrhs, where,
-                                [&](const cplx*, int la, cplx* b, int) { hss_ldiv<cplx>(*HZ(H), b, la, (int)nrhs); });
-      } else {
-        hss_factor<double>(*HD(H));
-        with_device_block<double>(HD(H)->n, B, ldb, B, ldb, (int)nrhs, where,
-                                  [&](const double*, int la, double* b, int) { hss_ldiv<double>(*HD(H), b, la, (int)nrhs); });
-      });
+// B <- op(H)^-1 B in place; factors on first use
+template <class T>
+static void hss_ldiv_staged(HssT<T>& H, int trans, T* B, int64_t ldb, int q, int where) {
+  hss_factor<T>(H);
+  with_device_block<T>(H.n, B, ldb, B, ldb, q, where, [&](const T*, int la, T* b, int) { hss_ldiv<T>(H, b, la, q, trans); });
 }
-
-extern "C" int hs_hss_ldiv_t(hs_hss* H, int trans, double* B, int64_t ldb, int64_t nrhs, int where) {
+static int hss_ldiv_abi(const char* name, hs_hss* H, int trans, double* B, int64_t ldb, int64_t nrhs, int where) {
   if (!H || !B || nrhs < 0) {
-    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_ldiv_t needs a right-hand side");
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs a right-hand side", name);
     return HS_ERR_ARGUMENT;
   }
   if (trans < 0 || trans > 2) {
-    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: hs_hss_ldiv_t: trans = %d (0: H^-1, 1: H^-T, 2: H^-H)", trans);
+    hs_set_error(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: H^-1, 1: H^-T, 2: H^-H)", name, trans);
     return HS_ERR_ARGUMENT;
   }
-  if (trans == 0) return hs_hss_ldiv(H, B, ldb, nrhs, where);
   if (nrhs == 0) return HS_OK;
-  HS_GUARD(
-      if (H->is_complex) {
-        hss_factor<cplx>(*HZ(H));
-        with_device_block<cplx>(HZ(H)->n, (const cplx*)B, ldb, (cplx*)B, ldb, (int)nrhs, where,
-                                [&](const cplx*, int la, cplx* b, int) { hss_ldiv_t<cplx>(*HZ(H), b, la, (int)nrhs, trans == 2); });
-      } else {
-        hss_factor<double>(*HD(H));
-        with_device_block<double>(HD(H)->n, B, ldb, B, ldb, (int)nrhs, where,
-                                  [&](const double*, int la, double* b, int) { hss_ldiv_t<double>(*HD(H), b, la, (int)nrhs, 0); });
-      });
+  HS_GUARD(if (H->is_complex) hss_ldiv_staged<cplx>(*HZ(H), trans, (cplx*)B, ldb, (int)nrhs, where);
+            else hss_ldiv_staged<double>(*HD(H), trans, B, ldb, (int)nrhs, where));
+}
+extern "C" int hs_hss_ldiv(hs_hss* H, double* B, int64_t ldb, int64_t nrhs, int where) { return hss_ldiv_abi("hs_hss_ldiv", H, 0, B, ldb, nrhs, where); }
+extern "C" int hs_hss_ldiv_t(hs_hss* H, int trans, double* B, int64_t ldb, int64_t nrhs, int where) {
+  return hss_ldiv_abi("hs_hss_ldiv_t", H, trans, B, ldb, nrhs, where);
 }
 
 extern "C" void hs_hss_free(hs_hss* H) {

@@ -16,6 +16,7 @@
 #pragma once
 #include "../../include/hs_hss.h"
 #include "hs_lowrank.h"
+#include "hs_ulv_t.h"
 
 // order of the interior positions in which every DOF of int1 is followed by its neighbours in int2 (pattern of A):
 // perm[new position] = original position; empty = identity
@@ -312,14 +313,37 @@ static void factor_hss_fronts(hs_handle* h, const int* ids, int count, const Nod
   cleanup();
 }
 
-// B (ni x q, device) <- D^-1 B for a front whose interior block is held in HSS form: one HSS solve, or the reference's block solve
-// `blockldiv!` (src/blockmatrix.jl:134-144) over [A11 A12; A21 A22] with S22 = A22 - A21*A11^-1*A12:
-//   y1 = A11^-1 B1;  x2 = S22^-1 (B2 - A21 y1);  x1 = y1 - (A11^-1 A12) x2          (A12 = C12*Z12, A21 = C21*Z21, W12 = A11^-1*C12)
+// One product of a front's block solve on q columns, with A stored rows x cols (column-major, lda) and `minus`: subtract from C, else set C:
+//   trans = 0     C (rows x q) (-)= A X          the MFMA GEMM
+//   trans = 1, 2  C (cols x q) (-)= op(A)^T X    the grouped product of kernels_ulv_t.hip, op = conj for trans = 2 (ComplexF64)
+// The job description goes through `slot`, HS_FRONT_SLOT bytes of the caller's on the device.  The slot is used again by the next product, so
+// the stream is drained between the upload and the launch.
+constexpr size_t HS_FRONT_SLOT = 256;
 template <class T>
-static void hss_d_solve(hs_handle* h, const NodeH& x, T* B, int ldb, int q, hipStream_t s) {
+static void hss_front_prod(void* slot, int trans, const T* A, int lda, int rows, int cols, const T* X, int ldx, T* C, int ldc, int q, bool minus,
+                           hipStream_t s) {
+  static_assert(sizeof(UlvTJob<T>) <= HS_FRONT_SLOT && sizeof(GemmProb<T>) <= HS_FRONT_SLOT, "a job description fits the slot");
+  if (rows <= 0 || cols <= 0) return;
+  const GemmProb<T> g{A, X, C, rows, q, cols, lda, ldx, ldc};
+  const UlvTJob<T> j{A, X, minus ? C : nullptr, C, cols, rows, q, lda, ldx, ldc, ldc, (trans == 2 && sizeof(T) == 16) ? 1 : 0, HS_ULVT_FULL};
+  if (trans == 0) HS_HIP(hipMemcpyAsync(slot, &g, sizeof g, hipMemcpyHostToDevice, s));
+  else HS_HIP(hipMemcpyAsync(slot, &j, sizeof j, hipMemcpyHostToDevice, s));
+  HS_HIP(hipStreamSynchronize(s));
+  if (trans == 0) launch_gemm_probs<T>((const GemmProb<T>*)slot, 1, rows, q, minus ? 1 : 0, s);
+  else launch_ulv_t<T>((const UlvTJob<T>*)slot, 1, cols, q, s);
+}
+
+// B (ni x q, device) <- op(D)^-1 B for a front whose interior block is held in HSS form, op = identity / transpose / adjoint (trans = 0, 1, 2):
+// one HSS solve, or the reference's block solve `blockldiv!` (src/blockmatrix.jl:134-144) over [A11 A12; A21 A22] with S22 = A22 - A21*A11^-1*A12
+// (hss = A11, hss2 = S22, A12 = C12*Z12, A21 = C21*Z21, W12 = A11^-1*C12):
+//   trans = 0     y1 = A11^-1 B1;  x2 = S22^-1 (B2 - A21 y1);  x1 = y1 - (W12 Z12) x2
+//   trans = 1, 2  the same steps transposed, last to first:
+//                 b2 -= op(Z12)^T (op(W12)^T b1);  x2 = op(S22)^-T b2;  b1 -= op(Z21)^T (op(C21)^T x2);  x1 = op(A11)^-T b1
+template <class T>
+static void hss_d_solve(hs_handle* h, const NodeH& x, int trans, T* B, int ldb, int q, hipStream_t s) {
   auto hsolve = [&](void* H, T* b) {
     int st = hs_hss_set_stream((hs_hss*)H, (void*)s);
-    if (st == 0) st = hs_hss_ldiv((hs_hss*)H, (double*)b, ldb, q, 1);
+    if (st == 0) st = hs_hss_ldiv_t((hs_hss*)H, trans, (double*)b, ldb, q, 1);
     HS_CHECK(st);
   };
   if (!x.mfb) {
@@ -328,8 +352,8 @@ static void hss_d_solve(hs_handle* h, const NodeH& x, T* B, int ldb, int q, hipS
   }
   const int n1 = x.ni1, n2 = x.ni - x.ni1, k12 = x.bk12, k21 = x.bk21;
   T *B1 = B, *B2 = B + n1;
-  hsolve(x.hss, B1);
-  if (q == 1) {
+  if (trans == 0 && q == 1) {
+    hsolve(x.hss, B1);
     if (k21 > 0) {
       ensure_lr_workspace<T>(h, k21, n1);
       launch_lr_zmul<T>((const T*)x.bZ21, x.bldz21, k21, n1, B1, nullptr, (T*)h->d_lr_part, (T*)h->d_lr_t, s);
@@ -343,35 +367,46 @@ static void hss_d_solve(hs_handle* h, const NodeH& x, T* B, int ldb, int q, hipS
     }
     return;
   }
-  // blocks of right-hand sides (W = D^-1 C_R during the factorization): the same steps as MFMA products
+  // blocks of right-hand sides (W = D^-1 C_R during the factorization, hs_ldiv_ulv_*): the same steps as grouped products
   const int kmax = std::max(std::max(k12, k21), 1), ldt = (kmax + 1) / 2 * 2;
   T* t = nullptr;
-  GemmProb<T>* dgp = nullptr;
-  if (hs_lr_alloc((void**)&t, ((size_t)ldt * q + 32) * sizeof(T)) != 0 || hs_lr_alloc((void**)&dgp, 2 * sizeof(GemmProb<T>)) != 0) {
+  void* slot = nullptr;
+  if (hs_lr_alloc((void**)&t, ((size_t)ldt * q + 32) * sizeof(T)) != 0 || hs_lr_alloc(&slot, HS_FRONT_SLOT) != 0) {
     hs_lr_free(t);
     HS_FAIL(HS_ERR_NOMEM, 0, "hipMalloc of the block-solve scratch failed");
   }
-  auto pair = [&](const T* Z, int ldz, int k, int cols, const T* X, const T* C, int ldc, int rows, T* Y) {  // Y -= C * (Z * X)
+  // Y -= op(C Z) X through t, with C rows x k and Z k x cols:  Y -= C (Z X),  transposed  Y -= op(Z)^T (op(C)^T X)
+  auto lowrank = [&](const T* C, int ldc, int rows, const T* Z, int ldz, int cols, int k, const T* X, T* Y) {
     if (k <= 0) return;
-    GemmProb<T> gp[2] = {GemmProb<T>{Z, X, t, k, q, cols, ldz, ldb, ldt}, GemmProb<T>{C, t, Y, rows, q, k, ldc, ldt, ldb}};
-    HS_HIP(hipMemcpyAsync(dgp, gp, sizeof gp, hipMemcpyHostToDevice, s));
-    HS_HIP(hipStreamSynchronize(s));
-    launch_gemm_probs<T>(dgp, 1, k, q, 0, s);
-    launch_gemm_probs<T>(dgp + 1, 1, rows, q, 1, s);
+    if (trans == 0) {
+      hss_front_prod<T>(slot, 0, Z, ldz, k, cols, X, ldb, t, ldt, q, false, s);
+      hss_front_prod<T>(slot, 0, C, ldc, rows, k, t, ldt, Y, ldb, q, true, s);
+    } else {
+      hss_front_prod<T>(slot, trans, C, ldc, rows, k, X, ldb, t, ldt, q, false, s);
+      hss_front_prod<T>(slot, trans, Z, ldz, k, cols, t, ldt, Y, ldb, q, true, s);
+    }
   };
   try {
-    pair((const T*)x.bZ21, x.bldz21, k21, n1, B1, (const T*)x.bC21, x.bldc21, n2, B2);
-    hsolve(x.hss2, B2);
-    pair((const T*)x.bZ12, x.bldz12, k12, n2, B2, (const T*)x.bW12, x.bldw, n1, B1);
+    if (trans == 0) {
+      hsolve(x.hss, B1);
+      lowrank((const T*)x.bC21, x.bldc21, n2, (const T*)x.bZ21, x.bldz21, n1, k21, B1, B2);
+      hsolve(x.hss2, B2);
+      lowrank((const T*)x.bW12, x.bldw, n1, (const T*)x.bZ12, x.bldz12, n2, k12, B2, B1);
+    } else {
+      lowrank((const T*)x.bW12, x.bldw, n1, (const T*)x.bZ12, x.bldz12, n2, k12, B1, B2);
+      hsolve(x.hss2, B2);
+      lowrank((const T*)x.bC21, x.bldc21, n2, (const T*)x.bZ21, x.bldz21, n1, k21, B2, B1);
+      hsolve(x.hss, B1);
+    }
     HS_HIP(hipStreamSynchronize(s));
   } catch (...) {
     (void)hipStreamSynchronize(s);
     hs_lr_free(t);
-    hs_lr_free(dgp);
+    hs_lr_free(slot);
     throw;
   }
   hs_lr_free(t);
-  hs_lr_free(dgp);
+  hs_lr_free(slot);
 }
 
 // forward sweep of level lv:  t = H^-1 rhs[int];  rhs[bnd] -= C_L * (Z_L * t)
@@ -383,7 +418,7 @@ static void solve_hss_fwd(hs_handle* h, int lv, T* db, hipStream_t s) {
     if (!(x.hssd || x.mf) || !x.hss) continue;
     T* t = (T*)x.ht;
     launch_pack_idx(h->d_int + x.off_fidx, x.ni, db, t, (int)sizeof(T), s);
-    hss_d_solve<T>(h, x, t, x.ni, 1, s);
+    hss_d_solve<T>(h, x, 0, t, x.ni, 1, s);
     if (x.nb == 0 || !x.lrL) continue;
     const LowRank<T>& lr = *(const LowRank<T>*)x.lrL;
     if (lr.r == 0) continue;

@@ -729,7 +729,7 @@ static void factor_mf_fronts(hs_handle* h, const int* ids, int count) {
         lap("Aib, Abi from the generators");
         // ---- W = Aii^-1 * C_R (the R transform; C_R itself is not needed again) -------------------------------------------------------------------
         if (rR > 0) {
-          hss_d_solve<T>(h, x, lrR->Cd, lrR->ldc, rR, s);
+          hss_d_solve<T>(h, x, 0, lrR->Cd, lrR->ldc, rR, s);
           x.hW = lrR->Cd;  // ownership moves to the node (freed with the HSS objects); the low-rank object keeps only Z_R
           x.hldw = lrR->ldc;
           lrR->Cd = nullptr;

@@ -181,6 +181,32 @@ def test_hss_ldiv_t_permuted(hs, complex_):
 
 
 @pytest.mark.parametrize("complex_", [False, True])
+@pytest.mark.parametrize("kind", ["random", "mixed"])
+def test_hss_ldiv_full_rank_nodes(hs, kind, complex_):
+    """Non-root nodes that keep full rank (r == m) eliminate nothing: the walk only moves their rows, in all three directions.
+    "random": a dense random matrix, every non-root node is such a node.  "mixed": a smooth matrix with one dense random block row and
+    column at 1e-13, where the 12-point leaves keep full rank and nodes above them compress, so both kinds share the launches of a level."""
+    n = 96
+    rng = np.random.default_rng(3)
+    R = rng.standard_normal((n, n)) + (1j * rng.standard_normal((n, n)) if complex_ else 0)
+    if kind == "random":
+        A = R + n * np.eye(n)
+    else:
+        A = kernel_matrix(n, complex_)
+        A[:12, :] += 0.1 * R[:12, :]
+        A[:, :12] += 0.1 * R[:, :12]
+    H = hs.hss.compress(A, leafsize=16, atol=1e-13, rtol=1e-13, kest=32)
+    info = [H._info(i) for i in range(1, H.num_nodes)]
+    print(f"{kind} complex={complex_}: (m, r) of the non-root nodes {[(d['m'], d['r']) for d in info]}")
+    assert H.num_nodes >= 7 and any(d["r"] == d["m"] for d in info)
+    if kind == "random":
+        assert all(d["r"] == d["m"] for d in info)
+    else:
+        assert any(d["r"] < d["m"] for d in info)
+    check_solves(H, complex_)
+
+
+@pytest.mark.parametrize("complex_", [False, True])
 def test_hss_ldiv_t_device_pointer_and_arguments(hs, complex_):
     """where = 1 agrees bitwise with where = 0; trans outside 0..2 is refused with B untouched."""
     import torch
