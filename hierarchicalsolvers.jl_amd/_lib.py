@@ -113,7 +113,7 @@ EXPORTS = [
     "hs_hss_offdiag", "hs_hss_bytes", "hs_hss_prune_leaves", "hs_hss_compatible", "hs_hss_depth", "hs_hss_compress_blockop_d", "hs_hss_compress_blockop_z", "hs_hss_blockop_apply",
     "hsk_gemm_d", "hsk_gemm_z", "hsk_lowrank_d", "hsk_lowrank_z", "hsk_front_factor_d", "hsk_front_factor_z", "hsk_front_batch_d", "hsk_front_batch_z", "hsk_sweep_level_d", "hsk_sweep_level_z", "hsk_flow_tall_rule", "hsk_sweep_path", "hsk_mfma_f64_peak", "hsk_mfma_f64_peak_random", "hsk_flow_pingpong_us", "hsk_bisect_perm",
     "hs_probs_stats_mode", "hs_probs_stats", "hs_trim", "hs_stream_order",
-    "hsk_leaf_envelope", "hsk_envelope_enable", "hsk_op_flops_mode", "hsk_op_flops",
+    "hsk_leaf_envelope", "hsk_envelope_enable", "hsk_branch_envelope", "hsk_branch_envelope_enable", "hsk_front_batch_env_d", "hsk_op_flops_mode", "hsk_op_flops",
     "hsk_gemm_op_d", "hsk_gemm_lds_enable", "hsk_gemm_lds_launches",
     "hsk_gemm_lds_edge_launches", "hsk_gemm_reg_launches", "hsk_gemm_lds_route", "hsk_gemm_schur_d",
     "hsk_trsm_inv_d", "hsk_trsm_strip_enable", "hsk_trsm_strip_launches", "hsk_trsm_half_launches", "hsk_lookahead_runs",
@@ -629,6 +629,12 @@ def lib():
     L.hsk_leaf_envelope.restype = C.c_int
     L.hsk_envelope_enable.argtypes = [C.c_int]
     L.hsk_envelope_enable.restype = C.c_int
+    L.hsk_branch_envelope.argtypes = [i64, p_i64, p_i64, C.POINTER(C.c_int32), i64, i64, i64, i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.hsk_branch_envelope.restype = C.c_int
+    L.hsk_front_batch_env_d.argtypes = [i64, p_i64, p_i64, C.c_int, p_f64, C.POINTER(C.c_int32), p_f64, p_f64, p_f64, p_i64, p_i64, p_i64]
+    L.hsk_front_batch_env_d.restype = C.c_int
+    L.hsk_branch_envelope_enable.argtypes = [C.c_int]
+    L.hsk_branch_envelope_enable.restype = C.c_int
     L.hsk_op_flops_mode.argtypes = [C.c_int]
     L.hsk_op_flops_mode.restype = C.c_int
     L.hsk_op_flops.argtypes = [p_f64]

@@ -122,7 +122,7 @@ struct NodeH {
   size_t off_fidx = 0, off_ipiv = 0, off_rperm = 0, off_cmap = 0, off_cand = 0;  // int offsets
   int ncand = 0;
   int batch_pos = -1;      // index inside its level's batch of owned fronts
-  long long off_env = -1;  // leaf eliminated by Sched: int offset of its block envelope in hs_handle::env_host / d_env (hs_envelope.h); -1: dense
+  long long off_env = -1;  // front eliminated by Sched: int offset of its block envelope in hs_handle::env_host / d_env (hs_envelope.h); -1: dense
   void* ext_sb = nullptr;  // caller-provided device buffer for the Schur complement (exchange between ranks)
   long long woff = 0;
   bool compressed = false;  // level <= swlevel && |bnd| >= swsize (factorization.jl:15): low-rank Gauss transforms
@@ -179,6 +179,7 @@ struct LevelH {
   size_t sc_off = 0, sc_cnt = 0;    // ScatterDesc range
   std::vector<int> h_ni, h_nb;
   std::vector<const int*> h_env;    // block envelopes of the dense batch on the host (null: dense front); empty when no front of the level has one
+  std::vector<const int*> h_env_leaf;  // the same with the branch fronts' entries null (HS_BRANCH_ENVELOPE=0); empty when no leaf of the level has one
   int ndense = 0;                          // the first ndense entries of `mine` are dense fronts (one batch), the rest compressed
   int nplain = 0;                          // of those, the first nplain keep a dense LU of D, the others an HSS form (hs_hssfront.h)
   int nmf = 0;                             // the last nmf entries of `mine` are matrix-free fronts (hs_mffront.h): never assembled
@@ -240,8 +241,12 @@ struct hs_handle {
   void* d_nodes = nullptr;  // NodeDesc<T>[] of the owned fronts, level by level
   void* d_sc = nullptr;     // ScatterDesc<T>[]
   void* d_solve = nullptr;  // SolveNode<T>[] (same order as d_nodes)
-  int* d_env = nullptr;     // block envelopes of the leaf fronts (NodeDesc::env), built once per pattern
+  int* d_env = nullptr;     // block envelopes of the leaf and branch fronts (NodeDesc::env), built once per pattern
   std::vector<int> env_host;
+  // NodeDesc::env of every descriptor (d_nodes order) with the branch fronts' tables and without them, and which of the two the device holds:
+  // hs_numeric_levels rewrites the field when the branch switch (hs_branch_envelope_enabled) has changed since.  Empty: no branch front has a table
+  std::vector<const int*> env_dev[2];
+  int env_dev_state = 1;
   void* d_w1 = nullptr;
   void* d_w2 = nullptr;
   int* d_flow = nullptr;    // dataflow sweeps (kernels_solve_wide.hip): 64 workgroup-id counters, one per launch, used as a ring
@@ -1069,33 +1074,43 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
       if (!owned.empty()) HS_HIP(hipMemcpy(h->d_owned, owned.data(), owned.size() * sizeof(int), hipMemcpyHostToDevice));
     }
 
-    // ---- block envelopes of the leaf fronts the level schedule eliminates densely (hs_envelope.h) -----------------
-    // A leaf is assembled from A alone, so its pattern is known here.  Everything else (branch fronts: two dense Schur complements; slices
-    // of split fronts; fronts of the compressed / HSS / matrix-free flows) keeps a null pointer, which means "dense".
+    // ---- block envelopes of the fronts the level schedule eliminates densely (hs_envelope.h) ----------------------
+    // A leaf is assembled from A alone, so its pattern is known here.  A branch front is two dense Schur complements on disjoint DOF sets plus
+    // the entries of A across the cut, so its pattern is known too: the two diagonal blocks of [int1; int2 | bnd1; bnd2] are full, the rest is
+    // A's.  Everything else (slices of split fronts; fronts of the compressed / HSS / matrix-free flows; fronts eliminated by a group of
+    // ranks) keeps a null pointer, which means "dense".
     if (colptr && rowval) {
       std::vector<int> where((size_t)n, -1);
       for (LevelH& L : h->levels) {
         L.h_env.clear();
+        L.h_env_leaf.clear();
         for (int k = 0; k < L.ndense; ++k) {
           NodeH& x = N[L.mine[k]];
-          if (!x.leaf || x.kind != 0 || x.dist || x.compressed || x.hssd || x.mf || x.ni <= 0) continue;
+          if (x.kind != 0 || x.dist || x.compressed || x.hssd || x.mf || x.ni <= 0) continue;
           const int nblk = hs_env_nblocks(x.ni, x.nb);
           x.off_env = (long long)h->env_host.size();
           h->env_host.resize(h->env_host.size() + 2 * (size_t)nblk);
           int* fl = h->env_host.data() + x.off_env;
-          hs_leaf_envelope(colptr, rowval, h->fidx_host.data() + x.off_fidx, x.ni, x.nb, where.data(), fl, fl + nblk);
+          const int* fidx = h->fidx_host.data() + x.off_fidx;
+          if (x.leaf)
+            hs_leaf_envelope(colptr, rowval, fidx, x.ni, x.nb, where.data(), fl, fl + nblk);
+          else
+            hs_branch_envelope(colptr, rowval, fidx, x.ni, x.nb, x.ni1, x.nb1, where.data(), fl, fl + nblk);
         }
       }
       if (!h->env_host.empty()) {
-        dmalloc((void**)&h->d_env, h->env_host.size() * sizeof(int), "leaf envelopes");
+        dmalloc((void**)&h->d_env, h->env_host.size() * sizeof(int), "front envelopes");
         HS_HIP(hipMemcpy(h->d_env, h->env_host.data(), h->env_host.size() * sizeof(int), hipMemcpyHostToDevice));
         for (LevelH& L : h->levels) {  // (env_host no longer moves)
-          bool any = false;
-          for (int k = 0; k < L.ndense; ++k) any = any || N[L.mine[k]].off_env >= 0;
-          if (!any) continue;
+          bool any = false, any_leaf = false;
+          for (int k = 0; k < L.ndense; ++k) {
+            any = any || N[L.mine[k]].off_env >= 0;
+            any_leaf = any_leaf || (N[L.mine[k]].off_env >= 0 && N[L.mine[k]].leaf);
+          }
           for (int k = 0; k < L.ndense; ++k) {
             const NodeH& x = N[L.mine[k]];
-            L.h_env.push_back(x.off_env >= 0 ? h->env_host.data() + x.off_env : nullptr);
+            if (any) L.h_env.push_back(x.off_env >= 0 ? h->env_host.data() + x.off_env : nullptr);
+            if (any_leaf) L.h_env_leaf.push_back(x.off_env >= 0 && x.leaf ? h->env_host.data() + x.off_env : nullptr);
           }
         }
       }
@@ -1139,6 +1154,8 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
           d.env = x.off_env >= 0 ? h->d_env + x.off_env : nullptr;
           d.finalize();
           hn.push_back(d);
+          h->env_dev[1].push_back(d.env);
+          h->env_dev[0].push_back(x.leaf ? d.env : nullptr);
           if (x.batch_pos < L.ndense && ((((uintptr_t)d.LF | (uintptr_t)d.UR | (uintptr_t)d.SB) & 15) || ((d.ldl | d.ldu | d.lds) & 1)))
             L.aligned16 = false;  // (the dense batch only: the compressed, HSS and matrix-free fronts of the level never reach Sched::gemm through it)
           SolveNode<T> q;
@@ -1177,6 +1194,8 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
       dmalloc(&h->d_sc, hsc.size() * sizeof(ScatterDesc<T>), "scatter descriptors");
       dmalloc(&h->d_solve, sn.size() * sizeof(SolveNode<T>), "solve descriptors");
       if (!hn.empty()) HS_HIP(hipMemcpy(h->d_nodes, hn.data(), hn.size() * sizeof(NodeDesc<T>), hipMemcpyHostToDevice));
+      if (h->env_dev[0] == h->env_dev[1]) h->env_dev[0].clear(), h->env_dev[1].clear();  // no branch table: nothing to switch
+      h->env_dev_state = 1;
       if (!hsc.empty()) HS_HIP(hipMemcpy(h->d_sc, hsc.data(), hsc.size() * sizeof(ScatterDesc<T>), hipMemcpyHostToDevice));
       if (!sn.empty()) HS_HIP(hipMemcpy(h->d_solve, sn.data(), sn.size() * sizeof(SolveNode<T>), hipMemcpyHostToDevice));
     }
@@ -1257,6 +1276,16 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
   T* dsb = (T*)h->d_sb;
   const NodeDesc<T>* dn_all = (const NodeDesc<T>*)h->d_nodes;
   const ScatterDesc<T>* dsc_all = (const ScatterDesc<T>*)h->d_sc;
+  // the branch fronts' tables nest under the leaves' switch: HS_BRANCH_ENVELOPE=0 / hsk_branch_envelope_enable(0) takes them away alone, on the
+  // device (NodeDesc::env of the branch fronts) and on the host (LevelH::h_env_leaf)
+  const bool branch_env = hs_branch_envelope_enabled();
+  if (!h->env_dev[0].empty() && h->env_dev_state != (branch_env ? 1 : 0)) {
+    HS_HIP(hipStreamSynchronize(s));
+    const std::vector<const int*>& v = h->env_dev[branch_env ? 1 : 0];
+    HS_HIP(hipMemcpy2D((char*)h->d_nodes + offsetof(NodeDesc<T>, env), sizeof(NodeDesc<T>), v.data(), sizeof(const int*), sizeof(const int*), v.size(),
+                       hipMemcpyHostToDevice));
+    h->env_dev_state = branch_env ? 1 : 0;
+  }
   for (int lv = lv_from; lv >= lv_to; --lv) {
     LevelH& L = h->levels[lv];
     if (L.mine.empty()) continue;
@@ -1331,11 +1360,12 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
       sch.sn = (const SolveNode<T>*)h->d_solve + L.desc_off;  // lu_rec leaves the 256x256 inverse diagonal blocks behind
       sch.optimistic = try_opt && attempt == 0;
       sch.aligned16 = L.aligned16 && h->nranks == 1;  // (a Schur complement handed in by another rank lives in the caller's buffer)
-      // the block envelope of the leaves holds while rows are swapped inside 32-row diagonal blocks only: the redo of a level and
+      // the block envelope of a front holds while rows are swapped inside 32-row diagonal blocks only: the redo of a level and
       // HS_OPTIMISTIC=0 (tournament pivoting) eliminate every front as a dense matrix
-      if (sch.optimistic && !dx && !L.h_env.empty() && hs_envelope_enabled()) {
+      const std::vector<const int*>& henv = branch_env ? L.h_env : L.h_env_leaf;
+      if (sch.optimistic && !dx && !henv.empty() && hs_envelope_enabled()) {
         sch.env = true;
-        sch.h_env = L.h_env.data();
+        sch.h_env = henv.data();
       }
       if (dx)
         factor_front_dist<T>(sch, DF);

@@ -120,7 +120,7 @@ struct NodeDesc {
   int pivrows;   // pivot candidates are rows [c0, pivrows): ni for a front (`\\` on Aii pivots inside Aii only), all rows for a sketch
   int isleaf;
   int node;      // post-order id
-  const int* env;  // leaf front: block envelope of its sparsity pattern (hs_envelope.h), firstL then firstU, one entry per 32-row / 32-column
+  const int* env;  // leaf or branch front: block envelope of its sparsity pattern (hs_envelope.h), firstL then firstU, one entry per 32-row / 32-column
                    // block of the front (interior blocks first, boundary blocks counted from the start of the boundary part); null = dense
   // the same three matrices indexed by HS_MAT_*: kernels that pick a matrix at run time index these
   // tables (plain address arithmetic) instead of branching over LF/UR/SB -- hipcc (ROCm 7.2) was seen
@@ -209,7 +209,7 @@ __device__ inline void mat_of(const NodeDesc<T>* pn, int which, T*& p, int& ld, 
 enum { HS_GEMM_ROUTE_REG = 0, HS_GEMM_ROUTE_LDS = 1, HS_GEMM_ROUTE_EDGE = 2 };
 template <class T>
 void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s, int route = HS_GEMM_ROUTE_REG,
-                    bool shifted = false);
+                    bool shifted = false, long long live_tiles = -1);  // live_tiles: tiles of an enveloped launch that run (-1: not counted)
 // Which kernel may run the plain update (cmat, r0, k0, k1) of a front with ni interior DOFs?  The direct-to-LDS load moves 16 bytes per
 // lane and is given 16-byte aligned sources only.  With LF / UR / SB 16-byte aligned and even leading dimensions (the caller's premise:
 // Sched::aligned16) B = B0 + k0 + c0 ldb is aligned when k0 is even, and A = LF + r0 (+ ni when C is SB) + k0 ldl when its row offset is even.
@@ -234,7 +234,8 @@ bool hs_trsm_strip_enabled();
 void hs_trsm_half_note();  // one Float64 lower half product (ainv 3 or 4) was launched instead (hsk_trsm_half_launches)
 void hs_lookahead_note();  // Sched::factor_fronts sent one batch to factor_fronts_lookahead (hsk_lookahead_runs; hs_testhooks.hip)
 void launch_trsm_strip(const NodeDesc<double>* dnodes, int nbatch, int maxN, const GemmOp& op, hipStream_t s);
-bool hs_envelope_enabled();  // HS_LEAF_ENVELOPE (default on) / hsk_envelope_enable: leaf fronts are eliminated inside their block envelope
+bool hs_envelope_enabled();  // HS_LEAF_ENVELOPE (default on) / hsk_envelope_enable: fronts are eliminated inside their block envelope
+bool hs_branch_envelope_enabled();  // HS_BRANCH_ENVELOPE (default on) / hsk_branch_envelope_enable: the branch fronts too (only while the first is on)
 template <class T>
 void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN, int accumulate_minus, hipStream_t s);
 

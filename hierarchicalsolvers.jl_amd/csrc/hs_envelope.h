@@ -1,4 +1,5 @@
-// hs_envelope.h -- block envelope of a leaf front's sparsity pattern (host side, analysis time).
+// hs_envelope.h -- block envelope of a front's sparsity pattern (host side, analysis time): leaf fronts (hs_leaf_envelope) and branch fronts
+// (hs_branch_envelope: two dense Schur complements on disjoint DOF sets plus A's entries across the cut -- not a dense matrix).
 //
 // A leaf front F = [Aii Aib; Abi Abb] (front order [int; bnd]) is assembled from A alone, and LU that pivots only inside the 32-row diagonal
 // blocks (optimistic pivoting) keeps the envelope of F taken per 32-row / 32-column block:
@@ -38,4 +39,24 @@ inline void hs_leaf_envelope(const int64_t* colptr, const int64_t* rowval, const
     }
   }
   for (int p = 0; p < m; ++p) where[fidx[p]] = -1;
+}
+
+// A branch front is assembled from the Schur complements of its two children and from the entries of A across the cut.  The children own
+// disjoint DOFs: positions p < ni1 and ni <= p < ni + nb1 belong to child 1, the others to child 2 (front order [int1; int2 | bnd1; bnd2]).
+// Its structural pattern is every pair of positions of the same child (a Schur complement is dense), every stored entry of A between the
+// front's DOFs and the interior diagonal; the tables are those of hs_leaf_envelope for that pattern.  For a 7-point stencil rows bnd2 then
+// have nothing in columns int1 (L[bnd2, int1] = 0, U[int1, bnd2] = 0) and rows int2 start at their partner column of int1.
+// A missing child is ni1 = nb1 = 0 or ni1 = ni, nb1 = nb: one dense block.  Arguments as for hs_leaf_envelope.
+inline void hs_branch_envelope(const int64_t* colptr, const int64_t* rowval, const int* fidx, int ni, int nb, int ni1, int nb1, int* where, int* firstL,
+                               int* firstU) {
+  hs_leaf_envelope(colptr, rowval, fidx, ni, nb, where, firstL, firstU);  // the entries of A and the diagonal
+  const int m = ni + nb;
+  // a position of child s meets every interior position of child s: the first of them is 0 (child 1) or ni1 (child 2)
+  const int first[2] = {ni1 > 0 ? 0 : HS_ENV_NONE, ni1 < ni ? (ni1 & ~31) : HS_ENV_NONE};
+  for (int p = 0; p < m; ++p) {
+    const int side = p < ni ? (p < ni1 ? 0 : 1) : (p - ni < nb1 ? 0 : 1);
+    const int b = hs_env_block(p, ni);
+    firstL[b] = std::min(firstL[b], first[side]);
+    firstU[b] = std::min(firstU[b], first[side]);
+  }
 }

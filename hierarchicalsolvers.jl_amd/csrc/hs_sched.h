@@ -6,8 +6,10 @@
 // dimension is the width of the finished left half, so almost all flops run at large K.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 #include <vector>
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
@@ -120,12 +122,15 @@ struct Sched {
   int rows_of(int mat) const { return mat == HS_MAT_LF ? maxm : (mat == HS_MAT_UR ? maxni : maxnb); }
   int cols_of(int mat) const { return mat == HS_MAT_LF ? maxni : maxnb; }
 
-  std::vector<int> kcol, kcol_rd;  // scratch of the enveloped accounting below
+  std::vector<std::pair<int, int>> kcol;  // scratch of the enveloped accounting below: (K start, width) of the live tile columns
+  std::vector<long long> kpre;            // ... and their prefix sums
   void gemm(int cmat, int bmat, int r0, int r1, int c0, int c1, int k0, int k1, int cap = 0) {
     GemmOp op{cmat, bmat, r0, r1, c0, c1, k0, k1, 0, cap, hiprio, env ? 1 : 0};
     int M = std::min(r1, rows_of(cmat)) - r0, N = std::min(c1, cols_of(cmat)) - c0, K = std::min(k1, maxni) - k0;
     if (M <= 0 || N <= 0 || K <= 0) return;
     double fl = 0.0;
+    bool clipped = false;  // some tile of an enveloped front starts its K loop late or does not run at all
+    long long live = 0;  // tiles of the enveloped fronts that run, plus every tile of the dense ones (enveloped launches: launch_gemm_op sizes its grid by it)
     int route = (sizeof(T) == 8 && aligned16 && h_ni) ? HS_GEMM_ROUTE_LDS : HS_GEMM_ROUTE_REG;
     bool shifted = false;
     if (h_ni) {
@@ -143,41 +148,65 @@ struct Sched {
             // (M + 1 rows from row0 - 1): its tiles' clips can start earlier and its first tile row always meets the last interior block, so
             // it may run more K-steps than counted here, all of them over exact zeros of L -- work the result does not need.  Bytes: C of the tiles that run, A / B once per tile
             // row / column over the longest K range one of its tiles reads.
+            // Cost: O(tile rows + tile columns) per front (a branch front has 256 x 256 tiles at the root and hundreds of launches).  A tile
+            // runs when max(kr, kc) < kend; every term is an integer below 2^53, so the sums do not depend on their order.
             const int BMh = 128, BNh = sizeof(T) == 16 ? 64 : 128;
-            const int M_ = (int)Mi, N_ = (int)Ni, K_ = (int)Ki;
+            const int M_ = (int)Mi, N_ = (int)Ni, kend = k0 + (int)Ki;
             const int* fL = h_env[i];
             const int* fU = fL + hs_env_block(m - 1, ni) + 1;
             const int row0 = r0 + (cmat == HS_MAT_SB ? ni : 0), col0 = c0 + (cmat == HS_MAT_LF ? 0 : ni);
             const int tn_ = (N_ + BNh - 1) / BNh;
-            kcol.resize(tn_);
-            kcol_rd.assign(tn_, 0);
-            for (int tn = 0; tn < tn_; ++tn) kcol[tn] = hs_env_min(fU, ni, col0 + tn * BNh, col0 + std::min(N_, (tn + 1) * BNh));
-            for (int m0 = 0; m0 < M_; m0 += BMh) {
+            // the live tile columns, sorted by their start: prefix sums of the widths and of width * start
+            kcol.clear();
+            long long ncols = 0;
+            int kc_min = HS_ENV_NONE;
+            for (int tn = 0; tn < tn_; ++tn) {
+              const int kc = hs_env_min(fU, ni, col0 + tn * BNh, col0 + std::min(N_, (tn + 1) * BNh));
+              if (kc >= kend) continue;
+              kcol.push_back({kc, std::min(BNh, N_ - tn * BNh)});
+              kc_min = std::min(kc_min, kc);
+            }
+            std::sort(kcol.begin(), kcol.end());
+            kpre.assign(2 * (kcol.size() + 1), 0);
+            for (size_t j = 0; j < kcol.size(); ++j) {
+              kpre[2 * (j + 1)] = kpre[2 * j] + kcol[j].second;
+              kpre[2 * (j + 1) + 1] = kpre[2 * j + 1] + (long long)kcol[j].second * kcol[j].first;
+            }
+            ncols = kpre[2 * kcol.size()];
+            const long long ncolsk = kpre[2 * kcol.size() + 1];
+            long long macs = 0, nrows = 0, rd = 0;
+            int kr_min = HS_ENV_NONE;
+            for (int m0 = 0; m0 < M_ && ncols > 0; m0 += BMh) {
               const int mt = std::min(BMh, M_ - m0);
               const int kr = std::max(k0, hs_env_min(fL, ni, row0 + m0, row0 + m0 + mt));
-              int krow_rd = 0;
-              for (int tn = 0; tn < tn_; ++tn) {
-                const int kt = K_ - (std::max(kr, kcol[tn]) - k0);
-                if (kt <= 0) continue;
-                const int nt = std::min(BNh, N_ - tn * BNh);
-                fl += 2.0 * mt * (double)nt * kt;
-                pf->gemm_bytes += 2.0 * mt * nt * sizeof(T);
-                krow_rd = std::max(krow_rd, kt);
-                kcol_rd[tn] = std::max(kcol_rd[tn], kt);
-              }
-              pf->gemm_bytes += (double)mt * krow_rd * sizeof(T);
+              if (kr >= kend) continue;
+              // columns that start at or before kr run kend - kr steps, the others kend - kc
+              const size_t j = std::upper_bound(kcol.begin(), kcol.end(), std::make_pair(kr, INT_MAX)) - kcol.begin();
+              macs += mt * (kpre[2 * j] * (kend - kr) + (ncols - kpre[2 * j]) * kend - (ncolsk - kpre[2 * j + 1]));
+              nrows += mt;
+              rd += (long long)mt * (kend - std::max(kr, kc_min));  // A: once per tile row over the longest K range one of its tiles reads
+              kr_min = std::min(kr_min, kr);
             }
-            for (int tn = 0; tn < tn_; ++tn) pf->gemm_bytes += (double)std::min(BNh, N_ - tn * BNh) * kcol_rd[tn] * sizeof(T);
+            fl += 2.0 * (double)macs;
+            clipped = clipped || macs != (long long)M_ * N_ * (kend - k0);
+            live += (long long)((nrows + BMh - 1) / BMh) * (long long)kcol.size();
+            if (nrows > 0)
+              for (const auto& c : kcol) rd += (long long)c.second * (kend - std::max(c.first, kr_min));  // B likewise, per tile column
+            pf->gemm_bytes += (2.0 * (double)nrows * (double)ncols + (double)rd) * sizeof(T);
             continue;
           }
           fl += 2.0 * Mi * Ni * Ki;
           pf->gemm_bytes += (Mi * Ki + Ki * Ni + 2.0 * Mi * Ni) * sizeof(T);
+          live += (long long)(((int)Mi + 127) / 128) * (((int)Ni + (sizeof(T) == 16 ? 63 : 127)) / (sizeof(T) == 16 ? 64 : 128));
         }
       }
       if (sizeof(T) == 16) fl *= 4.0;
     }
+    // An enveloped launch in which no front clips anything is a dense one: it runs the dense kernels (the direct-to-LDS tile where the
+    // route allows).  That is every update of a branch front once the elimination has reached its second child (k0 >= ni1).
+    if (env && h_ni && !clipped) op.env = 0;
     hipEvent_t e0 = pf->begin(s);
-    launch_gemm_op<T>(dn, nbatch, M, N, op, s, route, shifted);
+    launch_gemm_op<T>(dn, nbatch, M, N, op, s, route, shifted, op.env ? live : -1);
     pf->end(e0, HS_CAT_GEMM, s, fl, M, N, K, nbatch, 0, hiprio);
     dbg("gemm", cmat, r0, c0, k0);
   }

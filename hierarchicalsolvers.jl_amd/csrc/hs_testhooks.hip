@@ -388,6 +388,8 @@ struct FrontBatch {
   SolveNode<T>* dsn = nullptr;
   std::vector<NodeDesc<T>> hn;
   std::vector<SolveNode<T>> hs;  // filled by setup, reaches the device with upload_solve (a caller may complete it in between)
+  std::vector<int> env_host;     // caller-made block envelopes (set_env): firstL then firstU of every front, packed in batch order
+  std::vector<const int*> h_env; // ... one pointer per front, for Sched::h_env; empty: the batch is dense
   // the argument checks both hooks share; nothing on the device yet
   static void check(const char* name, int64_t count, const int64_t* ni_, const int64_t* nb_, const T* F, int mode, int mode_lo, int mode_hi = 3) {
     if (count <= 0 || count > 65535 || !ni_ || !nb_ || !F || mode < mode_lo || mode > mode_hi)
@@ -399,6 +401,7 @@ struct FrontBatch {
   }
   void setup(int64_t count_, const int64_t* ni_, const int64_t* nb_, const T* F);
   void upload_solve() { HS_HIP(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice)); }
+  void set_env(const int32_t* env);
   int aligned16_status() const;
   void factor(int mode, double* ms_out);
   void copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U);
@@ -475,6 +478,25 @@ void FrontBatch<T>::setup(int64_t count_, const int64_t* ni_, const int64_t* nb_
   HS_HIP(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
 }
 
+// Block envelopes made by the caller (hs_envelope.h: 2 * hs_env_nblocks(ni, nb) entries per front, firstL then firstU, packed in batch order):
+// every front gets its table, and the optimistic modes then run the batch as hs_numeric runs a level whose fronts carry tables (Sched::env).
+template <class T>
+void FrontBatch<T>::set_env(const int32_t* env) {
+  size_t nE = 0;
+  for (int64_t k = 0; k < count; ++k) nE += 2 * (size_t)hs_env_nblocks(o[k].ni, o[k].nb);
+  env_host.assign(env, env + nE);
+  int* denv = buf.get<int>(nE);
+  HS_HIP(hipMemcpy(denv, env_host.data(), sizeof(int) * nE, hipMemcpyHostToDevice));
+  h_env.resize(count);
+  size_t off = 0;
+  for (int64_t k = 0; k < count; ++k) {
+    hn[k].env = denv + off;
+    h_env[k] = env_host.data() + off;
+    off += 2 * (size_t)hs_env_nblocks(o[k].ni, o[k].nb);
+  }
+  HS_HIP(hipMemcpy(dn, hn.data(), sizeof(NodeDesc<T>) * count, hipMemcpyHostToDevice));
+}
+
 // The premise of Sched::aligned16, which hs_numeric sets for the dense batch of a level: setup lays LF / UR / SB of every front out at multiples
 // of 32 elements of a hipMalloc block (so 16-byte aligned) with even ldl / ldu / lds.  HS_OK when that holds for the whole batch.
 template <class T>
@@ -513,6 +535,10 @@ void FrontBatch<T>::factor(int mode, double* ms_out) {
   if (mode >= 2) sch.sn = dsn;
   sch.optimistic = (mode == 1 || mode == 2);
   sch.aligned16 = aligned;
+  if (sch.optimistic && !h_env.empty()) {
+    sch.env = true;
+    sch.h_env = h_env.data();
+  }
   const auto h0 = std::chrono::steady_clock::now();
   sch.factor_fronts();
   HS_HIP(hipEventRecord(ev[1], st.main));
@@ -555,12 +581,14 @@ void FrontBatch<T>::copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, i
 template <class T>
 static void front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, T* outLF, T* outUR, T* outSB,
                              int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U,
-                             double* ms_out) {
+                             double* ms_out, const int32_t* env = nullptr) {
   FrontBatch<T>::check("hsk_front_batch", count, ni_, nb_, F, mode, 0, 7);
+  if (env && (mode & 3) != 1 && (mode & 3) != 2) HS_FAIL(HS_ERR_ARGUMENT, mode, "hsk_front_batch_env: block envelopes hold under optimistic pivoting only (modes 1, 2)");
   if ((outInvL || outInvU || outInv256L || outInv256U) && (mode & 3) < 2)
     HS_FAIL(HS_ERR_ARGUMENT, mode, "hsk_front_batch: the stored inverses are returned by modes 2 and 3 only");
   FrontBatch<T> fb;
   fb.setup(count, ni_, nb_, F);
+  if (env) fb.set_env(env);
   fb.upload_solve();
   fb.factor(mode, ms_out);
   fb.copy_out(outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U);
@@ -708,6 +736,10 @@ extern "C" int hsk_front_batch_d(int64_t count, const int64_t* ni, const int64_t
                                  double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
                                  double* outInv256L, double* outInv256U, double* ms_out) {
   HS_GUARD(front_batch_hook<double>(count, ni, nb, mode, F, outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U, ms_out));
+}
+extern "C" int hsk_front_batch_env_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int32_t* env, double* outLF,
+                                     double* outUR, double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth) {
+  HS_GUARD(front_batch_hook<double>(count, ni, nb, mode, F, outLF, outUR, outSB, out_rperm, info, growth, nullptr, nullptr, nullptr, nullptr, nullptr, env));
 }
 extern "C" int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
                                  double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
@@ -1200,18 +1232,30 @@ extern "C" int hsk_gn_rowsq_d(int64_t n, int64_t kc, const double* X, int64_t ld
 extern "C" int hsk_gn_rowsq_z(int64_t n, int64_t kc, const double* X, int64_t ldx, double* acc) { HS_GUARD(gn_rowsq_hook<cplx>(n, kc, (const cplx*)X, ldx, acc)); }
 
 #include "hs_envelope.h"
+static bool envelope_args_ok(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, const int32_t* firstL,
+                             const int32_t* firstU) {
+  if (n <= 0 || !colptr || !rowval || !fidx || ni < 0 || nb < 0 || ni + nb <= 0 || !firstL || !firstU) return false;
+  for (int64_t p = 0; p < ni + nb; ++p)
+    if (fidx[p] < 0 || fidx[p] >= n) return false;
+  if (colptr[0] != 1) return false;
+  for (int64_t j = 0; j < n; ++j)
+    if (colptr[j + 1] < colptr[j]) return false;
+  for (int64_t e = 0; e < colptr[n] - 1; ++e)
+    if (rowval[e] < 1 || rowval[e] > n) return false;
+  return true;
+}
 extern "C" int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL,
                                  int32_t* firstU) {
-  if (n <= 0 || !colptr || !rowval || !fidx || ni < 0 || nb < 0 || ni + nb <= 0 || !firstL || !firstU) return -1;
-  for (int64_t p = 0; p < ni + nb; ++p)
-    if (fidx[p] < 0 || fidx[p] >= n) return -1;
-  if (colptr[0] != 1) return -1;
-  for (int64_t j = 0; j < n; ++j)
-    if (colptr[j + 1] < colptr[j]) return -1;
-  for (int64_t e = 0; e < colptr[n] - 1; ++e)
-    if (rowval[e] < 1 || rowval[e] > n) return -1;
+  if (!envelope_args_ok(n, colptr, rowval, fidx, ni, nb, firstL, firstU)) return -1;
   std::vector<int> where((size_t)n, -1);
   hs_leaf_envelope(colptr, rowval, fidx, (int)ni, (int)nb, where.data(), firstL, firstU);
+  return 0;
+}
+extern "C" int hsk_branch_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int64_t ni1,
+                                   int64_t nb1, int32_t* firstL, int32_t* firstU) {
+  if (!envelope_args_ok(n, colptr, rowval, fidx, ni, nb, firstL, firstU) || ni1 < 0 || ni1 > ni || nb1 < 0 || nb1 > nb) return -1;
+  std::vector<int> where((size_t)n, -1);
+  hs_branch_envelope(colptr, rowval, fidx, (int)ni, (int)nb, (int)ni1, (int)nb1, where.data(), firstL, firstU);
   return 0;
 }
 

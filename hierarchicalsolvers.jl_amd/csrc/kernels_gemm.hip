@@ -1068,6 +1068,7 @@ __global__ void resolve_dump_kernel(const NodeDesc<T>* __restrict__ nodes, GemmO
 // Switches of the leaf envelope and of the device-side flop count (test hooks, include/hs_kernels.h)
 namespace {
 std::atomic<int> g_env_on{-1};      // -1: not read yet (HS_LEAF_ENVELOPE, default on)
+std::atomic<int> g_benv_on{-1};     // -1: not read yet (HS_BRANCH_ENVELOPE, default on)
 std::atomic<int> g_op_count_on{0};
 std::atomic<int> g_lds_on{-1};      // -1: not read yet (HS_GEMM_LDS, default on)
 std::atomic<long long> g_lds_launches{0};
@@ -1111,6 +1112,21 @@ bool hs_envelope_enabled() {
 extern "C" int hsk_envelope_enable(int on) {  // returns the previous setting
   const int prev = hs_envelope_enabled() ? 1 : 0;
   g_env_on.store(on ? 1 : 0);
+  return prev;
+}
+// the branch fronts' tables alone; effective only while the envelope as a whole is on
+bool hs_branch_envelope_enabled() {
+  int v = g_benv_on.load();
+  if (v < 0) {
+    const char* e = getenv("HS_BRANCH_ENVELOPE");
+    v = (e && e[0] == '0') ? 0 : 1;
+    g_benv_on.store(v);
+  }
+  return v != 0;
+}
+extern "C" int hsk_branch_envelope_enable(int on) {  // returns the previous setting
+  const int prev = hs_branch_envelope_enabled() ? 1 : 0;
+  g_benv_on.store(on ? 1 : 0);
   return prev;
 }
 extern "C" int hsk_op_flops_mode(int on) {  // resets the counter
@@ -1178,7 +1194,8 @@ static OpKernel<T> pick_op_kernel(const GemmOp& op, int route) {
 }
 
 template <class T>
-void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s, int route, bool shifted) {
+void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s, int route, bool shifted,
+                    long long live_tiles) {
   if (nbatch <= 0 || maxM <= 0 || maxN <= 0) return;
   GemmOp op = op_in;
   op.count = (!op.ainv && g_op_count_on.load(std::memory_order_relaxed)) ? 1 : 0;
@@ -1190,11 +1207,15 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
   if (route == HS_GEMM_ROUTE_EDGE && shifted) maxM += 1;  // a front whose A sits at an odd row runs one row higher (edge_shift_rows)
   int tiles = ((maxM + TileCfg<T>::BM - 1) / TileCfg<T>::BM) * ((maxN + TileCfg<T>::BN - 1) / TileCfg<T>::BN);
   if (op.cap > 0 && tiles > op.cap) tiles = std::max(8, op.cap / 8 * 8);
-  // Enveloped launch (a batch of leaf fronts): most tiles of the bounding box are empty.  A workgroup per tile would start, read its
+  // Enveloped launch of a batch of leaf fronts: most tiles of the bounding box are empty.  A workgroup per tile would start, read its
   // descriptor and leave; instead a quarter as many workgroups (HS_ENV_WALK, 1: off) walk the tiles, so that an empty tile costs a table
-  // look-up inside a running workgroup.  The batch itself keeps the chip full (hundreds of fronts).
+  // look-up inside a running workgroup.  The batch itself keeps the chip full (hundreds of fronts).  A branch front is the other case: most
+  // of its tiles run, and a workgroup that walks four of them in a row loses the second resident workgroup of its CU that hides the C
+  // traffic of the first.  So the walk is no longer than the grid's share of empty tiles, which the caller counted (live_tiles; -1: unknown).
   if (op.env && !(op.cap > 0)) {
-    static const int walk = getenv("HS_ENV_WALK") ? atoi(getenv("HS_ENV_WALK")) : 4;
+    static const int walk_max = getenv("HS_ENV_WALK") ? atoi(getenv("HS_ENV_WALK")) : 4;
+    int walk = walk_max;
+    if (live_tiles >= 0) walk = (int)std::min<long long>(walk, (long long)tiles * nbatch / std::max(1LL, live_tiles));
     if (walk > 1 && tiles >= 32 && (long long)tiles * nbatch >= 4096) tiles = std::max(8, tiles / walk / 8 * 8);
   }
   static std::once_flag once_reg;
@@ -1291,7 +1312,7 @@ void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN,
   hipLaunchKernelGGL(gemm_probs_kernel<T>, dim3(tiles, nprob), dim3(256), lds_bytes, s, dprobs, minus);
 }
 
-template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, const GemmOp&, hipStream_t, int, bool);
-template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t, int, bool);
+template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, const GemmOp&, hipStream_t, int, bool, long long);
+template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t, int, bool, long long);
 template void launch_gemm_probs<double>(const GemmProb<double>*, int, int, int, int, hipStream_t);
 template void launch_gemm_probs<cplx>(const GemmProb<cplx>*, int, int, int, int, hipStream_t);

@@ -53,6 +53,11 @@ int hsk_front_batch_d(int64_t count, const int64_t* ni, const int64_t* nb, int m
 int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
                       double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
                       double* outInv256L, double* outInv256U, double* ms_out);
+/* hsk_front_batch_d with block envelopes made by the caller (optimistic modes 1, 2, with or without bit 2): env holds, per front in batch
+ * order, firstL then firstU, ceil(ni/32) + ceil(nb/32) entries each, as hsk_leaf_envelope lays them out; the caller vouches that every entry
+ * of F outside them is zero.  The batch then runs as hs_numeric runs a level whose fronts carry tables (Sched::env).  env == NULL: dense. */
+int hsk_front_batch_env_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int32_t* env, double* outLF,
+                          double* outUR, double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth);
 
 /* One tree level of ldiv!: the batch of hsk_front_batch_* (same packing of ni, nb, F), factored in mode 2 or 3 so that the stored inverses are
  * the production ones, then the level's forward and backward sweeps on the global vector b (length n), through the per-level driver that
@@ -254,13 +259,17 @@ int hsk_bisect_perm(int64_t n, const int64_t* colptr, const int64_t* rowval, int
 int hs_probs_stats_mode(int mode);
 int hs_probs_stats(double* out3);
 
-/* Block envelope of leaf fronts (optimistic pivoting eliminates a leaf inside the envelope of its sparsity pattern, taken per 32-row /
- * 32-column block).
+/* Block envelope of leaf and branch fronts (optimistic pivoting eliminates a front inside the envelope of its sparsity pattern, taken per
+ * 32-row / 32-column block).
  *   hsk_leaf_envelope   : host only, no device.  The builder the analysis runs for every leaf: CSC pattern of A (1-based colptr / rowval, n
  *                         columns), fidx = ni + nb global ids (0-based) in front order [int; bnd]; firstL / firstU receive
  *                         ceil(ni / 32) + ceil(nb / 32) entries each (interior blocks first, boundary blocks counted from the start of the
  *                         boundary part): first interior column / row, rounded down to a multiple of 32, with a structural entry in the
  *                         block's rows / columns; 2^30 = none.  Returns 0, or -1 for a bad argument.
+ *   hsk_branch_envelope : the same for a branch front [int1; int2 | bnd1; bnd2] with ni1 = |int1|, nb1 = |bnd1|: the pattern is every pair of
+ *                         positions of the same child, the stored entries of A between the front's DOFs and the interior diagonal.
+ *   hsk_branch_envelope_enable : 1 / 0 turns the branch fronts' tables alone on / off (default: on unless HS_BRANCH_ENVELOPE=0); returns the
+ *                         previous setting.  Effective only while hsk_envelope_enable is on.
  *   hsk_envelope_enable : 1 / 0 turns the envelope on / off for the factorizations that follow (default: on unless HS_LEAF_ENVELOPE=0);
  *                         returns the previous setting.  Off, every front is eliminated as a dense matrix.
  *   hsk_op_flops_mode   : 1: the plain updates add the flops of the K-steps they really run to a device counter (one atomic per tile);
@@ -269,7 +278,10 @@ int hs_probs_stats(double* out3);
  *                         hsk_op_flops(out) reads the counter (synchronises the device): equals hs_stats.gemm_flops.
  *   (hsk_leaf_envelope checks fidx, colptr and rowval against n.) */
 int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL, int32_t* firstU);
+int hsk_branch_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int64_t ni1, int64_t nb1,
+                        int32_t* firstL, int32_t* firstU);
 int hsk_envelope_enable(int on);
+int hsk_branch_envelope_enable(int on);
 int hsk_op_flops_mode(int on);
 int hsk_op_flops(double* out);
 

@@ -1,0 +1,121 @@
+"""usage (no GPU): python tools/branch_envelope_model.py [WORKLOAD] -- flops of the branch fronts eliminated inside their block envelope
+(csrc/hs_envelope.h: hs_branch_envelope) against the dense count, per tree level, on the tree bench.py prepares (default poisson3d_128).
+
+Every entry C[r, c] of a front takes the products k in [max(firstL[block of r], firstU[block of c]), min(r, c, ni)).  The tables are the
+library's own (hsk_branch_envelope, host only).  Two counts: `env 32` clips per 32-block pair, which is what the tables allow; `env T` clips
+per tile of T x T positions (T = 128, or the environment variable T), a tile starting at the smallest start of its 32-blocks -- what a GEMM
+tile of that size can skip (an estimate: the real tiles are aligned to their launch, not to the front).  Leaves are not counted."""
+import ctypes as C
+import os
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sp
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hsamd  # noqa: E402
+
+G = 32
+NONE = 1 << 30
+
+
+def tables(L, colptr, rowval, n, idx, ni, ni1, nb1):
+    m = len(idx)
+    nblk = (ni + G - 1) // G + (m - ni + G - 1) // G
+    fL = np.empty(nblk, dtype=np.int32)
+    fU = np.empty(nblk, dtype=np.int32)
+    fidx = np.ascontiguousarray(idx, dtype=np.int32)
+    p64, p32 = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+    rc = L.hsk_branch_envelope(n, colptr.ctypes.data_as(p64), rowval.ctypes.data_as(p64), fidx.ctypes.data_as(p32), ni, m - ni, ni1, nb1,
+                               fL.ctypes.data_as(p32), fU.ctypes.data_as(p32))
+    assert rc == 0
+    return fL.astype(np.int64), fU.astype(np.int64)
+
+
+def coarsen(f, nbi, t):
+    """the start a tile of t 32-blocks sees: the smallest of its blocks (interior and boundary blocks grouped separately)"""
+    out = f.copy()
+    for lo, hi in ((0, nbi), (nbi, len(f))):
+        for b in range(lo, hi, t):
+            out[b : min(b + t, hi)] = f[b : min(b + t, hi)].min()
+    return out
+
+
+def front_macs(ni, nb, fL, fU):
+    """multiply-adds of one front: sum over (r, c) of max(0, min(r, c, ni) - max(firstL[r], firstU[c])), by 32-block pairs; None: dense"""
+    m = ni + nb
+    nbi = (ni + G - 1) // G
+    start = np.concatenate([np.arange(nbi) * G, ni + np.arange((nb + G - 1) // G) * G])
+    size = np.minimum(np.concatenate([np.full(nbi, ni), np.full(len(start) - nbi, m)]) - start, G)
+    pos = np.concatenate([np.arange(nbi), np.full(len(start) - nbi, nbi)])  # elimination order of the blocks: the boundary comes last, all alike
+    # sum over the block's positions of min(p, ni), and the value a block's positions have at least
+    rs = np.where(start < ni, size * start + size * (size - 1) // 2, size * ni).astype(np.float64)
+    ustart = np.minimum(start, ni)
+    if fL is None:
+        lo = np.zeros((len(start), len(start)))
+    else:
+        lo = np.maximum(fL[:, None], fU[None, :]).astype(np.float64)
+    sz = size.astype(np.float64)
+    upper_is_row = (pos[:, None] < pos[None, :]) | ((pos[:, None] == nbi) & (pos[None, :] == nbi))  # min(r, c, ni) is decided by the row
+    upper_is_col = pos[:, None] > pos[None, :]
+    a = np.where(lo <= ustart[:, None], (rs[:, None] - lo * sz[:, None]) * sz[None, :], 0.0)
+    b = np.where(lo <= ustart[None, :], (rs[None, :] - lo * sz[None, :]) * sz[:, None], 0.0)
+    macs = np.where(upper_is_row, a, 0.0).sum() + np.where(upper_is_col, b, 0.0).sum()
+    # interior diagonal blocks: sum of min(r, c) - lo, lo <= the block's start
+    d = np.arange(nbi)
+    s = size[d].astype(np.float64)
+    mins = s * s * start[d] + (s - 1) * s * (2 * s - 1) / 6.0
+    macs += (mins - np.diagonal(lo)[:nbi] * s * s).sum()
+    return macs
+
+
+def main():
+    name = sys.argv[1] if len(sys.argv) > 1 else "poisson3d_128"
+    T = int(os.environ.get("T", "128")) // G
+    hs = hsamd.load()
+    L = hs._lib.lib()
+    t0 = time.time()
+    A, b, nd = hs.problems.make_problem(name, rhs="randn")
+    nd, nd_loc = hs.symfact(nd)
+    perm = hs.postorder(nd)
+    Ap = sp.csc_matrix(A[perm - 1][:, perm - 1])
+    nd = hs.permuted(nd, hs.invperm(perm))
+    n = Ap.shape[0]
+    colptr = np.ascontiguousarray(Ap.indptr, dtype=np.int64) + 1
+    rowval = np.ascontiguousarray(Ap.indices, dtype=np.int64) + 1
+    lev = {}
+    stack = [(nd, 1)]
+    while stack:
+        x, lv = stack.pop()
+        if x.left is None and x.right is None:
+            continue
+        stack += [(c, lv + 1) for c in (x.left, x.right) if c is not None]
+        it, bd = np.asarray(x.int) - 1, np.asarray(x.bnd) - 1
+        ni, nb = len(it), len(bd)
+        if ni == 0:
+            continue
+        lb = np.asarray(x.left.bnd) - 1 if x.left is not None else np.zeros(0, np.int64)
+        ni1, nb1 = int(np.isin(it, lb).sum()), int(np.isin(bd, lb).sum())
+        fL, fU = tables(L, colptr, rowval, n, np.concatenate([it, bd]), ni, ni1, nb1)
+        nbi = (ni + G - 1) // G
+        r = lev.setdefault(lv, dict(fronts=0, ni=0, nb=0, dense=0.0, e32=0.0, eT=0.0))
+        r["fronts"] += 1
+        r["ni"], r["nb"] = max(r["ni"], ni), max(r["nb"], nb)
+        r["dense"] += 2.0 * front_macs(ni, nb, None, None)
+        r["e32"] += 2.0 * front_macs(ni, nb, fL, fU)
+        r["eT"] += 2.0 * front_macs(ni, nb, coarsen(fL, nbi, T), coarsen(fU, nbi, T))
+    print("# %s, n = %d: flops of the branch fronts, dense and inside the block envelope (%.1f s)" % (name, n, time.time() - t0))
+    print("| level | fronts | max (ni, nb) | dense | env 32 | ratio | env %d | ratio |" % (T * G))
+    print("|---|---|---|---|---|---|---|---|")
+    tot = np.zeros(3)
+    for lv in sorted(lev):
+        r = lev[lv]
+        tot += [r["dense"], r["e32"], r["eT"]]
+        print("| %d | %d | %d, %d | %.4g | %.4g | %.3f | %.4g | %.3f |" % (lv, r["fronts"], r["ni"], r["nb"], r["dense"], r["e32"], r["e32"] / r["dense"],
+                                                                     r["eT"], r["eT"] / r["dense"]))
+    print("| all | | | %.4g | %.4g | %.3f | %.4g | %.3f |" % (tot[0], tot[1], tot[1] / tot[0], tot[2], tot[2] / tot[0]))
+
+
+if __name__ == "__main__":
+    main()
