@@ -157,6 +157,8 @@ struct GemmOp {
   int env;         // 1: fronts that carry a block envelope (NodeDesc::env) skip the K range and the tiles known to be exact zeros (optimistic pivoting only)
   int count;       // 1: the launch goes to gemm_op_env_kernel, which adds the flops of the K-steps it runs to a device counter (hsk_op_flops; set by
                    // launch_gemm_op while the hook is on)
+  int order;       // 1: an enveloped plain update deals its tiles to the XCDs in the balanced order (env_order_stride, kernels_gemm.hip; set by
+                   // launch_gemm_op unless HS_ENV_ORDER=0 / hsk_env_order_enable(0)); 0: the order of the dense launches
 };
 
 // Block envelope of a leaf front (hs_envelope.h): the smallest entry of `first` over the 32-blocks that meet the front positions [lo, hi).

@@ -60,7 +60,7 @@ struct TileCfg<cplx> {
 // bijective XCD-aware remap of a 1-D block id (cdna guide section 5, "XCD swizzle must be bijective"):
 // blocks b and b+8 share an XCD; give each XCD a contiguous chunk of tile ids so neighbouring tiles
 // (which share A row-panels / B column-panels) hit the same L2.
-__device__ inline int xcd_remap(int bid, int nwg) {
+__host__ __device__ inline int xcd_remap(int bid, int nwg) {
   int q = nwg >> 3, r = nwg & 7, x = bid & 7, o = bid >> 3;
   int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
   return base + o;
@@ -69,7 +69,7 @@ __device__ inline int xcd_remap(int bid, int nwg) {
 // workgroup id blockIdx.x + gridDim.x * blockIdx.y, so block `bid` of front y sits on XCD (bid + shift) & 7 with shift = (gridDim.x * y) & 7.
 // Round 2 assumed bid & 7 for every front: with gridDim.x not a multiple of 8 the chunks of every front but the first grouped tiles of
 // DIFFERENT L2s.  Bijective on [0, nwg): XCD x owns the bids first_x, first_x + 8, ... and gets a contiguous chunk.
-__device__ inline int xcd_remap_shift(int bid, int nwg, int shift) {
+__host__ __device__ inline int xcd_remap_shift(int bid, int nwg, int shift) {
   if (shift == 0) return xcd_remap(bid, nwg);
   const int x = (bid + shift) & 7;
   int base = 0;
@@ -83,7 +83,7 @@ __device__ inline int xcd_remap_shift(int bid, int nwg, int shift) {
 }
 
 // tile id -> (tile_m, tile_n): walk column-panels of GROUP_M tiles so a group shares B panels and re-uses A panels
-__device__ inline void tile_coords(int t, int tiles_m, int tiles_n, int& tm, int& tn) {
+__host__ __device__ inline void tile_coords(int t, int tiles_m, int tiles_n, int& tm, int& tn) {
   const int GROUP_M = 8;
   int per_group = GROUP_M * tiles_n;
   int g = t / per_group;
@@ -92,6 +92,30 @@ __device__ inline void tile_coords(int t, int tiles_m, int tiles_n, int& tm, int
   int in_g = t - g * per_group;
   tm = first_m + in_g % gm;
   tn = in_g / gm;
+}
+
+// Balanced tile order of an enveloped plain update (GemmOp::order; HS_ENV_ORDER, DESIGN.md section 4 "Branch fronts").  The remap above hands
+// every XCD the same NUMBER of tiles, a contiguous run of tile rows; under an envelope the K length of a tile depends on where it lies -- in a
+// branch front [int1; int2 | bnd1; bnd2] the tiles of bnd1 x bnd1 run all of K, every other tile starts at ni1 -- so the XCDs that own the
+// upper rows finish last.  The order sends tile row i to (i * s) mod T with s the integer nearest 0.618 T that is coprime to T (a bijection
+// of [0, T)): any window of consecutive i lands spread over the whole row range, so every chunk holds about the same mix of long and short
+// tiles.  The columns go through the same map: a chunk boundary that cuts a group of 8 tile rows cuts it by COLUMNS (tile_coords runs down
+// the group column after column), and left alone one chunk would get the group's left, long columns and the next its right, short ones.
+// The 8 tile rows of a group are still 8 rows and its columns still columns: co-resident workgroups share A row panels and B column panels
+// in L2 as before.  T <= 8 (one group: nothing to deal) keeps s = 1.  Plain updates only: their tiles are independent of one another.
+__host__ __device__ inline int env_order_stride(int T) {
+  if (T <= 8) return 1;
+  const int s0 = (T * 40503 + 32768) >> 16;  // 40503 / 65536 = 0.61803; T is a tile count, at most 2^15 (a front of 4 M rows) in all int products here
+  for (int d = 0;; ++d)                      // ends at s = 1 at the latest (s0 - d >= 1 > 0 up to there)
+    for (int s = s0 - d; s <= s0 + d; s += (d ? 2 * d : 1)) {
+      int a = s, b = T;
+      while (b) { const int r = a % b; a = b; b = r; }
+      if (a == 1) return s;
+    }
+}
+__host__ __device__ inline void env_order_apply(int& tm, int& tn, int tiles_m, int tiles_n, int sm, int sn) {
+  if (sm > 1) tm = tm * sm % tiles_m;
+  if (sn > 1) tn = tn * sn % tiles_n;
 }
 
 // The block envelope of a leaf front (GemmOp::env, NodeDesc::env; hs_envelope.h) comes back in `e`: which of firstL / firstU says something
@@ -882,12 +906,15 @@ __device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* s
 
 // The same loop for a launch whose fronts may carry a block envelope (gemm_op_env_kernel, trsm_inv_env_kernel below)
 template <class T, Tile TILE = Tile::Reg>  // (enveloped launches have no Tile::Lds twin: launch_gemm_op sends them to the edge tile)
-__device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* smem, const EnvClip* e, int count, int mlo = 0) {
+__device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* smem, const EnvClip* e, int count, int order, int mlo = 0) {
   const TileWalk<T> w(p.M, p.N);
+  // (GemmOp::order: the strides of the balanced order, once per front and uniform over the workgroup; 1, 1 is the order of the dense launches)
+  const int sm = order ? env_order_stride(w.tiles_m) : 1, sn = order ? env_order_stride(w.tiles_n) : 1;
   bool ran = false;
   for (int bid = blockIdx.x; bid < w.ntiles; bid += gridDim.x) {
     int tm, tn;
     w.coords(bid, tm, tn);
+    env_order_apply(tm, tn, w.tiles_m, w.tiles_n, sm, sn);
     int dk = 0;
     {
       // Leaf front with a block envelope: everything here is uniform over the workgroup and done once per tile; the tile code is handed a
@@ -989,7 +1016,7 @@ __global__ __launch_bounds__(256, 2) void gemm_op_env_kernel(const NodeDesc<T>* 
   if (op.prio) __builtin_amdgcn_s_setprio(2);
   if (op.ainv) return;  // (launch_gemm_op sends those to trsm_inv_env_kernel: lets the compiler drop the in-place forms and their growth check here)
   if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
-  gemm_dispatch_env<T>(p, true, smem, &e, op.count);
+  gemm_dispatch_env<T>(p, true, smem, &e, op.count, op.order);
 }
 // The enveloped plain update on the edge tile (batches of leaf fronts whose k0 is even): the clip moves A and B by a multiple of 32
 // columns / rows, which keeps their alignment and the K tail.  A shifted front looks its rows up one position higher (row0 - 1): the
@@ -1009,7 +1036,7 @@ __global__ __launch_bounds__(256, 2) void gemm_op_env_lds_kernel(const NodeDesc<
   if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
   const int mlo = edge_shift_rows(p);
   e.row0 -= mlo;
-  gemm_dispatch_env<T, Tile::LdsEdge>(p, true, smem, &e, 0, mlo);
+  gemm_dispatch_env<T, Tile::LdsEdge>(p, true, smem, &e, 0, op.order, mlo);
 }
 template <class T>
 __global__ __launch_bounds__(256, 2) void trsm_inv_env_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
@@ -1019,7 +1046,7 @@ __global__ __launch_bounds__(256, 2) void trsm_inv_env_kernel(const NodeDesc<T>*
   __builtin_amdgcn_s_setprio(2);
   if (!op.ainv) return;  // (plain updates run as gemm_op_env_kernel)
   if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
-  gemm_dispatch_env<T>(p, false, smem, &e, 0);
+  gemm_dispatch_env<T>(p, false, smem, &e, 0, 0);  // (in place, one tile row or column per launch: the order of the dense launches)
 }
 
 // Accounting of the grouped products (hs_probs_stats, include/hs_kernels.h): the descriptors live on the device, so the kernel itself adds
@@ -1069,6 +1096,7 @@ __global__ void resolve_dump_kernel(const NodeDesc<T>* __restrict__ nodes, GemmO
 namespace {
 std::atomic<int> g_env_on{-1};      // -1: not read yet (HS_LEAF_ENVELOPE, default on)
 std::atomic<int> g_benv_on{-1};     // -1: not read yet (HS_BRANCH_ENVELOPE, default on)
+std::atomic<int> g_env_order_on{-1};  // -1: not read yet (HS_ENV_ORDER, default on)
 std::atomic<int> g_op_count_on{0};
 std::atomic<int> g_lds_on{-1};      // -1: not read yet (HS_GEMM_LDS, default on)
 std::atomic<long long> g_lds_launches{0};
@@ -1128,6 +1156,36 @@ extern "C" int hsk_branch_envelope_enable(int on) {  // returns the previous set
   const int prev = hs_branch_envelope_enabled() ? 1 : 0;
   g_benv_on.store(on ? 1 : 0);
   return prev;
+}
+// HS_ENV_ORDER=0 / hsk_env_order_enable(0): enveloped plain updates walk their tiles in the order of the dense launches
+static bool env_order_enabled() {
+  int v = g_env_order_on.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("HS_ENV_ORDER");
+    v = (e && e[0] == '0') ? 0 : 1;
+    g_env_order_on.store(v);
+  }
+  return v != 0;
+}
+extern "C" int hsk_env_order_enable(int on) {  // returns the previous setting
+  const int prev = env_order_enabled() ? 1 : 0;
+  g_env_order_on.store(on ? 1 : 0);
+  return prev;
+}
+// The tile every block id of a launch with one workgroup per tile gets (first front of a batch: shift 0), by the functions
+// gemm_dispatch_env calls.  Host only.
+extern "C" int hsk_env_tile_order(int tiles_m, int tiles_n, int order, int32_t* tm, int32_t* tn) {
+  if (tiles_m <= 0 || tiles_n <= 0 || tiles_m > 32768 || tiles_n > 32768 || !tm || !tn || (long long)tiles_m * tiles_n > (1 << 24)) return -1;
+  const int ntiles = tiles_m * tiles_n;
+  const int sm = order ? env_order_stride(tiles_m) : 1, sn = order ? env_order_stride(tiles_n) : 1;
+  for (int bid = 0; bid < ntiles; ++bid) {
+    int m, n;
+    tile_coords(xcd_remap_shift(bid, ntiles, 0), tiles_m, tiles_n, m, n);
+    env_order_apply(m, n, tiles_m, tiles_n, sm, sn);
+    tm[bid] = m;
+    tn[bid] = n;
+  }
+  return 0;
 }
 extern "C" int hsk_op_flops_mode(int on) {  // resets the counter
   (void)hipDeviceSynchronize();
@@ -1199,6 +1257,7 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
   if (nbatch <= 0 || maxM <= 0 || maxN <= 0) return;
   GemmOp op = op_in;
   op.count = (!op.ainv && g_op_count_on.load(std::memory_order_relaxed)) ? 1 : 0;
+  op.order = (op.env && !op.ainv && env_order_enabled()) ? 1 : 0;
   static const bool dump = getenv("HS_DEBUG_SYNC") && getenv("HS_DEBUG_SYNC")[0] == '2';
   if (dump) dump_resolved_op(dnodes, nbatch, maxM, maxN, op, s);
   // (the caller vouches for K and the alignment of every front: hs_gemm_lds_route)

@@ -276,12 +276,21 @@ int hs_probs_stats(double* out3);
  *                         resets the counter.  Counting changes which kernel runs: while it is on, every plain update -- of dense fronts
  *                         too -- is launched as `gemm_op_env_kernel` (the same tile code; `gemm_op_kernel` holds no counter).
  *                         hsk_op_flops(out) reads the counter (synchronises the device): equals hs_stats.gemm_flops.
+ *   hsk_env_order_enable : 1 / 0 turns the balanced tile order of the enveloped plain updates on / off (default: on unless HS_ENV_ORDER=0);
+ *                         returns the previous setting.  Off, an enveloped launch maps block ids to tiles as a dense one does.  Which
+ *                         workgroup runs a tile changes, never what the tile computes: every stored value keeps its bits.
+ *   hsk_env_tile_order  : host only, no device.  For bid = 0 .. tiles_m * tiles_n - 1, the tile (tm[bid], tn[bid]) that block `bid` of a
+ *                         launch with one workgroup per tile runs (first front of a batch), by the functions the kernels call; order 0 /
+ *                         1 as the switch.  Blocks bid, bid + 8, ... share an XCD.  Returns 0, or -1 for a bad argument (a tile count outside
+ *                         1 .. 32768, more than 2^24 tiles in all, a null pointer).
  *   (hsk_leaf_envelope checks fidx, colptr and rowval against n.) */
 int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL, int32_t* firstU);
 int hsk_branch_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int64_t ni1, int64_t nb1,
                         int32_t* firstL, int32_t* firstU);
 int hsk_envelope_enable(int on);
 int hsk_branch_envelope_enable(int on);
+int hsk_env_order_enable(int on);
+int hsk_env_tile_order(int tiles_m, int tiles_n, int order, int32_t* tm, int32_t* tn);
 int hsk_op_flops_mode(int on);
 int hsk_op_flops(double* out);
 

@@ -4,7 +4,12 @@
 Every entry C[r, c] of a front takes the products k in [max(firstL[block of r], firstU[block of c]), min(r, c, ni)).  The tables are the
 library's own (hsk_branch_envelope, host only).  Two counts: `env 32` clips per 32-block pair, which is what the tables allow; `env T` clips
 per tile of T x T positions (T = 128, or the environment variable T), a tile starting at the smallest start of its 32-blocks -- what a GEMM
-tile of that size can skip (an estimate: the real tiles are aligned to their launch, not to the front).  Leaves are not counted."""
+tile of that size can skip (an estimate: the real tiles are aligned to their launch, not to the front).  Leaves are not counted.
+
+A second table takes the level-wide Schur launch of every branch level -- the longest plain update of a level -- tile by tile: the K-steps
+each of the 8 XCDs runs under the dense tile order and under the balanced one (GemmOp::order, HS_ENV_ORDER; the block id -> tile map is the
+library's own, hsk_env_tile_order), as heaviest XCD over mean.  The other plain updates of a level (panel and block-column updates inside
+the interior part) are not modelled: they follow the blocked LU schedule, which this tool does not restate."""
 import ctypes as C
 import os
 import sys
@@ -70,6 +75,60 @@ def front_macs(ni, nb, fL, fU):
     return macs
 
 
+XCDS = 8
+BM = 128  # the Float64 tile (TileCfg<double>: 128 x 128, BK = 16)
+BK = 16
+
+
+def xcd_remap_shift(bid, nwg, shift):
+    """csrc/kernels_gemm.hip restated: block `bid` of a front sits on XCD (bid + shift) & 7; XCD x owns a contiguous chunk of tile ids"""
+    x = (bid + shift) & 7
+    first = (np.arange(XCDS) - shift) & 7
+    cnt = np.where(first < nwg, (nwg - first + 7) >> 3, 0)
+    base = np.concatenate([[0], np.cumsum(cnt)])[x]
+    return base + ((bid - ((x - shift) & 7)) >> 3)
+
+
+def tile_of_id(L, tiles, order):
+    """tile id t -> (tm, tn) under the dense (0) or the balanced (1) order, from the library's own hsk_env_tile_order (which answers per
+    block id of an unshifted front: undo its remap)"""
+    nt = tiles * tiles
+    tm, tn = np.empty(nt, dtype=np.int32), np.empty(nt, dtype=np.int32)
+    p32 = C.POINTER(C.c_int32)
+    assert L.hsk_env_tile_order(tiles, tiles, order, tm.ctypes.data_as(p32), tn.ctypes.data_as(p32)) == 0
+    t = xcd_remap_shift(np.arange(nt), nt, 0)
+    om, on = np.empty(nt, dtype=np.int64), np.empty(nt, dtype=np.int64)
+    om[t], on[t] = tm, tn
+    return om, on
+
+
+def schur_xcd_load(L, fronts, order):
+    """K-steps every XCD runs in the level-wide Schur launch SB -= LF[ni.., 0:ni) * UR of a batch (one workgroup per tile, grid.x = the tiles
+    of the largest front; the hardware deals workgroups to the XCDs round-robin over blockIdx.x + gridDim.x * blockIdx.y).  The fronts are
+    taken in tree order, which need not be the batch order of the library: the shifts of the single fronts are an estimate."""
+    gx = max(-(-nb // BM) ** 2 for _, nb, _, _ in fronts)
+    load = np.zeros(XCDS)
+    cache = {}
+    for y, (ni, nb, fL, fU) in enumerate(fronts):
+        tiles = -(-nb // BM)
+        if tiles == 0:
+            continue
+        nbi = (ni + G - 1) // G
+        pad = np.full(tiles * (BM // G) - (len(fL) - nbi), NONE)
+        rmin = np.concatenate([fL[nbi:], pad]).reshape(tiles, BM // G).min(axis=1)
+        cmin = np.concatenate([fU[nbi:], pad]).reshape(tiles, BM // G).min(axis=1)
+        steps = -(-np.maximum(ni - np.maximum(rmin[:, None], cmin[None, :]), 0) // BK)  # [tm, tn]
+        if tiles not in cache:
+            cache[tiles] = tile_of_id(L, tiles, order)
+        om, on = cache[tiles]
+        nt = tiles * tiles
+        shift = (gx * y) & 7 if gx & 7 else 0
+        bid = np.arange(nt)
+        t = xcd_remap_shift(bid, nt, shift)
+        load += np.bincount((bid + shift) & 7, weights=steps[om[t], on[t]].astype(np.float64), minlength=XCDS)
+    return load
+
+
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else "poisson3d_128"
     T = int(os.environ.get("T", "128")) // G
@@ -99,8 +158,9 @@ def main():
         ni1, nb1 = int(np.isin(it, lb).sum()), int(np.isin(bd, lb).sum())
         fL, fU = tables(L, colptr, rowval, n, np.concatenate([it, bd]), ni, ni1, nb1)
         nbi = (ni + G - 1) // G
-        r = lev.setdefault(lv, dict(fronts=0, ni=0, nb=0, dense=0.0, e32=0.0, eT=0.0))
+        r = lev.setdefault(lv, dict(fronts=0, ni=0, nb=0, dense=0.0, e32=0.0, eT=0.0, fr=[]))
         r["fronts"] += 1
+        r["fr"].append((ni, nb, fL, fU))
         r["ni"], r["nb"] = max(r["ni"], ni), max(r["nb"], nb)
         r["dense"] += 2.0 * front_macs(ni, nb, None, None)
         r["e32"] += 2.0 * front_macs(ni, nb, fL, fU)
@@ -115,6 +175,20 @@ def main():
         print("| %d | %d | %d, %d | %.4g | %.4g | %.3f | %.4g | %.3f |" % (lv, r["fronts"], r["ni"], r["nb"], r["dense"], r["e32"], r["e32"] / r["dense"],
                                                                      r["eT"], r["eT"] / r["dense"]))
     print("| all | | | %.4g | %.4g | %.3f | %.4g | %.3f |" % (tot[0], tot[1], tot[1] / tot[0], tot[2], tot[2] / tot[0]))
+    print()
+    print("# level-wide Schur launches: K-steps of the heaviest XCD over the mean, dense tile order (HS_ENV_ORDER=0) and balanced order (1);")
+    print("# K-steps run / dense = the share of the dense launch's K-steps that the clipped tiles run")
+    print("| level | fronts | tile rows (largest front) | K-steps run / dense | heaviest / mean, order 0 | order 1 |")
+    print("|---|---|---|---|---|---|")
+    for lv in sorted(lev):
+        fr = [f for f in lev[lv]["fr"] if f[1] > 0]
+        if not fr:
+            continue
+        l0, l1 = schur_xcd_load(L, fr, 0), schur_xcd_load(L, fr, 1)
+        dense = sum((-(-nb // BM)) ** 2 * -(-ni // BK) for ni, nb, _, _ in fr)
+        assert l0.sum() == l1.sum()
+        print("| %d | %d | %d | %.3f | %.3f | %.3f |" % (lv, len(fr), max(-(-nb // BM) for _, nb, _, _ in fr), l0.sum() / dense, l0.max() / l0.mean(),
+                                                    l1.max() / l1.mean()))
 
 
 if __name__ == "__main__":
