@@ -23,7 +23,7 @@ class hs_options(C.Structure):
     _fields_ = [
         ("swlevel", i64), ("swsize", i64), ("atol", C.c_double), ("rtol", C.c_double), ("c_tol", C.c_double),
         ("leafsize", i64), ("kest", i64), ("stepsize", i64), ("verbose", C.c_uint8),
-        ("keep_schur", C.c_uint8), ("profile", C.c_uint8), ("split", C.c_uint8), ("hss_d", C.c_uint8), ("hss_dexp", C.c_uint8), ("mf", C.c_uint8), ("dist_top", C.c_uint8), ("seed", i64),
+        ("keep_schur", C.c_uint8), ("profile", C.c_uint8), ("split", C.c_uint8), ("hss_d", C.c_uint8), ("hss_dexp", C.c_uint8), ("mf", C.c_uint8), ("dist_top", C.c_uint8), ("seed", i64), ("symmetric", C.c_uint8),
     ]
 
 
@@ -85,7 +85,7 @@ EXPORTS = [
     "hs_ldiv_sparse_d", "hs_ldiv_sparse_z", "hs_ldiv_sparse_dev_d", "hs_ldiv_sparse_dev_z", "hs_ldiv_sparse_plan", "hs_ldiv_sparse_info",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
-    "hs_logabsdet", "hs_selinv", "hs_selinv_info", "hs_selinv_lr", "hs_selinv_lr_info",
+    "hs_logabsdet", "hs_selinv", "hs_selinv_info", "hs_selinv_lr", "hs_selinv_lr_info", "hs_sym_info",
     "hs_interface_size", "hs_interface_indices", "hs_interface_matrix_d", "hs_interface_matrix_z", "hs_interface_info", "hsk_lu_product_d", "hsk_lu_product_z",
     "hs_interface_condense_d", "hs_interface_condense_z", "hs_interface_condense_dev_d", "hs_interface_condense_dev_z",
     "hs_interface_solve_d", "hs_interface_solve_z", "hs_interface_solve_dev_d", "hs_interface_solve_dev_z",
@@ -117,7 +117,7 @@ EXPORTS = [
     "hsk_env_order_enable", "hsk_env_tile_order",
     "hsk_gemm_op_d", "hsk_gemm_lds_enable", "hsk_gemm_lds_launches",
     "hsk_gemm_lds_edge_launches", "hsk_gemm_reg_launches", "hsk_gemm_lds_route", "hsk_gemm_schur_d",
-    "hsk_trsm_inv_d", "hsk_trsm_strip_enable", "hsk_trsm_strip_launches", "hsk_trsm_half_launches", "hsk_lookahead_runs",
+    "hsk_trsm_inv_d", "hsk_trsm_strip_enable", "hsk_trsm_strip_launches", "hsk_trsm_half_launches", "hsk_lookahead_runs", "hsk_front_batch_sym_d", "hsk_front_batch_sym_z",
     "hsk_qr_params", "hsk_qr_chol_d", "hsk_qr_chol_z", "hsk_qr_select", "hsk_qr_refine_d", "hsk_qr_refine_z",
 ]
 
@@ -417,6 +417,8 @@ def lib():
     L.hs_schur_unpack.restype = C.c_int
     L.hs_flow_info.argtypes = [vp, p_i64]
     L.hs_flow_info.restype = C.c_int
+    L.hs_sym_info.argtypes = [vp, p_i64]
+    L.hs_sym_info.restype = C.c_int
     L.hs_hss_qr_order.argtypes = [C.c_int]
     L.hs_hss_qr_order.restype = C.c_int
     L.hs_hss_pack_size.argtypes = [vp, p_i64]
@@ -527,7 +529,7 @@ def lib():
     for f in (L.hsk_front_factor_d, L.hsk_front_factor_z):
         f.argtypes = [i64, i64, i64, p_f64, p_f64, p_f64, p_f64, p_i64, p_i64, p_f64]
         f.restype = C.c_int
-    for f in (L.hsk_front_batch_d, L.hsk_front_batch_z):
+    for f in (L.hsk_front_batch_d, L.hsk_front_batch_z, L.hsk_front_batch_sym_d, L.hsk_front_batch_sym_z):
         f.argtypes = [i64, p_i64, p_i64, C.c_int, p_f64, p_f64, p_f64, p_f64, p_i64, p_i64, p_i64, p_f64, p_f64, p_f64, p_f64, p_f64]
         f.restype = C.c_int
     for f in (L.hsk_sweep_level_d, L.hsk_sweep_level_z):

@@ -185,6 +185,8 @@ struct LevelH {
   int nmf = 0;                             // the last nmf entries of `mine` are matrix-free fronts (hs_mffront.h): never assembled
   int dmaxni = 0, dmaxnb = 0, dmaxm = 0;   // extents of the dense batch
   bool aligned16 = true;                   // every front of the dense batch has LF / UR / SB 16-byte aligned and even ldl / ldu / lds (Sched::aligned16)
+  bool sym_ok = true;                      // every front of the dense batch is assembled from A and from Schur complements of densely eliminated children
+                                           // only: symmetric when A is (a compressed child's S is symmetric to its tolerance only).  Sched::sym
 };
 
 struct Exchange {
@@ -222,6 +224,8 @@ struct hs_handle {
   int* d_tmpi = nullptr;  // cand, pivlist, info[nnodes], own[n], pos[n]
   int* d_info = nullptr;
   int* d_growth = nullptr;
+  unsigned long long* d_symflag = nullptr;  // hs_options.symmetric: the first entry of A that differs from its transposed partner (sym_check_kernel)
+  int64_t sym_fronts = 0, sym_plain = 0;    // hs_sym_info: dense fronts of the last factorization eliminated on their lower triangle / as before
   bool optimistic = true;   // HS_OPTIMISTIC=0 turns it off; a level that had to be redone turns it off for the rest of the handle's life
   int* d_own = nullptr;
   int* d_pos = nullptr;
@@ -390,7 +394,7 @@ static void free_handle(hs_handle* h) {
   arena_give(h->d_cfs, h->cfs_bytes);
   void* ptrs[] = {h->d_int, h->d_tmpi, h->d_colptr, h->d_rowval, h->d_nz,
                   h->d_nodes, h->d_sc,  h->d_solve, h->d_w1,  h->d_w2,   h->d_part,   h->d_b,   h->d_owned,
-                  h->d_rowptr, h->d_colind, h->d_tperm, h->d_nzr, h->d_lpos, h->d_env};
+                  h->d_rowptr, h->d_colind, h->d_tperm, h->d_nzr, h->d_lpos, h->d_env, h->d_symflag};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -683,6 +687,8 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
   if (n <= 0 || (!plan_only && (!colptr || !rowval))) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: empty matrix");
   if (!plan_only && colptr[0] != 1) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: colptr must be 1-based (SparseMatrixCSC)");
   if (nranks < 1 || rank < 0 || rank >= nranks) HS_FAIL(HS_ERR_ARGUMENT, rank, "ArgumentError: rank %d of %d", rank, nranks);
+  if (opts.symmetric && nranks > 1)
+    HS_FAIL(HS_ERR_UNSUPPORTED, nranks, "hs_options.symmetric with %d ranks: single-rank factorizations only", nranks);
   if (!plan_only) require_device();
 
   hs_handle* h = new hs_handle();
@@ -795,6 +801,9 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
         L.h_ni.push_back(x.ni);
         L.h_nb.push_back(x.nb);
         if (!x.compressed && !x.hssd && !x.mf) {
+          for (int c : {x.left, x.right})
+            if (!x.leaf && c >= 0 && (N[c].compressed || N[c].hssd || N[c].mf || N[c].s_hss)) L.sym_ok = false;
+          if (x.kind != 0 || x.dist) L.sym_ok = false;
           L.ndense = (int)k + 1;
           L.dmaxni = std::max(L.dmaxni, x.ni);
           L.dmaxnb = std::max(L.dmaxnb, x.nb);
@@ -1011,6 +1020,7 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
     dmalloc((void**)&h->d_colptr, (n + 1) * sizeof(int64_t), "colptr");
     dmalloc((void**)&h->d_rowval, nnz * sizeof(int32_t), "rowval");
     dmalloc(&h->d_nz, nnz * sizeof(T), "nzval");
+    if (opts.symmetric) dmalloc((void**)&h->d_symflag, sizeof(unsigned long long), "symmetry flag");
     {
       std::vector<int64_t> cp(n + 1);
       for (int64_t j = 0; j <= n; ++j) {
@@ -1256,6 +1266,26 @@ static void numeric_begin(hs_handle* h, const void* nzval, int on_device) {
   free_mf_nodes<T>(h);
   free_lowrank_nodes<T>(h);
   HS_HIP(hipMemcpyAsync(h->d_nz, nzval, h->nnz * sizeof(T), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  h->sym_fronts = h->sym_plain = 0;
+  if (h->opts.symmetric) {
+    // the claim A == transpose(A) is checked on the stored entries before any front is touched
+    HS_HIP(hipMemsetAsync(h->d_symflag, 0xff, sizeof(unsigned long long), s));
+    launch_sym_check<T>(h->n, h->d_colptr, h->d_rowval, (const T*)h->d_nz, h->d_symflag, s);
+    unsigned long long first = 0;
+    HS_HIP(hipMemcpyAsync(&first, h->d_symflag, sizeof first, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
+    if (first != ~0ull) {
+      int32_t r = 0;
+      HS_HIP(hipMemcpy(&r, h->d_rowval + first, sizeof r, hipMemcpyDeviceToHost));
+      std::vector<int64_t> cp((size_t)h->n + 1);
+      HS_HIP(hipMemcpy(cp.data(), h->d_colptr, sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost));
+      const int64_t c = std::upper_bound(cp.begin(), cp.end(), (int64_t)first) - cp.begin() - 1;
+      HS_FAIL(HS_ERR_ARGUMENT, (int64_t)first,
+              "ArgumentError: hs_options.symmetric, but A is not equal to its transpose bit for bit: the entry at (row %lld, column %lld) has no equal "
+              "partner at (%lld, %lld) (1-based; Hermitian matrices are not served by this option)",
+              (long long)r + 1, (long long)c + 1, (long long)c + 1, (long long)r + 1);
+    }
+  }
   if (h->mf_on) launch_perm_gather<T>((const T*)h->d_nz, h->d_tperm, (T*)h->d_nzr, h->nnz, s);
   HS_HIP(hipMemsetAsync(h->d_own, 0xff, h->n * sizeof(int), s));
   h->prof = Profiler();
@@ -1333,6 +1363,7 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
       // every member of the group pivots the same way
       try_opt = dist_group_or(h->comm, h->d_gflags, dx->glo, dx->gcnt, h->rank, try_opt ? 0 : 1, sc) == 0 && L.ndense > 0;
     }
+    int sym_counted = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
     h->prof.tag = lv;
     hipEvent_t ea = h->prof.begin(s);
@@ -1367,6 +1398,12 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
         sch.env = true;
         sch.h_env = henv.data();
       }
+      sch.sym = h->opts.symmetric && sch.optimistic && !dx && L.sym_ok;
+      // hs_sym_info: what the last complete pass over the level did (a redone level counts as eliminated as before)
+      if (attempt == 1) h->sym_fronts -= sym_counted, h->sym_plain -= L.ndense - sym_counted;
+      sym_counted = sch.sym ? L.ndense : 0;
+      h->sym_fronts += sym_counted;
+      h->sym_plain += L.ndense - sym_counted;
       if (dx)
         factor_front_dist<T>(sch, DF);
       else
@@ -1387,6 +1424,7 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
       h->optimistic = false;
       if (h->opts.verbose) fprintf(stderr, "[hs] level %d: a pivot outside the diagonal block was needed; redoing the level with tournament pivoting\n", lv);
     }
+    h->sym_plain += (int64_t)L.mine.size() - L.ndense;  // compressed, HSS and matrix-free fronts keep their path whatever hs_options.symmetric says
     if (L.nplain > 0) factor_compressed_level<T>(h, L.mine.data() + L.ndense, L.nplain, dn + L.ndense, (const SolveNode<T>*)h->d_solve + L.desc_off + L.ndense, 2);  // hs_compress.h, steps B-F
     if (nb_ > L.ndense + L.nplain) factor_hss_fronts<T>(h, L.mine.data() + L.ndense + L.nplain, nb_ - L.ndense - L.nplain, dn + L.ndense + L.nplain);  // hs_hssfront.h
     {  // F2: a flagged front eliminated densely (a leaf) still hands its S on as an HSS matrix (factorization.jl:45-59)
@@ -2284,6 +2322,12 @@ extern "C" int hs_flow_info(const hs_handle* h, int64_t* out8) {
              out8[1] += x.mf ? 1 : 0; out8[2] += x.s_hss ? 1 : 0; out8[3] += (x.compressed && !x.leaf) ? 1 : 0; out8[4] += x.hssd ? 1 : 0; out8[5] += x.dist ? 1 : 0;
              out8[7] += x.kind != 0 ? 1 : 0;
            });
+}
+// out4 = {hs_options.symmetric, dense fronts of the last factorization eliminated on their lower triangle (Sched::sym), fronts eliminated as
+//         before -- dense ones of a tournament-pivoted or redone level, of a level fed by compressed children, and the compressed, HSS and matrix-free ones --, 0}
+extern "C" int hs_sym_info(const hs_handle* h, int64_t* out4) {
+  HS_GUARD(check_handle(h); if (!out4) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: out4 == NULL");
+           out4[0] = h->opts.symmetric ? 1 : 0; out4[1] = h->sym_fronts; out4[2] = h->sym_plain; out4[3] = 0;);
 }
 extern "C" int64_t hs_node_owner(const hs_handle* h, int64_t node) {
   if (!h || node < 0 || node >= h->nnodes) return -1;

@@ -260,6 +260,18 @@ template <class T>
 bool launch_group256(const NodeDesc<T>* dnodes, int nbatch, int grp, hipStream_t s);  // the panel chain of the 256 x 256 diagonal block of group `grp` in one launch (Float64; false: not available)
 template <class T>
 void launch_laswp(const NodeDesc<T>* dnodes, int nbatch, int mat, int c0, int c1, int k0, int k1, int maxcols, hipStream_t s);
+// Symmetric fronts (Sched::sym, kernels_sym.hip).  Column strips of the lower-triangle updates start at multiples of HS_SYM_STRIP and are a
+// multiple of it wide (Sched::sym_strip).
+#define HS_SYM_STRIP 256
+// mat[c0:c1, r0:r1) <- transpose(mat[r0:r1, c0:c1)) for every front of the batch, inside the square part of `mat` (LF: the interior block, SB: all of
+// it), each front clipping the ranges to its own ni / nb.  lower = 1: [r0, r1) == [c0, c1), the strictly upper triangle of that diagonal square is
+// rebuilt from the strictly lower one.  Plain transpose (never conjugating).  maxrows / maxcols: the largest clipped source extents of the batch.
+template <class T>
+void launch_sym_transpose(const NodeDesc<T>* dnodes, int nbatch, int mat, int r0, int r1, int c0, int c1, int lower, int maxrows, int maxcols, hipStream_t s);
+// hs_options.symmetric: compares every stored entry of the CSC matrix with its transposed partner, bit for bit (an entry without a partner is a
+// mismatch); *first (device, preset to all ones) receives the smallest offending entry index
+template <class T>
+void launch_sym_check(int64_t n, const int64_t* colptr, const int32_t* rowval, const T* nz, unsigned long long* first, hipStream_t s);
 
 template <class T>
 void launch_init_fronts(const NodeDesc<T>* dnodes, int nbatch, int maxni, hipStream_t s);  // rperm = 0:ni-1, info = 0

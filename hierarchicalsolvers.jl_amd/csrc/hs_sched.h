@@ -99,6 +99,9 @@ struct Sched {
   bool env = false;                  // leaf fronts of the batch are eliminated inside their block envelope (NodeDesc::env, hs_envelope.h).  Only with
                                      // `optimistic`: the tournament swaps rows across 32-blocks, which breaks the row envelope
   const int* const* h_env = nullptr; // the same tables on the host, one pointer per front (null: dense), for the flop / byte accounting
+  bool sym = false;                  // every front of the batch is symmetric (A == transpose(A), hs_options.symmetric): trailing updates of 256 columns or
+                                     // more run on lower strips (sym_strip: multiples of HS_SYM_STRIP columns), the upper blocks follow by transposition (sym_on).  Only with
+                                     // `optimistic`, like `env`: the tournament swaps rows across 32-blocks and the trailing matrix stops being symmetric
   bool aligned16 = false;            // LF, UR and SB of every front are 16-byte aligned and ldl, ldu, lds even (needs h_ni / h_nb): plain updates then
                                      // run the direct-to-LDS kernel all their fronts allow (hs_gemm_lds_route; Float64)
 
@@ -252,6 +255,49 @@ struct Sched {
     launch_laswp<T>(dn, nbatch, mat, c0, c1, k0, k1, nc, s);
     pf->end(e0, HS_CAT_LASWP, s, 0.0, 0, 0, 0, nbatch, 0, hiprio);
     dbg("laswp", mat, c0, k0, k1);
+  }
+  // ---- symmetric fronts (Sched::sym) --------------------------------------------------------------------------------------------------------
+  // Invariant: when a column range [c0, c1) is about to be factored its diagonal square is whole (both triangles) and the rows below it are
+  // up to date; the blocks of the trailing interior strictly above the diagonal are never read as matrix entries, only written as U.
+  // Under optimistic pivoting every row swap stays inside a 32-row diagonal block and the update a block column k applies to the blocks
+  // right of and below it is A_ik A_kk^-1 A_kj whatever P_k is, so the trailing matrix stays symmetric and its upper blocks are the
+  // transposes of the lower ones.
+  bool sym_on() const { return sym && optimistic && rlim == HS_BIG; }
+  // Strip width of a lower-triangle update of `extent` columns whose launches span `tiles_m` tile rows over the batch: a multiple of
+  // HS_SYM_STRIP.  Narrow strips waste least above their diagonals (n strips execute (1 + 1/n) / 2 of the square), but every strip is a launch
+  // of its own and a launch of a few tiles leaves most of the chip idle.  So: at most 16 strips (1/32 above the ideal half), widened until a
+  // launch carries about two rounds of workgroups (1024 tiles), but never to fewer than 4 strips (5/8 of the square).  bn: tile columns.
+  static int sym_strip(int extent, long long tiles_m, int bn) {
+    const int lo = HS_SYM_STRIP * std::max(1, (extent + 16 * HS_SYM_STRIP - 1) / (16 * HS_SYM_STRIP));
+    const int hi = std::max(lo, extent / 4 / HS_SYM_STRIP * HS_SYM_STRIP);
+    const long long units = (1024LL * bn + HS_SYM_STRIP * std::max(1LL, tiles_m) - 1) / (HS_SYM_STRIP * std::max(1LL, tiles_m));
+    return (int)std::min<long long>(hi, std::max<long long>(lo, HS_SYM_STRIP * units));
+  }
+  // C[c0.., c0:c1) -= A B on lower strips: one update per strip of sym_strip columns, rows from the strip's own first column on -- its
+  // diagonal block whole, everything below in full.  C is LF (interior columns, rows down to the end of the front) or SB.  Returns false
+  // when one strip covers the range: that is the full update, nothing above a diagonal block was left behind.
+  bool gemm_lower(int cmat, int bmat, int c0, int c1, int k0, int k1, int cap = 0) {
+    c1 = std::min(c1, cols_of(cmat));
+    if (c1 <= c0) return false;
+    long long tiles_m = 0;
+    for (int i = 0; i < nbatch; ++i) {
+      const int rows = !h_ni ? rows_of(cmat) : (cmat == HS_MAT_LF ? h_ni[i] + h_nb[i] : h_nb[i]);
+      tiles_m += std::max(0, rows - c0 + 127) / 128;
+    }
+    const int W = sym_strip(c1 - c0, tiles_m, sizeof(T) == 16 ? 64 : 128);
+    for (int j0 = c0; j0 < c1; j0 += W) gemm(cmat, bmat, j0, HS_BIG, j0, std::min(c1, j0 + W), k0, k1, cap);
+    return c1 - c0 > W;
+  }
+  // mat[c0:c1, r0:r1) <- transpose(mat[r0:r1, c0:c1)) inside the square part of LF (the interior) or SB; with `lower` the range is a diagonal
+  // square [r0, r1)^2 whose strictly upper triangle is rebuilt from the strictly lower one.  Plain transpose, never conjugating.
+  void transpose(int mat, int r0, int r1, int c0, int c1, bool lower) {
+    const int lim = mat == HS_MAT_LF ? maxni : maxnb;
+    const int nr = std::min(r1, lim) - r0, nc = std::min(c1, lim) - c0;
+    if (nr <= 0 || nc <= 0) return;
+    hipEvent_t e0 = pf->begin(s);
+    launch_sym_transpose<T>(dn, nbatch, mat, r0, r1, c0, c1, lower ? 1 : 0, nr, nc, s);
+    pf->end(e0, HS_CAT_LASWP, s, 0.0, 0, 0, 0, nbatch, 0, hiprio);
+    dbg("sym_transpose", mat, r0, c0, lower);
   }
   // The bytes an in-place product must move at least, over the fronts of the batch (profiled runs only: the HS_LAUNCH_LOG line of the launch).
   // The inverse block covers [blk0, blk0 + blkw) of the interior, clipped to ni; of that extent the launch reads [0, rd_hi) and writes
@@ -430,7 +476,11 @@ struct Sched {
     if (mid < maxni) {
       laswp(HS_MAT_LF, mid, c1, c0, mid);
       trsm_rec(HS_MAT_LF, c0, mid, mid, c1);
-      gemm(HS_MAT_LF, HS_MAT_LF, mid, rlim, mid, c1, c0, mid);
+      if (sym_on() && c1 - mid >= 256) {
+        if (gemm_lower(HS_MAT_LF, HS_MAT_LF, mid, c1, c0, mid)) transpose(HS_MAT_LF, mid, c1, mid, c1, true);  // lu_rec(mid, c1) finds its diagonal square whole
+      } else {
+        gemm(HS_MAT_LF, HS_MAT_LF, mid, rlim, mid, c1, c0, mid);
+      }
       lu_rec(mid, c1);
       laswp(HS_MAT_LF, c0, mid, mid, c1);
     }
@@ -492,13 +542,22 @@ struct Sched {
         mn.laswp(HS_MAT_LF, c1, c2, c0, c1);
         mn.trsm_rec(HS_MAT_LF, c0, c1, c1, c2);
         mn.gemm(HS_MAT_LF, HS_MAT_LF, c1, HS_BIG, c1, c2, c0, c1);
+        if (mn.sym_on()) {
+          // the strips of the earlier trailing updates left the blocks above the strip diagonals inside [c1, c2)^2 behind: rebuild them, then
+          // write the future U row block [c1, c2) x [c2, ni) -- up to date with respect to everything left of c1 -- from the column block
+          mn.transpose(HS_MAT_LF, c1, c2, c1, c2, true);
+          mn.transpose(HS_MAT_LF, c2, HS_BIG, c1, c2, false);
+        }
         (void)hipEventRecord(ev_main, mn.s);
         (void)hipStreamWaitEvent(s2, ev_main, 0);
         side.lu_rec(c1, c2);
         (void)hipEventRecord(ev_side, s2);
         mn.laswp(HS_MAT_LF, c2, HS_BIG, c0, c1);
         mn.trsm_rec(HS_MAT_LF, c0, c1, c2, HS_BIG);
-        mn.gemm(HS_MAT_LF, HS_MAT_LF, c1, HS_BIG, c2, HS_BIG, c0, c1, has_next ? gcap : 0);
+        if (mn.sym_on())  // each strip from its own first row: rows [c1, c2) of the columns right of c2 were written by the transposition above
+          mn.gemm_lower(HS_MAT_LF, HS_MAT_LF, c2, HS_BIG, c0, c1, has_next ? gcap : 0);
+        else
+          mn.gemm(HS_MAT_LF, HS_MAT_LF, c1, HS_BIG, c2, HS_BIG, c0, c1, has_next ? gcap : 0);
       }
       if (maxnb > 0) {
         mn.laswp(HS_MAT_UR, 0, HS_BIG, c0, c1);
@@ -514,7 +573,7 @@ struct Sched {
       (void)hipEventRecord(ev_main, s_la);
       (void)hipStreamWaitEvent(s, ev_main, 0);
     }
-    if (maxnb > 0) gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG);
+    if (maxnb > 0) schur_update();
     (void)hipEventDestroy(ev_main);
     (void)hipEventDestroy(ev_side);
   }
@@ -538,6 +597,15 @@ struct Sched {
     if (maxnb > 0) {
       laswp(HS_MAT_UR, 0, HS_BIG, 0, P2);
       trsm_rec(HS_MAT_UR, 0, P2, 0, HS_BIG);
+      schur_update();
+    }
+  }
+  // S = Abb - Lbi Uib.  Symmetric fronts: lower strips, then one mirror -- the Schur complement leaves the front whole
+  void schur_update() {
+    if (sym_on()) {
+      gemm_lower(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG);
+      transpose(HS_MAT_SB, 0, HS_BIG, 0, HS_BIG, true);
+    } else {
       gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG);
     }
   }

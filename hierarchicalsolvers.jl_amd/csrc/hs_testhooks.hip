@@ -403,7 +403,7 @@ struct FrontBatch {
   void upload_solve() { HS_HIP(hipMemcpy(dsn, hs.data(), sizeof(SolveNode<T>) * count, hipMemcpyHostToDevice)); }
   void set_env(const int32_t* env);
   int aligned16_status() const;
-  void factor(int mode, double* ms_out);
+  void factor(int mode, double* ms_out, bool sym = false);
   void copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U);
 };
 
@@ -513,7 +513,7 @@ int FrontBatch<T>::aligned16_status() const {
 
 // mode & 3: the pivoting and the descriptors (hsk_front_batch_*); mode & 4: Sched::aligned16, the routing of the plain updates hs_numeric runs with
 template <class T>
-void FrontBatch<T>::factor(int mode, double* ms_out) {
+void FrontBatch<T>::factor(int mode, double* ms_out, bool sym) {
   const bool aligned = (mode & 4) != 0;
   mode &= 3;
   if (aligned) HS_CHECK(aligned16_status());
@@ -535,6 +535,7 @@ void FrontBatch<T>::factor(int mode, double* ms_out) {
   if (mode >= 2) sch.sn = dsn;
   sch.optimistic = (mode == 1 || mode == 2);
   sch.aligned16 = aligned;
+  sch.sym = sym && sch.optimistic;  // (hsk_front_batch_sym_*: the caller vouches that every front equals its transpose)
   if (sch.optimistic && !h_env.empty()) {
     sch.env = true;
     sch.h_env = h_env.data();
@@ -581,8 +582,10 @@ void FrontBatch<T>::copy_out(T* outLF, T* outUR, T* outSB, int64_t* out_rperm, i
 template <class T>
 static void front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* nb_, int mode, const T* F, T* outLF, T* outUR, T* outSB,
                              int64_t* out_rperm, int64_t* info, int64_t* growth, T* outInvL, T* outInvU, T* outInv256L, T* outInv256U,
-                             double* ms_out, const int32_t* env = nullptr) {
-  FrontBatch<T>::check("hsk_front_batch", count, ni_, nb_, F, mode, 0, 7);
+                             double* ms_out, const int32_t* env = nullptr, bool sym = false) {
+  FrontBatch<T>::check(sym ? "hsk_front_batch_sym" : "hsk_front_batch", count, ni_, nb_, F, mode, 0, 7);
+  if (sym && mode != 1 && mode != 2 && mode != (2 | 4))
+    HS_FAIL(HS_ERR_ARGUMENT, mode, "hsk_front_batch_sym: the symmetric schedule runs under optimistic pivoting only (modes 1, 2 and 2 | 4)");
   if (env && (mode & 3) != 1 && (mode & 3) != 2) HS_FAIL(HS_ERR_ARGUMENT, mode, "hsk_front_batch_env: block envelopes hold under optimistic pivoting only (modes 1, 2)");
   if ((outInvL || outInvU || outInv256L || outInv256U) && (mode & 3) < 2)
     HS_FAIL(HS_ERR_ARGUMENT, mode, "hsk_front_batch: the stored inverses are returned by modes 2 and 3 only");
@@ -590,7 +593,7 @@ static void front_batch_hook(int64_t count, const int64_t* ni_, const int64_t* n
   fb.setup(count, ni_, nb_, F);
   if (env) fb.set_env(env);
   fb.upload_solve();
-  fb.factor(mode, ms_out);
+  fb.factor(mode, ms_out, sym);
   fb.copy_out(outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U);
 }
 
@@ -746,6 +749,19 @@ extern "C" int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t
                                  double* outInv256L, double* outInv256U, double* ms_out) {
   HS_GUARD(front_batch_hook<cplx>(count, ni, nb, mode, (const cplx*)F, (cplx*)outLF, (cplx*)outUR, (cplx*)outSB, out_rperm, info, growth,
                                   (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, ms_out));
+}
+// hsk_front_batch_{d,z} with Sched::sym = true: every front must equal its transpose (plain, not conjugated); modes 1, 2 and 2 | 4 only.
+extern "C" int hsk_front_batch_sym_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
+                                     double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
+                                     double* outInv256L, double* outInv256U, double* ms_out) {
+  HS_GUARD(front_batch_hook<double>(count, ni, nb, mode, F, outLF, outUR, outSB, out_rperm, info, growth, outInvL, outInvU, outInv256L, outInv256U, ms_out,
+                                    nullptr, true));
+}
+extern "C" int hsk_front_batch_sym_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
+                                     double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
+                                     double* outInv256L, double* outInv256U, double* ms_out) {
+  HS_GUARD(front_batch_hook<cplx>(count, ni, nb, mode, (const cplx*)F, (cplx*)outLF, (cplx*)outUR, (cplx*)outSB, out_rperm, info, growth,
+                                  (cplx*)outInvL, (cplx*)outInvU, (cplx*)outInv256L, (cplx*)outInv256U, ms_out, nullptr, true));
 }
 
 // Batches Sched::factor_fronts has sent to factor_fronts_lookahead since the last reset (process-wide, host only): one note per batch.

@@ -35,7 +35,7 @@ from . import _lib
 from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
-           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info", "selinv_lr", "selinv_lr_diag", "selinv_lr_info",
+           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info", "selinv_lr", "selinv_lr_diag", "selinv_lr_info", "sym_info",
            "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "tangent", "gn_hessvec", "gn_diag", "gn_info", "eigs", "eigs_info", "eigs_gen_info", "interface_indices", "schur_complement", "condense", "interface_solve", "expand", "interface_info"]
 
 
@@ -44,7 +44,7 @@ class SolverOptions:
     ``5, 1, 1e-6, 1e-6, 0.5, 32, -1, 10, false`` (HierarchicalSolvers.jl:43-54)."""
 
     _fields = ("swlevel", "swsize", "atol", "rtol", "c_tol", "leafsize", "kest", "stepsize", "verbose")
-    _ext = ("keep_schur", "seed", "profile", "split_size", "hss_min", "hss_dexp", "mf", "dist_top")
+    _ext = ("keep_schur", "seed", "profile", "split_size", "hss_min", "hss_dexp", "mf", "dist_top", "symmetric")
 
     def __init__(self, **kw):
         self.swlevel, self.swsize = 5, 1
@@ -62,6 +62,9 @@ class SolverOptions:
         self.mf = False
         # multi-rank factorizations: fronts above the rank cut are eliminated by all ranks of their group (csrc/hs_dist.h) instead of its first rank
         self.dist_top = False
+        # A == A.T entry for entry (real symmetric or COMPLEX symmetric; not Hermitian): dense fronts update only their lower triangle.  Checked on
+        # the device by hs_numeric_begin (ValueError naming the first offending entry); sym_info(F) reports what the factorization did with it
+        self.symmetric = False
         self._set(kw)
 
     def _set(self, kw):
@@ -106,6 +109,7 @@ class SolverOptions:
         else:
             raise ValueError("mf must be False, True / 'dense', 2 / 'hss' or 3 / 'block'")
         o.dist_top = 1 if self.dist_top else 0
+        o.symmetric = 1 if self.symmetric else 0
         if self.hss_dexp is not None:
             if not 0 <= int(self.hss_dexp) <= 12:
                 raise ValueError("hss_dexp must be in 0:12")
@@ -1489,6 +1493,15 @@ def _selinv_call(entry, name, F, diag, pattern, budget):
 def selinv_diag(F, budget=0):
     """``diag(A^-1)`` (marginal variances of a GMRF with precision ``A``, the diagonal of a Green's function) by :func:`selinv`."""
     return selinv(F, diag=True, pattern=False, budget=budget)[0]
+
+
+def sym_info(F):
+    """What ``SolverOptions.symmetric`` did in the last factorization of ``F`` (``hs_sym_info``): ``option`` (in effect), ``fronts_lower`` (dense
+    fronts eliminated on their lower triangle) and ``fronts_general`` (fronts eliminated as without the option: dense fronts of a tournament-pivoted
+    or redone level or with compressed children, and the compressed, HSS and matrix-free fronts)."""
+    out = np.zeros(4, dtype=np.int64)
+    _lib.check(_lib.lib().hs_sym_info(F._h, _p64(out)))
+    return dict(option=bool(out[0]), fronts_lower=int(out[1]), fronts_general=int(out[2]))
 
 
 def selinv_info(F):

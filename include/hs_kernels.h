@@ -58,6 +58,14 @@ int hsk_front_batch_z(int64_t count, const int64_t* ni, const int64_t* nb, int m
  * of F outside them is zero.  The batch then runs as hs_numeric runs a level whose fronts carry tables (Sched::env).  env == NULL: dense. */
 int hsk_front_batch_env_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, const int32_t* env, double* outLF,
                           double* outUR, double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth);
+/* hsk_front_batch_{d,z} with the symmetric schedule (Sched::sym, hs_options.symmetric): the caller vouches that every front equals its plain
+ * transpose.  Same arguments and outputs; modes 1, 2 and 2 | 4 only (the schedule needs optimistic pivoting), any other mode: HS_ERR_ARGUMENT. */
+int hsk_front_batch_sym_d(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
+                          double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
+                          double* outInv256L, double* outInv256U, double* ms_out);
+int hsk_front_batch_sym_z(int64_t count, const int64_t* ni, const int64_t* nb, int mode, const double* F, double* outLF, double* outUR,
+                          double* outSB, int64_t* out_rperm, int64_t* info, int64_t* growth, double* outInvL, double* outInvU,
+                          double* outInv256L, double* outInv256U, double* ms_out);
 
 /* One tree level of ldiv!: the batch of hsk_front_batch_* (same packing of ni, nb, F), factored in mode 2 or 3 so that the stored inverses are
  * the production ones, then the level's forward and backward sweeps on the global vector b (length n), through the per-level driver that

@@ -93,6 +93,15 @@ typedef struct hs_options {
                          factors and Schur complement, sibling groups swap Schur complements pairwise at the join.  Needs a communicator
                          (hs_set_comm).  Fronts above the cut are eliminated exactly in this mode (no compression there). */
   int64_t seed;       /* RNG seed of the randomized compression (reference: Random.seed!(123), test/rungmres.jl:7) */
+  uint8_t symmetric;  /* 1: the caller states A == transpose(A), entry for entry and bit for bit: real symmetric and COMPLEX SYMMETRIC matrices
+                         (plain transpose).  Hermitian matrices are not served by this option (A != transpose(A) unless real).  The fronts a level
+                         eliminates densely then update only the lower triangle of their trailing blocks and of the Schur complement, in column
+                         strips (multiples of 256 wide), and rebuild the upper blocks by transposition: same pivots, the same P, L, U, Lbi, Uib, S up
+                         to rounding, in the same layout -- every solve-phase entry point works on such a handle unchanged.  Compressed, HSS and
+                         matrix-free fronts, dense fronts fed by compressed children, tournament-pivoted and redone levels keep the general
+                         path (hs_sym_info reports the counts).  hs_numeric_begin checks the claim on the device and returns HS_ERR_ARGUMENT
+                         naming the first offending (row, column) before any front is touched; with nranks > 1 hs_analyze / hs_plan return
+                         HS_ERR_UNSUPPORTED.  Appended after `seed`: the offsets of the older fields do not move.  Default 0. */
 } hs_options;
 
 /* Defaults of the reference's kw-constructor (HierarchicalSolvers.jl:43-54): 5,1,1e-6,1e-6,0.5,32,-1,10,false */
@@ -721,6 +730,10 @@ int hs_schur_unpack(hs_handle* F, int64_t node, const void* dev_buf, int64_t byt
 /* What a factorization does with its options on THIS rank: out8 = {hs_options.mf in effect (0 = the dense-S flow), matrix-free fronts, fronts whose S
  * leaves as an HSS matrix, fronts with low-rank L / R, fronts with an HSS D (hss_d), group fronts (dist_top), ranks, fronts eliminated in slices}. */
 int hs_flow_info(const hs_handle* F, int64_t* out8);
+/* What hs_options.symmetric did: out4 = {the option in effect, dense fronts of the last factorization eliminated on their lower triangle,
+ * fronts eliminated as before (dense ones of a tournament-pivoted or redone level or with compressed children; compressed, HSS and matrix-free
+ * fronts), 0}.  Counts are of the last hs_numeric_begin .. hs_numeric_end on this rank. */
+int hs_sym_info(const hs_handle* F, int64_t* out4);
 /* make `dptr` (device memory owned by the caller, hs_exchange_info's element count) the node's Schur buffer */
 int hs_set_schur_buffer(hs_handle* F, int64_t node, void* dptr);
 int hs_pack_bnd(const hs_handle* F, int64_t node, const void* d_b, void* d_buf, void* stream);   /* buf[j] = b[bnd_j] */
