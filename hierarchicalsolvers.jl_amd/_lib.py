@@ -114,7 +114,7 @@ EXPORTS = [
     "hsk_gemm_d", "hsk_gemm_z", "hsk_lowrank_d", "hsk_lowrank_z", "hsk_front_factor_d", "hsk_front_factor_z", "hsk_front_batch_d", "hsk_front_batch_z", "hsk_sweep_level_d", "hsk_sweep_level_z", "hsk_flow_tall_rule", "hsk_sweep_path", "hsk_mfma_f64_peak", "hsk_mfma_f64_peak_random", "hsk_flow_pingpong_us", "hsk_bisect_perm",
     "hs_probs_stats_mode", "hs_probs_stats", "hs_trim", "hs_stream_order",
     "hsk_leaf_envelope", "hsk_envelope_enable", "hsk_branch_envelope", "hsk_branch_envelope_enable", "hsk_front_batch_env_d", "hsk_op_flops_mode", "hsk_op_flops",
-    "hsk_env_order_enable", "hsk_env_tile_order",
+    "hsk_env_order_enable", "hsk_env_tile_order", "hsk_env_phase_order", "hsk_env_perm", "hsk_env_perm_slot_limit", "hsk_env_perm_min_tiles", "hsk_env_perm_launches",
     "hsk_gemm_op_d", "hsk_gemm_lds_enable", "hsk_gemm_lds_launches",
     "hsk_gemm_lds_edge_launches", "hsk_gemm_reg_launches", "hsk_gemm_lds_route", "hsk_gemm_schur_d",
     "hsk_trsm_inv_d", "hsk_trsm_strip_enable", "hsk_trsm_strip_launches", "hsk_trsm_half_launches", "hsk_lookahead_runs", "hsk_front_batch_sym_d", "hsk_front_batch_sym_z",
@@ -642,6 +642,16 @@ def lib():
     L.hsk_env_order_enable.restype = C.c_int
     L.hsk_env_tile_order.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.hsk_env_tile_order.restype = C.c_int
+    L.hsk_env_phase_order.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int] + [C.POINTER(C.c_int32)] * 3
+    L.hsk_env_phase_order.restype = C.c_int
+    L.hsk_env_perm.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_int32)] + [C.c_int] * 10 + [C.POINTER(C.c_uint16)]
+    L.hsk_env_perm.restype = C.c_int
+    L.hsk_env_perm_slot_limit.argtypes = [C.c_int]
+    L.hsk_env_perm_slot_limit.restype = C.c_int
+    L.hsk_env_perm_min_tiles.argtypes = [C.c_int]
+    L.hsk_env_perm_min_tiles.restype = C.c_int
+    L.hsk_env_perm_launches.argtypes = [C.c_int]
+    L.hsk_env_perm_launches.restype = C.c_longlong
     L.hsk_op_flops_mode.argtypes = [C.c_int]
     L.hsk_op_flops_mode.restype = C.c_int
     L.hsk_op_flops.argtypes = [p_f64]

@@ -246,6 +246,10 @@ struct hs_handle {
   void* d_sc = nullptr;     // ScatterDesc<T>[]
   void* d_solve = nullptr;  // SolveNode<T>[] (same order as d_nodes)
   int* d_env = nullptr;     // block envelopes of the leaf and branch fronts (NodeDesc::env), built once per pattern
+  // scratch of the K-sorted tile order of the enveloped updates (Sched::perm / perm_side): two areas of perm_cap uint16 each, one per stream that
+  // issues them, sized for the level that needs most
+  uint16_t* d_perm = nullptr;
+  size_t perm_cap = 0;
   std::vector<int> env_host;
   // NodeDesc::env of every descriptor (d_nodes order) with the branch fronts' tables and without them, and which of the two the device holds:
   // hs_numeric_levels rewrites the field when the branch switch (hs_branch_envelope_enabled) has changed since.  Empty: no branch front has a table
@@ -394,7 +398,7 @@ static void free_handle(hs_handle* h) {
   arena_give(h->d_cfs, h->cfs_bytes);
   void* ptrs[] = {h->d_int, h->d_tmpi, h->d_colptr, h->d_rowval, h->d_nz,
                   h->d_nodes, h->d_sc,  h->d_solve, h->d_w1,  h->d_w2,   h->d_part,   h->d_b,   h->d_owned,
-                  h->d_rowptr, h->d_colind, h->d_tperm, h->d_nzr, h->d_lpos, h->d_env, h->d_symflag};
+                  h->d_rowptr, h->d_colind, h->d_tperm, h->d_nzr, h->d_lpos, h->d_env, h->d_symflag, h->d_perm};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1123,6 +1127,15 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
             if (any_leaf) L.h_env_leaf.push_back(x.off_env >= 0 && x.leaf ? h->env_host.data() + x.off_env : nullptr);
           }
         }
+        // the tables of the K-sorted tile order: one slot per front of a level's dense batch, for the main and for the look-ahead side stream.
+        // Float64 only (the order runs on the direct-to-LDS tile), and only the levels whose fronts can reach its lower tile limit
+        for (const LevelH& L : h->levels) {
+          int maxm = 0;
+          for (int k = 0; k < L.ndense; ++k) maxm = std::max(maxm, N[L.mine[k]].ni + N[L.mine[k]].nb);
+          if (sizeof(T) == 8 && L.ndense > 0 && hs_env_perm_wanted(maxm))
+            h->perm_cap = std::max(h->perm_cap, (size_t)L.ndense * hs_env_perm_stride(hs_env_perm_slot(maxm)));
+        }
+        if (h->perm_cap) dmalloc((void**)&h->d_perm, 2 * h->perm_cap * sizeof(uint16_t), "tile order tables");
       }
     }
 
@@ -1397,6 +1410,9 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
       if (sch.optimistic && !dx && !henv.empty() && hs_envelope_enabled()) {
         sch.env = true;
         sch.h_env = henv.data();
+        sch.perm = h->d_perm;
+        sch.perm_side = h->d_perm ? h->d_perm + h->perm_cap : nullptr;
+        sch.perm_cap = h->perm_cap;
       }
       sch.sym = h->opts.symmetric && sch.optimistic && !dx && L.sym_ok;
       // hs_sym_info: what the last complete pass over the level did (a redone level counts as eliminated as before)

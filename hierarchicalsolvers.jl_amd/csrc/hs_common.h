@@ -158,8 +158,20 @@ struct GemmOp {
   int count;       // 1: the launch goes to gemm_op_env_kernel, which adds the flops of the K-steps it runs to a device counter (hsk_op_flops; set by
                    // launch_gemm_op while the hook is on)
   int order;       // 1: an enveloped plain update deals its tiles to the XCDs in the balanced order (env_order_stride, kernels_gemm.hip; set by
-                   // launch_gemm_op unless HS_ENV_ORDER=0 / hsk_env_order_enable(0)); 0: the order of the dense launches
+                   // launch_gemm_op unless HS_ENV_ORDER=0 / hsk_env_order_enable(0)); 0: the order of the dense launches;
+                   // 2: the K-sorted order (env_phase_*, kernels_gemm.hip), through the tables of `perm`
+  int perm_slot;   // order 2: tile rows / columns a front's tables hold (hs_env_perm_stride entries per front)
+  uint16_t* perm;  // order 2: the launch's permutation tables, one slot per front of the batch, written by env_perm_kernel in front of the update
 };
+// Scratch of the K-sorted order, per front (uint16 units): [0] 1 = tables valid (0: the front has more tile rows or columns than the slot holds
+// and runs the balanced order), [1] unused, then the table block id -> (tile row, tile column) the update reads, slot^2 pairs, and behind it
+// what it was made from: rowperm[slot], colperm[slot] and unitperm[(slot / 8)^2].  `slot` is a multiple of 8.
+#define HS_ENV_PERM_MAX 512
+#define HS_ENV_PERM_MIN_TILES 2048  // default of the lower limit: fronts with fewer tiles keep the balanced order (hs_env_perm_min_tiles, kernels_gemm.hip)
+__host__ __device__ inline int hs_env_perm_stride(int slot) { return (2 + 2 * slot * slot + 2 * slot + (slot >> 3) * (slot >> 3) + 1) & ~1; }  // (even: the table is read as words)
+// tile rows / columns of the largest launch of a batch whose fronts have at most maxm rows (128 x 128 Float64 tiles; + 1: the shifted edge tile)
+int hs_env_perm_slot(int maxm);
+bool hs_env_perm_wanted(int maxm);  // a front of maxm rows can have the tiles the lower limit asks for
 
 // Block envelope of a leaf front (hs_envelope.h): the smallest entry of `first` over the 32-blocks that meet the front positions [lo, hi).
 // Interior positions (< ni) are block p / 32, boundary positions block nI + (p - ni) / 32 with nI = ceil(ni / 32): consecutive in the table.
@@ -211,7 +223,8 @@ __device__ inline void mat_of(const NodeDesc<T>* pn, int which, T*& p, int& ld, 
 enum { HS_GEMM_ROUTE_REG = 0, HS_GEMM_ROUTE_LDS = 1, HS_GEMM_ROUTE_EDGE = 2 };
 template <class T>
 void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op, hipStream_t s, int route = HS_GEMM_ROUTE_REG,
-                    bool shifted = false, long long live_tiles = -1);  // live_tiles: tiles of an enveloped launch that run (-1: not counted)
+                    bool shifted = false, long long live_tiles = -1,  // live_tiles: tiles of an enveloped launch that run (-1: not counted)
+                    uint16_t* perm = nullptr, int perm_slot = 0);      // perm: this stream's scratch for the K-sorted order, nbatch slots (null: no order 2)
 // Which kernel may run the plain update (cmat, r0, k0, k1) of a front with ni interior DOFs?  The direct-to-LDS load moves 16 bytes per
 // lane and is given 16-byte aligned sources only.  With LF / UR / SB 16-byte aligned and even leading dimensions (the caller's premise:
 // Sched::aligned16) B = B0 + k0 + c0 ldb is aligned when k0 is even, and A = LF + r0 (+ ni when C is SB) + k0 ldl when its row offset is even.

@@ -146,6 +146,7 @@ static void factor_front_dist(Sched<T>& base, const DistFront<T>& D) {
   side.s2 = nullptr;
   side.s_la = nullptr;
   side.hiprio = base.s2 ? 1 : 0;
+  side.perm = base.s2 ? base.perm_side : base.perm;
   hipStream_t s = mn.s, s2 = side.s, sc = D.sc;
   int b0, b1;
   dist_bnd_slice(D.nb, g, me, b0, b1);

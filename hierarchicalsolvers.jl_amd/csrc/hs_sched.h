@@ -105,6 +105,10 @@ struct Sched {
   bool aligned16 = false;            // LF, UR and SB of every front are 16-byte aligned and ldl, ldu, lds even (needs h_ni / h_nb): plain updates then
                                      // run the direct-to-LDS kernel all their fronts allow (hs_gemm_lds_route; Float64)
 
+  uint16_t* perm = nullptr;          // scratch of the K-sorted tile order (GemmOp::order 2, kernels_gemm.hip) for the launches of THIS schedule's stream: at
+  uint16_t* perm_side = nullptr;     // least perm_cap uint16; perm_side: the same for the look-ahead side stream, which runs beside it.  Null: no order 2
+  size_t perm_cap = 0;
+
   // HS_DEBUG_SYNC=1: synchronise after every launch and report the first failing one (diagnostics only)
   void dbg(const char* what, int a = 0, int b = 0, int c = 0, int d = 0) {
     static int on = -1;
@@ -209,7 +213,9 @@ struct Sched {
     // route allows).  That is every update of a branch front once the elimination has reached its second child (k0 >= ni1).
     if (env && h_ni && !clipped) op.env = 0;
     hipEvent_t e0 = pf->begin(s);
-    launch_gemm_op<T>(dn, nbatch, M, N, op, s, route, shifted, op.env ? live : -1);
+    const int pslot = (sizeof(T) == 8 && op.env && perm) ? hs_env_perm_slot(maxm) : 0;
+    const bool pfits = pslot > 0 && (size_t)nbatch * hs_env_perm_stride(pslot) <= perm_cap;
+    launch_gemm_op<T>(dn, nbatch, M, N, op, s, route, shifted, op.env ? live : -1, pfits ? perm : nullptr, pfits ? pslot : 0);
     pf->end(e0, HS_CAT_GEMM, s, fl, M, N, K, nbatch, 0, hiprio);
     dbg("gemm", cmat, r0, c0, k0);
   }
@@ -513,6 +519,7 @@ struct Sched {
     side.s2 = nullptr;
     side.s_la = nullptr;
     side.hiprio = 1;
+    side.perm = perm_side;  // (the two schedules issue enveloped updates side by side)
     if (s_la) {
       (void)hipStreamWaitEvent(s2, ev_main, 0);
       side.lu_rec(0, NB);

@@ -240,6 +240,8 @@ static void gemm_schur_hook(int64_t count, const int64_t* ni_, const int64_t* nb
     sch.optimistic = true;
     sch.env = true;
     sch.h_env = h_envp.data();
+    sch.perm_cap = (size_t)count * hs_env_perm_stride(hs_env_perm_slot(maxm));
+    sch.perm = buf.get<uint16_t>(sch.perm_cap);
   }
   const long long lds0 = hsk_gemm_lds_launches(0), edge0 = hsk_gemm_lds_edge_launches(0);
   sch.gemm(HS_MAT_SB, HS_MAT_UR, 0, HS_BIG, 0, HS_BIG, 0, HS_BIG);
@@ -539,6 +541,11 @@ void FrontBatch<T>::factor(int mode, double* ms_out, bool sym) {
   if (sch.optimistic && !h_env.empty()) {
     sch.env = true;
     sch.h_env = h_env.data();
+    if (sizeof(T) == 8) {  // the K-sorted tile order (Float64): main and side stream
+      sch.perm_cap = (size_t)count * hs_env_perm_stride(hs_env_perm_slot(maxm));
+      sch.perm = buf.template get<uint16_t>(2 * sch.perm_cap);
+      sch.perm_side = sch.perm + sch.perm_cap;
+    }
   }
   const auto h0 = std::chrono::steady_clock::now();
   sch.factor_fronts();

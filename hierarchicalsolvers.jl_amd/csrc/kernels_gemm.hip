@@ -24,10 +24,12 @@
 #include <vector>
 #include <algorithm>
 #include <initializer_list>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include "hs_common.h"
+#include "hs_envelope.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef hs_d2u double2_u;
@@ -116,6 +118,72 @@ __host__ __device__ inline int env_order_stride(int T) {
 __host__ __device__ inline void env_order_apply(int& tm, int& tn, int tiles_m, int tiles_n, int sm, int sn) {
   if (sm > 1) tm = tm * sm % tiles_m;
   if (sn > 1) tn = tn * sn % tiles_n;
+}
+
+// K-sorted tile order of an enveloped plain update (GemmOp::order == 2; HS_ENV_ORDER=2, DESIGN.md section 4 "K-sorted order").  The balanced
+// order above mixes long and short tiles among the 64 workgroups an XCD holds at a time on purpose; this one keeps tiles of one K start
+// together.  Per front and launch env_perm_kernel sorts the tile rows by kr[i] = max(k0, min firstL over the rows of tile row i) and the tile
+// columns by kc[j] likewise (stable, ascending; a row or column with nothing left counts as kend), so that the tile at sorted position
+// (a, b) starts at max(kr, kc), monotone in a and in b.  The sorted grid is cut into UNITS of 8 sorted rows x 8 sorted columns; the whole
+// units come first in the sequence of positions, heaviest first (unitperm: stable by the summed K starts of their 64 tiles), 64 positions
+// each, column after column -- what tile_coords does inside a group; the right strip (fewer than 8 columns left) and the bottom strip (fewer
+// than 8 rows) follow.  Block ids reach positions through env_phase_pos: whole rounds of 8 units are dealt one unit per XCD, back and forth
+// (x, then 7 - x: under weights that fall along the sequence the XCD that got the heaviest unit of one round gets the lightest of the
+// next), what is left -- fewer than 8 units and the strips -- position by position the same way (8 consecutive positions are one column
+// of a unit: an XCD gets one sorted row of it in the even columns and the mirrored row in the odd ones, so its tiles of a unit still share
+// an A row panel), and the last < 8 block ids one per XCD.  A rest of at most 256 positions -- a launch, or the end of one, that gives every
+// CU at most one tile -- goes to the XCDs in contiguous chunks like a dense launch.
+// Every step is a bijection, so the map is one for every tile count and shift.  A static map: no atomics, nothing shared between workgroups.
+__host__ __device__ inline int env_rank(const int* keys, int n, int i) {  // position of element i in a stable ascending sort of keys[0, n)
+  const int k = keys[i];
+  int r = 0;
+  for (int j = 0; j < n; ++j) r += (keys[j] < k || (keys[j] == k && j < i)) ? 1 : 0;
+  return r;
+}
+// summed K starts of the 64 tiles of the unit (g, c), from the SORTED keys (each at most kend <= ni: the sum stays far below 2^31)
+__host__ __device__ inline int env_unit_key(const int* skr, const int* skc, int g, int c) {
+  int sum = 0;
+  for (int a = 8 * g; a < 8 * g + 8; ++a)
+    for (int b = 8 * c; b < 8 * c + 8; ++b) sum += skr[a] > skc[b] ? skr[a] : skc[b];
+  return sum;
+}
+// block id -> position in the sequence; nfull = whole units of the tiling, shift as for xcd_remap_shift
+__host__ __device__ inline int env_phase_pos(int bid, int ntiles, int nfull, int shift) {
+  const int head = (nfull >> 3) << 9;  // whole rounds of 8 units; block ids [0, head) are exactly those whose rank on their XCD is below head / 8
+  int b = bid, base = 0, lg = 6;
+  if (bid >= head) {
+    b = bid - head;  // (head is a multiple of 8: the XCD of b is still (b + shift) & 7)
+    base = head;
+    lg = 0;
+    // (at most 256 positions left: a tile per CU, nothing to balance -- contiguous chunks, which keep tiles of one K start on one XCD)
+    const int sub = ntiles - head <= 256 ? 0 : ((ntiles - head) >> 3) << 3;  // whole rounds of 8 positions
+    if (b >= sub) return head + sub + xcd_remap_shift(b - sub, ntiles - head - sub, shift);
+  }
+  const int x = (b + shift) & 7, o = (b - ((x - shift) & 7)) >> 3;  // XCD and rank of the block id among those of its XCD
+  const int r = o >> lg;
+  return base + (((r << 3) + ((r & 1) ? 7 - x : x)) << lg) + (o & ((1 << lg) - 1));
+}
+// position -> sorted tile coordinates (a, b)
+__host__ __device__ inline void env_phase_coords(int p, int tiles_m, int tiles_n, const uint16_t* unitperm, int& a, int& b) {
+  const int gm = tiles_m >> 3, gn = tiles_n >> 3;
+  if (p < 64 * gm * gn) {
+    const int u = unitperm[p >> 6], q = p & 63;
+    a = 8 * (u / gn) + (q & 7);
+    b = 8 * (u % gn) + (q >> 3);
+    return;
+  }
+  p -= 64 * gm * gn;
+  const int wr = tiles_n - 8 * gn;  // right strip: sorted rows [0, 8 gm) x the last wr columns, a group of 8 rows at a time
+  if (p < 8 * gm * wr) {
+    const int g = p / (8 * wr), q = p - g * 8 * wr;
+    a = 8 * g + (q & 7);
+    b = 8 * gn + (q >> 3);
+    return;
+  }
+  p -= 8 * gm * wr;
+  const int hb = tiles_m - 8 * gm;  // bottom strip: the last hb sorted rows x every column
+  a = 8 * gm + p % hb;
+  b = p / hb;
 }
 
 // The block envelope of a leaf front (GemmOp::env, NodeDesc::env; hs_envelope.h) comes back in `e`: which of firstL / firstU says something
@@ -906,15 +974,22 @@ __device__ inline void gemm_dispatch(const GemmProb<T>& p, bool minus, double* s
 
 // The same loop for a launch whose fronts may carry a block envelope (gemm_op_env_kernel, trsm_inv_env_kernel below)
 template <class T, Tile TILE = Tile::Reg>  // (enveloped launches have no Tile::Lds twin: launch_gemm_op sends them to the edge tile)
-__device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* smem, const EnvClip* e, int count, int order, int mlo = 0) {
+__device__ inline void gemm_dispatch_env(GemmProb<T>& p, bool minus, double* smem, const EnvClip* e, int count, int order, int mlo = 0,
+                                         const uint32_t* pm = nullptr) {
   const TileWalk<T> w(p.M, p.N);
   // (GemmOp::order: the strides of the balanced order, once per front and uniform over the workgroup; 1, 1 is the order of the dense launches)
-  const int sm = order ? env_order_stride(w.tiles_m) : 1, sn = order ? env_order_stride(w.tiles_n) : 1;
+  const int sm = (order && !pm) ? env_order_stride(w.tiles_m) : 1, sn = (order && !pm) ? env_order_stride(w.tiles_n) : 1;
   bool ran = false;
   for (int bid = blockIdx.x; bid < w.ntiles; bid += gridDim.x) {
     int tm, tn;
-    w.coords(bid, tm, tn);
-    env_order_apply(tm, tn, w.tiles_m, w.tiles_n, sm, sn);
+    if (pm) {  // the K-sorted order: the front's table (env_perm_slot), one read per tile
+      const uint32_t t = pm[bid];
+      tm = (int)(t & 0xffffu);
+      tn = (int)(t >> 16);
+    } else {
+      w.coords(bid, tm, tn);
+      env_order_apply(tm, tn, w.tiles_m, w.tiles_n, sm, sn);
+    }
     int dk = 0;
     {
       // Leaf front with a block envelope: everything here is uniform over the workgroup and done once per tile; the tile code is handed a
@@ -1005,6 +1080,83 @@ __global__ __launch_bounds__(256, 2) void trsm_inv_kernel(const NodeDesc<T>* __r
   if (!op_prologue<T, true>(nodes, op, p)) return;
   gemm_dispatch<T>(p, false, smem);
 }
+// The table of this front for the K-sorted order (GemmOp::order == 2): block id -> tile, tile row in the low and tile column in the high
+// half of a word.  Null: the launch runs another order, or the front did not fit its slot and takes the balanced order (the flag
+// env_perm_kernel left).
+__device__ __forceinline__ const uint32_t* env_perm_slot(const GemmOp& op) {
+  if (op.order != 2) return nullptr;
+  const uint16_t* pm = op.perm + (size_t)blockIdx.y * hs_env_perm_stride(op.perm_slot);
+  return pm[0] ? (const uint32_t*)(pm + 2) : nullptr;
+}
+// The tables themselves, written on the stream of the update in front of it (launch_gemm_op): grid (workgroups, fronts).  The op is resolved
+// as the update resolves it (edge: the update runs gemm_op_env_lds_kernel, which tiles a front whose A sits at an odd row from one row
+// higher), the keys are those hs_env_kstart gives the tiles, split into their row and column part.  A front without tables has constant
+// keys and gets the identity.  Every workgroup of a front does the sorts for itself in LDS (rank sorts: tile counts are at most
+// HS_ENV_PERM_MAX, a few hundred at the root of the benchmark) and fills its share of the block id -> tile table; the first also leaves the
+// permutations behind the table.  A front whose tables are not written -- more tile rows or columns than the slot holds, or fewer tiles than
+// min_tiles -- gets the flag 0 and runs the balanced order.  gridx: gridDim.x of the update, which decides the XCD a front's first block id sits on (TileWalk).
+template <class T>
+__global__ __launch_bounds__(256) void env_perm_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op, int edge, int gridx, int min_tiles) {
+  constexpr int MAXT = HS_ENV_PERM_MAX, MAXG = MAXT / 8;
+  __shared__ int key[2 * MAXT], skey[2 * MAXT], ukey[MAXG * MAXG];
+  __shared__ uint16_t rowperm[MAXT], colperm[MAXT], unitperm[MAXG * MAXG];
+  const int slot = op.perm_slot;
+  uint16_t* const pm = op.perm + (size_t)blockIdx.y * hs_env_perm_stride(slot);
+  GemmProb<T> p;
+  EnvClip e;
+  const bool ok = resolve_op<T, true>(nodes + blockIdx.y, op, p, &e);
+  if constexpr (sizeof(T) == 8)
+    if (ok && edge) e.row0 -= edge_shift_rows(p);
+  const int tiles_m = ok ? (p.M + TileCfg<T>::BM - 1) / TileCfg<T>::BM : 0, tiles_n = ok ? (p.N + TileCfg<T>::BN - 1) / TileCfg<T>::BN : 0;
+  // (min_tiles: a front with fewer tiles keeps the balanced order -- hs_env_perm_min_tiles)
+  if (!ok || tiles_m > slot || tiles_n > slot || slot > MAXT || tiles_m * tiles_n < min_tiles) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) pm[0] = 0;
+    return;
+  }
+  const int kend = e.kbase + p.K;
+  for (int i = threadIdx.x; i < tiles_m; i += blockDim.x) {
+    const int lo = i * TileCfg<T>::BM, hi = min(lo + TileCfg<T>::BM, p.M);
+    const int v = e.fL ? hs_env_min(e.fL, e.ni, e.row0 + lo, e.row0 + hi) : e.kbase;
+    key[i] = min(max(v, e.kbase), kend);
+  }
+  for (int j = threadIdx.x; j < tiles_n; j += blockDim.x) {
+    const int lo = j * TileCfg<T>::BN, hi = min(lo + TileCfg<T>::BN, p.N);
+    const int v = e.fU ? hs_env_min(e.fU, e.ni, e.col0 + lo, e.col0 + hi) : e.kbase;
+    key[MAXT + j] = min(max(v, e.kbase), kend);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < tiles_m; i += blockDim.x) {
+    const int r = env_rank(key, tiles_m, i);
+    rowperm[r] = (uint16_t)i;
+    skey[r] = key[i];
+  }
+  for (int j = threadIdx.x; j < tiles_n; j += blockDim.x) {
+    const int r = env_rank(key + MAXT, tiles_n, j);
+    colperm[r] = (uint16_t)j;
+    skey[MAXT + r] = key[MAXT + j];
+  }
+  __syncthreads();
+  const int gn = tiles_n >> 3, nfull = (tiles_m >> 3) * gn, ntiles = tiles_m * tiles_n;
+  for (int u = threadIdx.x; u < nfull; u += blockDim.x) ukey[u] = env_unit_key(skey, skey + MAXT, u / gn, u % gn);
+  __syncthreads();
+  for (int u = threadIdx.x; u < nfull; u += blockDim.x) unitperm[env_rank(ukey, nfull, u)] = (uint16_t)u;
+  __syncthreads();
+  const int shift = (gridx & 7) ? (int)(((unsigned)gridx * blockIdx.y) & 7u) : 0;  // as TileWalk has it
+  uint32_t* const tab = (uint32_t*)(pm + 2);
+  for (int bid = blockIdx.x * blockDim.x + threadIdx.x; bid < ntiles; bid += gridDim.x * blockDim.x) {
+    int a, b;
+    env_phase_coords(env_phase_pos(bid, ntiles, nfull, shift), tiles_m, tiles_n, unitperm, a, b);
+    tab[bid] = (uint32_t)rowperm[a] | ((uint32_t)colperm[b] << 16);
+  }
+  if (blockIdx.x == 0) {
+    uint16_t* const out = pm + 2 + 2 * slot * slot;
+    for (int i = threadIdx.x; i < tiles_m; i += blockDim.x) out[i] = rowperm[i];
+    for (int j = threadIdx.x; j < tiles_n; j += blockDim.x) out[slot + j] = colperm[j];
+    for (int u = threadIdx.x; u < nfull; u += blockDim.x) out[2 * slot + u] = unitperm[u];
+    if (threadIdx.x == 0) pm[0] = 1;
+  }
+}
+
 // The two kernels again for launches with GemmOp::env (batches of leaf fronts under optimistic pivoting) or GemmOp::count: kernels of their
 // own, so that the dense launches above -- every level but the leaves, 87 % of the factorization -- keep the code they had: with the
 // clip inside gemm_op_kernel<double> its register allocation moved and the dense levels of Poisson 128^3 ran 10-14 % slower.
@@ -1016,6 +1168,9 @@ __global__ __launch_bounds__(256, 2) void gemm_op_env_kernel(const NodeDesc<T>* 
   if (op.prio) __builtin_amdgcn_s_setprio(2);
   if (op.ainv) return;  // (launch_gemm_op sends those to trsm_inv_env_kernel: lets the compiler drop the in-place forms and their growth check here)
   if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
+  // (no K-sorted order here: launch_gemm_op gives the launches of this kernel -- ComplexF64, and Float64 with an odd k0 or counted -- the
+  // balanced order, so that the register-staged tiles keep the code they had.  With the table read in it the Float64 kernel went from 26 to
+  // 27 spilled VGPRs, the ComplexF64 one from 13 to 18 spilled SGPRs and helmholtz3d_64 ran 8 % slower on the balanced order itself.)
   gemm_dispatch_env<T>(p, true, smem, &e, op.count, op.order);
 }
 // The enveloped plain update on the edge tile (batches of leaf fronts whose k0 is even): the clip moves A and B by a multiple of 32
@@ -1036,7 +1191,7 @@ __global__ __launch_bounds__(256, 2) void gemm_op_env_lds_kernel(const NodeDesc<
   if (!resolve_op<T, true>(nodes + blockIdx.y, op, p, &e)) return;
   const int mlo = edge_shift_rows(p);
   e.row0 -= mlo;
-  gemm_dispatch_env<T, Tile::LdsEdge>(p, true, smem, &e, 0, op.order, mlo);
+  gemm_dispatch_env<T, Tile::LdsEdge>(p, true, smem, &e, 0, op.order, mlo, env_perm_slot(op));
 }
 template <class T>
 __global__ __launch_bounds__(256, 2) void trsm_inv_env_kernel(const NodeDesc<T>* __restrict__ nodes, GemmOp op) {
@@ -1096,7 +1251,7 @@ __global__ void resolve_dump_kernel(const NodeDesc<T>* __restrict__ nodes, GemmO
 namespace {
 std::atomic<int> g_env_on{-1};      // -1: not read yet (HS_LEAF_ENVELOPE, default on)
 std::atomic<int> g_benv_on{-1};     // -1: not read yet (HS_BRANCH_ENVELOPE, default on)
-std::atomic<int> g_env_order_on{-1};  // -1: not read yet (HS_ENV_ORDER, default on)
+std::atomic<int> g_env_order_on{-1};  // -1: not read yet (HS_ENV_ORDER, default 2)
 std::atomic<int> g_op_count_on{0};
 std::atomic<int> g_lds_on{-1};      // -1: not read yet (HS_GEMM_LDS, default on)
 std::atomic<long long> g_lds_launches{0};
@@ -1157,19 +1312,62 @@ extern "C" int hsk_branch_envelope_enable(int on) {  // returns the previous set
   g_benv_on.store(on ? 1 : 0);
   return prev;
 }
-// HS_ENV_ORDER=0 / hsk_env_order_enable(0): enveloped plain updates walk their tiles in the order of the dense launches
-static bool env_order_enabled() {
+// HS_ENV_ORDER / hsk_env_order_enable: 0 = enveloped plain updates walk their tiles in the order of the dense launches, 1 = the balanced
+// order, 2 = the K-sorted order (default; launches whose Sched carries no scratch for the tables run 1)
+static int env_order_setting() {
   int v = g_env_order_on.load(std::memory_order_relaxed);
   if (v < 0) {
     const char* e = getenv("HS_ENV_ORDER");
-    v = (e && e[0] == '0') ? 0 : 1;
+    v = (e && e[0] == '0') ? 0 : ((e && e[0] == '1') ? 1 : 2);
     g_env_order_on.store(v);
   }
-  return v != 0;
+  return v;
 }
 extern "C" int hsk_env_order_enable(int on) {  // returns the previous setting
-  const int prev = env_order_enabled() ? 1 : 0;
-  g_env_order_on.store(on ? 1 : 0);
+  const int prev = env_order_setting();
+  g_env_order_on.store(on < 0 ? 0 : (on > 2 ? 2 : on));
+  return prev;
+}
+// Tile rows / columns a scratch slot of the K-sorted order holds for a batch whose fronts have at most maxm rows; hs_env_perm_wanted: whether
+// a front of that size can reach the lower tile limit at all (analysis: levels that cannot get no scratch).  hsk_env_perm_slot_limit
+// (tests) lowers the cap, so that small fronts take the fallback of fronts that do not fit; returns the previous cap.
+namespace {
+std::atomic<int> g_perm_slot_limit{HS_ENV_PERM_MAX};
+std::atomic<int> g_perm_min_tiles{-1};  // -1: not read yet
+std::atomic<long long> g_perm_launches{0};
+}
+int hs_env_perm_slot(int maxm) {
+  const int need = ((maxm + 1 + 127) / 128 + 7) / 8 * 8;  // (128 x 128 Float64 tiles: the only ones that take the order; + 1: the shifted edge tile)
+  return std::max(8, std::min(need, g_perm_slot_limit.load(std::memory_order_relaxed)));
+}
+// Fronts with fewer tiles than this keep the balanced order under HS_ENV_ORDER=2 (HS_ENV_ORDER_MIN_TILES; default 2048 = four rounds of 8
+// units).  The K-sorted order evens the XCDs out over whole rounds, heaviest unit to another XCD in each; a front of a few hundred tiles has
+// one round or none, and in a batched launch every front leans the same way.  A heuristic fitted on ONE problem, Poisson 128^3
+// (profiles/r27_env_phase_order.txt): the level-wide Schur launches of 2116 tiles per front and more gain 3-9 %, those of 121, 361 and 900
+// tiles lose 7-70 % without the limit.  The reason given suggests a criterion in rounds of units per XCD over the whole batch; not tried.
+static int hs_env_perm_min_tiles() {
+  int v = g_perm_min_tiles.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("HS_ENV_ORDER_MIN_TILES");
+    v = e ? std::max(0, atoi(e)) : HS_ENV_PERM_MIN_TILES;
+    g_perm_min_tiles.store(v);
+  }
+  return v;
+}
+extern "C" int hsk_env_perm_min_tiles(int min_tiles) {  // tests; < 0: back to the default.  Returns the previous limit
+  const int prev = hs_env_perm_min_tiles();
+  g_perm_min_tiles.store(min_tiles < 0 ? HS_ENV_PERM_MIN_TILES : min_tiles);
+  return prev;
+}
+// launches of env_perm_kernel from launch_gemm_op since the last reset: the enveloped updates that really ran the K-sorted order
+extern "C" long long hsk_env_perm_launches(int reset) { return reset ? g_perm_launches.exchange(0) : g_perm_launches.load(); }
+bool hs_env_perm_wanted(int maxm) {
+  const long long t = (maxm + 1 + 127) / 128;
+  return t * t >= hs_env_perm_min_tiles();
+}
+extern "C" int hsk_env_perm_slot_limit(int limit) {
+  const int prev = g_perm_slot_limit.load();
+  g_perm_slot_limit.store(std::max(8, std::min(limit / 8 * 8, HS_ENV_PERM_MAX)));
   return prev;
 }
 // The tile every block id of a launch with one workgroup per tile gets (first front of a batch: shift 0), by the functions
@@ -1186,6 +1384,77 @@ extern "C" int hsk_env_tile_order(int tiles_m, int tiles_n, int order, int32_t* 
     tn[bid] = n;
   }
   return 0;
+}
+// The same for the K-sorted order, from caller-made keys (kr: tiles_m, kc: tiles_n entries, what env_perm_kernel computes from a front's
+// tables) and the shift of the front in its batch.  Host only; the sorts, the unit keys and the map are the functions the kernels call.
+extern "C" int hsk_env_phase_order(int tiles_m, int tiles_n, const int32_t* kr, const int32_t* kc, int shift, int32_t* tm, int32_t* tn, int32_t* pos) {
+  if (tiles_m <= 0 || tiles_n <= 0 || tiles_m > HS_ENV_PERM_MAX || tiles_n > HS_ENV_PERM_MAX || !kr || !kc || !tm || !tn || shift < 0 || shift > 7) return -1;
+  for (int i = 0; i < tiles_m; ++i)
+    if (kr[i] < 0 || kr[i] > (1 << 24)) return -1;
+  for (int j = 0; j < tiles_n; ++j)
+    if (kc[j] < 0 || kc[j] > (1 << 24)) return -1;
+  std::vector<uint16_t> rowperm(tiles_m), colperm(tiles_n);
+  std::vector<int> skr(tiles_m), skc(tiles_n);
+  for (int i = 0; i < tiles_m; ++i) { const int r = env_rank(kr, tiles_m, i); rowperm[r] = (uint16_t)i; skr[r] = kr[i]; }
+  for (int j = 0; j < tiles_n; ++j) { const int r = env_rank(kc, tiles_n, j); colperm[r] = (uint16_t)j; skc[r] = kc[j]; }
+  const int gn = tiles_n >> 3, nfull = (tiles_m >> 3) * gn, ntiles = tiles_m * tiles_n;
+  std::vector<int> ukey(nfull);
+  std::vector<uint16_t> unitperm(nfull + 1);
+  for (int u = 0; u < nfull; ++u) ukey[u] = env_unit_key(skr.data(), skc.data(), u / gn, u % gn);
+  for (int u = 0; u < nfull; ++u) unitperm[env_rank(ukey.data(), nfull, u)] = (uint16_t)u;
+  for (int bid = 0; bid < ntiles; ++bid) {
+    int a, b;
+    const int p = env_phase_pos(bid, ntiles, nfull, shift);
+    env_phase_coords(p, tiles_m, tiles_n, unitperm.data(), a, b);
+    if (pos) pos[bid] = p;
+    tm[bid] = rowperm[a];
+    tn[bid] = colperm[b];
+  }
+  return 0;
+}
+// env_perm_kernel on one front, as launch_gemm_op launches it in front of the plain update (cmat, bmat, r0 .. k1) of a front with ni / nb
+// rows and the block envelope `env` (2 * hs_env_nblocks entries, firstL then firstU; null: none).  No matrix is touched: the descriptor
+// carries 16-byte aligned addresses that are never read.  out: hs_env_perm_stride(slot) entries, the slot as the kernel leaves it for the
+// first front of a launch (XCD shift 0).
+template <class T>
+static int env_perm_hook(int ni, int nb, const int32_t* env, const GemmOp& op_in, int edge, int slot, uint16_t* out) {
+  if (ni <= 0 || nb < 0 || ni + nb > (1 << 20) || slot < 8 || (slot & 7) || slot > HS_ENV_PERM_MAX || !out) return -1;
+  const int m = ni + nb, nblk = hs_env_nblocks(ni, nb), stride = hs_env_perm_stride(slot);
+  NodeDesc<T> d;
+  memset(&d, 0, sizeof d);
+  d.ni = ni; d.nb = nb; d.m = m;
+  d.ldl = (m + 1) / 2 * 2; d.ldu = (ni + 1) / 2 * 2; d.lds = std::max((nb + 1) / 2 * 2, 2);
+  d.LF = (T*)(uintptr_t)0x10000000; d.UR = (T*)(uintptr_t)0x20000000; d.SB = (T*)(uintptr_t)0x30000000;
+  d.ni1 = ni; d.nb1 = nb;
+  int* denv = nullptr;
+  NodeDesc<T>* dn = nullptr;
+  uint16_t* dpm = nullptr;
+  int rc = 0;
+  if (env && hipMalloc((void**)&denv, sizeof(int) * 2 * nblk) != hipSuccess) rc = -6;
+  if (!rc && hipMalloc((void**)&dn, sizeof d) != hipSuccess) rc = -6;
+  if (!rc && hipMalloc((void**)&dpm, sizeof(uint16_t) * stride) != hipSuccess) rc = -6;
+  if (!rc && env && hipMemcpy(denv, env, sizeof(int) * 2 * nblk, hipMemcpyHostToDevice) != hipSuccess) rc = -6;
+  if (!rc) {
+    d.env = denv;
+    d.finalize();
+    GemmOp op = op_in;
+    op.ainv = 0; op.env = env ? 1 : 0; op.order = 2; op.perm = dpm; op.perm_slot = slot;
+    if (hipMemcpy(dn, &d, sizeof d, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dpm, 0xFF, sizeof(uint16_t) * stride) != hipSuccess) rc = -6;
+    if (!rc) {
+      hipLaunchKernelGGL(env_perm_kernel<T>, dim3(2), dim3(256), 0, nullptr, dn, op, edge, 8, 0);  // (two workgroups share the table; shift 0; no lower limit)
+      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, dpm, sizeof(uint16_t) * stride, hipMemcpyDeviceToHost) != hipSuccess) rc = -6;
+    }
+  }
+  if (denv) (void)hipFree(denv);
+  if (dn) (void)hipFree(dn);
+  if (dpm) (void)hipFree(dpm);
+  return rc;
+}
+extern "C" int hsk_env_perm(int is_complex, int ni, int nb, const int32_t* env, int cmat, int bmat, int r0, int r1, int c0, int c1, int k0, int k1,
+                            int edge, int slot, uint16_t* out) {
+  if (cmat < 0 || cmat > 2 || bmat < 0 || bmat > 2 || r0 < 0 || c0 < 0 || k0 < 0) return -1;
+  GemmOp op{cmat, bmat, r0, r1, c0, c1, k0, k1};
+  return is_complex ? env_perm_hook<cplx>(ni, nb, env, op, 0, slot, out) : env_perm_hook<double>(ni, nb, env, op, edge ? 1 : 0, slot, out);
 }
 extern "C" int hsk_op_flops_mode(int on) {  // resets the counter
   (void)hipDeviceSynchronize();
@@ -1253,18 +1522,24 @@ static OpKernel<T> pick_op_kernel(const GemmOp& op, int route) {
 
 template <class T>
 void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, const GemmOp& op_in, hipStream_t s, int route, bool shifted,
-                    long long live_tiles) {
+                    long long live_tiles, uint16_t* perm, int perm_slot) {
   if (nbatch <= 0 || maxM <= 0 || maxN <= 0) return;
   GemmOp op = op_in;
   op.count = (!op.ainv && g_op_count_on.load(std::memory_order_relaxed)) ? 1 : 0;
-  op.order = (op.env && !op.ainv && env_order_enabled()) ? 1 : 0;
+  op.order = (op.env && !op.ainv) ? env_order_setting() : 0;
+  if (op.order == 2 && (!perm || perm_slot < 8 || perm_slot > HS_ENV_PERM_MAX)) op.order = 1;  // no scratch for the tables on this path
   static const bool dump = getenv("HS_DEBUG_SYNC") && getenv("HS_DEBUG_SYNC")[0] == '2';
   if (dump) dump_resolved_op(dnodes, nbatch, maxM, maxN, op, s);
   // (the caller vouches for K and the alignment of every front: hs_gemm_lds_route)
   if (sizeof(T) != 8 || op.ainv || op.count || !gemm_lds_enabled()) route = HS_GEMM_ROUTE_REG;
   if (op.env && route == HS_GEMM_ROUTE_LDS) route = HS_GEMM_ROUTE_EDGE;  // one enveloped twin: the edge tile
+  if (op.order == 2 && route == HS_GEMM_ROUTE_REG) op.order = 1;  // (gemm_op_env_kernel holds no K-sorted order: ComplexF64, odd k0, counted launches)
+  op.perm = op.order == 2 ? perm : nullptr;
+  op.perm_slot = op.order == 2 ? perm_slot : 0;
   if (route == HS_GEMM_ROUTE_EDGE && shifted) maxM += 1;  // a front whose A sits at an odd row runs one row higher (edge_shift_rows)
   int tiles = ((maxM + TileCfg<T>::BM - 1) / TileCfg<T>::BM) * ((maxN + TileCfg<T>::BN - 1) / TileCfg<T>::BN);
+  const int all_tiles = tiles;
+  if (op.order == 2 && all_tiles < hs_env_perm_min_tiles()) op.order = 1, op.perm = nullptr, op.perm_slot = 0;  // (no front of the launch is large enough)
   if (op.cap > 0 && tiles > op.cap) tiles = std::max(8, op.cap / 8 * 8);
   // Enveloped launch of a batch of leaf fronts: most tiles of the bounding box are empty.  A workgroup per tile would start, read its
   // descriptor and leave; instead a quarter as many workgroups (HS_ENV_WALK, 1: off) walk the tiles, so that an empty tile costs a table
@@ -1287,6 +1562,11 @@ void launch_gemm_op(const NodeDesc<T>* dnodes, int nbatch, int maxM, int maxN, c
   }
   const OpKernel<T> k = pick_op_kernel<T>(op, route);
   if (k.launches) k.launches->fetch_add(1, std::memory_order_relaxed);
+  if (op.order == 2) {  // the tables of the K-sorted order, per front, for the tiling and the grid of the kernel below (the edge tile)
+    g_perm_launches.fetch_add(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(env_perm_kernel<T>, dim3(std::max(1, std::min(32, all_tiles / 2048)), nbatch), dim3(256), 0, s, dnodes, op, 1, tiles,
+                       hs_env_perm_min_tiles());
+  }
   hipLaunchKernelGGL(k.fn, dim3(tiles, nbatch), dim3(256), k.lds_bytes, s, dnodes, op);
 }
 
@@ -1371,7 +1651,7 @@ void launch_gemm_probs(const GemmProb<T>* dprobs, int nprob, int maxM, int maxN,
   hipLaunchKernelGGL(gemm_probs_kernel<T>, dim3(tiles, nprob), dim3(256), lds_bytes, s, dprobs, minus);
 }
 
-template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, const GemmOp&, hipStream_t, int, bool, long long);
-template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t, int, bool, long long);
+template void launch_gemm_op<double>(const NodeDesc<double>*, int, int, int, const GemmOp&, hipStream_t, int, bool, long long, uint16_t*, int);
+template void launch_gemm_op<cplx>(const NodeDesc<cplx>*, int, int, int, const GemmOp&, hipStream_t, int, bool, long long, uint16_t*, int);
 template void launch_gemm_probs<double>(const GemmProb<double>*, int, int, int, int, hipStream_t);
 template void launch_gemm_probs<cplx>(const GemmProb<cplx>*, int, int, int, int, hipStream_t);

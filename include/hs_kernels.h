@@ -284,13 +284,33 @@ int hs_probs_stats(double* out3);
  *                         resets the counter.  Counting changes which kernel runs: while it is on, every plain update -- of dense fronts
  *                         too -- is launched as `gemm_op_env_kernel` (the same tile code; `gemm_op_kernel` holds no counter).
  *                         hsk_op_flops(out) reads the counter (synchronises the device): equals hs_stats.gemm_flops.
- *   hsk_env_order_enable : 1 / 0 turns the balanced tile order of the enveloped plain updates on / off (default: on unless HS_ENV_ORDER=0);
- *                         returns the previous setting.  Off, an enveloped launch maps block ids to tiles as a dense one does.  Which
+ *   hsk_env_order_enable : the tile order of the enveloped plain updates (HS_ENV_ORDER): 2 the K-sorted order (default: tiles of one K start
+ *                         run side by side; Float64 fronts of at least 2048 tiles, every other launch runs 1), 1 the balanced order, 0 off -- an enveloped
+ *                         launch maps block ids to tiles as a dense one does.  Returns the previous setting.  Which
  *                         workgroup runs a tile changes, never what the tile computes: every stored value keeps its bits.
  *   hsk_env_tile_order  : host only, no device.  For bid = 0 .. tiles_m * tiles_n - 1, the tile (tm[bid], tn[bid]) that block `bid` of a
  *                         launch with one workgroup per tile runs (first front of a batch), by the functions the kernels call; order 0 /
  *                         1 as the switch.  Blocks bid, bid + 8, ... share an XCD.  Returns 0, or -1 for a bad argument (a tile count outside
  *                         1 .. 32768, more than 2^24 tiles in all, a null pointer).
+ *   hsk_env_phase_order : the same for the K-sorted order (2), host only: kr[tiles_m] / kc[tiles_n] are the K starts of the tile rows / columns
+ *                         (0 .. 2^24), shift 0 .. 7 the XCD of the front's first block in a batched launch; at most 512 tile rows /
+ *                         columns.  pos (may be null): the position of every block id in the sequence the tiles are dealt from.
+ *                         Positions 64 u .. 64 u + 63 of the sequence, u below (tiles_m / 8) * (tiles_n / 8), are one unit
+ *                         of 8 sorted tile rows x 8 sorted tile columns.
+ *   hsk_env_perm        : the kernel that writes the tables of the K-sorted order, on one front (ni, nb; env: firstL then firstU as
+ *                         hsk_leaf_envelope lays them out, or null) for the plain update (cmat, bmat, rows r0 .. r1, columns c0 .. c1,
+ *                         k0 .. k1) as a factorization poses it; edge != 0: the tiling of the direct-to-LDS edge kernel (a front whose A
+ *                         sits at an odd row is tiled from one row higher; Float64 only).  slot: tile rows / columns the tables hold, a
+ *                         multiple of 8 in 8 .. 512.  out: 2 + 2 slot^2 + 2 slot + (slot / 8)^2 entries -- [0] 1 = valid (0: the front has
+ *                         more tile rows or columns than the slot), from [2] the pairs (tile row, tile column) of block id 0, 1, ... of the
+ *                         first front of a launch, then from [2 + 2 slot^2] rowperm[slot], colperm[slot] and the unit order.
+ *   hsk_env_perm_slot_limit : caps the slot the factorizations and hooks that follow use (tests: fronts that do not fit take the balanced
+ *                         order); returns the previous cap.
+ *   hsk_env_perm_min_tiles : fronts with fewer tiles than this keep the balanced order under order 2 (HS_ENV_ORDER_MIN_TILES, default 2048);
+ *                         a negative value restores the default.  Returns the previous limit.  hsk_env_perm itself applies none.
+ *   hsk_env_perm_launches : enveloped updates that really ran the K-sorted order since the last reset (launches of the table kernel).  The
+ *                         order runs on the Float64 direct-to-LDS tile only: ComplexF64 launches, Float64 launches with an odd k0 and
+ *                         counted launches (hsk_op_flops_mode) run the balanced order under setting 2.
  *   (hsk_leaf_envelope checks fidx, colptr and rowval against n.) */
 int hsk_leaf_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int32_t* firstL, int32_t* firstU);
 int hsk_branch_envelope(int64_t n, const int64_t* colptr, const int64_t* rowval, const int32_t* fidx, int64_t ni, int64_t nb, int64_t ni1, int64_t nb1,
@@ -299,6 +319,12 @@ int hsk_envelope_enable(int on);
 int hsk_branch_envelope_enable(int on);
 int hsk_env_order_enable(int on);
 int hsk_env_tile_order(int tiles_m, int tiles_n, int order, int32_t* tm, int32_t* tn);
+int hsk_env_phase_order(int tiles_m, int tiles_n, const int32_t* kr, const int32_t* kc, int shift, int32_t* tm, int32_t* tn, int32_t* pos);
+int hsk_env_perm(int is_complex, int ni, int nb, const int32_t* env, int cmat, int bmat, int r0, int r1, int c0, int c1, int k0, int k1, int edge,
+                 int slot, uint16_t* out);
+int hsk_env_perm_slot_limit(int limit);
+int hsk_env_perm_min_tiles(int min_tiles);
+long long hsk_env_perm_launches(int reset);
 int hsk_op_flops_mode(int on);
 int hsk_op_flops(double* out);
 

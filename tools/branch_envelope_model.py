@@ -7,7 +7,7 @@ per tile of T x T positions (T = 128, or the environment variable T), a tile sta
 tile of that size can skip (an estimate: the real tiles are aligned to their launch, not to the front).  Leaves are not counted.
 
 A second table takes the level-wide Schur launch of every branch level -- the longest plain update of a level -- tile by tile: the K-steps
-each of the 8 XCDs runs under the dense tile order and under the balanced one (GemmOp::order, HS_ENV_ORDER; the block id -> tile map is the
+each of the 8 XCDs runs under the dense tile order, the balanced one and the K-sorted one (GemmOp::order, HS_ENV_ORDER; the block id -> tile map is the
 library's own, hsk_env_tile_order), as heaviest XCD over mean.  The other plain updates of a level (panel and block-column updates inside
 the interior part) are not modelled: they follow the blocked LU schedule, which this tool does not restate."""
 import ctypes as C
@@ -102,13 +102,20 @@ def tile_of_id(L, tiles, order):
     return om, on
 
 
+MIN_TILES = int(os.environ.get("HS_ENV_ORDER_MIN_TILES", "2048"))  # fronts with fewer tiles keep the balanced order under order 2 (kernels_gemm.hip)
+
+
 def schur_xcd_load(L, fronts, order):
     """K-steps every XCD runs in the level-wide Schur launch SB -= LF[ni.., 0:ni) * UR of a batch (one workgroup per tile, grid.x = the tiles
     of the largest front; the hardware deals workgroups to the XCDs round-robin over blockIdx.x + gridDim.x * blockIdx.y).  The fronts are
-    taken in tree order, which need not be the batch order of the library: the shifts of the single fronts are an estimate."""
+    taken in tree order, which need not be the batch order of the library: the shifts of the single fronts are an estimate.  order 2: the
+    K-sorted order, from the library's own hsk_env_phase_order.  Also returns the share of the tiles that sit among the 64 consecutive
+    block ids of their XCD (the workgroups it holds at a time) with a single K start."""
     gx = max(-(-nb // BM) ** 2 for _, nb, _, _ in fronts)
     load = np.zeros(XCDS)
     cache = {}
+    single = total = 0
+    p32 = C.POINTER(C.c_int32)
     for y, (ni, nb, fL, fU) in enumerate(fronts):
         tiles = -(-nb // BM)
         if tiles == 0:
@@ -118,15 +125,31 @@ def schur_xcd_load(L, fronts, order):
         rmin = np.concatenate([fL[nbi:], pad]).reshape(tiles, BM // G).min(axis=1)
         cmin = np.concatenate([fU[nbi:], pad]).reshape(tiles, BM // G).min(axis=1)
         steps = -(-np.maximum(ni - np.maximum(rmin[:, None], cmin[None, :]), 0) // BK)  # [tm, tn]
-        if tiles not in cache:
-            cache[tiles] = tile_of_id(L, tiles, order)
-        om, on = cache[tiles]
         nt = tiles * tiles
         shift = (gx * y) & 7 if gx & 7 else 0
         bid = np.arange(nt)
-        t = xcd_remap_shift(bid, nt, shift)
-        load += np.bincount((bid + shift) & 7, weights=steps[om[t], on[t]].astype(np.float64), minlength=XCDS)
-    return load
+        if order == 2 and nt >= MIN_TILES and tiles <= 512:
+            kr = np.ascontiguousarray(np.clip(rmin, 0, ni), dtype=np.int32)
+            kc = np.ascontiguousarray(np.clip(cmin, 0, ni), dtype=np.int32)
+            tm, tn = np.empty(nt, dtype=np.int32), np.empty(nt, dtype=np.int32)
+            assert L.hsk_env_phase_order(tiles, tiles, kr.ctypes.data_as(p32), kc.ctypes.data_as(p32), shift, tm.ctypes.data_as(p32),
+                                         tn.ctypes.data_as(p32), None) == 0
+        else:
+            o = min(order, 1)
+            if (tiles, o) not in cache:
+                cache[(tiles, o)] = tile_of_id(L, tiles, o)
+            om, on = cache[(tiles, o)]
+            t = xcd_remap_shift(bid, nt, shift)
+            tm, tn = om[t], on[t]
+        st = steps[tm, tn]
+        load += np.bincount((bid + shift) & 7, weights=st.astype(np.float64), minlength=XCDS)
+        for x in range(XCDS):
+            mine = st[((bid + shift) & 7) == x]
+            for lo in range(0, mine.size, 64):
+                c = mine[lo : lo + 64]
+                single += c.size if np.all(c == c[0]) else 0
+        total += nt
+    return load, single / max(total, 1)
 
 
 def main():
@@ -176,19 +199,20 @@ def main():
                                                                      r["eT"], r["eT"] / r["dense"]))
     print("| all | | | %.4g | %.4g | %.3f | %.4g | %.3f |" % (tot[0], tot[1], tot[1] / tot[0], tot[2], tot[2] / tot[0]))
     print()
-    print("# level-wide Schur launches: K-steps of the heaviest XCD over the mean, dense tile order (HS_ENV_ORDER=0) and balanced order (1);")
-    print("# K-steps run / dense = the share of the dense launch's K-steps that the clipped tiles run")
-    print("| level | fronts | tile rows (largest front) | K-steps run / dense | heaviest / mean, order 0 | order 1 |")
-    print("|---|---|---|---|---|---|")
+    print("# level-wide Schur launches: K-steps of the heaviest XCD over the mean, dense tile order (HS_ENV_ORDER=0), balanced order (1) and")
+    print("# K-sorted order (2; fronts below %d tiles keep order 1); K-steps run / dense = the share of the dense launch's K-steps that the" % MIN_TILES)
+    print("# clipped tiles run; single start = share of the tiles whose 64 co-resident block ids of their XCD have one K start, orders 0 / 1 / 2")
+    print("| level | fronts | tile rows (largest front) | K-steps run / dense | heaviest / mean, order 0 | order 1 | order 2 | single start 0 / 1 / 2 |")
+    print("|---|---|---|---|---|---|---|---|")
     for lv in sorted(lev):
         fr = [f for f in lev[lv]["fr"] if f[1] > 0]
         if not fr:
             continue
-        l0, l1 = schur_xcd_load(L, fr, 0), schur_xcd_load(L, fr, 1)
+        (l0, s0), (l1, s1), (l2, s2) = (schur_xcd_load(L, fr, o) for o in (0, 1, 2))
         dense = sum((-(-nb // BM)) ** 2 * -(-ni // BK) for ni, nb, _, _ in fr)
-        assert l0.sum() == l1.sum()
-        print("| %d | %d | %d | %.3f | %.3f | %.3f |" % (lv, len(fr), max(-(-nb // BM) for _, nb, _, _ in fr), l0.sum() / dense, l0.max() / l0.mean(),
-                                                    l1.max() / l1.mean()))
+        assert l0.sum() == l1.sum() == l2.sum()
+        print("| %d | %d | %d | %.3f | %.3f | %.3f | %.3f | %.2f / %.2f / %.2f |" % (lv, len(fr), max(-(-nb // BM) for _, nb, _, _ in fr), l0.sum() / dense,
+                                                                            l0.max() / l0.mean(), l1.max() / l1.mean(), l2.max() / l2.mean(), s0, s1, s2))
 
 
 if __name__ == "__main__":
