@@ -79,7 +79,7 @@ EXPORTS = [
     "hs_ldiv_t_d", "hs_ldiv_t_z", "hs_ldiv_dev_t_d", "hs_ldiv_dev_t_z",
     "hs_ldiv_block_d", "hs_ldiv_block_z", "hs_ldiv_block_dev_d", "hs_ldiv_block_dev_z", "hs_ldiv_block_info", "hsk_multi_prob_d", "hsk_multi_prob_z",
     "hs_ldiv_block_t_d", "hs_ldiv_block_t_z", "hs_ldiv_block_dev_t_d", "hs_ldiv_block_dev_t_z", "hsk_multi_prob_t_d", "hsk_multi_prob_t_z",
-    "hs_ldiv_ulv_d", "hs_ldiv_ulv_z", "hs_ldiv_ulv_dev_d", "hs_ldiv_ulv_dev_z",
+    "hs_ldiv_ulv_d", "hs_ldiv_ulv_z", "hs_ldiv_ulv_dev_d", "hs_ldiv_ulv_dev_z", "hs_ulv_mode", "hs_hss_logabsdet", "hsk_ulv_det_d", "hsk_ulv_det_z",
     "hs_mul_d", "hs_mul_z", "hs_mul_dev_d", "hs_mul_dev_z", "hs_mul_info", "hs_factor_error_d", "hs_factor_error_z",
     "hsk_multi_tri_d", "hsk_multi_tri_z", "hsk_multi_tri_t_d", "hsk_multi_tri_t_z",
     "hs_ldiv_sparse_d", "hs_ldiv_sparse_z", "hs_ldiv_sparse_dev_d", "hs_ldiv_sparse_dev_z", "hs_ldiv_sparse_plan", "hs_ldiv_sparse_info",
@@ -357,6 +357,13 @@ def lib():
     L.hsk_eigs_gen_mprod_seconds.restype = C.c_double
     L.hs_logabsdet.argtypes = [vp, p_f64, p_f64]
     L.hs_logabsdet.restype = C.c_int
+    L.hs_ulv_mode.argtypes = [vp, C.c_int]
+    L.hs_ulv_mode.restype = C.c_int
+    L.hs_hss_logabsdet.argtypes = [vp, p_f64, p_f64, p_f64]
+    L.hs_hss_logabsdet.restype = C.c_int
+    for f in (L.hsk_ulv_det_d, L.hsk_ulv_det_z):
+        f.argtypes = [i64, p_i64, p_i64, p_f64, C.POINTER(C.c_int32), p_f64, C.POINTER(C.c_int32), p_f64]
+        f.restype = C.c_int
     L.hs_selinv.argtypes = [vp, C.c_int, vp, vp, C.c_int, i64, vp]
     L.hs_selinv.restype = C.c_int
     L.hs_selinv_info.argtypes = [vp, p_f64]

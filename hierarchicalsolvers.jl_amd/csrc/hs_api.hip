@@ -268,6 +268,7 @@ struct hs_handle {
   size_t fac_elems = 0, inv_elems = 0, sb_elems = 0, int_elems = 0;
   bool sb_kept = false;
   bool numeric_open = false, factored = false;
+  int ulv_mode = 0;  // hs_ulv_mode: 1 -- the lockstep drivers and hs_logabsdet serve fronts with an HSS interior block through the ULV block solve
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;    // side stream for look-ahead panels (own compute units, or high priority)
   hipStream_t stream_la = nullptr;  // CU-masked pair for the look-ahead schedule of a lone front: stream_la = every CU
@@ -2035,6 +2036,7 @@ void hs_handle_view(hs_handle* h, HsHandleView* v) {
   v->device = h->d_nodes ? 1 : 0;
   v->nranks = h->nranks;
   v->t_refused_node = first_hss_front(h);  // what check_solve_t refuses
+  v->ulv = hs_handle_ulv_routed(h);
   v->seed = h->opts.seed;
   v->colptr = h->d_colptr;
   v->rowval = h->d_rowval;
@@ -2048,6 +2050,7 @@ void hs_handle_view(hs_handle* h, HsHandleView* v) {
   v->cx = &h->cx;
   v->cx_free = &h->cx_free;
 }
+int hs_handle_ulv_routed(const hs_handle* h) { return h && h->ulv_mode == 1 && first_hss_front(h) >= 0 ? 1 : 0; }
 int hs_handle_flow_check(hs_handle* h) { HS_GUARD(flow_check(h)); }
 double* hs_handle_sens_info(hs_handle* h) { return h->sens_info; }  // hs_sens.h
 double* hs_handle_gn_info(hs_handle* h) { return h->gn_info; }      // hs_gn.h
@@ -2064,6 +2067,7 @@ void hs_selinv_view(hs_handle* h, HsSelView* v) {
   v->stream = h->stream;
   v->sx = &h->sx;
   v->sx_free = &h->sx_free;
+  v->ulv_mode = h->ulv_mode;
   if (!v->device) return;
   v->fidx_host = h->fidx_host.data();
   v->colptr = h->d_colptr;
@@ -2079,7 +2083,12 @@ void hs_selinv_view(hs_handle* h, HsSelView* v) {
     f.ni = x.ni;
     f.nb = x.nb;
     if (x.ext_sb) sb_idle = false;
-    if (x.hss_interior()) f.flags |= HS_SEL_NOLU;
+    if (x.hss_interior()) {
+      f.flags |= HS_SEL_NOLU;
+      f.hss = (const hs_hss*)x.hss;
+      f.hss2 = x.mfb ? (const hs_hss*)x.hss2 : nullptr;
+      f.mfb = x.mfb ? 1 : 0;
+    }
     if (x.compressed || x.mf) f.flags |= HS_SEL_LOWRANK;
     if (x.kind != 0) f.flags |= HS_SEL_SLICE;
     if ((x.compressed || x.mfd) && !x.hss_interior() && (x.lrL || x.lrR)) {  // the fronts hs_multi_view lists in HsMultiLevel::lr (hs_selinv_lr)
@@ -2338,6 +2347,20 @@ extern "C" int hs_flow_info(const hs_handle* h, int64_t* out8) {
              out8[1] += x.mf ? 1 : 0; out8[2] += x.s_hss ? 1 : 0; out8[3] += (x.compressed && !x.leaf) ? 1 : 0; out8[4] += x.hssd ? 1 : 0; out8[5] += x.dist ? 1 : 0;
              out8[7] += x.kind != 0 ? 1 : 0;
            });
+}
+// Handle state, host side only (a plan-only handle has it too): it survives hs_numeric_begin and every refactorization.
+extern "C" int hs_ulv_mode(hs_handle* h, int mode) {
+  if (!h) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ulv_mode: null factorization handle");
+    return HS_ERR_ARGUMENT;
+  }
+  if (mode < -1 || mode > 1) {
+    hs_set_error(HS_ERR_ARGUMENT, mode, "ArgumentError: hs_ulv_mode: mode = %d (0: off, 1: on, -1: query)", mode);
+    return HS_ERR_ARGUMENT;
+  }
+  const int prev = h->ulv_mode;
+  if (mode >= 0) h->ulv_mode = mode;
+  return prev;
 }
 // out4 = {hs_options.symmetric, dense fronts of the last factorization eliminated on their lower triangle (Sched::sym), fronts eliminated as
 //         before -- dense ones of a tournament-pivoted or redone level, of a level fed by compressed children, and the compressed, HSS and matrix-free ones --, 0}

@@ -16,6 +16,7 @@ struct HsHandleView {
   int device = 0;          // 0: a host-side plan only (hs_plan)
   int nranks = 1;
   int t_refused_node = -1; // first owned node whose transposed solve is refused (D kept as an HSS matrix: hss_d, mf = 2, 3); -1: none
+  int ulv = 0;             // hs_ulv_mode is 1 and t_refused_node >= 0: op(F)^-1 goes through hs_ldiv_ulv_dev_* (hs_block_apply.h)
   int64_t seed = 0;        // hs_options.seed
   const int64_t* colptr = nullptr;  // A in CSC on the device, 0-based; hs_numeric_begin keeps the values current
   const int32_t* rowval = nullptr;
@@ -29,6 +30,8 @@ struct HsHandleView {
 };
 
 void hs_handle_view(hs_handle* h, HsHandleView* v);
+// HsHandleView::ulv alone (null: 0): what hs_block_apply.h asks before every application; no node is looked at while hs_ulv_mode is 0
+int hs_handle_ulv_routed(const hs_handle* h);
 // HS_OK, or HS_ERR_DEVICE with hs_last_error set when a dataflow sweep since the last check timed out (call after every synchronisation)
 int hs_handle_flow_check(hs_handle* h);
 

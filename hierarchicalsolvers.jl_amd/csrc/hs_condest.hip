@@ -21,6 +21,7 @@
 #define HS_CONDEST_KERNELS
 #include "hs_condest.h"
 #include "hs_normest.h"
+#include "hs_block_apply.h"
 
 // No contraction of a*b + c into an fma in this file: the residual r = b - op(A) x and the weights w are then the plain products and sums, row by
 // row in column order, that scipy's CSR product computes -- a test can recompute berr from the returned X and compare (berr is ~eps, and the
@@ -324,10 +325,7 @@ namespace {
 // F^-1, F^-T, F^-H (tr = 0, 1, 2) in place on nc columns of leading dimension n
 template <class T>
 void solve_dev(hs_handle* F, int tr, T* X, int64_t n, int64_t nc, hipStream_t s) {
-  if (sizeof(T) == 16)
-    HS_CHECK(hs_ldiv_dev_t_z(F, tr, (double*)X, n, (const double*)X, n, n, nc, (void*)s));
-  else
-    HS_CHECK(hs_ldiv_dev_t_d(F, tr, (double*)X, n, (const double*)X, n, n, nc, (void*)s));
+  HS_CHECK(hs_block_apply_dev<T>(F, HS_VIA_COLS_T, tr, X, n, (const T*)X, n, n, nc, s));
 }
 
 // ---- argument checks: refuse, never drop ----------------------------------------------------------------------------------------------
@@ -341,9 +339,14 @@ void check_factored(const HsHandleView& v, const char* fn) {
   if (!v.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
 }
 void check_t_solves(const HsHandleView& v, const char* fn, const char* what) {
-  if (v.t_refused_node >= 0)
+  if (v.t_refused_node >= 0 && !v.ulv)  // (hs_ulv_mode 1: solve_dev goes through hs_ldiv_ulv_dev_*, which serves N, T and H)
     HS_FAIL(HS_ERR_UNSUPPORTED, v.t_refused_node, "%s: %s needs transposed solves, and node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): "
             "transposed ULV solves are not implemented", fn, what, v.t_refused_node);
+}
+// hs_ulv_mode 1 on a handle with such fronts: what hs_ldiv_ulv_dev_* refuses is refused before any device work, with its words
+void check_ulv_serves(hs_handle* F, const HsHandleView& v) {
+  if (!v.ulv) return;
+  HS_CHECK(v.is_complex ? hs_block_probe<cplx>(F, HS_VIA_COLS_T, 0) : hs_block_probe<double>(F, HS_VIA_COLS_T, 0));
 }
 void check_t(const HsHandleView& v, int64_t t, const char* fn) {
   const int64_t tmax = std::min<int64_t>(CE_MAXT, v.n);
@@ -462,6 +465,7 @@ void refine_entry(hs_handle* F, int trans, T* X, int64_t ldx, const T* B, int64_
   check_refine_args<T>(fn, v, trans, X, ldx, B, ldb, n, nrhs, itmax, berr, steps);
   if (trans != 0) check_t_solves(v, fn, "trans != 0");
   if (ferr) check_t_solves(v, fn, "the forward error bound ferr");
+  check_ulv_serves(F, v);
   if (nrhs == 0) return;
   if (on_device) {
     check_no_alias<T>(fn, X, ldx, B, ldb, nrhs);
@@ -492,7 +496,7 @@ extern "C" int hs_normestinv(hs_handle* F, int trans, int64_t t, int64_t itmax, 
            check_t(v, t, "hs_normestinv");
            if (itmax < 1 || itmax > CE_MAXIT) HS_FAIL(HS_ERR_ARGUMENT, itmax, "ArgumentError: hs_normestinv: itmax = %lld outside 1:%d", (long long)itmax, CE_MAXIT);
            if (!est) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_normestinv: est == NULL");
-           check_t_solves(v, "hs_normestinv", "the estimator");
+           check_t_solves(v, "hs_normestinv", "the estimator"); check_ulv_serves(F, v);
            hipStream_t s = (hipStream_t)stream;
            *est = v.is_complex ? normestinv_impl<cplx>(F, v, trans, (int)t, (int)itmax, nsolves, s) : normestinv_impl<double>(F, v, trans, (int)t, (int)itmax, nsolves, s));
 }
@@ -501,7 +505,7 @@ extern "C" int hs_condest(hs_handle* F, int p, int64_t t, double* cond, double* 
   HS_GUARD(const HsHandleView v = checked_view(F, "hs_condest"); check_factored(v, "hs_condest");
            if (p != 0 && p != 1) HS_FAIL(HS_ERR_ARGUMENT, p, "ArgumentError: hs_condest: p = %d (1 or 0 = Inf)", p);
            check_t(v, t, "hs_condest"); if (!cond) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_condest: cond == NULL");
-           check_t_solves(v, "hs_condest", "the estimator");
+           check_t_solves(v, "hs_condest", "the estimator"); check_ulv_serves(F, v);
            hipStream_t s = (hipStream_t)stream;
            const int trans = p == 1 ? 0 : 1;  // ||F^-1||_Inf = ||F^-T||_1
            const double na = v.is_complex ? opnorm_impl<cplx>(F, v, p, s) : opnorm_impl<double>(F, v, p, s);

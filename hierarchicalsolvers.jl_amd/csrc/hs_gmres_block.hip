@@ -39,6 +39,7 @@
 
 #include "../../include/hs_kernels.h"
 #include "hs_host.h"
+#include "hs_block_apply.h"
 #include "hs_gmres_common.h"
 #include "hs_solve_multi.h"
 #include "hs_mod.h"  // hs_mod_apply_prec, hs_mod_handle
@@ -296,28 +297,6 @@ __global__ __launch_bounds__(64) void breset_kernel(GbSmall<T> S, int m, int nac
   S.mask[c] = 1;
 }
 
-template <class T>
-int prec_block(hs_handle* F, T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s);
-template <>
-int prec_block<double>(hs_handle* F, double* out, const double* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) {
-  return hs_ldiv_block_dev_d(F, 0, out, ld, in, ld, n, nc, (void*)s);
-}
-template <>
-int prec_block<cplx>(hs_handle* F, cplx* out, const cplx* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) {
-  return hs_ldiv_block_dev_z(F, 0, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
-}
-
-template <class T>
-int prec_block_t(hs_handle* F, int trans, T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s);
-template <>
-int prec_block_t<double>(hs_handle* F, int trans, double* out, const double* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) {
-  return hs_ldiv_block_dev_t_d(F, trans, out, ld, in, ld, n, nc, (void*)s);
-}
-template <>
-int prec_block_t<cplx>(hs_handle* F, int trans, cplx* out, const cplx* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) {
-  return hs_ldiv_block_dev_t_z(F, trans, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
-}
-
 // What gmres_group is instantiated on.  The operator: Y[:, c] = A X[:, xmap[c]], or B[:, bmap[c]] - A X[:, xmap[c]] with B.  The
 // preconditioner: out = Pr^-1 in on an n x nc block; F == nullptr: none.
 template <class T>
@@ -339,7 +318,7 @@ struct RowsSpmm {  // hs_gmres_block_t_*: op(A) over entry ranges
 template <class T>
 struct PrecBlockFwd {  // hs_ldiv_block_dev_*
   hs_handle* F;
-  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return prec_block<T>(F, out, in, ld, n, nc, s); }
+  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return hs_block_apply_dev<T>(F, HS_VIA_BLOCK, 0, out, ld, in, ld, n, nc, s); }
 };
 template <class T>
 struct PrecBlockMod {  // hs_mod_ldiv_dev_*: op(A + U V^H)^-1 through the factors of A
@@ -359,7 +338,7 @@ template <class T>
 struct PrecBlockOp {  // hs_ldiv_block_dev_t_*: op(F)
   hs_handle* F;
   int trans;
-  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return prec_block_t<T>(F, trans, out, in, ld, n, nc, s); }
+  int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const { return hs_block_apply_dev<T>(F, HS_VIA_BLOCK_T, trans, out, ld, in, ld, n, nc, s); }
 };
 
 // hs_gmres_* / hs_gmres_t_*: the single-right-hand-side solves, which also serve the handles the block solve refuses (their columns are
@@ -368,8 +347,7 @@ template <class T>
 struct PrecFwd {  // hs_ldiv_dev_*
   hs_handle* F;
   int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const {
-    if constexpr (sizeof(T) == 16) return hs_ldiv_dev_z(F, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
-    else return hs_ldiv_dev_d(F, out, ld, in, ld, n, nc, (void*)s);
+    return hs_block_apply_dev<T>(F, HS_VIA_COLS, 0, out, ld, in, ld, n, nc, s);
   }
 };
 template <class T>
@@ -377,8 +355,7 @@ struct PrecOp {  // hs_ldiv_dev_t_*: op(F)
   hs_handle* F;
   int trans;
   int operator()(T* out, const T* in, int64_t ld, int64_t n, int64_t nc, hipStream_t s) const {
-    if constexpr (sizeof(T) == 16) return hs_ldiv_dev_t_z(F, trans, (double*)out, ld, (const double*)in, ld, n, nc, (void*)s);
-    else return hs_ldiv_dev_t_d(F, trans, out, ld, in, ld, n, nc, (void*)s);
+    return hs_block_apply_dev<T>(F, HS_VIA_COLS_T, trans, out, ld, in, ld, n, nc, s);
   }
 };
 
@@ -576,12 +553,6 @@ int64_t group_width(size_t per_col, int64_t nrhs) {
   return std::max<int64_t>(fit / KC * KC, std::min<int64_t>(KC, nrhs));
 }
 
-template <class T>
-int refused_by_block_solve(hs_handle* F, int trans, int64_t n) {  // zero columns: the checks of the block solve and nothing else
-  if (trans == 0) return sizeof(T) == 16 ? hs_ldiv_block_dev_z(F, 0, nullptr, n, nullptr, n, n, 0, nullptr) : hs_ldiv_block_dev_d(F, 0, nullptr, n, nullptr, n, n, 0, nullptr);
-  return sizeof(T) == 16 ? hs_ldiv_block_dev_t_z(F, trans, nullptr, n, nullptr, n, n, 0, nullptr) : hs_ldiv_block_dev_t_d(F, trans, nullptr, n, nullptr, n, n, 0, nullptr);
-}
-
 // the dimension test and the defaults every GMRES entry point applies after its own argument checks
 template <class T>
 void gmres_defaults(hs_handle* F, int64_t n, int64_t* restart, int64_t* maxiter, double* reltol) {
@@ -730,6 +701,9 @@ void gmres_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int64_t* 
   if (n <= 0 || !colptr || !rowval || !nz || !b || !x || !iters || !converged)
     HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_gmres needs A (CSC), b, x and the two result slots");
   gmres_defaults<T>(F, n, &restart, &maxiter, &reltol);
+  // hs_ulv_mode 1 on a handle with HSS interior blocks: what hs_ldiv_ulv_dev_* refuses is refused here, before any device work (mode 0 keeps
+  // its order of events: hs_ldiv_dev_* speaks inside the run, as it always did)
+  if (hs_ulv_routed(F)) HS_CHECK(hs_block_probe<T>(F, HS_VIA_COLS, 0));
   gmres_one_run<T>(csr_op_of<T>(n, colptr, rowval, nz), PrecFwd<T>{F}, n, b, x, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);
 }
 
@@ -751,15 +725,10 @@ void gmres_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colptr, co
 }
 
 // What the block solve refuses is refused before any device work, so nothing is silently looped: an "unsupported" is reworded for the caller
-// of `fn` (`hint` says who serves such a handle), any other status travels on as it is.
+// of `fn` (`hint` says who serves such a handle), any other status travels on as it is (hs_block_apply.h).
 template <class T>
-void refuse_what_block_solve_refuses(hs_handle* F, int trans, int64_t n, const char* fn, const char* hint) {
-  const int st = refused_by_block_solve<T>(F, trans, n);
-  if (st == HS_ERR_UNSUPPORTED) {
-    const std::string why = hs_last_error();
-    HS_FAIL(st, hs_last_error_info(), "%s: the block solve does not serve this preconditioner (%s)%s", fn, why.c_str(), hint);
-  }
-  HS_CHECK(st);
+void refuse_what_block_solve_refuses(hs_handle* F, int trans, const char* fn, const char* hint) {
+  hs_block_probe_or_fail<T>(F, trans == 0 ? HS_VIA_BLOCK : HS_VIA_BLOCK_T, trans, fn, "preconditioner", hint, true);
 }
 
 template <class T>
@@ -771,7 +740,8 @@ void gmres_block_entry(hs_handle* F, int64_t n, const int64_t* colptr, const int
     return;
   }
   gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged);
-  if (F) refuse_what_block_solve_refuses<T>(F, 0, n, "hs_gmres_block_*", "; hs_gmres_* serves it, one right-hand side at a time");
+  // (the hint is true only while hs_gmres_* takes another route than this call: with hs_ulv_mode 1 both go through hs_ldiv_ulv_dev_*)
+  if (F) refuse_what_block_solve_refuses<T>(F, 0, "hs_gmres_block_*", hs_ulv_routed(F) ? "" : "; hs_gmres_* serves it, one right-hand side at a time");
   gmres_block_run<T>(csr_op_of<T>(n, colptr, rowval, nz), PrecBlockFwd<T>{F}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged,
                      stream);
 }
@@ -793,7 +763,7 @@ void gmres_block_t_entry(hs_handle* F, int trans, int64_t n, const int64_t* colp
   }
   gmres_block_check<T>(F, n, B, ldb, X, ldx, where, &restart, &maxiter, &reltol, iters, converged);
   if (own) HS_CHECK(hs_gmres_own_check(F, "hs_gmres_block_t_*", 1));
-  if (F) refuse_what_block_solve_refuses<T>(F, trans, n, "hs_gmres_block_t_*", "");  // (whatever trans is)
+  if (F) refuse_what_block_solve_refuses<T>(F, trans, "hs_gmres_block_t_*", "");  // (whatever trans is)
   if (own) HS_CHECK(hs_gmres_own_check(F, "hs_gmres_block_t_*", 0));
   auto make_op = [&](HsDevBuf& buf, hipStream_t s) { return RowsSpmm<T>{gm_rows_of_op<T>(buf, F, trans, own, n, colptr, rowval, nz, s)}; };
   gmres_block_run<T>(make_op, PrecBlockOp<T>{F, trans}, n, B, ldb, X, ldx, nrhs, where, use_x0, reltol, abstol, restart, maxiter, resnorm, iters, converged, stream);

@@ -28,6 +28,7 @@
 #include "hs_common.h"
 #define HS_CONDEST_KERNELS  // hs_ce::csr_of; switches contraction off for the rest of this file (host arithmetic only: no kernel lives here)
 #include "hs_condest.h"
+#include "hs_block_apply.h"
 #include "hs_solve_multi.h"  // hs_ldiv_block_cols
 #include "hs_sens.h"
 #include "hs_sens_solve.h"

@@ -35,6 +35,7 @@
 #include "hs_host.h"
 #include "hs_lowrank.h"
 #include "hs_sched.h"
+#include "hs_selinv.h"
 #include "hs_ulv_t.h"
 
 namespace {
@@ -3724,6 +3725,35 @@ static int hss_ldiv_abi(const char* name, hs_hss* H, int trans, double* B, int64
 extern "C" int hs_hss_ldiv(hs_hss* H, double* B, int64_t ldb, int64_t nrhs, int where) { return hss_ldiv_abi("hs_hss_ldiv", H, 0, B, ldb, nrhs, where); }
 extern "C" int hs_hss_ldiv_t(hs_hss* H, int trans, double* B, int64_t ldb, int64_t nrhs, int where) {
   return hss_ldiv_abi("hs_hss_ldiv_t", H, trans, B, ldb, nrhs, where);
+}
+
+// det H from the ULV factors (include/hs_hss.h): the eliminated nodes in node order, the root's LU last, one grouped launch
+template <class T>
+static void hss_logabsdet(const HssT<T>& H, double* logabs, double* sign_re, double* sign_im) {
+  if (!H.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_logabsdet: the matrix is not eliminated (hs_hss_factor)");
+  std::vector<LogdetFront> ln;
+  for (const HNode<T>& x : H.nd)
+    if (x.has_front) ln.push_back(LogdetFront{x.fd.LF, x.fd.rperm, x.fd.ni, x.fd.ldl});
+  ln.push_back(LogdetFront{H.rootfd.LF, H.rootfd.rperm, H.rootfd.ni, H.rootfd.ldl});
+  const int nn = (int)ln.size();
+  Pool tmp(global_cache());
+  const LogdetFront* dn = upload(tmp, ln, H.s);
+  LogdetOut* dout = tmp.get<LogdetOut>((size_t)nn);
+  launch_ulv_det<T>(dn, nn, dout, H.s);
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipStreamSynchronize(H.s));
+  std::vector<LogdetOut> out((size_t)nn);
+  HS_HIP(hipMemcpy(out.data(), dout, sizeof(LogdetOut) * (size_t)nn, hipMemcpyDeviceToHost));
+  LogdetAcc acc;
+  for (const LogdetOut& o : out) acc.add(o);
+  acc.finish(sizeof(T) != sizeof(double), logabs, sign_re, sign_im);
+}
+extern "C" int hs_hss_logabsdet(const hs_hss* H, double* logabs, double* sign_re, double* sign_im) {
+  if (!H || !logabs || !sign_re || !sign_im) {
+    hs_set_error(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_hss_logabsdet: H, logabs, sign_re and sign_im must not be NULL");
+    return HS_ERR_ARGUMENT;
+  }
+  HS_GUARD(if (H->is_complex) hss_logabsdet<cplx>(*HZ(H), logabs, sign_re, sign_im); else hss_logabsdet<double>(*HD(H), logabs, sign_re, sign_im));
 }
 
 extern "C" void hs_hss_free(hs_hss* H) {

@@ -32,6 +32,7 @@
 #define HS_CONDEST_KERNELS
 #include "hs_condest.h"  // switches fma contraction off for the rest of this file
 #include "hs_normest.h"
+#include "hs_block_apply.h"
 #include "hs_solve_multi.h"
 
 #define RB_T 2      // estimator columns per right-hand side: t = min(2, n)
@@ -194,10 +195,7 @@ struct Driver {
   HostIo io{F, s};
 
   void bsolve(int tr, T* X, int64_t ld, int64_t nc) {
-    if (sizeof(T) == 16)
-      HS_CHECK(hs_ldiv_block_dev_t_z(F, tr, (double*)X, ld, (const double*)X, ld, v.n, nc, (void*)s));
-    else
-      HS_CHECK(hs_ldiv_block_dev_t_d(F, tr, (double*)X, ld, (const double*)X, ld, v.n, nc, (void*)s));
+    HS_CHECK(hs_block_apply_dev<T>(F, HS_VIA_BLOCK_T, tr, X, ld, (const T*)X, ld, v.n, nc, s));
     g_info[RI_SOLVES] += 1;
     g_info[RI_COL_APPS] += (double)nc;
   }
@@ -357,21 +355,15 @@ void refine_block_entry(hs_handle* F, int trans, T* X, int64_t ldx, const T* B, 
   // what hs_ldiv_block_t_* refuses, whatever trans and ferr are (a host-side plan names these too)
   if (v.nranks > 1)
     HS_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: a factorization over %d ranks is not supported (single-rank factorizations only)", fn, v.nranks);
-  if (v.t_refused_node >= 0)
+  if (v.t_refused_node >= 0 && !v.ulv)  // (hs_ulv_mode 1: the router below serves these fronts)
     HS_FAIL(HS_ERR_UNSUPPORTED, v.t_refused_node,
             "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): block solves and transposed ULV solves are not implemented; "
             "hs_ldiv_refine_* serves this handle with trans = 0 and without ferr",
             fn, v.t_refused_node);
   if (!v.device) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
   if (!v.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
-  {  // whatever else the block solve refuses is refused here: nothing is silently looped
-    const int st = sizeof(T) == 16 ? hs_ldiv_block_dev_t_z(F, trans, nullptr, n, nullptr, n, n, 0, nullptr) : hs_ldiv_block_dev_t_d(F, trans, nullptr, n, nullptr, n, n, 0, nullptr);
-    if (st != HS_OK) {
-      const std::string why = hs_last_error();
-      hs_set_error(st, hs_last_error_info(), "%s: the block solve does not serve this handle (%s)", fn, why.c_str());
-      throw st;
-    }
-  }
+  // whatever else the block solve refuses is refused here: nothing is silently looped
+  hs_block_probe_or_fail<T>(F, HS_VIA_BLOCK_T, trans, fn, "handle", "", false);
   for (double& x : g_info) x = 0.0;
   if (nrhs == 0) return;
   HsDevBuf buf("condest workspace");  // freed after the stream is drained, on every path

@@ -3,11 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
+#include <limits>
 #include <vector>
 
 #include "hs_common.h"
 
 struct hs_handle;
+struct hs_hss;
 
 enum {
   HS_SEL_NOLU = 1,     // D = Aii is kept as an HSS matrix (hss_d, mf = 2, 3): there is no pivoted LU to read
@@ -31,11 +34,17 @@ struct HsSelFront {          // one owned front, every pointer a device pointer
   // Lbi ~= C_L Z_L' (lrL: Cd nb x rL, Z rL x ni) and Uib ~= G Z_R (lrR: Cd ni x rR, Z rR x nb); null: dense front, or a front the call refuses
   const void* lrL = nullptr;
   const void* lrR = nullptr;
+  // HS_SEL_NOLU only (hs_logabsdet with hs_ulv_mode 1): D as an eliminated HSS matrix; mfb: the 2 x 2 block form of mf = 3, D = [A11 A12; A21 A22]
+  // with hss = A11 and hss2 = S22 (null while the factorization is incomplete)
+  const hs_hss* hss = nullptr;
+  const hs_hss* hss2 = nullptr;
+  int mfb = 0;
 };
 
 struct HsSelView {
   int64_t n = 0, nnz = 0;
   int is_complex = 0, factored = 0, device = 0, nranks = 1;
+  int ulv_mode = 0;                // hs_ulv_mode
   std::vector<HsSelFront> fronts;  // tree nodes in post-order (children before parents), the pseudo-root last
   const int* fidx_host = nullptr;
   const int64_t* colptr = nullptr;  // A's pattern on the device, 0-based
@@ -61,6 +70,46 @@ struct LogdetOut {  // per front: sum log|u_kk|, sum arg(u_kk) (Float64: pi per 
 };
 template <class T>
 void launch_logdet(const LogdetFront* df, int nfronts, LogdetOut* out, hipStream_t s);
+// the same per-node figures for the fronts of a ULV elimination (hs_hss_logabsdet): the nodes of an HSS tree are small and many, so a
+// workgroup is one wave-reduced pass; ni = 0 (a node that eliminates nothing) gives the neutral element
+template <class T>
+void launch_ulv_det(const LogdetFront* df, int nnodes, LogdetOut* out, hipStream_t s);
+// the host side of both launches: the per-front results are added in the order they are given, always the same
+struct LogdetAcc {
+  double la = 0.0, ang = 0.0;
+  long long flips = 0;
+  bool zero = false;
+  void add(const LogdetOut& o) {
+    const double twopi = 6.283185307179586476925286766559;
+    la += o.logabs;
+    ang = std::remainder(ang + std::remainder(o.angle, twopi), twopi);
+    flips += o.neg + o.odd;
+    zero = zero || o.zero != 0;
+  }
+  void add(double logabs, double sign_re, double sign_im) {  // a finished factor: (log|d|, d / |d|)
+    if (sign_re == 0.0 && sign_im == 0.0) { zero = true; return; }
+    LogdetOut o{logabs, 0.0, 0, 0, 0, 0};
+    if (sign_im == 0.0) o.neg = sign_re < 0.0 ? 1 : 0;
+    else o.angle = std::atan2(sign_im, sign_re);
+    add(o);
+  }
+  void finish(bool is_complex, double* logabs, double* sign_re, double* sign_im) const {
+    if (zero) {
+      *logabs = -std::numeric_limits<double>::infinity();
+      *sign_re = *sign_im = 0.0;
+      return;
+    }
+    *logabs = la;
+    if (!is_complex) {
+      *sign_re = (flips & 1) ? -1.0 : 1.0;
+      *sign_im = 0.0;
+    } else {
+      const double a = (flips & 1) ? ang + 3.14159265358979323846264338327950288 : ang;
+      *sign_re = std::cos(a);
+      *sign_im = std::sin(a);
+    }
+  }
+};
 
 template <class T>
 struct SelDesc {  // one front of a selected-inversion batch

@@ -32,6 +32,7 @@
 #include <new>
 #include <vector>
 
+#include "../../include/hs_hss.h"
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
 #include "hs_host.h"
@@ -174,15 +175,22 @@ void build_cache(const HsSelView& v, SelCache* c) {
 }
 
 // ---- checks shared by the entry points: everything here happens before any device work ---------------------------------------------
-void check_common(hs_handle* F, HsSelView& v, const char* fn) {
+// ulv_ok: the caller serves fronts whose D is an eliminated HSS matrix when the handle's hs_ulv_mode is 1 (hs_logabsdet only)
+void check_common(hs_handle* F, HsSelView& v, const char* fn, bool ulv_ok = false) {
   if (!F) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
   hs_selinv_view(F, &v);
   if (v.nranks > 1)
     HS_FAIL(HS_ERR_UNSUPPORTED, v.nranks, "%s: the factorization is spread over %d ranks; this call needs all fronts in one process", fn, v.nranks);
   if (!v.device || !v.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs a completed numeric factorization (the handle is a plan, or hs_numeric_end has not run)", fn);
-  for (size_t i = 0; i < v.fronts.size(); ++i)
-    if (v.fronts[i].flags & HS_SEL_NOLU)
-      HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d keeps its interior block D as an HSS matrix (ULV factors; hs_options.hss_d, mf = 2, 3): it has no pivoted LU whose diagonal could be read", fn, (int)i);
+  for (size_t i = 0; i < v.fronts.size(); ++i) {
+    if (!(v.fronts[i].flags & HS_SEL_NOLU)) continue;
+    if (ulv_ok && v.ulv_mode == 1) {
+      if (!v.fronts[i].hss || (v.fronts[i].mfb && !v.fronts[i].hss2))
+        HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d has no eliminated interior block (incomplete factorization)", fn, (int)i);
+      continue;
+    }
+    HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: front %d keeps its interior block D as an HSS matrix (ULV factors; hs_options.hss_d, mf = 2, 3): it has no pivoted LU whose diagonal could be read", fn, (int)i);
+  }
 }
 
 // ---- log-determinant ------------------------------------------------------------------------------------------------------------------
@@ -190,11 +198,9 @@ template <class T>
 void logabsdet_impl(const HsSelView& v, double* logabs, double* sign2) {
   std::vector<LogdetFront> lf;
   for (const HsSelFront& x : v.fronts)
-    if (x.ni > 0) lf.push_back(LogdetFront{x.LU, x.rperm, x.ni, x.ldlu});
+    if (x.ni > 0 && !(x.flags & HS_SEL_NOLU)) lf.push_back(LogdetFront{x.LU, x.rperm, x.ni, x.ldlu});
   const int nf = (int)lf.size();
-  double la = 0.0, ang = 0.0;
-  long long flips = 0;
-  bool zero = false;
+  LogdetAcc acc;
   if (nf > 0) {
     HsScratch din, dout;
     din.take(sizeof(LogdetFront) * (size_t)nf, "log-determinant descriptors");
@@ -206,28 +212,20 @@ void logabsdet_impl(const HsSelView& v, double* logabs, double* sign2) {
     HS_HIP(hipGetLastError());
     HS_HIP(hipStreamSynchronize(v.stream));
     HS_HIP(hipMemcpy(out.data(), dout.p, sizeof(LogdetOut) * (size_t)nf, hipMemcpyDeviceToHost));
-    const double twopi = 6.283185307179586476925286766559;
-    for (int i = 0; i < nf; ++i) {  // post-order, always the same
-      la += out[(size_t)i].logabs;
-      ang = std::remainder(ang + std::remainder(out[(size_t)i].angle, twopi), twopi);
-      flips += out[(size_t)i].neg + out[(size_t)i].odd;
-      zero = zero || out[(size_t)i].zero != 0;
+    for (int i = 0; i < nf; ++i) acc.add(out[(size_t)i]);  // post-order, always the same
+  }
+  // hs_ulv_mode 1 (check_common let them through): a front whose D is an eliminated HSS matrix adds det D from its ULV factors, after the
+  // fronts above and in post-order; the 2 x 2 block form of mf = 3 is det D = det(A11) det(S22)
+  for (const HsSelFront& x : v.fronts) {
+    if (!(x.flags & HS_SEL_NOLU) || x.ni <= 0) continue;
+    for (const hs_hss* H : {x.hss, x.hss2}) {
+      if (!H) continue;
+      double l = 0.0, sr = 0.0, si = 0.0;
+      HS_CHECK(hs_hss_logabsdet(H, &l, &sr, &si));
+      acc.add(l, sr, si);
     }
   }
-  if (zero) {
-    *logabs = -std::numeric_limits<double>::infinity();
-    sign2[0] = sign2[1] = 0.0;
-    return;
-  }
-  *logabs = la;
-  if (sizeof(T) == sizeof(double)) {
-    sign2[0] = (flips & 1) ? -1.0 : 1.0;
-    sign2[1] = 0.0;
-  } else {
-    if (flips & 1) ang += 3.14159265358979323846264338327950288;
-    sign2[0] = std::cos(ang);
-    sign2[1] = std::sin(ang);
-  }
+  acc.finish(sizeof(T) != sizeof(double), logabs, &sign2[0], &sign2[1]);
 }
 
 // ---- selected inversion ---------------------------------------------------------------------------------------------------------------
@@ -683,7 +681,7 @@ void selinv_impl(const HsSelView& v, SelCache* c, bool lrmode, int trans, void* 
 }  // namespace
 
 extern "C" int hs_logabsdet(hs_handle* F, double* logabs, double* sign2) {
-  HS_GUARD(HsSelView v; check_common(F, v, "hs_logabsdet");
+  HS_GUARD(HsSelView v; check_common(F, v, "hs_logabsdet", true);
            if (!logabs || !sign2) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_logabsdet: logabs and sign2 must not be NULL");
            if (v.is_complex) logabsdet_impl<cplx>(v, logabs, sign2); else logabsdet_impl<double>(v, logabs, sign2));
 }

@@ -31,6 +31,7 @@
 #include "../../include/hs_solver.h"
 #include "hs_common.h"
 #include "hs_host.h"
+#include "hs_block_apply.h"
 #pragma clang fp contract(off)  // host arithmetic only (no kernel lives here): the plain products and sums
 #include "hs_solve_multi.h"  // hs_ldiv_block_cols
 #include "hs_sens.h"
@@ -83,6 +84,7 @@ struct Driver {
     gs.n = n;
     gs.itmax = c.itmax;
     gs.s = s;
+    gs.ulv = c.v.ulv != 0;
     const bool cplx_ = sizeof(T) == 16;
     const bool cjw = cplx_ && c.trans == 1;  // the adjoint solve runs on conj(W) and returns conj(Lam)
     const int tadj = c.trans == 0 ? 2 : 0;
@@ -93,7 +95,8 @@ struct Driver {
       return;
     }
     const bool wsparse = c.misfit || c.W.sparse();
-    const bool need_stage = c.itmax > 0 && (c.B.sparse() || wsparse || cjw);
+    const bool expand = c.itmax > 0 || gs.ulv;  // sparse blocks reach their solve as dense ones
+    const bool need_stage = expand && (c.B.sparse() || wsparse || (cjw && c.itmax > 0));
     const size_t per_col = (size_t)n * sizeof(T) * (need_stage ? 3 : 2) + (c.misfit ? (size_t)c.nrows * sizeof(T) : 0);
     Gc = std::min<int64_t>(group_width(per_col, c.nrhs, "HS_SENS_GROUP", "hs_sens_*"), c.nrhs);
     Xg = buf.get<T>((size_t)n * Gc);
@@ -108,11 +111,11 @@ struct Driver {
     }
     if (c.misfit) maxw = c.nrows * Gc;
     maxe = std::max(maxe, maxw);
-    if (cjw && !c.misfit && c.W.sparse() && c.itmax == 0) {
+    if (cjw && !c.misfit && c.W.sparse() && !expand) {
       gs.vstage = buf.get<T>((size_t)maxw);
       extra += (size_t)maxw * sizeof(T);
     }
-    if (c.itmax > 0 && (c.B.sparse() || wsparse)) {
+    if (expand && (c.B.sparse() || wsparse)) {
       gs.d_er = buf.get<int32_t>((size_t)maxe);
       gs.d_ec = buf.get<int32_t>((size_t)maxe);
       extra += (size_t)maxe * 2 * sizeof(int32_t);
@@ -166,6 +169,16 @@ struct Driver {
   }
 };
 
+// hs_ulv_mode 1 on a handle with HSS interior blocks: the caller's sparse blocks stay refused -- they are solved by the pruned sweeps of
+// hs_ldiv_sparse_*, which run no HSS hook
+void check_dense_under_ulv(const HsHandleView& v, const char* fn, const char* name, const hs_block_arg* b, int64_t nrhs) {
+  if (v.ulv && nrhs > 0 && !b->dense)
+    HS_FAIL(HS_ERR_UNSUPPORTED, v.t_refused_node,
+            "%s: %s is a sparse block, and node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): with hs_ulv_mode 1 the ULV block solve "
+            "serves dense blocks only (sparse blocks are solved on pruned tree paths, which run no ULV solves); pass %s dense",
+            fn, name, v.t_refused_node, name);
+}
+
 void finish(hs_handle* F, const double* info) { memcpy(hs_handle_sens_info(F), info, 8 * sizeof(double)); }
 
 template <class T>
@@ -173,9 +186,11 @@ void sens_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_block
                 int64_t ldl, bool on_device, void* stream) {
   const char* fn = on_device ? "hs_sens_dev_*" : "hs_sens_*";
   Call<T> c;
-  check_common<T>(F, fn, trans, n, nrhs, itmax, pattern, &c.v);
+  check_common<T>(F, fn, trans, n, nrhs, itmax, pattern, &c.v, true);
   check_block<T>(F, trans, fn, "B", B, n, nrhs);
   check_block<T>(F, trans, fn, "W", W, n, nrhs);
+  check_dense_under_ulv(c.v, fn, "B", B, nrhs);
+  check_dense_under_ulv(c.v, fn, "W", W, nrhs);
   if (!G) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: G == NULL", fn);
   if ((X && ldx < n) || (Lam && ldl < n)) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: ldx = %lld, ldl = %lld, the blocks have %lld rows", fn, (long long)ldx, (long long)ldl, (long long)n);
   c.F = F; c.trans = trans; c.pattern = pattern; c.n = n; c.nrhs = nrhs; c.itmax = itmax;
@@ -216,8 +231,9 @@ void misfit_entry(hs_handle* F, int trans, int64_t n, int64_t nrhs, const hs_blo
                   int pattern, double* J, T* R, int64_t ldr, T* G, bool on_device, void* stream) {
   const char* fn = on_device ? "hs_misfit_dev_*" : "hs_misfit_*";
   Call<T> c;
-  check_common<T>(F, fn, trans, n, nrhs, itmax, pattern, &c.v);
+  check_common<T>(F, fn, trans, n, nrhs, itmax, pattern, &c.v, true);
   check_block<T>(F, trans, fn, "B", B, n, nrhs);
+  check_dense_under_ulv(c.v, fn, "B", B, nrhs);
   if (nrows < 0 || nrows > n) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: nrows = %lld, F is %lld x %lld", fn, (long long)nrows, (long long)n, (long long)n);
   if (!G || (nrows > 0 && !rows) || (nrhs > 0 && !J) || (nrows > 0 && nrhs > 0 && !D)) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: G, rows, D and J must not be NULL", fn);
   if (ldd < nrows || (R && ldr < nrows))

@@ -1,7 +1,7 @@
 // hs_sens_solve.h -- what the two column-group drivers over the stored factorization share (hs_sens.hip: hs_sens_*, hs_misfit_*; hs_gn.hip:
 // hs_tangent_*, hs_gn_hessvec_*, hs_gn_diag_*): the block argument, the choice among the library's own solves for one group of columns with
 // its staging, the group width, the receiver rows as a sparse cotangent, and the refusals both word alike.  Host code only, internal
-// linkage; include it after hs_solver.h, hs_common.h, hs_host.h, hs_solve_multi.h and hs_sens.h.
+// linkage; include it after hs_solver.h, hs_common.h, hs_host.h, hs_block_apply.h, hs_solve_multi.h and hs_sens.h.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -22,8 +22,11 @@ struct Blk {  // an n x nrhs block: the values on the device, the index arrays o
   int64_t nnz(int64_t c0, int64_t c1) const { return colptr[c1] - colptr[c0]; }
 };
 
+// the block application of op(F)^-1 (hs_block_apply.h).  ulv: the driver serves handles whose hs_ulv_mode reroutes it (hs_sens.hip); a
+// driver that does not (hs_gn.hip) keeps hs_ldiv_block_dev_t_* and its refusals in either mode
 template <class T>
-int block_solve(hs_handle* F, int t, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nc, hipStream_t s) {
+int block_solve(hs_handle* F, bool ulv, int t, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nc, hipStream_t s) {
+  if (ulv) return hs_block_apply_dev<T>(F, HS_VIA_BLOCK_T, t, C, ldc, B, ldb, n, nc, s);
   if (sizeof(T) == 16) return hs_ldiv_block_dev_t_z(F, t, (double*)C, ldc, (const double*)B, ldb, n, nc, (void*)s);
   return hs_ldiv_block_dev_t_d(F, t, (double*)C, ldc, (const double*)B, ldb, n, nc, (void*)s);
 }
@@ -65,6 +68,7 @@ struct HsGroupSolve {
   hs_handle* F = nullptr;
   int64_t n = 0, itmax = 0;
   hipStream_t s = nullptr;
+  bool ulv = false;         // the handle's hs_ulv_mode reroutes this driver (HsHandleView::ulv): block_solve above, sparse blocks expanded
   T* stage = nullptr;       // n x Gc: the dense right-hand side of a refined solve that is not the caller's block as it stands
   T* vstage = nullptr;      // conjugated values of a sparse block (itmax = 0)
   int32_t* d_er = nullptr;  // entries of a sparse group for the expansion (itmax > 0)
@@ -83,14 +87,14 @@ struct HsGroupSolve {
       cp.resize((size_t)gc + 1);
       for (int j = 0; j <= gc; ++j) cp[(size_t)j] = b.colptr[g0 + j] - off;
     }
-    if (itmax == 0) {
+    if (itmax == 0 && !(ulv && b.sparse())) {
       if (!b.sparse()) {
         const T* src = b.dense + (size_t)g0 * b.ld;
         if (cjin) {
           launch_sens_copy<T>(out, n, src, b.ld, n, gc, 1, s);
-          HS_CHECK(block_solve<T>(F, t, out, n, out, n, n, gc, s));
+          HS_CHECK(block_solve<T>(F, ulv, t, out, n, out, n, n, gc, s));
         } else {
-          HS_CHECK(block_solve<T>(F, t, out, n, src, b.ld, n, gc, s));
+          HS_CHECK(block_solve<T>(F, ulv, t, out, n, src, b.ld, n, gc, s));
         }
         return;
       }
@@ -128,6 +132,10 @@ struct HsGroupSolve {
           launch_sens_expand<T>(stage, n, d_er, d_ec, b.nzval + off, cnt, cjin ? 1 : 0, s);
         }
       }
+    }
+    if (itmax == 0) {  // (ulv: a sparse block of the driver's own, expanded above -- the pruned sweeps run no HSS hook)
+      HS_CHECK(block_solve<T>(F, ulv, t, out, n, src, lds, n, gc, s));
+      return;
     }
     berr.resize((size_t)gc);
     steps.resize((size_t)gc);
@@ -194,7 +202,7 @@ void check_block(hs_handle* F, int trans, const char* fn, const char* name, cons
 }
 
 template <class T>
-void check_common(hs_handle* F, const char* fn, int trans, int64_t n, int64_t nrhs, int64_t itmax, int pattern, HsHandleView* v) {
+void check_common(hs_handle* F, const char* fn, int trans, int64_t n, int64_t nrhs, int64_t itmax, int pattern, HsHandleView* v, bool ulv = false) {
   *v = hs_view_of(F, fn);
   if ((v->is_complex != 0) != (sizeof(T) == 16)) HS_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and of the blocks differ", fn);
   hs_check_trans(fn, trans);
@@ -203,7 +211,7 @@ void check_common(hs_handle* F, const char* fn, int trans, int64_t n, int64_t nr
   if (!v->device) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: handle holds a host-side plan only (hs_plan)", fn);
   if (!v->factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
   {  // what hs_ldiv_block_t_* refuses is refused here, by its own check: a block solve of no columns
-    const int st = block_solve<T>(F, trans, nullptr, v->n, nullptr, v->n, v->n, 0, nullptr);
+    const int st = block_solve<T>(F, ulv, trans, nullptr, v->n, nullptr, v->n, v->n, 0, nullptr);
     if (st != HS_OK) {
       const std::string why = hs_last_error();
       hs_set_error(st, hs_last_error_info(), "%s: the block solve does not serve this handle (%s)", fn, why.c_str());

@@ -1487,3 +1487,61 @@ extern "C" int hsk_lu_product_d(int64_t nb, const double* LF, int64_t ldl, const
 extern "C" int hsk_lu_product_z(int64_t nb, const double* LF, int64_t ldl, const int32_t* rperm, double* S, int64_t lds, double* flops_out) {
   HS_GUARD(lu_product_hook<cplx>(nb, (const cplx*)LF, ldl, (const int32_t*)rperm, (cplx*)S, lds, flops_out));
 }
+
+// ---- hs_hss_logabsdet: the per-node determinant reduction of the ULV factors (kernels_selinv.hip: ulv_det_kernel) on host data ----------------
+#include "hs_selinv.h"
+template <class T>
+static void ulv_det_hook(int64_t nnodes, const int64_t* ni, const int64_t* ld, const T* LU, const int32_t* rperm, double* out2, int32_t* flags3, double* res3) {
+  bool ok = nnodes >= 1 && nnodes <= 65535 && ni && ld && out2 && flags3 && res3;
+  size_t nlu = 0, np = 0;
+  for (int64_t k = 0; ok && k < nnodes; ++k) {
+    ok = ni[k] >= 0 && ni[k] <= (1 << 20) && ld[k] >= std::max<int64_t>(ni[k], 1);
+    if (!ok) break;
+    std::vector<char> seen((size_t)ni[k], 0);
+    for (int64_t i = 0; ok && i < ni[k]; ++i) {
+      const int32_t q = rperm[np + (size_t)i];
+      ok = q >= 0 && q < ni[k] && !seen[(size_t)q];
+      if (ok) seen[(size_t)q] = 1;
+    }
+    nlu += (size_t)ld[k] * (size_t)ni[k];
+    np += (size_t)ni[k];
+  }
+  if (!ok || (nlu > 0 && (!LU || !rperm)))
+    HS_FAIL(HS_ERR_ARGUMENT, 0, "hsk_ulv_det: 1..65535 nodes, ni >= 0, ld >= max(ni, 1), non-null arrays and every rperm a permutation of 0..ni-1 required");
+  need_device();
+  HsDevBuf b("hsk_ulv_det");
+  T* dL = b.get<T>(std::max<size_t>(nlu, 1));
+  int* dp = b.get<int>(std::max<size_t>(np, 1));
+  LogdetFront* dn = b.get<LogdetFront>((size_t)nnodes);
+  LogdetOut* dout = b.get<LogdetOut>((size_t)nnodes);
+  if (nlu > 0) HS_HIP(hipMemcpy(dL, LU, sizeof(T) * nlu, hipMemcpyHostToDevice));
+  if (np > 0) HS_HIP(hipMemcpy(dp, rperm, sizeof(int) * np, hipMemcpyHostToDevice));
+  std::vector<LogdetFront> hn((size_t)nnodes);
+  size_t ol = 0, op = 0;
+  for (int64_t k = 0; k < nnodes; ++k) {
+    hn[(size_t)k] = LogdetFront{dL + ol, dp + op, (int)ni[k], (int)ld[k]};
+    ol += (size_t)ld[k] * (size_t)ni[k];
+    op += (size_t)ni[k];
+  }
+  HS_HIP(hipMemcpy(dn, hn.data(), sizeof(LogdetFront) * (size_t)nnodes, hipMemcpyHostToDevice));
+  HS_HIP(hipMemset(dout, 0xff, sizeof(LogdetOut) * (size_t)nnodes));  // an unwritten result shows
+  launch_ulv_det<T>(dn, (int)nnodes, dout, 0);
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipDeviceSynchronize());
+  std::vector<LogdetOut> out((size_t)nnodes);
+  HS_HIP(hipMemcpy(out.data(), dout, sizeof(LogdetOut) * (size_t)nnodes, hipMemcpyDeviceToHost));
+  LogdetAcc acc;
+  for (int64_t k = 0; k < nnodes; ++k) {
+    const LogdetOut& o = out[(size_t)k];
+    out2[2 * k] = o.logabs; out2[2 * k + 1] = o.angle;
+    flags3[3 * k] = o.neg; flags3[3 * k + 1] = o.odd; flags3[3 * k + 2] = o.zero;
+    acc.add(o);
+  }
+  acc.finish(sizeof(T) != sizeof(double), &res3[0], &res3[1], &res3[2]);
+}
+extern "C" int hsk_ulv_det_d(int64_t nnodes, const int64_t* ni, const int64_t* ld, const double* LU, const int32_t* rperm, double* out2, int32_t* flags3, double* res3) {
+  HS_GUARD(ulv_det_hook<double>(nnodes, ni, ld, LU, rperm, out2, flags3, res3));
+}
+extern "C" int hsk_ulv_det_z(int64_t nnodes, const int64_t* ni, const int64_t* ld, const double* LU, const int32_t* rperm, double* out2, int32_t* flags3, double* res3) {
+  HS_GUARD(ulv_det_hook<cplx>(nnodes, ni, ld, (const cplx*)LU, rperm, out2, flags3, res3));
+}

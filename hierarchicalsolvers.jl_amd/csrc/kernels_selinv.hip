@@ -80,6 +80,49 @@ void launch_logdet(const LogdetFront* df, int nfronts, LogdetOut* out, hipStream
 template void launch_logdet<double>(const LogdetFront*, int, LogdetOut*, hipStream_t);
 template void launch_logdet<cplx>(const LogdetFront*, int, LogdetOut*, hipStream_t);
 
+// The determinant of a ULV-eliminated HSS matrix (hs_hss_logabsdet): det H = det(root LU) * prod over the eliminated nodes of det(X_RR),
+// every factor read from the diagonal of a node's pivoted LU and the parity of its rperm, as above.  The nodes of an HSS tree are many and
+// small (at most a leaf size of eliminated rows each, the root a few ranks), so a node is one wave: lane l walks the diagonal entries
+// l, l + 64, ... in order, and the 64 partial results meet in the fixed shuffle tree below -- no LDS, no barrier, no atomics, and two
+// calls return the same bits.  ni = 0 writes the neutral element.
+template <class T>
+__global__ __launch_bounds__(64) void ulv_det_kernel(const LogdetFront* __restrict__ nodes, LogdetOut* __restrict__ out) {
+  const LogdetFront f = nodes[blockIdx.x];
+  const T* LU = (const T*)f.LU;
+  const int l = threadIdx.x;
+  double la = 0.0, ang = 0.0;
+  int neg = 0, cyc = 0, zero = 0;
+  for (int i = l; i < f.ni; i += 64) {
+    logdet_term<T>(gld(LU + (size_t)i * f.ld + i), la, ang, neg, zero);
+    int j = f.rperm[i], steps = 0;
+    while (j > i && j < f.ni && steps < f.ni) {  // (bounded, and an entry outside 0:ni-1 ends the walk: a corrupt list can neither hang nor stray)
+      j = f.rperm[j];
+      ++steps;
+    }
+    cyc += (j == i) ? 1 : 0;
+  }
+  for (int w = 32; w >= 1; w >>= 1) {
+    la += __shfl_down(la, w, 64);
+    ang += __shfl_down(ang, w, 64);
+    neg += __shfl_down(neg, w, 64);
+    cyc += __shfl_down(cyc, w, 64);
+    zero |= __shfl_down(zero, w, 64);
+  }
+  if (l == 0) {
+    LogdetOut o;
+    o.logabs = la; o.angle = ang; o.neg = neg; o.odd = (f.ni - cyc) & 1; o.zero = zero; o.pad = 0;
+    out[blockIdx.x] = o;
+  }
+}
+
+template <class T>
+void launch_ulv_det(const LogdetFront* dn, int nnodes, LogdetOut* out, hipStream_t s) {
+  if (nnodes <= 0) return;
+  hipLaunchKernelGGL(ulv_det_kernel<T>, dim3(nnodes), dim3(64), 0, s, dn, out);
+}
+template void launch_ulv_det<double>(const LogdetFront*, int, LogdetOut*, hipStream_t);
+template void launch_ulv_det<cplx>(const LogdetFront*, int, LogdetOut*, hipStream_t);
+
 // ------------------------------------------------------------------------------------------------
 // selected inversion
 // ------------------------------------------------------------------------------------------------

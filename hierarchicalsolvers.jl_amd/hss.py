@@ -195,6 +195,15 @@ class HssMatrix:
             _lib.check(self.L.hs_hss_ldiv_t(self._h, "NTC".index(trans), B2.ctypes.data_as(C.c_void_p), n, q, 0))
         return B2[:, 0] if one else B2
 
+    def logabsdet(self):
+        """``(sign, log|det H|)`` like ``numpy.linalg.slogdet``, from the ULV factors (``hs_hss_logabsdet``; the elimination is computed on
+        first use): ``sign`` is ``+-1.0`` for a real matrix and a unit complex number for a complex one, ``(0, -inf)`` with an exactly zero
+        pivot.  This is the determinant of the compressed matrix."""
+        self.factor()
+        la, sr, si = C.c_double(), C.c_double(), C.c_double()
+        _lib.check(self.L.hs_hss_logabsdet(self._h, C.byref(la), C.byref(sr), C.byref(si)))
+        return (complex(sr.value, si.value) if self.is_complex else sr.value), la.value
+
     def pack(self, device="cuda:0"):
         """The whole matrix in ONE device buffer (a ``torch.uint8`` tensor): what crosses ranks at a join when a child's Schur complement
         travels as an ``HssMatrix`` (src/factorization.jl:126-140 reads S1, S2 as HSS; include/hs_hss.h ``hs_hss_pack``)."""

@@ -35,7 +35,7 @@ from . import _lib
 from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
-           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "selinv", "selinv_diag", "selinv_info", "selinv_lr", "selinv_lr_diag", "selinv_lr_info", "sym_info",
+           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "ulv_mode", "selinv", "selinv_diag", "selinv_info", "selinv_lr", "selinv_lr_diag", "selinv_lr_info", "sym_info",
            "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "tangent", "gn_hessvec", "gn_diag", "gn_info", "eigs", "eigs_info", "eigs_gen_info", "interface_indices", "schur_complement", "condense", "interface_solve", "expand", "interface_info"]
 
 
@@ -1316,6 +1316,21 @@ def _unwrap(F):
     if not isinstance(F, FactorNode):
         raise TypeError(f"expected a FactorNode, got {type(F).__name__}")
     return F, 0
+
+
+def ulv_mode(F, on=None):
+    """The per-handle switch ``hs_ulv_mode``: with ``on=True`` :func:`gmres_block`, :func:`gmres`, :func:`ldiv_refine`,
+    :func:`ldiv_refine_block`, :func:`opnormestinv`, :func:`condest`, :func:`sensitivity` / :func:`misfit` (dense blocks) and
+    :func:`logabsdet` serve a handle whose fronts keep their interior block ``D`` as an HSS matrix (``hss_d``, ``mf = 2, 3``) through
+    the ULV block solve of :func:`ldiv_ulv`; with ``on=False`` (the default state of a handle) they refuse it as before.  A handle without
+    such fronts is not affected.  ``on=None`` only queries.  Returns the previous setting.  ``F``, ``transpose(F)`` and ``adjoint(F)``
+    are views of one handle and share the setting; do not change it while another thread is inside a call on that handle."""
+    F, _ = _unwrap(F)
+    mode = -1 if on is None else (1 if on else 0)
+    prev = int(_lib.lib().hs_ulv_mode(F._h, mode))
+    if prev < 0:
+        _lib.check(prev)
+    return bool(prev)
 
 
 def _pcode(p):

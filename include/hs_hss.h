@@ -184,6 +184,13 @@ int hs_hss_ldiv(hs_hss* H, double* B, int64_t ldb, int64_t nrhs, int where);
  * E^T = F, and the local matrix M = E^-1 X F^-1 has M^T = E^-1 X^T F^-1: the same tree walk with each front's LU read along its other index
  * (csrc/kernels_ulv_t.hip; DESIGN.md "Transposed and adjoint ULV solves").  Two calls return equal bits. */
 int hs_hss_ldiv_t(hs_hss* H, int trans, double* B, int64_t ldb, int64_t nrhs, int where);
+/* log|det H| and det H / |det H| of an ELIMINATED matrix (hs_hss_factor has run; else HS_ERR_ARGUMENT), from the stored ULV factors.  With
+ * X = E M F per node (E, F unit triangular, above) and one symmetric permutation per node, det H = det(root LU) * prod over the eliminated
+ * nodes of det(X_RR); every factor is the diagonal of a pivoted LU times the parity of its row permutation.  One grouped launch, one
+ * wave per node, the per-node results are summed on the host in node order: two calls return equal bits.  *sign_im = 0 for a real matrix;
+ * an exactly zero pivot gives *logabs = -Inf and a zero sign.  This is the determinant of the compressed matrix, which differs from that
+ * of the matrix it was compressed from by the compression error. */
+int hs_hss_logabsdet(const hs_hss* H, double* logabs, double* sign_re, double* sign_im);
 /* wall time of the last compress / factor on the device (seconds, host clock around a synchronised stream) */
 double hs_hss_time(const hs_hss* H, int what); /* 0: compress, 1: factor */
 /* The module recycles its device blocks (and those of the low-rank compressions of hs_factor_*) through process-wide caches, up to

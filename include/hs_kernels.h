@@ -424,6 +424,14 @@ int hsk_eigs_phases(double* out4);
  * then puts a stream synchronisation before and behind every product); 0 otherwise.  They are part of the phases above they occur in. */
 double hsk_eigs_gen_mprod_seconds(void);
 
+/* hsk_ulv_det: the per-node reduction of hs_hss_logabsdet (ulv_det_kernel, one wave per node) on host data.  nnodes packed LUs, node k
+ * ni[k] x ni[k] with leading dimension ld[k] >= max(ni[k], 1), one after the other in LU; their row permutations one after the other in
+ * rperm (0-based; ni[k] = 0: an empty node).  out2[2k] = sum log|u_ii|, out2[2k+1] = sum arg(u_ii) (ComplexF64; 0 for Float64),
+ * flags3[3k..] = {negative diagonal entries (Float64), parity of rperm, an exactly zero pivot}; res3 = {log|det|, sign_re, sign_im} of
+ * the product over all nodes, folded in node order as hs_hss_logabsdet folds it. */
+int hsk_ulv_det_d(int64_t nnodes, const int64_t* ni, const int64_t* ld, const double* LU, const int32_t* rperm, double* out2, int32_t* flags3, double* res3);
+int hsk_ulv_det_z(int64_t nnodes, const int64_t* ni, const int64_t* ld, const double* LU, const int32_t* rperm, double* out2, int32_t* flags3, double* res3);
+
 /* Microseconds per ROUND TRIP (two exchanges) between workgroup 0 and workgroup `peer` of one launch through agent-scope atomic stores and polled
  * loads -- the exchange primitive of the dataflow sweeps of ldiv! (kernels_solve_wide.hip).  peer = 1: another XCD, peer = 8: the same XCD. */
 double hsk_flow_pingpong_us(int peer, int iters);

@@ -203,6 +203,20 @@ int hs_ldiv_ulv_d(hs_handle* F, int trans, double* C, int64_t ldc, const double*
 int hs_ldiv_ulv_z(hs_handle* F, int trans, double* C, int64_t ldc, const double* B, int64_t ldb, int64_t n, int64_t nrhs);
 int hs_ldiv_ulv_dev_d(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
 int hs_ldiv_ulv_dev_z(hs_handle* F, int trans, double* dC, int64_t ldc, const double* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream);
+/* Per-handle switch: who applies op(F)^-1 inside the lockstep drivers and hs_logabsdet on a handle whose fronts keep their interior block D
+ * as an HSS matrix (hs_options.hss_d, mf = 2, 3).
+ *   mode = 0 (default): today's routing and today's refusals, bit for bit.
+ *   mode = 1: on such a handle hs_gmres_*, hs_gmres_t_*, hs_gmres_block_*, hs_gmres_block_t_*, hs_ldiv_refine_* (any trans, ferr),
+ *             hs_ldiv_refine_block_*, hs_normestinv, hs_condest and hs_sens_* / hs_misfit_* (dense B and W; sparse ones stay refused)
+ *             apply op(F)^-1 through hs_ldiv_ulv_dev_*, and what that entry point refuses is refused with its words; hs_logabsdet adds
+ *             det D of every such front from its ULV factors (hs_hss_logabsdet).  A handle WITHOUT such fronts keeps its routing and
+ *             returns the bits of mode 0.  Everything else keeps its refusals in either mode (hs_ldiv_block_*, hs_ldiv_t_*, hs_ldiv_sparse_*,
+ *             hs_selinv*, hs_tangent_*, hs_gn_*, hs_mod_*, hs_eigs_*, hs_f32_*, hs_mul_*, hs_interface_*).
+ *   mode = -1: query only.
+ * Returns the previous mode (0 or 1), or HS_ERR_ARGUMENT (negative) for a null handle or another mode.  The mode is host state of the
+ * handle: a plan-only handle (hs_plan) and a handle over several ranks accept the call (the drivers' own refusals then speak), and it
+ * survives hs_numeric_begin and every refactorization.  Do not change it while another thread is inside a call on the same handle. */
+int hs_ulv_mode(hs_handle* F, int mode);
 /* last block solve of the handle, whichever direction it had (waits for it): out6 = {seconds on the device, factor bytes read by the model (column chunks x sum over
  * fronts of (ni^2 + 2 ni nb) sizeof(T), the factor term of hs_stats.bytes_solve), flops executed on the matrix pipe (padding included),
  * useful flops, column chunks, workspace bytes} */
