@@ -10,7 +10,7 @@ from .nesteddissection import (  # noqa: F401
     contigious, parse_elimtree, serialize_elimtree, getinterior, getboundary, flatten_tree, native_symbolic, native_graph_symbolic,
 )
 from . import problems  # noqa: F401
-from .solver import SolverOptions, chkopts, factor, factorize, FactorNode, TransposedFactor, ldiv, maxrank, trim, transpose, adjoint, opnorm, opnormestinv, condest, ldiv_refine, ldiv_refine_block, ldiv_refine_block_info, logabsdet, logdet, det, ulv_mode, selinv, selinv_diag, selinv_info, selinv_lr, selinv_lr_diag, selinv_lr_info, sym_info, ldiv_block, ldiv_block_t, ldiv_ulv, ldiv_block_info, mul, mul_info, factor_error, ldiv_sparse, ldiv_sparse_plan, ldiv_sparse_info, inv_entries, sensitivity, sensitivity_matrix, misfit, sens_info, tangent, gn_hessvec, gn_diag, gn_info, ModifiedFactor, modify, ldiv_mod, DemotedFactor, demote, ldiv_f32, eigs, eigs_info, eigs_gen_info, interface_indices, schur_complement, condense, interface_solve, expand, interface_info  # noqa: F401,E402
+from .solver import SolverOptions, chkopts, factor, factorize, FactorNode, TransposedFactor, ldiv, maxrank, trim, transpose, adjoint, opnorm, opnormestinv, condest, ldiv_refine, ldiv_refine_block, ldiv_refine_block_info, logabsdet, logdet, det, ulv_mode, selinv, selinv_diag, selinv_info, selinv_lr, selinv_lr_diag, selinv_lr_info, sym_info, equil_info, equil_scales, ldiv_block, ldiv_block_t, ldiv_ulv, ldiv_block_info, mul, mul_info, factor_error, ldiv_sparse, ldiv_sparse_plan, ldiv_sparse_info, inv_entries, sensitivity, sensitivity_matrix, misfit, sens_info, tangent, gn_hessvec, gn_diag, gn_info, ModifiedFactor, modify, ldiv_mod, DemotedFactor, demote, ldiv_f32, eigs, eigs_info, eigs_gen_info, interface_indices, schur_complement, condense, interface_solve, expand, interface_info  # noqa: F401,E402
 from ._lib import DimensionMismatch, SingularException, DeviceError, UnsupportedError, NoConvergence  # noqa: F401,E402
 from . import _lib  # noqa: F401,E402
 from . import dist  # noqa: F401,E402

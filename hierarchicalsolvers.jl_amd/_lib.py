@@ -23,7 +23,7 @@ class hs_options(C.Structure):
     _fields_ = [
         ("swlevel", i64), ("swsize", i64), ("atol", C.c_double), ("rtol", C.c_double), ("c_tol", C.c_double),
         ("leafsize", i64), ("kest", i64), ("stepsize", i64), ("verbose", C.c_uint8),
-        ("keep_schur", C.c_uint8), ("profile", C.c_uint8), ("split", C.c_uint8), ("hss_d", C.c_uint8), ("hss_dexp", C.c_uint8), ("mf", C.c_uint8), ("dist_top", C.c_uint8), ("seed", i64), ("symmetric", C.c_uint8),
+        ("keep_schur", C.c_uint8), ("profile", C.c_uint8), ("split", C.c_uint8), ("hss_d", C.c_uint8), ("hss_dexp", C.c_uint8), ("mf", C.c_uint8), ("dist_top", C.c_uint8), ("seed", i64), ("symmetric", C.c_uint8), ("equilibrate", C.c_uint8),
     ]
 
 
@@ -85,7 +85,7 @@ EXPORTS = [
     "hs_ldiv_sparse_d", "hs_ldiv_sparse_z", "hs_ldiv_sparse_dev_d", "hs_ldiv_sparse_dev_z", "hs_ldiv_sparse_plan", "hs_ldiv_sparse_info",
     "hs_opnorm", "hs_normestinv", "hs_condest", "hs_ldiv_refine_d", "hs_ldiv_refine_z", "hs_ldiv_refine_dev_d", "hs_ldiv_refine_dev_z",
     "hs_ldiv_refine_block_d", "hs_ldiv_refine_block_z", "hs_ldiv_refine_block_dev_d", "hs_ldiv_refine_block_dev_z", "hs_ldiv_refine_block_info",
-    "hs_logabsdet", "hs_selinv", "hs_selinv_info", "hs_selinv_lr", "hs_selinv_lr_info", "hs_sym_info",
+    "hs_logabsdet", "hs_selinv", "hs_selinv_info", "hs_selinv_lr", "hs_selinv_lr_info", "hs_sym_info", "hs_equil_info", "hs_equil_scales",
     "hs_interface_size", "hs_interface_indices", "hs_interface_matrix_d", "hs_interface_matrix_z", "hs_interface_info", "hsk_lu_product_d", "hsk_lu_product_z",
     "hs_interface_condense_d", "hs_interface_condense_z", "hs_interface_condense_dev_d", "hs_interface_condense_dev_z",
     "hs_interface_solve_d", "hs_interface_solve_z", "hs_interface_solve_dev_d", "hs_interface_solve_dev_z",
@@ -426,6 +426,10 @@ def lib():
     L.hs_flow_info.restype = C.c_int
     L.hs_sym_info.argtypes = [vp, p_i64]
     L.hs_sym_info.restype = C.c_int
+    L.hs_equil_info.argtypes = [vp, p_i64]
+    L.hs_equil_info.restype = C.c_int
+    L.hs_equil_scales.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.hs_equil_scales.restype = C.c_int
     L.hs_hss_qr_order.argtypes = [C.c_int]
     L.hs_hss_qr_order.restype = C.c_int
     L.hs_hss_pack_size.argtypes = [vp, p_i64]

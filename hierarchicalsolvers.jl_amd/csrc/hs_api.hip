@@ -226,6 +226,13 @@ struct hs_handle {
   int* d_growth = nullptr;
   unsigned long long* d_symflag = nullptr;  // hs_options.symmetric: the first entry of A that differs from its transposed partner (sym_check_kernel)
   int64_t sym_fronts = 0, sym_plain = 0;    // hs_sym_info: dense fronts of the last factorization eliminated on their lower triangle / as before
+  // hs_options.equilibrate (null / 0 without it): A_s = 2^er A 2^ec.  d_nzs holds the values of A_s in CSC order -- what feeds the fronts
+  // (front_values); d_nz stays the caller's A.  d_eqmax: 2 n row / column maxima of a sweep, then the flag words of the sweeps and of the scaling
+  int32_t *d_er = nullptr, *d_ec = nullptr;
+  void* d_nzs = nullptr;
+  unsigned long long* d_eqmax = nullptr;
+  int64_t eq_info[6] = {0, 0, 0, 0, 0, 0};  // hs_equil_info
+  int64_t eq_sum = 0;                       // sum er + sum ec of the last hs_numeric_begin (hs_logabsdet)
   bool optimistic = true;   // HS_OPTIMISTIC=0 turns it off; a level that had to be redone turns it off for the rest of the handle's life
   int* d_own = nullptr;
   int* d_pos = nullptr;
@@ -399,7 +406,8 @@ static void free_handle(hs_handle* h) {
   arena_give(h->d_cfs, h->cfs_bytes);
   void* ptrs[] = {h->d_int, h->d_tmpi, h->d_colptr, h->d_rowval, h->d_nz,
                   h->d_nodes, h->d_sc,  h->d_solve, h->d_w1,  h->d_w2,   h->d_part,   h->d_b,   h->d_owned,
-                  h->d_rowptr, h->d_colind, h->d_tperm, h->d_nzr, h->d_lpos, h->d_env, h->d_symflag, h->d_perm};
+                  h->d_rowptr, h->d_colind, h->d_tperm, h->d_nzr, h->d_lpos, h->d_env, h->d_symflag, h->d_perm,
+                  h->d_er, h->d_ec, h->d_nzs, h->d_eqmax};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -639,6 +647,11 @@ static void build_plan(hs_handle* h, int64_t n, const hs_tree* tr, const SplitTr
   }
 }
 
+// the values the fronts are assembled from: A_s with hs_options.equilibrate, else the caller's A
+template <class T>
+static const T* front_values(const hs_handle* h) {
+  return (const T*)(h->d_nzs ? h->d_nzs : h->d_nz);
+}
 static void dmalloc(void** p, size_t bytes, const char* what);
 template <class T>
 static void mf_compress_schur_dense(hs_handle* h, int id, const T* SB, int lds, const T* C_, int ldc, const T* M, int ldm, const T* Z, int ldz, int r1, int r2,
@@ -694,6 +707,8 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
   if (nranks < 1 || rank < 0 || rank >= nranks) HS_FAIL(HS_ERR_ARGUMENT, rank, "ArgumentError: rank %d of %d", rank, nranks);
   if (opts.symmetric && nranks > 1)
     HS_FAIL(HS_ERR_UNSUPPORTED, nranks, "hs_options.symmetric with %d ranks: single-rank factorizations only", nranks);
+  if (opts.equilibrate && nranks > 1)
+    HS_FAIL(HS_ERR_UNSUPPORTED, nranks, "hs_options.equilibrate with %d ranks: single-rank factorizations only", nranks);
   if (!plan_only) require_device();
 
   hs_handle* h = new hs_handle();
@@ -1026,6 +1041,12 @@ static hs_handle* analyze_impl(int64_t n, const int64_t* colptr, const int64_t* 
     dmalloc((void**)&h->d_rowval, nnz * sizeof(int32_t), "rowval");
     dmalloc(&h->d_nz, nnz * sizeof(T), "nzval");
     if (opts.symmetric) dmalloc((void**)&h->d_symflag, sizeof(unsigned long long), "symmetry flag");
+    if (opts.equilibrate) {
+      dmalloc((void**)&h->d_er, n * sizeof(int32_t), "row scale exponents");
+      dmalloc((void**)&h->d_ec, n * sizeof(int32_t), "column scale exponents");
+      dmalloc(&h->d_nzs, nnz * sizeof(T), "scaled nzval");
+      dmalloc((void**)&h->d_eqmax, (2 * (size_t)n + 2) * sizeof(unsigned long long), "row and column maxima");
+    }
     {
       std::vector<int64_t> cp(n + 1);
       for (int64_t j = 0; j <= n; ++j) {
@@ -1268,6 +1289,61 @@ static void check_device_handle(const hs_handle* h) {
   if (!h->d_nodes) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: handle holds a host-side plan only (hs_plan); use hs_analyze");
 }
 
+#define HS_EQUIL_MAX_SWEEPS 16
+// hs_options.equilibrate: the exponents er, ec by Ruiz sweeps on the device (kernels_equil.hip; include/hs_solver.h has the rule), then
+// d_nzs = 2^er A 2^ec.  Every sweep ends with one flag coming down; the exponents come down once, for hs_equil_info and hs_logabsdet.
+// (n >= 1: analyze_impl refuses an empty matrix.)
+template <class T>
+static void equilibrate(hs_handle* h, hipStream_t s) {
+  const int64_t n = h->n;
+  unsigned long long *rmax = h->d_eqmax, *cmax = rmax + n, *bad = cmax + n;
+  int* changed = (int*)(bad + 1);
+  for (int64_t& x : h->eq_info) x = 0;  // (a call that fails below leaves "no sweeps run": hs_equil_scales then refuses the handle)
+  h->eq_info[0] = 1;
+  h->eq_sum = 0;
+  int64_t sweeps = 0;
+  HS_HIP(hipMemsetAsync(h->d_er, 0, n * sizeof(int32_t), s));
+  HS_HIP(hipMemsetAsync(h->d_ec, 0, n * sizeof(int32_t), s));
+  for (int sweep = 0; sweep < HS_EQUIL_MAX_SWEEPS; ++sweep) {
+    HS_HIP(hipMemsetAsync(rmax, 0, n * sizeof(unsigned long long), s));
+    HS_HIP(hipMemsetAsync(changed, 0, sizeof(int), s));
+    launch_equil_maxima<T>(n, h->d_colptr, h->d_rowval, (const T*)h->d_nz, h->d_er, h->d_ec, rmax, cmax, s);
+    launch_equil_update(n, rmax, cmax, h->d_er, h->d_ec, changed, s);
+    int moved = 0;
+    HS_HIP(hipMemcpyAsync(&moved, changed, sizeof moved, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
+    sweeps = sweep + 1;
+    if (!moved) break;
+  }
+  HS_HIP(hipMemsetAsync(bad, 0xff, sizeof(unsigned long long), s));
+  launch_equil_scale<T>(n, h->d_colptr, h->d_rowval, (const T*)h->d_nz, h->d_er, h->d_ec, (T*)h->d_nzs, bad, s);
+  unsigned long long first = 0;
+  std::vector<int32_t> e((size_t)2 * n);
+  HS_HIP(hipMemcpyAsync(&first, bad, sizeof first, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipMemcpyAsync(e.data(), h->d_er, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipMemcpyAsync(e.data() + n, h->d_ec, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  h->eq_info[1] = sweeps;
+  h->eq_info[2] = *std::min_element(e.begin(), e.begin() + n);
+  h->eq_info[3] = *std::max_element(e.begin(), e.begin() + n);
+  h->eq_info[4] = *std::min_element(e.begin() + n, e.end());
+  h->eq_info[5] = *std::max_element(e.begin() + n, e.end());
+  for (int32_t x : e) h->eq_sum += x;
+  if (first != ~0ull) {
+    for (int64_t& x : h->eq_info) x = 0;  // d_nzs is not the scaled matrix: the handle reports no exponents
+    h->eq_sum = 0;
+    int32_t r = 0;
+    HS_HIP(hipMemcpy(&r, h->d_rowval + first, sizeof r, hipMemcpyDeviceToHost));
+    std::vector<int64_t> cp((size_t)n + 1);
+    HS_HIP(hipMemcpy(cp.data(), h->d_colptr, sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost));
+    const int64_t c = std::upper_bound(cp.begin(), cp.end(), (int64_t)first) - cp.begin() - 1;
+    HS_FAIL(HS_ERR_UNSUPPORTED, (int64_t)first,
+            "hs_options.equilibrate: the entry at (row %lld, column %lld) (1-based) scaled by 2^(%d + %d) leaves the normal range of Float64 (subnormal or "
+            "infinite): the scaling would not be exact; factor without the option or rescale A",
+            (long long)r + 1, (long long)c + 1, (int)e[(size_t)r], (int)e[(size_t)(n + c)]);
+  }
+}
+
 template <class T>
 static void numeric_begin(hs_handle* h, const void* nzval, int on_device) {
   if (!nzval) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: nzval == NULL");
@@ -1300,7 +1376,8 @@ static void numeric_begin(hs_handle* h, const void* nzval, int on_device) {
               (long long)r + 1, (long long)c + 1, (long long)c + 1, (long long)r + 1);
     }
   }
-  if (h->mf_on) launch_perm_gather<T>((const T*)h->d_nz, h->d_tperm, (T*)h->d_nzr, h->nnz, s);
+  if (h->opts.equilibrate) equilibrate<T>(h, s);
+  if (h->mf_on) launch_perm_gather<T>(front_values<T>(h), h->d_tperm, (T*)h->d_nzr, h->nnz, s);
   HS_HIP(hipMemsetAsync(h->d_own, 0xff, h->n * sizeof(int), s));
   h->prof = Profiler();
   h->prof.on = h->opts.profile != 0;
@@ -1397,7 +1474,7 @@ static void numeric_levels(hs_handle* h, int lv_from, int lv_to) {
     }
     launch_init_fronts<T>(dn, nb_, L.maxni, s);
     launch_mark<T>(dn, nb_, L.maxm, h->d_own, h->d_pos, s);
-    launch_gather<T>(dn, nb_, L.maxm, h->d_colptr, h->d_rowval, (const T*)h->d_nz, h->d_own, h->d_pos, s);
+    launch_gather<T>(dn, nb_, L.maxm, h->d_colptr, h->d_rowval, front_values<T>(h), h->d_own, h->d_pos, s);
     launch_scatter<T>(dn, dsc_all + L.sc_off, (int)L.sc_cnt, L.maxnbc, s);
     h->prof.end(ea, HS_CAT_ASSEMBLE, s);
     if (L.ndense > 0) {
@@ -1678,6 +1755,19 @@ static void check_no_hss_front(const hs_handle* h, const char* fn, const char* w
     HS_FAIL(HS_ERR_UNSUPPORTED, (long long)i, "%s: node %d keeps its interior block D as an HSS matrix (hs_options.hss_d / mf = 2, 3): %s are not implemented", fn, i, what);
 }
 
+// ---- hs_options.equilibrate: op(F)^-1 B = 2^ec (F_s^-1 (2^er B)) for trans = 0, 2^er (F_s^-T (2^ec B)) for trans = 1, 2 (the scales are real:
+// the adjoint needs nothing more).  The exponents a solve scales the rows of its block by before and after the sweeps; null without the option
+static const int32_t* equil_before(const hs_handle* h, int trans) { return trans == 0 ? h->d_er : h->d_ec; }
+static const int32_t* equil_after(const hs_handle* h, int trans) { return trans == 0 ? h->d_ec : h->d_er; }
+// the in-place pass over an n x nrhs device block (nothing without the option)
+template <class T>
+static void equil_rows(const int32_t* e, T* d, int64_t ld, int64_t n, int64_t nrhs, hipStream_t s) {
+  if (e) launch_scale_rows<T>(n, nrhs, e, d, ld, d, ld, s);
+}
+// what every refused entry point of hs_options.equilibrate says (hs_host.h)
+int hs_handle_equilibrated(const hs_handle* h) { return h && h->opts.equilibrate ? 1 : 0; }
+int64_t hs_handle_equil_sum(const hs_handle* h) { return h ? h->eq_sum : 0; }
+
 // ---- column by column: solve(c, s) is one single-vector solve in place on the device
 // host columns travel through d_b: upload, solve between the handle's events, download; t_solve = the sum of the device times
 template <class T, class Solve>
@@ -1709,6 +1799,24 @@ static void each_column_dev(T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_
   }
 }
 
+// ... of an equilibrated handle: the scaling before the solves stands in for the copy (read B, write scaled C), one in-place pass follows them
+template <class T, class Solve>
+static void each_column_dev_op(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, hipStream_t s, Solve solve) {
+  if (!h->d_er) return each_column_dev<T>(dC, ldc, dB, ldb, n, nrhs, s, solve);
+  launch_scale_rows<T>(n, nrhs, equil_before(h, trans), dB, ldb, dC, ldc, s);
+  each_column_dev<T>(dC, ldc, (const T*)dC, ldc, n, nrhs, s, solve);
+  equil_rows<T>(equil_after(h, trans), dC, ldc, n, nrhs, s);
+}
+// one host column at a time: scaled where it lies in d_b, before and after its solve
+template <class T, class Solve>
+static void each_column_host_op(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs, Solve solve) {
+  each_column_host<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* db, hipStream_t s) {
+    equil_rows<T>(equil_before(h, trans), db, n, n, 1, s);
+    solve(db, s);
+    equil_rows<T>(equil_after(h, trans), db, n, n, 1, s);
+  });
+}
+
 // what hs_ldiv_* / hs_ldiv_dev_* refuse; true: the factorization is spread over ranks with hs_options.dist_top (solve_dist)
 static bool check_solve_n(hs_handle* h, const char* fn, bool cplx, int64_t ldc, int64_t ldb, int64_t n, int64_t nrhs) {
   check_solve_args(h, cplx, ldc, ldb, n, nrhs);
@@ -1731,12 +1839,12 @@ static void solve_n(hs_handle* h, bool dsolve, T* db, hipStream_t s) {
 template <class T>
 static void ldiv_host(hs_handle* h, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
   const bool dsolve = check_solve_n(h, "hs_ldiv_*", sizeof(T) == 16, ldc, ldb, n, nrhs);
-  each_column_host<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* db, hipStream_t s) { solve_n<T>(h, dsolve, db, s); });
+  each_column_host_op<T>(h, 0, C, ldc, B, ldb, n, nrhs, [&](T* db, hipStream_t s) { solve_n<T>(h, dsolve, db, s); });
 }
 template <class T>
 static void ldiv_dev(hs_handle* h, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   const bool dsolve = check_solve_n(h, "hs_ldiv_dev_*", sizeof(T) == 16, ldc, ldb, n, nrhs);
-  each_column_dev<T>(dC, ldc, dB, ldb, n, nrhs, (hipStream_t)stream, [&](T* c, hipStream_t s) { solve_n<T>(h, dsolve, c, s); });
+  each_column_dev_op<T>(h, 0, dC, ldc, dB, ldb, n, nrhs, (hipStream_t)stream, [&](T* c, hipStream_t s) { solve_n<T>(h, dsolve, c, s); });
 }
 
 
@@ -1756,14 +1864,14 @@ static void ldiv_host_t(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, 
   check_solve_t(h, trans, "hs_ldiv_t_*");
   if (trans == 0) return ldiv_host<T>(h, C, ldc, B, ldb, n, nrhs);
   check_solve_args(h, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  each_column_host<T>(h, C, ldc, B, ldb, n, nrhs, [&](T* db, hipStream_t s) { solve_t<T>(h, trans, db, s); });
+  each_column_host_op<T>(h, trans, C, ldc, B, ldb, n, nrhs, [&](T* db, hipStream_t s) { solve_t<T>(h, trans, db, s); });
 }
 template <class T>
 static void ldiv_dev_t(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   check_solve_t(h, trans, "hs_ldiv_dev_t_*");
   if (trans == 0) return ldiv_dev<T>(h, dC, ldc, dB, ldb, n, nrhs, stream);
   check_solve_args(h, sizeof(T) == 16, ldc, ldb, n, nrhs);
-  each_column_dev<T>(dC, ldc, dB, ldb, n, nrhs, (hipStream_t)stream, [&](T* c, hipStream_t s) { solve_t<T>(h, trans, c, s); });
+  each_column_dev_op<T>(h, trans, dC, ldc, dB, ldb, n, nrhs, (hipStream_t)stream, [&](T* c, hipStream_t s) { solve_t<T>(h, trans, c, s); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1835,12 +1943,14 @@ static void check_solve_block_t(hs_handle* h, int trans, bool cplx, int64_t ldc,
   check_single_rank(h, fn, "block solves");
   check_no_hss_front(h, fn, "transposed ULV solves");
 }
-// a device block is solved in place in C: what every device entry does between its checks and its solve
+// a device block is solved in place in C: what every device entry does between its checks and its solve.  On an equilibrated handle the
+// scaling before the solve takes the place of the copy (read B, write scaled C; in place when C is B)
 template <class T>
-static hipStream_t block_in_place(const char* fn, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
+static hipStream_t block_in_place(const hs_handle* h, int trans, const char* fn, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   if (!dC || !dB) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", fn);
   hipStream_t s = (hipStream_t)stream;
-  if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
+  if (h->d_er) launch_scale_rows<T>(n, nrhs, equil_before(h, trans), dB, ldb, dC, ldc, s);
+  else if (dC != dB) HS_HIP(hipMemcpy2DAsync(dC, ldc * sizeof(T), dB, ldb * sizeof(T), n * sizeof(T), nrhs, hipMemcpyDeviceToDevice, s));
   return s;
 }
 // the block solve of a checked handle without HSS interior blocks; trans = 0 speaks as hs_ldiv_block_*, whichever entry point came here
@@ -1850,16 +1960,21 @@ static void block_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, i
   if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null block", trans ? "hs_ldiv_block_t_*" : "hs_ldiv_block_*");
   HsMultiView v;
   hs_multi_view(h, &v);
-  hs_stage_block<T>(h->stream, "block solve right-hand sides", C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { hs_solve_multi_run<T>(v, trans, d, ld, nrhs, s); });
+  hs_stage_block<T>(h->stream, "block solve right-hand sides", C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) {
+    equil_rows<T>(equil_before(h, trans), d, ld, n, nrhs, s);
+    hs_solve_multi_run<T>(v, trans, d, ld, nrhs, s);
+    equil_rows<T>(equil_after(h, trans), d, ld, n, nrhs, s);
+  });
   h->stats.t_solve = hs_solve_multi_seconds(h->mx);
 }
 template <class T>
 static void block_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   if (nrhs == 0) return;
-  hipStream_t s = block_in_place<T>(trans ? "hs_ldiv_block_dev_t_*" : "hs_ldiv_block_dev_*", dC, ldc, dB, ldb, n, nrhs, stream);
+  hipStream_t s = block_in_place<T>(h, trans, trans ? "hs_ldiv_block_dev_t_*" : "hs_ldiv_block_dev_*", dC, ldc, dB, ldb, n, nrhs, stream);
   HsMultiView v;
   hs_multi_view(h, &v);
   hs_solve_multi_run<T>(v, trans, dC, ldc, nrhs, s);
+  equil_rows<T>(equil_after(h, trans), dC, ldc, n, nrhs, s);
 }
 template <class T>
 static void ldiv_block_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B, int64_t ldb, int64_t n, int64_t nrhs) {
@@ -2015,15 +2130,20 @@ static void ldiv_ulv_host(hs_handle* h, int trans, T* C, int64_t ldc, const T* B
   if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return block_host<T>(h, trans, C, ldc, B, ldb, n, nrhs);
   if (nrhs == 0) return;
   if (!C || !B) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_ldiv_ulv_*: null block");
-  hs_stage_block<T>(h->stream, "block solve right-hand sides", C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) { ulv_run<T>(h, trans, d, ld, nrhs, s); });
+  hs_stage_block<T>(h->stream, "block solve right-hand sides", C, ldc, B, ldb, n, nrhs, [&](T* d, int64_t ld, hipStream_t s) {
+    equil_rows<T>(equil_before(h, trans), d, ld, n, nrhs, s);
+    ulv_run<T>(h, trans, d, ld, nrhs, s);
+    equil_rows<T>(equil_after(h, trans), d, ld, n, nrhs, s);
+  });
   h->stats.t_solve = hs_solve_multi_seconds(h->mx);
 }
 template <class T>
 static void ldiv_ulv_dev(hs_handle* h, int trans, T* dC, int64_t ldc, const T* dB, int64_t ldb, int64_t n, int64_t nrhs, void* stream) {
   if (!check_solve_ulv(h, trans, sizeof(T) == 16, ldc, ldb, n, nrhs)) return block_dev<T>(h, trans, dC, ldc, dB, ldb, n, nrhs, stream);
   if (nrhs == 0) return;
-  hipStream_t s = block_in_place<T>("hs_ldiv_ulv_dev_*", dC, ldc, dB, ldb, n, nrhs, stream);
+  hipStream_t s = block_in_place<T>(h, trans, "hs_ldiv_ulv_dev_*", dC, ldc, dB, ldb, n, nrhs, stream);
   ulv_run<T>(h, trans, dC, ldc, nrhs, s);  // (waits for s: the HSS solves of the fronts synchronise it anyway)
+  equil_rows<T>(equil_after(h, trans), dC, ldc, n, nrhs, s);
 }
 
 // the handle as hs_condest.hip sees it (hs_condest.h)
@@ -2268,11 +2388,11 @@ extern "C" int hs_ldiv_block_info(const hs_handle* F, double* out6) {
 }
 
 extern "C" int hs_solve_fwd_levels(hs_handle* h, void* d_b, int64_t lv_from, int64_t lv_to, void* stream) {
-  HS_GUARD(check_handle(h); if (h->is_complex) solve_fwd<cplx>(h, 0, (cplx*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream);
+  HS_GUARD(check_handle(h); hs_refuse_equilibrated(h, "hs_solve_fwd_levels"); if (h->is_complex) solve_fwd<cplx>(h, 0, (cplx*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream);
            else solve_fwd<double>(h, 0, (double*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream));
 }
 extern "C" int hs_solve_bwd_levels(hs_handle* h, void* d_b, int64_t lv_from, int64_t lv_to, void* stream) {
-  HS_GUARD(check_handle(h); if (h->is_complex) solve_bwd<cplx>(h, 0, (cplx*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream);
+  HS_GUARD(check_handle(h); hs_refuse_equilibrated(h, "hs_solve_bwd_levels"); if (h->is_complex) solve_bwd<cplx>(h, 0, (cplx*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream);
            else solve_bwd<double>(h, 0, (double*)d_b, (int)lv_from, (int)lv_to, (hipStream_t)stream));
 }
 
@@ -2367,6 +2487,19 @@ extern "C" int hs_ulv_mode(hs_handle* h, int mode) {
 extern "C" int hs_sym_info(const hs_handle* h, int64_t* out4) {
   HS_GUARD(check_handle(h); if (!out4) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: out4 == NULL");
            out4[0] = h->opts.symmetric ? 1 : 0; out4[1] = h->sym_fronts; out4[2] = h->sym_plain; out4[3] = 0;);
+}
+// out6 = {hs_options.equilibrate, sweeps run, min er, max er, min ec, max ec} of the last hs_numeric_begin
+extern "C" int hs_equil_info(const hs_handle* h, int64_t* out6) {
+  HS_GUARD(check_handle(h); if (!out6) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: out6 == NULL");
+           for (int k = 0; k < 6; ++k) out6[k] = h->eq_info[k]; out6[0] = h->opts.equilibrate ? 1 : 0;);
+}
+extern "C" int hs_equil_scales(const hs_handle* h, int32_t* er, int32_t* ec) {
+  HS_GUARD(check_handle(h);
+           if (!h->d_er) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_equil_scales: the handle has no scale factors (hs_options.equilibrate is off, or a host-side plan)");
+           if (!h->eq_info[1]) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_equil_scales: no hs_numeric_begin has found exponents on this handle yet (none ran, or the last one failed)");
+           HS_HIP(hipStreamSynchronize(h->stream));
+           if (er) HS_HIP(hipMemcpy(er, h->d_er, h->n * sizeof(int32_t), hipMemcpyDeviceToHost));
+           if (ec) HS_HIP(hipMemcpy(ec, h->d_ec, h->n * sizeof(int32_t), hipMemcpyDeviceToHost)););
 }
 extern "C" int64_t hs_node_owner(const hs_handle* h, int64_t node) {
   if (!h || node < 0 || node >= h->nnodes) return -1;
@@ -2475,6 +2608,7 @@ void hs_sparse_tree(const hs_handle* hc, HsSparseTree* t) {
 static void check_sparse_handle(const hs_handle* h, int trans, const char* fn) {
   check_handle(h);
   hs_check_trans(fn, trans);
+  hs_refuse_equilibrated(h, fn);
   check_single_rank(h, fn, "block solves");
   check_no_hss_front(h, fn, "block solves");
 }

@@ -286,6 +286,24 @@ void launch_sym_transpose(const NodeDesc<T>* dnodes, int nbatch, int mat, int r0
 template <class T>
 void launch_sym_check(int64_t n, const int64_t* colptr, const int32_t* rowval, const T* nz, unsigned long long* first, hipStream_t s);
 
+// ---- hs_options.equilibrate (kernels_equil.hip): A_s = 2^er A 2^ec, integer exponents found by Ruiz sweeps in the infinity norm ----------
+// One sweep is two launches.  equil_maxima: rmax[i] / cmax[j] (device, n each; rmax zeroed by the caller) receive the bit patterns of the
+// largest ldexp(|a|, er[row] + ec[col]) of row i / column j (|a| = fabs, |re| + |im| for complex).  equil_update: every exponent moves by
+// -floor((floor(log2 m) + 1) / 2) of its maximum m (a zero or non-finite maximum moves nothing), rows and columns from the same maxima;
+// *changed (device, zeroed by the caller) becomes non-zero if any exponent moved.
+template <class T>
+void launch_equil_maxima(int64_t n, const int64_t* colptr, const int32_t* rowval, const T* nz, const int32_t* er, const int32_t* ec, unsigned long long* rmax,
+                         unsigned long long* cmax, hipStream_t s);
+void launch_equil_update(int64_t n, const unsigned long long* rmax, const unsigned long long* cmax, int32_t* er, int32_t* ec, int* changed, hipStream_t s);
+// nzs[p] = ldexp(nz[p], er[row] + ec[col]); *bad (device, preset to all ones) receives the smallest index of a non-zero finite component whose
+// scaled value is subnormal or infinite
+template <class T>
+void launch_equil_scale(int64_t n, const int64_t* colptr, const int32_t* rowval, const T* nz, const int32_t* er, const int32_t* ec, T* nzs, unsigned long long* bad,
+                        hipStream_t s);
+// C[i, j] = ldexp(B[i, j], e[i]) for an n x nrhs column-major block; C == B scales in place
+template <class T>
+void launch_scale_rows(int64_t n, int64_t nrhs, const int32_t* e, const T* B, int64_t ldb, T* C, int64_t ldc, hipStream_t s);
+
 template <class T>
 void launch_init_fronts(const NodeDesc<T>* dnodes, int nbatch, int maxni, hipStream_t s);  // rperm = 0:ni-1, info = 0
 template <class T>

@@ -272,6 +272,7 @@ void create_entry(hs_handle* F, void* stream, hs_f32** out) {
   if (!out) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_f32_create: G == NULL");
   *out = nullptr;
   HsHandleView hv = hs_view_of(F, "hs_f32_create");
+  hs_refuse_equilibrated(F, "hs_f32_create");
   // The handles the block solve never serves are named first, so that a host-side plan (which the probe below would only call unfactored)
   // hears the lasting reason; every other refusal is the probe's own status and message.
   if (hv.nranks > 1)

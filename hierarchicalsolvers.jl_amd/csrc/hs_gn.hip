@@ -325,6 +325,8 @@ void check_gn(Call<T>* c, hs_handle* F, const char* fn, int mode, int trans, int
   hs_view_of(F, fn);  // a null handle
   if (!B && !Xin) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: B and Xin are both NULL (the right-hand sides, or the fields of an earlier call)", fn);
   check_common<T>(F, fn, trans, n, nrhs, itmax, pattern, &c->v);
+  // the adjoint columns of the receiver rows are sparse and take the pruned sweeps of hs_ldiv_sparse_* unless they are refined (itmax > 0)
+  if (mode != GN_TANGENT && itmax == 0) hs_refuse_equilibrated(F, fn);
   if (Xin) {
     if (nrhs > 0 && ldxin < n) HS_FAIL(HS_ERR_DIMENSION, 0, "DimensionMismatch: %s: the leading dimension of Xin is %lld, it has %lld rows", fn, (long long)ldxin, (long long)n);
   } else {

@@ -162,6 +162,16 @@ void hs_stage_block(hipStream_t s, const char* what, T* C, int64_t ldc, const T*
 inline void hs_check_trans(const char* fn, int trans) {
   if (trans < 0 || trans > 2) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d (0: F, 1: transpose(F), 2: adjoint(F))", fn, trans);
 }
+// hs_options.equilibrate: the stored factors are those of A_s = 2^er A 2^ec.  An entry point that reads them directly (not through the
+// hs_ldiv_* family, which scales around its sweeps) would answer for A_s: it refuses here, before any device work
+int hs_handle_equilibrated(const hs_handle* F);  // hs_api.hip; null: 0
+int64_t hs_handle_equil_sum(const hs_handle* F);  // sum er + sum ec of the last hs_numeric_begin (0 without the option)
+inline void hs_refuse_equilibrated(const hs_handle* F, const char* fn) {
+  if (hs_handle_equilibrated(F))
+    HS_FAIL(HS_ERR_UNSUPPORTED, 0,
+            "%s: the handle was factored with hs_options.equilibrate, its stored factors are those of the scaled matrix 2^er A 2^ec and this call reads "
+            "them directly (the hs_ldiv_* family and the drivers built on it serve such a handle; factor without equilibrate for this call)", fn);
+}
 inline HsHandleView hs_view_of(hs_handle* F, const char* fn) {
   if (!F) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
   HsHandleView v;

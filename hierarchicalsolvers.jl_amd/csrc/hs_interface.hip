@@ -73,6 +73,7 @@ void check_served(const HsInterfaceView& v, const char* fn) {
 void check_factored(hs_handle* F, HsInterfaceView& v, bool cplx, const char* fn) {
   if (!F) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: null factorization handle", fn);
   hs_interface_view(F, &v);
+  hs_refuse_equilibrated(F, fn);
   check_served(v, fn);
   if (!v.device || !v.factored)
     HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s needs a completed numeric factorization (the handle is a plan, or hs_numeric_end has not run)", fn);

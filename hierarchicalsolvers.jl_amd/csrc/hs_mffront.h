@@ -406,7 +406,7 @@ static void mf_fill(hs_handle* h, const std::vector<HsFillEntry>& f, T* out, int
   HsFillEntry* d = (HsFillEntry*)buf.get((f.size() * sizeof(HsFillEntry) + sizeof(T) - 1) / sizeof(T), "coupling entries");
   HS_HIP(hipMemcpyAsync(d, f.data(), f.size() * sizeof(HsFillEntry), hipMemcpyHostToDevice, s));
   HS_HIP(hipStreamSynchronize(s));
-  launch_fill_entries<T>(d, (int)f.size(), (const T*)h->d_nz, out, ld, s);
+  launch_fill_entries<T>(d, (int)f.size(), front_values<T>(h), out, ld, s);
 }
 
 // ---- numeric: the matrix-free fronts of one level, one at a time (they are the few large fronts at the top of the tree) --------------
@@ -414,7 +414,7 @@ template <class T>
 static void factor_mf_fronts(hs_handle* h, const int* ids, int count) {
   static const bool vt = getenv("HS_VERBOSE_COMPRESS") != nullptr;
   const bool say = h->opts.verbose || vt;
-  hs_sparse_dev As{h->n, h->d_colptr, h->d_rowval, h->d_nz, h->d_rowptr, h->d_colind, h->d_nzr};
+  hs_sparse_dev As{h->n, h->d_colptr, h->d_rowval, (const void*)front_values<T>(h), h->d_rowptr, h->d_colind, h->d_nzr};  // (A_s with hs_options.equilibrate)
   const double dsc = std::pow(10.0, -(double)(h->opts.hss_dexp == 0 ? 2 : h->opts.hss_dexp - 1));  // hs_options.hss_dexp
   mf_parallel(h, count, [&](int k, hipStream_t s) {
     const int id = ids[k];

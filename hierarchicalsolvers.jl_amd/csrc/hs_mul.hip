@@ -20,6 +20,7 @@ namespace {
 HsHandleView mul_check(hs_handle* F, const char* fn, int trans, bool cplx_call, int64_t n, int64_t ld1, int64_t ld2, int64_t ncols) {
   const HsHandleView v = hs_view_of(F, fn);
   hs_check_trans(fn, trans);
+  hs_refuse_equilibrated(F, fn);
   HS_CHECK(hs_handle_flow_check(F));
   if (!v.factored) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: factorization is not complete", fn);
   if ((v.is_complex != 0) != cplx_call) HS_FAIL(HS_ERR_ARGUMENT, 0, "MethodError: %s: eltype of F and B differ", fn);

@@ -683,7 +683,9 @@ void selinv_impl(const HsSelView& v, SelCache* c, bool lrmode, int trans, void* 
 extern "C" int hs_logabsdet(hs_handle* F, double* logabs, double* sign2) {
   HS_GUARD(HsSelView v; check_common(F, v, "hs_logabsdet", true);
            if (!logabs || !sign2) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: hs_logabsdet: logabs and sign2 must not be NULL");
-           if (v.is_complex) logabsdet_impl<cplx>(v, logabs, sign2); else logabsdet_impl<double>(v, logabs, sign2));
+           if (v.is_complex) logabsdet_impl<cplx>(v, logabs, sign2); else logabsdet_impl<double>(v, logabs, sign2);
+           // hs_options.equilibrate: det A_s = 2^(sum er + sum ec) det A, the exponent sum exact in int64
+           if (hs_handle_equilibrated(F)) *logabs -= 0.6931471805599453094 * (double)hs_handle_equil_sum(F));
 }
 
 // hs_selinv (lrmode = false) and hs_selinv_lr (true): the same arguments, the same checks before any device work; they differ in what
@@ -691,6 +693,7 @@ extern "C" int hs_logabsdet(hs_handle* F, double* logabs, double* sign2) {
 static void selinv_entry(const char* fn, bool lrmode, hs_handle* F, int trans, void* diag, void* zval, int where, int64_t budget_bytes, void* stream) {
   HsSelView v;
   check_common(F, v, fn);
+  hs_refuse_equilibrated(F, fn);
   if (trans != 0 && trans != 1) HS_FAIL(HS_ERR_ARGUMENT, trans, "ArgumentError: %s: trans = %d must be 0 (entries of A^-1) or 1 (of its transpose)", fn, trans);
   if (where != 0 && where != 1) HS_FAIL(HS_ERR_ARGUMENT, where, "ArgumentError: %s: where = %d must be 0 (host pointers) or 1 (device pointers)", fn, where);
   if (!diag && !zval) HS_FAIL(HS_ERR_ARGUMENT, 0, "ArgumentError: %s: diag and zval are both NULL, nothing to compute", fn);

@@ -84,7 +84,9 @@ struct Driver {
     gs.n = n;
     gs.itmax = c.itmax;
     gs.s = s;
-    gs.ulv = c.v.ulv != 0;
+    // (an equilibrated handle takes the same route: the pruned sweeps refuse it, so the driver's own sparse cotangent of hs_misfit_* is
+    // expanded and solved by the block solve, which scales around its sweeps)
+    gs.ulv = c.v.ulv != 0 || hs_handle_equilibrated(c.F) != 0;
     const bool cplx_ = sizeof(T) == 16;
     const bool cjw = cplx_ && c.trans == 1;  // the adjoint solve runs on conj(W) and returns conj(Lam)
     const int tadj = c.trans == 0 ? 2 : 0;

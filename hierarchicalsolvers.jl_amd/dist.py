@@ -389,6 +389,7 @@ class HipBackend:
         # exchange buffers live in torch memory and are registered with the library
         self._schur, self._bnd = {}, {}
         self.dist_top = bool(opts.dist_top) and self.nranks > 1
+        self.equilibrate = bool(opts.equilibrate)  # single rank only (hs_analyze refuses it over ranks)
         self.libcomm = None
         if self.dist_top:  # the library moves the Schur complements and the block columns itself (csrc/hs_dist.h)
             self._own_libcomm = libcomm is None
@@ -537,6 +538,8 @@ class StagedSolver:
 
     def solve(self, b):
         """In place on a device tensor ``b`` of length n (every rank passes the same right-hand side)."""
+        if self.backend.equilibrate:  # the level sweeps refuse an equilibrated handle: the library's own ldiv! scales around them
+            return self.backend.ldiv_dev(b)
         if self.backend.dist_top:
             if not self.host_solve:
                 return self.backend.ldiv_dev(b)

@@ -35,7 +35,7 @@ from . import _lib
 from .nesteddissection import flatten_tree
 
 __all__ = ["SolverOptions", "chkopts", "factor", "factorize", "FactorNode", "ldiv", "maxrank", "transpose", "adjoint", "opnorm", "opnormestinv", "condest",
-           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "ulv_mode", "selinv", "selinv_diag", "selinv_info", "selinv_lr", "selinv_lr_diag", "selinv_lr_info", "sym_info",
+           "ldiv_refine", "ldiv_refine_block", "ldiv_refine_block_info", "logabsdet", "logdet", "det", "ulv_mode", "selinv", "selinv_diag", "selinv_info", "selinv_lr", "selinv_lr_diag", "selinv_lr_info", "sym_info", "equil_info", "equil_scales",
            "sensitivity", "sensitivity_matrix", "misfit", "sens_info", "tangent", "gn_hessvec", "gn_diag", "gn_info", "eigs", "eigs_info", "eigs_gen_info", "interface_indices", "schur_complement", "condense", "interface_solve", "expand", "interface_info"]
 
 
@@ -44,7 +44,7 @@ class SolverOptions:
     ``5, 1, 1e-6, 1e-6, 0.5, 32, -1, 10, false`` (HierarchicalSolvers.jl:43-54)."""
 
     _fields = ("swlevel", "swsize", "atol", "rtol", "c_tol", "leafsize", "kest", "stepsize", "verbose")
-    _ext = ("keep_schur", "seed", "profile", "split_size", "hss_min", "hss_dexp", "mf", "dist_top", "symmetric")
+    _ext = ("keep_schur", "seed", "profile", "split_size", "hss_min", "hss_dexp", "mf", "dist_top", "symmetric", "equilibrate")
 
     def __init__(self, **kw):
         self.swlevel, self.swsize = 5, 1
@@ -65,6 +65,10 @@ class SolverOptions:
         # A == A.T entry for entry (real symmetric or COMPLEX symmetric; not Hermitian): dense fronts update only their lower triangle.  Checked on
         # the device by hs_numeric_begin (ValueError naming the first offending entry); sym_info(F) reports what the factorization did with it
         self.symmetric = False
+        # scale the rows and columns of A by powers of two on the device before it is factored (A_s = 2^er A 2^ec, Ruiz sweeps in the infinity
+        # norm): pivoting and the compression tolerances atol / rtol then act on A_s, the solves scale B and the result so that they answer for A
+        # itself, bit for bit as a handle of the prescaled matrix would; equil_info(F) / equil_scales(F) report what was found
+        self.equilibrate = False
         self._set(kw)
 
     def _set(self, kw):
@@ -110,6 +114,7 @@ class SolverOptions:
             raise ValueError("mf must be False, True / 'dense', 2 / 'hss' or 3 / 'block'")
         o.dist_top = 1 if self.dist_top else 0
         o.symmetric = 1 if self.symmetric else 0
+        o.equilibrate = 1 if self.equilibrate else 0
         if self.hss_dexp is not None:
             if not 0 <= int(self.hss_dexp) <= 12:
                 raise ValueError("hss_dexp must be in 0:12")
@@ -1517,6 +1522,27 @@ def sym_info(F):
     out = np.zeros(4, dtype=np.int64)
     _lib.check(_lib.lib().hs_sym_info(F._h, _p64(out)))
     return dict(option=bool(out[0]), fronts_lower=int(out[1]), fronts_general=int(out[2]))
+
+
+def equil_info(F):
+    """What ``SolverOptions.equilibrate`` did in the last factorization of ``F`` (``hs_equil_info``): ``option`` (in effect), ``sweeps`` (Ruiz sweeps
+    run, the one that moved no exponent included) and the extreme exponents ``er_min``, ``er_max``, ``ec_min``, ``ec_max`` of
+    ``A_s = 2^er A 2^ec``.  With the option off everything is 0."""
+    F, _ = _unwrap(F)
+    out = np.zeros(6, dtype=np.int64)
+    _lib.check(_lib.lib().hs_equil_info(F._h, _p64(out)))
+    return dict(option=bool(out[0]), sweeps=int(out[1]), er_min=int(out[2]), er_max=int(out[3]), ec_min=int(out[4]), ec_max=int(out[5]))
+
+
+def equil_scales(F):
+    """``(er, ec)``: the int32 exponents of the row and column scales an equilibrated factorization found, ``A_s = 2^er A 2^ec``
+    (``hs_equil_scales``); ``ValueError`` on a handle factored without ``equilibrate``."""
+    F, _ = _unwrap(F)
+    er = np.zeros(F.n, dtype=np.int32)
+    ec = np.zeros(F.n, dtype=np.int32)
+    p32 = C.POINTER(C.c_int32)
+    _lib.check(_lib.lib().hs_equil_scales(F._h, er.ctypes.data_as(p32), ec.ctypes.data_as(p32)))
+    return er, ec
 
 
 def selinv_info(F):

@@ -102,6 +102,26 @@ typedef struct hs_options {
                          path (hs_sym_info reports the counts).  hs_numeric_begin checks the claim on the device and returns HS_ERR_ARGUMENT
                          naming the first offending (row, column) before any front is touched; with nranks > 1 hs_analyze / hs_plan return
                          HS_ERR_UNSUPPORTED.  Appended after `seed`: the offsets of the older fields do not move.  Default 0. */
+  uint8_t equilibrate; /* 1: hs_numeric_begin scales the rows and columns of A by powers of two before any front is assembled: integer exponents
+                         er, ec (hs_equil_scales) with A_s = 2^er A 2^ec, found on the device by Ruiz sweeps in the infinity norm (|a| = fabs,
+                         |re| + |im| for complex; per sweep every exponent moves by -floor((floor(log2 max) + 1) / 2) of its row / column maximum,
+                         rows and columns together; the first sweep that moves nothing ends them, 16 at most; at a fixed point every maximum
+                         lies in [0.5, 2) -- except one that is not finite: a magnitude that overflows, which takes an entry near the
+                         largest Float64 (|re| + |im| of a complex entry can reach it unscaled), or an infinite entry, moves nothing: its row and
+                         column keep the exponents they have and may end outside that range; a NaN entry enters no maximum).  Scaling by 2^e is exact, so the handle is a plain handle of A_s between two exact scalings: the
+                         fronts, the pivoting decisions and the compression tolerances atol / rtol act on A_s, and hs_ldiv_*, hs_ldiv_t_*,
+                         hs_ldiv_block_*, hs_ldiv_block_t_*, hs_ldiv_ulv_* (and every driver built on them) return
+                         2^ec (F_s^-1 (2^er B)) for trans = 0 and 2^er (F_s^-T (2^ec B)) for trans = 1, 2 -- bit for bit what a handle of the
+                         prescaled matrix returns for the prescaled block.  hs_logabsdet subtracts ln 2 (sum er + sum ec).  The handle's own A
+                         (residuals, hs_opnorm, GMRES, sensitivities) stays the caller's unscaled matrix.  Entry points that read the stored
+                         factors directly (hs_mul_*, hs_factor_error_*, hs_selinv, hs_selinv_lr, hs_f32_create, hs_interface_*,
+                         hs_ldiv_sparse_* and the calls that solve on its pruned paths -- sparse blocks of hs_sens_* / hs_tangent_* / hs_gn_*,
+                         hs_gn_hessvec_* / hs_gn_diag_* with itmax = 0, hs_mod_create_sparse_* --, hs_solve_fwd_levels / hs_solve_bwd_levels)
+                         return HS_ERR_UNSUPPORTED on such a handle;
+                         hs_node_export returns blocks of A_s.  A non-zero entry whose scaled value would be subnormal or infinite makes
+                         hs_numeric_begin return HS_ERR_UNSUPPORTED naming it; with nranks > 1 hs_analyze / hs_plan return HS_ERR_UNSUPPORTED.
+                         With symmetric, the claim is checked on the caller's values; er == ec then, so A_s is symmetric bit for bit.
+                         Every hs_numeric_begin finds the exponents anew.  Appended after `symmetric`.  Default 0: nothing is launched or allocated. */
 } hs_options;
 
 /* Defaults of the reference's kw-constructor (HierarchicalSolvers.jl:43-54): 5,1,1e-6,1e-6,0.5,32,-1,10,false */
@@ -614,7 +634,8 @@ int hs_ldiv_refine_block_info(double* out8);
  * launch reads the n diagonal entries and the n permutation entries, every reduction runs in a fixed order (two calls return the same bits).
  * Compressed factorizations (swlevel > 0) whose fronts keep a dense or compact LU of D are supported and return logabsdet(F), which
  * approximates A's only as well as F approximates A.  Refused with HS_ERR_UNSUPPORTED before any device work: fronts that keep D as an HSS
- * matrix (hs_options.hss_d, mf = 2, 3), factorizations over more than one rank. */
+ * matrix (hs_options.hss_d, mf = 2, 3), factorizations over more than one rank.  With hs_options.equilibrate the factors are those of
+ * A_s = 2^er A 2^ec: logabs is returned less ln 2 (sum er + sum ec), the sums taken exactly in int64; the sign is that of A_s, which is A's. */
 int hs_logabsdet(hs_handle* F, double* logabs, double* sign2);
 /* Selected inverse of an exact factorization (swlevel = 0): diag (n elements of T, or NULL) = diag(A^-1); zval (nnz(A) elements of T in A's
  * CSC order, or NULL) = (A^-1)_ij for every stored entry (i, j) of A (trans = 0) or (A^-1)_ji (trans = 1: the selected inverse of A^T on
@@ -748,6 +769,11 @@ int hs_flow_info(const hs_handle* F, int64_t* out8);
  * fronts eliminated as before (dense ones of a tournament-pivoted or redone level or with compressed children; compressed, HSS and matrix-free
  * fronts), 0}.  Counts are of the last hs_numeric_begin .. hs_numeric_end on this rank. */
 int hs_sym_info(const hs_handle* F, int64_t* out4);
+/* What hs_options.equilibrate did in the last hs_numeric_begin: out6 = {the option in effect, sweeps run (the one that moved nothing
+ * included), min er, max er, min ec, max ec}; all 0 with the option off.  hs_equil_scales copies the exponents to host arrays of n int32
+ * each (either may be NULL); with the option off it returns HS_ERR_ARGUMENT. */
+int hs_equil_info(const hs_handle* F, int64_t* out6);
+int hs_equil_scales(const hs_handle* F, int32_t* er, int32_t* ec);
 /* make `dptr` (device memory owned by the caller, hs_exchange_info's element count) the node's Schur buffer */
 int hs_set_schur_buffer(hs_handle* F, int64_t node, void* dptr);
 int hs_pack_bnd(const hs_handle* F, int64_t node, const void* d_b, void* d_buf, void* stream);   /* buf[j] = b[bnd_j] */
@@ -917,7 +943,8 @@ int hs_node_info(const hs_handle* F, int64_t node, int64_t* ni, int64_t* nb, int
  *                         and eliminated densely and which exports no other block (what hs_logabsdet reads; with hs_node_export_piv)
  * out must hold rows*cols elements of T (2 doubles per element for complex).
  *   hs_node_export_piv: ni int64 values, 0-based row permutation p with (P*x)[i] = x[p[i]].
- * From these: D = P'LU, L = Lbi*L^{-1}*P, R = U^{-1}*Uib  (FactorNode fields, factornode.jl:7-12). */
+ * From these: D = P'LU, L = Lbi*L^{-1}*P, R = U^{-1}*Uib  (FactorNode fields, factornode.jl:7-12).
+ * With hs_options.equilibrate these (and the S kept by keep_schur) are blocks of the scaled matrix A_s = 2^er A 2^ec. */
 enum { HS_BLK_LU = 0, HS_BLK_LBI = 1, HS_BLK_UIB = 2, HS_BLK_S = 3, HS_BLK_DLU = 4 };
 int hs_node_export(const hs_handle* F, int64_t node, int which, double* out);
 int hs_node_export_piv(const hs_handle* F, int64_t node, int64_t* out);
